@@ -16,6 +16,9 @@ steps are gathered on rank 0 over RCCL (one collective after the last step, insi
 the library keeps the steps in flight on its own lanes and streams; the caller owns one workspace and one stream and sets
 no environment variable.  --pipeline streams: round 2's caller-driven form (--inflight P workspaces on P torch streams),
 kept as a probe.  Every step runs completely inside the timed region.  Prints ONE JSON line on rank 0.
+A plain run sets up, warms up, times the steps and prints the line.  --full adds what takes runs of its own: the kernels'
+own durations (one call at a time), the RLC mode beside a per-proof run, the 1 %-reject dataset and the CPU baseline.
+--dump-outputs DIR writes the accept / status vectors of the last timed step as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -156,6 +159,12 @@ def main():
                     help="nccl = RCCL over xGMI (the product path); gloo = rehearsal of the N > 1 code path on a box with one GPU "
                          "(every rank on the device H2V_BENCH_DEVICE names, accept bytes gathered through host memory)")
     ap.add_argument("--no-gather", action="store_true", help="N > 1: leave the accept gather out (rehearsals: what the collective costs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the one-step-at-a-time pass (the kernels' own durations), the RLC "
+                         "mode beside a per-proof run, the 1 %% reject dataset and the CPU baseline (the --no-* flags below leave one out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: the accept / status vectors of the last step as DIR/<name>.npy, float32 "
+                         "(N > 1: <name>_rank<r>.npy per rank)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rlc-secondary", action="store_true", help="per-proof runs: skip the extra measurement of the RLC mode")
     ap.add_argument("--cpu-sample", type=int, default=2048, help="proofs the CPU baseline verifies (2048 x ~9 ms of one core each = ~20 core-seconds, ~1.2 s on the 16 threads)")
@@ -167,6 +176,8 @@ def main():
                          "dataset, no CPU baseline): the form profiled under rocprofv3, whose per-kernel averages then cover the same "
                          "launches as the line's kernel_ms")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_rlc_secondary = args.no_alone = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -289,9 +300,9 @@ def main():
         ws.set_option(backend.Workspace.OPT_PAIRING_ENGINE, eng)
 
     class Run:
-        """what a timed run leaves behind: elapsed seconds, the last step's accept bytes, per-step kernel timings per part"""
-        def __init__(self, el, accept, timings, rlc_result, close, in_flight, all_steps_ok):
-            self.el, self.accept, self.timings, self.rlc_result, self.close, self.in_flight, self.all_steps_ok = el, accept, timings, rlc_result, close, in_flight, all_steps_ok
+        """what a timed run leaves behind: elapsed seconds, the last step's accept bytes and status bits, per-step kernel timings per part"""
+        def __init__(self, el, accept, status, timings, rlc_result, close, in_flight, all_steps_ok):
+            self.el, self.accept, self.status, self.timings, self.rlc_result, self.close, self.in_flight, self.all_steps_ok = el, accept, status, timings, rlc_result, close, in_flight, all_steps_ok
 
     def finish_timing(t0):
         torch.cuda.synchronize()
@@ -390,7 +401,8 @@ def main():
                 ws.close()
         nP = len(parts)
         back = (lambda j, p: j * nP + (nP - 1 - p)) if shared else (lambda j, p: j)     # (a shared workspace sees the parts' calls interleaved)
-        return Run(el, d_accepts[(steps - 1) % RING].cpu().numpy(), lambda j, p: wss[p].timings(back(j, p)), lambda j, p: wss[p].rlc_result(calls_back=back(j, p)), close, in_flight, ok)
+        return Run(el, d_accepts[(steps - 1) % RING].cpu().numpy(), d_statuses[(steps - 1) % RING].cpu().numpy(),
+                   lambda j, p: wss[p].timings(back(j, p)), lambda j, p: wss[p].rlc_result(calls_back=back(j, p)), close, in_flight, ok)
 
     def streams_run(mode, inflight, steps, warmup, gather, sync_every_step=False):
         """--pipeline streams (round 2): `inflight` workspaces per part on `inflight` torch streams, driven from here"""
@@ -448,7 +460,7 @@ def main():
                 for w_ in row:
                     w_.close()
         ok = all(expected_ok(d_accepts[(steps - 1 - j) % inflight].cpu().numpy()) for j in range(min(steps, inflight)))
-        return Run(el, d_accepts[(steps - 1) % inflight].cpu().numpy(),
+        return Run(el, d_accepts[(steps - 1) % inflight].cpu().numpy(), d_statuses[(steps - 1) % inflight].cpu().numpy(),
                    lambda j, p: wss[(steps - 1 - j) % inflight][p].timings(j // inflight),
                    lambda j, p: wss[(steps - 1 - j) % inflight][p].rlc_result(calls_back=j // inflight), close, inflight, ok)
 
@@ -526,6 +538,8 @@ def main():
         inflight = run.in_flight
     co_main = list(coalesce_state)           # (of the main run: the secondary RLC measurement overwrites the list)
     elapsed, accept = run.el, run.accept
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"accept": run.accept, "status": run.status}, "" if world == 1 else "_rank%d" % rank)
     k_steps = min(args.steps, 48 if not (args.shared_workspace and len(parts) > 1) else 48 // len(parts))   # (the library's event ring holds 64 calls per workspace)
     per_part = [kernel_times(run, args.mode, k_steps, p) for p in range(len(parts))]   # [(kernel_ms overlapped, latency, shape)]
     steps_ok = run.all_steps_ok
@@ -579,7 +593,7 @@ def main():
     # second dataset (untimed): 1 % of the proofs get the reference example's byte flip (examples/simple_mul.rs:87-95,
     # first scalar of the proof) - exactly those proofs must be rejected (rlc: through the per-proof fall-back)
     reject_check = None
-    if rank == 0 and not args.timed_only:
+    if rank == 0 and args.full and not args.timed_only:
         tot_c, tot_r, exact, fb_any = 0, 0, True, None
         for P in parts:
             rej = synth.with_rejects(P.pl, P.batch, P.vk.n_public_inputs, fraction=0.01, seed=77, kinds=["flip_first_scalar"])
@@ -624,6 +638,25 @@ def main():
         dist.destroy_process_group()
     if not ok_all:
         raise SystemExit("bench: the GPU's verdict vector differs from the synthetic batch's expected one")
+
+
+DUMP_LIMIT = 64 << 20   # bytes of one --dump-outputs directory
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: every array (same length) as out_dir/<name><suffix>.npy in float32.  Past DUMP_LIMIT bytes, a fixed,
+    seeded sample of the same elements of every array, their indices in sample_index<suffix>.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    idx = None
+    room = DUMP_LIMIT - 256 * (len(arrays) + 1)     # (less the .npy headers)
+    if 4 * n * len(arrays) > room:
+        idx = np.sort(np.random.default_rng(0).choice(n, room // (4 * len(arrays) + 8), replace=False))
+        np.save(os.path.join(out_dir, "sample_index%s.npy" % suffix), idx.astype(np.float64))
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), (a if idx is None else a[idx]).astype(np.float32))
 
 
 def part_model(P, PL, mode, shape):
@@ -759,7 +792,7 @@ def report(args, parts, per_part, per_part_alone, alone, elapsed, inflight, infl
         return {"kernel": kname[k], "bound": "hbm", "achieved": round(gbps, 4), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": round(gbps / HBM_PEAK_GBPS, 6), "traffic": traffic, "traffic_uncorrected_fetch_plus_write": traffic_raw, "traffic_source": pmc_src if traffic is not None else None,
                 "avg_launch_ms": round(kernel_ms[k] / n_l, 4),
-                "duration_is": "the kernel's own (one call at a time, same launch shape)" if alone else "from the timed steps (one step in flight)",
+                "duration_is": "the kernel's own (one call at a time, same launch shape)" if alone else "from the timed steps (%d in flight)" % inflight,
                 "avg_launch_ms_in_the_timed_steps": round(kernel_ms_overlapped[k] / n_l, 4), "launches_per_step": n_l,
                 # a launch of W waves occupies min(1, W / #SIMDs) of the chip: why a kernel's own duration can exceed the step it is overlapped in
                 "simd_share": round(min(1.0, sum(waves) / len(waves) / 1024.0), 3) if waves else None,

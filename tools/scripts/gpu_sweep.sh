@@ -5,7 +5,7 @@ O=gpurun_out/sweep; mkdir -p $O
 i=0
 for v in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 python bench.py --steps 120 --no-cpu-baseline --no-rlc-secondary $v > $O/b_$i.log 2>&1; rc=$?
+  timeout -k 10 300 python bench.py --full --steps 120 --no-cpu-baseline --no-rlc-secondary $v > $O/b_$i.log 2>&1; rc=$?
   python - "$v" "$rc" "$O/b_$i.log" <<'PY'
 import json,sys
 v,rc,f=sys.argv[1:4]

@@ -10,7 +10,7 @@
 #   TAG_pmc_summary.txt           mean counters per launch from separate --pmc passes of that one-step-at-a-time command
 #                                 (tools/pmc_summary.py); its first line records what was profiled, and bench.py only
 #                                 attaches `traffic` from a file whose workload / batch / mode match
-#   TAG_bench.json                the bench line of the default-length run (CPU baseline included), taken LAST, with the
+#   TAG_bench.json                the bench line of the default-length run (--full: CPU baseline included), taken LAST, with the
 #                                 PMC summary already in profiles/ on the box, so that roofline.traffic is never null
 TAG=$1; WL=$2; BATCH=$3; MODE=$4; shift 4
 ARGS="--workload $WL --batch $BATCH --mode $MODE --no-rlc-secondary $*"
@@ -51,7 +51,7 @@ done
 { echo "# workload=$WL batch=$((BATCH * CO)) mode=$MODE pmc_steps=3 tag=$TAG calls_per_launch=$CO (rocprofv3 --pmc, separate passes; bench.py $ARGS_L --steps 2 --warmup 1 --timed-only --no-alone --pipeline streams --inflight 1 --hint $INF $FORCE)"; python tools/pmc_summary.py $O/pmc_${TAG}_*; } > $O/${TAG}_pmc_summary.txt
 cp $O/${TAG}_pmc_summary.txt profiles/${TAG}_pmc_summary.txt    # (on the box: the final line below reads it)
 # 5. the line
-timeout -k 10 400 python bench.py $ARGS $FORCE --steps $((240 * CO)) > $O/b_$TAG.log 2>&1 || fail 5 $? $O/b_$TAG.log
+timeout -k 10 400 python bench.py $ARGS $FORCE --full --steps $((240 * CO)) > $O/b_$TAG.log 2>&1 || fail 5 $? $O/b_$TAG.log
 grep "^{" $O/b_$TAG.log | tail -1 > $O/${TAG}_bench.json
 grep -E "INSTS_VALU|FETCH|WRITE_SIZE" $O/${TAG}_pmc_summary.txt
 head -8 $O/${TAG}_kernel_stats.csv | cut -d, -f1-5
