@@ -57,11 +57,9 @@ typedef struct {
     const uint8_t *committed;
 } h2v_batch;
 
-/* optional per-stage device timings (milliseconds, HIP events on the streams the kernels run on).  A large batch is
- * cut into `launches` chunks that run as overlapping pipelines when H2V_PIPES > 1 (default 1): each *_ms is
- * the SUM of that kernel's launch durations over the chunks, total_ms the span from the first launch to the last end.
- * g1_decompress_ms is the longer of the decompression kernel's two concurrent launches (square roots + window tables
- * on one stream, subgroup tests on another).  msm_lanes_per_term is the shape the MSM launcher chose for the call:
+/* optional per-stage device timings (milliseconds, HIP events on the streams the kernels run on).  `launches` is 1 for an
+ * ordinary workspace and the number of chunks for a laned one: each *_ms is the SUM of that kernel's launch durations over
+ * the chunks, total_ms the span from the first launch to the last end.  msm_lanes_per_term is the shape the MSM launcher chose for the call:
  * 2 = one lane per GLV half, 1 = both halves on one lane (shared doublings), 3 = ladders for the per-proof terms beside a
  * fixed-base launch for the VK bases, 8 = a quad of lanes per GLV half (small launches of few terms: the four lanes share
  * the multiplications of every doubling and addition), 18 / 20 = two / four terms per lane (H2V_MSM_TPL). */
@@ -174,15 +172,14 @@ int h2v_workspace_join(h2v_workspace *ws, void *stream);
  * launcher's own choice (DESIGN.md sections 4.1, 4.2, 6). */
 #define H2V_OPT_MSM_TERMS_PER_LANE 1u /* per-proof MSM: 1 .. 4 terms per lane on one accumulator (shared doublings) */
 #define H2V_OPT_PAIRING_ENGINE 2u     /* lanes per proof of the pairing kernel: 6 (ten proofs per wave), 12 (five), 16 (narrow: four), 32, 64 (wide), 1 (the one-lane cross-check kernel) */
-#define H2V_OPT_STREAMS 3u            /* -1 auto, 0: three library streams per call, 1: everything on the caller's stream, 2: + one side stream */
+#define H2V_OPT_STREAMS 3u            /* -1 auto, 0: two library streams per call, 1: everything on the caller's stream, 2: + one side stream */
 /* (round 4) every remaining shape dimension, formerly H2V_* environment variables read once per process: */
 #define H2V_OPT_MSM_LANES_PER_TERM 4u /* ladder launches: 1 (both GLV halves on one lane), 2 (one lane per half), 8 (a quad of lanes per half) */
 #define H2V_OPT_MSM_BLOCK_SIZE 5u     /* threads per block of the MSM launches: 64 .. 512 in steps of 64 */
 #define H2V_OPT_MSM_FIXED_SPLIT 6u    /* VK-base terms through the all-window tables beside the ladders: 1 .. 4 bases per lane; -1: never split */
 #define H2V_OPT_COMBINER_SCHEDULE 7u  /* transcript + combiner kernel: 1 the plan's narrow bundle schedule, 2 the wide one */
 #define H2V_OPT_COMBINER_PROOFS_PER_BLOCK 8u /* proofs per one-wave block of that kernel (a power of two <= what fits LDS) */
-#define H2V_OPT_DECOMPRESS_FORM 9u    /* 0: one launch that takes 64-point units from a queue; 1: square roots and subgroup tests as two launches; 2: one launch of paired 128-thread blocks */
-#define H2V_OPT_PIPES 10u             /* an ordinary workspace cuts a call into 2 .. 4 sub-pipelines on streams of their own (0 / 1: one) */
+/* ids 9 and 10 are retired (forms of the decompression launch, sub-pipelines): not reused, refused with H2V_E_ARG */
 #define H2V_OPT_RLC_GROUP_STAGE 11u   /* RLC fall-back: -1 skips the group checks (straight to the per-proof kernels) */
 #define H2V_OPT_RLC_WINDOW_BITS 12u   /* bucket MSM: window width */
 #define H2V_OPT_RLC_CHAIN 13u         /* bucket MSM: most entries one lane sums */

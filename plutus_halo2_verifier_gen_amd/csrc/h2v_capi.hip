@@ -127,31 +127,24 @@ struct h2v_workspace {
     uint32_t *accl = nullptr, *accr = nullptr, *fold_pts = nullptr, *fold_scal = nullptr, *el2 = nullptr, *er2 = nullptr;
     uint32_t *pt_tab = nullptr;  // MSM window tables of every per-proof point, written by the decompression kernel
     uint32_t *er_fix = nullptr;  // sum of the VK-base terms when the MSM is split into a ladder and a fixed-base launch
-    uint32_t *dec_ctr = nullptr; // work-queue counters of the decompression launch (one per pipeline chunk)
+    uint32_t *dec_ctr = nullptr; // work-queue counter of the decompression launch
     uint8_t *valid = nullptr, *valid_sub = nullptr, *accept = nullptr;
     // Host-buffer entry points: the batch is packed into ONE pinned host block (offsets | instances | committed | proofs),
     // uploaded with one asynchronous copy on the workspace's own stream `hs`, verified there, and the accept bytes come
     // back into pinned memory the same way: h2v_verify_batch_submit returns once everything is enqueued, _wait collects.
-    // in_* point into the device block.
-    uint8_t *in_block = nullptr, *h_block = nullptr, *h_accept = nullptr;
-    size_t in_block_cap = 0, h_accept_cap = 0;
-    uint8_t *in_proofs = nullptr, *in_inst = nullptr, *in_ci = nullptr;
-    uint64_t *in_off = nullptr;
+    // An ordinary workspace stages its one batch in hslot[0] (below); accept[] comes back from `accept`.
     hipStream_t hs = nullptr;
-    hipEvent_t ev_host = nullptr;
-    bool pending = false, pending_rlc = false;
-    uint64_t pending_n = 0;
-    // A batch is cut into up to MAXP chunks that run as independent pipelines on their own stream pairs, so that one
-    // chunk's decompression / transcript kernels (few waves) overlap another chunk's MSM / pairing kernels.
-    static constexpr int MAXP = 4;
-    hipStream_t pmain[MAXP] = {}, pside[MAXP] = {}, psub[MAXP] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[MAXP] = {}, ev_sub[MAXP] = {}, ev_fix[MAXP] = {}, ev_done[MAXP] = {};
-    // ring of per-call, per-chunk event sets: [0]/[1] around the transcript+combiner kernel, [2]/[3] around the
-    // decompression kernel's square-root half (side stream), [4]/[5] around the MSM, [5]/[6] around the pairing kernel,
-    // [7]/[8] around the decompression kernel's subgroup half (third stream)
-    static constexpr int RING = 64, NEV = 12;   // (+ [9]/[10] around the fixed-base MSM launch, [11] the end of the ladder launch beside it)
-    hipEvent_t ring[RING][MAXP][NEV] = {};
-    uint8_t ring_pipes[RING] = {}, ring_split[RING] = {}, ring_lpt[RING] = {}, ring_pair[RING] = {}, ring_var[RING] = {};
+    bool pending = false;
+    // the streams of the pipeline (ws_streams): the transcript + combiner kernel and everything after it on pmain, the
+    // decompression beside it on pside
+    hipStream_t pmain = nullptr, pside = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_hold = nullptr, ev_fix = nullptr, ev_done = nullptr;
+    // ring of per-call event sets: [0]/[1] around the transcript+combiner kernel, [2]/[3] around the decompression kernel
+    // (side stream), [4]/[5] around the MSM, [5]/[6] around the pairing kernel, [7]/[8] around the fixed-base MSM launch of a
+    // split MSM, [9] the end of the ladder launch beside it; [10]/[11] mark the MSM's hold (run_pipeline) and are not read
+    static constexpr int RING = 64, NEV = 12;
+    hipEvent_t ring[RING][NEV] = {};
+    uint8_t ring_lpt[RING] = {}, ring_pair[RING] = {}, ring_var[RING] = {};
     uint64_t calls = 0;
     struct RlcWs *rlc = nullptr;   // buffers of the RLC batch mode, created by its first call
     std::vector<struct RlcWs *> rlc_parked;   // the same for OTHER plans this workspace has served in that mode (rlc_ensure swaps; never freed before the workspace)
@@ -171,7 +164,7 @@ struct h2v_workspace {
     uint64_t next_lane = 0;                 // round-robin position (persists across calls: consecutive calls interleave)
     H2vDevPlan lane_plan{};                 // the creating plan's shape: lanes are created when first used
     // host-buffer batches in flight on a laned workspace (h2v_verify_batch_submit / _wait): a ring of staging slots, each
-    // with its own pinned block, device block and accept buffers; uploads on `hs`, downloads on `hs_down`
+    // with its own pinned block, device block and accept buffers; uploads on `hs`, downloads on `hs_down` (stage_batch)
     struct HostSlot {
         uint8_t *in_block = nullptr, *h_block = nullptr, *h_accept = nullptr, *d_accept = nullptr;
         size_t in_cap = 0, acc_cap = 0;
@@ -516,27 +509,18 @@ static void ws_release(h2v_workspace *w) {
     for (struct RlcWs *r : w->rlc_parked) rlc_release(r);
     w->rlc_parked.clear();
     if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
-    void *ptrs[] = {w->rlc_stats, w->rlc_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->dec_ctr, w->accept, w->in_block, w->msm_tab,
+    void *ptrs[] = {w->rlc_stats, w->rlc_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->dec_ctr, w->accept, w->msm_tab,
                     w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab};
     for (void *q : ptrs) if (q) (void)hipFree(q);
-    if (w->h_block) (void)hipHostFree(w->h_block);
-    if (w->h_accept) (void)hipHostFree(w->h_accept);
     if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
     if (w->copy_streams_owned) {
         if (w->hs) (void)hipStreamDestroy(w->hs);
         if (w->hs_down) (void)hipStreamDestroy(w->hs_down);
         w->hs = w->hs_down = nullptr; w->copy_streams_owned = false;
     }
-    if (w->ev_host) (void)hipEventDestroy(w->ev_host);
-    for (hipStream_t q : w->pmain) if (q) (void)hipStreamSynchronize(q);
-    for (hipStream_t q : w->pside) if (q) (void)hipStreamSynchronize(q);
-    for (hipStream_t q : w->psub) if (q) (void)hipStreamSynchronize(q);
-    for (hipEvent_t e : w->ev_sub) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : w->ev_fix) if (e) (void)hipEventDestroy(e);
-    if (w->ev_fork) (void)hipEventDestroy(w->ev_fork);
-    for (hipEvent_t e : w->ev_join) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : w->ev_done) if (e) (void)hipEventDestroy(e);
-    for (auto &call : w->ring) for (auto &set : call) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
+    for (hipStream_t q : {w->pmain, w->pside}) if (q) (void)hipStreamSynchronize(q);
+    for (hipEvent_t e : {w->ev_fork, w->ev_join, w->ev_hold, w->ev_fix, w->ev_done}) if (e) (void)hipEventDestroy(e);
+    for (auto &set : w->ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
 }
 static uint32_t vm_lds_slots(const H2vDevPlan &d);
 static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bool with_trace, h2v_workspace **out) {
@@ -557,7 +541,7 @@ static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bo
     WSALLOC(pts, (size_t)max_batch * slots * 96)
     WSALLOC(valid, (size_t)max_batch * slots)
     WSALLOC(valid_sub, (size_t)max_batch * slots)
-    WSALLOC(dec_ctr, 64)
+    WSALLOC(dec_ctr, 4)
     if (d.fix_tab) { WSALLOC(er_fix, (size_t)max_batch * 36 * 4) }
     WSALLOC(er, (size_t)max_batch * 144)
     WSALLOC(pt_tab, (size_t)max_batch * slots * 448 * 4)             // per (proof, slot): [1..8]P and [1..8]phi(P), affine, 2 x 14 x 28-bit limbs
@@ -576,11 +560,10 @@ static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bo
 #undef WSALLOC
     // Streams are created on first use (ws_streams): the runtime maps streams onto a few hardware queues round robin, and
     // streams that are never used would only make the ones in use collide (several batches in flight: bench.py --inflight).
-    bool ok = hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming) == hipSuccess;
-    for (int k = 0; k < h2v_workspace::MAXP && ok; k++)
-        ok = hipEventCreateWithFlags(&w->ev_sub[k], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&w->ev_fix[k], hipEventDisableTiming) == hipSuccess &&
-             hipEventCreateWithFlags(&w->ev_join[k], hipEventDisableTiming) == hipSuccess && hipEventCreateWithFlags(&w->ev_done[k], hipEventDisableTiming) == hipSuccess;
-    for (auto &call : w->ring) for (auto &set : call) for (hipEvent_t &e : set)
+    bool ok = true;
+    for (hipEvent_t *e : {&w->ev_fork, &w->ev_join, &w->ev_hold, &w->ev_fix, &w->ev_done})
+        if (ok) ok = hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    for (auto &set : w->ring) for (hipEvent_t &e : set)
         if (ok) ok = hipEventCreate(&e) == hipSuccess;
     if (!ok) { ws_release(w); delete w; return fail(H2V_E_DEVICE, "stream/event creation failed"); }
     *out = w;
@@ -623,7 +606,7 @@ static int ensure_lane(h2v_workspace *w, uint32_t l) {
     int rc = ws_create_for(w->lane_plan, w->device, w->chunk, false, &lw);
     if (rc) return rc;
     lw->one_stream_mode = 2;            // (set per call: laned_depth)
-    lw->pside[0] = side_st;             // (the decompression's stream in the two-stream form: the other half of the lane's pair)
+    lw->pside = side_st;                // (the decompression's stream in the two-stream form: the other half of the lane's pair)
     lw->in_flight_hint = w->in_flight_hint > w->n_lanes ? w->in_flight_hint : w->n_lanes;
     memcpy(lw->opt, w->opt, sizeof lw->opt);
     w->lane[l] = lw;
@@ -710,14 +693,12 @@ static int option_check(uint32_t option, int32_t value) {
         if (value != 0 && value != 1 && value != 6 && value != 12 && value != 16 && value != 32 && value != 64)
             return bad("pairing engine: 0 (auto), 6, 12, 16, 32, 64 lanes per proof, or 1 (the one-lane cross-check kernel)");
         break;
-    case H2V_OPT_STREAMS: if (value < -1 || value > 2) return bad("streams: -1 (auto), 0 (three), 1 (the caller's), 2 (the caller's + one for the decompression)"); break;
+    case H2V_OPT_STREAMS: if (value < -1 || value > 2) return bad("streams: -1 (auto), 0 (two of the library's), 1 (the caller's), 2 (the caller's + one for the decompression)"); break;
     case H2V_OPT_MSM_LANES_PER_TERM: if (value != 0 && value != 1 && value != 2 && value != 8) return bad("MSM lanes per term: 0 (auto), 1, 2, 8"); break;
     case H2V_OPT_MSM_BLOCK_SIZE: if (value < 0 || value > 512 || value % 64) return bad("MSM block size: 0 (auto), 64 .. 512 in steps of 64"); break;
     case H2V_OPT_MSM_FIXED_SPLIT: if (value < -1 || value > 4) return bad("fixed-base split: 0 (auto), 1 .. 4 bases per lane, -1 (never)"); break;
     case H2V_OPT_COMBINER_SCHEDULE: if (value < 0 || value > 2) return bad("combiner schedule: 0 (auto), 1 (narrow), 2 (wide)"); break;
     case H2V_OPT_COMBINER_PROOFS_PER_BLOCK: if (value < 0 || value > 64 || (value & (value - 1))) return bad("combiner proofs per block: 0 (auto) or a power of two <= 64"); break;
-    case H2V_OPT_DECOMPRESS_FORM: if (value < 0 || value > 2) return bad("decompression: 0 (auto: one queue launch), 1 (two launches), 2 (one launch of paired blocks)"); break;
-    case H2V_OPT_PIPES: if (value < 0 || value > h2v_workspace::MAXP) return bad("pipes: 0 / 1 (one pipeline) .. 4"); break;
     case H2V_OPT_RLC_GROUP_STAGE: if (value < -1 || value > 0) return bad("RLC group stage: 0 (auto), -1 (off)"); break;
     case H2V_OPT_RLC_WINDOW_BITS: if (value != 0 && (value < 3 || value > (int32_t)PIP_MAX_C)) return bad("RLC window bits: 0 (auto), 3 .. the bucket MSM's maximum"); break;
     case H2V_OPT_RLC_CHAIN: if (value != 0 && (value < 2 || value > 1024)) return bad("RLC entries per lane: 0 (auto), 2 .. 1024"); break;
@@ -741,6 +722,7 @@ extern "C" int h2v_workspace_set_option(h2v_workspace *ws, uint32_t option, int3
 }
 extern "C" int h2v_workspace_get_option(const h2v_workspace *ws, uint32_t option, int32_t *value) {
     if (!ws || !value || option == 0 || option >= H2V_OPT_COUNT) return fail(H2V_E_ARG, "bad argument");
+    if (option == 9 || option == 10) return fail(H2V_E_ARG, "unknown option");   // (retired ids: include/h2v.h)
     *value = option == H2V_OPT_STREAMS ? ws->one_stream_mode : ws->opt[option];
     return H2V_OK;
 }
@@ -775,6 +757,18 @@ static int null_stream_check(const h2v_workspace *ws, const void *stream) {
         return fail(H2V_E_ARG, "a workspace with deferred joins needs a stream of its own: the legacy NULL stream (PyTorch's default stream) is ordered with "
                                "every library stream and would serialise the lanes - pass a non-default stream, or h2v_workspace_defer_joins(ws, 0)");
     return H2V_OK;
+}
+// An error part of the way through enqueueing a call: work enqueued before it (earlier chunks, the upload from a pinned block)
+// may still read the caller's or the workspace's buffers, so nothing may be reused before every stream the workspace may have
+// enqueued on has drained.  Returns rc with the error's message.
+static int drain_after_error(h2v_workspace *w, int rc) {
+    const std::string e = g_err;
+    for (hipStream_t q : {w->hs, w->hs_down, w->pmain, w->pside}) if (q) (void)hipStreamSynchronize(q);
+    for (uint32_t l = 0; l < w->n_lanes; l++) {
+        if (w->lane_st[l]) (void)hipStreamSynchronize(w->lane_st[l]);
+        w->lane_busy[l] = false;
+    }
+    return fail(rc, e);
 }
 // every lane that has work enqueued since the last join: `st` waits for its last chunk
 static int lanes_join(h2v_workspace *w, hipStream_t st, bool host_block = false) {
@@ -937,11 +931,10 @@ extern "C" int h2v_shutdown(int device) {
     }
     return rc;
 }
-// the main / side / third stream of pipeline chunk k, created when first asked for
-static int ws_streams(h2v_workspace *w, int k, bool need_main, bool need_side, bool need_sub) {
-    if (need_main && !w->pmain[k]) HIPCHK(make_stream(&w->pmain[k]));
-    if (need_side && !w->pside[k]) HIPCHK(make_stream(&w->pside[k]));
-    if (need_sub && !w->psub[k]) HIPCHK(make_stream(&w->psub[k]));
+// the main / side stream of the pipeline, created when first asked for
+static int ws_streams(h2v_workspace *w, bool need_main, bool need_side) {
+    if (need_main && !w->pmain) HIPCHK(make_stream(&w->pmain));
+    if (need_side && !w->pside) HIPCHK(make_stream(&w->pside));
     return H2V_OK;
 }
 
@@ -1231,8 +1224,8 @@ static uint32_t launch_pairing(const H2vDevPlan &d, uint32_t n, const uint32_t *
 }
 
 // ---------------------------------------------------------------------------------------------- pipeline
-// Enqueues the four kernels.  Without timings the transcript/combiner kernel (few, long waves) and the
-// decompression kernel (many short ones) run concurrently on two streams and join before the MSM.
+// Enqueues the four kernels.  The decompression kernel (many short waves) runs on a side stream beside the
+// transcript+combiner kernel (few long waves), and the two join before the MSM.
 extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_timings *tm);
 static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst,
                         const uint8_t *ci, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
@@ -1240,162 +1233,105 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     opts_from(w);
     struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
     const uint32_t slots = H2V_SLOTS(d);
-    const uint32_t vm_blocks = (n + 63) / 64;
-    const uint32_t dec_blocks = (n * slots + 63) / 64;
-    (void)vm_blocks; (void)dec_blocks;
     uint32_t *trace = want_trace ? w->trace : nullptr;
-    uint32_t *status = w->status;
-    static const bool dbg = getenv("H2V_DEBUG_SYNC") != nullptr;  // serialise + sync after every kernel, say which one ran
-    if (dbg) {
-#define DBG_STAGE(name, launch)                                                                 \
-        fprintf(stderr, "[h2v] launching %s (n=%u)\n", name, n); fflush(stderr);               \
-        launch;                                                                                 \
-        HIPCHK(hipGetLastError());                                                              \
-        HIPCHK(hipDeviceSynchronize());                                                         \
-        fprintf(stderr, "[h2v] %s done\n", name); fflush(stderr);
-        DBG_STAGE("k_g1_decompress", hipLaunchKernelGGL(k_g1_decompress, dim3(dec_blocks), dim3(128), 0, st, d, n, proofs, off, ci, inst, w->pts, w->valid, w->pt_tab, 0u, (uint8_t *)nullptr))
-        DBG_STAGE("k_transcript_combiner", { int rcv = launch_vm(d, n, w->stride, proofs, off, inst, ci, w->regs, w->scalars, status, trace, st); if (rcv) return rcv; })
-        DBG_STAGE("k_g1_msm", launch_msm(d, n, w->scalars, w->pts, w->pt_tab, w->er, w->accl, w->accr, st))
-        if (d.ivc) {
-            const IvcBufs ib = {w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2};
-            DBG_STAGE("ivc fold", launch_ivc_fold(d, n, w->pts, w->er, ib, w->msm_tab, st))
-        }
-        DBG_STAGE("k_pairing_check", launch_pairing(d, n, w->pts, w->valid, nullptr, d.ivc ? w->er2 : w->er, d.ivc ? w->el2 : nullptr, status, accept, nullptr, st))
-#undef DBG_STAGE
-        if (status_out) HIPCHK(hipMemcpyAsync(status_out, status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    // H2V_DEBUG_SYNC: after each stage, say which kernel was launched and wait for the whole device, so that a fault is
+    // reported at the stage that caused it
+    static const bool dbg = getenv("H2V_DEBUG_SYNC") != nullptr;
+    auto stage_done = [&](const char *kernel) -> int {
+        if (!dbg) return H2V_OK;
+        fprintf(stderr, "[h2v] launching %s (n=%u)\n", kernel, n); fflush(stderr);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
         return H2V_OK;
-    }
-    // number of chunks (H2V_OPT_PIPES).  Default 1: measured on MI355X, 2/3/4 concurrent pipelines of a 4096-proof batch
-    // took 14.2 / 20.7 / 29.1 ms against 13.5 ms for one (kernels with different private-segment sizes alternating on
-    // several queues cost more than the idle SIMDs they fill), so the split is kept as an experiment knob only.
-    const int dec_form = w->opt[H2V_OPT_DECOMPRESS_FORM];     // 0 / 1: two roles (queue launch / two launches); 2: one launch of paired blocks
-    const bool split_dec = dec_form != 2;
-    const int env_pipes = w->opt[H2V_OPT_PIPES];
-    int pipes = env_pipes > 0 ? env_pipes : 1;
-    if (pipes > h2v_workspace::MAXP) pipes = h2v_workspace::MAXP;
-    if (want_trace || (uint32_t)pipes > n) pipes = 1;
+    };
+    // A caller that keeps >= 6 batches in flight (h2v_workspace_hint_in_flight) gets the whole pipeline on ITS stream: the
+    // other batches fill the chip, and one stream per batch keeps many batches within the 16 hardware queues (three
+    // streams per batch collide from the sixth batch on).  Measured, 40 steps of simple_mul x 4096: three streams 5 / 8 / 11
+    // in flight 4.46 / 4.66 / 4.75 ms per step, one stream 4.80 / 4.39 / 4.50.  H2V_OPT_STREAMS forces the choice.
+    const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode == 1 : w->in_flight_hint >= 6;
+    // one_stream_mode 2 (lanes): the pipeline on the stream it is given, only the decompression beside it on a side stream
+    const bool two_stream = w->one_stream_mode == 2;
+    if (!one_stream)
+        if (int rcs = ws_streams(w, !two_stream, true)) return rcs;
+    hipStream_t pm = (one_stream || two_stream) ? st : w->pmain, ps = one_stream ? st : w->pside;
     const int slot = (int)(w->calls % h2v_workspace::RING);
-    w->ring_pipes[slot] = (uint8_t)pipes;
-    w->ring_split[slot] = split_dec ? 1 : 0;
+    hipEvent_t *ev = w->ring[slot];
     w->calls++;
     HIPCHK(hipEventRecord(w->ev_fork, st));
-    for (int k = 0; k < pipes; k++) {
-        const uint32_t lo = (uint32_t)((uint64_t)n * k / pipes), hi = (uint32_t)((uint64_t)n * (k + 1) / pipes), m = hi - lo;
-        hipEvent_t *ev = w->ring[slot][k];
-        const bool dec_queue_on = dec_form == 0;
-        // A caller that keeps >= 6 batches in flight (h2v_workspace_hint_in_flight) gets the whole pipeline on ITS stream: the
-        // other batches fill the chip, and one stream per batch keeps many batches within the 16 hardware queues (three
-        // streams per batch collide from the sixth batch on).  Measured, 40 steps of simple_mul x 4096: three streams 5 / 8 / 11
-        // in flight 4.46 / 4.66 / 4.75 ms per step, one stream 4.80 / 4.39 / 4.50.  H2V_OPT_STREAMS forces the choice.
-        const bool one_stream = pipes == 1 && (w->one_stream_mode >= 0 ? w->one_stream_mode == 1 : w->in_flight_hint >= 6);
-        // one_stream_mode 2 (lanes): the pipeline on the stream it is given, only the decompression beside it on a side stream
-        const bool two_stream = pipes == 1 && w->one_stream_mode == 2;
-        if (!one_stream || two_stream)
-            if (int rcs = ws_streams(w, k, !two_stream, true, !two_stream && split_dec && !dec_queue_on)) return rcs;
-        hipStream_t pm = (one_stream || two_stream) ? st : w->pmain[k], ps = (one_stream && !two_stream) ? st : w->pside[k];
-        const uint64_t *off_k = off + lo;
-        const uint8_t *inst_k = inst ? inst + (size_t)lo * d.n_pi * 32 : nullptr;
-        const uint8_t *ci_k = ci ? ci + (size_t)lo * 48 : nullptr;
-        uint32_t *regs_k = w->regs + lo, *scal_k = w->scalars + (size_t)lo * d.n_terms * 8, *pts_k = w->pts + (size_t)lo * slots * 24;
-        uint32_t *er_k = w->er + (size_t)lo * 36, *status_k = status + lo;
-        uint8_t *valid_k = w->valid + (size_t)lo * slots, *accept_k = accept + lo;
-        HIPCHK(hipStreamWaitEvent(pm, w->ev_fork, 0));
-        HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
-        // decompression (many short waves) runs beside the transcript+combiner kernel (few long waves)
-        uint32_t *pt_tab_k = w->pt_tab + (size_t)lo * slots * 448;
-        uint8_t *vsub_k = split_dec ? w->valid_sub + (size_t)lo * slots : nullptr;
-        const uint32_t dec_grid = (m * slots + 63) / 64;
-        int rcv = 0;
-        auto vm = [&]() {
-            HIPCHK(hipEventRecord(ev[0], pm));
-            rcv = launch_vm(d, m, w->stride, proofs, off_k, inst_k, ci_k, regs_k, scal_k, status_k, trace, pm);
-            HIPCHK(hipEventRecord(ev[1], pm));
-            return 0;
-        };
-        // Decompression: by default ONE launch whose waves (at most one per SIMD) take 64-point units from a queue - all
-        // subgroup tests, then all square roots (k_g1_decompress_queue); H2V_OPT_DECOMPRESS_FORM = 1: the two halves as two
-        // launches of 64-thread blocks on two streams; = 2: one launch of 128-thread blocks, a root wave and a subgroup
-        // wave per block.
-        const bool dec_queue = dec_form == 0;
-        auto sqrt_half = [&]() {
-            HIPCHK(hipEventRecord(ev[2], ps));
-            if (split_dec && dec_queue) {
-                uint32_t *ctr = w->dec_ctr + k;
-                HIPCHK(hipMemsetAsync(ctr, 0, 4, ps));
-                const uint32_t units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
-                uint32_t blocks = (units + 3) / 4;
-                if (blocks > max_blocks) blocks = max_blocks;
-                hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, ps, d, m, proofs, off_k, ci_k, inst_k, pts_k, valid_k, pt_tab_k, vsub_k, ctr, dec_grid);
-            } else if (split_dec) hipLaunchKernelGGL(k_g1_decompress, dim3(dec_grid), dim3(64), 0, ps, d, m, proofs, off_k, ci_k, inst_k, pts_k, valid_k, pt_tab_k, 1u, (uint8_t *)nullptr);
-            else hipLaunchKernelGGL(k_g1_decompress, dim3(dec_grid), dim3(128), 0, ps, d, m, proofs, off_k, ci_k, inst_k, pts_k, valid_k, pt_tab_k, 0u, (uint8_t *)nullptr);
-            HIPCHK(hipEventRecord(ev[3], ps));
-            HIPCHK(hipEventRecord(w->ev_join[k], ps));
-            return 0;
-        };
-        auto sub_half = [&]() {
-            // the subgroup tests as a launch of their own (only without the queue)
-            if (!split_dec) return 0;
-            hipStream_t pb = (dec_queue || one_stream || two_stream) ? ps : w->psub[k];   // (with the queue there is no third launch: only the events are recorded)
-            HIPCHK(hipStreamWaitEvent(pb, w->ev_fork, 0));
-            HIPCHK(hipEventRecord(ev[7], pb));
-            if (!dec_queue) hipLaunchKernelGGL(k_g1_decompress, dim3(dec_grid), dim3(64), 0, pb, d, m, proofs, off_k, ci_k, inst_k, pts_k, valid_k, (uint32_t *)nullptr, 2u, vsub_k);
-            HIPCHK(hipEventRecord(ev[8], pb));
-            HIPCHK(hipEventRecord(w->ev_sub[k], pb));
-            return 0;
-        };
-        const int rco = sqrt_half() || sub_half() || vm();
-        if (rco) return rco;
-        if (rcv) return rcv;
-        HIPCHK(hipStreamWaitEvent(pm, w->ev_join[k], 0));
-        // The MSM also waits for the subgroup launch although it does not read its result: a merged-halves MSM relies on
-        // finding every SIMD empty (one wave each: 1.9 ms; a SIMD shared with a leftover wave: 2.2 ms for the launch)
-        if (split_dec) HIPCHK(hipStreamWaitEvent(pm, w->ev_sub[k], 0));
-        HIPCHK(hipEventRecord(ev[4], pm));
-        uint32_t *tab_k = d.ivc ? w->msm_tab + (size_t)lo * 4 * 2 * 8 * 28 : nullptr;   // fold MSMs only
-        const IvcBufs ib = {d.ivc ? w->accl + (size_t)lo * 36 : nullptr, d.ivc ? w->accr + (size_t)lo * 36 : nullptr,
-                            d.ivc ? w->fold_pts + (size_t)lo * 96 : nullptr, d.ivc ? w->fold_scal + (size_t)lo * 32 : nullptr,
-                            d.ivc ? w->el2 + (size_t)lo * 36 : nullptr, d.ivc ? w->er2 + (size_t)lo * 36 : nullptr};
-        const MsmShape single = msm_ladder_shape(d.ivc ? d.n_terms : d.n_main_terms, m, 0.0, true);
-        const MsmSplit split = w->er_fix ? msm_split_shape(d, m, single, w->in_flight_hint) : MsmSplit{false, {}, {}, 0};
-        if (split.on) {
-            // per-proof terms as ladders on the main stream; the VK-base terms beside them on the side stream (free since
-            // the square roots finished), which first waits for the combiner's scalars; a one-lane-per-proof kernel adds
-            // the two sums
-            uint32_t *erf_k = w->er_fix + (size_t)lo * 36;
-            H2vMsmArgs mv = {d.terms, 0, d.n_var, d.n_terms, 0, slots, {d.n_var, d.n_var, d.n_var}, {er_k, nullptr, nullptr}, pt_tab_k, d.vk_tab, nullptr, 0, 0};
-            H2vMsmArgs mf = {d.terms, d.n_var, d.n_fix, d.n_terms, d.n_var, slots, {d.n_fix, d.n_fix, d.n_fix}, {erf_k, nullptr, nullptr}, pt_tab_k, d.vk_tab,
-                             d.fix_tab, split.k, (d.n_fix + split.k - 1) / split.k};
-            HIPCHK(hipStreamWaitEvent(ps, ev[1], 0));
-            const uint32_t pbf = split.fix.bs / mf.n_fixl;
-            HIPCHK(hipEventRecord(ev[9], ps));
-            hipLaunchKernelGGL(k_g1_msm_fixed, dim3((m + pbf - 1) / pbf), dim3(split.fix.bs), (size_t)split.fix.bs * 172, ps, d, mf, m, pbf, scal_k, pts_k, (uint32_t *)nullptr);
-            HIPCHK(hipEventRecord(ev[10], ps));
-            HIPCHK(hipEventRecord(w->ev_fix[k], ps));
-            if (ps == pm) HIPCHK(hipEventRecord(ev[4], pm));   // (one stream: the ladder launch starts behind the fixed-base one)
-            uint32_t var_code;
-            if (msm_terms_per_lane(w->in_flight_hint) > 1) var_code = launch_msm_range(d, mv, m, scal_k, pts_k, nullptr, pm, w->in_flight_hint);   // (several terms per lane)
-            else var_code = launch_msm_ladders(d, mv, m, split.var, scal_k, pts_k, nullptr, pm);
-            HIPCHK(hipEventRecord(ev[11], pm));
-            w->ring_var[slot] = (uint8_t)var_code;
-            HIPCHK(hipStreamWaitEvent(pm, w->ev_fix[k], 0));
-            hipLaunchKernelGGL(k_g1_sum_pairs, dim3((m + 63) / 64), dim3(64), 0, pm, m, er_k, erf_k);
-            w->ring_lpt[slot] = 3;
-        } else {
-            w->ring_lpt[slot] = (uint8_t)launch_msm(d, m, scal_k, pts_k, pt_tab_k, er_k, ib.accl, ib.accr, pm, w->in_flight_hint);
-        }
-        const uint32_t *er_in = er_k, *el_in = nullptr;
-        if (d.ivc) {   // (timed with the MSM: the challenge hash and one more pass of the same kernel)
-            launch_ivc_fold(d, m, pts_k, er_k, ib, tab_k, pm);
-            er_in = ib.er2; el_in = ib.el2;
-        }
-        HIPCHK(hipEventRecord(ev[5], pm));
-        w->ring_pair[slot] = (uint8_t)launch_pairing(d, m, pts_k, valid_k, vsub_k, er_in, el_in, status_k, accept_k, nullptr, pm, w->in_flight_hint);
-        HIPCHK(hipEventRecord(ev[6], pm));
-        HIPCHK(hipEventRecord(w->ev_done[k], pm));
-        HIPCHK(hipStreamWaitEvent(st, w->ev_done[k], 0));
+    HIPCHK(hipStreamWaitEvent(pm, w->ev_fork, 0));
+    HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
+    // Decompression: ONE launch whose waves (at most one per SIMD) take 64-point units from a queue - all subgroup tests,
+    // then all square roots (k_g1_decompress_queue)
+    const uint32_t dec_grid = (n * slots + 63) / 64;
+    HIPCHK(hipEventRecord(ev[2], ps));
+    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, ps));
+    {
+        const uint32_t units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
+        uint32_t blocks = (units + 3) / 4;
+        if (blocks > max_blocks) blocks = max_blocks;
+        hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, ps, d, n, proofs, off, ci, inst, w->pts, w->valid, w->pt_tab, w->valid_sub, w->dec_ctr, dec_grid);
     }
+    HIPCHK(hipEventRecord(ev[3], ps));
+    HIPCHK(hipEventRecord(w->ev_join, ps));
+    // The MSM's hold: it waits for a few more packets on the side stream than its inputs need (a wait, two timed markers, the
+    // marker it waits for).  The MSM wants every SIMD to itself, and it is faster for the small delay: measured with the
+    // default simple_mul x 4096 run, five runs each, 1.257 M proofs/s with the hold, 1.248 M with the marker and the wait
+    // alone, 1.241 M without any.
+    HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
+    HIPCHK(hipEventRecord(ev[10], ps));
+    HIPCHK(hipEventRecord(ev[11], ps));
+    HIPCHK(hipEventRecord(w->ev_hold, ps));
+    if (int rcd = stage_done("k_g1_decompress_queue")) return rcd;
+    HIPCHK(hipEventRecord(ev[0], pm));
+    if (int rcv = launch_vm(d, n, w->stride, proofs, off, inst, ci, w->regs, w->scalars, w->status, trace, pm)) return rcv;
+    HIPCHK(hipEventRecord(ev[1], pm));
+    if (int rcd = stage_done("k_transcript_combiner")) return rcd;
+    HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
+    HIPCHK(hipStreamWaitEvent(pm, w->ev_hold, 0));
+    HIPCHK(hipEventRecord(ev[4], pm));
+    const MsmShape single = msm_ladder_shape(d.ivc ? d.n_terms : d.n_main_terms, n, 0.0, true);
+    const MsmSplit split = w->er_fix ? msm_split_shape(d, n, single, w->in_flight_hint) : MsmSplit{false, {}, {}, 0};
+    if (split.on) {
+        // per-proof terms as ladders on the main stream; the VK-base terms beside them on the side stream (free since
+        // the square roots finished), which first waits for the combiner's scalars; a one-lane-per-proof kernel adds
+        // the two sums
+        H2vMsmArgs mv = {d.terms, 0, d.n_var, d.n_terms, 0, slots, {d.n_var, d.n_var, d.n_var}, {w->er, nullptr, nullptr}, w->pt_tab, d.vk_tab, nullptr, 0, 0};
+        H2vMsmArgs mf = {d.terms, d.n_var, d.n_fix, d.n_terms, d.n_var, slots, {d.n_fix, d.n_fix, d.n_fix}, {w->er_fix, nullptr, nullptr}, w->pt_tab, d.vk_tab,
+                         d.fix_tab, split.k, (d.n_fix + split.k - 1) / split.k};
+        HIPCHK(hipStreamWaitEvent(ps, ev[1], 0));
+        const uint32_t pbf = split.fix.bs / mf.n_fixl;
+        HIPCHK(hipEventRecord(ev[7], ps));
+        hipLaunchKernelGGL(k_g1_msm_fixed, dim3((n + pbf - 1) / pbf), dim3(split.fix.bs), (size_t)split.fix.bs * 172, ps, d, mf, n, pbf, w->scalars, w->pts, (uint32_t *)nullptr);
+        HIPCHK(hipEventRecord(ev[8], ps));
+        HIPCHK(hipEventRecord(w->ev_fix, ps));
+        if (ps == pm) HIPCHK(hipEventRecord(ev[4], pm));   // (one stream: the ladder launch starts behind the fixed-base one)
+        uint32_t var_code;
+        if (msm_terms_per_lane(w->in_flight_hint) > 1) var_code = launch_msm_range(d, mv, n, w->scalars, w->pts, nullptr, pm, w->in_flight_hint);   // (several terms per lane)
+        else var_code = launch_msm_ladders(d, mv, n, split.var, w->scalars, w->pts, nullptr, pm);
+        HIPCHK(hipEventRecord(ev[9], pm));
+        w->ring_var[slot] = (uint8_t)var_code;
+        HIPCHK(hipStreamWaitEvent(pm, w->ev_fix, 0));
+        hipLaunchKernelGGL(k_g1_sum_pairs, dim3((n + 63) / 64), dim3(64), 0, pm, n, w->er, w->er_fix);
+        w->ring_lpt[slot] = 3;
+    } else {
+        w->ring_lpt[slot] = (uint8_t)launch_msm(d, n, w->scalars, w->pts, w->pt_tab, w->er, w->accl, w->accr, pm, w->in_flight_hint);
+    }
+    if (int rcd = stage_done("k_g1_msm")) return rcd;
+    const uint32_t *er_in = w->er, *el_in = nullptr;
+    if (d.ivc) {   // (timed with the MSM: the challenge hash and one more pass of the same kernel)
+        const IvcBufs ib = {w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2};
+        launch_ivc_fold(d, n, w->pts, w->er, ib, w->msm_tab, pm);
+        er_in = ib.er2; el_in = ib.el2;
+        if (int rcd = stage_done("k_ivc_challenge + fold MSM")) return rcd;
+    }
+    HIPCHK(hipEventRecord(ev[5], pm));
+    w->ring_pair[slot] = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
+    HIPCHK(hipEventRecord(ev[6], pm));
+    HIPCHK(hipEventRecord(w->ev_done, pm));
+    HIPCHK(hipStreamWaitEvent(st, w->ev_done, 0));
+    if (int rcd = stage_done("k_pairing")) return rcd;
     HIPCHK(hipGetLastError());
-    if (status_out) HIPCHK(hipMemcpyAsync(status_out, status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     if (tm) {
         HIPCHK(hipStreamSynchronize(st));
         int rc = h2v_workspace_timings(w, 0, tm);
@@ -1534,14 +1470,7 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
             lw->in_flight_hint = call_hint;
             rc = run_pipeline(d, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, nullptr, false);
         }
-        if (rc) {
-            // earlier chunks of this call (and of calls before it) are still in flight on other lanes: nothing of the caller's may
-            // be reused before they have drained, so an error return waits for every lane
-            const std::string e = g_err;
-            for (uint32_t q = 0; q < w->n_lanes; q++) if (w->lane_st[q]) (void)hipStreamSynchronize(w->lane_st[q]);
-            for (uint32_t q = 0; q < w->n_lanes; q++) w->lane_busy[q] = false;
-            return fail(rc, e);
-        }
+        if (rc) return drain_after_error(w, rc);   // (earlier chunks of this call and of calls before it are in flight on other lanes)
         HIPCHK(hipEventRecord(w->lane_ev[l], ls));
         w->lane_busy[l] = true;
     }
@@ -1667,12 +1596,7 @@ static int co_flush_lane(h2v_workspace *w, uint32_t l) {
     c.parts.clear();
     c.count = 0;
     c.plan = nullptr;
-    if (rc) {
-        const std::string e = g_err;
-        for (uint32_t q = 0; q < w->n_lanes; q++) if (w->lane_st[q]) (void)hipStreamSynchronize(w->lane_st[q]);
-        for (uint32_t q = 0; q < w->n_lanes; q++) w->lane_busy[q] = false;
-        return fail(rc, e);
-    }
+    if (rc) return drain_after_error(w, rc);
     HIPCHK(hipEventRecord(w->lane_ev[l], ls));
     w->lane_busy[l] = true;
     return H2V_OK;
@@ -1937,7 +1861,7 @@ extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_
             tm->g1_msm_ms += t1.g1_msm_ms; tm->pairing_ms += t1.pairing_ms; tm->g1_msm_fixed_ms += t1.g1_msm_fixed_ms;
             tm->msm_var_lanes_per_term = t1.msm_var_lanes_per_term;
             tm->msm_lanes_per_term = t1.msm_lanes_per_term; tm->pairing_lanes_per_proof = t1.pairing_lanes_per_proof;
-            hipEvent_t *ev = lw->ring[idx % h2v_workspace::RING][0];
+            hipEvent_t *ev = lw->ring[idx % h2v_workspace::RING];
             if (!first) first = ev[2];
             float span = 0;
             HIPCHK(hipEventElapsedTime(&span, first, ev[6]));
@@ -1950,48 +1874,30 @@ extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_
         }
         return H2V_OK;
     }
-    const int pipes = w->ring_pipes[slot];
     memset(tm, 0, sizeof *tm);
-    tm->launches = (uint32_t)pipes;
+    tm->launches = 1;
     tm->msm_lanes_per_term = w->ring_lpt[slot];
     tm->pairing_lanes_per_proof = w->ring_pair[slot];
-    float first_start = 0, last_end = 0;
-    for (int k = 0; k < pipes; k++) {
-        hipEvent_t *ev = w->ring[slot][k];
-        HIPCHK(hipEventSynchronize(ev[6]));
-        float a, b, c, e, t0 = 0, t1 = 0;
-        HIPCHK(hipEventElapsedTime(&a, ev[0], ev[1]));
-        HIPCHK(hipEventElapsedTime(&b, ev[2], ev[3]));
-        if (getenv("H2V_TIMELINE")) {
-            const int ne = w->ring_split[slot] ? 9 : 7;
-            fprintf(stderr, "[h2v timeline]");
-            for (int q = 0; q < ne; q++) { float t; HIPCHK(hipEventElapsedTime(&t, ev[0], ev[q])); fprintf(stderr, " e%d=%.3f", q, t); }
-            fprintf(stderr, "\n");
-        }
-        if (w->ring_split[slot]) {   // two concurrent launches: report the longer one
-            float b2;
-            HIPCHK(hipEventElapsedTime(&b2, ev[7], ev[8]));
-            if (b2 > b) b = b2;
-        }
-        if (w->ring_lpt[slot] == 3) {
-            // split MSM: the ladder launch over the per-proof terms ([4] .. [11]) and, beside it on another stream, the
-            // fixed-base launch over the VK-base terms ([9] .. [10]) - two kernels, two durations
-            float fx;
-            HIPCHK(hipEventElapsedTime(&c, ev[4], ev[11]));
-            HIPCHK(hipEventElapsedTime(&fx, ev[9], ev[10]));
-            tm->g1_msm_fixed_ms += fx;
-            tm->msm_var_lanes_per_term = w->ring_var[slot];
-        } else {
-            HIPCHK(hipEventElapsedTime(&c, ev[4], ev[5]));
-        }
-        HIPCHK(hipEventElapsedTime(&e, ev[5], ev[6]));
-        tm->transcript_combiner_ms += a; tm->g1_decompress_ms += b; tm->g1_msm_ms += c; tm->pairing_ms += e;
-        if (k > 0) { HIPCHK(hipEventElapsedTime(&t0, w->ring[slot][0][2], ev[2])); }
-        HIPCHK(hipEventElapsedTime(&t1, w->ring[slot][0][2], ev[6]));
-        if (k == 0 || t0 < first_start) first_start = t0;
-        if (t1 > last_end) last_end = t1;
+    hipEvent_t *ev = w->ring[slot];
+    HIPCHK(hipEventSynchronize(ev[6]));
+    HIPCHK(hipEventElapsedTime(&tm->transcript_combiner_ms, ev[0], ev[1]));
+    HIPCHK(hipEventElapsedTime(&tm->g1_decompress_ms, ev[2], ev[3]));
+    if (getenv("H2V_TIMELINE")) {
+        fprintf(stderr, "[h2v timeline]");
+        for (int q = 0; q < 7; q++) { float t; HIPCHK(hipEventElapsedTime(&t, ev[0], ev[q])); fprintf(stderr, " e%d=%.3f", q, t); }
+        fprintf(stderr, "\n");
     }
-    tm->total_ms = last_end - first_start;
+    if (w->ring_lpt[slot] == 3) {
+        // split MSM: the ladder launch over the per-proof terms ([4] .. [9]) and, beside it on another stream, the
+        // fixed-base launch over the VK-base terms ([7] .. [8]) - two kernels, two durations
+        HIPCHK(hipEventElapsedTime(&tm->g1_msm_ms, ev[4], ev[9]));
+        HIPCHK(hipEventElapsedTime(&tm->g1_msm_fixed_ms, ev[7], ev[8]));
+        tm->msm_var_lanes_per_term = w->ring_var[slot];
+    } else {
+        HIPCHK(hipEventElapsedTime(&tm->g1_msm_ms, ev[4], ev[5]));
+    }
+    HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[5], ev[6]));
+    HIPCHK(hipEventElapsedTime(&tm->total_ms, ev[2], ev[6]));
     return H2V_OK;
 }
 
@@ -2010,52 +1916,54 @@ static int host_stream(h2v_workspace *ws) {
             HIPCHK(make_stream(&ws->hs));
         }
     }
-    if (!ws->ev_host) HIPCHK(hipEventCreateWithFlags(&ws->ev_host, hipEventDisableTiming));
     return H2V_OK;
 }
 // bytes a host-buffer call's verdicts take in its pinned download block: accept[n], then the RLC verdict word at the next multiple of 8
 static inline size_t accept_extent(uint64_t n) { return (size_t)((n + 7) & ~(uint64_t)7) + 8; }
-// Packs the caller's host buffers into the pinned block and enqueues ONE upload on ws->hs.
-static int stage_inputs(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws) {
+// Packs the caller's host buffers into the pinned block of staging slot `sl` (offsets | instances | committed | proofs, each
+// 16-byte aligned), enqueues ONE upload of it on ws->hs, and returns the batch's device view in `in`.  The slot's blocks grow
+// to a quarter more than a batch that does not fit.  A laned workspace's slot is free by construction and downloads accept[]
+// through a device buffer of its own (d_accept); an ordinary workspace stages in hslot[0], and its accept[] is ws->accept.
+struct Staged { const uint8_t *proofs, *inst, *ci; const uint64_t *off; };
+static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, h2v_workspace::HostSlot &sl, Staged *in) {
+    const bool laned = ws->n_lanes != 0;
     const uint64_t n = b->n;
     const uint64_t total = b->proof_off[n];
     for (uint64_t i = 0; i < n; i++)
         if (b->proof_off[i + 1] < b->proof_off[i]) return fail(H2V_E_ARG, "proof offsets must be non-decreasing");
-    int rc = host_stream(ws);
-    if (rc) return rc;
+    if (int rc = host_stream(ws)) return rc;
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_off = 0, o_inst = up16((n + 1) * 8), o_ci = o_inst + up16(n * p->d.n_pi * 32), o_proofs = o_ci + up16(n * p->d.n_ci * 48),
+    const size_t o_inst = up16((n + 1) * 8), o_ci = o_inst + up16(n * p->d.n_pi * 32), o_proofs = o_ci + up16(n * p->d.n_ci * 48),
                  need = o_proofs + up16(total + 64);
-    if (need > ws->in_block_cap) {
-        HIPCHK(hipStreamSynchronize(ws->hs));
-        if (ws->in_block) (void)hipFree(ws->in_block);
-        if (ws->h_block) (void)hipHostFree(ws->h_block);
-        ws->in_block = nullptr; ws->h_block = nullptr; ws->in_block_cap = 0;
+    if (need > sl.in_cap) {
+        if (!laned) HIPCHK(hipStreamSynchronize(ws->hs));   // (the ordinary workspace's one slot: an earlier upload may still read it)
+        if (sl.in_block) (void)hipFree(sl.in_block);
+        if (sl.h_block) (void)hipHostFree(sl.h_block);
+        sl.in_block = nullptr; sl.h_block = nullptr; sl.in_cap = 0;
         const size_t cap = need + need / 4;
-        if (hipMalloc((void **)&ws->in_block, cap) != hipSuccess || hipHostMalloc((void **)&ws->h_block, cap, hipHostMallocDefault) != hipSuccess)
+        if (hipMalloc((void **)&sl.in_block, cap) != hipSuccess || hipHostMalloc((void **)&sl.h_block, cap, hipHostMallocDefault) != hipSuccess)
             return fail(H2V_E_DEVICE, "staging allocation failed");
-        ws->in_block_cap = cap;
+        sl.in_cap = cap;
     }
     // (accept bytes, then - RLC mode - the verdict word at the next multiple of 8: the capacity is compared with THAT extent;
     //  comparing it with n let a batch within 8 proofs of an earlier, smaller batch's slack put the word past the end of the
     //  pinned block: hipMemcpyAsync "invalid argument", found by tools/soak.py)
-    if (accept_extent(n) > ws->h_accept_cap) {
-        if (ws->h_accept) (void)hipHostFree(ws->h_accept);
-        ws->h_accept = nullptr; ws->h_accept_cap = 0;
+    if (accept_extent(n) > sl.acc_cap) {
+        if (sl.h_accept) (void)hipHostFree(sl.h_accept);
+        if (sl.d_accept) (void)hipFree(sl.d_accept);
+        sl.h_accept = nullptr; sl.d_accept = nullptr; sl.acc_cap = 0;
         const size_t cap = accept_extent(n) + n / 4 + 64;
-        if (hipHostMalloc((void **)&ws->h_accept, cap, hipHostMallocDefault) != hipSuccess) return fail(H2V_E_DEVICE, "staging allocation failed");
-        ws->h_accept_cap = cap;
+        if (hipHostMalloc((void **)&sl.h_accept, cap, hipHostMallocDefault) != hipSuccess || (laned && hipMalloc((void **)&sl.d_accept, cap) != hipSuccess))
+            return fail(H2V_E_DEVICE, "staging allocation failed");
+        sl.acc_cap = cap;
     }
-    memcpy(ws->h_block + o_off, b->proof_off, (n + 1) * 8);
-    if (p->d.n_pi) memcpy(ws->h_block + o_inst, b->instances, n * p->d.n_pi * 32);
-    if (p->d.n_ci) memcpy(ws->h_block + o_ci, b->committed, n * 48);
-    memcpy(ws->h_block + o_proofs, b->proofs, total);
-    memset(ws->h_block + o_proofs + total, 0, 64);
-    HIPCHK(hipMemcpyAsync(ws->in_block, ws->h_block, need, hipMemcpyHostToDevice, ws->hs));
-    ws->in_off = (uint64_t *)(ws->in_block + o_off);
-    ws->in_inst = ws->in_block + o_inst;
-    ws->in_ci = ws->in_block + o_ci;
-    ws->in_proofs = ws->in_block + o_proofs;
+    memcpy(sl.h_block, b->proof_off, (n + 1) * 8);
+    if (p->d.n_pi) memcpy(sl.h_block + o_inst, b->instances, n * p->d.n_pi * 32);
+    if (p->d.n_ci) memcpy(sl.h_block + o_ci, b->committed, n * 48);
+    memcpy(sl.h_block + o_proofs, b->proofs, total);
+    memset(sl.h_block + o_proofs + total, 0, 64);
+    HIPCHK(hipMemcpyAsync(sl.in_block, sl.h_block, need, hipMemcpyHostToDevice, ws->hs));
+    *in = {sl.in_block + o_proofs, sl.in_block + o_inst, sl.in_block + o_ci, (const uint64_t *)sl.in_block};
     return H2V_OK;
 }
 static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
@@ -2080,38 +1988,9 @@ static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws
     const uint64_t n = b->n;
     sl.n = n; sl.rlc = rlc;
     if (n) {
-        const uint64_t total = b->proof_off[n];
-        for (uint64_t i = 0; i < n; i++)
-            if (b->proof_off[i + 1] < b->proof_off[i]) return fail(H2V_E_ARG, "proof offsets must be non-decreasing");
-        auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        const size_t o_inst = up16((n + 1) * 8), o_ci = o_inst + up16(n * p->d.n_pi * 32), o_proofs = o_ci + up16(n * p->d.n_ci * 48),
-                     need = o_proofs + up16(total + 64);
-        if (need > sl.in_cap) {     // (the slot is free: its previous batch has been collected)
-            if (sl.in_block) (void)hipFree(sl.in_block);
-            if (sl.h_block) (void)hipHostFree(sl.h_block);
-            sl.in_block = nullptr; sl.h_block = nullptr; sl.in_cap = 0;
-            const size_t cap = need + need / 4;
-            if (hipMalloc((void **)&sl.in_block, cap) != hipSuccess || hipHostMalloc((void **)&sl.h_block, cap, hipHostMallocDefault) != hipSuccess)
-                return fail(H2V_E_DEVICE, "staging allocation failed");
-            sl.in_cap = cap;
-        }
-        if (accept_extent(n) > sl.acc_cap) {
-            if (sl.h_accept) (void)hipHostFree(sl.h_accept);
-            if (sl.d_accept) (void)hipFree(sl.d_accept);
-            sl.h_accept = nullptr; sl.d_accept = nullptr; sl.acc_cap = 0;
-            const size_t cap = accept_extent(n) + n / 4 + 64;
-            if (hipHostMalloc((void **)&sl.h_accept, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&sl.d_accept, cap) != hipSuccess)
-                return fail(H2V_E_DEVICE, "staging allocation failed");
-            sl.acc_cap = cap;
-        }
-        memcpy(sl.h_block, b->proof_off, (n + 1) * 8);
-        if (p->d.n_pi) memcpy(sl.h_block + o_inst, b->instances, n * p->d.n_pi * 32);
-        if (p->d.n_ci) memcpy(sl.h_block + o_ci, b->committed, n * 48);
-        memcpy(sl.h_block + o_proofs, b->proofs, total);
-        memset(sl.h_block + o_proofs + total, 0, 64);
-        HIPCHK(hipMemcpyAsync(sl.in_block, sl.h_block, need, hipMemcpyHostToDevice, ws->hs));
-        int rc = run_laned(p, (uint32_t)n, sl.in_block + o_proofs, (const uint64_t *)sl.in_block, sl.in_block + o_inst, sl.in_block + o_ci, sl.d_accept, nullptr,
-                           ws, ws->hs, rlc, seed, false, true);
+        Staged in;
+        if (int rcs = stage_batch(p, b, ws, sl, &in)) return rcs;
+        int rc = run_laned(p, (uint32_t)n, in.proofs, in.off, in.inst, in.ci, sl.d_accept, nullptr, ws, ws->hs, rlc, seed, false, true);
         if (rc == H2V_OK) {
             // the download waits for the lanes this call's chunks ran on (their events as recorded just now)
             const int slot = (int)((ws->calls - 1) % h2v_workspace::RING);
@@ -2125,13 +2004,7 @@ static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws
             if (rc == H2V_OK && rlc && hipMemcpyAsync(sl.h_accept + ((n + 7) & ~(uint64_t)7), ws->rlc_fail + slot, 4, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess)
                 rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
         }
-        if (rc) {
-            const std::string e = g_err;
-            (void)hipStreamSynchronize(ws->hs);
-            for (uint32_t l = 0; l < ws->n_lanes; l++) if (ws->lane_st[l]) (void)hipStreamSynchronize(ws->lane_st[l]);
-            (void)hipStreamSynchronize(ws->hs_down);
-            return fail(rc, e);
-        }
+        if (rc) return drain_after_error(ws, rc);
     }
     HIPCHK(hipEventRecord(sl.ev, ws->hs_down));
     ws->h_head++;
@@ -2170,43 +2043,30 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
     HIPCHK(hipSetDevice(p->device));
     int rc = host_stream(ws);
     if (rc) return rc;
+    if (b->n && (rc = ws_fits(ws, p, b->n, false))) return rc;
+    const bool rlc = (flags & H2V_SUBMIT_RLC) && rlc_supported(p);
+    uint32_t seed[8] = {};
     if (ws->n_lanes) {
-        if (b->n && (rc = ws_fits(ws, p, b->n, false))) return rc;
-        const bool rlc_l = (flags & H2V_SUBMIT_RLC) && rlc_supported(p);
-        uint32_t seed_l[8] = {};
-        if (rlc_l && (rc = rlc_seed(opts, seed_l))) return rc;
-        return submit_laned(p, b, ws, rlc_l, seed_l);
+        if (rlc && (rc = rlc_seed(opts, seed))) return rc;
+        return submit_laned(p, b, ws, rlc, seed);
     }
-    ws->pending_n = b->n;
-    ws->pending_rlc = false;
+    h2v_workspace::HostSlot &sl = ws->hslot[0];
+    if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    sl.n = b->n;
+    sl.rlc = false;
     if (b->n) {
-        if ((rc = ws_fits(ws, p, b->n, false))) return rc;
-        if ((rc = stage_inputs(p, b, ws))) return rc;
-        const bool rlc = (flags & H2V_SUBMIT_RLC) && rlc_supported(p);
-        uint32_t seed[8] = {};
-        if (rlc && (rc = rlc_seed(opts, seed))) { (void)hipStreamSynchronize(ws->hs); return rc; }
-        if (ws->n_lanes) {
-            rc = run_laned(p, (uint32_t)b->n, ws->in_proofs, ws->in_off, ws->in_inst, ws->in_ci, ws->accept, nullptr, ws, ws->hs, rlc, seed, true);
-        } else if (rlc) {
-            rc = run_rlc_or_routed(p, (uint32_t)b->n, ws->in_proofs, ws->in_off, ws->in_inst, ws->in_ci, ws->accept, nullptr, ws, ws->hs, seed,
-                                   opts && (opts->flags & H2V_RLC_ONE_STREAM));
-        } else {
-            rc = run_pipeline(p->d, (uint32_t)b->n, ws->in_proofs, ws->in_off, ws->in_inst, ws->in_ci, ws->accept, nullptr, ws, ws->hs, nullptr, false);
-        }
-        ws->pending_rlc = rlc;
-        if (rc == H2V_OK && hipMemcpyAsync(ws->h_accept, ws->accept, b->n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-        if (rc == H2V_OK && rlc && ws->rlc && hipMemcpyAsync(ws->h_accept + ((b->n + 7) & ~(uint64_t)7), rlc_flags_of(ws), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
+        if (rlc && (rc = rlc_seed(opts, seed))) return rc;
+        Staged in;
+        if ((rc = stage_batch(p, b, ws, sl, &in))) return rc;
+        if (rlc) rc = run_rlc_or_routed(p, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, seed, opts && (opts->flags & H2V_RLC_ONE_STREAM));
+        else rc = run_pipeline(p->d, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, nullptr, false);
+        sl.rlc = rlc;
+        if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, ws->accept, b->n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
+        if (rc == H2V_OK && rlc && ws->rlc && hipMemcpyAsync(sl.h_accept + ((b->n + 7) & ~(uint64_t)7), rlc_flags_of(ws), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
             rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
-        if (rc) {
-            // the upload from the pinned block and some kernels may already be enqueued: nothing of this workspace may be
-            // reused before they have drained
-            const std::string e = g_err;
-            (void)hipStreamSynchronize(ws->hs);
-            for (uint32_t l = 0; l < ws->n_lanes; l++) if (ws->lane_st[l]) (void)hipStreamSynchronize(ws->lane_st[l]);
-            return fail(rc, e);
-        }
+        if (rc) return drain_after_error(ws, rc);   // (the upload from the pinned block and some kernels may already be enqueued)
     }
-    HIPCHK(hipEventRecord(ws->ev_host, ws->hs));
+    HIPCHK(hipEventRecord(sl.ev, ws->hs));
     ws->pending = true;
     return H2V_OK;
 }
@@ -2219,13 +2079,14 @@ extern "C" int h2v_verify_batch_wait(h2v_workspace *ws, uint8_t *accept, int *fe
     if (!ws->pending) return fail(H2V_E_ARG, "no batch in flight on this workspace");
     HIPCHK(hipSetDevice(ws->device));
     ws->pending = false;
-    HIPCHK(hipEventSynchronize(ws->ev_host));
-    if (ws->pending_n) memcpy(accept, ws->h_accept, ws->pending_n);
+    const h2v_workspace::HostSlot &sl = ws->hslot[0];
+    HIPCHK(hipEventSynchronize(sl.ev));
+    if (sl.n) memcpy(accept, sl.h_accept, sl.n);
     if (fell_back) {
         *fell_back = 0;
-        if (ws->pending_rlc && ws->pending_n) {     // the batch verdict came back with the accept bytes (1 = passed)
+        if (sl.rlc && sl.n) {     // the batch verdict came back with the accept bytes (1 = passed)
             uint32_t passed = 1;
-            memcpy(&passed, ws->h_accept + ((ws->pending_n + 7) & ~(uint64_t)7), 4);
+            memcpy(&passed, sl.h_accept + ((sl.n + 7) & ~(uint64_t)7), 4);
             *fell_back = passed ? 0 : 1;
         }
     }
@@ -2543,8 +2404,8 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     // one_stream (h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM, or H2V_OPT_STREAMS = 1): everything on
     // the caller's stream, decompression before the combiner - one stream per batch in flight instead of two
     const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode != 0 : (one_stream_opt || w->in_flight_hint >= 3);   // (H2V_OPT_STREAMS, the flag, or the caller's in-flight hint)
-    if (!one_stream && (rc = ws_streams(w, 0, false, true, false))) return rc;
-    hipStream_t pm = st, ps = one_stream ? st : w->pside[0];
+    if (!one_stream && (rc = ws_streams(w, false, true))) return rc;
+    hipStream_t pm = st, ps = one_stream ? st : w->pside;
     if (!one_stream) {
         HIPCHK(hipEventRecord(w->ev_fork, st));
         HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
@@ -2559,12 +2420,12 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
         hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, ps, d, n, proofs, off, ci, inst, w->pts, w->valid, (uint32_t *)nullptr, w->valid_sub, w->dec_ctr, dec_grid);
     }
     HIPCHK(hipEventRecord(ev[1], ps));
-    HIPCHK(hipEventRecord(w->ev_join[0], ps));
+    HIPCHK(hipEventRecord(w->ev_join, ps));
     HIPCHK(hipEventRecord(ev[2], pm));
     rc = launch_vm(d, n, w->stride, proofs, off, inst, ci, w->regs, w->scalars, w->status, nullptr, pm);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ev[3], pm));
-    if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join[0], 0));
+    if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
     HIPCHK(hipEventRecord(ev[10], pm));
     // the batch check
     RlcArgs ra = {n, p->n_var, p->n_fix, slots, d.pi_point, d.n_terms, d.terms, w->scalars, w->status, w->valid, w->valid_sub, {},
@@ -2792,8 +2653,9 @@ extern "C" int h2v_trace(const h2v_plan *p, const uint8_t *proof, size_t proof_l
     uint64_t off[2] = {0, proof_len};
     h2v_batch b = {1, proof, off, instances, committed};
     uint8_t *d_pts96 = nullptr;
-    rc = stage_inputs(p, &b, ws);
-    if (rc == H2V_OK) rc = run_pipeline(p->d, 1, ws->in_proofs, ws->in_off, ws->in_inst, ws->in_ci, ws->accept, nullptr, ws, ws->hs, nullptr, true);
+    Staged in;
+    rc = stage_batch(p, &b, ws, ws->hslot[0], &in);
+    if (rc == H2V_OK) rc = run_pipeline(p->d, 1, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, nullptr, true);
     if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "trace pipeline failed");
     do {
         if (rc) break;

@@ -874,19 +874,19 @@ def test_circuit_without_public_inputs(be):
 
 # (option id, value) pairs of h2v_workspace_set_option + the fixed-base window width of h2v_plan_load_ex: every launch-shape
 # dimension that used to be an H2V_* environment variable read once per process (round 3: seventeen child processes)
-_O = dict(tpl=1, pairing=2, streams=3, lpt=4, bs=5, fix=6, vm=7, vm_p=8, dec=9, pipes=10, rlc_grp=11, rlc_c=12, rlc_chain=13)
-_MODES = [dict(pipes=3), dict(pairing=1), dict(lpt=1), dict(lpt=2, bs=256), dict(dec=2), dict(dec=1), dict(fix=1), dict(fix=3),
+_O = dict(tpl=1, pairing=2, streams=3, lpt=4, bs=5, fix=6, vm=7, vm_p=8, rlc_grp=11, rlc_c=12, rlc_chain=13)
+_MODES = [dict(pairing=1), dict(lpt=1), dict(lpt=2, bs=256), dict(fix=1), dict(fix=3),
           dict(fix=2, fix_c=4), dict(fix=1, fix_c=8), dict(fix=-1), dict(vm=2), dict(vm=1), dict(tpl=2), dict(tpl=4), dict(pairing=32), dict(pairing=64),
           dict(pairing=16), dict(pairing=12), dict(pairing=6), dict(vm_p=8), dict(streams=0), dict(streams=1), dict(streams=2)]
 
 
 @pytest.mark.parametrize("mode", _MODES, ids=lambda m: ",".join("%s=%s" % kv for kv in m.items()))
 def test_alternate_pipeline_modes(be, circuits, mode):
-    """Every launch-shape option of h2v_workspace_set_option (chunked sub-pipelines, every pairing engine incl. the one-lane
-    cross-check kernel, the MSM launch shape - lanes per term, block size, terms per lane, fixed-base lanes for the VK bases
-    with all-window tables of 12- (default), 8- or 4-bit windows -, the forms of the decompression launch, the narrow / wide
-    schedule of the combiner, the stream layout) IN-PROCESS, on three circuits: the same verdicts as the construction.
-    The launcher would otherwise pick these from the batch size."""
+    """Every launch-shape option of h2v_workspace_set_option (every pairing engine incl. the one-lane cross-check kernel,
+    the MSM launch shape - lanes per term, block size, terms per lane, fixed-base lanes for the VK bases with all-window
+    tables of 12- (default), 8- or 4-bit windows -, the narrow / wide schedule of the combiner, the stream layout)
+    IN-PROCESS, on three circuits: the same verdicts as the construction.  The launcher would otherwise pick these from
+    the batch size.  The retired ids 9 and 10 are refused."""
     from plutus_halo2_verifier_gen_amd import synth
     for name in ("simple_mul", "ivc", "lookup_table"):
         vk, td, pl, dp0, ov = circuits[name]
@@ -915,6 +915,16 @@ def test_alternate_pipeline_modes(be, circuits, mode):
     with pytest.raises(be.H2VError):
         w_ = be.Workspace(circuits["simple_mul"][3], 8)
         w_.set_option(_O["bs"], 100)
+    w_ = be.Workspace(circuits["simple_mul"][3], 8)
+    for retired in (9, 10):
+        for v in (0, 1, 2):
+            with pytest.raises(be.H2VError):
+                w_.set_option(retired, v)
+        with pytest.raises(be.H2VError):
+            w_.get_option(retired)
+        with pytest.raises(be.H2VError):
+            be.probe_set_option(retired, 0)
+    w_.close()
 
 
 def test_debug_sync_path_in_a_child_process(be):

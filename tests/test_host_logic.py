@@ -294,6 +294,17 @@ def test_shutdown_is_exported_and_idempotent_without_a_gpu():
     assert r.returncode == 0 and "shutdown ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
 
 
+def test_retired_option_ids_are_refused_without_a_gpu():
+    """Option ids 9 and 10 (the retired decompression forms and sub-pipelines, include/h2v.h) are not reused: the option
+    check refuses them with H2V_E_ARG before anything touches a device."""
+    L = ctypes.CDLL(os.path.join(ROOT, "plutus_halo2_verifier_gen_amd", "libh2v_hip.so"))
+    L.h2v_probe_set_option.argtypes = [ctypes.c_uint32, ctypes.c_int32]
+    L.h2v_probe_set_option.restype = ctypes.c_int
+    E_ARG = -1
+    assert L.h2v_probe_set_option(9, 0) == E_ARG
+    assert L.h2v_probe_set_option(10, 0) == E_ARG
+
+
 def test_no_cpu_fallback_without_gpu():
     """Without a GPU the product path fails loudly instead of detouring through a CPU implementation."""
     import torch
