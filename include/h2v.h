@@ -31,7 +31,12 @@ extern "C" {
 #define H2V_E_ARG (-1)     /* null / inconsistent argument */
 #define H2V_E_PLAN (-2)    /* malformed plan blob */
 #define H2V_E_DEVICE (-3)  /* HIP error (no device, out of memory, launch failure) */
-#define H2V_E_LIMIT (-4)   /* plan exceeds a backend limit (e.g. more than 64 MSM terms) */
+#define H2V_E_LIMIT (-4)   /* plan exceeds a backend limit (e.g. an MSM sum of more than H2V_MAX_MSM_TERMS terms) */
+
+/* Widest MSM sum a plan may have: the proof's own final MSM and, with recursion, each of its sums (acc_left; acc_right plus
+ * the fixed bases).  h2v_plan_load and h2v_probe_g1_msm return H2V_E_LIMIT above it, and h2v_last_error() names the sum,
+ * its width and this cap.  Sums wider than one workgroup are cut into segments whose partial sums are then added. */
+#define H2V_MAX_MSM_TERMS 4096u
 
 /* per-proof status bits (h2v_verify_batch_ex / trace): 0 = accepted */
 #define H2V_ST_BAD_SCALAR 1u       /* non-canonical scalar encoding in the proof */

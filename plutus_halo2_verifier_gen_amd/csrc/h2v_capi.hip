@@ -127,6 +127,11 @@ struct h2v_workspace {
     uint32_t *accl = nullptr, *accr = nullptr, *fold_pts = nullptr, *fold_scal = nullptr, *el2 = nullptr, *er2 = nullptr;
     uint32_t *pt_tab = nullptr;  // MSM window tables of every per-proof point, written by the decompression kernel
     uint32_t *er_fix = nullptr;  // sum of the VK-base terms when the MSM is split into a ladder and a fixed-base launch
+    // partial sums of a segmented MSM, [segment][proof][36 dwords] (plans with a sum of more than 64 terms only): room for
+    // sz_segs segments of cap proofs (msm_max_segments of the widest sum the workspace was created for)
+    uint32_t *msm_parts = nullptr;
+    uint32_t sz_segs = 0;
+    uint32_t lane_width = 0;     // laned: the widest MSM sum its lanes are created for (msm_sum_width; a multi-plan set: the widest plan's)
     uint32_t *dec_ctr = nullptr; // work-queue counter of the decompression launch
     uint8_t *valid = nullptr, *valid_sub = nullptr, *accept = nullptr;
     // Host-buffer entry points: the batch is packed into ONE pinned host block (offsets | instances | committed | proofs),
@@ -237,8 +242,13 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
     const uint32_t ivc = w[H2V_HW_IVC], n_main = w[H2V_HW_N_MAIN_TERMS];
     if (ivc > 1 || n_main == 0 || n_main > n_terms || (!ivc && n_main != n_terms) || (ivc && n_terms < n_main + 2))
         return fail(H2V_E_PLAN, "inconsistent recursion header");
-    if (n_main > 64 || (ivc && n_terms - n_main - 1 > 64))
-        return fail(H2V_E_LIMIT, "more than 64 MSM terms per sum is not supported by this backend");
+    // the widest sum the launcher cuts into segments (H2V_MAX_MSM_TERMS; the partial-sum buffer is sized from it)
+    if (n_main > H2V_MAX_MSM_TERMS)
+        return fail(H2V_E_LIMIT, std::string(ivc ? "the proof's own MSM" : "the final MSM") + " has " + std::to_string(n_main) +
+                                     " terms; this backend sums at most " + std::to_string(H2V_MAX_MSM_TERMS) + " terms per MSM (H2V_MAX_MSM_TERMS)");
+    if (ivc && n_terms - n_main - 1 > H2V_MAX_MSM_TERMS)
+        return fail(H2V_E_LIMIT, "the recursion sum acc_right + fixed bases has " + std::to_string(n_terms - n_main - 1) +
+                                     " terms; this backend sums at most " + std::to_string(H2V_MAX_MSM_TERMS) + " terms per MSM (H2V_MAX_MSM_TERMS)");
     if (ivc)
         for (int k = 0; k < 8; k++)
             if (w[H2V_HW_ACC_IDX0 + k] >= n_pi) return fail(H2V_E_PLAN, "accumulator public-input index out of range");
@@ -509,7 +519,7 @@ static void ws_release(h2v_workspace *w) {
     for (struct RlcWs *r : w->rlc_parked) rlc_release(r);
     w->rlc_parked.clear();
     if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
-    void *ptrs[] = {w->rlc_stats, w->rlc_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->dec_ctr, w->accept, w->msm_tab,
+    void *ptrs[] = {w->rlc_stats, w->rlc_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
                     w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
@@ -523,7 +533,10 @@ static void ws_release(h2v_workspace *w) {
     for (auto &set : w->ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
 }
 static uint32_t vm_lds_slots(const H2vDevPlan &d);
-static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bool with_trace, h2v_workspace **out) {
+static uint32_t msm_max_segments(uint32_t T);
+static uint32_t msm_sum_width(const H2vDevPlan &d);
+// width: the widest MSM sum the workspace must serve (0: the plan's own, msm_sum_width)
+static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bool with_trace, h2v_workspace **out, uint32_t width = 0) {
     if (max_batch == 0 || max_batch > (1ull << 24)) return fail(H2V_E_ARG, "max_batch out of range");
     ALIVE_DEV(device);
     HIPCHK(hipSetDevice(device));
@@ -543,6 +556,8 @@ static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bo
     WSALLOC(valid_sub, (size_t)max_batch * slots)
     WSALLOC(dec_ctr, 4)
     if (d.fix_tab) { WSALLOC(er_fix, (size_t)max_batch * 36 * 4) }
+    w->sz_segs = msm_max_segments(width ? width : msm_sum_width(d));
+    if (w->sz_segs) { WSALLOC(msm_parts, (size_t)max_batch * w->sz_segs * 144) }
     WSALLOC(er, (size_t)max_batch * 144)
     WSALLOC(pt_tab, (size_t)max_batch * slots * 448 * 4)             // per (proof, slot): [1..8]P and [1..8]phi(P), affine, 2 x 14 x 28-bit limbs
     if (d.ivc) { WSALLOC(msm_tab, (size_t)max_batch * 4 * 2 * 8 * 112) }  // fold MSMs build their four tables on the spot
@@ -603,7 +618,7 @@ static int ensure_lane(h2v_workspace *w, uint32_t l) {
     if (int rcs = lane_streams(l, &w->lane_st[l], &side_st)) { w->lane_st[l] = nullptr; return rcs; }
     if (!w->lane_ev[l] && hipEventCreateWithFlags(&w->lane_ev[l], hipEventDisableTiming) != hipSuccess) { w->lane_ev[l] = nullptr; return fail(H2V_E_DEVICE, "lane event creation failed"); }
     h2v_workspace *lw = nullptr;
-    int rc = ws_create_for(w->lane_plan, w->device, w->chunk, false, &lw);
+    int rc = ws_create_for(w->lane_plan, w->device, w->chunk, false, &lw, w->lane_width);
     if (rc) return rc;
     lw->one_stream_mode = 2;            // (set per call: laned_depth)
     lw->pside = side_st;                // (the decompression's stream in the two-stream form: the other half of the lane's pair)
@@ -612,7 +627,7 @@ static int ensure_lane(h2v_workspace *w, uint32_t l) {
     w->lane[l] = lw;
     return H2V_OK;
 }
-static int create_lanes_for(const H2vDevPlan &d, int device, uint64_t max_batch, uint32_t n_lanes, uint32_t chunk, h2v_workspace **out) {
+static int create_lanes_for(const H2vDevPlan &d, int device, uint64_t max_batch, uint32_t n_lanes, uint32_t chunk, h2v_workspace **out, uint32_t width = 0) {
     if (max_batch == 0 || max_batch > (1ull << 24)) return fail(H2V_E_ARG, "max_batch out of range");
     if (n_lanes > (uint32_t)h2v_workspace::MAXL) return fail(H2V_E_ARG, "at most 16 lanes");
     // chunk = 0, the library's choice: the plan's own chunk even when max_batch - the largest single call - is smaller: the lanes
@@ -624,6 +639,7 @@ static int create_lanes_for(const H2vDevPlan &d, int device, uint64_t max_batch,
     w->device = device; w->cap = max_batch; w->chunk = chunk;
     w->stride = (uint32_t)((max_batch + 63) / 64 * 64);
     w->lane_plan = d;
+    w->lane_width = width ? width : msm_sum_width(d);
     w->sz_terms = d.n_terms; w->sz_slots = (uint32_t)H2V_SLOTS(d); w->sz_regs = vm_lds_slots(d) == 0 ? d.n_regs : 0; w->sz_trace = 0; w->sz_ivc = d.ivc != 0; w->sz_fix = d.fix_tab != nullptr;
     w->lanes_per_proof = n_lanes ? n_lanes : H2V_PER_PROOF_LANES;     // an explicit lane count holds for both modes
     w->n_lanes = n_lanes ? n_lanes : H2V_DEFAULT_LANES;
@@ -656,9 +672,10 @@ extern "C" int h2v_workspace_create_multi(const h2v_plan *const *plans, uint32_t
         if (plans[k]->device != plans[0]->device) return fail(H2V_E_ARG, "the plans of one workspace must live on one device");
     }
     H2vDevPlan u = plans[0]->d;
-    uint32_t slots = 0, regs_global = 0, chunk_min = 0;
+    uint32_t slots = 0, regs_global = 0, chunk_min = 0, width = 0;
     for (uint32_t k = 0; k < n_plans; k++) {
         const H2vDevPlan &d = plans[k]->d;
+        width = msm_sum_width(d) > width ? msm_sum_width(d) : width;
         u.n_terms = d.n_terms > u.n_terms ? d.n_terms : u.n_terms;
         u.n_main_terms = d.n_main_terms > u.n_main_terms ? d.n_main_terms : u.n_main_terms;
         slots = (uint32_t)H2V_SLOTS(d) > slots ? (uint32_t)H2V_SLOTS(d) : slots;
@@ -673,7 +690,7 @@ extern "C" int h2v_workspace_create_multi(const h2v_plan *const *plans, uint32_t
     if (regs_global) { u.vm_lanes = 1; u.n_regs = regs_global; }   // vm_lds_slots(u) == 0: a global register file of that size
     else if (vm_lds_slots(u) == 0) return fail(H2V_E_ARG, "internal: union shape");
     (void)chunk_min;
-    return create_lanes_for(u, plans[0]->device, max_batch, n_lanes, chunk, out);      // (chunk = 0: the library's lane size, whatever max_batch is)
+    return create_lanes_for(u, plans[0]->device, max_batch, n_lanes, chunk, out, width);      // (chunk = 0: the library's lane size, whatever max_batch is)
 }
 extern "C" int h2v_workspace_create(const h2v_plan *p, uint64_t max_batch, h2v_workspace **out) {
     if (!p || !out) return fail(H2V_E_ARG, "null argument");
@@ -818,6 +835,7 @@ static int ws_fits(const h2v_workspace *w, const h2v_plan *p, uint64_t n, bool w
     if (vm_lds_slots(d) == 0 && d.n_regs > w->sz_regs) return fail(H2V_E_ARG, "workspace has no (or too small a) global register file for this plan");
     if (d.ivc && !w->sz_ivc) return fail(H2V_E_ARG, "workspace was created for a non-recursive plan");
     if (d.fix_tab && !w->sz_fix) return fail(H2V_E_ARG, "workspace lacks the fixed-base sum buffer of this plan");
+    if (msm_max_segments(msm_sum_width(d)) > w->sz_segs) return fail(H2V_E_ARG, "workspace was created for a plan with narrower MSM sums (no room for the partial sums of a segmented MSM)");
     if (want_trace && d.n_trace > w->sz_trace) return fail(H2V_E_ARG, "workspace has no trace buffer for this plan");
     return H2V_OK;
 }
@@ -1008,13 +1026,19 @@ static double msm_n_simd() {
     }();
     return v;
 }
-struct MsmShape { uint32_t lpt, bs; double cost, waves; };
-// lanes_per_proof lanes of chain length `chain` per proof; other_waves: waves of a launch running beside this one
-static void msm_try_shape(MsmShape &best, uint32_t lpt, uint32_t lpp, double chain, uint32_t n, double other_waves, uint32_t force_bs) {
+// n_seg > 1: a segmented shape (h2v_kernels.hip: k_g1_msm_seg) - n_seg segments of seg_terms terms, then the fold launch
+struct MsmShape { uint32_t lpt, bs; double cost, waves; uint32_t n_seg = 1, seg_terms = 0; };
+// The partial-sum buffer of segmented launches: [segment][proof][36 dwords], room for max_seg segments of the launch's proofs.
+// parts == NULL: the launch may not be segmented.
+struct SegBuf { uint32_t *parts = nullptr; uint32_t max_seg = 0; };
+// lanes_per_proof lanes of chain length `chain` per proof (of each of n_seg segments); other_waves: waves of a launch running
+// beside this one
+static void msm_try_shape(MsmShape &best, uint32_t lpt, uint32_t lpp, double chain, uint32_t n, double other_waves, uint32_t force_bs,
+                          uint32_t n_seg = 1, uint32_t seg_terms = 0) {
     for (uint32_t cand = 64; cand <= 512; cand += 64) {
         if (cand < lpp || (force_bs && cand != force_bs)) continue;
         const uint32_t pb = cand / lpp;
-        const double waves = (double)((n + pb - 1) / pb) * (cand / 64), rho = (waves + other_waves) / msm_n_simd();
+        const double waves = (double)n_seg * (double)((n + pb - 1) / pb) * (cand / 64), rho = (waves + other_waves) / msm_n_simd();
         const bool spreads = cand == 64 || cand == 256;
         const double rounds = rho > 2.0 ? (double)(uint64_t)((rho + 1.999) / 2.0) : 1.0;
         double cost = chain * ((spreads && rho <= 1.0) ? 1.0 : 1.7 * rounds);
@@ -1022,10 +1046,23 @@ static void msm_try_shape(MsmShape &best, uint32_t lpt, uint32_t lpp, double cha
         // launch of 128-thread blocks, 1024 one-wave blocks of this kernel measured 2.47 ms instead of 1.86, 256-thread
         // blocks 1.87), then one-wave blocks, then fewer idle lanes
         cost *= 1.0 + (cand == 256 ? 0.0 : cand == 64 ? 0.004 : 0.01) + 0.005 * (double)(cand - pb * lpp) / cand;
-        if (cost < best.cost) { best.cost = cost; best.lpt = lpt; best.bs = cand; best.waves = waves; }
+        // the fold of a segmented shape: a launch of one lane per proof, n_seg - 1 complete additions (16 multiplications of
+        // the 12-limb field each) deep.  NOT MEASURED: an estimate in the ladder's units (~60 per addition plus 40 for the
+        // launch's own gap) whose only job is to break ties towards fewer segments; sums of <= 64 terms never reach it
+        if (n_seg > 1) cost += 60.0 * (n_seg - 1) + 40.0;
+        if (cost < best.cost) { best.cost = cost; best.lpt = lpt; best.bs = cand; best.waves = waves; best.n_seg = n_seg; best.seg_terms = seg_terms; }
     }
 }
-static MsmShape msm_ladder_shape(uint32_t n_terms, uint32_t n, double other_waves, bool quad_ok = false) {
+// Segments a sum of T terms can be cut into (0: never, T <= 64): the fewest segments that fit a block at two lanes per term
+// in a 64-thread block, ceil(T / 32), and up to two more (msm_ladder_shape).  Sizes the partial-sum buffer.
+static uint32_t msm_max_segments(uint32_t T) { return T <= 64 ? 0u : (T + 31) / 32 + 2; }
+// the widest sum of a plan: the proof's own MSM; with recursion also acc_right + the fixed bases
+static uint32_t msm_sum_width(const H2vDevPlan &d) {
+    const uint32_t f = d.ivc && d.n_terms > d.n_main_terms + 1 ? d.n_terms - d.n_main_terms - 1 : 0;
+    return d.n_main_terms > f ? d.n_main_terms : f;
+}
+// Shapes whose LPT x T lanes fit one block (cost 1e300: none under the forced options)
+static MsmShape msm_ladder_fit(uint32_t n_terms, uint32_t n, double other_waves, bool quad_ok) {
     const int env_lpt = g_opts.v[H2V_OPT_MSM_LANES_PER_TERM];
     const uint32_t env_bs = (uint32_t)g_opts.v[H2V_OPT_MSM_BLOCK_SIZE];
     MsmShape best = {2, 512, 1e300, 0};
@@ -1042,15 +1079,67 @@ static MsmShape msm_ladder_shape(uint32_t n_terms, uint32_t n, double other_wave
         msm_try_shape(q, 8, 8 * n_terms, 1080.0, n, other_waves, env_bs);
         if (q.cost < 1e300) best = q;
     }
-    if (best.cost == 1e300) {   // forced shape that does not fit: fall back to the widest block
-        const uint32_t pb = 512 / (2 * n_terms) ? 512 / (2 * n_terms) : 1;
-        best.lpt = 2; best.bs = 512; best.waves = (double)((n + pb - 1) / pb) * 8;
+    return best;
+}
+// seg.parts != NULL: sums of more than 64 terms may also be segmented - when no shape fits one block (forced options included:
+// a forced LPT 8 segments at two lanes per term), or when the cost model prefers it.  Per (LPT, block size) it prices the fewest
+// segments that fit and the next two (fuller blocks), all waves of all segments plus the fold.  Sums of at most 64 terms are
+// never segmented: they keep the shape they always had, a forced shape that does not fit included (the widest block, which
+// holds 2 x 64 lanes).  bs == 0: nothing fits and the sum may not be segmented (the launchers then launch nothing and report 0).
+static MsmShape msm_ladder_shape(uint32_t n_terms, uint32_t n, double other_waves, bool quad_ok = false, const SegBuf &seg = SegBuf()) {
+    MsmShape best = msm_ladder_fit(n_terms, n, other_waves, quad_ok);
+    if (seg.parts && n_terms > 64) {
+        const int env_lpt = g_opts.v[H2V_OPT_MSM_LANES_PER_TERM];
+        const uint32_t env_bs = (uint32_t)g_opts.v[H2V_OPT_MSM_BLOCK_SIZE];
+        for (uint32_t cl = 2; cl >= 1; cl--) {
+            if (env_lpt && (env_lpt == 8 ? cl != 2 : (uint32_t)env_lpt != cl)) continue;
+            for (uint32_t cand = 64; cand <= 512; cand += 64) {
+                if (env_bs && cand != env_bs) continue;
+                const uint32_t per = cand / cl, s0 = (n_terms + per - 1) / per;
+                for (uint32_t S = s0 < 2 ? 2 : s0; S <= s0 + 2; S++) {
+                    const uint32_t ts = (n_terms + S - 1) / S, s_real = (n_terms + ts - 1) / ts;
+                    if (s_real > seg.max_seg) continue;
+                    msm_try_shape(best, cl, cl * ts, cl == 2 ? 1250.0 : 1600.0, n, other_waves, cand, s_real, ts);
+                }
+            }
+        }
+    }
+    if (best.cost == 1e300) {
+        if (2 * n_terms <= 512) {   // forced shape that does not fit: fall back to the widest block (it fits)
+            const uint32_t pb = 512 / (2 * n_terms);
+            best.lpt = 2; best.bs = 512; best.waves = (double)((n + pb - 1) / pb) * 8;
+        } else {
+            best.bs = 0;
+        }
     }
     return best;
 }
+// the segmented form of a one-group range (MsmShape.n_seg > 1): S segments per blockIdx.y into seg.parts, then the fold into
+// ma.out[0] on the same stream
+static uint32_t launch_msm_segments(const H2vDevPlan &d, const H2vMsmArgs &ma, uint32_t n, const MsmShape &sh, const uint32_t *scalars,
+                                    const uint32_t *pts, uint32_t *tabws, hipStream_t st, const SegBuf &seg) {
+    if (!seg.parts || sh.n_seg > seg.max_seg || !ma.pt_tab || ma.grp_end[0] != ma.n_terms || sh.lpt > 2) return 0;
+    const uint32_t lpp = sh.lpt * sh.seg_terms, per_block = sh.bs / lpp;
+    if (per_block == 0 || (uint64_t)sh.seg_terms * (sh.n_seg - 1) >= ma.n_terms) return 0;
+    const uint32_t blocks = (n + per_block - 1) / per_block;
+    if (ma.skip) {
+        const uint32_t cg = (uint32_t)(msm_n_simd() / 4.0), per_seg = (cg + sh.n_seg - 1) / sh.n_seg, blocks_c = blocks < per_seg ? blocks : per_seg;
+        if (sh.lpt == 1) hipLaunchKernelGGL(k_g1_msm_merged_cond_seg, dim3(blocks_c, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
+        else hipLaunchKernelGGL(k_g1_msm_cond_seg, dim3(blocks_c, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
+    } else if (sh.lpt == 1) {
+        hipLaunchKernelGGL(k_g1_msm_merged_seg, dim3(blocks, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
+    } else {
+        hipLaunchKernelGGL(k_g1_msm_seg, dim3(blocks, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
+    }
+    hipLaunchKernelGGL(k_g1_sum_segments, dim3((n + 63) / 64), dim3(64), 0, st, n, sh.n_seg, (const uint32_t *)seg.parts, ma.out[0], ma.skip);
+    return sh.lpt;
+}
+// returns the lanes per term launched, 0 if nothing was launched (no shape fits: see msm_ladder_shape)
 static uint32_t launch_msm_ladders(const H2vDevPlan &d, const H2vMsmArgs &ma, uint32_t n, const MsmShape &sh, const uint32_t *scalars,
-                                   const uint32_t *pts, uint32_t *tabws, hipStream_t st) {
+                                   const uint32_t *pts, uint32_t *tabws, hipStream_t st, const SegBuf &seg = SegBuf()) {
+    if (sh.n_seg > 1) return launch_msm_segments(d, ma, n, sh, scalars, pts, tabws, st, seg);
     const uint32_t lpp = sh.lpt * ma.n_terms;
+    if (sh.bs == 0 || lpp > sh.bs) return 0;
     const uint32_t per_block = sh.bs / lpp;
     const uint32_t blocks = (n + per_block - 1) / per_block;
     if (ma.skip) {   // fall-back of the RLC batch mode: a grid of at most one block per CU walks the logical blocks
@@ -1080,7 +1169,7 @@ static int msm_terms_per_lane(uint32_t in_flight_hint, uint32_t n = 0, uint32_t 
     return 2;
 }
 static uint32_t launch_msm_range(const H2vDevPlan &d, const H2vMsmArgs &ma, uint32_t n, const uint32_t *scalars, const uint32_t *pts,
-                                 uint32_t *tabws, hipStream_t st, uint32_t in_flight_hint = 1) {
+                                 uint32_t *tabws, hipStream_t st, uint32_t in_flight_hint = 1, const SegBuf &seg = SegBuf()) {
     const int tpl = msm_terms_per_lane(in_flight_hint, n, ma.n_terms);
     // (only launches of at least a quarter of a wave per SIMD at one lane per term: below that the launch is a chain of lone
     //  waves whatever else is in flight, and the two-lanes-per-term ladder is the shortest chain - sha256 shape x 128 with six
@@ -1099,7 +1188,9 @@ static uint32_t launch_msm_range(const H2vDevPlan &d, const H2vMsmArgs &ma, uint
         hipLaunchKernelGGL(k_g1_msm_multi, dim3(blocks), dim3(bs), (size_t)bs * 172, st, d, ma, n, per_block, hpl, scalars, pts, tabws);
         return 16 + (hpl + 1) / 2;   // reported as msm_lanes_per_term: 18 / 19 / 20 = up to two / three / four terms' halves per lane
     }
-    return launch_msm_ladders(d, ma, n, msm_ladder_shape(ma.n_terms, n, 0.0, ma.pt_tab != nullptr && !ma.skip), scalars, pts, tabws, st);
+    // (segments: one-group ranges with prebuilt window tables only)
+    const SegBuf sg = ma.pt_tab && ma.grp_end[0] == ma.n_terms ? seg : SegBuf();
+    return launch_msm_ladders(d, ma, n, msm_ladder_shape(ma.n_terms, n, 0.0, ma.pt_tab != nullptr && !ma.skip, sg), scalars, pts, tabws, st, sg);
 }
 // Fixed-base split of the plan's own MSM (non-recursive plans, tables present): the per-proof terms [0, n_var) as ladders
 // and, beside them on another stream, the VK-base terms as one lane per term that walks the all-window table of its base
@@ -1109,7 +1200,7 @@ static uint32_t launch_msm_range(const H2vDevPlan &d, const H2vMsmArgs &ma, uint
 // pair up on SIMDs even when there would be room for all of them alone.  So the rule is: split (one base per lane) only
 // when the single launch cannot have one wave per SIMD and most terms are VK bases.  H2V_OPT_MSM_FIXED_SPLIT = k forces a split with k bases per lane, -1 forbids it.
 struct MsmSplit { bool on; MsmShape var, fix; uint32_t k; };
-static MsmSplit msm_split_shape(const H2vDevPlan &d, uint32_t n, const MsmShape &single, uint32_t in_flight_hint = 1) {
+static MsmSplit msm_split_shape(const H2vDevPlan &d, uint32_t n, const MsmShape &single, uint32_t in_flight_hint = 1, const SegBuf &seg = SegBuf()) {
     const int opt_fix = g_opts.v[H2V_OPT_MSM_FIXED_SPLIT];                  // 0 auto, 1 .. 4 bases per lane, -1 never
     const int env_fix = opt_fix == 0 ? -1 : opt_fix < 0 ? 0 : opt_fix;       // (-1 auto, 0 never, k forced: the form the rule below is written in)
     const uint32_t env_bs = (uint32_t)g_opts.v[H2V_OPT_MSM_BLOCK_SIZE];
@@ -1132,21 +1223,41 @@ static MsmSplit msm_split_shape(const H2vDevPlan &d, uint32_t n, const MsmShape 
     out.on = true;
     out.k = k;
     out.fix = fx;
-    out.var = msm_ladder_shape(d.n_var, n, fx.waves);
+    out.var = msm_ladder_shape(d.n_var, n, fx.waves, false, seg);   // (the per-proof part may be segmented)
+    if (out.var.bs == 0) out.on = false;
     return out;
 }
 // the proof's own MSM: terms [0, n_main_terms) of the plan's table, scalars from the combiner, points from decompression.
 // A recursive plan sums acc_left and acc_right + fixed bases in the same launch (three groups, three outputs).
+// Recursive plans with a sum of more than 64 terms take the three-group launch only when its lanes fit one block; otherwise the
+// three sums run as separate ranges one after the other on the stream, each segmented where it needs to be and each with the
+// caller's in-flight hint (the multi-term form where it applies).
+// Returns the lanes per term launched - of the proof's own sum when the ranges run separately - or 0: nothing launched.
 static uint32_t launch_msm(const H2vDevPlan &d, uint32_t n, const uint32_t *scalars, const uint32_t *pts, const uint32_t *pt_tab,
-                       uint32_t *er, uint32_t *accl, uint32_t *accr, hipStream_t st, uint32_t in_flight_hint = 1) {
+                       uint32_t *er, uint32_t *accl, uint32_t *accr, hipStream_t st, uint32_t in_flight_hint = 1, const SegBuf &seg = SegBuf()) {
     H2vMsmArgs ma = {d.terms, 0, d.n_main_terms, d.n_terms, 0, H2V_SLOTS(d), {d.n_main_terms, d.n_main_terms, d.n_main_terms}, {er, nullptr, nullptr},
                      pt_tab, d.vk_tab, nullptr, 0, 0};
     if (d.ivc) {
+        if (msm_sum_width(d) > 64 && msm_ladder_fit(d.n_terms, n, 0.0, pt_tab != nullptr).cost == 1e300) {
+            const uint32_t m = d.n_main_terms;
+            const H2vMsmArgs ranges[3] = {
+                ma,
+                {d.terms, m, 1, d.n_terms, m, H2V_SLOTS(d), {1, 1, 1}, {accl, nullptr, nullptr}, pt_tab, d.vk_tab, nullptr, 0, 0},
+                {d.terms, m + 1, d.n_terms - m - 1, d.n_terms, m + 1, H2V_SLOTS(d), {d.n_terms - m - 1, d.n_terms - m - 1, d.n_terms - m - 1},
+                 {accr, nullptr, nullptr}, pt_tab, d.vk_tab, nullptr, 0, 0}};
+            uint32_t code = 0;
+            for (const H2vMsmArgs &r : ranges) {
+                const uint32_t c = launch_msm_range(d, r, n, scalars, pts, nullptr, st, in_flight_hint, seg);
+                if (!c) return 0;
+                if (!code) code = c;
+            }
+            return code;
+        }
         ma.n_terms = d.n_terms;
         ma.grp_end[0] = d.n_main_terms; ma.grp_end[1] = d.n_main_terms + 1; ma.grp_end[2] = d.n_terms;
         ma.out[1] = accl; ma.out[2] = accr;
     }
-    return launch_msm_range(d, ma, n, scalars, pts, nullptr, st, in_flight_hint);
+    return launch_msm_range(d, ma, n, scalars, pts, nullptr, st, in_flight_hint, seg);
 }
 // Recursion (IVC) fold between the MSM and the pairing (emitters/aiken.rs:696-757): the batching challenge from
 // (el, er, acc_left, acc_right_final), then el' = el + c acc_left and er' = er + c acc_right_final in one two-group
@@ -1289,8 +1400,9 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
     HIPCHK(hipStreamWaitEvent(pm, w->ev_hold, 0));
     HIPCHK(hipEventRecord(ev[4], pm));
-    const MsmShape single = msm_ladder_shape(d.ivc ? d.n_terms : d.n_main_terms, n, 0.0, true);
-    const MsmSplit split = w->er_fix ? msm_split_shape(d, n, single, w->in_flight_hint) : MsmSplit{false, {}, {}, 0};
+    const SegBuf seg = {w->msm_parts, w->sz_segs};   // (NULL for workspaces of plans whose sums are all <= 64 terms)
+    const MsmShape single = msm_ladder_shape(d.ivc ? d.n_terms : d.n_main_terms, n, 0.0, true, d.ivc ? SegBuf() : seg);
+    const MsmSplit split = w->er_fix ? msm_split_shape(d, n, single, w->in_flight_hint, seg) : MsmSplit{false, {}, {}, 0};
     if (split.on) {
         // per-proof terms as ladders on the main stream; the VK-base terms beside them on the side stream (free since
         // the square roots finished), which first waits for the combiner's scalars; a one-lane-per-proof kernel adds
@@ -1306,15 +1418,17 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
         HIPCHK(hipEventRecord(w->ev_fix, ps));
         if (ps == pm) HIPCHK(hipEventRecord(ev[4], pm));   // (one stream: the ladder launch starts behind the fixed-base one)
         uint32_t var_code;
-        if (msm_terms_per_lane(w->in_flight_hint) > 1) var_code = launch_msm_range(d, mv, n, w->scalars, w->pts, nullptr, pm, w->in_flight_hint);   // (several terms per lane)
-        else var_code = launch_msm_ladders(d, mv, n, split.var, w->scalars, w->pts, nullptr, pm);
+        if (msm_terms_per_lane(w->in_flight_hint) > 1) var_code = launch_msm_range(d, mv, n, w->scalars, w->pts, nullptr, pm, w->in_flight_hint, seg);   // (several terms per lane)
+        else var_code = launch_msm_ladders(d, mv, n, split.var, w->scalars, w->pts, nullptr, pm, seg);
+        if (!var_code) return fail(H2V_E_LIMIT, "internal: no MSM launch shape for the per-proof terms");
         HIPCHK(hipEventRecord(ev[9], pm));
         w->ring_var[slot] = (uint8_t)var_code;
         HIPCHK(hipStreamWaitEvent(pm, w->ev_fix, 0));
         hipLaunchKernelGGL(k_g1_sum_pairs, dim3((n + 63) / 64), dim3(64), 0, pm, n, w->er, w->er_fix);
         w->ring_lpt[slot] = 3;
     } else {
-        w->ring_lpt[slot] = (uint8_t)launch_msm(d, n, w->scalars, w->pts, w->pt_tab, w->er, w->accl, w->accr, pm, w->in_flight_hint);
+        w->ring_lpt[slot] = (uint8_t)launch_msm(d, n, w->scalars, w->pts, w->pt_tab, w->er, w->accl, w->accr, pm, w->in_flight_hint, seg);
+        if (!w->ring_lpt[slot]) return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
     }
     if (int rcd = stage_done("k_g1_msm")) return rcd;
     const uint32_t *er_in = w->er, *el_in = nullptr;
@@ -2467,7 +2581,8 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     {
         H2vMsmArgs ma = {d.terms, 0, d.n_main_terms, d.n_terms, 0, slots, {d.n_main_terms, d.n_main_terms, d.n_main_terms}, {w->er, nullptr, nullptr},
                          w->pt_tab, d.vk_tab, nullptr, 0, 0, skip};
-        launch_msm_range(d, ma, n, w->scalars, w->pts, nullptr, pm);
+        if (!launch_msm_range(d, ma, n, w->scalars, w->pts, nullptr, pm, 1, SegBuf{w->msm_parts, w->sz_segs}))
+            return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
     }
     {
         const uint32_t nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
@@ -2777,18 +2892,24 @@ extern "C" int h2v_probe_g1_decompress(int device, uint32_t n, const uint8_t *co
 extern "C" int h2v_probe_g1_msm(int device, uint32_t n, uint32_t T, const uint8_t *scalars, const uint8_t *bases_compressed, uint8_t *out_xy_be) {
     int rc = pick_device(device);
     if (rc) return rc;
-    if (!scalars || !bases_compressed || !out_xy_be || n == 0 || T == 0 || T > 64) return fail(H2V_E_ARG, "bad argument");
+    if (!scalars || !bases_compressed || !out_xy_be || n == 0 || T == 0) return fail(H2V_E_ARG, "bad argument");
+    if (T > H2V_MAX_MSM_TERMS)
+        return fail(H2V_E_LIMIT, "the MSM has " + std::to_string(T) + " terms; this backend sums at most " + std::to_string(H2V_MAX_MSM_TERMS) +
+                                     " terms per MSM (H2V_MAX_MSM_TERMS)");
     ProbeOpts probe_opts;
     MiniPlan mp;
-    DevBuf din, doff, dsc, dpts, dvalid, der, dout, dtab;
+    DevBuf din, doff, dsc, dpts, dvalid, der, dout, dtab, dparts;
+    const uint32_t segs = msm_max_segments(T);
     if (mp.build(T, T, nullptr, nullptr) || upload_offsets(doff, n, 48 * T) || din.alloc((size_t)n * T * 48) || dsc.alloc((size_t)n * T * 32) ||
-        dpts.alloc((size_t)n * T * 96) || dvalid.alloc((size_t)n * T) || der.alloc((size_t)n * 144) || dout.alloc((size_t)n * 96))
+        dpts.alloc((size_t)n * T * 96) || dvalid.alloc((size_t)n * T) || der.alloc((size_t)n * 144) || dout.alloc((size_t)n * 96) ||
+        (segs && dparts.alloc((size_t)n * segs * 144)))
         return fail(H2V_E_DEVICE, "probe setup failed");
     HIPCHK(hipMemcpy(din.p, bases_compressed, (size_t)n * T * 48, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dsc.p, scalars, (size_t)n * T * 32, hipMemcpyHostToDevice));
     if (dtab.alloc((size_t)n * T * 448 * 4)) return fail(H2V_E_DEVICE, "hipMalloc failed");
     hipLaunchKernelGGL(k_g1_decompress, dim3((n * T + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), dtab.as<uint32_t>(), 0u, (uint8_t *)nullptr);
-    launch_msm(mp.d, n, dsc.as<uint32_t>(), dpts.as<uint32_t>(), dtab.as<uint32_t>(), der.as<uint32_t>(), nullptr, nullptr, nullptr);
+    if (!launch_msm(mp.d, n, dsc.as<uint32_t>(), dpts.as<uint32_t>(), dtab.as<uint32_t>(), der.as<uint32_t>(), nullptr, nullptr, nullptr, 1, SegBuf{dparts.as<uint32_t>(), segs}))
+        return fail(H2V_E_LIMIT, "no MSM launch shape fits this sum");
     hipLaunchKernelGGL(k_export_points, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, 1, der.as<uint32_t>(), dout.as<uint8_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());

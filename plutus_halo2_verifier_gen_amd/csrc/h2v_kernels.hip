@@ -577,7 +577,7 @@ k_g1_decompress_queue(H2vDevPlan plan, uint32_t n, const uint8_t *__restrict__ p
 }
 
 // ============================================================================ K4: per-proof G1 MSM
-// er = sum_t s_t * B_t with T = n_terms (16 ... ~60) 255-bit scalars per proof.  T is far too small for bucket
+// er = sum_t s_t * B_t with T = n_terms (16 ... ~70 for real keys) 255-bit scalars per proof.  T is far too small for bucket
 // (Pippenger) accumulation to pay - 2^c buckets per window would outnumber the terms - so the mapping is:
 //   * TWO lanes per (proof, term): the GLV split k = k1 + k2*lambda gives lane 0 the pair (k1, P) and lane 1
 //     (k2, phi(P) = (beta' x, y)), both scalars below 2^128 (half the doubling chain, twice the waves);
@@ -590,7 +590,7 @@ k_g1_decompress_queue(H2vDevPlan plan, uint32_t n, const uint8_t *__restrict__ p
 struct H2vMsmArgs {
     const uint32_t *terms;     // (kind, index) pairs; kind = VK base or per-proof slot of `pts`
     uint32_t term_base;        // first term of the range
-    uint32_t n_terms;          // terms in the range (2 * n_terms lanes per proof, <= 512)
+    uint32_t n_terms;          // terms in the range (LPT * n_terms lanes per proof, <= the block; wider: segments, k_g1_msm_seg)
     uint32_t scal_stride;      // scalars per proof in `scalars`
     uint32_t scal_col_base;    // column of the range's first term
     uint32_t slots;            // point slots per proof in `pts`
@@ -1120,6 +1120,88 @@ k_g1_sum_pairs(uint32_t n, uint32_t *__restrict__ er, const uint32_t *__restrict
     g1j_add(r, a, b);
 #pragma unroll
     for (int k = 0; k < 12; k++) { er[(size_t)i * 36 + k] = r.x.v[k]; er[(size_t)i * 36 + 12 + k] = r.y.v[k]; er[(size_t)i * 36 + 24 + k] = r.z.v[k]; }
+}
+
+// ---------------------------------------------------------------------------- segmented per-proof MSM
+// A sum whose LPT x T lanes do not fit one block (or that the launcher's cost model prefers to cut: T > 64 only) is cut into
+// S segments of Ts terms, segment s = terms [s Ts, min((s + 1) Ts, T)) of the range, one segment per blockIdx.y.  Each block
+// runs the unchanged msm_body over its segment and writes the segment's sum to parts[s][proof][36] (Jacobian, proof stride n);
+// k_g1_sum_segments then folds the S partial sums of every proof in a second launch on the same stream: blocks of one launch
+// never exchange data.  Single-group ranges with prebuilt window tables only (the launcher guarantees both): the per-lane
+// table slabs of `tabws` are numbered by the range's own terms.
+H2V_DI H2vMsmArgs msm_segment_args(const H2vMsmArgs &ma, uint32_t seg_terms, uint32_t s, uint32_t n, uint32_t *parts) {
+    H2vMsmArgs a = ma;
+    const uint32_t lo = s * seg_terms, hi = lo + seg_terms < ma.n_terms ? lo + seg_terms : ma.n_terms;
+    a.term_base = ma.term_base + lo;
+    a.scal_col_base = ma.scal_col_base + lo;
+    a.n_terms = hi - lo;
+    a.grp_end[0] = a.grp_end[1] = a.grp_end[2] = hi - lo;
+    uint32_t *o = parts + (size_t)s * n * 36;
+    a.out[0] = a.out[1] = a.out[2] = o;
+    return a;
+}
+extern "C" __global__ void __launch_bounds__(512, 2)
+k_g1_msm_seg(H2vDevPlan plan, H2vMsmArgs ma, uint32_t n, uint32_t per_block, uint32_t seg_terms, uint32_t *__restrict__ parts,
+             const uint32_t *__restrict__ scalars, const uint32_t *__restrict__ pts, uint32_t *__restrict__ tabws) {
+    extern __shared__ uint32_t red[];
+    const H2vMsmArgs sa = msm_segment_args(ma, seg_terms, blockIdx.y, n, parts);
+    msm_body<2, false, true>(plan, sa, n, per_block, scalars, pts, tabws, red, blockIdx.x);
+}
+extern "C" __global__ void __launch_bounds__(512, 2)
+k_g1_msm_merged_seg(H2vDevPlan plan, H2vMsmArgs ma, uint32_t n, uint32_t per_block, uint32_t seg_terms, uint32_t *__restrict__ parts,
+                    const uint32_t *__restrict__ scalars, const uint32_t *__restrict__ pts, uint32_t *__restrict__ tabws) {
+    extern __shared__ uint32_t red[];
+    const H2vMsmArgs sa = msm_segment_args(ma, seg_terms, blockIdx.y, n, parts);
+    msm_body<1, false, true>(plan, sa, n, per_block, scalars, pts, tabws, red, blockIdx.x);
+}
+// the RLC fall-back's forms (as k_g1_msm_cond / k_g1_msm_merged_cond: a small grid walks the logical blocks of its segment)
+extern "C" __global__ void __launch_bounds__(512, 2)
+k_g1_msm_cond_seg(H2vDevPlan plan, H2vMsmArgs ma, uint32_t n, uint32_t per_block, uint32_t seg_terms, uint32_t *__restrict__ parts,
+                  const uint32_t *__restrict__ scalars, const uint32_t *__restrict__ pts, uint32_t *__restrict__ tabws) {
+    extern __shared__ uint32_t red[];
+    if (ma.skip[0]) return;
+    const H2vMsmArgs sa = msm_segment_args(ma, seg_terms, blockIdx.y, n, parts);
+    const uint32_t n_blocks = (n + per_block - 1) / per_block;
+    for (uint32_t bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) {
+        if (msm_groups_passed(ma.skip, bid, per_block, n)) continue;   // (uniform over the block)
+        msm_body<2, false, true>(plan, sa, n, per_block, scalars, pts, tabws, red, bid);
+        __syncthreads();
+    }
+}
+extern "C" __global__ void __launch_bounds__(512, 2)
+k_g1_msm_merged_cond_seg(H2vDevPlan plan, H2vMsmArgs ma, uint32_t n, uint32_t per_block, uint32_t seg_terms, uint32_t *__restrict__ parts,
+                         const uint32_t *__restrict__ scalars, const uint32_t *__restrict__ pts, uint32_t *__restrict__ tabws) {
+    extern __shared__ uint32_t red[];
+    if (ma.skip[0]) return;
+    const H2vMsmArgs sa = msm_segment_args(ma, seg_terms, blockIdx.y, n, parts);
+    const uint32_t n_blocks = (n + per_block - 1) / per_block;
+    for (uint32_t bid = blockIdx.x; bid < n_blocks; bid += gridDim.x) {
+        if (msm_groups_passed(ma.skip, bid, per_block, n)) continue;   // (uniform over the block)
+        msm_body<1, false, true>(plan, sa, n, per_block, scalars, pts, tabws, red, bid);
+        __syncthreads();
+    }
+}
+// out[i] = sum_s parts[s][i] with the complete law (one lane per proof, 64-lane blocks): a crafted proof can make two segment
+// sums equal, opposite or the point at infinity.  skip (RLC fall-back, else NULL): the batch check passed (skip[0]) or this
+// block's 64 proofs - exactly one group of the check (skip[1 + g]) - passed their group check, and nothing reads their sums.
+extern "C" __global__ void __launch_bounds__(64)
+k_g1_sum_segments(uint32_t n, uint32_t S, const uint32_t *__restrict__ parts, uint32_t *__restrict__ out, const uint32_t *__restrict__ skip) {
+    if (skip && (skip[0] || skip[1 + blockIdx.x])) return;
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    G1J acc, b, r;
+#pragma unroll
+    for (int k = 0; k < 12; k++) { acc.x.v[k] = parts[(size_t)i * 36 + k]; acc.y.v[k] = parts[(size_t)i * 36 + 12 + k]; acc.z.v[k] = parts[(size_t)i * 36 + 24 + k]; }
+#pragma unroll 1
+    for (uint32_t s = 1; s < S; s++) {
+        const uint32_t *q = parts + ((size_t)s * n + i) * 36;
+#pragma unroll
+        for (int k = 0; k < 12; k++) { b.x.v[k] = q[k]; b.y.v[k] = q[12 + k]; b.z.v[k] = q[24 + k]; }
+        g1j_add(r, acc, b);
+        acc = r;
+    }
+#pragma unroll
+    for (int k = 0; k < 12; k++) { out[(size_t)i * 36 + k] = acc.x.v[k]; out[(size_t)i * 36 + 12 + k] = acc.y.v[k]; out[(size_t)i * 36 + 24 + k] = acc.z.v[k]; }
 }
 
 // ============================================================================ K5: pairing check

@@ -709,3 +709,96 @@ BUILDERS = {
     "trashcan_mix": trashcan_mix_vk,
     "phased": phased_vk,
 }
+
+
+# ---------------------------------------------------------------------------------------------------- wide keys
+# Keys whose final MSM has more than 64 terms in one sum (the backend cuts such sums into segments).  Kept apart from
+# BUILDERS, which the existing suites and bench.py iterate.
+
+# docs/chip_profiles.json "bls12381" as committed in the reference (tests/golden/chip_profiles.json holds the file; the CPU
+# suite checks this literal against it)
+BLS12381_PROFILE = {"degree": 5, "advice_cols": 15, "fixed_cols": 21, "copy_constraints": 16, "gates": 9,
+                    "gate_expressions": 23, "lookups": 16, "proof_commitments": 31, "vk_commitments": 37, "evals": 80,
+                    "gate_ops": {"neg": 80, "add": 1431, "sub": 0, "mul": 2349, "from_int": 1349},
+                    "lookup_ops": {"neg": 16, "add": 31, "sub": 0, "mul": 31, "from_int": 16}, "proof_size": 4048,
+                    "commitment_map_sets": [[1, 41], [2, 2], [3, 5], [2, 4], [3, 11]]}
+
+
+def bls12381_vk(seed: int = 0x48325639, chip_alone: bool = False):
+    """BLS12-381 emulation chip shape, pinned on docs/chip_profiles.json "bls12381" (BLS12381_PROFILE): 15 advice columns,
+    21 fixed, 16 copy-constrained columns (the 15 advice + native's fixed_values), degree 5, 31 proof commitments =>
+    (31 - 15 - ceil(16 / 3) - 5 - 2) / 3 = 1 lookup argument, of the profile's 16 expressions; its lookup_ops (16 neg /
+    31 add / 31 mul / 16 constants, i.e. one of each per expression plus the batching) are secp256k1's per expression, so the
+    input expression is the same `c * (advice - advice)`.
+    Rotations: the profile's commitment map is {cur}: 41, {cur,next}: 2, {cur,next,last}: 5, {prev,cur}: 4,
+    {prev,cur,next}: 11 (63 entries).  The permutation runs over 16 columns in chunks of degree - 2 = 3: six products
+    z_0..z_5, each opened at {cur,next}, the five that are not last also at `last`.  So {cur,next,last}: 5 = z_0..z_4, and
+    {cur,next}: 2 = z_5 + the lookup product, which leaves no advice column at {cur,next}.  {cur}: 41 = 21 fixed + 16 sigma
+    + 2 vanishing + 1 permuted table + 1 advice column; {prev,cur}: 4 = the permuted lookup input + 3 advice columns;
+    {prev,cur,next}: 11 advice columns.  So 11 advice columns at {-1,0,1}, 3 at {-1,0} and 1 at {0} (15 in all), and the
+    plan compiler and the oracle both count T = 69 MSM terms with chip_alone=True (the profile's setting: pi = 1, ci = 0).
+    The default is the wrapper of examples/bls12381.rs:123: one committed-instance column, empty (the identity), and the
+    public inputs `format_instance` of one G1 point.  How many field elements that is depends on the foreign-field
+    emulation parameters of the library the example builds on, which is not in the tree: 4 is chosen here.  Both instance
+    columns join the permutation (18 columns, still 6 chunks) and the committed column is opened at x: 72 MSM terms."""
+    adv = [[-1, 0, 1]] * 11 + [[-1, 0]] * 3 + [[0]]
+    return chip_profile_vk("bls12381", seed, BLS12381_PROFILE, advice_rotations=adv, n_adv_cc=15,
+                           lookup_input=lambda rng, na, nf: scaled(sub(advice(rng.randrange(na)), advice(rng.randrange(na))),
+                                                                   rng.randrange(1, bls.R)),
+                           n_pi=1 if chip_alone else 4, n_ci=0 if chip_alone else 1,
+                           instance_in_permutation=not chip_alone)
+
+
+def _wide_composite_vk(name, seed, n_adv, n_fix, n_cc):
+    """Synthetic composite of several chips (as examples/credential_properties.rs combines them; no profile in the tree
+    counts such a circuit): half the advice columns at {-1,0,1}, a quarter at {0,1}, the rest at {0}; two lookup arguments
+    of 3 and 2 expressions, 4 public inputs and a committed instance column, degree 5, k = 12."""
+    h, q = n_adv // 2, n_adv // 4
+    adv = [[-1, 0, 1]] * h + [[0, 1]] * q + [[0]] * (n_adv - h - q)
+    return _shaped_vk(name, seed, k=12, degree=5, n_adv=n_adv, n_fix=n_fix, n_cc=n_cc, lookup_arg_exprs=[3, 2],
+                      gate_exprs=6, gate_ops={"mul": 48, "add": 40, "neg": 6}, adv_rot_sets=adv, n_pi=4, n_ci=1)
+
+
+def composite_vk(seed: int = 0x4832563a):
+    """~126 MSM terms: 24 advice, 60 fixed, 20 copy-constrained columns (_wide_composite_vk)."""
+    return _wide_composite_vk("composite", seed, 24, 60, 20)
+
+
+def wide335_vk(seed: int = 0x4832563b):
+    """~335 MSM terms (40 advice, 240 fixed, 30 copy-constrained columns): needs segments at two lanes per term."""
+    return _wide_composite_vk("wide335", seed, 40, 240, 30)
+
+
+def wide677_vk(seed: int = 0x4832563c):
+    """~677 MSM terms (48 advice, 560 fixed, 40 copy-constrained columns): needs segments at one lane per term when the
+    VK bases are not split off into the fixed-base launch."""
+    return _wide_composite_vk("wide677", seed, 48, 560, 40)
+
+
+def ivc_wide_vk(seed: int = 0x4832563d):
+    """ivc_vk with a fixed-base sum wider than 64 terms: 8 advice, 40 fixed and 16 copy-constrained columns and one inner
+    key of 40 + 16 commitments: F = 1 + 40 + 16 + 40 + 16 = 113 fixed bases (the recursion's acc_right + F sum has 114
+    terms), a main sum of 81 terms, 196 MSM terms in all (emitters/plinth.rs:692-726 builds F the same way)."""
+    adv = [[0, 1]] * 4 + [[0]] * 4
+    rng = random.Random(seed ^ 0x1)
+    inner_f_d, inner_f = _commitments(rng, 40)
+    inner_p_d, inner_p = _commitments(rng, 16)
+    inner = [{"name": "inner", "transcript_repr": rng.randrange(bls.R), "fixed_commitments": inner_f,
+              "permutation_commitments": inner_p}]
+    n_fix, n_cc = 40, 16
+    f_len = 1 + n_fix + n_cc + 40 + 16
+    n_pi = 2 + f_len + 10 + 1
+    vk, td = _shaped_vk("ivc_wide", seed, k=10, degree=5, n_adv=8, n_fix=n_fix, n_cc=n_cc, lookup_arg_exprs=[2],
+                        gate_exprs=4, gate_ops={"mul": 24, "add": 20, "neg": 4}, adv_rot_sets=adv, n_pi=n_pi, n_ci=0)
+    vk.recursion_vks = inner
+    td.rec_dlogs = inner_f_d + inner_p_d
+    return vk, td
+
+
+WIDE_BUILDERS = {
+    "bls12381": bls12381_vk,
+    "composite": composite_vk,
+    "wide335": wide335_vk,
+    "wide677": wide677_vk,
+    "ivc_wide": ivc_wide_vk,
+}
