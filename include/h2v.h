@@ -298,6 +298,36 @@ int h2v_verify_batch_rlc_device(const h2v_plan *plan, const h2v_batch *batch, ui
 /* after synchronising the stream of an RLC call: the batch verdict (1 = passed) and the kernel times of that call */
 int h2v_workspace_rlc_result(h2v_workspace *ws, uint32_t calls_back, uint32_t *batch_accepted, h2v_rlc_timings *timings);
 
+/* ---- prepare and pair check (the two halves of verification: the reference's `prepare` -> DualMSM -> `check`) -----------
+ * h2v_prepare_batch(_device) runs the verify pipeline up to the final pairing check  e(L, s_g2) == e(R, G2)  and returns the
+ * two points of every proof instead of checking them:
+ *   pairs[96 i .. 96 i + 96) = compress(L) || compress(R), each 48-byte zcash compressed (as bls12_381.g1_compress);
+ *   accept[i] of h2v_verify_batch == (status[i] == 0 && e(L, s_g2) == e(R, G2)).
+ * L, R are exactly the points the pairing kernels use (the oracle's `el` / `er`): non-recursive keys L = the proof's pi
+ * commitment and R = the multi-open MSM (the collapsed DualMSM, aiken_halo2/lib/halo2_kzg.ak:10-12); recursive (IVC) keys
+ * the folded pair el' = el + c acc_left, er' = er + c acc_right_final.  status[i] (n x uint32, may be NULL) is what the
+ * verify call reports with H2V_ST_PAIRING cleared (H2V_ST_RECURSION stays).  A proof rejected before the pairing
+ * (status[i] != 0) gets 96 ZERO bytes: not a valid encoding (compression flag unset), so h2v_check_pairs rejects it with
+ * H2V_ST_BAD_POINT - never (inf, inf), which would pass the pairing.
+ * h2v_check_pairs(_device) checks n such pairs from anywhere: accept[i] (n bytes) = e(L_i, s_g2 of plan) == e(R_i, G2).  Both
+ * points are decoded with the rules verify applies to proof points (flags, canonical x, on the curve, in G1, infinity
+ * allowed); otherwise status[i] = H2V_ST_BAD_POINT; a failed equation sets H2V_ST_PAIRING.
+ * Arguments and error codes as h2v_verify_batch(_device): the workspace must fit the plan (a workspace for max_batch proofs
+ * takes up to max_batch pairs), no host batch may be in flight on it, and under deferred joins the device forms refuse
+ * stream = NULL.  The device forms enqueue on `stream` and return (device pointers; pairs of the prepare form 4-byte
+ * aligned); the host forms return when the outputs are written.  ws = NULL: a temporary workspace.  A laned workspace cuts
+ * the call into chunks across its lanes as for verify (pairs offset by 96 bytes per proof); prepare and check calls are
+ * never gathered into coalesced groups, and their arrival runs the open groups first.  h2v_workspace_timings of a prepare
+ * call reports pairing_ms = 0. */
+int h2v_prepare_batch(const h2v_plan *plan, const h2v_batch *batch, uint8_t *pairs /* n*96 */, uint32_t *status /* or NULL */,
+                      h2v_workspace *ws /* or NULL */);
+int h2v_prepare_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_t *pairs, uint32_t *status, h2v_workspace *ws,
+                             void *stream);
+int h2v_check_pairs(const h2v_plan *plan, uint64_t n, const uint8_t *pairs /* n*96 */, uint8_t *accept, uint32_t *status /* or NULL */,
+                    h2v_workspace *ws /* or NULL */);
+int h2v_check_pairs_device(const h2v_plan *plan, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status,
+                           h2v_workspace *ws, void *stream);
+
 /* ---- parity / debugging surface ----------------------------------------------------------------------------
  * The reference's own intermediate-value trace (cargo feature plutus_debug, src/plutus_gen/emitters/plinth.rs:792-831):
  * theta, beta, gamma, x, y, hEval, vanishing_s, ..., every expression_i, plus el / er.

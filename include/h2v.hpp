@@ -97,7 +97,19 @@ class CircuitTranscript {  // verifier-side transcript: a cursor over the proof 
     size_t consumed_ = 0;
 };
 
-class Guard {  // CS::VerificationGuard: consumed by verify() (Guard::verify) or check() (DualMSM::check)
+// The collapsed DualMSM of one proof: the two points of its final pairing check e(left, s_g2) == e(right, G2), 48-byte
+// compressed each (h2v_prepare_batch).  check() runs that pairing (h2v_check_pairs).
+struct DualMSM {
+    uint8_t left[48], right[48];
+    bool check(const VerifyingKey &vk) const {
+        uint8_t pair[96], acc = 0;
+        for (int k = 0; k < 48; k++) { pair[k] = left[k]; pair[48 + k] = right[k]; }
+        h2v::check(h2v_check_pairs(vk.handle(), 1, pair, &acc, nullptr, nullptr));
+        return acc != 0;
+    }
+};
+
+class Guard {  // CS::VerificationGuard: consumed by verify() (Guard::verify), check() (DualMSM::check) or dual_msm()
   public:
     Guard(const VerifyingKey &vk, std::vector<uint8_t> proof, std::vector<uint8_t> instances, std::vector<uint8_t> committed)
         : vk_(vk), proof_(std::move(proof)), inst_(std::move(instances)), ci_(std::move(committed)) {}
@@ -106,6 +118,20 @@ class Guard {  // CS::VerificationGuard: consumed by verify() (Guard::verify) or
         if (st) throw VerifyError(st);
     }
     bool check() { return run() == 0; }
+    /// the proof's pair (h2v_prepare_batch with n = 1); throws VerifyError for a proof rejected before the pairing
+    DualMSM dual_msm() {
+        if (used_) throw Error(H2V_E_ARG, "guard already consumed");
+        used_ = true;
+        const uint64_t off[2] = {0, proof_.size()};
+        const h2v_batch b = {1, proof_.data(), off, inst_.empty() ? nullptr : inst_.data(), ci_.empty() ? nullptr : ci_.data()};
+        uint8_t pair[96];
+        uint32_t st = 0;
+        h2v::check(h2v_prepare_batch(vk_.handle(), &b, pair, &st, nullptr));
+        if (st) throw VerifyError(st);
+        DualMSM m;
+        for (int k = 0; k < 48; k++) { m.left[k] = pair[k]; m.right[k] = pair[48 + k]; }
+        return m;
+    }
 
   private:
     uint32_t run() {
@@ -146,6 +172,29 @@ inline std::vector<uint8_t> verify_batch(const VerifyingKey &vk, const h2v_batch
     std::vector<uint8_t> accept(batch.n);
     check(h2v_verify_batch(vk.handle(), &batch, accept.data(), ws));
     return accept;
+}
+// The two halves of verify_batch: prepare_batch returns every proof's pair compress(L) || compress(R) (96 bytes; zero for a
+// proof rejected before the pairing, whose status word says why) and check_pairs runs the pairing on pairs from anywhere.
+// check_pairs(vk, prepare_batch(vk, b).pairs).accept == verify_batch(vk, b).
+struct PreparedBatch {
+    std::vector<uint8_t> pairs;    // n x 96
+    std::vector<uint32_t> status;  // H2V_ST_* bits without H2V_ST_PAIRING
+};
+inline PreparedBatch prepare_batch(const VerifyingKey &vk, const h2v_batch &batch, h2v_workspace *ws = nullptr) {
+    PreparedBatch r{std::vector<uint8_t>(batch.n * 96), std::vector<uint32_t>(batch.n)};
+    check(h2v_prepare_batch(vk.handle(), &batch, r.pairs.data(), r.status.data(), ws));
+    return r;
+}
+struct PairVerdicts {
+    std::vector<uint8_t> accept;
+    std::vector<uint32_t> status;  // H2V_ST_BAD_POINT / H2V_ST_PAIRING
+};
+inline PairVerdicts check_pairs(const VerifyingKey &vk, const std::vector<uint8_t> &pairs, h2v_workspace *ws = nullptr) {
+    if (pairs.size() % 96) throw Error(H2V_E_ARG, "pairs: a multiple of 96 bytes");
+    const uint64_t n = pairs.size() / 96;
+    PairVerdicts r{std::vector<uint8_t>(n), std::vector<uint32_t>(n)};
+    check(h2v_check_pairs(vk.handle(), n, pairs.data(), r.accept.data(), r.status.data(), ws));
+    return r;
 }
 // The same vector through the batch-accept fast path (one random linear combination of the batch's pairing equations:
 // one bucketed G1 MSM + one pairing; the per-proof kernels only if the batch check fails).  fell_back (optional) tells

@@ -16,7 +16,7 @@ problems raise `backend.H2VError`.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
 from . import backend
@@ -95,6 +95,38 @@ class Verifier:
         n = len(proofs)
         if n == 0:
             return []
+        proofs_b, off, inst, ci = self._pack(proofs, instances, committed)
+        if mode == "rlc":
+            acc, _fell_back = self.device_plan.verify_batch_rlc(proofs_b, off, inst, ci, ws=self._workspace(n), seed=seed)
+        elif mode == "per-proof":
+            acc = self.device_plan.verify_batch(proofs_b, off, inst, ci, ws=self._workspace(n))
+        else:
+            raise ValueError("mode is 'per-proof' or 'rlc'")
+        return [bool(a) for a in acc]
+
+    def prepare_batch(self, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
+                      committed: Optional[Sequence[Optional[bytes]]] = None):
+        """The first half of verify_batch: (pairs, status).  pairs[i] = compress(L) || compress(R) (96 bytes), the two
+        points of proof i's final check e(L, s_g2) == e(R, G2) - 96 zero bytes for a proof rejected before the pairing;
+        status[i] = verify's status bits without ST_PAIRING (include/h2v.h: h2v_prepare_batch)."""
+        n = len(proofs)
+        if n == 0:
+            return [], []
+        raw, st = self.device_plan.prepare_batch(*self._pack(proofs, instances, committed), ws=self._workspace(n))
+        return [raw[96 * i:96 * i + 96] for i in range(n)], st
+
+    def check_pairs(self, pairs: Sequence[bytes]):
+        """The second half: (accept, status) for pairs compress(L) || compress(R) from anywhere (h2v_check_pairs)."""
+        n = len(pairs)
+        if n == 0:
+            return [], []
+        if any(len(p) != 96 for p in pairs):
+            raise ValueError("a pair is 96 bytes: compress(L) || compress(R)")
+        acc, st = self.device_plan.check_pairs(b"".join(bytes(p) for p in pairs), ws=self._workspace(n))
+        return [bool(a) for a in acc], st
+
+    def _pack(self, proofs, instances, committed):
+        n = len(proofs)
         if len(instances) != n:
             raise ValueError("one instance list per proof")
         n_pi = self.plan.n_pi
@@ -110,13 +142,24 @@ class Verifier:
             if committed is None or len(committed) != n:
                 raise ValueError("this circuit takes one committed instance per proof")
             ci = b"".join(bls.g1_compress(None) if c is None else bytes(c) for c in committed)
-        if mode == "rlc":
-            acc, _fell_back = self.device_plan.verify_batch_rlc(b"".join(proofs), off, inst, ci, ws=self._workspace(n), seed=seed)
-        elif mode == "per-proof":
-            acc = self.device_plan.verify_batch(b"".join(proofs), off, inst, ci, ws=self._workspace(n))
-        else:
-            raise ValueError("mode is 'per-proof' or 'rlc'")
-        return [bool(a) for a in acc]
+        return b"".join(proofs), off, inst, ci
+
+
+@dataclass
+class DualMSM:
+    """The collapsed DualMSM of one proof (aiken_halo2/lib/halo2_kzg.ak: `left` is the PI commitment): the two points of its
+    final check e(left, s_g2) == e(right, G2), 48-byte compressed each.  check() runs that pairing on the GPU."""
+    left: bytes
+    right: bytes
+    _verifier: Optional["Verifier"] = field(default=None, repr=False, compare=False)
+
+    def check(self, params: Optional[ParamsVerifierKZG] = None) -> bool:
+        if self._verifier is None:
+            raise RuntimeError("this DualMSM has no verifying key to check against")
+        if params is not None and bytes(params.s_g2) != bytes.fromhex(self._verifier.vk.s_g2):
+            raise ValueError("verifier params do not match the verifying key's SRS (s_g2 differs)")
+        acc, _st = self._verifier.check_pairs([bytes(self.left) + bytes(self.right)])
+        return acc[0]
 
 
 class Guard:
@@ -143,6 +186,17 @@ class Guard:
 
     def check(self, params: Optional[ParamsVerifierKZG] = None) -> bool:
         return self._run(params) == 0
+
+    def dual_msm(self) -> DualMSM:
+        """The proof's pair (prepare with n = 1); raises VerifyError for a proof rejected before the pairing."""
+        if self._used:
+            raise RuntimeError("guard already consumed")
+        self._used = True
+        off = [0, len(self._proof)]
+        raw, st = self._v.device_plan.prepare_batch(self._proof, off, self._instances, self._committed)
+        if st[0]:
+            raise VerifyError(st[0])
+        return DualMSM(raw[:48], raw[48:96], self._v)
 
 
 _VERIFIERS = {}

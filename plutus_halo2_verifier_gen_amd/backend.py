@@ -84,6 +84,7 @@ EXPORTS = [
     "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_pairing", "h2v_probe_pairing_ex",
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
+    "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
 ]
 
 _lib = None
@@ -148,6 +149,10 @@ def lib():
         L.h2v_probe_pairing.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
         L.h2v_probe_pairing_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
         L.h2v_shutdown.argtypes = [C.c_int]
+        L.h2v_prepare_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]
+        L.h2v_prepare_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.h2v_check_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.h2v_check_pairs_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         # h2v_shutdown before the interpreter goes down: the library's pool streams (hardware queues of their own) must not
         # outlive the HIP runtime / a profiler's tool library (include/h2v.h: library lifecycle).  Handles that Python still
         # holds afterwards are empty shells; their __del__ frees the host structs only.
@@ -286,6 +291,35 @@ class DevicePlan:
         check(lib().h2v_verify_batch_device(self._h, C.byref(b), d_accept, d_status, ws.handle if ws else None, stream,
                                             C.byref(tm) if timings else None))
         return tm
+
+    # ---- prepare (the pairing's two points per proof) and the pair check (include/h2v.h)
+    def prepare_batch(self, proofs: bytes, proof_off, instances: bytes, committed: Optional[bytes], ws=None):
+        """h2v_prepare_batch: (pairs, status) - pairs = n x 96 bytes compress(L) || compress(R) (96 zero bytes for a proof
+        rejected before the pairing), status = the verify call's status words without ST_PAIRING."""
+        n, b, _keep = self._host_batch(proofs, proof_off, instances, committed)
+        pairs = C.create_string_buffer(96 * max(1, n))
+        st = (C.c_uint32 * max(1, n))()
+        check(lib().h2v_prepare_batch(self._h, C.byref(b), pairs, st, ws.handle if ws else None))
+        return pairs.raw[:96 * n], list(st[:n])
+
+    def prepare_batch_device(self, n, d_proofs, d_off, d_inst, d_ci, d_pairs, d_status=None, ws=None, stream=None):
+        """h2v_prepare_batch_device: enqueues on `stream`; d_pairs = n x 96 bytes of device memory (4-byte aligned)"""
+        b = Batch(n, d_proofs, d_off, d_inst, d_ci)
+        check(lib().h2v_prepare_batch_device(self._h, C.byref(b), d_pairs, d_status, ws.handle if ws else None, stream))
+
+    def check_pairs(self, pairs: bytes, ws=None):
+        """h2v_check_pairs: (accept bytes, status) for n = len(pairs) / 96 pairs compress(L) || compress(R)"""
+        if len(pairs) % 96:
+            raise H2VError("pairs: a multiple of 96 bytes")
+        n = len(pairs) // 96
+        acc = (C.c_uint8 * max(1, n))()
+        st = (C.c_uint32 * max(1, n))()
+        check(lib().h2v_check_pairs(self._h, n, bytes(pairs), acc, st, ws.handle if ws else None))
+        return bytes(acc[:n]), list(st[:n])
+
+    def check_pairs_device(self, n, d_pairs, d_accept, d_status=None, ws=None, stream=None):
+        """h2v_check_pairs_device: enqueues on `stream`"""
+        check(lib().h2v_check_pairs_device(self._h, n, d_pairs, d_accept, d_status, ws.handle if ws else None, stream))
 
     def trace(self, proof: bytes, instances: bytes, committed: Optional[bytes]):
         nt = len(self.trace_slots)

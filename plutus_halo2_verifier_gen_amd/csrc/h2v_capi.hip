@@ -134,6 +134,13 @@ struct h2v_workspace {
     uint32_t lane_width = 0;     // laned: the widest MSM sum its lanes are created for (msm_sum_width; a multi-plan set: the widest plan's)
     uint32_t *dec_ctr = nullptr; // work-queue counter of the decompression launch
     uint8_t *valid = nullptr, *valid_sub = nullptr, *accept = nullptr;
+    // pair check (run_check): the two-slot view of 96-byte records - offsets 96 i (cap + 1 entries) and the slot table {0, 48} -
+    // allocated and filled by the first check call on this workspace; hp_buf: the device side of the host-buffer prepare /
+    // check calls (grown when a larger batch comes along)
+    uint64_t *pair_off = nullptr;
+    uint32_t *pair_pts = nullptr;
+    uint8_t *hp_buf = nullptr;
+    size_t hp_cap = 0;
     // Host-buffer entry points: the batch is packed into ONE pinned host block (offsets | instances | committed | proofs),
     // uploaded with one asynchronous copy on the workspace's own stream `hs`, verified there, and the accept bytes come
     // back into pinned memory the same way: h2v_verify_batch_submit returns once everything is enqueued, _wait collects.
@@ -520,7 +527,7 @@ static void ws_release(h2v_workspace *w) {
     w->rlc_parked.clear();
     if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
     void *ptrs[] = {w->rlc_stats, w->rlc_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
-                    w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab};
+                    w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts, w->hp_buf};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
     if (w->copy_streams_owned) {
@@ -1338,9 +1345,11 @@ static uint32_t launch_pairing(const H2vDevPlan &d, uint32_t n, const uint32_t *
 // Enqueues the four kernels.  The decompression kernel (many short waves) runs on a side stream beside the
 // transcript+combiner kernel (few long waves), and the two join before the MSM.
 extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_timings *tm);
+// pairs_out (prepare calls): instead of the pairing, k_prepare_export writes each proof's pair compress(L) || compress(R)
+// there (n x 24 dwords) and the status words without H2V_ST_PAIRING; accept is not written.
 static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst,
                         const uint8_t *ci, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
-                        h2v_timings *tm, bool want_trace) {
+                        h2v_timings *tm, bool want_trace, uint32_t *pairs_out = nullptr) {
     opts_from(w);
     struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
     const uint32_t slots = H2V_SLOTS(d);
@@ -1439,11 +1448,16 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
         if (int rcd = stage_done("k_ivc_challenge + fold MSM")) return rcd;
     }
     HIPCHK(hipEventRecord(ev[5], pm));
-    w->ring_pair[slot] = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
+    if (pairs_out) {   // (ring_pair 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
+        hipLaunchKernelGGL(k_prepare_export, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, pairs_out);
+        w->ring_pair[slot] = 0;
+    } else {
+        w->ring_pair[slot] = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
+    }
     HIPCHK(hipEventRecord(ev[6], pm));
     HIPCHK(hipEventRecord(w->ev_done, pm));
     HIPCHK(hipStreamWaitEvent(st, w->ev_done, 0));
-    if (int rcd = stage_done("k_pairing")) return rcd;
+    if (int rcd = stage_done(pairs_out ? "k_prepare_export" : "k_pairing")) return rcd;
     HIPCHK(hipGetLastError());
     if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     if (tm) {
@@ -1451,6 +1465,53 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
         int rc = h2v_workspace_timings(w, 0, tm);
         if (rc) return rc;
     }
+    return H2V_OK;
+}
+
+// Pair check: n records of 96 bytes compress(L) || compress(R) are decoded as two-slot "proofs" of a view of the plan (its
+// line tables of s_g2 and G2, proof_len 96, slots at bytes 0 and 48) by the pipeline's decompression launch - flags, canonical
+// x, on the curve, in G1, infinity allowed - into the workspace's point buffers; R goes to Jacobian form (k_pairs_to_jac) and
+// the production pairing launcher checks e(L, s_g2) == e(R, G2).  Everything on `st`.  Events as run_pipeline's ring:
+// [2]/[3] around the decompression, [4]/[5] around the conversion, [5]/[6] around the pairing.
+static int pair_view_ensure(h2v_workspace *w) {
+    if (w->pair_off) return H2V_OK;
+    std::vector<uint64_t> off(w->cap + 1);
+    for (uint64_t i = 0; i <= w->cap; i++) off[i] = 96 * i;
+    const uint32_t slot_off[2] = {0, 48};
+    if (hipMalloc((void **)&w->pair_pts, 8) != hipSuccess || hipMalloc((void **)&w->pair_off, off.size() * 8) != hipSuccess ||
+        hipMemcpy(w->pair_pts, slot_off, 8, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(w->pair_off, off.data(), off.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        for (void *q : {(void *)w->pair_off, (void *)w->pair_pts}) if (q) (void)hipFree(q);
+        w->pair_off = nullptr; w->pair_pts = nullptr;
+        return fail(H2V_E_DEVICE, "allocation of the pair-check buffers failed");
+    }
+    return H2V_OK;
+}
+static int run_check(const H2vDevPlan &d, uint32_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st) {
+    opts_from(w);
+    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
+    if (int rc = pair_view_ensure(w)) return rc;
+    H2vDevPlan v = d;
+    v.proof_len = 96; v.n_points = 2; v.n_ci = 0; v.n_pi = 0; v.ivc = 0; v.pi_point = 0; v.points = w->pair_pts;
+    const int slot = (int)(w->calls % h2v_workspace::RING);
+    hipEvent_t *ev = w->ring[slot];
+    w->calls++;
+    for (int q : {0, 1, 2}) HIPCHK(hipEventRecord(ev[q], st));
+    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
+    HIPCHK(hipMemsetAsync(w->status, 0, (size_t)n * 4, st));
+    const uint32_t dec_grid = (n * 2 + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
+    const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
+    hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, pairs, (const uint64_t *)w->pair_off, (const uint8_t *)nullptr,
+                       (const uint8_t *)nullptr, w->pts, w->valid, (uint32_t *)nullptr, w->valid_sub, w->dec_ctr, dec_grid);
+    HIPCHK(hipEventRecord(ev[3], st));
+    HIPCHK(hipEventRecord(ev[4], st));
+    hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er);
+    HIPCHK(hipEventRecord(ev[5], st));
+    w->ring_lpt[slot] = 0;
+    w->ring_pair[slot] = (uint8_t)launch_pairing(v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, accept, nullptr, st, w->in_flight_hint);
+    HIPCHK(hipEventRecord(ev[6], st));
+    HIPCHK(hipGetLastError());
+    if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
 
@@ -1520,9 +1581,12 @@ static uint32_t laned_depth(const h2v_workspace *w, uint64_t n, bool rlc, int *s
     }
     return (small || w->lanes_per_proof >= w->n_lanes) ? w->n_lanes : w->lanes_per_proof;
 }
+// A prepare or pair-check call through the lanes (never RLC): prepare writes pairs to `out`; a check reads them from `in`
+// (then proofs / off / inst / ci are unused).  Both are n x 96 bytes, cut into chunks like accept[].
+struct PairIO { uint8_t *out; const uint8_t *in; };
 static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
                      uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t *seed, bool force_join,
-                     bool never_join = false) {
+                     bool never_join = false, const PairIO *pio = nullptr) {
     const H2vDevPlan &d = p->d;
     if (int rcf = co_flush(w)) return rcf;          // (calls start in submission order: an open group of coalesced calls first)
     int stream_mode = 1;
@@ -1579,10 +1643,14 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
                 rc = run_rlc(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, true);
             }
             if (rc == H2V_OK && hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, ls) != hipSuccess) rc = fail(H2V_E_DEVICE, "routing counters: copy failed");
+        } else if (pio && pio->in) {
+            lw->in_flight_hint = call_hint;
+            rc = run_check(d, m, pio->in + (size_t)lo * 96, accept + lo, status_out ? status_out + lo : nullptr, lw, ls);
         } else {
             lw->one_stream_mode = stream_mode;
             lw->in_flight_hint = call_hint;
-            rc = run_pipeline(d, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, nullptr, false);
+            rc = run_pipeline(d, m, proofs, off + lo, inst_c, ci_c, accept ? accept + lo : nullptr, status_out ? status_out + lo : nullptr, lw, ls, nullptr, false,
+                              pio ? (uint32_t *)(pio->out + (size_t)lo * 96) : nullptr);
         }
         if (rc) return drain_after_error(w, rc);   // (earlier chunks of this call and of calls before it are in flight on other lanes)
         HIPCHK(hipEventRecord(w->lane_ev[l], ls));
@@ -2010,7 +2078,7 @@ extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_
     } else {
         HIPCHK(hipEventElapsedTime(&tm->g1_msm_ms, ev[4], ev[5]));
     }
-    HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[5], ev[6]));
+    if (w->ring_pair[slot]) HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[5], ev[6]));   // (0: a prepare call - no pairing ran)
     HIPCHK(hipEventElapsedTime(&tm->total_ms, ev[2], ev[6]));
     return H2V_OK;
 }
@@ -2225,6 +2293,134 @@ static int verify_host(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, h
 }
 extern "C" int h2v_verify_batch(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, h2v_workspace *ws) {
     return verify_host(p, b, accept, ws, 0, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------- prepare / pair check
+// h2v_prepare_batch(_device): the verify pipeline up to the pairing, which k_prepare_export replaces (run_pipeline's pairs_out);
+// h2v_check_pairs(_device): the pairing alone on pairs from anywhere (run_check).  Same argument rules as the verify calls;
+// never gathered into coalesced groups (run_laned flushes the open groups first).
+static int pairs_common(const h2v_plan *p, uint64_t n, h2v_workspace *ws, const void *stream, bool device_form, h2v_workspace **tmp) {
+    ALIVE(p); ALIVE(ws);
+    HIPCHK(hipSetDevice(p->device));
+    if (H2V_SLOTS(p->d) < 2) return fail(H2V_E_ARG, "internal: a plan with fewer than two point slots");
+    if (!ws) {
+        if (int rc = ws_create_for(p->d, p->device, n, false, tmp)) return rc;
+        ws = *tmp;
+    }
+    int rc = ws_fits(ws, p, n, false);
+    if (rc == H2V_OK && ws->pending) rc = fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
+    if (rc == H2V_OK && device_form) rc = null_stream_check(ws, stream);
+    if (rc && *tmp) { h2v_workspace_free(*tmp); *tmp = nullptr; }
+    return rc;
+}
+static int batch_args(const h2v_plan *p, const h2v_batch *b) {
+    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null proofs / offsets");
+    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
+    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    return H2V_OK;
+}
+// enqueue a prepare (pio->out) or check (pio->in) call of n proofs / pairs on `st`; join: the stream waits for the lanes
+static int pairs_enqueue(const h2v_plan *p, uint64_t n, const h2v_batch *b, const PairIO &pio, uint8_t *accept, uint32_t *status,
+                         h2v_workspace *ws, hipStream_t st, bool join) {
+    const uint8_t *proofs = b ? b->proofs : nullptr, *inst = b ? b->instances : nullptr, *ci = b ? b->committed : nullptr;
+    const uint64_t *off = b ? b->proof_off : nullptr;
+    if (ws->n_lanes) return run_laned(p, (uint32_t)n, proofs, off, inst, ci, accept, status, ws, st, false, nullptr, join, false, &pio);
+    if (pio.in) return run_check(p->d, (uint32_t)n, pio.in, accept, status, ws, st);
+    return run_pipeline(p->d, (uint32_t)n, proofs, off, inst, ci, nullptr, status, ws, st, nullptr, false, (uint32_t *)pio.out);
+}
+// the device side of a host-buffer call: n pairs, n status words, n accept bytes
+static int hp_ensure(h2v_workspace *ws, uint64_t n) {
+    const size_t need = (size_t)n * (96 + 4 + 1) + 64;
+    if (ws->hp_cap >= need) return H2V_OK;
+    if (ws->hp_buf) { HIPCHK(hipStreamSynchronize(ws->hs)); (void)hipFree(ws->hp_buf); }
+    ws->hp_buf = nullptr; ws->hp_cap = 0;
+    if (hipMalloc((void **)&ws->hp_buf, need) != hipSuccess) return fail(H2V_E_DEVICE, "hipMalloc(host-call buffers) failed");
+    ws->hp_cap = need;
+    return H2V_OK;
+}
+extern "C" int h2v_prepare_batch_device(const h2v_plan *p, const h2v_batch *b, uint8_t *pairs, uint32_t *status, h2v_workspace *ws, void *stream) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!b) return fail(H2V_E_ARG, "null argument: batch");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (b->n == 0) return H2V_OK;
+    if ((uintptr_t)pairs & 3) return fail(H2V_E_ARG, "pairs must be 4-byte aligned");
+    if (int rc = batch_args(p, b)) return rc;
+    h2v_workspace *tmp = nullptr;
+    if (int rc = pairs_common(p, b->n, ws, stream, true, &tmp)) return rc;
+    if (tmp) ws = tmp;
+    int rc = pairs_enqueue(p, b->n, b, PairIO{pairs, nullptr}, nullptr, status, ws, (hipStream_t)stream, false);
+    if (tmp) {
+        if (rc == H2V_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
+        h2v_workspace_free(tmp);
+    }
+    return rc;
+}
+extern "C" int h2v_check_pairs_device(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws, void *stream) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
+    if (n == 0) return H2V_OK;
+    h2v_workspace *tmp = nullptr;
+    if (int rc = pairs_common(p, n, ws, stream, true, &tmp)) return rc;
+    if (tmp) ws = tmp;
+    int rc = pairs_enqueue(p, n, nullptr, PairIO{nullptr, pairs}, accept, status, ws, (hipStream_t)stream, false);
+    if (tmp) {
+        if (rc == H2V_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
+        h2v_workspace_free(tmp);
+    }
+    return rc;
+}
+// Host-buffer forms: the batch is staged as for h2v_verify_batch (pinned block, one upload on the workspace's stream), the
+// call runs there with its lanes joined, and the outputs come back before the function returns.
+extern "C" int h2v_prepare_batch(const h2v_plan *p, const h2v_batch *b, uint8_t *pairs, uint32_t *status, h2v_workspace *ws) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!b) return fail(H2V_E_ARG, "null argument: batch");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (b->n == 0) return H2V_OK;
+    if (int rc = batch_args(p, b)) return rc;
+    h2v_workspace *tmp = nullptr;
+    if (int rc = pairs_common(p, b->n, ws, nullptr, false, &tmp)) return rc;
+    if (tmp) ws = tmp;
+    const uint64_t n = b->n;
+    int rc = host_stream(ws);
+    Staged in{};
+    if (rc == H2V_OK) rc = hp_ensure(ws, n);
+    if (rc == H2V_OK) rc = stage_batch(p, b, ws, ws->n_lanes ? ws->hslot[ws->h_head % h2v_workspace::MAXH] : ws->hslot[0], &in);
+    if (rc == H2V_OK) {
+        uint8_t *d_pairs = ws->hp_buf;
+        uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
+        const h2v_batch db = {n, in.proofs, in.off, in.inst, in.ci};
+        rc = pairs_enqueue(p, n, &db, PairIO{d_pairs, nullptr}, nullptr, d_status, ws, ws->hs, true);
+        if (rc == H2V_OK && hipMemcpyAsync(pairs, d_pairs, (size_t)n * 96, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the pairs failed");
+        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
+        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "prepare kernels failed");
+        if (rc) rc = drain_after_error(ws, rc);
+    }
+    if (tmp) h2v_workspace_free(tmp);
+    return rc;
+}
+extern "C" int h2v_check_pairs(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
+    if (n == 0) return H2V_OK;
+    h2v_workspace *tmp = nullptr;
+    if (int rc = pairs_common(p, n, ws, nullptr, false, &tmp)) return rc;
+    if (tmp) ws = tmp;
+    int rc = host_stream(ws);
+    if (rc == H2V_OK) rc = hp_ensure(ws, n);
+    if (rc == H2V_OK) {
+        uint8_t *d_pairs = ws->hp_buf, *d_accept = ws->hp_buf + (size_t)n * 100;
+        uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
+        if (hipMemcpyAsync(d_pairs, pairs, (size_t)n * 96, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the pairs failed");
+        if (rc == H2V_OK) rc = pairs_enqueue(p, n, nullptr, PairIO{nullptr, d_pairs}, d_accept, d_status, ws, ws->hs, true);
+        if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
+        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
+        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "pair check kernels failed");
+        if (rc) rc = drain_after_error(ws, rc);
+    }
+    if (tmp) h2v_workspace_free(tmp);
+    return rc;
 }
 
 

@@ -1330,6 +1330,33 @@ H2V_DN void g1_compress_dev(uint8_t (&out)[48], const G1A &a) {
     }
     out[0] |= fp_is_lex_larger(a.y) ? 0xa0 : 0x80;
 }
+// Affine forms of N Jacobian points with ONE field inversion (Montgomery's trick).  A point at infinity contributes Z := 1 to
+// the product, so the product is never zero, and comes out as the affine infinity sentinel.  Used by k_ivc_challenge (its
+// three sums) and k_prepare_export (the pair L, R).
+template <int N>
+H2V_DI void g1j_to_affine_batch(G1A *out, const G1J *j) {
+    Fp z[N], pre[N], inv, t;
+    bool inf[N];
+    for (int q = 0; q < N; q++) {
+        inf[q] = g1j_is_inf(j[q]);
+        z[q] = j[q].z;
+        if (inf[q]) fp_set_one(z[q]);
+    }
+    pre[0] = z[0];
+    for (int q = 1; q < N; q++) fp_mul(pre[q], pre[q - 1], z[q]);
+    (void)fp_inv(inv, pre[N - 1]);          // never zero: every factor is a non-zero Z or 1
+    for (int q = N - 1; q >= 0; q--) {
+        Fp zi;
+        if (q > 0) { fp_mul(zi, inv, pre[q - 1]); fp_mul(t, inv, z[q]); inv = t; } else zi = inv;
+        G1A &o = out[q];
+        if (inf[q]) { g1a_set_inf(o); continue; }
+        Fp zi2;
+        fp_sqr(zi2, zi);
+        fp_mul(o.x, j[q].x, zi2);
+        fp_mul(zi2, zi2, zi);
+        fp_mul(o.y, j[q].y, zi2);
+    }
+}
 extern "C" __global__ void __launch_bounds__(64)
 k_ivc_challenge(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, const uint32_t *__restrict__ er_jac,
                 const uint32_t *__restrict__ accl_jac, const uint32_t *__restrict__ accr_jac,
@@ -1347,33 +1374,14 @@ k_ivc_challenge(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, c
         for (int k = 0; k < 12; k++) { p[0].x.v[k] = pp[k]; p[0].y.v[k] = pp[12 + k]; }
     }
     {
-        // batch normalisation of the three Jacobian points; a point at infinity contributes Z := 1 to the product
+        // batch normalisation of the three Jacobian points (g1j_to_affine_batch: one inversion)
         G1J j[3];
         const uint32_t *src[3] = {er_jac, accl_jac, accr_jac};
-        Fp z[3], pre[3], inv, t;
-        bool inf[3];
         for (int q = 0; q < 3; q++) {
 #pragma unroll
             for (int k = 0; k < 12; k++) { j[q].x.v[k] = src[q][(size_t)ii * 36 + k]; j[q].y.v[k] = src[q][(size_t)ii * 36 + 12 + k]; j[q].z.v[k] = src[q][(size_t)ii * 36 + 24 + k]; }
-            inf[q] = g1j_is_inf(j[q]);
-            z[q] = j[q].z;
-            if (inf[q]) fp_set_one(z[q]);
         }
-        pre[0] = z[0];
-        fp_mul(pre[1], pre[0], z[1]);
-        fp_mul(pre[2], pre[1], z[2]);
-        (void)fp_inv(inv, pre[2]);          // never zero: every factor is a non-zero Z or 1
-        for (int q = 2; q >= 0; q--) {
-            Fp zi;
-            if (q > 0) { fp_mul(zi, inv, pre[q - 1]); fp_mul(t, inv, z[q]); inv = t; } else zi = inv;
-            G1A &o = p[q + 1];
-            if (inf[q]) { g1a_set_inf(o); continue; }
-            Fp zi2;
-            fp_sqr(zi2, zi);
-            fp_mul(o.x, j[q].x, zi2);
-            fp_mul(zi2, zi2, zi);
-            fp_mul(o.y, j[q].y, zi2);
-        }
+        g1j_to_affine_batch<3>(p + 1, j);
     }
     Transcript tr;
     tr_init(tr);
@@ -1404,6 +1412,71 @@ k_ivc_challenge(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, c
             for (int l = 0; l < 8; l++) ds[l] = (q & 1) ? c.v[l] : (l == 0 ? 1u : 0u);
         }
     }
+}
+
+// ============================================================================ K5': prepare (the pairing's two points, exported)
+// What the pairing kernels would check for proof i, written out instead: L = the proof's pi point (or the folded el' of a
+// recursive plan), R = er (or the folded er').  status folds valid / valid_sub into H2V_ST_BAD_POINT exactly as the pairing
+// kernels do; a proof whose status is not 0 gets 96 zero bytes, which is not a valid encoding (compression flag unset).
+// Otherwise pairs[i] = compress(L) || compress(R), normalised with one inversion (g1j_to_affine_batch) and written as 24
+// dword stores (pairs: n x 24 dwords, 4-byte aligned).
+extern "C" __global__ void __launch_bounds__(64)
+k_prepare_export(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, const uint8_t *__restrict__ valid, const uint8_t *__restrict__ valid_sub,
+                 const uint32_t *__restrict__ er_jac, const uint32_t *__restrict__ el_jac /* folded el (recursion) or NULL */,
+                 uint32_t *__restrict__ status, uint32_t *__restrict__ pairs) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t slots = H2V_SLOTS(plan);
+    uint32_t st = status[i];
+    for (uint32_t j = 0; j < slots; j++)
+        if (!valid[(size_t)i * slots + j] || (valid_sub && !valid_sub[(size_t)i * slots + j])) st |= H2V_ST_BAD_POINT;
+    status[i] = st;
+    uint32_t words[24];
+#pragma unroll
+    for (int k = 0; k < 24; k++) words[k] = 0;
+    if (st == 0) {
+        G1J j[2];
+        if (el_jac) {
+#pragma unroll
+            for (int k = 0; k < 12; k++) { j[0].x.v[k] = el_jac[(size_t)i * 36 + k]; j[0].y.v[k] = el_jac[(size_t)i * 36 + 12 + k]; j[0].z.v[k] = el_jac[(size_t)i * 36 + 24 + k]; }
+        } else {
+            G1A l;
+            const uint32_t *pp = pts + ((size_t)i * slots + plan.pi_point) * 24;
+#pragma unroll
+            for (int k = 0; k < 12; k++) { l.x.v[k] = pp[k]; l.y.v[k] = pp[12 + k]; }
+            g1j_from_affine(j[0], l);
+        }
+#pragma unroll
+        for (int k = 0; k < 12; k++) { j[1].x.v[k] = er_jac[(size_t)i * 36 + k]; j[1].y.v[k] = er_jac[(size_t)i * 36 + 12 + k]; j[1].z.v[k] = er_jac[(size_t)i * 36 + 24 + k]; }
+        G1A a[2];
+        g1j_to_affine_batch<2>(a, j);
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            uint8_t enc[48];
+            g1_compress_dev(enc, a[q]);
+#pragma unroll
+            for (int k = 0; k < 12; k++)
+                words[12 * q + k] = (uint32_t)enc[4 * k] | ((uint32_t)enc[4 * k + 1] << 8) | ((uint32_t)enc[4 * k + 2] << 16) | ((uint32_t)enc[4 * k + 3] << 24);
+        }
+    }
+    uint32_t *o = pairs + (size_t)i * 24;
+#pragma unroll
+    for (int k = 0; k < 24; k++) o[k] = words[k];
+}
+// The pair check's R as the pairing kernels take it: slot 1 of each two-slot record of `pts` (affine) -> Jacobian (n x 36 dwords)
+extern "C" __global__ void __launch_bounds__(64)
+k_pairs_to_jac(uint32_t n, const uint32_t *__restrict__ pts, uint32_t *__restrict__ er_jac) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    G1A a;
+    const uint32_t *pp = pts + ((size_t)i * 2 + 1) * 24;
+#pragma unroll
+    for (int k = 0; k < 12; k++) { a.x.v[k] = pp[k]; a.y.v[k] = pp[12 + k]; }
+    G1J j;
+    g1j_from_affine(j, a);
+    uint32_t *o = er_jac + (size_t)i * 36;
+#pragma unroll
+    for (int k = 0; k < 12; k++) { o[k] = j.x.v[k]; o[12 + k] = j.y.v[k]; o[24 + k] = j.z.v[k]; }
 }
 
 // ============================================================================ plan load: window tables of the VK bases
