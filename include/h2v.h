@@ -360,6 +360,17 @@ int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t *scalars, c
  * 28 bits each, Montgomery form R = 2^392): the one-lane result, then lanes 0..3 of a quad.  Guards a compiler issue
  * (csrc/h2v_curve28.hpp: g1j28_madd_quad). */
 int h2v_probe_quad_madd(int device, const uint32_t *pq, int neg, uint32_t *out);
+/* The merged products of the lazily reduced field (csrc/h2v_fp28.hpp: f28_dot2) and the one-lane G1 formulas built on them, on
+ * RAW records: 14 dwords = 14 limbs of 28 bits, Montgomery form R = 2^392, limbs and values as large as the bounds stated in
+ * the headers allow (h2v_probe_field takes canonical operands and cannot carry such limbs).
+ *   op & 15:  0: a b + c d    1: a^2 + c d    2: 2 a^2 + c d      n records each in a, b, c, d (b unused by 1, 2); out n x 14
+ *             8: 2P    9: P + Q with Q affine (mixed, unchecked)    10: P + Q (complete but for infinity)
+ *                P = n x 42 dwords (X, Y, Z) in a, Q likewise in b (Z ignored by 9); c, d unused (may be NULL);
+ *                out n x 44 dwords: X, Y, Z, the return code of the full addition (0 sum, 1 doubled, 2 infinity), 0
+ *   op | 16:  the forms with the multiplier inlined (ops 0 .. 9)      op | 64: subtract Q (ops 9, 10)
+ * tests/test_field_dot2_gpu.py */
+int h2v_probe_f28_dot2(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                       uint32_t *out);
 /* e(p1, s_g2 of plan) == e(p2, G2) for n pairs of compressed G1 points; out[i] = 1/0 */
 int h2v_probe_pairing(const h2v_plan *plan, uint32_t n, const uint8_t *p1_compressed, const uint8_t *p2_compressed,
                       uint8_t *out);

@@ -81,7 +81,7 @@ EXPORTS = [
     "h2v_workspace_join", "h2v_workspace_lanes", "h2v_workspace_depth", "h2v_workspace_set_option", "h2v_workspace_get_option", "h2v_workspace_tune", "h2v_probe_set_option",
     "h2v_verify_batch", "h2v_verify_batch_submit", "h2v_verify_batch_wait", "h2v_verify_batch_device", "h2v_verify_batch_rlc", "h2v_verify_batch_rlc_device",
     "h2v_workspace_rlc_result", "h2v_probe_g1_msm_pippenger", "h2v_plan_trace_slots", "h2v_trace", "h2v_probe_field",
-    "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_pairing", "h2v_probe_pairing_ex",
+    "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_f28_dot2", "h2v_probe_pairing", "h2v_probe_pairing_ex",
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
@@ -142,6 +142,7 @@ def lib():
         L.h2v_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
         L.h2v_probe_field.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.h2v_probe_f28_dot2.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_blake2b.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
         L.h2v_probe_g1_decompress.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_g1_msm.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
@@ -537,6 +538,33 @@ def probe_g1_msm_fixed(plan: DevicePlan, scalar_rows, bases_per_lane: int = 1):
     check(lib().h2v_probe_g1_msm_fixed(plan.handle, n, bases_per_lane, sc, out, C.byref(nf)))
     assert all(len(row) == nf.value for row in scalar_rows)
     return [_unxy(out.raw[96 * i:96 * i + 96]) for i in range(n)]
+
+
+# h2v_probe_f28_dot2 op codes (include/h2v.h)
+DOT2_MUL, DOT2_SQR, DOT2_SQR2, DOT2_DBL, DOT2_MADD, DOT2_ADD, DOT2_INLINE, DOT2_NEG_Q = 0, 1, 2, 8, 9, 10, 16, 64
+
+
+def probe_f28_dot2(op: int, a, b=None, c=None, d=None, device: int = 0):
+    """h2v_probe_f28_dot2 on raw lazily reduced records.  Field ops (0..2): a, b, c, d are lists of 14-limb records, the result
+    a list of 14-limb records.  Point ops (8..10): a and b are lists of (X, Y, Z) triples of 14-limb records, the result a list
+    of ((X, Y, Z) records, return code)."""
+    n = len(a)
+    field = (op & 15) < 8
+
+    def pack(recs):
+        if recs is None:
+            return None
+        flat = [l for r in recs for l in (r if field else [x for rec in r for x in rec])]
+        assert len(flat) == n * (14 if field else 42)
+        return (C.c_uint32 * len(flat))(*flat)
+
+    out = (C.c_uint32 * (n * (14 if field else 44)))()
+    if field and b is None:
+        b = a
+    check(lib().h2v_probe_f28_dot2(device, op, n, pack(a), pack(b), pack(c), pack(d), out))
+    if field:
+        return [list(out[14 * i:14 * i + 14]) for i in range(n)]
+    return [(tuple(list(out[44 * i + 14 * j:44 * i + 14 * j + 14]) for j in range(3)), int(out[44 * i + 42])) for i in range(n)]
 
 
 def probe_quad_madd(p_xy, q_xy, neg: bool, device: int = 0):

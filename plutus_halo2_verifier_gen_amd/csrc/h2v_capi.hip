@@ -3032,6 +3032,30 @@ extern "C" int h2v_probe_quad_madd(int device, const uint32_t *pq /* 48 dwords *
     HIPCHK(hipMemcpy(out, dout.p, 210 * 4, hipMemcpyDeviceToHost));
     return H2V_OK;
 }
+extern "C" int h2v_probe_f28_dot2(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
+                                  uint32_t *out) {
+    int rc = pick_device(device);
+    if (rc) return rc;
+    const int what = op & 15;
+    const bool field = what <= 2, point = what >= 8 && what <= 10;
+    if ((op & ~(15 | 16 | 64)) != 0 || !(field || point) || (what == 10 && (op & 16)) || n == 0 || !a || !out) return fail(H2V_E_ARG, "bad argument");
+    if (field ? (!b || !c || !d) : (what != 8 && !b)) return fail(H2V_E_ARG, "bad argument");
+    const size_t in_b = (size_t)n * (field ? 14 : 42) * 4, out_b = (size_t)n * (field ? 14 : 44) * 4;
+    DevBuf da, db, dc, dd, dout;
+    if (da.alloc(in_b) || db.alloc(in_b) || dc.alloc(in_b) || dd.alloc(in_b) || dout.alloc(out_b)) return fail(H2V_E_DEVICE, "hipMalloc failed");
+    HIPCHK(hipMemcpy(da.p, a, in_b, hipMemcpyHostToDevice));
+    if (field || what != 8) HIPCHK(hipMemcpy(db.p, b, in_b, hipMemcpyHostToDevice));
+    if (field) {
+        HIPCHK(hipMemcpy(dc.p, c, in_b, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dd.p, d, in_b, hipMemcpyHostToDevice));
+    }
+    hipLaunchKernelGGL(k_probe_f28_dot2, dim3((n + 63) / 64), dim3(64), 0, nullptr, op, n, da.as<uint32_t>(), db.as<uint32_t>(),
+                       dc.as<uint32_t>(), dd.as<uint32_t>(), dout.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, dout.p, out_b, hipMemcpyDeviceToHost));
+    return H2V_OK;
+}
 extern "C" int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint8_t *digests) {
     int rc = pick_device(device);
     if (rc) return rc;

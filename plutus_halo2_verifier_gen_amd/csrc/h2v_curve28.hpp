@@ -7,8 +7,9 @@
 // (aiken-verifier/aiken_halo2/lib/bls_utils.ak:77-86, the Plutus builtins bls12_381_G1_add / scalarMul).
 //
 // Coordinate bounds (v, lam) of every stored point, see h2v_fp28.hpp for the notation:
-//     X (31, 1)   Y (20, 1)   Z (4, 2)           -- closed under g1j28_dbl and g1j28_add (derivations inline);
-//     table entries (never negated in place) have Y (19, 1)
+//     X (31, 1)   Y (20, 1)   Z (4, 2)           -- closed under g1j28_dbl and g1j28_add (derivations inline: the one-lane
+//     formulas return X (19,1) Y (2,1) Z (4,2) or better, the quad-cooperative ones X (31,1) Y (19,1) Z (4,2); Y (20,1) is a
+//     point negated in place, g1j28_acc_add)
 #pragma once
 #include "h2v_curve.hpp"
 #include "h2v_fp28.hpp"
@@ -30,42 +31,47 @@ H2V_DI void g1j28_to_g1j(G1J &r, const G1J28 &p, const bool inf) {
     f28_to_fp(r.y, p.y);
     f28_to_fp(r.z, z);
 }
-// dbl-2009-l, 2M + 5S.  p must not be infinity and must not have y == 0 (no 2-torsion on these curves: the group
-// order is odd).  In: X (<=43, 1), Y (<=45, 1), Z (v_Y v_Z <= 2048, lam <= 2).  Out: X (31,1) Y (19,1) Z (4,2).
+// dbl-2009-l with D = 4 X B taken as a product, 3M + 3S + one merged product: C = B^2 is then needed by
+//     Y3 = E (D - X3) - 8 B^2
+// alone and shares its reduction: -Y3 = 2 (2B)^2 + E (X3 - D) is one f28_dot2_sqr<2> (the square enters with a minus sign, so the
+// NEGATED sum is what the square form can serve).  The sign goes into Z instead of a negation and a carry of Y3: the formula
+// runs on -Y for Z3 alone and returns (X3, -Y3, -Z3), the same point as (X3, Y3, Z3) (Jacobian scaling by lambda = -1).
+// 2 x 392 + 3 x 301 + 497 = 2184 multiply-adds (2289 before), two carries (three before).
+// p must not be infinity and must not have y == 0 (no 2-torsion on these curves: the group order is odd).
+// In: X (<=43, 1), Y (<=20, 1), Z (21 v_Z <= 2048, lam <= 2).  Out: X (19,1) Y (2,1) Z (4,2).
 #define F28_MUL_(r, a, b) do { if (INL) f28_mul_inl(r, a, b); else f28_mul(r, a, b); } while (0)
 #define F28_SQR_(r, a) do { if (INL) f28_sqr_inl(r, a); else f28_sqr(r, a); } while (0)
 template <bool INL>
 H2V_DI void g1j28_dbl_t(G1J28 &r, const G1J28 &p) {
-    F28 X = p.x, Y = p.y, Z = p.z, A, B, C, D, t;
-    F28_MUL_(Z, Y, Z); f28_mul_small<2>(Z, Z);        // Z3 = 2 Y Z                      (4, 2)
+    F28 X = p.x, Y = p.y, Z = p.z, A, B, D, t;
+    F28_NEG(t, Y, 21, 1);                            // -Y                               (21, 3)
+    F28_MUL_(Z, t, Z); f28_mul_small<2>(Z, Z);        // -Z3 = 2 (-Y) Z  lam 6, v 21 v_Z  (4, 2)
     F28_SQR_(A, X);                                   // A = X^2                          (2, 1)
-    F28_SQR_(B, Y);                                   // B = Y^2                          (2, 1)
-    f28_add(t, X, B); F28_SQR_(t, t);                 // (X + B)^2, operand (v_X+2, 2)    (2, 1)
-    F28_SQR_(C, B);                                   // C = B^2                          (2, 1)
-    f28_add(D, A, C);                                //                                  (4, 2)
-    F28_SUB(t, t, D, 5, 2);                          // (X+B)^2 - A - C                  (7, 5)
-    f28_mul_small<2>(D, t); f28_carry(D);            // D                                (14, 1)
+    F28_SQR_(B, Y);                                   // B = Y^2         v 400            (2, 1)
+    F28_MUL_(D, X, B);                                // X B             v 86             (2, 1)
     f28_mul_small<3>(A, A);                          // E = 3A                           (6, 3)
     F28_SQR_(X, A);                                   // E^2   lam 9, v 36                (2, 1)
-    f28_mul_small<2>(t, D);                          // 2D                               (28, 2)
-    F28_SUB(X, X, t, 29, 2); f28_carry(X);           // X3 = E^2 - 2D                    (31, 1)
-    F28_SUB(t, D, X, 32, 1);                         // D - X3                           (46, 4)
-    F28_MUL_(Y, A, t);                                // E (D - X3)  lam 12, v 276        (2, 1)
-    f28_mul_small<8>(C, C);                          // 8C                               (16, 8)
-    F28_SUB(Y, Y, C, 17, 8); f28_carry(Y);           // Y3                               (19, 1)
+    f28_mul_small<8>(t, D);                          // 2D = 8 X B                       (16, 8)
+    F28_SUB(X, X, t, 17, 8); f28_carry(X);           // X3 = E^2 - 2D                    (19, 1)
+    f28_mul_small<4>(D, D);                          // D = 4 X B                        (8, 4)
+    F28_SUB(t, X, D, 9, 4); f28_carry(t);            // X3 - D                           (28, 1)
+    f28_mul_small<2>(B, B);                          // 2B                               (4, 2)
+    if (INL) f28_dot2_sqr_inl<2>(Y, B, A, t);        // -Y3 = 2 (2B)^2 + E (X3 - D)      (2, 1)
+    else f28_dot2_sqr<2>(Y, B, A, t);                //   lam 2 2^2 + 3 1 = 11 <= 17, v 2 4^2 + 6 28 = 200 <= 2048
     r.x = X; r.y = Y; r.z = Z;
 }
 #undef F28_MUL_
 #undef F28_SQR_
 H2V_DI void g1j28_dbl(G1J28 &r, const G1J28 &p) { g1j28_dbl_t<false>(r, p); }
-// r = p + (neg_q ? -q : q), 12M + 4S; neither operand is infinity (the callers keep the flags).
+// r = p + (neg_q ? -q : q), 10M + 4S + one merged product; neither operand is infinity (the callers keep the flags).
 // Returns 0: generic sum in r; 1: p == +-q with equal y -> r = 2p; 2: p == -(+-q) -> the sum is infinity (r untouched).
-// In: both operands with the stored-point bounds.  Out: X (10,1) Y (5,1) Z (2,1).
+// The signs are arranged so that no product is subtracted (see g1j28_madd_ladder_t): -R, -HH, -HHH, -V.
+// In: both operands with the stored-point bounds.  Out: X (8,1) Y (2,1) Z (2,1).
 H2V_DI int g1j28_add(G1J28 &r, const G1J28 &p, const G1J28 &q, const bool neg_q) {
     F28 X1 = p.x, Y1 = p.y, Z1 = p.z, a, b, c, t;
     f28_sqr(a, q.z);                                 // Z2^2       lam 4, v 16           (2, 1)
     f28_mul(X1, X1, a);                              // U1         v 62                  (2, 1)
-    f28_mul(t, q.z, a); f28_mul(Y1, Y1, t);          // S1         v 8 ; 38              (2, 1)
+    f28_mul(t, q.z, a); f28_mul(Y1, Y1, t);          // S1         v 8 ; 40              (2, 1)
     f28_sqr(a, Z1);                                  // Z1^2                             (2, 1)
     f28_mul(b, q.x, a);                              // U2                               (2, 1)
     f28_mul(t, Z1, a);                               // Z1^3                             (2, 1)
@@ -76,31 +82,34 @@ H2V_DI int g1j28_add(G1J28 &r, const G1J28 &p, const G1J28 &q, const bool neg_q)
         f28_mul(c, qy, t);                           // S2         lam 3, v 40           (2, 1)
     }
     F28_SUB(b, b, X1, 3, 1); f28_carry(b);           // H = U2 - U1                      (5, 1)
-    F28_SUB(c, c, Y1, 3, 1); f28_carry(c);           // R = S2 - S1                      (5, 1)
+    F28_SUB(c, Y1, c, 3, 1); f28_carry(c);           // -R = S1 - S2                     (5, 1)
     if (f28_is_zero_v5(b)) {
         if (f28_is_zero_v5(c)) { g1j28_dbl(r, p); return 1; }
         return 2;
     }
     f28_mul(Z1, Z1, q.z); f28_mul(Z1, Z1, b);        // Z3         lam 4, v 16 ; v 10    (2, 1)
     f28_sqr(a, b);                                   // HH                               (2, 1)
-    f28_mul(b, b, a);                                // HHH                              (2, 1)
-    f28_mul(a, X1, a);                               // V = U1 HH                        (2, 1)
+    F28_NEG(t, a, 3, 1);                             // -HH                              (3, 3)
+    f28_mul(b, b, t);                                // -HHH       lam 3, v 15           (2, 1)
+    f28_mul(a, X1, t);                               // -V = -U1 HH  lam 3, v 6          (2, 1)
     f28_sqr(X1, c);                                  // R^2                              (2, 1)
-    F28_SUB(X1, X1, b, 3, 1);                        // R^2 - HHH                        (5, 4)
-    f28_mul_small<2>(t, a);                          // 2V                               (4, 2)
-    F28_SUB(X1, X1, t, 5, 2); f28_carry(X1);         // X3                               (10, 1)
-    F28_SUB(t, a, X1, 11, 1);                        // V - X3                           (13, 4)
-    f28_mul(c, c, t);                                // R (V - X3)   lam 4, v 65         (2, 1)
-    f28_mul(t, Y1, b);                               // S1 HHH                           (2, 1)
-    F28_SUB(Y1, c, t, 3, 1); f28_carry(Y1);          // Y3                               (5, 1)
-    r.x = X1; r.y = Y1; r.z = Z1;
+    f28_add(X1, X1, b);                              // R^2 - HHH                        (4, 2)
+    f28_mul_small<2>(t, a);                          // -2V                              (4, 2)
+    f28_add(X1, X1, t); f28_carry(X1);               // X3 = R^2 - HHH - 2V              (8, 1)
+    f28_add(t, a, X1);                               // -(V - X3)                        (10, 2)
+    f28_dot2(Y1, c, t, Y1, b);                       // Y3 = (-R) (X3 - V) + S1 (-HHH)   (2, 1)
+    r.x = X1; r.y = Y1; r.z = Z1;                    //   lam 1 2 + 1 1 = 3, v 5 10 + 2 2 = 54
     return 0;
 }
-// Mixed addition r = p + (neg_q ? -q : q) with q AFFINE (qx, qy carried, v <= 2): 8M + 3S.  NO exceptional cases:
+// Mixed addition r = p + (neg_q ? -q : q) with q AFFINE (qx, qy carried, v <= 2): 6M + 3S + one merged product.  NO exceptional cases:
 // the caller guarantees p != +-q and both finite.  That holds in the MSM ladder by construction - p = [a]P with
 // a = 16 * (a non-zero prefix of a scalar below 2^128), q = [d]P with 1 <= d <= 8, and P of prime order r > 2^254, so
 // a +- d is never 0 mod r - and nowhere else is this function used.
-// In: p with the stored-point bounds.  Out: X (10,1) Y (5,1) Z (2,1).
+// Y3 = R (V - X3) - Y1 HHH is ONE merged product (f28_dot2), and no product is subtracted anywhere: the formula carries
+// -R = Y1 - S2 (R enters as R^2 and as a factor of Y3 only), -HH (one limb-wise negation), hence -HHH = H (-HH) and
+// -V = X1 (-HH), so that X3 = R^2 + (-HHH) + 2 (-V) and Y3 = (-R) ((-V) + X3) + Y1 (-HHH) are plain sums - no bias tables, one
+// carry (two before).  6 x 392 + 3 x 301 + 588 = 3843 multiply-adds (4039 before).
+// In: p with the stored-point bounds.  Out: X (8,1) Y (2,1) Z (2,1).
 #define F28_MUL_(r, a, b) do { if (INL) f28_mul_inl(r, a, b); else f28_mul(r, a, b); } while (0)
 #define F28_SQR_(r, a) do { if (INL) f28_sqr_inl(r, a); else f28_sqr(r, a); } while (0)
 template <bool INL>
@@ -116,19 +125,19 @@ H2V_DI void g1j28_madd_ladder_t(G1J28 &r, const G1J28 &p, const F28 &qx, const F
         F28_MUL_(c, qy, t);                           // S2          lam 3, v 6           (2, 1)
     }
     F28_SUB(b, b, X1, 32, 1);                        // H = U2 - X1                      (34, 4)
-    F28_SUB(c, c, Y1, 21, 1);                        // R = S2 - Y1                      (23, 4)
+    F28_SUB(c, Y1, c, 3, 1);                         // -R = Y1 - S2                     (23, 4)
     F28_MUL_(Z1, Z1, b);                              // Z3 = Z1 H   lam 8, v 136         (2, 1)
     F28_SQR_(a, b);                                   // HH          lam 16, v 1156       (2, 1)
-    F28_MUL_(b, b, a);                                // HHH         lam 4, v 68          (2, 1)
-    F28_MUL_(a, X1, a);                               // V = X1 HH   v 62                 (2, 1)
+    F28_NEG(t, a, 3, 1);                             // -HH                              (3, 3)
+    F28_MUL_(b, b, t);                                // -HHH        lam 12, v 102        (2, 1)
+    F28_MUL_(a, X1, t);                               // -V = -X1 HH lam 3, v 93          (2, 1)
     F28_SQR_(X1, c);                                  // R^2         lam 16, v 529        (2, 1)
-    F28_SUB(X1, X1, b, 3, 1);                        // R^2 - HHH                        (5, 4)
-    f28_mul_small<2>(t, a);                          // 2V                               (4, 2)
-    F28_SUB(X1, X1, t, 5, 2); f28_carry(X1);         // X3                               (10, 1)
-    F28_SUB(t, a, X1, 11, 1);                        // V - X3                           (13, 4)
-    F28_MUL_(c, c, t);                                // R (V - X3)  lam 16, v 299        (2, 1)
-    F28_MUL_(t, Y1, b);                               // Y1 HHH      v 40                 (2, 1)
-    F28_SUB(Y1, c, t, 3, 1); f28_carry(Y1);          // Y3                               (5, 1)
+    f28_add(X1, X1, b);                              // R^2 - HHH                        (4, 2)
+    f28_mul_small<2>(t, a);                          // -2V                              (4, 2)
+    f28_add(X1, X1, t); f28_carry(X1);               // X3 = R^2 - HHH - 2V              (8, 1)
+    f28_add(t, a, X1);                               // -(V - X3)                        (10, 2)
+    if (INL) f28_dot2_inl(Y1, c, t, Y1, b);          // Y3 = (-R) (X3 - V) + Y1 (-HHH)   (2, 1)
+    else f28_dot2(Y1, c, t, Y1, b);                  //   lam 4 2 + 1 1 = 9 <= 17, v 23 10 + 20 2 = 270 <= 2048
     r.x = X1; r.y = Y1; r.z = Z1;
 }
 #undef F28_MUL_

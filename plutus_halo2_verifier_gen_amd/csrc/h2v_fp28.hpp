@@ -10,6 +10,16 @@
 //   an element is described by (v, lam):  value < v*p  and every limb < lam * 2^28  (top limb: whatever v implies)
 //   * f28_mul / f28_sqr need lam_a * lam_b <= 17 (14 products + 14 reduction terms per 64-bit column) and
 //     v_a * v_b <= 2048 = R/p-ish (R = 2^392), and return (2, 1)
+//   * f28_dot2(a, b, c, d) = a b + c d with ONE reduction (fp_mont28_dot2: both products enter the rolling column before the
+//     m[k] step).  A column holds at most 14 products a_i b_j, 14 products c_i d_j and 14 reduction terms m_i p_j, so
+//     14 (lam_a lam_b + lam_c lam_d) 2^56 + 14 2^56 + carry-in (< 2^36) < 2^64 needs  lam_a lam_b + lam_c lam_d <= 17
+//     (17: 252 2^56 + 2^36 < 2^64; 18 would reach 266 2^56).  The value is (a b + c d + m p) / R with m < R and
+//     p / R < 2^-11, so  v_a v_b + v_c v_d <= 2048  gives < p + p = 2p: the result is (2, 1) like a single product's.
+//     f28_dot2_sqr<W>(a, c, d) = W a^2 + c d, W = 1 or 2, takes the square's off-diagonal terms once against 2 W a as f28_sqr
+//     does (2 W lam_a <= 15 so that the scaled limbs stay 32-bit):  W lam_a^2 + lam_c lam_d <= 17,  W v_a^2 + v_c v_d <= 2048.
+//     588 (497) multiply-adds instead of 784 (693) for two reduced products.  A difference a b - c d is written as a sum with one
+//     operand negated (F28_NEG) - or, where the formula allows, with the sign moved into a product that is computed anyway.
+//     (tests/test_field_dot2.py replays the loop limb for limb on operands at these bounds and asserts the 2^64 column bound.)
 //   * f28_add: (v_a + v_b, lam_a + lam_b);  f28_mul_small(k): (k v, k lam);  lam must stay <= 15 (32-bit limbs)
 //   * f28_sub<K, M>(a, b) = a + (K p spread so that every limb >= M 2^28) - b needs v_b <= K - 1, lam_b <= M and
 //     returns (v_a + K, lam_a + M + 2)
@@ -61,6 +71,40 @@ H2V_DI void f28_sqr(F28 &r, const F28 &a) {
     const F28Regs z = f28_sqr_raw(x.a, x.b, x.c, x.d);
     r = f28_unpack(z.a, z.b, z.c, z.d);
 }
+// a b + c d / W a^2 + c d with one reduction, out of line.  The device ABI has 32 argument VGPRs: of the 56 (42) operand dwords
+// the first 32 travel in registers, the other 24 (10) through the caller's outgoing-argument area - plain scratch stores and
+// loads the compiler writes, 48 memory instructions against the 196 multiply-adds of the reduction they save (and 104 bytes of
+// private segment in every kernel that reaches one).  A register-only form like f28_mul_raw's does not exist for four operands;
+// the hot loops use the inlined forms below, these serve the complete addition and the table builders.
+H2V_DN F28Regs f28_dot2_raw(u32x4 a0, u32x4 a1, u32x4 a2, u32x2 a3, u32x4 b0, u32x4 b1, u32x4 b2, u32x2 b3,
+                            u32x4 c0, u32x4 c1, u32x4 c2, u32x2 c3, u32x4 d0, u32x4 d1, u32x4 d2, u32x2 d3) {
+    const F28 a = f28_unpack(a0, a1, a2, a3), b = f28_unpack(b0, b1, b2, b3), c = f28_unpack(c0, c1, c2, c3), d = f28_unpack(d0, d1, d2, d3);
+    F28 t;
+    fp_mont28_dot2(t.l, a.l, b.l, c.l, d.l);
+    return f28_pack(t);
+}
+H2V_DI void f28_dot2(F28 &r, const F28 &a, const F28 &b, const F28 &c, const F28 &d) {
+    const F28Regs x = f28_pack(a), y = f28_pack(b), u = f28_pack(c), v = f28_pack(d);
+    const F28Regs z = f28_dot2_raw(x.a, x.b, x.c, x.d, y.a, y.b, y.c, y.d, u.a, u.b, u.c, u.d, v.a, v.b, v.c, v.d);
+    r = f28_unpack(z.a, z.b, z.c, z.d);
+}
+template <int W>
+H2V_DN F28Regs f28_dot2_sqr_raw(u32x4 a0, u32x4 a1, u32x4 a2, u32x2 a3, u32x4 c0, u32x4 c1, u32x4 c2, u32x2 c3,
+                                u32x4 d0, u32x4 d1, u32x4 d2, u32x2 d3) {
+    const F28 a = f28_unpack(a0, a1, a2, a3), c = f28_unpack(c0, c1, c2, c3), d = f28_unpack(d0, d1, d2, d3);
+    F28 t;
+    fp_mont28_dot2_sqr<W>(t.l, a.l, c.l, d.l);
+    return f28_pack(t);
+}
+template <int W>
+H2V_DI void f28_dot2_sqr(F28 &r, const F28 &a, const F28 &c, const F28 &d) {
+    const F28Regs x = f28_pack(a), u = f28_pack(c), v = f28_pack(d);
+    const F28Regs z = f28_dot2_sqr_raw<W>(x.a, x.b, x.c, x.d, u.a, u.b, u.c, u.d, v.a, v.b, v.c, v.d);
+    r = f28_unpack(z.a, z.b, z.c, z.d);
+}
+H2V_DI void f28_dot2_inl(F28 &r, const F28 &a, const F28 &b, const F28 &c, const F28 &d) { F28 t; fp_mont28_dot2(t.l, a.l, b.l, c.l, d.l); r = t; }
+template <int W>
+H2V_DI void f28_dot2_sqr_inl(F28 &r, const F28 &a, const F28 &c, const F28 &d) { F28 t; fp_mont28_dot2_sqr<W>(t.l, a.l, c.l, d.l); r = t; }
 // inlined forms (no call, no argument marshalling) for the one loop that is short enough to afford the code size
 H2V_DI void f28_mul_inl(F28 &r, const F28 &a, const F28 &b) { F28 t; fp_mont28(t.l, a.l, b.l); r = t; }
 H2V_DI void f28_sqr_inl(F28 &r, const F28 &a) { F28 t; fp_montsqr28(t.l, a.l); r = t; }

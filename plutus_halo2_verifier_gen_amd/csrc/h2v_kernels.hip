@@ -1604,6 +1604,47 @@ k_probe_quad_madd(const uint32_t *__restrict__ pq, int neg, uint32_t *__restrict
     if (l < 4)
         for (int k = 0; k < 14; k++) { out[42 * (1 + l) + k] = b.x.l[k]; out[42 * (1 + l) + 14 + k] = b.y.l[k]; out[42 * (1 + l) + 28 + k] = b.z.l[k]; }
 }
+// dev probe of the merged products and of the three one-lane group formulas built on them, on RAW lazily reduced records (14
+// limbs of 28 bits that may be uncarried: the bounds of h2v_fp28.hpp are the caller's to respect - or to sit on).
+//   op & 15:  0: a b + c d   1: a^2 + c d   2: 2 a^2 + c d          (records of 14 dwords in a, b, c, d; out: 14 dwords)
+//             8: 2P          9: P + Q, Q affine (mixed)   10: P + Q  (P = 42 dwords X, Y, Z in a, Q likewise in b; out: 44 dwords:
+//                                                                     X, Y, Z, the return code of g1j28_add, 0)
+//   op & 16:  the inlined multiplier forms (ops 0..9)      op & 64: subtract Q (ops 9, 10)
+extern "C" __global__ void __launch_bounds__(64)
+k_probe_f28_dot2(int op, uint32_t n, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ c,
+                 const uint32_t *__restrict__ d, uint32_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const int what = op & 15;
+    const bool inl = (op & 16) != 0, neg = (op & 64) != 0;
+    if (what < 8) {
+        F28 x, y, u, v, r;
+#pragma unroll
+        for (int k = 0; k < 14; k++) { x.l[k] = a[(size_t)i * 14 + k]; y.l[k] = b[(size_t)i * 14 + k]; u.l[k] = c[(size_t)i * 14 + k]; v.l[k] = d[(size_t)i * 14 + k]; }
+        if (what == 0) { if (inl) f28_dot2_inl(r, x, y, u, v); else f28_dot2(r, x, y, u, v); }
+        else if (what == 1) { if (inl) f28_dot2_sqr_inl<1>(r, x, u, v); else f28_dot2_sqr<1>(r, x, u, v); }
+        else { if (inl) f28_dot2_sqr_inl<2>(r, x, u, v); else f28_dot2_sqr<2>(r, x, u, v); }
+#pragma unroll
+        for (int k = 0; k < 14; k++) out[(size_t)i * 14 + k] = r.l[k];
+        return;
+    }
+    G1J28 P, Q, r;
+#pragma unroll
+    for (int k = 0; k < 14; k++) {
+        P.x.l[k] = a[(size_t)i * 42 + k]; P.y.l[k] = a[(size_t)i * 42 + 14 + k]; P.z.l[k] = a[(size_t)i * 42 + 28 + k];
+        Q.x.l[k] = what == 8 ? 0u : b[(size_t)i * 42 + k]; Q.y.l[k] = what == 8 ? 0u : b[(size_t)i * 42 + 14 + k];
+        Q.z.l[k] = what == 8 ? 0u : b[(size_t)i * 42 + 28 + k];
+    }
+    r = P;
+    int rc = 0;
+    if (what == 8) { if (inl) g1j28_dbl_t<true>(r, P); else g1j28_dbl_t<false>(r, P); }
+    else if (what == 9) { if (inl) g1j28_madd_ladder_t<true>(r, P, Q.x, Q.y, neg); else g1j28_madd_ladder_t<false>(r, P, Q.x, Q.y, neg); }
+    else rc = g1j28_add(r, P, Q, neg);
+#pragma unroll
+    for (int k = 0; k < 14; k++) { out[(size_t)i * 44 + k] = r.x.l[k]; out[(size_t)i * 44 + 14 + k] = r.y.l[k]; out[(size_t)i * 44 + 28 + k] = r.z.l[k]; }
+    out[(size_t)i * 44 + 42] = (uint32_t)rc;
+    out[(size_t)i * 44 + 43] = 0u;
+}
 // blake2b-256 of n messages of `len` bytes each through the LDS transcript path (one message per lane)
 extern "C" __global__ void __launch_bounds__(64)
 k_probe_blake2b(uint32_t n, uint32_t len, const uint8_t *__restrict__ msgs, uint32_t *__restrict__ out) {

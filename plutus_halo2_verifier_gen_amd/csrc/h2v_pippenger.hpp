@@ -20,7 +20,7 @@
 //                     lanes ran 3 ms chains beside 0.3 ms ones); empty buckets get no lane
 //   k_pip_scatter     one lane per term: (term, half, sign) into its bucket's slice of the entry list
 //   k_pip_accumulate  THE bulk kernel: buckets in descending size, 2^k neighbouring lanes per bucket of class k (a block
-//                     holds one class); each lane sums its slice with mixed additions (8M + 3S, affine base read once per
+//                     holds one class); each lane sums its slice with mixed additions (6M + 3S + one merged product, affine base read once per
 //                     use as 2 x 56 bytes), the 2^k partial sums meet in an LDS tree.  Exceptional additions (equal /
 //                     opposite points, which adversarial or merely repeated proof points can produce) zero the running Z:
 //                     detected ONCE at the end of the chain, and that chain is then redone with the complete addition
