@@ -230,7 +230,11 @@ int h2v_workspace_depth(const h2v_workspace *ws, uint64_t n, int rlc, uint32_t *
  * of chunks of the call - unless this function was called: then the given value holds. */
 int h2v_workspace_hint_in_flight(h2v_workspace *ws, uint32_t n_in_flight);
 /* Per-kernel device times of a past call that used `ws` (calls_back = 0: the most recent; up to 63 back), from HIP
- * events recorded on the streams the kernels ran on.  Synchronise the launch stream before asking. */
+ * events recorded on the streams the kernels ran on.  Synchronise the launch stream before asking.  EVERY call on a workspace
+ * takes one record - verify, prepare, check and RLC calls alike, on ordinary and laned workspaces - and calls_back counts them
+ * all.  H2V_E_ARG: no such record (64 or more back; on a laned workspace also when a lane has made 64 calls since, "rings have
+ * wrapped"), an RLC call that ran its batch check (h2v_workspace_rlc_result has its times; a call routed to the per-proof
+ * kernels has its per-proof times here), or a coalesced call whose group has not run yet. */
 int h2v_workspace_timings(h2v_workspace *ws, uint32_t calls_back, h2v_timings *out);
 
 /* ---- verification (replaces prepare + Guard::verify / DualMSM::check) --------------------------------------
@@ -295,7 +299,10 @@ int h2v_verify_batch_rlc(const h2v_plan *plan, const h2v_batch *batch, uint8_t *
                          const h2v_rlc_opts *opts /* or NULL */, int *fell_back /* or NULL: 1 = the per-proof kernels ran */);
 int h2v_verify_batch_rlc_device(const h2v_plan *plan, const h2v_batch *batch, uint8_t *accept, uint32_t *status,
                                 h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts /* or NULL */);
-/* after synchronising the stream of an RLC call: the batch verdict (1 = passed) and the kernel times of that call */
+/* after synchronising the stream of an RLC call: the batch verdict (1 = passed) and the kernel times of that call.  calls_back
+ * counts the workspace's records as h2v_workspace_timings does (every call takes one; up to 63 back).  A call routed to the
+ * per-proof kernels reports (0, zeros).  H2V_E_ARG: no such record or a lane's ring has wrapped since (as there), a call that
+ * was not an RLC call, or a coalesced call whose group has not run yet. */
 int h2v_workspace_rlc_result(h2v_workspace *ws, uint32_t calls_back, uint32_t *batch_accepted, h2v_rlc_timings *timings);
 
 /* ---- prepare and pair check (the two halves of verification: the reference's `prepare` -> DualMSM -> `check`) -----------

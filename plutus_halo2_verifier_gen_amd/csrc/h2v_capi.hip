@@ -151,13 +151,31 @@ struct h2v_workspace {
     // decompression beside it on pside
     hipStream_t pmain = nullptr, pside = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_hold = nullptr, ev_fix = nullptr, ev_done = nullptr;
-    // ring of per-call event sets: [0]/[1] around the transcript+combiner kernel, [2]/[3] around the decompression kernel
-    // (side stream), [4]/[5] around the MSM, [5]/[6] around the pairing kernel, [7]/[8] around the fixed-base MSM launch of a
-    // split MSM, [9] the end of the ladder launch beside it; [10]/[11] mark the MSM's hold (run_pipeline) and are not read
-    static constexpr int RING = 64, NEV = 12;
-    hipEvent_t ring[RING][NEV] = {};
-    uint8_t ring_lpt[RING] = {}, ring_pair[RING] = {}, ring_var[RING] = {};
+    // ONE record per call of any kind, in a ring: call number k (absolute, counted from 0) is rec[k % RING] until call k + RING
+    // takes the slot, so a lookup compares the record's own number with the one it wants (rec_at)
+    static constexpr int RING = 64, NEV = 12, MAXL = 16;
+    enum Kind : uint8_t { VERIFY, PREPARE, CHECK, RLC };
+    struct CallRec {
+        uint64_t call = ~0ull;
+        Kind kind = VERIFY;
+        bool routed = false;       // an RLC call sent straight to the per-proof kernels (rlc_route): per-proof times, no batch check
+        bool co = false, ran = false;   // coalesced (coalesce_call); its group has run - only then is the rest filled in (co_flush_lane)
+        float share = 0.0f;        // coalesced: its proofs / the group's
+        // ordinary workspace: the event set, created with the workspace.  Per proof (run_pipeline; run_check a subset):
+        // [0]/[1] around the transcript+combiner kernel, [2]/[3] around the decompression kernel (side stream), [4]/[5] around
+        // the MSM, [5]/[6] around the pairing kernel, [7]/[8] around the fixed-base MSM launch of a split MSM, [9] the end of the
+        // ladder launch beside it, [10]/[11] mark the MSM's hold and are not read.  RLC: run_rlc's eleven.
+        hipEvent_t ev[NEV] = {};
+        uint8_t lpt = 0, var_lpt = 0, pair = 0;   // MSM lanes per term (3: split), the ladder half of a split MSM, pairing lanes (0: none ran)
+        uint32_t rlc_terms = 0, rlc_c = 0, rlc_W = 0, rlc_chain = 0;   // RLC: the bucket MSM's terms, window bits, windows, chain
+        // laned workspace: chunk c ran on lane (first + c) % mod as that lane's record start[lane] + c / mod (a coalesced call:
+        // one "chunk", its group's run)
+        uint32_t first = 0, mod = 1, chunks = 0;
+        uint64_t start[MAXL] = {};
+    };
+    CallRec rec[RING];
     uint64_t calls = 0;
+    uint32_t *rec_fail = nullptr;   // RING device words: failed batch checks of record k at [k % RING] (RLC calls; rlc_stats_ensure)
     struct RlcWs *rlc = nullptr;   // buffers of the RLC batch mode, created by its first call
     std::vector<struct RlcWs *> rlc_parked;   // the same for OTHER plans this workspace has served in that mode (rlc_ensure swaps; never freed before the workspace)
     int32_t opt[H2V_OPT_COUNT] = {};   // h2v_workspace_set_option / h2v_workspace_tune: 0 = the launcher's choice
@@ -165,7 +183,6 @@ struct h2v_workspace {
     // ---- lanes (h2v_workspace_create_lanes): a laned workspace owns no kernel buffers of its own, only n_lanes ordinary
     // workspaces of `chunk` proofs and one library-owned stream per lane.  A verify call is cut into chunks that go round
     // robin through the lanes; chunk c of a call runs entirely on lane_st[lane of c], behind that lane's earlier chunks.
-    static constexpr int MAXL = 16;
     uint32_t n_lanes = 0, chunk = 0;
     h2v_workspace *lane[MAXL] = {};
     hipStream_t lane_st[MAXL] = {};
@@ -181,7 +198,7 @@ struct h2v_workspace {
         uint8_t *in_block = nullptr, *h_block = nullptr, *h_accept = nullptr, *d_accept = nullptr;
         size_t in_cap = 0, acc_cap = 0;
         hipEvent_t ev = nullptr;
-        uint64_t n = 0, call = 0;
+        uint64_t n = 0;
         bool rlc = false;
     };
     static constexpr int MAXH = 16;
@@ -189,29 +206,35 @@ struct h2v_workspace {
     uint64_t h_head = 0, h_tail = 0;
     hipStream_t hs_down = nullptr;
     bool copy_streams_owned = false;        // laned: hs / hs_down carry copies only and are plain streams of this workspace (host_stream)
-    uint32_t *rlc_fail = nullptr;           // RING counters: failed batch checks among the chunks of a call (RLC mode)
-    uint32_t *rlc_fail_ptr = nullptr;       // (a lane: where its batch check reports a failure; set by the parent per call)
     // routing of RLC calls by what earlier calls met (rlc_route): cumulative device counters [groups seen, groups failed], a
     // pinned host mirror refreshed behind every call, and the running estimate of the failing-group rate
     uint32_t *rlc_stats = nullptr, *rlc_stats_ptr = nullptr, *h_rlc_stats = nullptr;
     uint32_t seen_groups = 0, seen_failed = 0;
     float fail_rate = 0.0f;
     bool routed = false;                    // the most recent RLC call ran the per-proof kernels directly
-    uint8_t lring_routed[64] = {};          // (per call slot)
-    // per call (ring): number of chunks, first lane, and every lane's call counters when the call had been enqueued -
-    // what h2v_workspace_timings / _rlc_result need to find the chunks' event sets in the lanes' own rings
-    uint32_t lring_chunks[RING] = {}, lring_first[RING] = {}, lring_mod[RING] = {};
-    uint64_t lring_calls[RING][MAXL] = {}, lring_rlc_calls[RING][MAXL] = {};
-    const struct RlcWs *lring_rlc_obj[RING][MAXL] = {};   // (whose counter lring_rlc_calls holds: a lane serves one plan's RLC buffers at a time)
-    uint8_t lring_rlc[RING] = {};
     // ---- coalescing of small device-resident calls (coalesce_call): per lane a staging area the proofs of several calls are
-    // gathered into; co_open: the lanes whose groups are open, oldest first (one group per plan and mode, at most four); per call
-    // slot: coalesced?, its share of the group
+    // gathered into; co_open: the lanes whose groups are open, oldest first (one group per plan and mode, at most four)
     struct Coalesce *co[MAXL] = {};
     std::vector<uint32_t> co_open;
-    uint8_t lring_co[RING] = {};
-    float lring_share[RING] = {};
 };
+using CallRec = h2v_workspace::CallRec;
+// the record of the call being made on w (every call takes exactly one), and the record of call number `call` while no later
+// call has taken its slot (NULL once one has)
+static CallRec &rec_new(h2v_workspace *w, h2v_workspace::Kind kind) {
+    CallRec &r = w->rec[w->calls % h2v_workspace::RING];
+    CallRec fresh;
+    memcpy(fresh.ev, r.ev, sizeof fresh.ev);   // (the event set belongs to the slot)
+    r = fresh;
+    r.call = w->calls++;
+    r.kind = kind;
+    return r;
+}
+static CallRec *rec_at(h2v_workspace *w, uint64_t call) {
+    CallRec &r = w->rec[call % h2v_workspace::RING];
+    return r.call == call ? &r : nullptr;
+}
+static CallRec &rec_last(h2v_workspace *w) { return w->rec[(w->calls - 1) % h2v_workspace::RING]; }
+static uint32_t *rec_word(h2v_workspace *w, const CallRec &r) { return w->rec_fail + r.call % h2v_workspace::RING; }
 
 // LDS left for the combiner's register file in a block: 160 KB minus the 8 KB hash buffer and 1 KB of slack
 // (plan.py: VM_LDS_BYTES)
@@ -526,7 +549,7 @@ static void ws_release(h2v_workspace *w) {
     for (struct RlcWs *r : w->rlc_parked) rlc_release(r);
     w->rlc_parked.clear();
     if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
-    void *ptrs[] = {w->rlc_stats, w->rlc_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
+    void *ptrs[] = {w->rlc_stats, w->rec_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
                     w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts, w->hp_buf};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
@@ -537,7 +560,7 @@ static void ws_release(h2v_workspace *w) {
     }
     for (hipStream_t q : {w->pmain, w->pside}) if (q) (void)hipStreamSynchronize(q);
     for (hipEvent_t e : {w->ev_fork, w->ev_join, w->ev_hold, w->ev_fix, w->ev_done}) if (e) (void)hipEventDestroy(e);
-    for (auto &set : w->ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
+    for (CallRec &r : w->rec) for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
 }
 static uint32_t vm_lds_slots(const H2vDevPlan &d);
 static uint32_t msm_max_segments(uint32_t T);
@@ -585,7 +608,7 @@ static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bo
     bool ok = true;
     for (hipEvent_t *e : {&w->ev_fork, &w->ev_join, &w->ev_hold, &w->ev_fix, &w->ev_done})
         if (ok) ok = hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-    for (auto &set : w->ring) for (hipEvent_t &e : set)
+    for (CallRec &r : w->rec) for (hipEvent_t &e : r.ev)
         if (ok) ok = hipEventCreate(&e) == hipSuccess;
     if (!ok) { ws_release(w); delete w; return fail(H2V_E_DEVICE, "stream/event creation failed"); }
     *out = w;
@@ -651,8 +674,7 @@ static int create_lanes_for(const H2vDevPlan &d, int device, uint64_t max_batch,
     w->lanes_per_proof = n_lanes ? n_lanes : H2V_PER_PROOF_LANES;     // an explicit lane count holds for both modes
     w->n_lanes = n_lanes ? n_lanes : H2V_DEFAULT_LANES;
     w->in_flight_hint = w->n_lanes;
-    bool ok = hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming) == hipSuccess && hipMalloc((void **)&w->accept, (size_t)max_batch) == hipSuccess &&
-              hipMalloc((void **)&w->rlc_fail, h2v_workspace::RING * 4) == hipSuccess && hipMemset(w->rlc_fail, 0, h2v_workspace::RING * 4) == hipSuccess;
+    bool ok = hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming) == hipSuccess && hipMalloc((void **)&w->accept, (size_t)max_batch) == hipSuccess;
     // the first lane now (an allocation failure surfaces here, not in the middle of a verify call); the others on first use
     if (ok) ok = ensure_lane(w, 0) == H2V_OK;
     if (!ok) { const std::string e = g_err; ws_release(w); delete w; return fail(H2V_E_DEVICE, "lane creation failed: " + e); }
@@ -1374,9 +1396,8 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     if (!one_stream)
         if (int rcs = ws_streams(w, !two_stream, true)) return rcs;
     hipStream_t pm = (one_stream || two_stream) ? st : w->pmain, ps = one_stream ? st : w->pside;
-    const int slot = (int)(w->calls % h2v_workspace::RING);
-    hipEvent_t *ev = w->ring[slot];
-    w->calls++;
+    CallRec &rec = rec_new(w, pairs_out ? h2v_workspace::PREPARE : h2v_workspace::VERIFY);
+    hipEvent_t *ev = rec.ev;
     HIPCHK(hipEventRecord(w->ev_fork, st));
     HIPCHK(hipStreamWaitEvent(pm, w->ev_fork, 0));
     HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
@@ -1431,13 +1452,13 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
         else var_code = launch_msm_ladders(d, mv, n, split.var, w->scalars, w->pts, nullptr, pm, seg);
         if (!var_code) return fail(H2V_E_LIMIT, "internal: no MSM launch shape for the per-proof terms");
         HIPCHK(hipEventRecord(ev[9], pm));
-        w->ring_var[slot] = (uint8_t)var_code;
+        rec.var_lpt = (uint8_t)var_code;
         HIPCHK(hipStreamWaitEvent(pm, w->ev_fix, 0));
         hipLaunchKernelGGL(k_g1_sum_pairs, dim3((n + 63) / 64), dim3(64), 0, pm, n, w->er, w->er_fix);
-        w->ring_lpt[slot] = 3;
+        rec.lpt = 3;
     } else {
-        w->ring_lpt[slot] = (uint8_t)launch_msm(d, n, w->scalars, w->pts, w->pt_tab, w->er, w->accl, w->accr, pm, w->in_flight_hint, seg);
-        if (!w->ring_lpt[slot]) return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
+        rec.lpt = (uint8_t)launch_msm(d, n, w->scalars, w->pts, w->pt_tab, w->er, w->accl, w->accr, pm, w->in_flight_hint, seg);
+        if (!rec.lpt) return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
     }
     if (int rcd = stage_done("k_g1_msm")) return rcd;
     const uint32_t *er_in = w->er, *el_in = nullptr;
@@ -1448,12 +1469,10 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
         if (int rcd = stage_done("k_ivc_challenge + fold MSM")) return rcd;
     }
     HIPCHK(hipEventRecord(ev[5], pm));
-    if (pairs_out) {   // (ring_pair 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
+    if (pairs_out)   // (rec.pair stays 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
         hipLaunchKernelGGL(k_prepare_export, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, pairs_out);
-        w->ring_pair[slot] = 0;
-    } else {
-        w->ring_pair[slot] = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
-    }
+    else
+        rec.pair = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
     HIPCHK(hipEventRecord(ev[6], pm));
     HIPCHK(hipEventRecord(w->ev_done, pm));
     HIPCHK(hipStreamWaitEvent(st, w->ev_done, 0));
@@ -1471,7 +1490,7 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
 // Pair check: n records of 96 bytes compress(L) || compress(R) are decoded as two-slot "proofs" of a view of the plan (its
 // line tables of s_g2 and G2, proof_len 96, slots at bytes 0 and 48) by the pipeline's decompression launch - flags, canonical
 // x, on the curve, in G1, infinity allowed - into the workspace's point buffers; R goes to Jacobian form (k_pairs_to_jac) and
-// the production pairing launcher checks e(L, s_g2) == e(R, G2).  Everything on `st`.  Events as run_pipeline's ring:
+// the production pairing launcher checks e(L, s_g2) == e(R, G2).  Everything on `st`.  Events as run_pipeline's:
 // [2]/[3] around the decompression, [4]/[5] around the conversion, [5]/[6] around the pairing.
 static int pair_view_ensure(h2v_workspace *w) {
     if (w->pair_off) return H2V_OK;
@@ -1493,9 +1512,8 @@ static int run_check(const H2vDevPlan &d, uint32_t n, const uint8_t *pairs, uint
     if (int rc = pair_view_ensure(w)) return rc;
     H2vDevPlan v = d;
     v.proof_len = 96; v.n_points = 2; v.n_ci = 0; v.n_pi = 0; v.ivc = 0; v.pi_point = 0; v.points = w->pair_pts;
-    const int slot = (int)(w->calls % h2v_workspace::RING);
-    hipEvent_t *ev = w->ring[slot];
-    w->calls++;
+    CallRec &rec = rec_new(w, h2v_workspace::CHECK);
+    hipEvent_t *ev = rec.ev;
     for (int q : {0, 1, 2}) HIPCHK(hipEventRecord(ev[q], st));
     HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
     HIPCHK(hipMemsetAsync(w->status, 0, (size_t)n * 4, st));
@@ -1507,8 +1525,7 @@ static int run_check(const H2vDevPlan &d, uint32_t n, const uint8_t *pairs, uint
     HIPCHK(hipEventRecord(ev[4], st));
     hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er);
     HIPCHK(hipEventRecord(ev[5], st));
-    w->ring_lpt[slot] = 0;
-    w->ring_pair[slot] = (uint8_t)launch_pairing(v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, accept, nullptr, st, w->in_flight_hint);
+    rec.pair = (uint8_t)launch_pairing(v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, accept, nullptr, st, w->in_flight_hint);
     HIPCHK(hipEventRecord(ev[6], st));
     HIPCHK(hipGetLastError());
     if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
@@ -1516,7 +1533,8 @@ static int run_check(const H2vDevPlan &d, uint32_t n, const uint8_t *pairs, uint
 }
 
 static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                   uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt);
+                   uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt,
+                   uint32_t *fail_ctr);
 // ROUTING of RLC calls (round 4).  The batch-accept mode pays for every batch whose check fails: with 1 % rejecting proofs
 // nearly half of the groups of 64 fail, and the call costs 1.3 x the per-proof mode it falls back to.  A workspace therefore
 // keeps a running estimate of the rate of FAILING GROUPS among the groups its RLC calls have seen - cumulative device
@@ -1526,9 +1544,12 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
 // measured (simple_mul x 4096, sixteen calls in flight, ms per call): honest 1.37; one failing group (1 reject) 2.74; 17 % of the
 // groups failing (0.3 % rejects) 3.72; the per-proof mode 3.25 whatever it meets: about 2.6 + 6.4 x rate, equal at a rate of 0.1.
 // Same accept[] either way; fell_back / h2v_workspace_rlc_result report which path ran.  H2V_OPT_RLC_ROUTE = -1: never route.
+// (also the records' verdict words: RLC calls are made on a workspace that has been through here, lanes' chunks excepted - they
+// report into their parent's record)
 static int rlc_stats_ensure(h2v_workspace *w) {
     if (w->rlc_stats) return H2V_OK;
-    if (hipMalloc((void **)&w->rlc_stats, 8) != hipSuccess || hipMemset(w->rlc_stats, 0, 8) != hipSuccess ||
+    if (hipMalloc((void **)&w->rec_fail, h2v_workspace::RING * 4) != hipSuccess ||
+        hipMalloc((void **)&w->rlc_stats, 8) != hipSuccess || hipMemset(w->rlc_stats, 0, 8) != hipSuccess ||
         hipHostMalloc((void **)&w->h_rlc_stats, 8, hipHostMallocDefault) != hipSuccess)
         return fail(H2V_E_DEVICE, "allocation of the routing counters failed");
     w->h_rlc_stats[0] = w->h_rlc_stats[1] = 0;
@@ -1547,17 +1568,17 @@ static bool rlc_route(h2v_workspace *w) {
     w->routed = w->routed ? w->fail_rate > 0.05f : w->fail_rate > 0.10f;
     return w->routed;
 }
-// a routed chunk / call: the per-proof pipeline, then the counters from its status words
+// a routed chunk / call: the per-proof pipeline (its record: a routed RLC call), then the counters from its status words
 static int run_routed(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
                       uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, uint32_t *stats) {
     int rc = run_pipeline(p->d, n, proofs, off, inst, ci, accept, status_out, w, st, nullptr, false);
     if (rc) return rc;
+    rec_last(w).kind = h2v_workspace::RLC;
+    rec_last(w).routed = true;
     hipLaunchKernelGGL(k_rlc_count_groups, dim3(((n + 63) / 64 + 63) / 64), dim3(64), 0, st, n, w->status, stats);
     HIPCHK(hipGetLastError());
     return H2V_OK;
 }
-static uint64_t rlc_calls_of(const h2v_workspace *w);
-static const uint32_t *rlc_flags_of(const h2v_workspace *w);
 // A call on a laned workspace: chunks of at most w->chunk proofs, round robin through the lanes (continuing where the
 // previous call stopped).  Chunk c runs on its lane's own stream(s) behind everything the caller had enqueued on `st`
 // before the call and behind the lane's earlier chunks.  Nothing else orders the chunks: the kernels of neighbouring
@@ -1607,16 +1628,14 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
     // consecutive calls overlap and every lane is busy; a call that waits for its own chunks has only THOSE in flight - one
     // 4096-proof chunk on a laned workspace is a lone batch (with the full-chip shapes it took 11.6 ms instead of 5.8).
     const uint32_t call_hint = w->hint_given ? w->in_flight_hint : (w->defer_joins || never_join) ? w->n_lanes : (nch < L ? nch : L);
-    const int slot = (int)(w->calls % h2v_workspace::RING);
-    w->calls++;
-    w->lring_chunks[slot] = nch; w->lring_first[slot] = (uint32_t)(w->next_lane % L); w->lring_mod[slot] = L; w->lring_rlc[slot] = rlc ? 1 : 0;
-    w->lring_co[slot] = 0;
+    CallRec &rec = rec_new(w, rlc ? h2v_workspace::RLC : !pio ? h2v_workspace::VERIFY : pio->in ? h2v_workspace::CHECK : h2v_workspace::PREPARE);
+    rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = nch;
+    for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;   // (every chunk takes one record on its lane)
     bool routed = false;
     if (rlc) {
         if (int rcs = rlc_stats_ensure(w)) return rcs;
-        routed = rlc_route(w);
-        w->lring_routed[slot] = routed ? 1 : 0;
-        HIPCHK(hipMemsetAsync(w->rlc_fail + slot, routed ? 1 : 0, 4, st));      // (routed: "a batch check failed" = the per-proof kernels produce accept[])
+        routed = rec.routed = rlc_route(w);
+        HIPCHK(hipMemsetAsync(rec_word(w, rec), routed ? 1 : 0, 4, st));      // (routed: "a batch check failed" = the per-proof kernels produce accept[])
     }
     HIPCHK(hipEventRecord(w->ev_fork, st));
     for (uint32_t c = 0; c < nch; c++) {
@@ -1632,7 +1651,6 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
             uint32_t sd[8];
             for (int k = 0; k < 8; k++) sd[k] = seed[k];
             sd[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
-            lw->rlc_fail_ptr = w->rlc_fail + slot;
             lw->rlc_stats_ptr = w->rlc_stats;
             lw->in_flight_hint = call_hint;
             lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
@@ -1640,7 +1658,7 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
                 lw->one_stream_mode = 1;
                 rc = run_routed(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, w->rlc_stats);
             } else {
-                rc = run_rlc(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, true);
+                rc = run_rlc(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, true, rec_word(w, rec));
             }
             if (rc == H2V_OK && hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, ls) != hipSuccess) rc = fail(H2V_E_DEVICE, "routing counters: copy failed");
         } else if (pio && pio->in) {
@@ -1655,11 +1673,6 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
         if (rc) return drain_after_error(w, rc);   // (earlier chunks of this call and of calls before it are in flight on other lanes)
         HIPCHK(hipEventRecord(w->lane_ev[l], ls));
         w->lane_busy[l] = true;
-    }
-    for (uint32_t l = 0; l < w->n_lanes; l++) {
-        w->lring_calls[slot][l] = w->lane[l] ? w->lane[l]->calls : 0;
-        w->lring_rlc_calls[slot][l] = w->lane[l] ? rlc_calls_of(w->lane[l]) : 0;
-        w->lring_rlc_obj[slot][l] = w->lane[l] ? w->lane[l]->rlc : nullptr;
     }
     if (never_join) return H2V_OK;
     if (!w->defer_joins || force_join) return lanes_join(w, st);
@@ -1677,6 +1690,9 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
 // H2V_OPT_COALESCE = -1 on the workspace switches it off.
 struct Coalesce {
     uint8_t *proofs = nullptr, *inst = nullptr, *ci = nullptr, *accept = nullptr;
+    // one allocation: the group's verdict word (RLC: failed batch checks; 8 bytes) and behind it off[0 .. cap], so that the one
+    // memset that opens a group zeroes both
+    uint32_t *fail = nullptr;
     uint64_t *off = nullptr;
     uint32_t *status = nullptr;
     size_t cap_proof_bytes = 0, cap_inst = 0;
@@ -1686,13 +1702,13 @@ struct Coalesce {
     uint32_t count = 0;
     bool rlc = false;                    // the open group's mode: per proof, or ONE batch check over the whole group
     uint32_t seed[8] = {};               // (RLC: the first call's - one fresh seed makes every coefficient unpredictable)
-    struct Part { uint8_t *accept; uint32_t *status; uint32_t base, n; int slot; };
+    struct Part { uint8_t *accept; uint32_t *status; uint32_t base, n; uint64_t call; };
     std::vector<Part> parts;
 };
 static void co_release(h2v_workspace *w) {
     for (auto &c : w->co) {
         if (!c) continue;
-        void *ptrs[] = {c->proofs, c->inst, c->ci, c->accept, c->off, c->status};
+        void *ptrs[] = {c->proofs, c->inst, c->ci, c->accept, c->fail, c->status};
         for (void *q : ptrs) if (q) (void)hipFree(q);
         delete c;
         c = nullptr;
@@ -1707,14 +1723,15 @@ static int co_ensure(h2v_workspace *w, uint32_t l, const h2v_plan *p) {
     const size_t need_p = (size_t)cap * p->d.proof_len + 64, need_i = (size_t)cap * (p->d.n_pi ? p->d.n_pi : 1) * 32;
     if (c.cap == cap && c.cap_proof_bytes >= need_p && c.cap_inst >= need_i) return H2V_OK;
     HIPCHK(hipStreamSynchronize(w->lane_st[l]));              // (an earlier group may still be running out of the old buffers)
-    void *ptrs[] = {c.proofs, c.inst, c.ci, c.accept, c.off, c.status};
+    void *ptrs[] = {c.proofs, c.inst, c.ci, c.accept, c.fail, c.status};
     for (void *q : ptrs) if (q) (void)hipFree(q);
-    c.proofs = c.inst = c.ci = c.accept = nullptr; c.off = nullptr; c.status = nullptr; c.cap = 0;
+    c.proofs = c.inst = c.ci = c.accept = nullptr; c.fail = nullptr; c.off = nullptr; c.status = nullptr; c.cap = 0;
     const size_t bp = need_p > c.cap_proof_bytes ? need_p : c.cap_proof_bytes, bi = need_i > c.cap_inst ? need_i : c.cap_inst;
     bool ok = hipMalloc((void **)&c.proofs, bp) == hipSuccess && hipMalloc((void **)&c.inst, bi) == hipSuccess &&
               hipMalloc((void **)&c.ci, (size_t)cap * 48) == hipSuccess && hipMalloc((void **)&c.accept, cap) == hipSuccess &&
-              hipMalloc((void **)&c.off, ((size_t)cap + 1) * 8) == hipSuccess && hipMalloc((void **)&c.status, (size_t)cap * 4) == hipSuccess;
+              hipMalloc((void **)&c.fail, ((size_t)cap + 2) * 8) == hipSuccess && hipMalloc((void **)&c.status, (size_t)cap * 4) == hipSuccess;
     if (!ok) return fail(H2V_E_DEVICE, "hipMalloc(coalescing buffers) failed");
+    c.off = (uint64_t *)c.fail + 1;
     c.cap = cap; c.cap_proof_bytes = bp; c.cap_inst = bi;
     return H2V_OK;
 }
@@ -1741,20 +1758,15 @@ static int co_flush_lane(h2v_workspace *w, uint32_t l) {
     const uint8_t *inst_g = p->d.n_pi ? c.inst : nullptr, *ci_g = p->d.n_ci ? c.ci : nullptr;
     int rc = H2V_OK;
     bool routed = false;
-    const int slot0 = c.parts.empty() ? 0 : c.parts.front().slot;
     if (c.rlc) {
-        // one batch check over the group (as a chunk of run_laned): the verdict counter of the group's FIRST call takes the
-        // kernel's report and is copied to the other calls' counters behind it
+        // one batch check over the group (as a chunk of run_laned), reporting into the group's own verdict word (zeroed when
+        // the group was opened); copied below into the calls' records
         if ((rc = rlc_stats_ensure(w)) == H2V_OK) {
             routed = rlc_route(w);
-            if (hipMemsetAsync(w->rlc_fail + slot0, routed ? 1 : 0, 4, ls) != hipSuccess) rc = fail(H2V_E_DEVICE, "memset failed");
-        }
-        if (rc == H2V_OK) {
-            lw->rlc_fail_ptr = w->rlc_fail + slot0;
             lw->rlc_stats_ptr = w->rlc_stats;
             lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
             if (routed) { lw->one_stream_mode = 1; rc = run_routed(p, c.count, c.proofs, c.off, inst_g, ci_g, c.accept, c.status, lw, ls, w->rlc_stats); }
-            else rc = run_rlc(p, c.count, c.proofs, c.off, inst_g, ci_g, c.accept, c.status, lw, ls, c.seed, true);
+            else rc = run_rlc(p, c.count, c.proofs, c.off, inst_g, ci_g, c.accept, c.status, lw, ls, c.seed, true, c.fail);
             if (rc == H2V_OK && hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, ls) != hipSuccess) rc = fail(H2V_E_DEVICE, "routing counters: copy failed");
         }
     } else {
@@ -1763,17 +1775,16 @@ static int co_flush_lane(h2v_workspace *w, uint32_t l) {
     for (const Coalesce::Part &q : c.parts) {
         if (rc) break;
         if (hipMemcpyAsync(q.accept, c.accept + q.base, q.n, hipMemcpyDeviceToDevice, ls) != hipSuccess ||
-            (q.status && hipMemcpyAsync(q.status, c.status + q.base, (size_t)q.n * 4, hipMemcpyDeviceToDevice, ls) != hipSuccess) ||
-            (c.rlc && q.slot != slot0 && hipMemcpyAsync(w->rlc_fail + q.slot, w->rlc_fail + slot0, 4, hipMemcpyDeviceToDevice, ls) != hipSuccess))
+            (q.status && hipMemcpyAsync(q.status, c.status + q.base, (size_t)q.n * 4, hipMemcpyDeviceToDevice, ls) != hipSuccess))
             rc = fail(H2V_E_DEVICE, "coalesced calls: copying the verdicts out failed");
-        // the call's record: its group ran as this lane's most recent call; its share of that launch
-        w->lring_share[q.slot] = (float)q.n / (float)c.count;
-        w->lring_routed[q.slot] = routed ? 1 : 0;
-        for (uint32_t k = 0; k < w->n_lanes; k++) {
-            w->lring_calls[q.slot][k] = w->lane[k] ? w->lane[k]->calls : 0;
-            w->lring_rlc_calls[q.slot][k] = w->lane[k] ? rlc_calls_of(w->lane[k]) : 0;
-            w->lring_rlc_obj[q.slot][k] = w->lane[k] ? w->lane[k]->rlc : nullptr;
-        }
+        // the call's record, unless a later call has taken it: its group ran as this lane's most recent call; its share of that
+        // launch; the group's verdict (routed: "a batch check failed" = the per-proof kernels produce accept[])
+        CallRec *r = rec_at(w, q.call);
+        if (!r || rc) continue;
+        if (c.rlc && (routed ? hipMemsetAsync(rec_word(w, *r), 1, 4, ls) : hipMemcpyAsync(rec_word(w, *r), c.fail, 4, hipMemcpyDeviceToDevice, ls)) != hipSuccess)
+            rc = fail(H2V_E_DEVICE, "coalesced calls: copying the batch verdict out failed");
+        r->ran = true; r->share = (float)q.n / (float)c.count; r->routed = routed;
+        r->first = l; r->mod = w->n_lanes; r->chunks = 1; r->start[l] = lw->calls - 1;
     }
     c.parts.clear();
     c.count = 0;
@@ -1824,7 +1835,7 @@ static int coalesce_call(const h2v_plan *p, const h2v_batch *b, uint8_t *accept,
         c.plan = p; c.plan_gen = p->gen; c.count = 0; c.parts.clear();
         c.rlc = rlc;
         for (int k = 0; k < 8; k++) c.seed[k] = rlc && seed ? seed[k] : 0;
-        HIPCHK(hipMemsetAsync(c.off, 0, 8, w->lane_st[l]));     // off[0] = 0: behind the previous group's pipeline on this stream
+        HIPCHK(hipMemsetAsync(c.fail, 0, 16, w->lane_st[l]));   // verdict word and off[0] = 0: behind the previous group's flush on this stream
         w->co_open.push_back(l);
         found = (int)l;
     }
@@ -1838,27 +1849,14 @@ static int coalesce_call(const h2v_plan *p, const h2v_batch *b, uint8_t *accept,
     HIPCHK(hipGetLastError());
     if (p->d.n_pi) HIPCHK(hipMemcpyAsync(c.inst + (size_t)c.count * p->d.n_pi * 32, b->instances, (size_t)n * p->d.n_pi * 32, hipMemcpyDeviceToDevice, ls));
     if (p->d.n_ci) HIPCHK(hipMemcpyAsync(c.ci + (size_t)c.count * 48, b->committed, (size_t)n * 48, hipMemcpyDeviceToDevice, ls));
-    // the call's record in the ring: one "chunk" on lane l, that lane's NEXT pipeline call (nothing else runs there before the flush)
-    const int slot = (int)(w->calls % h2v_workspace::RING);
-    w->calls++;
-    w->lring_chunks[slot] = 1; w->lring_first[slot] = l; w->lring_mod[slot] = w->n_lanes; w->lring_rlc[slot] = rlc ? 1 : 0; w->lring_routed[slot] = 0;
-    w->lring_co[slot] = 1; w->lring_share[slot] = 0.0f;      // (0: its group has not run yet)
-    for (uint32_t q = 0; q < w->n_lanes; q++) { w->lring_calls[slot][q] = 0; w->lring_rlc_calls[slot][q] = 0; w->lring_rlc_obj[slot][q] = nullptr; }   // (filled in by the flush)
-    c.parts.push_back({accept, status, c.count, n, slot});
+    // the call's record: where its group ran is filled in by the flush (co_flush_lane)
+    CallRec &rec = rec_new(w, rlc ? h2v_workspace::RLC : h2v_workspace::VERIFY);
+    rec.co = true;
+    c.parts.push_back({accept, status, c.count, n, rec.call});
     c.count += n;
     w->lane_busy[l] = true;              // (h2v_workspace_join must look at this lane; its event is recorded by the flush)
     if (c.count >= c.cap) return co_flush_lane(w, l);
     return H2V_OK;
-}
-
-// chunk c of the call in ring slot `slot` ran on lane *l as that lane's call number (0-based, absolute) *idx
-static void laned_chunk_pos(const h2v_workspace *w, int slot, uint32_t c, bool rlc, uint32_t *l, uint64_t *idx) {
-    const uint32_t L = w->lring_mod[slot], nch = w->lring_chunks[slot], f = w->lring_first[slot];
-    *l = (f + c) % L;
-    uint32_t uses = 0;                       // chunks of this call on that lane
-    for (uint32_t q = 0; q < nch; q++) if ((f + q) % L == *l) uses++;
-    const uint64_t end = rlc ? w->lring_rlc_calls[slot][*l] : w->lring_calls[slot][*l];
-    *idx = end - uses + c / L;
 }
 
 extern "C" int h2v_verify_batch_device(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, uint32_t *status,
@@ -2016,51 +2014,69 @@ extern "C" int h2v_workspace_tune(const h2v_plan *p, const h2v_batch *b, h2v_wor
     return rc;
 }
 
+// The record of the call `calls_back` calls before the most recent one on w (H2V_E_ARG: 64 or more back, or an earlier call's
+// slot; a coalesced call whose group has not run yet has nothing to report).
+static int rec_lookup(h2v_workspace *w, uint32_t calls_back, const CallRec **out) {
+    const CallRec *r = calls_back < w->calls ? rec_at(w, w->calls - 1 - calls_back) : nullptr;
+    if (!r) return fail(H2V_E_ARG, "no such call in the event ring");
+    if (r->co && !r->ran) return fail(H2V_E_ARG, "that call is in a group of coalesced calls that has not run yet: h2v_workspace_join first");
+    *out = r;
+    return H2V_OK;
+}
+// The chunk walker of a laned workspace's record r: f(lane record) for chunk c = 0, 1, ... in order - chunk c ran on lane
+// (first + c) % mod as that lane's record start[lane] + c / mod.  H2V_E_ARG when a lane has since given that record's slot to a
+// later call.
+template <class F> static int each_chunk(h2v_workspace *w, const CallRec &r, F &&f) {
+    for (uint32_t c = 0; c < r.chunks; c++) {
+        const uint32_t l = (r.first + c) % r.mod;
+        const CallRec *lr = w->lane[l] ? rec_at(w->lane[l], r.start[l] + c / r.mod) : nullptr;
+        if (!lr) return fail(H2V_E_ARG, "the lanes' event rings have wrapped since that call");
+        if (int rc = f(*lr)) return rc;
+    }
+    return H2V_OK;
+}
+static int rec_timings(const CallRec &r, h2v_timings *tm);
 // Per-kernel device times of a PAST call on this workspace (0 = the most recent, up to 63 back).  The events were
 // recorded on the streams the kernels ran on; the caller must have synchronised the launch stream first.
 extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_timings *tm) {
     if (!w || !tm) return fail(H2V_E_ARG, "null argument");
     ALIVE(w);
-    if (calls_back >= h2v_workspace::RING || calls_back >= w->calls) return fail(H2V_E_ARG, "no such call in the event ring");
+    const CallRec *r;
+    if (int rc = rec_lookup(w, calls_back, &r)) return rc;
+    if (r->kind == h2v_workspace::RLC && !r->routed) return fail(H2V_E_ARG, "that call ran in RLC mode: h2v_workspace_rlc_result");
     HIPCHK(hipSetDevice(w->device));
-    const int slot = (int)((w->calls - 1 - calls_back) % h2v_workspace::RING);
-    if (w->n_lanes) {
-        // sums over the call's chunks (h2v_timings: `launches` = chunks); total_ms = first chunk's start .. the last end
-        if (w->lring_co[slot] && w->lring_share[slot] == 0.0f) return fail(H2V_E_ARG, "that call is in a group of coalesced calls that has not run yet: h2v_workspace_join first");
-        if (w->lring_rlc[slot] && !w->lring_routed[slot]) return fail(H2V_E_ARG, "that call ran in RLC mode: h2v_workspace_rlc_result");
-        memset(tm, 0, sizeof *tm);
-        const uint32_t nch = w->lring_chunks[slot];
-        hipEvent_t first = nullptr;
-        for (uint32_t c = 0; c < nch; c++) {
-            uint32_t l; uint64_t idx;
-            laned_chunk_pos(w, slot, c, false, &l, &idx);
-            h2v_workspace *lw = w->lane[l];
-            if (lw->calls - 1 - idx >= (uint64_t)h2v_workspace::RING) return fail(H2V_E_ARG, "the lanes' event rings have wrapped since that call");
-            h2v_timings t1;
-            int rc = h2v_workspace_timings(lw, (uint32_t)(lw->calls - 1 - idx), &t1);
-            if (rc) return rc;
-            tm->transcript_combiner_ms += t1.transcript_combiner_ms; tm->g1_decompress_ms += t1.g1_decompress_ms;
-            tm->g1_msm_ms += t1.g1_msm_ms; tm->pairing_ms += t1.pairing_ms; tm->g1_msm_fixed_ms += t1.g1_msm_fixed_ms;
-            tm->msm_var_lanes_per_term = t1.msm_var_lanes_per_term;
-            tm->msm_lanes_per_term = t1.msm_lanes_per_term; tm->pairing_lanes_per_proof = t1.pairing_lanes_per_proof;
-            hipEvent_t *ev = lw->ring[idx % h2v_workspace::RING];
-            if (!first) first = ev[2];
-            float span = 0;
-            HIPCHK(hipEventElapsedTime(&span, first, ev[6]));
-            if (span > tm->total_ms) tm->total_ms = span;
-        }
-        tm->launches = nch;
-        if (w->lring_co[slot]) {     // a coalesced call: its share of the one launch that served its group
-            const float f = w->lring_share[slot];
-            tm->transcript_combiner_ms *= f; tm->g1_decompress_ms *= f; tm->g1_msm_ms *= f; tm->pairing_ms *= f; tm->g1_msm_fixed_ms *= f;
-        }
+    if (!w->n_lanes) return rec_timings(*r, tm);
+    // sums over the call's chunks (h2v_timings: `launches` = chunks); total_ms = first chunk's start .. the last end
+    memset(tm, 0, sizeof *tm);
+    hipEvent_t first = nullptr;
+    int rc = each_chunk(w, *r, [&](const CallRec &lr) -> int {
+        h2v_timings t1;
+        if (int rc1 = rec_timings(lr, &t1)) return rc1;
+        tm->transcript_combiner_ms += t1.transcript_combiner_ms; tm->g1_decompress_ms += t1.g1_decompress_ms;
+        tm->g1_msm_ms += t1.g1_msm_ms; tm->pairing_ms += t1.pairing_ms; tm->g1_msm_fixed_ms += t1.g1_msm_fixed_ms;
+        tm->msm_var_lanes_per_term = t1.msm_var_lanes_per_term;
+        tm->msm_lanes_per_term = t1.msm_lanes_per_term; tm->pairing_lanes_per_proof = t1.pairing_lanes_per_proof;
+        if (!first) first = lr.ev[2];
+        float span = 0;
+        HIPCHK(hipEventElapsedTime(&span, first, lr.ev[6]));
+        if (span > tm->total_ms) tm->total_ms = span;
         return H2V_OK;
+    });
+    if (rc) return rc;
+    tm->launches = r->chunks;
+    if (r->co) {     // a coalesced call: its share of the one launch that served its group
+        const float f = r->share;
+        tm->transcript_combiner_ms *= f; tm->g1_decompress_ms *= f; tm->g1_msm_ms *= f; tm->pairing_ms *= f; tm->g1_msm_fixed_ms *= f;
     }
+    return H2V_OK;
+}
+// the times of one record of an ordinary workspace (or of a lane)
+static int rec_timings(const CallRec &r, h2v_timings *tm) {
     memset(tm, 0, sizeof *tm);
     tm->launches = 1;
-    tm->msm_lanes_per_term = w->ring_lpt[slot];
-    tm->pairing_lanes_per_proof = w->ring_pair[slot];
-    hipEvent_t *ev = w->ring[slot];
+    tm->msm_lanes_per_term = r.lpt;
+    tm->pairing_lanes_per_proof = r.pair;
+    const hipEvent_t *ev = r.ev;
     HIPCHK(hipEventSynchronize(ev[6]));
     HIPCHK(hipEventElapsedTime(&tm->transcript_combiner_ms, ev[0], ev[1]));
     HIPCHK(hipEventElapsedTime(&tm->g1_decompress_ms, ev[2], ev[3]));
@@ -2069,16 +2085,16 @@ extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_
         for (int q = 0; q < 7; q++) { float t; HIPCHK(hipEventElapsedTime(&t, ev[0], ev[q])); fprintf(stderr, " e%d=%.3f", q, t); }
         fprintf(stderr, "\n");
     }
-    if (w->ring_lpt[slot] == 3) {
+    if (r.lpt == 3) {
         // split MSM: the ladder launch over the per-proof terms ([4] .. [9]) and, beside it on another stream, the
         // fixed-base launch over the VK-base terms ([7] .. [8]) - two kernels, two durations
         HIPCHK(hipEventElapsedTime(&tm->g1_msm_ms, ev[4], ev[9]));
         HIPCHK(hipEventElapsedTime(&tm->g1_msm_fixed_ms, ev[7], ev[8]));
-        tm->msm_var_lanes_per_term = w->ring_var[slot];
+        tm->msm_var_lanes_per_term = r.var_lpt;
     } else {
         HIPCHK(hipEventElapsedTime(&tm->g1_msm_ms, ev[4], ev[5]));
     }
-    if (w->ring_pair[slot]) HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[5], ev[6]));   // (0: a prepare call - no pairing ran)
+    if (r.pair) HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[5], ev[6]));   // (0: a prepare call - no pairing ran)
     HIPCHK(hipEventElapsedTime(&tm->total_ms, ev[2], ev[6]));
     return H2V_OK;
 }
@@ -2148,14 +2164,11 @@ static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws,
     *in = {sl.in_block + o_proofs, sl.in_block + o_inst, sl.in_block + o_ci, (const uint64_t *)sl.in_block};
     return H2V_OK;
 }
-static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                   uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt);
 static bool rlc_supported(const h2v_plan *p);
 static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]);
 static int run_rlc_or_routed(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
                              uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt);
 
-extern "C" int h2v_workspace_rlc_result(h2v_workspace *w, uint32_t calls_back, uint32_t *batch_accepted, h2v_rlc_timings *tm);
 // Host-buffer batches on a LANED workspace: as many in flight as the mode has lanes, on ONE workspace.  Every batch gets a
 // staging slot of its own (pinned block + device block + accept buffers); uploads run in order on `hs`, the chunks on
 // the lanes, and the downloads on `hs_down`, each behind the lanes its batch ran on.  h2v_verify_batch_wait collects the
@@ -2175,15 +2188,13 @@ static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws
         int rc = run_laned(p, (uint32_t)n, in.proofs, in.off, in.inst, in.ci, sl.d_accept, nullptr, ws, ws->hs, rlc, seed, false, true);
         if (rc == H2V_OK) {
             // the download waits for the lanes this call's chunks ran on (their events as recorded just now)
-            const int slot = (int)((ws->calls - 1) % h2v_workspace::RING);
-            sl.call = ws->calls - 1;
-            const uint32_t nch = ws->lring_chunks[slot], mod = ws->lring_mod[slot], first = ws->lring_first[slot];
-            for (uint32_t c = 0; c < nch && c < mod; c++)
-                if (hipStreamWaitEvent(ws->hs_down, ws->lane_ev[(first + c) % mod], 0) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream wait failed");
+            const CallRec &r = rec_last(ws);
+            for (uint32_t c = 0; c < r.chunks && c < r.mod; c++)
+                if (hipStreamWaitEvent(ws->hs_down, ws->lane_ev[(r.first + c) % r.mod], 0) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream wait failed");
             if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, sl.d_accept, n, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
             // (RLC: how many of the call's batch checks failed comes back the same way - a synchronous copy in _wait would go
             //  through the legacy NULL stream, which every pool stream is ordered with: it would drain all batches in flight)
-            if (rc == H2V_OK && rlc && hipMemcpyAsync(sl.h_accept + ((n + 7) & ~(uint64_t)7), ws->rlc_fail + slot, 4, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess)
+            if (rc == H2V_OK && rlc && hipMemcpyAsync(sl.h_accept + ((n + 7) & ~(uint64_t)7), rec_word(ws, r), 4, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess)
                 rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
         }
         if (rc) return drain_after_error(ws, rc);
@@ -2193,19 +2204,19 @@ static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws
     ws->pending = true;
     return H2V_OK;
 }
+// A downloaded batch: accept bytes to the caller; fell_back (optional) = an RLC call whose record counted a failed batch check -
+// the word that came back behind accept[] - so that the per-proof kernels produced accept[] (either kind of workspace)
+static void host_results(const h2v_workspace::HostSlot &sl, uint8_t *accept, int *fell_back) {
+    if (sl.n) memcpy(accept, sl.h_accept, sl.n);
+    uint32_t failed = 0;
+    if (sl.rlc && sl.n) memcpy(&failed, sl.h_accept + ((sl.n + 7) & ~(uint64_t)7), 4);
+    if (fell_back) *fell_back = failed ? 1 : 0;
+}
 static int wait_laned(h2v_workspace *ws, uint8_t *accept, int *fell_back) {
     if (ws->h_head == ws->h_tail) return fail(H2V_E_ARG, "no batch in flight on this workspace");
     h2v_workspace::HostSlot &sl = ws->hslot[ws->h_tail % h2v_workspace::MAXH];
     HIPCHK(hipEventSynchronize(sl.ev));
-    if (sl.n) memcpy(accept, sl.h_accept, sl.n);
-    if (fell_back) {
-        *fell_back = 0;
-        if (sl.rlc && sl.n) {
-            uint32_t failed = 0;
-            memcpy(&failed, sl.h_accept + ((sl.n + 7) & ~(uint64_t)7), 4);
-            *fell_back = failed ? 1 : 0;
-        }
-    }
+    host_results(sl, accept, fell_back);
     ws->h_tail++;
     ws->pending = ws->h_head != ws->h_tail;
     return H2V_OK;
@@ -2244,7 +2255,7 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
         else rc = run_pipeline(p->d, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, nullptr, false);
         sl.rlc = rlc;
         if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, ws->accept, b->n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-        if (rc == H2V_OK && rlc && ws->rlc && hipMemcpyAsync(sl.h_accept + ((b->n + 7) & ~(uint64_t)7), rlc_flags_of(ws), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
+        if (rc == H2V_OK && rlc && hipMemcpyAsync(sl.h_accept + ((b->n + 7) & ~(uint64_t)7), rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
             rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
         if (rc) return drain_after_error(ws, rc);   // (the upload from the pinned block and some kernels may already be enqueued)
     }
@@ -2263,15 +2274,7 @@ extern "C" int h2v_verify_batch_wait(h2v_workspace *ws, uint8_t *accept, int *fe
     ws->pending = false;
     const h2v_workspace::HostSlot &sl = ws->hslot[0];
     HIPCHK(hipEventSynchronize(sl.ev));
-    if (sl.n) memcpy(accept, sl.h_accept, sl.n);
-    if (fell_back) {
-        *fell_back = 0;
-        if (sl.rlc && sl.n) {     // the batch verdict came back with the accept bytes (1 = passed)
-            uint32_t passed = 1;
-            memcpy(&passed, sl.h_accept + ((sl.n + 7) & ~(uint64_t)7), 4);
-            *fell_back = passed ? 0 : 1;
-        }
-    }
+    host_results(sl, accept, fell_back);
     return H2V_OK;
 }
 static int verify_host(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back) {
@@ -2525,13 +2528,6 @@ struct RlcWs {
         size_t cnt_bytes = 0, pool_bytes = 0;
         uint32_t cap_G = 0;
     } grp;
-    static constexpr int NEV = 11;
-    hipEvent_t ring[h2v_workspace::RING][NEV] = {};
-    uint64_t calls = 0;
-    uint64_t run_len = 0;       // calls since these buffers last became the workspace's current ones (rlc_ensure)
-    uint32_t last_c = 0, last_W = 0, last_chain = 0, last_terms = 0;
-    bool last_routed = false;   // the most recent call on this (ordinary) workspace went straight to the per-proof kernels
-    uint8_t routed_ring[64] = {};
 };
 static void rlc_release(RlcWs *r) {
     void *ptrs[] = {r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good, r->sums, r->misc, r->flags, r->grp.g_scal, r->grp.g_idx, r->grp.er_g,
@@ -2539,7 +2535,6 @@ static void rlc_release(RlcWs *r) {
     for (void *q : ptrs) if (q) (void)hipFree(q);
     for (void *q : r->grp.staged) (void)hipHostFree(q);   // (the caller has drained the streams: ws_release)
     pip_free(r->R); pip_free(r->L);
-    for (auto &set : r->ring) for (hipEvent_t e : set) if (e) (void)hipEventDestroy(e);
     delete r;
 }
 // One set of buffers per plan SHAPE (n_var, n_fix) the workspace has served: a workspace that alternates between plans (ws_fits
@@ -2553,7 +2548,6 @@ static int rlc_ensure(h2v_workspace *w, const h2v_plan *p) {
             w->rlc_parked[k] = w->rlc;
             if (!w->rlc_parked[k]) w->rlc_parked.erase(w->rlc_parked.begin() + (long)k);
             w->rlc = q;
-            q->run_len = 0;
             return H2V_OK;
         }
     }
@@ -2571,14 +2565,11 @@ static int rlc_ensure(h2v_workspace *w, const h2v_plan *p) {
               hipMalloc((void **)&r->sums, 72 * 4) == hipSuccess && hipMalloc((void **)&r->misc, 32 * 4) == hipSuccess &&
               hipMemset(r->misc, 0, 32 * 4) == hipSuccess && hipMalloc((void **)&r->flags, (blocks + 2) * 4) == hipSuccess &&
               hipMemset(r->flags, 0, (blocks + 2) * 4) == hipSuccess;
-    for (auto &set : r->ring) for (hipEvent_t &e : set) if (ok) ok = hipEventCreate(&e) == hipSuccess;
     if (ok) ok = pip_alloc(r->R, (uint32_t)nr, 2) == H2V_OK && pip_alloc(r->L, (uint32_t)w->cap, 1) == H2V_OK;
     if (!ok) { rlc_release(r); return fail(H2V_E_DEVICE, "RLC workspace allocation failed"); }
     w->rlc = r;
     return H2V_OK;
 }
-static uint64_t rlc_calls_of(const h2v_workspace *w) { return w->rlc ? w->rlc->calls : 0; }
-static const uint32_t *rlc_flags_of(const h2v_workspace *w) { return w->rlc->flags; }
 static bool rlc_supported(const h2v_plan *p) { return !p->d.ivc && p->n_var > 0 && p->n_fix > 0 && p->n_var + p->n_fix == p->d.n_terms; }
 
 // Fall-back stage 1: group checks (h2v_rlc.hpp: k_rlc_group_terms, k_pairing_rlc_groups).  Groups of 64 proofs; every group
@@ -2698,8 +2689,12 @@ static int rlc_groups_launch(RlcWs *r, const h2v_plan *p, h2v_workspace *w, uint
 
 // One batch in RLC mode.  Phase 1 as in run_pipeline (the decompression launch builds no window tables), then the batch
 // check; the per-proof MSM + pairing kernels are queued behind it and return at once unless the batch check failed.
+// fail_ctr: where a failed batch check is counted - a lane's chunk or a coalesced group: its parent's word; NULL (a call of
+// its own): its record's word, zeroed here.  Events (the record's): [0]/[1] around the decompression, [2]/[3] around the
+// combiner, [10]/[4] around the scalar preparation, [5] .. [8] the bucket MSMs (pip_launch), [8]/[9] around the pairing.
 static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                   uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt) {
+                   uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt,
+                   uint32_t *fail_ctr) {
     const H2vDevPlan &d = p->d;
     int rc = rlc_ensure(w, p);
     if (rc) return rc;
@@ -2707,9 +2702,8 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
     RlcWs *r = w->rlc;
     const uint32_t slots = H2V_SLOTS(d);
-    hipEvent_t *ev = r->ring[r->calls % h2v_workspace::RING];
-    r->calls++;
-    r->run_len++;
+    CallRec &rec = rec_new(w, h2v_workspace::RLC);
+    hipEvent_t *ev = rec.ev;
     // two streams per batch: the caller's (transcript + combiner, then everything else) and one for the decompression
     // one_stream (h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM, or H2V_OPT_STREAMS = 1): everything on
     // the caller's stream, decompression before the combiner - one stream per batch in flight instead of two
@@ -2752,7 +2746,7 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     pa[1].n = n; pa[1].halves = 1; pa[1].scal = r->l_scal; pa[1].pidx = r->l_idx; pa[1].pool0 = w->pts; pa[1].n_pool0 = n * slots; pa[1].pool1 = nullptr; pa[1].out = r->sums + 36;
     const PipWs *pws[2] = {&r->R, &r->L};
     if ((rc = pip_launch(pws, pa, 2, pm, ev + 5))) return rc;   // ev[5..8]
-    r->last_c = pa[0].c; r->last_W = pa[0].W; r->last_chain = pa[0].chain; r->last_terms = pa[0].n;
+    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
     // one pairing check over a one-proof view of the plan: el = L, er = R (both Jacobian), no per-proof points
     H2vDevPlan d1 = d;
     d1.n_points = 1; d1.n_ci = 0; d1.ivc = 0; d1.pi_point = 0;
@@ -2760,9 +2754,13 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     uint8_t *valid1 = (uint8_t *)(r->misc + 26), *acc1 = (uint8_t *)(r->misc + 27);
     HIPCHK(hipMemsetAsync(r->misc + 24, 0, 4, pm));            // status of the batch check
     HIPCHK(hipMemsetAsync(valid1, 1, 1, pm));
+    if (!fail_ctr) {
+        fail_ctr = rec_word(w, rec);
+        HIPCHK(hipMemsetAsync(fail_ctr, 0, 4, pm));
+    }
     const uint32_t n_groups = (n + 63) / 64;
     hipLaunchKernelGGL(k_pairing_rlc, dim3(1), dim3(64), COOP_LDS_BYTES(1), pm, d1, r->misc, valid1, r->sums, r->sums + 36, st1, acc1, n, r->good, accept, skip,
-                       n_groups, w->rlc_fail_ptr, w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats, rlc_groups_on(n) ? 1u : 0u);
+                       n_groups, fail_ctr, w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats, rlc_groups_on(n) ? 1u : 0u);
     HIPCHK(hipEventRecord(ev[9], pm));
     // fall-back, skipped on the device when the batch check passed.  Stage 1 finds the groups of 64 proofs that hold a failing
     // proof (everything else is final); stage 2 - window tables, per-proof MSM, per-proof pairing - decides inside those
@@ -2819,22 +2817,16 @@ static int rlc_check_batch(const h2v_plan *p, const h2v_batch *b, const uint8_t 
     if (b->n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 proofs");
     return H2V_OK;
 }
-// an RLC call on an ORDINARY workspace: the batch check, or - routed - the per-proof pipeline (flags[0] = 0: "fell back")
+// an RLC call on an ORDINARY workspace: the batch check, or - routed - the per-proof pipeline (its record's word: "failed")
 static int run_rlc_or_routed(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
                              uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt) {
     int rc = rlc_stats_ensure(w);
     if (rc) return rc;
     if (rlc_route(w)) {
-        if ((rc = rlc_ensure(w, p))) return rc;
-        HIPCHK(hipMemsetAsync(w->rlc->flags, 0, 4, st));
-        w->rlc->routed_ring[w->rlc->calls % h2v_workspace::RING] = 1;   // (its event set stays unrecorded: h2v_workspace_rlc_result reports zeros)
-        w->rlc->calls++;
-        w->rlc->run_len++;
-        w->rlc->last_routed = true;
         rc = run_routed(p, n, proofs, off, inst, ci, accept, status_out, w, st, w->rlc_stats);
+        if (rc == H2V_OK) HIPCHK(hipMemsetAsync(rec_word(w, rec_last(w)), 1, 4, st));
     } else {
-        rc = run_rlc(p, n, proofs, off, inst, ci, accept, status_out, w, st, seed, one_stream_opt);
-        if (rc == H2V_OK) { w->rlc->last_routed = false; w->rlc->routed_ring[(w->rlc->calls - 1) % h2v_workspace::RING] = 0; }
+        rc = run_rlc(p, n, proofs, off, inst, ci, accept, status_out, w, st, seed, one_stream_opt, nullptr);
     }
     if (rc == H2V_OK) HIPCHK(hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, st));
     return rc;
@@ -2870,84 +2862,67 @@ extern "C" int h2v_verify_batch_rlc(const h2v_plan *p, const h2v_batch *b, uint8
 }
 // After the stream of an RLC call has been synchronised: did the batch check pass (1) or did the per-proof kernels run (0)?
 // kernel times of a past call (calls_back = 0: the most recent).
-static int rlc_timings_of(const RlcWs *r, uint32_t calls_back, h2v_rlc_timings *tm);
+static int rec_rlc_timings(const CallRec &r, h2v_rlc_timings *tm);
 extern "C" int h2v_workspace_rlc_result(h2v_workspace *w, uint32_t calls_back, uint32_t *batch_accepted, h2v_rlc_timings *tm) {
+    if (!w) return fail(H2V_E_ARG, "null argument");
     ALIVE(w);
-    if (w && w->n_lanes) {
-        // laned: the AND of the chunks' batch verdicts; times summed over the chunks, total = first start .. last verdict
-        if (w->calls == 0 || calls_back >= h2v_workspace::RING || calls_back >= w->calls) return fail(H2V_E_ARG, "no such call in the event ring");
-        const int slot = (int)((w->calls - 1 - calls_back) % h2v_workspace::RING);
-        if (!w->lring_rlc[slot]) return fail(H2V_E_ARG, "that call did not run in RLC mode");
-        if (w->lring_co[slot] && w->lring_share[slot] == 0.0f) return fail(H2V_E_ARG, "that call is in a group of coalesced calls that has not run yet: h2v_workspace_join first");
-        if (w->lring_routed[slot]) {       // routed to the per-proof kernels: no batch check ran (h2v_workspace_timings has no record either)
-            if (batch_accepted) *batch_accepted = 0;
-            if (tm) memset(tm, 0, sizeof *tm);
-            return H2V_OK;
-        }
-        if (batch_accepted) {
-            uint32_t failed = 0;
-            HIPCHK(hipMemcpy(&failed, w->rlc_fail + slot, 4, hipMemcpyDeviceToHost));
-            *batch_accepted = failed == 0 ? 1u : 0u;
-        }
-        if (!tm) return H2V_OK;
-        memset(tm, 0, sizeof *tm);
-        hipEvent_t first = nullptr;
-        for (uint32_t c = 0; c < w->lring_chunks[slot]; c++) {
-            uint32_t l; uint64_t idx;
-            laned_chunk_pos(w, slot, c, true, &l, &idx);
-            h2v_workspace *lw = w->lane[l];
-            // the buffers (and event ring) the chunk ran on: the lane's current ones, or parked since by another plan's call
-            const RlcWs *r1 = w->lring_rlc_obj[slot][l];
-            bool alive = r1 && lw->rlc == r1;
-            for (const RlcWs *q : lw->rlc_parked) alive = alive || (r1 && q == r1);
-            if (!alive || r1->calls - 1 - idx >= (uint64_t)h2v_workspace::RING) return fail(H2V_E_ARG, "the lanes' event rings have wrapped since that call");
-            h2v_rlc_timings t1;
-            int rc = rlc_timings_of(r1, (uint32_t)(r1->calls - 1 - idx), &t1);
-            if (rc) return rc;
-            tm->transcript_combiner_ms += t1.transcript_combiner_ms; tm->g1_decompress_ms += t1.g1_decompress_ms; tm->prepare_ms += t1.prepare_ms;
-            tm->bucket_sort_ms += t1.bucket_sort_ms; tm->bucket_accumulate_ms += t1.bucket_accumulate_ms; tm->bucket_reduce_ms += t1.bucket_reduce_ms;
-            tm->pairing_ms += t1.pairing_ms;
-            tm->msm_terms = t1.msm_terms; tm->window_bits = t1.window_bits; tm->windows = t1.windows; tm->max_chain = t1.max_chain;
-            const hipEvent_t *ev = r1->ring[idx % h2v_workspace::RING];
-            if (!first) first = ev[0];
-            float span = 0;
-            HIPCHK(hipEventElapsedTime(&span, first, ev[9]));
-            if (span > tm->total_ms) tm->total_ms = span;
-        }
-        if (w->lring_co[slot]) {     // a coalesced call: its share of the one batch check that served its group (total_ms: the group's)
-            const float f = w->lring_share[slot];
-            tm->transcript_combiner_ms *= f; tm->g1_decompress_ms *= f; tm->prepare_ms *= f; tm->bucket_sort_ms *= f;
-            tm->bucket_accumulate_ms *= f; tm->bucket_reduce_ms *= f; tm->pairing_ms *= f;
-        }
+    const CallRec *r;
+    if (int rc = rec_lookup(w, calls_back, &r)) return rc;
+    if (r->kind != h2v_workspace::RLC) return fail(H2V_E_ARG, "that call did not run in RLC mode");
+    if (r->routed) {       // routed to the per-proof kernels: no batch check ran (h2v_workspace_timings has its times)
+        if (batch_accepted) *batch_accepted = 0;
+        if (tm) memset(tm, 0, sizeof *tm);
         return H2V_OK;
     }
-    if (!w || !w->rlc || w->rlc->calls == 0) return fail(H2V_E_ARG, "no RLC call was made with this workspace");
-    RlcWs *r = w->rlc;
     HIPCHK(hipSetDevice(w->device));
-    if (calls_back >= r->run_len) return fail(H2V_E_ARG, "an RLC call of another plan has used this workspace since that call");
-    if (batch_accepted) HIPCHK(hipMemcpy(batch_accepted, r->flags, 4, hipMemcpyDeviceToHost));
-    return tm ? rlc_timings_of(r, calls_back, tm) : H2V_OK;
-}
-static int rlc_timings_of(const RlcWs *r, uint32_t calls_back, h2v_rlc_timings *tm) {
-    {
-        if (calls_back >= h2v_workspace::RING || calls_back >= r->calls) return fail(H2V_E_ARG, "no such call in the event ring");
-        const hipEvent_t *ev = r->ring[(r->calls - 1 - calls_back) % h2v_workspace::RING];
-        memset(tm, 0, sizeof *tm);
-        if (r->routed_ring[(r->calls - 1 - calls_back) % h2v_workspace::RING]) return H2V_OK;   // routed: no batch check ran
-        HIPCHK(hipEventSynchronize(ev[9]));
-        HIPCHK(hipEventElapsedTime(&tm->g1_decompress_ms, ev[0], ev[1]));
-        HIPCHK(hipEventElapsedTime(&tm->transcript_combiner_ms, ev[2], ev[3]));
-        HIPCHK(hipEventElapsedTime(&tm->prepare_ms, ev[10], ev[4]));
-        HIPCHK(hipEventElapsedTime(&tm->bucket_sort_ms, ev[5], ev[6]));
-        HIPCHK(hipEventElapsedTime(&tm->bucket_accumulate_ms, ev[6], ev[7]));
-        HIPCHK(hipEventElapsedTime(&tm->bucket_reduce_ms, ev[7], ev[8]));
-        HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[8], ev[9]));
-        float a0, a1;
-        HIPCHK(hipEventElapsedTime(&a0, ev[0], ev[9]));
-        HIPCHK(hipEventElapsedTime(&a1, ev[2], ev[9]));
-        tm->total_ms = a0 > a1 ? a0 : a1;
-        tm->msm_terms = r->last_terms; tm->window_bits = r->last_c; tm->windows = r->last_W; tm->max_chain = r->last_chain;
+    if (batch_accepted) {   // (laned: the AND of the chunks' batch verdicts)
+        uint32_t failed = 0;
+        HIPCHK(hipMemcpy(&failed, rec_word(w, *r), 4, hipMemcpyDeviceToHost));
+        *batch_accepted = failed == 0 ? 1u : 0u;
     }
+    if (!tm) return H2V_OK;
+    if (!w->n_lanes) return rec_rlc_timings(*r, tm);
+    // laned: times summed over the chunks, total = first start .. last verdict
+    memset(tm, 0, sizeof *tm);
+    hipEvent_t first = nullptr;
+    int rc = each_chunk(w, *r, [&](const CallRec &lr) -> int {
+        h2v_rlc_timings t1;
+        if (int rc1 = rec_rlc_timings(lr, &t1)) return rc1;
+        tm->transcript_combiner_ms += t1.transcript_combiner_ms; tm->g1_decompress_ms += t1.g1_decompress_ms; tm->prepare_ms += t1.prepare_ms;
+        tm->bucket_sort_ms += t1.bucket_sort_ms; tm->bucket_accumulate_ms += t1.bucket_accumulate_ms; tm->bucket_reduce_ms += t1.bucket_reduce_ms;
+        tm->pairing_ms += t1.pairing_ms;
+        tm->msm_terms = t1.msm_terms; tm->window_bits = t1.window_bits; tm->windows = t1.windows; tm->max_chain = t1.max_chain;
+        if (!first) first = lr.ev[0];
+        float span = 0;
+        HIPCHK(hipEventElapsedTime(&span, first, lr.ev[9]));
+        if (span > tm->total_ms) tm->total_ms = span;
+        return H2V_OK;
+    });
+    if (rc) return rc;
+    if (r->co) {     // a coalesced call: its share of the one batch check that served its group (total_ms: the group's)
+        const float f = r->share;
+        tm->transcript_combiner_ms *= f; tm->g1_decompress_ms *= f; tm->prepare_ms *= f; tm->bucket_sort_ms *= f;
+        tm->bucket_accumulate_ms *= f; tm->bucket_reduce_ms *= f; tm->pairing_ms *= f;
+    }
+    return H2V_OK;
+}
+// the times of one batch check of an ordinary workspace (or of a lane): run_rlc's events
+static int rec_rlc_timings(const CallRec &r, h2v_rlc_timings *tm) {
+    const hipEvent_t *ev = r.ev;
+    memset(tm, 0, sizeof *tm);
+    HIPCHK(hipEventSynchronize(ev[9]));
+    HIPCHK(hipEventElapsedTime(&tm->g1_decompress_ms, ev[0], ev[1]));
+    HIPCHK(hipEventElapsedTime(&tm->transcript_combiner_ms, ev[2], ev[3]));
+    HIPCHK(hipEventElapsedTime(&tm->prepare_ms, ev[10], ev[4]));
+    HIPCHK(hipEventElapsedTime(&tm->bucket_sort_ms, ev[5], ev[6]));
+    HIPCHK(hipEventElapsedTime(&tm->bucket_accumulate_ms, ev[6], ev[7]));
+    HIPCHK(hipEventElapsedTime(&tm->bucket_reduce_ms, ev[7], ev[8]));
+    HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[8], ev[9]));
+    float a0, a1;
+    HIPCHK(hipEventElapsedTime(&a0, ev[0], ev[9]));
+    HIPCHK(hipEventElapsedTime(&a1, ev[2], ev[9]));
+    tm->total_ms = a0 > a1 ? a0 : a1;
+    tm->msm_terms = r.rlc_terms; tm->window_bits = r.rlc_c; tm->windows = r.rlc_W; tm->max_chain = r.rlc_chain;
     return H2V_OK;
 }
 

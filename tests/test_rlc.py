@@ -525,3 +525,171 @@ def test_rlc_one_stream_form(be, circuits):
             torch.cuda.synchronize()
             assert acc.cpu().tolist() == b.expected, (name, streams, flag)
             ws.close()
+
+
+# ---- call records (h2v_capi.hip: CallRec): every call of any kind takes ONE record, which knows its own call number
+def _one_pairing_reject(circuits, name, n, seed):
+    """n forged proofs of `name` whose proof 0 only the pairing rejects: a synth.Batch"""
+    from plutus_halo2_verifier_gen_amd import synth
+    vk, td, pl, dp, ov = circuits[name]
+    n_pi = vk.n_public_inputs
+    good = synth.forge_batch(vk, td, n, seed=seed, plan=pl, workers=8)
+    proofs = [good.proof(i) for i in range(n)]
+    insts = [good.instances[32 * n_pi * i:32 * n_pi * (i + 1)] for i in range(n)]
+    proofs[0], insts[0] = synth.corrupt(pl, proofs[0], insts[0], "wrong_pi", random.Random(seed))
+    off = [0]
+    for p_ in proofs:
+        off.append(off[-1] + len(p_))
+    return synth.Batch(n=n, proofs=b"".join(proofs), proof_off=off, instances=b"".join(insts), committed=good.committed,
+                       expected=[0] + [1] * (n - 1))
+
+
+def _msm_terms(pl, n):
+    """terms of the right-hand bucket MSM of an RLC call of n proofs: n per-proof terms per proof + one per VK base"""
+    return n * sum(1 for k, _ in pl.terms if k != 1) + sum(1 for k, _ in pl.terms if k == 1)
+
+
+def _coalesced_groups(ns, cap):
+    """which calls of sizes ns run together (include/h2v.h, COALESCING): a group runs when the next call would not fit `cap`
+    proofs, and at once when it is full"""
+    out, cur, count = [], [], 0
+    for j, n in enumerate(ns):
+        if count + n > cap:
+            out.append(cur)
+            cur, count = [], 0
+        cur.append(j)
+        count += n
+        if count >= cap:
+            out.append(cur)
+            cur, count = [], 0
+    return out + ([cur] if cur else [])
+
+
+@pytest.mark.parametrize("rlc", [True, False], ids=["rlc", "per-proof"])
+def test_a_late_coalesced_group_reports_into_no_newer_record(be, circuits, rlc):
+    """A multi-plan laned workspace with deferred joins and chunks of 128: a group of plan X (lookup_table) is opened by ONE
+    call that holds a proof only the pairing rejects, then 65 small honest calls of plan Y (simple_mul, 8 .. 48 proofs) fill and
+    run thirteen groups of their own while X's group stays open until the join.  X's call is then 65 calls back: H2V_E_ARG.
+    Every Y call within 63 back reports its own record: batch_accepted = 1 (RLC) and its share of its group's launch - each
+    field is the group's time x n / count, so field / n is the same for all the calls of one group (float32 products: equal to
+    1e-6 relative).  (Before call records, X's group wrote its share, its lane position and its failed batch check into the
+    record slot of the 64th Y call, which had taken the slot of X's call.)  Every accept[] is the construction's."""
+    import math
+    import torch
+    dev = torch.device("cuda", 0)
+    up = lambda x: torch.frombuffer(bytearray(x), dtype=torch.uint8).to(dev) if x else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    s = torch.cuda.Stream(device=dev)
+    from plutus_halo2_verifier_gen_amd import synth
+    vkY, tdY, plY, dpY, _ov = circuits["simple_mul"]
+    dpX = circuits["lookup_table"][3]
+    bX = _one_pairing_reject(circuits, "lookup_table", 4, 71)
+    bY = synth.forge_batch(vkY, tdY, 48, seed=72, plan=plY, workers=8)
+    dX = (up(bX.proofs), torch.tensor(bX.proof_off, dtype=torch.int64).to(dev), up(bX.instances), up(bX.committed))
+    dY = (up(bY.proofs), torch.tensor(bY.proof_off, dtype=torch.int64).to(dev), up(bY.instances), up(bY.committed))
+    ns = [8, 24, 16, 32, 48] * 13                       # (a Y call of n proofs: the pool's first n)
+    groups = _coalesced_groups(ns, 128)
+    assert len(ns) == 65 and all(sum(ns[j] for j in g) == 128 for g in groups)   # every Y group runs before the join
+    ws = be.Workspace.multi([dpX, dpY], 128, lanes=4, chunk=128)
+    ws.defer_joins(True)
+    ws.set_option(be.OPT_RLC_ROUTE, -1)
+    held = []
+
+    def call(dp, d, n, expected):
+        acc = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+        args = (n, ptr(d[0]), ptr(d[1]), ptr(d[2]), ptr(d[3]), acc.data_ptr(), None)
+        if rlc:
+            dp.verify_batch_rlc_device(*args, ws=ws, stream=s.cuda_stream, seed=bytes(range(32)))
+        else:
+            dp.verify_batch_device(*args, ws=ws, stream=s.cuda_stream)
+        held.append((acc, expected))
+
+    call(dpX, dX, bX.n, bX.expected)
+    for n in ns:
+        call(dpY, dY, n, [1] * n)
+    ws.join(s.cuda_stream)
+    s.synchronize()
+    for k, (acc, expected) in enumerate(held):
+        assert acc.cpu().tolist() == expected, k
+    record = (lambda back: ws.rlc_result(back)) if rlc else (lambda back: (None, ws.timings(back)))
+    fields = (["transcript_combiner_ms", "g1_decompress_ms", "prepare_ms", "bucket_sort_ms", "bucket_accumulate_ms",
+               "bucket_reduce_ms", "pairing_ms"] if rlc else
+              ["transcript_combiner_ms", "g1_decompress_ms", "g1_msm_ms", "g1_msm_fixed_ms", "pairing_ms"])
+    with pytest.raises(be.H2VError, match="h2v error -1"):
+        record(len(ns))                                  # X's call: 65 back
+    per_n = {}
+    for back in range(64):
+        j = len(ns) - 1 - back
+        ok, tm = record(back)
+        if rlc:
+            assert ok, back
+        per_n[j] = [getattr(tm, f) / ns[j] for f in fields]
+        print("Y call %d (%d back, n = %d): %s" % (j, back, ns[j], ["%.6g" % v for v in per_n[j]]))
+        assert tm.g1_decompress_ms > 0 and tm.pairing_ms > 0, back
+    for g in groups:
+        live = [j for j in g if j in per_n]
+        for j in live[1:]:
+            for f, a, b in zip(fields, per_n[live[0]], per_n[j]):
+                assert math.isclose(a, b, rel_tol=1e-6), (g, j, f, a, b)
+    ws.close()
+
+
+def test_ordinary_workspace_records_every_call(be, circuits):
+    """One ORDINARY workspace: a failing RLC call of n1 proofs, then a passing one of n2 != n1 proofs - rlc_result(1) is the
+    first call's (batch_accepted 0, msm_terms n1 n_var + n_fix), rlc_result(0) the second's.  Then a per-proof call takes the
+    next record: timings(0) is its own, rlc_result(0) of it and timings(1) of the RLC call are H2V_E_ARG, and the two RLC
+    calls are now 1 and 2 back."""
+    from plutus_halo2_verifier_gen_amd import synth
+    vk, td, pl, dp, ov = circuits["simple_mul"]
+    n1, n2 = 100, 60
+    bad = _one_pairing_reject(circuits, "simple_mul", n1, 73)
+    good = synth.forge_batch(vk, td, n2, seed=74, plan=pl, workers=8)
+    ws = be.Workspace(dp, 128)
+    assert ws.lanes()[0] == 1
+    ws.set_option(be.OPT_RLC_ROUTE, -1)              # (the second call meets the batch check whatever the first one met)
+    got, fb = dp.verify_batch_rlc(bad.proofs, bad.proof_off, bad.instances, bad.committed, ws=ws, seed=b"\x09" * 32)
+    assert list(got) == bad.expected and fb
+    got, fb = dp.verify_batch_rlc(good.proofs, good.proof_off, good.instances, good.committed, ws=ws, seed=b"\x0a" * 32)
+    assert list(got) == [1] * n2 and not fb
+    ok1, tm1 = ws.rlc_result(1)
+    ok0, tm0 = ws.rlc_result(0)
+    assert (ok1, tm1.msm_terms) == (False, _msm_terms(pl, n1))
+    assert (ok0, tm0.msm_terms) == (True, _msm_terms(pl, n2))
+    assert list(dp.verify_batch(good.proofs, good.proof_off, good.instances, good.committed, ws=ws)) == [1] * n2
+    assert ws.timings(0).pairing_ms > 0
+    with pytest.raises(be.H2VError, match="did not run in RLC mode"):
+        ws.rlc_result(0)
+    with pytest.raises(be.H2VError, match="ran in RLC mode"):
+        ws.timings(1)
+    ok1, tm1 = ws.rlc_result(1)
+    ok2, tm2 = ws.rlc_result(2)
+    assert (ok1, tm1.msm_terms) == (True, _msm_terms(pl, n2))
+    assert (ok2, tm2.msm_terms) == (False, _msm_terms(pl, n1))
+    ws.close()
+
+
+def test_host_buffer_fell_back_on_both_kinds_of_workspace(be, circuits):
+    """h2v_verify_batch_wait's fell_back, RLC mode: the same answer on an ordinary workspace (h2v_verify_batch_rlc) and on a
+    laned one (a submit / wait stream): 0 for a batch whose check passes, 1 for one that holds a proof only the pairing
+    rejects; the accept vectors are the construction's."""
+    from plutus_halo2_verifier_gen_amd import synth
+    vk, td, pl, dp, ov = circuits["simple_mul"]
+    n = 40
+    good = synth.forge_batch(vk, td, n, seed=75, plan=pl, workers=8)
+    bad = _one_pairing_reject(circuits, "simple_mul", n, 76)
+    ws = be.Workspace(dp, 64)
+    assert ws.lanes()[0] == 1
+    ws.set_option(be.OPT_RLC_ROUTE, -1)
+    ordinary = [dp.verify_batch_rlc(b.proofs, b.proof_off, b.instances, b.committed, ws=ws, seed=b"\x0b" * 32) for b in (good, bad)]
+    ws.close()
+    bs = be.BatchStream(dp, 64, 2, rlc=True, seed=b"\x0c" * 32)
+    bs.ws.set_option(be.OPT_RLC_ROUTE, -1)
+    keep = []
+    for b in (good, bad):
+        hb, k_ = dp.host_batch(b.proofs, b.proof_off, b.instances, b.committed)
+        keep.append(k_)
+        assert bs.push(hb, n) is None
+    laned = bs.drain()
+    bs.close()
+    for got in (ordinary, laned):
+        assert [(list(a), fb) for a, fb in got] == [([1] * n, False), (bad.expected, True)]
