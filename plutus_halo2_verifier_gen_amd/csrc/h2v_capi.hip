@@ -106,11 +106,75 @@ struct h2v_plan {
     void *fold_terms = nullptr;  // recursion: the 4-entry term table of the two fold MSMs
     void *vk_tab = nullptr;      // window tables of the VK bases (k_vk_tables at load)
     void *fix_tab = nullptr;     // all-window tables of the VK bases (k_vk_fixed_tables at load; non-recursive plans)
+    void *six_tab = nullptr;     // unit-coefficient line constants of the six-lane pairing engine + its dump constants (six_line_tables)
     uint32_t n_var = 0, n_fix = 0;  // per-proof terms [0, n_var), VK-base terms [n_var, n_var + n_fix) when the list is so ordered
     uint32_t n_squeezes = 0, stream_len = 0;
     uint64_t gen = 0;            // process-wide load counter: what caches key on (a freed plan's address may be reused)
     std::vector<uint32_t> trace_slots;
 };
+
+// The six-lane pairing engine multiplies by lines with a UNIT coefficient (h2v_pairing_six.hpp): from the blob's line records
+// [-lambda, xi (-lambda), c, xi c] (28-bit Montgomery limbs) the constants A = -lambda / c, B = 1 / c of every line of both loops,
+// laid out [line][loop][A0, A1, B0, B1][16 dwords], followed by [1, K1, K2, K1 K2] (2 x 12 Montgomery words each) with K_u the
+// product of loop u's c along the Miller schedule (k <- k^2 per bit, k <- k c per line): K times the unit-line Miller value is
+// the plan's.  One Fp2 inversion per line, 136 per plan load.  false: some c is zero (no table; the engine is not offered).
+#define SIX_NORM_DW (H2V_MILLER_LINES * 2 * 4 * 16)
+static bool six_line_tables(const uint8_t *l28_sg2, const uint8_t *l28_g2, std::vector<uint32_t> &out) {
+    using namespace h2vhost;
+    U384 c376;                                   // a Montgomery product with 2^376 turns x 2^392 into the host form x 2^384
+    c376.w[5] = (uint64_t)1 << (376 - 320);
+    auto slot_fp = [&](const uint8_t *slot) {
+        U384 m;
+        for (int i = 0; i < 14; i++) {
+            uint32_t limb;
+            memcpy(&limb, slot + 4 * i, 4);
+            const int bit = 28 * i;
+            m.w[bit >> 6] |= (uint64_t)limb << (bit & 63);
+            if ((bit & 63) > 36 && (bit >> 6) + 1 < 6) m.w[(bit >> 6) + 1] |= (uint64_t)limb >> (64 - (bit & 63));
+        }
+        return FpE{FP().mul(m, c376)};
+    };
+    auto put_slot = [&](uint32_t *dst, const FpE &a) {
+        uint8_t b[48];
+        fp_mont392_bytes(a, b);
+        U384 m;
+        memcpy(m.w, b, 48);
+        for (int i = 0; i < 14; i++) {
+            const int bit = 28 * i;
+            uint64_t v = m.w[bit >> 6] >> (bit & 63);
+            if ((bit & 63) > 36 && (bit >> 6) + 1 < 6) v |= m.w[(bit >> 6) + 1] << (64 - (bit & 63));
+            dst[i] = (uint32_t)(v & 0xfffffffu);
+        }
+        dst[14] = dst[15] = 0;
+    };
+    auto put_words = [&](uint32_t *dst, const FpE &a) {
+        uint8_t b[48];
+        fp_mont392_bytes(a, b);
+        memcpy(dst, b, 48);
+    };
+    out.assign(SIX_NORM_DW + 4 * 24, 0);
+    const uint8_t *src[2] = {l28_sg2, l28_g2};
+    F2 K[2] = {f2_one(), f2_one()};
+    int ln = 0;
+    for (int bit = 62; bit >= 0; bit--) {
+        const int steps = ((0xd201000000010000ull >> bit) & 1) ? 2 : 1;
+        for (int u = 0; u < 2; u++) K[u] = f2_sqr(K[u]);
+        for (int s2 = 0; s2 < steps; s2++, ln++)
+            for (int u = 0; u < 2; u++) {
+                const uint8_t *rec = src[u] + (size_t)ln * 8 * 64;
+                const F2 nl = {slot_fp(rec), slot_fp(rec + 64)}, cc = {slot_fp(rec + 4 * 64), slot_fp(rec + 5 * 64)};
+                if (f2_is_zero(cc)) return false;
+                const F2 B = f2_inv(cc), A = f2_mul(nl, B);
+                uint32_t *dst = out.data() + ((size_t)ln * 2 + u) * 4 * 16;
+                put_slot(dst, A.a); put_slot(dst + 16, A.b); put_slot(dst + 32, B.a); put_slot(dst + 48, B.b);
+                K[u] = f2_mul(K[u], cc);
+            }
+    }
+    if (ln != H2V_MILLER_LINES) return false;
+    const F2 ks[4] = {f2_one(), K[0], K[1], f2_mul(K[0], K[1])};
+    for (int q = 0; q < 4; q++) { put_words(out.data() + SIX_NORM_DW + 24 * q, ks[q].a); put_words(out.data() + SIX_NORM_DW + 24 * q + 12, ks[q].b); }
+    return true;
+}
 
 struct h2v_workspace {
     int device = 0;
@@ -447,6 +511,20 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
         }
     }
     d.vk_tab = (const uint32_t *)p->vk_tab;
+    {   // the six-lane pairing engine's own line constants (host math, once per plan)
+        std::vector<uint32_t> six;
+        if (six_line_tables(blob + w[H2V_HW_OFF_LINES28_SG2], blob + w[H2V_HW_OFF_LINES28_G2], six)) {
+            if (hipMalloc(&p->six_tab, six.size() * 4) != hipSuccess || hipMemcpy(p->six_tab, six.data(), six.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+                if (p->six_tab) (void)hipFree(p->six_tab);
+                (void)hipFree(p->vk_tab);
+                if (p->fold_terms) (void)hipFree(p->fold_terms);
+                (void)hipFree(p->blob); delete p;
+                return fail(H2V_E_DEVICE, "six-lane line table upload failed");
+            }
+            d.six_norm28 = (const uint32_t *)p->six_tab;
+            d.six_k = d.six_norm28 + SIX_NORM_DW;
+        }
+    }
     // fixed-base launches of the MSM (non-recursive plans whose VK-base terms are the tail of the term list, as plan.py
     // orders them): every window multiple of every VK base
     if (!ivc && n_bases) {
@@ -474,6 +552,7 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
             d.fix_c = fc; d.fix_W = fW;
             if (!okf) {
                 if (p->fix_tab) (void)hipFree(p->fix_tab);
+                if (p->six_tab) (void)hipFree(p->six_tab);
                 (void)hipFree(p->vk_tab);
                 (void)hipFree(p->blob); delete p;
                 return fail(H2V_E_DEVICE, "fixed-base table setup failed");
@@ -497,7 +576,8 @@ static void plan_release(h2v_plan *p) {   // the device memory; the host-side fa
     if (p->fold_terms) (void)hipFree(p->fold_terms);
     if (p->vk_tab) (void)hipFree(p->vk_tab);
     if (p->fix_tab) (void)hipFree(p->fix_tab);
-    p->blob = p->fold_terms = p->vk_tab = p->fix_tab = nullptr;
+    if (p->six_tab) (void)hipFree(p->six_tab);
+    p->blob = p->fold_terms = p->vk_tab = p->fix_tab = p->six_tab = nullptr;
 }
 extern "C" void h2v_plan_free(h2v_plan *p) {
     if (!p) return;
@@ -1310,7 +1390,8 @@ static uint32_t launch_pairing_impl(int impl, const H2vDevPlan &d, uint32_t n, c
     // impl 2 / 3 / 5 / 6 (probe): the narrow / the wide / the six-lane / the twelve-lane kernel whatever n
     const int forced = g_opts.v[H2V_OPT_PAIRING_ENGINE];
     if (impl == 1 && forced) impl = forced == 1 ? 0 : forced == 16 ? 2 : forced == 64 ? 3 : forced == 6 ? 5 : forced == 12 ? 6 : 4;   // 4: the two-proofs-per-wave engine
-    if (impl == 5 || (impl == 1 && !skip && prefer_six)) {
+    // (the six-lane engine needs its plan-load line table: a plan without one - some line coefficient c is zero - never takes it)
+    if ((impl == 5 || (impl == 1 && !skip && prefer_six)) && d.six_norm28) {
         hipLaunchKernelGGL(k_pairing_six, dim3((n + SIX_GROUPS - 1) / SIX_GROUPS), dim3(64), SIX_LDS_BYTES, st, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg);
         return 6u;
     }
@@ -3181,6 +3262,8 @@ extern "C" int h2v_probe_pairing_ex(const h2v_plan *p, uint32_t n, const uint8_t
     DevBuf din, doff, dsc, dpts, dvalid, der, dst, dacc, dtab;
     mp.d.lines28_sg2 = p->d.lines28_sg2;
     mp.d.lines28_g2 = p->d.lines28_g2;
+    mp.d.six_norm28 = p->d.six_norm28;
+    mp.d.six_k = p->d.six_k;
     if (mp.build(2, 1, p->d.lines_sg2, p->d.lines_g2) || upload_offsets(doff, n, 96) || din.alloc((size_t)n * 96) || dsc.alloc((size_t)n * 32) ||
         dpts.alloc((size_t)n * 192) || dvalid.alloc((size_t)n * 2) || der.alloc((size_t)n * 144) || dst.alloc((size_t)n * 4) || dacc.alloc(n))
         return fail(H2V_E_DEVICE, "probe setup failed");

@@ -67,11 +67,12 @@ H2V_DI void g1j28_dbl(G1J28 &r, const G1J28 &p) { g1j28_dbl_t<false>(r, p); }
 // Returns 0: generic sum in r; 1: p == +-q with equal y -> r = 2p; 2: p == -(+-q) -> the sum is infinity (r untouched).
 // The signs are arranged so that no product is subtracted (see g1j28_madd_ladder_t): -R, -HH, -HHH, -V.
 // In: both operands with the stored-point bounds.  Out: X (8,1) Y (2,1) Z (2,1).
-H2V_DI int g1j28_add(G1J28 &r, const G1J28 &p, const G1J28 &q, const bool neg_q) {
+// g1j28_add_zz takes zz = Z2^2, zzz = Z2^3 (both (2, 1)) from the caller: a chain that adds the SAME q again and again
+// (g1j28_mul_x_abs) computes them once - one square and one product less per addition (5019 multiply-adds).
+H2V_DI int g1j28_add_zz(G1J28 &r, const G1J28 &p, const G1J28 &q, const bool neg_q, const F28 &zz, const F28 &zzz) {
     F28 X1 = p.x, Y1 = p.y, Z1 = p.z, a, b, c, t;
-    f28_sqr(a, q.z);                                 // Z2^2       lam 4, v 16           (2, 1)
-    f28_mul(X1, X1, a);                              // U1         v 62                  (2, 1)
-    f28_mul(t, q.z, a); f28_mul(Y1, Y1, t);          // S1         v 8 ; 40              (2, 1)
+    f28_mul(X1, X1, zz);                             // U1         v 62                  (2, 1)
+    f28_mul(Y1, Y1, zzz);                            // S1         v 40                  (2, 1)
     f28_sqr(a, Z1);                                  // Z1^2                             (2, 1)
     f28_mul(b, q.x, a);                              // U2                               (2, 1)
     f28_mul(t, Z1, a);                               // Z1^3                             (2, 1)
@@ -98,6 +99,47 @@ H2V_DI int g1j28_add(G1J28 &r, const G1J28 &p, const G1J28 &q, const bool neg_q)
     f28_add(X1, X1, t); f28_carry(X1);               // X3 = R^2 - HHH - 2V              (8, 1)
     f28_add(t, a, X1);                               // -(V - X3)                        (10, 2)
     f28_dot2(Y1, c, t, Y1, b);                       // Y3 = (-R) (X3 - V) + S1 (-HHH)   (2, 1)
+    r.x = X1; r.y = Y1; r.z = Z1;                    //   lam 1 2 + 1 1 = 3, v 5 10 + 2 2 = 54
+    return 0;
+}
+H2V_DI int g1j28_add(G1J28 &r, const G1J28 &p, const G1J28 &q, const bool neg_q) {
+    F28 zz, zzz;
+    f28_sqr(zz, q.z);                                // Z2^2       lam 4, v 16           (2, 1)
+    f28_mul(zzz, q.z, zz);                           // Z2^3       lam 2, v 8            (2, 1)
+    return g1j28_add_zz(r, p, q, neg_q, zz, zzz);
+}
+// COMPLETE mixed addition r = p + q with q AFFINE and finite (qx, qy carried, v <= 2), p finite: the complete addition above
+// with Z2 = 1 (U1 = X1, S1 = Y1, Z3 = Z1 H: one square and four products less - 6M + 3S + one merged product = 3843
+// multiply-adds, the mixed addition's count) and the SAME exceptional-case tests and return values: the subgroup ladder runs on
+// curve points of any order, so H == 0 (p == +-q) can happen and must be seen.  H = U2 - X1 is therefore brought below 2p
+// and a hair by a fold (f28_fold: one 14-step carry chain, no product) before the exact zero test, where the complete
+// addition gets there by reducing U1 with a product.
+// In: p as a doubling returns it, X (<=19, 1) Y (<=2, 1) Z (4, 2) - the ladder adds right after a doubling.
+// Out: X (8,1) Y (2,1) Z (2,1).
+H2V_DI int g1j28_madd_complete(G1J28 &r, const G1J28 &p, const F28 &qx, const F28 &qy) {
+    F28 X1 = p.x, Y1 = p.y, Z1 = p.z, a, b, c, t;
+    f28_sqr(a, Z1);                                  // Z1^2       lam 4, v 16           (2, 1)
+    f28_mul(b, qx, a);                               // U2                               (2, 1)
+    f28_mul(t, Z1, a);                               // Z1^3       lam 2, v 8            (2, 1)
+    f28_mul(c, qy, t);                               // S2                               (2, 1)
+    F28_SUB(b, b, X1, 20, 1);                        // H = U2 - X1   limbs < 2^30       (22, 4)
+    f28_fold(b);                                     //   22 < 32: below 2p + p / 1024   (3, 1)
+    F28_SUB(c, Y1, c, 3, 1); f28_carry(c);           // -R = Y1 - S2                     (5, 1)
+    if (f28_is_zero_v5(b)) {
+        if (f28_is_zero_v5(c)) { g1j28_dbl(r, p); return 1; }
+        return 2;
+    }
+    f28_mul(Z1, Z1, b);                              // Z3 = Z1 H  lam 2, v 12           (2, 1)
+    f28_sqr(a, b);                                   // HH         v 9                   (2, 1)
+    F28_NEG(t, a, 3, 1);                             // -HH                              (3, 3)
+    f28_mul(b, b, t);                                // -HHH       lam 3, v 9            (2, 1)
+    f28_mul(a, X1, t);                               // -V = -X1 HH  lam 3, v 57         (2, 1)
+    f28_sqr(X1, c);                                  // R^2        v 25                  (2, 1)
+    f28_add(X1, X1, b);                              // R^2 - HHH                        (4, 2)
+    f28_mul_small<2>(t, a);                          // -2V                              (4, 2)
+    f28_add(X1, X1, t); f28_carry(X1);               // X3 = R^2 - HHH - 2V              (8, 1)
+    f28_add(t, a, X1);                               // -(V - X3)                        (10, 2)
+    f28_dot2(Y1, c, t, Y1, b);                       // Y3 = (-R) (X3 - V) + Y1 (-HHH)   (2, 1)
     r.x = X1; r.y = Y1; r.z = Z1;                    //   lam 1 2 + 1 1 = 3, v 5 10 + 2 2 = 54
     return 0;
 }
@@ -378,14 +420,33 @@ H2V_DI void g1j28_acc_add(G1J28 &acc, bool &acc_inf, const G1J28 &q, const bool 
     if (k == 2) acc_inf = true;
 }
 
-// [|x|]P, |x| = 0xd201000000010000, complete (P of any order on an a = 0 curve of odd order)
+// [|x|]P, |x| = 0xd201000000010000, complete (P of any order on an a = 0 curve of odd order).  The five additions know their
+// operand: AFFINE (p.z is the Montgomery one, p.x and p.y canonical: the subgroup test's first chain) - the complete mixed
+// addition; else Z2^2 and Z2^3 of the base are computed once for all five.  Every addition follows a doubling, so the
+// accumulator has the doubling's result bounds X (19,1) Y (2,1) Z (4,2).  r may alias p (written at the end).
+template <bool AFFINE>
 H2V_DN void g1j28_mul_x_abs(G1J28 &r, bool &r_inf, const G1J28 &p, const bool p_inf) {
     G1J28 acc = p;
     bool inf = p_inf;
+    F28 zz, zzz;
+    f28_set_zero(zz);
+    f28_set_zero(zzz);
+    if (!AFFINE && !p_inf) {
+        f28_sqr(zz, p.z);                        // Z2^2       lam 4, v 16           (2, 1)
+        f28_mul(zzz, p.z, zz);                   // Z2^3       lam 2, v 8            (2, 1)
+    }
 #pragma unroll 1
     for (int i = 62; i >= 0; i--) {
         if (!inf) g1j28_dbl_t<true>(acc, acc);   // the chain's 63 doublings with the multiplier inlined
-        if (((BLS_X_ABS >> i) & 1) && !p_inf) g1j28_acc_add(acc, inf, p, false);
+        if (((BLS_X_ABS >> i) & 1) && !p_inf) {
+            if (inf) {                           // (a chain that passed through infinity: start again from the base)
+                acc = p;
+                inf = false;
+            } else {
+                const int k = AFFINE ? g1j28_madd_complete(acc, acc, p.x, p.y) : g1j28_add_zz(acc, acc, p, false, zz, zzz);
+                if (k == 2) inf = true;
+            }
+        }
     }
     r = acc;
     r_inf = inf;
@@ -396,8 +457,8 @@ H2V_DN bool g1a_in_subgroup28(const G1A &a) {
     G1J28 p, t;
     bool tinf = false;
     g1j28_from_affine(p, a);
-    g1j28_mul_x_abs(t, tinf, p, false);
-    g1j28_mul_x_abs(t, tinf, t, tinf);   // [x^2]P
+    g1j28_mul_x_abs<true>(t, tinf, p, false);   // [x]P: the base is the affine input
+    g1j28_mul_x_abs<false>(t, tinf, t, tinf);   // [x^2]P: the base is [x]P, Jacobian
     if (tinf) return false;
     G1J tj;
     g1j28_to_g1j(tj, t, false);

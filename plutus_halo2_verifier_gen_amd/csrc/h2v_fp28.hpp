@@ -138,9 +138,12 @@ H2V_DI void f28_carry(F28 &a) {
     }
     a.l[13] += c;
 }
-// Fold a carried element with value < 32p below 2p (and a hair): the quotient by p is estimated from the top limb (never too
-// large, at most one too small) and q p subtracted with signed carries.  (tools/gen_six_tables.py: fold - the same integer
-// steps, checked on every multiple of p up to 32p, its neighbours and random values.)
+// Fold an element with value < 32p below 2p (and a hair, p / 1024 at most), carried: the quotient by p is estimated from the top
+// limb (never too large, at most one too small) and q p subtracted with signed carries.  The input need NOT be carried (limbs
+// below 2^31): the subtraction's carry chain normalises the limbs on the way, and the estimate from an uncarried top limb only
+// misses the carry the lower limbs would send up (below 8, against p's top limb near 2^24.7).  (tools/gen_six_tables.py: fold -
+// the same integer steps, checked on every multiple of p up to 32p, its neighbours and random values, each carried, with every
+// lower limb at its maximum, and in random uncarried forms.)
 H2V_DI void f28_fold(F28 &a) {
     const uint32_t q = __umulhi(a.l[13], FP_FOLD_M);
     int64_t t = 0;

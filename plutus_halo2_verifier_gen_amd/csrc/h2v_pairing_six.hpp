@@ -14,8 +14,15 @@
 // U - V is taken in two's complement columns (|column| < 2^63) and reduced with arithmetic carries, p added at the end.
 // Wrapped terms (x xi) take the xi on the A side: XA = xi a = (a0 - a1, a0 + a1).  The cyclotomic squaring is five
 // products into U, U, V, W, W (re = U - V, im = W + V: S_b M_b and 2 b0 b1 serve both parts); the lane forms 3 r -/+ 2 g itself
-// and folds it below 2p with a quotient estimate from the top limb (f28_fold).  Per line the products
-// b = (-lambda) xP of the two loops are taken by lanes 0..3 of the group just before the two line steps (one product each).
+// and folds it below 2p with a quotient estimate from the top limb (f28_fold).
+// Miller lines have a UNIT coefficient: the plan's line c + ((-lambda) xP) w^2 + yP w^3 is divided by its own c (an Fp2 constant
+// of the fixed G2 argument; any factor in Fp2* of the Miller value dies in the easy part of the final exponentiation), so
+//   f (l / c) = f + f (a w^2 + b w^3),   a = A xP,  b = B yP,   A = -lambda / c,  B = 1 / c  (a table derived at plan load),
+// is TWO Karatsuba terms per lane and the lane's own staged coefficient added after the reduction (8 units of 196 multiply-adds
+// where the three-term line took 11).  Per round the eight products A_u xP_u, B_u yP_u (two parts each, both loops) are taken just
+// before the line steps: six in one pass (one per lane), the last two in a second.  The value grows by the added coefficient
+// from the squaring to the round's last line and falls back with the next squaring; the loop's staging takes re <= 12p,
+// im <= 7p (gen_six_tables.py: miller_round_bounds), and the value is folded once after the loop.
 // Tables and the headroom argument: tools/gen_six_tables.py (value-level check against big-integer Fp12 arithmetic and a
 // limb-level model of this code with the column bounds asserted).  Program, line tables, semantics: h2v_pairing_coop.hpp.
 //
@@ -133,12 +140,14 @@ H2V_DI void six_reduce(F28 &r, uint64_t (&acc)[28]) {
     }
 }
 // NT Karatsuba terms from the lane's table row (4 slot bytes per term: x0 y0 x1 y1) -> (re, im), both below 3p.
+// addself (line steps): the lane's own staged coefficient (its A slots) is added to the result - as f R into columns 14..27
+// before the reductions, whose final carry then serves both; the read comes before the write of the same slots below.
 // The result does not come back through the call: it is written, carried, into the lane's own A slots (2k, 2k + 1) - every
 // operand slot is dead once the last term has been read (one wave per block: the lanes have all read before any writes) -
 // and the caller reads it from there (six_result).  A 28-dword struct is returned through private memory by the calling
 // convention: a store, a wait for it, and a load per engine call, ~550 calls per pairing (round 3: the kernel's scratch
 // traffic).  keep (per lane): leave the A slots as they are - the staged input survives (line steps of a skipped loop).
-H2V_DN void six_kara(const Six c, const int tab_row_byte, const int nt, const bool keep) {
+H2V_DN void six_kara(const Six c, const int tab_row_byte, const int nt, const bool keep, const bool addself) {
     const uint8_t *tab = reinterpret_cast<const uint8_t *>(coop_lds + SIX_TAB_OFF) + tab_row_byte;
     uint64_t U[28], V[28], W[28];
 #pragma unroll
@@ -158,6 +167,12 @@ H2V_DN void six_kara(const Six c, const int tab_row_byte, const int nt, const bo
     for (int i = 0; i < 27; i++) {   // (column 27 holds no product)
         W[i] -= U[i] + V[i];
         U[i] -= V[i];
+    }
+    if (addself) {
+        uint32_t f0[14], f1[14];
+        six_load_pair(f0, f1, six_slot(c, SIX_SLOT_A + 2 * c.k), six_slot(c, SIX_SLOT_A + 2 * c.k + 1));
+#pragma unroll
+        for (int i = 0; i < 14; i++) { U[14 + i] += f0[i]; W[14 + i] += f1[i]; }
     }
     SixF2 r;
     six_reduce<false>(r.im, W);
@@ -227,14 +242,17 @@ H2V_DI SixF2 six_unpack(const SixRegs &z) {
     return r;
 }
 
-// ---- staging (values: v <= 6, carried).  Slots: six_tables.h / gen_six_tables.py
+// ---- staging (values: v <= 6, carried; MILLER - the loop's squaring and lines - re <= 12p, im <= 7p).  Slots: six_tables.h / gen_six_tables.py
+template <bool MILLER = false>
 H2V_DI void six_stage_a(const Six &c, const SixF2 &a, const int xa_from) {
     if (!c.act) return;
     six_store(six_slot(c, SIX_SLOT_A + 2 * c.k), a.re);
     six_store(six_slot(c, SIX_SLOT_A + 2 * c.k + 1), a.im);
-    if (c.k >= xa_from) {   // xi a = (re - im + 7p, re + im)
+    if (c.k >= xa_from) {   // xi a = (re - im + 7p, re + im); in the Miller loop + 11p (SIX_MILLER_K)
         F28 t, x0, x1;
-        F28_NEG(t, a.im, 7, 1);
+        static_assert(SIX_MILLER_K == 11, "the bias table of the Miller loop's staging");
+        if (MILLER) F28_NEG(t, a.im, 11, 1);
+        else F28_NEG(t, a.im, 7, 1);
         f28_add(x0, a.re, t);
         f28_carry(x0);
         f28_add(x1, a.re, a.im);
@@ -260,24 +278,24 @@ H2V_DI SixF2 six_mul(const Six &c, const SixF2 &a, const SixF2 &b) {
     six_stage_a(c, a, 1);
     six_stage_b(c, b);
     __syncthreads();
-    six_kara(c, SIX_TAB_MUL_B + c.k * 4 * SIX_N_MUL, SIX_N_MUL, false);
+    six_kara(c, SIX_TAB_MUL_B + c.k * 4 * SIX_N_MUL, SIX_N_MUL, false, false);
     __syncthreads();
     return six_result(c, SIX_SLOT_A);
 }
-H2V_DI SixF2 six_sqr(const Six &c, const SixF2 &a) {
-    six_stage_a(c, a, 3);
+H2V_DI SixF2 six_sqr(const Six &c, const SixF2 &a) {   // (the Miller loop's squaring)
+    six_stage_a<true>(c, a, 3);
     six_stage_d(c, a);
     __syncthreads();
-    six_kara(c, SIX_TAB_SQR_B + c.k * 4 * SIX_N_SQR, SIX_N_SQR, false);
+    six_kara(c, SIX_TAB_SQR_B + c.k * 4 * SIX_N_SQR, SIX_N_SQR, false, false);
     __syncthreads();
     return six_result(c, SIX_SLOT_A);
 }
-// f times the line of loop LOOP; skip (per proof: that loop's G1 argument is infinity): f comes back unchanged
+// f times the unit-coefficient line of loop LOOP; skip (per proof: that loop's G1 argument is infinity): f comes back unchanged
 template <int LOOP>
 H2V_DI SixF2 six_line(const Six &c, const SixF2 &f, const bool skip) {
-    six_stage_a(c, f, 3);
+    six_stage_a<true>(c, f, 3);
     __syncthreads();
-    six_kara(c, (LOOP == 1 ? SIX_TAB_LINE1_B : SIX_TAB_LINE2_B) + c.k * 4 * SIX_N_LINE, SIX_N_LINE, skip);
+    six_kara(c, (LOOP == 1 ? SIX_TAB_LINE1_B : SIX_TAB_LINE2_B) + c.k * 4 * SIX_N_LINE, SIX_N_LINE, skip, true);
     __syncthreads();
     return six_result(c, SIX_SLOT_A);
 }
@@ -309,6 +327,10 @@ H2V_DI SixF2 six_csqr(const Six &c, const SixF2 &a) {
     const SixF2 g = six_result(c, SIX_SLOT_A);      // (a itself, read back: nothing of it stays live across the engine call)
     // h_k = 3 Q_k - 2 g_k (k even) / + 2 g_k (k odd), folded: 3 r + (13p - 2g | 2g) is below 20p (r < 2.2p, g < 6p), the fold
     // brings it below 2p.  (The other engines multiply g by the constants -/+ 2/3 inside the sum: two products more per lane.)
+    // The sum goes to the fold UNCARRIED (limbs below 2^31): the fold's own signed carry chain normalises the limbs, and its
+    // quotient estimate from the uncarried top limb is short of the carried one's by the carry the lower limbs would have sent
+    // up (at most 7 against p's top limb near 2^24.7) - still never too large, still at most one too small
+    // (gen_six_tables.py: fold, checked with every lower limb at its maximum).
     const bool minus = (c.k & 1) == 0;
 #pragma unroll
     for (int i = 0; i < 14; i++) {
@@ -316,8 +338,6 @@ H2V_DI SixF2 six_csqr(const Six &c, const SixF2 &a) {
         r.re.l[i] = 3u * r.re.l[i] + (minus ? F28_BIAS_13_2[i] - g0 : g0);
         r.im.l[i] = 3u * r.im.l[i] + (minus ? F28_BIAS_13_2[i] - g1 : g1);
     }
-    f28_carry(r.re);
-    f28_carry(r.im);
     f28_fold(r.re);
     f28_fold(r.im);
     return r;
@@ -377,14 +397,15 @@ H2V_DN H2V_NO_TAIL_MARK SixRegs six_inv_raw(const Six c, const SixRegs fr, bool 
     o.im = f28_pack(r.im);
     return o;
 }
-// The constants of line `idx` as the lane's share of the copy into the wave-shared slots: 8 slots x 16 dwords in the plan
-// (14 limbs + 2 of padding), lane -> slot lane / 8, dwords 2 (lane % 8)..
-H2V_DI uint2 six_line_share(const uint32_t *lines28, int idx, int lane) {
-    return reinterpret_cast<const uint2 *>(lines28 + (size_t)idx * 8 * 16)[lane];
+// The constants of line `idx` of BOTH loops as the lane's share of the copy into the wave-shared slots: 2 x 4 slots
+// [A0, A1, B0, B1] x 16 dwords in the plan-load table (14 limbs + 2 of padding), lane -> slot lane / 8, dwords 2 (lane % 8)..
+H2V_DI uint2 six_line_share(const uint32_t *norm28, int idx, int lane) {
+    return reinterpret_cast<const uint2 *>(norm28 + (size_t)idx * 8 * 16)[lane];
 }
-H2V_DI void six_line_store(int shared_slot, const uint2 v, int lane) {
+H2V_DI void six_line_store(const uint2 v, int lane) {
+    static_assert(SIX_SLOT_LN2 == SIX_SLOT_LN1 + 4, "the two loops' constants are one run of eight slots");
     if ((lane & 7) == 7) return;    // the padding
-    uint32_t *dst = coop_lds + (shared_slot - SIX_SHARED_BASE + (lane >> 3)) * SIX_SLOT_DW + 2 * (lane & 7);
+    uint32_t *dst = coop_lds + (SIX_SLOT_LN1 - SIX_SHARED_BASE + (lane >> 3)) * SIX_SLOT_DW + 2 * (lane & 7);
     dst[0] = v.x;
     dst[1] = v.y;
 }
@@ -476,31 +497,37 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
             vars[d] = x;
         } break;
         case COOP_OP_MILLER: {
-            // Per bit of |x| below the leading one: F = F^2, then one or two rounds of { the products b = (-lambda) xP of both
-            // loops' lines (lanes 0..3: loop = k >> 1, part = k & 1), line of loop 1, line of loop 2 }.  The constants of the
-            // next round's two lines are fetched a round ahead into two registers per lane.
+            // Per bit of |x| below the leading one: F = F^2, then one or two rounds of { the products a = A xP, b = B yP of both
+            // loops' lines: lane k < 4 takes part k & 1 of a of loop 1 + (k >> 1), lanes 4, 5 the parts of b of loop 1, and a second
+            // pass (lanes 0, 1) those of b of loop 2; line of loop 1, line of loop 2 }.  The constants of the next round's
+            // two lines are fetched a round ahead into one register pair per lane.
             SixF2 f = vars[COOP_VAR_F];
             int ln = 0;
-            uint2 c1 = six_line_share(plan.lines28_sg2, 0, lane), c2 = six_line_share(plan.lines28_g2, 0, lane);
+            uint2 cn = six_line_share(plan.six_norm28, 0, lane);
+            const int u = (c.k >> 1) & 1, part = c.k & 1;
+            const int xs1 = c.k < 4 ? (u ? SIX_SLOT_LN2 : SIX_SLOT_LN1) + part : SIX_SLOT_LN1 + 2 + part;
+            const int ys1 = c.k < 4 ? (u ? SIX_SLOT_PX2 : SIX_SLOT_PX1) : SIX_SLOT_PY1;
 #pragma unroll 1
             for (int bit = 62; bit >= 0; bit--) {
                 f = six_sqr(c, f);
                 const int steps = ((BLS_X_ABS >> bit) & 1) ? 2 : 1;
 #pragma unroll 1
                 for (int s2 = 0; s2 < steps; s2++, ln++) {
-                    six_line_store(SIX_SLOT_LN1, c1, lane);
-                    six_line_store(SIX_SLOT_LN2, c2, lane);
-                    if (ln + 1 < H2V_MILLER_LINES) { c1 = six_line_share(plan.lines28_sg2, ln + 1, lane); c2 = six_line_share(plan.lines28_g2, ln + 1, lane); }
+                    six_line_store(cn, lane);
+                    if (ln + 1 < H2V_MILLER_LINES) cn = six_line_share(plan.six_norm28, ln + 1, lane);
                     __syncthreads();
                     {
-                        const int u = (c.k >> 1) & 1, part = c.k & 1;
-                        const F28Regs z = six_prod(c, (u ? SIX_SLOT_LN2 : SIX_SLOT_LN1) + part, u ? SIX_SLOT_PX2 : SIX_SLOT_PX1);
-                        if (c.act && c.k < 4) six_store(six_slot(c, (u ? SIX_SLOT_T2 : SIX_SLOT_T1) + part), f28_unpack(z.a, z.b, z.c, z.d));
+                        F28Regs z = six_prod(c, xs1, ys1);
+                        if (c.act) six_store(six_slot(c, SIX_SLOT_T + c.k), f28_unpack(z.a, z.b, z.c, z.d));
+                        z = six_prod(c, SIX_SLOT_LN2 + 2 + part, SIX_SLOT_PY2);
+                        if (c.act && c.k < 2) six_store(six_slot(c, SIX_SLOT_T + 6 + c.k), f28_unpack(z.a, z.b, z.c, z.d));
                     }
                     f = six_line<1>(c, f, skip1);                   // (its staging barrier also covers the T slots)
                     f = six_line<2>(c, f, skip2);
                 }
             }
+            f28_fold(f.re);                                         // (below 12p, 7p -> below 2p and a hair: what the program's
+            f28_fold(f.im);                                         //  CONJ / INV / MUL take)
             vars[COOP_VAR_F] = f;
         } break;
         case COOP_OP_EXPX: {   // d = a^x (x < 0: conjugate of a^|x|)
@@ -536,13 +563,26 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
         } break;
         case COOP_OP_DUMP: {
             if (dbg && live && c.act) {
-                Fp o, oc;
-                f28_to_fp(oc, vars[a].re);
-                fp_from_mont(o, oc);
+                Fp2 v;
+                f28_to_fp(v.c0, vars[a].re);
+                f28_to_fp(v.c1, vars[a].im);
+                if (d == 0) {
+                    // dump 0 is the Miller value.  With unit-coefficient lines it is the plan's Miller value divided by the
+                    // product K of the lines' c along the loop's schedule (an Fp2 constant per loop, coefficient w^0: the
+                    // conjugation leaves it alone); the probe reports the plan's value, so K goes back in HERE - the verdict's path
+                    // never touches it.  six_k: [1, K1, K2, K1 K2] by the proof's skip flags (a skipped loop has no lines).
+                    const uint32_t *kp = plan.six_k + ((skip1 ? 0 : 1) + (skip2 ? 0 : 2)) * 24;
+                    Fp2 kk, t;
+#pragma unroll
+                    for (int q = 0; q < 12; q++) { kk.c0.v[q] = kp[q]; kk.c1.v[q] = kp[12 + q]; }
+                    fp2_mul(t, v, kk);
+                    v = t;
+                }
+                Fp o;
+                fp_from_mont(o, v.c0);
 #pragma unroll
                 for (int q = 0; q < 12; q++) dbg[((size_t)i * 24 + 12 * d + 2 * c.k) * 12 + q] = o.v[q];
-                f28_to_fp(oc, vars[a].im);
-                fp_from_mont(o, oc);
+                fp_from_mont(o, v.c1);
 #pragma unroll
                 for (int q = 0; q < 12; q++) dbg[((size_t)i * 24 + 12 * d + 2 * c.k + 1) * 12 + q] = o.v[q];
             }

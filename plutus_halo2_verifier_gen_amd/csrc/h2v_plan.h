@@ -68,6 +68,12 @@ struct H2vDevPlan {
     const uint32_t *lines_g2;
     const uint32_t *lines28_sg2; // 68 * 8 operand slots of 16 dwords (28-bit limbs): cooperative pairing engine
     const uint32_t *lines28_g2;
+    // six-lane pairing engine, derived at plan load from the two tables above (not part of the blob): per line both loops'
+    // unit-coefficient constants [A0, A1, B0, B1] = (-lambda / c, 1 / c) as operand slots of 16 dwords, 68 x 2 x 4 of them; NULL
+    // when some c is zero (the launcher then never takes that engine).  six_k: [1, K1, K2, K1 K2] (Fp2, 2 x 12 Montgomery words
+    // each), K_u = the product of loop u's c along the Miller schedule - read by the probe's dump path alone.
+    const uint32_t *six_norm28;
+    const uint32_t *six_k;
     const uint32_t *trace;     // n_trace * 2    (slot id, register)
     // recursion (IVC): terms [0, n_main_terms) are the proof's own MSM, term n_main_terms is acc_left, the rest
     // acc_right and its fixed bases; acc_idx = public-input positions of (x_hi, x_lo, y_hi, y_lo) x (left, right)
