@@ -371,11 +371,13 @@ int h2v_probe_quad_madd(int device, const uint32_t *pq, int neg, uint32_t *out);
  * RAW records: 14 dwords = 14 limbs of 28 bits, Montgomery form R = 2^392, limbs and values as large as the bounds stated in
  * the headers allow (h2v_probe_field takes canonical operands and cannot carry such limbs).
  *   op & 15:  0: a b + c d    1: a^2 + c d    2: 2 a^2 + c d      n records each in a, b, c, d (b unused by 1, 2); out n x 14
+ *             3: a b    4: a^2     the plain product and squaring (fp_mont28, fp_montsqr28); b (for 4), c and d are passed like
+ *                                  the other ops' and unused
  *             8: 2P    9: P + Q with Q affine (mixed, unchecked)    10: P + Q (complete but for infinity)
  *                P = n x 42 dwords (X, Y, Z) in a, Q likewise in b (Z ignored by 9); c, d unused (may be NULL);
  *                out n x 44 dwords: X, Y, Z, the return code of the full addition (0 sum, 1 doubled, 2 infinity), 0
- *   op | 16:  the forms with the multiplier inlined (ops 0 .. 9)      op | 64: subtract Q (ops 9, 10)
- * tests/test_field_dot2_gpu.py */
+ *   op | 16:  the forms with the multiplier inlined (ops 0 .. 4, 8, 9)      op | 64: subtract Q (ops 9, 10)
+ * tests/test_field_dot2_gpu.py, tests/test_field_carry_chain.py */
 int h2v_probe_f28_dot2(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
                        uint32_t *out);
 /* e(p1, s_g2 of plan) == e(p2, G2) for n pairs of compressed G1 points; out[i] = 1/0 */

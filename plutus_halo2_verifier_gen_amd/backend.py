@@ -542,11 +542,12 @@ def probe_g1_msm_fixed(plan: DevicePlan, scalar_rows, bases_per_lane: int = 1):
 
 # h2v_probe_f28_dot2 op codes (include/h2v.h)
 DOT2_MUL, DOT2_SQR, DOT2_SQR2, DOT2_DBL, DOT2_MADD, DOT2_ADD, DOT2_INLINE, DOT2_NEG_Q = 0, 1, 2, 8, 9, 10, 16, 64
+DOT2_PLAIN_MUL, DOT2_PLAIN_SQR = 3, 4   # a b through fp_mont28, a^2 through fp_montsqr28
 
 
 def probe_f28_dot2(op: int, a, b=None, c=None, d=None, device: int = 0):
-    """h2v_probe_f28_dot2 on raw lazily reduced records.  Field ops (0..2): a, b, c, d are lists of 14-limb records, the result
-    a list of 14-limb records.  Point ops (8..10): a and b are lists of (X, Y, Z) triples of 14-limb records, the result a list
+    """h2v_probe_f28_dot2 on raw lazily reduced records.  Field ops (0..4): a, b, c, d are lists of 14-limb records (one the op does not
+    use may be left out), the result a list of 14-limb records.  Point ops (8..10): a and b are lists of (X, Y, Z) triples of 14-limb records, the result a list
     of ((X, Y, Z) records, return code)."""
     n = len(a)
     field = (op & 15) < 8
@@ -559,8 +560,8 @@ def probe_f28_dot2(op: int, a, b=None, c=None, d=None, device: int = 0):
         return (C.c_uint32 * len(flat))(*flat)
 
     out = (C.c_uint32 * (n * (14 if field else 44)))()
-    if field and b is None:
-        b = a
+    if field:
+        b, c, d = (a if r is None else r for r in (b, c, d))
     check(lib().h2v_probe_f28_dot2(device, op, n, pack(a), pack(b), pack(c), pack(d), out))
     if field:
         return [list(out[14 * i:14 * i + 14]) for i in range(n)]

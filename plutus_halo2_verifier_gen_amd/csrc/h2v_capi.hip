@@ -3093,7 +3093,7 @@ extern "C" int h2v_probe_f28_dot2(int device, int op, uint32_t n, const uint32_t
     int rc = pick_device(device);
     if (rc) return rc;
     const int what = op & 15;
-    const bool field = what <= 2, point = what >= 8 && what <= 10;
+    const bool field = what <= 4, point = what >= 8 && what <= 10;
     if ((op & ~(15 | 16 | 64)) != 0 || !(field || point) || (what == 10 && (op & 16)) || n == 0 || !a || !out) return fail(H2V_E_ARG, "bad argument");
     if (field ? (!b || !c || !d) : (what != 8 && !b)) return fail(H2V_E_ARG, "bad argument");
     const size_t in_b = (size_t)n * (field ? 14 : 42) * 4, out_b = (size_t)n * (field ? 14 : 44) * 4;

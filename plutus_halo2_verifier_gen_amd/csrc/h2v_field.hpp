@@ -192,6 +192,19 @@ H2V_DI void fp_from28(uint32_t (&r)[12], const uint32_t (&t)[14]) {
         r[j] = v;
     }
 }
+// One term of a column: acc += x y, and the partial sum passes through fp28_chain so that the column stays ONE chain of
+// v_mad_u64_u32 in source order, the previous column's carry (acc >> 28) riding as the addend of the first.  Left alone, the
+// optimiser reassociates a column into "products first, carry last" and pays a separate 64-bit addition per column (27 per
+// product).  llvm.amdgcn.softwqm is opaque to the IR passes and, in a kernel without whole-quad mode (every compute kernel), is
+// lowered to a COPY that the register coalescer removes: no instruction, and no inline-asm statement for the hazard recogniser to
+// pad with an s_nop.  (Forms compared on the GPU: tools/ubench/mont_carry.hip)
+extern "C" __device__ uint64_t fp28_chain(uint64_t) __asm("llvm.amdgcn.softwqm.i64");
+H2V_DI void fp28_mac(uint64_t &acc, uint32_t x, uint32_t y) {
+    acc = fp28_chain(acc + (uint64_t)x * y);
+}
+// the column's LAST term: two addends cannot be reassociated, and the column's value is then the multiply-add's own result (through
+// fp28_chain it came back as a copy that the allocator kept apart from the limb cut out of it: a v_mov per column of the upper half)
+H2V_DI void fp28_mac_end(uint64_t &acc, uint32_t x, uint32_t y) { acc += (uint64_t)x * y; }
 // t = a*b/2^392 mod p in 28-bit limbs (value < 2p; limbs normalised, top limb may carry the excess)
 H2V_DI void fp_mont28(uint32_t (&t)[14], const uint32_t (&a)[14], const uint32_t (&b)[14]) {
     uint32_t m[14];
@@ -199,19 +212,20 @@ H2V_DI void fp_mont28(uint32_t (&t)[14], const uint32_t (&a)[14], const uint32_t
 #pragma unroll
     for (int k = 0; k < 14; k++) {
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc += (uint64_t)a[i] * b[k - i];
+        for (int i = 0; i <= k; i++) fp28_mac(acc, a[i], b[k - i]);
 #pragma unroll
-        for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = 0; i < k; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
         m[k] = ((uint32_t)acc * FP_N0_28) & FP28_MASK;
-        acc += (uint64_t)m[k] * FP_MOD28[0];
+        fp28_mac_end(acc, m[k], FP_MOD28[0]);
         acc >>= 28;
     }
 #pragma unroll
     for (int k = 14; k < 27; k++) {
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)a[i] * b[k - i];
+        for (int i = k - 13; i < 14; i++) fp28_mac(acc, a[i], b[k - i]);
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = k - 13; i < 13; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
+        fp28_mac_end(acc, m[13], FP_MOD28[k - 13]);
         t[k - 14] = (uint32_t)acc & FP28_MASK;
         acc >>= 28;
     }
@@ -226,21 +240,22 @@ H2V_DI void fp_montsqr28(uint32_t (&t)[14], const uint32_t (&a)[14]) {
 #pragma unroll
     for (int k = 0; k < 14; k++) {
 #pragma unroll
-        for (int i = 0; 2 * i < k; i++) acc += (uint64_t)d[i] * a[k - i];
-        if ((k & 1) == 0) acc += (uint64_t)a[k / 2] * a[k / 2];
+        for (int i = 0; 2 * i < k; i++) fp28_mac(acc, d[i], a[k - i]);
+        if ((k & 1) == 0) fp28_mac(acc, a[k / 2], a[k / 2]);
 #pragma unroll
-        for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = 0; i < k; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
         m[k] = ((uint32_t)acc * FP_N0_28) & FP28_MASK;
-        acc += (uint64_t)m[k] * FP_MOD28[0];
+        fp28_mac_end(acc, m[k], FP_MOD28[0]);
         acc >>= 28;
     }
 #pragma unroll
     for (int k = 14; k < 27; k++) {
 #pragma unroll
-        for (int i = k - 13; 2 * i < k; i++) acc += (uint64_t)d[i] * a[k - i];
-        if ((k & 1) == 0) acc += (uint64_t)a[k / 2] * a[k / 2];
+        for (int i = k - 13; 2 * i < k; i++) fp28_mac(acc, d[i], a[k - i]);
+        if ((k & 1) == 0) fp28_mac(acc, a[k / 2], a[k / 2]);
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = k - 13; i < 13; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
+        fp28_mac_end(acc, m[13], FP_MOD28[k - 13]);
         t[k - 14] = (uint32_t)acc & FP28_MASK;
         acc >>= 28;
     }
@@ -255,23 +270,24 @@ H2V_DI void fp_mont28_dot2(uint32_t (&t)[14], const uint32_t (&a)[14], const uin
 #pragma unroll
     for (int k = 0; k < 14; k++) {
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc += (uint64_t)a[i] * b[k - i];
+        for (int i = 0; i <= k; i++) fp28_mac(acc, a[i], b[k - i]);
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc += (uint64_t)c[i] * d[k - i];
+        for (int i = 0; i <= k; i++) fp28_mac(acc, c[i], d[k - i]);
 #pragma unroll
-        for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = 0; i < k; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
         m[k] = ((uint32_t)acc * FP_N0_28) & FP28_MASK;
-        acc += (uint64_t)m[k] * FP_MOD28[0];
+        fp28_mac_end(acc, m[k], FP_MOD28[0]);
         acc >>= 28;
     }
 #pragma unroll
     for (int k = 14; k < 27; k++) {
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)a[i] * b[k - i];
+        for (int i = k - 13; i < 14; i++) fp28_mac(acc, a[i], b[k - i]);
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)c[i] * d[k - i];
+        for (int i = k - 13; i < 14; i++) fp28_mac(acc, c[i], d[k - i]);
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = k - 13; i < 13; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
+        fp28_mac_end(acc, m[13], FP_MOD28[k - 13]);
         t[k - 14] = (uint32_t)acc & FP28_MASK;
         acc >>= 28;
     }
@@ -288,25 +304,26 @@ H2V_DI void fp_mont28_dot2_sqr(uint32_t (&t)[14], const uint32_t (&a)[14], const
 #pragma unroll
     for (int k = 0; k < 14; k++) {
 #pragma unroll
-        for (int i = 0; 2 * i < k; i++) acc += (uint64_t)o[i] * a[k - i];
-        if ((k & 1) == 0) acc += (uint64_t)(a[k / 2] * (uint32_t)W) * a[k / 2];
+        for (int i = 0; 2 * i < k; i++) fp28_mac(acc, o[i], a[k - i]);
+        if ((k & 1) == 0) fp28_mac(acc, a[k / 2] * (uint32_t)W, a[k / 2]);
 #pragma unroll
-        for (int i = 0; i <= k; i++) acc += (uint64_t)c[i] * d[k - i];
+        for (int i = 0; i <= k; i++) fp28_mac(acc, c[i], d[k - i]);
 #pragma unroll
-        for (int i = 0; i < k; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = 0; i < k; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
         m[k] = ((uint32_t)acc * FP_N0_28) & FP28_MASK;
-        acc += (uint64_t)m[k] * FP_MOD28[0];
+        fp28_mac_end(acc, m[k], FP_MOD28[0]);
         acc >>= 28;
     }
 #pragma unroll
     for (int k = 14; k < 27; k++) {
 #pragma unroll
-        for (int i = k - 13; 2 * i < k; i++) acc += (uint64_t)o[i] * a[k - i];
-        if ((k & 1) == 0) acc += (uint64_t)(a[k / 2] * (uint32_t)W) * a[k / 2];
+        for (int i = k - 13; 2 * i < k; i++) fp28_mac(acc, o[i], a[k - i]);
+        if ((k & 1) == 0) fp28_mac(acc, a[k / 2] * (uint32_t)W, a[k / 2]);
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)c[i] * d[k - i];
+        for (int i = k - 13; i < 14; i++) fp28_mac(acc, c[i], d[k - i]);
 #pragma unroll
-        for (int i = k - 13; i < 14; i++) acc += (uint64_t)m[i] * FP_MOD28[k - i];
+        for (int i = k - 13; i < 13; i++) fp28_mac(acc, m[i], FP_MOD28[k - i]);
+        fp28_mac_end(acc, m[13], FP_MOD28[k - 13]);
         t[k - 14] = (uint32_t)acc & FP28_MASK;
         acc >>= 28;
     }

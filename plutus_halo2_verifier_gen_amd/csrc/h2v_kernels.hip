@@ -1607,9 +1607,10 @@ k_probe_quad_madd(const uint32_t *__restrict__ pq, int neg, uint32_t *__restrict
 // dev probe of the merged products and of the three one-lane group formulas built on them, on RAW lazily reduced records (14
 // limbs of 28 bits that may be uncarried: the bounds of h2v_fp28.hpp are the caller's to respect - or to sit on).
 //   op & 15:  0: a b + c d   1: a^2 + c d   2: 2 a^2 + c d          (records of 14 dwords in a, b, c, d; out: 14 dwords)
+//             3: a b         4: a^2           (the plain product and squaring, fp_mont28 / fp_montsqr28; c, d read and unused)
 //             8: 2P          9: P + Q, Q affine (mixed)   10: P + Q  (P = 42 dwords X, Y, Z in a, Q likewise in b; out: 44 dwords:
 //                                                                     X, Y, Z, the return code of g1j28_add, 0)
-//   op & 16:  the inlined multiplier forms (ops 0..9)      op & 64: subtract Q (ops 9, 10)
+//   op & 16:  the inlined multiplier forms (ops 0..4, 8, 9)      op & 64: subtract Q (ops 9, 10)
 extern "C" __global__ void __launch_bounds__(64)
 k_probe_f28_dot2(int op, uint32_t n, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ c,
                  const uint32_t *__restrict__ d, uint32_t *__restrict__ out) {
@@ -1623,7 +1624,9 @@ k_probe_f28_dot2(int op, uint32_t n, const uint32_t *__restrict__ a, const uint3
         for (int k = 0; k < 14; k++) { x.l[k] = a[(size_t)i * 14 + k]; y.l[k] = b[(size_t)i * 14 + k]; u.l[k] = c[(size_t)i * 14 + k]; v.l[k] = d[(size_t)i * 14 + k]; }
         if (what == 0) { if (inl) f28_dot2_inl(r, x, y, u, v); else f28_dot2(r, x, y, u, v); }
         else if (what == 1) { if (inl) f28_dot2_sqr_inl<1>(r, x, u, v); else f28_dot2_sqr<1>(r, x, u, v); }
-        else { if (inl) f28_dot2_sqr_inl<2>(r, x, u, v); else f28_dot2_sqr<2>(r, x, u, v); }
+        else if (what == 2) { if (inl) f28_dot2_sqr_inl<2>(r, x, u, v); else f28_dot2_sqr<2>(r, x, u, v); }
+        else if (what == 3) { if (inl) f28_mul_inl(r, x, y); else f28_mul(r, x, y); }
+        else { if (inl) f28_sqr_inl(r, x); else f28_sqr(r, x); }
 #pragma unroll
         for (int k = 0; k < 14; k++) out[(size_t)i * 14 + k] = r.l[k];
         return;

@@ -44,7 +44,7 @@ cp $O/prof_$TAG/*/*kernel_stats.csv $O/${TAG}_kernel_stats.csv
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profa_$TAG -- python3 bench.py $ARGS_L --steps 20 --warmup 3 --timed-only --no-alone --pipeline streams --inflight 1 --hint $INF $FORCE > $O/profa_$TAG.log 2>&1 || fail 3 $? $O/profa_$TAG.log
 cp $O/profa_$TAG/*/*kernel_stats.csv $O/${TAG}_kernel_stats_alone.csv
 # 4. counters, separate passes, same one-step-at-a-time command
-for c in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU" "FETCH_SIZE" "WRITE_SIZE"; do
+for c in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_VALU SQ_INSTS_SALU" "FETCH_SIZE" "WRITE_SIZE"; do
   n=$(echo $c | cut -d" " -f1)
   timeout -k 10 300 rocprofv3 --pmc $c --output-format csv -d $O/pmc_${TAG}_$n -- python3 bench.py $ARGS_L --steps 2 --warmup 1 --timed-only --no-alone --pipeline streams --inflight 1 --hint $INF $FORCE > $O/pmc_${TAG}_$n.log 2>&1 || fail "4 ($n)" $? $O/pmc_${TAG}_$n.log
 done
@@ -53,7 +53,7 @@ cp $O/${TAG}_pmc_summary.txt profiles/${TAG}_pmc_summary.txt    # (on the box: t
 # 5. the line
 timeout -k 10 400 python bench.py $ARGS $FORCE --full --steps $((240 * CO)) > $O/b_$TAG.log 2>&1 || fail 5 $? $O/b_$TAG.log
 grep "^{" $O/b_$TAG.log | tail -1 > $O/${TAG}_bench.json
-grep -E "INSTS_VALU|FETCH|WRITE_SIZE" $O/${TAG}_pmc_summary.txt
+grep -E "INSTS_VALU|INSTS_SALU|FETCH|WRITE_SIZE" $O/${TAG}_pmc_summary.txt
 head -8 $O/${TAG}_kernel_stats.csv | cut -d, -f1-5
 head -8 $O/${TAG}_kernel_stats_alone.csv | cut -d, -f1-5
 cut -c1-300 $O/${TAG}_bench.json
