@@ -12,9 +12,12 @@
 // The sums x0 + x1, y0 + y1 are formed LIMB-WISE in registers (uncarried), so W - U - V equals sum(x0 y1 + x1 y0) column by column: the
 // imaginary part's columns are non-negative (unsigned reduction; W itself may wrap modulo 2^64 on the way - harmless);
 // U - V is taken in two's complement columns (|column| < 2^63) and reduced with arithmetic carries, p added at the end.
-// Wrapped terms (x xi) take the xi on the A side: XA = xi a = (a0 - a1, a0 + a1).  The cyclotomic squaring is five
-// products into U, U, V, W, W (re = U - V, im = W + V: S_b M_b and 2 b0 b1 serve both parts); the lane forms 3 r -/+ 2 g itself
-// and folds it below 2p with a quotient estimate from the top limb (f28_fold).
+// Wrapped terms (x xi) take the xi on the A side: XA = xi a = (a0 - a1, a0 + a1).  The cyclotomic squaring is four
+// products into three sets (re = P1 + P2 - P4, im = P1 + P3 + P4: the set of P1 + P2 starts as a copy of P1's, taken as the
+// addend of its first multiply-adds; six_csqr_products); the lane forms 3 r -/+ 2 g itself and folds it below 2p with a quotient
+// estimate from the top limb (f28_fold).  A run of squarings - the hard part's x^|x| has runs of 1, 2, 3, 9, 32 and 16 between its
+// multiplications - is ONE out-of-line call (six_csqr_run): the value stays in registers from one squaring's fold to the next one's
+// staging.
 // Miller lines have a UNIT coefficient: the plan's line c + ((-lambda) xP) w^2 + yP w^3 is divided by its own c (an Fp2 constant
 // of the fixed G2 argument; any factor in Fp2* of the Miller value dies in the easy part of the final exponentiation), so
 //   f (l / c) = f + f (a w^2 + b w^3),   a = A xP,  b = B yP,   A = -lambda / c,  B = 1 / c  (a table derived at plan load),
@@ -40,7 +43,7 @@
 #define SIX_GROUPS 10
 #define SIX_SLOT_DW 14
 #define SIX_GROUP_DW (SIX_N_GROUP_SLOTS * SIX_SLOT_DW)
-#define SIX_TAB_DW ((6 * 4 * SIX_N_MUL + 6 * 4 * SIX_N_SQR + 2 * 6 * 4 * SIX_N_LINE + 6 * 16) / 4)
+#define SIX_TAB_DW ((6 * 4 * SIX_N_MUL + 6 * 4 * SIX_N_SQR + 2 * 6 * 4 * SIX_N_LINE + 6 * 3 * SIX_N_CSQR) / 4)
 #define SIX_TAB_OFF (SIX_N_SHARED_SLOTS * SIX_SLOT_DW)
 #define SIX_GRP_OFF ((SIX_TAB_OFF + SIX_TAB_DW + 1) & ~1)
 #define SIX_LDS_BYTES ((size_t)(SIX_GRP_OFF + SIX_GROUPS * SIX_GROUP_DW) * 4)
@@ -182,39 +185,97 @@ H2V_DN void six_kara(const Six c, const int tab_row_byte, const int nt, const bo
         six_store(six_slot(c, SIX_SLOT_A + 2 * c.k + 1), r.im);
     }
 }
-// cyclotomic squaring: five products (x + x2) y into U, U, V, W, W (3 slot bytes each; gen_six_tables.py: csqr_table) ->
-// re = U - V (signed columns), im = W + V, reduced: re below 2.2p, im below 1.2p.  The lane finishes with 3 r -/+ 2 g (six_csqr).
-// Result into the lane's B slots (the doubled operand D, dead by then); the A slots keep g for the caller.
-H2V_DN void six_csqr_engine(const Six c, const int tab_row_byte) {
-    const uint8_t *tab = reinterpret_cast<const uint8_t *>(coop_lds + SIX_TAB_OFF) + tab_row_byte;
-    uint64_t U[28], V[28], W[28];
+// an engine's result (or a staged value) back from the lane's slots `base + 2k`, `base + 2k + 1`; shadow lanes read group 9's
+H2V_DI SixF2 six_result(const Six &c, const int base) {
+    SixF2 r;
+    six_load_pair(r.re.l, r.im.l, six_slot(c, base + 2 * c.k), six_slot(c, base + 2 * c.k + 1));
+    return r;
+}
+// acc2 = acc + x y, acc2 not yet written: the first multiply-add into each column of acc2 (row 0 and the last of every other
+// row) takes acc's column as its addend - v_mad_u64_u32 writes D = S0 S1 + S2 with D apart from S2, so the copy costs nothing.
+H2V_DI void six_mac_from(uint64_t (&acc2)[28], const uint64_t (&acc)[28], const uint32_t (&x)[14], const uint32_t (&y)[14]) {
 #pragma unroll
-    for (int i = 0; i < 28; i++) { U[i] = 0; V[i] = 0; W[i] = 0; }
+    for (int i = 0; i < 14; i++)
+#pragma unroll
+        for (int j = 0; j < 14; j++) acc2[i + j] = ((i == 0 || j == 13) ? acc[i + j] : acc2[i + j]) + (uint64_t)x[i] * y[j];
+}
+// cyclotomic squaring: four products (x + x2) y, P1..P4 (3 slot bytes each; gen_six_tables.py: csqr_table), into three sets
+//   A = P1     B = A + P2 (B starts as a copy of A)     A += P3     C = P4     ->  re = B - C (signed columns), im = A + C,
+// reduced: re below 2.2p, im below 1.2p.  The lane finishes with 3 r -/+ 2 g (six_csqr_run).
+H2V_DI void six_csqr_products(const Six &c, const uint8_t *tab, SixF2 &r) {
+    uint64_t A[28], B[28], C[28];
+#pragma unroll
+    for (int i = 0; i < 28; i++) { A[i] = 0; C[i] = 0; }
+    B[27] = 0;                       // (column 27 holds no product)
     uint32_t x[14], x2[14], y[14];
-#define SIX_CSQR_SET(ACC, T)                                                                             \
+#define SIX_CSQR_OPS(T)                                                                                  \
     do {                                                                                                 \
         six_load_pair(x, x2, six_slot(c, tab[3 * (T)]), six_slot(c, tab[3 * (T) + 1]));                  \
         six_load(y, six_slot(c, tab[3 * (T) + 2]));                                                      \
         _Pragma("unroll") for (int i_ = 0; i_ < 14; i_++) x[i_] += x2[i_];                               \
-        six_mac(ACC, x, y);                                                                              \
     } while (0)
-    SIX_CSQR_SET(U, 0);
-    SIX_CSQR_SET(U, 1);
-    SIX_CSQR_SET(V, 2);
-    SIX_CSQR_SET(W, 3);
-    SIX_CSQR_SET(W, 4);
-#undef SIX_CSQR_SET
+    SIX_CSQR_OPS(0);
+    six_mac(A, x, y);
+    SIX_CSQR_OPS(1);
+    six_mac_from(B, A, x, y);
+    SIX_CSQR_OPS(2);
+    six_mac(A, x, y);
+    SIX_CSQR_OPS(3);
+    six_mac(C, x, y);
+#undef SIX_CSQR_OPS
 #pragma unroll
-    for (int i = 0; i < 27; i++) {   // (column 27 holds no product)
-        U[i] -= V[i];
-        W[i] += V[i];
+    for (int i = 0; i < 27; i++) {
+        B[i] -= C[i];
+        A[i] += C[i];
     }
-    SixF2 r;
-    six_reduce<true>(r.re, U);
-    six_reduce<false>(r.im, W);
-    if (c.act) {
-        six_store(six_slot(c, SIX_SLOT_B + 2 * c.k), r.re);
-        six_store(six_slot(c, SIX_SLOT_B + 2 * c.k + 1), r.im);
+    six_reduce<true>(r.re, B);
+    six_reduce<false>(r.im, A);
+}
+// A RUN of n cyclotomic squarings as one call: the value comes in and goes back through the lane's A slots (staged by the caller,
+// read by six_result), and between two squarings of the run it stays in registers - per squaring: staging (D = 2x into the B slots,
+// M into its slot; x itself is in the A slots already), the four products and two reductions, h = 3 r -/+ 2 g, the fold, and x back
+// into the A slots, which is both the next squaring's staging and the run's result.  g is read back from the A slots after the
+// products (nothing of x stays live while the three accumulator sets are).  Barriers as around every engine call: after the
+// staging, and after the last read (the lane's own g) before any lane writes again.
+H2V_DN void six_csqr_run(const Six c, const int tab_row_byte, const int n) {
+    const uint8_t *tab = reinterpret_cast<const uint8_t *>(coop_lds + SIX_TAB_OFF) + tab_row_byte;
+    SixF2 x = six_result(c, SIX_SLOT_A);
+    const bool minus = (c.k & 1) == 0;
+#pragma unroll 1
+    for (int rep = 0; rep < n; rep++) {
+        if (c.act) {
+            F28 d0, d1, m;
+            F28_SUB(m, x.re, x.im, 7, 1);          // M = re - im + 7p                         (13, 4)
+            f28_carry(m);
+            f28_mul_small<2>(d0, x.re);            // D = 2x, uncarried                        (12, 2)
+            f28_mul_small<2>(d1, x.im);
+            six_store(six_slot(c, SIX_SLOT_B + 2 * c.k), d0);
+            six_store(six_slot(c, SIX_SLOT_B + 2 * c.k + 1), d1);
+            six_store(six_slot(c, SIX_C_M(c.k)), m);
+        }
+        __syncthreads();
+        SixF2 r;
+        six_csqr_products(c, tab, r);
+        const SixF2 g = six_result(c, SIX_SLOT_A);
+        // h_k = 3 Q_k - 2 g_k (k even) / + 2 g_k (k odd), folded: 3 r + (13p - 2g | 2g) is below 20p (r < 2.2p, g < 6p), the fold
+        // brings it below 2p.  (The other engines multiply g by the constants -/+ 2/3 inside the sum: two products more per lane.)
+        // The sum goes to the fold UNCARRIED (limbs below 2^31): the fold's own signed carry chain normalises the limbs, and its
+        // quotient estimate from the uncarried top limb is short of the carried one's by the carry the lower limbs would have sent
+        // up (at most 7 against p's top limb near 2^24.7) - still never too large, still at most one too small
+        // (gen_six_tables.py: fold, checked with every lower limb at its maximum).
+#pragma unroll
+        for (int i = 0; i < 14; i++) {
+            const uint32_t g0 = g.re.l[i] << 1, g1 = g.im.l[i] << 1;
+            x.re.l[i] = 3u * r.re.l[i] + (minus ? F28_BIAS_13_2[i] - g0 : g0);
+            x.im.l[i] = 3u * r.im.l[i] + (minus ? F28_BIAS_13_2[i] - g1 : g1);
+        }
+        f28_fold(x.re);
+        f28_fold(x.im);
+        __syncthreads();
+        if (c.act) {
+            six_store(six_slot(c, SIX_SLOT_A + 2 * c.k), x.re);
+            six_store(six_slot(c, SIX_SLOT_A + 2 * c.k + 1), x.im);
+        }
     }
 }
 // one product of two staged slots, reduced (< 2p)
@@ -228,12 +289,6 @@ H2V_DN F28Regs six_prod(const Six c, const int xs, const int ys) {
     F28 r;
     six_reduce<false>(r, acc);
     return f28_pack(r);
-}
-// an engine's result (or a staged value) back from the lane's slots `base + 2k`, `base + 2k + 1`; shadow lanes read group 9's
-H2V_DI SixF2 six_result(const Six &c, const int base) {
-    SixF2 r;
-    six_load_pair(r.re.l, r.im.l, six_slot(c, base + 2 * c.k), six_slot(c, base + 2 * c.k + 1));
-    return r;
 }
 H2V_DI SixF2 six_unpack(const SixRegs &z) {
     SixF2 r;
@@ -299,48 +354,15 @@ H2V_DI SixF2 six_line(const Six &c, const SixF2 &f, const bool skip) {
     __syncthreads();
     return six_result(c, SIX_SLOT_A);
 }
-H2V_DI SixF2 six_csqr(const Six &c, const SixF2 &a) {
+H2V_DI SixF2 six_csqr(const Six &c, const SixF2 &a, const int n) {   // a^(2^n), a in the cyclotomic subgroup
     if (c.act) {
-        F28 na, d0, d1, m;
-        F28_NEG(na, a.im, 7, 1);               // 7p - im                                  (7, 3)
-        f28_add(m, a.re, na);                  // re - im + 7p                             (13, 4)
-        f28_carry(na);
-        f28_carry(m);
-        f28_mul_small<2>(d0, a.re);            // D = 2a, uncarried                        (12, 2)
-        f28_mul_small<2>(d1, a.im);
-        six_store(six_slot(c, SIX_SLOT_A + 2 * c.k), a.re);       // (S = re + im is formed by the engine)
+        six_store(six_slot(c, SIX_SLOT_A + 2 * c.k), a.re);
         six_store(six_slot(c, SIX_SLOT_A + 2 * c.k + 1), a.im);
-        six_store(six_slot(c, SIX_SLOT_C_NA + c.k), na);
-        six_store(six_slot(c, SIX_SLOT_B + 2 * c.k), d0);
-        six_store(six_slot(c, SIX_SLOT_B + 2 * c.k + 1), d1);
-        six_store(six_slot(c, SIX_C_M(c.k)), m);
-        if (c.k == 2) {                        // ND2 = 2 NA_2, uncarried                  (14, 2)
-            F28 nd;
-            f28_mul_small<2>(nd, na);
-            six_store(six_slot(c, SIX_SLOT_C_ND2), nd);
-        }
     }
     __syncthreads();
-    six_csqr_engine(c, SIX_TAB_CSQR_B + c.k * 16);
+    six_csqr_run(c, SIX_TAB_CSQR_B + c.k * 3 * SIX_N_CSQR, n);
     __syncthreads();
-    SixF2 r = six_result(c, SIX_SLOT_B);
-    const SixF2 g = six_result(c, SIX_SLOT_A);      // (a itself, read back: nothing of it stays live across the engine call)
-    // h_k = 3 Q_k - 2 g_k (k even) / + 2 g_k (k odd), folded: 3 r + (13p - 2g | 2g) is below 20p (r < 2.2p, g < 6p), the fold
-    // brings it below 2p.  (The other engines multiply g by the constants -/+ 2/3 inside the sum: two products more per lane.)
-    // The sum goes to the fold UNCARRIED (limbs below 2^31): the fold's own signed carry chain normalises the limbs, and its
-    // quotient estimate from the uncarried top limb is short of the carried one's by the carry the lower limbs would have sent
-    // up (at most 7 against p's top limb near 2^24.7) - still never too large, still at most one too small
-    // (gen_six_tables.py: fold, checked with every lower limb at its maximum).
-    const bool minus = (c.k & 1) == 0;
-#pragma unroll
-    for (int i = 0; i < 14; i++) {
-        const uint32_t g0 = g.re.l[i] << 1, g1 = g.im.l[i] << 1;
-        r.re.l[i] = 3u * r.re.l[i] + (minus ? F28_BIAS_13_2[i] - g0 : g0);
-        r.im.l[i] = 3u * r.im.l[i] + (minus ? F28_BIAS_13_2[i] - g1 : g1);
-    }
-    f28_fold(r.re);
-    f28_fold(r.im);
-    return r;
+    return six_result(c, SIX_SLOT_A);
 }
 H2V_DI SixF2 six_conj(const Six &c, const SixF2 &a) {   // w -> -w: odd coefficients change sign.  a: v <= 5
     SixF2 r = a;
@@ -491,10 +513,8 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
             vars[d] = six_mul(c, x, y);
         } break;
         case COOP_OP_CSQR: {
-            SixF2 x = vars[a];
-#pragma unroll 1
-            for (int rep = 0; rep < b; rep++) x = six_csqr(c, x);
-            vars[d] = x;
+            const SixF2 x = vars[a];
+            vars[d] = six_csqr(c, x, b);
         } break;
         case COOP_OP_MILLER: {
             // Per bit of |x| below the leading one: F = F^2, then one or two rounds of { the products a = A xP, b = B yP of both
@@ -532,10 +552,15 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
         } break;
         case COOP_OP_EXPX: {   // d = a^x (x < 0: conjugate of a^|x|)
             SixF2 x = vars[a];
+            int run = 0;               // squarings since the last multiplication: runs of 1, 2, 3, 9, 32 and 16
 #pragma unroll 1
             for (int bit = 62; bit >= 0; bit--) {
-                x = six_csqr(c, x);
-                if ((BLS_X_ABS >> bit) & 1) {
+                run++;
+                const bool set = ((BLS_X_ABS >> bit) & 1) != 0;
+                if (!set && bit != 0) continue;
+                x = six_csqr(c, x, run);
+                run = 0;
+                if (set) {
                     const SixF2 y = vars[a];
                     x = six_mul(c, x, y);
                 }

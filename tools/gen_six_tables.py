@@ -12,8 +12,9 @@ and an engine call (MUL: 6 terms, SQR: 4, LINE: 2 and the lane's own coefficient
 equal to sum(x0 y1 + x1 y0) because the engine forms the sums LIMB-WISE in registers, so unsigned), one Montgomery reduction each: 3 NT + 2 products
 of 196 multiply-adds where the one-coefficient-per-lane engine spends 2 (2 NT + 1) on the same Fp2 coefficient.
 Wrapped terms (x xi) take the xi on the A side: XA = xi a = (a0 - a1, a0 + a1).
-The cyclotomic squaring is five products into U, U, V, W, W (operands S = re + im - formed by the engine -, M = re - im,
-NA = -im, D = 2a): re = U - V, im = W + V; the lane forms h = 3 (reduced) -/+ 2 g itself and folds it below 2p by a quotient
+The cyclotomic squaring is four products P1..P4 into three sets (operands S = re + im - formed by the engine -, M = re - im,
+D = 2a; no negated operand): re = P1 + P2 - P4, im = P1 + P3 + P4, the set of P1 + P2 starting as a copy of P1's through the
+addend of its first multiply-adds (csqr_table); the lane forms h = 3 (reduced) -/+ 2 g itself and folds it below 2p by a quotient
 estimate from the top limb (the +-2/3 constant products of the other engines cost two products more).
 A group's operand slots are 56 bytes (14 limbs, no padding) and 38 in number: 2.1 KB per proof, 23 KB per wave of ten.
 """
@@ -40,10 +41,8 @@ XA1 = lambda k: 13 + 2 * (k - 1)
 B0 = lambda k: 22 + 2 * k               # MUL: b ; SQR / CSQR: D = 2a ; between the squaring and the lines of a Miller round the
 B1 = lambda k: 23 + 2 * k               # line products: a = A xP of loop 1 at 22, 23, of loop 2 at 24, 25; b = B yP at 26, 27 and 28, 29
 TA1, TA2, TB1, TB2 = (22, 23), (24, 25), (26, 27), (28, 29)
-# cyclotomic squaring: NA, ND2 in the XA area, M = re - im behind them and in the P area; S = re + im is formed by the engine (A0 + A1)
-C_NA = lambda k: 12 + k
-C_ND2 = 18
-C_M = lambda k: 19 + k if k < 3 else 31 + k     # 19..21 behind ND2, 34..36 over the points
+# cyclotomic squaring: M = re - im in the XA area and in the P area; S = re + im is formed by the engine (A0 + A1)
+C_M = lambda k: 19 + k if k < 3 else 31 + k     # 19..21, 34..36 over the points
 PX1, PY1, PX2, PY2 = 34, 35, 36, 37
 N_GROUP_SLOTS = 38
 SH = 64
@@ -56,7 +55,7 @@ LN_A0, LN_A1, LN_B0, LN_B1 = 0, 1, 2, 3
 C23P, C23N, ZERO = SH + 16, SH + 17, SH + 18
 N_SHARED_SLOTS = 19
 C23 = 2 * pow(3, -1, P) % P
-N_MUL, N_SQR, N_LINE, N_CSQR = 6, 4, 2, 5
+N_MUL, N_SQR, N_LINE, N_CSQR = 6, 4, 2, 4
 ZT = (ZERO, ZERO, ZERO, ZERO)
 
 
@@ -115,28 +114,30 @@ def line_table(loop):
 
 
 def csqr_table():
-    """Per lane FIVE products (x + x2) * y into the accumulators U, U, V, W, W; the engine ends with re = U - V (signed columns),
-    im = W + V, one reduction each (formulas: gen_coop_tables.csqr_table; x2 = ZERO except for S_k = re_k + im_k, which the engine
-    forms from A0(k), A1(k)).  Granger-Scott with the pair (a, b) of the lane's kind:
-       even    a^2 + xi b^2:  re = S_a M_a + S_b M_b - 2 b0 b1     im = 2 a0 a1 + S_b M_b + 2 b0 b1     (V = b0 D_b1 is SHARED, and so
-                                                                                                         is the product S_b M_b: U and W)
-       odd     2 a b:         re = a0 D_b0 + (-a1) D_b1            im = a0 D_b1 + a1 D_b0               (V = 0)
-       xi-odd  2 xi a b:      re = D_a0 M_b + (-2 a1) S_b          im = S_b D_a0 + D_a1 M_b             (V = 0)
-    The lane then forms h = 3 (reduced) -/+ 2 g_k itself and folds it below 2p (h2v_pairing_six.hpp: six_csqr)."""
+    """Per lane FOUR products (x + x2) * y, P1..P4, into three sets of column accumulators
+           A = P1      B = A + P2 (B starts as a copy of A: the addend of P2's first multiply-add per column)      A += P3      C = P4
+       and the engine ends with re = B - C = P1 + P2 - P4 (signed columns), im = A + C = P1 + P3 + P4, one reduction each
+       (x2 = ZERO except where a sum is formed limb-wise by the engine: S = re + im from A0, A1; 2 S from B0, B1; 2 M from M, M).
+       Granger-Scott with the pair (a, b) of the lane's kind, D = 2 (re, im), M = re - im (+ 7p), S = re + im:
+       kind                      P1 (both parts)    P2                 P3                   P4
+       even    a^2 + xi b^2      S_b M_b            S_a M_a            a0 D_a1              b0 D_b1
+       odd     2 a b             a0 D_b1            D_a0 M_b           D_a1 M_b             a1 D_b1
+       xi-odd  2 xi a b          M_a D_b1           (M_a + M_a) M_b    (D_a0 + D_a1) M_b    (a0 + a1) D_b1        (xi a = (M_a, S_a))
+       odd:  re = 2 a0 b1 + 2 a0 (b0 - b1) - 2 a1 b1,  im = 2 a0 b1 + 2 a1 (b0 - b1) + 2 a1 b1.  No lane has a null product, and no
+       negated operand is staged.  The lane then forms h = 3 (reduced) -/+ 2 g_k itself and folds it below 2p (h2v_pairing_six.hpp: six_csqr_run)."""
     kind = {0: ("even", 0, 3), 3: ("odd", 0, 3), 1: ("xi_odd", 2, 5), 4: ("even", 2, 5), 2: ("even", 1, 4), 5: ("odd", 1, 4)}
-    Z = (ZERO, ZERO, ZERO)
     one = lambda x, y: (x, ZERO, y)
     SxM = lambda k: (A0(k), A1(k), C_M(k))
     tab = []
     for k in range(6):
         ty, a, b = kind[k]
         if ty == "even":
-            sets = [SxM(a), SxM(b), one(A0(b), B1(b)), one(A0(a), B1(a)), SxM(b)]
+            sets = [SxM(b), SxM(a), one(A0(a), B1(a)), one(A0(b), B1(b))]
         elif ty == "odd":
-            sets = [one(A0(a), B0(b)), one(C_NA(a), B1(b)), Z, one(A0(a), B1(b)), one(A1(a), B0(b))]
+            sets = [one(A0(a), B1(b)), one(B0(a), C_M(b)), one(B1(a), C_M(b)), one(A1(a), B1(b))]
         else:
-            assert a == 2
-            sets = [one(B0(a), C_M(b)), (A0(b), A1(b), C_ND2), Z, (A0(b), A1(b), B0(a)), one(B1(a), C_M(b))]
+            sets = [one(C_M(a), B1(b)), (C_M(a), C_M(a), C_M(b)), (B0(a), B1(a), C_M(b)), (A0(a), A1(a), B1(b))]
+        assert len(sets) == N_CSQR
         tab.append(sets)
     return tab
 
@@ -189,10 +190,9 @@ def stage_d(s, f):
 def stage_csqr(s, g):
     s.put(C23P, C23 * R % P); s.put(C23N, (-C23) % P * R % P)     # Montgomery forms of +-2/3
     for k in range(6):
-        s.put(A0(k), g[k][0]); s.put(A1(k), g[k][1]); s.put(C_NA(k), 7 * P - g[k][1])
+        s.put(A0(k), g[k][0]); s.put(A1(k), g[k][1])
         s.put_scaled(B0(k), A0(k), 2); s.put_scaled(B1(k), A1(k), 2)
         s.put(C_M(k), g[k][0] + 7 * P - g[k][1])
-    s.put_scaled(C_ND2, C_NA(2), 2)
 
 
 # ----------------------------------------------------------------------------- the device engine, limb for limb
@@ -370,18 +370,29 @@ def uncarried_forms(v, rng):
     return forms
 
 
-def csqr_engine(sets, s, g, k):
-    """sets: the lane's five products; g = (re, im) limbs of the lane's own coefficient as staged in A0(k), A1(k)"""
+CSQR_RE_BOUND, CSQR_IM_BOUND = 22 * P // 10, 12 * P // 10      # the reduced parts of a squaring (operands staged by stage_csqr: v <= 6)
+
+
+def csqr_engine(sets, s, g, k, reduced=None):
+    """sets: the lane's four products P1..P4; g = (re, im) limbs of the lane's own coefficient as staged in A0(k), A1(k).
+    reduced: a list that receives the two reduced parts (before 3 r -/+ 2 g), for the tests"""
     lam3 = lambda t: 14 * (s.lam[t[0]] + s.lam[t[1]]) * s.lam[t[2]]
-    assert lam3(sets[0]) + lam3(sets[1]) + RED < (1 << 63) and lam3(sets[2]) < (1 << 63), "re columns"
-    assert lam3(sets[2]) + lam3(sets[3]) + lam3(sets[4]) + RED < (1 << 64), "im columns"
-    U, V, W = [0] * 28, [0] * 28, [0] * 28
-    for acc, (x, x2, y) in zip((U, U, V, W, W), sets):
-        mac(acc, [a + b for a, b in zip(s[x], s[x2])], s[y])
-    assert max(U) < (1 << 63) and max(V) < (1 << 63)
-    re = [(U[i] - V[i]) & M64 for i in range(28)]
-    im = [(W[i] + V[i]) & M64 for i in range(28)]
+    assert lam3(sets[0]) + lam3(sets[1]) + RED < (1 << 63) and lam3(sets[3]) < (1 << 63), "re columns"
+    assert lam3(sets[0]) + lam3(sets[2]) + lam3(sets[3]) + RED < (1 << 64), "im columns"
+    prod = lambda t: ([a + b for a, b in zip(s[t[0]], s[t[1]])], s[t[2]])
+    A, C = [0] * 28, [0] * 28
+    mac(A, *prod(sets[0]))
+    B = list(A)                         # (the device: A's column is the addend of the first multiply-add into B's)
+    mac(B, *prod(sets[1]))
+    mac(A, *prod(sets[2]))
+    mac(C, *prod(sets[3]))
+    assert max(B) < (1 << 63) and max(C) < (1 << 63)
+    re = [(B[i] - C[i]) & M64 for i in range(28)]
+    im = [(A[i] + C[i]) & M64 for i in range(28)]
     r = [reduce_cols(re, True), reduce_cols(im, False)]
+    assert limbs_val(r[0]) < CSQR_RE_BOUND and limbs_val(r[1]) < CSQR_IM_BOUND
+    if reduced is not None:
+        reduced.extend(limbs_val(v) for v in r)
     bias = bias_13_2()
     out = []
     for part in range(2):
@@ -499,7 +510,7 @@ def emit():
     assert self_check()
     o = ["// GENERATED by tools/gen_six_tables.py (tables checked against big-integer Fp12 arithmetic and a limb-level model of the",
          "// engine) - do not edit.", "#pragma once", "#include <stdint.h>"]
-    for name, val in (("A", 0), ("XA", 12), ("T", TA1[0]), ("B", 22), ("C_NA", 12), ("C_ND2", C_ND2), ("PX1", PX1),
+    for name, val in (("A", 0), ("XA", 12), ("T", TA1[0]), ("B", 22), ("PX1", PX1),
                       ("PY1", PY1), ("PX2", PX2), ("PY2", PY2), ("ZERO", ZERO), ("LN1", LN1), ("LN2", LN2), ("C23P", C23P), ("C23N", C23N)):
         o.append("#define SIX_SLOT_%s %d" % (name, val))
     for name, val in (("N_GROUP_SLOTS", N_GROUP_SLOTS), ("N_SHARED_SLOTS", N_SHARED_SLOTS), ("SHARED_BASE", SH), ("N_MUL", N_MUL), ("N_SQR", N_SQR),
@@ -514,7 +525,7 @@ def emit():
     arr("SIX_TAB_SQR", sqr_table(), 4 * N_SQR)
     arr("SIX_TAB_LINE1", line_table(1), 4 * N_LINE)
     arr("SIX_TAB_LINE2", line_table(2), 4 * N_LINE)
-    arr("SIX_TAB_CSQR", [row + [(ZERO,)] for row in csqr_table()], 16)      # (15 slot bytes per lane, padded to 16)
+    arr("SIX_TAB_CSQR", csqr_table(), 3 * N_CSQR)
     path = os.path.join(ROOT, "plutus_halo2_verifier_gen_amd", "csrc", "six_tables.h")
     with open(path, "w") as f:
         f.write("\n".join(o) + "\n")
