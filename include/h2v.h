@@ -271,7 +271,7 @@ int h2v_verify_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_
  * before the pairing (malformed encodings, points off the curve or outside G1, inverse of zero ...) are rejected
  * individually and take no part in the combination.  If the batch check fails, the per-proof MSM and pairing kernels run
  * for the whole batch, so accept[] is always what the per-proof mode returns, except with probability <= 2^-128 over the
- * seed (a rejecting proof hidden by the combination).  Recursive (IVC) plans have no batch form and run per proof.
+ * seed (a rejecting proof hidden by the combination).  Recursive (IVC) plans run per proof unless H2V_RLC_FOLD_PAIRS is set.
  * ws must not be NULL for the device form.
  * ROUTING (round 4): a failed batch check costs more than the per-proof mode it falls back to, so a workspace keeps a running
  * estimate of the rate of FAILING GROUPS (64 proofs each) among the groups its RLC calls have met, and while that rate is
@@ -286,6 +286,12 @@ int h2v_verify_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_
                                * 0.3 ms more per batch alone, but one stream per batch for callers that keep many batches in
                                * flight - more of them fit the hardware queues (measured: 2.47 M proofs/s with 7 in flight
                                * against 2.24 M with 5 on two streams each) */
+#define H2V_RLC_FOLD_PAIRS 4u /* recursive (IVC) plans only, ignored on any other: the batch form that starts AFTER the fold.  The
+                               * per-proof pipeline runs up to and including the fold (its challenge hashes each proof's own MSM
+                               * result, so nothing before it can be combined); then every proof is a pair (el', er') like any
+                               * other, and the pairs are checked as h2v_check_pairs_rlc checks pairs: ONE pairing for the batch,
+                               * and after a failed check the per-proof pairing on the folded points (no MSM is repeated).
+                               * accept[] / status[] are the per-proof mode's.  Never routed, never coalesced. */
 typedef struct h2v_rlc_opts_s {
     uint8_t seed[32];   /* used when flags & H2V_RLC_SEED_GIVEN (tests, reproducible measurements - never a service) */
     uint32_t flags;
@@ -334,6 +340,23 @@ int h2v_check_pairs(const h2v_plan *plan, uint64_t n, const uint8_t *pairs /* n*
                     h2v_workspace *ws /* or NULL */);
 int h2v_check_pairs_device(const h2v_plan *plan, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status,
                            h2v_workspace *ws, void *stream);
+/* h2v_check_pairs_rlc(_device): h2v_check_pairs's contract - the same decoding of both points (the subgroup test stays per
+ * point), the same accept[] / status[] - with the batch check deciding only which kernels produce them: the reference's "scale
+ * each DualMSM by a random coefficient, add, check once".  L = sum r_i L_i and R = sum r_i R_i over the pairs that decoded
+ * (r_i = low 128 bits of blake2b-256(seed || LE32(i)), never 0; an undecodable pair gets H2V_ST_BAD_POINT, accept 0 and
+ * coefficient 0) are two bucket MSMs, followed by ONE pairing.  Passed: accept[i] = "decoded".  Failed: checks of groups of
+ * 64 pairs and then the per-pair kernels of h2v_check_pairs run behind it on the device and set H2V_ST_PAIRING on the pairs
+ * whose own equation fails; nothing comes back to the host in between.  Soundness <= 2^-128 over the seed, completeness exact;
+ * (inf, inf) pairs pass, and so does a batch whose participating pairs sum to infinity on both sides (an empty one included).
+ * The seed follows h2v_verify_batch_rlc's rules; H2V_RLC_ONE_STREAM is accepted and means nothing (one stream already).
+ * Workspaces as for h2v_check_pairs; a laned one makes every chunk its own check.  The device form needs a workspace.  The call
+ * takes one record of kind RLC: h2v_workspace_rlc_result reports its verdict and times (g1_decompress_ms: the decoding,
+ * transcript_combiner_ms: 0, prepare_ms: the coefficient kernel, msm_terms: n), h2v_workspace_timings refuses it.  Never
+ * routed, never coalesced, and the workspace's failing-group estimate does not move.  n > 2^22: H2V_E_LIMIT. */
+int h2v_check_pairs_rlc(const h2v_plan *plan, uint64_t n, const uint8_t *pairs /* n*96 */, uint8_t *accept, uint32_t *status /* or NULL */,
+                        h2v_workspace *ws /* or NULL */, const h2v_rlc_opts *opts /* or NULL */, int *fell_back /* or NULL */);
+int h2v_check_pairs_rlc_device(const h2v_plan *plan, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status,
+                               h2v_workspace *ws /* not NULL */, void *stream, const h2v_rlc_opts *opts /* or NULL */);
 
 /* ---- parity / debugging surface ----------------------------------------------------------------------------
  * The reference's own intermediate-value trace (cargo feature plutus_debug, src/plutus_gen/emitters/plinth.rs:792-831):

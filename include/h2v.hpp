@@ -196,16 +196,32 @@ inline PairVerdicts check_pairs(const VerifyingKey &vk, const std::vector<uint8_
     check(h2v_check_pairs(vk.handle(), n, pairs.data(), r.accept.data(), r.status.data(), ws));
     return r;
 }
+// check_pairs with ONE pairing for the batch (h2v_check_pairs_rlc): the reference's "scale each DualMSM by a random coefficient,
+// add, check once" (examples/ivc.rs:85-96).  The same accept / status as check_pairs; fell_back (optional): the batch check
+// failed and the per-pair kernels produced them.  seed: 32 bytes that provers cannot predict, or nullptr = drawn from the OS.
+inline PairVerdicts check_pairs_rlc(const VerifyingKey &vk, const std::vector<uint8_t> &pairs, h2v_workspace *ws = nullptr,
+                                    const uint8_t *seed = nullptr, bool *fell_back = nullptr) {
+    if (pairs.size() % 96) throw Error(H2V_E_ARG, "pairs: a multiple of 96 bytes");
+    const uint64_t n = pairs.size() / 96;
+    PairVerdicts r{std::vector<uint8_t>(n), std::vector<uint32_t>(n)};
+    h2v_rlc_opts opts{};
+    if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
+    int fb = 0;
+    check(h2v_check_pairs_rlc(vk.handle(), n, pairs.data(), r.accept.data(), r.status.data(), ws, seed ? &opts : nullptr, &fb));
+    if (fell_back) *fell_back = fb != 0;
+    return r;
+}
 // The same vector through the batch-accept fast path (one random linear combination of the batch's pairing equations:
 // one bucketed G1 MSM + one pairing; the per-proof kernels only if the batch check fails).  fell_back (optional) tells
 // which of the two produced the vector.  seed: 32 bytes that provers cannot predict, or nullptr = drawn from the OS.
 inline std::vector<uint8_t> verify_batch_rlc(const VerifyingKey &vk, const h2v_batch &batch, h2v_workspace *ws = nullptr,
-                                             bool *fell_back = nullptr, const uint8_t *seed = nullptr) {
+                                             bool *fell_back = nullptr, const uint8_t *seed = nullptr, bool fold_pairs = false) {
     std::vector<uint8_t> accept(batch.n);
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
+    if (fold_pairs) opts.flags |= H2V_RLC_FOLD_PAIRS;   // recursive keys: combine the pairs the fold leaves (ignored by other keys)
     int fb = 0;
-    check(h2v_verify_batch_rlc(vk.handle(), &batch, accept.data(), ws, seed ? &opts : nullptr, &fb));
+    check(h2v_verify_batch_rlc(vk.handle(), &batch, accept.data(), ws, (seed || fold_pairs) ? &opts : nullptr, &fb));
     if (fell_back) *fell_back = fb != 0;
     return accept;
 }

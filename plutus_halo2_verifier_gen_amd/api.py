@@ -87,17 +87,19 @@ class Verifier:
 
     def verify_batch(self, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
                      committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof",
-                     seed: Optional[bytes] = None) -> List[bool]:
+                     seed: Optional[bytes] = None, fold_pairs: bool = False) -> List[bool]:
         """accept[i] for n independent proofs of this circuit (instances[i]: the public-input scalars of proof i;
         committed[i]: its committed instance as 48 compressed bytes, when the circuit has one).
         mode="rlc": the batch-accept fast path (one bucket MSM + one pairing for the batch, per-proof kernels only if
-        the batch check fails; same accept vector up to a 2^-128 soundness error over `seed`, drawn from the OS when None)."""
+        the batch check fails; same accept vector up to a 2^-128 soundness error over `seed`, drawn from the OS when None).
+        fold_pairs (mode="rlc", recursive circuits): combine the pairs the fold leaves instead of one pairing per proof."""
         n = len(proofs)
         if n == 0:
             return []
         proofs_b, off, inst, ci = self._pack(proofs, instances, committed)
         if mode == "rlc":
-            acc, _fell_back = self.device_plan.verify_batch_rlc(proofs_b, off, inst, ci, ws=self._workspace(n), seed=seed)
+            acc, _fell_back = self.device_plan.verify_batch_rlc(proofs_b, off, inst, ci, ws=self._workspace(n), seed=seed,
+                                                                   fold_pairs=fold_pairs)
         elif mode == "per-proof":
             acc = self.device_plan.verify_batch(proofs_b, off, inst, ci, ws=self._workspace(n))
         else:
@@ -115,14 +117,22 @@ class Verifier:
         raw, st = self.device_plan.prepare_batch(*self._pack(proofs, instances, committed), ws=self._workspace(n))
         return [raw[96 * i:96 * i + 96] for i in range(n)], st
 
-    def check_pairs(self, pairs: Sequence[bytes]):
-        """The second half: (accept, status) for pairs compress(L) || compress(R) from anywhere (h2v_check_pairs)."""
+    def check_pairs(self, pairs: Sequence[bytes], mode: str = "per-pair", seed: Optional[bytes] = None):
+        """The second half: (accept, status) for pairs compress(L) || compress(R) from anywhere (h2v_check_pairs).
+        mode="rlc" (h2v_check_pairs_rlc): the same outputs from ONE pairing for the batch - "scale each DualMSM by a random
+        coefficient, add, check once" - with the per-pair kernels only behind a failed check."""
+        if mode not in ("per-pair", "rlc"):
+            raise ValueError("mode is 'per-pair' or 'rlc'")
         n = len(pairs)
         if n == 0:
             return [], []
         if any(len(p) != 96 for p in pairs):
             raise ValueError("a pair is 96 bytes: compress(L) || compress(R)")
-        acc, st = self.device_plan.check_pairs(b"".join(bytes(p) for p in pairs), ws=self._workspace(n))
+        raw = b"".join(bytes(p) for p in pairs)
+        if mode == "rlc":
+            acc, st, _fell_back = self.device_plan.check_pairs_rlc(raw, ws=self._workspace(n), seed=seed)
+        else:
+            acc, st = self.device_plan.check_pairs(raw, ws=self._workspace(n))
         return [bool(a) for a in acc], st
 
     def _pack(self, proofs, instances, committed):

@@ -60,13 +60,14 @@ OPT_COUNT = 16
 
 RLC_SEED_GIVEN = 1
 RLC_ONE_STREAM = 2
+RLC_FOLD_PAIRS = 4   # recursive plans: combine the pairs (el', er') the fold leaves (include/h2v.h)
 SUBMIT_RLC = 1
 
 
-def _rlc_opts(seed, one_stream: bool = False):
-    if seed is None and not one_stream:
+def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False):
+    if seed is None and not one_stream and not fold_pairs:
         return None
-    flags = RLC_ONE_STREAM if one_stream else 0
+    flags = (RLC_ONE_STREAM if one_stream else 0) | (RLC_FOLD_PAIRS if fold_pairs else 0)
     if seed is None:
         return RlcOpts((C.c_uint8 * 32)(), flags)
     seed = bytes(seed)
@@ -85,6 +86,7 @@ EXPORTS = [
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
+    "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device",
 ]
 
 _lib = None
@@ -154,6 +156,10 @@ def lib():
         L.h2v_prepare_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_check_pairs.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_check_pairs_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.h2v_check_pairs_rlc.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RlcOpts),
+                                          C.POINTER(C.c_int)]
+        L.h2v_check_pairs_rlc_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(RlcOpts)]
         # h2v_shutdown before the interpreter goes down: the library's pool streams (hardware queues of their own) must not
         # outlive the HIP runtime / a profiler's tool library (include/h2v.h: library lifecycle).  Handles that Python still
         # holds afterwards are empty shells; their __del__ frees the host structs only.
@@ -260,27 +266,29 @@ class DevicePlan:
         n, b, keep = self._host_batch(proofs, proof_off, instances, committed)
         return b, keep
 
-    def submit(self, batch: "Batch", ws, rlc: bool = False, seed: Optional[bytes] = None, one_stream: bool = False):
+    def submit(self, batch: "Batch", ws, rlc: bool = False, seed: Optional[bytes] = None, one_stream: bool = False,
+               fold_pairs: bool = False):
         """h2v_verify_batch_submit: copy + upload + verification + download enqueued on the workspace's stream."""
-        opts = _rlc_opts(seed, one_stream)
+        opts = _rlc_opts(seed, one_stream, fold_pairs)
         check(lib().h2v_verify_batch_submit(self._h, C.byref(batch), ws.handle, SUBMIT_RLC if rlc else 0,
                                             C.byref(opts) if opts is not None else None))
 
     def verify_batch_rlc(self, proofs: bytes, proof_off, instances: bytes, committed: Optional[bytes], ws=None,
-                         seed: Optional[bytes] = None):
-        """Batch-accept fast path (h2v_verify_batch_rlc): returns (accept bytes, fell_back)."""
+                         seed: Optional[bytes] = None, fold_pairs: bool = False):
+        """Batch-accept fast path (h2v_verify_batch_rlc): returns (accept bytes, fell_back).  fold_pairs (RLC_FOLD_PAIRS):
+        the batch form of recursive plans, which starts after the fold; ignored by any other plan."""
         n, b, _keep = self._host_batch(proofs, proof_off, instances, committed)
         acc = (C.c_uint8 * max(1, n))()
         fb = C.c_int(0)
-        opts = _rlc_opts(seed)
+        opts = _rlc_opts(seed, fold_pairs=fold_pairs)
         check(lib().h2v_verify_batch_rlc(self._h, C.byref(b), acc, ws.handle if ws else None,
                                          C.byref(opts) if opts is not None else None, C.byref(fb)))
         return bytes(acc[:n]), bool(fb.value)
 
     def verify_batch_rlc_device(self, n, d_proofs, d_off, d_inst, d_ci, d_accept, d_status=None, ws=None, stream=None,
-                                seed: Optional[bytes] = None, one_stream: bool = False):
+                                seed: Optional[bytes] = None, one_stream: bool = False, fold_pairs: bool = False):
         b = Batch(n, d_proofs, d_off, d_inst, d_ci)
-        opts = _rlc_opts(seed, one_stream)
+        opts = _rlc_opts(seed, one_stream, fold_pairs)
         check(lib().h2v_verify_batch_rlc_device(self._h, C.byref(b), d_accept, d_status, ws.handle if ws else None, stream,
                                                 C.byref(opts) if opts is not None else None))
 
@@ -321,6 +329,26 @@ class DevicePlan:
     def check_pairs_device(self, n, d_pairs, d_accept, d_status=None, ws=None, stream=None):
         """h2v_check_pairs_device: enqueues on `stream`"""
         check(lib().h2v_check_pairs_device(self._h, n, d_pairs, d_accept, d_status, ws.handle if ws else None, stream))
+
+    def check_pairs_rlc(self, pairs: bytes, ws=None, seed: Optional[bytes] = None):
+        """h2v_check_pairs_rlc: (accept bytes, status, fell_back) - check_pairs's outputs with ONE pairing for the batch
+        when every decoded pair's equation holds; fell_back: the batch check failed and the per-pair kernels ran."""
+        if len(pairs) % 96:
+            raise H2VError("pairs: a multiple of 96 bytes")
+        n = len(pairs) // 96
+        acc = (C.c_uint8 * max(1, n))()
+        st = (C.c_uint32 * max(1, n))()
+        fb = C.c_int(0)
+        opts = _rlc_opts(seed)
+        check(lib().h2v_check_pairs_rlc(self._h, n, bytes(pairs), acc, st, ws.handle if ws else None,
+                                        C.byref(opts) if opts is not None else None, C.byref(fb)))
+        return bytes(acc[:n]), list(st[:n]), bool(fb.value)
+
+    def check_pairs_rlc_device(self, n, d_pairs, d_accept, d_status=None, ws=None, stream=None, seed: Optional[bytes] = None):
+        """h2v_check_pairs_rlc_device: enqueues on `stream`; ws.rlc_result() has the batch verdict afterwards"""
+        opts = _rlc_opts(seed)
+        check(lib().h2v_check_pairs_rlc_device(self._h, n, d_pairs, d_accept, d_status, ws.handle if ws else None, stream,
+                                               C.byref(opts) if opts is not None else None))
 
     def trace(self, proof: bytes, instances: bytes, committed: Optional[bytes]):
         nt = len(self.trace_slots)

@@ -222,6 +222,7 @@ struct h2v_workspace {
     struct CallRec {
         uint64_t call = ~0ull;
         Kind kind = VERIFY;
+        bool no_vm = false;        // an RLC call over pairs from anywhere: no transcript ran (transcript_combiner_ms = 0)
         bool routed = false;       // an RLC call sent straight to the per-proof kernels (rlc_route): per-proof times, no batch check
         bool co = false, ran = false;   // coalesced (coalesce_call); its group has run - only then is the rest filled in (co_flush_lane)
         float share = 0.0f;        // coalesced: its proofs / the group's
@@ -241,6 +242,8 @@ struct h2v_workspace {
     uint64_t calls = 0;
     uint32_t *rec_fail = nullptr;   // RING device words: failed batch checks of record k at [k % RING] (RLC calls; rlc_stats_ensure)
     struct RlcWs *rlc = nullptr;   // buffers of the RLC batch mode, created by its first call
+    struct RlcWs *prlc = nullptr;  // the pair-RLC set (h2v_check_pairs_rlc, H2V_RLC_FOLD_PAIRS): created by the first such call
+    hipEvent_t ev_pipe[12] = {};   // H2V_RLC_FOLD_PAIRS: the pipeline's own markers (the record's events carry the RLC layout)
     std::vector<struct RlcWs *> rlc_parked;   // the same for OTHER plans this workspace has served in that mode (rlc_ensure swaps; never freed before the workspace)
     int32_t opt[H2V_OPT_COUNT] = {};   // h2v_workspace_set_option / h2v_workspace_tune: 0 = the launcher's choice
     int one_stream_mode = -1;      // lanes: 1 = the whole pipeline on the stream it is given (-1: decided from the hint)
@@ -628,6 +631,8 @@ static void ws_release(h2v_workspace *w) {
     if (w->rlc) { rlc_release(w->rlc); w->rlc = nullptr; }
     for (struct RlcWs *r : w->rlc_parked) rlc_release(r);
     w->rlc_parked.clear();
+    if (w->prlc) { rlc_release(w->prlc); w->prlc = nullptr; }
+    for (hipEvent_t &e : w->ev_pipe) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
     void *ptrs[] = {w->rlc_stats, w->rec_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
                     w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts, w->hp_buf};
@@ -1448,11 +1453,14 @@ static uint32_t launch_pairing(const H2vDevPlan &d, uint32_t n, const uint32_t *
 // Enqueues the four kernels.  The decompression kernel (many short waves) runs on a side stream beside the
 // transcript+combiner kernel (few long waves), and the two join before the MSM.
 extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_timings *tm);
+// fold (H2V_RLC_FOLD_PAIRS, recursive plans): instead of the per-proof pairing, the batch check over the folded pairs (fold_pairs_tail)
+struct FoldPairs { const h2v_plan *p; const uint32_t *seed; uint32_t *fail_ctr; };
+static int fold_pairs_tail(const FoldPairs &f, uint32_t n, const uint32_t *er2, const uint32_t *el2, uint8_t *accept, h2v_workspace *w, CallRec &rec, hipStream_t st);
 // pairs_out (prepare calls): instead of the pairing, k_prepare_export writes each proof's pair compress(L) || compress(R)
 // there (n x 24 dwords) and the status words without H2V_ST_PAIRING; accept is not written.
 static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst,
                         const uint8_t *ci, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
-                        h2v_timings *tm, bool want_trace, uint32_t *pairs_out = nullptr) {
+                        h2v_timings *tm, bool want_trace, uint32_t *pairs_out = nullptr, const FoldPairs *fold = nullptr) {
     opts_from(w);
     struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
     const uint32_t slots = H2V_SLOTS(d);
@@ -1477,8 +1485,14 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     if (!one_stream)
         if (int rcs = ws_streams(w, !two_stream, true)) return rcs;
     hipStream_t pm = (one_stream || two_stream) ? st : w->pmain, ps = one_stream ? st : w->pside;
-    CallRec &rec = rec_new(w, pairs_out ? h2v_workspace::PREPARE : h2v_workspace::VERIFY);
+    CallRec &rec = rec_new(w, fold ? h2v_workspace::RLC : pairs_out ? h2v_workspace::PREPARE : h2v_workspace::VERIFY);
+    // fold (H2V_RLC_FOLD_PAIRS): the record's events carry run_rlc's layout - [0]/[1] around the decompression, [2]/[3] around the
+    // combiner, the rest recorded by pairs_rlc_core - and the pipeline's own markers go to a set of the workspace that nobody reads
     hipEvent_t *ev = rec.ev;
+    if (fold) {
+        for (hipEvent_t &e : w->ev_pipe) if (!e) HIPCHK(hipEventCreate(&e));
+        ev = w->ev_pipe;
+    }
     HIPCHK(hipEventRecord(w->ev_fork, st));
     HIPCHK(hipStreamWaitEvent(pm, w->ev_fork, 0));
     HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
@@ -1486,6 +1500,7 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     // then all square roots (k_g1_decompress_queue)
     const uint32_t dec_grid = (n * slots + 63) / 64;
     HIPCHK(hipEventRecord(ev[2], ps));
+    if (fold) HIPCHK(hipEventRecord(rec.ev[0], ps));
     HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, ps));
     {
         const uint32_t units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
@@ -1494,6 +1509,7 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
         hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, ps, d, n, proofs, off, ci, inst, w->pts, w->valid, w->pt_tab, w->valid_sub, w->dec_ctr, dec_grid);
     }
     HIPCHK(hipEventRecord(ev[3], ps));
+    if (fold) HIPCHK(hipEventRecord(rec.ev[1], ps));
     HIPCHK(hipEventRecord(w->ev_join, ps));
     // The MSM's hold: it waits for a few more packets on the side stream than its inputs need (a wait, two timed markers, the
     // marker it waits for).  The MSM wants every SIMD to itself, and it is faster for the small delay: measured with the
@@ -1505,8 +1521,10 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     HIPCHK(hipEventRecord(w->ev_hold, ps));
     if (int rcd = stage_done("k_g1_decompress_queue")) return rcd;
     HIPCHK(hipEventRecord(ev[0], pm));
+    if (fold) HIPCHK(hipEventRecord(rec.ev[2], pm));
     if (int rcv = launch_vm(d, n, w->stride, proofs, off, inst, ci, w->regs, w->scalars, w->status, trace, pm)) return rcv;
     HIPCHK(hipEventRecord(ev[1], pm));
+    if (fold) HIPCHK(hipEventRecord(rec.ev[3], pm));
     if (int rcd = stage_done("k_transcript_combiner")) return rcd;
     HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
     HIPCHK(hipStreamWaitEvent(pm, w->ev_hold, 0));
@@ -1550,7 +1568,9 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
         if (int rcd = stage_done("k_ivc_challenge + fold MSM")) return rcd;
     }
     HIPCHK(hipEventRecord(ev[5], pm));
-    if (pairs_out)   // (rec.pair stays 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
+    if (fold) {
+        if (int rcf = fold_pairs_tail(*fold, n, er_in, el_in, accept, w, rec, pm)) return rcf;
+    } else if (pairs_out)   // (rec.pair stays 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
         hipLaunchKernelGGL(k_prepare_export, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, pairs_out);
     else
         rec.pair = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
@@ -1604,7 +1624,7 @@ static int run_check(const H2vDevPlan &d, uint32_t n, const uint8_t *pairs, uint
                        (const uint8_t *)nullptr, w->pts, w->valid, (uint32_t *)nullptr, w->valid_sub, w->dec_ctr, dec_grid);
     HIPCHK(hipEventRecord(ev[3], st));
     HIPCHK(hipEventRecord(ev[4], st));
-    hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er);
+    hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er, (const uint32_t *)nullptr);
     HIPCHK(hipEventRecord(ev[5], st));
     rec.pair = (uint8_t)launch_pairing(v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, accept, nullptr, st, w->in_flight_hint);
     HIPCHK(hipEventRecord(ev[6], st));
@@ -1685,14 +1705,23 @@ static uint32_t laned_depth(const h2v_workspace *w, uint64_t n, bool rlc, int *s
 }
 // A prepare or pair-check call through the lanes (never RLC): prepare writes pairs to `out`; a check reads them from `in`
 // (then proofs / off / inst / ci are unused).  Both are n x 96 bytes, cut into chunks like accept[].
-struct PairIO { uint8_t *out; const uint8_t *in; };
+// rlc_seed: the call is a batch check - over the pairs of `in` (h2v_check_pairs_rlc), or, without `in` / `out`, a verify call of
+// a recursive plan whose folded pairs are combined (H2V_RLC_FOLD_PAIRS); every chunk is its own check, as for rlc.
+struct PairIO { uint8_t *out; const uint8_t *in; const uint32_t *rlc_seed = nullptr; };
+static int run_pairs_rlc(const h2v_plan *p, uint32_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
+                         const uint32_t seed[8], uint32_t *fail_ctr);
+static int run_fold_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
+                        uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], uint32_t *fail_ctr);
 static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
                      uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t *seed, bool force_join,
                      bool never_join = false, const PairIO *pio = nullptr) {
     const H2vDevPlan &d = p->d;
     if (int rcf = co_flush(w)) return rcf;          // (calls start in submission order: an open group of coalesced calls first)
     int stream_mode = 1;
-    const uint32_t L = laned_depth(w, n, rlc, &stream_mode);
+    const bool pair_rlc = pio && pio->rlc_seed && pio->in, fold_rlc = pio && pio->rlc_seed && !pio->in;   // (then rlc is false)
+    const uint32_t *pair_seed = (pair_rlc || fold_rlc) ? pio->rlc_seed : nullptr;
+    if (fold_rlc) pio = nullptr;
+    const uint32_t L = laned_depth(w, n, rlc || pair_rlc, &stream_mode);
     // A per-proof call that would leave lanes empty at the workspace's chunk size is cut finer, one chunk per lane (in 512s,
     // not below 2048: there the chains' latency costs more than the extra lanes win).  One call on 20 480 simple_mul proofs,
     // eight lanes: chunks of 4096 24.0 ms, 2560 22.5 ms, 2048 27.7 ms.  (RLC mode: every chunk is a batch check of its own and
@@ -1700,7 +1729,7 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
     uint32_t chunk = w->chunk;
     // (only for a call that waits for its own chunks: with deferred joins or streamed host batches the NEXT call fills the lanes,
     //  and whole chunks keep the full-chip launch shapes - a stream of 16 384-proof calls: 15.9 ms per call cut in 2048s, ~13 in 4096s)
-    if (!rlc && !w->defer_joins && !never_join && n > chunk && (uint64_t)n < (uint64_t)L * chunk) {
+    if (!rlc && !pair_seed && !w->defer_joins && !never_join && n > chunk && (uint64_t)n < (uint64_t)L * chunk) {
         const uint32_t c2 = (uint32_t)(((n + L - 1) / L + 511) / 512 * 512);
         if (c2 >= default_chunk(d) / 2 && c2 < chunk) chunk = c2;       // (simple_mul: 2048; T = 60: 512)
     }
@@ -1709,7 +1738,7 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
     // consecutive calls overlap and every lane is busy; a call that waits for its own chunks has only THOSE in flight - one
     // 4096-proof chunk on a laned workspace is a lone batch (with the full-chip shapes it took 11.6 ms instead of 5.8).
     const uint32_t call_hint = w->hint_given ? w->in_flight_hint : (w->defer_joins || never_join) ? w->n_lanes : (nch < L ? nch : L);
-    CallRec &rec = rec_new(w, rlc ? h2v_workspace::RLC : !pio ? h2v_workspace::VERIFY : pio->in ? h2v_workspace::CHECK : h2v_workspace::PREPARE);
+    CallRec &rec = rec_new(w, (rlc || pair_seed) ? h2v_workspace::RLC : !pio ? h2v_workspace::VERIFY : pio->in ? h2v_workspace::CHECK : h2v_workspace::PREPARE);
     rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = nch;
     for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;   // (every chunk takes one record on its lane)
     bool routed = false;
@@ -1717,6 +1746,10 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
         if (int rcs = rlc_stats_ensure(w)) return rcs;
         routed = rec.routed = rlc_route(w);
         HIPCHK(hipMemsetAsync(rec_word(w, rec), routed ? 1 : 0, 4, st));      // (routed: "a batch check failed" = the per-proof kernels produce accept[])
+    }
+    if (pair_seed) {              // never routed, and the failing-group estimate stays where it is
+        if (int rcs = rlc_stats_ensure(w)) return rcs;
+        HIPCHK(hipMemsetAsync(rec_word(w, rec), 0, 4, st));
     }
     HIPCHK(hipEventRecord(w->ev_fork, st));
     for (uint32_t c = 0; c < nch; c++) {
@@ -1742,6 +1775,18 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
                 rc = run_rlc(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, true, rec_word(w, rec));
             }
             if (rc == H2V_OK && hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, ls) != hipSuccess) rc = fail(H2V_E_DEVICE, "routing counters: copy failed");
+        } else if (pair_seed) {
+            uint32_t sd[8];
+            for (int k = 0; k < 8; k++) sd[k] = pair_seed[k];
+            sd[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
+            lw->in_flight_hint = call_hint;
+            lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
+            if (pair_rlc) {
+                rc = run_pairs_rlc(p, m, pio->in + (size_t)lo * 96, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, rec_word(w, rec));
+            } else {
+                lw->one_stream_mode = stream_mode;
+                rc = run_fold_rlc(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, rec_word(w, rec));
+            }
         } else if (pio && pio->in) {
             lw->in_flight_hint = call_hint;
             rc = run_check(d, m, pio->in + (size_t)lo * 96, accept + lo, status_out ? status_out + lo : nullptr, lw, ls);
@@ -2246,6 +2291,7 @@ static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws,
     return H2V_OK;
 }
 static bool rlc_supported(const h2v_plan *p);
+static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o);
 static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]);
 static int run_rlc_or_routed(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
                              uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt);
@@ -2254,7 +2300,7 @@ static int run_rlc_or_routed(const h2v_plan *p, uint32_t n, const uint8_t *proof
 // staging slot of its own (pinned block + device block + accept buffers); uploads run in order on `hs`, the chunks on
 // the lanes, and the downloads on `hs_down`, each behind the lanes its batch ran on.  h2v_verify_batch_wait collects the
 // OLDEST batch.
-static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, bool rlc, const uint32_t *seed) {
+static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, bool rlc, const uint32_t *seed, bool fold = false) {
     const uint32_t depth = laned_depth(ws, b->n, rlc, nullptr);
     if (ws->h_head - ws->h_tail >= depth || ws->h_head - ws->h_tail >= (uint64_t)h2v_workspace::MAXH)
         return fail(H2V_E_ARG, "as many batches in flight as this workspace has lanes: call h2v_verify_batch_wait first");
@@ -2262,11 +2308,12 @@ static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws
     h2v_workspace::HostSlot &sl = ws->hslot[ws->h_head % h2v_workspace::MAXH];
     if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
     const uint64_t n = b->n;
-    sl.n = n; sl.rlc = rlc;
+    sl.n = n; sl.rlc = rlc || fold;
     if (n) {
         Staged in;
         if (int rcs = stage_batch(p, b, ws, sl, &in)) return rcs;
-        int rc = run_laned(p, (uint32_t)n, in.proofs, in.off, in.inst, in.ci, sl.d_accept, nullptr, ws, ws->hs, rlc, seed, false, true);
+        const PairIO fold_io{nullptr, nullptr, seed};
+        int rc = run_laned(p, (uint32_t)n, in.proofs, in.off, in.inst, in.ci, sl.d_accept, nullptr, ws, ws->hs, rlc, seed, false, true, fold ? &fold_io : nullptr);
         if (rc == H2V_OK) {
             // the download waits for the lanes this call's chunks ran on (their events as recorded just now)
             const CallRec &r = rec_last(ws);
@@ -2275,7 +2322,7 @@ static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws
             if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, sl.d_accept, n, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
             // (RLC: how many of the call's batch checks failed comes back the same way - a synchronous copy in _wait would go
             //  through the legacy NULL stream, which every pool stream is ordered with: it would drain all batches in flight)
-            if (rc == H2V_OK && rlc && hipMemcpyAsync(sl.h_accept + ((n + 7) & ~(uint64_t)7), rec_word(ws, r), 4, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess)
+            if (rc == H2V_OK && sl.rlc && hipMemcpyAsync(sl.h_accept + ((n + 7) & ~(uint64_t)7), rec_word(ws, r), 4, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess)
                 rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
         }
         if (rc) return drain_after_error(ws, rc);
@@ -2319,24 +2366,26 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
     if (rc) return rc;
     if (b->n && (rc = ws_fits(ws, p, b->n, false))) return rc;
     const bool rlc = (flags & H2V_SUBMIT_RLC) && rlc_supported(p);
+    const bool fold = (flags & H2V_SUBMIT_RLC) && !rlc && fold_pairs_wanted(p, opts);   // recursive plans: the batch check after the fold
     uint32_t seed[8] = {};
     if (ws->n_lanes) {
-        if (rlc && (rc = rlc_seed(opts, seed))) return rc;
-        return submit_laned(p, b, ws, rlc, seed);
+        if ((rlc || fold) && (rc = rlc_seed(opts, seed))) return rc;
+        return submit_laned(p, b, ws, rlc, seed, fold);
     }
     h2v_workspace::HostSlot &sl = ws->hslot[0];
     if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
     sl.n = b->n;
     sl.rlc = false;
     if (b->n) {
-        if (rlc && (rc = rlc_seed(opts, seed))) return rc;
+        if ((rlc || fold) && (rc = rlc_seed(opts, seed))) return rc;
         Staged in;
         if ((rc = stage_batch(p, b, ws, sl, &in))) return rc;
-        if (rlc) rc = run_rlc_or_routed(p, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, seed, opts && (opts->flags & H2V_RLC_ONE_STREAM));
+        if (fold) rc = run_fold_rlc(p, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, seed, nullptr);
+        else if (rlc) rc = run_rlc_or_routed(p, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, seed, opts && (opts->flags & H2V_RLC_ONE_STREAM));
         else rc = run_pipeline(p->d, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, nullptr, false);
-        sl.rlc = rlc;
+        sl.rlc = rlc || fold;
         if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, ws->accept, b->n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-        if (rc == H2V_OK && rlc && hipMemcpyAsync(sl.h_accept + ((b->n + 7) & ~(uint64_t)7), rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
+        if (rc == H2V_OK && sl.rlc && hipMemcpyAsync(sl.h_accept + ((b->n + 7) & ~(uint64_t)7), rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
             rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
         if (rc) return drain_after_error(ws, rc);   // (the upload from the pinned block and some kernels may already be enqueued)
     }
@@ -2591,6 +2640,7 @@ struct RlcWs {
     uint32_t n_var = 0, n_fix = 0;
     uint32_t *r_scal = nullptr, *r_idx = nullptr, *l_scal = nullptr, *l_idx = nullptr, *vk_part = nullptr;
     uint8_t *good = nullptr;
+    uint32_t *pool = nullptr;   // the pair-RLC set, H2V_RLC_FOLD_PAIRS: cap two-slot records of folded pairs (k_fold_pairs_affine)
     PipWs R, L;
     uint32_t *sums = nullptr;   // er (36 dwords) then el (36): the two MSM results
     uint32_t *misc = nullptr;   // [0..23] a dummy affine point, [24] status of the batch check, [26] its valid byte, [27] its accept byte
@@ -2611,12 +2661,30 @@ struct RlcWs {
     } grp;
 };
 static void rlc_release(RlcWs *r) {
-    void *ptrs[] = {r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good, r->sums, r->misc, r->flags, r->grp.g_scal, r->grp.g_idx, r->grp.er_g,
+    if (r->l_scal == r->r_scal) r->l_scal = nullptr;      // (the pair-RLC set: one scalar array for both sums)
+    void *ptrs[] = {r->pool, r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good, r->sums, r->misc, r->flags, r->grp.g_scal, r->grp.g_idx, r->grp.er_g,
                     r->grp.el_g, r->grp.pts_g, r->grp.status_g, r->grp.valid_g, r->grp.accept_g, r->grp.pool, r->grp.args_d};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     for (void *q : r->grp.staged) (void)hipHostFree(q);   // (the caller has drained the streams: ws_release)
     pip_free(r->R); pip_free(r->L);
     delete r;
+}
+// n_fix == 0 (pairs): 128-bit scalars on both sides and no left-hand array of its own (l_scal = r_scal)
+static RlcWs *rlc_new(uint64_t cap, uint32_t n_var, uint32_t n_fix) {
+    RlcWs *r = new RlcWs();
+    r->cap = cap; r->n_var = n_var; r->n_fix = n_fix;
+    const bool pairs = n_fix == 0;
+    const size_t nr = (size_t)cap * n_var + n_fix, blocks = (cap + 63) / 64;
+    bool ok = hipMalloc((void **)&r->r_scal, nr * 32) == hipSuccess && hipMalloc((void **)&r->r_idx, nr * 4) == hipSuccess &&
+              (pairs || hipMalloc((void **)&r->l_scal, (size_t)cap * 32) == hipSuccess) && hipMalloc((void **)&r->l_idx, (size_t)cap * 4) == hipSuccess &&
+              hipMalloc((void **)&r->vk_part, blocks * (n_fix ? n_fix : 1) * 32) == hipSuccess && hipMalloc((void **)&r->good, cap) == hipSuccess &&
+              hipMalloc((void **)&r->sums, 72 * 4) == hipSuccess && hipMalloc((void **)&r->misc, 32 * 4) == hipSuccess &&
+              hipMemset(r->misc, 0, 32 * 4) == hipSuccess && hipMalloc((void **)&r->flags, (blocks + 2) * 4) == hipSuccess &&
+              hipMemset(r->flags, 0, (blocks + 2) * 4) == hipSuccess;
+    if (ok && pairs) r->l_scal = r->r_scal;
+    if (ok) ok = pip_alloc(r->R, (uint32_t)nr, pairs ? 1 : 2) == H2V_OK && pip_alloc(r->L, (uint32_t)cap, 1) == H2V_OK;
+    if (!ok) { rlc_release(r); return nullptr; }
+    return r;
 }
 // One set of buffers per plan SHAPE (n_var, n_fix) the workspace has served: a workspace that alternates between plans (ws_fits
 // allows any plan that fits; h2v_workspace_create_multi is made for it) swaps between parked sets instead of freeing and
@@ -2637,18 +2705,18 @@ static int rlc_ensure(h2v_workspace *w, const h2v_plan *p) {
         w->rlc_parked.push_back(w->rlc);
         w->rlc = nullptr;
     }
-    RlcWs *r = new RlcWs();
-    r->cap = w->cap; r->n_var = p->n_var; r->n_fix = p->n_fix;
-    const size_t nr = (size_t)w->cap * p->n_var + p->n_fix, blocks = (w->cap + 63) / 64;
-    bool ok = hipMalloc((void **)&r->r_scal, nr * 32) == hipSuccess && hipMalloc((void **)&r->r_idx, nr * 4) == hipSuccess &&
-              hipMalloc((void **)&r->l_scal, (size_t)w->cap * 32) == hipSuccess && hipMalloc((void **)&r->l_idx, (size_t)w->cap * 4) == hipSuccess &&
-              hipMalloc((void **)&r->vk_part, blocks * (p->n_fix ? p->n_fix : 1) * 32) == hipSuccess && hipMalloc((void **)&r->good, w->cap) == hipSuccess &&
-              hipMalloc((void **)&r->sums, 72 * 4) == hipSuccess && hipMalloc((void **)&r->misc, 32 * 4) == hipSuccess &&
-              hipMemset(r->misc, 0, 32 * 4) == hipSuccess && hipMalloc((void **)&r->flags, (blocks + 2) * 4) == hipSuccess &&
-              hipMemset(r->flags, 0, (blocks + 2) * 4) == hipSuccess;
-    if (ok) ok = pip_alloc(r->R, (uint32_t)nr, 2) == H2V_OK && pip_alloc(r->L, (uint32_t)w->cap, 1) == H2V_OK;
-    if (!ok) { rlc_release(r); return fail(H2V_E_DEVICE, "RLC workspace allocation failed"); }
+    RlcWs *r = rlc_new(w->cap, p->n_var, p->n_fix);
+    if (!r) return fail(H2V_E_DEVICE, "RLC workspace allocation failed");
     w->rlc = r;
+    return H2V_OK;
+}
+// The pair-RLC set of a workspace or lane (h2v_check_pairs_rlc, H2V_RLC_FOLD_PAIRS), sized by its capacity and allocated at
+// the first such call: the shape "one variable term per pair, no VK base" of the same buffers - one scalar array for both sums,
+// the index arrays 2 i / 2 i + 1, good, sums, flags, two bucket-MSM workspaces of 128-bit scalars.  with_pool: the folded pairs' own pool.
+static int pair_rlc_ensure(h2v_workspace *w, bool with_pool) {
+    if (!w->prlc && !(w->prlc = rlc_new(w->cap, 1, 0))) return fail(H2V_E_DEVICE, "pair-RLC workspace allocation failed");
+    if (with_pool && !w->prlc->pool && hipMalloc((void **)&w->prlc->pool, (size_t)w->cap * 48 * 4) != hipSuccess)
+        return fail(H2V_E_DEVICE, "pair-RLC workspace allocation failed");
     return H2V_OK;
 }
 static bool rlc_supported(const h2v_plan *p) { return !p->d.ivc && p->n_var > 0 && p->n_fix > 0 && p->n_var + p->n_fix == p->d.n_terms; }
@@ -2670,11 +2738,17 @@ static bool rlc_groups_on(uint32_t n) {
 // is uploaded ON THE CALL'S STREAM from a pinned host copy: the kernels of an earlier call on that stream read args_d when
 // they run, and a synchronous hipMemcpy (through the NULL stream, not ordered with a non-blocking caller stream) could
 // hand them the new batch size's pointers.  The key is the plan's load counter, not its address.
-static int rlc_groups_ensure(RlcWs *r, const h2v_plan *p, h2v_workspace *w, uint32_t n, hipStream_t st) {
+// GrpShape: what the stage sums over - the proofs of a plan (grp_of_plan: its per-proof terms out of the workspace's point
+// buffer, then its VK bases; 255-bit scalars on the right) or pairs (grp_of_pairs: one term per pair out of `pool`, no VK base,
+// 128-bit scalars on both sides).
+struct GrpShape { uint32_t n_var, n_fix, slots, halves; const uint32_t *pool, *vk_bases, *terms; uint64_t gen; };
+static GrpShape grp_of_plan(const h2v_plan *p, const h2v_workspace *w) { return {p->n_var, p->n_fix, (uint32_t)H2V_SLOTS(p->d), 2, w->pts, p->d.vk_bases, p->d.terms, p->gen}; }
+static GrpShape grp_of_pairs(const h2v_plan *p, const uint32_t *pool) { return {1, 0, 2, 1, pool, nullptr, nullptr, p->gen}; }
+static int rlc_groups_ensure(RlcWs *r, const GrpShape &gs, uint32_t n, hipStream_t st) {
     RlcWs::Grp &g = r->grp;
-    const uint32_t G = (n + 63) / 64, slots = H2V_SLOTS(p->d);
-    const uint32_t W = 128 / GRP_C + 1, NB = 1u << (GRP_C - 1), nb = W * NB, stride = 64 * p->n_var + p->n_fix;
-    if (g.n == n && g.key_gen == p->gen && g.key_pts == w->pts && g.stride == stride) return H2V_OK;
+    const uint32_t G = (n + 63) / 64, slots = gs.slots;
+    const uint32_t W = 128 / GRP_C + 1, NB = 1u << (GRP_C - 1), nb = W * NB, stride = 64 * gs.n_var + gs.n_fix;
+    if (g.n == n && g.key_gen == gs.gen && g.key_pts == gs.pool && g.stride == stride) return H2V_OK;
     if (G > g.cap_G || stride > g.cap_stride) {
         HIPCHK(hipStreamSynchronize(st));     // (the buffers about to be freed may be in use by the previous call)
         void *old[] = {g.g_scal, g.g_idx, g.er_g, g.el_g, g.pts_g, g.status_g, g.valid_g, g.accept_g, g.pool, g.args_d};
@@ -2707,10 +2781,10 @@ static int rlc_groups_ensure(RlcWs *r, const h2v_plan *p, h2v_workspace *w, uint
         for (int side = 0; side < 2; side++) {
             PipArgs a = {};
             a.c = GRP_C; a.W = W; a.NB = NB; a.chain = 20;
-            a.pool0 = w->pts; a.n_pool0 = n * slots;
+            a.pool0 = gs.pool; a.n_pool0 = n * slots;
             if (side == 0) {
-                a.n = ng * p->n_var + p->n_fix; a.halves = 2;
-                a.scal = g.g_scal + (size_t)q * stride * 8; a.pidx = g.g_idx + (size_t)q * stride; a.pool1 = p->d.vk_bases; a.out = g.er_g + (size_t)q * 36;
+                a.n = ng * gs.n_var + gs.n_fix; a.halves = gs.halves;
+                a.scal = g.g_scal + (size_t)q * stride * 8; a.pidx = g.g_idx + (size_t)q * stride; a.pool1 = gs.vk_bases; a.out = g.er_g + (size_t)q * 36;
             } else {
                 a.n = ng; a.halves = 1;
                 a.scal = r->l_scal + (size_t)q * 64 * 8; a.pidx = r->l_idx + (size_t)q * 64; a.pool1 = nullptr; a.out = g.el_g + (size_t)q * 36;
@@ -2743,15 +2817,16 @@ static int rlc_groups_ensure(RlcWs *r, const h2v_plan *p, h2v_workspace *w, uint
     g.staged.push_back(pinned);
     memcpy(pinned, args.data(), args.size() * sizeof(PipArgs));
     HIPCHK(hipMemcpyAsync(g.args_d, pinned, args.size() * sizeof(PipArgs), hipMemcpyHostToDevice, st));   // behind the earlier call's kernels
-    g.n = n; g.G = G; g.stride = stride; g.max_n = max_n; g.acc_blocks = acc_blocks; g.key_gen = p->gen; g.key_pts = w->pts;
+    g.n = n; g.G = G; g.stride = stride; g.max_n = max_n; g.acc_blocks = acc_blocks; g.key_gen = gs.gen; g.key_pts = gs.pool;
     return H2V_OK;
 }
-static int rlc_groups_launch(RlcWs *r, const h2v_plan *p, h2v_workspace *w, uint32_t n, uint8_t *accept, const H2vDevPlan &d1, hipStream_t st) {
-    int rc = rlc_groups_ensure(r, p, w, n, st);
+// stats: the workspace's failing-group counters, or NULL (pairs: that estimate describes proofs of a plan)
+static int rlc_groups_launch(RlcWs *r, const GrpShape &gs, uint32_t n, uint8_t *accept, const H2vDevPlan &d1, hipStream_t st, uint32_t *stats) {
+    int rc = rlc_groups_ensure(r, gs, n, st);
     if (rc) return rc;
     RlcWs::Grp &g = r->grp;
     const uint32_t G = g.G;
-    RlcGroupArgs ga = {n, p->n_var, p->n_fix, (uint32_t)H2V_SLOTS(p->d), g.stride, p->d.terms, r->r_scal, r->r_idx, r->vk_part, g.g_scal, g.g_idx};
+    RlcGroupArgs ga = {n, gs.n_var, gs.n_fix, gs.slots, g.stride, gs.terms, r->r_scal, r->r_idx, r->vk_part, g.g_scal, g.g_idx};
     hipLaunchKernelGGL(k_rlc_group_terms, dim3(G), dim3(64), 0, st, ga, r->flags);
     HIPCHK(hipMemsetAsync(g.pool, 0, g.cnt_bytes, st));
     HIPCHK(hipMemsetAsync(g.status_g, 0, (size_t)G * 4, st));
@@ -2763,7 +2838,7 @@ static int rlc_groups_launch(RlcWs *r, const h2v_plan *p, h2v_workspace *w, uint
     hipLaunchKernelGGL(k_pip_wsum_many, dim3((2 * G * Wg * 4 + 63) / 64), dim3(64), 0, st, g.args_d, 2 * G, Wg, r->flags);
     hipLaunchKernelGGL(k_pip_horner_many, dim3(2 * G), dim3(64), 0, st, g.args_d, r->flags);
     hipLaunchKernelGGL(k_pairing_rlc_groups, dim3(G), dim3(64), COOP_LDS_BYTES(1), st, d1, g.pts_g, g.valid_g, g.er_g, g.el_g, g.status_g, g.accept_g, G, n,
-                       r->good, accept, r->flags, w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats);
+                       r->good, accept, r->flags, stats);
     HIPCHK(hipGetLastError());
     return H2V_OK;
 }
@@ -2847,7 +2922,7 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     // proof (everything else is final); stage 2 - window tables, per-proof MSM, per-proof pairing - decides inside those
     // groups.  Walking grids of one wave per SIMD: finding out that a launch is not needed costs a few microseconds, and a
     // launch that IS needed has the whole chip.
-    if (rlc_groups_on(n) && (rc = rlc_groups_launch(r, p, w, n, accept, d1, pm))) return rc;
+    if (rlc_groups_on(n) && (rc = rlc_groups_launch(r, grp_of_plan(p, w), n, accept, d1, pm, w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats))) return rc;
     const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0);
     {
         const uint32_t nb = (n * slots + 63) / 64;
@@ -2867,6 +2942,104 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
+
+// ---- the batch check over pairs (h2v_check_pairs_rlc; H2V_RLC_FOLD_PAIRS) ---------------------------------------------------
+// n two-slot records of affine points in `pool` (the layout of w->pts).  Enqueues on `st`: the coefficient kernel
+// (k_rlc_pairs_prepare), L = sum r_i L_i and R = sum r_i R_i as two bucket MSMs with 128-bit scalars in the same launches, ONE
+// k_pairing_rlc over a one-proof view of the plan, and - skipped on the device when the check passed - the group stage.  The
+// caller queues its stage 2 behind it with r->flags as skip flags.  good_given: r->good holds good_i already and `status` is
+// final (k_fold_pairs_affine ran, behind the caller's ev[10]); otherwise valid / valid_sub of the two slots decide and
+// H2V_ST_BAD_POINT is folded into `status`.  Events of the record: [10]/[4] around the coefficient kernel, [5] .. [8] the bucket
+// MSMs, [8]/[9] around the pairing.  The workspace's failing-group estimate is not touched (stats = NULL).
+static int pairs_rlc_core(const h2v_plan *p, uint32_t n, RlcWs *r, const uint32_t *pool, const uint8_t *valid, const uint8_t *valid_sub, bool good_given,
+                          uint32_t *status, uint8_t *accept, h2v_workspace *w, CallRec &rec, hipStream_t st, const uint32_t seed[8], uint32_t *fail_ctr) {
+    hipEvent_t *ev = rec.ev;
+    int rc;
+    if (!good_given) HIPCHK(hipEventRecord(ev[10], st));
+    RlcPairArgs ra = {n, status, valid, valid_sub, good_given ? r->good : nullptr, {}, r->r_scal, r->l_idx, r->r_idx, r->good};
+    for (int k = 0; k < 8; k++) ra.seed[k] = seed[k];
+    hipLaunchKernelGGL(k_rlc_pairs_prepare, dim3((n + 63) / 64), dim3(64), 0, st, ra);
+    HIPCHK(hipEventRecord(ev[4], st));
+    PipArgs pa[2] = {};
+    pa[0].n = n; pa[0].halves = 1; pa[0].scal = r->r_scal; pa[0].pidx = r->r_idx; pa[0].pool0 = pool; pa[0].n_pool0 = 2 * n; pa[0].pool1 = nullptr; pa[0].out = r->sums;
+    pa[1] = pa[0]; pa[1].pidx = r->l_idx; pa[1].out = r->sums + 36;
+    const PipWs *pws[2] = {&r->R, &r->L};
+    if ((rc = pip_launch(pws, pa, 2, st, ev + 5))) return rc;   // ev[5..8]
+    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    H2vDevPlan d1 = p->d;
+    d1.n_points = 1; d1.n_ci = 0; d1.ivc = 0; d1.pi_point = 0;
+    uint32_t *st1 = r->misc + 24, *skip = r->flags;
+    uint8_t *valid1 = (uint8_t *)(r->misc + 26), *acc1 = (uint8_t *)(r->misc + 27);
+    HIPCHK(hipMemsetAsync(r->misc + 24, 0, 4, st));
+    HIPCHK(hipMemsetAsync(valid1, 1, 1, st));
+    if (!fail_ctr) {
+        fail_ctr = rec_word(w, rec);
+        HIPCHK(hipMemsetAsync(fail_ctr, 0, 4, st));
+    }
+    hipLaunchKernelGGL(k_pairing_rlc, dim3(1), dim3(64), COOP_LDS_BYTES(1), st, d1, r->misc, valid1, r->sums, r->sums + 36, st1, acc1, n, r->good, accept, skip,
+                       (n + 63) / 64, fail_ctr, (uint32_t *)nullptr, rlc_groups_on(n) ? 1u : 0u);
+    HIPCHK(hipEventRecord(ev[9], st));
+    if (rlc_groups_on(n) && (rc = rlc_groups_launch(r, grp_of_pairs(p, pool), n, accept, d1, st, nullptr))) return rc;
+    HIPCHK(hipGetLastError());
+    return H2V_OK;
+}
+// One batch check over n encoded pairs: decoded as run_check decodes them (the same launch over the same two-slot view), then
+// pairs_rlc_core; stage 2 of the fall-back is run_check's own pair of kernels on a walking grid behind the skip flags.
+// Everything on `st`.  fail_ctr as for run_rlc.  Events: [0]/[1] around the decoding, [2] = [3] (no transcript), then the core's.
+static int run_pairs_rlc(const h2v_plan *p, uint32_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
+                         const uint32_t seed[8], uint32_t *fail_ctr) {
+    opts_from(w);
+    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
+    int rc;
+    if ((rc = pair_view_ensure(w)) || (rc = pair_rlc_ensure(w, false))) return rc;
+    if (!fail_ctr && (rc = rlc_stats_ensure(w))) return rc;      // (the records' verdict words)
+    H2vDevPlan v = p->d;
+    v.proof_len = 96; v.n_points = 2; v.n_ci = 0; v.n_pi = 0; v.ivc = 0; v.pi_point = 0; v.points = w->pair_pts;
+    RlcWs *r = w->prlc;
+    CallRec &rec = rec_new(w, h2v_workspace::RLC);
+    rec.no_vm = true;
+    hipEvent_t *ev = rec.ev;
+    for (int q : {0, 2, 3}) HIPCHK(hipEventRecord(ev[q], st));
+    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
+    HIPCHK(hipMemsetAsync(w->status, 0, (size_t)n * 4, st));
+    const uint32_t dec_grid = (n * 2 + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
+    const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
+    hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, pairs, (const uint64_t *)w->pair_off, (const uint8_t *)nullptr,
+                       (const uint8_t *)nullptr, w->pts, w->valid, (uint32_t *)nullptr, w->valid_sub, w->dec_ctr, dec_grid);
+    HIPCHK(hipEventRecord(ev[1], st));
+    if ((rc = pairs_rlc_core(p, n, r, w->pts, w->valid, w->valid_sub, false, w->status, accept, w, rec, st, seed, fail_ctr))) return rc;
+    const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
+    hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er, (const uint32_t *)r->flags);
+    hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, v, n, w->pts, w->valid, w->valid_sub, w->er, (const uint32_t *)nullptr,
+                       w->status, accept, (uint32_t *)nullptr, (const uint32_t *)r->flags);
+    HIPCHK(hipGetLastError());
+    if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    return H2V_OK;
+}
+// H2V_RLC_FOLD_PAIRS: what run_pipeline enqueues in place of the per-proof pairing of a recursive plan.  After the fold every
+// proof is a pair (el', er') like any other: k_fold_pairs_affine writes them into the set's pool, the core combines them, and
+// the fall-back is the per-proof pairing on the folded points behind the skip flags - no MSM is repeated.
+static int fold_pairs_tail(const FoldPairs &f, uint32_t n, const uint32_t *er2, const uint32_t *el2, uint8_t *accept, h2v_workspace *w, CallRec &rec, hipStream_t st) {
+    int rc;
+    if ((rc = pair_rlc_ensure(w, true))) return rc;
+    if (!f.fail_ctr && (rc = rlc_stats_ensure(w))) return rc;
+    RlcWs *r = w->prlc;
+    const H2vDevPlan &d = f.p->d;
+    HIPCHK(hipEventRecord(rec.ev[10], st));
+    hipLaunchKernelGGL(k_fold_pairs_affine, dim3((n + 63) / 64), dim3(64), 0, st, n, (uint32_t)H2V_SLOTS(d), w->valid, w->valid_sub, el2, er2, w->status, r->pool, r->good);
+    if ((rc = pairs_rlc_core(f.p, n, r, r->pool, nullptr, nullptr, true, w->status, accept, w, rec, st, f.seed, f.fail_ctr))) return rc;
+    const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
+    hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, d, n, w->pts, w->valid, w->valid_sub, er2, el2,
+                       w->status, accept, (uint32_t *)nullptr, (const uint32_t *)r->flags);
+    HIPCHK(hipGetLastError());
+    return H2V_OK;
+}
+static int run_fold_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
+                        uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], uint32_t *fail_ctr) {
+    const FoldPairs f = {p, seed, fail_ctr};
+    return run_pipeline(p->d, n, proofs, off, inst, ci, accept, status_out, w, st, nullptr, false, nullptr, &f);
+}
+static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o) { return p->d.ivc && o && (o->flags & H2V_RLC_FOLD_PAIRS); }
 // The batch coefficients must be unpredictable to whoever made the proofs: 32 bytes from the OS per call (getrandom; fails
 // closed).  A caller-given seed (H2V_RLC_SEED_GIVEN) is for TESTS and reproducible measurements only; even then every call
 // gets different coefficients - the process-wide call counter is mixed in - so that a service that copied a fixed seed
@@ -2924,6 +3097,13 @@ extern "C" int h2v_verify_batch_rlc_device(const h2v_plan *p, const h2v_batch *b
     if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
     if ((rc = null_stream_check(ws, stream))) return rc;
     // recursive plans fold an accumulator per proof (the challenge hashes that proof's own MSM result): no batch form
+    if (!rlc_supported(p) && fold_pairs_wanted(p, opts)) {     // the opt-in batch form of recursive plans: it starts after the fold
+        uint32_t seed[8];
+        if ((rc = rlc_seed(opts, seed))) return rc;
+        const PairIO pio{nullptr, nullptr, seed};
+        if (ws->n_lanes) return run_laned(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, false, nullptr, false, false, &pio);
+        return run_fold_rlc(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, seed, nullptr);
+    }
     if (!rlc_supported(p)) {
         if (ws->n_lanes) return run_laned(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, false, nullptr, false);
         return run_pipeline(p->d, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, nullptr, false);
@@ -2940,6 +3120,59 @@ extern "C" int h2v_verify_batch_rlc(const h2v_plan *p, const h2v_batch *b, uint8
     int rc = rlc_check_batch(p, b, accept);
     if (rc) return rc;
     return verify_host(p, b, accept, ws, H2V_SUBMIT_RLC, opts, fell_back);
+}
+
+// ---- h2v_check_pairs_rlc(_device): h2v_check_pairs's contract, with ONE pairing for the batch when every pair's equation holds ----
+static int pairs_rlc_enqueue(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws, hipStream_t st,
+                             const uint32_t seed[8], bool join) {
+    const PairIO pio{nullptr, pairs, seed};
+    if (ws->n_lanes) return run_laned(p, (uint32_t)n, nullptr, nullptr, nullptr, nullptr, accept, status, ws, st, false, nullptr, join, false, &pio);
+    return run_pairs_rlc(p, (uint32_t)n, pairs, accept, status, ws, st, seed, nullptr);
+}
+extern "C" int h2v_check_pairs_rlc_device(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status,
+                                          h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
+    if (n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 pairs");
+    if (n == 0) return H2V_OK;
+    if (!ws) return fail(H2V_E_ARG, "the RLC entry points need a workspace (results of the batch check live in it)");
+    h2v_workspace *tmp = nullptr;
+    if (int rc = pairs_common(p, n, ws, stream, true, &tmp)) return rc;
+    uint32_t seed[8];
+    if (int rc = rlc_seed(opts, seed)) return rc;
+    return pairs_rlc_enqueue(p, n, pairs, accept, status, ws, (hipStream_t)stream, seed, false);
+}
+extern "C" int h2v_check_pairs_rlc(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws,
+                                   const h2v_rlc_opts *opts, int *fell_back) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
+    if (n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 pairs");
+    if (fell_back) *fell_back = 0;
+    if (n == 0) return H2V_OK;
+    h2v_workspace *tmp = nullptr;
+    if (int rc = pairs_common(p, n, ws, nullptr, false, &tmp)) return rc;
+    if (tmp) ws = tmp;
+    uint32_t seed[8];
+    int rc = rlc_seed(opts, seed);
+    if (rc == H2V_OK) rc = host_stream(ws);
+    if (rc == H2V_OK) rc = hp_ensure(ws, n);
+    if (rc == H2V_OK) {
+        uint8_t *d_pairs = ws->hp_buf, *d_accept = ws->hp_buf + (size_t)n * 100;
+        uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
+        uint32_t failed = 0;
+        if (hipMemcpyAsync(d_pairs, pairs, (size_t)n * 96, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the pairs failed");
+        if (rc == H2V_OK) rc = pairs_rlc_enqueue(p, n, d_pairs, d_accept, d_status, ws, ws->hs, seed, true);
+        if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
+        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
+        if (rc == H2V_OK && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
+        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "pair check kernels failed");
+        if (rc) rc = drain_after_error(ws, rc);
+        else if (fell_back) *fell_back = failed ? 1 : 0;
+    }
+    if (tmp) h2v_workspace_free(tmp);
+    return rc;
 }
 // After the stream of an RLC call has been synchronised: did the batch check pass (1) or did the per-proof kernels run (0)?
 // kernel times of a past call (calls_back = 0: the most recent).
@@ -2993,7 +3226,7 @@ static int rec_rlc_timings(const CallRec &r, h2v_rlc_timings *tm) {
     memset(tm, 0, sizeof *tm);
     HIPCHK(hipEventSynchronize(ev[9]));
     HIPCHK(hipEventElapsedTime(&tm->g1_decompress_ms, ev[0], ev[1]));
-    HIPCHK(hipEventElapsedTime(&tm->transcript_combiner_ms, ev[2], ev[3]));
+    if (!r.no_vm) HIPCHK(hipEventElapsedTime(&tm->transcript_combiner_ms, ev[2], ev[3]));
     HIPCHK(hipEventElapsedTime(&tm->prepare_ms, ev[10], ev[4]));
     HIPCHK(hipEventElapsedTime(&tm->bucket_sort_ms, ev[5], ev[6]));
     HIPCHK(hipEventElapsedTime(&tm->bucket_accumulate_ms, ev[6], ev[7]));

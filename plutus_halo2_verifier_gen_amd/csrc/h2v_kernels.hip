@@ -1464,8 +1464,10 @@ k_prepare_export(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, 
     for (int k = 0; k < 24; k++) o[k] = words[k];
 }
 // The pair check's R as the pairing kernels take it: slot 1 of each two-slot record of `pts` (affine) -> Jacobian (n x 36 dwords)
+// skip (the fall-back of the pairs' batch check, or NULL): return at once when *skip != 0
 extern "C" __global__ void __launch_bounds__(64)
-k_pairs_to_jac(uint32_t n, const uint32_t *__restrict__ pts, uint32_t *__restrict__ er_jac) {
+k_pairs_to_jac(uint32_t n, const uint32_t *__restrict__ pts, uint32_t *__restrict__ er_jac, const uint32_t *__restrict__ skip) {
+    if (skip && skip[0]) return;
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     G1A a;

@@ -179,3 +179,86 @@ k_rlc_group_terms(RlcGroupArgs a, const uint32_t *__restrict__ skip) {
         a.g_idx[dst + nt + f] = a.n * a.slots + a.terms[2 * (a.n_var + f) + 1];
     }
 }
+
+// ---- the batch check over PAIRS (h2v_check_pairs_rlc, and recursive plans after the fold: H2V_RLC_FOLD_PAIRS) --------------
+// n two-slot records (L_i, R_i) of affine points in a pool laid out like the workspace's point buffer (2 x 24 dwords each):
+//   L = sum_i r_i L_i (point index 2 i),  R = sum_i r_i R_i (index 2 i + 1),  ONE scalar array for both sums (128-bit: no GLV)
+// k_rlc_pairs_prepare, one lane per pair: good_i - from valid / valid_sub of the pair's two slots, with H2V_ST_BAD_POINT folded
+// into the status word (decoded pairs), or as given (good_in: pairs that k_fold_pairs_affine made) - and r_i as k_rlc_prepare
+// draws it (0 when !good_i).  A lane beyond n computes on a clamped index and writes nothing.
+struct RlcPairArgs {
+    uint32_t n;
+    uint32_t *status;                        // n (decoded pairs: H2V_ST_BAD_POINT is folded in here)
+    const uint8_t *valid, *valid_sub;        // n x 2, or NULL with good_in
+    const uint8_t *good_in;                  // n, or NULL (may be `good` itself)
+    uint32_t seed[8];
+    uint32_t *scal, *l_idx, *r_idx;          // n x 8, n, n
+    uint8_t *good;                           // n
+};
+extern "C" __global__ void __launch_bounds__(64)
+k_rlc_pairs_prepare(RlcPairArgs a) {
+    __shared__ uint32_t sbuf[32 * 64];
+    const int lane = threadIdx.x;
+    const uint32_t i = blockIdx.x * 64 + lane;
+    const bool live = i < a.n;
+    const uint32_t ii = live ? i : a.n - 1;
+    uint32_t st = a.status[ii];
+    bool good;
+    if (a.good_in) {
+        good = live && a.good_in[ii] != 0;
+    } else {
+        for (uint32_t j = 0; j < 2; j++)
+            if (!a.valid[(size_t)ii * 2 + j] || (a.valid_sub && !a.valid_sub[(size_t)ii * 2 + j])) st |= H2V_ST_BAD_POINT;
+        good = live && st == 0;
+    }
+    Transcript tr;
+    tr_init(tr);
+#pragma unroll 1
+    for (int k = 0; k < 32; k++) tr_put(tr, sbuf, lane, (a.seed[k >> 2] >> (8 * (k & 3))) & 0xffu);
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) tr_put(tr, sbuf, lane, (ii >> (8 * k)) & 0xffu);
+    uint64_t h[4];
+    tr_digest(tr, sbuf, lane, h);
+    uint32_t r[4] = {(uint32_t)h[0], (uint32_t)(h[0] >> 32), (uint32_t)h[1], (uint32_t)(h[1] >> 32)};
+    if ((r[0] | r[1] | r[2] | r[3]) == 0) r[0] = 1;
+    if (!good) { r[0] = 0; r[1] = 0; r[2] = 0; r[3] = 0; }
+    if (live) {
+        if (!a.good_in) a.status[i] = st;
+        a.good[i] = good ? 1 : 0;
+#pragma unroll
+        for (int l = 0; l < 8; l++) a.scal[(size_t)i * 8 + l] = l < 4 ? r[l] : 0u;
+        a.l_idx[i] = 2 * i;
+        a.r_idx[i] = 2 * i + 1;
+    }
+}
+
+// Recursive plans, after launch_ivc_fold: the folded pair (el', er') of every proof (Jacobian, n x 36 dwords each) as a
+// two-slot affine record of a pool of its own - ONE inversion per proof (g1j_to_affine_batch); infinity stays the all-zero
+// record the bucket MSM's loader reads as infinity.  status folds valid / valid_sub of the proof's slots into
+// H2V_ST_BAD_POINT as the pairing kernels do; good_i = nothing rejected so far (H2V_ST_RECURSION included).  One lane per proof.
+extern "C" __global__ void __launch_bounds__(64)
+k_fold_pairs_affine(uint32_t n, uint32_t slots, const uint8_t *__restrict__ valid, const uint8_t *__restrict__ valid_sub,
+                    const uint32_t *__restrict__ el_jac, const uint32_t *__restrict__ er_jac, uint32_t *__restrict__ status,
+                    uint32_t *__restrict__ pool /* n x 2 x 24 */, uint8_t *__restrict__ good) {
+    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    uint32_t st = status[i];
+    for (uint32_t j = 0; j < slots; j++)
+        if (!valid[(size_t)i * slots + j] || (valid_sub && !valid_sub[(size_t)i * slots + j])) st |= H2V_ST_BAD_POINT;
+    status[i] = st;
+    good[i] = st == 0 ? 1 : 0;
+    G1J j[2];
+    const uint32_t *src[2] = {el_jac, er_jac};
+    for (int q = 0; q < 2; q++) {
+#pragma unroll
+        for (int k = 0; k < 12; k++) { j[q].x.v[k] = src[q][(size_t)i * 36 + k]; j[q].y.v[k] = src[q][(size_t)i * 36 + 12 + k]; j[q].z.v[k] = src[q][(size_t)i * 36 + 24 + k]; }
+    }
+    if (st != 0) { g1j_set_inf(j[0]); g1j_set_inf(j[1]); }   // (takes no part: whatever the MSM left there is not normalised)
+    G1A p[2];
+    g1j_to_affine_batch<2>(p, j);
+    uint32_t *o = pool + (size_t)i * 48;
+#pragma unroll
+    for (int q = 0; q < 2; q++)
+#pragma unroll
+        for (int k = 0; k < 12; k++) { o[24 * q + k] = p[q].x.v[k]; o[24 * q + 12 + k] = p[q].y.v[k]; }
+}
