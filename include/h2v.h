@@ -109,6 +109,20 @@ void h2v_plan_free(h2v_plan *plan);
 /* plan facts: proof length in bytes, public inputs per proof, committed instances per proof (0/1), MSM terms T */
 int h2v_plan_info(const h2v_plan *plan, uint32_t *proof_len, uint32_t *n_public_inputs, uint32_t *n_committed,
                   uint32_t *n_msm_terms);
+/* The transcript hash of the plan's key: the H of the reference's CircuitTranscript<H>.  It is a property of the verifying
+ * key (docs/vk_schema.json: transcript_hash), carried by the plan and read by the launcher; callers never pass it per call.
+ *   H2V_TRANSCRIPT_CARDANO_BLAKE2B_256  CardanoFriendlyBlake2b (src/plutus_gen/adjusted_types/mod.rs:30-72): unkeyed
+ *                                       blake2b-256, a challenge is h || blake2b-256(h).  Plans without the field (version 4).
+ *   H2V_TRANSCRIPT_BLAKE2B_512          halo2's default blake2b_simd::State: blake2b with a 64-byte digest, keyed with a
+ *                                       domain-separator key of up to 64 bytes; a challenge is the 64-byte digest of a copy of
+ *                                       the running state.  Such plans are version 5: an older library refuses them.
+ * *kind: one of the above; key_out: the blake2b key, zero-padded to 64 bytes; *key_len: its length (0 for the Cardano kind).
+ * Any of the three may be NULL.
+ * A proof made under ANOTHER hash than the plan's is not an API error: it replays to other challenges, its pairing equation
+ * fails and it is REJECTED with H2V_ST_PAIRING, like any proof that does not verify under this key. */
+#define H2V_TRANSCRIPT_CARDANO_BLAKE2B_256 0u
+#define H2V_TRANSCRIPT_BLAKE2B_512 1u
+int h2v_plan_transcript(const h2v_plan *plan, uint32_t *kind, uint8_t key_out[64], uint32_t *key_len);
 
 /* A workspace is sized from `plan` (MSM terms, point slots, register file, recursion / fixed-base buffers).  It may be
  * reused with ANOTHER plan only if that plan needs no more of any of these; otherwise the verify calls return H2V_E_ARG
@@ -371,6 +385,12 @@ int h2v_trace(const h2v_plan *plan, const uint8_t *proof, size_t proof_len, cons
 /* primitive probes for the GPU parity tests (host buffers; canonical little-endian limbs) */
 int h2v_probe_field(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out);
 int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint8_t *digests);
+/* The same through the code path of the keyed transcript flavour: blake2b with a digest of digest_len = 32 or 64 bytes, keyed
+ * with key[0 .. key_len) (key_len <= 64; 0 = unkeyed, key may be NULL), of n messages of `len` bytes each; digests: n x
+ * digest_len bytes.  The state behind the key block is worked out on the host as h2v_plan_load does it; an empty message
+ * under a key (the key block is then the final block) is hashed on the device from the start. */
+int h2v_probe_blake2b_ex(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint32_t digest_len, const uint8_t *key,
+                         uint32_t key_len, uint8_t *digests);
 int h2v_probe_g1_decompress(int device, uint32_t n, const uint8_t *compressed, uint8_t *xy_be, uint8_t *valid);
 /* sum_t s_t * B_t per group: n groups of T terms; scalars n*T*32 B LE, bases n*T*48 B compressed; out n*96 B affine BE */
 int h2v_probe_g1_msm(int device, uint32_t n, uint32_t T, const uint8_t *scalars, const uint8_t *bases_compressed,

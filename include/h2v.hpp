@@ -77,14 +77,32 @@ class VerifyingKey {  // VerifyingKey<F, KZGCommitmentScheme<Bls12>> + ParamsVer
     uint32_t proof_len() const { uint32_t v; check(h2v_plan_info(p_, &v, nullptr, nullptr, nullptr)); return v; }
     uint32_t n_public_inputs() const { uint32_t v; check(h2v_plan_info(p_, nullptr, &v, nullptr, nullptr)); return v; }
     uint32_t n_committed_instances() const { uint32_t v; check(h2v_plan_info(p_, nullptr, nullptr, &v, nullptr)); return v; }
+    /// the transcript hash the key's proofs are made under (H2V_TRANSCRIPT_*), and its blake2b key (empty for the Cardano kind)
+    uint32_t transcript_kind() const { uint32_t v; check(h2v_plan_transcript(p_, &v, nullptr, nullptr)); return v; }
+    std::vector<uint8_t> transcript_key() const {
+        uint8_t key[64];
+        uint32_t n = 0;
+        check(h2v_plan_transcript(p_, nullptr, key, &n));
+        return std::vector<uint8_t>(key, key + n);
+    }
 
   private:
     h2v_plan *p_ = nullptr;
 };
 
-class CircuitTranscript {  // verifier-side transcript: a cursor over the proof bytes (hashing happens on the GPU)
+// The H of the reference's CircuitTranscript<H>, as tag types.  The hash itself is a property of the verifying key (it is in
+// the plan, h2v_plan_transcript) and runs on the GPU; the tag is what Rust's type parameter is: prepare() with a transcript
+// whose H is not the key's throws h2v::Error(H2V_E_ARG) - misuse, where Rust does not compile - and never rejects.  A proof
+// that was in fact made under another hash than its tag claims is rejected by the pairing like any other bad proof.
+struct CardanoFriendlyBlake2b { static constexpr uint32_t kind = H2V_TRANSCRIPT_CARDANO_BLAKE2B_256; };   // adjusted_types/mod.rs:30-72
+struct Blake2b512 { static constexpr uint32_t kind = H2V_TRANSCRIPT_BLAKE2B_512; };                       // blake2b_simd::State
+// Transcript<H> is CircuitTranscript<H>; `CircuitTranscript` itself stays the name of the Cardano instantiation, as every
+// caller written before there was a choice spells it (a C++ name cannot be a class and a template at once).
+template <class H>
+class Transcript {  // verifier-side transcript: a cursor over the proof bytes (hashing happens on the GPU)
   public:
-    static CircuitTranscript init_from_bytes(std::vector<uint8_t> proof) { return CircuitTranscript(std::move(proof)); }
+    typedef H Hash;
+    static Transcript init_from_bytes(std::vector<uint8_t> proof) { return Transcript(std::move(proof)); }
     const std::vector<uint8_t> &bytes() const { return proof_; }
     void mark_consumed(size_t n) { consumed_ = n; }
     void assert_empty() const {  // examples/ivc.rs:92-94
@@ -92,10 +110,12 @@ class CircuitTranscript {  // verifier-side transcript: a cursor over the proof 
     }
 
   private:
-    explicit CircuitTranscript(std::vector<uint8_t> p) : proof_(std::move(p)) {}
+    explicit Transcript(std::vector<uint8_t> p) : proof_(std::move(p)) {}
     std::vector<uint8_t> proof_;
     size_t consumed_ = 0;
 };
+using CircuitTranscript = Transcript<CardanoFriendlyBlake2b>;
+using CircuitTranscriptBlake2b512 = Transcript<Blake2b512>;
 
 // The collapsed DualMSM of one proof: the two points of its final pairing check e(left, s_g2) == e(right, G2), 48-byte
 // compressed each (h2v_prepare_batch).  check() runs that pairing (h2v_check_pairs).
@@ -150,8 +170,10 @@ class Guard {  // CS::VerificationGuard: consumed by verify() (Guard::verify), c
 
 // prepare(&vk, committed_instances, instances, &mut transcript): committed = 0 or 1 compressed G1 (48 B),
 // instances = the public-input scalars of the single public column, 32 B little-endian each.
+template <class H>
 inline Guard prepare(const VerifyingKey &vk, const std::vector<std::vector<uint8_t>> &committed_instances,
-                     const std::vector<std::vector<uint8_t>> &instances, CircuitTranscript &transcript) {
+                     const std::vector<std::vector<uint8_t>> &instances, Transcript<H> &transcript) {
+    if (vk.transcript_kind() != H::kind) throw Error(H2V_E_ARG, "transcript hash mismatch: the verifying key's proofs are made under another hash than this transcript's");
     if (instances.size() != vk.n_public_inputs()) throw Error(H2V_E_ARG, "wrong number of public inputs");
     if (committed_instances.size() != vk.n_committed_instances()) throw Error(H2V_E_ARG, "wrong number of committed instances");
     std::vector<uint8_t> inst, ci;

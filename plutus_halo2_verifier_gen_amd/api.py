@@ -49,17 +49,28 @@ class ParamsVerifierKZG:
     s_g2: bytes  # 96-byte zcash-compressed G2
 
 
-class CircuitTranscript:
-    """CircuitTranscript<CardanoFriendlyBlake2b> on the verifier side: a cursor over the proof bytes.
-    (/root/reference/src/plutus_gen/adjusted_types/mod.rs:30-72 is replayed on the GPU, not here.)"""
+# The H of CircuitTranscript<H>, as a tag: Rust's type parameter.  The hash itself belongs to the verifying key
+# (vk.transcript_hash) and is replayed on the GPU; the tag only says what the caller believes the proof was made under.
+CARDANO_FRIENDLY_BLAKE2B = "cardano-blake2b-256"   # CardanoFriendlyBlake2b (adjusted_types/mod.rs:30-72)
+BLAKE2B_512 = "blake2b-512"                        # blake2b_simd::State, halo2's and midnight's default
 
-    def __init__(self, proof: bytes):
+
+class CircuitTranscript:
+    """CircuitTranscript<H> on the verifier side: a cursor over the proof bytes and the tag of H
+    (CARDANO_FRIENDLY_BLAKE2B, the default, or BLAKE2B_512).  The hash is replayed on the GPU, not here
+    (/root/reference/src/plutus_gen/adjusted_types/mod.rs:30-72 and the default flavour it is adjusted from)."""
+
+    def __init__(self, proof: bytes, hash: str = CARDANO_FRIENDLY_BLAKE2B):
+        from .vk import TRANSCRIPT_KINDS
+        if hash not in TRANSCRIPT_KINDS:
+            raise ValueError("unknown transcript hash %r (known: %s)" % (hash, ", ".join(sorted(TRANSCRIPT_KINDS))))
         self._proof = bytes(proof)
         self._consumed = 0
+        self.hash = hash
 
     @classmethod
-    def init_from_bytes(cls, proof: bytes) -> "CircuitTranscript":
-        return cls(proof)
+    def init_from_bytes(cls, proof: bytes, hash: str = CARDANO_FRIENDLY_BLAKE2B) -> "CircuitTranscript":
+        return cls(proof, hash)
 
     @property
     def proof(self) -> bytes:
@@ -227,6 +238,13 @@ def prepare(vk: VerifyingKey, committed_instances: Sequence[Sequence[Optional[by
     (the outer slices have length 1, as at every call site of the reference)."""
     if len(instances) != 1 or len(committed_instances) != 1:
         raise ValueError("one proof per prepare() call; use Verifier.verify_batch for batches")
+    # prepare::<F, KZG, CircuitTranscript<H>> with an H that is not the key's does not compile in Rust; here it is API misuse
+    # (never a reject), found before anything is loaded or launched.  A proof that was MADE under another hash than its tag
+    # says is a different matter: nobody can see that, and it is rejected by the pairing like any bad proof.
+    from .vk import TRANSCRIPT_KINDS, transcript_kind
+    if TRANSCRIPT_KINDS[transcript.hash] != transcript_kind(vk)[0]:
+        want = [k for k, v in TRANSCRIPT_KINDS.items() if v == transcript_kind(vk)[0]][0]
+        raise ValueError("transcript hash mismatch: the transcript is CircuitTranscript<%s>, the verifying key's is %s" % (transcript.hash, want))
     cols = instances[0]
     pub = list(cols[0]) if len(cols) else []
     v = verifier_for(vk, device)

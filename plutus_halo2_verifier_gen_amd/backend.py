@@ -87,7 +87,12 @@ EXPORTS = [
     "h2v_device_count", "h2v_shutdown",
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
     "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device",
+    "h2v_plan_transcript", "h2v_probe_blake2b_ex",
 ]
+
+# transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
+TRANSCRIPT_CARDANO_BLAKE2B_256, TRANSCRIPT_BLAKE2B_512 = 0, 1
+TRANSCRIPT_NAMES = {TRANSCRIPT_CARDANO_BLAKE2B_256: "cardano-blake2b-256", TRANSCRIPT_BLAKE2B_512: "blake2b-512"}
 
 _lib = None
 
@@ -141,6 +146,8 @@ def lib():
         L.h2v_workspace_rlc_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RlcTimings)]
         L.h2v_probe_g1_msm_pippenger.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
         L.h2v_plan_trace_slots.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
+        L.h2v_plan_transcript.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32)]
+        L.h2v_probe_blake2b_ex.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p]
         L.h2v_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
         L.h2v_probe_field.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -219,6 +226,10 @@ class DevicePlan:
         slots = (C.c_uint32 * max(1, n.value))()
         check(lib().h2v_plan_trace_slots(self._h, slots, n.value, C.byref(n)))
         self.trace_slots = list(slots[:n.value])
+        kind, klen, key = C.c_uint32(), C.c_uint32(), C.create_string_buffer(64)
+        check(lib().h2v_plan_transcript(self._h, C.byref(kind), key, C.byref(klen)))
+        # the transcript hash of the plan's key (TRANSCRIPT_*) and its blake2b key: what api.prepare holds a transcript's tag against
+        self.transcript_kind, self.transcript_key = kind.value, key.raw[:klen.value]
 
     @property
     def handle(self):
@@ -528,6 +539,17 @@ def probe_blake2b(msgs, device: int = 0):
     out = C.create_string_buffer(32 * n)
     check(lib().h2v_probe_blake2b(device, n, ln, b"".join(msgs), out))
     return [out.raw[32 * i:32 * i + 32] for i in range(n)]
+
+
+def probe_blake2b_ex(msgs, digest_len: int = 64, key: bytes = b"", device: int = 0):
+    """blake2b of `digest_len` (32 / 64) bytes keyed with `key` of equally long messages, through the transcript code of the
+    keyed flavour (tr_put / tr_digest behind a host-computed state)."""
+    n = len(msgs)
+    ln = len(msgs[0])
+    assert all(len(m) == ln for m in msgs)
+    out = C.create_string_buffer(digest_len * n)
+    check(lib().h2v_probe_blake2b_ex(device, n, ln, b"".join(msgs), digest_len, bytes(key), len(key), out))
+    return [out.raw[digest_len * i:digest_len * (i + 1)] for i in range(n)]
 
 
 def _unxy(b):

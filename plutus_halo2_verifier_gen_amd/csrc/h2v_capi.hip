@@ -109,6 +109,8 @@ struct h2v_plan {
     void *six_tab = nullptr;     // unit-coefficient line constants of the six-lane pairing engine + its dump constants (six_line_tables)
     uint32_t n_var = 0, n_fix = 0;  // per-proof terms [0, n_var), VK-base terms [n_var, n_var + n_fix) when the list is so ordered
     uint32_t n_squeezes = 0, stream_len = 0;
+    uint32_t tr_kind = 0, tr_key_len = 0;   // transcript hash of the key (H2V_TRANSCRIPT_*) and its blake2b key
+    uint8_t tr_key[H2V_TR_KEY_MAX] = {};
     uint64_t gen = 0;            // process-wide load counter: what caches key on (a freed plan's address may be reused)
     std::vector<uint32_t> trace_slots;
 };
@@ -318,8 +320,16 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
     if (len < hdr || memcmp(blob, H2V_PLAN_MAGIC, 8) != 0) return fail(H2V_E_PLAN, "bad magic / truncated header");
     uint32_t w[H2V_PLAN_HDR_WORDS];
     for (int i = 0; i < H2V_PLAN_HDR_WORDS; i++) w[i] = rd32(blob + 8 + 4 * i);
-    if (w[H2V_HW_VERSION] != H2V_PLAN_VERSION) return fail(H2V_E_PLAN, "unsupported plan version");
+    if (w[H2V_HW_VERSION] != H2V_PLAN_VERSION && w[H2V_HW_VERSION] != H2V_PLAN_VERSION_FLAVOURED) return fail(H2V_E_PLAN, "unsupported plan version");
     if (w[H2V_HW_TOTAL_LEN] != len) return fail(H2V_E_PLAN, "length mismatch");
+    // transcript hash of the key: version 4 knows the Cardano flavour only (its three words are spare and zero)
+    const uint32_t tr_kind = w[H2V_HW_TR_KIND], tr_key_off = w[H2V_HW_TR_KEY_OFF], tr_key_len = w[H2V_HW_TR_KEY_LEN];
+    if (w[H2V_HW_VERSION] == H2V_PLAN_VERSION && (tr_kind || tr_key_off || tr_key_len)) return fail(H2V_E_PLAN, "a version-4 plan names a transcript hash");
+    if (tr_kind >= H2V_TR_KIND_COUNT) return fail(H2V_E_PLAN, "unknown transcript hash kind " + std::to_string(tr_kind));
+    if (tr_key_len > H2V_TR_KEY_MAX) return fail(H2V_E_PLAN, "transcript hash key longer than 64 bytes");
+    if (tr_kind == H2V_TR_CARDANO_BLAKE2B_256 && (tr_key_len || tr_key_off)) return fail(H2V_E_PLAN, "the Cardano transcript hash is unkeyed");
+    if (tr_key_len ? (tr_key_off < 8 + 4 * H2V_PLAN_HDR_WORDS || (uint64_t)tr_key_off + tr_key_len > len) : tr_key_off != 0)
+        return fail(H2V_E_PLAN, "transcript hash key out of bounds");
     struct Sec { int off_word; uint64_t bytes; };
     const uint32_t n_instr = w[H2V_HW_N_INSTR], n_consts = w[H2V_HW_N_CONSTS], n_points = w[H2V_HW_N_POINTS],
                    n_bases = w[H2V_HW_N_VK_BASES], n_terms = w[H2V_HW_N_TERMS], n_trace = w[H2V_HW_N_TRACE],
@@ -495,6 +505,12 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
     d.lines28_sg2 = (const uint32_t *)(base + w[H2V_HW_OFF_LINES28_SG2]);
     d.lines28_g2 = (const uint32_t *)(base + w[H2V_HW_OFF_LINES28_G2]);
     d.ivc = ivc; d.n_main_terms = n_main;
+    // the state every proof's transcript starts from: parameter block, then the key block compressed here, once per plan
+    // (a transcript always hashes at least one byte before a digest is taken, so the key block is never the final one)
+    p->tr_kind = d.tr_kind = tr_kind;
+    p->tr_key_len = tr_key_len;
+    if (tr_key_len) memcpy(p->tr_key, blob + tr_key_off, tr_key_len);
+    if (tr_kind == H2V_TR_BLAKE2B_512) d.tr_t0 = h2vhost::b2_keyed_midstate_host(d.tr_h0, 64, p->tr_key, tr_key_len);
     for (int k = 0; k < 8; k++) d.acc_idx[k] = w[H2V_HW_ACC_IDX0 + k];
     d.fold_terms = (const uint32_t *)p->fold_terms;
     // window tables of the VK bases for the MSM ladder: [1..8]B and [1..8]phi(B), affine, computed once per plan
@@ -594,6 +610,13 @@ extern "C" int h2v_plan_info(const h2v_plan *p, uint32_t *proof_len, uint32_t *n
     if (n_pi) *n_pi = p->d.n_pi;
     if (n_ci) *n_ci = p->d.n_ci;
     if (n_terms) *n_terms = p->d.n_terms;
+    return H2V_OK;
+}
+extern "C" int h2v_plan_transcript(const h2v_plan *p, uint32_t *kind, uint8_t key_out[64], uint32_t *key_len) {
+    if (!p) return fail(H2V_E_ARG, "null plan");
+    if (kind) *kind = p->tr_kind;
+    if (key_out) { memset(key_out, 0, H2V_TR_KEY_MAX); memcpy(key_out, p->tr_key, p->tr_key_len); }
+    if (key_len) *key_len = p->tr_key_len;
     return H2V_OK;
 }
 extern "C" int h2v_plan_trace_slots(const h2v_plan *p, uint32_t *slot_ids, uint32_t cap, uint32_t *n_out) {
@@ -1107,9 +1130,13 @@ static int launch_vm(const H2vDevPlan &d0, uint32_t n, uint32_t stride, const ui
     const uint64_t wide_waves = ((uint64_t)n * d.wide_lanes + 63) / 64;
     const bool wide = wide_ok && (env_wide >= 0 ? env_wide != 0 : wide_waves <= (g_opts.in_flight >= 8 ? 32u : 256u));
     if (wide) { d.vm_lanes = d.wide_lanes; d.n_regs = d.wide_n_regs; d.n_instr = d.wide_n_instr; d.instr = d.wide_instr; }
+    // the kernels are instantiated per transcript hash (a compile-time choice inside them): the plan's kind picks
+    const bool b512 = d.tr_kind == H2V_TR_BLAKE2B_512;
+    if (d.tr_kind >= H2V_TR_KIND_COUNT) return fail(H2V_E_PLAN, "no combiner kernel for this transcript hash");
     uint32_t P = vm_lds_slots(d);
     if (P == 0) {
-        hipLaunchKernelGGL(k_transcript_combiner, dim3((n + 63) / 64), dim3(64), 0, st, d, n, stride, proofs, off, inst, ci, regs, scalars, status, trace);
+        const auto k_glb = b512 ? k_transcript_combiner_b512 : k_transcript_combiner;
+        hipLaunchKernelGGL(k_glb, dim3((n + 63) / 64), dim3(64), 0, st, d, n, stride, proofs, off, inst, ci, regs, scalars, status, trace);
         return H2V_OK;
     }
     // Fewer proofs per block than the wave could serve (the spare lanes shadow): the register file of P proofs is what
@@ -1118,8 +1145,9 @@ static int launch_vm(const H2vDevPlan &d0, uint32_t n, uint32_t stride, const ui
     const int env_p = g_opts.v[H2V_OPT_COMBINER_PROOFS_PER_BLOCK];
     if (env_p >= 1 && (env_p & (env_p - 1)) == 0 && (uint32_t)env_p <= P) P = (uint32_t)env_p;
     const size_t lds = (size_t)d.n_regs * 32 * P;
-    HIPCHK(hipFuncSetAttribute((const void *)k_transcript_combiner_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_transcript_combiner_lds, dim3((n + P - 1) / P), dim3(64), lds, st, d, n, P, proofs, off, inst, ci, scalars, status, trace);
+    const auto k_lds = b512 ? k_transcript_combiner_lds_b512 : k_transcript_combiner_lds;
+    HIPCHK(hipFuncSetAttribute((const void *)k_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_lds, dim3((n + P - 1) / P), dim3(64), lds, st, d, n, P, proofs, off, inst, ci, scalars, status, trace);
     return H2V_OK;
 }
 
@@ -3356,6 +3384,33 @@ extern "C" int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uin
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipMemcpy(digests, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));
+    return H2V_OK;
+}
+extern "C" int h2v_probe_blake2b_ex(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint32_t digest_len, const uint8_t *key,
+                                    uint32_t key_len, uint8_t *digests) {
+    int rc = pick_device(device);
+    if (rc) return rc;
+    if ((len && !msgs) || !digests || n == 0 || (digest_len != 32 && digest_len != 64) || key_len > H2V_TR_KEY_MAX || (key_len && !key))
+        return fail(H2V_E_ARG, "bad argument");
+    if ((uint64_t)n * len > ((uint64_t)1 << 31)) return fail(H2V_E_LIMIT, "messages larger than 2 GB");
+    // with a message the hash starts behind the key block, from the state the plan loader computes on the host; an empty
+    // message makes the key block the final block, which the kernel then hashes itself
+    H2vProbeHash ph{};
+    uint8_t block[128] = {};
+    if (key_len) memcpy(block, key, key_len);
+    const bool key_is_last = key_len != 0 && len == 0;
+    ph.t0 = h2vhost::b2_keyed_midstate_host(ph.h0, digest_len, key, key_is_last ? 0u : key_len);
+    if (key_is_last) ph.h0[0] ^= (uint64_t)key_len << 8;   // (the mid-state helper was asked for the unkeyed state: put the key length back)
+    ph.prefix_len = key_is_last ? 128u : 0u;
+    ph.digest_words = digest_len / 8;
+    DevBuf dm, dk, dout;
+    if (dm.alloc((size_t)n * len + 16) || dk.alloc(128) || dout.alloc((size_t)n * digest_len)) return fail(H2V_E_DEVICE, "hipMalloc failed");
+    if (len) HIPCHK(hipMemcpy(dm.p, msgs, (size_t)n * len, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dk.p, block, 128, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(k_probe_blake2b_ex, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, len, dm.as<uint8_t>(), ph, dk.as<uint8_t>(), dout.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(digests, dout.p, (size_t)n * digest_len, hipMemcpyDeviceToHost));
     return H2V_OK;
 }
 // A throw-away plan whose "proof" is `slots` consecutive compressed points and whose MSM takes them in order.

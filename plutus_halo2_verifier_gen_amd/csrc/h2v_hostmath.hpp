@@ -414,4 +414,55 @@ static inline std::string g2_decompress(const uint8_t *b, G2 &out, bool check_su
     return "";
 }
 
+// ------------------------------------------------------------------ blake2b (RFC 7693): one compression on the host
+// Plan-load time only: the keyed transcript flavour's key block is compressed once per plan (h2v_plan_load), so that every
+// proof starts from the state behind it.  `block` is the 128-byte message block, `t` the byte counter after it.
+static inline void b2_compress_host(uint64_t h[8], const uint8_t block[128], uint64_t t, bool last) {
+    static const uint64_t IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                                   0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+    static const uint8_t SIGMA[10][16] = {
+        {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, {14, 10, 4, 8, 9, 15, 13, 6, 1, 12, 0, 2, 11, 7, 5, 3},
+        {11, 8, 12, 0, 5, 2, 15, 13, 10, 14, 3, 6, 7, 1, 9, 4}, {7, 9, 3, 1, 13, 12, 11, 14, 2, 6, 5, 10, 4, 0, 15, 8},
+        {9, 0, 5, 7, 2, 4, 10, 15, 14, 1, 11, 12, 6, 8, 3, 13}, {2, 12, 6, 10, 0, 11, 8, 3, 4, 13, 7, 5, 15, 14, 1, 9},
+        {12, 5, 1, 15, 14, 13, 4, 10, 0, 7, 6, 3, 9, 2, 8, 11}, {13, 11, 7, 14, 12, 1, 3, 9, 5, 0, 15, 4, 8, 6, 2, 10},
+        {6, 15, 14, 9, 11, 3, 0, 8, 12, 2, 13, 7, 1, 4, 10, 5}, {10, 2, 8, 4, 7, 6, 1, 5, 15, 11, 9, 14, 3, 12, 13, 0}};
+    uint64_t m[16], v[16];
+    for (int i = 0; i < 16; i++) {
+        m[i] = 0;
+        for (int k = 7; k >= 0; k--) m[i] = (m[i] << 8) | block[8 * i + k];
+    }
+    for (int i = 0; i < 8; i++) { v[i] = h[i]; v[i + 8] = IV[i]; }
+    v[12] ^= t;
+    if (last) v[14] = ~v[14];
+    auto rotr = [](uint64_t x, int n) { return (x >> n) | (x << (64 - n)); };
+    auto G = [&](int a, int b, int c, int d, uint64_t x, uint64_t y) {
+        v[a] = v[a] + v[b] + x; v[d] = rotr(v[d] ^ v[a], 32); v[c] = v[c] + v[d]; v[b] = rotr(v[b] ^ v[c], 24);
+        v[a] = v[a] + v[b] + y; v[d] = rotr(v[d] ^ v[a], 16); v[c] = v[c] + v[d]; v[b] = rotr(v[b] ^ v[c], 63);
+    };
+    for (int r = 0; r < 12; r++) {
+        const uint8_t *s = SIGMA[r % 10];
+        G(0, 4, 8, 12, m[s[0]], m[s[1]]); G(1, 5, 9, 13, m[s[2]], m[s[3]]);
+        G(2, 6, 10, 14, m[s[4]], m[s[5]]); G(3, 7, 11, 15, m[s[6]], m[s[7]]);
+        G(0, 5, 10, 15, m[s[8]], m[s[9]]); G(1, 6, 11, 12, m[s[10]], m[s[11]]);
+        G(2, 7, 8, 13, m[s[12]], m[s[13]]); G(3, 4, 9, 14, m[s[14]], m[s[15]]);
+    }
+    for (int i = 0; i < 8; i++) h[i] ^= v[i] ^ v[i + 8];
+}
+// The state a blake2b of `digest_len` bytes keyed with key[0..key_len) (<= 64 bytes) is in before its first message byte:
+// h = IV ^ parameter block (fanout 1, depth 1, no salt, no personalisation), and with a key the zero-padded key block
+// compressed as a non-final block.  Returns the byte counter: 128 with a key, 0 without.  NOT valid for an empty message
+// under a key: the key block is then itself the final block (callers that can meet that case hash the key block themselves).
+static inline uint32_t b2_keyed_midstate_host(uint64_t h[8], uint32_t digest_len, const uint8_t *key, uint32_t key_len) {
+    static const uint64_t IV[8] = {0x6a09e667f3bcc908ull, 0xbb67ae8584caa73bull, 0x3c6ef372fe94f82bull, 0xa54ff53a5f1d36f1ull,
+                                   0x510e527fade682d1ull, 0x9b05688c2b3e6c1full, 0x1f83d9abfb41bd6bull, 0x5be0cd19137e2179ull};
+    for (int i = 0; i < 8; i++) h[i] = IV[i];
+    h[0] ^= 0x01010000ull ^ ((uint64_t)key_len << 8) ^ (uint64_t)digest_len;
+    if (key_len == 0) return 0;
+    uint8_t block[128];
+    memset(block, 0, sizeof block);
+    memcpy(block, key, key_len);
+    b2_compress_host(h, block, 128, false);
+    return 128;
+}
+
 }  // namespace h2vhost

@@ -85,6 +85,14 @@ H2V_DI void tr_init(Transcript &s) {
     s.t = 0;
     s.buflen = 0;
 }
+// A hash that starts from a state worked out on the host (the keyed blake2b-512 transcript: parameter block and key block
+// are the same for every proof of a plan, h2v_plan.h: tr_h0 / tr_t0)
+H2V_DI void tr_init_state(Transcript &s, const uint64_t *h0, uint32_t t0) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) s.h[i] = h0[i];
+    s.t = t0;
+    s.buflen = 0;
+}
 H2V_DI void tr_put(Transcript &s, uint32_t *sbuf, int lane, uint32_t byte) {
     if (s.buflen == 128) {  // full and more input follows: not the last block
         s.t += 128;
@@ -103,7 +111,10 @@ H2V_DI void tr_put(Transcript &s, uint32_t *sbuf, int lane, uint32_t byte) {
 }
 // digest of everything absorbed so far, leaving the running state untouched (State::finalize on a clone).  The unused
 // tail of the block buffer is zeroed in place (the padding of the last block); the pending bytes stay where they are.
-H2V_DI void tr_digest(const Transcript &s, uint32_t *sbuf, int lane, uint64_t (&out)[4]) {
+// N = 4: the first 32 bytes of the state (a blake2b-256); N = 8: all 64 (a blake2b-512: the width is in the initial state).
+template <int N>
+H2V_DI void tr_digest(const Transcript &s, uint32_t *sbuf, int lane, uint64_t (&out)[N]) {
+    static_assert(N == 4 || N == 8, "32- or 64-byte digest");
     uint64_t h[8];
 #pragma unroll
     for (int i = 0; i < 8; i++) h[i] = s.h[i];
@@ -113,7 +124,7 @@ H2V_DI void tr_digest(const Transcript &s, uint32_t *sbuf, int lane, uint64_t (&
     for (uint32_t d = (bl + 3) >> 2; d < 32; d++) sbuf[d * 64 + lane] = 0;
     b2_compress_lds(h, sbuf + lane, (uint64_t)s.t + bl, true);
 #pragma unroll
-    for (int i = 0; i < 4; i++) out[i] = h[i];
+    for (int i = 0; i < N; i++) out[i] = h[i];
 }
 // blake2b-256 of a 32-byte message; borrows the lane's block buffer (saved and restored around the call)
 H2V_DI void b2_hash32(const uint64_t (&in)[4], uint64_t (&out)[4], uint32_t *sbuf, int lane) {
@@ -180,7 +191,9 @@ H2V_DI void tr_absorb_scalar(Transcript &s, uint32_t *sbuf, int lane, const Fr &
 // of each bundle.  The L lanes share the proof's register file (LDS), sit in the same wave, and a bundle's records are
 // independent, so program order is all the synchronisation there is: LDS serves one wave's accesses in issue order.
 // The transcript operations are on lane 0 by construction (the loader checks), so only that lane's hash state is real.
-template <class RF>
+// TRK = the transcript hash of the plan's key (h2v_plan.h: H2V_TR_*), a compile-time choice: the Cardano instantiation is
+// the code it was before there was a choice (its constants stay immediates), and the launcher picks by plan.tr_kind.
+template <class RF, uint32_t TRK = H2V_TR_CARDANO_BLAKE2B_256>
 H2V_DI void vm_run(const H2vDevPlan &plan, const RF rf, uint32_t *sbuf, const int lane, const uint32_t i, const uint32_t ii,
                    const bool live, const uint32_t L, const uint32_t sub, uint32_t *st_red /* 64 dwords of LDS */,
                    const uint32_t P /* proof slots of the block: lane l serves slot l & (P - 1) */,
@@ -204,7 +217,8 @@ H2V_DI void vm_run(const H2vDevPlan &plan, const RF rf, uint32_t *sbuf, const in
         for (uint32_t o = 64 * sub; o < plan.proof_len; o += 64 * L) warm += proof[o];
     }
     Transcript tr;
-    tr_init(tr);
+    if constexpr (TRK == H2V_TR_BLAKE2B_512) tr_init_state(tr, plan.tr_h0, plan.tr_t0);
+    else tr_init(tr);
     Fr a, b, r;
     // Record fetch: one 8-byte load per lane and bundle (the L lanes of a proof read L consecutive records), issued one
     // bundle ahead so that its latency - which a lone wave cannot hide behind anything else - overlaps the current bundle.
@@ -281,15 +295,27 @@ H2V_DI void vm_run(const H2vDevPlan &plan, const RF rf, uint32_t *sbuf, const in
         case H2V_OP_SQUEEZE: {
             // adjusted_types/mod.rs:44-71: update(0x00); h = finalize; h2 = blake2b256(h);
             // challenge = from_uniform_bytes(h || h2) = LE(h) + LE(h2) * 2^256 mod r   (transcript.ak:85-106)
+            // blake2b-512 (halo2's default blake2b_simd::State): update(0x00); out = the 64-byte digest of a copy of the
+            // state, which goes on with the 0x00 in it; challenge = from_uniform_bytes(out), the same formula on out[0:32] || out[32:64]
             tr_put(tr, sbuf, lane, 0);
-            uint64_t h[4], h2[4];
-            tr_digest(tr, sbuf, lane, h);
-            b2_hash32(h, h2, sbuf, lane);
             Fr lo, hi, k;
+            if constexpr (TRK == H2V_TR_BLAKE2B_512) {
+                uint64_t h[8];
+                tr_digest(tr, sbuf, lane, h);
 #pragma unroll
-            for (int l = 0; l < 4; l++) {
-                lo.v[2 * l] = (uint32_t)h[l]; lo.v[2 * l + 1] = (uint32_t)(h[l] >> 32);
-                hi.v[2 * l] = (uint32_t)h2[l]; hi.v[2 * l + 1] = (uint32_t)(h2[l] >> 32);
+                for (int l = 0; l < 4; l++) {
+                    lo.v[2 * l] = (uint32_t)h[l]; lo.v[2 * l + 1] = (uint32_t)(h[l] >> 32);
+                    hi.v[2 * l] = (uint32_t)h[4 + l]; hi.v[2 * l + 1] = (uint32_t)(h[4 + l] >> 32);
+                }
+            } else {
+                uint64_t h[4], h2[4];
+                tr_digest(tr, sbuf, lane, h);
+                b2_hash32(h, h2, sbuf, lane);
+#pragma unroll
+                for (int l = 0; l < 4; l++) {
+                    lo.v[2 * l] = (uint32_t)h[l]; lo.v[2 * l + 1] = (uint32_t)(h[l] >> 32);
+                    hi.v[2 * l] = (uint32_t)h2[l]; hi.v[2 * l + 1] = (uint32_t)(h2[l] >> 32);
+                }
             }
             fr_to_mont(a, lo);
             fr_const(k, FR_R3);
@@ -391,6 +417,37 @@ k_transcript_combiner_lds(H2vDevPlan plan, uint32_t n, uint32_t P, const uint8_t
     // a dead slot of the last block shadows proof n-1 but must not touch a live slot's registers: it owns slot q anyway
     const RegsLds rf = {P, q};
     vm_run(plan, rf, sbuf, lane, i, ii, live, L, sub, st_red, P, proofs, proof_off, instances, committed, scalars, status, trace);
+}
+// The two kernels above for a key whose transcript hash is the keyed blake2b-512 (same geometry, same arguments)
+extern "C" __global__ void __launch_bounds__(64)
+k_transcript_combiner_b512(H2vDevPlan plan, uint32_t n, uint32_t stride, const uint8_t *__restrict__ proofs,
+                           const uint64_t *__restrict__ proof_off, const uint8_t *__restrict__ instances,
+                           const uint8_t *__restrict__ committed, uint32_t *__restrict__ regs,
+                           uint32_t *__restrict__ scalars, uint32_t *__restrict__ status, uint32_t *__restrict__ trace) {
+    __shared__ uint32_t sbuf[32 * 64];
+    const int lane = threadIdx.x;
+    const uint32_t i = blockIdx.x * 64 + lane;
+    const bool live = i < n;
+    const uint32_t ii = live ? i : n - 1;
+    const RegsGlobal rf = {regs, stride, ii, i};
+    vm_run<RegsGlobal, H2V_TR_BLAKE2B_512>(plan, rf, sbuf, lane, i, ii, live, 1u, 0u, nullptr, 64u, proofs, proof_off, instances, committed, scalars, status, trace);
+}
+extern "C" __global__ void __launch_bounds__(64)
+k_transcript_combiner_lds_b512(H2vDevPlan plan, uint32_t n, uint32_t P, const uint8_t *__restrict__ proofs,
+                               const uint64_t *__restrict__ proof_off, const uint8_t *__restrict__ instances,
+                               const uint8_t *__restrict__ committed, uint32_t *__restrict__ scalars,
+                               uint32_t *__restrict__ status, uint32_t *__restrict__ trace) {
+    __shared__ uint32_t sbuf[32 * 64];
+    __shared__ uint32_t st_red[64];
+    const int lane = threadIdx.x;
+    const uint32_t L = plan.vm_lanes;
+    const uint32_t q = (uint32_t)lane & (P - 1);
+    const uint32_t sub = L > 1 ? ((uint32_t)lane / P) % L : 0u;
+    const uint32_t i = blockIdx.x * P + q;
+    const bool live = (uint32_t)lane < P * L && i < n;
+    const uint32_t ii = i < n ? i : n - 1;
+    const RegsLds rf = {P, q};
+    vm_run<RegsLds, H2V_TR_BLAKE2B_512>(plan, rf, sbuf, lane, i, ii, live, L, sub, st_red, P, proofs, proof_off, instances, committed, scalars, status, trace);
 }
 
 // ============================================================================ K2: G1 decompression
@@ -1665,6 +1722,31 @@ k_probe_blake2b(uint32_t n, uint32_t len, const uint8_t *__restrict__ msgs, uint
     if (i < n) {
 #pragma unroll
         for (int k = 0; k < 4; k++) { out[(size_t)i * 8 + 2 * k] = (uint32_t)h[k]; out[(size_t)i * 8 + 2 * k + 1] = (uint32_t)(h[k] >> 32); }
+    }
+}
+
+// A keyed / unkeyed blake2b of either width through the same path, from a state the host worked out (h0, t0: the parameter
+// block, and the key block behind it when a message follows).  `prefix` (prefix_len bytes, 0 or 128) is hashed in front of
+// every message: the key block itself when the message is empty - it is then the final block, and no mid-state applies.
+struct H2vProbeHash { uint64_t h0[8]; uint32_t t0, prefix_len, digest_words; };
+extern "C" __global__ void __launch_bounds__(64)
+k_probe_blake2b_ex(uint32_t n, uint32_t len, const uint8_t *__restrict__ msgs, H2vProbeHash ph, const uint8_t *__restrict__ prefix,
+                   uint32_t *__restrict__ out) {
+    __shared__ uint32_t sbuf[32 * 64];
+    const int lane = threadIdx.x;
+    const uint32_t i = blockIdx.x * 64 + lane;
+    const uint32_t ii = i < n ? i : n - 1;
+    Transcript tr;
+    tr_init_state(tr, ph.h0, ph.t0);
+    for (uint32_t k = 0; k < ph.prefix_len; k++) tr_put(tr, sbuf, lane, prefix[k]);
+    for (uint32_t k = 0; k < len; k++) tr_put(tr, sbuf, lane, msgs[(size_t)ii * len + k]);
+    uint64_t h[8];
+    tr_digest(tr, sbuf, lane, h);
+    if (i < n) {
+        const uint32_t dw = 2 * ph.digest_words;
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if ((uint32_t)(2 * k) < dw) { out[(size_t)i * dw + 2 * k] = (uint32_t)h[k]; out[(size_t)i * dw + 2 * k + 1] = (uint32_t)(h[k] >> 32); }
     }
 }
 

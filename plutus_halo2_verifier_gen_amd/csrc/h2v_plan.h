@@ -7,6 +7,15 @@
 
 #define H2V_PLAN_MAGIC "H2VPLAN1"
 #define H2V_PLAN_VERSION 4u
+// A plan whose transcript hash is not the Cardano flavour is written as version 5: a library that reads version 4 only
+// refuses it instead of replaying its proofs under the wrong hash.  A plan of kind 0 is still written as version 4 with
+// the three transcript words zero, byte for byte what earlier builds wrote.  The loader takes both.
+#define H2V_PLAN_VERSION_FLAVOURED 5u
+// transcript hash H of CircuitTranscript<H> (H2V_HW_TR_KIND; include/h2v.h: H2V_TRANSCRIPT_*)
+#define H2V_TR_CARDANO_BLAKE2B_256 0u   // CardanoFriendlyBlake2b: unkeyed blake2b-256, squeeze = h || blake2b-256(h)
+#define H2V_TR_BLAKE2B_512 1u           // blake2b_simd::State, 64-byte digest, keyed: squeeze = digest of a copy of the state
+#define H2V_TR_KIND_COUNT 2u
+#define H2V_TR_KEY_MAX 64u
 #define H2V_PLAN_HDR_WORDS 46
 #define H2V_MILLER_LINES 68  // 63 doublings + 5 additions for |x| = 0xd201000000010000
 
@@ -22,8 +31,11 @@ enum {
     H2V_HW_IVC, H2V_HW_N_MAIN_TERMS, H2V_HW_ACC_IDX0 /* .. +7 */,
     // lanes per proof of the transcript + combiner program (the instruction stream is a sequence of bundles of that many
     // records), and an optional second, wider schedule of the same program: lanes (0 = none), registers, records, offset
-    H2V_HW_VM_LANES = H2V_HW_ACC_IDX0 + 8, H2V_HW_VM2_LANES, H2V_HW_VM2_N_REGS, H2V_HW_VM2_N_INSTR, H2V_HW_VM2_OFF_INSTR
+    H2V_HW_VM_LANES = H2V_HW_ACC_IDX0 + 8, H2V_HW_VM2_LANES, H2V_HW_VM2_N_REGS, H2V_HW_VM2_N_INSTR, H2V_HW_VM2_OFF_INSTR,
+    // transcript hash of the key: kind (0 = Cardano), and the blake2b key's byte range in the blob (0, 0 = no key)
+    H2V_HW_TR_KIND, H2V_HW_TR_KEY_OFF, H2V_HW_TR_KEY_LEN
 };
+static_assert(H2V_HW_TR_KIND == 40 && H2V_HW_TR_KEY_LEN < H2V_PLAN_HDR_WORDS, "transcript words are header words 40-42");
 
 // opcodes of the transcript + Fr-combiner program (8-byte records: op, pad, dst, a, b).  The program is a sequence of
 // BUNDLES of `vm_lanes` records: record l of a bundle is executed by lane l of the proof's lanes (NOP = idle).  Records of
@@ -91,6 +103,12 @@ struct H2vDevPlan {
     // optional wide schedule of the program (0 lanes = none); host-side use only (launch_vm swaps it in)
     uint32_t wide_lanes, wide_n_regs, wide_n_instr;
     const H2vInstr *wide_instr;
+    // transcript hash of the key.  tr_kind picks the combiner's instantiation on the host (launch_vm); the Cardano
+    // instantiation reads none of these.  For the keyed blake2b-512 flavour the hash state every proof starts from is
+    // worked out once at plan load (h2v_hostmath.hpp: b2_compress_host): tr_h0 = the parameter block's state after the
+    // key block, tr_t0 = bytes compressed so far (128 with a key, 0 without: then tr_h0 is the plain initial state).
+    uint32_t tr_kind, tr_t0;
+    uint64_t tr_h0[8];
 };
 // per-proof point slots: the proof's G1 elements, the committed instance, then (recursion) the two accumulator points
 #define H2V_SLOTS(plan) ((plan).n_points + (plan).n_ci + 2u * (plan).ivc)

@@ -153,6 +153,8 @@ struct VK {
     struct Inner { std::string name; U256 transcript_repr; std::vector<std::string> fixed_comm, perm_comm; };
     std::vector<Inner> inner;
     std::vector<int> adv_phase, chal_phase;
+    uint32_t tr_kind = H2V_TR_CARDANO_BLAKE2B_256;   // transcript hash of the key (vk.py: transcript_kind) and its blake2b key
+    std::vector<uint8_t> tr_key;
     int chunk_len() const { return degree - 2; }
     int n_chunks() const { return ((int)perm_cols.size() + chunk_len() - 1) / chunk_len(); }
 };
@@ -205,7 +207,7 @@ static VK parse_vk(const char *json, size_t len) {
     static const char *known[] = {"schema_version", "name", "k", "blinding_factors", "cs_degree", "transcript_repr", "num_advice_columns",
                                   "num_fixed_columns", "advice_queries", "fixed_queries", "instance_queries", "gates", "lookups", "trashcans",
                                   "permutation_columns", "fixed_commitments", "permutation_commitments", "s_g2", "n_public_inputs",
-                                  "n_committed_instances", "recursion_vks", "advice_column_phase", "challenge_phase"};
+                                  "n_committed_instances", "recursion_vks", "advice_column_phase", "challenge_phase", "transcript_hash"};
     for (const auto &kv : root.o) {
         bool ok = false;
         for (const char *k : known) ok = ok || kv.first == k;
@@ -294,6 +296,29 @@ static VK parse_vk(const char *json, size_t len) {
             vk.chal_phase.push_back((int)jint(&x, "challenge_phase", 0, 255));
             if (vk.chal_phase.back() > top) throw CompileError("a challenge of a phase beyond the last advice phase is never squeezed (proof.rs:24-29)");
         }
+    }
+    // transcript hash (vk.py: transcript_kind): absent / null = the Cardano flavour.  The default key of blake2b-512 is a
+    // recollection of midnight-proofs 0.8.0 that nothing in the reference tree pins (vk.py: DEFAULT_BLAKE2B_512_KEY).
+    const JVal *th = root.get("transcript_hash");
+    if (th && th->kind != JVal::NUL) {
+        if (th->kind != JVal::OBJ) throw CompileError("transcript_hash: an object {kind, key_hex?}");
+        for (const auto &kv : th->o)
+            if (kv.first != "kind" && kv.first != "key_hex") throw CompileError("transcript_hash: an object {kind, key_hex?}");
+        const JVal *kd = th->get("kind"), *kh = th->get("key_hex");
+        if (!kd || kd->kind != JVal::STR) throw CompileError("transcript_hash: an object {kind, key_hex?}");
+        const bool has_key = kh && kh->kind != JVal::NUL;
+        if (kd->s == "cardano-blake2b-256") {
+            if (has_key && !(kh->kind == JVal::STR && kh->s.empty())) throw CompileError("transcript_hash: cardano-blake2b-256 is unkeyed");
+        } else if (kd->s == "blake2b-512") {
+            vk.tr_kind = H2V_TR_BLAKE2B_512;
+            if (!has_key) {
+                static const char dflt[] = "Domain separator for transcript";
+                vk.tr_key.assign(dflt, dflt + sizeof dflt - 1);
+            } else {
+                if (kh->kind != JVal::STR || (!kh->s.empty() && !hex_to_bytes(kh->s, vk.tr_key))) throw CompileError("transcript_hash: key_hex is not a hex string");
+                if (vk.tr_key.size() > H2V_TR_KEY_MAX) throw CompileError("transcript_hash: the key has " + std::to_string(vk.tr_key.size()) + " bytes; blake2b takes at most 64");
+            }
+        } else throw CompileError("transcript_hash: unknown kind " + kd->s);
     }
     return vk;
 }
@@ -1065,9 +1090,11 @@ static std::vector<uint8_t> compile_plan(const VK &vk) {
     for (const Line &l : lines_sg2) put_line_slots(l);
     section("lines28_g2");
     for (const Line &l : lines_g2) put_line_slots(l);
+    const bool flavoured = vk.tr_kind != H2V_TR_CARDANO_BLAKE2B_256;
+    if (flavoured && !vk.tr_key.empty()) { section("tr_key"); body.insert(body.end(), vk.tr_key.begin(), vk.tr_key.end()); }
     pad16(body);
     const uint32_t hdr_len = 8 + 4 * H2V_PLAN_HDR_WORDS;
-    std::vector<uint32_t> f = {H2V_PLAN_VERSION, proof_len, (uint32_t)vk.n_pi, (uint32_t)n_ci, (uint32_t)narrow.al.n_regs, (uint32_t)narrow.al.instrs.size(),
+    std::vector<uint32_t> f = {flavoured ? H2V_PLAN_VERSION_FLAVOURED : H2V_PLAN_VERSION, proof_len, (uint32_t)vk.n_pi, (uint32_t)n_ci, (uint32_t)narrow.al.n_regs, (uint32_t)narrow.al.instrs.size(),
                                (uint32_t)b.consts.size(), (uint32_t)points.size(), (uint32_t)vk_bases.size(), (uint32_t)terms.size(),
                                (uint32_t)trace_virt.size(), (uint32_t)pi_pt, n_squeezes, stream_len};
     for (const char *k : {"instr", "consts", "points", "vk_bases", "terms", "lines_sg2", "lines_g2", "trace"}) f.push_back(hdr_len + offs[k]);
@@ -1081,6 +1108,11 @@ static std::vector<uint8_t> compile_plan(const VK &vk) {
     if (has_wide) { f.push_back((uint32_t)wide.lanes); f.push_back((uint32_t)wide.al.n_regs); f.push_back((uint32_t)wide.al.instrs.size()); f.push_back(hdr_len + offs["instr_wide"]); }
     else { f.push_back(0); f.push_back(0); f.push_back(0); f.push_back(0); }
     while (f.size() < H2V_PLAN_HDR_WORDS) f.push_back(0);
+    if (flavoured) {   // (a plan of kind 0 keeps the three words zero: version 4, the bytes earlier builds wrote)
+        f[H2V_HW_TR_KIND] = vk.tr_kind;
+        f[H2V_HW_TR_KEY_OFF] = vk.tr_key.empty() ? 0u : hdr_len + offs["tr_key"];
+        f[H2V_HW_TR_KEY_LEN] = (uint32_t)vk.tr_key.size();
+    }
     std::vector<uint8_t> out(H2V_PLAN_MAGIC, H2V_PLAN_MAGIC + 8);
     for (uint32_t w : f) put32(out, w);
     out.insert(out.end(), body.begin(), body.end());

@@ -65,6 +65,11 @@ MAX_TRACE_EXPR = 256
 MILLER_LINES = 68
 PLAN_MAGIC = b"H2VPLAN1"
 PLAN_VERSION = 4
+# a plan whose transcript hash is not the Cardano flavour is written as version 5 (header words 40-42: kind, key offset,
+# key length), so that a library that knows version 4 only refuses it instead of replaying it under the wrong hash
+PLAN_VERSION_FLAVOURED = 5
+HW_TR_KIND, HW_TR_KEY_OFF, HW_TR_KEY_LEN = 40, 41, 42
+TR_CARDANO_BLAKE2B_256, TR_BLAKE2B_512 = 0, 1
 PLAN_HDR_WORDS = 46  # 8 + 4*46 = 192 bytes: keeps every 16-byte-padded section 16-byte aligned
 
 ROT_LAST = "last"  # rotation key of x_last = w^-(bf+1) x
@@ -106,6 +111,9 @@ class Plan:
     # commitment, in order, {commitment: (kind, idx), set: first-seen point-set index, sorted_set: position after the
     # cardinality sort (aiken.rs:580-587), pairs: [(rotation, eval key)...]} - what tests compare with ProofData.hs
     commitment_map: Optional[list] = None
+    # the transcript hash of the key (vk.transcript_kind): 0 = CardanoFriendlyBlake2b, 1 = keyed blake2b-512 and its key
+    transcript_kind: int = 0
+    transcript_key: bytes = b""
 
     def __post_init__(self):
         if self.n_main_terms < 0:
@@ -149,9 +157,12 @@ class Plan:
         # the same line tables as operand slots of the cooperative pairing engine (8 x 64 B per line)
         for name, tab in (("lines28_sg2", self.lines_sg2), ("lines28_g2", self.lines_g2)):
             section(name, b"".join(bls.line_slots(lam, c) for lam, c in tab))
+        flavoured = self.transcript_kind != TR_CARDANO_BLAKE2B_256
+        if flavoured and self.transcript_key:
+            section("tr_key", bytes(self.transcript_key))
         pad8(body)
         hdr_len = 8 + 4 * PLAN_HDR_WORDS
-        fields = [PLAN_VERSION, self.proof_len, self.n_pi, self.n_ci, self.n_regs, len(self.instrs), len(self.consts),
+        fields = [PLAN_VERSION_FLAVOURED if flavoured else PLAN_VERSION, self.proof_len, self.n_pi, self.n_ci, self.n_regs, len(self.instrs), len(self.consts),
                   len(self.points), len(self.vk_bases), len(self.terms), len(self.trace), self.pi_point,
                   self.n_squeezes, self.stream_len]
         sect = [hdr_len + offs[k] for k in ("instr", "consts", "points", "vk_bases", "terms", "lines_sg2", "lines_g2",
@@ -162,6 +173,10 @@ class Plan:
         fields += [self.vm_lanes]
         fields += [self.wide[0], self.wide[1], len(self.wide[2]), hdr_len + offs["instr_wide"]] if self.wide else [0, 0, 0, 0]
         fields += [0] * (PLAN_HDR_WORDS - len(fields))
+        if flavoured:
+            fields[HW_TR_KIND] = self.transcript_kind
+            fields[HW_TR_KEY_OFF] = hdr_len + offs["tr_key"] if self.transcript_key else 0
+            fields[HW_TR_KEY_LEN] = len(self.transcript_key)
         return PLAN_MAGIC + struct.pack("<%dI" % PLAN_HDR_WORDS, *fields) + bytes(body)
 
 
@@ -264,6 +279,8 @@ def compile_plan(vk: VerifyingKey, lanes: Optional[int] = None, legacy_no_trash_
     (extraction_steps/proof.rs:68) - the layout of the reference's only in-tree full proof, transcript.ak:241-382 -
     so that the GPU transcript kernel can be replayed against every challenge of that vector.  Only for keys without
     trashcan arguments; the first three advice evaluations are added to the trace set."""
+    from .vk import transcript_kind
+    tr_kind, tr_key = transcript_kind(vk)
     b = _Builder()
     L = len(vk.lookups)
     Cn = vk.n_perm_chunks
@@ -786,6 +803,7 @@ def compile_plan(vk: VerifyingKey, lanes: Optional[int] = None, legacy_no_trash_
         n_main_terms=n_main_terms, acc_coords=acc_coords, vm_lanes=vm_lanes, wide=wide,
         commitment_map=[{"commitment": ck, "set": set_of[ck], "sorted_set": sort_order.index(set_of[ck]),
                          "pairs": list(cmap[ck])} for ck in commitments],
+        transcript_kind=tr_kind, transcript_key=tr_key,
     )
     return plan
 
@@ -991,6 +1009,11 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
     regs = [0] * n_regs
     scalars = [0] * plan.n_terms
     acc = bytearray()
+    # the keyed blake2b-512 flavour keeps ONE running state: a squeeze is the digest of a copy, and the state goes on
+    flavoured = plan.transcript_kind == TR_BLAKE2B_512
+    if plan.transcript_kind not in (TR_CARDANO_BLAKE2B_256, TR_BLAKE2B_512):
+        raise ValueError("unknown transcript kind %d" % plan.transcript_kind)
+    state = hashlib.blake2b(key=bytes(plan.transcript_key), digest_size=64) if flavoured else None
     status = None
     n_points_read = 0
     if len(proof) < plan.proof_len and stop_before_point is None:
@@ -1024,8 +1047,14 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
             acc += b"\x01" + raw
         elif op == OP_SQUEEZE:
             acc += b"\x00"
-            h = hashlib.blake2b(bytes(acc), digest_size=32).digest()
-            h2 = hashlib.blake2b(h, digest_size=32).digest()
+            if flavoured:
+                state.update(bytes(acc))    # (everything absorbed since the last squeeze)
+                acc = bytearray()
+                out = state.copy().digest()
+                h, h2 = out[:32], out[32:]
+            else:
+                h = hashlib.blake2b(bytes(acc), digest_size=32).digest()
+                h2 = hashlib.blake2b(h, digest_size=32).digest()
             regs[d] = (int.from_bytes(h, "little") + int.from_bytes(h2, "little") * bls.R_2_256) % R
         elif op == OP_CONST:
             regs[d] = plan.consts[a]

@@ -4,8 +4,11 @@
 
   python -m plutus_halo2_verifier_gen_amd.verify_files --vk vk.json [--vk-constants verifier_key.ak] [--kzg-params kzg_params_K]
          --proof serialized_proof.hex [--proof more.hex ...] --public-inputs serialized_public_input.hex
-         [--committed serialized_committed_input.hex]
+         [--committed serialized_committed_input.hex] [--transcript-hash KIND[:KEYHEX]]
 
+--transcript-hash names the hash the proofs were made under (cardano-blake2b-256, or blake2b-512 with an optional blake2b key
+as hex; without KEYHEX the kind's default key, see vk.DEFAULT_BLAKE2B_512_KEY and its caveat) and overrides the key file's
+`transcript_hash` field.  Proofs made under another hash than the one in force are rejected, not refused.
 All proofs share the public-input / committed-instance files when only one of each is given; otherwise give one per
 proof.  Prints one line per proof (`accept` / `reject`) and exits 0 iff every proof verified.  Needs the HIP library
 and a GPU: there is no CPU fallback.
@@ -18,7 +21,7 @@ from typing import List
 
 from . import wire
 from .plan import compile_plan
-from .vk import BUILDERS, VerifyingKey
+from .vk import BUILDERS, VerifyingKey, transcript_kind
 
 
 def load_vk(spec: str) -> VerifyingKey:
@@ -26,6 +29,18 @@ def load_vk(spec: str) -> VerifyingKey:
         return BUILDERS[spec]()[0]
     with open(spec) as f:
         return VerifyingKey.from_json(f.read())
+
+
+def with_transcript_spec(vk: VerifyingKey, spec: str) -> VerifyingKey:
+    """`vk` under the transcript hash named by KIND[:KEYHEX] (the --transcript-hash switch)."""
+    import dataclasses
+    kind, sep, key_hex = spec.partition(":")
+    th = {"kind": kind}
+    if sep:
+        th["key_hex"] = key_hex
+    out = dataclasses.replace(vk, transcript_hash=th)
+    transcript_kind(out)    # VKError for an unknown kind / a bad key
+    return out
 
 
 def assemble(vk: VerifyingKey, proofs: List[bytes], pis: List[List[int]], cis: List):
@@ -65,8 +80,13 @@ def main(argv=None) -> int:
     ap.add_argument("--public-inputs", action="append", required=True)
     ap.add_argument("--committed", action="append", default=[])
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--transcript-hash", metavar="KIND[:KEYHEX]",
+                    help="the transcript hash the proofs were made under: cardano-blake2b-256 or blake2b-512[:blake2b key as hex]; "
+                         "overrides the key file's transcript_hash")
     a = ap.parse_args(argv)
     vk = load_vk(a.vk)
+    if a.transcript_hash:
+        vk = with_transcript_spec(vk, a.transcript_hash)
     if a.vk_constants:
         vk = vk.with_constants(wire.load_vk_constants(a.vk_constants))
     if a.kzg_params:

@@ -70,6 +70,10 @@ class VerifyingKey:
     # schema: a description without them means exactly that).
     advice_column_phase: Optional[List[int]] = None
     challenge_phase: Optional[List[int]] = None
+    # the hash H of CircuitTranscript<H> the key's proofs were made under: None = CardanoFriendlyBlake2b (the optional
+    # field absent means exactly that, and the plan is then the one this build always wrote), or
+    # {"kind": "cardano-blake2b-256"} / {"kind": "blake2b-512", "key_hex": ...} (TRANSCRIPT_KINDS below).
+    transcript_hash: Optional[dict] = None
 
     # ---- derived (instantiation_data.rs:84-103)
     @property
@@ -102,6 +106,9 @@ class VerifyingKey:
         return self.cs_degree - 1
 
     def to_json(self) -> str:
+        """The JSON form of the description.  It is also what callers hand to the CPU oracle (oracle.binding.vk_desc),
+        and the oracle replays the Cardano transcript only - it does not read `transcript_hash`.  Nothing may consult it
+        for a key of another kind (transcript_kind(vk)[0] != 0): its verdicts there are those of the wrong hash."""
         return json.dumps(asdict(self))
 
     # ---- the instantiation-specific part, as the generated constant files carry it (wire.py: VKConstants)
@@ -167,6 +174,58 @@ class VKError(ValueError):
 
 
 SCHEMA_VERSION = 1
+# Transcript hashes (the H of CircuitTranscript<H>), by the number the plan header carries.
+#   cardano-blake2b-256: CardanoFriendlyBlake2b (adjusted_types/mod.rs:30-72): unkeyed blake2b-256, squeeze = h || blake2b-256(h).
+#   blake2b-512: halo2's default blake2b_simd::State: blake2b with a 64-byte digest, keyed; squeeze = the 64-byte digest of
+#                a copy of the state.  The doc comment at adjusted_types/mod.rs:21-29 pins those two differences.
+TRANSCRIPT_KINDS = {"cardano-blake2b-256": 0, "blake2b-512": 1}
+TRANSCRIPT_KEY_MAX = 64   # blake2b takes keys of at most 64 bytes
+# CAVEAT: nothing in the reference tree pins the key string of the default transcript; it is defined in the
+# `midnight-proofs` crate, which is not vendored.  These 31 ASCII bytes are a recollection of midnight-proofs 0.8.0, not
+# a value checked against it.  That is why the key is a field of the description ("key_hex") and not a constant of the
+# kernels: a deployment states the key its prover uses, and a wrong key shows as every proof rejecting.
+DEFAULT_BLAKE2B_512_KEY = b"Domain separator for transcript"
+
+
+def transcript_kind(vk: "VerifyingKey"):
+    """(kind number, key bytes) of the key's transcript hash; (0, b"") for the Cardano flavour.  Validates the field."""
+    th = vk.transcript_hash
+    if th is None:
+        return 0, b""
+    if not isinstance(th, dict) or set(th) - {"kind", "key_hex"} or "kind" not in th:
+        raise VKError("transcript_hash: an object {kind, key_hex?}")
+    if not isinstance(th["kind"], str) or th["kind"] not in TRANSCRIPT_KINDS:
+        raise VKError("transcript_hash: unknown kind %r (known: %s)" % (th["kind"], ", ".join(sorted(TRANSCRIPT_KINDS))))
+    kind = TRANSCRIPT_KINDS[th["kind"]]
+    key_hex = th.get("key_hex")
+    if kind == 0:
+        if key_hex not in (None, ""):
+            raise VKError("transcript_hash: cardano-blake2b-256 is unkeyed")
+        return 0, b""
+    if key_hex is None:
+        return kind, DEFAULT_BLAKE2B_512_KEY
+    try:
+        if not isinstance(key_hex, str) or any(c not in "0123456789abcdefABCDEF" for c in key_hex):
+            raise ValueError
+        key = bytes.fromhex(key_hex)
+    except ValueError:
+        raise VKError("transcript_hash: key_hex is not a hex string")
+    if len(key) > TRANSCRIPT_KEY_MAX:
+        raise VKError("transcript_hash: the key has %d bytes; blake2b takes at most %d" % (len(key), TRANSCRIPT_KEY_MAX))
+    return kind, key
+
+
+def with_transcript_hash(vk: "VerifyingKey", kind: str, key: Optional[bytes] = None) -> "VerifyingKey":
+    """A copy of `vk` whose proofs are made under the named transcript hash (key None = the kind's default key)."""
+    from dataclasses import replace
+    th = {"kind": kind}
+    if key is not None:
+        th["key_hex"] = bytes(key).hex()
+    out = replace(vk, transcript_hash=th)
+    transcript_kind(out)
+    return out
+
+
 _EXPR_ARITY = {"const": 1, "fixed": 1, "advice": 1, "neg": 1, "sum": 2, "prod": 2, "scaled": 2}
 # Expression variants the reference panics on when it transpiles a gate / lookup / trashcan expression
 # (extraction/data/languages/aiken.rs:134-156): they must never reach the plan compiler either.
@@ -206,6 +265,7 @@ def validate(vk: "VerifyingKey", strict_rotations: bool = False) -> None:
             raise VKError("a challenge of a phase beyond the last advice phase is never squeezed (proof.rs:24-29 iterates 0..=max advice phase)")
     if not (0 <= vk.transcript_repr < bls.R):
         raise VKError("transcript_repr is not a canonical scalar")
+    transcript_kind(vk)
     for name, qs, ncols in (("advice", vk.advice_queries, vk.num_advice_columns), ("fixed", vk.fixed_queries, vk.num_fixed_columns),
                             ("instance", vk.instance_queries, vk.n_committed_instances + 1)):
         for col, rot in qs:
