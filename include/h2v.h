@@ -372,6 +372,56 @@ int h2v_check_pairs_rlc(const h2v_plan *plan, uint64_t n, const uint8_t *pairs /
 int h2v_check_pairs_rlc_device(const h2v_plan *plan, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status,
                                h2v_workspace *ws /* not NULL */, void *stream, const h2v_rlc_opts *opts /* or NULL */);
 
+/* ---- mixed-key batches: proofs of SEVERAL plans on one SRS in one call ---------------------------------------------------
+ * The reference verifies a list of (vk, instances, proof) triples in one call and one final check
+ * (midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs), src/circuits/schnorr_circuit.rs:223-231; BASELINE
+ * configs[2] is such a batch).  h2v_verify_mixed(_device) is that call: proof i belongs to plans[plan_of[i]], and accept[] /
+ * status[] come back in the caller's order.  The proofs are sorted by plan on the device (one small copy kernel), every plan's
+ * sub-batch runs the verify pipeline up to the pairing - on a laned workspace the sub-batches of all plans are in flight
+ * together - and ONE tail checks every proof's pair (L, R), which no longer knows its key: one pairing launch over all n proofs,
+ * or, with H2V_MIXED_RLC, ONE pairing for the call (the batch check of h2v_check_pairs_rlc; after a failed check the per-pair
+ * kernels run behind it on the device).
+ *   accept[i] / status[i] are exactly what h2v_verify_batch_device(plans[plan_of[i]], ...) gives for that proof alone - with
+ *   H2V_MIXED_RLC except with probability <= 2^-128 over the seed.  A proof rejected before the pairing keeps its status bits
+ *   and takes no part in anything after.  Recursive (IVC) plans are allowed in both modes: their pair is the folded (el', er').
+ *   ONE SRS PER CALL: every listed plan must carry the same s_g2 (the reference takes ONE `params` too); otherwise H2V_E_ARG,
+ *   and h2v_last_error() names the two plans.  api.verify_mixed / h2v::verify_mixed group a list by SRS and make one call each.
+ *   plan_of is HOST memory in both forms (like n: the host sizes the launches from the per-plan counts).  The other pointers
+ *   of h2v_mixed_batch are host pointers in the host form and device pointers in the device form, as for h2v_batch.
+ *   H2V_E_ARG: plan_of[i] >= n_plans; plans on different devices; a workspace that does not fit EVERY listed plan (take one
+ *   from h2v_workspace_create_multi over the same plans or a superset; ws = NULL in the host form: a temporary one), or that is
+ *   smaller than n; a host batch in flight on ws; stream = NULL on a workspace with deferred joins.  H2V_E_LIMIT: more than
+ *   H2V_MIXED_MAX_PLANS plans; n > 2^22 with H2V_MIXED_RLC.  n = 0 is H2V_OK.  A listed plan without a proof costs nothing.
+ *   DEFERRED JOINS: a mixed call is a join point - it runs the open coalesced groups first, and `stream` waits for the call's
+ *   lanes inside the call (accept[] / status[] are the stream's when the call returns).  Never routed, never coalesced; the
+ *   workspace's failing-group estimate does not move.
+ *   RECORDS: every plan with proofs takes one record as a prepare call does, and the tail takes the LAST record of the call, of
+ *   kind CHECK - or RLC with H2V_MIXED_RLC, so that h2v_workspace_rlc_result(ws, 0, ..) reports the call's batch verdict
+ *   (msm_terms: the pairs of the tail's last chunk - n on a workspace whose chunk holds the call).  On a laned workspace the tail
+ *   is cut into chunks like any check call, and every chunk is its own batch check.  fell_back = 1: that verdict is "failed".
+ *   SEED: h2v_verify_batch_rlc's rules.  ONE seed per call; the coefficient of proof i is drawn from its position in the CALL
+ *   (within its chunk of the tail), never from its position within its key - with repeated coefficients two proofs of
+ *   different keys could cancel each other's error.
+ * WHICH SHAPE IT IS FOR: many keys with few proofs each (a node that validates proofs of many scripts) - there the per-key
+ * route is one chain of lone waves per key.  It does not fold the MSMs of different keys into one bucket MSM: for a batch
+ * dominated by ONE key h2v_verify_batch_rlc on that key stays the faster batch-accept form.  Measurements: DESIGN.md. */
+#define H2V_MIXED_RLC 1u          /* batch-accept: ONE pairing for the call; otherwise one pairing per proof, in ONE launch */
+#define H2V_MIXED_MAX_PLANS 64u   /* more plans in one call: H2V_E_LIMIT */
+typedef struct {
+    uint64_t n;
+    const uint32_t *plan_of;      /* HOST memory in BOTH forms: n entries, plan_of[i] < n_plans */
+    const uint8_t *proofs;        /* as h2v_batch */
+    const uint64_t *proof_off;    /* n + 1 entries */
+    const uint8_t *instances;     /* proof i's 32 * n_public_inputs(plans[plan_of[i]]) bytes, concatenated in proof order */
+    const uint8_t *committed;     /* 48 bytes for every proof whose plan has a committed instance, in proof order; NULL if no listed plan has one */
+} h2v_mixed_batch;
+int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept,
+                     uint32_t *status /* or NULL */, h2v_workspace *ws /* or NULL */, uint32_t flags,
+                     const h2v_rlc_opts *opts /* or NULL */, int *fell_back /* or NULL */);
+int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept,
+                            uint32_t *status, h2v_workspace *ws /* not NULL */, void *stream, uint32_t flags,
+                            const h2v_rlc_opts *opts);
+
 /* ---- parity / debugging surface ----------------------------------------------------------------------------
  * The reference's own intermediate-value trace (cargo feature plutus_debug, src/plutus_gen/emitters/plinth.rs:792-831):
  * theta, beta, gamma, x, y, hEval, vanishing_s, ..., every expression_i, plus el / er.

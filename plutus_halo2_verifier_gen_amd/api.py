@@ -259,3 +259,80 @@ def prepare(vk: VerifyingKey, committed_instances: Sequence[Sequence[Optional[by
     inst = b"".join((int(x) % bls.R).to_bytes(32, "little") for x in pub)
     transcript._consumed = v.plan.proof_len
     return Guard(v, transcript.proof, inst, ci)
+
+
+# ---- mixed-key batches: one key per proof (include/h2v.h: h2v_verify_mixed)
+_MIXED_WS = {}
+
+
+def _mixed_workspace(verifiers, n: int) -> backend.Workspace:
+    """One multi-plan workspace per set of keys (grown when a larger batch comes along)."""
+    key = tuple(id(v) for v in verifiers)
+    ws = _MIXED_WS.get(key)
+    if ws is None or ws.max_batch < n:
+        if ws is not None:
+            ws.close()
+        ws = _MIXED_WS[key] = backend.Workspace.multi([v.device_plan for v in verifiers], max(n, 64))
+    return ws
+
+
+def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
+                 committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof", seed: Optional[bytes] = None,
+                 device: int = 0) -> List[bool]:
+    """accept[i] for n proofs, proof i under the key vks[i] (instances[i]: its public-input scalars; committed[i]: its
+    committed instance as 48 compressed bytes when its circuit has one, else None).  The proofs are grouped by SRS on the
+    host - one h2v_verify_mixed call per distinct s_g2, each over all its keys - and the verdicts come back in the caller's
+    order.  mode="rlc": ONE pairing per call (the reference's batch_verify); same accept vector up to a 2^-128 soundness error
+    over `seed` (from the OS when None)."""
+    return _verify_mixed(vks, proofs, instances, committed, mode, seed, device)[0]
+
+
+def _verify_mixed(vks, proofs, instances, committed, mode, seed, device):
+    """(accept, status) of verify_mixed"""
+    n = len(proofs)
+    if len(vks) != n or len(instances) != n or (committed is not None and len(committed) != n):
+        raise ValueError("one key, one instance list (and one committed instance or None) per proof")
+    if mode not in ("per-proof", "rlc"):
+        raise ValueError("mode is 'per-proof' or 'rlc'")
+    out: List[bool] = [False] * n
+    status: List[int] = [0] * n
+    groups = {}                                   # s_g2 -> positions, in the caller's order
+    for i, vk in enumerate(vks):
+        groups.setdefault(vk.s_g2, []).append(i)
+    for idx in groups.values():
+        verifiers, slot, plan_of = [], {}, []
+        for i in idx:
+            v = verifier_for(vks[i], device)
+            if id(v) not in slot:
+                slot[id(v)] = len(verifiers)
+                verifiers.append(v)
+            plan_of.append(slot[id(v)])
+        off, inst, ci = [0], [], []
+        for i, k in zip(idx, plan_of):
+            pl = verifiers[k].plan
+            if len(instances[i]) != pl.n_pi:
+                raise ValueError("proof %d: expected %d public inputs" % (i, pl.n_pi))
+            off.append(off[-1] + len(proofs[i]))
+            inst.append(b"".join((int(x) % bls.R).to_bytes(32, "little") for x in instances[i]))
+            if pl.n_ci:
+                c = committed[i] if committed is not None else None
+                ci.append(bls.g1_compress(None) if c is None else bytes(c))
+        acc, st, _fb = backend.verify_mixed([v.device_plan for v in verifiers], plan_of, b"".join(bytes(proofs[i]) for i in idx), off,
+                                             b"".join(inst), b"".join(ci) or None, ws=_mixed_workspace(verifiers, len(idx)), mode=mode,
+                                             seed=seed)
+        for i, a, s in zip(idx, acc, st):
+            out[i], status[i] = bool(a), s
+    return out, status
+
+
+def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instances: Sequence[Sequence[int]],
+                 proofs: Sequence[bytes], committed: Optional[Sequence[Optional[bytes]]] = None, device: int = 0) -> None:
+    """midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs) (src/circuits/schnorr_circuit.rs:223-231): one
+    call and one final check for a list of (vk, instances, proof) triples on ONE SRS - the batch-accept mode of verify_mixed.
+    Raises VerifyError unless every proof is accepted (Rust: Err(_)); a key on another SRS than `params` is a ValueError."""
+    for i, vk in enumerate(vks):
+        if bytes(params.s_g2) != bytes.fromhex(vk.s_g2):
+            raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
+    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device)
+    if not all(acc):
+        raise VerifyError(next(s for a, s in zip(acc, status) if not a))

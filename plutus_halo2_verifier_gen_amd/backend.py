@@ -25,6 +25,12 @@ class Batch(C.Structure):
                 ("committed", C.c_void_p)]
 
 
+class MixedBatch(C.Structure):
+    """h2v_mixed_batch: plan_of is HOST memory in both forms of the call"""
+    _fields_ = [("n", C.c_uint64), ("plan_of", C.c_void_p), ("proofs", C.c_void_p), ("proof_off", C.c_void_p),
+                ("instances", C.c_void_p), ("committed", C.c_void_p)]
+
+
 class Timings(C.Structure):
     _fields_ = [("transcript_combiner_ms", C.c_float), ("g1_decompress_ms", C.c_float), ("g1_msm_ms", C.c_float),
                 ("pairing_ms", C.c_float), ("total_ms", C.c_float), ("launches", C.c_uint32),
@@ -62,6 +68,8 @@ RLC_SEED_GIVEN = 1
 RLC_ONE_STREAM = 2
 RLC_FOLD_PAIRS = 4   # recursive plans: combine the pairs (el', er') the fold leaves (include/h2v.h)
 SUBMIT_RLC = 1
+MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
+MIXED_MAX_PLANS = 64   # H2V_MIXED_MAX_PLANS
 
 
 def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False):
@@ -88,6 +96,7 @@ EXPORTS = [
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
     "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device",
     "h2v_plan_transcript", "h2v_probe_blake2b_ex",
+    "h2v_verify_mixed", "h2v_verify_mixed_device",
 ]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
@@ -167,6 +176,10 @@ def lib():
                                           C.POINTER(C.c_int)]
         L.h2v_check_pairs_rlc_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.POINTER(RlcOpts)]
+        L.h2v_verify_mixed.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                       C.POINTER(RlcOpts), C.POINTER(C.c_int)]
+        L.h2v_verify_mixed_device.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint32, C.POINTER(RlcOpts)]
         # h2v_shutdown before the interpreter goes down: the library's pool streams (hardware queues of their own) must not
         # outlive the HIP runtime / a profiler's tool library (include/h2v.h: library lifecycle).  Handles that Python still
         # holds afterwards are empty shells; their __del__ frees the host structs only.
@@ -481,6 +494,57 @@ class Workspace:
             self.close()
         except Exception:
             pass
+
+
+# ---- mixed-key batches (include/h2v.h: h2v_verify_mixed)
+def _mixed_mode(mode: str) -> int:
+    if mode not in ("per-proof", "rlc"):
+        raise ValueError("mode is 'per-proof' or 'rlc'")
+    return MIXED_RLC if mode == "rlc" else 0
+
+
+def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
+                 mode: str = "per-proof", seed: Optional[bytes] = None):
+    """h2v_verify_mixed: n proofs of several plans on ONE SRS in one call; proof i belongs to plans[plan_of[i]], its public
+    inputs (and committed instance, where its plan has one) follow those of the proofs before it.  Returns (accept bytes,
+    status list, fell_back) in the caller's order.  mode="rlc": ONE pairing for the call (fell_back: the batch check failed
+    and the per-pair kernels produced accept[]).  ws: typically Workspace.multi over the same plans; None: a temporary one."""
+    n = len(proof_off) - 1
+    if n < 0 or len(plan_of) != n:
+        raise H2VError("plan_of: one entry per proof")
+    if any(proof_off[i + 1] < proof_off[i] for i in range(n)) or (n > 0 and (proof_off[0] < 0 or proof_off[-1] > len(proofs))):
+        raise H2VError("proof offsets must be non-decreasing and within the proof bytes handed over")
+    arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
+    po = (C.c_uint32 * max(1, n))(*plan_of)
+    off = (C.c_uint64 * (n + 1))(*proof_off)
+    pbuf = C.create_string_buffer(proofs, len(proofs)) if proofs else C.create_string_buffer(1)
+    ibuf = C.create_string_buffer(instances, len(instances)) if instances else None
+    cbuf = C.create_string_buffer(committed, len(committed)) if committed else None
+    b = MixedBatch(n, C.cast(po, C.c_void_p), C.cast(pbuf, C.c_void_p), C.cast(off, C.c_void_p),
+                   C.cast(ibuf, C.c_void_p) if ibuf is not None else None, C.cast(cbuf, C.c_void_p) if cbuf is not None else None)
+    acc = (C.c_uint8 * max(1, n))()
+    st = (C.c_uint32 * max(1, n))()
+    fb = C.c_int(0)
+    flags = _mixed_mode(mode)
+    opts = _rlc_opts(seed)
+    check(lib().h2v_verify_mixed(arr, len(plans), C.byref(b), acc, st, ws.handle if ws else None, flags,
+                                 C.byref(opts) if opts is not None else None, C.byref(fb)))
+    return bytes(acc[:n]), list(st[:n]), bool(fb.value)
+
+
+def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_accept, d_status=None, ws=None, stream=None,
+                        mode: str = "per-proof", seed: Optional[bytes] = None) -> None:
+    """h2v_verify_mixed_device: enqueues on `stream`; plan_of is a host list, every d_* a device pointer.  `stream` has
+    waited for the call's lanes when this returns (a join point, deferred joins or not); ws.rlc_result() has the batch
+    verdict of an mode="rlc" call once the stream is synchronised."""
+    if len(plan_of) != n:
+        raise H2VError("plan_of: one entry per proof")
+    arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
+    po = (C.c_uint32 * max(1, n))(*plan_of)
+    b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
+    opts = _rlc_opts(seed)
+    check(lib().h2v_verify_mixed_device(arr, len(plans), C.byref(b), d_accept, d_status, ws.handle if ws else None, stream,
+                                        _mixed_mode(mode), C.byref(opts) if opts is not None else None))
 
 
 # ---- primitive probes (GPU parity tests)

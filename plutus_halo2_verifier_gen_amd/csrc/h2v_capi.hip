@@ -13,6 +13,8 @@
 #include <vector>
 
 #include "h2v_kernels.hip"
+#include "h2v_mixed.hpp"
+#include "h2v_mixed_dev.hpp"
 #include "h2v_plancc.hpp"
 
 static thread_local std::string g_err;
@@ -112,6 +114,7 @@ struct h2v_plan {
     uint32_t tr_kind = 0, tr_key_len = 0;   // transcript hash of the key (H2V_TRANSCRIPT_*) and its blake2b key
     uint8_t tr_key[H2V_TR_KEY_MAX] = {};
     uint64_t gen = 0;            // process-wide load counter: what caches key on (a freed plan's address may be reused)
+    uint64_t sg2_digest[2] = {}; // of the s_g2 line-table section of the blob: plans of ONE SRS agree in it (h2v_verify_mixed)
     std::vector<uint32_t> trace_slots;
 };
 
@@ -176,6 +179,14 @@ static bool six_line_tables(const uint8_t *l28_sg2, const uint8_t *l28_g2, std::
     const F2 ks[4] = {f2_one(), K[0], K[1], f2_mul(K[0], K[1])};
     for (int q = 0; q < 4; q++) { put_words(out.data() + SIX_NORM_DW + 24 * q, ks[q].a); put_words(out.data() + SIX_NORM_DW + 24 * q + 12, ks[q].b); }
     return true;
+}
+
+// Two 64-bit FNV-1a sums (different offset bases) over a section of the plan blob: equal line tables of s_g2 = one SRS.  The
+// keys of a host are its own configuration, not an adversary's input: the digest guards against a mistake, not an attack.
+static void digest_section(const uint8_t *sec, size_t len, uint64_t out[2]) {
+    uint64_t a = 0xcbf29ce484222325ull, b = 0x84222325cbf29ce4ull;
+    for (size_t k = 0; k < len; k++) { a = (a ^ sec[k]) * 0x100000001b3ull; b = (b ^ (uint8_t)(sec[k] + 0x5a)) * 0x100000001b3ull; }
+    out[0] = a; out[1] = b;
 }
 
 struct h2v_workspace {
@@ -284,6 +295,7 @@ struct h2v_workspace {
     // ---- coalescing of small device-resident calls (coalesce_call): per lane a staging area the proofs of several calls are
     // gathered into; co_open: the lanes whose groups are open, oldest first (one group per plan and mode, at most four)
     struct Coalesce *co[MAXL] = {};
+    struct MixedWs *mixed = nullptr;        // staging of the mixed-key calls (h2v_verify_mixed), created by the first one
     std::vector<uint32_t> co_open;
 };
 using CallRec = h2v_workspace::CallRec;
@@ -581,6 +593,7 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
         }
     }
     d.fix_tab = (const uint32_t *)p->fix_tab; d.n_var = p->n_var; d.n_fix = p->n_fix;
+    digest_section(blob + w[H2V_HW_OFF_LINES28_SG2], 512u * H2V_MILLER_LINES, p->sg2_digest);
     p->n_squeezes = n_sq;
     p->stream_len = w[H2V_HW_STREAM_LEN];
     for (uint32_t k = 0; k < n_trace; k++) p->trace_slots.push_back(rd32(trp + 8 * k));
@@ -630,6 +643,7 @@ extern "C" int h2v_plan_trace_slots(const h2v_plan *p, uint32_t *slot_ids, uint3
 static void rlc_release(struct RlcWs *r);
 static hipError_t make_stream(hipStream_t *s);
 static void co_release(h2v_workspace *w);
+static void mixed_release(h2v_workspace *w);
 static int co_flush(h2v_workspace *w);
 static int lane_streams(uint32_t l, hipStream_t *main_st, hipStream_t *side_st);
 static void ws_release(h2v_workspace *w) {
@@ -645,6 +659,7 @@ static void ws_release(h2v_workspace *w) {
     }
     for (uint32_t l = 0; l < (uint32_t)h2v_workspace::MAXL; l++)
         if (w->lane_st[l]) { (void)hipStreamSynchronize(w->lane_st[l]); }
+    mixed_release(w);
     co_release(w);                        // (an open group is dropped: whoever frees a workspace has joined it or no longer wants the verdicts)
     for (uint32_t l = 0; l < (uint32_t)h2v_workspace::MAXL; l++) {
         if (w->lane[l]) { ws_release(w->lane[l]); delete w->lane[l]; w->lane[l] = nullptr; }
@@ -1483,12 +1498,15 @@ static uint32_t launch_pairing(const H2vDevPlan &d, uint32_t n, const uint32_t *
 extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_timings *tm);
 // fold (H2V_RLC_FOLD_PAIRS, recursive plans): instead of the per-proof pairing, the batch check over the folded pairs (fold_pairs_tail)
 struct FoldPairs { const h2v_plan *p; const uint32_t *seed; uint32_t *fail_ctr; };
+// mixed (h2v_verify_mixed, a per-plan sub-batch): instead of the pairing, k_mixed_pairs writes each proof's pair, `good` and its
+// pre-pairing status at pos[i] - its position in the call - of the call's pool; the record is a prepare call's.
+struct MixedOut { const uint32_t *pos; uint32_t *pool; uint8_t *good; uint32_t *status; };
 static int fold_pairs_tail(const FoldPairs &f, uint32_t n, const uint32_t *er2, const uint32_t *el2, uint8_t *accept, h2v_workspace *w, CallRec &rec, hipStream_t st);
 // pairs_out (prepare calls): instead of the pairing, k_prepare_export writes each proof's pair compress(L) || compress(R)
 // there (n x 24 dwords) and the status words without H2V_ST_PAIRING; accept is not written.
 static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst,
                         const uint8_t *ci, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
-                        h2v_timings *tm, bool want_trace, uint32_t *pairs_out = nullptr, const FoldPairs *fold = nullptr) {
+                        h2v_timings *tm, bool want_trace, uint32_t *pairs_out = nullptr, const FoldPairs *fold = nullptr, const MixedOut *mixed = nullptr) {
     opts_from(w);
     struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
     const uint32_t slots = H2V_SLOTS(d);
@@ -1513,7 +1531,7 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     if (!one_stream)
         if (int rcs = ws_streams(w, !two_stream, true)) return rcs;
     hipStream_t pm = (one_stream || two_stream) ? st : w->pmain, ps = one_stream ? st : w->pside;
-    CallRec &rec = rec_new(w, fold ? h2v_workspace::RLC : pairs_out ? h2v_workspace::PREPARE : h2v_workspace::VERIFY);
+    CallRec &rec = rec_new(w, fold ? h2v_workspace::RLC : (pairs_out || mixed) ? h2v_workspace::PREPARE : h2v_workspace::VERIFY);
     // fold (H2V_RLC_FOLD_PAIRS): the record's events carry run_rlc's layout - [0]/[1] around the decompression, [2]/[3] around the
     // combiner, the rest recorded by pairs_rlc_core - and the pipeline's own markers go to a set of the workspace that nobody reads
     hipEvent_t *ev = rec.ev;
@@ -1598,14 +1616,17 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     HIPCHK(hipEventRecord(ev[5], pm));
     if (fold) {
         if (int rcf = fold_pairs_tail(*fold, n, er_in, el_in, accept, w, rec, pm)) return rcf;
-    } else if (pairs_out)   // (rec.pair stays 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
+    } else if (mixed)
+        hipLaunchKernelGGL(k_mixed_pairs, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, (const uint32_t *)w->status, mixed->pos, mixed->pool,
+                           mixed->good, mixed->status);
+    else if (pairs_out)   // (rec.pair stays 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
         hipLaunchKernelGGL(k_prepare_export, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, pairs_out);
     else
         rec.pair = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
     HIPCHK(hipEventRecord(ev[6], pm));
     HIPCHK(hipEventRecord(w->ev_done, pm));
     HIPCHK(hipStreamWaitEvent(st, w->ev_done, 0));
-    if (int rcd = stage_done(pairs_out ? "k_prepare_export" : "k_pairing")) return rcd;
+    if (int rcd = stage_done(mixed ? "k_mixed_pairs" : pairs_out ? "k_prepare_export" : "k_pairing")) return rcd;
     HIPCHK(hipGetLastError());
     if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     if (tm) {
@@ -3202,6 +3223,376 @@ extern "C" int h2v_check_pairs_rlc(const h2v_plan *p, uint64_t n, const uint8_t 
     if (tmp) h2v_workspace_free(tmp);
     return rc;
 }
+// ---------------------------------------------------------------------------------------------- mixed-key batches
+// h2v_verify_mixed(_device): n proofs of SEVERAL plans on one SRS in one call.  Behind the per-proof MSM a proof of any key is a
+// pair (L, R) with e(L, s_g2) == e(R, G2), and the pairing sees nothing of the key but the SRS; so the call runs
+//   1. the partition (h2v_mixed.hpp, host) and k_mixed_gather: the proofs of each plan side by side in the workspace's staging;
+//   2. per plan, the pipeline up to the pairing (run_pipeline with MixedOut) - on a laned workspace the sub-batches of all plans
+//      go round robin through the lanes and are in flight together;
+//   3. ONE tail over the pool of pairs, which k_mixed_pairs filled in the CALLER's order: the per-proof pairing launch
+//      (run_check's second half), or - H2V_MIXED_RLC - the batch check over pairs (pairs_rlc_core) with the per-pair kernels
+//      behind its skip flags.  On a laned workspace the tail is cut into chunks like any check call, each its own batch check.
+// The tables go up in one copy from a pinned block; a call takes one of four such blocks (and the device copy its kernels read),
+// and a block is reused only when the call that took it last has finished on the device.
+struct MixedWs {
+    static constexpr int SLOTS = 4;
+    struct Slot { uint8_t *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; } slot[SLOTS];
+    uint64_t next = 0;
+    int last = -1;                        // the slot of the most recent call: the next one starts behind its end, whatever its stream
+    uint8_t *proofs = nullptr, *inst = nullptr, *ci = nullptr;       // grouped staging, grown on demand
+    size_t cap_proofs = 0, cap_inst = 0, cap_ci = 0;
+    uint32_t *pool = nullptr, *status = nullptr;                     // the call's pairs (cap x 48 dwords) and status words, caller's order
+    uint8_t *good = nullptr, *ones = nullptr;                        // good_i; 2 x cap bytes of 1: the `valid` of a two-slot view
+    uint8_t *h_in = nullptr, *d_in = nullptr, *d_out = nullptr;      // host form: pinned block, its device copy, accept + status + verdict
+    size_t in_cap = 0, out_cap = 0;
+};
+static void mixed_release(h2v_workspace *w) {
+    MixedWs *m = w->mixed;
+    if (!m) return;
+    for (auto &s : m->slot) {
+        if (s.used && s.done) (void)hipEventSynchronize(s.done);
+        if (s.h) (void)hipHostFree(s.h);
+        if (s.d) (void)hipFree(s.d);
+        if (s.done) (void)hipEventDestroy(s.done);
+    }
+    if (m->h_in) (void)hipHostFree(m->h_in);
+    void *ptrs[] = {m->proofs, m->inst, m->ci, m->pool, m->status, m->good, m->ones, m->d_in, m->d_out};
+    for (void *q : ptrs) if (q) (void)hipFree(q);
+    delete m;
+    w->mixed = nullptr;
+}
+// every earlier mixed call on w has finished on the device (before staging is freed or re-allocated)
+static int mixed_quiesce(MixedWs *m) {
+    for (auto &s : m->slot)
+        if (s.used) { HIPCHK(hipEventSynchronize(s.done)); s.used = false; }
+    return H2V_OK;
+}
+static int mixed_ensure(h2v_workspace *w, const h2vmixed::Partition &pt) {
+    if (!w->mixed) {
+        MixedWs *m = new MixedWs();
+        w->mixed = m;
+        const size_t cap = (size_t)w->cap;
+        bool ok = hipMalloc((void **)&m->pool, cap * 48 * 4) == hipSuccess && hipMalloc((void **)&m->status, cap * 4) == hipSuccess &&
+                  hipMalloc((void **)&m->good, cap) == hipSuccess && hipMalloc((void **)&m->ones, cap * 2) == hipSuccess &&
+                  hipMemset(m->ones, 1, cap * 2) == hipSuccess;
+        for (auto &s : m->slot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
+        if (!ok) { mixed_release(w); return fail(H2V_E_DEVICE, "allocation of the mixed-call buffers failed"); }
+    }
+    MixedWs *m = w->mixed;
+    const size_t need_p = (size_t)pt.proof_cap + 64, need_i = (size_t)pt.inst_total + 64, need_c = (size_t)pt.ci_total * 48 + 64;
+    if (need_p > m->cap_proofs || need_i > m->cap_inst || need_c > m->cap_ci) {
+        if (int rc = mixed_quiesce(m)) return rc;
+        auto grow = [](uint8_t **buf, size_t *cap, size_t need) -> bool {
+            if (need <= *cap) return true;
+            if (*buf) (void)hipFree(*buf);
+            *buf = nullptr; *cap = 0;
+            const size_t c = need + need / 4;
+            if (hipMalloc((void **)buf, c) != hipSuccess) return false;
+            *cap = c;
+            return true;
+        };
+        if (!grow(&m->proofs, &m->cap_proofs, need_p) || !grow(&m->inst, &m->cap_inst, need_i) || !grow(&m->ci, &m->cap_ci, need_c))
+            return fail(H2V_E_DEVICE, "hipMalloc(mixed-call staging) failed");
+    }
+    return H2V_OK;
+}
+// The tail over m pairs of the pool (two-slot affine records, caller's order) on an ordinary workspace or a lane: the per-proof
+// pairing launch of run_check, or the batch check of run_pairs_rlc, both without their decoding - the pipeline made these
+// points itself.  status: the call's words (pre-pairing bits in, H2V_ST_PAIRING folded in by the pairing kernels); good: the
+// call's good_i.  Events as run_check's / run_pairs_rlc's.  fail_ctr as for run_rlc.
+static int run_mixed_tail(const h2v_plan *p, uint32_t m, const uint32_t *pool, const uint8_t *good, const uint8_t *ones, uint32_t *status, uint8_t *accept,
+                          uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], uint32_t *fail_ctr) {
+    opts_from(w);
+    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
+    int rc;
+    if ((rc = pair_view_ensure(w))) return rc;
+    H2vDevPlan v = p->d;
+    v.proof_len = 96; v.n_points = 2; v.n_ci = 0; v.n_pi = 0; v.ivc = 0; v.pi_point = 0; v.points = w->pair_pts;
+    if (!rlc) {
+        CallRec &rec = rec_new(w, h2v_workspace::CHECK);
+        hipEvent_t *ev = rec.ev;
+        for (int q : {0, 1, 2, 3, 4}) HIPCHK(hipEventRecord(ev[q], st));
+        hipLaunchKernelGGL(k_pairs_to_jac, dim3((m + 63) / 64), dim3(64), 0, st, m, pool, w->er, (const uint32_t *)nullptr);
+        HIPCHK(hipEventRecord(ev[5], st));
+        rec.pair = (uint8_t)launch_pairing(v, m, pool, ones, nullptr, w->er, nullptr, status, accept, nullptr, st, w->in_flight_hint);
+        HIPCHK(hipEventRecord(ev[6], st));
+    } else {
+        if ((rc = pair_rlc_ensure(w, false))) return rc;
+        if (!fail_ctr && (rc = rlc_stats_ensure(w))) return rc;
+        RlcWs *r = w->prlc;
+        CallRec &rec = rec_new(w, h2v_workspace::RLC);
+        rec.no_vm = true;
+        for (int q : {0, 1, 2, 3, 10}) HIPCHK(hipEventRecord(rec.ev[q], st));
+        HIPCHK(hipMemcpyAsync(r->good, good, m, hipMemcpyDeviceToDevice, st));
+        if ((rc = pairs_rlc_core(p, m, r, pool, nullptr, nullptr, true, status, accept, w, rec, st, seed, fail_ctr))) return rc;
+        const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (m + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
+        hipLaunchKernelGGL(k_pairs_to_jac, dim3((m + 63) / 64), dim3(64), 0, st, m, pool, w->er, (const uint32_t *)r->flags);
+        hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, v, m, pool, ones, (const uint8_t *)nullptr, w->er, (const uint32_t *)nullptr,
+                           status, accept, (uint32_t *)nullptr, (const uint32_t *)r->flags);
+    }
+    HIPCHK(hipGetLastError());
+    if (status_out) HIPCHK(hipMemcpyAsync(status_out, status, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
+    return H2V_OK;
+}
+// host_off: the grouped proof offsets when the caller's proof_off is known on the host (the host form), else NULL
+struct MixedIn { const uint8_t *proofs; const uint64_t *proof_off; const uint8_t *inst, *ci; };
+static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const MixedIn &in, uint8_t *accept,
+                     uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8]) {
+    const uint32_t n = pt.n;
+    int rc;
+    if (w->n_lanes && (rc = co_flush(w))) return rc;       // (calls start in submission order: the open groups of coalesced calls first)
+    if ((rc = mixed_ensure(w, pt))) return rc;
+    if (rlc && (rc = rlc_stats_ensure(w))) return rc;
+    MixedWs *m = w->mixed;
+    // ---- the tables: one pinned block, one copy
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_off = 0, o_isrc = o_off + up16(((size_t)n + 1) * 8), o_idst = o_isrc + up16((size_t)n * 8), o_perm = o_idst + up16((size_t)n * 8),
+                 o_cap = o_perm + up16((size_t)n * 4), o_ilen = o_cap + up16((size_t)n * 4), o_csrc = o_ilen + up16((size_t)n * 4),
+                 o_cdst = o_csrc + up16((size_t)n * 4), need = o_cdst + up16((size_t)n * 4);
+    const int si = (int)(m->next++ % MixedWs::SLOTS);
+    MixedWs::Slot &sl = m->slot[si];
+    if (sl.used) { HIPCHK(hipEventSynchronize(sl.done)); sl.used = false; }      // (the call that took this block last: its copy and its kernels are done)
+    if (need > sl.cap) {
+        if (sl.h) (void)hipHostFree(sl.h);
+        if (sl.d) (void)hipFree(sl.d);
+        sl.h = sl.d = nullptr; sl.cap = 0;
+        const size_t cap = need + need / 4;
+        if (hipHostMalloc((void **)&sl.h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&sl.d, cap) != hipSuccess)
+            return fail(H2V_E_DEVICE, "allocation of the mixed-call tables failed");
+        sl.cap = cap;
+    }
+    if (host_off) memcpy(sl.h + o_off, host_off, ((size_t)n + 1) * 8);
+    memcpy(sl.h + o_isrc, pt.inst_src.data(), (size_t)n * 8); memcpy(sl.h + o_idst, pt.inst_dst.data(), (size_t)n * 8);
+    memcpy(sl.h + o_perm, pt.perm.data(), (size_t)n * 4); memcpy(sl.h + o_cap, pt.len_cap.data(), (size_t)n * 4);
+    memcpy(sl.h + o_ilen, pt.inst_len.data(), (size_t)n * 4); memcpy(sl.h + o_csrc, pt.ci_src.data(), (size_t)n * 4);
+    memcpy(sl.h + o_cdst, pt.ci_dst.data(), (size_t)n * 4);
+    if (m->last >= 0 && m->last != si && m->slot[m->last].used) HIPCHK(hipStreamWaitEvent(st, m->slot[m->last].done, 0));   // (the staging is the last call's until then)
+    HIPCHK(hipMemcpyAsync(sl.d, sl.h, need, hipMemcpyHostToDevice, st));
+    sl.used = true; m->last = si;
+    // from here on the block is in use: every return records its end on `st` (after an error: drained first)
+    auto finish = [&](int code) -> int {
+        if (code) code = drain_after_error(w, code);
+        if (hipEventRecord(sl.done, st) != hipSuccess && !code) code = fail(H2V_E_DEVICE, "event record failed");
+        return code;
+    };
+    uint64_t *d_off = (uint64_t *)(sl.d + o_off);
+    const uint32_t *d_perm = (const uint32_t *)(sl.d + o_perm);
+    const H2vMixedTab tab = {n, (const uint64_t *)(sl.d + o_isrc), (const uint64_t *)(sl.d + o_idst), d_perm, (const uint32_t *)(sl.d + o_cap),
+                             (const uint32_t *)(sl.d + o_ilen), (const uint32_t *)(sl.d + o_csrc), (const uint32_t *)(sl.d + o_cdst)};
+    if (!host_off) hipLaunchKernelGGL(k_mixed_offsets, dim3(1), dim3(256), 0, st, in.proof_off, tab, d_off);
+    hipLaunchKernelGGL(k_mixed_gather, dim3((n + 3) / 4), dim3(256), 0, st, tab, in.proofs, in.proof_off, in.inst, in.ci, m->proofs, (const uint64_t *)d_off, m->inst, m->ci);
+    if (hipGetLastError() != hipSuccess) return finish(fail(H2V_E_DEVICE, "launch of the gather kernels failed"));
+    const h2v_plan *p0 = nullptr;          // any plan of the call: the tail reads nothing of it but the SRS's line tables
+    uint32_t used_plans = 0;
+    for (uint32_t k = 0; k < pt.n_plans; k++) if (pt.count[k]) { if (!p0) p0 = plans[k]; used_plans++; }
+    auto sub_in = [&](uint32_t k, uint32_t lo, const uint8_t **inst_c, const uint8_t **ci_c) {
+        const H2vDevPlan &d = plans[k]->d;
+        *inst_c = d.n_pi ? m->inst + pt.inst_base[k] + (size_t)lo * d.n_pi * 32 : nullptr;
+        *ci_c = d.n_ci ? m->ci + ((size_t)pt.ci_base[k] + lo) * 48 : nullptr;
+    };
+    if (!w->n_lanes) {
+        // an ordinary workspace: the sub-batches one after the other on `st`, then the tail
+        for (uint32_t k = 0; k < pt.n_plans; k++) {
+            if (!pt.count[k]) continue;
+            const uint8_t *inst_c, *ci_c;
+            sub_in(k, 0, &inst_c, &ci_c);
+            const MixedOut mo = {d_perm + pt.base[k], m->pool, m->good, m->status};
+            if ((rc = run_pipeline(plans[k]->d, pt.count[k], m->proofs, d_off + pt.base[k], inst_c, ci_c, nullptr, nullptr, w, st, nullptr, false, nullptr, nullptr, &mo)))
+                return finish(rc);
+        }
+        return finish(run_mixed_tail(p0, n, m->pool, m->good, m->ones, m->status, accept, status_out, w, st, rlc, seed, nullptr));
+    }
+    // ---- laned: every plan's sub-batch in chunks through the lanes, nothing joined in between
+    uint32_t total_chunks = 0;
+    for (uint32_t k = 0; k < pt.n_plans; k++) total_chunks += (pt.count[k] + w->chunk - 1) / w->chunk;
+    const uint32_t call_hint = w->hint_given ? w->in_flight_hint : (w->defer_joins || total_chunks > w->n_lanes) ? w->n_lanes : total_chunks;
+    uint32_t *fail_word = w->rec_fail ? w->rec_fail + (w->calls + used_plans) % h2v_workspace::RING : nullptr;   // the tail's record: the call's last
+    if (rlc && hipMemsetAsync(fail_word, 0, 4, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "memset failed"));
+    if (hipEventRecord(w->ev_fork, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
+    bool used_lane[h2v_workspace::MAXL] = {};
+    auto lane_for = [&](uint32_t L, uint32_t *l_out) -> int {
+        const uint32_t l = (uint32_t)(w->next_lane++ % L);
+        if (int rce = ensure_lane(w, l)) return rce;
+        HIPCHK(hipStreamWaitEvent(w->lane_st[l], w->ev_fork, 0));
+        *l_out = l;
+        return H2V_OK;
+    };
+    for (uint32_t k = 0; k < pt.n_plans; k++) {
+        const uint32_t cnt = pt.count[k];
+        if (!cnt) continue;                                  // (a listed plan without a proof costs nothing)
+        const H2vDevPlan &d = plans[k]->d;
+        int stream_mode = 1;
+        const uint32_t L = laned_depth(w, cnt, false, &stream_mode), nch = (cnt + w->chunk - 1) / w->chunk;
+        CallRec &rec = rec_new(w, h2v_workspace::PREPARE);
+        rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = nch;
+        for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;
+        for (uint32_t c = 0; c < nch; c++) {
+            uint32_t l;
+            if ((rc = lane_for(L, &l))) return finish(rc);
+            h2v_workspace *lw = w->lane[l];
+            const uint32_t lo = c * w->chunk, mm = (cnt - lo) < w->chunk ? (cnt - lo) : w->chunk;
+            const uint8_t *inst_c, *ci_c;
+            sub_in(k, lo, &inst_c, &ci_c);
+            const MixedOut mo = {d_perm + pt.base[k] + lo, m->pool, m->good, m->status};
+            lw->one_stream_mode = stream_mode;
+            lw->in_flight_hint = call_hint;
+            if ((rc = run_pipeline(d, mm, m->proofs, d_off + pt.base[k] + lo, inst_c, ci_c, nullptr, nullptr, lw, w->lane_st[l], nullptr, false, nullptr, nullptr, &mo)))
+                return finish(rc);
+            if (hipEventRecord(w->lane_ev[l], w->lane_st[l]) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
+            w->lane_busy[l] = true; used_lane[l] = true;
+        }
+    }
+    // ---- the tail: chunks of the pool in the caller's order, each behind EVERY sub-batch (any of them may hold any position)
+    {
+        const uint32_t L = laned_depth(w, n, rlc, nullptr), nch = (n + w->chunk - 1) / w->chunk;
+        CallRec &rec = rec_new(w, rlc ? h2v_workspace::RLC : h2v_workspace::CHECK);
+        rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = nch;
+        for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;
+        for (uint32_t c = 0; c < nch; c++) {
+            uint32_t l;
+            if ((rc = lane_for(L, &l))) return finish(rc);
+            h2v_workspace *lw = w->lane[l];
+            hipStream_t ls = w->lane_st[l];
+            for (uint32_t u = 0; u < w->n_lanes; u++)
+                if (used_lane[u] && u != l && hipStreamWaitEvent(ls, w->lane_ev[u], 0) != hipSuccess) return finish(fail(H2V_E_DEVICE, "stream wait failed"));
+            const uint32_t lo = c * w->chunk, mm = (n - lo) < w->chunk ? (n - lo) : w->chunk;
+            uint32_t sd[8];
+            for (int q = 0; q < 8; q++) sd[q] = seed ? seed[q] : 0;
+            sd[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
+            lw->in_flight_hint = w->hint_given ? w->in_flight_hint : (w->defer_joins ? w->n_lanes : (nch < L ? nch : L));
+            lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
+            if ((rc = run_mixed_tail(p0, mm, m->pool + (size_t)lo * 48, m->good + lo, m->ones, m->status + lo, accept + lo, status_out ? status_out + lo : nullptr, lw, ls,
+                                     rlc, sd, fail_word)))
+                return finish(rc);
+            if (hipEventRecord(w->lane_ev[l], ls) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
+            w->lane_busy[l] = true; used_lane[l] = true;
+        }
+    }
+    // a mixed call is a join point: its caller-stream wait happens here, deferred joins or not
+    return finish(lanes_join(w, st));
+}
+// argument checks shared by the two forms; on success *pt is the partition and *n_used the number of listed plans with proofs
+static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, const uint8_t *accept, uint32_t flags, h2vmixed::Partition *pt) {
+    if (!plans || !b || !accept) return fail(H2V_E_ARG, "null argument");
+    if (n_plans > H2V_MIXED_MAX_PLANS) return fail(H2V_E_LIMIT, "at most " + std::to_string(H2V_MIXED_MAX_PLANS) + " plans in one mixed call (" + std::to_string(n_plans) + " listed)");
+    if (flags & ~H2V_MIXED_RLC) return fail(H2V_E_ARG, "unknown flag");
+    if (b->n == 0) return H2V_OK;
+    if (n_plans == 0) return fail(H2V_E_ARG, "no plan listed");
+    if ((flags & H2V_MIXED_RLC) && b->n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 proofs");
+    if (!b->plan_of || !b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null plan_of / proofs / offsets");
+    std::vector<h2vmixed::PlanShape> shapes(n_plans);
+    for (uint32_t k = 0; k < n_plans; k++) {
+        if (!plans[k]) return fail(H2V_E_ARG, "null plan (plans[" + std::to_string(k) + "])");
+        ALIVE(plans[k]);
+        if (plans[k]->device != plans[0]->device) return fail(H2V_E_ARG, "plans[" + std::to_string(k) + "] lives on another device than plans[0]: one device per call");
+        if (memcmp(plans[k]->sg2_digest, plans[0]->sg2_digest, sizeof plans[0]->sg2_digest))
+            return fail(H2V_E_ARG, "plans[0] and plans[" + std::to_string(k) + "] are on different SRS (their s_g2 differ): one SRS per mixed call");
+        shapes[k] = {plans[k]->d.proof_len, plans[k]->d.n_pi, plans[k]->d.n_ci};
+    }
+    std::string err;
+    if (!h2vmixed::partition(shapes.data(), n_plans, b->plan_of, b->n, *pt, &err)) return fail(H2V_E_ARG, err);
+    if (pt->inst_total && !b->instances) return fail(H2V_E_ARG, "a plan of the call has public inputs but instances == NULL");
+    if (pt->ci_total && !b->committed) return fail(H2V_E_ARG, "a plan of the call has a committed instance but committed == NULL");
+    return H2V_OK;
+}
+static int mixed_ws_check(const h2v_plan *const *plans, uint32_t n_plans, uint64_t n, const h2v_workspace *ws) {
+    for (uint32_t k = 0; k < n_plans; k++)
+        if (int rc = ws_fits(ws, plans[k], n, false)) return fail(rc, "plans[" + std::to_string(k) + "]: " + g_err);
+    if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
+    return H2V_OK;
+}
+extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
+                                       h2v_workspace *ws, void *stream, uint32_t flags, const h2v_rlc_opts *opts) {
+    h2vmixed::Partition pt;
+    int rc = mixed_args(plans, n_plans, b, accept, flags, &pt);
+    if (rc || b->n == 0) return rc;
+    if (!ws) return fail(H2V_E_ARG, "the device form needs a workspace (h2v_workspace_create_multi over the listed plans)");
+    ALIVE(ws);
+    HIPCHK(hipSetDevice(plans[0]->device));
+    if ((rc = mixed_ws_check(plans, n_plans, b->n, ws))) return rc;
+    if ((rc = null_stream_check(ws, stream))) return rc;
+    const bool rlc = (flags & H2V_MIXED_RLC) != 0;
+    uint32_t seed[8] = {};
+    if (rlc && (rc = rlc_seed(opts, seed))) return rc;
+    const MixedIn in = {b->proofs, b->proof_off, b->instances, b->committed};
+    return run_mixed(plans, pt, nullptr, in, accept, status, ws, (hipStream_t)stream, rlc, seed);
+}
+// Host-buffer form: offsets | instances | committed | proofs go up in one pinned block on the workspace's own stream, the call
+// runs there behind it, and accept[] / status[] / the batch verdict come back before the function returns.
+extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
+                                h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back) {
+    if (fell_back) *fell_back = 0;
+    h2vmixed::Partition pt;
+    int rc = mixed_args(plans, n_plans, b, accept, flags, &pt);
+    if (rc || b->n == 0) return rc;
+    ALIVE(ws);
+    HIPCHK(hipSetDevice(plans[0]->device));
+    const uint64_t n = b->n;
+    for (uint64_t i = 0; i < n; i++)
+        if (b->proof_off[i + 1] < b->proof_off[i]) return fail(H2V_E_ARG, "proof offsets must be non-decreasing");
+    h2v_workspace *tmp = nullptr;
+    if (!ws) {    // a temporary workspace over the listed plans: lanes of at most the call's size, created as they are used
+        if ((rc = h2v_workspace_create_multi(plans, n_plans, n, 0, n < 4096 ? (uint32_t)n : 4096u, &tmp))) return rc;
+        ws = tmp;
+    }
+    const bool rlc = (flags & H2V_MIXED_RLC) != 0;
+    uint32_t seed[8] = {};
+    rc = mixed_ws_check(plans, n_plans, n, ws);
+    if (rc == H2V_OK && rlc) rc = rlc_seed(opts, seed);
+    if (rc == H2V_OK) rc = host_stream(ws);
+    if (rc == H2V_OK) rc = mixed_ensure(ws, pt);
+    if (rc == H2V_OK) {
+        MixedWs *m = ws->mixed;
+        auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        const uint64_t total = b->proof_off[n] - b->proof_off[0];
+        const size_t o_inst = up16((n + 1) * 8), o_ci = o_inst + up16(pt.inst_total), o_proofs = o_ci + up16((size_t)pt.ci_total * 48), need = o_proofs + up16(total + 64);
+        const size_t out_need = up16(n) + (size_t)n * 4 + 16;
+        if (need > m->in_cap || out_need > m->out_cap) {
+            rc = mixed_quiesce(m);
+            if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
+            if (rc == H2V_OK && need > m->in_cap) {
+                if (m->h_in) (void)hipHostFree(m->h_in);
+                if (m->d_in) (void)hipFree(m->d_in);
+                m->h_in = m->d_in = nullptr; m->in_cap = 0;
+                const size_t cap = need + need / 4;
+                if (hipHostMalloc((void **)&m->h_in, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&m->d_in, cap) != hipSuccess) rc = fail(H2V_E_DEVICE, "staging allocation failed");
+                else m->in_cap = cap;
+            }
+            if (rc == H2V_OK && out_need > m->out_cap) {
+                if (m->d_out) (void)hipFree(m->d_out);
+                m->d_out = nullptr; m->out_cap = 0;
+                const size_t cap = out_need + out_need / 4;
+                if (hipMalloc((void **)&m->d_out, cap) != hipSuccess) rc = fail(H2V_E_DEVICE, "staging allocation failed");
+                else m->out_cap = cap;
+            }
+        }
+        if (rc == H2V_OK) {
+            uint64_t *h_off = (uint64_t *)m->h_in;
+            for (uint64_t i = 0; i <= n; i++) h_off[i] = b->proof_off[i] - b->proof_off[0];
+            if (pt.inst_total) memcpy(m->h_in + o_inst, b->instances, pt.inst_total);
+            if (pt.ci_total) memcpy(m->h_in + o_ci, b->committed, (size_t)pt.ci_total * 48);
+            memcpy(m->h_in + o_proofs, b->proofs + b->proof_off[0], total);
+            memset(m->h_in + o_proofs + total, 0, 64);
+            std::vector<uint64_t> grouped(n + 1);
+            h2vmixed::group_offsets(pt, h_off, grouped.data());
+            uint8_t *d_accept = m->d_out;
+            uint32_t *d_status = (uint32_t *)(m->d_out + up16(n));
+            uint32_t failed = 0;
+            if (hipMemcpyAsync(m->d_in, m->h_in, need, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the batch failed");
+            const MixedIn in = {m->d_in + o_proofs, (const uint64_t *)m->d_in, m->d_in + o_inst, m->d_in + o_ci};
+            if (rc == H2V_OK) rc = run_mixed(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed);
+            if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
+            if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
+            if (rc == H2V_OK && rlc && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
+            if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "mixed-call kernels failed");
+            if (rc) rc = drain_after_error(ws, rc);
+            else if (fell_back) *fell_back = failed ? 1 : 0;
+        }
+    }
+    if (tmp) h2v_workspace_free(tmp);
+    return rc;
+}
+
 // After the stream of an RLC call has been synchronised: did the batch check pass (1) or did the per-proof kernels run (0)?
 // kernel times of a past call (calls_back = 0: the most recent).
 static int rec_rlc_timings(const CallRec &r, h2v_rlc_timings *tm);

@@ -349,6 +349,18 @@ class Trapdoor:
     rec_dlogs: List[int] = field(default_factory=list)
 
 
+def on_srs(vk: "VerifyingKey", td: "Trapdoor", s: int):
+    """(vk', td'): this key and its trapdoor on the SRS with secret `s` (s_g2 = s G2).  Nothing else of a key depends on the
+    SRS here: the commitments are known multiples of G1 and the transcript representation is the key's own field.  Proofs
+    forged with td' verify under vk' and not under vk; keys moved to one `s` can share a mixed batch (h2v_verify_mixed).
+    Synthetic workloads only, like Trapdoor itself."""
+    from dataclasses import replace
+    s %= bls.R
+    if s == 0:
+        raise ValueError("the SRS secret must not be 0 mod r")
+    return replace(vk, s_g2=bls.g2_compress(bls.g2_mul(bls.G2_GEN, s)).hex()), replace(td, s=s)
+
+
 # ----------------------------------------------------------------------------- expression helpers
 def const(c):
     return ("const", c % bls.R)

@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""The mixed-key call (h2v_verify_mixed_device) against today's route for the same proofs, in ONE process, alternating:
+  (a) new:      one call per step on a multi-plan workspace;
+  (b) baseline: the same workspace kind with deferred joins, one per-key call per key and step on one caller stream, joined
+                at the end of the run (the form tests/test_gpu_parity.py::test_mixed_batch_of_two_plans_in_flight_on_one_device
+                drives: the parent's behaviour).
+Both modes (per proof, batch-accept), for two shapes on one SRS (vk.on_srs):
+  two      lookup_table x 2048 + atms_with_lookups x 2048 (BASELINE configs[2])
+  sixteen  16 keys x 64 proofs: simple_mul, lookup_table, trashcan_mix, atms_with_lookups under four seeds each
+All proofs accept (the batch-accept mode is measured where it is meant to be used); before timing, both routes must accept
+everything.  Every run is `--steps` steps between two device synchronisations; runs alternate new / baseline, `--runs` each.
+A gain is claimed only when the slowest new run beats the fastest baseline run.  --cache DIR keeps the forged batches (forging
+is CPU work).  Writes one JSON line per (shape, mode) and, with --out, the whole set.
+usage: bench_mixed.py [--shapes two,sixteen] [--runs 5] [--steps 20] [--cache DIR] [--out profiles/mixed_keys.json]"""
+import argparse
+import json
+import os
+import pickle
+import random
+import sys
+import time
+
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, ROOT)
+
+COMMON_S = 0x6d697865645f6b6579735f6f6e655f535253
+SHAPES = {
+    "two": [("lookup_table", None, 2048), ("atms_with_lookups", None, 2048)],
+    "sixteen": [(name, 0x4d580000 + 16 * k + q, 64) for k, name in enumerate(("simple_mul", "lookup_table", "trashcan_mix", "atms_with_lookups"))
+                for q in range(4)],
+}
+
+
+def forged(shape, cache):
+    """[(vk, plan, batch)] of the shape, every key on the common SRS"""
+    from plutus_halo2_verifier_gen_amd import plan as PL, synth, vk as V
+    path = os.path.join(cache, "bench_mixed_%s.pkl" % shape) if cache else None
+    if path and os.path.exists(path):
+        with open(path, "rb") as f:
+            return pickle.load(f)
+    out = []
+    for k, (name, seed, cnt) in enumerate(SHAPES[shape]):
+        vk, td = V.on_srs(*(V.BUILDERS[name]() if seed is None else V.BUILDERS[name](seed)), COMMON_S)
+        pl = PL.compile_plan(vk)
+        out.append((vk, pl, synth.forge_batch(vk, td, cnt, seed=100 + k, plan=pl, workers=16)))
+    if path:
+        os.makedirs(cache, exist_ok=True)
+        with open(path, "wb") as f:
+            pickle.dump(out, f)
+    return out
+
+
+def run_shape(shape, runs, steps, cache):
+    import torch
+    from plutus_halo2_verifier_gen_amd import backend
+    keys = forged(shape, cache)
+    dev = torch.device("cuda", 0)
+    plans = [backend.DevicePlan(pl.to_bytes(), 0) for _vk, pl, _b in keys]
+    t = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) if b else None
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    # per key: device-resident batch; mixed: the same proofs interleaved by a seeded shuffle
+    per_key = []
+    for _vk, _pl, b in keys:
+        per_key.append((b.n, t(b.proofs), torch.tensor(b.proof_off, dtype=torch.int64, device=dev), t(b.instances), t(b.committed),
+                        torch.zeros(b.n, dtype=torch.uint8, device=dev), torch.zeros(b.n, dtype=torch.int32, device=dev)))
+    order = [(k, j) for k, (_vk, _pl, b) in enumerate(keys) for j in range(b.n)]
+    random.Random(5).shuffle(order)
+    proofs, inst, ci, off = [], [], [], [0]
+    for k, j in order:
+        vk, _pl, b = keys[k]
+        proofs.append(b.proof(j))
+        off.append(off[-1] + len(proofs[-1]))
+        inst.append(b.instances[32 * vk.n_public_inputs * j:32 * vk.n_public_inputs * (j + 1)])
+        if b.committed is not None:
+            ci.append(b.ci(j))
+    n = len(order)
+    plan_of = [k for k, _ in order]
+    m_in = (t(b"".join(proofs)), torch.tensor(off, dtype=torch.int64, device=dev), t(b"".join(inst)), t(b"".join(ci)))
+    m_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
+    m_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    caller = torch.cuda.Stream(device=dev)
+    cs = caller.cuda_stream
+    ws_new = backend.Workspace.multi(plans, n)
+    ws_old = backend.Workspace.multi(plans, n)
+    ws_old.defer_joins(True)
+    seed = bytes(range(32))
+    results = []
+    for mode in ("per-proof", "rlc"):
+        def new_step():
+            backend.verify_mixed_device(plans, plan_of, n, *[ptr(x) for x in m_in], m_acc.data_ptr(), m_st.data_ptr(), ws=ws_new, stream=cs,
+                                        mode=mode, seed=seed if mode == "rlc" else None)
+
+        def old_step():
+            for dp, (cnt, p, o, i, c, acc, st) in zip(plans, per_key):
+                if mode == "rlc":
+                    dp.verify_batch_rlc_device(cnt, ptr(p), ptr(o), ptr(i), ptr(c), acc.data_ptr(), st.data_ptr(), ws=ws_old, stream=cs, seed=seed)
+                else:
+                    dp.verify_batch_device(cnt, ptr(p), ptr(o), ptr(i), ptr(c), acc.data_ptr(), st.data_ptr(), ws=ws_old, stream=cs)
+
+        def run(step, ws, k_steps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(k_steps):
+                step()
+            ws.join(cs)
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / k_steps
+
+        for step, ws in ((new_step, ws_new), (old_step, ws_old)):      # warm-up: first uses allocate
+            run(step, ws, 3)
+        assert m_acc.cpu().tolist() == [1] * n, "the mixed call rejects a forged proof"
+        assert all(x[5].cpu().tolist() == [1] * x[0] for x in per_key), "a per-key call rejects a forged proof"
+        new_ms, old_ms = [], []
+        for _ in range(runs):
+            new_ms.append(run(new_step, ws_new, steps))
+            old_ms.append(run(old_step, ws_old, steps))
+        med = lambda v: sorted(v)[len(v) // 2]
+        r = {"shape": shape, "keys": len(keys), "proofs": n, "mode": mode, "steps_per_run": steps,
+             "new_ms_per_step": [round(x, 4) for x in new_ms], "baseline_ms_per_step": [round(x, 4) for x in old_ms],
+             "new_median_ms": round(med(new_ms), 4), "baseline_median_ms": round(med(old_ms), 4),
+             "gain_by_the_rule": max(new_ms) < min(old_ms), "loss_by_the_rule": min(new_ms) > max(old_ms)}
+        print(json.dumps(r), flush=True)
+        results.append(r)
+    for w in (ws_new, ws_old):
+        w.close()
+    return results
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="two,sixteen")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--cache", default=None)
+    ap.add_argument("--forge-only", action="store_true", help="forge (and cache) the batches, then stop: no GPU needed")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.runs < 5 and not args.forge_only:
+        ap.error("at least five runs of each route")
+    if args.forge_only:
+        for shape in args.shapes.split(","):
+            forged(shape, args.cache)
+        return
+    import torch
+    results = []
+    for shape in args.shapes.split(","):
+        results += run_shape(shape, args.runs, args.steps, args.cache)
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/bench_mixed.py", "device": torch.cuda.get_device_name(0), "runs": args.runs, "cases": results}, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
