@@ -40,7 +40,8 @@ extern "C" {
 
 /* per-proof status bits (h2v_verify_batch_ex / trace): 0 = accepted */
 #define H2V_ST_BAD_SCALAR 1u       /* non-canonical scalar encoding in the proof */
-#define H2V_ST_INVERSE_OF_ZERO 2u  /* an inversion the verifier needs hit zero (recip_eea panics, bls_utils.ak:151-154) */
+#define H2V_ST_INVERSE_OF_ZERO 2u  /* an inversion the verifier needs hit zero (recip_eea panics, bls_utils.ak:151-154); no proof can
+                                    * steer a challenge there: produced by tests/test_vm_programs_gpu.py::test_status_bits_per_lane */
 #define H2V_ST_SHORT_PROOF 4u      /* fewer bytes than the plan's proof layout */
 #define H2V_ST_BAD_POINT 8u        /* a G1 encoding is malformed / off-curve / not in the subgroup */
 #define H2V_ST_PAIRING 16u         /* e(pi, s_g2) != e(er, G2) */
@@ -431,6 +432,18 @@ int h2v_plan_trace_slots(const h2v_plan *plan, uint32_t *slot_ids, uint32_t cap,
 int h2v_trace(const h2v_plan *plan, const uint8_t *proof, size_t proof_len, const uint8_t *instances,
               const uint8_t *committed, uint8_t *scalars_out, uint8_t *msm_scalars_out /* T*32 or NULL */,
               uint8_t el_out[96], uint8_t er_out[96], uint32_t *status_out, uint8_t *accept_out);
+
+/* The transcript + Fr-combiner interpreter ALONE on a batch of host buffers: no decompression, MSM or pairing runs, so the plan's
+ * program may be any byte code h2v_plan_load accepts (the hand-assembled programs of tests/test_vm_programs_gpu.py), whatever
+ * its OUT_SCALARs would mean to the rest of the pipeline.  status_out: n words, the H2V_ST_* bits the interpreter sets
+ * (BAD_SCALAR, INVERSE_OF_ZERO, SHORT_PROOF, RECURSION); msm_scalars_out: n * n_terms * 32 bytes LE (a term no OUT_SCALAR
+ * wrote reads zero); trace_out: n * n_trace * 32 bytes LE in the order of h2v_plan_trace_slots(), NULL unless want_trace.
+ * want_trace != 0 forces the plan's NARROW schedule, whatever H2V_OPT_COMBINER_SCHEDULE says: the trace table names the narrow
+ * schedule's registers; it needs a plan with a trace table.  The launch takes H2V_OPT_COMBINER_SCHEDULE and
+ * H2V_OPT_COMBINER_PROOFS_PER_BLOCK from h2v_probe_set_option.  Argument errors return H2V_E_ARG. */
+int h2v_probe_vm(const h2v_plan *plan, const h2v_batch *batch /* host buffers */, int want_trace,
+                 uint32_t *status_out /* n */, uint8_t *msm_scalars_out /* n * n_terms * 32, LE */,
+                 uint8_t *trace_out /* n * n_trace * 32, LE; NULL unless want_trace */);
 
 /* primitive probes for the GPU parity tests (host buffers; canonical little-endian limbs) */
 int h2v_probe_field(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out);

@@ -89,7 +89,7 @@ EXPORTS = [
     "h2v_workspace_timings", "h2v_workspace_hint_in_flight", "h2v_workspace_create_lanes", "h2v_workspace_create_multi", "h2v_workspace_defer_joins",
     "h2v_workspace_join", "h2v_workspace_lanes", "h2v_workspace_depth", "h2v_workspace_set_option", "h2v_workspace_get_option", "h2v_workspace_tune", "h2v_probe_set_option",
     "h2v_verify_batch", "h2v_verify_batch_submit", "h2v_verify_batch_wait", "h2v_verify_batch_device", "h2v_verify_batch_rlc", "h2v_verify_batch_rlc_device",
-    "h2v_workspace_rlc_result", "h2v_probe_g1_msm_pippenger", "h2v_plan_trace_slots", "h2v_trace", "h2v_probe_field",
+    "h2v_workspace_rlc_result", "h2v_probe_g1_msm_pippenger", "h2v_plan_trace_slots", "h2v_trace", "h2v_probe_vm", "h2v_probe_field",
     "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_f28_dot2", "h2v_probe_pairing", "h2v_probe_pairing_ex",
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
@@ -159,6 +159,7 @@ def lib():
         L.h2v_probe_blake2b_ex.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p]
         L.h2v_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+        L.h2v_probe_vm.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_field.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_f28_dot2.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_blake2b.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
@@ -580,6 +581,26 @@ class BatchStream:
         if self.ws is not None:
             self.ws.close()
             self.ws = None
+
+
+def probe_vm(plan: DevicePlan, proofs: bytes, proof_off, instances: bytes, committed: Optional[bytes], want_trace: bool = True):
+    """h2v_probe_vm: the transcript + combiner interpreter alone on a batch.  Returns (status words, scalars[n][n_terms],
+    trace) with trace = one {slot id: register value} dict per proof, or None without want_trace (which forces the plan's
+    narrow schedule: the trace table names its registers).  The launch shape comes from probe_set_option."""
+    n, b, _keep = plan._host_batch(proofs, proof_off, instances, committed)
+    nt, T = len(plan.trace_slots), plan.n_terms
+    st = (C.c_uint32 * max(1, n))()
+    ms = C.create_string_buffer(32 * T * max(1, n))
+    tr = C.create_string_buffer(32 * max(1, nt * n)) if want_trace else None
+    check(lib().h2v_probe_vm(plan.handle, C.byref(b), 1 if want_trace else 0, st, ms, tr))
+    raw = ms.raw
+    scal = [[int.from_bytes(raw[32 * (i * T + k):32 * (i * T + k + 1)], "little") for k in range(T)] for i in range(n)]
+    trace = None
+    if want_trace:
+        raw = tr.raw
+        trace = [{plan.trace_slots[k]: int.from_bytes(raw[32 * (i * nt + k):32 * (i * nt + k + 1)], "little") for k in range(nt)}
+                 for i in range(n)]
+    return list(st[:n]), scal, trace
 
 
 def probe_field(op: int, a_list, b_list, device: int = 0):

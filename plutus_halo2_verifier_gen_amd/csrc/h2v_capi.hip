@@ -3924,6 +3924,41 @@ extern "C" int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t 
     pip_free(pw);
     return rc;
 }
+// The transcript + combiner launch alone, on a batch: status words, term scalars and (want_trace) the plan's trace registers of
+// every proof.  Nothing behind launch_vm runs, so a plan whose OUT_SCALARs mean nothing to the MSM is safe here.  The outputs
+// are preset (scalars and trace zero, status all ones), so what the kernel left unwritten is visible as such.
+extern "C" int h2v_probe_vm(const h2v_plan *p, const h2v_batch *b, int want_trace, uint32_t *status_out, uint8_t *msm_scalars_out, uint8_t *trace_out) {
+    if (!p || !b || !status_out || !msm_scalars_out) return fail(H2V_E_ARG, "null argument");
+    if (b->n == 0 || b->n > (1ull << 24)) return fail(H2V_E_ARG, "batch size out of range");
+    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null batch buffers");
+    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
+    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    if (want_trace ? (!trace_out || !p->d.n_trace) : trace_out != nullptr)
+        return fail(H2V_E_ARG, "trace_out goes with want_trace and a plan that has a trace table");
+    ALIVE(p);
+    HIPCHK(hipSetDevice(p->device));
+    ProbeOpts probe_opts;
+    const uint32_t n = (uint32_t)b->n;
+    const H2vDevPlan &d = p->d;
+    h2v_workspace *ws = nullptr;
+    int rc = ws_create_for(d, p->device, n, want_trace != 0, &ws);
+    if (rc) return rc;
+    Staged in;
+    rc = stage_batch(p, b, ws, ws->hslot[0], &in);
+    do {
+        if (rc) break;
+        const size_t sc_bytes = (size_t)n * d.n_terms * 32, tr_bytes = (size_t)n * d.n_trace * 32;
+        if (hipMemsetAsync(ws->scalars, 0, sc_bytes, ws->hs) != hipSuccess || hipMemsetAsync(ws->status, 0xff, (size_t)n * 4, ws->hs) != hipSuccess ||
+            (want_trace && hipMemsetAsync(ws->trace, 0, tr_bytes, ws->hs) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "hipMemsetAsync failed"); break; }
+        if ((rc = launch_vm(d, n, ws->stride, in.proofs, in.off, in.inst, in.ci, ws->regs, ws->scalars, ws->status, want_trace ? ws->trace : nullptr, ws->hs))) break;
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ws->hs) != hipSuccess) { rc = fail(H2V_E_DEVICE, "combiner kernel failed"); break; }
+        if (hipMemcpy(status_out, ws->status, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(msm_scalars_out, ws->scalars, sc_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+            (want_trace && hipMemcpy(trace_out, ws->trace, tr_bytes, hipMemcpyDeviceToHost) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
+    } while (0);
+    h2v_workspace_free(ws);
+    return rc;
+}
 extern "C" int h2v_probe_pairing_ex(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out, int impl, uint8_t *dbg);
 extern "C" int h2v_probe_pairing(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out) {
     return h2v_probe_pairing_ex(p, n, p1c, p2c, out, -1, nullptr);

@@ -998,11 +998,14 @@ class PlanReject(Exception):
 
 
 def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional[bytes] = None,
-             stop_before_point: Optional[int] = None, use_wide: bool = False):
+             stop_before_point: Optional[int] = None, use_wide: bool = False, reasons: Optional[set] = None,
+             squeezed: Optional[list] = None):
     """Executes the plan's bytecode with Python integers (host-side tool: used by the synthetic-proof forger and by
     the CPU tests of the compiler; NOT the verification path).  Returns (term scalars, registers, status).
     status: None = ran to the end, or a reject reason string.  With stop_before_point=i the run stops just before
-    READ_POINT of point slot i (used to forge the last proof element)."""
+    READ_POINT of point slot i (used to forge the last proof element).  `reasons`, a set the caller hands in, receives
+    EVERY reject reason of the run (status names the first only); `squeezed`, a list, the two 256-bit halves (lo, hi) that
+    every SQUEEZE reduces to its challenge."""
     import hashlib
 
     instrs, n_regs = (plan.wide[2], plan.wide[1]) if use_wide else (plan.instrs, plan.n_regs)
@@ -1017,7 +1020,14 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
     status = None
     n_points_read = 0
     if len(proof) < plan.proof_len and stop_before_point is None:
+        if reasons is not None:
+            reasons.add("short")
         return scalars, regs, "short"
+
+    def reject(why):
+        if reasons is not None:
+            reasons.add(why)
+        return status or why
     for op, d, a, c in instrs:
         if op == OP_END:
             break
@@ -1029,7 +1039,7 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
             acc += b"\x01" + committed
         elif op == OP_LOAD_INSTANCE:
             if not 0 <= instances[a] < R:   # only the canonical encoding of a public input exists on the reference side
-                status = status or "scalar"
+                status = reject("scalar")
             regs[d] = instances[a] % R
         elif op == OP_READ_POINT:
             if stop_before_point is not None and n_points_read == stop_before_point:
@@ -1042,7 +1052,7 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
             raw = proof[off:off + 32]
             val = int.from_bytes(raw, "little")
             if val >= R:
-                status = status or "scalar"
+                status = reject("scalar")
             regs[d] = val % R
             acc += b"\x01" + raw
         elif op == OP_SQUEEZE:
@@ -1056,6 +1066,8 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
                 h = hashlib.blake2b(bytes(acc), digest_size=32).digest()
                 h2 = hashlib.blake2b(h, digest_size=32).digest()
             regs[d] = (int.from_bytes(h, "little") + int.from_bytes(h2, "little") * bls.R_2_256) % R
+            if squeezed is not None:
+                squeezed.append((int.from_bytes(h, "little"), int.from_bytes(h2, "little")))
         elif op == OP_CONST:
             regs[d] = plan.consts[a]
         elif op == OP_ADD:
@@ -1068,7 +1080,7 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
             regs[d] = (-regs[a]) % R
         elif op == OP_INV:
             if regs[a] == 0:
-                status = status or "inverse"
+                status = reject("inverse")
                 regs[d] = 0
             else:
                 regs[d] = pow(regs[a], R - 2, R)
@@ -1076,7 +1088,7 @@ def run_plan(plan: Plan, proof: bytes, instances: List[int], committed: Optional
             scalars[d] = regs[a]
         elif op == OP_ASSERT_ZERO:
             if regs[a] != 0:
-                status = status or "recursion"
+                status = reject("recursion")
         else:
             raise ValueError("bad opcode %d" % op)
     return scalars, regs, status
