@@ -1113,7 +1113,11 @@ static int ws_streams(h2v_workspace *w, bool need_main, bool need_side) {
 struct LaunchOptions { int32_t v[H2V_OPT_COUNT] = {}; uint32_t in_flight = 1; };
 static thread_local LaunchOptions g_opts;
 static thread_local LaunchOptions g_probe_opts;     // h2v_probe_set_option: the shape options the probes of this thread launch with
-static void opts_from(const h2v_workspace *w) { memcpy(g_opts.v, w->opt, sizeof g_opts.v); g_opts.in_flight = w->in_flight_hint; }
+// the launch options of workspace w while a call's kernels are enqueued on this thread
+struct LaunchOptsScope {
+    explicit LaunchOptsScope(const h2v_workspace *w) { memcpy(g_opts.v, w->opt, sizeof g_opts.v); g_opts.in_flight = w->in_flight_hint; }
+    ~LaunchOptsScope() { g_opts = LaunchOptions(); }
+};
 struct ProbeOpts { ProbeOpts() { g_opts = g_probe_opts; } ~ProbeOpts() { g_opts = LaunchOptions(); } };
 extern "C" int h2v_probe_set_option(uint32_t option, int32_t value) {
     if (option == H2V_OPT_STREAMS) return fail(H2V_E_ARG, "the probes run on the NULL stream");
@@ -1496,21 +1500,92 @@ static uint32_t launch_pairing(const H2vDevPlan &d, uint32_t n, const uint32_t *
 // Enqueues the four kernels.  The decompression kernel (many short waves) runs on a side stream beside the
 // transcript+combiner kernel (few long waves), and the two join before the MSM.
 extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_timings *tm);
-// fold (H2V_RLC_FOLD_PAIRS, recursive plans): instead of the per-proof pairing, the batch check over the folded pairs (fold_pairs_tail)
-struct FoldPairs { const h2v_plan *p; const uint32_t *seed; uint32_t *fail_ctr; };
-// mixed (h2v_verify_mixed, a per-plan sub-batch): instead of the pairing, k_mixed_pairs writes each proof's pair, `good` and its
-// pre-pairing status at pos[i] - its position in the call - of the call's pool; the record is a prepare call's.
-struct MixedOut { const uint32_t *pos; uint32_t *pool; uint8_t *good; uint32_t *status; };
-static int fold_pairs_tail(const FoldPairs &f, uint32_t n, const uint32_t *er2, const uint32_t *el2, uint8_t *accept, h2v_workspace *w, CallRec &rec, hipStream_t st);
-// pairs_out (prepare calls): instead of the pairing, k_prepare_export writes each proof's pair compress(L) || compress(R)
-// there (n x 24 dwords) and the status words without H2V_ST_PAIRING; accept is not written.
-static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst,
-                        const uint8_t *ci, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
-                        h2v_timings *tm, bool want_trace, uint32_t *pairs_out = nullptr, const FoldPairs *fold = nullptr, const MixedOut *mixed = nullptr) {
-    opts_from(w);
-    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
+// ---- one unit of work on one ordinary workspace (or lane): its kind and its buffers, nothing else
+//   VERIFY       the four kernels; accept[] and (optional) status[]
+//   PREPARE      instead of the pairing, k_prepare_export writes each proof's pair compress(L) || compress(R) to pairs_out
+//                (n x 24 dwords) and the status words without H2V_ST_PAIRING; accept is not written
+//   CHECK        the pairing alone over n x 96 bytes of `pairs` (run_check)
+//   RLC          the batch check over the proofs, the per-proof kernels behind its skip flags (run_rlc)
+//   PAIR_RLC     the batch check over `pairs` (run_pairs_rlc)
+//   FOLD_RLC     H2V_RLC_FOLD_PAIRS, recursive plans: instead of the per-proof pairing, the batch check over the folded pairs
+//                (fold_pairs_tail)
+//   ROUTED       an RLC call sent straight to the per-proof kernels (run_routed)
+//   MIXED_SUB    h2v_verify_mixed, a per-plan sub-batch: instead of the pairing, k_mixed_pairs writes each proof's pair, `good`
+//                and its pre-pairing status at pos[i] - its position in the call - of the call's pool; the record is a prepare call's
+//   MIXED_TAIL / MIXED_TAIL_RLC   the pairing / the batch check over the call's pool (run_mixed_tail)
+// seed: the batch coefficients' (RLC kinds).  fail_ctr: where a failed batch check is counted - a lane's chunk or a coalesced
+// group: its parent's word; NULL (a call of its own): its record's word, zeroed by the call.
+enum class UnitKind : uint8_t { VERIFY, PREPARE, CHECK, RLC, PAIR_RLC, FOLD_RLC, ROUTED, MIXED_SUB, MIXED_TAIL, MIXED_TAIL_RLC };
+// the pool of a mixed call, caller's order: pairs (two-slot affine records), good_i, 2 x cap bytes of 1 (the `valid` of a two-slot
+// view) and the status words (pre-pairing bits; the tail folds H2V_ST_PAIRING in)
+struct MixedPool { uint32_t *pool; uint8_t *good; const uint8_t *ones; uint32_t *status; };
+struct Unit {
+    UnitKind kind;
+    const h2v_plan *p;
+    uint32_t n;
+    const uint8_t *proofs = nullptr; const uint64_t *off = nullptr; const uint8_t *inst = nullptr, *ci = nullptr;
+    const uint8_t *pairs = nullptr;
+    uint8_t *accept = nullptr; uint32_t *status = nullptr; uint8_t *pairs_out = nullptr;
+    MixedPool pool = {}; const uint32_t *pos = nullptr;
+    uint32_t seed[8] = {};
+    uint32_t *fail_ctr = nullptr;
+    bool one_stream_opt = false;       // RLC: h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM (lanes and coalesced groups: always)
+    bool trace = false;                // h2v_trace: the combiner's intermediate values to the workspace's trace buffer
+    bool batch_check() const { return kind == UnitKind::RLC || kind == UnitKind::PAIR_RLC || kind == UnitKind::FOLD_RLC || kind == UnitKind::MIXED_TAIL_RLC; }
+    // the same unit for proofs / pairs lo .. lo + m (proof offsets are absolute: `proofs` stays; a sub-batch writes the pool
+    // through pos[], the tail reads its own part of it)
+    Unit slice(uint32_t lo, uint32_t m) const {
+        Unit c = *this;
+        c.n = m;
+        if (off) c.off = off + lo;
+        if (inst) c.inst = inst + (size_t)lo * p->d.n_pi * 32;
+        if (ci) c.ci = ci + (size_t)lo * 48;
+        if (pairs) c.pairs = pairs + (size_t)lo * 96;
+        if (accept) c.accept = accept + lo;
+        if (status) c.status = status + lo;
+        if (pairs_out) c.pairs_out = pairs_out + (size_t)lo * 96;
+        if (pos) c.pos = pos + lo;
+        if (kind == UnitKind::MIXED_TAIL || kind == UnitKind::MIXED_TAIL_RLC) c.pool = {pool.pool + (size_t)lo * 48, pool.good + lo, pool.ones, pool.status + lo};
+        return c;
+    }
+};
+static Unit unit_of_batch(UnitKind kind, const h2v_plan *p, const h2v_batch *b, uint8_t *accept, uint32_t *status) {
+    Unit u{kind, p, (uint32_t)b->n};
+    u.proofs = b->proofs; u.off = b->proof_off; u.inst = b->instances; u.ci = b->committed;
+    u.accept = accept; u.status = status;
+    return u;
+}
+static Unit unit_of_pairs(UnitKind kind, const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status) {
+    Unit u{kind, p, (uint32_t)n};
+    u.pairs = pairs; u.accept = accept; u.status = status;
+    return u;
+}
+static int fold_pairs_tail(const Unit &u, const uint32_t *er2, const uint32_t *el2, h2v_workspace *w, CallRec &rec, hipStream_t st);
+// Decompression: ONE launch whose waves (at most one per SIMD) take 64-point units from a queue - all subgroup tests,
+// then all square roots (k_g1_decompress_queue).  v: the plan, or a view of it (pair_view); tab: where the MSM window tables
+// go (NULL: none are built).
+static int launch_decompress(const H2vDevPlan &v, uint32_t n, const uint8_t *src, const uint64_t *off, const uint8_t *ci, const uint8_t *inst,
+                             h2v_workspace *w, uint32_t *tab, hipStream_t st) {
+    const uint32_t dec_grid = (n * H2V_SLOTS(v) + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
+    const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
+    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
+    hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, src, off, ci, inst, w->pts, w->valid, tab, w->valid_sub, w->dec_ctr, dec_grid);
+    return H2V_OK;
+}
+// The per-proof pairing behind skip flags (the fall-back of a batch check): a walking grid of one wave per SIMD - finding out
+// that the launch is not needed costs a few microseconds, and a launch that IS needed has the whole chip.
+static void launch_pairing_behind(const uint32_t *skip, const H2vDevPlan &v, uint32_t n, const uint32_t *pts, const uint8_t *valid, const uint8_t *valid_sub,
+                                  const uint32_t *er, const uint32_t *el, uint32_t *status, uint8_t *accept, hipStream_t st) {
+    const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
+    hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, v, n, pts, valid, valid_sub, er, el, status, accept, (uint32_t *)nullptr, skip);
+}
+static int run_pipeline(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const H2vDevPlan &d = u.p->d;
+    const uint32_t n = u.n;
+    const bool fold = u.kind == UnitKind::FOLD_RLC, mixed = u.kind == UnitKind::MIXED_SUB, prepare = u.kind == UnitKind::PREPARE;
+    LaunchOptsScope opts(w);
     const uint32_t slots = H2V_SLOTS(d);
-    uint32_t *trace = want_trace ? w->trace : nullptr;
+    uint32_t *trace = u.trace ? w->trace : nullptr;
     // H2V_DEBUG_SYNC: after each stage, say which kernel was launched and wait for the whole device, so that a fault is
     // reported at the stage that caused it
     static const bool dbg = getenv("H2V_DEBUG_SYNC") != nullptr;
@@ -1531,7 +1606,7 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     if (!one_stream)
         if (int rcs = ws_streams(w, !two_stream, true)) return rcs;
     hipStream_t pm = (one_stream || two_stream) ? st : w->pmain, ps = one_stream ? st : w->pside;
-    CallRec &rec = rec_new(w, fold ? h2v_workspace::RLC : (pairs_out || mixed) ? h2v_workspace::PREPARE : h2v_workspace::VERIFY);
+    CallRec &rec = rec_new(w, fold ? h2v_workspace::RLC : (prepare || mixed) ? h2v_workspace::PREPARE : h2v_workspace::VERIFY);
     // fold (H2V_RLC_FOLD_PAIRS): the record's events carry run_rlc's layout - [0]/[1] around the decompression, [2]/[3] around the
     // combiner, the rest recorded by pairs_rlc_core - and the pipeline's own markers go to a set of the workspace that nobody reads
     hipEvent_t *ev = rec.ev;
@@ -1542,18 +1617,9 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     HIPCHK(hipEventRecord(w->ev_fork, st));
     HIPCHK(hipStreamWaitEvent(pm, w->ev_fork, 0));
     HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
-    // Decompression: ONE launch whose waves (at most one per SIMD) take 64-point units from a queue - all subgroup tests,
-    // then all square roots (k_g1_decompress_queue)
-    const uint32_t dec_grid = (n * slots + 63) / 64;
     HIPCHK(hipEventRecord(ev[2], ps));
     if (fold) HIPCHK(hipEventRecord(rec.ev[0], ps));
-    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, ps));
-    {
-        const uint32_t units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
-        uint32_t blocks = (units + 3) / 4;
-        if (blocks > max_blocks) blocks = max_blocks;
-        hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, ps, d, n, proofs, off, ci, inst, w->pts, w->valid, w->pt_tab, w->valid_sub, w->dec_ctr, dec_grid);
-    }
+    if (int rcl = launch_decompress(d, n, u.proofs, u.off, u.ci, u.inst, w, w->pt_tab, ps)) return rcl;
     HIPCHK(hipEventRecord(ev[3], ps));
     if (fold) HIPCHK(hipEventRecord(rec.ev[1], ps));
     HIPCHK(hipEventRecord(w->ev_join, ps));
@@ -1568,7 +1634,7 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     if (int rcd = stage_done("k_g1_decompress_queue")) return rcd;
     HIPCHK(hipEventRecord(ev[0], pm));
     if (fold) HIPCHK(hipEventRecord(rec.ev[2], pm));
-    if (int rcv = launch_vm(d, n, w->stride, proofs, off, inst, ci, w->regs, w->scalars, w->status, trace, pm)) return rcv;
+    if (int rcv = launch_vm(d, n, w->stride, u.proofs, u.off, u.inst, u.ci, w->regs, w->scalars, w->status, trace, pm)) return rcv;
     HIPCHK(hipEventRecord(ev[1], pm));
     if (fold) HIPCHK(hipEventRecord(rec.ev[3], pm));
     if (int rcd = stage_done("k_transcript_combiner")) return rcd;
@@ -1615,25 +1681,20 @@ static int run_pipeline(const H2vDevPlan &d, uint32_t n, const uint8_t *proofs, 
     }
     HIPCHK(hipEventRecord(ev[5], pm));
     if (fold) {
-        if (int rcf = fold_pairs_tail(*fold, n, er_in, el_in, accept, w, rec, pm)) return rcf;
+        if (int rcf = fold_pairs_tail(u, er_in, el_in, w, rec, pm)) return rcf;
     } else if (mixed)
-        hipLaunchKernelGGL(k_mixed_pairs, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, (const uint32_t *)w->status, mixed->pos, mixed->pool,
-                           mixed->good, mixed->status);
-    else if (pairs_out)   // (rec.pair stays 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
-        hipLaunchKernelGGL(k_prepare_export, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, pairs_out);
+        hipLaunchKernelGGL(k_mixed_pairs, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, (const uint32_t *)w->status, u.pos, u.pool.pool,
+                           u.pool.good, u.pool.status);
+    else if (prepare)   // (rec.pair stays 0: h2v_workspace_timings reports pairing_ms = 0 for the call)
+        hipLaunchKernelGGL(k_prepare_export, dim3((n + 63) / 64), dim3(64), 0, pm, d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, (uint32_t *)u.pairs_out);
     else
-        rec.pair = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, accept, nullptr, pm, w->in_flight_hint);
+        rec.pair = (uint8_t)launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er_in, el_in, w->status, u.accept, nullptr, pm, w->in_flight_hint);
     HIPCHK(hipEventRecord(ev[6], pm));
     HIPCHK(hipEventRecord(w->ev_done, pm));
     HIPCHK(hipStreamWaitEvent(st, w->ev_done, 0));
-    if (int rcd = stage_done(mixed ? "k_mixed_pairs" : pairs_out ? "k_prepare_export" : "k_pairing")) return rcd;
+    if (int rcd = stage_done(mixed ? "k_mixed_pairs" : prepare ? "k_prepare_export" : "k_pairing")) return rcd;
     HIPCHK(hipGetLastError());
-    if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
-    if (tm) {
-        HIPCHK(hipStreamSynchronize(st));
-        int rc = h2v_workspace_timings(w, 0, tm);
-        if (rc) return rc;
-    }
+    if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
 
@@ -1656,35 +1717,36 @@ static int pair_view_ensure(h2v_workspace *w) {
     }
     return H2V_OK;
 }
-static int run_check(const H2vDevPlan &d, uint32_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st) {
-    opts_from(w);
-    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
-    if (int rc = pair_view_ensure(w)) return rc;
+// the two-slot view of plan d on a workspace that has been through pair_view_ensure
+static H2vDevPlan pair_view(const H2vDevPlan &d, const h2v_workspace *w) {
     H2vDevPlan v = d;
     v.proof_len = 96; v.n_points = 2; v.n_ci = 0; v.n_pi = 0; v.ivc = 0; v.pi_point = 0; v.points = w->pair_pts;
+    return v;
+}
+static int run_check(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const uint32_t n = u.n;
+    LaunchOptsScope opts(w);
+    if (int rc = pair_view_ensure(w)) return rc;
+    const H2vDevPlan v = pair_view(u.p->d, w);
     CallRec &rec = rec_new(w, h2v_workspace::CHECK);
     hipEvent_t *ev = rec.ev;
     for (int q : {0, 1, 2}) HIPCHK(hipEventRecord(ev[q], st));
-    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
     HIPCHK(hipMemsetAsync(w->status, 0, (size_t)n * 4, st));
-    const uint32_t dec_grid = (n * 2 + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
-    const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
-    hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, pairs, (const uint64_t *)w->pair_off, (const uint8_t *)nullptr,
-                       (const uint8_t *)nullptr, w->pts, w->valid, (uint32_t *)nullptr, w->valid_sub, w->dec_ctr, dec_grid);
+    if (int rc = launch_decompress(v, n, u.pairs, w->pair_off, nullptr, nullptr, w, nullptr, st)) return rc;
     HIPCHK(hipEventRecord(ev[3], st));
     HIPCHK(hipEventRecord(ev[4], st));
     hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er, (const uint32_t *)nullptr);
     HIPCHK(hipEventRecord(ev[5], st));
-    rec.pair = (uint8_t)launch_pairing(v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, accept, nullptr, st, w->in_flight_hint);
+    rec.pair = (uint8_t)launch_pairing(v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, nullptr, st, w->in_flight_hint);
     HIPCHK(hipEventRecord(ev[6], st));
     HIPCHK(hipGetLastError());
-    if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
 
-static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                   uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt,
-                   uint32_t *fail_ctr);
+static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st);
+static int run_pairs_rlc(const Unit &u, h2v_workspace *w, hipStream_t st);
+static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
 // ROUTING of RLC calls (round 4).  The batch-accept mode pays for every batch whose check fails: with 1 % rejecting proofs
 // nearly half of the groups of 64 fail, and the call costs 1.3 x the per-proof mode it falls back to.  A workspace therefore
 // keeps a running estimate of the rate of FAILING GROUPS among the groups its RLC calls have seen - cumulative device
@@ -1718,23 +1780,39 @@ static bool rlc_route(h2v_workspace *w) {
     w->routed = w->routed ? w->fail_rate > 0.05f : w->fail_rate > 0.10f;
     return w->routed;
 }
-// a routed chunk / call: the per-proof pipeline (its record: a routed RLC call), then the counters from its status words
-static int run_routed(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                      uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, uint32_t *stats) {
-    int rc = run_pipeline(p->d, n, proofs, off, inst, ci, accept, status_out, w, st, nullptr, false);
+// the counters to their pinned mirror, behind an RLC or routed unit on `st`
+static int rlc_stats_mirror(h2v_workspace *w, hipStream_t st) {
+    if (hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(H2V_E_DEVICE, "routing counters: copy failed");
+    return H2V_OK;
+}
+// a routed chunk / call: the per-proof pipeline (its record: a routed RLC call), then the counters (a lane's: its parent's)
+// from its status words
+static int run_routed(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    int rc = run_pipeline(u, w, st);
     if (rc) return rc;
     rec_last(w).kind = h2v_workspace::RLC;
     rec_last(w).routed = true;
-    hipLaunchKernelGGL(k_rlc_count_groups, dim3(((n + 63) / 64 + 63) / 64), dim3(64), 0, st, n, w->status, stats);
+    hipLaunchKernelGGL(k_rlc_count_groups, dim3(((u.n + 63) / 64 + 63) / 64), dim3(64), 0, st, u.n, w->status, w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats);
     HIPCHK(hipGetLastError());
     return H2V_OK;
+}
+static int run_unit(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    switch (u.kind) {
+    case UnitKind::CHECK: return run_check(u, w, st);
+    case UnitKind::RLC: return run_rlc(u, w, st);
+    case UnitKind::PAIR_RLC: return run_pairs_rlc(u, w, st);
+    case UnitKind::ROUTED: return run_routed(u, w, st);
+    case UnitKind::MIXED_TAIL: case UnitKind::MIXED_TAIL_RLC: return run_mixed_tail(u, w, st);
+    case UnitKind::VERIFY: case UnitKind::PREPARE: case UnitKind::FOLD_RLC: case UnitKind::MIXED_SUB: break;
+    }
+    return run_pipeline(u, w, st);
 }
 // A call on a laned workspace: chunks of at most w->chunk proofs, round robin through the lanes (continuing where the
 // previous call stopped).  Chunk c runs on its lane's own stream(s) behind everything the caller had enqueued on `st`
 // before the call and behind the lane's earlier chunks.  Nothing else orders the chunks: the kernels of neighbouring
 // chunks drift apart by themselves (a decompression launch wants every SIMD, so the second one queues behind the first),
-// and an explicit stagger - chunk c waiting for phase 1 of chunk c - 1 - measured 10-20 % slower.  rlc: every chunk is
-// its own batch check.
+// and an explicit stagger - chunk c waiting for phase 1 of chunk c - 1 - measured 10-20 % slower.  Batch checks: every chunk is
+// its own.
 // How many lanes a call of n proofs cycles through, and (per-proof mode) the streams of a chunk.  Chunks that give the MSM
 // at most half a wave per SIMD are chains of lone waves - latency, not issue slots - and want as many of them in flight
 // as there are streams: every lane, each chunk on its lane's stream alone.  Larger chunks: H2V_PER_PROOF_LANES lanes, the
@@ -1752,25 +1830,70 @@ static uint32_t laned_depth(const h2v_workspace *w, uint64_t n, bool rlc, int *s
     }
     return (small || w->lanes_per_proof >= w->n_lanes) ? w->n_lanes : w->lanes_per_proof;
 }
-// A prepare or pair-check call through the lanes (never RLC): prepare writes pairs to `out`; a check reads them from `in`
-// (then proofs / off / inst / ci are unused).  Both are n x 96 bytes, cut into chunks like accept[].
-// rlc_seed: the call is a batch check - over the pairs of `in` (h2v_check_pairs_rlc), or, without `in` / `out`, a verify call of
-// a recursive plan whose folded pairs are combined (H2V_RLC_FOLD_PAIRS); every chunk is its own check, as for rlc.
-struct PairIO { uint8_t *out; const uint8_t *in; const uint32_t *rlc_seed = nullptr; };
-static int run_pairs_rlc(const h2v_plan *p, uint32_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
-                         const uint32_t seed[8], uint32_t *fail_ctr);
-static int run_fold_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                        uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], uint32_t *fail_ctr);
-static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                     uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t *seed, bool force_join,
-                     bool never_join = false, const PairIO *pio = nullptr) {
-    const H2vDevPlan &d = p->d;
+// What the chunks' launch shapes may assume about the chip: with deferred joins (and the host-buffer stream of batches)
+// consecutive calls overlap and every lane is busy; a call that waits for its own chunks has only THOSE in flight - one
+// 4096-proof chunk on a laned workspace is a lone batch (with the full-chip shapes it took 11.6 ms instead of 5.8).
+// lanes_stay_full: the caller knows that the lanes are full whatever this call brings; own: what this call alone puts in flight.
+static uint32_t call_hint(const h2v_workspace *w, bool lanes_stay_full, uint32_t own) {
+    return w->hint_given ? w->in_flight_hint : (w->defer_joins || lanes_stay_full) ? w->n_lanes : own;
+}
+static uint32_t n_chunks(uint32_t n, uint32_t chunk) { return (n + chunk - 1) / chunk; }
+// the record of a call of n proofs on a laned workspace, cut into `chunk`s that cycle through L lanes from where the previous
+// call stopped
+static CallRec &rec_laned(h2v_workspace *w, h2v_workspace::Kind kind, uint32_t L, uint32_t n, uint32_t chunk) {
+    CallRec &rec = rec_new(w, kind);
+    rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = n_chunks(n, chunk);
+    for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;   // (every chunk takes one record on its lane)
+    return rec;
+}
+// One unit on lane l.  hint: what its launch shapes may assume (call_hint); stream_mode: the streams of a pipeline (laned_depth) -
+// a routed unit runs on the lane's stream alone, and a batch check or a pair check keeps the lane's streams as they are.  Behind
+// an RLC or routed unit the workspace's failing-group counters go to their mirror.
+struct LaneSetup { uint32_t hint; int stream_mode; };
+static int run_on_lane(h2v_workspace *w, uint32_t l, const Unit &u, const LaneSetup &s) {
+    h2v_workspace *lw = w->lane[l];
+    const bool counted = u.kind == UnitKind::RLC || u.kind == UnitKind::ROUTED;
+    lw->in_flight_hint = s.hint;
+    lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
+    if (counted) lw->rlc_stats_ptr = w->rlc_stats;
+    if (u.kind == UnitKind::ROUTED) lw->one_stream_mode = 1;
+    else if (u.kind == UnitKind::VERIFY || u.kind == UnitKind::PREPARE || u.kind == UnitKind::FOLD_RLC || u.kind == UnitKind::MIXED_SUB) lw->one_stream_mode = s.stream_mode;
+    int rc = run_unit(u, lw, w->lane_st[l]);
+    if (rc == H2V_OK && counted) rc = rlc_stats_mirror(w, w->lane_st[l]);
+    return rc;
+}
+// the end of lane l's most recent chunk, for the joins
+static int lane_done(h2v_workspace *w, uint32_t l) {
+    HIPCHK(hipEventRecord(w->lane_ev[l], w->lane_st[l]));
+    w->lane_busy[l] = true;
+    return H2V_OK;
+}
+// THE chunk loop: unit u in `chunk`s round robin through L lanes, each behind the caller's w->ev_fork.  before(lane, stream) runs
+// before a chunk is enqueued on its lane (the mixed tail: its waits for the sub-batches' lanes).  An error of a chunk comes back
+// drained: earlier chunks of this call and of calls before it are in flight on other lanes.
+template <class Before> static int run_chunks(h2v_workspace *w, const Unit &u, uint32_t L, uint32_t chunk, const LaneSetup &s, Before &&before) {
+    for (uint32_t c = 0, nch = n_chunks(u.n, chunk); c < nch; c++) {
+        const uint32_t l = (uint32_t)(w->next_lane++ % L);
+        if (int rc = ensure_lane(w, l)) return rc;
+        HIPCHK(hipStreamWaitEvent(w->lane_st[l], w->ev_fork, 0));
+        if (int rc = before(l, w->lane_st[l])) return rc;
+        const uint32_t lo = c * chunk;
+        Unit cu = u.slice(lo, (u.n - lo) < chunk ? (u.n - lo) : chunk);
+        cu.seed[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
+        if (int rc = run_on_lane(w, l, cu, s)) return drain_after_error(w, rc);
+        if (int rc = lane_done(w, l)) return rc;
+    }
+    return H2V_OK;
+}
+// when `st` waits for the lanes of a call: as the workspace defers its joins or not, now whatever it defers, or not at all (the
+// streamed host batches: their downloads wait for their own lanes)
+enum class Join { AS_DEFERRED, NOW, NEVER };
+static int co_flush(h2v_workspace *w);
+static int run_laned(Unit u, h2v_workspace *w, hipStream_t st, Join join) {
     if (int rcf = co_flush(w)) return rcf;          // (calls start in submission order: an open group of coalesced calls first)
     int stream_mode = 1;
-    const bool pair_rlc = pio && pio->rlc_seed && pio->in, fold_rlc = pio && pio->rlc_seed && !pio->in;   // (then rlc is false)
-    const uint32_t *pair_seed = (pair_rlc || fold_rlc) ? pio->rlc_seed : nullptr;
-    if (fold_rlc) pio = nullptr;
-    const uint32_t L = laned_depth(w, n, rlc || pair_rlc, &stream_mode);
+    const uint32_t n = u.n;
+    const uint32_t L = laned_depth(w, n, u.kind == UnitKind::RLC || u.kind == UnitKind::PAIR_RLC, &stream_mode);
     // A per-proof call that would leave lanes empty at the workspace's chunk size is cut finer, one chunk per lane (in 512s,
     // not below 2048: there the chains' latency costs more than the extra lanes win).  One call on 20 480 simple_mul proofs,
     // eight lanes: chunks of 4096 24.0 ms, 2560 22.5 ms, 2048 27.7 ms.  (RLC mode: every chunk is a batch check of its own and
@@ -1778,79 +1901,28 @@ static int run_laned(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const
     uint32_t chunk = w->chunk;
     // (only for a call that waits for its own chunks: with deferred joins or streamed host batches the NEXT call fills the lanes,
     //  and whole chunks keep the full-chip launch shapes - a stream of 16 384-proof calls: 15.9 ms per call cut in 2048s, ~13 in 4096s)
-    if (!rlc && !pair_seed && !w->defer_joins && !never_join && n > chunk && (uint64_t)n < (uint64_t)L * chunk) {
+    if (!u.batch_check() && !w->defer_joins && join != Join::NEVER && n > chunk && (uint64_t)n < (uint64_t)L * chunk) {
         const uint32_t c2 = (uint32_t)(((n + L - 1) / L + 511) / 512 * 512);
-        if (c2 >= default_chunk(d) / 2 && c2 < chunk) chunk = c2;       // (simple_mul: 2048; T = 60: 512)
+        if (c2 >= default_chunk(u.p->d) / 2 && c2 < chunk) chunk = c2;       // (simple_mul: 2048; T = 60: 512)
     }
-    const uint32_t nch = (n + chunk - 1) / chunk;
-    // What the chunks' launch shapes may assume about the chip: with deferred joins (and the host-buffer stream of batches)
-    // consecutive calls overlap and every lane is busy; a call that waits for its own chunks has only THOSE in flight - one
-    // 4096-proof chunk on a laned workspace is a lone batch (with the full-chip shapes it took 11.6 ms instead of 5.8).
-    const uint32_t call_hint = w->hint_given ? w->in_flight_hint : (w->defer_joins || never_join) ? w->n_lanes : (nch < L ? nch : L);
-    CallRec &rec = rec_new(w, (rlc || pair_seed) ? h2v_workspace::RLC : !pio ? h2v_workspace::VERIFY : pio->in ? h2v_workspace::CHECK : h2v_workspace::PREPARE);
-    rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = nch;
-    for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;   // (every chunk takes one record on its lane)
-    bool routed = false;
-    if (rlc) {
+    const uint32_t nch = n_chunks(n, chunk);
+    CallRec &rec = rec_laned(w, u.batch_check() ? h2v_workspace::RLC : u.kind == UnitKind::CHECK ? h2v_workspace::CHECK : u.kind == UnitKind::PREPARE ? h2v_workspace::PREPARE : h2v_workspace::VERIFY,
+                             L, n, chunk);
+    if (u.batch_check()) {
+        // the chunks report into this record's word.  RLC over proofs: routed - "a batch check failed" = the per-proof kernels
+        // produce accept[]; over pairs (given or folded): never routed, and the failing-group estimate stays where it is
         if (int rcs = rlc_stats_ensure(w)) return rcs;
-        routed = rec.routed = rlc_route(w);
-        HIPCHK(hipMemsetAsync(rec_word(w, rec), routed ? 1 : 0, 4, st));      // (routed: "a batch check failed" = the per-proof kernels produce accept[])
-    }
-    if (pair_seed) {              // never routed, and the failing-group estimate stays where it is
-        if (int rcs = rlc_stats_ensure(w)) return rcs;
-        HIPCHK(hipMemsetAsync(rec_word(w, rec), 0, 4, st));
+        if (u.kind == UnitKind::RLC && (rec.routed = rlc_route(w))) u.kind = UnitKind::ROUTED;
+        HIPCHK(hipMemsetAsync(rec_word(w, rec), rec.routed ? 1 : 0, 4, st));
+        u.fail_ctr = rec_word(w, rec);
+        u.one_stream_opt = true;
     }
     HIPCHK(hipEventRecord(w->ev_fork, st));
-    for (uint32_t c = 0; c < nch; c++) {
-        const uint32_t l = (uint32_t)(w->next_lane++ % L);
-        int rc = ensure_lane(w, l);
-        if (rc) return rc;
-        h2v_workspace *lw = w->lane[l];
-        hipStream_t ls = w->lane_st[l];
-        const uint32_t lo = c * chunk, m = (n - lo) < chunk ? (n - lo) : chunk;
-        HIPCHK(hipStreamWaitEvent(ls, w->ev_fork, 0));
-        const uint8_t *inst_c = inst ? inst + (size_t)lo * d.n_pi * 32 : nullptr, *ci_c = ci ? ci + (size_t)lo * 48 : nullptr;
-        if (rlc) {
-            uint32_t sd[8];
-            for (int k = 0; k < 8; k++) sd[k] = seed[k];
-            sd[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
-            lw->rlc_stats_ptr = w->rlc_stats;
-            lw->in_flight_hint = call_hint;
-            lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
-            if (routed) {
-                lw->one_stream_mode = 1;
-                rc = run_routed(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, w->rlc_stats);
-            } else {
-                rc = run_rlc(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, true, rec_word(w, rec));
-            }
-            if (rc == H2V_OK && hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, ls) != hipSuccess) rc = fail(H2V_E_DEVICE, "routing counters: copy failed");
-        } else if (pair_seed) {
-            uint32_t sd[8];
-            for (int k = 0; k < 8; k++) sd[k] = pair_seed[k];
-            sd[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
-            lw->in_flight_hint = call_hint;
-            lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
-            if (pair_rlc) {
-                rc = run_pairs_rlc(p, m, pio->in + (size_t)lo * 96, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, rec_word(w, rec));
-            } else {
-                lw->one_stream_mode = stream_mode;
-                rc = run_fold_rlc(p, m, proofs, off + lo, inst_c, ci_c, accept + lo, status_out ? status_out + lo : nullptr, lw, ls, sd, rec_word(w, rec));
-            }
-        } else if (pio && pio->in) {
-            lw->in_flight_hint = call_hint;
-            rc = run_check(d, m, pio->in + (size_t)lo * 96, accept + lo, status_out ? status_out + lo : nullptr, lw, ls);
-        } else {
-            lw->one_stream_mode = stream_mode;
-            lw->in_flight_hint = call_hint;
-            rc = run_pipeline(d, m, proofs, off + lo, inst_c, ci_c, accept ? accept + lo : nullptr, status_out ? status_out + lo : nullptr, lw, ls, nullptr, false,
-                              pio ? (uint32_t *)(pio->out + (size_t)lo * 96) : nullptr);
-        }
-        if (rc) return drain_after_error(w, rc);   // (earlier chunks of this call and of calls before it are in flight on other lanes)
-        HIPCHK(hipEventRecord(w->lane_ev[l], ls));
-        w->lane_busy[l] = true;
-    }
-    if (never_join) return H2V_OK;
-    if (!w->defer_joins || force_join) return lanes_join(w, st);
+    // (a call that waits for its own chunks has only those in flight; streamed host batches keep every lane busy)
+    const LaneSetup setup = {call_hint(w, join == Join::NEVER, nch < L ? nch : L), stream_mode};
+    if (int rc = run_chunks(w, u, L, chunk, setup, [](uint32_t, hipStream_t) { return H2V_OK; })) return rc;
+    if (join == Join::NEVER) return H2V_OK;
+    if (!w->defer_joins || join == Join::NOW) return lanes_join(w, st);
     return H2V_OK;
 }
 // ---- coalescing of small calls (round 4; VERDICT r3 #6: "let lanes pack units of several small calls of the same plan into one
@@ -1927,26 +1999,22 @@ static int co_flush_lane(h2v_workspace *w, uint32_t l) {
     hipStream_t ls = w->lane_st[l];
     int stream_mode = 1;
     (void)laned_depth(w, c.count, false, &stream_mode);
-    lw->one_stream_mode = stream_mode;
-    lw->in_flight_hint = w->hint_given ? w->in_flight_hint : w->n_lanes;
     const h2v_plan *p = c.plan;
-    const uint8_t *inst_g = p->d.n_pi ? c.inst : nullptr, *ci_g = p->d.n_ci ? c.ci : nullptr;
+    const h2v_batch group = {c.count, c.proofs, c.off, p->d.n_pi ? c.inst : nullptr, p->d.n_ci ? c.ci : nullptr};
+    Unit u = unit_of_batch(c.rlc ? UnitKind::RLC : UnitKind::VERIFY, p, &group, c.accept, c.status);
     int rc = H2V_OK;
     bool routed = false;
     if (c.rlc) {
         // one batch check over the group (as a chunk of run_laned), reporting into the group's own verdict word (zeroed when
         // the group was opened); copied below into the calls' records
-        if ((rc = rlc_stats_ensure(w)) == H2V_OK) {
-            routed = rlc_route(w);
-            lw->rlc_stats_ptr = w->rlc_stats;
-            lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
-            if (routed) { lw->one_stream_mode = 1; rc = run_routed(p, c.count, c.proofs, c.off, inst_g, ci_g, c.accept, c.status, lw, ls, w->rlc_stats); }
-            else rc = run_rlc(p, c.count, c.proofs, c.off, inst_g, ci_g, c.accept, c.status, lw, ls, c.seed, true, c.fail);
-            if (rc == H2V_OK && hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, ls) != hipSuccess) rc = fail(H2V_E_DEVICE, "routing counters: copy failed");
-        }
-    } else {
-        rc = run_pipeline(p->d, c.count, c.proofs, c.off, inst_g, ci_g, c.accept, c.status, lw, ls, nullptr, false);
+        if ((rc = rlc_stats_ensure(w)) == H2V_OK && (routed = rlc_route(w))) u.kind = UnitKind::ROUTED;
+        memcpy(u.seed, c.seed, sizeof u.seed);
+        u.fail_ctr = c.fail;
+        u.one_stream_opt = true;
     }
+    lw->one_stream_mode = stream_mode;      // (a group's batch check too: it runs with the streams of a per-proof group of its size)
+    // (groups are gathered with deferred joins: the next calls keep every lane busy)
+    if (rc == H2V_OK) rc = run_on_lane(w, l, u, {call_hint(w, true, 0), stream_mode});
     for (const Coalesce::Part &q : c.parts) {
         if (rc) break;
         if (hipMemcpyAsync(q.accept, c.accept + q.base, q.n, hipMemcpyDeviceToDevice, ls) != hipSuccess ||
@@ -1965,18 +2033,16 @@ static int co_flush_lane(h2v_workspace *w, uint32_t l) {
     c.count = 0;
     c.plan = nullptr;
     if (rc) return drain_after_error(w, rc);
-    HIPCHK(hipEventRecord(w->lane_ev[l], ls));
-    w->lane_busy[l] = true;
-    return H2V_OK;
+    return lane_done(w, l);
 }
-static bool co_wanted(const h2v_workspace *w, const h2v_plan *p, uint64_t n) {
+static bool co_wanted(const h2v_workspace *w, uint64_t n) {
     return w->n_lanes && w->defer_joins && w->opt[H2V_OPT_COALESCE] >= 0 && n * 2 <= w->chunk && !w->pending;
-    (void)p;
 }
-// one small call: gathered into the open group (opening one, or running the open one first when this call does not fit it)
-static int coalesce_call(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, uint32_t *status, h2v_workspace *w, hipStream_t st, bool rlc = false,
-                         const uint32_t *seed = nullptr) {
-    const uint32_t n = (uint32_t)b->n;
+// one small call (VERIFY or RLC): gathered into the open group (opening one, or running the open one first when this call does not fit it)
+static int coalesce_call(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const h2v_plan *p = u.p;
+    const uint32_t n = u.n;
+    const bool rlc = u.kind == UnitKind::RLC;
     // the open group of this plan and mode (a workspace that serves several plans keeps one group per plan open: calls that
     // alternate between two plans would otherwise run every group at one call)
     int found = -1;
@@ -2009,7 +2075,7 @@ static int coalesce_call(const h2v_plan *p, const h2v_batch *b, uint8_t *accept,
         Coalesce &c = *w->co[l];
         c.plan = p; c.plan_gen = p->gen; c.count = 0; c.parts.clear();
         c.rlc = rlc;
-        for (int k = 0; k < 8; k++) c.seed[k] = rlc && seed ? seed[k] : 0;
+        for (int k = 0; k < 8; k++) c.seed[k] = rlc ? u.seed[k] : 0;
         HIPCHK(hipMemsetAsync(c.fail, 0, 16, w->lane_st[l]));   // verdict word and off[0] = 0: behind the previous group's flush on this stream
         w->co_open.push_back(l);
         found = (int)l;
@@ -2019,55 +2085,79 @@ static int coalesce_call(const h2v_plan *p, const h2v_batch *b, uint8_t *accept,
     hipStream_t ls = w->lane_st[l];
     HIPCHK(hipEventRecord(w->ev_fork, st));
     HIPCHK(hipStreamWaitEvent(ls, w->ev_fork, 0));
-    hipLaunchKernelGGL(k_coalesce_offsets, dim3(1), dim3(256), 0, ls, b->proof_off, n, p->d.proof_len, c.off + c.count);
-    hipLaunchKernelGGL(k_coalesce_copy, dim3(n), dim3(256), 0, ls, b->proofs, b->proof_off, c.proofs, c.off + c.count, n);
+    hipLaunchKernelGGL(k_coalesce_offsets, dim3(1), dim3(256), 0, ls, u.off, n, p->d.proof_len, c.off + c.count);
+    hipLaunchKernelGGL(k_coalesce_copy, dim3(n), dim3(256), 0, ls, u.proofs, u.off, c.proofs, c.off + c.count, n);
     HIPCHK(hipGetLastError());
-    if (p->d.n_pi) HIPCHK(hipMemcpyAsync(c.inst + (size_t)c.count * p->d.n_pi * 32, b->instances, (size_t)n * p->d.n_pi * 32, hipMemcpyDeviceToDevice, ls));
-    if (p->d.n_ci) HIPCHK(hipMemcpyAsync(c.ci + (size_t)c.count * 48, b->committed, (size_t)n * 48, hipMemcpyDeviceToDevice, ls));
+    if (p->d.n_pi) HIPCHK(hipMemcpyAsync(c.inst + (size_t)c.count * p->d.n_pi * 32, u.inst, (size_t)n * p->d.n_pi * 32, hipMemcpyDeviceToDevice, ls));
+    if (p->d.n_ci) HIPCHK(hipMemcpyAsync(c.ci + (size_t)c.count * 48, u.ci, (size_t)n * 48, hipMemcpyDeviceToDevice, ls));
     // the call's record: where its group ran is filled in by the flush (co_flush_lane)
     CallRec &rec = rec_new(w, rlc ? h2v_workspace::RLC : h2v_workspace::VERIFY);
     rec.co = true;
-    c.parts.push_back({accept, status, c.count, n, rec.call});
+    c.parts.push_back({u.accept, u.status, c.count, n, rec.call});
     c.count += n;
     w->lane_busy[l] = true;              // (h2v_workspace_join must look at this lane; its event is recorded by the flush)
     if (c.count >= c.cap) return co_flush_lane(w, l);
     return H2V_OK;
 }
+// an RLC call on an ORDINARY workspace: the batch check, or - routed - the per-proof pipeline (its record's word: "failed")
+static int run_rlc_or_routed(Unit u, h2v_workspace *w, hipStream_t st) {
+    int rc = rlc_stats_ensure(w);
+    if (rc) return rc;
+    if (rlc_route(w)) u.kind = UnitKind::ROUTED;
+    if ((rc = run_unit(u, w, st))) return rc;
+    if (u.kind == UnitKind::ROUTED) HIPCHK(hipMemsetAsync(rec_word(w, rec_last(w)), 1, 4, st));
+    return rlc_stats_mirror(w, st);
+}
+// a call of its own (not gathered into a group) on either form of workspace
+static int run_call(const Unit &u, h2v_workspace *ws, hipStream_t st, Join join = Join::AS_DEFERRED) {
+    if (ws->n_lanes) return run_laned(u, ws, st, join);
+    if (u.kind == UnitKind::RLC) return run_rlc_or_routed(u, ws, st);
+    return run_unit(u, ws, st);
+}
+// The argument rules of a batch with proofs in it
+static int batch_args(const h2v_plan *p, const h2v_batch *b) {
+    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null proofs / offsets");
+    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
+    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    return H2V_OK;
+}
+// The temporary workspace of a call that was given none: freed when the entry point returns, which `finish` makes wait for the
+// call's stream first (the enqueued kernels use the workspace's buffers).
+struct TmpWs {
+    h2v_workspace *ws = nullptr;
+    ~TmpWs() { if (ws) h2v_workspace_free(ws); }
+    int make(const h2v_plan *p, uint64_t n, h2v_workspace *&ws_io) {
+        if (ws_io) return H2V_OK;
+        if (int rc = ws_create_for(p->d, p->device, n, false, &ws)) return rc;
+        ws_io = ws;
+        return H2V_OK;
+    }
+    int finish(int rc, hipStream_t st) const {
+        if (ws && rc == H2V_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
+        return rc;
+    }
+};
 
 extern "C" int h2v_verify_batch_device(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, uint32_t *status,
                                        h2v_workspace *ws, void *stream, h2v_timings *timings) {
     if (!p || !b || !accept) return fail(H2V_E_ARG, "null argument");
     if (b->n == 0) return H2V_OK;
-    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null proofs / offsets");
-    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
-    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    if (int rca = batch_args(p, b)) return rca;
     ALIVE(p); ALIVE(ws);
     HIPCHK(hipSetDevice(p->device));
-    h2v_workspace *tmp = nullptr;
-    if (!ws) {
-        int rc = ws_create_for(p->d, p->device, b->n, false, &tmp);
-        if (rc) return rc;
-        ws = tmp;
-    }
-    if (int rcf = ws_fits(ws, p, b->n, false)) { if (tmp) h2v_workspace_free(tmp); return rcf; }
+    TmpWs tmp;
+    if (int rct = tmp.make(p, b->n, ws)) return rct;
+    if (int rcf = ws_fits(ws, p, b->n, false)) return rcf;
     if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
-    if (int rcn = null_stream_check(ws, stream)) { if (tmp) h2v_workspace_free(tmp); return rcn; }
-    if (ws->n_lanes) {
-        if (!timings && co_wanted(ws, p, b->n)) return coalesce_call(p, b, accept, status, ws, (hipStream_t)stream);
-        int rcl = run_laned(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, false, nullptr, timings != nullptr);
-        if (rcl == H2V_OK && timings) {
-            HIPCHK(hipStreamSynchronize((hipStream_t)stream));
-            rcl = h2v_workspace_timings(ws, 0, timings);
-        }
-        return rcl;
+    if (int rcn = null_stream_check(ws, stream)) return rcn;
+    const Unit u = unit_of_batch(UnitKind::VERIFY, p, b, accept, status);
+    if (!timings && co_wanted(ws, b->n)) return coalesce_call(u, ws, (hipStream_t)stream);
+    int rc = run_call(u, ws, (hipStream_t)stream, timings ? Join::NOW : Join::AS_DEFERRED);
+    if (rc == H2V_OK && timings) {
+        HIPCHK(hipStreamSynchronize((hipStream_t)stream));
+        rc = h2v_workspace_timings(ws, 0, timings);
     }
-    int rc = run_pipeline(p->d, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws,
-                          (hipStream_t)stream, timings, false);
-    if (tmp) {
-        if (rc == H2V_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
-        h2v_workspace_free(tmp);
-    }
-    return rc;
+    return tmp.finish(rc, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------- measured launch shapes
@@ -2084,8 +2174,7 @@ extern "C" int h2v_workspace_tune(const h2v_plan *p, const h2v_batch *b, h2v_wor
     ALIVE(p); ALIVE(ws);
     if (flags != 0) return fail(H2V_E_ARG, "flags must be 0 (the per-proof mode is what is tuned)");
     if (b->n == 0 || !b->proofs || !b->proof_off) return fail(H2V_E_ARG, "tuning needs a representative device-resident batch");
-    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
-    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    if (int rca = batch_args(p, b)) return rca;
     HIPCHK(hipSetDevice(p->device));
     if (int rcf = ws_fits(ws, p, b->n, false)) return rcf;
     if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
@@ -2111,11 +2200,10 @@ extern "C" int h2v_workspace_tune(const h2v_plan *p, const h2v_batch *b, h2v_wor
         (void)h2v_workspace_set_option(ws, H2V_OPT_PAIRING_ENGINE, pairing);
         (void)h2v_workspace_set_option(ws, H2V_OPT_MSM_TERMS_PER_LANE, tpl);
     };
+    const Unit u = unit_of_batch(UnitKind::VERIFY, p, b, acc_tmp, nullptr);
     auto round_of_calls = [&](uint32_t calls) -> int {
         for (uint32_t k = 0; k < calls; k++) {
-            int r = co ? coalesce_call(p, b, acc_tmp, nullptr, ws, st)
-                  : laned ? run_laned(p, n, b->proofs, b->proof_off, b->instances, b->committed, acc_tmp, nullptr, ws, st, false, nullptr, false)
-                          : run_pipeline(p->d, n, b->proofs, b->proof_off, b->instances, b->committed, acc_tmp, nullptr, ws, st, nullptr, false);
+            int r = co ? coalesce_call(u, ws, st) : run_call(u, ws, st);
             if (r) return r;
         }
         return laned ? lanes_join(ws, st) : H2V_OK;
@@ -2297,8 +2385,7 @@ static inline size_t accept_extent(uint64_t n) { return (size_t)((n + 7) & ~(uin
 // 16-byte aligned), enqueues ONE upload of it on ws->hs, and returns the batch's device view in `in`.  The slot's blocks grow
 // to a quarter more than a batch that does not fit.  A laned workspace's slot is free by construction and downloads accept[]
 // through a device buffer of its own (d_accept); an ordinary workspace stages in hslot[0], and its accept[] is ws->accept.
-struct Staged { const uint8_t *proofs, *inst, *ci; const uint64_t *off; };
-static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, h2v_workspace::HostSlot &sl, Staged *in) {
+static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, h2v_workspace::HostSlot &sl, h2v_batch *in) {
     const bool laned = ws->n_lanes != 0;
     const uint64_t n = b->n;
     const uint64_t total = b->proof_off[n];
@@ -2336,33 +2423,32 @@ static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws,
     memcpy(sl.h_block + o_proofs, b->proofs, total);
     memset(sl.h_block + o_proofs + total, 0, 64);
     HIPCHK(hipMemcpyAsync(sl.in_block, sl.h_block, need, hipMemcpyHostToDevice, ws->hs));
-    *in = {sl.in_block + o_proofs, sl.in_block + o_inst, sl.in_block + o_ci, (const uint64_t *)sl.in_block};
+    *in = {n, sl.in_block + o_proofs, (const uint64_t *)sl.in_block, sl.in_block + o_inst, sl.in_block + o_ci};
     return H2V_OK;
 }
 static bool rlc_supported(const h2v_plan *p);
 static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o);
 static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]);
-static int run_rlc_or_routed(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                             uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt);
 
 // Host-buffer batches on a LANED workspace: as many in flight as the mode has lanes, on ONE workspace.  Every batch gets a
 // staging slot of its own (pinned block + device block + accept buffers); uploads run in order on `hs`, the chunks on
 // the lanes, and the downloads on `hs_down`, each behind the lanes its batch ran on.  h2v_verify_batch_wait collects the
-// OLDEST batch.
-static int submit_laned(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, bool rlc, const uint32_t *seed, bool fold = false) {
-    const uint32_t depth = laned_depth(ws, b->n, rlc, nullptr);
+// OLDEST batch.  u: the call's kind and seed; its buffers are filled in here.
+static int submit_laned(Unit u, const h2v_batch *b, h2v_workspace *ws) {
+    const uint32_t depth = laned_depth(ws, b->n, u.kind == UnitKind::RLC, nullptr);
     if (ws->h_head - ws->h_tail >= depth || ws->h_head - ws->h_tail >= (uint64_t)h2v_workspace::MAXH)
         return fail(H2V_E_ARG, "as many batches in flight as this workspace has lanes: call h2v_verify_batch_wait first");
     if (!ws->hs_down) HIPCHK(make_stream(&ws->hs_down));
     h2v_workspace::HostSlot &sl = ws->hslot[ws->h_head % h2v_workspace::MAXH];
     if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
     const uint64_t n = b->n;
-    sl.n = n; sl.rlc = rlc || fold;
+    sl.n = n; sl.rlc = u.batch_check();
     if (n) {
-        Staged in;
-        if (int rcs = stage_batch(p, b, ws, sl, &in)) return rcs;
-        const PairIO fold_io{nullptr, nullptr, seed};
-        int rc = run_laned(p, (uint32_t)n, in.proofs, in.off, in.inst, in.ci, sl.d_accept, nullptr, ws, ws->hs, rlc, seed, false, true, fold ? &fold_io : nullptr);
+        h2v_batch in;
+        if (int rcs = stage_batch(u.p, b, ws, sl, &in)) return rcs;
+        u.proofs = in.proofs; u.off = in.proof_off; u.inst = in.instances; u.ci = in.committed;
+        u.accept = sl.d_accept;
+        int rc = run_laned(u, ws, ws->hs, Join::NEVER);
         if (rc == H2V_OK) {
             // the download waits for the lanes this call's chunks ran on (their events as recorded just now)
             const CallRec &r = rec_last(ws);
@@ -2407,32 +2493,32 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
     if (!p || !b || !ws) return fail(H2V_E_ARG, "null argument");
     ALIVE(p); ALIVE(ws);
     if (ws->pending && !ws->n_lanes) return fail(H2V_E_ARG, "the workspace already has a batch in flight: call h2v_verify_batch_wait first");
-    if (b->n && (!b->proofs || !b->proof_off)) return fail(H2V_E_ARG, "null proofs / offsets");
-    if (b->n && p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
-    if (b->n && p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    if (b->n)
+        if (int rca = batch_args(p, b)) return rca;
     HIPCHK(hipSetDevice(p->device));
     int rc = host_stream(ws);
     if (rc) return rc;
     if (b->n && (rc = ws_fits(ws, p, b->n, false))) return rc;
     const bool rlc = (flags & H2V_SUBMIT_RLC) && rlc_supported(p);
     const bool fold = (flags & H2V_SUBMIT_RLC) && !rlc && fold_pairs_wanted(p, opts);   // recursive plans: the batch check after the fold
-    uint32_t seed[8] = {};
+    Unit u{fold ? UnitKind::FOLD_RLC : rlc ? UnitKind::RLC : UnitKind::VERIFY, p, (uint32_t)b->n};
+    u.one_stream_opt = opts && (opts->flags & H2V_RLC_ONE_STREAM);
     if (ws->n_lanes) {
-        if ((rlc || fold) && (rc = rlc_seed(opts, seed))) return rc;
-        return submit_laned(p, b, ws, rlc, seed, fold);
+        if (u.batch_check() && (rc = rlc_seed(opts, u.seed))) return rc;
+        return submit_laned(u, b, ws);
     }
     h2v_workspace::HostSlot &sl = ws->hslot[0];
     if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
     sl.n = b->n;
     sl.rlc = false;
     if (b->n) {
-        if ((rlc || fold) && (rc = rlc_seed(opts, seed))) return rc;
-        Staged in;
+        if (u.batch_check() && (rc = rlc_seed(opts, u.seed))) return rc;
+        h2v_batch in;
         if ((rc = stage_batch(p, b, ws, sl, &in))) return rc;
-        if (fold) rc = run_fold_rlc(p, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, seed, nullptr);
-        else if (rlc) rc = run_rlc_or_routed(p, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, seed, opts && (opts->flags & H2V_RLC_ONE_STREAM));
-        else rc = run_pipeline(p->d, (uint32_t)b->n, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, nullptr, false);
-        sl.rlc = rlc || fold;
+        u.proofs = in.proofs; u.off = in.proof_off; u.inst = in.instances; u.ci = in.committed;
+        u.accept = ws->accept;
+        rc = run_call(u, ws, ws->hs);
+        sl.rlc = u.batch_check();
         if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, ws->accept, b->n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
         if (rc == H2V_OK && sl.rlc && hipMemcpyAsync(sl.h_accept + ((b->n + 7) & ~(uint64_t)7), rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
             rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
@@ -2462,15 +2548,10 @@ static int verify_host(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, h
     if (b->n == 0) return H2V_OK;
     ALIVE(p); ALIVE(ws);
     HIPCHK(hipSetDevice(p->device));
-    h2v_workspace *tmp = nullptr;
-    int rc;
-    if (!ws) {
-        if ((rc = ws_create_for(p->d, p->device, b->n, false, &tmp))) return rc;
-        ws = tmp;
-    }
-    rc = h2v_verify_batch_submit(p, b, ws, flags, opts);
+    TmpWs tmp;
+    int rc = tmp.make(p, b->n, ws);
+    if (rc == H2V_OK) rc = h2v_verify_batch_submit(p, b, ws, flags, opts);
     if (rc == H2V_OK) rc = h2v_verify_batch_wait(ws, accept, fell_back);
-    if (tmp) h2v_workspace_free(tmp);
     return rc;
 }
 extern "C" int h2v_verify_batch(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, h2v_workspace *ws) {
@@ -2478,37 +2559,30 @@ extern "C" int h2v_verify_batch(const h2v_plan *p, const h2v_batch *b, uint8_t *
 }
 
 // ---------------------------------------------------------------------------------------------- prepare / pair check
-// h2v_prepare_batch(_device): the verify pipeline up to the pairing, which k_prepare_export replaces (run_pipeline's pairs_out);
+// h2v_prepare_batch(_device): the verify pipeline up to the pairing, which k_prepare_export replaces (a PREPARE unit);
 // h2v_check_pairs(_device): the pairing alone on pairs from anywhere (run_check).  Same argument rules as the verify calls;
 // never gathered into coalesced groups (run_laned flushes the open groups first).
-static int pairs_common(const h2v_plan *p, uint64_t n, h2v_workspace *ws, const void *stream, bool device_form, h2v_workspace **tmp) {
+static int pairs_common(const h2v_plan *p, uint64_t n, h2v_workspace *&ws, const void *stream, bool device_form, TmpWs &tmp) {
     ALIVE(p); ALIVE(ws);
     HIPCHK(hipSetDevice(p->device));
     if (H2V_SLOTS(p->d) < 2) return fail(H2V_E_ARG, "internal: a plan with fewer than two point slots");
-    if (!ws) {
-        if (int rc = ws_create_for(p->d, p->device, n, false, tmp)) return rc;
-        ws = *tmp;
-    }
+    if (int rc = tmp.make(p, n, ws)) return rc;
     int rc = ws_fits(ws, p, n, false);
     if (rc == H2V_OK && ws->pending) rc = fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
     if (rc == H2V_OK && device_form) rc = null_stream_check(ws, stream);
-    if (rc && *tmp) { h2v_workspace_free(*tmp); *tmp = nullptr; }
     return rc;
 }
-static int batch_args(const h2v_plan *p, const h2v_batch *b) {
-    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null proofs / offsets");
-    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
-    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+static int prepare_args(const h2v_plan *p, const h2v_batch *b, const uint8_t *pairs) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!b) return fail(H2V_E_ARG, "null argument: batch");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
     return H2V_OK;
 }
-// enqueue a prepare (pio->out) or check (pio->in) call of n proofs / pairs on `st`; join: the stream waits for the lanes
-static int pairs_enqueue(const h2v_plan *p, uint64_t n, const h2v_batch *b, const PairIO &pio, uint8_t *accept, uint32_t *status,
-                         h2v_workspace *ws, hipStream_t st, bool join) {
-    const uint8_t *proofs = b ? b->proofs : nullptr, *inst = b ? b->instances : nullptr, *ci = b ? b->committed : nullptr;
-    const uint64_t *off = b ? b->proof_off : nullptr;
-    if (ws->n_lanes) return run_laned(p, (uint32_t)n, proofs, off, inst, ci, accept, status, ws, st, false, nullptr, join, false, &pio);
-    if (pio.in) return run_check(p->d, (uint32_t)n, pio.in, accept, status, ws, st);
-    return run_pipeline(p->d, (uint32_t)n, proofs, off, inst, ci, nullptr, status, ws, st, nullptr, false, (uint32_t *)pio.out);
+static int pairs_args(const h2v_plan *p, const uint8_t *pairs, const uint8_t *accept) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
+    return H2V_OK;
 }
 // the device side of a host-buffer call: n pairs, n status words, n accept bytes
 static int hp_ensure(h2v_workspace *ws, uint64_t n) {
@@ -2521,88 +2595,79 @@ static int hp_ensure(h2v_workspace *ws, uint64_t n) {
     return H2V_OK;
 }
 extern "C" int h2v_prepare_batch_device(const h2v_plan *p, const h2v_batch *b, uint8_t *pairs, uint32_t *status, h2v_workspace *ws, void *stream) {
-    if (!p) return fail(H2V_E_ARG, "null argument: plan");
-    if (!b) return fail(H2V_E_ARG, "null argument: batch");
-    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (int rc = prepare_args(p, b, pairs)) return rc;
     if (b->n == 0) return H2V_OK;
     if ((uintptr_t)pairs & 3) return fail(H2V_E_ARG, "pairs must be 4-byte aligned");
     if (int rc = batch_args(p, b)) return rc;
-    h2v_workspace *tmp = nullptr;
-    if (int rc = pairs_common(p, b->n, ws, stream, true, &tmp)) return rc;
-    if (tmp) ws = tmp;
-    int rc = pairs_enqueue(p, b->n, b, PairIO{pairs, nullptr}, nullptr, status, ws, (hipStream_t)stream, false);
-    if (tmp) {
-        if (rc == H2V_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
-        h2v_workspace_free(tmp);
-    }
-    return rc;
+    TmpWs tmp;
+    if (int rc = pairs_common(p, b->n, ws, stream, true, tmp)) return rc;
+    Unit u = unit_of_batch(UnitKind::PREPARE, p, b, nullptr, status);
+    u.pairs_out = pairs;
+    return tmp.finish(run_call(u, ws, (hipStream_t)stream), (hipStream_t)stream);
 }
 extern "C" int h2v_check_pairs_device(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws, void *stream) {
-    if (!p) return fail(H2V_E_ARG, "null argument: plan");
-    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
-    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
+    if (int rc = pairs_args(p, pairs, accept)) return rc;
     if (n == 0) return H2V_OK;
-    h2v_workspace *tmp = nullptr;
-    if (int rc = pairs_common(p, n, ws, stream, true, &tmp)) return rc;
-    if (tmp) ws = tmp;
-    int rc = pairs_enqueue(p, n, nullptr, PairIO{nullptr, pairs}, accept, status, ws, (hipStream_t)stream, false);
-    if (tmp) {
-        if (rc == H2V_OK && hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
-        h2v_workspace_free(tmp);
-    }
-    return rc;
+    TmpWs tmp;
+    if (int rc = pairs_common(p, n, ws, stream, true, tmp)) return rc;
+    return tmp.finish(run_call(unit_of_pairs(UnitKind::CHECK, p, n, pairs, accept, status), ws, (hipStream_t)stream), (hipStream_t)stream);
 }
 // Host-buffer forms: the batch is staged as for h2v_verify_batch (pinned block, one upload on the workspace's stream), the
 // call runs there with its lanes joined, and the outputs come back before the function returns.
 extern "C" int h2v_prepare_batch(const h2v_plan *p, const h2v_batch *b, uint8_t *pairs, uint32_t *status, h2v_workspace *ws) {
-    if (!p) return fail(H2V_E_ARG, "null argument: plan");
-    if (!b) return fail(H2V_E_ARG, "null argument: batch");
-    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
+    if (int rc = prepare_args(p, b, pairs)) return rc;
     if (b->n == 0) return H2V_OK;
     if (int rc = batch_args(p, b)) return rc;
-    h2v_workspace *tmp = nullptr;
-    if (int rc = pairs_common(p, b->n, ws, nullptr, false, &tmp)) return rc;
-    if (tmp) ws = tmp;
+    TmpWs tmp;
+    if (int rc = pairs_common(p, b->n, ws, nullptr, false, tmp)) return rc;
     const uint64_t n = b->n;
     int rc = host_stream(ws);
-    Staged in{};
+    h2v_batch in{};
     if (rc == H2V_OK) rc = hp_ensure(ws, n);
     if (rc == H2V_OK) rc = stage_batch(p, b, ws, ws->n_lanes ? ws->hslot[ws->h_head % h2v_workspace::MAXH] : ws->hslot[0], &in);
     if (rc == H2V_OK) {
         uint8_t *d_pairs = ws->hp_buf;
         uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
-        const h2v_batch db = {n, in.proofs, in.off, in.inst, in.ci};
-        rc = pairs_enqueue(p, n, &db, PairIO{d_pairs, nullptr}, nullptr, d_status, ws, ws->hs, true);
+        Unit u = unit_of_batch(UnitKind::PREPARE, p, &in, nullptr, d_status);
+        u.pairs_out = d_pairs;
+        rc = run_call(u, ws, ws->hs, Join::NOW);
         if (rc == H2V_OK && hipMemcpyAsync(pairs, d_pairs, (size_t)n * 96, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the pairs failed");
         if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
         if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "prepare kernels failed");
         if (rc) rc = drain_after_error(ws, rc);
     }
-    if (tmp) h2v_workspace_free(tmp);
     return rc;
 }
-extern "C" int h2v_check_pairs(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws) {
-    if (!p) return fail(H2V_E_ARG, "null argument: plan");
-    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
-    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
-    if (n == 0) return H2V_OK;
-    h2v_workspace *tmp = nullptr;
-    if (int rc = pairs_common(p, n, ws, nullptr, false, &tmp)) return rc;
-    if (tmp) ws = tmp;
-    int rc = host_stream(ws);
+// The host-buffer pair checks, u.kind CHECK (h2v_check_pairs) or PAIR_RLC (h2v_check_pairs_rlc: a seed, and the batch verdict
+// comes back as fell_back): pairs up, the call with its lanes joined, accept[] / status[] down, all on the workspace's stream.
+static int check_pairs_host(Unit u, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws, const h2v_rlc_opts *opts, int *fell_back) {
+    const uint64_t n = u.n;
+    const bool rlc = u.kind == UnitKind::PAIR_RLC;
+    TmpWs tmp;
+    if (int rc = pairs_common(u.p, n, ws, nullptr, false, tmp)) return rc;
+    int rc = rlc ? rlc_seed(opts, u.seed) : H2V_OK;
+    if (rc == H2V_OK) rc = host_stream(ws);
     if (rc == H2V_OK) rc = hp_ensure(ws, n);
     if (rc == H2V_OK) {
         uint8_t *d_pairs = ws->hp_buf, *d_accept = ws->hp_buf + (size_t)n * 100;
         uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
+        uint32_t failed = 0;
+        u.pairs = d_pairs; u.accept = d_accept; u.status = d_status;
         if (hipMemcpyAsync(d_pairs, pairs, (size_t)n * 96, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the pairs failed");
-        if (rc == H2V_OK) rc = pairs_enqueue(p, n, nullptr, PairIO{nullptr, d_pairs}, d_accept, d_status, ws, ws->hs, true);
+        if (rc == H2V_OK) rc = run_call(u, ws, ws->hs, Join::NOW);
         if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
         if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
+        if (rc == H2V_OK && rlc && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
         if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "pair check kernels failed");
         if (rc) rc = drain_after_error(ws, rc);
+        else if (fell_back) *fell_back = failed ? 1 : 0;
     }
-    if (tmp) h2v_workspace_free(tmp);
     return rc;
+}
+extern "C" int h2v_check_pairs(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws) {
+    if (int rc = pairs_args(p, pairs, accept)) return rc;
+    if (n == 0) return H2V_OK;
+    return check_pairs_host(Unit{UnitKind::CHECK, p, (uint32_t)n}, pairs, accept, status, ws, nullptr, nullptr);
 }
 
 
@@ -2892,19 +2957,40 @@ static int rlc_groups_launch(RlcWs *r, const GrpShape &gs, uint32_t n, uint8_t *
     return H2V_OK;
 }
 
+// ONE pairing check for the batch over a one-proof view of the plan: el = L = r->sums + 36, er = R = r->sums (both Jacobian), no
+// per-proof points; ev9 marks its end.  Behind it - skipped on the device when the check passed - the group stage over gs.
+// fail_ctr: the unit's, or NULL: the record's word, zeroed here.  stats: the failing-group counters, or NULL (pairs: that
+// estimate describes proofs of a plan).  Everything behind it takes r->flags as skip flags.
+static int launch_batch_pairing(const Unit &u, RlcWs *r, const GrpShape &gs, uint32_t *stats, h2v_workspace *w, CallRec &rec, hipStream_t st) {
+    const uint32_t n = u.n;
+    H2vDevPlan d1 = u.p->d;
+    d1.n_points = 1; d1.n_ci = 0; d1.ivc = 0; d1.pi_point = 0;
+    uint32_t *st1 = r->misc + 24, *fail_ctr = u.fail_ctr;
+    uint8_t *valid1 = (uint8_t *)(r->misc + 26), *acc1 = (uint8_t *)(r->misc + 27);
+    HIPCHK(hipMemsetAsync(st1, 0, 4, st));            // status of the batch check
+    HIPCHK(hipMemsetAsync(valid1, 1, 1, st));
+    if (!fail_ctr) {
+        fail_ctr = rec_word(w, rec);
+        HIPCHK(hipMemsetAsync(fail_ctr, 0, 4, st));
+    }
+    hipLaunchKernelGGL(k_pairing_rlc, dim3(1), dim3(64), COOP_LDS_BYTES(1), st, d1, r->misc, valid1, r->sums, r->sums + 36, st1, acc1, n, r->good, u.accept, r->flags,
+                       (n + 63) / 64, fail_ctr, stats, rlc_groups_on(n) ? 1u : 0u);
+    HIPCHK(hipEventRecord(rec.ev[9], st));
+    if (rlc_groups_on(n))
+        if (int rc = rlc_groups_launch(r, gs, n, u.accept, d1, st, stats)) return rc;
+    return H2V_OK;
+}
 // One batch in RLC mode.  Phase 1 as in run_pipeline (the decompression launch builds no window tables), then the batch
 // check; the per-proof MSM + pairing kernels are queued behind it and return at once unless the batch check failed.
-// fail_ctr: where a failed batch check is counted - a lane's chunk or a coalesced group: its parent's word; NULL (a call of
-// its own): its record's word, zeroed here.  Events (the record's): [0]/[1] around the decompression, [2]/[3] around the
+// Events (the record's): [0]/[1] around the decompression, [2]/[3] around the
 // combiner, [10]/[4] around the scalar preparation, [5] .. [8] the bucket MSMs (pip_launch), [8]/[9] around the pairing.
-static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                   uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt,
-                   uint32_t *fail_ctr) {
+static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const h2v_plan *p = u.p;
     const H2vDevPlan &d = p->d;
+    const uint32_t n = u.n;
     int rc = rlc_ensure(w, p);
     if (rc) return rc;
-    opts_from(w);
-    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
+    LaunchOptsScope opts(w);
     RlcWs *r = w->rlc;
     const uint32_t slots = H2V_SLOTS(d);
     CallRec &rec = rec_new(w, h2v_workspace::RLC);
@@ -2912,7 +2998,7 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     // two streams per batch: the caller's (transcript + combiner, then everything else) and one for the decompression
     // one_stream (h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM, or H2V_OPT_STREAMS = 1): everything on
     // the caller's stream, decompression before the combiner - one stream per batch in flight instead of two
-    const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode != 0 : (one_stream_opt || w->in_flight_hint >= 3);   // (H2V_OPT_STREAMS, the flag, or the caller's in-flight hint)
+    const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode != 0 : (u.one_stream_opt || w->in_flight_hint >= 3);   // (H2V_OPT_STREAMS, the flag, or the caller's in-flight hint)
     if (!one_stream && (rc = ws_streams(w, false, true))) return rc;
     hipStream_t pm = st, ps = one_stream ? st : w->pside;
     if (!one_stream) {
@@ -2921,17 +3007,11 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     }
     // phase 1
     HIPCHK(hipEventRecord(ev[0], ps));
-    {
-        const uint32_t dec_grid = (n * slots + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
-        uint32_t blocks = (units + 3) / 4;
-        if (blocks > max_blocks) blocks = max_blocks;
-        HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, ps));
-        hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, ps, d, n, proofs, off, ci, inst, w->pts, w->valid, (uint32_t *)nullptr, w->valid_sub, w->dec_ctr, dec_grid);
-    }
+    if ((rc = launch_decompress(d, n, u.proofs, u.off, u.ci, u.inst, w, nullptr, ps))) return rc;
     HIPCHK(hipEventRecord(ev[1], ps));
     HIPCHK(hipEventRecord(w->ev_join, ps));
     HIPCHK(hipEventRecord(ev[2], pm));
-    rc = launch_vm(d, n, w->stride, proofs, off, inst, ci, w->regs, w->scalars, w->status, nullptr, pm);
+    rc = launch_vm(d, n, w->stride, u.proofs, u.off, u.inst, u.ci, w->regs, w->scalars, w->status, nullptr, pm);
     if (rc) return rc;
     HIPCHK(hipEventRecord(ev[3], pm));
     if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
@@ -2939,7 +3019,7 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     // the batch check
     RlcArgs ra = {n, p->n_var, p->n_fix, slots, d.pi_point, d.n_terms, d.terms, w->scalars, w->status, w->valid, w->valid_sub, {},
                   r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good};
-    for (int k = 0; k < 8; k++) ra.seed[k] = seed[k];
+    for (int k = 0; k < 8; k++) ra.seed[k] = u.seed[k];
     const uint32_t blocks = (n + 63) / 64;
     hipLaunchKernelGGL(k_rlc_prepare, dim3(blocks), dim3(64), 0, pm, ra);
     hipLaunchKernelGGL(k_rlc_vk_sum, dim3((p->n_fix + 63) / 64), dim3(64), 0, pm, ra, blocks);
@@ -2952,26 +3032,12 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
     const PipWs *pws[2] = {&r->R, &r->L};
     if ((rc = pip_launch(pws, pa, 2, pm, ev + 5))) return rc;   // ev[5..8]
     rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
-    // one pairing check over a one-proof view of the plan: el = L, er = R (both Jacobian), no per-proof points
-    H2vDevPlan d1 = d;
-    d1.n_points = 1; d1.n_ci = 0; d1.ivc = 0; d1.pi_point = 0;
-    uint32_t *st1 = r->misc + 24, *skip = r->flags;
-    uint8_t *valid1 = (uint8_t *)(r->misc + 26), *acc1 = (uint8_t *)(r->misc + 27);
-    HIPCHK(hipMemsetAsync(r->misc + 24, 0, 4, pm));            // status of the batch check
-    HIPCHK(hipMemsetAsync(valid1, 1, 1, pm));
-    if (!fail_ctr) {
-        fail_ctr = rec_word(w, rec);
-        HIPCHK(hipMemsetAsync(fail_ctr, 0, 4, pm));
-    }
-    const uint32_t n_groups = (n + 63) / 64;
-    hipLaunchKernelGGL(k_pairing_rlc, dim3(1), dim3(64), COOP_LDS_BYTES(1), pm, d1, r->misc, valid1, r->sums, r->sums + 36, st1, acc1, n, r->good, accept, skip,
-                       n_groups, fail_ctr, w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats, rlc_groups_on(n) ? 1u : 0u);
-    HIPCHK(hipEventRecord(ev[9], pm));
     // fall-back, skipped on the device when the batch check passed.  Stage 1 finds the groups of 64 proofs that hold a failing
     // proof (everything else is final); stage 2 - window tables, per-proof MSM, per-proof pairing - decides inside those
     // groups.  Walking grids of one wave per SIMD: finding out that a launch is not needed costs a few microseconds, and a
     // launch that IS needed has the whole chip.
-    if (rlc_groups_on(n) && (rc = rlc_groups_launch(r, grp_of_plan(p, w), n, accept, d1, pm, w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats))) return rc;
+    if ((rc = launch_batch_pairing(u, r, grp_of_plan(p, w), w->rlc_stats_ptr ? w->rlc_stats_ptr : w->rlc_stats, w, rec, pm))) return rc;
+    uint32_t *skip = r->flags;
     const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0);
     {
         const uint32_t nb = (n * slots + 63) / 64;
@@ -2983,30 +3049,28 @@ static int run_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const u
         if (!launch_msm_range(d, ma, n, w->scalars, w->pts, nullptr, pm, 1, SegBuf{w->msm_parts, w->sz_segs}))
             return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
     }
-    {
-        const uint32_t nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
-        hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), pm, d, n, w->pts, w->valid, w->valid_sub, w->er, (const uint32_t *)nullptr, w->status, accept, (uint32_t *)nullptr, skip);
-    }
+    launch_pairing_behind(skip, d, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, pm);
     HIPCHK(hipGetLastError());
-    if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
 
 // ---- the batch check over pairs (h2v_check_pairs_rlc; H2V_RLC_FOLD_PAIRS) ---------------------------------------------------
-// n two-slot records of affine points in `pool` (the layout of w->pts).  Enqueues on `st`: the coefficient kernel
+// u.n two-slot records of affine points in `pool` (the layout of w->pts).  Enqueues on `st`: the coefficient kernel
 // (k_rlc_pairs_prepare), L = sum r_i L_i and R = sum r_i R_i as two bucket MSMs with 128-bit scalars in the same launches, ONE
 // k_pairing_rlc over a one-proof view of the plan, and - skipped on the device when the check passed - the group stage.  The
 // caller queues its stage 2 behind it with r->flags as skip flags.  good_given: r->good holds good_i already and `status` is
 // final (k_fold_pairs_affine ran, behind the caller's ev[10]); otherwise valid / valid_sub of the two slots decide and
 // H2V_ST_BAD_POINT is folded into `status`.  Events of the record: [10]/[4] around the coefficient kernel, [5] .. [8] the bucket
 // MSMs, [8]/[9] around the pairing.  The workspace's failing-group estimate is not touched (stats = NULL).
-static int pairs_rlc_core(const h2v_plan *p, uint32_t n, RlcWs *r, const uint32_t *pool, const uint8_t *valid, const uint8_t *valid_sub, bool good_given,
-                          uint32_t *status, uint8_t *accept, h2v_workspace *w, CallRec &rec, hipStream_t st, const uint32_t seed[8], uint32_t *fail_ctr) {
+static int pairs_rlc_core(const Unit &u, RlcWs *r, const uint32_t *pool, const uint8_t *valid, const uint8_t *valid_sub, bool good_given,
+                          uint32_t *status, h2v_workspace *w, CallRec &rec, hipStream_t st) {
+    const uint32_t n = u.n;
     hipEvent_t *ev = rec.ev;
     int rc;
     if (!good_given) HIPCHK(hipEventRecord(ev[10], st));
     RlcPairArgs ra = {n, status, valid, valid_sub, good_given ? r->good : nullptr, {}, r->r_scal, r->l_idx, r->r_idx, r->good};
-    for (int k = 0; k < 8; k++) ra.seed[k] = seed[k];
+    for (int k = 0; k < 8; k++) ra.seed[k] = u.seed[k];
     hipLaunchKernelGGL(k_rlc_pairs_prepare, dim3((n + 63) / 64), dim3(64), 0, st, ra);
     HIPCHK(hipEventRecord(ev[4], st));
     PipArgs pa[2] = {};
@@ -3015,78 +3079,51 @@ static int pairs_rlc_core(const h2v_plan *p, uint32_t n, RlcWs *r, const uint32_
     const PipWs *pws[2] = {&r->R, &r->L};
     if ((rc = pip_launch(pws, pa, 2, st, ev + 5))) return rc;   // ev[5..8]
     rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
-    H2vDevPlan d1 = p->d;
-    d1.n_points = 1; d1.n_ci = 0; d1.ivc = 0; d1.pi_point = 0;
-    uint32_t *st1 = r->misc + 24, *skip = r->flags;
-    uint8_t *valid1 = (uint8_t *)(r->misc + 26), *acc1 = (uint8_t *)(r->misc + 27);
-    HIPCHK(hipMemsetAsync(r->misc + 24, 0, 4, st));
-    HIPCHK(hipMemsetAsync(valid1, 1, 1, st));
-    if (!fail_ctr) {
-        fail_ctr = rec_word(w, rec);
-        HIPCHK(hipMemsetAsync(fail_ctr, 0, 4, st));
-    }
-    hipLaunchKernelGGL(k_pairing_rlc, dim3(1), dim3(64), COOP_LDS_BYTES(1), st, d1, r->misc, valid1, r->sums, r->sums + 36, st1, acc1, n, r->good, accept, skip,
-                       (n + 63) / 64, fail_ctr, (uint32_t *)nullptr, rlc_groups_on(n) ? 1u : 0u);
-    HIPCHK(hipEventRecord(ev[9], st));
-    if (rlc_groups_on(n) && (rc = rlc_groups_launch(r, grp_of_pairs(p, pool), n, accept, d1, st, nullptr))) return rc;
+    if ((rc = launch_batch_pairing(u, r, grp_of_pairs(u.p, pool), nullptr, w, rec, st))) return rc;
     HIPCHK(hipGetLastError());
     return H2V_OK;
 }
 // One batch check over n encoded pairs: decoded as run_check decodes them (the same launch over the same two-slot view), then
 // pairs_rlc_core; stage 2 of the fall-back is run_check's own pair of kernels on a walking grid behind the skip flags.
-// Everything on `st`.  fail_ctr as for run_rlc.  Events: [0]/[1] around the decoding, [2] = [3] (no transcript), then the core's.
-static int run_pairs_rlc(const h2v_plan *p, uint32_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st,
-                         const uint32_t seed[8], uint32_t *fail_ctr) {
-    opts_from(w);
-    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
+// Everything on `st`.  Events: [0]/[1] around the decoding, [2] = [3] (no transcript), then the core's.
+static int run_pairs_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const uint32_t n = u.n;
+    LaunchOptsScope opts(w);
     int rc;
     if ((rc = pair_view_ensure(w)) || (rc = pair_rlc_ensure(w, false))) return rc;
-    if (!fail_ctr && (rc = rlc_stats_ensure(w))) return rc;      // (the records' verdict words)
-    H2vDevPlan v = p->d;
-    v.proof_len = 96; v.n_points = 2; v.n_ci = 0; v.n_pi = 0; v.ivc = 0; v.pi_point = 0; v.points = w->pair_pts;
+    if (!u.fail_ctr && (rc = rlc_stats_ensure(w))) return rc;      // (the records' verdict words)
+    const H2vDevPlan v = pair_view(u.p->d, w);
     RlcWs *r = w->prlc;
     CallRec &rec = rec_new(w, h2v_workspace::RLC);
     rec.no_vm = true;
     hipEvent_t *ev = rec.ev;
     for (int q : {0, 2, 3}) HIPCHK(hipEventRecord(ev[q], st));
-    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
     HIPCHK(hipMemsetAsync(w->status, 0, (size_t)n * 4, st));
-    const uint32_t dec_grid = (n * 2 + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
-    const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
-    hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, pairs, (const uint64_t *)w->pair_off, (const uint8_t *)nullptr,
-                       (const uint8_t *)nullptr, w->pts, w->valid, (uint32_t *)nullptr, w->valid_sub, w->dec_ctr, dec_grid);
+    if ((rc = launch_decompress(v, n, u.pairs, w->pair_off, nullptr, nullptr, w, nullptr, st))) return rc;
     HIPCHK(hipEventRecord(ev[1], st));
-    if ((rc = pairs_rlc_core(p, n, r, w->pts, w->valid, w->valid_sub, false, w->status, accept, w, rec, st, seed, fail_ctr))) return rc;
-    const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
+    if ((rc = pairs_rlc_core(u, r, w->pts, w->valid, w->valid_sub, false, w->status, w, rec, st))) return rc;
     hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er, (const uint32_t *)r->flags);
-    hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, v, n, w->pts, w->valid, w->valid_sub, w->er, (const uint32_t *)nullptr,
-                       w->status, accept, (uint32_t *)nullptr, (const uint32_t *)r->flags);
+    launch_pairing_behind(r->flags, v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, st);
     HIPCHK(hipGetLastError());
-    if (status_out) HIPCHK(hipMemcpyAsync(status_out, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
 // H2V_RLC_FOLD_PAIRS: what run_pipeline enqueues in place of the per-proof pairing of a recursive plan.  After the fold every
 // proof is a pair (el', er') like any other: k_fold_pairs_affine writes them into the set's pool, the core combines them, and
 // the fall-back is the per-proof pairing on the folded points behind the skip flags - no MSM is repeated.
-static int fold_pairs_tail(const FoldPairs &f, uint32_t n, const uint32_t *er2, const uint32_t *el2, uint8_t *accept, h2v_workspace *w, CallRec &rec, hipStream_t st) {
+static int fold_pairs_tail(const Unit &u, const uint32_t *er2, const uint32_t *el2, h2v_workspace *w, CallRec &rec, hipStream_t st) {
+    const uint32_t n = u.n;
     int rc;
     if ((rc = pair_rlc_ensure(w, true))) return rc;
-    if (!f.fail_ctr && (rc = rlc_stats_ensure(w))) return rc;
+    if (!u.fail_ctr && (rc = rlc_stats_ensure(w))) return rc;
     RlcWs *r = w->prlc;
-    const H2vDevPlan &d = f.p->d;
+    const H2vDevPlan &d = u.p->d;
     HIPCHK(hipEventRecord(rec.ev[10], st));
     hipLaunchKernelGGL(k_fold_pairs_affine, dim3((n + 63) / 64), dim3(64), 0, st, n, (uint32_t)H2V_SLOTS(d), w->valid, w->valid_sub, el2, er2, w->status, r->pool, r->good);
-    if ((rc = pairs_rlc_core(f.p, n, r, r->pool, nullptr, nullptr, true, w->status, accept, w, rec, st, f.seed, f.fail_ctr))) return rc;
-    const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
-    hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, d, n, w->pts, w->valid, w->valid_sub, er2, el2,
-                       w->status, accept, (uint32_t *)nullptr, (const uint32_t *)r->flags);
+    if ((rc = pairs_rlc_core(u, r, r->pool, nullptr, nullptr, true, w->status, w, rec, st))) return rc;
+    launch_pairing_behind(r->flags, d, n, w->pts, w->valid, w->valid_sub, er2, el2, w->status, u.accept, st);
     HIPCHK(hipGetLastError());
     return H2V_OK;
-}
-static int run_fold_rlc(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                        uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], uint32_t *fail_ctr) {
-    const FoldPairs f = {p, seed, fail_ctr};
-    return run_pipeline(p->d, n, proofs, off, inst, ci, accept, status_out, w, st, nullptr, false, nullptr, &f);
 }
 static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o) { return p->d.ivc && o && (o->flags & H2V_RLC_FOLD_PAIRS); }
 // The batch coefficients must be unpredictable to whoever made the proofs: 32 bytes from the OS per call (getrandom; fails
@@ -3114,25 +3151,10 @@ static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]) {
 }
 static int rlc_check_batch(const h2v_plan *p, const h2v_batch *b, const uint8_t *accept) {
     if (!p || !b || !accept) return fail(H2V_E_ARG, "null argument");
-    if (b->n && (!b->proofs || !b->proof_off)) return fail(H2V_E_ARG, "null proofs / offsets");
-    if (b->n && p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
-    if (b->n && p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    if (b->n)
+        if (int rc = batch_args(p, b)) return rc;
     if (b->n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 proofs");
     return H2V_OK;
-}
-// an RLC call on an ORDINARY workspace: the batch check, or - routed - the per-proof pipeline (its record's word: "failed")
-static int run_rlc_or_routed(const h2v_plan *p, uint32_t n, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst, const uint8_t *ci,
-                             uint8_t *accept, uint32_t *status_out, h2v_workspace *w, hipStream_t st, const uint32_t seed[8], bool one_stream_opt) {
-    int rc = rlc_stats_ensure(w);
-    if (rc) return rc;
-    if (rlc_route(w)) {
-        rc = run_routed(p, n, proofs, off, inst, ci, accept, status_out, w, st, w->rlc_stats);
-        if (rc == H2V_OK) HIPCHK(hipMemsetAsync(rec_word(w, rec_last(w)), 1, 4, st));
-    } else {
-        rc = run_rlc(p, n, proofs, off, inst, ci, accept, status_out, w, st, seed, one_stream_opt, nullptr);
-    }
-    if (rc == H2V_OK) HIPCHK(hipMemcpyAsync(w->h_rlc_stats, w->rlc_stats, 8, hipMemcpyDeviceToHost, st));
-    return rc;
 }
 extern "C" int h2v_verify_batch_rlc_device(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, uint32_t *status, h2v_workspace *ws,
                                            void *stream, const h2v_rlc_opts *opts) {
@@ -3145,24 +3167,13 @@ extern "C" int h2v_verify_batch_rlc_device(const h2v_plan *p, const h2v_batch *b
     if ((rc = ws_fits(ws, p, b->n, false))) return rc;
     if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
     if ((rc = null_stream_check(ws, stream))) return rc;
-    // recursive plans fold an accumulator per proof (the challenge hashes that proof's own MSM result): no batch form
-    if (!rlc_supported(p) && fold_pairs_wanted(p, opts)) {     // the opt-in batch form of recursive plans: it starts after the fold
-        uint32_t seed[8];
-        if ((rc = rlc_seed(opts, seed))) return rc;
-        const PairIO pio{nullptr, nullptr, seed};
-        if (ws->n_lanes) return run_laned(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, false, nullptr, false, false, &pio);
-        return run_fold_rlc(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, seed, nullptr);
-    }
-    if (!rlc_supported(p)) {
-        if (ws->n_lanes) return run_laned(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, false, nullptr, false);
-        return run_pipeline(p->d, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, nullptr, false);
-    }
-    uint32_t seed[8];
-    if ((rc = rlc_seed(opts, seed))) return rc;
-    if (ws->n_lanes && co_wanted(ws, p, b->n)) return coalesce_call(p, b, accept, status, ws, (hipStream_t)stream, true, seed);
-    if (ws->n_lanes) return run_laned(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, true, seed, false);
-    return run_rlc_or_routed(p, (uint32_t)b->n, b->proofs, b->proof_off, b->instances, b->committed, accept, status, ws, (hipStream_t)stream, seed,
-                             opts && (opts->flags & H2V_RLC_ONE_STREAM));
+    // recursive plans fold an accumulator per proof (the challenge hashes that proof's own MSM result): no batch form, but
+    // the opt-in one that starts after the fold
+    Unit u = unit_of_batch(rlc_supported(p) ? UnitKind::RLC : fold_pairs_wanted(p, opts) ? UnitKind::FOLD_RLC : UnitKind::VERIFY, p, b, accept, status);
+    u.one_stream_opt = opts && (opts->flags & H2V_RLC_ONE_STREAM);
+    if (u.batch_check() && (rc = rlc_seed(opts, u.seed))) return rc;
+    if (u.kind == UnitKind::RLC && co_wanted(ws, b->n)) return coalesce_call(u, ws, (hipStream_t)stream);
+    return run_call(u, ws, (hipStream_t)stream);
 }
 extern "C" int h2v_verify_batch_rlc(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, h2v_workspace *ws, const h2v_rlc_opts *opts,
                                     int *fell_back) {
@@ -3172,62 +3183,34 @@ extern "C" int h2v_verify_batch_rlc(const h2v_plan *p, const h2v_batch *b, uint8
 }
 
 // ---- h2v_check_pairs_rlc(_device): h2v_check_pairs's contract, with ONE pairing for the batch when every pair's equation holds ----
-static int pairs_rlc_enqueue(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws, hipStream_t st,
-                             const uint32_t seed[8], bool join) {
-    const PairIO pio{nullptr, pairs, seed};
-    if (ws->n_lanes) return run_laned(p, (uint32_t)n, nullptr, nullptr, nullptr, nullptr, accept, status, ws, st, false, nullptr, join, false, &pio);
-    return run_pairs_rlc(p, (uint32_t)n, pairs, accept, status, ws, st, seed, nullptr);
+static int pairs_rlc_args(const h2v_plan *p, uint64_t n, const uint8_t *pairs, const uint8_t *accept) {
+    if (int rc = pairs_args(p, pairs, accept)) return rc;
+    if (n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 pairs");
+    return H2V_OK;
 }
 extern "C" int h2v_check_pairs_rlc_device(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status,
                                           h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts) {
-    if (!p) return fail(H2V_E_ARG, "null argument: plan");
-    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
-    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
-    if (n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 pairs");
+    if (int rc = pairs_rlc_args(p, n, pairs, accept)) return rc;
     if (n == 0) return H2V_OK;
     if (!ws) return fail(H2V_E_ARG, "the RLC entry points need a workspace (results of the batch check live in it)");
-    h2v_workspace *tmp = nullptr;
-    if (int rc = pairs_common(p, n, ws, stream, true, &tmp)) return rc;
-    uint32_t seed[8];
-    if (int rc = rlc_seed(opts, seed)) return rc;
-    return pairs_rlc_enqueue(p, n, pairs, accept, status, ws, (hipStream_t)stream, seed, false);
+    TmpWs none;
+    if (int rc = pairs_common(p, n, ws, stream, true, none)) return rc;
+    Unit u = unit_of_pairs(UnitKind::PAIR_RLC, p, n, pairs, accept, status);
+    if (int rc = rlc_seed(opts, u.seed)) return rc;
+    return run_call(u, ws, (hipStream_t)stream);
 }
 extern "C" int h2v_check_pairs_rlc(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws,
                                    const h2v_rlc_opts *opts, int *fell_back) {
-    if (!p) return fail(H2V_E_ARG, "null argument: plan");
-    if (!pairs) return fail(H2V_E_ARG, "null argument: pairs");
-    if (!accept) return fail(H2V_E_ARG, "null argument: accept");
-    if (n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 pairs");
+    if (int rc = pairs_rlc_args(p, n, pairs, accept)) return rc;
     if (fell_back) *fell_back = 0;
     if (n == 0) return H2V_OK;
-    h2v_workspace *tmp = nullptr;
-    if (int rc = pairs_common(p, n, ws, nullptr, false, &tmp)) return rc;
-    if (tmp) ws = tmp;
-    uint32_t seed[8];
-    int rc = rlc_seed(opts, seed);
-    if (rc == H2V_OK) rc = host_stream(ws);
-    if (rc == H2V_OK) rc = hp_ensure(ws, n);
-    if (rc == H2V_OK) {
-        uint8_t *d_pairs = ws->hp_buf, *d_accept = ws->hp_buf + (size_t)n * 100;
-        uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
-        uint32_t failed = 0;
-        if (hipMemcpyAsync(d_pairs, pairs, (size_t)n * 96, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the pairs failed");
-        if (rc == H2V_OK) rc = pairs_rlc_enqueue(p, n, d_pairs, d_accept, d_status, ws, ws->hs, seed, true);
-        if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
-        if (rc == H2V_OK && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
-        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "pair check kernels failed");
-        if (rc) rc = drain_after_error(ws, rc);
-        else if (fell_back) *fell_back = failed ? 1 : 0;
-    }
-    if (tmp) h2v_workspace_free(tmp);
-    return rc;
+    return check_pairs_host(Unit{UnitKind::PAIR_RLC, p, (uint32_t)n}, pairs, accept, status, ws, opts, fell_back);
 }
 // ---------------------------------------------------------------------------------------------- mixed-key batches
 // h2v_verify_mixed(_device): n proofs of SEVERAL plans on one SRS in one call.  Behind the per-proof MSM a proof of any key is a
 // pair (L, R) with e(L, s_g2) == e(R, G2), and the pairing sees nothing of the key but the SRS; so the call runs
 //   1. the partition (h2v_mixed.hpp, host) and k_mixed_gather: the proofs of each plan side by side in the workspace's staging;
-//   2. per plan, the pipeline up to the pairing (run_pipeline with MixedOut) - on a laned workspace the sub-batches of all plans
+//   2. per plan, the pipeline up to the pairing (MIXED_SUB units) - on a laned workspace the sub-batches of all plans
 //      go round robin through the lanes and are in flight together;
 //   3. ONE tail over the pool of pairs, which k_mixed_pairs filled in the CALLER's order: the per-proof pairing launch
 //      (run_check's second half), or - H2V_MIXED_RLC - the batch check over pairs (pairs_rlc_core) with the per-pair kernels
@@ -3296,47 +3279,43 @@ static int mixed_ensure(h2v_workspace *w, const h2vmixed::Partition &pt) {
     }
     return H2V_OK;
 }
-// The tail over m pairs of the pool (two-slot affine records, caller's order) on an ordinary workspace or a lane: the per-proof
-// pairing launch of run_check, or the batch check of run_pairs_rlc, both without their decoding - the pipeline made these
-// points itself.  status: the call's words (pre-pairing bits in, H2V_ST_PAIRING folded in by the pairing kernels); good: the
-// call's good_i.  Events as run_check's / run_pairs_rlc's.  fail_ctr as for run_rlc.
-static int run_mixed_tail(const h2v_plan *p, uint32_t m, const uint32_t *pool, const uint8_t *good, const uint8_t *ones, uint32_t *status, uint8_t *accept,
-                          uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], uint32_t *fail_ctr) {
-    opts_from(w);
-    struct Reset { ~Reset() { g_opts = LaunchOptions(); } } reset_opts;
+// The tail over u.n pairs of the pool (two-slot affine records, caller's order) on an ordinary workspace or a lane: the per-proof
+// pairing launch of run_check, or (MIXED_TAIL_RLC) the batch check of run_pairs_rlc, both without their decoding - the pipeline
+// made these points itself.  Events as run_check's / run_pairs_rlc's.
+static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const uint32_t m = u.n;
+    const MixedPool &mp = u.pool;
+    LaunchOptsScope opts(w);
     int rc;
     if ((rc = pair_view_ensure(w))) return rc;
-    H2vDevPlan v = p->d;
-    v.proof_len = 96; v.n_points = 2; v.n_ci = 0; v.n_pi = 0; v.ivc = 0; v.pi_point = 0; v.points = w->pair_pts;
-    if (!rlc) {
+    const H2vDevPlan v = pair_view(u.p->d, w);
+    if (u.kind == UnitKind::MIXED_TAIL) {
         CallRec &rec = rec_new(w, h2v_workspace::CHECK);
         hipEvent_t *ev = rec.ev;
         for (int q : {0, 1, 2, 3, 4}) HIPCHK(hipEventRecord(ev[q], st));
-        hipLaunchKernelGGL(k_pairs_to_jac, dim3((m + 63) / 64), dim3(64), 0, st, m, pool, w->er, (const uint32_t *)nullptr);
+        hipLaunchKernelGGL(k_pairs_to_jac, dim3((m + 63) / 64), dim3(64), 0, st, m, (const uint32_t *)mp.pool, w->er, (const uint32_t *)nullptr);
         HIPCHK(hipEventRecord(ev[5], st));
-        rec.pair = (uint8_t)launch_pairing(v, m, pool, ones, nullptr, w->er, nullptr, status, accept, nullptr, st, w->in_flight_hint);
+        rec.pair = (uint8_t)launch_pairing(v, m, mp.pool, mp.ones, nullptr, w->er, nullptr, mp.status, u.accept, nullptr, st, w->in_flight_hint);
         HIPCHK(hipEventRecord(ev[6], st));
     } else {
         if ((rc = pair_rlc_ensure(w, false))) return rc;
-        if (!fail_ctr && (rc = rlc_stats_ensure(w))) return rc;
+        if (!u.fail_ctr && (rc = rlc_stats_ensure(w))) return rc;
         RlcWs *r = w->prlc;
         CallRec &rec = rec_new(w, h2v_workspace::RLC);
         rec.no_vm = true;
         for (int q : {0, 1, 2, 3, 10}) HIPCHK(hipEventRecord(rec.ev[q], st));
-        HIPCHK(hipMemcpyAsync(r->good, good, m, hipMemcpyDeviceToDevice, st));
-        if ((rc = pairs_rlc_core(p, m, r, pool, nullptr, nullptr, true, status, accept, w, rec, st, seed, fail_ctr))) return rc;
-        const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (m + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
-        hipLaunchKernelGGL(k_pairs_to_jac, dim3((m + 63) / 64), dim3(64), 0, st, m, pool, w->er, (const uint32_t *)r->flags);
-        hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, v, m, pool, ones, (const uint8_t *)nullptr, w->er, (const uint32_t *)nullptr,
-                           status, accept, (uint32_t *)nullptr, (const uint32_t *)r->flags);
+        HIPCHK(hipMemcpyAsync(r->good, mp.good, m, hipMemcpyDeviceToDevice, st));
+        if ((rc = pairs_rlc_core(u, r, mp.pool, nullptr, nullptr, true, mp.status, w, rec, st))) return rc;
+        hipLaunchKernelGGL(k_pairs_to_jac, dim3((m + 63) / 64), dim3(64), 0, st, m, (const uint32_t *)mp.pool, w->er, (const uint32_t *)r->flags);
+        launch_pairing_behind(r->flags, v, m, mp.pool, mp.ones, nullptr, w->er, nullptr, mp.status, u.accept, st);
     }
     HIPCHK(hipGetLastError());
-    if (status_out) HIPCHK(hipMemcpyAsync(status_out, status, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
+    if (u.status) HIPCHK(hipMemcpyAsync(u.status, mp.status, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
-// host_off: the grouped proof offsets when the caller's proof_off is known on the host (the host form), else NULL
-struct MixedIn { const uint8_t *proofs; const uint64_t *proof_off; const uint8_t *inst, *ci; };
-static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const MixedIn &in, uint8_t *accept,
+// in: the call's device-resident buffers; host_off: the grouped proof offsets when the caller's proof_off is known on the host
+// (the host form), else NULL
+static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
                      uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8]) {
     const uint32_t n = pt.n;
     int rc;
@@ -3380,93 +3359,60 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     const H2vMixedTab tab = {n, (const uint64_t *)(sl.d + o_isrc), (const uint64_t *)(sl.d + o_idst), d_perm, (const uint32_t *)(sl.d + o_cap),
                              (const uint32_t *)(sl.d + o_ilen), (const uint32_t *)(sl.d + o_csrc), (const uint32_t *)(sl.d + o_cdst)};
     if (!host_off) hipLaunchKernelGGL(k_mixed_offsets, dim3(1), dim3(256), 0, st, in.proof_off, tab, d_off);
-    hipLaunchKernelGGL(k_mixed_gather, dim3((n + 3) / 4), dim3(256), 0, st, tab, in.proofs, in.proof_off, in.inst, in.ci, m->proofs, (const uint64_t *)d_off, m->inst, m->ci);
+    hipLaunchKernelGGL(k_mixed_gather, dim3((n + 3) / 4), dim3(256), 0, st, tab, in.proofs, in.proof_off, in.instances, in.committed, m->proofs, (const uint64_t *)d_off, m->inst, m->ci);
     if (hipGetLastError() != hipSuccess) return finish(fail(H2V_E_DEVICE, "launch of the gather kernels failed"));
     const h2v_plan *p0 = nullptr;          // any plan of the call: the tail reads nothing of it but the SRS's line tables
     uint32_t used_plans = 0;
     for (uint32_t k = 0; k < pt.n_plans; k++) if (pt.count[k]) { if (!p0) p0 = plans[k]; used_plans++; }
-    auto sub_in = [&](uint32_t k, uint32_t lo, const uint8_t **inst_c, const uint8_t **ci_c) {
+    const MixedPool pool = {m->pool, m->good, m->ones, m->status};
+    // plan k's sub-batch out of the grouped staging, and the tail over the whole pool
+    auto sub_unit = [&](uint32_t k) {
         const H2vDevPlan &d = plans[k]->d;
-        *inst_c = d.n_pi ? m->inst + pt.inst_base[k] + (size_t)lo * d.n_pi * 32 : nullptr;
-        *ci_c = d.n_ci ? m->ci + ((size_t)pt.ci_base[k] + lo) * 48 : nullptr;
+        Unit u{UnitKind::MIXED_SUB, plans[k], pt.count[k]};
+        u.proofs = m->proofs; u.off = d_off + pt.base[k];
+        u.inst = d.n_pi ? m->inst + pt.inst_base[k] : nullptr;
+        u.ci = d.n_ci ? m->ci + (size_t)pt.ci_base[k] * 48 : nullptr;
+        u.pos = d_perm + pt.base[k]; u.pool = pool;
+        return u;
     };
+    Unit tail{rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, n};
+    tail.pool = pool; tail.accept = accept; tail.status = status_out;
+    for (int q = 0; q < 8; q++) tail.seed[q] = seed ? seed[q] : 0;
     if (!w->n_lanes) {
         // an ordinary workspace: the sub-batches one after the other on `st`, then the tail
-        for (uint32_t k = 0; k < pt.n_plans; k++) {
-            if (!pt.count[k]) continue;
-            const uint8_t *inst_c, *ci_c;
-            sub_in(k, 0, &inst_c, &ci_c);
-            const MixedOut mo = {d_perm + pt.base[k], m->pool, m->good, m->status};
-            if ((rc = run_pipeline(plans[k]->d, pt.count[k], m->proofs, d_off + pt.base[k], inst_c, ci_c, nullptr, nullptr, w, st, nullptr, false, nullptr, nullptr, &mo)))
-                return finish(rc);
-        }
-        return finish(run_mixed_tail(p0, n, m->pool, m->good, m->ones, m->status, accept, status_out, w, st, rlc, seed, nullptr));
+        for (uint32_t k = 0; k < pt.n_plans; k++)
+            if (pt.count[k] && (rc = run_unit(sub_unit(k), w, st))) return finish(rc);
+        return finish(run_unit(tail, w, st));
     }
     // ---- laned: every plan's sub-batch in chunks through the lanes, nothing joined in between
     uint32_t total_chunks = 0;
-    for (uint32_t k = 0; k < pt.n_plans; k++) total_chunks += (pt.count[k] + w->chunk - 1) / w->chunk;
-    const uint32_t call_hint = w->hint_given ? w->in_flight_hint : (w->defer_joins || total_chunks > w->n_lanes) ? w->n_lanes : total_chunks;
-    uint32_t *fail_word = w->rec_fail ? w->rec_fail + (w->calls + used_plans) % h2v_workspace::RING : nullptr;   // the tail's record: the call's last
-    if (rlc && hipMemsetAsync(fail_word, 0, 4, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "memset failed"));
+    for (uint32_t k = 0; k < pt.n_plans; k++) total_chunks += n_chunks(pt.count[k], w->chunk);
+    // (the sub-batches of all plans are in flight together: what they may assume is the call's chunks, not one plan's)
+    const uint32_t sub_hint = call_hint(w, total_chunks > w->n_lanes, total_chunks);
+    tail.fail_ctr = w->rec_fail ? w->rec_fail + (w->calls + used_plans) % h2v_workspace::RING : nullptr;   // the tail's record: the call's last
+    if (rlc && hipMemsetAsync(tail.fail_ctr, 0, 4, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "memset failed"));
     if (hipEventRecord(w->ev_fork, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
     bool used_lane[h2v_workspace::MAXL] = {};
-    auto lane_for = [&](uint32_t L, uint32_t *l_out) -> int {
-        const uint32_t l = (uint32_t)(w->next_lane++ % L);
-        if (int rce = ensure_lane(w, l)) return rce;
-        HIPCHK(hipStreamWaitEvent(w->lane_st[l], w->ev_fork, 0));
-        *l_out = l;
-        return H2V_OK;
-    };
     for (uint32_t k = 0; k < pt.n_plans; k++) {
-        const uint32_t cnt = pt.count[k];
-        if (!cnt) continue;                                  // (a listed plan without a proof costs nothing)
-        const H2vDevPlan &d = plans[k]->d;
+        if (!pt.count[k]) continue;                                  // (a listed plan without a proof costs nothing)
         int stream_mode = 1;
-        const uint32_t L = laned_depth(w, cnt, false, &stream_mode), nch = (cnt + w->chunk - 1) / w->chunk;
-        CallRec &rec = rec_new(w, h2v_workspace::PREPARE);
-        rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = nch;
-        for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;
-        for (uint32_t c = 0; c < nch; c++) {
-            uint32_t l;
-            if ((rc = lane_for(L, &l))) return finish(rc);
-            h2v_workspace *lw = w->lane[l];
-            const uint32_t lo = c * w->chunk, mm = (cnt - lo) < w->chunk ? (cnt - lo) : w->chunk;
-            const uint8_t *inst_c, *ci_c;
-            sub_in(k, lo, &inst_c, &ci_c);
-            const MixedOut mo = {d_perm + pt.base[k] + lo, m->pool, m->good, m->status};
-            lw->one_stream_mode = stream_mode;
-            lw->in_flight_hint = call_hint;
-            if ((rc = run_pipeline(d, mm, m->proofs, d_off + pt.base[k] + lo, inst_c, ci_c, nullptr, nullptr, lw, w->lane_st[l], nullptr, false, nullptr, nullptr, &mo)))
-                return finish(rc);
-            if (hipEventRecord(w->lane_ev[l], w->lane_st[l]) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
-            w->lane_busy[l] = true; used_lane[l] = true;
-        }
+        const uint32_t L = laned_depth(w, pt.count[k], false, &stream_mode);
+        rec_laned(w, h2v_workspace::PREPARE, L, pt.count[k], w->chunk);
+        if ((rc = run_chunks(w, sub_unit(k), L, w->chunk, {sub_hint, stream_mode}, [&](uint32_t l, hipStream_t) { used_lane[l] = true; return (int)H2V_OK; })))
+            return finish(rc);
     }
     // ---- the tail: chunks of the pool in the caller's order, each behind EVERY sub-batch (any of them may hold any position)
     {
-        const uint32_t L = laned_depth(w, n, rlc, nullptr), nch = (n + w->chunk - 1) / w->chunk;
-        CallRec &rec = rec_new(w, rlc ? h2v_workspace::RLC : h2v_workspace::CHECK);
-        rec.first = (uint32_t)(w->next_lane % L); rec.mod = L; rec.chunks = nch;
-        for (uint32_t l = 0; l < w->n_lanes; l++) rec.start[l] = w->lane[l] ? w->lane[l]->calls : 0;
-        for (uint32_t c = 0; c < nch; c++) {
-            uint32_t l;
-            if ((rc = lane_for(L, &l))) return finish(rc);
-            h2v_workspace *lw = w->lane[l];
-            hipStream_t ls = w->lane_st[l];
-            for (uint32_t u = 0; u < w->n_lanes; u++)
-                if (used_lane[u] && u != l && hipStreamWaitEvent(ls, w->lane_ev[u], 0) != hipSuccess) return finish(fail(H2V_E_DEVICE, "stream wait failed"));
-            const uint32_t lo = c * w->chunk, mm = (n - lo) < w->chunk ? (n - lo) : w->chunk;
-            uint32_t sd[8];
-            for (int q = 0; q < 8; q++) sd[q] = seed ? seed[q] : 0;
-            sd[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
-            lw->in_flight_hint = w->hint_given ? w->in_flight_hint : (w->defer_joins ? w->n_lanes : (nch < L ? nch : L));
-            lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
-            if ((rc = run_mixed_tail(p0, mm, m->pool + (size_t)lo * 48, m->good + lo, m->ones, m->status + lo, accept + lo, status_out ? status_out + lo : nullptr, lw, ls,
-                                     rlc, sd, fail_word)))
-                return finish(rc);
-            if (hipEventRecord(w->lane_ev[l], ls) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
-            w->lane_busy[l] = true; used_lane[l] = true;
-        }
+        const uint32_t L = laned_depth(w, n, rlc, nullptr), nch = n_chunks(n, w->chunk);
+        rec_laned(w, rlc ? h2v_workspace::RLC : h2v_workspace::CHECK, L, n, w->chunk);
+        auto behind_subs = [&](uint32_t l, hipStream_t ls) -> int {
+            for (uint32_t q = 0; q < w->n_lanes; q++)
+                if (used_lane[q] && q != l && hipStreamWaitEvent(ls, w->lane_ev[q], 0) != hipSuccess) return fail(H2V_E_DEVICE, "stream wait failed");
+            used_lane[l] = true;
+            return H2V_OK;
+        };
+        // (a mixed call joins at its end: its tail has only its own chunks in flight unless joins are deferred)
+        if ((rc = run_chunks(w, tail, L, w->chunk, {call_hint(w, false, nch < L ? nch : L), 1}, behind_subs))) return finish(rc);
     }
     // a mixed call is a join point: its caller-stream wait happens here, deferred joins or not
     return finish(lanes_join(w, st));
@@ -3514,7 +3460,7 @@ extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_
     const bool rlc = (flags & H2V_MIXED_RLC) != 0;
     uint32_t seed[8] = {};
     if (rlc && (rc = rlc_seed(opts, seed))) return rc;
-    const MixedIn in = {b->proofs, b->proof_off, b->instances, b->committed};
+    const h2v_batch in = {b->n, b->proofs, b->proof_off, b->instances, b->committed};
     return run_mixed(plans, pt, nullptr, in, accept, status, ws, (hipStream_t)stream, rlc, seed);
 }
 // Host-buffer form: offsets | instances | committed | proofs go up in one pinned block on the workspace's own stream, the call
@@ -3579,7 +3525,7 @@ extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, 
             uint32_t *d_status = (uint32_t *)(m->d_out + up16(n));
             uint32_t failed = 0;
             if (hipMemcpyAsync(m->d_in, m->h_in, need, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the batch failed");
-            const MixedIn in = {m->d_in + o_proofs, (const uint64_t *)m->d_in, m->d_in + o_inst, m->d_in + o_ci};
+            const h2v_batch in = {n, m->d_in + o_proofs, (const uint64_t *)m->d_in, m->d_in + o_inst, m->d_in + o_ci};
             if (rc == H2V_OK) rc = run_mixed(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed);
             if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
             if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
@@ -3672,9 +3618,13 @@ extern "C" int h2v_trace(const h2v_plan *p, const uint8_t *proof, size_t proof_l
     uint64_t off[2] = {0, proof_len};
     h2v_batch b = {1, proof, off, instances, committed};
     uint8_t *d_pts96 = nullptr;
-    Staged in;
+    h2v_batch in;
     rc = stage_batch(p, &b, ws, ws->hslot[0], &in);
-    if (rc == H2V_OK) rc = run_pipeline(p->d, 1, in.proofs, in.off, in.inst, in.ci, ws->accept, nullptr, ws, ws->hs, nullptr, true);
+    if (rc == H2V_OK) {
+        Unit u = unit_of_batch(UnitKind::VERIFY, p, &in, ws->accept, nullptr);
+        u.trace = true;
+        rc = run_pipeline(u, ws, ws->hs);
+    }
     if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "trace pipeline failed");
     do {
         if (rc) break;
@@ -3943,14 +3893,14 @@ extern "C" int h2v_probe_vm(const h2v_plan *p, const h2v_batch *b, int want_trac
     h2v_workspace *ws = nullptr;
     int rc = ws_create_for(d, p->device, n, want_trace != 0, &ws);
     if (rc) return rc;
-    Staged in;
+    h2v_batch in;
     rc = stage_batch(p, b, ws, ws->hslot[0], &in);
     do {
         if (rc) break;
         const size_t sc_bytes = (size_t)n * d.n_terms * 32, tr_bytes = (size_t)n * d.n_trace * 32;
         if (hipMemsetAsync(ws->scalars, 0, sc_bytes, ws->hs) != hipSuccess || hipMemsetAsync(ws->status, 0xff, (size_t)n * 4, ws->hs) != hipSuccess ||
             (want_trace && hipMemsetAsync(ws->trace, 0, tr_bytes, ws->hs) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "hipMemsetAsync failed"); break; }
-        if ((rc = launch_vm(d, n, ws->stride, in.proofs, in.off, in.inst, in.ci, ws->regs, ws->scalars, ws->status, want_trace ? ws->trace : nullptr, ws->hs))) break;
+        if ((rc = launch_vm(d, n, ws->stride, in.proofs, in.proof_off, in.instances, in.committed, ws->regs, ws->scalars, ws->status, want_trace ? ws->trace : nullptr, ws->hs))) break;
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ws->hs) != hipSuccess) { rc = fail(H2V_E_DEVICE, "combiner kernel failed"); break; }
         if (hipMemcpy(status_out, ws->status, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(msm_scalars_out, ws->scalars, sc_bytes, hipMemcpyDeviceToHost) != hipSuccess ||

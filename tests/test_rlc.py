@@ -335,6 +335,50 @@ def test_rlc_calls_are_routed_by_the_observed_failing_group_rate(be, circuits, l
         ws.close()
 
 
+def test_a_routed_call_is_cut_into_chunks_like_any_other(be, circuits):
+    """ROUTING through more chunks than lanes: seven simple_mul proofs in chunks of 3 on 2 lanes - three chunks, the round robin
+    wraps, the last chunk is one proof, and that proof is the call's only reject (the pairing alone rejects it).  A chunk is one
+    group of the failing-group estimate, so every call reports 3 groups, 1 of them failed: the estimate a call starts with moves a
+    quarter of the way to 1/3 per call - 0, 0.083, 0.146, ... - and crosses the routing threshold of 0.10 (include/h2v.h, ROUTING)
+    before the third call.  Every call, routed or not: verdicts == the oracle's, status words zero for the accepted proofs and
+    H2V_ST_PAIRING alone for the reject, and rlc_result says that the per-proof kernels decided; the batch check's timings are
+    there exactly while the call is not routed."""
+    import torch
+    from plutus_halo2_verifier_gen_amd import synth
+    vk, td, pl, dp, ov = circuits["simple_mul"]
+    n, n_pi = 7, vk.n_public_inputs
+    good = synth.forge_batch(vk, td, n, seed=91, plan=pl, workers=1)
+    rng = random.Random(92)
+    proofs = [good.proof(i) for i in range(n)]
+    insts = [good.instances[32 * n_pi * i:32 * n_pi * (i + 1)] for i in range(n)]
+    proofs[6], insts[6] = synth.corrupt(pl, proofs[6], insts[6], "wrong_pi", rng)
+    off = [0]
+    for p_ in proofs:
+        off.append(off[-1] + len(p_))
+    want = list(ov.verify_batch(b"".join(proofs), off, b"".join(insts), None, threads=2))
+    assert want == [1] * 6 + [0]
+    dev = torch.device("cuda", 0)
+    up = lambda x: torch.frombuffer(bytearray(x), dtype=torch.uint8).to(dev)
+    d = (up(b"".join(proofs)), torch.tensor(off, dtype=torch.int64).to(dev), up(b"".join(insts)))
+    s = torch.cuda.Stream(device=dev)
+    ws = be.Workspace(dp, n, lanes=2, chunk=3)
+    routed = []
+    for _call in range(3):
+        acc = torch.full((n,), 7, dtype=torch.uint8, device=dev)
+        st = torch.full((n,), 0x7777, dtype=torch.int32, device=dev)
+        dp.verify_batch_rlc_device(n, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), None, acc.data_ptr(), st.data_ptr(), ws=ws,
+                                   stream=s.cuda_stream, seed=bytes(range(32)))
+        s.synchronize()
+        torch.cuda.synchronize()
+        assert acc.cpu().tolist() == want
+        assert st.cpu().tolist() == [0] * 6 + [be.ST_PAIRING]
+        ok, tm = ws.rlc_result()
+        assert not ok
+        routed.append(tm.total_ms == 0)
+    assert routed == [False, False, True], routed
+    ws.close()
+
+
 def test_rlc_duplicate_proofs_and_small_batches(be, circuits):
     """The same proof many times in one batch (equal points with different coefficients meet in the buckets), batches of
     1 and 2 proofs, and a recursive plan (no batch form: runs per proof behind the same entry point)."""
