@@ -15,6 +15,7 @@
 #include "h2v_kernels.hip"
 #include "h2v_mixed.hpp"
 #include "h2v_mixed_dev.hpp"
+#include "h2v_msm_shape.hpp"
 #include "h2v_plancc.hpp"
 
 static thread_local std::string g_err;
@@ -686,7 +687,6 @@ static void ws_release(h2v_workspace *w) {
     for (CallRec &r : w->rec) for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
 }
 static uint32_t vm_lds_slots(const H2vDevPlan &d);
-static uint32_t msm_max_segments(uint32_t T);
 static uint32_t msm_sum_width(const H2vDevPlan &d);
 // width: the widest MSM sum the workspace must serve (0: the plan's own, msm_sum_width)
 static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bool with_trace, h2v_workspace **out, uint32_t width = 0) {
@@ -1170,15 +1170,9 @@ static int launch_vm(const H2vDevPlan &d0, uint32_t n, uint32_t stride, const ui
     return H2V_OK;
 }
 
-// MSM launch geometry: 2 lanes per (proof, term); LDS 172 B per thread (42 limbs + the infinity flag).
-// MSM launch shape from a cost model fitted to MI355X measurements:
-//  * lanes per term: 2 = one lane per GLV half, chain of ~1250 multiplications; 1 = both halves on one accumulator,
-//    chain ~1600 but 36 % less work per proof and half the waves;
-//  * a wave alone on its SIMD runs ~1.7x faster than two sharing one (2048 proofs: 1.50 ms, 4096: 2.6 ms), and the
-//    dispatcher only spreads one wave per SIMD for 64- and 256-thread blocks (128 / 192 / 320 / 384 / 448 / 512
-//    put two waves of a block on the same SIMD: 2.5 ms where 64 / 256 take 1.5 ms at 1024 waves).
-// cost = chain x (1 if every wave can sit alone, else 1.7 x whole rounds of two waves per SIMD: the waves of a
-// launch all take the same time, so a partly filled round costs a full one).
+// MSM launch geometry: the shape model is host-only code of its own (h2v_msm_shape.hpp: lanes per term, block size, segments,
+// fixed-base split, terms per lane); this file gives it the device's SIMD count and the H2V_OPT_MSM_* options and launches
+// what it decides.  LDS: MSM_LDS_BYTES (h2v_msm.hpp, next to the reduction whose layout it is).
 static double msm_n_simd() {
     static const double v = []() {
         int dev = 0, cus = 0;
@@ -1187,158 +1181,88 @@ static double msm_n_simd() {
     }();
     return v;
 }
-// n_seg > 1: a segmented shape (h2v_kernels.hip: k_g1_msm_seg) - n_seg segments of seg_terms terms, then the fold launch
-struct MsmShape { uint32_t lpt, bs; double cost, waves; uint32_t n_seg = 1, seg_terms = 0; };
+static MsmModel msm_model() {
+    return {msm_n_simd(), g_opts.v[H2V_OPT_MSM_LANES_PER_TERM], (uint32_t)g_opts.v[H2V_OPT_MSM_BLOCK_SIZE], g_opts.v[H2V_OPT_MSM_TERMS_PER_LANE],
+            g_opts.v[H2V_OPT_MSM_FIXED_SPLIT]};
+}
 // The partial-sum buffer of segmented launches: [segment][proof][36 dwords], room for max_seg segments of the launch's proofs.
 // parts == NULL: the launch may not be segmented.
-struct SegBuf { uint32_t *parts = nullptr; uint32_t max_seg = 0; };
-// lanes_per_proof lanes of chain length `chain` per proof (of each of n_seg segments); other_waves: waves of a launch running
-// beside this one
-static void msm_try_shape(MsmShape &best, uint32_t lpt, uint32_t lpp, double chain, uint32_t n, double other_waves, uint32_t force_bs,
-                          uint32_t n_seg = 1, uint32_t seg_terms = 0) {
-    for (uint32_t cand = 64; cand <= 512; cand += 64) {
-        if (cand < lpp || (force_bs && cand != force_bs)) continue;
-        const uint32_t pb = cand / lpp;
-        const double waves = (double)n_seg * (double)((n + pb - 1) / pb) * (cand / 64), rho = (waves + other_waves) / msm_n_simd();
-        const bool spreads = cand == 64 || cand == 256;
-        const double rounds = rho > 2.0 ? (double)(uint64_t)((rho + 1.999) / 2.0) : 1.0;
-        double cost = chain * ((spreads && rho <= 1.0) ? 1.0 : 1.7 * rounds);
-        // ties: 256-thread blocks first (four waves, one per SIMD of a CU whatever the dispatcher's state: after a
-        // launch of 128-thread blocks, 1024 one-wave blocks of this kernel measured 2.47 ms instead of 1.86, 256-thread
-        // blocks 1.87), then one-wave blocks, then fewer idle lanes
-        cost *= 1.0 + (cand == 256 ? 0.0 : cand == 64 ? 0.004 : 0.01) + 0.005 * (double)(cand - pb * lpp) / cand;
-        // the fold of a segmented shape: a launch of one lane per proof, n_seg - 1 complete additions (16 multiplications of
-        // the 12-limb field each) deep.  NOT MEASURED: an estimate in the ladder's units (~60 per addition plus 40 for the
-        // launch's own gap) whose only job is to break ties towards fewer segments; sums of <= 64 terms never reach it
-        if (n_seg > 1) cost += 60.0 * (n_seg - 1) + 40.0;
-        if (cost < best.cost) { best.cost = cost; best.lpt = lpt; best.bs = cand; best.waves = waves; best.n_seg = n_seg; best.seg_terms = seg_terms; }
-    }
-}
-// Segments a sum of T terms can be cut into (0: never, T <= 64): the fewest segments that fit a block at two lanes per term
-// in a 64-thread block, ceil(T / 32), and up to two more (msm_ladder_shape).  Sizes the partial-sum buffer.
-static uint32_t msm_max_segments(uint32_t T) { return T <= 64 ? 0u : (T + 31) / 32 + 2; }
+struct SegBuf {
+    uint32_t *parts = nullptr; uint32_t max_seg = 0;
+    uint32_t room() const { return parts ? max_seg : 0u; }   // (what the shape model takes)
+};
 // the widest sum of a plan: the proof's own MSM; with recursion also acc_right + the fixed bases
 static uint32_t msm_sum_width(const H2vDevPlan &d) {
     const uint32_t f = d.ivc && d.n_terms > d.n_main_terms + 1 ? d.n_terms - d.n_main_terms - 1 : 0;
     return d.n_main_terms > f ? d.n_main_terms : f;
 }
-// Shapes whose LPT x T lanes fit one block (cost 1e300: none under the forced options)
-static MsmShape msm_ladder_fit(uint32_t n_terms, uint32_t n, double other_waves, bool quad_ok) {
-    const int env_lpt = g_opts.v[H2V_OPT_MSM_LANES_PER_TERM];
-    const uint32_t env_bs = (uint32_t)g_opts.v[H2V_OPT_MSM_BLOCK_SIZE];
-    MsmShape best = {2, 512, 1e300, 0};
-    for (uint32_t cl = 2; cl >= 1; cl--) {
-        if (env_lpt && (uint32_t)env_lpt != cl) continue;
-        msm_try_shape(best, cl, cl * n_terms, cl == 2 ? 1250.0 : 1600.0, n, other_waves, env_bs);
-    }
-    // a quad per GLV half (h2v_kernels.hip: msm_body, LPT = 8)
-    // Only on request (H2V_OPT_MSM_LANES_PER_TERM = 8): alone it shortens a T = 16 launch of 64-512 proofs from 1.35 to 1.17-1.27 ms, but it issues
-    // four times the instructions, and with four steps in flight - how small batches are run for throughput - the step got
-    // slower at 64 and 512 proofs (1.30 -> 1.40, 1.66 -> 1.90 ms) and faster only at 256 (1.57 -> 1.47).
-    if (quad_ok && 8 * n_terms <= 512 && env_lpt == 8) {
-        MsmShape q = {8, 512, 1e300, 0};
-        msm_try_shape(q, 8, 8 * n_terms, 1080.0, n, other_waves, env_bs);
-        if (q.cost < 1e300) best = q;
-    }
-    return best;
+// The one-group range of a term table: terms [term_base, term_base + n_terms), their scalars from column col_base on of
+// scal_stride per proof, summed into `out`.  pt_tab: the per-proof window tables, or NULL (every lane builds its own).
+static H2vMsmArgs msm_args(const H2vDevPlan &d, uint32_t term_base, uint32_t n_terms, uint32_t scal_stride, uint32_t col_base, uint32_t slots,
+                           uint32_t *out, const uint32_t *pt_tab) {
+    H2vMsmArgs a = {};
+    a.terms = d.terms; a.term_base = term_base; a.n_terms = n_terms; a.scal_stride = scal_stride; a.scal_col_base = col_base; a.slots = slots;
+    a.grp_end[0] = a.grp_end[1] = a.grp_end[2] = n_terms;
+    a.out[0] = out;
+    a.pt_tab = pt_tab; a.vk_tab = d.vk_tab;
+    return a;
 }
-// seg.parts != NULL: sums of more than 64 terms may also be segmented - when no shape fits one block (forced options included:
-// a forced LPT 8 segments at two lanes per term), or when the cost model prefers it.  Per (LPT, block size) it prices the fewest
-// segments that fit and the next two (fuller blocks), all waves of all segments plus the fold.  Sums of at most 64 terms are
-// never segmented: they keep the shape they always had, a forced shape that does not fit included (the widest block, which
-// holds 2 x 64 lanes).  bs == 0: nothing fits and the sum may not be segmented (the launchers then launch nothing and report 0).
-static MsmShape msm_ladder_shape(uint32_t n_terms, uint32_t n, double other_waves, bool quad_ok = false, const SegBuf &seg = SegBuf()) {
-    MsmShape best = msm_ladder_fit(n_terms, n, other_waves, quad_ok);
-    if (seg.parts && n_terms > 64) {
-        const int env_lpt = g_opts.v[H2V_OPT_MSM_LANES_PER_TERM];
-        const uint32_t env_bs = (uint32_t)g_opts.v[H2V_OPT_MSM_BLOCK_SIZE];
-        for (uint32_t cl = 2; cl >= 1; cl--) {
-            if (env_lpt && (env_lpt == 8 ? cl != 2 : (uint32_t)env_lpt != cl)) continue;
-            for (uint32_t cand = 64; cand <= 512; cand += 64) {
-                if (env_bs && cand != env_bs) continue;
-                const uint32_t per = cand / cl, s0 = (n_terms + per - 1) / per;
-                for (uint32_t S = s0 < 2 ? 2 : s0; S <= s0 + 2; S++) {
-                    const uint32_t ts = (n_terms + S - 1) / S, s_real = (n_terms + ts - 1) / ts;
-                    if (s_real > seg.max_seg) continue;
-                    msm_try_shape(best, cl, cl * ts, cl == 2 ? 1250.0 : 1600.0, n, other_waves, cand, s_real, ts);
-                }
-            }
-        }
-    }
-    if (best.cost == 1e300) {
-        if (2 * n_terms <= 512) {   // forced shape that does not fit: fall back to the widest block (it fits)
-            const uint32_t pb = 512 / (2 * n_terms);
-            best.lpt = 2; best.bs = 512; best.waves = (double)((n + pb - 1) / pb) * 8;
-        } else {
-            best.bs = 0;
-        }
-    }
-    return best;
+// ... of the plan's VK-base terms through the all-window tables, k bases per lane (k_g1_msm_fixed)
+static H2vMsmArgs msm_fixed_args(const H2vDevPlan &d, uint32_t scal_stride, uint32_t col_base, uint32_t *out, const uint32_t *pt_tab, uint32_t k) {
+    H2vMsmArgs a = msm_args(d, d.n_var, d.n_fix, scal_stride, col_base, H2V_SLOTS(d), out, pt_tab);
+    a.fix_tab = d.fix_tab; a.fix_k = k; a.n_fixl = (d.n_fix + k - 1) / k;
+    return a;
 }
-// the segmented form of a one-group range (MsmShape.n_seg > 1): S segments per blockIdx.y into seg.parts, then the fold into
-// ma.out[0] on the same stream
-static uint32_t launch_msm_segments(const H2vDevPlan &d, const H2vMsmArgs &ma, uint32_t n, const MsmShape &sh, const uint32_t *scalars,
-                                    const uint32_t *pts, uint32_t *tabws, hipStream_t st, const SegBuf &seg) {
-    if (!seg.parts || sh.n_seg > seg.max_seg || !ma.pt_tab || ma.grp_end[0] != ma.n_terms || sh.lpt > 2) return 0;
-    const uint32_t lpp = sh.lpt * sh.seg_terms, per_block = sh.bs / lpp;
-    if (per_block == 0 || (uint64_t)sh.seg_terms * (sh.n_seg - 1) >= ma.n_terms) return 0;
-    const uint32_t blocks = (n + per_block - 1) / per_block;
-    if (ma.skip) {
-        const uint32_t cg = (uint32_t)(msm_n_simd() / 4.0), per_seg = (cg + sh.n_seg - 1) / sh.n_seg, blocks_c = blocks < per_seg ? blocks : per_seg;
-        if (sh.lpt == 1) hipLaunchKernelGGL(k_g1_msm_merged_cond_seg, dim3(blocks_c, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
-        else hipLaunchKernelGGL(k_g1_msm_cond_seg, dim3(blocks_c, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
-    } else if (sh.lpt == 1) {
-        hipLaunchKernelGGL(k_g1_msm_merged_seg, dim3(blocks, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
-    } else {
-        hipLaunchKernelGGL(k_g1_msm_seg, dim3(blocks, sh.n_seg), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
-    }
-    hipLaunchKernelGGL(k_g1_sum_segments, dim3((n + 63) / 64), dim3(64), 0, st, n, sh.n_seg, (const uint32_t *)seg.parts, ma.out[0], ma.skip);
-    return sh.lpt;
+static void launch_msm_fixed(const H2vDevPlan &d, const H2vMsmArgs &mf, uint32_t n, uint32_t bs, const uint32_t *scalars, const uint32_t *pts, hipStream_t st) {
+    const uint32_t pbf = bs / mf.n_fixl;
+    hipLaunchKernelGGL(k_g1_msm_fixed, dim3((n + pbf - 1) / pbf), dim3(bs), MSM_LDS_BYTES(bs), st, d, mf, n, pbf, scalars, pts, (uint32_t *)nullptr);
 }
+// the eight ladder entry points (h2v_msm.hpp: msm_ladder_entry, MSM_COND_BODY); the unsegmented ones take no (seg_terms, parts)
+typedef void (*MsmLadderKernel)(H2vDevPlan, H2vMsmArgs, uint32_t, uint32_t, const uint32_t *, const uint32_t *, uint32_t *);
+typedef void (*MsmSegKernel)(H2vDevPlan, H2vMsmArgs, uint32_t, uint32_t, uint32_t, uint32_t *, const uint32_t *, const uint32_t *, uint32_t *);
+static MsmLadderKernel msm_ladder_kernel(uint32_t lpt, bool cond) {
+    static const MsmLadderKernel tab[2][2] = {{k_g1_msm, k_g1_msm_cond}, {k_g1_msm_merged, k_g1_msm_merged_cond}};
+    return lpt == 8 && !cond ? k_g1_msm_quad : tab[lpt == 1][cond];   // (the quad has no conditional form; its shape is never chosen for a launch with ma.skip)
+}
+static MsmSegKernel msm_seg_kernel(uint32_t lpt, bool cond) {
+    static const MsmSegKernel tab[2][2] = {{k_g1_msm_seg, k_g1_msm_cond_seg}, {k_g1_msm_merged_seg, k_g1_msm_merged_cond_seg}};
+    return tab[lpt == 1][cond];
+}
+// The ladder launch of a range in the shape `sh`.  The segmented form of a one-group range (sh.n_seg > 1): one segment per
+// blockIdx.y into seg.parts, then the fold into ma.out[0] on the same stream.  ma.skip (fall-back of the RLC batch mode): a grid
+// of at most one block per CU - over all segments - walks the logical blocks.
 // returns the lanes per term launched, 0 if nothing was launched (no shape fits: see msm_ladder_shape)
 static uint32_t launch_msm_ladders(const H2vDevPlan &d, const H2vMsmArgs &ma, uint32_t n, const MsmShape &sh, const uint32_t *scalars,
                                    const uint32_t *pts, uint32_t *tabws, hipStream_t st, const SegBuf &seg = SegBuf()) {
-    if (sh.n_seg > 1) return launch_msm_segments(d, ma, n, sh, scalars, pts, tabws, st, seg);
-    const uint32_t lpp = sh.lpt * ma.n_terms;
-    if (sh.bs == 0 || lpp > sh.bs) return 0;
-    const uint32_t per_block = sh.bs / lpp;
-    const uint32_t blocks = (n + per_block - 1) / per_block;
-    if (ma.skip) {   // fall-back of the RLC batch mode: a grid of at most one block per CU walks the logical blocks
-        const uint32_t cg = (uint32_t)(msm_n_simd() / 4.0), blocks_c = blocks < cg ? blocks : cg;
-        if (sh.lpt == 1) hipLaunchKernelGGL(k_g1_msm_merged_cond, dim3(blocks_c), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, scalars, pts, tabws);
-        else hipLaunchKernelGGL(k_g1_msm_cond, dim3(blocks_c), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, scalars, pts, tabws);
-    } else if (sh.lpt == 8) hipLaunchKernelGGL(k_g1_msm_quad, dim3(blocks), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, scalars, pts, tabws);
-    else if (sh.lpt == 1) hipLaunchKernelGGL(k_g1_msm_merged, dim3(blocks), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, scalars, pts, tabws);
-    else hipLaunchKernelGGL(k_g1_msm, dim3(blocks), dim3(sh.bs), (size_t)sh.bs * 172, st, d, ma, n, per_block, scalars, pts, tabws);
+    const bool segmented = sh.n_seg > 1;
+    if (segmented) {
+        if (!seg.parts || sh.n_seg > seg.max_seg || !ma.pt_tab || ma.grp_end[0] != ma.n_terms || sh.lpt > 2) return 0;
+        if (sh.bs < sh.lpt * sh.seg_terms || (uint64_t)sh.seg_terms * (sh.n_seg - 1) >= ma.n_terms) return 0;
+    } else if (sh.bs == 0 || sh.lpt * ma.n_terms > sh.bs) {
+        return 0;
+    }
+    const uint32_t per_block = sh.bs / (sh.lpt * (segmented ? sh.seg_terms : ma.n_terms));
+    const uint32_t blocks = (n + per_block - 1) / per_block, cg = ((uint32_t)(msm_n_simd() / 4.0) + sh.n_seg - 1) / sh.n_seg;
+    const dim3 grid(ma.skip && cg < blocks ? cg : blocks, sh.n_seg);
+    if (segmented) {
+        hipLaunchKernelGGL(msm_seg_kernel(sh.lpt, ma.skip != nullptr), grid, dim3(sh.bs), MSM_LDS_BYTES(sh.bs), st, d, ma, n, per_block, sh.seg_terms, seg.parts, scalars, pts, tabws);
+        hipLaunchKernelGGL(k_g1_sum_segments, dim3((n + 63) / 64), dim3(64), 0, st, n, sh.n_seg, (const uint32_t *)seg.parts, ma.out[0], ma.skip);
+    } else {
+        hipLaunchKernelGGL(msm_ladder_kernel(sh.lpt, ma.skip != nullptr), grid, dim3(sh.bs), MSM_LDS_BYTES(sh.bs), st, d, ma, n, per_block, scalars, pts, tabws);
+    }
     return sh.lpt;
-}
-// H2V_OPT_MSM_TERMS_PER_LANE = 2 .. 4: k_g1_msm_multi (several terms per lane share the doublings: less work, fewer and longer waves;
-// for callers that keep several batches in flight).  Single-group launches with prebuilt tables only.
-// Without the option the caller's hint decides (h2v_workspace_hint_in_flight): a caller that keeps >= 4 batches in flight is
-// bound by the instructions issued, not by chain length, and two terms per lane issue 26 % fewer multiply-adds per proof
-// (measured, simple_mul x 4096: 5 in flight 5.12 -> 4.66 ms per step; with 3 in flight 5.04 -> 5.01).
-// Terms per lane of the ladder kernel for callers that keep the chip full: more terms per lane share more doublings and make
-// fewer, longer waves - as many as still leave the launch a quarter of a wave per SIMD (two at least).  ms per batch, eight
-// batches in flight, terms per lane 2 / 3 / 4: simple_mul x 4096 (10 terms: 320 / 256 / 192 waves) 3.73 / 3.64 / 3.84;
-// lookup_table x 2048 (25 terms: 416 / 288 / 224) 3.42 / 3.36 / -; x 4096 6.82 / 6.71 / 6.59; atms x 2048 (20 terms: 320 / 224 /
-// 160) 3.55 / 3.72 / 4.05; sha256 shape in chunks of 1024 (25 terms: 208 / 144) 2.26 / 2.35.
-static int msm_terms_per_lane(uint32_t in_flight_hint, uint32_t n = 0, uint32_t n_terms = 0) {
-    if (g_opts.v[H2V_OPT_MSM_TERMS_PER_LANE] >= 1) return g_opts.v[H2V_OPT_MSM_TERMS_PER_LANE];
-    if (in_flight_hint < 4) return 1;
-    for (int t = 4; t > 2; t--)
-        if ((double)n * ((n_terms + t - 1) / t) / 64.0 >= msm_n_simd() / 4.0) return t;
-    return 2;
 }
 static uint32_t launch_msm_range(const H2vDevPlan &d, const H2vMsmArgs &ma, uint32_t n, const uint32_t *scalars, const uint32_t *pts,
                                  uint32_t *tabws, hipStream_t st, uint32_t in_flight_hint = 1, const SegBuf &seg = SegBuf()) {
-    const int tpl = msm_terms_per_lane(in_flight_hint, n, ma.n_terms);
+    const MsmModel m = msm_model();
+    const int tpl = msm_terms_per_lane(m, in_flight_hint, n, ma.n_terms);
     // (only launches of at least a quarter of a wave per SIMD at one lane per term: below that the launch is a chain of lone
     //  waves whatever else is in flight, and the two-lanes-per-term ladder is the shortest chain - sha256 shape x 128 with six
     //  shares in flight: MSM 2.5 ms -> 1.4 ms alone)
     // (eight or more batches in flight: from an eighth - sha256 / secp256k1 shape x 256, sixteen shares in flight: 1.05 / 1.08 ->
     //  0.89 / 0.91 ms per share with two terms per lane; x 128 and x 64 stay with the shortest chain: 0.66 -> 0.74, 0.54 -> 0.64)
     const bool fills = (double)n * ma.n_terms / 64.0 >= msm_n_simd() / (in_flight_hint >= 8 ? 8.0 : 4.0);
-    const bool tpl_forced = g_opts.v[H2V_OPT_MSM_TERMS_PER_LANE] > 0;
+    const bool tpl_forced = m.terms_per_lane > 0;
     if (tpl > 1 && (fills || tpl_forced) && ma.pt_tab && !ma.skip && ma.grp_end[0] == ma.n_terms && ma.n_terms >= (uint32_t)tpl && ma.n_terms <= 256u * tpl) {
         // lanes per proof as for `tpl` whole terms per lane, then the proof's 2 T GLV halves dealt out evenly over them: ten terms
         // on four lanes are 5 + 5 + 5 + 5 halves, not 6 + 6 + 6 + 2 (a forced tpl keeps its 2 tpl halves per lane)
@@ -1346,47 +1270,12 @@ static uint32_t launch_msm_range(const H2vDevPlan &d, const H2vMsmArgs &ma, uint
         const uint32_t hpl = tpl_forced ? 2u * (uint32_t)tpl : (2 * ma.n_terms + lpp0 - 1) / lpp0;
         const uint32_t lpp = (2 * ma.n_terms + hpl - 1) / hpl;
         const uint32_t per_block = bs / lpp, blocks = (n + per_block - 1) / per_block;
-        hipLaunchKernelGGL(k_g1_msm_multi, dim3(blocks), dim3(bs), (size_t)bs * 172, st, d, ma, n, per_block, hpl, scalars, pts, tabws);
+        hipLaunchKernelGGL(k_g1_msm_multi, dim3(blocks), dim3(bs), MSM_LDS_BYTES(bs), st, d, ma, n, per_block, hpl, scalars, pts, tabws);
         return 16 + (hpl + 1) / 2;   // reported as msm_lanes_per_term: 18 / 19 / 20 = up to two / three / four terms' halves per lane
     }
     // (segments: one-group ranges with prebuilt window tables only)
     const SegBuf sg = ma.pt_tab && ma.grp_end[0] == ma.n_terms ? seg : SegBuf();
-    return launch_msm_ladders(d, ma, n, msm_ladder_shape(ma.n_terms, n, 0.0, ma.pt_tab != nullptr && !ma.skip, sg), scalars, pts, tabws, st, sg);
-}
-// Fixed-base split of the plan's own MSM (non-recursive plans, tables present): the per-proof terms [0, n_var) as ladders
-// and, beside them on another stream, the VK-base terms as one lane per term that walks the all-window table of its base
-// (65 mixed additions, no doubling: 0.88 ms alone).  Measured (2048 proofs): T = 50 with 30 VK bases 3.37 -> 2.52 ms,
-// T = 34 with 9 VK bases 3.42 -> 2.68 ms; but where the single launch already has every SIMD to itself the split is
-// slower (simple_mul x 4096: 1.87 -> 2.50 ms, sha256 shape x 1024: 1.99 -> 2.56 ms) - waves of two concurrent launches
-// pair up on SIMDs even when there would be room for all of them alone.  So the rule is: split (one base per lane) only
-// when the single launch cannot have one wave per SIMD and most terms are VK bases.  H2V_OPT_MSM_FIXED_SPLIT = k forces a split with k bases per lane, -1 forbids it.
-struct MsmSplit { bool on; MsmShape var, fix; uint32_t k; };
-static MsmSplit msm_split_shape(const H2vDevPlan &d, uint32_t n, const MsmShape &single, uint32_t in_flight_hint = 1, const SegBuf &seg = SegBuf()) {
-    const int opt_fix = g_opts.v[H2V_OPT_MSM_FIXED_SPLIT];                  // 0 auto, 1 .. 4 bases per lane, -1 never
-    const int env_fix = opt_fix == 0 ? -1 : opt_fix < 0 ? 0 : opt_fix;       // (-1 auto, 0 never, k forced: the form the rule below is written in)
-    const uint32_t env_bs = (uint32_t)g_opts.v[H2V_OPT_MSM_BLOCK_SIZE];
-    MsmSplit out = {false, {}, {}, 0};
-    if (!d.fix_tab || !d.n_fix || !d.n_var || d.ivc || env_fix == 0) return out;
-    // (and only when the VK bases are the majority of the terms: with 9 of 34 the MSM gained 0.8 ms and the pairing kernel
-    // that followed the three launches lost as much of its own placement; with 6 of 16 at 8192 proofs the split was slower)
-    // A caller that keeps the chip full (hint >= 4: the lanes) is bound by the instructions issued: the VK-base terms then
-    // ALWAYS go through the all-window tables, two bases per lane (65 mixed additions each and no doubling, where a ladder
-    // lane shares 128 doublings between two terms) - measured with six batches in flight, ms per batch: simple_mul x 4096
-    // 4.39 -> 4.30, sha256 shape x 1024 2.67 -> 2.56, atms x 2048 4.43 -> 4.21, lookup_table x 2048 and secp256k1 x 512
-    // unchanged (+-1 %); launches below a quarter of a wave per SIMD keep the single ladder launch (sha256 x 128: 1.17 -> 1.26).
-    const bool in_flight = in_flight_hint >= 4 && d.n_fix >= 2 && (double)n * d.n_main_terms / 64.0 >= msm_n_simd() / 4.0;
-    if (env_fix < 0 && !in_flight && (single.waves <= msm_n_simd() || d.n_fix < d.n_var)) return out;
-    const uint32_t k = env_fix > 0 ? (uint32_t)(env_fix > 4 ? 4 : env_fix) : in_flight ? (d.n_fix >= 16 ? 4u : 2u) : 1u;   // (bases per lane: +-1 % either way)
-    const uint32_t lanes = (d.n_fix + k - 1) / k;
-    MsmShape fx = {1, 512, 1e300, 0};
-    msm_try_shape(fx, 1, lanes, k * 800.0, n, 0.0, env_bs);
-    if (fx.cost == 1e300) return out;
-    out.on = true;
-    out.k = k;
-    out.fix = fx;
-    out.var = msm_ladder_shape(d.n_var, n, fx.waves, false, seg);   // (the per-proof part may be segmented)
-    if (out.var.bs == 0) out.on = false;
-    return out;
+    return launch_msm_ladders(d, ma, n, msm_ladder_shape(m, ma.n_terms, n, 0.0, ma.pt_tab != nullptr && !ma.skip, sg.room()), scalars, pts, tabws, st, sg);
 }
 // the proof's own MSM: terms [0, n_main_terms) of the plan's table, scalars from the combiner, points from decompression.
 // A recursive plan sums acc_left and acc_right + fixed bases in the same launch (three groups, three outputs).
@@ -1396,16 +1285,14 @@ static MsmSplit msm_split_shape(const H2vDevPlan &d, uint32_t n, const MsmShape 
 // Returns the lanes per term launched - of the proof's own sum when the ranges run separately - or 0: nothing launched.
 static uint32_t launch_msm(const H2vDevPlan &d, uint32_t n, const uint32_t *scalars, const uint32_t *pts, const uint32_t *pt_tab,
                        uint32_t *er, uint32_t *accl, uint32_t *accr, hipStream_t st, uint32_t in_flight_hint = 1, const SegBuf &seg = SegBuf()) {
-    H2vMsmArgs ma = {d.terms, 0, d.n_main_terms, d.n_terms, 0, H2V_SLOTS(d), {d.n_main_terms, d.n_main_terms, d.n_main_terms}, {er, nullptr, nullptr},
-                     pt_tab, d.vk_tab, nullptr, 0, 0};
+    H2vMsmArgs ma = msm_args(d, 0, d.n_main_terms, d.n_terms, 0, H2V_SLOTS(d), er, pt_tab);
     if (d.ivc) {
-        if (msm_sum_width(d) > 64 && msm_ladder_fit(d.n_terms, n, 0.0, pt_tab != nullptr).cost == 1e300) {
+        if (msm_sum_width(d) > 64 && msm_ladder_fit(msm_model(), d.n_terms, n, 0.0, pt_tab != nullptr).cost == 1e300) {
             const uint32_t m = d.n_main_terms;
             const H2vMsmArgs ranges[3] = {
                 ma,
-                {d.terms, m, 1, d.n_terms, m, H2V_SLOTS(d), {1, 1, 1}, {accl, nullptr, nullptr}, pt_tab, d.vk_tab, nullptr, 0, 0},
-                {d.terms, m + 1, d.n_terms - m - 1, d.n_terms, m + 1, H2V_SLOTS(d), {d.n_terms - m - 1, d.n_terms - m - 1, d.n_terms - m - 1},
-                 {accr, nullptr, nullptr}, pt_tab, d.vk_tab, nullptr, 0, 0}};
+                msm_args(d, m, 1, d.n_terms, m, H2V_SLOTS(d), accl, pt_tab),
+                msm_args(d, m + 1, d.n_terms - m - 1, d.n_terms, m + 1, H2V_SLOTS(d), accr, pt_tab)};
             uint32_t code = 0;
             for (const H2vMsmArgs &r : ranges) {
                 const uint32_t c = launch_msm_range(d, r, n, scalars, pts, nullptr, st, in_flight_hint, seg);
@@ -1427,7 +1314,9 @@ struct IvcBufs { uint32_t *accl, *accr, *fold_pts, *fold_scal, *el2, *er2; };
 static void launch_ivc_fold(const H2vDevPlan &d, uint32_t n, const uint32_t *pts, const uint32_t *er,
                             const IvcBufs &b, uint32_t *tabws, hipStream_t st) {
     hipLaunchKernelGGL(k_ivc_challenge, dim3((n + 63) / 64), dim3(64), 0, st, d, n, pts, er, b.accl, b.accr, b.fold_pts, b.fold_scal);
-    const H2vMsmArgs fold = {d.fold_terms, 0, 4, 4, 0, 4, {2, 4, 4}, {b.el2, b.er2, nullptr}, nullptr, nullptr, nullptr, 0, 0};
+    H2vMsmArgs fold = msm_args(d, 0, 4, 4, 0, 4, b.el2, nullptr);   // two groups of two terms over the fold's own table
+    fold.terms = d.fold_terms; fold.vk_tab = nullptr;
+    fold.grp_end[0] = 2; fold.out[1] = b.er2;
     launch_msm_range(d, fold, n, b.fold_scal, b.fold_pts, tabws, st);
 }
 // Pairing kernel selection: the cooperative 16-lanes-per-proof kernel is the product path; the one-lane-per-proof
@@ -1642,24 +1531,24 @@ static int run_pipeline(const Unit &u, h2v_workspace *w, hipStream_t st) {
     HIPCHK(hipStreamWaitEvent(pm, w->ev_hold, 0));
     HIPCHK(hipEventRecord(ev[4], pm));
     const SegBuf seg = {w->msm_parts, w->sz_segs};   // (NULL for workspaces of plans whose sums are all <= 64 terms)
-    const MsmShape single = msm_ladder_shape(d.ivc ? d.n_terms : d.n_main_terms, n, 0.0, true, d.ivc ? SegBuf() : seg);
-    const MsmSplit split = w->er_fix ? msm_split_shape(d, n, single, w->in_flight_hint, seg) : MsmSplit{false, {}, {}, 0};
+    const MsmModel mm = msm_model();
+    const MsmShape single = msm_ladder_shape(mm, d.ivc ? d.n_terms : d.n_main_terms, n, 0.0, true, d.ivc ? 0u : seg.room());
+    const MsmSplit split = w->er_fix && d.fix_tab && !d.ivc ? msm_split_shape(mm, MsmSplitTerms{d.n_var, d.n_fix, d.n_main_terms}, n, single, w->in_flight_hint, seg.room())
+                                                            : MsmSplit{false, {}, {}, 0};
     if (split.on) {
         // per-proof terms as ladders on the main stream; the VK-base terms beside them on the side stream (free since
         // the square roots finished), which first waits for the combiner's scalars; a one-lane-per-proof kernel adds
         // the two sums
-        H2vMsmArgs mv = {d.terms, 0, d.n_var, d.n_terms, 0, slots, {d.n_var, d.n_var, d.n_var}, {w->er, nullptr, nullptr}, w->pt_tab, d.vk_tab, nullptr, 0, 0};
-        H2vMsmArgs mf = {d.terms, d.n_var, d.n_fix, d.n_terms, d.n_var, slots, {d.n_fix, d.n_fix, d.n_fix}, {w->er_fix, nullptr, nullptr}, w->pt_tab, d.vk_tab,
-                         d.fix_tab, split.k, (d.n_fix + split.k - 1) / split.k};
+        const H2vMsmArgs mv = msm_args(d, 0, d.n_var, d.n_terms, 0, slots, w->er, w->pt_tab);
+        const H2vMsmArgs mf = msm_fixed_args(d, d.n_terms, d.n_var, w->er_fix, w->pt_tab, split.k);
         HIPCHK(hipStreamWaitEvent(ps, ev[1], 0));
-        const uint32_t pbf = split.fix.bs / mf.n_fixl;
         HIPCHK(hipEventRecord(ev[7], ps));
-        hipLaunchKernelGGL(k_g1_msm_fixed, dim3((n + pbf - 1) / pbf), dim3(split.fix.bs), (size_t)split.fix.bs * 172, ps, d, mf, n, pbf, w->scalars, w->pts, (uint32_t *)nullptr);
+        launch_msm_fixed(d, mf, n, split.fix.bs, w->scalars, w->pts, ps);
         HIPCHK(hipEventRecord(ev[8], ps));
         HIPCHK(hipEventRecord(w->ev_fix, ps));
         if (ps == pm) HIPCHK(hipEventRecord(ev[4], pm));   // (one stream: the ladder launch starts behind the fixed-base one)
         uint32_t var_code;
-        if (msm_terms_per_lane(w->in_flight_hint) > 1) var_code = launch_msm_range(d, mv, n, w->scalars, w->pts, nullptr, pm, w->in_flight_hint, seg);   // (several terms per lane)
+        if (msm_terms_per_lane(mm, w->in_flight_hint) > 1) var_code = launch_msm_range(d, mv, n, w->scalars, w->pts, nullptr, pm, w->in_flight_hint, seg);   // (several terms per lane)
         else var_code = launch_msm_ladders(d, mv, n, split.var, w->scalars, w->pts, nullptr, pm, seg);
         if (!var_code) return fail(H2V_E_LIMIT, "internal: no MSM launch shape for the per-proof terms");
         HIPCHK(hipEventRecord(ev[9], pm));
@@ -3044,8 +2933,8 @@ static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
         hipLaunchKernelGGL(k_build_tables, dim3(nb < 4 * cond_grid ? nb : 4 * cond_grid), dim3(64), 0, pm, n * slots, w->pts, w->valid, w->pt_tab, skip, slots);
     }
     {
-        H2vMsmArgs ma = {d.terms, 0, d.n_main_terms, d.n_terms, 0, slots, {d.n_main_terms, d.n_main_terms, d.n_main_terms}, {w->er, nullptr, nullptr},
-                         w->pt_tab, d.vk_tab, nullptr, 0, 0, skip};
+        H2vMsmArgs ma = msm_args(d, 0, d.n_main_terms, d.n_terms, 0, slots, w->er, w->pt_tab);
+        ma.skip = skip;
         if (!launch_msm_range(d, ma, n, w->scalars, w->pts, nullptr, pm, 1, SegBuf{w->msm_parts, w->sz_segs}))
             return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
     }
@@ -3834,12 +3723,10 @@ extern "C" int h2v_probe_g1_msm_fixed(const h2v_plan *p, uint32_t n, uint32_t k,
     DevBuf dsc, der, dout;
     if (dsc.alloc((size_t)n * d.n_fix * 32) || der.alloc((size_t)n * 144) || dout.alloc((size_t)n * 96)) return fail(H2V_E_DEVICE, "hipMalloc failed");
     HIPCHK(hipMemcpy(dsc.p, scalars, (size_t)n * d.n_fix * 32, hipMemcpyHostToDevice));
-    H2vMsmArgs mf = {d.terms, d.n_var, d.n_fix, d.n_fix, 0, (uint32_t)H2V_SLOTS(d), {d.n_fix, d.n_fix, d.n_fix}, {der.as<uint32_t>(), nullptr, nullptr}, nullptr, d.vk_tab,
-                     d.fix_tab, k, (d.n_fix + k - 1) / k};
+    const H2vMsmArgs mf = msm_fixed_args(d, d.n_fix, 0, der.as<uint32_t>(), nullptr, k);
     const uint32_t bs = mf.n_fixl <= 64 ? 64u : mf.n_fixl <= 256 ? 256u : 512u;
     if (mf.n_fixl > bs) return fail(H2V_E_LIMIT, "too many VK bases for one block");
-    const uint32_t pbf = bs / mf.n_fixl;
-    hipLaunchKernelGGL(k_g1_msm_fixed, dim3((n + pbf - 1) / pbf), dim3(bs), (size_t)bs * 172, nullptr, d, mf, n, pbf, dsc.as<uint32_t>(), (const uint32_t *)nullptr, (uint32_t *)nullptr);
+    launch_msm_fixed(d, mf, n, bs, dsc.as<uint32_t>(), nullptr, nullptr);
     hipLaunchKernelGGL(k_export_points, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, 1, der.as<uint32_t>(), dout.as<uint8_t>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());

@@ -234,6 +234,48 @@ def test_rlc_fall_back_with_passing_and_failing_groups(be, wide):  # noqa: F811
         ws.close()
 
 
+def _with_one_reject(pl, clean, n_pi, k, seed):
+    from plutus_halo2_verifier_gen_amd import synth
+    p2, i2 = synth.corrupt(pl, clean.proof(k), clean.instances[32 * n_pi * k:32 * n_pi * (k + 1)], "flip_first_scalar", random.Random(seed))
+    proofs = [p2 if i == k else clean.proof(i) for i in range(clean.n)]
+    off = [0]
+    for p in proofs:
+        off.append(off[-1] + len(p))
+    return synth.Batch(n=clean.n, proofs=b"".join(proofs), proof_off=off,
+                       instances=clean.instances[:32 * n_pi * k] + i2 + clean.instances[32 * n_pi * (k + 1):],
+                       committed=clean.committed, expected=[int(i != k) for i in range(clean.n)])
+
+
+@pytest.fixture(scope="module")
+def narrow_rejects():
+    """simple_mul x 256 (four groups of 64): its device plan and three batches with one pairing-only reject each - the first
+    proof of group 2, an inner one, its last"""
+    from plutus_halo2_verifier_gen_amd import backend, plan as PL, synth, vk as V
+    vk, td = V.simple_mul_vk()
+    pl = PL.compile_plan(vk)
+    clean = synth.forge_batch(vk, td, 256, seed=37, plan=pl, workers=16)
+    return backend.DevicePlan(pl.to_bytes(), 0), [_with_one_reject(pl, clean, vk.n_public_inputs, k, 9 + k) for k in (128, 150, 191)]
+
+
+@pytest.mark.parametrize("lpt, bs", [(1, 64), (1, 256), (2, 64), (2, 256), (1, 192), (2, 192)])
+def test_rlc_fall_back_with_passing_and_failing_groups_narrow(be, narrow_rejects, lpt, bs):  # noqa: F811
+    """The narrow twin of the test above: the UNSEGMENTED conditional ladders (k_g1_msm_cond / k_g1_msm_merged_cond) with
+    passing and failing groups, under both lane forms.  simple_mul under RLC at 256 proofs, always the batch check first
+    (OPT_RLC_ROUTE = -1): the batch check fails, groups 0, 1 and 3 pass their group checks and their logical blocks are
+    skipped, group 2's other 63 proofs still need their sums.  The fall-back sums the key's 16 terms per proof in one launch:
+    2, 4, 8 or 16 proofs per block at 64 / 256 threads, which divide the groups of 64; 192-thread blocks hold 6 or 12
+    proofs, so that a block straddles each border of group 2 (skipped only when BOTH groups it touches passed)."""
+    dp, batches = narrow_rejects
+    for one in batches:
+        ws = be.Workspace(dp, one.n)
+        ws.set_option(be.OPT_RLC_ROUTE, -1)
+        ws.set_option(be.OPT_MSM_LANES_PER_TERM, lpt)
+        ws.set_option(be.OPT_MSM_BLOCK_SIZE, bs)
+        acc, fell_back = dp.verify_batch_rlc(one.proofs, one.proof_off, one.instances, one.committed, ws=ws)
+        assert fell_back and list(acc) == one.expected, one.expected.index(0)
+        ws.close()
+
+
 def test_wide_ivc_fold_and_separate_ranges(be, wide):  # noqa: F811
     """ivc_wide: F = 113 fixed bases.  At two lanes per term the three sums fill 392 lanes of one block; forcing 256-thread
     blocks makes them run as three separate ranges (segmented where they must be).  el / er after the fold equal the
