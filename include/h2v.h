@@ -403,10 +403,32 @@ int h2v_check_pairs_rlc_device(const h2v_plan *plan, uint64_t n, const uint8_t *
  *   SEED: h2v_verify_batch_rlc's rules.  ONE seed per call; the coefficient of proof i is drawn from its position in the CALL
  *   (within its chunk of the tail), never from its position within its key - with repeated coefficients two proofs of
  *   different keys could cancel each other's error.
+ *   H2V_MIXED_FOLD_MSM (only together with H2V_MIXED_RLC; alone: H2V_E_ARG): the reference's whole batch_verify - every
+ *   proof's DualMSM scaled by a random coefficient, added, ONE MSM and ONE pairing for the call.  H2V_MIXED_RLC alone folds only
+ *   the pairings: every proof still runs its own ladder MSM.  With the flag, a plan that has the batch form of
+ *   h2v_verify_batch_rlc (per-proof terms plus VK bases) runs phase 1 only and hands its terms - scalars scaled by the proof's
+ *   coefficient, COPIES of the points, the VK-base scalars summed per plan - to ONE bucket MSM over the call; any other plan (a
+ *   recursive one: its fold challenge hashes the proof's own MSM result) runs as without the flag and joins as one pair per proof.
+ *   accept[] / status[] keep the contract above.
+ *   TERM COUNT of a call: N_R = sum over the plans with the batch form that have proofs of (count_k * n_var_k + n_fix_k) + the
+ *   number of proofs of the other plans (count_k: the plan's proofs in the call; n_var_k / n_fix_k: its per-proof and VK-base
+ *   MSM terms).  N_R > 2^22 is H2V_E_LIMIT, decided on the host before anything is enqueued.  h2v_workspace_rlc_result(ws, 0, ..)
+ *   reports msm_terms = N_R and the verdict; the tail's record is the call's last, of kind RLC, and is ONE piece on a laned
+ *   workspace too (coefficients follow the position in the call, not in a chunk).
+ *   FALL-BACK: when the one check fails, per-proof verdicts are needed and phase-1 results no longer exist (the lanes recycle
+ *   them), so the HOST decides: the call downloads the verdict and synchronises `stream` ONCE - BOTH forms, the device form too,
+ *   return only after the batch verdict is known - and after a failed check runs the H2V_MIXED_RLC path on the same inputs with
+ *   the same seed; its accept[] / status[] are final, fell_back = 1, and the last record is that second pass's.  A failing call
+ *   pays the attempt plus the call without the flag; a passing call never runs a ladder.
  * WHICH SHAPE IT IS FOR: many keys with few proofs each (a node that validates proofs of many scripts) - there the per-key
- * route is one chain of lone waves per key.  It does not fold the MSMs of different keys into one bucket MSM: for a batch
- * dominated by ONE key h2v_verify_batch_rlc on that key stays the faster batch-accept form.  Measurements: DESIGN.md. */
+ * route is one chain of lone waves per key.  Without H2V_MIXED_FOLD_MSM it does not fold the MSMs of different keys into one
+ * bucket MSM: for a batch dominated by ONE key h2v_verify_batch_rlc on that key stays the faster batch-accept form.  With the
+ * flag it does, and on 16 keys x 64 proofs it is the fastest of the three routes measured (tools/bench_mixed.py --fold: 6.8 ms a
+ * call against 10.3 without the flag and 12.7 for one h2v_verify_batch_rlc call per key); on 2 keys x 2048 proofs it LOSES to the
+ * per-key h2v_verify_batch_rlc calls (7.1 against 3.3-4.8 ms), whose steps overlap in the lanes: few keys with many proofs each
+ * stay with that route.  Measurements: DESIGN.md 15 / 15.1, profiles/mixed_fold.json. */
 #define H2V_MIXED_RLC 1u          /* batch-accept: ONE pairing for the call; otherwise one pairing per proof, in ONE launch */
+#define H2V_MIXED_FOLD_MSM 2u     /* with H2V_MIXED_RLC: ONE bucket MSM over the call's per-proof terms as well; one host synchronisation */
 #define H2V_MIXED_MAX_PLANS 64u   /* more plans in one call: H2V_E_LIMIT */
 typedef struct {
     uint64_t n;
@@ -468,6 +490,9 @@ int h2v_probe_g1_msm_fixed(const h2v_plan *plan, uint32_t n, uint32_t bases_per_
  * (encodings that do not decompress count as infinity); out 96 B affine BE (all-zero = infinity) */
 int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t *scalars, const uint8_t *bases_compressed,
                                uint8_t *out_xy_be);
+/* test-only: the two sums of the most recent H2V_MIXED_FOLD_MSM call on ws, L = sum r_i L_i then R = sum r_i R_i: affine, 96 B
+ * big-endian x || y each, all-zero = infinity.  Synchronises the device.  H2V_E_ARG when no such call has run on ws. */
+int h2v_probe_mixed_fold_sums(h2v_workspace *ws, uint8_t out_xy_be[192]);
 /* 2P + (neg ? -Q : Q) by the one-lane mixed addition and by the quad-cooperative one (the forced MSM shape H2V_MSM_LPT=8):
  * pq = x_P, y_P, x_Q, y_Q as 12 canonical LE dwords each; out = 5 x 42 dwords of lazily reduced limbs (X, Y, Z; 14 limbs of
  * 28 bits each, Montgomery form R = 2^392): the one-lane result, then lanes 0..3 of a quad.  Guards a compiler issue

@@ -251,26 +251,28 @@ inline std::vector<uint8_t> verify_batch_rlc(const VerifyingKey &vk, const h2v_b
 // SRS (otherwise Error(H2V_E_ARG) naming two keys: a host with several SRS makes one call per SRS).  accept / status in the
 // caller's order, exactly the per-key verify call's.  rlc: ONE pairing for the call - the same vectors up to a 2^-128
 // soundness error over the seed (32 bytes that provers cannot predict, or nullptr = drawn from the OS); fell_back (optional):
-// that batch check failed and the per-pair kernels produced them.  ws: one made for the same keys or a superset
-// (Workspace(vks, max_batch)), or nullptr for a temporary one.
+// that batch check failed and the per-pair kernels produced them.  fold_msm (only with rlc; H2V_MIXED_FOLD_MSM): ONE bucket MSM
+// over the call's per-proof terms as well; a failed check runs the call again without it (fell_back).  ws: one made for the same
+// keys or a superset (Workspace(vks, max_batch)), or nullptr for a temporary one.
 inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
-                                 bool rlc = false, const uint8_t *seed = nullptr, bool *fell_back = nullptr) {
+                                 bool rlc = false, const uint8_t *seed = nullptr, bool *fell_back = nullptr, bool fold_msm = false) {
     std::vector<const h2v_plan *> plans;
     for (const VerifyingKey *k : vks) plans.push_back(k ? k->handle() : nullptr);
     PairVerdicts r{std::vector<uint8_t>(batch.n), std::vector<uint32_t>(batch.n)};
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
     int fb = 0;
-    check(h2v_verify_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.accept.data(), r.status.data(), ws, rlc ? H2V_MIXED_RLC : 0u,
-                           seed ? &opts : nullptr, &fb));
+    check(h2v_verify_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.accept.data(), r.status.data(), ws,
+                           (rlc ? H2V_MIXED_RLC : 0u) | (fold_msm ? H2V_MIXED_FOLD_MSM : 0u), seed ? &opts : nullptr, &fb));
     if (fell_back) *fell_back = fb != 0;
     return r;
 }
 // midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs) (src/circuits/schnorr_circuit.rs:223-231): one call and
 // one final check for a list of (vk, instances, proof) triples on one SRS.  Throws VerifyError (with the first rejected proof's
 // status) unless every proof is accepted.
-inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr) {
-    const PairVerdicts r = verify_mixed(vks, batch, ws, true);
+inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
+                         bool fold_msm = false) {
+    const PairVerdicts r = verify_mixed(vks, batch, ws, true, nullptr, nullptr, fold_msm);
     for (uint64_t i = 0; i < batch.n; i++)
         if (!r.accept[i]) throw VerifyError(r.status[i]);
 }

@@ -278,22 +278,25 @@ def _mixed_workspace(verifiers, n: int) -> backend.Workspace:
 
 def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
                  committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof", seed: Optional[bytes] = None,
-                 device: int = 0) -> List[bool]:
+                 device: int = 0, fold_msm: bool = False) -> List[bool]:
     """accept[i] for n proofs, proof i under the key vks[i] (instances[i]: its public-input scalars; committed[i]: its
     committed instance as 48 compressed bytes when its circuit has one, else None).  The proofs are grouped by SRS on the
     host - one h2v_verify_mixed call per distinct s_g2, each over all its keys - and the verdicts come back in the caller's
     order.  mode="rlc": ONE pairing per call (the reference's batch_verify); same accept vector up to a 2^-128 soundness error
-    over `seed` (from the OS when None)."""
-    return _verify_mixed(vks, proofs, instances, committed, mode, seed, device)[0]
+    over `seed` (from the OS when None).  fold_msm (mode="rlc" only): ONE bucket MSM over the call's per-proof terms as well
+    (H2V_MIXED_FOLD_MSM); a failed check runs the call again without it."""
+    return _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm)[0]
 
 
-def _verify_mixed(vks, proofs, instances, committed, mode, seed, device):
+def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm=False):
     """(accept, status) of verify_mixed"""
     n = len(proofs)
     if len(vks) != n or len(instances) != n or (committed is not None and len(committed) != n):
         raise ValueError("one key, one instance list (and one committed instance or None) per proof")
     if mode not in ("per-proof", "rlc"):
         raise ValueError("mode is 'per-proof' or 'rlc'")
+    if fold_msm and mode != "rlc":
+        raise ValueError("fold_msm needs mode='rlc'")
     out: List[bool] = [False] * n
     status: List[int] = [0] * n
     groups = {}                                   # s_g2 -> positions, in the caller's order
@@ -319,20 +322,22 @@ def _verify_mixed(vks, proofs, instances, committed, mode, seed, device):
                 ci.append(bls.g1_compress(None) if c is None else bytes(c))
         acc, st, _fb = backend.verify_mixed([v.device_plan for v in verifiers], plan_of, b"".join(bytes(proofs[i]) for i in idx), off,
                                              b"".join(inst), b"".join(ci) or None, ws=_mixed_workspace(verifiers, len(idx)), mode=mode,
-                                             seed=seed)
+                                             seed=seed, fold_msm=fold_msm)
         for i, a, s in zip(idx, acc, st):
             out[i], status[i] = bool(a), s
     return out, status
 
 
 def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instances: Sequence[Sequence[int]],
-                 proofs: Sequence[bytes], committed: Optional[Sequence[Optional[bytes]]] = None, device: int = 0) -> None:
+                 proofs: Sequence[bytes], committed: Optional[Sequence[Optional[bytes]]] = None, device: int = 0,
+                 fold_msm: bool = False) -> None:
     """midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs) (src/circuits/schnorr_circuit.rs:223-231): one
     call and one final check for a list of (vk, instances, proof) triples on ONE SRS - the batch-accept mode of verify_mixed.
-    Raises VerifyError unless every proof is accepted (Rust: Err(_)); a key on another SRS than `params` is a ValueError."""
+    Raises VerifyError unless every proof is accepted (Rust: Err(_)); a key on another SRS than `params` is a ValueError.
+    fold_msm: one bucket MSM for the list as well (verify_mixed)."""
     for i, vk in enumerate(vks):
         if bytes(params.s_g2) != bytes.fromhex(vk.s_g2):
             raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
-    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device)
+    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm)
     if not all(acc):
         raise VerifyError(next(s for a, s in zip(acc, status) if not a))

@@ -69,6 +69,7 @@ RLC_ONE_STREAM = 2
 RLC_FOLD_PAIRS = 4   # recursive plans: combine the pairs (el', er') the fold leaves (include/h2v.h)
 SUBMIT_RLC = 1
 MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
+MIXED_FOLD_MSM = 2     # ... and ONE bucket MSM over the call's per-proof terms (only together with MIXED_RLC)
 MIXED_MAX_PLANS = 64   # H2V_MIXED_MAX_PLANS
 
 
@@ -96,7 +97,7 @@ EXPORTS = [
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
     "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device",
     "h2v_plan_transcript", "h2v_probe_blake2b_ex",
-    "h2v_verify_mixed", "h2v_verify_mixed_device",
+    "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums",
 ]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
@@ -181,6 +182,7 @@ def lib():
                                        C.POINTER(RlcOpts), C.POINTER(C.c_int)]
         L.h2v_verify_mixed_device.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_uint32, C.POINTER(RlcOpts)]
+        L.h2v_probe_mixed_fold_sums.argtypes = [C.c_void_p, C.c_void_p]
         # h2v_shutdown before the interpreter goes down: the library's pool streams (hardware queues of their own) must not
         # outlive the HIP runtime / a profiler's tool library (include/h2v.h: library lifecycle).  Handles that Python still
         # holds afterwards are empty shells; their __del__ frees the host structs only.
@@ -498,18 +500,22 @@ class Workspace:
 
 
 # ---- mixed-key batches (include/h2v.h: h2v_verify_mixed)
-def _mixed_mode(mode: str) -> int:
+def _mixed_mode(mode: str, fold_msm: bool = False) -> int:
     if mode not in ("per-proof", "rlc"):
         raise ValueError("mode is 'per-proof' or 'rlc'")
-    return MIXED_RLC if mode == "rlc" else 0
+    if fold_msm and mode != "rlc":
+        raise ValueError("fold_msm needs mode='rlc' (H2V_MIXED_FOLD_MSM is valid only together with H2V_MIXED_RLC)")
+    return (MIXED_RLC if mode == "rlc" else 0) | (MIXED_FOLD_MSM if fold_msm else 0)
 
 
 def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
-                 mode: str = "per-proof", seed: Optional[bytes] = None):
+                 mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False):
     """h2v_verify_mixed: n proofs of several plans on ONE SRS in one call; proof i belongs to plans[plan_of[i]], its public
     inputs (and committed instance, where its plan has one) follow those of the proofs before it.  Returns (accept bytes,
     status list, fell_back) in the caller's order.  mode="rlc": ONE pairing for the call (fell_back: the batch check failed
-    and the per-pair kernels produced accept[]).  ws: typically Workspace.multi over the same plans; None: a temporary one."""
+    and the per-pair kernels produced accept[]).  fold_msm (mode="rlc" only; MIXED_FOLD_MSM): ONE bucket MSM over the call's
+    per-proof terms as well - no ladder MSM unless the check fails, in which case the call runs again without it (fell_back).
+    ws: typically Workspace.multi over the same plans; None: a temporary one."""
     n = len(proof_off) - 1
     if n < 0 or len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
@@ -526,7 +532,7 @@ def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[b
     acc = (C.c_uint8 * max(1, n))()
     st = (C.c_uint32 * max(1, n))()
     fb = C.c_int(0)
-    flags = _mixed_mode(mode)
+    flags = _mixed_mode(mode, fold_msm)
     opts = _rlc_opts(seed)
     check(lib().h2v_verify_mixed(arr, len(plans), C.byref(b), acc, st, ws.handle if ws else None, flags,
                                  C.byref(opts) if opts is not None else None, C.byref(fb)))
@@ -534,18 +540,27 @@ def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[b
 
 
 def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_accept, d_status=None, ws=None, stream=None,
-                        mode: str = "per-proof", seed: Optional[bytes] = None) -> None:
+                        mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False) -> None:
     """h2v_verify_mixed_device: enqueues on `stream`; plan_of is a host list, every d_* a device pointer.  `stream` has
     waited for the call's lanes when this returns (a join point, deferred joins or not); ws.rlc_result() has the batch
-    verdict of an mode="rlc" call once the stream is synchronised."""
+    verdict of an mode="rlc" call once the stream is synchronised.  fold_msm: as verify_mixed; the call then returns only
+    after the batch verdict is known (it synchronises `stream` once)."""
     if len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
+    flags = _mixed_mode(mode, fold_msm)
     arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
     po = (C.c_uint32 * max(1, n))(*plan_of)
     b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
     opts = _rlc_opts(seed)
     check(lib().h2v_verify_mixed_device(arr, len(plans), C.byref(b), d_accept, d_status, ws.handle if ws else None, stream,
-                                        _mixed_mode(mode), C.byref(opts) if opts is not None else None))
+                                        flags, C.byref(opts) if opts is not None else None))
+
+
+def probe_mixed_fold_sums(ws):
+    """h2v_probe_mixed_fold_sums: (L, R) of the most recent fold_msm call on ws as affine (x, y) integer pairs, None = infinity"""
+    out = C.create_string_buffer(192)
+    check(lib().h2v_probe_mixed_fold_sums(ws.handle, out))
+    return _unxy(out.raw[:96]), _unxy(out.raw[96:])
 
 
 # ---- primitive probes (GPU parity tests)

@@ -15,6 +15,8 @@
 #include "h2v_kernels.hip"
 #include "h2v_mixed.hpp"
 #include "h2v_mixed_dev.hpp"
+#include "h2v_mixed_fold.hpp"
+#include "h2v_mixed_fold_dev.hpp"
 #include "h2v_msm_shape.hpp"
 #include "h2v_plancc.hpp"
 
@@ -1402,9 +1404,13 @@ extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_
 //   MIXED_SUB    h2v_verify_mixed, a per-plan sub-batch: instead of the pairing, k_mixed_pairs writes each proof's pair, `good`
 //                and its pre-pairing status at pos[i] - its position in the call - of the call's pool; the record is a prepare call's
 //   MIXED_TAIL / MIXED_TAIL_RLC   the pairing / the batch check over the call's pool (run_mixed_tail)
+//   MIXED_SUB_TERMS   H2V_MIXED_FOLD_MSM, a sub-batch of a plan that has the batch form: phase 1 alone, then k_mixed_terms writes the
+//                proofs' terms into the call's term pool (run_mixed_terms); no MSM, no pair; the record is a prepare call's
+//   MIXED_FOLD_TAIL   H2V_MIXED_FOLD_MSM: ONE bucket MSM over the call's term pool and ONE pairing (run_mixed_fold_tail)
 // seed: the batch coefficients' (RLC kinds).  fail_ctr: where a failed batch check is counted - a lane's chunk or a coalesced
 // group: its parent's word; NULL (a call of its own): its record's word, zeroed by the call.
-enum class UnitKind : uint8_t { VERIFY, PREPARE, CHECK, RLC, PAIR_RLC, FOLD_RLC, ROUTED, MIXED_SUB, MIXED_TAIL, MIXED_TAIL_RLC };
+enum class UnitKind : uint8_t { VERIFY, PREPARE, CHECK, RLC, PAIR_RLC, FOLD_RLC, ROUTED, MIXED_SUB, MIXED_TAIL, MIXED_TAIL_RLC, MIXED_SUB_TERMS, MIXED_FOLD_TAIL };
+struct MixedFold;
 // the pool of a mixed call, caller's order: pairs (two-slot affine records), good_i, 2 x cap bytes of 1 (the `valid` of a two-slot
 // view) and the status words (pre-pairing bits; the tail folds H2V_ST_PAIRING in)
 struct MixedPool { uint32_t *pool; uint8_t *good; const uint8_t *ones; uint32_t *status; };
@@ -1416,6 +1422,8 @@ struct Unit {
     const uint8_t *pairs = nullptr;
     uint8_t *accept = nullptr; uint32_t *status = nullptr; uint8_t *pairs_out = nullptr;
     MixedPool pool = {}; const uint32_t *pos = nullptr;
+    const MixedFold *fold = nullptr;   // H2V_MIXED_FOLD_MSM: the call's term pool and its layout; fold_plan: the unit's plan in the call's
+    uint32_t fold_plan = 0, first = 0; // list; first: the unit's first proof within its plan's sub-batch (slice)
     uint32_t seed[8] = {};
     uint32_t *fail_ctr = nullptr;
     bool one_stream_opt = false;       // RLC: h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM (lanes and coalesced groups: always)
@@ -1434,6 +1442,7 @@ struct Unit {
         if (status) c.status = status + lo;
         if (pairs_out) c.pairs_out = pairs_out + (size_t)lo * 96;
         if (pos) c.pos = pos + lo;
+        c.first = first + lo;
         if (kind == UnitKind::MIXED_TAIL || kind == UnitKind::MIXED_TAIL_RLC) c.pool = {pool.pool + (size_t)lo * 48, pool.good + lo, pool.ones, pool.status + lo};
         return c;
     }
@@ -1636,6 +1645,8 @@ static int run_check(const Unit &u, h2v_workspace *w, hipStream_t st) {
 static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_pairs_rlc(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
+static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st);
+static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
 // ROUTING of RLC calls (round 4).  The batch-accept mode pays for every batch whose check fails: with 1 % rejecting proofs
 // nearly half of the groups of 64 fail, and the call costs 1.3 x the per-proof mode it falls back to.  A workspace therefore
 // keeps a running estimate of the rate of FAILING GROUPS among the groups its RLC calls have seen - cumulative device
@@ -1692,6 +1703,8 @@ static int run_unit(const Unit &u, h2v_workspace *w, hipStream_t st) {
     case UnitKind::PAIR_RLC: return run_pairs_rlc(u, w, st);
     case UnitKind::ROUTED: return run_routed(u, w, st);
     case UnitKind::MIXED_TAIL: case UnitKind::MIXED_TAIL_RLC: return run_mixed_tail(u, w, st);
+    case UnitKind::MIXED_SUB_TERMS: return run_mixed_terms(u, w, st);
+    case UnitKind::MIXED_FOLD_TAIL: return run_mixed_fold_tail(u, w, st);
     case UnitKind::VERIFY: case UnitKind::PREPARE: case UnitKind::FOLD_RLC: case UnitKind::MIXED_SUB: break;
     }
     return run_pipeline(u, w, st);
@@ -1746,7 +1759,8 @@ static int run_on_lane(h2v_workspace *w, uint32_t l, const Unit &u, const LaneSe
     lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
     if (counted) lw->rlc_stats_ptr = w->rlc_stats;
     if (u.kind == UnitKind::ROUTED) lw->one_stream_mode = 1;
-    else if (u.kind == UnitKind::VERIFY || u.kind == UnitKind::PREPARE || u.kind == UnitKind::FOLD_RLC || u.kind == UnitKind::MIXED_SUB) lw->one_stream_mode = s.stream_mode;
+    else if (u.kind == UnitKind::VERIFY || u.kind == UnitKind::PREPARE || u.kind == UnitKind::FOLD_RLC || u.kind == UnitKind::MIXED_SUB || u.kind == UnitKind::MIXED_SUB_TERMS)
+        lw->one_stream_mode = s.stream_mode;
     int rc = run_unit(u, lw, w->lane_st[l]);
     if (rc == H2V_OK && counted) rc = rlc_stats_mirror(w, w->lane_st[l]);
     return rc;
@@ -2849,8 +2863,10 @@ static int rlc_groups_launch(RlcWs *r, const GrpShape &gs, uint32_t n, uint8_t *
 // ONE pairing check for the batch over a one-proof view of the plan: el = L = r->sums + 36, er = R = r->sums (both Jacobian), no
 // per-proof points; ev9 marks its end.  Behind it - skipped on the device when the check passed - the group stage over gs.
 // fail_ctr: the unit's, or NULL: the record's word, zeroed here.  stats: the failing-group counters, or NULL (pairs: that
-// estimate describes proofs of a plan).  Everything behind it takes r->flags as skip flags.
-static int launch_batch_pairing(const Unit &u, RlcWs *r, const GrpShape &gs, uint32_t *stats, h2v_workspace *w, CallRec &rec, hipStream_t st) {
+// estimate describes proofs of a plan).  Everything behind it takes r->flags as skip flags.  group_stage = false: the check
+// alone (the fold form of a mixed call: a group of 64 call positions spans plans, so no group term list applies).
+static int launch_batch_pairing(const Unit &u, RlcWs *r, const GrpShape &gs, uint32_t *stats, h2v_workspace *w, CallRec &rec, hipStream_t st,
+                                bool group_stage = true) {
     const uint32_t n = u.n;
     H2vDevPlan d1 = u.p->d;
     d1.n_points = 1; d1.n_ci = 0; d1.ivc = 0; d1.pi_point = 0;
@@ -2863,9 +2879,9 @@ static int launch_batch_pairing(const Unit &u, RlcWs *r, const GrpShape &gs, uin
         HIPCHK(hipMemsetAsync(fail_ctr, 0, 4, st));
     }
     hipLaunchKernelGGL(k_pairing_rlc, dim3(1), dim3(64), COOP_LDS_BYTES(1), st, d1, r->misc, valid1, r->sums, r->sums + 36, st1, acc1, n, r->good, u.accept, r->flags,
-                       (n + 63) / 64, fail_ctr, stats, rlc_groups_on(n) ? 1u : 0u);
+                       (n + 63) / 64, fail_ctr, stats, group_stage && rlc_groups_on(n) ? 1u : 0u);
     HIPCHK(hipEventRecord(rec.ev[9], st));
-    if (rlc_groups_on(n))
+    if (group_stage && rlc_groups_on(n))
         if (int rc = rlc_groups_launch(r, gs, n, u.accept, d1, st, stats)) return rc;
     return H2V_OK;
 }
@@ -3117,6 +3133,25 @@ struct MixedWs {
     uint8_t *good = nullptr, *ones = nullptr;                        // good_i; 2 x cap bytes of 1: the `valid` of a two-slot view
     uint8_t *h_in = nullptr, *d_in = nullptr, *d_out = nullptr;      // host form: pinned block, its device copy, accept + status + verdict
     size_t in_cap = 0, out_cap = 0;
+    // H2V_MIXED_FOLD_MSM, allocated by the first fold call and grown behind mixed_quiesce: the call-level term pool - `fold` holds
+    // the scalars of the R-terms (r_scal, fold_cap_terms records) and of the L-terms (l_scal, by call position), the per-block
+    // sums of the VK-base scalars (vk_part, fold_cap_parts Fr records), good, the two bucket-MSM workspaces and the sums / misc /
+    // flags set of the one pairing; fold_rpts / fold_lpts are the COPIED points of the terms (24 dwords each)
+    struct RlcWs *fold = nullptr;
+    uint32_t *fold_rpts = nullptr, *fold_lpts = nullptr;
+    size_t fold_cap_terms = 0, fold_cap_parts = 0;
+    bool fold_ran = false;                // fold->sums holds the sums of a fold call (h2v_probe_mixed_fold_sums)
+};
+// one fold call: the pool, its layout, the device table of the foldable plans, the call's seed (ONE per call: chunks of a
+// sub-batch do not derive their own, coefficients follow the position in the call)
+struct MixedFold {
+    MixedWs *m;
+    const h2vmixed::FoldLayout *lay;
+    const h2vmixed::Partition *pt;
+    const h2v_plan *const *plans;
+    const H2vFoldPlan *d_plans;           // lay->n_foldable entries
+    const uint32_t *d_perm;               // grouped index -> position in the call
+    uint32_t seed[8];
 };
 static void mixed_release(h2v_workspace *w) {
     MixedWs *m = w->mixed;
@@ -3128,7 +3163,8 @@ static void mixed_release(h2v_workspace *w) {
         if (s.done) (void)hipEventDestroy(s.done);
     }
     if (m->h_in) (void)hipHostFree(m->h_in);
-    void *ptrs[] = {m->proofs, m->inst, m->ci, m->pool, m->status, m->good, m->ones, m->d_in, m->d_out};
+    if (m->fold) rlc_release(m->fold);
+    void *ptrs[] = {m->proofs, m->inst, m->ci, m->pool, m->status, m->good, m->ones, m->d_in, m->d_out, m->fold_rpts, m->fold_lpts};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     delete m;
     w->mixed = nullptr;
@@ -3168,6 +3204,125 @@ static int mixed_ensure(h2v_workspace *w, const h2vmixed::Partition &pt) {
     }
     return H2V_OK;
 }
+// The term pool of the fold form for a call of this layout (the first fold call allocates, a larger one grows it once every
+// earlier mixed call has finished on the device).
+static int mixed_fold_ensure(h2v_workspace *w, const h2vmixed::FoldLayout &lay) {
+    MixedWs *m = w->mixed;
+    const size_t need_t = (size_t)lay.n_r, need_p = (size_t)lay.n_parts;
+    if (m->fold && need_t <= m->fold_cap_terms && need_p <= m->fold_cap_parts) return H2V_OK;
+    if (int rc = mixed_quiesce(m)) return rc;
+    if (m->fold) { rlc_release(m->fold); m->fold = nullptr; }
+    for (uint32_t **q : {&m->fold_rpts, &m->fold_lpts}) if (*q) { (void)hipFree(*q); *q = nullptr; }
+    size_t cap_t = need_t + need_t / 4, cap_p = need_p + need_p / 4 + 1;
+    if (cap_t > H2V_MIXED_FOLD_MAX_TERMS) cap_t = (size_t)H2V_MIXED_FOLD_MAX_TERMS;
+    if (cap_t < m->fold_cap_terms) cap_t = m->fold_cap_terms;
+    if (cap_p < m->fold_cap_parts) cap_p = m->fold_cap_parts;
+    m->fold_cap_terms = m->fold_cap_parts = 0; m->fold_ran = false;
+    RlcWs *r = new RlcWs();
+    const size_t cap = (size_t)w->cap, blocks = (cap + 63) / 64;
+    r->cap = cap;
+    bool ok = hipMalloc((void **)&r->r_scal, cap_t * 32) == hipSuccess && hipMalloc((void **)&r->l_scal, cap * 32) == hipSuccess &&
+              hipMalloc((void **)&r->vk_part, cap_p * 32) == hipSuccess && hipMalloc((void **)&r->good, cap) == hipSuccess &&
+              hipMalloc((void **)&r->sums, 72 * 4) == hipSuccess && hipMalloc((void **)&r->misc, 32 * 4) == hipSuccess &&
+              hipMemset(r->misc, 0, 32 * 4) == hipSuccess && hipMalloc((void **)&r->flags, (blocks + 2) * 4) == hipSuccess &&
+              hipMemset(r->flags, 0, (blocks + 2) * 4) == hipSuccess && hipMalloc((void **)&m->fold_rpts, cap_t * 96) == hipSuccess &&
+              hipMalloc((void **)&m->fold_lpts, cap * 96) == hipSuccess;
+    if (ok) ok = pip_alloc(r->R, (uint32_t)cap_t, 2) == H2V_OK && pip_alloc(r->L, (uint32_t)cap, 1) == H2V_OK;
+    if (!ok) {
+        rlc_release(r);
+        for (uint32_t **q : {&m->fold_rpts, &m->fold_lpts}) if (*q) { (void)hipFree(*q); *q = nullptr; }
+        return fail(H2V_E_DEVICE, "allocation of the fold form's term pool failed");
+    }
+    m->fold = r; m->fold_cap_terms = cap_t; m->fold_cap_parts = cap_p;
+    return H2V_OK;
+}
+// H2V_MIXED_FOLD_MSM, a sub-batch (or a lane's chunk of one) of a plan that has the batch form: phase 1 exactly as run_rlc runs it
+// - the decompression launch builds no window tables, the combiner beside it, joined - and then k_mixed_terms: the proofs'
+// scaled scalars and COPIES of their points into the call's term pool, their share of the VK-base sums, and good / status /
+// (r, pi) at their positions in the call.  No MSM, no pair, no pairing.  The record is a prepare call's; events as run_pipeline's:
+// [0]/[1] around the combiner, [2]/[3] around the decompression, [4] = [5] (no MSM), [5]/[6] around k_mixed_terms.
+static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const h2v_plan *p = u.p;
+    const H2vDevPlan &d = p->d;
+    const MixedFold &f = *u.fold;
+    const h2vmixed::FoldLayout &lay = *f.lay;
+    const uint32_t n = u.n, k = u.fold_plan, slots = H2V_SLOTS(d);
+    LaunchOptsScope opts(w);
+    int rc;
+    CallRec &rec = rec_new(w, h2v_workspace::PREPARE);
+    hipEvent_t *ev = rec.ev;
+    const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode == 1 : w->in_flight_hint >= 3;
+    if (!one_stream && (rc = ws_streams(w, false, true))) return rc;
+    hipStream_t pm = st, ps = one_stream ? st : w->pside;
+    if (!one_stream) {
+        HIPCHK(hipEventRecord(w->ev_fork, st));
+        HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
+    }
+    HIPCHK(hipEventRecord(ev[2], ps));
+    if ((rc = launch_decompress(d, n, u.proofs, u.off, u.ci, u.inst, w, nullptr, ps))) return rc;
+    HIPCHK(hipEventRecord(ev[3], ps));
+    HIPCHK(hipEventRecord(w->ev_join, ps));
+    HIPCHK(hipEventRecord(ev[0], pm));
+    if ((rc = launch_vm(d, n, w->stride, u.proofs, u.off, u.inst, u.ci, w->regs, w->scalars, w->status, nullptr, pm))) return rc;
+    HIPCHK(hipEventRecord(ev[1], pm));
+    if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
+    HIPCHK(hipEventRecord(ev[4], pm));
+    HIPCHK(hipEventRecord(ev[5], pm));
+    RlcWs *r = f.m->fold;
+    const size_t t0 = (size_t)lay.term_base[k] + (size_t)u.first * p->n_var;                                   // the chunk's first R-term
+    const size_t b0 = (size_t)lay.part_base[k] + (size_t)h2vmixed::fold_chunk_block(u.first, lay.chunk) * p->n_fix;   // ... and Fr record
+    if (t0 + (size_t)n * p->n_var > f.m->fold_cap_terms || b0 + (size_t)((n + 63) / 64) * p->n_fix > f.m->fold_cap_parts)
+        return fail(H2V_E_DEVICE, "internal: a chunk's terms lie outside the call's term pool");
+    MixedTermsArgs a = {n, p->n_var, p->n_fix, slots, d.pi_point, d.n_terms, d.terms, w->scalars, w->status, w->valid, w->valid_sub, w->pts, u.pos, {},
+                        r->r_scal + t0 * 8, f.m->fold_rpts + t0 * 24, r->l_scal, f.m->fold_lpts, r->vk_part + b0 * 8, u.pool.good, u.pool.status};
+    for (int q = 0; q < 8; q++) a.seed[q] = f.seed[q];
+    hipLaunchKernelGGL(k_mixed_terms, dim3((n + 63) / 64), dim3(64), 0, pm, a);
+    HIPCHK(hipEventRecord(ev[6], pm));
+    HIPCHK(hipGetLastError());
+    return H2V_OK;
+}
+// H2V_MIXED_FOLD_MSM, the tail, behind every sub-batch of the call: the VK-base terms of the foldable plans (k_mixed_vk_sum), one
+// pair of terms per proof of the other plans out of the call's pool of pairs (k_mixed_pair_terms), then R over the term pool
+// (255-bit scalars, GLV) and L over the n call positions (128-bit) side by side in the six bucket-MSM launches, and ONE
+// k_pairing_rlc without a group stage, whose epilogue writes accept[i] = good_i in the caller's order when the check passes.  A
+// failed check leaves accept[] alone: the host runs the H2V_MIXED_RLC path then (run_mixed_call).  w: the ordinary workspace, or
+// the lane whose record the tail takes - none of its buffers is used.  Events as run_pairs_rlc's (no decoding, no transcript).
+static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const MixedFold &f = *u.fold;
+    const h2vmixed::FoldLayout &lay = *f.lay;
+    MixedWs *m = f.m;
+    RlcWs *r = m->fold;
+    const uint32_t n = u.n;
+    LaunchOptsScope opts(w);
+    int rc;
+    if (!u.fail_ctr && (rc = rlc_stats_ensure(w))) return rc;
+    CallRec &rec = rec_new(w, h2v_workspace::RLC);
+    rec.no_vm = true;
+    for (int q : {0, 1, 2, 3, 10}) HIPCHK(hipEventRecord(rec.ev[q], st));
+    HIPCHK(hipMemcpyAsync(r->good, m->good, n, hipMemcpyDeviceToDevice, st));
+    if (lay.total_fix)
+        hipLaunchKernelGGL(k_mixed_vk_sum, dim3((lay.total_fix + 63) / 64), dim3(64), 0, st, f.d_plans, lay.n_foldable, lay.total_fix, (const uint32_t *)r->vk_part,
+                           r->r_scal, m->fold_rpts);
+    for (uint32_t k = 0; k < lay.n_plans; k++) {
+        if (!f.pt->count[k] || lay.foldable[k]) continue;
+        MixedPairTermsArgs pa = {f.pt->count[k], lay.pair_base[k], f.d_perm + f.pt->base[k], m->pool, m->good, {}, r->r_scal, m->fold_rpts, r->l_scal, m->fold_lpts};
+        for (int q = 0; q < 8; q++) pa.seed[q] = f.seed[q];
+        hipLaunchKernelGGL(k_mixed_pair_terms, dim3((pa.n + 63) / 64), dim3(64), 0, st, pa);
+    }
+    HIPCHK(hipEventRecord(rec.ev[4], st));
+    PipArgs pa[2] = {};
+    pa[0].n = (uint32_t)lay.n_r; pa[0].halves = 2; pa[0].scal = r->r_scal; pa[0].pidx = nullptr; pa[0].pool0 = m->fold_rpts; pa[0].n_pool0 = (uint32_t)lay.n_r;
+    pa[0].pool1 = nullptr; pa[0].out = r->sums;
+    pa[1].n = n; pa[1].halves = 1; pa[1].scal = r->l_scal; pa[1].pidx = nullptr; pa[1].pool0 = m->fold_lpts; pa[1].n_pool0 = n; pa[1].pool1 = nullptr; pa[1].out = r->sums + 36;
+    const PipWs *pws[2] = {&r->R, &r->L};
+    if ((rc = pip_launch(pws, pa, 2, st, rec.ev + 5))) return rc;   // ev[5..8]
+    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    if ((rc = launch_batch_pairing(u, r, GrpShape{}, nullptr, w, rec, st, false))) return rc;
+    m->fold_ran = true;
+    HIPCHK(hipGetLastError());
+    if (u.status) HIPCHK(hipMemcpyAsync(u.status, m->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    return H2V_OK;
+}
 // The tail over u.n pairs of the pool (two-slot affine records, caller's order) on an ordinary workspace or a lane: the per-proof
 // pairing launch of run_check, or (MIXED_TAIL_RLC) the batch check of run_pairs_rlc, both without their decoding - the pipeline
 // made these points itself.  Events as run_check's / run_pairs_rlc's.
@@ -3204,19 +3359,22 @@ static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
 }
 // in: the call's device-resident buffers; host_off: the grouped proof offsets when the caller's proof_off is known on the host
 // (the host form), else NULL
+// lay: H2V_MIXED_FOLD_MSM - the layout of the call's term pool (fold_layout over this workspace's chunk size) - or NULL
 static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
-                     uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8]) {
+                     uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay = nullptr) {
     const uint32_t n = pt.n;
     int rc;
     if (w->n_lanes && (rc = co_flush(w))) return rc;       // (calls start in submission order: the open groups of coalesced calls first)
     if ((rc = mixed_ensure(w, pt))) return rc;
     if (rlc && (rc = rlc_stats_ensure(w))) return rc;
+    if (lay && (rc = mixed_fold_ensure(w, *lay))) return rc;
     MixedWs *m = w->mixed;
     // ---- the tables: one pinned block, one copy
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_off = 0, o_isrc = o_off + up16(((size_t)n + 1) * 8), o_idst = o_isrc + up16((size_t)n * 8), o_perm = o_idst + up16((size_t)n * 8),
                  o_cap = o_perm + up16((size_t)n * 4), o_ilen = o_cap + up16((size_t)n * 4), o_csrc = o_ilen + up16((size_t)n * 4),
-                 o_cdst = o_csrc + up16((size_t)n * 4), need = o_cdst + up16((size_t)n * 4);
+                 o_cdst = o_csrc + up16((size_t)n * 4), o_fold = o_cdst + up16((size_t)n * 4),
+                 need = o_fold + (lay ? up16((size_t)lay->n_foldable * sizeof(H2vFoldPlan)) : 0);
     const int si = (int)(m->next++ % MixedWs::SLOTS);
     MixedWs::Slot &sl = m->slot[si];
     if (sl.used) { HIPCHK(hipEventSynchronize(sl.done)); sl.used = false; }      // (the call that took this block last: its copy and its kernels are done)
@@ -3234,6 +3392,12 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     memcpy(sl.h + o_perm, pt.perm.data(), (size_t)n * 4); memcpy(sl.h + o_cap, pt.len_cap.data(), (size_t)n * 4);
     memcpy(sl.h + o_ilen, pt.inst_len.data(), (size_t)n * 4); memcpy(sl.h + o_csrc, pt.ci_src.data(), (size_t)n * 4);
     memcpy(sl.h + o_cdst, pt.ci_dst.data(), (size_t)n * 4);
+    if (lay) {               // what k_mixed_vk_sum reads of the foldable plans, in list order
+        H2vFoldPlan *fp = (H2vFoldPlan *)(sl.h + o_fold);
+        for (uint32_t k = 0; k < pt.n_plans; k++)
+            if (lay->foldable[k])
+                *fp++ = H2vFoldPlan{plans[k]->d.vk_bases, plans[k]->d.terms, plans[k]->n_var, plans[k]->n_fix, lay->fix_base[k], lay->n_blocks[k], lay->vk_base[k], 0u, lay->part_base[k]};
+    }
     if (m->last >= 0 && m->last != si && m->slot[m->last].used) HIPCHK(hipStreamWaitEvent(st, m->slot[m->last].done, 0));   // (the staging is the last call's until then)
     HIPCHK(hipMemcpyAsync(sl.d, sl.h, need, hipMemcpyHostToDevice, st));
     sl.used = true; m->last = si;
@@ -3254,18 +3418,21 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     uint32_t used_plans = 0;
     for (uint32_t k = 0; k < pt.n_plans; k++) if (pt.count[k]) { if (!p0) p0 = plans[k]; used_plans++; }
     const MixedPool pool = {m->pool, m->good, m->ones, m->status};
+    MixedFold fc = {m, lay, &pt, plans, (const H2vFoldPlan *)(sl.d + o_fold), d_perm, {}};
+    for (int q = 0; q < 8; q++) fc.seed[q] = seed ? seed[q] : 0;
     // plan k's sub-batch out of the grouped staging, and the tail over the whole pool
     auto sub_unit = [&](uint32_t k) {
         const H2vDevPlan &d = plans[k]->d;
-        Unit u{UnitKind::MIXED_SUB, plans[k], pt.count[k]};
+        Unit u{lay && lay->foldable[k] ? UnitKind::MIXED_SUB_TERMS : UnitKind::MIXED_SUB, plans[k], pt.count[k]};
+        if (lay) { u.fold = &fc; u.fold_plan = k; }
         u.proofs = m->proofs; u.off = d_off + pt.base[k];
         u.inst = d.n_pi ? m->inst + pt.inst_base[k] : nullptr;
         u.ci = d.n_ci ? m->ci + (size_t)pt.ci_base[k] * 48 : nullptr;
         u.pos = d_perm + pt.base[k]; u.pool = pool;
         return u;
     };
-    Unit tail{rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, n};
-    tail.pool = pool; tail.accept = accept; tail.status = status_out;
+    Unit tail{lay ? UnitKind::MIXED_FOLD_TAIL : rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, n};
+    tail.pool = pool; tail.accept = accept; tail.status = status_out; tail.fold = lay ? &fc : nullptr;
     for (int q = 0; q < 8; q++) tail.seed[q] = seed ? seed[q] : 0;
     if (!w->n_lanes) {
         // an ordinary workspace: the sub-batches one after the other on `st`, then the tail
@@ -3279,6 +3446,7 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     // (the sub-batches of all plans are in flight together: what they may assume is the call's chunks, not one plan's)
     const uint32_t sub_hint = call_hint(w, total_chunks > w->n_lanes, total_chunks);
     tail.fail_ctr = w->rec_fail ? w->rec_fail + (w->calls + used_plans) % h2v_workspace::RING : nullptr;   // the tail's record: the call's last
+    if (rlc && !tail.fail_ctr) return finish(fail(H2V_E_DEVICE, "internal: no verdict words"));
     if (rlc && hipMemsetAsync(tail.fail_ctr, 0, 4, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "memset failed"));
     if (hipEventRecord(w->ev_fork, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
     bool used_lane[h2v_workspace::MAXL] = {};
@@ -3289,6 +3457,15 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
         rec_laned(w, h2v_workspace::PREPARE, L, pt.count[k], w->chunk);
         if ((rc = run_chunks(w, sub_unit(k), L, w->chunk, {sub_hint, stream_mode}, [&](uint32_t l, hipStream_t) { used_lane[l] = true; return (int)H2V_OK; })))
             return finish(rc);
+    }
+    if (lay) {
+        // ---- the fold form's tail: ONE piece on the call's stream, behind every lane; its record (one "chunk") is a lane's
+        if ((rc = lanes_join(w, st))) return finish(rc);
+        const CallRec &rec = rec_laned(w, h2v_workspace::RLC, w->n_lanes, n, n);
+        if (rec_word(w, rec) != tail.fail_ctr) return finish(fail(H2V_E_DEVICE, "internal: the tail's record is not the call's last"));
+        const uint32_t l = (uint32_t)(w->next_lane++ % w->n_lanes);
+        if ((rc = ensure_lane(w, l))) return finish(rc);
+        return finish(run_unit(tail, w->lane[l], st));
     }
     // ---- the tail: chunks of the pool in the caller's order, each behind EVERY sub-batch (any of them may hold any position)
     {
@@ -3310,7 +3487,8 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
 static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, const uint8_t *accept, uint32_t flags, h2vmixed::Partition *pt) {
     if (!plans || !b || !accept) return fail(H2V_E_ARG, "null argument");
     if (n_plans > H2V_MIXED_MAX_PLANS) return fail(H2V_E_LIMIT, "at most " + std::to_string(H2V_MIXED_MAX_PLANS) + " plans in one mixed call (" + std::to_string(n_plans) + " listed)");
-    if (flags & ~H2V_MIXED_RLC) return fail(H2V_E_ARG, "unknown flag");
+    if (flags & ~(H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM)) return fail(H2V_E_ARG, "unknown flag");
+    if ((flags & H2V_MIXED_FOLD_MSM) && !(flags & H2V_MIXED_RLC)) return fail(H2V_E_ARG, "H2V_MIXED_FOLD_MSM is valid only together with H2V_MIXED_RLC");
     if (b->n == 0) return H2V_OK;
     if (n_plans == 0) return fail(H2V_E_ARG, "no plan listed");
     if ((flags & H2V_MIXED_RLC) && b->n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 proofs");
@@ -3336,6 +3514,34 @@ static int mixed_ws_check(const h2v_plan *const *plans, uint32_t n_plans, uint64
     if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
     return H2V_OK;
 }
+// H2V_MIXED_FOLD_MSM: the layout of the call's term pool on workspace w (h2v_mixed_fold.hpp) - which plans have the batch form
+// (rlc_supported), where their terms and block sums go, N_R - decided on the host before anything is enqueued: H2V_E_LIMIT above
+// 2^22 terms.
+static int mixed_fold_layout(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const h2v_workspace *w, h2vmixed::FoldLayout *lay) {
+    std::vector<h2vmixed::FoldShape> shapes(pt.n_plans);
+    for (uint32_t k = 0; k < pt.n_plans; k++) shapes[k] = {plans[k]->n_var, plans[k]->n_fix, rlc_supported(plans[k])};
+    std::string err;
+    if (!h2vmixed::fold_layout(shapes.data(), pt.count.data(), pt.n_plans, w->n_lanes ? w->chunk : 0u, *lay, &err)) return fail(H2V_E_LIMIT, err);
+    return H2V_OK;
+}
+// One mixed call on `st`.  lay (H2V_MIXED_FOLD_MSM): the fold form first - one bucket MSM and one pairing for the call - and then
+// the HOST decides: the record's verdict word comes down and `st` is synchronised (the one synchronisation of the form; phase-1
+// results no longer exist by then, the lanes have recycled them).  Passed: accept[] / status[] are final.  Failed: the
+// H2V_MIXED_RLC path runs on the same inputs with the same seed - its pair check, group stage and per-pair kernels localise the
+// rejects -, *fold_failed is set and the call's last record is that second pass's.
+static int run_mixed_call(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
+                          uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay,
+                          bool *fold_failed) {
+    if (!lay) return run_mixed(plans, pt, host_off, in, accept, status_out, w, st, rlc, seed);
+    int rc = run_mixed(plans, pt, host_off, in, accept, status_out, w, st, true, seed, lay);
+    if (rc) return rc;
+    uint32_t failed = 0;
+    if (hipMemcpyAsync(&failed, rec_word(w, rec_last(w)), 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return drain_after_error(w, fail(H2V_E_DEVICE, "mixed-call kernels failed (fold form)"));
+    if (!failed) return H2V_OK;
+    if (fold_failed) *fold_failed = true;
+    return run_mixed(plans, pt, host_off, in, accept, status_out, w, st, true, seed);
+}
 extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
                                        h2v_workspace *ws, void *stream, uint32_t flags, const h2v_rlc_opts *opts) {
     h2vmixed::Partition pt;
@@ -3349,8 +3555,11 @@ extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_
     const bool rlc = (flags & H2V_MIXED_RLC) != 0;
     uint32_t seed[8] = {};
     if (rlc && (rc = rlc_seed(opts, seed))) return rc;
+    h2vmixed::FoldLayout lay;
+    const bool fold = (flags & H2V_MIXED_FOLD_MSM) != 0;
+    if (fold && (rc = mixed_fold_layout(plans, pt, ws, &lay))) return rc;
     const h2v_batch in = {b->n, b->proofs, b->proof_off, b->instances, b->committed};
-    return run_mixed(plans, pt, nullptr, in, accept, status, ws, (hipStream_t)stream, rlc, seed);
+    return run_mixed_call(plans, pt, nullptr, in, accept, status, ws, (hipStream_t)stream, rlc, seed, fold ? &lay : nullptr, nullptr);
 }
 // Host-buffer form: offsets | instances | committed | proofs go up in one pinned block on the workspace's own stream, the call
 // runs there behind it, and accept[] / status[] / the batch verdict come back before the function returns.
@@ -3372,7 +3581,11 @@ extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, 
     }
     const bool rlc = (flags & H2V_MIXED_RLC) != 0;
     uint32_t seed[8] = {};
+    h2vmixed::FoldLayout lay;
+    const bool fold = (flags & H2V_MIXED_FOLD_MSM) != 0;
+    bool fold_failed = false;
     rc = mixed_ws_check(plans, n_plans, n, ws);
+    if (rc == H2V_OK && fold) rc = mixed_fold_layout(plans, pt, ws, &lay);
     if (rc == H2V_OK && rlc) rc = rlc_seed(opts, seed);
     if (rc == H2V_OK) rc = host_stream(ws);
     if (rc == H2V_OK) rc = mixed_ensure(ws, pt);
@@ -3415,13 +3628,13 @@ extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, 
             uint32_t failed = 0;
             if (hipMemcpyAsync(m->d_in, m->h_in, need, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the batch failed");
             const h2v_batch in = {n, m->d_in + o_proofs, (const uint64_t *)m->d_in, m->d_in + o_inst, m->d_in + o_ci};
-            if (rc == H2V_OK) rc = run_mixed(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed);
+            if (rc == H2V_OK) rc = run_mixed_call(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed);
             if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
             if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
             if (rc == H2V_OK && rlc && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
             if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "mixed-call kernels failed");
             if (rc) rc = drain_after_error(ws, rc);
-            else if (fell_back) *fell_back = failed ? 1 : 0;
+            else if (fell_back) *fell_back = (failed || fold_failed) ? 1 : 0;
         }
     }
     if (tmp) h2v_workspace_free(tmp);
@@ -3760,6 +3973,25 @@ extern "C" int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t 
     }
     pip_free(pw);
     return rc;
+}
+// The two sums of the most recent H2V_MIXED_FOLD_MSM call on ws - L then R, affine, 96 bytes big-endian x || y each, all-zero for
+// infinity - whether its check passed or the call fell back (the second pass does not touch them).  The call has synchronised its
+// stream already; the conversion runs on the NULL stream and the device is synchronised behind it.
+extern "C" int h2v_probe_mixed_fold_sums(h2v_workspace *ws, uint8_t out_xy_be[192]) {
+    if (!ws || !out_xy_be) return fail(H2V_E_ARG, "null argument");
+    ALIVE(ws);
+    const MixedWs *m = ws->mixed;
+    if (!m || !m->fold || !m->fold_ran) return fail(H2V_E_ARG, "no call with H2V_MIXED_FOLD_MSM has run on this workspace");
+    HIPCHK(hipSetDevice(ws->device));
+    DevBuf dout;
+    if (dout.alloc(192)) return fail(H2V_E_DEVICE, "hipMalloc failed");
+    HIPCHK(hipDeviceSynchronize());
+    hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 2u, 1, (const uint32_t *)m->fold->sums, dout.as<uint8_t>());   // [0] = R, [1] = L
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out_xy_be, (const uint8_t *)dout.p + 96, 96, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_xy_be + 96, dout.p, 96, hipMemcpyDeviceToHost));
+    return H2V_OK;
 }
 // The transcript + combiner launch alone, on a batch: status words, term scalars and (want_trace) the plan's trace registers of
 // every proof.  Nothing behind launch_vm runs, so a plan whose OUT_SCALARs mean nothing to the MSM is safe here.  The outputs

@@ -11,7 +11,13 @@ All proofs accept (the batch-accept mode is measured where it is meant to be use
 everything.  Every run is `--steps` steps between two device synchronisations; runs alternate new / baseline, `--runs` each.
 A gain is claimed only when the slowest new run beats the fastest baseline run.  --cache DIR keeps the forged batches (forging
 is CPU work).  Writes one JSON line per (shape, mode) and, with --out, the whole set.
-usage: bench_mixed.py [--shapes two,sixteen] [--runs 5] [--steps 20] [--cache DIR] [--out profiles/mixed_keys.json]"""
+--fold adds a third route to the batch-accept mode and measures that mode alone:
+  (c) fold:     the call of (a) with H2V_MIXED_FOLD_MSM - one bucket MSM over the call's per-proof terms and one pairing; it
+                synchronises the caller's stream once per call (the verdict comes back to the host).
+The three routes alternate (c), (a), (b), `--runs` each, in this one process; the fold form gains on a shape only when its
+slowest run beats the fastest run of (a) AND of (b), and loses when its fastest run is behind the slowest of either.
+usage: bench_mixed.py [--shapes two,sixteen] [--runs 5] [--steps 20] [--cache DIR] [--out profiles/mixed_keys.json]
+       bench_mixed.py --fold [...] [--out profiles/mixed_fold.json]"""
 import argparse
 import json
 import os
@@ -50,7 +56,7 @@ def forged(shape, cache):
     return out
 
 
-def run_shape(shape, runs, steps, cache):
+def run_shape(shape, runs, steps, cache, fold=False):
     import torch
     from plutus_halo2_verifier_gen_amd import backend
     keys = forged(shape, cache)
@@ -85,7 +91,12 @@ def run_shape(shape, runs, steps, cache):
     ws_old.defer_joins(True)
     seed = bytes(range(32))
     results = []
-    for mode in ("per-proof", "rlc"):
+    ws_fold = backend.Workspace.multi(plans, n) if fold else None
+    for mode in (("rlc",) if fold else ("per-proof", "rlc")):
+        def fold_step():
+            backend.verify_mixed_device(plans, plan_of, n, *[ptr(x) for x in m_in], m_acc.data_ptr(), m_st.data_ptr(), ws=ws_fold, stream=cs,
+                                        mode="rlc", seed=seed, fold_msm=True)
+
         def new_step():
             backend.verify_mixed_device(plans, plan_of, n, *[ptr(x) for x in m_in], m_acc.data_ptr(), m_st.data_ptr(), ws=ws_new, stream=cs,
                                         mode=mode, seed=seed if mode == "rlc" else None)
@@ -106,12 +117,19 @@ def run_shape(shape, runs, steps, cache):
             torch.cuda.synchronize()
             return (time.perf_counter() - t0) * 1e3 / k_steps
 
+        if fold:
+            run(fold_step, ws_fold, 3)
+            assert m_acc.cpu().tolist() == [1] * n, "the fold form rejects a forged proof"
+            assert ws_fold.rlc_result(timings=False)[0], "the fold form's check failed on forged proofs: the runs would time the fall-back"
+            m_acc.zero_()
         for step, ws in ((new_step, ws_new), (old_step, ws_old)):      # warm-up: first uses allocate
             run(step, ws, 3)
         assert m_acc.cpu().tolist() == [1] * n, "the mixed call rejects a forged proof"
         assert all(x[5].cpu().tolist() == [1] * x[0] for x in per_key), "a per-key call rejects a forged proof"
-        new_ms, old_ms = [], []
+        new_ms, old_ms, fold_ms = [], [], []
         for _ in range(runs):
+            if fold:
+                fold_ms.append(run(fold_step, ws_fold, steps))
             new_ms.append(run(new_step, ws_new, steps))
             old_ms.append(run(old_step, ws_old, steps))
         med = lambda v: sorted(v)[len(v) // 2]
@@ -119,9 +137,14 @@ def run_shape(shape, runs, steps, cache):
              "new_ms_per_step": [round(x, 4) for x in new_ms], "baseline_ms_per_step": [round(x, 4) for x in old_ms],
              "new_median_ms": round(med(new_ms), 4), "baseline_median_ms": round(med(old_ms), 4),
              "gain_by_the_rule": max(new_ms) < min(old_ms), "loss_by_the_rule": min(new_ms) > max(old_ms)}
+        if fold:
+            r.update({"fold_ms_per_step": [round(x, 4) for x in fold_ms], "fold_median_ms": round(med(fold_ms), 4),
+                      "fold_terms": ws_fold.rlc_result(timings=True)[1].msm_terms,
+                      "fold_gain_by_the_rule": max(fold_ms) < min(new_ms) and max(fold_ms) < min(old_ms),
+                      "fold_loss_by_the_rule": min(fold_ms) > max(new_ms) or min(fold_ms) > max(old_ms)})
         print(json.dumps(r), flush=True)
         results.append(r)
-    for w in (ws_new, ws_old):
+    for w in (ws_new, ws_old) + ((ws_fold,) if fold else ()):
         w.close()
     return results
 
@@ -134,6 +157,7 @@ def main():
     ap.add_argument("--cache", default=None)
     ap.add_argument("--forge-only", action="store_true", help="forge (and cache) the batches, then stop: no GPU needed")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fold", action="store_true", help="batch-accept mode only, with route (c): the call with H2V_MIXED_FOLD_MSM")
     args = ap.parse_args()
     if args.runs < 5 and not args.forge_only:
         ap.error("at least five runs of each route")
@@ -144,7 +168,7 @@ def main():
     import torch
     results = []
     for shape in args.shapes.split(","):
-        results += run_shape(shape, args.runs, args.steps, args.cache)
+        results += run_shape(shape, args.runs, args.steps, args.cache, args.fold)
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/bench_mixed.py", "device": torch.cuda.get_device_name(0), "runs": args.runs, "cases": results}, f, indent=1)
