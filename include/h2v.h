@@ -490,6 +490,32 @@ int h2v_probe_g1_msm_fixed(const h2v_plan *plan, uint32_t n, uint32_t bases_per_
  * (encodings that do not decompress count as infinity); out 96 B affine BE (all-zero = infinity) */
 int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t *scalars, const uint8_t *bases_compressed,
                                uint8_t *out_xy_be);
+/* The same kernels as the RLC mode launches them: 1 or 2 problems side by side in every launch (the production calls run their
+ * right- and left-hand sums that way), each with its own term count, halves, scalars, point pool and index map.
+ *   halves            2: scalars < r, split by GLV; 1: scalars below 2^128 (H2V_E_ARG for a larger one)
+ *   points_compressed n_points x 48 B, decompressed on the device; infinity and encodings that do not decompress give the all-zero
+ *                     record.  Records [0, n_pool0) are served through the kernels' pool0, the rest through pool1 (n_pool0 ==
+ *                     n_points: one pool).
+ *   pidx              n indices into the pool (may repeat; one >= n_points is H2V_E_ARG), or NULL for the identity map, which
+ *                     needs n == n_points
+ *   out_xy_be         96 B affine big-endian, all-zero = infinity
+ *   dump              NULL, or H2V_PIP_DUMP_DWORDS dwords: [0..4] the shape the launcher chose - window bits c, windows W, buckets
+ *                     per window NB, chain - and the number of blocks k_pip_accumulate was launched with; [5..32] the size classes
+ *                     k_pip_scan wrote (per class k = 0..8: first rank, end rank, first lane; then the lane total); then the
+ *                     W NB + 1 exclusive offsets of the buckets' entry lists; then the W NB bucket ids by descending size
+ * acc_grid_cap: test-only, 0 = none; caps the grid of k_pip_accumulate so that every block walks several logical blocks.
+ * The shape options H2V_OPT_RLC_WINDOW_BITS / H2V_OPT_RLC_CHAIN of h2v_probe_set_option apply.  tests/test_bucket_msm_shapes_gpu.py */
+#define H2V_PIP_DUMP_DWORDS 20514
+typedef struct h2v_pip_probe {
+    uint32_t n, halves;
+    const uint8_t *scalars;            /* n x 32 B LE */
+    uint32_t n_points, n_pool0;
+    const uint8_t *points_compressed;
+    const uint32_t *pidx;
+    uint8_t *out_xy_be;
+    uint32_t *dump;
+} h2v_pip_probe;
+int h2v_probe_g1_msm_pippenger_ex(int device, uint32_t n_problems, const h2v_pip_probe *problems, uint32_t acc_grid_cap);
 /* test-only: the two sums of the most recent H2V_MIXED_FOLD_MSM call on ws, L = sum r_i L_i then R = sum r_i R_i: affine, 96 B
  * big-endian x || y each, all-zero = infinity.  Synchronises the device.  H2V_E_ARG when no such call has run on ws. */
 int h2v_probe_mixed_fold_sums(h2v_workspace *ws, uint8_t out_xy_be[192]);

@@ -38,6 +38,12 @@ class Timings(C.Structure):
                 ("g1_msm_fixed_ms", C.c_float), ("msm_var_lanes_per_term", C.c_uint32)]
 
 
+class PipProbe(C.Structure):
+    """h2v_pip_probe (include/h2v.h)"""
+    _fields_ = [("n", C.c_uint32), ("halves", C.c_uint32), ("scalars", C.c_char_p), ("n_points", C.c_uint32), ("n_pool0", C.c_uint32),
+                ("points_compressed", C.c_char_p), ("pidx", C.POINTER(C.c_uint32)), ("out_xy_be", C.c_void_p), ("dump", C.POINTER(C.c_uint32))]
+
+
 class RlcOpts(C.Structure):
     _fields_ = [("seed", C.c_uint8 * 32), ("flags", C.c_uint32)]
 
@@ -90,7 +96,7 @@ EXPORTS = [
     "h2v_workspace_timings", "h2v_workspace_hint_in_flight", "h2v_workspace_create_lanes", "h2v_workspace_create_multi", "h2v_workspace_defer_joins",
     "h2v_workspace_join", "h2v_workspace_lanes", "h2v_workspace_depth", "h2v_workspace_set_option", "h2v_workspace_get_option", "h2v_workspace_tune", "h2v_probe_set_option",
     "h2v_verify_batch", "h2v_verify_batch_submit", "h2v_verify_batch_wait", "h2v_verify_batch_device", "h2v_verify_batch_rlc", "h2v_verify_batch_rlc_device",
-    "h2v_workspace_rlc_result", "h2v_probe_g1_msm_pippenger", "h2v_plan_trace_slots", "h2v_trace", "h2v_probe_vm", "h2v_probe_field",
+    "h2v_workspace_rlc_result", "h2v_probe_g1_msm_pippenger", "h2v_probe_g1_msm_pippenger_ex", "h2v_plan_trace_slots", "h2v_trace", "h2v_probe_vm", "h2v_probe_field",
     "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_f28_dot2", "h2v_probe_pairing", "h2v_probe_pairing_ex",
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
@@ -155,6 +161,7 @@ def lib():
                                                   C.c_void_p, C.POINTER(RlcOpts)]
         L.h2v_workspace_rlc_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(RlcTimings)]
         L.h2v_probe_g1_msm_pippenger.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
+        L.h2v_probe_g1_msm_pippenger_ex.argtypes = [C.c_int, C.c_uint32, C.POINTER(PipProbe), C.c_uint32]
         L.h2v_plan_trace_slots.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.POINTER(C.c_uint32)]
         L.h2v_plan_transcript.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p, C.POINTER(C.c_uint32)]
         L.h2v_probe_blake2b_ex.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_uint32, C.c_char_p, C.c_uint32, C.c_void_p]
@@ -740,6 +747,45 @@ def probe_g1_msm_pippenger(scalars, bases_compressed, device: int = 0):
     out = C.create_string_buffer(96)
     check(lib().h2v_probe_g1_msm_pippenger(device, n, sc, b"".join(bases_compressed), out))
     return _unxy(out.raw)
+
+
+PIP_DUMP_DWORDS = 20514   # H2V_PIP_DUMP_DWORDS
+
+
+def probe_g1_msm_pippenger_ex(problems, acc_grid_cap: int = 0, dump: bool = False, device: int = 0):
+    """h2v_probe_g1_msm_pippenger_ex: 1 or 2 bucket MSMs side by side in the same launches.  Each problem is a dict with
+    scalars (ints), points (48-byte compressed: the pool), and optionally halves (2), n_pool0 (the pool size: one pool) and pidx
+    (None: the identity map).  Returns one (sum, dump) per problem: the affine sum or None, and - with dump=True - a dict with
+    the launcher's shape c, W, NB, chain, the accumulate grid acc_blocks, and cls, off, order as k_pip_scan wrote them."""
+    recs = (PipProbe * len(problems))()
+    keep = []
+    for r, p in zip(recs, problems):
+        scalars, points, pidx = p["scalars"], p["points"], p.get("pidx")
+        r.n, r.halves = len(scalars), p.get("halves", 2)
+        r.scalars = b"".join(int(s).to_bytes(32, "little") for s in scalars)
+        r.n_points = len(points)
+        r.n_pool0 = len(points) if p.get("n_pool0") is None else p["n_pool0"]
+        r.points_compressed = b"".join(points)
+        out = C.create_string_buffer(96)
+        idx = None if pidx is None else (C.c_uint32 * len(pidx))(*pidx)
+        if pidx is not None and len(pidx) != len(scalars):
+            raise ValueError("one point index per scalar")
+        dmp = (C.c_uint32 * PIP_DUMP_DWORDS)() if dump else None
+        r.pidx = idx if idx is not None else C.POINTER(C.c_uint32)()
+        r.out_xy_be = C.cast(out, C.c_void_p)
+        r.dump = dmp if dmp is not None else C.POINTER(C.c_uint32)()
+        keep.append((out, idx, dmp))
+    check(lib().h2v_probe_g1_msm_pippenger_ex(device, len(problems), recs, acc_grid_cap))
+    res = []
+    for out, _, dmp in keep:
+        d = None
+        if dmp is not None:
+            c, W, NB, chain, blocks = dmp[0:5]
+            nb = W * NB
+            d = {"c": c, "W": W, "NB": NB, "chain": chain, "acc_blocks": blocks, "cls": list(dmp[5:33]),
+                 "off": list(dmp[33:33 + nb + 1]), "order": list(dmp[34 + nb:34 + 2 * nb])}
+        res.append((_unxy(out.raw), d))
+    return res
 
 
 def probe_pairing(plan: DevicePlan, p1_list, p2_list):

@@ -2617,9 +2617,12 @@ static void pip_bind(const PipWs &w, PipArgs &a) {
     a.pts28 = w.pts28; a.dig = w.dig; a.cnt = w.cnt; a.off = w.off; a.order = w.order; a.cls = w.cls; a.list = w.list; a.partial = w.partial; a.wsum = w.wsum;
 }
 // Enqueues the six kernels of one or two bucket MSMs (np problems side by side in every launch) on `st`.
-// a[]: n, halves, scal, pidx, pool0 / n_pool0 / pool1, out filled in.  ev (optional): 4 events recorded at the start,
-// before and after k_pip_accumulate, and at the end.
-static int pip_launch(const PipWs *const *ws, PipArgs *a, uint32_t np, hipStream_t st, hipEvent_t *ev) {
+// a[]: n, halves, scal, pidx, pool0 / n_pool0 / pool1, out filled in; the shape (c, W, NB, chain) is filled in here.  ev (optional):
+// 4 events recorded at the start, before and after k_pip_accumulate, and at the end.  acc_grid_cap (test-only, 0 = none: what every
+// production call passes) caps the grid of k_pip_accumulate below the host's estimate, so that its blocks walk several logical
+// blocks each; acc_blocks_out (optional) receives the number of blocks that launch had.
+static int pip_launch(const PipWs *const *ws, PipArgs *a, uint32_t np, hipStream_t st, hipEvent_t *ev, uint32_t acc_grid_cap = 0,
+                      uint32_t *acc_blocks_out = nullptr) {
     PipArgs2 a2 = {};
     uint32_t max_n = 0, max_W = 0, max_NB = 0, max_acc_blocks = 0;
     for (uint32_t q = 0; q < np; q++) {
@@ -2634,6 +2637,8 @@ static int pip_launch(const PipWs *const *ws, PipArgs *a, uint32_t np, hipStream
         const uint32_t blocks = (uint32_t)((lanes + 255) / 256);
         max_acc_blocks = blocks > max_acc_blocks ? blocks : max_acc_blocks;
     }
+    if (acc_grid_cap && acc_grid_cap < max_acc_blocks) max_acc_blocks = acc_grid_cap;
+    if (acc_blocks_out) *acc_blocks_out = max_acc_blocks;
     if (ev) HIPCHK(hipEventRecord(ev[0], st));
     for (uint32_t q = 0; q < np; q++) HIPCHK(hipMemsetAsync(a[q].cnt, 0, (size_t)a[q].W * a[q].NB * 4, st));
     if (max_n) hipLaunchKernelGGL(k_pip_digits, dim3((max_n + 255) / 256, np), dim3(256), 0, st, a2);
@@ -3947,32 +3952,85 @@ extern "C" int h2v_probe_g1_msm_fixed(const h2v_plan *p, uint32_t n, uint32_t k,
     return H2V_OK;
 }
 
-// sum_n s_n * P_n through the bucket MSM: n scalars (32 B LE, < r) and n compressed bases; out 96 B affine big-endian
-extern "C" int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t *scalars, const uint8_t *bases_compressed, uint8_t *out_xy_be) {
+// The bucket MSM on its own, through pip_alloc / pip_launch as the RLC mode calls them: 1 or 2 problems side by side in every launch,
+// each with its own term count, halves, scalars, point pool (compressed; decompressed here; split into pool0 / pool1 at n_pool0,
+// which live in separate allocations) and optional index map; the grid of k_pip_accumulate capped at acc_grid_cap blocks (0: not
+// capped); per problem an optional dump of what the launcher chose and k_pip_scan wrote (include/h2v.h has the layout).
+extern "C" int h2v_probe_g1_msm_pippenger_ex(int device, uint32_t n_problems, const h2v_pip_probe *pr, uint32_t acc_grid_cap) {
     int rc = pick_device(device);
     if (rc) return rc;
-    if (!scalars || !bases_compressed || !out_xy_be || n == 0 || n > (1u << 24)) return fail(H2V_E_ARG, "bad argument");
+    if (!pr || n_problems < 1 || n_problems > 2) return fail(H2V_E_ARG, "bad argument");
+    static_assert(H2V_PIP_DUMP_DWORDS == 5 + PIP_CLS_DW + 2 * PIP_MAX_W * (1u << (PIP_MAX_C - 1)) + 1, "h2v.h: the dump holds the largest shape");
+    for (uint32_t q = 0; q < n_problems; q++) {
+        const h2v_pip_probe &p = pr[q];
+        if (!p.scalars || !p.points_compressed || !p.out_xy_be || p.n == 0 || p.n > (1u << 24) || p.n_points == 0 || p.n_points > (1u << 24) ||
+            (p.halves != 1 && p.halves != 2) || p.n_pool0 > p.n_points || (!p.pidx && p.n != p.n_points))
+            return fail(H2V_E_ARG, "bad argument");
+        if (p.pidx)
+            for (uint32_t i = 0; i < p.n; i++)
+                if (p.pidx[i] >= p.n_points) return fail(H2V_E_ARG, "point index " + std::to_string(p.pidx[i]) + " is outside the pool");
+        if (p.halves == 1)
+            for (uint32_t i = 0; i < p.n; i++)
+                for (int k = 16; k < 32; k++)
+                    if (p.scalars[(size_t)i * 32 + k]) return fail(H2V_E_ARG, "halves = 1 takes scalars below 2^128");
+    }
     ProbeOpts probe_opts;
     MiniPlan mp;
-    DevBuf din, doff, dsc, dpts, dvalid, dres, dout;
-    if (mp.build(1, 0, nullptr, nullptr) || upload_offsets(doff, n, 48) || din.alloc((size_t)n * 48) || dsc.alloc((size_t)n * 32) ||
-        dpts.alloc((size_t)n * 96) || dvalid.alloc(n) || dres.alloc(144) || dout.alloc(96)) return fail(H2V_E_DEVICE, "probe setup failed");
-    HIPCHK(hipMemcpy(din.p, bases_compressed, (size_t)n * 48, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dsc.p, scalars, (size_t)n * 32, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_g1_decompress, dim3((n + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), (uint32_t *)nullptr, 0u, (uint8_t *)nullptr);
-    PipWs pw;
-    if ((rc = pip_alloc(pw, n, 2))) return rc;
-    PipArgs a = {};
-    a.n = n; a.halves = 2; a.scal = dsc.as<uint32_t>(); a.pidx = nullptr; a.pool0 = dpts.as<uint32_t>(); a.n_pool0 = n; a.pool1 = nullptr; a.out = dres.as<uint32_t>();
-    const PipWs *pws[1] = {&pw};
-    rc = pip_launch(pws, &a, 1, nullptr, nullptr);
-    if (rc == H2V_OK) {
-        hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 1u, 1, dres.as<uint32_t>(), dout.as<uint8_t>());
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) rc = fail(H2V_E_DEVICE, "bucket MSM kernels failed");
-        else if (hipMemcpy(out_xy_be, dout.p, 96, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(H2V_E_DEVICE, "download failed");
+    struct Prob {
+        DevBuf din, doff, dsc, didx, dpts, dpool1, dvalid, dres;
+        PipWs pw;
+        ~Prob() { pip_free(pw); }
+    } P[2];
+    DevBuf dout;
+    if (mp.build(1, 0, nullptr, nullptr) || dout.alloc(2 * 96)) return fail(H2V_E_DEVICE, "probe setup failed");
+    PipArgs a[2] = {};
+    const PipWs *pws[2] = {&P[0].pw, &P[1].pw};
+    for (uint32_t q = 0; q < n_problems; q++) {
+        const h2v_pip_probe &p = pr[q];
+        Prob &b = P[q];
+        const uint32_t n1 = p.n_points - p.n_pool0;
+        if (upload_offsets(b.doff, p.n_points, 48) || b.din.alloc((size_t)p.n_points * 48) || b.dsc.alloc((size_t)p.n * 32) ||
+            b.dpts.alloc((size_t)p.n_points * 96) || b.dvalid.alloc(p.n_points) || b.dres.alloc(144) || (p.pidx && b.didx.alloc((size_t)p.n * 4)) ||
+            (n1 && b.dpool1.alloc((size_t)n1 * 96))) return fail(H2V_E_DEVICE, "probe setup failed");
+        HIPCHK(hipMemcpy(b.din.p, p.points_compressed, (size_t)p.n_points * 48, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(b.dsc.p, p.scalars, (size_t)p.n * 32, hipMemcpyHostToDevice));
+        if (p.pidx) HIPCHK(hipMemcpy(b.didx.p, p.pidx, (size_t)p.n * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_g1_decompress, dim3((p.n_points + 63) / 64), dim3(128), 0, nullptr, mp.d, p.n_points, b.din.as<uint8_t>(), b.doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, b.dpts.as<uint32_t>(), b.dvalid.as<uint8_t>(), (uint32_t *)nullptr, 0u, (uint8_t *)nullptr);
+        if (n1) {   // the records from n_pool0 on move to an allocation of their own and read as infinity where they were
+            HIPCHK(hipMemcpy(b.dpool1.p, b.dpts.as<uint8_t>() + (size_t)p.n_pool0 * 96, (size_t)n1 * 96, hipMemcpyDeviceToDevice));
+            HIPCHK(hipMemset(b.dpts.as<uint8_t>() + (size_t)p.n_pool0 * 96, 0, (size_t)n1 * 96));
+        }
+        if ((rc = pip_alloc(b.pw, p.n, p.halves))) return rc;
+        // a bucket sum, window value or result the kernels fail to write must read as infinity, not as what an earlier run of the
+        // same input left at the address the allocator hands out again
+        HIPCHK(hipMemset(b.pw.partial, 0xff, (size_t)PIP_MAX_W * (1u << (PIP_MAX_C - 1)) * PIP_PART_DW * 4));
+        HIPCHK(hipMemset(b.pw.wsum, 0xff, (size_t)PIP_MAX_W * PIP_PART_DW * 4));
+        HIPCHK(hipMemset(b.dres.p, 0, 144));
+        a[q].n = p.n; a[q].halves = p.halves; a[q].scal = b.dsc.as<uint32_t>(); a[q].pidx = p.pidx ? b.didx.as<uint32_t>() : nullptr;
+        a[q].pool0 = b.dpts.as<uint32_t>(); a[q].n_pool0 = p.n_pool0; a[q].pool1 = n1 ? b.dpool1.as<uint32_t>() : nullptr; a[q].out = b.dres.as<uint32_t>();
     }
-    pip_free(pw);
-    return rc;
+    uint32_t acc_blocks = 0;
+    if ((rc = pip_launch(pws, a, n_problems, nullptr, nullptr, acc_grid_cap, &acc_blocks))) return rc;
+    for (uint32_t q = 0; q < n_problems; q++)
+        hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 1u, 1, P[q].dres.as<uint32_t>(), dout.as<uint8_t>() + 96 * q);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(H2V_E_DEVICE, "bucket MSM kernels failed");
+    for (uint32_t q = 0; q < n_problems; q++) {
+        HIPCHK(hipMemcpy(pr[q].out_xy_be, dout.as<uint8_t>() + 96 * q, 96, hipMemcpyDeviceToHost));
+        if (uint32_t *d = pr[q].dump) {
+            const uint32_t nb = a[q].W * a[q].NB;
+            d[0] = a[q].c; d[1] = a[q].W; d[2] = a[q].NB; d[3] = a[q].chain; d[4] = acc_blocks;
+            HIPCHK(hipMemcpy(d + 5, P[q].pw.cls, PIP_CLS_DW * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(d + 5 + PIP_CLS_DW, P[q].pw.off, (size_t)(nb + 1) * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(d + 5 + PIP_CLS_DW + nb + 1, P[q].pw.order, (size_t)nb * 4, hipMemcpyDeviceToHost));
+        }
+    }
+    return H2V_OK;
+}
+// sum_n s_n * P_n through the bucket MSM: n scalars (32 B LE, < r) and n compressed bases; out 96 B affine big-endian
+extern "C" int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t *scalars, const uint8_t *bases_compressed, uint8_t *out_xy_be) {
+    h2v_pip_probe p = {};
+    p.n = n; p.halves = 2; p.scalars = scalars; p.n_points = n; p.n_pool0 = n; p.points_compressed = bases_compressed; p.out_xy_be = out_xy_be;
+    return h2v_probe_g1_msm_pippenger_ex(device, 1, &p, 0);
 }
 // The two sums of the most recent H2V_MIXED_FOLD_MSM call on ws - L then R, affine, 96 bytes big-endian x || y each, all-zero for
 // infinity - whether its check passed or the call fell back (the second pass does not touch them).  The call has synchronised its
