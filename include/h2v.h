@@ -137,7 +137,9 @@ void h2v_workspace_free(h2v_workspace *ws);
  * pairing kernels of others; accept[] / status[] are written in place, chunk by chunk, and the caller's stream waits for
  * the last one (unless joins are deferred, below).  Device memory is n_lanes x chunk proofs' worth, whatever max_batch is.
  * Verdicts never depend on n_lanes or chunk (tests/test_gpu_parity.py::test_verdicts_do_not_depend_on_the_chunking); in
- * RLC mode every chunk is its own batch check.
+ * RLC mode every chunk is its own batch check with coefficients of its own: chunk c draws r_i from i = the position within the
+ * chunk, under the call's seed with 0x9e3779b9 * (c + 1) xored into its last 32-bit word (the one chunk of a call that fits a
+ * chunk is chunk 0 and carries that tweak too; an ordinary workspace hashes the call's seed as it is).
  *   n_lanes = 0 / chunk = 0: the library's choice (chunk = 4096 proofs whatever the plan and whatever max_batch - the largest
  *   single call - is: small calls are gathered into the lanes, COALESCING below; 16 lanes, of which the per-proof mode cycles
  *   through 8 - all 16 for launches too small to fill the chip: h2v_workspace_depth).  An explicit chunk is cut to max_batch.
@@ -177,8 +179,12 @@ int h2v_workspace_create_multi(const h2v_plan *const *plans, uint32_t n_plans, u
  * the caller beyond what deferred joins already say - inputs untouched and accept[] / status[] unread until the join - but a
  * stream of 64-proof calls costs a 1024-proof launch per sixteen of them instead of sixteen chains of lone waves (the per-GPU
  * shares of a batch cut over eight GPUs: DESIGN.md section 6.1).  Verdicts do not depend on it.  h2v_workspace_timings of such
- * a call reports its share of the group's launch.  RLC calls are gathered among themselves: ONE batch check over the group, with
- * the coefficients of its first call's seed; accept[] stays per proof and exact, h2v_workspace_rlc_result of each call reports the
+ * a call reports its share of the group's launch.  RLC calls are gathered among themselves: ONE batch check over the group.  Its
+ * coefficients: the SEED is that of the call that opened the group - the OS's draw for that call, or its given seed with the call
+ * count that call mixed in; every later call of the group still draws a seed (a given one ticks the count), which is not used -
+ * and the POSITION of a proof is counted through the group: the number of proofs gathered before its call plus its index within
+ * the call (no chunk tweak: a group is one piece).  So no two proofs of a group share a coefficient, whichever calls they came in
+ * (tests/test_batch_cancellation_gpu.py::test_coalesced_rlc_group).  accept[] stays per proof and exact, h2v_workspace_rlc_result of each call reports the
  * GROUP's batch verdict (a rejecting proof of a neighbouring call fails the check for all of them) and the call's share of the
  * times.  An open group does not start by itself: a caller that stops submitting for a while and wants the GPU to get on with
  * what it has calls h2v_workspace_join(ws, stream) with a stream of its own - that runs the open groups and does not block the
@@ -296,7 +302,8 @@ int h2v_verify_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_
  * fell_back = 1 / batch_accepted = 0 say that the per-proof kernels produced it.  H2V_OPT_RLC_ROUTE = -1 switches routing off. */
 #define H2V_RLC_SEED_GIVEN 1u /* TEST ONLY: soundness rests on the seed being unpredictable to the provers; without this flag
                                * the library draws 32 bytes from the OS per call (getrandom) and fails closed.  With it, a
-                               * process-wide call counter is still mixed into the seed, so repeated calls differ. */
+                               * process-wide call counter is still mixed into the seed, so repeated calls differ: the count of
+                               * seeded calls of EVERY form so far (RLC, pair check, mixed), xored into seed words 5 (low) and 6. */
 #define H2V_RLC_ONE_STREAM 2u /* everything on the caller's stream (decompression before the combiner instead of beside it):
                                * 0.3 ms more per batch alone, but one stream per batch for callers that keep many batches in
                                * flight - more of them fit the hardware queues (measured: 2.47 M proofs/s with 7 in flight
@@ -401,8 +408,9 @@ int h2v_check_pairs_rlc_device(const h2v_plan *plan, uint64_t n, const uint8_t *
  *   (msm_terms: the pairs of the tail's last chunk - n on a workspace whose chunk holds the call).  On a laned workspace the tail
  *   is cut into chunks like any check call, and every chunk is its own batch check.  fell_back = 1: that verdict is "failed".
  *   SEED: h2v_verify_batch_rlc's rules.  ONE seed per call; the coefficient of proof i is drawn from its position in the CALL
- *   (within its chunk of the tail), never from its position within its key - with repeated coefficients two proofs of
- *   different keys could cancel each other's error.
+ *   (within its chunk of the tail - every chunk a check of its own under its own tweak of the seed, as for any RLC call on a laned
+ *   workspace, and h2v_workspace_create_multi makes a laned one), never from its position within its key - with repeated
+ *   coefficients two proofs of different keys could cancel each other's error.
  *   H2V_MIXED_FOLD_MSM (only together with H2V_MIXED_RLC; alone: H2V_E_ARG): the reference's whole batch_verify - every
  *   proof's DualMSM scaled by a random coefficient, added, ONE MSM and ONE pairing for the call.  H2V_MIXED_RLC alone folds only
  *   the pairings: every proof still runs its own ladder MSM.  With the flag, a plan that has the batch form of

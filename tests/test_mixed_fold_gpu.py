@@ -5,7 +5,6 @@ atms_with_lookups listed without one, shuffled: 145 proofs, which cross a 64-lan
 and a key without the batch form (ivc), and on 4 lanes x 40 run in chunks that are no multiples of 64.  Expectations come from
 the CPU oracle, from construction, from the per-key h2v_verify_batch_device status words and, for the sums, from the big-integer
 model (bls12_381.py) - never from the call under test."""
-import hashlib
 import os
 import random
 import struct
@@ -14,6 +13,7 @@ import subprocess
 import pytest
 
 from plutus_halo2_verifier_gen_amd import bls12_381 as bls, synth
+from tests.cancel import coeff as _coeff
 from tests.test_gpu_parity import be  # noqa: F401  (module fixture)
 from tests.test_mixed_keys import COMMON_S, MIXED_KEYS, PKG, ROOT
 from tests.test_mixed_keys_gpu import LISTED, SEED, Mix, _DeviceCall, _interleaved, _per_key_device, _want_status, fx  # noqa: F401
@@ -131,16 +131,6 @@ def test_only_pre_pairing_rejects_do_not_fall_back(be, fx):
 
 
 # ---- 4
-def _coeff(seed, counter, pos):
-    """r of call position `pos`: low 128 bits of blake2b-256(seed' || LE32(pos)), 1 if 0.  seed' is the given seed with the
-    library's process-wide count of seeded calls mixed into words 5 and 6 (include/h2v.h: H2V_RLC_SEED_GIVEN)."""
-    w = list(struct.unpack("<8I", seed))
-    w[5] ^= counter & 0xffffffff
-    w[6] ^= counter >> 32
-    r = int.from_bytes(hashlib.blake2b(struct.pack("<8I", *w) + struct.pack("<I", pos), digest_size=32).digest()[:16], "little")
-    return r or 1
-
-
 def _model_l(points, seed, counter):
     acc = None
     for pos, p in enumerate(points):
