@@ -62,9 +62,12 @@ struct Six {
 struct SixF2 { F28 re, im; };
 struct SixRegs { F28Regs re, im; };
 
-H2V_DI uint32_t *six_slot(const Six &c, int s) {
-    return coop_lds + (s < SIX_SHARED_BASE ? c.grp_off + s * SIX_SLOT_DW : (s - SIX_SHARED_BASE) * SIX_SLOT_DW);
+H2V_DI int six_slot_dw(const Six &c, int s) {
+    return s < SIX_SHARED_BASE ? c.grp_off + s * SIX_SLOT_DW : (s - SIX_SHARED_BASE) * SIX_SLOT_DW;
 }
+H2V_DI uint32_t *six_slot(const Six &c, int s) { return coop_lds + six_slot_dw(c, s); }
+// ... of slot byte b of a table dword
+H2V_DI uint32_t *six_slot_of(const Six &c, const uint32_t w, const int b) { return six_slot(c, (int)__builtin_amdgcn_ubfe(w, 8 * b, 8)); }
 H2V_DI void six_store(uint32_t *p, const F28 &a) {   // limbs as staged (carried, or the doubled operands' 2^29)
     uint2 *q = reinterpret_cast<uint2 *>(p);
 #pragma unroll
@@ -75,35 +78,62 @@ H2V_DI void six_store(uint32_t *p, const Fp &a) {
     f28_from_fp(t, a);
     six_store(p, t);
 }
-// Two operands with 64-bit LDS reads (slots are 8-byte aligned 56-byte records); one asm block for the reason given at
-// coop_load28_pair.
-#define SIX_RD7(o0, o1, o2, o3, o4, o5, o6, a)                                                                              \
-    "ds_read_b64 %" #o0 ", %" #a "\n\tds_read_b64 %" #o1 ", %" #a " offset:8\n\tds_read_b64 %" #o2 ", %" #a " offset:16\n\t"     \
-    "ds_read_b64 %" #o3 ", %" #a " offset:24\n\tds_read_b64 %" #o4 ", %" #a " offset:32\n\tds_read_b64 %" #o5 ", %" #a " offset:40\n\t" \
-    "ds_read_b64 %" #o6 ", %" #a " offset:48\n\t"
-H2V_DI void six_load_pair(uint32_t (&x)[14], uint32_t (&y)[14], const uint32_t *px, const uint32_t *py) {
-    const uint32_t ax = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)px;
-    const uint32_t ay = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)py;
-    u32x2_t a0, a1, a2, a3, a4, a5, a6, b0, b1, b2, b3, b4, b5, b6;
-    asm volatile(SIX_RD7(0, 1, 2, 3, 4, 5, 6, 14) SIX_RD7(7, 8, 9, 10, 11, 12, 13, 15) "s_waitcnt lgkmcnt(0)"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(a5), "=&v"(a6), "=&v"(b0), "=&v"(b1), "=&v"(b2), "=&v"(b3),
-                   "=&v"(b4), "=&v"(b5), "=&v"(b6)
-                 : "v"(ax), "v"(ay)
-                 : "memory");
-    x[0] = a0.x; x[1] = a0.y; x[2] = a1.x; x[3] = a1.y; x[4] = a2.x; x[5] = a2.y; x[6] = a3.x; x[7] = a3.y;
-    x[8] = a4.x; x[9] = a4.y; x[10] = a5.x; x[11] = a5.y; x[12] = a6.x; x[13] = a6.y;
-    y[0] = b0.x; y[1] = b0.y; y[2] = b1.x; y[3] = b1.y; y[4] = b2.x; y[5] = b2.y; y[6] = b3.x; y[7] = b3.y;
-    y[8] = b4.x; y[9] = b4.y; y[10] = b5.x; y[11] = b5.y; y[12] = b6.x; y[13] = b6.y;
+// Operand fetches of the squaring runs and the line products: ISSUE and ARRIVAL are separate steps, so that the reads of the NEXT
+// operands are in flight while the 196 multiply-adds of the current product issue, and the wave meets their s_waitcnt after the
+// product, when the data has long arrived.
+// With every hot kernel at 248-256 registers a SIMD holds two waves, and while one of them sits in a wait the other issues
+// v_mad_u64_u32 at half rate (profiles/r04_imad_ubench.txt).
+//   six_issue    seven 64-bit LDS loads per operand (slots are 8-byte aligned 56-byte records), VOLATILE: they keep their place
+//                among the pins below.  The waits stay the compiler's: it puts the s_waitcnt in front of the first instruction
+//                that reads a fetched register, which is the arrival pin - no hand-written wait, nothing to get wrong when the
+//                register allocator moves a fetched value.  (The asm block of coop_load28_pair answers the optimiser re-cutting
+//                128-BIT loads; these are 64-bit and stay whole.)
+//   six_arrive   an empty asm that reads and writes every register of two fetched operands: the compiler's wait stands in front of
+//                it, no consumer of the operands is scheduled above it - and, given the CURRENT product's operands after the
+//                issue of the next ones, that product cannot start above the issue.
+//   six_done     an empty asm that reads and writes the 27 product columns of an accumulator set (column 27 holds no product and
+//                stays a constant, not a register): the product cannot end below it.  Asm
+//                statements and volatile loads keep their order, so  issue(next); arrive(current) ... product ... done(set);
+//                arrive(next)  is what the wave executes.
+// Program order is the one rule for correctness: the block is one wave and LDS executes in order, so a fetch may stand anywhere
+// after the last store to its slot (and the barrier that publishes another lane's store) and before the next store to it.
+struct SixOp { u32x2_t v[7]; };
+H2V_DI void six_issue(SixOp &o, const uint32_t *p) {
+    const volatile __attribute__((address_space(3))) u32x2_t *q = (const volatile __attribute__((address_space(3))) u32x2_t *)p;
+#pragma unroll
+    for (int i = 0; i < 7; i++) o.v[i] = q[i];
 }
-H2V_DI void six_load(uint32_t (&x)[14], const uint32_t *px) {
-    const uint32_t ax = (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) uint32_t *)px;
-    u32x2_t a0, a1, a2, a3, a4, a5, a6;
-    asm volatile(SIX_RD7(0, 1, 2, 3, 4, 5, 6, 7) "s_waitcnt lgkmcnt(0)"
-                 : "=&v"(a0), "=&v"(a1), "=&v"(a2), "=&v"(a3), "=&v"(a4), "=&v"(a5), "=&v"(a6)
-                 : "v"(ax)
-                 : "memory");
-    x[0] = a0.x; x[1] = a0.y; x[2] = a1.x; x[3] = a1.y; x[4] = a2.x; x[5] = a2.y; x[6] = a3.x; x[7] = a3.y;
-    x[8] = a4.x; x[9] = a4.y; x[10] = a5.x; x[11] = a5.y; x[12] = a6.x; x[13] = a6.y;
+H2V_DI void six_arrive(SixOp &a, SixOp &b) {
+    asm volatile(""
+                 : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(a.v[2]), "+v"(a.v[3]), "+v"(a.v[4]), "+v"(a.v[5]), "+v"(a.v[6]), "+v"(b.v[0]), "+v"(b.v[1]),
+                   "+v"(b.v[2]), "+v"(b.v[3]), "+v"(b.v[4]), "+v"(b.v[5]), "+v"(b.v[6]));
+}
+H2V_DI void six_arrive(SixOp &a) {
+    asm volatile("" : "+v"(a.v[0]), "+v"(a.v[1]), "+v"(a.v[2]), "+v"(a.v[3]), "+v"(a.v[4]), "+v"(a.v[5]), "+v"(a.v[6]));
+}
+H2V_DI void six_arrive(uint32_t (&a)[14], uint32_t (&b)[14]) {   // (limb sums: operands that were not fetched as they are)
+    asm volatile(""
+                 : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8]), "+v"(a[9]),
+                   "+v"(a[10]), "+v"(a[11]), "+v"(a[12]), "+v"(a[13]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]),
+                   "+v"(b[6]), "+v"(b[7]), "+v"(b[8]), "+v"(b[9]), "+v"(b[10]), "+v"(b[11]), "+v"(b[12]), "+v"(b[13]));
+}
+H2V_DI void six_done(uint64_t (&c)[28]) {
+    asm volatile(""
+                 : "+v"(c[0]), "+v"(c[1]), "+v"(c[2]), "+v"(c[3]), "+v"(c[4]), "+v"(c[5]), "+v"(c[6]), "+v"(c[7]), "+v"(c[8]), "+v"(c[9]),
+                   "+v"(c[10]), "+v"(c[11]), "+v"(c[12]), "+v"(c[13]), "+v"(c[14]), "+v"(c[15]), "+v"(c[16]), "+v"(c[17]), "+v"(c[18]),
+                   "+v"(c[19]), "+v"(c[20]), "+v"(c[21]), "+v"(c[22]), "+v"(c[23]), "+v"(c[24]), "+v"(c[25]), "+v"(c[26]));
+}
+H2V_DI void six_limbs(uint32_t (&x)[14], const SixOp &o) {
+#pragma unroll
+    for (int i = 0; i < 7; i++) { x[2 * i] = o.v[i].x; x[2 * i + 1] = o.v[i].y; }
+}
+H2V_DI void six_load_pair(uint32_t (&x)[14], uint32_t (&y)[14], const uint32_t *px, const uint32_t *py) {   // fetched and waited for
+    SixOp a, b;
+    six_issue(a, px);
+    six_issue(b, py);
+    six_arrive(a, b);
+    six_limbs(x, a);
+    six_limbs(y, b);
 }
 H2V_DI void six_mac(uint64_t (&acc)[28], const uint32_t (&x)[14], const uint32_t (&y)[14]) {
 #pragma unroll
@@ -150,6 +180,8 @@ H2V_DI void six_reduce(F28 &r, uint64_t (&acc)[28]) {
 // and the caller reads it from there (six_result).  A 28-dword struct is returned through private memory by the calling
 // convention: a store, a wait for it, and a load per engine call, ~550 calls per pairing (round 3: the kernel's scratch
 // traffic).  keep (per lane): leave the A slots as they are - the staged input survives (line steps of a skipped loop).
+// The term loop fetches where it uses (six_load_pair): with three accumulator sets and two operand pairs live it is the one place
+// without registers for operands in flight - see DESIGN 4.1.1 for what the overlapped form of this loop cost and measured.
 H2V_DN void six_kara(const Six c, const int tab_row_byte, const int nt, const bool keep, const bool addself) {
     const uint8_t *tab = reinterpret_cast<const uint8_t *>(coop_lds + SIX_TAB_OFF) + tab_row_byte;
     uint64_t U[28], V[28], W[28];
@@ -202,27 +234,60 @@ H2V_DI void six_mac_from(uint64_t (&acc2)[28], const uint64_t (&acc)[28], const 
 // cyclotomic squaring: four products (x + x2) y, P1..P4 (3 slot bytes each; gen_six_tables.py: csqr_table), into three sets
 //   A = P1     B = A + P2 (B starts as a copy of A)     A += P3     C = P4     ->  re = B - C (signed columns), im = A + C,
 // reduced: re below 2.2p, im below 1.2p.  The lane finishes with 3 r -/+ 2 g (six_csqr_run).
-H2V_DI void six_csqr_products(const Six &c, const uint8_t *tab, SixF2 &r) {
+// Fetch schedule (see six_issue): the whole triple of product T + 1 goes under product T - B is not live before P2 and C not before
+// P4, so under P3 the count is two sets, x, y and the next triple - and the read-back of g (the lane's A slots; x itself is not
+// kept in registers while the three sets are live) under the two reductions.  tw: the row's 12 table bytes as three dwords, read
+// once per run by the caller.
+H2V_DI const uint32_t *six_csqr_slot(const Six &c, const uint32_t (&tw)[3], const int b) {
+    return six_slot_of(c, tw[b >> 2], b & 3);
+}
+H2V_DI void six_csqr_products(const Six &c, const uint32_t (&tw)[3], SixF2 &r, SixF2 &g) {
     uint64_t A[28], B[28], C[28];
 #pragma unroll
     for (int i = 0; i < 28; i++) { A[i] = 0; C[i] = 0; }
     B[27] = 0;                       // (column 27 holds no product)
-    uint32_t x[14], x2[14], y[14];
-#define SIX_CSQR_OPS(T)                                                                                  \
+    uint32_t x[14], y[14], x2[14];
+    SixOp fx, fx2, fy;
+#define SIX_CSQR_ISSUE(T)                                                                                \
     do {                                                                                                 \
-        six_load_pair(x, x2, six_slot(c, tab[3 * (T)]), six_slot(c, tab[3 * (T) + 1]));                  \
-        six_load(y, six_slot(c, tab[3 * (T) + 2]));                                                      \
+        six_issue(fx, six_csqr_slot(c, tw, 3 * (T)));                                                    \
+        six_issue(fx2, six_csqr_slot(c, tw, 3 * (T) + 1));                                               \
+        six_issue(fy, six_csqr_slot(c, tw, 3 * (T) + 2));                                                \
+    } while (0)
+#define SIX_CSQR_TAKE()                                                                                  \
+    do {                                                                                                 \
+        six_arrive(fx, fx2);                                                                             \
+        six_arrive(fy);                                                                                  \
+        six_limbs(x, fx);                                                                                \
+        six_limbs(x2, fx2);                                                                              \
+        six_limbs(y, fy);                                                                                \
         _Pragma("unroll") for (int i_ = 0; i_ < 14; i_++) x[i_] += x2[i_];                               \
     } while (0)
-    SIX_CSQR_OPS(0);
+    SIX_CSQR_ISSUE(0);
+    SIX_CSQR_TAKE();
+    SIX_CSQR_ISSUE(1);
+    six_arrive(x, y);
     six_mac(A, x, y);
-    SIX_CSQR_OPS(1);
+    six_done(A);
+    SIX_CSQR_TAKE();
+    SIX_CSQR_ISSUE(2);
+    six_arrive(x, y);
     six_mac_from(B, A, x, y);
-    SIX_CSQR_OPS(2);
+    six_done(B);
+    SIX_CSQR_TAKE();
+    SIX_CSQR_ISSUE(3);
+    six_arrive(x, y);
     six_mac(A, x, y);
-    SIX_CSQR_OPS(3);
+    six_done(A);
+    SIX_CSQR_TAKE();
     six_mac(C, x, y);
-#undef SIX_CSQR_OPS
+#undef SIX_CSQR_ISSUE
+#undef SIX_CSQR_TAKE
+    six_done(C);
+    six_issue(fx, six_slot(c, SIX_SLOT_A + 2 * c.k));
+    six_issue(fy, six_slot(c, SIX_SLOT_A + 2 * c.k + 1));
+    six_done(B);                     // (the reductions start below the issue)
+    six_done(A);
 #pragma unroll
     for (int i = 0; i < 27; i++) {
         B[i] -= C[i];
@@ -230,15 +295,22 @@ H2V_DI void six_csqr_products(const Six &c, const uint8_t *tab, SixF2 &r) {
     }
     six_reduce<true>(r.re, B);
     six_reduce<false>(r.im, A);
+    six_arrive(r.re.l, r.im.l);   // (the reductions end above g's arrival)
+    six_arrive(fx, fy);
+    six_limbs(g.re.l, fx);
+    six_limbs(g.im.l, fy);
 }
 // A RUN of n cyclotomic squarings as one call: the value comes in and goes back through the lane's A slots (staged by the caller,
 // read by six_result), and between two squarings of the run it stays in registers - per squaring: staging (D = 2x into the B slots,
 // M into its slot; x itself is in the A slots already), the four products and two reductions, h = 3 r -/+ 2 g, the fold, and x back
 // into the A slots, which is both the next squaring's staging and the run's result.  g is read back from the A slots after the
 // products (nothing of x stays live while the three accumulator sets are).  Barriers as around every engine call: after the
-// staging, and after the last read (the lane's own g) before any lane writes again.
+// staging, and after the last read (the lane's own g) before any lane writes again.  The next squaring's first fetch stands after
+// the barrier that follows its staging: it reads what this one's A-slot store and that staging wrote.
 H2V_DN void six_csqr_run(const Six c, const int tab_row_byte, const int n) {
-    const uint8_t *tab = reinterpret_cast<const uint8_t *>(coop_lds + SIX_TAB_OFF) + tab_row_byte;
+    static_assert(SIX_TAB_CSQR_B % 4 == 0 && SIX_N_CSQR == 4, "a row of the squaring's table is three dwords");
+    const uint32_t *tabw = coop_lds + SIX_TAB_OFF + (tab_row_byte >> 2);
+    const uint32_t tw[3] = {tabw[0], tabw[1], tabw[2]};
     SixF2 x = six_result(c, SIX_SLOT_A);
     const bool minus = (c.k & 1) == 0;
 #pragma unroll 1
@@ -254,9 +326,8 @@ H2V_DN void six_csqr_run(const Six c, const int tab_row_byte, const int n) {
             six_store(six_slot(c, SIX_C_M(c.k)), m);
         }
         __syncthreads();
-        SixF2 r;
-        six_csqr_products(c, tab, r);
-        const SixF2 g = six_result(c, SIX_SLOT_A);
+        SixF2 r, g;
+        six_csqr_products(c, tw, r, g);
         // h_k = 3 Q_k - 2 g_k (k even) / + 2 g_k (k odd), folded: 3 r + (13p - 2g | 2g) is below 20p (r < 2.2p, g < 6p), the fold
         // brings it below 2p.  (The other engines multiply g by the constants -/+ 2/3 inside the sum: two products more per lane.)
         // The sum goes to the fold UNCARRIED (limbs below 2^31): the fold's own signed carry chain normalises the limbs, and its
@@ -278,17 +349,40 @@ H2V_DN void six_csqr_run(const Six c, const int tab_row_byte, const int n) {
         }
     }
 }
-// one product of two staged slots, reduced (< 2p)
-H2V_DN F28Regs six_prod(const Six c, const int xs, const int ys) {
-    uint64_t acc[28];
-#pragma unroll
-    for (int i = 0; i < 28; i++) acc[i] = 0;
+// The line products of a Miller round as one call: x1 y1 into the lane's T slot, x2 y2 into T slot 6 + k of lanes 0 and 1, each
+// reduced (< 2p).  Both operand pairs are fetched up front (one accumulator set is live: registers are plentiful), so the second
+// product meets no wait.  No operand is a T slot.
+H2V_DN void six_prod2(const Six c, const int xs1, const int ys1) {
+    const int xs2 = SIX_SLOT_LN2 + 2 + (c.k & 1), ys2 = SIX_SLOT_PY2;     // (lanes 0, 1: the parts of b of loop 2)
+    SixOp fx, fy, fx2, fy2;
+    six_issue(fx, six_slot(c, xs1));
+    six_issue(fy, six_slot(c, ys1));
+    six_issue(fx2, six_slot(c, xs2));
+    six_issue(fy2, six_slot(c, ys2));
+    six_arrive(fx, fy);
     uint32_t x[14], y[14];
-    six_load_pair(x, y, six_slot(c, xs), six_slot(c, ys));
-    six_mac(acc, x, y);
     F28 r;
-    six_reduce<false>(r, acc);
-    return f28_pack(r);
+    {
+        uint64_t acc[28];
+#pragma unroll
+        for (int i = 0; i < 28; i++) acc[i] = 0;
+        six_limbs(x, fx);
+        six_limbs(y, fy);
+        six_mac(acc, x, y);
+        six_reduce<false>(r, acc);
+    }
+    if (c.act) six_store(six_slot(c, SIX_SLOT_T + c.k), r);
+    six_arrive(fx2, fy2);
+    {
+        uint64_t acc[28];
+#pragma unroll
+        for (int i = 0; i < 28; i++) acc[i] = 0;
+        six_limbs(x, fx2);
+        six_limbs(y, fy2);
+        six_mac(acc, x, y);
+        six_reduce<false>(r, acc);
+    }
+    if (c.act && c.k < 2) six_store(six_slot(c, SIX_SLOT_T + 6 + c.k), r);
 }
 H2V_DI SixF2 six_unpack(const SixRegs &z) {
     SixF2 r;
@@ -536,12 +630,7 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
                     six_line_store(cn, lane);
                     if (ln + 1 < H2V_MILLER_LINES) cn = six_line_share(plan.six_norm28, ln + 1, lane);
                     __syncthreads();
-                    {
-                        F28Regs z = six_prod(c, xs1, ys1);
-                        if (c.act) six_store(six_slot(c, SIX_SLOT_T + c.k), f28_unpack(z.a, z.b, z.c, z.d));
-                        z = six_prod(c, SIX_SLOT_LN2 + 2 + part, SIX_SLOT_PY2);
-                        if (c.act && c.k < 2) six_store(six_slot(c, SIX_SLOT_T + 6 + c.k), f28_unpack(z.a, z.b, z.c, z.d));
-                    }
+                    six_prod2(c, xs1, ys1);
                     f = six_line<1>(c, f, skip1);                   // (its staging barrier also covers the T slots)
                     f = six_line<2>(c, f, skip2);
                 }
