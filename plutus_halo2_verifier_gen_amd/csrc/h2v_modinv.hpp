@@ -7,7 +7,7 @@
 // Numbers are signed, L limbs of 30 bits (value = sum v[i] 2^(30 i), lower limbs in [0, 2^30), top limb signed).
 // Invariants (as in the published algorithm): d*x = f, e*x = g (mod M) up to the common power of two removed by the
 // exact divisions, |f|, |g| <= M, d, e in (-2M, M).  The loop ends when g == 0; then f = +-1 (M prime, x != 0) and
-// x^-1 = +-d.  Model and cross-check: tests/test_host_logic.py::test_safegcd_model.
+// x^-1 = +-d.  Model: tests/safegcd_model.py; operands by exit path: tests/test_inverter_paths.py, tests/test_inverter_paths_gpu.py.
 #pragma once
 #include <stdint.h>
 // (included by h2v_field.hpp after its H2V_DI / H2V_DN definitions)
@@ -29,7 +29,8 @@ struct ModInv30 {
             c1 &= c2;
             zeta = (zeta ^ c1) - 1;
             f += g & (uint32_t)c1; u += q & c1; v += r & c1;
-            g >>= 1; u <<= 1; v <<= 1;
+            g >>= 1;
+            u = (int32_t)((uint32_t)u << 1); v = (int32_t)((uint32_t)v << 1);   // (u, v may be negative: no signed shift)
         }
         t[0] = u; t[1] = v; t[2] = q; t[3] = r;
         return zeta;
