@@ -113,13 +113,16 @@ class Batch:
 
 
 def _forge_range(args):
-    vk_json, td, lo, hi, seed, ci_identity = args
+    vk_json, td, lo, hi, seed, ci_identity = args   # (worker processes: never with an accumulator hook, see forge_batch)
     vk = VerifyingKey.from_json(vk_json)
     plan = compile_plan(vk)
     return _forge_with_plan(vk, td, plan, lo, hi, seed, ci_identity)
 
 
-def _forge_with_plan(vk: VerifyingKey, td: Trapdoor, plan: Plan, lo: int, hi: int, seed: int, ci_identity: bool):
+def _forge_with_plan(vk: VerifyingKey, td: Trapdoor, plan: Plan, lo: int, hi: int, seed: int, ci_identity: bool, accumulator=None):
+    """accumulator (recursive keys only): a callable (vk, td, rng, inst, i) -> None that writes the accumulator fields of proof
+    i's public inputs in place of ivc.make_accumulator.  The main MSM is forged around whatever it writes, so a hook that
+    writes an invalid accumulator gives a proof whose only defect is the accumulator."""
     fb = fixed_base()
     n_pts = len(plan.points)
     pi_pt = plan.pi_point
@@ -172,7 +175,10 @@ def _forge_with_plan(vk: VerifyingKey, td: Trapdoor, plan: Plan, lo: int, hi: in
         else:
             inst = [rng.randrange(R) for _ in range(vk.n_public_inputs)]
         if vk.recursion_vks is not None:
-            ivc.make_accumulator(vk, td, rng, inst)  # a valid accumulator: the fold keeps the pairing equation true
+            if accumulator is None:
+                ivc.make_accumulator(vk, td, rng, inst)  # a valid accumulator: the fold keeps the pairing equation true
+            else:
+                accumulator(vk, td, rng, inst, i)
         ci_bytes, ci_dlog = None, 0
         if vk.n_committed_instances:
             if ci_identity:
@@ -211,13 +217,17 @@ def _forge_with_plan(vk: VerifyingKey, td: Trapdoor, plan: Plan, lo: int, hi: in
 
 
 def forge_batch(vk: VerifyingKey, td: Trapdoor, n: int, seed: int = 1, workers: Optional[int] = None,
-                plan: Optional[Plan] = None, ci_identity: bool = True) -> Batch:
-    """n accepting proofs for `vk` (all valid)."""
+                plan: Optional[Plan] = None, ci_identity: bool = True, accumulator=None) -> Batch:
+    """n accepting proofs for `vk` (all valid).  accumulator: see _forge_with_plan - the hook of recursive keys that replaces
+    ivc.make_accumulator (the proofs accept only if what it writes is a valid accumulator); it is a Python callable, so it is
+    allowed only where forging stays in this process (workers=1, or n < 64)."""
     if workers is None:
         workers = min(os.cpu_count() or 1, 16)
+    if accumulator is not None and not (n < 64 or workers <= 1):
+        raise ValueError("forge_batch: accumulator= needs in-process forging (workers=1, or n < 64)")
     if n < 64 or workers <= 1:
         plan = plan or compile_plan(vk)
-        parts = [_forge_with_plan(vk, td, plan, 0, n, seed, ci_identity)]
+        parts = [_forge_with_plan(vk, td, plan, 0, n, seed, ci_identity, accumulator)]
     else:
         vk_json = vk.to_json()
         chunks = [(vk_json, td, n * w // workers, n * (w + 1) // workers, seed, ci_identity) for w in range(workers)]

@@ -1,6 +1,9 @@
 """Recursion (IVC) accumulator fold (emitters/aiken.rs:648-757, docs/algorithms.html "Recursion").
 CPU: the big-integer model (ivc.py), the plan compiler and the C oracle agree on layout, fold and verdicts.
-GPU: the device path (accumulator decompression, three extra sums, challenge hash, two fold MSMs) against the oracle."""
+GPU: the device path (accumulator decompression, three extra sums, challenge hash, two fold MSMs) against the oracle.
+The accumulators here are random and generic; the edges (limbs that wrap past p, sums at infinity, a reduction that doubles or
+cancels, the sign boundary of y, small order, scalars 0 and r - 1, the opening point at infinity) are the table of
+tests/ivc_edges.py, held on the CPU by tests/test_ivc_edges.py and on the device by tests/test_ivc_edges_gpu.py."""
 import json
 import random
 
