@@ -475,6 +475,28 @@ int h2v_probe_vm(const h2v_plan *plan, const h2v_batch *batch /* host buffers */
                  uint32_t *status_out /* n */, uint8_t *msm_scalars_out /* n * n_terms * 32, LE */,
                  uint8_t *trace_out /* n * n_trace * 32, LE; NULL unless want_trace */);
 
+/* The G1 decompression launch ALONE on a batch of host buffers, made exactly as the pipelines make it (one launch whose waves
+ * take 64-point units from a queue: the subgroup tests, then the square roots): nothing behind it runs.  The points are those
+ * of proof 0's slots, then proof 1's, ...; a proof has S = n_points + n_ci + 2 * ivc slots: the plan's proof points in plan
+ * order (the last one is the opening proof pi), the committed instance if the plan has one, the left and the right
+ * accumulator point if the plan is recursive.  Every buffer is the caller's, sized for n * S points:
+ *   xy_be         n * S * 96    affine x || y, big-endian canonical; all-zero for infinity and wherever valid == 0
+ *   valid         n * S         1: the encoding is well-formed (compression bit, a canonical x or the one infinity encoding; the
+ *                               proof is not short) and x is on the curve; the point is stored, whether in G1 or not.  Else 0
+ *   valid_sub     n * S         1: the encoding is well-formed and the r-torsion test passed for the curve points with this x
+ *                               (the valid infinity encoding: 1).  It is taken without the square root: where x^3 + 4 is not
+ *                               a square it says nothing, and only valid && valid_sub - "a point of G1" - is the verdict
+ *   tables        n * S * 448   dwords, or NULL: the MSM window tables as the kernel left them - per point [1..8]P, then
+ *                               [1..8]phi(P), each entry x, y as 14 + 14 limbs of 28 bits, Montgomery (R = 2^392), below 2p.
+ *                               Only with with_tables != 0 (the launch is then given the workspace's tables; with 0 it builds
+ *                               none, as the pair checks and the batch-accept forms run it).  The tables of a point with
+ *                               valid == 0 are not written; those of a curve point outside G1 are unspecified
+ *   blocks_out    1             the grid of the launch: blocks of four waves; 2 * ceil(n * S / 64) units go through the queue
+ * Before the launch every output is preset to 0xA5 bytes, so that what the kernel left unwritten shows.
+ * Argument errors return H2V_E_ARG. */
+int h2v_probe_decompress(const h2v_plan *plan, const h2v_batch *batch /* host buffers */, int with_tables,
+                         uint8_t *xy_be, uint8_t *valid, uint8_t *valid_sub, uint32_t *tables /* or NULL */, uint32_t *blocks_out);
+
 /* primitive probes for the GPU parity tests (host buffers; canonical little-endian limbs) */
 int h2v_probe_field(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out);
 int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint8_t *digests);

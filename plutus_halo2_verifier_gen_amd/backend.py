@@ -103,7 +103,7 @@ EXPORTS = [
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
     "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device",
     "h2v_plan_transcript", "h2v_probe_blake2b_ex",
-    "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums",
+    "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums", "h2v_probe_decompress",
 ]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
@@ -168,6 +168,7 @@ def lib():
         L.h2v_trace.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
         L.h2v_probe_vm.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.h2v_probe_decompress.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.h2v_probe_field.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_f28_dot2.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_blake2b.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
@@ -623,6 +624,21 @@ def probe_vm(plan: DevicePlan, proofs: bytes, proof_off, instances: bytes, commi
         trace = [{plan.trace_slots[k]: int.from_bytes(raw[32 * (i * nt + k):32 * (i * nt + k + 1)], "little") for k in range(nt)}
                  for i in range(n)]
     return list(st[:n]), scal, trace
+
+
+def probe_decompress(plan: DevicePlan, slots: int, proofs: bytes, proof_off, instances: bytes, committed: Optional[bytes], tables: bool = True):
+    """h2v_probe_decompress: the decompression launch of the pipelines alone on a batch.  slots = point slots per proof (proof
+    points + committed instance + 2 accumulator points of a recursive plan).  Returns (xy, valid, valid_sub, tab, blocks) over
+    the n * slots points, proof by proof: xy = 96 bytes x || y big-endian per point in one bytes object, valid / valid_sub = one
+    byte per point, tab = 1792 bytes (448 little-endian dwords) per point or None without `tables` (the launch then builds
+    none), blocks = the grid of the launch."""
+    n, b, _keep = plan._host_batch(proofs, proof_off, instances, committed)
+    m = max(1, n * slots)
+    xy, valid, sub = C.create_string_buffer(96 * m), C.create_string_buffer(m), C.create_string_buffer(m)
+    tab = C.create_string_buffer(1792 * m) if tables else None
+    blocks = C.c_uint32()
+    check(lib().h2v_probe_decompress(plan.handle, C.byref(b), 1 if tables else 0, xy, valid, sub, tab, C.byref(blocks)))
+    return xy.raw, valid.raw, sub.raw, tab.raw if tables else None, blocks.value
 
 
 def probe_field(op: int, a_list, b_list, device: int = 0):

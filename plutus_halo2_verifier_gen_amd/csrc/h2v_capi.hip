@@ -1461,11 +1461,12 @@ static Unit unit_of_pairs(UnitKind kind, const h2v_plan *p, uint64_t n, const ui
 static int fold_pairs_tail(const Unit &u, const uint32_t *er2, const uint32_t *el2, h2v_workspace *w, CallRec &rec, hipStream_t st);
 // Decompression: ONE launch whose waves (at most one per SIMD) take 64-point units from a queue - all subgroup tests,
 // then all square roots (k_g1_decompress_queue).  v: the plan, or a view of it (pair_view); tab: where the MSM window tables
-// go (NULL: none are built).
+// go (NULL: none are built); blocks_out (h2v_probe_decompress): the grid of the launch.
 static int launch_decompress(const H2vDevPlan &v, uint32_t n, const uint8_t *src, const uint64_t *off, const uint8_t *ci, const uint8_t *inst,
-                             h2v_workspace *w, uint32_t *tab, hipStream_t st) {
+                             h2v_workspace *w, uint32_t *tab, hipStream_t st, uint32_t *blocks_out = nullptr) {
     const uint32_t dec_grid = (n * H2V_SLOTS(v) + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
     const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
+    if (blocks_out) *blocks_out = blocks;
     HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
     hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, src, off, ci, inst, w->pts, w->valid, tab, w->valid_sub, w->dec_ctr, dec_grid);
     return H2V_OK;
@@ -4082,6 +4083,49 @@ extern "C" int h2v_probe_vm(const h2v_plan *p, const h2v_batch *b, int want_trac
         if (hipMemcpy(status_out, ws->status, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(msm_scalars_out, ws->scalars, sc_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
             (want_trace && hipMemcpy(trace_out, ws->trace, tr_bytes, hipMemcpyDeviceToHost) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
+    } while (0);
+    h2v_workspace_free(ws);
+    return rc;
+}
+// The decompression launch alone, on a batch, exactly as the pipelines make it (launch_decompress on a staged batch, with or
+// without the window tables): every per-point output of k_g1_decompress_queue and the grid it ran on.  The outputs are preset
+// (points, verdicts and tables to 0xA5 bytes), so what the kernel left unwritten is visible as such.
+extern "C" int h2v_probe_decompress(const h2v_plan *p, const h2v_batch *b, int with_tables, uint8_t *xy_be, uint8_t *valid_out, uint8_t *valid_sub_out,
+                                    uint32_t *tables_out, uint32_t *blocks_out) {
+    if (!p || !b || !xy_be || !valid_out || !valid_sub_out || !blocks_out) return fail(H2V_E_ARG, "null argument");
+    if (b->n == 0 || b->n > (1ull << 24)) return fail(H2V_E_ARG, "batch size out of range");
+    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null batch buffers");
+    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
+    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
+    if (tables_out && !with_tables) return fail(H2V_E_ARG, "tables_out goes with with_tables");
+    ALIVE(p);
+    HIPCHK(hipSetDevice(p->device));
+    const uint32_t n = (uint32_t)b->n;
+    const H2vDevPlan &d = p->d;
+    const size_t n_pts = (size_t)n * H2V_SLOTS(d);
+    h2v_workspace *ws = nullptr;
+    int rc = ws_create_for(d, p->device, n, false, &ws);
+    if (rc) return rc;
+    DevBuf dout;
+    h2v_batch in;
+    rc = stage_batch(p, b, ws, ws->hslot[0], &in);
+    do {
+        if (rc) break;
+        if (dout.alloc(n_pts * 96)) { rc = fail(H2V_E_DEVICE, "hipMalloc failed"); break; }
+        if (hipMemsetAsync(ws->pts, 0xa5, n_pts * 96, ws->hs) != hipSuccess || hipMemsetAsync(ws->valid, 0xa5, n_pts, ws->hs) != hipSuccess ||
+            hipMemsetAsync(ws->valid_sub, 0xa5, n_pts, ws->hs) != hipSuccess || hipMemsetAsync(ws->pt_tab, 0xa5, n_pts * 448 * 4, ws->hs) != hipSuccess) {
+            rc = fail(H2V_E_DEVICE, "hipMemsetAsync failed"); break;
+        }
+        if ((rc = launch_decompress(d, n, in.proofs, in.proof_off, in.committed, in.instances, ws, with_tables ? ws->pt_tab : nullptr, ws->hs, blocks_out))) break;
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ws->hs) != hipSuccess) { rc = fail(H2V_E_DEVICE, "decompression kernel failed"); break; }
+        if (hipMemcpy(valid_out, ws->valid, n_pts, hipMemcpyDeviceToHost) != hipSuccess ||
+            hipMemcpy(valid_sub_out, ws->valid_sub, n_pts, hipMemcpyDeviceToHost) != hipSuccess ||
+            (tables_out && hipMemcpy(tables_out, ws->pt_tab, n_pts * 448 * 4, hipMemcpyDeviceToHost) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
+        // (a point slot the kernel left at the preset is no field element: k_export_points would reduce it; such a slot shows in
+        //  valid[], which the preset makes neither 0 nor 1)
+        hipLaunchKernelGGL(k_export_points, dim3((uint32_t)((n_pts + 63) / 64)), dim3(64), 0, ws->hs, (uint32_t)n_pts, 0, ws->pts, dout.as<uint8_t>());
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ws->hs) != hipSuccess) { rc = fail(H2V_E_DEVICE, "export kernel failed"); break; }
+        if (hipMemcpy(xy_be, dout.p, n_pts * 96, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
     } while (0);
     h2v_workspace_free(ws);
     return rc;

@@ -93,6 +93,14 @@ def test_g1_decompress(be, orc, kats):
         assert ok == ook, c.hex()
         if ok:
             assert pt == opt, c.hex()
+    # the whole table of tests/g1_encodings.py through the same one-block form (the MSM and pairing probes decompress with it):
+    # the merged verdict, the point where it is 1 and (0, 0) where it is 0
+    from tests import g1_encodings as G
+    table = G.cases()
+    got = be.probe_g1_decompress([c.enc for c in table] * 3)          # (three times: every case in three lane positions)
+    for c, (ok, pt) in zip(table * 3, got):
+        assert ok == c.in_g1, (c.name, c.enc.hex())
+        assert pt == (c.point if c.in_g1 else None), (c.name, c.enc.hex())
 
 
 def test_g1_msm(be, orc):
