@@ -124,6 +124,9 @@ int h2v_plan_info(const h2v_plan *plan, uint32_t *proof_len, uint32_t *n_public_
 #define H2V_TRANSCRIPT_CARDANO_BLAKE2B_256 0u
 #define H2V_TRANSCRIPT_BLAKE2B_512 1u
 int h2v_plan_transcript(const h2v_plan *plan, uint32_t *kind, uint8_t key_out[64], uint32_t *key_len);
+/* 1 if the two plans carry the same SRS (the same s_g2: what h2v_verify_mixed demands of the plans of one call), 0 if not;
+ * H2V_E_ARG for a null plan.  Host-only: needs no device. */
+int h2v_plan_same_srs(const h2v_plan *a, const h2v_plan *b);
 
 /* A workspace is sized from `plan` (MSM terms, point slots, register file, recursion / fixed-base buffers).  It may be
  * reused with ANOTHER plan only if that plan needs no more of any of these; otherwise the verify calls return H2V_E_ARG
@@ -329,7 +332,8 @@ int h2v_verify_batch_rlc_device(const h2v_plan *plan, const h2v_batch *batch, ui
                                 h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts /* or NULL */);
 /* after synchronising the stream of an RLC call: the batch verdict (1 = passed) and the kernel times of that call.  calls_back
  * counts the workspace's records as h2v_workspace_timings does (every call takes one; up to 63 back).  A call routed to the
- * per-proof kernels reports (0, zeros).  H2V_E_ARG: no such record or a lane's ring has wrapped since (as there), a call that
+ * per-proof kernels reports (0, zeros); an aggregate call (h2v_aggregate_batch / _mixed, below) reports batch_accepted =
+ * H2V_BATCH_NOT_CHECKED and pairing_ms = 0.  H2V_E_ARG: no such record or a lane's ring has wrapped since (as there), a call that
  * was not an RLC call, or a coalesced call whose group has not run yet. */
 int h2v_workspace_rlc_result(h2v_workspace *ws, uint32_t calls_back, uint32_t *batch_accepted, h2v_rlc_timings *timings);
 
@@ -452,6 +456,67 @@ int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_m
 int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept,
                             uint32_t *status, h2v_workspace *ws /* not NULL */, void *stream, uint32_t flags,
                             const h2v_rlc_opts *opts);
+
+/* ---- aggregate calls: ONE pair (L, R) per batch, checked later and elsewhere ------------------------------------------------
+ * Every batch-accept form above ends inside the call: it forms L = sum r_i L_i and R = sum r_i R_i, runs one pairing on them
+ * and queues its fall-back behind that pairing.  The reference's callers keep exactly that value - the collapsed DualMSM of
+ * the batch - and decide later when to check it: `dual_msm.scale(r)`, `acc.add_msm(..)`, then `check` once over everything
+ * collected (examples/ivc.rs:85-96, 195-208; midnight_zk_stdlib::batch_verify).  h2v_aggregate_batch / h2v_aggregate_mixed are
+ * that first half: they split batch-accept the way h2v_prepare_batch / h2v_check_pairs split per-proof verification - "prepare the
+ * batch's pair" now, "check pairs from anywhere" (h2v_check_pairs for one, h2v_check_pairs_rlc for many: one pairing) later.
+ *   PAIR.  pair = compress(L) || compress(R), two 48-byte zcash encodings: the format of h2v_prepare_batch.  L = sum r_i L_i and
+ *   R = sum r_i R_i over the INCLUDED proofs, (L_i, R_i) being the pair h2v_prepare_batch returns for proof i (a non-recursive
+ *   key: pi and the multi-open MSM; a recursive key: the folded (el', er')).  An infinite sum is encoded 0xc0, 0, ...; when
+ *   nothing is included the pair is (inf, inf), which h2v_check_pairs accepts (as an empty RLC batch passes).  n = 0 is H2V_OK and
+ *   writes (inf, inf).
+ *   COEFFICIENTS.  Single-key form: exactly those the h2v_verify_batch_rlc call of the same shape would draw on that workspace -
+ *   r_i = the low 128 bits of blake2b-256(seed' || LE32(pos)), or 1 if that is 0.  An ordinary workspace: seed' = seed_used, pos =
+ *   the index in the call.  A laned workspace: chunk c (proofs c * chunk ..) hashes seed_used with 0x9e3779b9 * (c + 1) xored into
+ *   its last 32-bit word, pos = the index within the chunk.  Mixed form: pos = the position in the CALL, no tweak (the rule of
+ *   H2V_MIXED_FOLD_MSM); info->chunk is 0 for it.  h2v_aggregate_info carries what is needed to recompute them.
+ *   included[i] (n bytes) = 1 iff proof i was not rejected before the pairing: phase-1 status zero with H2V_ST_BAD_POINT folded in,
+ *   the RLC forms' good_i.  It is NOT a verdict: an included proof is accepted iff the pair's equation holds (up to the soundness
+ *   error).  status[i] (may be NULL) is what h2v_prepare_batch reports: H2V_ST_PAIRING is never set, H2V_ST_RECURSION stays.
+ *   WHERE THE CALLS STOP.  No pairing, no group stage, no per-proof MSM or pairing: nothing is queued behind the bucket MSMs but
+ *   the export (one small kernel that adds the chunks' sums and compresses the two totals).  A recursive plan in
+ *   h2v_aggregate_batch takes the H2V_RLC_FOLD_PAIRS route, flag or not: the per-proof pipeline through the fold, then the pairs
+ *   are combined.  A non-recursive plan whose VK-base terms are not the tail of its term list (no plan.py plan) has no batch form:
+ *   H2V_E_ARG.  h2v_aggregate_mixed is the H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM form without its verdict: the same layout, term count
+ *   (info->msm_terms = N_R) and limits, one SRS per call, at most H2V_MIXED_MAX_PLANS plans, recursive plans join as one pair per
+ *   proof; the device form returns after enqueueing - no download, no synchronisation of `stream`, no second pass.
+ *   LANED WORKSPACES.  The call is a join point as a mixed call is: it runs the open coalesced groups first, and `stream` waits for
+ *   the call's lanes inside the call (the per-chunk sums must meet).  Never coalesced, never routed; the failing-group estimate
+ *   does not move.  Consecutive calls on ONE stream therefore run one after the other; calls issued on SEVERAL streams overlap in
+ *   the lanes (a workspace keeps the sums of up to 16 calls of at most 128 chunks each apart; a call of more chunks waits for every
+ *   export before it and holds the others back behind its own) - a caller that wants the throughput of deferred RLC
+ *   calls gives every call in flight a stream of its own (DESIGN.md section 16 has what that measured).
+ *   RECORDS.  One record of kind RLC (the mixed form: its tail's, the call's last): h2v_workspace_rlc_result reports its times
+ *   with pairing_ms = 0 and batch_accepted = H2V_BATCH_NOT_CHECKED.
+ *   ERRORS as h2v_verify_batch_rlc(_device) / h2v_verify_mixed(_device): n > 2^22 is H2V_E_LIMIT; stream = NULL under deferred
+ *   joins, a host batch in flight on ws, ws = NULL in a device form are H2V_E_ARG; ws = NULL in a host form: a temporary workspace.
+ *   opts->flags: H2V_RLC_SEED_GIVEN and H2V_RLC_ONE_STREAM as ever, H2V_RLC_FOLD_PAIRS accepted and ignored, any other bit H2V_E_ARG.
+ *   The device forms take device pointers (pair 4-byte aligned; plan_of stays host memory); info is HOST memory in both forms.
+ *   SOUNDNESS.  A pair vouches for its proofs only to someone who trusts that seed_used was unpredictable to the provers - the same
+ *   trust domain as the caller of h2v_verify_batch_rlc.  It is NOT a proof for third parties.  Whoever combines the pairs of several
+ *   calls must scale them again with fresh coefficients - which is what h2v_check_pairs_rlc does; adding pairs unscaled lets the
+ *   errors of two calls cancel (tests/test_aggregate_gpu.py). */
+#define H2V_BATCH_NOT_CHECKED 2u  /* h2v_workspace_rlc_result: batch_accepted of an aggregate call */
+typedef struct {
+    uint8_t  seed_used[32];  /* the effective seed of THIS call: the OS draw, or the given seed with the call count mixed in */
+    uint32_t chunk;          /* 0 on an ordinary workspace and for the mixed form; else the chunk size that cut the call (coefficients follow it) */
+    uint32_t n_chunks;       /* 1 on an ordinary workspace and for the mixed form (and for n = 0 on any workspace) */
+    uint32_t msm_terms;      /* terms of the right-hand bucket MSM(s), summed over chunks */
+    uint32_t reserved;
+} h2v_aggregate_info;        /* HOST memory, written before the call returns, in both forms; may be NULL */
+int h2v_aggregate_batch(const h2v_plan *plan, const h2v_batch *batch, uint8_t pair[96], uint8_t *included /* n */, uint32_t *status /* or NULL */,
+                        h2v_workspace *ws /* or NULL */, const h2v_rlc_opts *opts /* or NULL */, h2v_aggregate_info *info /* or NULL */);
+int h2v_aggregate_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_t *pair, uint8_t *included, uint32_t *status,
+                               h2v_workspace *ws /* not NULL */, void *stream, const h2v_rlc_opts *opts, h2v_aggregate_info *info);
+int h2v_aggregate_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t pair[96], uint8_t *included,
+                        uint32_t *status /* or NULL */, h2v_workspace *ws /* or NULL */, const h2v_rlc_opts *opts, h2v_aggregate_info *info);
+int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *pair, uint8_t *included,
+                               uint32_t *status, h2v_workspace *ws /* not NULL */, void *stream, const h2v_rlc_opts *opts,
+                               h2v_aggregate_info *info);
 
 /* ---- parity / debugging surface ----------------------------------------------------------------------------
  * The reference's own intermediate-value trace (cargo feature plutus_debug, src/plutus_gen/emitters/plinth.rs:792-831):

@@ -276,6 +276,97 @@ inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v
     for (uint64_t i = 0; i < batch.n; i++)
         if (!r.accept[i]) throw VerifyError(r.status[i]);
 }
+// Aggregate calls (h2v_aggregate_batch / h2v_aggregate_mixed): the batch's ONE pair compress(L) || compress(R), L = sum r_i L_i and
+// R = sum r_i R_i over the included proofs, instead of a pairing on it - the reference's `dual_msm.scale(r)` / `acc.add_msm(..)`;
+// check_pairs(_rlc) is its `check`.  included[i] = 1: proof i was not rejected before the pairing (NOT a verdict: it is accepted
+// iff the pair's equation holds); status as prepare_batch; info: the seed and chunking the coefficients follow.  seed: 32 bytes
+// that provers cannot predict, or nullptr = drawn from the OS.
+struct Aggregate {
+    uint8_t pair[96];
+    std::vector<uint8_t> included;
+    std::vector<uint32_t> status;
+    h2v_aggregate_info info;
+};
+inline Aggregate aggregate_batch(const VerifyingKey &vk, const h2v_batch &batch, h2v_workspace *ws = nullptr, const uint8_t *seed = nullptr) {
+    Aggregate r{{}, std::vector<uint8_t>(batch.n ? batch.n : 1), std::vector<uint32_t>(batch.n ? batch.n : 1), {}};
+    h2v_rlc_opts opts{};
+    if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
+    check(h2v_aggregate_batch(vk.handle(), &batch, r.pair, r.included.data(), r.status.data(), ws, seed ? &opts : nullptr, &r.info));
+    r.included.resize(batch.n); r.status.resize(batch.n);
+    return r;
+}
+inline Aggregate aggregate_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
+                                 const uint8_t *seed = nullptr) {
+    std::vector<const h2v_plan *> plans;
+    for (const VerifyingKey *k : vks) plans.push_back(k ? k->handle() : nullptr);
+    Aggregate r{{}, std::vector<uint8_t>(batch.n ? batch.n : 1), std::vector<uint32_t>(batch.n ? batch.n : 1), {}};
+    h2v_rlc_opts opts{};
+    if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
+    check(h2v_aggregate_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.pair, r.included.data(), r.status.data(), ws, seed ? &opts : nullptr,
+                              &r.info));
+    r.included.resize(batch.n); r.status.resize(batch.n);
+    return r;
+}
+// Collects the pairs of several calls - keys of ONE SRS - and checks them ONCE (examples/ivc.rs:85-96, 195-208: scale, add_msm,
+// then one `check`).  push() aggregates a call and keeps its pair, included[] and a COPY of its inputs; finish() checks the K pairs
+// with one pairing (check_pairs_rlc; check_pairs for K = 1): a call whose pair passes gets accept = included, a call whose pair
+// fails is verified per proof (verify_batch) on the kept inputs.  Same semantics as api.Aggregator (there `params` names the SRS).  finish() returns the per-call accept vectors in push order and
+// fills `reverified` with the indices of the calls verified again.  The keys must outlive the Aggregator; keep it inside one trust
+// domain (a pair is only worth what the seed of its call is).
+class Aggregator {
+  public:
+    Aggregator() {}
+    Aggregator(const Aggregator &) = delete;
+    Aggregator &operator=(const Aggregator &) = delete;
+    /// one SRS per Aggregator - that of the first key pushed: a key on another SRS is Error(H2V_E_ARG), before anything runs
+    size_t push(const VerifyingKey &vk, const h2v_batch &b, const uint8_t *seed = nullptr) {
+        if (!srs_) srs_ = &vk;
+        const int same = h2v_plan_same_srs(srs_->handle(), vk.handle());
+        if (same < 0) check(same);
+        if (same != 1) throw Error(H2V_E_ARG, "Aggregator: this key is on another SRS than the keys pushed before (s_g2 differs)");
+        Call c;
+        c.vk = &vk;
+        const Aggregate a = aggregate_batch(vk, b, nullptr, seed);
+        for (int k = 0; k < 96; k++) c.pair[k] = a.pair[k];
+        c.included = a.included;
+        c.off.assign(b.proof_off, b.proof_off + b.n + 1);
+        const uint64_t base = c.off[0];
+        for (uint64_t &o : c.off) o -= base;
+        c.proofs.assign(b.proofs + base, b.proofs + base + c.off[b.n]);
+        if (b.instances) c.inst.assign(b.instances, b.instances + b.n * 32 * vk.n_public_inputs());
+        if (b.committed && vk.n_committed_instances()) c.ci.assign(b.committed, b.committed + b.n * 48);
+        calls_.push_back(std::move(c));
+        return calls_.size() - 1;
+    }
+    std::vector<std::vector<uint8_t>> finish(std::vector<size_t> *reverified = nullptr, const uint8_t *seed = nullptr) {
+        std::vector<Call> calls;
+        calls.swap(calls_);
+        std::vector<std::vector<uint8_t>> out;
+        if (reverified) reverified->clear();
+        if (calls.empty()) return out;
+        std::vector<uint8_t> pairs;
+        for (const Call &c : calls) pairs.insert(pairs.end(), c.pair, c.pair + 96);
+        const PairVerdicts v = calls.size() > 1 ? check_pairs_rlc(*calls[0].vk, pairs, nullptr, seed) : check_pairs(*calls[0].vk, pairs);
+        for (size_t k = 0; k < calls.size(); k++) {
+            const Call &c = calls[k];
+            if (v.accept[k]) { out.push_back(c.included); continue; }
+            if (reverified) reverified->push_back(k);
+            const h2v_batch b{c.included.size(), c.proofs.data(), c.off.data(), c.inst.empty() ? nullptr : c.inst.data(), c.ci.empty() ? nullptr : c.ci.data()};
+            out.push_back(verify_batch(*c.vk, b));
+        }
+        return out;
+    }
+
+  private:
+    struct Call {
+        const VerifyingKey *vk = nullptr;
+        uint8_t pair[96];
+        std::vector<uint8_t> included, proofs, inst, ci;
+        std::vector<uint64_t> off;
+    };
+    std::vector<Call> calls_;
+    const VerifyingKey *srs_ = nullptr;
+};
 
 // A reusable workspace, and the streaming form: submit() returns once the batch is copied and everything is enqueued,
 // wait() collects the accept vector.  Alternate two Workspaces to overlap the upload of one batch with the kernels of the

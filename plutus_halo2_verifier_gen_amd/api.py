@@ -146,6 +146,18 @@ class Verifier:
             acc, st = self.device_plan.check_pairs(raw, ws=self._workspace(n))
         return [bool(a) for a in acc], st
 
+    def aggregate_batch(self, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
+                        committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None):
+        """The batch's ONE pair instead of a verdict (h2v_aggregate_batch): (pair, included, status, info).  pair = compress(L) ||
+        compress(R) with L = sum r_i L_i, R = sum r_i R_i over the included proofs - the reference's DualMSM of the batch, scaled
+        and added, not yet checked; included[i] = "not rejected before the pairing" (not a verdict: an included proof is accepted
+        iff the pair's equation holds); status as prepare_batch; info = backend.AggregateInfo.  check_pairs checks the pair -
+        with mode="rlc" many of them in one pairing (Aggregator does that).  seed: tests only, as for verify_batch."""
+        n = len(proofs)      # (n = 0 goes through the library too: (inf, inf), and the info carries the call's seed and n_chunks = 1)
+        pair, inc, st, info = self.device_plan.aggregate_batch(*self._pack(proofs, instances, committed), ws=self._workspace(n) if n else None,
+                                                               seed=seed)
+        return pair, [bool(a) for a in inc], st, info
+
     def _pack(self, proofs, instances, committed):
         n = len(proofs)
         if len(instances) != n:
@@ -341,3 +353,50 @@ def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instanc
     acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm)
     if not all(acc):
         raise VerifyError(next(s for a, s in zip(acc, status) if not a))
+
+
+class Aggregator:
+    """Collects the pairs of several calls and checks them ONCE: the reference's `dual_msm.scale(r)` / `acc.add_msm(..)` per call
+    and one `check` over everything collected (examples/ivc.rs:85-96, 195-208).  One Aggregator per SRS (`params`); a key on
+    another SRS is a ValueError.
+
+        agg = Aggregator(params)
+        agg.push(vk_a, proofs_a, instances_a)         # h2v_aggregate_batch: no pairing runs
+        agg.push(vk_b, proofs_b, instances_b)
+        accepts, reverified = agg.finish()            # ONE pairing over the K pairs (h2v_check_pairs_rlc; h2v_check_pairs for K = 1)
+
+    finish() returns the per-call accept lists in push order and the indices of the calls that had to be verified again: a call
+    whose pair passes gets accept = included; a call whose pair fails is verified per proof (verify_batch) on the inputs push
+    kept.  The pairs of different calls are scaled again with fresh coefficients by the check, so the errors of two calls cannot
+    cancel.  A pair is only worth what the seed of its call is: keep an Aggregator inside one trust domain."""
+
+    def __init__(self, params: ParamsVerifierKZG, device: int = 0):
+        self.params, self.device = params, device
+        self._calls = []      # (verifier, pair, included, (proofs, instances, committed))
+
+    def push(self, vk: VerifyingKey, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
+             committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None) -> int:
+        """aggregates one call of proofs of `vk` and keeps its pair, included[] and a reference to the inputs; returns the call's index"""
+        if bytes(self.params.s_g2) != bytes.fromhex(vk.s_g2):
+            raise ValueError("verifier params do not match the verifying key's SRS (s_g2 differs)")
+        v = verifier_for(vk, self.device)
+        pair, included, _status, _info = v.aggregate_batch(proofs, instances, committed, seed=seed)
+        self._calls.append((v, pair, included, (proofs, instances, committed)))
+        return len(self._calls) - 1
+
+    def finish(self, seed: Optional[bytes] = None):
+        """(accepts, reverified): one check over the collected pairs, per-proof verification of the calls whose pair fails.  The
+        Aggregator is empty afterwards."""
+        calls, self._calls = self._calls, []
+        if not calls:
+            return [], []
+        pairs = [c[1] for c in calls]
+        ok, _st = calls[0][0].check_pairs(pairs, mode="rlc" if len(pairs) > 1 else "per-pair", seed=seed)
+        accepts, reverified = [], []
+        for k, (v, _pair, included, (proofs, instances, committed)) in enumerate(calls):
+            if ok[k]:
+                accepts.append(list(included))
+            else:
+                reverified.append(k)
+                accepts.append(v.verify_batch(proofs, instances, committed))
+        return accepts, reverified

@@ -55,6 +55,12 @@ class RlcTimings(C.Structure):
                 ("window_bits", C.c_uint32), ("windows", C.c_uint32), ("max_chain", C.c_uint32)]
 
 
+class AggregateInfo(C.Structure):
+    """h2v_aggregate_info (include/h2v.h): what is needed to recompute the coefficients of an aggregate call"""
+    _fields_ = [("seed_used", C.c_uint8 * 32), ("chunk", C.c_uint32), ("n_chunks", C.c_uint32), ("msm_terms", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class PlanOpts(C.Structure):
     _fields_ = [("fixed_base_window_bits", C.c_uint32), ("reserved", C.c_uint32 * 7)]
 
@@ -77,6 +83,7 @@ SUBMIT_RLC = 1
 MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
 MIXED_FOLD_MSM = 2     # ... and ONE bucket MSM over the call's per-proof terms (only together with MIXED_RLC)
 MIXED_MAX_PLANS = 64   # H2V_MIXED_MAX_PLANS
+BATCH_NOT_CHECKED = 2  # H2V_BATCH_NOT_CHECKED: batch_accepted of an aggregate call (Workspace.rlc_verdict)
 
 
 def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False):
@@ -104,6 +111,7 @@ EXPORTS = [
     "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device",
     "h2v_plan_transcript", "h2v_probe_blake2b_ex",
     "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums", "h2v_probe_decompress",
+    "h2v_aggregate_batch", "h2v_aggregate_batch_device", "h2v_aggregate_mixed", "h2v_aggregate_mixed_device", "h2v_plan_same_srs",
 ]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
@@ -191,6 +199,15 @@ def lib():
         L.h2v_verify_mixed_device.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_uint32, C.POINTER(RlcOpts)]
         L.h2v_probe_mixed_fold_sums.argtypes = [C.c_void_p, C.c_void_p]
+        L.h2v_plan_same_srs.argtypes = [C.c_void_p, C.c_void_p]
+        L.h2v_aggregate_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RlcOpts),
+                                          C.POINTER(AggregateInfo)]
+        L.h2v_aggregate_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(RlcOpts), C.POINTER(AggregateInfo)]
+        L.h2v_aggregate_mixed.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.POINTER(RlcOpts), C.POINTER(AggregateInfo)]
+        L.h2v_aggregate_mixed_device.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(RlcOpts), C.POINTER(AggregateInfo)]
         # h2v_shutdown before the interpreter goes down: the library's pool streams (hardware queues of their own) must not
         # outlive the HIP runtime / a profiler's tool library (include/h2v.h: library lifecycle).  Handles that Python still
         # holds afterwards are empty shells; their __del__ frees the host structs only.
@@ -385,6 +402,33 @@ class DevicePlan:
         check(lib().h2v_check_pairs_rlc_device(self._h, n, d_pairs, d_accept, d_status, ws.handle if ws else None, stream,
                                                C.byref(opts) if opts is not None else None))
 
+    # ---- aggregate calls: the batch's ONE pair instead of a pairing on it (include/h2v.h: h2v_aggregate_batch)
+    def aggregate_batch(self, proofs: bytes, proof_off, instances: bytes, committed: Optional[bytes], ws=None,
+                        seed: Optional[bytes] = None, one_stream: bool = False):
+        """h2v_aggregate_batch: (pair, included, status, info) - pair = 96 bytes compress(L) || compress(R) with L = sum r_i L_i,
+        R = sum r_i R_i over the included proofs; included = n bytes, 1 = not rejected before the pairing (NOT a verdict);
+        status = h2v_prepare_batch's; info = an AggregateInfo (the seed and the chunking the coefficients follow)."""
+        n, b, _keep = self._host_batch(proofs, proof_off, instances, committed)
+        pair = C.create_string_buffer(96)
+        inc = (C.c_uint8 * max(1, n))()
+        st = (C.c_uint32 * max(1, n))()
+        info = AggregateInfo()
+        opts = _rlc_opts(seed, one_stream)
+        check(lib().h2v_aggregate_batch(self._h, C.byref(b), pair, inc, st, ws.handle if ws else None,
+                                        C.byref(opts) if opts is not None else None, C.byref(info)))
+        return pair.raw, bytes(inc[:n]), list(st[:n]), info
+
+    def aggregate_batch_device(self, n, d_proofs, d_off, d_inst, d_ci, d_pair, d_included, d_status=None, ws=None, stream=None,
+                               seed: Optional[bytes] = None, one_stream: bool = False) -> AggregateInfo:
+        """h2v_aggregate_batch_device: enqueues on `stream`; d_pair = 96 bytes of device memory (4-byte aligned), d_included = n.
+        Returns the call's AggregateInfo (host memory, filled in before the call returns)."""
+        b = Batch(n, d_proofs, d_off, d_inst, d_ci)
+        info = AggregateInfo()
+        opts = _rlc_opts(seed, one_stream)
+        check(lib().h2v_aggregate_batch_device(self._h, C.byref(b), d_pair, d_included, d_status, ws.handle if ws else None, stream,
+                                               C.byref(opts) if opts is not None else None, C.byref(info)))
+        return info
+
     def trace(self, proof: bytes, instances: bytes, committed: Optional[bytes]):
         nt = len(self.trace_slots)
         sc = C.create_string_buffer(32 * max(1, nt))
@@ -495,6 +539,13 @@ class Workspace:
         check(lib().h2v_workspace_rlc_result(self._h, calls_back, C.byref(ok), C.byref(tm) if timings else None))
         return bool(ok.value), tm
 
+    def rlc_verdict(self, calls_back: int = 0) -> int:
+        """batch_accepted of h2v_workspace_rlc_result as the library reports it: 1 passed, 0 failed / routed, BATCH_NOT_CHECKED (2)
+        for an aggregate call"""
+        ok = C.c_uint32(0)
+        check(lib().h2v_workspace_rlc_result(self._h, calls_back, C.byref(ok), None))
+        return ok.value
+
     def close(self):
         if getattr(self, "_h", None):
             lib().h2v_workspace_free(self._h)
@@ -562,6 +613,48 @@ def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d
     opts = _rlc_opts(seed)
     check(lib().h2v_verify_mixed_device(arr, len(plans), C.byref(b), d_accept, d_status, ws.handle if ws else None, stream,
                                         flags, C.byref(opts) if opts is not None else None))
+
+
+def aggregate_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
+                    seed: Optional[bytes] = None):
+    """h2v_aggregate_mixed: the fold_msm form of verify_mixed without its verdict - (pair, included, status, info) for the call,
+    included / status in the caller's order; the coefficient of proof i follows its position in the call (info.chunk = 0)."""
+    n = len(proof_off) - 1
+    if n < 0 or len(plan_of) != n:
+        raise H2VError("plan_of: one entry per proof")
+    if any(proof_off[i + 1] < proof_off[i] for i in range(n)) or (n > 0 and (proof_off[0] < 0 or proof_off[-1] > len(proofs))):
+        raise H2VError("proof offsets must be non-decreasing and within the proof bytes handed over")
+    arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
+    po = (C.c_uint32 * max(1, n))(*plan_of)
+    off = (C.c_uint64 * (n + 1))(*proof_off)
+    pbuf = C.create_string_buffer(proofs, len(proofs)) if proofs else C.create_string_buffer(1)
+    ibuf = C.create_string_buffer(instances, len(instances)) if instances else None
+    cbuf = C.create_string_buffer(committed, len(committed)) if committed else None
+    b = MixedBatch(n, C.cast(po, C.c_void_p), C.cast(pbuf, C.c_void_p), C.cast(off, C.c_void_p),
+                   C.cast(ibuf, C.c_void_p) if ibuf is not None else None, C.cast(cbuf, C.c_void_p) if cbuf is not None else None)
+    pair = C.create_string_buffer(96)
+    inc = (C.c_uint8 * max(1, n))()
+    st = (C.c_uint32 * max(1, n))()
+    info = AggregateInfo()
+    opts = _rlc_opts(seed)
+    check(lib().h2v_aggregate_mixed(arr, len(plans), C.byref(b), pair, inc, st, ws.handle if ws else None,
+                                    C.byref(opts) if opts is not None else None, C.byref(info)))
+    return pair.raw, bytes(inc[:n]), list(st[:n]), info
+
+
+def aggregate_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_pair, d_included, d_status=None, ws=None,
+                           stream=None, seed: Optional[bytes] = None) -> AggregateInfo:
+    """h2v_aggregate_mixed_device: enqueues on `stream` and returns - no verdict comes down, the stream is not synchronised"""
+    if len(plan_of) != n:
+        raise H2VError("plan_of: one entry per proof")
+    arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
+    po = (C.c_uint32 * max(1, n))(*plan_of)
+    b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
+    info = AggregateInfo()
+    opts = _rlc_opts(seed)
+    check(lib().h2v_aggregate_mixed_device(arr, len(plans), C.byref(b), d_pair, d_included, d_status, ws.handle if ws else None, stream,
+                                           C.byref(opts) if opts is not None else None, C.byref(info)))
+    return info
 
 
 def probe_mixed_fold_sums(ws):

@@ -17,6 +17,7 @@
 #include "h2v_mixed_dev.hpp"
 #include "h2v_mixed_fold.hpp"
 #include "h2v_mixed_fold_dev.hpp"
+#include "h2v_aggregate_dev.hpp"
 #include "h2v_msm_shape.hpp"
 #include "h2v_plancc.hpp"
 
@@ -240,6 +241,7 @@ struct h2v_workspace {
         Kind kind = VERIFY;
         bool no_vm = false;        // an RLC call over pairs from anywhere: no transcript ran (transcript_combiner_ms = 0)
         bool routed = false;       // an RLC call sent straight to the per-proof kernels (rlc_route): per-proof times, no batch check
+        bool agg = false;          // an aggregate call (h2v_aggregate_batch / _mixed): the sums were exported, no pairing ran ("not checked")
         bool co = false, ran = false;   // coalesced (coalesce_call); its group has run - only then is the rest filled in (co_flush_lane)
         float share = 0.0f;        // coalesced: its proofs / the group's
         // ordinary workspace: the event set, created with the workspace.  Per proof (run_pipeline; run_check a subset):
@@ -299,6 +301,15 @@ struct h2v_workspace {
     // gathered into; co_open: the lanes whose groups are open, oldest first (one group per plan and mode, at most four)
     struct Coalesce *co[MAXL] = {};
     struct MixedWs *mixed = nullptr;        // staging of the mixed-key calls (h2v_verify_mixed), created by the first one
+    // aggregate calls (h2v_aggregate_batch / _mixed): the parts buffer, agg_cap parts of [2][36] dwords - every chunk's two
+    // Jacobian sums, which k_aggregate_export adds.  AGG_SLOTS fixed slots of AGG_SLOT_PARTS parts each, one per call in flight, so
+    // that calls on several caller streams overlap; a call of more parts takes the whole buffer (agg_ensure has the invariant)
+    static constexpr uint32_t AGG_SLOTS = 16, AGG_SLOT_PARTS = 128;     // (as many calls as a workspace has lanes)
+    uint32_t *agg_parts = nullptr;
+    uint32_t agg_cap = 0;
+    uint64_t agg_calls = 0;
+    hipEvent_t ev_agg[AGG_SLOTS] = {};
+    bool agg_used[AGG_SLOTS] = {};
     std::vector<uint32_t> co_open;
 };
 using CallRec = h2v_workspace::CallRec;
@@ -635,6 +646,10 @@ extern "C" int h2v_plan_transcript(const h2v_plan *p, uint32_t *kind, uint8_t ke
     if (key_len) *key_len = p->tr_key_len;
     return H2V_OK;
 }
+extern "C" int h2v_plan_same_srs(const h2v_plan *a, const h2v_plan *b) {
+    if (!a || !b) return fail(H2V_E_ARG, "null argument");
+    return memcmp(a->sg2_digest, b->sg2_digest, sizeof a->sg2_digest) == 0 ? 1 : 0;
+}
 extern "C" int h2v_plan_trace_slots(const h2v_plan *p, uint32_t *slot_ids, uint32_t cap, uint32_t *n_out) {
     if (!p || !n_out) return fail(H2V_E_ARG, "null argument");
     *n_out = (uint32_t)p->trace_slots.size();
@@ -676,8 +691,9 @@ static void ws_release(h2v_workspace *w) {
     for (hipEvent_t &e : w->ev_pipe) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
     void *ptrs[] = {w->rlc_stats, w->rec_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
-                    w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts, w->hp_buf};
+                    w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts, w->hp_buf, w->agg_parts};
     for (void *q : ptrs) if (q) (void)hipFree(q);
+    for (hipEvent_t &e : w->ev_agg) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
     if (w->copy_streams_owned) {
         if (w->hs) (void)hipStreamDestroy(w->hs);
@@ -1428,6 +1444,11 @@ struct Unit {
     uint32_t *fail_ctr = nullptr;
     bool one_stream_opt = false;       // RLC: h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM (lanes and coalesced groups: always)
     bool trace = false;                // h2v_trace: the combiner's intermediate values to the workspace's trace buffer
+    // an AGGREGATE call (h2v_aggregate_batch / _mixed; kinds RLC, FOLD_RLC, MIXED_FOLD_TAIL): instead of the batch pairing and what
+    // is queued behind it, the unit's two sums go to part `part` of agg_parts (its chunk number: run_chunks) and good_i to accept[],
+    // which is the caller's included[] (agg_chunk)
+    uint32_t *agg_parts = nullptr;
+    uint32_t part = 0;
     bool batch_check() const { return kind == UnitKind::RLC || kind == UnitKind::PAIR_RLC || kind == UnitKind::FOLD_RLC || kind == UnitKind::MIXED_TAIL_RLC; }
     // the same unit for proofs / pairs lo .. lo + m (proof offsets are absolute: `proofs` stays; a sub-batch writes the pool
     // through pos[], the tail reads its own part of it)
@@ -1459,6 +1480,7 @@ static Unit unit_of_pairs(UnitKind kind, const h2v_plan *p, uint64_t n, const ui
     return u;
 }
 static int fold_pairs_tail(const Unit &u, const uint32_t *er2, const uint32_t *el2, h2v_workspace *w, CallRec &rec, hipStream_t st);
+static int agg_chunk(const Unit &u, struct RlcWs *r, h2v_workspace *w, CallRec &rec, hipStream_t st);
 // Decompression: ONE launch whose waves (at most one per SIMD) take 64-point units from a queue - all subgroup tests,
 // then all square roots (k_g1_decompress_queue).  v: the plan, or a view of it (pair_view); tab: where the MSM window tables
 // go (NULL: none are built); blocks_out (h2v_probe_decompress): the grid of the launch.
@@ -1755,7 +1777,7 @@ static CallRec &rec_laned(h2v_workspace *w, h2v_workspace::Kind kind, uint32_t L
 struct LaneSetup { uint32_t hint; int stream_mode; };
 static int run_on_lane(h2v_workspace *w, uint32_t l, const Unit &u, const LaneSetup &s) {
     h2v_workspace *lw = w->lane[l];
-    const bool counted = u.kind == UnitKind::RLC || u.kind == UnitKind::ROUTED;
+    const bool counted = (u.kind == UnitKind::RLC || u.kind == UnitKind::ROUTED) && !u.agg_parts;   // (an aggregate call moves no estimate)
     lw->in_flight_hint = s.hint;
     lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
     if (counted) lw->rlc_stats_ptr = w->rlc_stats;
@@ -1784,6 +1806,7 @@ template <class Before> static int run_chunks(h2v_workspace *w, const Unit &u, u
         const uint32_t lo = c * chunk;
         Unit cu = u.slice(lo, (u.n - lo) < chunk ? (u.n - lo) : chunk);
         cu.seed[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
+        cu.part = c;
         if (int rc = run_on_lane(w, l, cu, s)) return drain_after_error(w, rc);
         if (int rc = lane_done(w, l)) return rc;
     }
@@ -1816,7 +1839,8 @@ static int run_laned(Unit u, h2v_workspace *w, hipStream_t st, Join join) {
         // the chunks report into this record's word.  RLC over proofs: routed - "a batch check failed" = the per-proof kernels
         // produce accept[]; over pairs (given or folded): never routed, and the failing-group estimate stays where it is
         if (int rcs = rlc_stats_ensure(w)) return rcs;
-        if (u.kind == UnitKind::RLC && (rec.routed = rlc_route(w))) u.kind = UnitKind::ROUTED;
+        if (u.kind == UnitKind::RLC && !u.agg_parts && (rec.routed = rlc_route(w))) u.kind = UnitKind::ROUTED;   // (an aggregate call is never routed)
+        rec.agg = u.agg_parts != nullptr;
         HIPCHK(hipMemsetAsync(rec_word(w, rec), rec.routed ? 1 : 0, 4, st));
         u.fail_ctr = rec_word(w, rec);
         u.one_stream_opt = true;
@@ -2891,6 +2915,18 @@ static int launch_batch_pairing(const Unit &u, RlcWs *r, const GrpShape &gs, uin
         if (int rc = rlc_groups_launch(r, gs, n, u.accept, d1, st, stats)) return rc;
     return H2V_OK;
 }
+// The end of a unit of an AGGREGATE call, in place of launch_batch_pairing and everything its callers queue behind it: good_i to the
+// caller's included[] (u.accept, the unit's range of it), the unit's two sums (r->sums: R, then L, Jacobian) to its part of the
+// call's parts buffer - a lane's r->sums is overwritten by its next chunk -, ev[9] for the record's times.  The record's verdict
+// word stays 0 and means nothing: h2v_workspace_rlc_result reports H2V_BATCH_NOT_CHECKED for a record with `agg` set.
+static int agg_chunk(const Unit &u, RlcWs *r, h2v_workspace *w, CallRec &rec, hipStream_t st) {
+    rec.agg = true;
+    if (!u.fail_ctr) HIPCHK(hipMemsetAsync(rec_word(w, rec), 0, 4, st));
+    HIPCHK(hipMemcpyAsync(u.accept, r->good, u.n, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(u.agg_parts + (size_t)u.part * AGG_PART_DW, r->sums, AGG_PART_DW * 4, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipEventRecord(rec.ev[9], st));
+    return H2V_OK;
+}
 // One batch in RLC mode.  Phase 1 as in run_pipeline (the decompression launch builds no window tables), then the batch
 // check; the per-proof MSM + pairing kernels are queued behind it and return at once unless the batch check failed.
 // Events (the record's): [0]/[1] around the decompression, [2]/[3] around the
@@ -2943,6 +2979,11 @@ static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
     const PipWs *pws[2] = {&r->R, &r->L};
     if ((rc = pip_launch(pws, pa, 2, pm, ev + 5))) return rc;   // ev[5..8]
     rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    if (u.agg_parts) {      // an aggregate call stops here: no pairing, no group stage, no per-proof kernels
+        if ((rc = agg_chunk(u, r, w, rec, pm))) return rc;
+        if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+        return H2V_OK;
+    }
     // fall-back, skipped on the device when the batch check passed.  Stage 1 finds the groups of 64 proofs that hold a failing
     // proof (everything else is final); stage 2 - window tables, per-proof MSM, per-proof pairing - decides inside those
     // groups.  Walking grids of one wave per SIMD: finding out that a launch is not needed costs a few microseconds, and a
@@ -2990,6 +3031,7 @@ static int pairs_rlc_core(const Unit &u, RlcWs *r, const uint32_t *pool, const u
     const PipWs *pws[2] = {&r->R, &r->L};
     if ((rc = pip_launch(pws, pa, 2, st, ev + 5))) return rc;   // ev[5..8]
     rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    if (u.agg_parts) return agg_chunk(u, r, w, rec, st);      // (an aggregate call: the sums are exported, nothing is checked)
     if ((rc = launch_batch_pairing(u, r, grp_of_pairs(u.p, pool), nullptr, w, rec, st))) return rc;
     HIPCHK(hipGetLastError());
     return H2V_OK;
@@ -3032,6 +3074,7 @@ static int fold_pairs_tail(const Unit &u, const uint32_t *er2, const uint32_t *e
     HIPCHK(hipEventRecord(rec.ev[10], st));
     hipLaunchKernelGGL(k_fold_pairs_affine, dim3((n + 63) / 64), dim3(64), 0, st, n, (uint32_t)H2V_SLOTS(d), w->valid, w->valid_sub, el2, er2, w->status, r->pool, r->good);
     if ((rc = pairs_rlc_core(u, r, r->pool, nullptr, nullptr, true, w->status, w, rec, st))) return rc;
+    if (u.agg_parts) return H2V_OK;
     launch_pairing_behind(r->flags, d, n, w->pts, w->valid, w->valid_sub, er2, el2, w->status, u.accept, st);
     HIPCHK(hipGetLastError());
     return H2V_OK;
@@ -3323,7 +3366,9 @@ static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st) 
     const PipWs *pws[2] = {&r->R, &r->L};
     if ((rc = pip_launch(pws, pa, 2, st, rec.ev + 5))) return rc;   // ev[5..8]
     rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
-    if ((rc = launch_batch_pairing(u, r, GrpShape{}, nullptr, w, rec, st, false))) return rc;
+    if (u.agg_parts) rc = agg_chunk(u, r, w, rec, st);
+    else rc = launch_batch_pairing(u, r, GrpShape{}, nullptr, w, rec, st, false);
+    if (rc) return rc;
     m->fold_ran = true;
     HIPCHK(hipGetLastError());
     if (u.status) HIPCHK(hipMemcpyAsync(u.status, m->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
@@ -3367,7 +3412,8 @@ static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
 // (the host form), else NULL
 // lay: H2V_MIXED_FOLD_MSM - the layout of the call's term pool (fold_layout over this workspace's chunk size) - or NULL
 static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
-                     uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay = nullptr) {
+                     uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay = nullptr,
+                     uint32_t *agg_parts = nullptr /* h2v_aggregate_mixed (with lay): the tail exports its sums to part 0, accept = included[] */) {
     const uint32_t n = pt.n;
     int rc;
     if (w->n_lanes && (rc = co_flush(w))) return rc;       // (calls start in submission order: the open groups of coalesced calls first)
@@ -3439,6 +3485,7 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     };
     Unit tail{lay ? UnitKind::MIXED_FOLD_TAIL : rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, n};
     tail.pool = pool; tail.accept = accept; tail.status = status_out; tail.fold = lay ? &fc : nullptr;
+    tail.agg_parts = lay ? agg_parts : nullptr;
     for (int q = 0; q < 8; q++) tail.seed[q] = seed ? seed[q] : 0;
     if (!w->n_lanes) {
         // an ordinary workspace: the sub-batches one after the other on `st`, then the tail
@@ -3467,7 +3514,8 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     if (lay) {
         // ---- the fold form's tail: ONE piece on the call's stream, behind every lane; its record (one "chunk") is a lane's
         if ((rc = lanes_join(w, st))) return finish(rc);
-        const CallRec &rec = rec_laned(w, h2v_workspace::RLC, w->n_lanes, n, n);
+        CallRec &rec = rec_laned(w, h2v_workspace::RLC, w->n_lanes, n, n);
+        rec.agg = tail.agg_parts != nullptr;
         if (rec_word(w, rec) != tail.fail_ctr) return finish(fail(H2V_E_DEVICE, "internal: the tail's record is not the call's last"));
         const uint32_t l = (uint32_t)(w->next_lane++ % w->n_lanes);
         if ((rc = ensure_lane(w, l))) return finish(rc);
@@ -3569,8 +3617,14 @@ extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_
 }
 // Host-buffer form: offsets | instances | committed | proofs go up in one pinned block on the workspace's own stream, the call
 // runs there behind it, and accept[] / status[] / the batch verdict come back before the function returns.
-extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
-                                h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back) {
+// agg_pair (h2v_aggregate_mixed): the fold form without its verdict - `accept` is the caller's included[], the call's pair comes
+// back in agg_pair and nothing is checked, downloaded in between or run a second time.
+static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint32_t chunk, uint32_t nch, uint64_t terms);
+struct AggSlot { uint32_t *parts; uint32_t slot; };
+static int agg_export(h2v_workspace *ws, const AggSlot &a, uint32_t n_parts, uint8_t *d_pair, hipStream_t st);
+static int agg_ensure(h2v_workspace *ws, uint32_t n_parts, hipStream_t st, AggSlot *out);
+static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
+                      h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back, uint8_t *agg_pair, h2v_aggregate_info *info) {
     if (fell_back) *fell_back = 0;
     h2vmixed::Partition pt;
     int rc = mixed_args(plans, n_plans, b, accept, flags, &pt);
@@ -3600,7 +3654,7 @@ extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, 
         auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
         const uint64_t total = b->proof_off[n] - b->proof_off[0];
         const size_t o_inst = up16((n + 1) * 8), o_ci = o_inst + up16(pt.inst_total), o_proofs = o_ci + up16((size_t)pt.ci_total * 48), need = o_proofs + up16(total + 64);
-        const size_t out_need = up16(n) + (size_t)n * 4 + 16;
+        const size_t o_pair = up16(up16(n) + (size_t)n * 4), out_need = o_pair + 96 + 16;
         if (need > m->in_cap || out_need > m->out_cap) {
             rc = mixed_quiesce(m);
             if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
@@ -3634,10 +3688,16 @@ extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, 
             uint32_t failed = 0;
             if (hipMemcpyAsync(m->d_in, m->h_in, need, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the batch failed");
             const h2v_batch in = {n, m->d_in + o_proofs, (const uint64_t *)m->d_in, m->d_in + o_inst, m->d_in + o_ci};
-            if (rc == H2V_OK) rc = run_mixed_call(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed);
+            if (rc == H2V_OK && agg_pair) {
+                AggSlot as{};
+                if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = run_mixed(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, true, seed, &lay, as.parts);
+                if (rc == H2V_OK) rc = agg_export(ws, as, 1, m->d_out + o_pair, ws->hs);
+                if (rc == H2V_OK && hipMemcpyAsync(agg_pair, m->d_out + o_pair, 96, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the pair failed");
+                if (rc == H2V_OK) rc = agg_info_fill(info, seed, 0, 1, lay.n_r);
+            } else if (rc == H2V_OK) rc = run_mixed_call(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed);
             if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
             if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
-            if (rc == H2V_OK && rlc && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
+            if (rc == H2V_OK && rlc && !agg_pair && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
             if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "mixed-call kernels failed");
             if (rc) rc = drain_after_error(ws, rc);
             else if (fell_back) *fell_back = (failed || fold_failed) ? 1 : 0;
@@ -3645,6 +3705,202 @@ extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, 
     }
     if (tmp) h2v_workspace_free(tmp);
     return rc;
+}
+extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
+                                h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back) {
+    return mixed_host(plans, n_plans, b, accept, status, ws, flags, opts, fell_back, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------------------------- aggregate calls
+// h2v_aggregate_batch(_device) / h2v_aggregate_mixed(_device): the batch-accept forms up to and including their bucket MSMs, and
+// then the batch's pair  compress(L) || compress(R),  L = sum r_i L_i, R = sum r_i R_i,  instead of a pairing on it - "prepare the
+// batch's pair" beside h2v_prepare_batch's "prepare every proof's pair"; h2v_check_pairs(_rlc) checks pairs from anywhere.  The
+// pipelines are run_rlc, run_pipeline + fold_pairs_tail (recursive plans) and run_mixed with the fold layout, unchanged up to
+// pip_launch; agg_chunk ends every unit, and ONE k_aggregate_export per call (h2v_aggregate_dev.hpp) adds the units' sums and
+// writes the pair, on the caller's stream behind the call's lanes.  Never routed, never coalesced; no estimate moves.
+// THE INVARIANT of the parts buffer: slot q is the FIXED range [q * AGG_SLOT_PARTS, (q + 1) * AGG_SLOT_PARTS) of it, whatever the
+// calls' sizes, and ev_agg[q] - while agg_used[q] - is recorded behind the last export that read anything in that range.  A call of
+// at most AGG_SLOT_PARTS parts takes ONE slot (round robin) and waits for that slot's event; a larger call takes the WHOLE buffer
+// from its start (every slot and what lies behind them), waits for every used event and records every event behind its export.  So
+// whoever writes a range has waited, on its own stream, for every export that read it - on whatever streams the calls arrive and in
+// whatever order their sizes change.  Growing the buffer (a larger call only) waits on the host for those same events: every export
+// so far, and with them the copies of their chunks, are done; no other stream of the process is touched.
+static int agg_ensure(h2v_workspace *ws, uint32_t n_parts, hipStream_t st, AggSlot *out) {
+    constexpr uint32_t S = h2v_workspace::AGG_SLOTS, P = h2v_workspace::AGG_SLOT_PARTS;
+    const uint32_t per = n_parts ? n_parts : 1u, need = per <= P ? S * P : per;
+    for (hipEvent_t &e : ws->ev_agg) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (ws->agg_cap < need) {
+        for (uint32_t q = 0; q < S; q++)
+            if (ws->agg_used[q]) { HIPCHK(hipEventSynchronize(ws->ev_agg[q])); ws->agg_used[q] = false; }
+        if (ws->agg_parts) (void)hipFree(ws->agg_parts);
+        ws->agg_parts = nullptr; ws->agg_cap = 0;
+        const uint32_t cap = need == S * P ? need : need + need / 4;
+        if (hipMalloc((void **)&ws->agg_parts, (size_t)cap * AGG_PART_DW * 4) != hipSuccess) return fail(H2V_E_DEVICE, "hipMalloc(aggregate parts) failed");
+        ws->agg_cap = cap;
+    }
+    if (per <= P) {
+        out->slot = (uint32_t)(ws->agg_calls++ % S);
+        out->parts = ws->agg_parts + (size_t)out->slot * P * AGG_PART_DW;
+        if (ws->agg_used[out->slot]) HIPCHK(hipStreamWaitEvent(st, ws->ev_agg[out->slot], 0));
+    } else {
+        out->slot = S;      // the whole buffer
+        out->parts = ws->agg_parts;
+        for (uint32_t q = 0; q < S; q++)
+            if (ws->agg_used[q]) HIPCHK(hipStreamWaitEvent(st, ws->ev_agg[q], 0));
+    }
+    return H2V_OK;
+}
+static int agg_export(h2v_workspace *ws, const AggSlot &a, uint32_t n_parts, uint8_t *d_pair, hipStream_t st) {
+    constexpr uint32_t S = h2v_workspace::AGG_SLOTS;
+    hipLaunchKernelGGL(k_aggregate_export, dim3(1), dim3(256), 0, st, (const uint32_t *)a.parts, n_parts, (uint32_t *)d_pair);
+    HIPCHK(hipGetLastError());
+    for (uint32_t q = a.slot < S ? a.slot : 0; q < (a.slot < S ? a.slot + 1 : S); q++) {
+        HIPCHK(hipEventRecord(ws->ev_agg[q], st));
+        ws->agg_used[q] = true;
+    }
+    return H2V_OK;
+}
+static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint32_t chunk, uint32_t nch, uint64_t terms) {
+    if (!info) return H2V_OK;
+    memset(info, 0, sizeof *info);
+    memcpy(info->seed_used, seed, 32);
+    info->chunk = chunk; info->n_chunks = nch; info->msm_terms = (uint32_t)terms;
+    return H2V_OK;
+}
+static void agg_pair_inf(uint8_t pair[96]) { memset(pair, 0, 96); pair[0] = 0xc0; pair[48] = 0xc0; }
+static int agg_flags(const h2v_rlc_opts *o) {
+    if (o && (o->flags & ~(H2V_RLC_SEED_GIVEN | H2V_RLC_ONE_STREAM | H2V_RLC_FOLD_PAIRS))) return fail(H2V_E_ARG, "unknown flag in h2v_rlc_opts.flags");
+    return H2V_OK;
+}
+// the argument rules of the single-key forms that need no device
+static int agg_batch_args(const h2v_plan *p, const h2v_batch *b, const uint8_t *pair, const uint8_t *included, const h2v_rlc_opts *opts) {
+    if (!p) return fail(H2V_E_ARG, "null argument: plan");
+    if (!b) return fail(H2V_E_ARG, "null argument: batch");
+    if (!pair) return fail(H2V_E_ARG, "null argument: pair");
+    if (b->n && !included) return fail(H2V_E_ARG, "null argument: included");
+    if (int rc = agg_flags(opts)) return rc;
+    if (b->n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 proofs");
+    if (b->n)
+        if (int rc = batch_args(p, b)) return rc;
+    if (b->n && !rlc_supported(p) && !p->d.ivc) return fail(H2V_E_ARG, "this plan has no batch form (its VK-base terms are not the tail of its term list)");
+    return H2V_OK;
+}
+// One single-key aggregate call on `st`: device-resident batch `in` of n > 0 proofs, d_pair / d_included / d_status device memory.
+// A laned workspace: the chunks through the lanes, `st` joined inside the call (the per-chunk sums must meet), then the export.
+static int agg_run(const h2v_plan *p, const h2v_batch *in, uint8_t *d_pair, uint8_t *d_included, uint32_t *d_status, h2v_workspace *ws, hipStream_t st,
+                   const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
+    const uint32_t n = (uint32_t)in->n, nch = ws->n_lanes ? n_chunks(n, ws->chunk) : 1u;
+    Unit u = unit_of_batch(rlc_supported(p) ? UnitKind::RLC : UnitKind::FOLD_RLC, p, in, d_included, d_status);
+    u.one_stream_opt = opts && (opts->flags & H2V_RLC_ONE_STREAM);
+    int rc = rlc_seed(opts, u.seed);
+    if (rc) return rc;
+    agg_info_fill(info, u.seed, ws->n_lanes ? ws->chunk : 0u, nch, u.kind == UnitKind::RLC ? (uint64_t)n * p->n_var + (uint64_t)nch * p->n_fix : (uint64_t)n);
+    if ((rc = rlc_stats_ensure(ws))) return rc;      // (the records' verdict words)
+    AggSlot as{};
+    if ((rc = agg_ensure(ws, nch, st, &as))) return rc;
+    u.agg_parts = as.parts;
+    if ((rc = ws->n_lanes ? run_laned(u, ws, st, Join::NOW) : run_unit(u, ws, st))) return rc;
+    return agg_export(ws, as, nch, d_pair, st);
+}
+extern "C" int h2v_aggregate_batch_device(const h2v_plan *p, const h2v_batch *b, uint8_t *pair, uint8_t *included, uint32_t *status, h2v_workspace *ws,
+                                          void *stream, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
+    int rc = agg_batch_args(p, b, pair, included, opts);
+    if (rc) return rc;
+    if ((uintptr_t)pair & 3) return fail(H2V_E_ARG, "pair must be 4-byte aligned");
+    if (!ws) return fail(H2V_E_ARG, "the device form needs a workspace");
+    ALIVE(p); ALIVE(ws);
+    HIPCHK(hipSetDevice(p->device));
+    if (b->n && (rc = ws_fits(ws, p, b->n, false))) return rc;
+    if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
+    if ((rc = null_stream_check(ws, stream))) return rc;
+    if (b->n == 0) {       // nothing is included: (inf, inf), which h2v_check_pairs accepts
+        uint32_t seed[8];
+        if ((rc = rlc_seed(opts, seed))) return rc;
+        agg_info_fill(info, seed, ws->n_lanes ? ws->chunk : 0u, 1u, 0);
+        AggSlot as{};
+        if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
+        return agg_export(ws, as, 0, pair, (hipStream_t)stream);
+    }
+    return agg_run(p, b, pair, included, status, ws, (hipStream_t)stream, opts, info);
+}
+// Host-buffer form: staged as h2v_prepare_batch stages its batch; pair, included[] and status[] come back before the call returns.
+extern "C" int h2v_aggregate_batch(const h2v_plan *p, const h2v_batch *b, uint8_t pair[96], uint8_t *included, uint32_t *status, h2v_workspace *ws,
+                                   const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
+    int rc = agg_batch_args(p, b, pair, included, opts);
+    if (rc) return rc;
+    const uint64_t n = b->n;
+    if (n == 0) {
+        uint32_t seed[8];
+        if ((rc = rlc_seed(opts, seed))) return rc;
+        agg_info_fill(info, seed, ws && ws->n_lanes ? ws->chunk : 0u, 1u, 0);
+        agg_pair_inf(pair);
+        return H2V_OK;
+    }
+    TmpWs tmp;
+    if ((rc = pairs_common(p, n, ws, nullptr, false, tmp))) return rc;
+    rc = host_stream(ws);
+    h2v_batch in{};
+    if (rc == H2V_OK) rc = hp_ensure(ws, n);
+    if (rc == H2V_OK) rc = stage_batch(p, b, ws, ws->n_lanes ? ws->hslot[ws->h_head % h2v_workspace::MAXH] : ws->hslot[0], &in);
+    if (rc == H2V_OK) {
+        uint8_t *d_pair = ws->hp_buf, *d_included = ws->hp_buf + 96 + (size_t)n * 4;
+        uint32_t *d_status = (uint32_t *)(ws->hp_buf + 96);
+        rc = agg_run(p, &in, d_pair, d_included, d_status, ws, ws->hs, opts, info);
+        if (rc == H2V_OK && hipMemcpyAsync(pair, d_pair, 96, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the pair failed");
+        if (rc == H2V_OK && hipMemcpyAsync(included, d_included, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of included[] failed");
+        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
+        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "aggregate kernels failed");
+        if (rc) rc = drain_after_error(ws, rc);
+    }
+    return rc;
+}
+extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *pair, uint8_t *included,
+                                          uint32_t *status, h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
+    if (!pair) return fail(H2V_E_ARG, "null argument: pair");
+    if (b && b->n == 0 && !included) included = pair;      // (nothing to write; mixed_args wants a pointer)
+    if (int rca = agg_flags(opts)) return rca;
+    h2vmixed::Partition pt;
+    int rc = mixed_args(plans, n_plans, b, included, H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM, &pt);
+    if (rc) return rc;
+    if ((uintptr_t)pair & 3) return fail(H2V_E_ARG, "pair must be 4-byte aligned");
+    if (!ws) return fail(H2V_E_ARG, "the device form needs a workspace (h2v_workspace_create_multi over the listed plans)");
+    ALIVE(ws);
+    HIPCHK(hipSetDevice(ws->device));
+    if (b->n && (rc = mixed_ws_check(plans, n_plans, b->n, ws))) return rc;
+    if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
+    if ((rc = null_stream_check(ws, stream))) return rc;
+    uint32_t seed[8] = {};
+    if ((rc = rlc_seed(opts, seed))) return rc;
+    if (b->n == 0) {
+        agg_info_fill(info, seed, 0, 1, 0);
+        AggSlot as{};
+        if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
+        return agg_export(ws, as, 0, pair, (hipStream_t)stream);
+    }
+    h2vmixed::FoldLayout lay;
+    if ((rc = mixed_fold_layout(plans, pt, ws, &lay))) return rc;
+    agg_info_fill(info, seed, 0, 1, lay.n_r);
+    AggSlot as{};
+    if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
+    const h2v_batch in = {b->n, b->proofs, b->proof_off, b->instances, b->committed};
+    // (run_mixed, not run_mixed_call: no verdict comes down, the stream is not synchronised and nothing runs a second time)
+    if ((rc = run_mixed(plans, pt, nullptr, in, included, status, ws, (hipStream_t)stream, true, seed, &lay, as.parts))) return rc;
+    return agg_export(ws, as, 1, pair, (hipStream_t)stream);
+}
+extern "C" int h2v_aggregate_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t pair[96], uint8_t *included,
+                                   uint32_t *status, h2v_workspace *ws, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
+    if (!pair) return fail(H2V_E_ARG, "null argument: pair");
+    if (int rca = agg_flags(opts)) return rca;
+    if (b && b->n == 0) {      // (inf, inf) without a device; the argument rules still hold
+        h2vmixed::Partition pt;
+        if (int rc = mixed_args(plans, n_plans, b, pair, H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM, &pt)) return rc;
+        uint32_t seed[8] = {};
+        if (int rc = rlc_seed(opts, seed)) return rc;
+        agg_info_fill(info, seed, 0, 1, 0);
+        agg_pair_inf(pair);
+        return H2V_OK;
+    }
+    return mixed_host(plans, n_plans, b, included, status, ws, H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM, opts, nullptr, pair, info);
 }
 
 // After the stream of an RLC call has been synchronised: did the batch check pass (1) or did the per-proof kernels run (0)?
@@ -3662,7 +3918,8 @@ extern "C" int h2v_workspace_rlc_result(h2v_workspace *w, uint32_t calls_back, u
         return H2V_OK;
     }
     HIPCHK(hipSetDevice(w->device));
-    if (batch_accepted) {   // (laned: the AND of the chunks' batch verdicts)
+    if (batch_accepted && r->agg) *batch_accepted = H2V_BATCH_NOT_CHECKED;   // (an aggregate call: the pair was exported, no pairing ran)
+    else if (batch_accepted) {   // (laned: the AND of the chunks' batch verdicts)
         uint32_t failed = 0;
         HIPCHK(hipMemcpy(&failed, rec_word(w, *r), 4, hipMemcpyDeviceToHost));
         *batch_accepted = failed == 0 ? 1u : 0u;
@@ -3704,7 +3961,7 @@ static int rec_rlc_timings(const CallRec &r, h2v_rlc_timings *tm) {
     HIPCHK(hipEventElapsedTime(&tm->bucket_sort_ms, ev[5], ev[6]));
     HIPCHK(hipEventElapsedTime(&tm->bucket_accumulate_ms, ev[6], ev[7]));
     HIPCHK(hipEventElapsedTime(&tm->bucket_reduce_ms, ev[7], ev[8]));
-    HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[8], ev[9]));
+    if (!r.agg) HIPCHK(hipEventElapsedTime(&tm->pairing_ms, ev[8], ev[9]));   // (an aggregate call: ev[9] closes the copies of its sums)
     float a0, a1;
     HIPCHK(hipEventElapsedTime(&a0, ev[0], ev[9]));
     HIPCHK(hipEventElapsedTime(&a1, ev[2], ev[9]));
