@@ -636,11 +636,25 @@ int h2v_probe_f28_dot2(int device, int op, uint32_t n, const uint32_t *a, const 
 int h2v_probe_pairing(const h2v_plan *plan, uint32_t n, const uint8_t *p1_compressed, const uint8_t *p2_compressed,
                       uint8_t *out);
 /* same with an explicit kernel (impl 0: one lane per proof, 1: cooperative - 32 lanes per proof, or the wide engine for small n,
- * as the launcher picks -, 2 / 3 / 5: its narrow (16 lanes per proof) / wide (64) / six-lane engine whatever n, -1: default) and an
- * optional dump (n * 24 * 48 bytes): the 12 Fp coefficients (flat order w^k, re/im; canonical LE) of f after the
- * Miller loop and, for the cooperative kernel, after the final exponentiation */
+ * as the launcher picks, or the engine H2V_OPT_PAIRING_ENGINE of h2v_probe_set_option names -, 2 / 3 / 5 / 6: its narrow (16 lanes
+ * per proof) / wide (64) / six-lane / twelve-lane engine whatever n, -1: default) and an optional dump (n * 24 * 48 bytes): the 12 Fp
+ * coefficients (flat order w^k, re/im; canonical LE) of f after the Miller loop (records 0..11) and after the final
+ * exponentiation (records 12..23), from every kernel */
 int h2v_probe_pairing_ex(const h2v_plan *plan, uint32_t n, const uint8_t *p1_compressed, const uint8_t *p2_compressed,
                          uint8_t *out, int impl, uint8_t *dbg);
+/* The same launch with the entry states a pipeline can hand the pairing, and everything it writes.  Optional inputs (NULL: as
+ * above): status_in - n status words the proofs arrive with; valid_sub_in - n x 2 bytes, the subgroup verdict of slot p1 and of
+ * slot p2 (NULL: the kernel gets no such array); el_jac_in - n x 36 dwords X, Y, Z (12 x 32-bit limbs of the Montgomery form the kernels keep, R = 2^392;
+ * infinity is Z = 0): the first argument in Jacobian form, taken instead of slot p1 as recursion and the fold-pairs batch form
+ * pass it.  Outputs, each optional: status_out - n + H2V_PROBE_PAIRING_GUARD words; accept - n + GUARD bytes; dbg - (n + GUARD)
+ * x 24 x 48 bytes, records as above; lanes_out - lanes per proof of the engine that ran (1, 6, 12, 16, 32, 64).  Every device
+ * output is allocated for n + GUARD proofs, preset to 0xA5 bytes and copied back whole: a record no kernel wrote - a proof
+ * rejected on entry, and everything behind proof n - 1, where the dead groups of the last wave would write - reads 0xA5.
+ * tests/test_pairing_engines_gpu.py */
+#define H2V_PROBE_PAIRING_GUARD 64u
+int h2v_probe_pairing_states(const h2v_plan *plan, uint32_t n, const uint8_t *p1_compressed, const uint8_t *p2_compressed, int impl,
+                             const uint32_t *status_in, const uint8_t *valid_sub_in, const uint32_t *el_jac_in,
+                             uint32_t *status_out, uint8_t *accept, uint8_t *dbg, uint32_t *lanes_out);
 
 /* ---- library lifecycle (round 4) ---------------------------------------------------------------------------------
  * h2v_shutdown(device) - device = -1: every device - quiesces and releases everything the library owns there: it waits

@@ -105,6 +105,7 @@ EXPORTS = [
     "h2v_verify_batch", "h2v_verify_batch_submit", "h2v_verify_batch_wait", "h2v_verify_batch_device", "h2v_verify_batch_rlc", "h2v_verify_batch_rlc_device",
     "h2v_workspace_rlc_result", "h2v_probe_g1_msm_pippenger", "h2v_probe_g1_msm_pippenger_ex", "h2v_plan_trace_slots", "h2v_trace", "h2v_probe_vm", "h2v_probe_field",
     "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_f28_dot2", "h2v_probe_pairing", "h2v_probe_pairing_ex",
+    "h2v_probe_pairing_states",
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
@@ -185,6 +186,8 @@ def lib():
         L.h2v_probe_g1_msm_fixed.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.h2v_probe_pairing.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
         L.h2v_probe_pairing_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.h2v_probe_pairing_states.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.h2v_shutdown.argtypes = [C.c_int]
         L.h2v_prepare_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_prepare_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -916,3 +919,62 @@ def probe_pairing_ex(plan: DevicePlan, p1_list, p2_list, impl: int, dump: bool =
             row = [int.from_bytes(dbg.raw[(i * 24 + q) * 48:(i * 24 + q + 1) * 48], "little") for q in range(24)]
             vals.append((row[:12], row[12:]))
     return [out.raw[i] for i in range(n)], vals
+
+
+PROBE_PAIRING_GUARD = 64      # H2V_PROBE_PAIRING_GUARD: proofs' worth of preset records behind the batch
+
+
+def g1_jacobian_limbs(pt, z: int = 1) -> bytes:
+    """The 36 dwords X, Y, Z (h2v_probe_pairing_states: el_jac_in) of the affine point pt = (x, y) scaled to the Jacobian
+    representative with the chosen Z != 0 mod p: (x Z^2, y Z^3, Z), each as bls12_381.fp_mont_bytes has it (the kernels' Montgomery
+    form, R = 2^392, 12 little-endian 32-bit limbs).  pt None: infinity as g1j_set_inf writes it, (1, 1, 0)."""
+    from . import bls12_381 as bls
+    if pt is None:
+        return bls.fp_mont_bytes(1) + bls.fp_mont_bytes(1) + bls.fp_mont_bytes(0)
+    if z % bls.P == 0:
+        raise ValueError("Z = 0 is infinity")
+    x, y = pt
+    return bls.fp_mont_bytes(x * z * z) + bls.fp_mont_bytes(y * z * z * z) + bls.fp_mont_bytes(z)
+
+
+class PairingStates:
+    """What h2v_probe_pairing_states brought back.  accept / status / values: per proof (values: (Miller, final), 12 integers each,
+    None where the kernel left all 24 records at the preset; a record partly written is given as the integers it holds).  guard_clean:
+    every byte behind proof n - 1 of all three outputs is still the preset.  lanes: the engine that ran, in lanes per proof."""
+    __slots__ = ("accept", "status", "values", "guard_clean", "lanes")
+
+
+def probe_pairing_states(plan: DevicePlan, p1_list, p2_list, impl: int, status_in=None, valid_sub_in=None, el_jac_in=None) -> PairingStates:
+    """status_in: n integers; valid_sub_in: n pairs (slot p1, slot p2) of 0 / 1; el_jac_in: n byte strings from g1_jacobian_limbs.
+    Each may be None (the pipelines' plain first launch)."""
+    n = len(p1_list)
+    cap = n + PROBE_PAIRING_GUARD
+    if len(p2_list) != n or any(v is not None and len(v) != n for v in (status_in, valid_sub_in, el_jac_in)):
+        raise ValueError("one entry per proof")
+    st_in = (C.c_uint32 * n)(*status_in) if status_in is not None else None
+    sub_in = bytes(b for pair in valid_sub_in for b in pair) if valid_sub_in is not None else None
+    el_in = b"".join(el_jac_in) if el_jac_in is not None else None
+    if el_in is not None and len(el_in) != n * 144:
+        raise ValueError("el_jac_in: 144 bytes per proof")
+    st_out = (C.c_uint32 * cap)()
+    acc = C.create_string_buffer(cap)
+    dbg = C.create_string_buffer(cap * 24 * 48)
+    lanes = C.c_uint32(0)
+    check(lib().h2v_probe_pairing_states(plan.handle, n, b"".join(p1_list), b"".join(p2_list), impl, st_in, sub_in, el_in,
+                                         st_out, acc, dbg, C.byref(lanes)))
+    raw, preset = dbg.raw, b"\xa5" * (24 * 48)
+    r = PairingStates()
+    r.accept = [acc.raw[i] for i in range(n)]
+    r.status = [st_out[i] for i in range(n)]
+    r.values = []
+    for i in range(n):
+        rec = raw[i * 24 * 48:(i + 1) * 24 * 48]
+        if rec == preset:
+            r.values.append(None)
+            continue
+        row = [int.from_bytes(rec[q * 48:(q + 1) * 48], "little") for q in range(24)]
+        r.values.append((row[:12], row[12:]))
+    r.guard_clean = (raw[n * 24 * 48:] == b"\xa5" * (PROBE_PAIRING_GUARD * 24 * 48) and acc.raw[n:cap] == b"\xa5" * PROBE_PAIRING_GUARD
+                     and all(st_out[i] == 0xa5a5a5a5 for i in range(n, cap)))
+    r.lanes = lanes.value
+    return r

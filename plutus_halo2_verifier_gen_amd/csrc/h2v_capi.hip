@@ -4387,27 +4387,33 @@ extern "C" int h2v_probe_decompress(const h2v_plan *p, const h2v_batch *b, int w
     h2v_workspace_free(ws);
     return rc;
 }
-extern "C" int h2v_probe_pairing_ex(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out, int impl, uint8_t *dbg);
-extern "C" int h2v_probe_pairing(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out) {
-    return h2v_probe_pairing_ex(p, n, p1c, p2c, out, -1, nullptr);
-}
-// impl: -1 default, 0 one-lane-per-proof kernel, 1 cooperative kernel (the launcher's choice of engine), 2 / 3 its narrow / wide
-// engine whatever n; dbg (optional): n * 24 * 48 bytes
-// (f after the Miller loop and - cooperative kernel only - after the final exponentiation; canonical LE limbs)
-extern "C" int h2v_probe_pairing_ex(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out, int impl, uint8_t *dbg) {
-    if (!p || !p1c || !p2c || !out || n == 0) return fail(H2V_E_ARG, "bad argument");
+// The pairing launch alone on n pairs, with every entry state a pipeline can hand it.  impl: -1 default, 0 one-lane-per-proof kernel,
+// 1 cooperative kernel (the launcher's choice of engine, or H2V_OPT_PAIRING_ENGINE of h2v_probe_set_option), 2 / 3 / 5 / 6 its narrow /
+// wide / six-lane / twelve-lane engine whatever n.  Optional inputs (NULL: as the pipelines' first launch has them): status_in (n words
+// the proofs arrive with), valid_sub_in (n x 2 bytes, the subgroup verdicts of slots p1, p2; NULL: the kernels get no such array),
+// el_jac_in (n x 36 dwords X, Y, Z, Montgomery limbs: the first argument, instead of slot p1).  Outputs, each optional: status_out
+// (n + H2V_PROBE_PAIRING_GUARD words), accept (n + GUARD bytes), dbg ((n + GUARD) x 24 x 48 bytes: f after the Miller loop and after
+// the final exponentiation, canonical LE limbs; NULL: the kernels get no dump buffer), lanes_out (launch_pairing_impl's answer: the
+// engine that ran).  The device outputs are allocated for n + GUARD proofs, preset to 0xA5 bytes and copied back whole: what a
+// kernel left unwritten shows as such, and so does what a dead group of the last wave wrote behind proof n - 1.
+extern "C" int h2v_probe_pairing_states(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, int impl, const uint32_t *status_in,
+                                        const uint8_t *valid_sub_in, const uint32_t *el_jac_in, uint32_t *status_out, uint8_t *accept, uint8_t *dbg,
+                                        uint32_t *lanes_out) {
+    if (!p || !p1c || !p2c || n == 0 || n > (1u << 24)) return fail(H2V_E_ARG, "bad argument");
     ALIVE(p);
     ProbeOpts probe_opts;
-    DevBuf ddbg;
     HIPCHK(hipSetDevice(p->device));
     MiniPlan mp;
-    DevBuf din, doff, dsc, dpts, dvalid, der, dst, dacc, dtab;
+    DevBuf din, doff, dsc, dpts, dvalid, dsub, del, der, dst, dacc, dtab, ddbg;
     mp.d.lines28_sg2 = p->d.lines28_sg2;
     mp.d.lines28_g2 = p->d.lines28_g2;
     mp.d.six_norm28 = p->d.six_norm28;
     mp.d.six_k = p->d.six_k;
+    const size_t cap = (size_t)n + H2V_PROBE_PAIRING_GUARD;
     if (mp.build(2, 1, p->d.lines_sg2, p->d.lines_g2) || upload_offsets(doff, n, 96) || din.alloc((size_t)n * 96) || dsc.alloc((size_t)n * 32) ||
-        dpts.alloc((size_t)n * 192) || dvalid.alloc((size_t)n * 2) || der.alloc((size_t)n * 144) || dst.alloc((size_t)n * 4) || dacc.alloc(n))
+        dpts.alloc((size_t)n * 192) || dvalid.alloc((size_t)n * 2) || der.alloc((size_t)n * 144) || dst.alloc(cap * 4) || dacc.alloc(cap) ||
+        dtab.alloc((size_t)n * 2 * 448 * 4) || ddbg.alloc(dbg ? cap * 24 * 48 : 8) || (valid_sub_in && dsub.alloc((size_t)n * 2)) ||
+        (el_jac_in && del.alloc((size_t)n * 144)))
         return fail(H2V_E_DEVICE, "probe setup failed");
     // MSM "sum" is 1 * p2 (term 0 must read slot 1): patch the single term
     uint32_t term[2] = {H2V_TERM_PROOF_POINT, 1};
@@ -4416,15 +4422,36 @@ extern "C" int h2v_probe_pairing_ex(const h2v_plan *p, uint32_t n, const uint8_t
     for (uint32_t i = 0; i < n; i++) { memcpy(&in[(size_t)i * 96], p1c + (size_t)i * 48, 48); memcpy(&in[(size_t)i * 96 + 48], p2c + (size_t)i * 48, 48); one[(size_t)i * 32] = 1; }
     HIPCHK(hipMemcpy(din.p, in.data(), in.size(), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(dsc.p, one.data(), one.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dst.p, 0, (size_t)n * 4));
-    if (dtab.alloc((size_t)n * 2 * 448 * 4)) return fail(H2V_E_DEVICE, "hipMalloc failed");
+    HIPCHK(hipMemset(dst.p, 0xa5, cap * 4));
+    HIPCHK(hipMemset(dacc.p, 0xa5, cap));
+    if (dbg) HIPCHK(hipMemset(ddbg.p, 0xa5, cap * 24 * 48));
+    if (status_in) HIPCHK(hipMemcpy(dst.p, status_in, (size_t)n * 4, hipMemcpyHostToDevice));
+    else HIPCHK(hipMemset(dst.p, 0, (size_t)n * 4));
+    if (valid_sub_in) HIPCHK(hipMemcpy(dsub.p, valid_sub_in, (size_t)n * 2, hipMemcpyHostToDevice));
+    if (el_jac_in) HIPCHK(hipMemcpy(del.p, el_jac_in, (size_t)n * 144, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_g1_decompress, dim3((n * 2 + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), dtab.as<uint32_t>(), 0u, (uint8_t *)nullptr);
     launch_msm(mp.d, n, dsc.as<uint32_t>(), dpts.as<uint32_t>(), dtab.as<uint32_t>(), der.as<uint32_t>(), nullptr, nullptr, nullptr);
-    if (ddbg.alloc(dbg ? (size_t)n * 24 * 48 : 8)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    launch_pairing_impl(impl, mp.d, n, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), nullptr, der.as<uint32_t>(), nullptr, dst.as<uint32_t>(), dacc.as<uint8_t>(), dbg ? ddbg.as<uint32_t>() : nullptr, nullptr);
+    const uint32_t lanes = launch_pairing_impl(impl, mp.d, n, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), valid_sub_in ? dsub.as<uint8_t>() : nullptr, der.as<uint32_t>(),
+                                               el_jac_in ? del.as<uint32_t>() : nullptr, dst.as<uint32_t>(), dacc.as<uint8_t>(), dbg ? ddbg.as<uint32_t>() : nullptr, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dacc.p, n, hipMemcpyDeviceToHost));
-    if (dbg) HIPCHK(hipMemcpy(dbg, ddbg.p, (size_t)n * 24 * 48, hipMemcpyDeviceToHost));
+    if (lanes_out) *lanes_out = lanes;
+    if (status_out) HIPCHK(hipMemcpy(status_out, dst.p, cap * 4, hipMemcpyDeviceToHost));
+    if (accept) HIPCHK(hipMemcpy(accept, dacc.p, cap, hipMemcpyDeviceToHost));
+    if (dbg) HIPCHK(hipMemcpy(dbg, ddbg.p, cap * 24 * 48, hipMemcpyDeviceToHost));
     return H2V_OK;
+}
+// e(p1, s_g2) == e(p2, G2) with status 0 on entry: the first n verdicts (and, dbg given, the first n x 24 records) of the call above
+extern "C" int h2v_probe_pairing_ex(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out, int impl, uint8_t *dbg) {
+    if (!p || !p1c || !p2c || !out || n == 0 || n > (1u << 24)) return fail(H2V_E_ARG, "bad argument");
+    const size_t cap = (size_t)n + H2V_PROBE_PAIRING_GUARD;
+    std::vector<uint8_t> acc(cap), rec(dbg ? cap * 24 * 48 : 0);
+    const int rc = h2v_probe_pairing_states(p, n, p1c, p2c, impl, nullptr, nullptr, nullptr, nullptr, acc.data(), dbg ? rec.data() : nullptr, nullptr);
+    if (rc) return rc;
+    memcpy(out, acc.data(), n);
+    if (dbg) memcpy(dbg, rec.data(), (size_t)n * 24 * 48);
+    return H2V_OK;
+}
+extern "C" int h2v_probe_pairing(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out) {
+    return h2v_probe_pairing_ex(p, n, p1c, p2c, out, -1, nullptr);
 }

@@ -681,9 +681,10 @@ H2V_DN void fp12_exp_x(Fp12 &r, const Fp12 &a) {
     }
     fp12_conj(r, acc);
 }
-H2V_DN bool final_exp_is_one(const Fp12 &f) {
+// (out, optional: the final value, for the probe's dump; f itself - zero - where f has no inverse)
+H2V_DN bool final_exp_is_one(const Fp12 &f, Fp12 *out = nullptr) {
     Fp12 t, a, u, t0, t1, t2, t3;
-    if (!fp12_inv(a, f)) return false;
+    if (!fp12_inv(a, f)) { if (out) *out = f; return false; }
     fp12_conj(t, f); fp12_mul(t, t, a);                       // f^(p^6-1)
     fp12_frob(a, t); fp12_frob(a, a); fp12_mul(t, a, t);      // ^(p^2+1)
     fp12_exp_x(a, t); fp12_conj(u, t); fp12_mul(t0, a, u);    // t^(x-1)
@@ -694,6 +695,7 @@ H2V_DN bool final_exp_is_one(const Fp12 &f) {
     fp12_conj(u, t2); fp12_mul(t3, t3, u);                    // ^(x^2+p^2-1)
     fp12_sqr(u, t); fp12_mul(u, u, t);                        // t^3
     fp12_mul(t3, t3, u);
+    if (out) *out = t3;
     return fp12_is_one(t3);
 }
 
@@ -726,16 +728,21 @@ k_pairing_check(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, c
         fp_neg(er.y, er.y);  // -er (harmless on the infinity sentinel: skipped below)
         Fp12 f;
         miller_loop(f, el, plan.lines_sg2, el_inf, er, plan.lines_g2, er_inf);
-        if (dbg) {  // flat order (k, part): tower c0 = (w^0, w^2, w^4), c1 = (w^1, w^3, w^5)
-            const Fp2 *co[6] = {&f.c0.c0, &f.c1.c0, &f.c0.c1, &f.c1.c1, &f.c0.c2, &f.c1.c2};
+        // records 0..11: f after the Miller loop, 12..23: after the final exponentiation; flat order (k, part): tower
+        // c0 = (w^0, w^2, w^4), c1 = (w^1, w^3, w^5)
+        auto dump = [&](const Fp12 &v, int rec0) {
+            const Fp2 *co[6] = {&v.c0.c0, &v.c1.c0, &v.c0.c1, &v.c1.c1, &v.c0.c2, &v.c1.c2};
             for (int k = 0; k < 6; k++) {
                 Fp o0, o1;
                 fp_from_mont(o0, co[k]->c0);
                 fp_from_mont(o1, co[k]->c1);
-                for (int q = 0; q < 12; q++) { dbg[((size_t)i * 24 + 2 * k) * 12 + q] = o0.v[q]; dbg[((size_t)i * 24 + 2 * k + 1) * 12 + q] = o1.v[q]; }
+                for (int q = 0; q < 12; q++) { dbg[((size_t)i * 24 + rec0 + 2 * k) * 12 + q] = o0.v[q]; dbg[((size_t)i * 24 + rec0 + 2 * k + 1) * 12 + q] = o1.v[q]; }
             }
-        }
-        if (!final_exp_is_one(f)) st |= H2V_ST_PAIRING;
+        };
+        if (dbg) dump(f, 0);
+        Fp12 fin;
+        if (!final_exp_is_one(f, dbg ? &fin : nullptr)) st |= H2V_ST_PAIRING;
+        if (dbg) dump(fin, 12);
     }
     status[i] = st;
     accept[i] = st == 0 ? 1 : 0;

@@ -6,21 +6,13 @@ infinity, both - are replayed ONCE each with big integers (tools/gen_coop_progra
 trailing wave (nine dead groups shadowing it).  Both values the probe dumps - after the Miller loop and after the final
 exponentiation - are compared coefficient by coefficient; a loop whose G1 argument is infinity is skipped (the `keep` path: its line
 steps run and leave f as staged), so its Miller value is the other loop's alone."""
-import os
-import random
-import sys
-
 import pytest
 
-from plutus_halo2_verifier_gen_amd import bls12_381 as bls
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+from tests import pairing_kinds as K
+from tests.pairing_kinds import ACCEPT, REJECT_A, REJECT_B, INF_1, INF_2, INF_BOTH, N_KINDS
 
 pytestmark = pytest.mark.gpu
 IMPL_SIX = 5                              # h2v_probe_pairing_ex: the six-lane kernel
-ACCEPT, REJECT_A, REJECT_B, INF_1, INF_2, INF_BOTH = range(6)
-N_KINDS = 6
 BATCHES = (1, 10, 11, 21)
 
 
@@ -34,32 +26,10 @@ def simple_mul():
 
 @pytest.fixture(scope="module")
 def kinds(simple_mul):
-    """Per kind: (compressed p1, compressed p2, verdict, Miller value, final value), the values as 12 integers (re, im of coefficient
-    0..5) from the replay: accept <=> e(p1, [s]G2) == e(p2, G2)."""
-    import gen_coop_program as gp
+    """Per kind: (compressed p1, compressed p2, verdict, Miller value, final value, ...), the values as 12 integers (re, im of
+    coefficient 0..5) from the replay: accept <=> e(p1, [s]G2) == e(p2, G2).  tests/pairing_kinds.py builds them."""
     vk, td, dp = simple_mul
-    rng = random.Random(68)
-    q1 = bls.g2_mul(bls.G2_GEN, td.s)
-    assert bls.g2_compress(q1) == bytes.fromhex(vk.s_g2)
-    a, b, c = (bls.g1_mul(bls.G1_GEN, rng.randrange(1, bls.R)) for _ in range(3))
-    pts = {ACCEPT: (a, bls.g1_mul(a, td.s)),
-           REJECT_A: (b, bls.g1_add(bls.g1_mul(b, td.s), bls.G1_GEN)),
-           REJECT_B: (c, bls.g1_mul(c, (td.s + 2) % bls.R)),
-           INF_1: (None, bls.g1_mul(bls.G1_GEN, 5)),
-           INF_2: (bls.g1_mul(bls.G1_GEN, 7), None),
-           INF_BOTH: (None, None)}
-    prog = gp.build_program()
-    first_dump = [i for i, ins in enumerate(prog) if ins[0] == gp.OP_DUMP][0]
-    assert prog[first_dump][1:3] == (0, gp.U) and prog[first_dump - 1][:3] == (gp.OP_CONJ, gp.U, gp.F)
-    miller_prog = prog[:first_dump - 1] + [(gp.OP_END, 0, 0, 0)]       # dump 0 is conj(F) after the Miller loop
-    flat = lambda f: [x for pair in f for x in pair]
-    out = {}
-    for kind, (p1, p2) in pts.items():
-        final = gp.simulate(prog, p1, q1, p2, bls.G2_GEN)
-        miller = bls.f12_conj(gp.simulate(miller_prog, p1, q1, p2, bls.G2_GEN))
-        out[kind] = (bls.g1_compress(p1), bls.g1_compress(p2), 1 if final == bls.F12_ONE else 0, flat(miller), flat(final))
-    assert [out[k][2] for k in range(N_KINDS)] == [1, 0, 0, 0, 0, 1]
-    return out
+    return K.build_kinds(vk, td)
 
 
 def test_the_six_kinds_are_what_they_are_meant_to_be(kinds):
