@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "h2v_mixed_fold_dev.hpp"
 #include "h2v_aggregate_dev.hpp"
 #include "h2v_msm_shape.hpp"
+#include "h2v_hostcall_layout.hpp"
 #include "h2v_plancc.hpp"
 
 static thread_local std::string g_err;
@@ -38,6 +40,33 @@ static int fail(int code, const std::string &msg) {
     } while (0)
 
 extern "C" const char *h2v_last_error(void) { return g_err.c_str(); }
+
+// A block of device (PINNED = false) or pinned host memory that grows on demand, and THE slack rule of every staging block of this
+// file: a request that does not fit frees the block and allocates a quarter more than was asked for, so that a caller whose
+// batches creep upwards does not re-allocate at every call.  What may still be using the old block differs from site to site:
+// the caller passes its wait as `quiet`, which runs before the free (its error is returned and the block stays).  No destructor:
+// the workspace releases its blocks itself (ws_release), on the right device.
+template <bool PINNED> struct GrowBuf {
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+    template <class Quiet> int ensure(size_t need, const char *what, Quiet &&quiet) {
+        if (need <= cap) return H2V_OK;
+        if (int rc = quiet()) return rc;
+        release();
+        const size_t c = need + need / 4;
+        if ((PINNED ? hipHostMalloc((void **)&p, c, hipHostMallocDefault) : hipMalloc((void **)&p, c)) != hipSuccess) {
+            p = nullptr;
+            return fail(H2V_E_DEVICE, std::string("allocation of ") + what + " failed");
+        }
+        cap = c;
+        return H2V_OK;
+    }
+    void release() {
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        p = nullptr; cap = 0;
+    }
+};
+static int no_wait() { return H2V_OK; }      // (a GrowBuf whose old block nothing can still be using)
 
 // ---------------------------------------------------------------------------------------------- lifecycle
 // Everything the library owns on a device - the pool of CU-mask streams (make_stream), every live workspace's buffers,
@@ -216,12 +245,13 @@ struct h2v_workspace {
     uint32_t *dec_ctr = nullptr; // work-queue counter of the decompression launch
     uint8_t *valid = nullptr, *valid_sub = nullptr, *accept = nullptr;
     // pair check (run_check): the two-slot view of 96-byte records - offsets 96 i (cap + 1 entries) and the slot table {0, 48} -
-    // allocated and filled by the first check call on this workspace; hp_buf: the device side of the host-buffer prepare /
-    // check calls (grown when a larger batch comes along)
+    // allocated and filled by the first check call on this workspace
     uint64_t *pair_off = nullptr;
     uint32_t *pair_pts = nullptr;
-    uint8_t *hp_buf = nullptr;
-    size_t hp_cap = 0;
+    // THE result block of the blocking host-buffer forms (prepare, pair check, aggregate, mixed): the device memory their kernels
+    // write and the downloads read, laid out per call by hostcall::result_block.  One block serves every form because each of
+    // them synchronises `hs` before it returns (host_call_tail) or drains every stream on error: no two calls ever use it at once.
+    GrowBuf<false> res;
     // Host-buffer entry points: the batch is packed into ONE pinned host block (offsets | instances | committed | proofs),
     // uploaded with one asynchronous copy on the workspace's own stream `hs`, verified there, and the accept bytes come
     // back into pinned memory the same way: h2v_verify_batch_submit returns once everything is enqueued, _wait collects.
@@ -280,8 +310,8 @@ struct h2v_workspace {
     // host-buffer batches in flight on a laned workspace (h2v_verify_batch_submit / _wait): a ring of staging slots, each
     // with its own pinned block, device block and accept buffers; uploads on `hs`, downloads on `hs_down` (stage_batch)
     struct HostSlot {
-        uint8_t *in_block = nullptr, *h_block = nullptr, *h_accept = nullptr, *d_accept = nullptr;
-        size_t in_cap = 0, acc_cap = 0;
+        GrowBuf<false> in_block, d_accept;      // (d_accept: laned only)
+        GrowBuf<true> h_block, h_accept;
         hipEvent_t ev = nullptr;
         uint64_t n = 0;
         bool rlc = false;
@@ -301,12 +331,11 @@ struct h2v_workspace {
     // gathered into; co_open: the lanes whose groups are open, oldest first (one group per plan and mode, at most four)
     struct Coalesce *co[MAXL] = {};
     struct MixedWs *mixed = nullptr;        // staging of the mixed-key calls (h2v_verify_mixed), created by the first one
-    // aggregate calls (h2v_aggregate_batch / _mixed): the parts buffer, agg_cap parts of [2][36] dwords - every chunk's two
+    // aggregate calls (h2v_aggregate_batch / _mixed): the parts buffer, parts of [2][36] dwords - every chunk's two
     // Jacobian sums, which k_aggregate_export adds.  AGG_SLOTS fixed slots of AGG_SLOT_PARTS parts each, one per call in flight, so
     // that calls on several caller streams overlap; a call of more parts takes the whole buffer (agg_ensure has the invariant)
     static constexpr uint32_t AGG_SLOTS = 16, AGG_SLOT_PARTS = 128;     // (as many calls as a workspace has lanes)
-    uint32_t *agg_parts = nullptr;
-    uint32_t agg_cap = 0;
+    GrowBuf<false> agg_parts;
     uint64_t agg_calls = 0;
     hipEvent_t ev_agg[AGG_SLOTS] = {};
     bool agg_used[AGG_SLOTS] = {};
@@ -664,17 +693,15 @@ static void co_release(h2v_workspace *w);
 static void mixed_release(h2v_workspace *w);
 static int co_flush(h2v_workspace *w);
 static int lane_streams(uint32_t l, hipStream_t *main_st, hipStream_t *side_st);
+static void slot_release(h2v_workspace::HostSlot &sl) {
+    sl.in_block.release(); sl.d_accept.release(); sl.h_block.release(); sl.h_accept.release();
+    if (sl.ev) (void)hipEventDestroy(sl.ev);
+    sl = h2v_workspace::HostSlot();
+}
 static void ws_release(h2v_workspace *w) {
     (void)hipSetDevice(w->device);
     if (w->hs_down) (void)hipStreamSynchronize(w->hs_down);
-    for (auto &sl : w->hslot) {
-        if (sl.in_block) (void)hipFree(sl.in_block);
-        if (sl.d_accept) (void)hipFree(sl.d_accept);
-        if (sl.h_block) (void)hipHostFree(sl.h_block);
-        if (sl.h_accept) (void)hipHostFree(sl.h_accept);
-        if (sl.ev) (void)hipEventDestroy(sl.ev);
-        sl = h2v_workspace::HostSlot();
-    }
+    for (auto &sl : w->hslot) slot_release(sl);
     for (uint32_t l = 0; l < (uint32_t)h2v_workspace::MAXL; l++)
         if (w->lane_st[l]) { (void)hipStreamSynchronize(w->lane_st[l]); }
     mixed_release(w);
@@ -691,8 +718,9 @@ static void ws_release(h2v_workspace *w) {
     for (hipEvent_t &e : w->ev_pipe) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
     void *ptrs[] = {w->rlc_stats, w->rec_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
-                    w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts, w->hp_buf, w->agg_parts};
+                    w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts};
     for (void *q : ptrs) if (q) (void)hipFree(q);
+    w->res.release(); w->agg_parts.release();
     for (hipEvent_t &e : w->ev_agg) if (e) { (void)hipEventDestroy(e); e = nullptr; }
     if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
     if (w->copy_streams_owned) {
@@ -2307,52 +2335,87 @@ static int host_stream(h2v_workspace *ws) {
     }
     return H2V_OK;
 }
-// bytes a host-buffer call's verdicts take in its pinned download block: accept[n], then the RLC verdict word at the next multiple of 8
-static inline size_t accept_extent(uint64_t n) { return (size_t)((n + 7) & ~(uint64_t)7) + 8; }
-// Packs the caller's host buffers into the pinned block of staging slot `sl` (offsets | instances | committed | proofs, each
-// 16-byte aligned), enqueues ONE upload of it on ws->hs, and returns the batch's device view in `in`.  The slot's blocks grow
-// to a quarter more than a batch that does not fit.  A laned workspace's slot is free by construction and downloads accept[]
-// through a device buffer of its own (d_accept); an ordinary workspace stages in hslot[0], and its accept[] is ws->accept.
-static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, h2v_workspace::HostSlot &sl, h2v_batch *in) {
-    const bool laned = ws->n_lanes != 0;
-    const uint64_t n = b->n;
-    const uint64_t total = b->proof_off[n];
-    for (uint64_t i = 0; i < n; i++)
-        if (b->proof_off[i + 1] < b->proof_off[i]) return fail(H2V_E_ARG, "proof offsets must be non-decreasing");
-    if (int rc = host_stream(ws)) return rc;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_inst = up16((n + 1) * 8), o_ci = o_inst + up16(n * p->d.n_pi * 32), o_proofs = o_ci + up16(n * p->d.n_ci * 48),
-                 need = o_proofs + up16(total + 64);
-    if (need > sl.in_cap) {
-        if (!laned) HIPCHK(hipStreamSynchronize(ws->hs));   // (the ordinary workspace's one slot: an earlier upload may still read it)
-        if (sl.in_block) (void)hipFree(sl.in_block);
-        if (sl.h_block) (void)hipHostFree(sl.h_block);
-        sl.in_block = nullptr; sl.h_block = nullptr; sl.in_cap = 0;
-        const size_t cap = need + need / 4;
-        if (hipMalloc((void **)&sl.in_block, cap) != hipSuccess || hipHostMalloc((void **)&sl.h_block, cap, hipHostMallocDefault) != hipSuccess)
-            return fail(H2V_E_DEVICE, "staging allocation failed");
-        sl.in_cap = cap;
-    }
-    // (accept bytes, then - RLC mode - the verdict word at the next multiple of 8: the capacity is compared with THAT extent;
-    //  comparing it with n let a batch within 8 proofs of an earlier, smaller batch's slack put the word past the end of the
-    //  pinned block: hipMemcpyAsync "invalid argument", found by tools/soak.py)
-    if (accept_extent(n) > sl.acc_cap) {
-        if (sl.h_accept) (void)hipHostFree(sl.h_accept);
-        if (sl.d_accept) (void)hipFree(sl.d_accept);
-        sl.h_accept = nullptr; sl.d_accept = nullptr; sl.acc_cap = 0;
-        const size_t cap = accept_extent(n) + n / 4 + 64;
-        if (hipHostMalloc((void **)&sl.h_accept, cap, hipHostMallocDefault) != hipSuccess || (laned && hipMalloc((void **)&sl.d_accept, cap) != hipSuccess))
-            return fail(H2V_E_DEVICE, "staging allocation failed");
-        sl.acc_cap = cap;
-    }
-    memcpy(sl.h_block, b->proof_off, (n + 1) * 8);
-    if (p->d.n_pi) memcpy(sl.h_block + o_inst, b->instances, n * p->d.n_pi * 32);
-    if (p->d.n_ci) memcpy(sl.h_block + o_ci, b->committed, n * 48);
-    memcpy(sl.h_block + o_proofs, b->proofs, total);
-    memset(sl.h_block + o_proofs + total, 0, 64);
-    HIPCHK(hipMemcpyAsync(sl.in_block, sl.h_block, need, hipMemcpyHostToDevice, ws->hs));
-    *in = {n, sl.in_block + o_proofs, (const uint64_t *)sl.in_block, sl.in_block + o_inst, sl.in_block + o_ci};
+using HostSlot = h2v_workspace::HostSlot;
+// What a host-buffer form waits for before one of its blocks is freed: everything on `hs` - an earlier upload may still read the
+// block, an earlier call's kernels write it - and, a mixed form (m given), every earlier mixed call on the workspace before that.
+struct MixedWs;
+static int mixed_quiesce(MixedWs *m);
+static int host_quiet(h2v_workspace *ws, MixedWs *m) {
+    if (m)
+        if (int rc = mixed_quiesce(m)) return rc;
+    HIPCHK(hipStreamSynchronize(ws->hs));
     return H2V_OK;
+}
+// THE packer of the host-buffer forms.  Packs the caller's batch into the pinned block of staging slot `sl` (hostcall::input_block:
+// offsets | instances | committed | proofs; inst_bytes / ci_bytes size the two middle sections), enqueues ONE upload of it on
+// ws->hs and returns the batch's device view in `in`.  Before a block that is too small is freed: an ordinary workspace's one
+// slot (hslot[0]) waits for `hs`, a laned workspace's slot is free by construction, the mixed forms' slot (m given) waits as
+// host_quiet says.
+static int stage_batch(const h2v_batch *b, size_t inst_bytes, size_t ci_bytes, h2v_workspace *ws, HostSlot &sl, h2v_batch *in, MixedWs *m = nullptr) {
+    const uint64_t n = b->n;
+    if (!hostcall::offsets_ascend(n, b->proof_off)) return fail(H2V_E_ARG, "proof offsets must be non-decreasing");
+    if (int rc = host_stream(ws)) return rc;
+    const hostcall::InputBlock L = hostcall::input_block(n, inst_bytes, ci_bytes, b->proof_off[n] - b->proof_off[0]);
+    auto quiet = [&]() { return ws->n_lanes && !m ? (int)H2V_OK : host_quiet(ws, m); };
+    if (int rc = sl.in_block.ensure(L.need, "the staging block", quiet)) return rc;
+    if (int rc = sl.h_block.ensure(L.need, "the staging block", quiet)) return rc;
+    hostcall::pack_input(sl.h_block.p, L, n, b->proof_off, b->proofs, b->instances, b->committed);
+    HIPCHK(hipMemcpyAsync(sl.in_block.p, sl.h_block.p, L.need, hipMemcpyHostToDevice, ws->hs));
+    *in = {n, sl.in_block.p + L.proofs, (const uint64_t *)(sl.in_block.p + L.offsets), sl.in_block.p + L.inst, sl.in_block.p + L.ci};
+    return H2V_OK;
+}
+// the slot a blocking form stages in (no batch is in flight: pairs_common): the ring's next slot, or the ordinary workspace's one
+static HostSlot &own_slot(h2v_workspace *ws) { return ws->hslot[ws->n_lanes ? ws->h_head % h2v_workspace::MAXH : 0]; }
+// (one key: the section sizes follow from the plan)
+static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws, HostSlot &sl, h2v_batch *in) {
+    return stage_batch(b, (size_t)b->n * p->d.n_pi * 32, (size_t)b->n * p->d.n_ci * 48, ws, sl, in);
+}
+// A submitted batch: its slot's pinned download block (hostcall::accept_extent) and, laned, the device buffer its chunks write
+// accept[] to (an ordinary workspace's is ws->accept) - the slot has no batch in flight, so nothing is waited for -, then the
+// batch staged and u pointed at the device copy.
+static int stage_unit(Unit &u, const h2v_batch *b, h2v_workspace *ws, HostSlot &sl) {
+    const size_t need = hostcall::accept_extent(b->n);
+    if (int rc = sl.h_accept.ensure(need, "the download block", no_wait)) return rc;
+    if (ws->n_lanes)
+        if (int rc = sl.d_accept.ensure(need, "the download block", no_wait)) return rc;
+    h2v_batch in;
+    if (int rc = stage_batch(u.p, b, ws, sl, &in)) return rc;
+    u.proofs = in.proofs; u.off = in.proof_off; u.inst = in.instances; u.ci = in.committed;
+    return H2V_OK;
+}
+// How many batch checks of the call just enqueued on ws failed - its record's word - comes down on `st`.  (Asynchronous: a
+// synchronous copy would go through the legacy NULL stream, which every pool stream is ordered with, and drain all batches in flight.)
+static int verdict_down(h2v_workspace *ws, void *dst, hipStream_t st) {
+    if (hipMemcpyAsync(dst, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(H2V_E_DEVICE, "download of the batch verdict failed");
+    return H2V_OK;
+}
+// the results of the batch just enqueued into its slot's download block, on `st`: accept[n] and - a batch-check call - the verdict word
+static int slot_download(h2v_workspace *ws, HostSlot &sl, const uint8_t *d_accept, hipStream_t st) {
+    if (hipMemcpyAsync(sl.h_accept.p, d_accept, sl.n, hipMemcpyDeviceToHost, st) != hipSuccess) return fail(H2V_E_DEVICE, "download of accept[] failed");
+    return sl.rlc ? verdict_down(ws, sl.h_accept.p + hostcall::accept_word(sl.n), st) : (int)H2V_OK;
+}
+// THE tail of the blocking host-buffer forms (prepare, pair check, aggregate, mixed), after the call was enqueued on ws->hs with
+// its lanes joined and returned rc: every region of the result block with a destination comes down straight into the caller's
+// memory (NULL - an optional output - is skipped), `verdict`: the record's word too, then ONE synchronise.  Any failure, the
+// call's own included, returns through drain_after_error; otherwise fell_back (optional) = the batch check failed here or
+// (also_failed) in a pass the call has already read the verdict of.
+struct Down { void *dst; hostcall::Region from; const char *what; };
+static int host_call_tail(h2v_workspace *ws, int rc, std::initializer_list<Down> downs, bool verdict, int *fell_back, const char *call, bool also_failed = false) {
+    uint32_t failed = 0;
+    for (const Down &d : downs)
+        if (rc == H2V_OK && d.dst && hipMemcpyAsync(d.dst, ws->res.p + d.from.off, d.from.bytes, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
+            rc = fail(H2V_E_DEVICE, std::string("download of ") + d.what + " failed");
+    if (rc == H2V_OK && verdict) rc = verdict_down(ws, &failed, ws->hs);
+    if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, std::string(call) + " kernels failed");
+    if (rc) return drain_after_error(ws, rc);
+    if (fell_back) *fell_back = (failed || also_failed) ? 1 : 0;
+    return H2V_OK;
+}
+// The workspace's stream and its result block (ws->res) for one call of `kind` over n proofs; the block grows behind host_quiet.
+static int result_ensure(h2v_workspace *ws, hostcall::Call kind, uint64_t n, hostcall::ResultBlock *R, MixedWs *m = nullptr) {
+    if (int rc = host_stream(ws)) return rc;
+    *R = hostcall::result_block(kind, n);
+    return ws->res.ensure(R->extent, "the result block", [&]() { return host_quiet(ws, m); });
 }
 static bool rlc_supported(const h2v_plan *p);
 static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o);
@@ -2372,21 +2435,15 @@ static int submit_laned(Unit u, const h2v_batch *b, h2v_workspace *ws) {
     const uint64_t n = b->n;
     sl.n = n; sl.rlc = u.batch_check();
     if (n) {
-        h2v_batch in;
-        if (int rcs = stage_batch(u.p, b, ws, sl, &in)) return rcs;
-        u.proofs = in.proofs; u.off = in.proof_off; u.inst = in.instances; u.ci = in.committed;
-        u.accept = sl.d_accept;
+        if (int rcs = stage_unit(u, b, ws, sl)) return rcs;
+        u.accept = sl.d_accept.p;
         int rc = run_laned(u, ws, ws->hs, Join::NEVER);
         if (rc == H2V_OK) {
             // the download waits for the lanes this call's chunks ran on (their events as recorded just now)
             const CallRec &r = rec_last(ws);
             for (uint32_t c = 0; c < r.chunks && c < r.mod; c++)
                 if (hipStreamWaitEvent(ws->hs_down, ws->lane_ev[(r.first + c) % r.mod], 0) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream wait failed");
-            if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, sl.d_accept, n, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-            // (RLC: how many of the call's batch checks failed comes back the same way - a synchronous copy in _wait would go
-            //  through the legacy NULL stream, which every pool stream is ordered with: it would drain all batches in flight)
-            if (rc == H2V_OK && sl.rlc && hipMemcpyAsync(sl.h_accept + ((n + 7) & ~(uint64_t)7), rec_word(ws, r), 4, hipMemcpyDeviceToHost, ws->hs_down) != hipSuccess)
-                rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
+            if (rc == H2V_OK) rc = slot_download(ws, sl, sl.d_accept.p, ws->hs_down);
         }
         if (rc) return drain_after_error(ws, rc);
     }
@@ -2398,9 +2455,9 @@ static int submit_laned(Unit u, const h2v_batch *b, h2v_workspace *ws) {
 // A downloaded batch: accept bytes to the caller; fell_back (optional) = an RLC call whose record counted a failed batch check -
 // the word that came back behind accept[] - so that the per-proof kernels produced accept[] (either kind of workspace)
 static void host_results(const h2v_workspace::HostSlot &sl, uint8_t *accept, int *fell_back) {
-    if (sl.n) memcpy(accept, sl.h_accept, sl.n);
+    if (sl.n) memcpy(accept, sl.h_accept.p, sl.n);
     uint32_t failed = 0;
-    if (sl.rlc && sl.n) memcpy(&failed, sl.h_accept + ((sl.n + 7) & ~(uint64_t)7), 4);
+    if (sl.rlc && sl.n) memcpy(&failed, sl.h_accept.p + hostcall::accept_word(sl.n), 4);
     if (fell_back) *fell_back = failed ? 1 : 0;
 }
 static int wait_laned(h2v_workspace *ws, uint8_t *accept, int *fell_back) {
@@ -2441,15 +2498,11 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
     sl.rlc = false;
     if (b->n) {
         if (u.batch_check() && (rc = rlc_seed(opts, u.seed))) return rc;
-        h2v_batch in;
-        if ((rc = stage_batch(p, b, ws, sl, &in))) return rc;
-        u.proofs = in.proofs; u.off = in.proof_off; u.inst = in.instances; u.ci = in.committed;
+        if ((rc = stage_unit(u, b, ws, sl))) return rc;
         u.accept = ws->accept;
         rc = run_call(u, ws, ws->hs);
         sl.rlc = u.batch_check();
-        if (rc == H2V_OK && hipMemcpyAsync(sl.h_accept, ws->accept, b->n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-        if (rc == H2V_OK && sl.rlc && hipMemcpyAsync(sl.h_accept + ((b->n + 7) & ~(uint64_t)7), rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess)
-            rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
+        if (rc == H2V_OK) rc = slot_download(ws, sl, ws->accept, ws->hs);
         if (rc) return drain_after_error(ws, rc);   // (the upload from the pinned block and some kernels may already be enqueued)
     }
     HIPCHK(hipEventRecord(sl.ev, ws->hs));
@@ -2512,16 +2565,6 @@ static int pairs_args(const h2v_plan *p, const uint8_t *pairs, const uint8_t *ac
     if (!accept) return fail(H2V_E_ARG, "null argument: accept");
     return H2V_OK;
 }
-// the device side of a host-buffer call: n pairs, n status words, n accept bytes
-static int hp_ensure(h2v_workspace *ws, uint64_t n) {
-    const size_t need = (size_t)n * (96 + 4 + 1) + 64;
-    if (ws->hp_cap >= need) return H2V_OK;
-    if (ws->hp_buf) { HIPCHK(hipStreamSynchronize(ws->hs)); (void)hipFree(ws->hp_buf); }
-    ws->hp_buf = nullptr; ws->hp_cap = 0;
-    if (hipMalloc((void **)&ws->hp_buf, need) != hipSuccess) return fail(H2V_E_DEVICE, "hipMalloc(host-call buffers) failed");
-    ws->hp_cap = need;
-    return H2V_OK;
-}
 extern "C" int h2v_prepare_batch_device(const h2v_plan *p, const h2v_batch *b, uint8_t *pairs, uint32_t *status, h2v_workspace *ws, void *stream) {
     if (int rc = prepare_args(p, b, pairs)) return rc;
     if (b->n == 0) return H2V_OK;
@@ -2549,22 +2592,16 @@ extern "C" int h2v_prepare_batch(const h2v_plan *p, const h2v_batch *b, uint8_t 
     TmpWs tmp;
     if (int rc = pairs_common(p, b->n, ws, nullptr, false, tmp)) return rc;
     const uint64_t n = b->n;
-    int rc = host_stream(ws);
     h2v_batch in{};
-    if (rc == H2V_OK) rc = hp_ensure(ws, n);
-    if (rc == H2V_OK) rc = stage_batch(p, b, ws, ws->n_lanes ? ws->hslot[ws->h_head % h2v_workspace::MAXH] : ws->hslot[0], &in);
-    if (rc == H2V_OK) {
-        uint8_t *d_pairs = ws->hp_buf;
-        uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
-        Unit u = unit_of_batch(UnitKind::PREPARE, p, &in, nullptr, d_status);
-        u.pairs_out = d_pairs;
-        rc = run_call(u, ws, ws->hs, Join::NOW);
-        if (rc == H2V_OK && hipMemcpyAsync(pairs, d_pairs, (size_t)n * 96, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the pairs failed");
-        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
-        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "prepare kernels failed");
-        if (rc) rc = drain_after_error(ws, rc);
-    }
-    return rc;
+    hostcall::ResultBlock R;
+    int rc = result_ensure(ws, hostcall::Call::PREPARE, n, &R);
+    if (rc == H2V_OK) rc = stage_batch(p, b, ws, own_slot(ws), &in);
+    if (rc) return rc;
+    uint8_t *const d = ws->res.p;
+    Unit u = unit_of_batch(UnitKind::PREPARE, p, &in, nullptr, (uint32_t *)(d + R.status.off));
+    u.pairs_out = d + R.pairs.off;
+    rc = run_call(u, ws, ws->hs, Join::NOW);
+    return host_call_tail(ws, rc, {{pairs, R.pairs, "the pairs"}, {status, R.status, "the status words"}}, false, nullptr, "prepare");
 }
 // The host-buffer pair checks, u.kind CHECK (h2v_check_pairs) or PAIR_RLC (h2v_check_pairs_rlc: a seed, and the batch verdict
 // comes back as fell_back): pairs up, the call with its lanes joined, accept[] / status[] down, all on the workspace's stream.
@@ -2574,23 +2611,14 @@ static int check_pairs_host(Unit u, const uint8_t *pairs, uint8_t *accept, uint3
     TmpWs tmp;
     if (int rc = pairs_common(u.p, n, ws, nullptr, false, tmp)) return rc;
     int rc = rlc ? rlc_seed(opts, u.seed) : H2V_OK;
-    if (rc == H2V_OK) rc = host_stream(ws);
-    if (rc == H2V_OK) rc = hp_ensure(ws, n);
-    if (rc == H2V_OK) {
-        uint8_t *d_pairs = ws->hp_buf, *d_accept = ws->hp_buf + (size_t)n * 100;
-        uint32_t *d_status = (uint32_t *)(ws->hp_buf + (size_t)n * 96);
-        uint32_t failed = 0;
-        u.pairs = d_pairs; u.accept = d_accept; u.status = d_status;
-        if (hipMemcpyAsync(d_pairs, pairs, (size_t)n * 96, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the pairs failed");
-        if (rc == H2V_OK) rc = run_call(u, ws, ws->hs, Join::NOW);
-        if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
-        if (rc == H2V_OK && rlc && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
-        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "pair check kernels failed");
-        if (rc) rc = drain_after_error(ws, rc);
-        else if (fell_back) *fell_back = failed ? 1 : 0;
-    }
-    return rc;
+    hostcall::ResultBlock R;
+    if (rc == H2V_OK) rc = result_ensure(ws, hostcall::Call::CHECK, n, &R);
+    if (rc) return rc;
+    uint8_t *const d = ws->res.p;
+    u.pairs = d + R.pairs.off; u.accept = d + R.accept.off; u.status = (uint32_t *)(d + R.status.off);
+    if (hipMemcpyAsync(d + R.pairs.off, pairs, R.pairs.bytes, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the pairs failed");
+    if (rc == H2V_OK) rc = run_call(u, ws, ws->hs, Join::NOW);
+    return host_call_tail(ws, rc, {{accept, R.accept, "accept[]"}, {status, R.status, "the status words"}}, rlc, fell_back, "pair check");
 }
 extern "C" int h2v_check_pairs(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws) {
     if (int rc = pairs_args(p, pairs, accept)) return rc;
@@ -3176,12 +3204,12 @@ struct MixedWs {
     struct Slot { uint8_t *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; } slot[SLOTS];
     uint64_t next = 0;
     int last = -1;                        // the slot of the most recent call: the next one starts behind its end, whatever its stream
-    uint8_t *proofs = nullptr, *inst = nullptr, *ci = nullptr;       // grouped staging, grown on demand
-    size_t cap_proofs = 0, cap_inst = 0, cap_ci = 0;
+    GrowBuf<false> proofs, inst, ci;                                 // grouped staging, grown on demand behind mixed_quiesce
     uint32_t *pool = nullptr, *status = nullptr;                     // the call's pairs (cap x 48 dwords) and status words, caller's order
     uint8_t *good = nullptr, *ones = nullptr;                        // good_i; 2 x cap bytes of 1: the `valid` of a two-slot view
-    uint8_t *h_in = nullptr, *d_in = nullptr, *d_out = nullptr;      // host form: pinned block, its device copy, accept + status + verdict
-    size_t in_cap = 0, out_cap = 0;
+    // host form: the staging slot of its own (stage_batch).  Not one of ws->hslot: a mixed call does not look at ws->pending, and
+    // a submitted batch may be in flight in any of those
+    h2v_workspace::HostSlot in;
     // H2V_MIXED_FOLD_MSM, allocated by the first fold call and grown behind mixed_quiesce: the call-level term pool - `fold` holds
     // the scalars of the R-terms (r_scal, fold_cap_terms records) and of the L-terms (l_scal, by call position), the per-block
     // sums of the VK-base scalars (vk_part, fold_cap_parts Fr records), good, the two bucket-MSM workspaces and the sums / misc /
@@ -3211,9 +3239,10 @@ static void mixed_release(h2v_workspace *w) {
         if (s.d) (void)hipFree(s.d);
         if (s.done) (void)hipEventDestroy(s.done);
     }
-    if (m->h_in) (void)hipHostFree(m->h_in);
+    slot_release(m->in);
+    m->proofs.release(); m->inst.release(); m->ci.release();
     if (m->fold) rlc_release(m->fold);
-    void *ptrs[] = {m->proofs, m->inst, m->ci, m->pool, m->status, m->good, m->ones, m->d_in, m->d_out, m->fold_rpts, m->fold_lpts};
+    void *ptrs[] = {m->pool, m->status, m->good, m->ones, m->fold_rpts, m->fold_lpts};
     for (void *q : ptrs) if (q) (void)hipFree(q);
     delete m;
     w->mixed = nullptr;
@@ -3236,22 +3265,10 @@ static int mixed_ensure(h2v_workspace *w, const h2vmixed::Partition &pt) {
         if (!ok) { mixed_release(w); return fail(H2V_E_DEVICE, "allocation of the mixed-call buffers failed"); }
     }
     MixedWs *m = w->mixed;
-    const size_t need_p = (size_t)pt.proof_cap + 64, need_i = (size_t)pt.inst_total + 64, need_c = (size_t)pt.ci_total * 48 + 64;
-    if (need_p > m->cap_proofs || need_i > m->cap_inst || need_c > m->cap_ci) {
-        if (int rc = mixed_quiesce(m)) return rc;
-        auto grow = [](uint8_t **buf, size_t *cap, size_t need) -> bool {
-            if (need <= *cap) return true;
-            if (*buf) (void)hipFree(*buf);
-            *buf = nullptr; *cap = 0;
-            const size_t c = need + need / 4;
-            if (hipMalloc((void **)buf, c) != hipSuccess) return false;
-            *cap = c;
-            return true;
-        };
-        if (!grow(&m->proofs, &m->cap_proofs, need_p) || !grow(&m->inst, &m->cap_inst, need_i) || !grow(&m->ci, &m->cap_ci, need_c))
-            return fail(H2V_E_DEVICE, "hipMalloc(mixed-call staging) failed");
-    }
-    return H2V_OK;
+    auto quiet = [m]() { return mixed_quiesce(m); };
+    if (int rc = m->proofs.ensure((size_t)pt.proof_cap + 64, "the mixed-call staging", quiet)) return rc;
+    if (int rc = m->inst.ensure((size_t)pt.inst_total + 64, "the mixed-call staging", quiet)) return rc;
+    return m->ci.ensure((size_t)pt.ci_total * 48 + 64, "the mixed-call staging", quiet);
 }
 // The term pool of the fold form for a call of this layout (the first fold call allocates, a larger one grows it once every
 // earlier mixed call has finished on the device).
@@ -3464,7 +3481,7 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     const H2vMixedTab tab = {n, (const uint64_t *)(sl.d + o_isrc), (const uint64_t *)(sl.d + o_idst), d_perm, (const uint32_t *)(sl.d + o_cap),
                              (const uint32_t *)(sl.d + o_ilen), (const uint32_t *)(sl.d + o_csrc), (const uint32_t *)(sl.d + o_cdst)};
     if (!host_off) hipLaunchKernelGGL(k_mixed_offsets, dim3(1), dim3(256), 0, st, in.proof_off, tab, d_off);
-    hipLaunchKernelGGL(k_mixed_gather, dim3((n + 3) / 4), dim3(256), 0, st, tab, in.proofs, in.proof_off, in.instances, in.committed, m->proofs, (const uint64_t *)d_off, m->inst, m->ci);
+    hipLaunchKernelGGL(k_mixed_gather, dim3((n + 3) / 4), dim3(256), 0, st, tab, in.proofs, in.proof_off, in.instances, in.committed, m->proofs.p, (const uint64_t *)d_off, m->inst.p, m->ci.p);
     if (hipGetLastError() != hipSuccess) return finish(fail(H2V_E_DEVICE, "launch of the gather kernels failed"));
     const h2v_plan *p0 = nullptr;          // any plan of the call: the tail reads nothing of it but the SRS's line tables
     uint32_t used_plans = 0;
@@ -3477,9 +3494,9 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
         const H2vDevPlan &d = plans[k]->d;
         Unit u{lay && lay->foldable[k] ? UnitKind::MIXED_SUB_TERMS : UnitKind::MIXED_SUB, plans[k], pt.count[k]};
         if (lay) { u.fold = &fc; u.fold_plan = k; }
-        u.proofs = m->proofs; u.off = d_off + pt.base[k];
-        u.inst = d.n_pi ? m->inst + pt.inst_base[k] : nullptr;
-        u.ci = d.n_ci ? m->ci + (size_t)pt.ci_base[k] * 48 : nullptr;
+        u.proofs = m->proofs.p; u.off = d_off + pt.base[k];
+        u.inst = d.n_pi ? m->inst.p + pt.inst_base[k] : nullptr;
+        u.ci = d.n_ci ? m->ci.p + (size_t)pt.ci_base[k] * 48 : nullptr;
         u.pos = d_perm + pt.base[k]; u.pool = pool;
         return u;
     };
@@ -3590,7 +3607,7 @@ static int run_mixed_call(const h2v_plan *const *plans, const h2vmixed::Partitio
     int rc = run_mixed(plans, pt, host_off, in, accept, status_out, w, st, true, seed, lay);
     if (rc) return rc;
     uint32_t failed = 0;
-    if (hipMemcpyAsync(&failed, rec_word(w, rec_last(w)), 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    if (verdict_down(w, &failed, st) || hipStreamSynchronize(st) != hipSuccess)
         return drain_after_error(w, fail(H2V_E_DEVICE, "mixed-call kernels failed (fold form)"));
     if (!failed) return H2V_OK;
     if (fold_failed) *fold_failed = true;
@@ -3632,8 +3649,6 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
     ALIVE(ws);
     HIPCHK(hipSetDevice(plans[0]->device));
     const uint64_t n = b->n;
-    for (uint64_t i = 0; i < n; i++)
-        if (b->proof_off[i + 1] < b->proof_off[i]) return fail(H2V_E_ARG, "proof offsets must be non-decreasing");
     h2v_workspace *tmp = nullptr;
     if (!ws) {    // a temporary workspace over the listed plans: lanes of at most the call's size, created as they are used
         if ((rc = h2v_workspace_create_multi(plans, n_plans, n, 0, n < 4096 ? (uint32_t)n : 4096u, &tmp))) return rc;
@@ -3644,64 +3659,30 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
     h2vmixed::FoldLayout lay;
     const bool fold = (flags & H2V_MIXED_FOLD_MSM) != 0;
     bool fold_failed = false;
+    h2v_batch in{};
+    hostcall::ResultBlock R;
     rc = mixed_ws_check(plans, n_plans, n, ws);
     if (rc == H2V_OK && fold) rc = mixed_fold_layout(plans, pt, ws, &lay);
     if (rc == H2V_OK && rlc) rc = rlc_seed(opts, seed);
-    if (rc == H2V_OK) rc = host_stream(ws);
     if (rc == H2V_OK) rc = mixed_ensure(ws, pt);
+    if (rc == H2V_OK) rc = result_ensure(ws, hostcall::Call::MIXED, n, &R, ws->mixed);
     if (rc == H2V_OK) {
-        MixedWs *m = ws->mixed;
-        auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-        const uint64_t total = b->proof_off[n] - b->proof_off[0];
-        const size_t o_inst = up16((n + 1) * 8), o_ci = o_inst + up16(pt.inst_total), o_proofs = o_ci + up16((size_t)pt.ci_total * 48), need = o_proofs + up16(total + 64);
-        const size_t o_pair = up16(up16(n) + (size_t)n * 4), out_need = o_pair + 96 + 16;
-        if (need > m->in_cap || out_need > m->out_cap) {
-            rc = mixed_quiesce(m);
-            if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "stream synchronize failed");
-            if (rc == H2V_OK && need > m->in_cap) {
-                if (m->h_in) (void)hipHostFree(m->h_in);
-                if (m->d_in) (void)hipFree(m->d_in);
-                m->h_in = m->d_in = nullptr; m->in_cap = 0;
-                const size_t cap = need + need / 4;
-                if (hipHostMalloc((void **)&m->h_in, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&m->d_in, cap) != hipSuccess) rc = fail(H2V_E_DEVICE, "staging allocation failed");
-                else m->in_cap = cap;
-            }
-            if (rc == H2V_OK && out_need > m->out_cap) {
-                if (m->d_out) (void)hipFree(m->d_out);
-                m->d_out = nullptr; m->out_cap = 0;
-                const size_t cap = out_need + out_need / 4;
-                if (hipMalloc((void **)&m->d_out, cap) != hipSuccess) rc = fail(H2V_E_DEVICE, "staging allocation failed");
-                else m->out_cap = cap;
-            }
-        }
-        if (rc == H2V_OK) {
-            uint64_t *h_off = (uint64_t *)m->h_in;
-            for (uint64_t i = 0; i <= n; i++) h_off[i] = b->proof_off[i] - b->proof_off[0];
-            if (pt.inst_total) memcpy(m->h_in + o_inst, b->instances, pt.inst_total);
-            if (pt.ci_total) memcpy(m->h_in + o_ci, b->committed, (size_t)pt.ci_total * 48);
-            memcpy(m->h_in + o_proofs, b->proofs + b->proof_off[0], total);
-            memset(m->h_in + o_proofs + total, 0, 64);
-            std::vector<uint64_t> grouped(n + 1);
-            h2vmixed::group_offsets(pt, h_off, grouped.data());
-            uint8_t *d_accept = m->d_out;
-            uint32_t *d_status = (uint32_t *)(m->d_out + up16(n));
-            uint32_t failed = 0;
-            if (hipMemcpyAsync(m->d_in, m->h_in, need, hipMemcpyHostToDevice, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "upload of the batch failed");
-            const h2v_batch in = {n, m->d_in + o_proofs, (const uint64_t *)m->d_in, m->d_in + o_inst, m->d_in + o_ci};
-            if (rc == H2V_OK && agg_pair) {
-                AggSlot as{};
-                if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = run_mixed(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, true, seed, &lay, as.parts);
-                if (rc == H2V_OK) rc = agg_export(ws, as, 1, m->d_out + o_pair, ws->hs);
-                if (rc == H2V_OK && hipMemcpyAsync(agg_pair, m->d_out + o_pair, 96, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the pair failed");
-                if (rc == H2V_OK) rc = agg_info_fill(info, seed, 0, 1, lay.n_r);
-            } else if (rc == H2V_OK) rc = run_mixed_call(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed);
-            if (rc == H2V_OK && hipMemcpyAsync(accept, d_accept, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of accept[] failed");
-            if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
-            if (rc == H2V_OK && rlc && !agg_pair && hipMemcpyAsync(&failed, rec_word(ws, rec_last(ws)), 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the batch verdict failed");
-            if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "mixed-call kernels failed");
-            if (rc) rc = drain_after_error(ws, rc);
-            else if (fell_back) *fell_back = (failed || fold_failed) ? 1 : 0;
-        }
+        const h2v_batch hb = {n, b->proofs, b->proof_off, b->instances, b->committed};
+        rc = stage_batch(&hb, pt.inst_total, (size_t)pt.ci_total * 48, ws, ws->mixed->in, &in, ws->mixed);
+    }
+    if (rc == H2V_OK) {
+        std::vector<uint64_t> grouped(n + 1);
+        h2vmixed::group_offsets(pt, (const uint64_t *)ws->mixed->in.h_block.p, grouped.data());     // (the packed offsets: rebased)
+        uint8_t *const d = ws->res.p, *d_accept = d + R.accept.off;
+        uint32_t *d_status = (uint32_t *)(d + R.status.off);
+        if (agg_pair) {
+            AggSlot as{};
+            if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = run_mixed(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, true, seed, &lay, as.parts);
+            if (rc == H2V_OK) rc = agg_export(ws, as, 1, d + R.pairs.off, ws->hs);
+            if (rc == H2V_OK) rc = agg_info_fill(info, seed, 0, 1, lay.n_r);
+        } else rc = run_mixed_call(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed);
+        rc = host_call_tail(ws, rc, {{agg_pair, R.pairs, "the pair"}, {accept, R.accept, "accept[]"}, {status, R.status, "the status words"}},
+                            rlc && !agg_pair, fell_back, "mixed-call", fold_failed);
     }
     if (tmp) h2v_workspace_free(tmp);
     return rc;
@@ -3729,22 +3710,19 @@ static int agg_ensure(h2v_workspace *ws, uint32_t n_parts, hipStream_t st, AggSl
     constexpr uint32_t S = h2v_workspace::AGG_SLOTS, P = h2v_workspace::AGG_SLOT_PARTS;
     const uint32_t per = n_parts ? n_parts : 1u, need = per <= P ? S * P : per;
     for (hipEvent_t &e : ws->ev_agg) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (ws->agg_cap < need) {
-        for (uint32_t q = 0; q < S; q++)
-            if (ws->agg_used[q]) { HIPCHK(hipEventSynchronize(ws->ev_agg[q])); ws->agg_used[q] = false; }
-        if (ws->agg_parts) (void)hipFree(ws->agg_parts);
-        ws->agg_parts = nullptr; ws->agg_cap = 0;
-        const uint32_t cap = need == S * P ? need : need + need / 4;
-        if (hipMalloc((void **)&ws->agg_parts, (size_t)cap * AGG_PART_DW * 4) != hipSuccess) return fail(H2V_E_DEVICE, "hipMalloc(aggregate parts) failed");
-        ws->agg_cap = cap;
-    }
+    if (int rc = ws->agg_parts.ensure((size_t)need * AGG_PART_DW * 4, "the aggregate parts", [&]() -> int {
+            for (uint32_t q = 0; q < S; q++)
+                if (ws->agg_used[q]) { HIPCHK(hipEventSynchronize(ws->ev_agg[q])); ws->agg_used[q] = false; }
+            return H2V_OK;
+        })) return rc;
+    uint32_t *const parts = (uint32_t *)ws->agg_parts.p;
     if (per <= P) {
         out->slot = (uint32_t)(ws->agg_calls++ % S);
-        out->parts = ws->agg_parts + (size_t)out->slot * P * AGG_PART_DW;
+        out->parts = parts + (size_t)out->slot * P * AGG_PART_DW;
         if (ws->agg_used[out->slot]) HIPCHK(hipStreamWaitEvent(st, ws->ev_agg[out->slot], 0));
     } else {
         out->slot = S;      // the whole buffer
-        out->parts = ws->agg_parts;
+        out->parts = parts;
         for (uint32_t q = 0; q < S; q++)
             if (ws->agg_used[q]) HIPCHK(hipStreamWaitEvent(st, ws->ev_agg[q], 0));
     }
@@ -3838,21 +3816,14 @@ extern "C" int h2v_aggregate_batch(const h2v_plan *p, const h2v_batch *b, uint8_
     }
     TmpWs tmp;
     if ((rc = pairs_common(p, n, ws, nullptr, false, tmp))) return rc;
-    rc = host_stream(ws);
     h2v_batch in{};
-    if (rc == H2V_OK) rc = hp_ensure(ws, n);
-    if (rc == H2V_OK) rc = stage_batch(p, b, ws, ws->n_lanes ? ws->hslot[ws->h_head % h2v_workspace::MAXH] : ws->hslot[0], &in);
-    if (rc == H2V_OK) {
-        uint8_t *d_pair = ws->hp_buf, *d_included = ws->hp_buf + 96 + (size_t)n * 4;
-        uint32_t *d_status = (uint32_t *)(ws->hp_buf + 96);
-        rc = agg_run(p, &in, d_pair, d_included, d_status, ws, ws->hs, opts, info);
-        if (rc == H2V_OK && hipMemcpyAsync(pair, d_pair, 96, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the pair failed");
-        if (rc == H2V_OK && hipMemcpyAsync(included, d_included, n, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of included[] failed");
-        if (rc == H2V_OK && status && hipMemcpyAsync(status, d_status, (size_t)n * 4, hipMemcpyDeviceToHost, ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "download of the status words failed");
-        if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "aggregate kernels failed");
-        if (rc) rc = drain_after_error(ws, rc);
-    }
-    return rc;
+    hostcall::ResultBlock R;
+    rc = result_ensure(ws, hostcall::Call::AGGREGATE, n, &R);
+    if (rc == H2V_OK) rc = stage_batch(p, b, ws, own_slot(ws), &in);
+    if (rc) return rc;
+    uint8_t *const d = ws->res.p;
+    rc = agg_run(p, &in, d + R.pairs.off, d + R.accept.off, (uint32_t *)(d + R.status.off), ws, ws->hs, opts, info);
+    return host_call_tail(ws, rc, {{pair, R.pairs, "the pair"}, {included, R.accept, "included[]"}, {status, R.status, "the status words"}}, false, nullptr, "aggregate");
 }
 extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *pair, uint8_t *included,
                                           uint32_t *status, h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
@@ -3970,488 +3941,5 @@ static int rec_rlc_timings(const CallRec &r, h2v_rlc_timings *tm) {
     return H2V_OK;
 }
 
-// ---------------------------------------------------------------------------------------------- trace
-extern "C" int h2v_trace(const h2v_plan *p, const uint8_t *proof, size_t proof_len, const uint8_t *instances,
-                         const uint8_t *committed, uint8_t *scalars_out, uint8_t *msm_scalars_out, uint8_t el_out[96],
-                         uint8_t er_out[96], uint32_t *status_out, uint8_t *accept_out) {
-    if (!p || !proof) return fail(H2V_E_ARG, "null argument");
-    ALIVE(p);
-    HIPCHK(hipSetDevice(p->device));
-    h2v_workspace *ws = nullptr;
-    int rc = ws_create_for(p->d, p->device, 1, true, &ws);
-    if (rc) return rc;
-    uint64_t off[2] = {0, proof_len};
-    h2v_batch b = {1, proof, off, instances, committed};
-    uint8_t *d_pts96 = nullptr;
-    h2v_batch in;
-    rc = stage_batch(p, &b, ws, ws->hslot[0], &in);
-    if (rc == H2V_OK) {
-        Unit u = unit_of_batch(UnitKind::VERIFY, p, &in, ws->accept, nullptr);
-        u.trace = true;
-        rc = run_pipeline(u, ws, ws->hs);
-    }
-    if (rc == H2V_OK && hipStreamSynchronize(ws->hs) != hipSuccess) rc = fail(H2V_E_DEVICE, "trace pipeline failed");
-    do {
-        if (rc) break;
-        if (hipMalloc((void **)&d_pts96, 192) != hipSuccess) { rc = fail(H2V_E_DEVICE, "hipMalloc failed"); break; }
-        // el / er as they enter the pairing: after the accumulator fold when the plan is recursive
-        if (p->d.ivc) hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 1u, 1, ws->el2, d_pts96);
-        else hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 1u, 0, ws->pts + (size_t)p->d.pi_point * 24, d_pts96);
-        hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 1u, 1, p->d.ivc ? ws->er2 : ws->er, d_pts96 + 96);
-        if (hipDeviceSynchronize() != hipSuccess) { rc = fail(H2V_E_DEVICE, "trace kernels failed"); break; }
-        uint8_t both[192];
-        if (hipMemcpy(both, d_pts96, 192, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-        if (el_out) memcpy(el_out, both, 96);
-        if (er_out) memcpy(er_out, both + 96, 96);
-        if (scalars_out && p->d.n_trace && hipMemcpy(scalars_out, ws->trace, (size_t)p->d.n_trace * 32, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-        if (msm_scalars_out && hipMemcpy(msm_scalars_out, ws->scalars, (size_t)p->d.n_terms * 32, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-        if (status_out && hipMemcpy(status_out, ws->status, 4, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-        if (accept_out && hipMemcpy(accept_out, ws->accept, 1, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-    } while (0);
-    if (d_pts96) (void)hipFree(d_pts96);
-    h2v_workspace_free(ws);
-    return rc;
-}
-
-// ---------------------------------------------------------------------------------------------- probes
-struct DevBuf {
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t n) { return hipMalloc(&p, n ? n : 8) == hipSuccess ? 0 : -1; }
-    template <class T> T *as() { return (T *)p; }
-};
-static int pick_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(H2V_E_DEVICE, "no HIP device: the HIP backend is required (no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(H2V_E_ARG, "device index out of range");
-    ALIVE_DEV(device);
-    HIPCHK(hipSetDevice(device));
-    return H2V_OK;
-}
-extern "C" int h2v_probe_field(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, uint32_t *out) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    if (op < 0 || op > 5 || !a || !b || !out || n == 0) return fail(H2V_E_ARG, "bad argument");
-    const size_t bytes = (size_t)n * (op < 4 ? 48 : 32);
-    DevBuf da, db, dout;
-    if (da.alloc(bytes) || db.alloc(bytes) || dout.alloc(bytes)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    HIPCHK(hipMemcpy(da.p, a, bytes, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db.p, b, bytes, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_field, dim3((n + 63) / 64), dim3(64), 0, nullptr, op, n, da.as<uint32_t>(), db.as<uint32_t>(), dout.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, bytes, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-extern "C" int h2v_probe_quad_madd(int device, const uint32_t *pq /* 48 dwords */, int neg, uint32_t *out /* 210 dwords */) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    DevBuf din, dout;
-    if (din.alloc(48 * 4) || dout.alloc(210 * 4)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    HIPCHK(hipMemcpy(din.p, pq, 48 * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_quad_madd, dim3(1), dim3(64), 0, nullptr, din.as<uint32_t>(), neg, dout.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, 210 * 4, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-extern "C" int h2v_probe_f28_dot2(int device, int op, uint32_t n, const uint32_t *a, const uint32_t *b, const uint32_t *c, const uint32_t *d,
-                                  uint32_t *out) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    const int what = op & 15;
-    const bool field = what <= 4, point = what >= 8 && what <= 10;
-    if ((op & ~(15 | 16 | 64)) != 0 || !(field || point) || (what == 10 && (op & 16)) || n == 0 || !a || !out) return fail(H2V_E_ARG, "bad argument");
-    if (field ? (!b || !c || !d) : (what != 8 && !b)) return fail(H2V_E_ARG, "bad argument");
-    const size_t in_b = (size_t)n * (field ? 14 : 42) * 4, out_b = (size_t)n * (field ? 14 : 44) * 4;
-    DevBuf da, db, dc, dd, dout;
-    if (da.alloc(in_b) || db.alloc(in_b) || dc.alloc(in_b) || dd.alloc(in_b) || dout.alloc(out_b)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    HIPCHK(hipMemcpy(da.p, a, in_b, hipMemcpyHostToDevice));
-    if (field || what != 8) HIPCHK(hipMemcpy(db.p, b, in_b, hipMemcpyHostToDevice));
-    if (field) {
-        HIPCHK(hipMemcpy(dc.p, c, in_b, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(dd.p, d, in_b, hipMemcpyHostToDevice));
-    }
-    hipLaunchKernelGGL(k_probe_f28_dot2, dim3((n + 63) / 64), dim3(64), 0, nullptr, op, n, da.as<uint32_t>(), db.as<uint32_t>(),
-                       dc.as<uint32_t>(), dd.as<uint32_t>(), dout.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, dout.p, out_b, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-extern "C" int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint8_t *digests) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    if (!msgs || !digests || n == 0) return fail(H2V_E_ARG, "bad argument");
-    DevBuf dm, dout;
-    if (dm.alloc((size_t)n * len) || dout.alloc((size_t)n * 32)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    if (len) HIPCHK(hipMemcpy(dm.p, msgs, (size_t)n * len, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_blake2b, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, len, dm.as<uint8_t>(), dout.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(digests, dout.p, (size_t)n * 32, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-extern "C" int h2v_probe_blake2b_ex(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint32_t digest_len, const uint8_t *key,
-                                    uint32_t key_len, uint8_t *digests) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    if ((len && !msgs) || !digests || n == 0 || (digest_len != 32 && digest_len != 64) || key_len > H2V_TR_KEY_MAX || (key_len && !key))
-        return fail(H2V_E_ARG, "bad argument");
-    if ((uint64_t)n * len > ((uint64_t)1 << 31)) return fail(H2V_E_LIMIT, "messages larger than 2 GB");
-    // with a message the hash starts behind the key block, from the state the plan loader computes on the host; an empty
-    // message makes the key block the final block, which the kernel then hashes itself
-    H2vProbeHash ph{};
-    uint8_t block[128] = {};
-    if (key_len) memcpy(block, key, key_len);
-    const bool key_is_last = key_len != 0 && len == 0;
-    ph.t0 = h2vhost::b2_keyed_midstate_host(ph.h0, digest_len, key, key_is_last ? 0u : key_len);
-    if (key_is_last) ph.h0[0] ^= (uint64_t)key_len << 8;   // (the mid-state helper was asked for the unkeyed state: put the key length back)
-    ph.prefix_len = key_is_last ? 128u : 0u;
-    ph.digest_words = digest_len / 8;
-    DevBuf dm, dk, dout;
-    if (dm.alloc((size_t)n * len + 16) || dk.alloc(128) || dout.alloc((size_t)n * digest_len)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    if (len) HIPCHK(hipMemcpy(dm.p, msgs, (size_t)n * len, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dk.p, block, 128, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_blake2b_ex, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, len, dm.as<uint8_t>(), ph, dk.as<uint8_t>(), dout.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(digests, dout.p, (size_t)n * digest_len, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-// A throw-away plan whose "proof" is `slots` consecutive compressed points and whose MSM takes them in order.
-struct MiniPlan {
-    H2vDevPlan d{};
-    DevBuf points, terms;
-    int build(uint32_t slots, uint32_t n_terms, const uint32_t *lines_sg2, const uint32_t *lines_g2) {
-        std::vector<uint32_t> pts(slots), terms_h(2 * (n_terms ? n_terms : 1));
-        for (uint32_t j = 0; j < slots; j++) pts[j] = 48 * j;
-        for (uint32_t t = 0; t < n_terms; t++) { terms_h[2 * t] = H2V_TERM_PROOF_POINT; terms_h[2 * t + 1] = t; }
-        if (points.alloc(slots * 4) || terms.alloc(terms_h.size() * 4)) return -1;
-        if (hipMemcpy(points.p, pts.data(), slots * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
-        if (hipMemcpy(terms.p, terms_h.data(), terms_h.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return -1;
-        d.proof_len = 48 * slots; d.n_points = slots; d.n_terms = n_terms; d.n_main_terms = n_terms; d.pi_point = 0;
-        d.points = points.as<uint32_t>(); d.terms = terms.as<uint32_t>();
-        d.lines_sg2 = lines_sg2; d.lines_g2 = lines_g2;
-        return 0;
-    }
-};
-static int upload_offsets(DevBuf &doff, uint32_t n, uint32_t rec) {
-    std::vector<uint64_t> off(n + 1);
-    for (uint32_t i = 0; i <= n; i++) off[i] = (uint64_t)i * rec;
-    if (doff.alloc((n + 1) * 8)) return -1;
-    return hipMemcpy(doff.p, off.data(), (n + 1) * 8, hipMemcpyHostToDevice) == hipSuccess ? 0 : -1;
-}
-extern "C" int h2v_probe_g1_decompress(int device, uint32_t n, const uint8_t *compressed, uint8_t *xy_be, uint8_t *valid) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    if (!compressed || !xy_be || !valid || n == 0) return fail(H2V_E_ARG, "bad argument");
-    MiniPlan mp;
-    DevBuf din, doff, dpts, dvalid, dout;
-    if (mp.build(1, 0, nullptr, nullptr) || upload_offsets(doff, n, 48) || din.alloc((size_t)n * 48) || dpts.alloc((size_t)n * 96) ||
-        dvalid.alloc(n) || dout.alloc((size_t)n * 96)) return fail(H2V_E_DEVICE, "probe setup failed");
-    HIPCHK(hipMemcpy(din.p, compressed, (size_t)n * 48, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_g1_decompress, dim3((n + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), (uint32_t *)nullptr, 0u, (uint8_t *)nullptr);
-    hipLaunchKernelGGL(k_export_points, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, 0, dpts.as<uint32_t>(), dout.as<uint8_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(xy_be, dout.p, (size_t)n * 96, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(valid, dvalid.p, n, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-extern "C" int h2v_probe_g1_msm(int device, uint32_t n, uint32_t T, const uint8_t *scalars, const uint8_t *bases_compressed, uint8_t *out_xy_be) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    if (!scalars || !bases_compressed || !out_xy_be || n == 0 || T == 0) return fail(H2V_E_ARG, "bad argument");
-    if (T > H2V_MAX_MSM_TERMS)
-        return fail(H2V_E_LIMIT, "the MSM has " + std::to_string(T) + " terms; this backend sums at most " + std::to_string(H2V_MAX_MSM_TERMS) +
-                                     " terms per MSM (H2V_MAX_MSM_TERMS)");
-    ProbeOpts probe_opts;
-    MiniPlan mp;
-    DevBuf din, doff, dsc, dpts, dvalid, der, dout, dtab, dparts;
-    const uint32_t segs = msm_max_segments(T);
-    if (mp.build(T, T, nullptr, nullptr) || upload_offsets(doff, n, 48 * T) || din.alloc((size_t)n * T * 48) || dsc.alloc((size_t)n * T * 32) ||
-        dpts.alloc((size_t)n * T * 96) || dvalid.alloc((size_t)n * T) || der.alloc((size_t)n * 144) || dout.alloc((size_t)n * 96) ||
-        (segs && dparts.alloc((size_t)n * segs * 144)))
-        return fail(H2V_E_DEVICE, "probe setup failed");
-    HIPCHK(hipMemcpy(din.p, bases_compressed, (size_t)n * T * 48, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dsc.p, scalars, (size_t)n * T * 32, hipMemcpyHostToDevice));
-    if (dtab.alloc((size_t)n * T * 448 * 4)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    hipLaunchKernelGGL(k_g1_decompress, dim3((n * T + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), dtab.as<uint32_t>(), 0u, (uint8_t *)nullptr);
-    if (!launch_msm(mp.d, n, dsc.as<uint32_t>(), dpts.as<uint32_t>(), dtab.as<uint32_t>(), der.as<uint32_t>(), nullptr, nullptr, nullptr, 1, SegBuf{dparts.as<uint32_t>(), segs}))
-        return fail(H2V_E_LIMIT, "no MSM launch shape fits this sum");
-    hipLaunchKernelGGL(k_export_points, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, 1, der.as<uint32_t>(), dout.as<uint8_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out_xy_be, dout.p, (size_t)n * 96, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-
-// the fixed-base launch of a split MSM over the plan's own VK-base terms, scalars given by the caller
-extern "C" int h2v_probe_g1_msm_fixed(const h2v_plan *p, uint32_t n, uint32_t k, const uint8_t *scalars, uint8_t *out_xy_be, uint32_t *n_fix_out) {
-    if (!p) return fail(H2V_E_ARG, "bad argument");
-    ALIVE(p);
-    if (n_fix_out) *n_fix_out = p->n_fix;
-    if (!p->fix_tab || !p->n_fix) return fail(H2V_E_ARG, "this plan has no fixed-base tables");
-    if (!scalars || !out_xy_be || n == 0 || k == 0 || k > 4) return fail(H2V_E_ARG, "bad argument");
-    HIPCHK(hipSetDevice(p->device));
-    const H2vDevPlan &d = p->d;
-    DevBuf dsc, der, dout;
-    if (dsc.alloc((size_t)n * d.n_fix * 32) || der.alloc((size_t)n * 144) || dout.alloc((size_t)n * 96)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    HIPCHK(hipMemcpy(dsc.p, scalars, (size_t)n * d.n_fix * 32, hipMemcpyHostToDevice));
-    const H2vMsmArgs mf = msm_fixed_args(d, d.n_fix, 0, der.as<uint32_t>(), nullptr, k);
-    const uint32_t bs = mf.n_fixl <= 64 ? 64u : mf.n_fixl <= 256 ? 256u : 512u;
-    if (mf.n_fixl > bs) return fail(H2V_E_LIMIT, "too many VK bases for one block");
-    launch_msm_fixed(d, mf, n, bs, dsc.as<uint32_t>(), nullptr, nullptr);
-    hipLaunchKernelGGL(k_export_points, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, 1, der.as<uint32_t>(), dout.as<uint8_t>());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out_xy_be, dout.p, (size_t)n * 96, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-
-// The bucket MSM on its own, through pip_alloc / pip_launch as the RLC mode calls them: 1 or 2 problems side by side in every launch,
-// each with its own term count, halves, scalars, point pool (compressed; decompressed here; split into pool0 / pool1 at n_pool0,
-// which live in separate allocations) and optional index map; the grid of k_pip_accumulate capped at acc_grid_cap blocks (0: not
-// capped); per problem an optional dump of what the launcher chose and k_pip_scan wrote (include/h2v.h has the layout).
-extern "C" int h2v_probe_g1_msm_pippenger_ex(int device, uint32_t n_problems, const h2v_pip_probe *pr, uint32_t acc_grid_cap) {
-    int rc = pick_device(device);
-    if (rc) return rc;
-    if (!pr || n_problems < 1 || n_problems > 2) return fail(H2V_E_ARG, "bad argument");
-    static_assert(H2V_PIP_DUMP_DWORDS == 5 + PIP_CLS_DW + 2 * PIP_MAX_W * (1u << (PIP_MAX_C - 1)) + 1, "h2v.h: the dump holds the largest shape");
-    for (uint32_t q = 0; q < n_problems; q++) {
-        const h2v_pip_probe &p = pr[q];
-        if (!p.scalars || !p.points_compressed || !p.out_xy_be || p.n == 0 || p.n > (1u << 24) || p.n_points == 0 || p.n_points > (1u << 24) ||
-            (p.halves != 1 && p.halves != 2) || p.n_pool0 > p.n_points || (!p.pidx && p.n != p.n_points))
-            return fail(H2V_E_ARG, "bad argument");
-        if (p.pidx)
-            for (uint32_t i = 0; i < p.n; i++)
-                if (p.pidx[i] >= p.n_points) return fail(H2V_E_ARG, "point index " + std::to_string(p.pidx[i]) + " is outside the pool");
-        if (p.halves == 1)
-            for (uint32_t i = 0; i < p.n; i++)
-                for (int k = 16; k < 32; k++)
-                    if (p.scalars[(size_t)i * 32 + k]) return fail(H2V_E_ARG, "halves = 1 takes scalars below 2^128");
-    }
-    ProbeOpts probe_opts;
-    MiniPlan mp;
-    struct Prob {
-        DevBuf din, doff, dsc, didx, dpts, dpool1, dvalid, dres;
-        PipWs pw;
-        ~Prob() { pip_free(pw); }
-    } P[2];
-    DevBuf dout;
-    if (mp.build(1, 0, nullptr, nullptr) || dout.alloc(2 * 96)) return fail(H2V_E_DEVICE, "probe setup failed");
-    PipArgs a[2] = {};
-    const PipWs *pws[2] = {&P[0].pw, &P[1].pw};
-    for (uint32_t q = 0; q < n_problems; q++) {
-        const h2v_pip_probe &p = pr[q];
-        Prob &b = P[q];
-        const uint32_t n1 = p.n_points - p.n_pool0;
-        if (upload_offsets(b.doff, p.n_points, 48) || b.din.alloc((size_t)p.n_points * 48) || b.dsc.alloc((size_t)p.n * 32) ||
-            b.dpts.alloc((size_t)p.n_points * 96) || b.dvalid.alloc(p.n_points) || b.dres.alloc(144) || (p.pidx && b.didx.alloc((size_t)p.n * 4)) ||
-            (n1 && b.dpool1.alloc((size_t)n1 * 96))) return fail(H2V_E_DEVICE, "probe setup failed");
-        HIPCHK(hipMemcpy(b.din.p, p.points_compressed, (size_t)p.n_points * 48, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(b.dsc.p, p.scalars, (size_t)p.n * 32, hipMemcpyHostToDevice));
-        if (p.pidx) HIPCHK(hipMemcpy(b.didx.p, p.pidx, (size_t)p.n * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_g1_decompress, dim3((p.n_points + 63) / 64), dim3(128), 0, nullptr, mp.d, p.n_points, b.din.as<uint8_t>(), b.doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, b.dpts.as<uint32_t>(), b.dvalid.as<uint8_t>(), (uint32_t *)nullptr, 0u, (uint8_t *)nullptr);
-        if (n1) {   // the records from n_pool0 on move to an allocation of their own and read as infinity where they were
-            HIPCHK(hipMemcpy(b.dpool1.p, b.dpts.as<uint8_t>() + (size_t)p.n_pool0 * 96, (size_t)n1 * 96, hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemset(b.dpts.as<uint8_t>() + (size_t)p.n_pool0 * 96, 0, (size_t)n1 * 96));
-        }
-        if ((rc = pip_alloc(b.pw, p.n, p.halves))) return rc;
-        // a bucket sum, window value or result the kernels fail to write must read as infinity, not as what an earlier run of the
-        // same input left at the address the allocator hands out again
-        HIPCHK(hipMemset(b.pw.partial, 0xff, (size_t)PIP_MAX_W * (1u << (PIP_MAX_C - 1)) * PIP_PART_DW * 4));
-        HIPCHK(hipMemset(b.pw.wsum, 0xff, (size_t)PIP_MAX_W * PIP_PART_DW * 4));
-        HIPCHK(hipMemset(b.dres.p, 0, 144));
-        a[q].n = p.n; a[q].halves = p.halves; a[q].scal = b.dsc.as<uint32_t>(); a[q].pidx = p.pidx ? b.didx.as<uint32_t>() : nullptr;
-        a[q].pool0 = b.dpts.as<uint32_t>(); a[q].n_pool0 = p.n_pool0; a[q].pool1 = n1 ? b.dpool1.as<uint32_t>() : nullptr; a[q].out = b.dres.as<uint32_t>();
-    }
-    uint32_t acc_blocks = 0;
-    if ((rc = pip_launch(pws, a, n_problems, nullptr, nullptr, acc_grid_cap, &acc_blocks))) return rc;
-    for (uint32_t q = 0; q < n_problems; q++)
-        hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 1u, 1, P[q].dres.as<uint32_t>(), dout.as<uint8_t>() + 96 * q);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(H2V_E_DEVICE, "bucket MSM kernels failed");
-    for (uint32_t q = 0; q < n_problems; q++) {
-        HIPCHK(hipMemcpy(pr[q].out_xy_be, dout.as<uint8_t>() + 96 * q, 96, hipMemcpyDeviceToHost));
-        if (uint32_t *d = pr[q].dump) {
-            const uint32_t nb = a[q].W * a[q].NB;
-            d[0] = a[q].c; d[1] = a[q].W; d[2] = a[q].NB; d[3] = a[q].chain; d[4] = acc_blocks;
-            HIPCHK(hipMemcpy(d + 5, P[q].pw.cls, PIP_CLS_DW * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(d + 5 + PIP_CLS_DW, P[q].pw.off, (size_t)(nb + 1) * 4, hipMemcpyDeviceToHost));
-            HIPCHK(hipMemcpy(d + 5 + PIP_CLS_DW + nb + 1, P[q].pw.order, (size_t)nb * 4, hipMemcpyDeviceToHost));
-        }
-    }
-    return H2V_OK;
-}
-// sum_n s_n * P_n through the bucket MSM: n scalars (32 B LE, < r) and n compressed bases; out 96 B affine big-endian
-extern "C" int h2v_probe_g1_msm_pippenger(int device, uint32_t n, const uint8_t *scalars, const uint8_t *bases_compressed, uint8_t *out_xy_be) {
-    h2v_pip_probe p = {};
-    p.n = n; p.halves = 2; p.scalars = scalars; p.n_points = n; p.n_pool0 = n; p.points_compressed = bases_compressed; p.out_xy_be = out_xy_be;
-    return h2v_probe_g1_msm_pippenger_ex(device, 1, &p, 0);
-}
-// The two sums of the most recent H2V_MIXED_FOLD_MSM call on ws - L then R, affine, 96 bytes big-endian x || y each, all-zero for
-// infinity - whether its check passed or the call fell back (the second pass does not touch them).  The call has synchronised its
-// stream already; the conversion runs on the NULL stream and the device is synchronised behind it.
-extern "C" int h2v_probe_mixed_fold_sums(h2v_workspace *ws, uint8_t out_xy_be[192]) {
-    if (!ws || !out_xy_be) return fail(H2V_E_ARG, "null argument");
-    ALIVE(ws);
-    const MixedWs *m = ws->mixed;
-    if (!m || !m->fold || !m->fold_ran) return fail(H2V_E_ARG, "no call with H2V_MIXED_FOLD_MSM has run on this workspace");
-    HIPCHK(hipSetDevice(ws->device));
-    DevBuf dout;
-    if (dout.alloc(192)) return fail(H2V_E_DEVICE, "hipMalloc failed");
-    HIPCHK(hipDeviceSynchronize());
-    hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, 2u, 1, (const uint32_t *)m->fold->sums, dout.as<uint8_t>());   // [0] = R, [1] = L
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out_xy_be, (const uint8_t *)dout.p + 96, 96, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out_xy_be + 96, dout.p, 96, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-// The transcript + combiner launch alone, on a batch: status words, term scalars and (want_trace) the plan's trace registers of
-// every proof.  Nothing behind launch_vm runs, so a plan whose OUT_SCALARs mean nothing to the MSM is safe here.  The outputs
-// are preset (scalars and trace zero, status all ones), so what the kernel left unwritten is visible as such.
-extern "C" int h2v_probe_vm(const h2v_plan *p, const h2v_batch *b, int want_trace, uint32_t *status_out, uint8_t *msm_scalars_out, uint8_t *trace_out) {
-    if (!p || !b || !status_out || !msm_scalars_out) return fail(H2V_E_ARG, "null argument");
-    if (b->n == 0 || b->n > (1ull << 24)) return fail(H2V_E_ARG, "batch size out of range");
-    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null batch buffers");
-    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
-    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
-    if (want_trace ? (!trace_out || !p->d.n_trace) : trace_out != nullptr)
-        return fail(H2V_E_ARG, "trace_out goes with want_trace and a plan that has a trace table");
-    ALIVE(p);
-    HIPCHK(hipSetDevice(p->device));
-    ProbeOpts probe_opts;
-    const uint32_t n = (uint32_t)b->n;
-    const H2vDevPlan &d = p->d;
-    h2v_workspace *ws = nullptr;
-    int rc = ws_create_for(d, p->device, n, want_trace != 0, &ws);
-    if (rc) return rc;
-    h2v_batch in;
-    rc = stage_batch(p, b, ws, ws->hslot[0], &in);
-    do {
-        if (rc) break;
-        const size_t sc_bytes = (size_t)n * d.n_terms * 32, tr_bytes = (size_t)n * d.n_trace * 32;
-        if (hipMemsetAsync(ws->scalars, 0, sc_bytes, ws->hs) != hipSuccess || hipMemsetAsync(ws->status, 0xff, (size_t)n * 4, ws->hs) != hipSuccess ||
-            (want_trace && hipMemsetAsync(ws->trace, 0, tr_bytes, ws->hs) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "hipMemsetAsync failed"); break; }
-        if ((rc = launch_vm(d, n, ws->stride, in.proofs, in.proof_off, in.instances, in.committed, ws->regs, ws->scalars, ws->status, want_trace ? ws->trace : nullptr, ws->hs))) break;
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ws->hs) != hipSuccess) { rc = fail(H2V_E_DEVICE, "combiner kernel failed"); break; }
-        if (hipMemcpy(status_out, ws->status, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(msm_scalars_out, ws->scalars, sc_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-            (want_trace && hipMemcpy(trace_out, ws->trace, tr_bytes, hipMemcpyDeviceToHost) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-    } while (0);
-    h2v_workspace_free(ws);
-    return rc;
-}
-// The decompression launch alone, on a batch, exactly as the pipelines make it (launch_decompress on a staged batch, with or
-// without the window tables): every per-point output of k_g1_decompress_queue and the grid it ran on.  The outputs are preset
-// (points, verdicts and tables to 0xA5 bytes), so what the kernel left unwritten is visible as such.
-extern "C" int h2v_probe_decompress(const h2v_plan *p, const h2v_batch *b, int with_tables, uint8_t *xy_be, uint8_t *valid_out, uint8_t *valid_sub_out,
-                                    uint32_t *tables_out, uint32_t *blocks_out) {
-    if (!p || !b || !xy_be || !valid_out || !valid_sub_out || !blocks_out) return fail(H2V_E_ARG, "null argument");
-    if (b->n == 0 || b->n > (1ull << 24)) return fail(H2V_E_ARG, "batch size out of range");
-    if (!b->proofs || !b->proof_off) return fail(H2V_E_ARG, "null batch buffers");
-    if (p->d.n_pi && !b->instances) return fail(H2V_E_ARG, "plan has public inputs but instances == NULL");
-    if (p->d.n_ci && !b->committed) return fail(H2V_E_ARG, "plan has a committed instance but committed == NULL");
-    if (tables_out && !with_tables) return fail(H2V_E_ARG, "tables_out goes with with_tables");
-    ALIVE(p);
-    HIPCHK(hipSetDevice(p->device));
-    const uint32_t n = (uint32_t)b->n;
-    const H2vDevPlan &d = p->d;
-    const size_t n_pts = (size_t)n * H2V_SLOTS(d);
-    h2v_workspace *ws = nullptr;
-    int rc = ws_create_for(d, p->device, n, false, &ws);
-    if (rc) return rc;
-    DevBuf dout;
-    h2v_batch in;
-    rc = stage_batch(p, b, ws, ws->hslot[0], &in);
-    do {
-        if (rc) break;
-        if (dout.alloc(n_pts * 96)) { rc = fail(H2V_E_DEVICE, "hipMalloc failed"); break; }
-        if (hipMemsetAsync(ws->pts, 0xa5, n_pts * 96, ws->hs) != hipSuccess || hipMemsetAsync(ws->valid, 0xa5, n_pts, ws->hs) != hipSuccess ||
-            hipMemsetAsync(ws->valid_sub, 0xa5, n_pts, ws->hs) != hipSuccess || hipMemsetAsync(ws->pt_tab, 0xa5, n_pts * 448 * 4, ws->hs) != hipSuccess) {
-            rc = fail(H2V_E_DEVICE, "hipMemsetAsync failed"); break;
-        }
-        if ((rc = launch_decompress(d, n, in.proofs, in.proof_off, in.committed, in.instances, ws, with_tables ? ws->pt_tab : nullptr, ws->hs, blocks_out))) break;
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ws->hs) != hipSuccess) { rc = fail(H2V_E_DEVICE, "decompression kernel failed"); break; }
-        if (hipMemcpy(valid_out, ws->valid, n_pts, hipMemcpyDeviceToHost) != hipSuccess ||
-            hipMemcpy(valid_sub_out, ws->valid_sub, n_pts, hipMemcpyDeviceToHost) != hipSuccess ||
-            (tables_out && hipMemcpy(tables_out, ws->pt_tab, n_pts * 448 * 4, hipMemcpyDeviceToHost) != hipSuccess)) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-        // (a point slot the kernel left at the preset is no field element: k_export_points would reduce it; such a slot shows in
-        //  valid[], which the preset makes neither 0 nor 1)
-        hipLaunchKernelGGL(k_export_points, dim3((uint32_t)((n_pts + 63) / 64)), dim3(64), 0, ws->hs, (uint32_t)n_pts, 0, ws->pts, dout.as<uint8_t>());
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ws->hs) != hipSuccess) { rc = fail(H2V_E_DEVICE, "export kernel failed"); break; }
-        if (hipMemcpy(xy_be, dout.p, n_pts * 96, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(H2V_E_DEVICE, "download failed"); break; }
-    } while (0);
-    h2v_workspace_free(ws);
-    return rc;
-}
-// The pairing launch alone on n pairs, with every entry state a pipeline can hand it.  impl: -1 default, 0 one-lane-per-proof kernel,
-// 1 cooperative kernel (the launcher's choice of engine, or H2V_OPT_PAIRING_ENGINE of h2v_probe_set_option), 2 / 3 / 5 / 6 its narrow /
-// wide / six-lane / twelve-lane engine whatever n.  Optional inputs (NULL: as the pipelines' first launch has them): status_in (n words
-// the proofs arrive with), valid_sub_in (n x 2 bytes, the subgroup verdicts of slots p1, p2; NULL: the kernels get no such array),
-// el_jac_in (n x 36 dwords X, Y, Z, Montgomery limbs: the first argument, instead of slot p1).  Outputs, each optional: status_out
-// (n + H2V_PROBE_PAIRING_GUARD words), accept (n + GUARD bytes), dbg ((n + GUARD) x 24 x 48 bytes: f after the Miller loop and after
-// the final exponentiation, canonical LE limbs; NULL: the kernels get no dump buffer), lanes_out (launch_pairing_impl's answer: the
-// engine that ran).  The device outputs are allocated for n + GUARD proofs, preset to 0xA5 bytes and copied back whole: what a
-// kernel left unwritten shows as such, and so does what a dead group of the last wave wrote behind proof n - 1.
-extern "C" int h2v_probe_pairing_states(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, int impl, const uint32_t *status_in,
-                                        const uint8_t *valid_sub_in, const uint32_t *el_jac_in, uint32_t *status_out, uint8_t *accept, uint8_t *dbg,
-                                        uint32_t *lanes_out) {
-    if (!p || !p1c || !p2c || n == 0 || n > (1u << 24)) return fail(H2V_E_ARG, "bad argument");
-    ALIVE(p);
-    ProbeOpts probe_opts;
-    HIPCHK(hipSetDevice(p->device));
-    MiniPlan mp;
-    DevBuf din, doff, dsc, dpts, dvalid, dsub, del, der, dst, dacc, dtab, ddbg;
-    mp.d.lines28_sg2 = p->d.lines28_sg2;
-    mp.d.lines28_g2 = p->d.lines28_g2;
-    mp.d.six_norm28 = p->d.six_norm28;
-    mp.d.six_k = p->d.six_k;
-    const size_t cap = (size_t)n + H2V_PROBE_PAIRING_GUARD;
-    if (mp.build(2, 1, p->d.lines_sg2, p->d.lines_g2) || upload_offsets(doff, n, 96) || din.alloc((size_t)n * 96) || dsc.alloc((size_t)n * 32) ||
-        dpts.alloc((size_t)n * 192) || dvalid.alloc((size_t)n * 2) || der.alloc((size_t)n * 144) || dst.alloc(cap * 4) || dacc.alloc(cap) ||
-        dtab.alloc((size_t)n * 2 * 448 * 4) || ddbg.alloc(dbg ? cap * 24 * 48 : 8) || (valid_sub_in && dsub.alloc((size_t)n * 2)) ||
-        (el_jac_in && del.alloc((size_t)n * 144)))
-        return fail(H2V_E_DEVICE, "probe setup failed");
-    // MSM "sum" is 1 * p2 (term 0 must read slot 1): patch the single term
-    uint32_t term[2] = {H2V_TERM_PROOF_POINT, 1};
-    HIPCHK(hipMemcpy(mp.terms.p, term, 8, hipMemcpyHostToDevice));
-    std::vector<uint8_t> in((size_t)n * 96), one((size_t)n * 32, 0);
-    for (uint32_t i = 0; i < n; i++) { memcpy(&in[(size_t)i * 96], p1c + (size_t)i * 48, 48); memcpy(&in[(size_t)i * 96 + 48], p2c + (size_t)i * 48, 48); one[(size_t)i * 32] = 1; }
-    HIPCHK(hipMemcpy(din.p, in.data(), in.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(dsc.p, one.data(), one.size(), hipMemcpyHostToDevice));
-    HIPCHK(hipMemset(dst.p, 0xa5, cap * 4));
-    HIPCHK(hipMemset(dacc.p, 0xa5, cap));
-    if (dbg) HIPCHK(hipMemset(ddbg.p, 0xa5, cap * 24 * 48));
-    if (status_in) HIPCHK(hipMemcpy(dst.p, status_in, (size_t)n * 4, hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(dst.p, 0, (size_t)n * 4));
-    if (valid_sub_in) HIPCHK(hipMemcpy(dsub.p, valid_sub_in, (size_t)n * 2, hipMemcpyHostToDevice));
-    if (el_jac_in) HIPCHK(hipMemcpy(del.p, el_jac_in, (size_t)n * 144, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_g1_decompress, dim3((n * 2 + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), dtab.as<uint32_t>(), 0u, (uint8_t *)nullptr);
-    launch_msm(mp.d, n, dsc.as<uint32_t>(), dpts.as<uint32_t>(), dtab.as<uint32_t>(), der.as<uint32_t>(), nullptr, nullptr, nullptr);
-    const uint32_t lanes = launch_pairing_impl(impl, mp.d, n, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), valid_sub_in ? dsub.as<uint8_t>() : nullptr, der.as<uint32_t>(),
-                                               el_jac_in ? del.as<uint32_t>() : nullptr, dst.as<uint32_t>(), dacc.as<uint8_t>(), dbg ? ddbg.as<uint32_t>() : nullptr, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    if (lanes_out) *lanes_out = lanes;
-    if (status_out) HIPCHK(hipMemcpy(status_out, dst.p, cap * 4, hipMemcpyDeviceToHost));
-    if (accept) HIPCHK(hipMemcpy(accept, dacc.p, cap, hipMemcpyDeviceToHost));
-    if (dbg) HIPCHK(hipMemcpy(dbg, ddbg.p, cap * 24 * 48, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-// e(p1, s_g2) == e(p2, G2) with status 0 on entry: the first n verdicts (and, dbg given, the first n x 24 records) of the call above
-extern "C" int h2v_probe_pairing_ex(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out, int impl, uint8_t *dbg) {
-    if (!p || !p1c || !p2c || !out || n == 0 || n > (1u << 24)) return fail(H2V_E_ARG, "bad argument");
-    const size_t cap = (size_t)n + H2V_PROBE_PAIRING_GUARD;
-    std::vector<uint8_t> acc(cap), rec(dbg ? cap * 24 * 48 : 0);
-    const int rc = h2v_probe_pairing_states(p, n, p1c, p2c, impl, nullptr, nullptr, nullptr, nullptr, acc.data(), dbg ? rec.data() : nullptr, nullptr);
-    if (rc) return rc;
-    memcpy(out, acc.data(), n);
-    if (dbg) memcpy(dbg, rec.data(), (size_t)n * 24 * 48);
-    return H2V_OK;
-}
-extern "C" int h2v_probe_pairing(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, uint8_t *out) {
-    return h2v_probe_pairing_ex(p, n, p1c, p2c, out, -1, nullptr);
-}
+// the single-proof trace and the probes of the device code (tests and tools call them)
+#include "h2v_probes.hpp"
