@@ -20,6 +20,7 @@
 #include "h2v_mixed_fold_dev.hpp"
 #include "h2v_aggregate_dev.hpp"
 #include "h2v_msm_shape.hpp"
+#include "h2v_pairing_engine.hpp"
 #include "h2v_hostcall_layout.hpp"
 #include "h2v_plancc.hpp"
 
@@ -905,7 +906,7 @@ static int option_check(uint32_t option, int32_t value) {
     switch (option) {
     case H2V_OPT_MSM_TERMS_PER_LANE: if (value < 0 || value > 4) return bad("terms per lane: 0 (auto) .. 4"); break;
     case H2V_OPT_PAIRING_ENGINE:
-        if (value != 0 && value != 1 && value != 6 && value != 12 && value != 16 && value != 32 && value != 64)
+        if (!pairing_option_legal(value))
             return bad("pairing engine: 0 (auto), 6, 12, 16, 32, 64 lanes per proof, or 1 (the one-lane cross-check kernel)");
         break;
     case H2V_OPT_STREAMS: if (value < -1 || value > 2) return bad("streams: -1 (auto), 0 (two of the library's), 1 (the caller's), 2 (the caller's + one for the decompression)"); break;
@@ -1365,70 +1366,41 @@ static void launch_ivc_fold(const H2vDevPlan &d, uint32_t n, const uint32_t *pts
     fold.grp_end[0] = 2; fold.out[1] = b.er2;
     launch_msm_range(d, fold, n, b.fold_scal, b.fold_pts, tabws, st);
 }
-// Pairing kernel selection: the cooperative 16-lanes-per-proof kernel is the product path; the one-lane-per-proof
-// kernel stays as a cross-check (H2V_OPT_PAIRING_ENGINE = 1, or impl = 0 in the probe).
-static uint32_t launch_pairing_impl(int impl, const H2vDevPlan &d, uint32_t n, const uint32_t *pts, const uint8_t *valid, const uint8_t *valid_sub, const uint32_t *er,
-                                const uint32_t *el_jac, uint32_t *status, uint8_t *accept, uint32_t *dbg, hipStream_t st, const uint32_t *skip = nullptr,
-                                bool prefer_narrow = false, double wide_up_to = -1.0, bool prefer_six = false, bool prefer_twelve = false) {
-    if (wide_up_to < 0) wide_up_to = msm_n_simd();
-    // The WIDE engine (one proof per wave, four lanes per coefficient: 3 / 2 / 1 terms per lane and call instead of 6 / 4 / 2)
-    // when even one wave per proof leaves SIMDs free: n <= #SIMDs.  Above that the two-proofs-per-wave kernel does less
-    // total work.  H2V_OPT_PAIRING_ENGINE forces an engine; the conditional (RLC fall-back) launch is never wide.
-    // impl 2 / 3 / 5 / 6 (probe): the narrow / the wide / the six-lane / the twelve-lane kernel whatever n
-    const int forced = g_opts.v[H2V_OPT_PAIRING_ENGINE];
-    if (impl == 1 && forced) impl = forced == 1 ? 0 : forced == 16 ? 2 : forced == 64 ? 3 : forced == 6 ? 5 : forced == 12 ? 6 : 4;   // 4: the two-proofs-per-wave engine
-    // (the six-lane engine needs its plan-load line table: a plan without one - some line coefficient c is zero - never takes it)
-    if ((impl == 5 || (impl == 1 && !skip && prefer_six)) && d.six_norm28) {
-        hipLaunchKernelGGL(k_pairing_six, dim3((n + SIX_GROUPS - 1) / SIX_GROUPS), dim3(64), SIX_LDS_BYTES, st, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg);
-        return 6u;
-    }
-    const bool wide = !skip && impl != 2 && impl != 4 && impl != 6 && (impl == 3 || (double)n <= wide_up_to);
-    const bool narrow = !skip && !wide && impl != 4 && (impl == 2 || prefer_narrow);
-    // the narrow engine packed five proofs to a wave (impl 6, option 12): wherever the narrow one would run
-    if (impl == 6 || (narrow && impl != 2 && prefer_twelve)) {
-        hipLaunchKernelGGL(k_pairing_coop_twelve, dim3((n + COOP_GROUPS_TWELVE - 1) / COOP_GROUPS_TWELVE), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_TWELVE), st, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg);
-        return 12u;
-    }
-    if (impl == 0) { hipLaunchKernelGGL(k_pairing_check, dim3((n + 63) / 64), dim3(64), 0, st, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg); return 1; }
-    else if (wide) hipLaunchKernelGGL(k_pairing_coop_wide, dim3(n), dim3(64), COOP_LDS_BYTES(1), st, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg);
-    else if (narrow) hipLaunchKernelGGL(k_pairing_coop_narrow, dim3((n + 3) / 4), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_NARROW), st, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg);
-    else hipLaunchKernelGGL(k_pairing_coop, dim3((n + 1) / 2), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg, skip);
-    return wide ? 64u : narrow ? 16u : 32u;
-}
-// The NARROW engine (four proofs per wave, one lane per coefficient: 21 % fewer instructions per pairing, twice the chain).
-// Measured (simple_mul, pairing kernel alone / step with five batches in flight):
-//   n = 1536: normal 1.94 ms / 2.32 ms, narrow 2.60 / 2.40      n = 2048: 1.96 / 2.71, 2.61 / 2.64
-//   n = 3072: 2.99 / 3.71, 2.63 / 3.46     n = 4096: 3.00 / 4.81, 2.66 / 4.50     n = 8192: 5.65 / 9.59, 6.59 / 8.91
-// (a narrow block needs 22.5 KB of LDS: seven per CU, so its second wave per SIMD does not fit everywhere).  Rule: a caller
-// that keeps the chip full (hint >= 4) takes it from 2 * #SIMDs proofs up; one step at a time takes it exactly where the
-// normal kernel needs a second wave per SIMD and the narrow one does not.  H2V_OPT_PAIRING_ENGINE forces the choice.
+// The per-proof pairing: ONE launch site for the six engines.  Which engine runs, and on what grid, is h2v_pairing_engine.hpp's
+// answer (the engine table, the rule and the measurements behind its thresholds); here are the table's kernels and their LDS bytes.
+// skip != NULL: the conditional form, the fall-back of a batch check - the normal engine on its walking grid, every block of which
+// returns at once when *skip != 0.  probe_impl: h2v_probe_pairing_states' impl (its hint: PAIRING_HINT_PROBE); the pipelines'
+// launches are the rule under the workspace's option, which is what the probes call impl 1.
+// Returns the lanes per proof of the engine that ran (h2v_timings.pairing_lanes_per_proof, the probes' lanes_out).
+typedef void (*PairingKernel)(H2vDevPlan, uint32_t, const uint32_t *, const uint8_t *, const uint8_t *, const uint32_t *, const uint32_t *, uint32_t *, uint8_t *, uint32_t *);
+typedef void (*PairingKernelSkip)(H2vDevPlan, uint32_t, const uint32_t *, const uint8_t *, const uint8_t *, const uint32_t *, const uint32_t *, uint32_t *, uint8_t *, uint32_t *, const uint32_t *);
+// k_pairing_coop alone takes the skip pointer, as its last argument: the launch below hands every kernel the same argument list, of
+// which a kernel reads as many as it has parameters.  That erases the kernels' types, so a kernel gets into the table only through
+// pairing_kernel(): an implicit conversion to one of the two signatures, which does not compile for a kernel with other parameters.
+static const void *pairing_kernel(PairingKernel k) { return (const void *)k; }
+static const void *pairing_kernel(PairingKernelSkip k) { return (const void *)k; }
+struct PairingLaunchRow { const void *kernel; size_t lds; };
+static const PairingLaunchRow PAIRING_LAUNCH[PE_COUNT] = {
+    {pairing_kernel(k_pairing_check), 0},
+    {pairing_kernel(k_pairing_six), SIX_LDS_BYTES},
+    {pairing_kernel(k_pairing_coop_twelve), COOP_LDS_BYTES(COOP_GROUPS_TWELVE)},
+    {pairing_kernel(k_pairing_coop_narrow), COOP_LDS_BYTES(COOP_GROUPS_NARROW)},
+    {pairing_kernel(k_pairing_coop), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE)},
+    {pairing_kernel(k_pairing_coop_wide), COOP_LDS_BYTES(1)},
+};
+static_assert(PAIRING_ENGINES[PE_ONE_LANE].per_wave == 64 && PAIRING_ENGINES[PE_SIX].per_wave == SIX_GROUPS &&
+              PAIRING_ENGINES[PE_TWELVE].per_wave == COOP_GROUPS_TWELVE && PAIRING_ENGINES[PE_NARROW].per_wave == COOP_GROUPS_NARROW &&
+              PAIRING_ENGINES[PE_COOP32].per_wave == COOP_GROUPS_PER_WAVE && PAIRING_ENGINES[PE_WIDE].per_wave == 1,
+              "h2v_pairing_engine.hpp: proofs per wave are the kernels' group counts");
 static uint32_t launch_pairing(const H2vDevPlan &d, uint32_t n, const uint32_t *pts, const uint8_t *valid, const uint8_t *valid_sub, const uint32_t *er,
-                           const uint32_t *el_jac, uint32_t *status, uint8_t *accept, uint32_t *dbg, hipStream_t st, uint32_t in_flight_hint = 1) {
-    const int impl = 1;
+                               const uint32_t *el_jac, uint32_t *status, uint8_t *accept, uint32_t *dbg, hipStream_t st, uint32_t in_flight_hint = 1,
+                               const uint32_t *skip = nullptr, int probe_impl = PAIRING_IMPL_RULE) {
     const double S = msm_n_simd();
-    // Eight or more batches in flight (the library's lanes): the chip is full whatever one launch brings, so the engine with the
-    // fewest instructions that still has waves to spread wins much earlier - wide (2 x the normal engine's instructions) only up
-    // to #SIMDs / 16 proofs, narrow from 3/8 #SIMDs.  ms per batch, wide / normal / narrow: secp256k1 shape x 64 0.55 / 0.58 / 0.63;
-    // sha256 shape x 128 0.67 / 0.66 / 0.72; x 256 1.15 / 1.08 / 1.06; x 512 1.61 / 1.43 / 1.47; secp256k1 x 512 1.67 / 1.57 / 1.55;
-    // simple_mul x 512 1.02 / 0.88 / 0.84; x 1024 - / 1.47 / 1.39; sha256 x 1024 - / 2.19 / 2.16.
-    // ... and where the narrow engine would run, its twelve-lane packing (five proofs per wave instead of four with four idle lanes
-    // each; the line products in a pass of their own): ms per batch, narrow -> twelve: sha256 shape x 1024 1.99 -> 1.96, secp256k1 x 512
-    // 1.21 -> 1.17, lookup_table x 2048 3.26 -> 3.16, atms x 2048 3.40 -> 3.34, simple_mul x 1024 1.24 -> 1.17.
-    const bool many = in_flight_hint >= 8;
-    // (round 4, from the tuner's measurements: at #SIMDs / 4 proofs - sha256 / secp256k1 shape x 256 - the normal engine beats the
-    //  twelve-lane one by 8-12 % in every run, 0.77-0.80 against 0.85-0.90 ms per batch; at x 512 neither wins by 3 %: the border is 3/8)
-    const bool prefer_narrow = many ? (double)n >= 3.0 * S / 8.0 : in_flight_hint >= 4 ? (double)n >= 2.0 * S : ((double)n > 2.0 * S && (double)n <= 4.0 * S);
-    // (the wide engine issues twice the instructions of the normal one: a caller that keeps the chip full takes it only up to
-    // #SIMDs / 2 proofs - sha256 shape x 1024, four in flight: wide 3.18, normal 2.98, narrow 3.12 ms per step; secp256k1 x 512:
-    // wide 2.37, normal 2.47, narrow 2.64)
-    // The SIX-lane engine (ten proofs per wave, h2v_pairing_six.hpp: a quarter fewer instructions per pairing than the narrow
-    // one, a chain almost twice as long) wherever a caller that keeps the chip full would take the narrow one
-    // from 4 * #SIMDs proofs up (410 waves; with eight or more batches in flight from 3 * #SIMDs: simple_mul x 3072 2.85 -> 2.69 ms per
-    // batch against the twelve-lane engine, x 2048 the same either way).  ms per step, narrow -> six: simple_mul x 4096
-    // 4.06 -> 3.88 with six batches in flight, 3.76 with eight; below that size its few long waves lose: lookup_table x 2048
-    // 3.48 -> 3.65, atms x 2048 3.92 -> 5.10.
-    return launch_pairing_impl(impl, d, n, pts, valid, valid_sub, er, el_jac, status, accept, dbg, st, nullptr, prefer_narrow,
-                               many ? S / 16.0 : in_flight_hint >= 4 ? S / 2.0 : S, in_flight_hint >= 4 && (double)n >= (many ? 3.0 : 4.0) * S, many);
+    const PairingEngine e = skip ? PE_COOP32 : pairing_engine(S, g_opts.v[H2V_OPT_PAIRING_ENGINE], n, in_flight_hint, d.six_norm28 != nullptr, probe_impl);
+    const uint32_t grid = skip ? pairing_grid_behind(S, n) : pairing_grid(e, n);
+    void *args[] = {(void *)&d, &n, &pts, &valid, &valid_sub, &er, &el_jac, &status, &accept, &dbg, &skip};
+    (void)hipLaunchKernel(PAIRING_LAUNCH[e].kernel, dim3(grid), dim3(64), args, PAIRING_LAUNCH[e].lds, st);   // (errors: the callers' hipGetLastError)
+    return (uint32_t)PAIRING_ENGINES[e].option;
 }
 
 // ---------------------------------------------------------------------------------------------- pipeline
@@ -1520,13 +1492,6 @@ static int launch_decompress(const H2vDevPlan &v, uint32_t n, const uint8_t *src
     HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
     hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, src, off, ci, inst, w->pts, w->valid, tab, w->valid_sub, w->dec_ctr, dec_grid);
     return H2V_OK;
-}
-// The per-proof pairing behind skip flags (the fall-back of a batch check): a walking grid of one wave per SIMD - finding out
-// that the launch is not needed costs a few microseconds, and a launch that IS needed has the whole chip.
-static void launch_pairing_behind(const uint32_t *skip, const H2vDevPlan &v, uint32_t n, const uint32_t *pts, const uint8_t *valid, const uint8_t *valid_sub,
-                                  const uint32_t *er, const uint32_t *el, uint32_t *status, uint8_t *accept, hipStream_t st) {
-    const uint32_t cond_grid = (uint32_t)(msm_n_simd() / 4.0), nb = (n + 1) / 2, grid = nb < 4 * cond_grid ? nb : 4 * cond_grid;
-    hipLaunchKernelGGL(k_pairing_coop, dim3(grid), dim3(64), COOP_LDS_BYTES(COOP_GROUPS_PER_WAVE), st, v, n, pts, valid, valid_sub, er, el, status, accept, (uint32_t *)nullptr, skip);
 }
 static int run_pipeline(const Unit &u, h2v_workspace *w, hipStream_t st) {
     const H2vDevPlan &d = u.p->d;
@@ -2196,9 +2161,8 @@ extern "C" int h2v_workspace_tune(const h2v_plan *p, const h2v_batch *b, h2v_wor
         if ((rc = measure(0, 0, &def_ms))) break;
         if (laned && 120.0f / def_ms > 3.0f * (float)depth && (rc = measure(0, 0, &def_ms))) break;   // (the baseline at the candidates' length)
         best_ms = def_ms;
-        const int32_t full[] = {6, 12, 16}, mid[] = {12, 16, 32}, low[] = {32, 64};
-        const int32_t *eng = (double)m >= 2.0 * S ? full : (double)m >= S / 4.0 ? mid : low;
-        const int n_eng = (double)m >= S / 4.0 ? 3 : 2;
+        const int32_t *eng = nullptr;
+        const int n_eng = pairing_tune_candidates(S, m, &eng);
         // (the fastest candidate replaces the launcher's rule when it is 3 % faster than THAT - not each candidate against the best so
         //  far, which favoured whichever engine happened to be measured first)
         float cand_ms = 0;
@@ -3029,7 +2993,7 @@ static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
         if (!launch_msm_range(d, ma, n, w->scalars, w->pts, nullptr, pm, 1, SegBuf{w->msm_parts, w->sz_segs}))
             return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
     }
-    launch_pairing_behind(skip, d, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, pm);
+    launch_pairing(d, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, nullptr, pm, w->in_flight_hint, skip);
     HIPCHK(hipGetLastError());
     if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
@@ -3084,7 +3048,7 @@ static int run_pairs_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
     HIPCHK(hipEventRecord(ev[1], st));
     if ((rc = pairs_rlc_core(u, r, w->pts, w->valid, w->valid_sub, false, w->status, w, rec, st))) return rc;
     hipLaunchKernelGGL(k_pairs_to_jac, dim3((n + 63) / 64), dim3(64), 0, st, n, (const uint32_t *)w->pts, w->er, (const uint32_t *)r->flags);
-    launch_pairing_behind(r->flags, v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, st);
+    launch_pairing(v, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, nullptr, st, w->in_flight_hint, r->flags);
     HIPCHK(hipGetLastError());
     if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
@@ -3103,7 +3067,7 @@ static int fold_pairs_tail(const Unit &u, const uint32_t *er2, const uint32_t *e
     hipLaunchKernelGGL(k_fold_pairs_affine, dim3((n + 63) / 64), dim3(64), 0, st, n, (uint32_t)H2V_SLOTS(d), w->valid, w->valid_sub, el2, er2, w->status, r->pool, r->good);
     if ((rc = pairs_rlc_core(u, r, r->pool, nullptr, nullptr, true, w->status, w, rec, st))) return rc;
     if (u.agg_parts) return H2V_OK;
-    launch_pairing_behind(r->flags, d, n, w->pts, w->valid, w->valid_sub, er2, el2, w->status, u.accept, st);
+    launch_pairing(d, n, w->pts, w->valid, w->valid_sub, er2, el2, w->status, u.accept, nullptr, st, w->in_flight_hint, r->flags);
     HIPCHK(hipGetLastError());
     return H2V_OK;
 }
@@ -3419,7 +3383,7 @@ static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
         HIPCHK(hipMemcpyAsync(r->good, mp.good, m, hipMemcpyDeviceToDevice, st));
         if ((rc = pairs_rlc_core(u, r, mp.pool, nullptr, nullptr, true, mp.status, w, rec, st))) return rc;
         hipLaunchKernelGGL(k_pairs_to_jac, dim3((m + 63) / 64), dim3(64), 0, st, m, (const uint32_t *)mp.pool, w->er, (const uint32_t *)r->flags);
-        launch_pairing_behind(r->flags, v, m, mp.pool, mp.ones, nullptr, w->er, nullptr, mp.status, u.accept, st);
+        launch_pairing(v, m, mp.pool, mp.ones, nullptr, w->er, nullptr, mp.status, u.accept, nullptr, st, w->in_flight_hint, r->flags);
     }
     HIPCHK(hipGetLastError());
     if (u.status) HIPCHK(hipMemcpyAsync(u.status, mp.status, (size_t)m * 4, hipMemcpyDeviceToDevice, st));

@@ -393,13 +393,13 @@ extern "C" int h2v_probe_decompress(const h2v_plan *p, const h2v_batch *b, int w
     h2v_workspace_free(ws);
     return rc;
 }
-// The pairing launch alone on n pairs, with every entry state a pipeline can hand it.  impl: -1 default, 0 one-lane-per-proof kernel,
-// 1 cooperative kernel (the launcher's choice of engine, or H2V_OPT_PAIRING_ENGINE of h2v_probe_set_option), 2 / 3 / 5 / 6 its narrow /
-// wide / six-lane / twelve-lane engine whatever n.  Optional inputs (NULL: as the pipelines' first launch has them): status_in (n words
+// The pairing launch alone on n pairs, with every entry state a pipeline can hand it.  impl: -1 default, 1 the same under
+// H2V_OPT_PAIRING_ENGINE of h2v_probe_set_option, or an engine's number in h2v_pairing_engine.hpp's table - that engine whatever
+// n; any other number is -1.  Optional inputs (NULL: as the pipelines' first launch has them): status_in (n words
 // the proofs arrive with), valid_sub_in (n x 2 bytes, the subgroup verdicts of slots p1, p2; NULL: the kernels get no such array),
 // el_jac_in (n x 36 dwords X, Y, Z, Montgomery limbs: the first argument, instead of slot p1).  Outputs, each optional: status_out
 // (n + H2V_PROBE_PAIRING_GUARD words), accept (n + GUARD bytes), dbg ((n + GUARD) x 24 x 48 bytes: f after the Miller loop and after
-// the final exponentiation, canonical LE limbs; NULL: the kernels get no dump buffer), lanes_out (launch_pairing_impl's answer: the
+// the final exponentiation, canonical LE limbs; NULL: the kernels get no dump buffer), lanes_out (launch_pairing's answer: the
 // engine that ran).  The device outputs are allocated for n + GUARD proofs, preset to 0xA5 bytes and copied back whole: what a
 // kernel left unwritten shows as such, and so does what a dead group of the last wave wrote behind proof n - 1.
 extern "C" int h2v_probe_pairing_states(const h2v_plan *p, uint32_t n, const uint8_t *p1c, const uint8_t *p2c, int impl, const uint32_t *status_in,
@@ -435,8 +435,9 @@ extern "C" int h2v_probe_pairing_states(const h2v_plan *p, uint32_t n, const uin
     else HIPCHK(hipMemset(dst.p, 0, (size_t)n * 4));
     hipLaunchKernelGGL(k_g1_decompress, dim3((n * 2 + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), dtab.as<uint32_t>(), 0u, (uint8_t *)nullptr);
     launch_msm(mp.d, n, dsc.as<uint32_t>(), dpts.as<uint32_t>(), dtab.as<uint32_t>(), der.as<uint32_t>(), nullptr, nullptr, nullptr);
-    const uint32_t lanes = launch_pairing_impl(impl, mp.d, n, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), valid_sub_in ? dsub.as<uint8_t>() : nullptr, der.as<uint32_t>(),
-                                               el_jac_in ? del.as<uint32_t>() : nullptr, dst.as<uint32_t>(), dacc.as<uint8_t>(), dbg ? ddbg.as<uint32_t>() : nullptr, nullptr);
+    const uint32_t lanes = launch_pairing(mp.d, n, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), valid_sub_in ? dsub.as<uint8_t>() : nullptr, der.as<uint32_t>(),
+                                          el_jac_in ? del.as<uint32_t>() : nullptr, dst.as<uint32_t>(), dacc.as<uint8_t>(), dbg ? ddbg.as<uint32_t>() : nullptr, nullptr,
+                                          PAIRING_HINT_PROBE, nullptr, impl);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
     if (lanes_out) *lanes_out = lanes;
