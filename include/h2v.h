@@ -317,6 +317,10 @@ int h2v_verify_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_
                                * other, and the pairs are checked as h2v_check_pairs_rlc checks pairs: ONE pairing for the batch,
                                * and after a failed check the per-proof pairing on the folded points (no MSM is repeated).
                                * accept[] / status[] are the per-proof mode's.  Never routed, never coalesced. */
+#define H2V_RLC_GROUPED 16u   /* h2v_aggregate_mixed(_device) only: the H2V_MIXED_GROUPED form of the call (below) - same pair, same
+                               * included[], same info; up to H2V_MIXED_GROUPED_MAX_PLANS plans.  H2V_E_ARG in any other aggregate call.
+                               * (Bit 8 stays unassigned: the aggregate calls have always answered H2V_E_ARG to it, and callers
+                               * and tests rely on that.) */
 typedef struct h2v_rlc_opts_s {
     uint8_t seed[32];   /* used when flags & H2V_RLC_SEED_GIVEN (tests, reproducible measurements - never a service) */
     uint32_t flags;
@@ -438,10 +442,39 @@ int h2v_check_pairs_rlc_device(const h2v_plan *plan, uint64_t n, const uint8_t *
  * flag it does, and on 16 keys x 64 proofs it is the fastest of the three routes measured (tools/bench_mixed.py --fold: 6.8 ms a
  * call against 10.3 without the flag and 12.7 for one h2v_verify_batch_rlc call per key); on 2 keys x 2048 proofs it LOSES to the
  * per-key h2v_verify_batch_rlc calls (7.1 against 3.3-4.8 ms), whose steps overlap in the lanes: few keys with many proofs each
- * stay with that route.  Measurements: DESIGN.md 15 / 15.1, profiles/mixed_fold.json. */
+ * stay with that route.  Measurements: DESIGN.md 15 / 15.1, profiles/mixed_fold.json.
+ *   H2V_MIXED_GROUPED (only together with H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM; otherwise H2V_E_ARG): phase 1 of every key in ONE
+ *   launch per kernel.  Without it every plan with proofs is a sub-batch of its own - a decompression launch, a combiner launch, a
+ *   terms launch and a record per KEY, so the cost of a call grows with its keys, not with its proofs.  With it the proofs of all
+ *   GROUPABLE plans - those that have the batch form above and whose combiner register file fits LDS - run as one unit over the
+ *   grouped positions (the proofs sorted by plan): one decompression launch, one combiner launch per transcript hash present,
+ *   one terms launch, each block finding its plan in a device table.  On a laned workspace the grouped positions are cut into
+ *   chunks through the lanes like any unit; a chunk may begin and end inside a plan and span many plans (the lanes of
+ *   h2v_workspace_create_multi are sized for the largest of every dimension).  Every other plan (recursive, or with a global
+ *   register file) keeps its own sub-batch and joins the tail as without the flag.
+ *   RESULTS are those of the same call without the flag under the same seed: accept[], status[], fell_back, and - the coefficient
+ *   of a proof being drawn from its position in the CALL - the call's two sums bit for bit.
+ *   RECORDS: the grouped part takes ONE record whatever the number of plans, every other plan with proofs one, the tail the last.
+ *   LIMITS: up to H2V_MIXED_GROUPED_MAX_PLANS plans may be listed, of which at most H2V_MIXED_GROUPED_MAX_OTHER plans that are not
+ *   groupable may have proofs (grouped part + 62 + tail = the 64 records of a workspace's ring); beyond either H2V_E_LIMIT, decided
+ *   on the host before anything is enqueued.  H2V_MIXED_MAX_PLANS holds for every call without the flag.
+ *   FALL-BACK as above.  With more than H2V_MIXED_MAX_PLANS plans with proofs the second pass - one sub-batch and one record per
+ *   plan - runs its sub-batches in slices of at most 62 plans, each slice joined before the next, and ends in the ONE tail.
+ *   OPTIONS: H2V_OPT_COMBINER_SCHEDULE and H2V_OPT_COMBINER_PROOFS_PER_BLOCK shape per-plan launches and do not apply to the
+ *   grouped launch: every plan runs its narrow schedule with as many proofs per block as its register file allows in LDS.  The
+ *   launch reserves the LDS of the largest register file among its plans for every block (one size class per transcript hash).
+ *   WHICH SHAPE IT IS FOR: many keys with a handful of proofs each.  Measured (tools/bench_mixed.py --fold --grouped,
+ *   profiles/mixed_grouped.json; 1024 accepting proofs, ms per call, five runs): 16 keys x 64 4.9-6.4 against 6.7-6.8 without the
+ *   flag; 64 keys x 16 5.7-6.9 against 13.5-13.7 (48.6-49.0 for one h2v_verify_batch_rlc call per key); 256 keys x 4 5.7-7.5 (186-188
+ *   per key; the call without the flag cannot take it) - it wins on all three by the project's rule.  NOT measured: 2 keys x 2048;
+ *   expect no gain for few keys with thousands of proofs each, where the chunks of the grouped unit are what the per-plan
+ *   sub-batches already were, and stay with the per-key h2v_verify_batch_rlc calls there.  The flag is opt-in.  DESIGN.md 15.2. */
 #define H2V_MIXED_RLC 1u          /* batch-accept: ONE pairing for the call; otherwise one pairing per proof, in ONE launch */
 #define H2V_MIXED_FOLD_MSM 2u     /* with H2V_MIXED_RLC: ONE bucket MSM over the call's per-proof terms as well; one host synchronisation */
-#define H2V_MIXED_MAX_PLANS 64u   /* more plans in one call: H2V_E_LIMIT */
+#define H2V_MIXED_GROUPED 4u      /* with both: phase 1 of every groupable plan in ONE launch per kernel; up to 1024 plans */
+#define H2V_MIXED_MAX_PLANS 64u   /* more plans in one call without H2V_MIXED_GROUPED: H2V_E_LIMIT */
+#define H2V_MIXED_GROUPED_MAX_PLANS 1024u /* more plans in one H2V_MIXED_GROUPED call: H2V_E_LIMIT */
+#define H2V_MIXED_GROUPED_MAX_OTHER 62u   /* ... of which plans that are not groupable and have proofs */
 typedef struct {
     uint64_t n;
     const uint32_t *plan_of;      /* HOST memory in BOTH forms: n entries, plan_of[i] < n_plans */
@@ -494,7 +527,8 @@ int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, cons
  *   with pairing_ms = 0 and batch_accepted = H2V_BATCH_NOT_CHECKED.
  *   ERRORS as h2v_verify_batch_rlc(_device) / h2v_verify_mixed(_device): n > 2^22 is H2V_E_LIMIT; stream = NULL under deferred
  *   joins, a host batch in flight on ws, ws = NULL in a device form are H2V_E_ARG; ws = NULL in a host form: a temporary workspace.
- *   opts->flags: H2V_RLC_SEED_GIVEN and H2V_RLC_ONE_STREAM as ever, H2V_RLC_FOLD_PAIRS accepted and ignored, any other bit H2V_E_ARG.
+ *   opts->flags: H2V_RLC_SEED_GIVEN and H2V_RLC_ONE_STREAM as ever, H2V_RLC_FOLD_PAIRS accepted and ignored, H2V_RLC_GROUPED in the
+ *   mixed forms (phase 1 grouped as with H2V_MIXED_GROUPED: the same pair bit for bit), any other bit H2V_E_ARG.
  *   The device forms take device pointers (pair 4-byte aligned; plan_of stays host memory); info is HOST memory in both forms.
  *   SOUNDNESS.  A pair vouches for its proofs only to someone who trusts that seed_used was unpredictable to the provers - the same
  *   trust domain as the caller of h2v_verify_batch_rlc.  It is NOT a proof for third parties.  Whoever combines the pairs of several

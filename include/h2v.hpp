@@ -252,10 +252,13 @@ inline std::vector<uint8_t> verify_batch_rlc(const VerifyingKey &vk, const h2v_b
 // caller's order, exactly the per-key verify call's.  rlc: ONE pairing for the call - the same vectors up to a 2^-128
 // soundness error over the seed (32 bytes that provers cannot predict, or nullptr = drawn from the OS); fell_back (optional):
 // that batch check failed and the per-pair kernels produced them.  fold_msm (only with rlc; H2V_MIXED_FOLD_MSM): ONE bucket MSM
-// over the call's per-proof terms as well; a failed check runs the call again without it (fell_back).  ws: one made for the same
-// keys or a superset (Workspace(vks, max_batch)), or nullptr for a temporary one.
+// over the call's per-proof terms as well; a failed check runs the call again without it (fell_back).  grouped (only with
+// fold_msm; H2V_MIXED_GROUPED): phase 1 of every key in one launch per kernel, up to H2V_MIXED_GROUPED_MAX_PLANS keys - many keys
+// with few proofs each; the same vectors.  ws: one made for the same keys or a superset (Workspace(vks, max_batch)), or nullptr
+// for a temporary one.
 inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
-                                 bool rlc = false, const uint8_t *seed = nullptr, bool *fell_back = nullptr, bool fold_msm = false) {
+                                 bool rlc = false, const uint8_t *seed = nullptr, bool *fell_back = nullptr, bool fold_msm = false,
+                                 bool grouped = false) {
     std::vector<const h2v_plan *> plans;
     for (const VerifyingKey *k : vks) plans.push_back(k ? k->handle() : nullptr);
     PairVerdicts r{std::vector<uint8_t>(batch.n), std::vector<uint32_t>(batch.n)};
@@ -263,7 +266,7 @@ inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, c
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
     int fb = 0;
     check(h2v_verify_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.accept.data(), r.status.data(), ws,
-                           (rlc ? H2V_MIXED_RLC : 0u) | (fold_msm ? H2V_MIXED_FOLD_MSM : 0u), seed ? &opts : nullptr, &fb));
+                           (rlc ? H2V_MIXED_RLC : 0u) | (fold_msm ? H2V_MIXED_FOLD_MSM : 0u) | (grouped ? H2V_MIXED_GROUPED : 0u), seed ? &opts : nullptr, &fb));
     if (fell_back) *fell_back = fb != 0;
     return r;
 }
@@ -271,8 +274,8 @@ inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, c
 // one final check for a list of (vk, instances, proof) triples on one SRS.  Throws VerifyError (with the first rejected proof's
 // status) unless every proof is accepted.
 inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
-                         bool fold_msm = false) {
-    const PairVerdicts r = verify_mixed(vks, batch, ws, true, nullptr, nullptr, fold_msm);
+                         bool fold_msm = false, bool grouped = false) {
+    const PairVerdicts r = verify_mixed(vks, batch, ws, true, nullptr, nullptr, fold_msm, grouped);
     for (uint64_t i = 0; i < batch.n; i++)
         if (!r.accept[i]) throw VerifyError(r.status[i]);
 }
@@ -280,7 +283,8 @@ inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v
 // R = sum r_i R_i over the included proofs, instead of a pairing on it - the reference's `dual_msm.scale(r)` / `acc.add_msm(..)`;
 // check_pairs(_rlc) is its `check`.  included[i] = 1: proof i was not rejected before the pairing (NOT a verdict: it is accepted
 // iff the pair's equation holds); status as prepare_batch; info: the seed and chunking the coefficients follow.  seed: 32 bytes
-// that provers cannot predict, or nullptr = drawn from the OS.
+// that provers cannot predict, or nullptr = drawn from the OS.  grouped (aggregate_mixed; H2V_RLC_GROUPED): phase 1 as
+// verify_mixed(.., grouped) runs it - the same pair.
 struct Aggregate {
     uint8_t pair[96];
     std::vector<uint8_t> included;
@@ -296,14 +300,15 @@ inline Aggregate aggregate_batch(const VerifyingKey &vk, const h2v_batch &batch,
     return r;
 }
 inline Aggregate aggregate_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
-                                 const uint8_t *seed = nullptr) {
+                                 const uint8_t *seed = nullptr, bool grouped = false) {
     std::vector<const h2v_plan *> plans;
     for (const VerifyingKey *k : vks) plans.push_back(k ? k->handle() : nullptr);
     Aggregate r{{}, std::vector<uint8_t>(batch.n ? batch.n : 1), std::vector<uint32_t>(batch.n ? batch.n : 1), {}};
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
-    check(h2v_aggregate_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.pair, r.included.data(), r.status.data(), ws, seed ? &opts : nullptr,
-                              &r.info));
+    if (grouped) opts.flags |= H2V_RLC_GROUPED;
+    check(h2v_aggregate_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.pair, r.included.data(), r.status.data(), ws,
+                              (seed || grouped) ? &opts : nullptr, &r.info));
     r.included.resize(batch.n); r.status.resize(batch.n);
     return r;
 }
@@ -312,10 +317,11 @@ inline Aggregate aggregate_mixed(const std::vector<const VerifyingKey *> &vks, c
 // with one pairing (check_pairs_rlc; check_pairs for K = 1): a call whose pair passes gets accept = included, a call whose pair
 // fails is verified per proof (verify_batch) on the kept inputs.  Same semantics as api.Aggregator (there `params` names the SRS).  finish() returns the per-call accept vectors in push order and
 // fills `reverified` with the indices of the calls verified again.  The keys must outlive the Aggregator; keep it inside one trust
-// domain (a pair is only worth what the seed of its call is).
+// domain (a pair is only worth what the seed of its call is).  push_mixed() aggregates a call over several keys
+// (aggregate_mixed; Aggregator(true): its grouped form) and is verified again, if its pair fails, with verify_mixed.
 class Aggregator {
   public:
-    Aggregator() {}
+    explicit Aggregator(bool grouped = false) : grouped_(grouped) {}
     Aggregator(const Aggregator &) = delete;
     Aggregator &operator=(const Aggregator &) = delete;
     /// one SRS per Aggregator - that of the first key pushed: a key on another SRS is Error(H2V_E_ARG), before anything runs
@@ -338,6 +344,32 @@ class Aggregator {
         calls_.push_back(std::move(c));
         return calls_.size() - 1;
     }
+    size_t push_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &b, const uint8_t *seed = nullptr) {
+        if (vks.empty() || !vks[0]) throw Error(H2V_E_ARG, "Aggregator: no key");
+        if (!srs_) srs_ = vks[0];
+        for (const VerifyingKey *k : vks) {
+            const int same = k ? h2v_plan_same_srs(srs_->handle(), k->handle()) : 0;
+            if (same < 0) check(same);
+            if (same != 1) throw Error(H2V_E_ARG, "Aggregator: this key is on another SRS than the keys pushed before (s_g2 differs)");
+        }
+        Call c;
+        c.vk = vks[0];
+        c.vks = vks;
+        const Aggregate a = aggregate_mixed(vks, b, nullptr, seed, grouped_);
+        for (int k = 0; k < 96; k++) c.pair[k] = a.pair[k];
+        c.included = a.included;
+        c.plan_of.assign(b.plan_of, b.plan_of + b.n);
+        c.off.assign(b.proof_off, b.proof_off + b.n + 1);
+        const uint64_t base = c.off[0];
+        for (uint64_t &o : c.off) o -= base;
+        c.proofs.assign(b.proofs + base, b.proofs + base + c.off[b.n]);
+        uint64_t n_inst = 0, n_ci = 0;
+        for (uint64_t i = 0; i < b.n; i++) { n_inst += 32ull * vks[b.plan_of[i]]->n_public_inputs(); n_ci += vks[b.plan_of[i]]->n_committed_instances() ? 48 : 0; }
+        if (b.instances) c.inst.assign(b.instances, b.instances + n_inst);
+        if (b.committed) c.ci.assign(b.committed, b.committed + n_ci);
+        calls_.push_back(std::move(c));
+        return calls_.size() - 1;
+    }
     std::vector<std::vector<uint8_t>> finish(std::vector<size_t> *reverified = nullptr, const uint8_t *seed = nullptr) {
         std::vector<Call> calls;
         calls.swap(calls_);
@@ -351,6 +383,12 @@ class Aggregator {
             const Call &c = calls[k];
             if (v.accept[k]) { out.push_back(c.included); continue; }
             if (reverified) reverified->push_back(k);
+            if (!c.vks.empty()) {
+                const h2v_mixed_batch mb{c.included.size(), c.plan_of.data(), c.proofs.data(), c.off.data(), c.inst.empty() ? nullptr : c.inst.data(),
+                                         c.ci.empty() ? nullptr : c.ci.data()};
+                out.push_back(verify_mixed(c.vks, mb).accept);
+                continue;
+            }
             const h2v_batch b{c.included.size(), c.proofs.data(), c.off.data(), c.inst.empty() ? nullptr : c.inst.data(), c.ci.empty() ? nullptr : c.ci.data()};
             out.push_back(verify_batch(*c.vk, b));
         }
@@ -363,9 +401,12 @@ class Aggregator {
         uint8_t pair[96];
         std::vector<uint8_t> included, proofs, inst, ci;
         std::vector<uint64_t> off;
+        std::vector<const VerifyingKey *> vks;   // push_mixed: the call's keys and plan_of
+        std::vector<uint32_t> plan_of;
     };
     std::vector<Call> calls_;
     const VerifyingKey *srs_ = nullptr;
+    bool grouped_ = false;
 };
 
 // A reusable workspace, and the streaming form: submit() returns once the batch is copied and everything is enqueued,

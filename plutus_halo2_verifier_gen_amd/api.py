@@ -290,27 +290,23 @@ def _mixed_workspace(verifiers, n: int) -> backend.Workspace:
 
 def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
                  committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof", seed: Optional[bytes] = None,
-                 device: int = 0, fold_msm: bool = False) -> List[bool]:
+                 device: int = 0, fold_msm: bool = False, grouped: bool = False) -> List[bool]:
     """accept[i] for n proofs, proof i under the key vks[i] (instances[i]: its public-input scalars; committed[i]: its
     committed instance as 48 compressed bytes when its circuit has one, else None).  The proofs are grouped by SRS on the
     host - one h2v_verify_mixed call per distinct s_g2, each over all its keys - and the verdicts come back in the caller's
     order.  mode="rlc": ONE pairing per call (the reference's batch_verify); same accept vector up to a 2^-128 soundness error
     over `seed` (from the OS when None).  fold_msm (mode="rlc" only): ONE bucket MSM over the call's per-proof terms as well
-    (H2V_MIXED_FOLD_MSM); a failed check runs the call again without it."""
-    return _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm)[0]
+    (H2V_MIXED_FOLD_MSM); a failed check runs the call again without it.  grouped (with fold_msm only; H2V_MIXED_GROUPED): phase 1
+    of every key in one launch per kernel and up to backend.MIXED_GROUPED_MAX_PLANS keys per call - for many keys with few proofs
+    each; the same verdicts."""
+    return _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm, grouped)[0]
 
 
-def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm=False):
-    """(accept, status) of verify_mixed"""
+def _mixed_calls(vks, proofs, instances, committed, device):
+    """The proofs grouped by SRS: per distinct s_g2 (positions, verifiers, plan_of, proof bytes, offsets, instances, committed)"""
     n = len(proofs)
     if len(vks) != n or len(instances) != n or (committed is not None and len(committed) != n):
         raise ValueError("one key, one instance list (and one committed instance or None) per proof")
-    if mode not in ("per-proof", "rlc"):
-        raise ValueError("mode is 'per-proof' or 'rlc'")
-    if fold_msm and mode != "rlc":
-        raise ValueError("fold_msm needs mode='rlc'")
-    out: List[bool] = [False] * n
-    status: List[int] = [0] * n
     groups = {}                                   # s_g2 -> positions, in the caller's order
     for i, vk in enumerate(vks):
         groups.setdefault(vk.s_g2, []).append(i)
@@ -332,9 +328,22 @@ def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_ms
             if pl.n_ci:
                 c = committed[i] if committed is not None else None
                 ci.append(bls.g1_compress(None) if c is None else bytes(c))
-        acc, st, _fb = backend.verify_mixed([v.device_plan for v in verifiers], plan_of, b"".join(bytes(proofs[i]) for i in idx), off,
-                                             b"".join(inst), b"".join(ci) or None, ws=_mixed_workspace(verifiers, len(idx)), mode=mode,
-                                             seed=seed, fold_msm=fold_msm)
+        yield idx, verifiers, plan_of, b"".join(bytes(proofs[i]) for i in idx), off, b"".join(inst), b"".join(ci) or None
+
+
+def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm=False, grouped=False):
+    """(accept, status) of verify_mixed"""
+    if mode not in ("per-proof", "rlc"):
+        raise ValueError("mode is 'per-proof' or 'rlc'")
+    if fold_msm and mode != "rlc":
+        raise ValueError("fold_msm needs mode='rlc'")
+    if grouped and not fold_msm:
+        raise ValueError("grouped needs mode='rlc' and fold_msm")
+    out: List[bool] = [False] * len(proofs)
+    status: List[int] = [0] * len(proofs)
+    for idx, verifiers, plan_of, pbytes, off, inst, ci in _mixed_calls(vks, proofs, instances, committed, device):
+        acc, st, _fb = backend.verify_mixed([v.device_plan for v in verifiers], plan_of, pbytes, off, inst, ci,
+                                             ws=_mixed_workspace(verifiers, len(idx)), mode=mode, seed=seed, fold_msm=fold_msm, grouped=grouped)
         for i, a, s in zip(idx, acc, st):
             out[i], status[i] = bool(a), s
     return out, status
@@ -342,15 +351,15 @@ def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_ms
 
 def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instances: Sequence[Sequence[int]],
                  proofs: Sequence[bytes], committed: Optional[Sequence[Optional[bytes]]] = None, device: int = 0,
-                 fold_msm: bool = False) -> None:
+                 fold_msm: bool = False, grouped: bool = False) -> None:
     """midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs) (src/circuits/schnorr_circuit.rs:223-231): one
     call and one final check for a list of (vk, instances, proof) triples on ONE SRS - the batch-accept mode of verify_mixed.
     Raises VerifyError unless every proof is accepted (Rust: Err(_)); a key on another SRS than `params` is a ValueError.
-    fold_msm: one bucket MSM for the list as well (verify_mixed)."""
+    fold_msm: one bucket MSM for the list as well; grouped: phase 1 of every key in one launch per kernel (verify_mixed)."""
     for i, vk in enumerate(vks):
         if bytes(params.s_g2) != bytes.fromhex(vk.s_g2):
             raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
-    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm)
+    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm, grouped)
     if not all(acc):
         raise VerifyError(next(s for a, s in zip(acc, status) if not a))
 
@@ -370,9 +379,10 @@ class Aggregator:
     kept.  The pairs of different calls are scaled again with fresh coefficients by the check, so the errors of two calls cannot
     cancel.  A pair is only worth what the seed of its call is: keep an Aggregator inside one trust domain."""
 
-    def __init__(self, params: ParamsVerifierKZG, device: int = 0):
-        self.params, self.device = params, device
-        self._calls = []      # (verifier, pair, included, (proofs, instances, committed))
+    def __init__(self, params: ParamsVerifierKZG, device: int = 0, grouped: bool = False):
+        """grouped: push_mixed runs phase 1 of every key in one launch per kernel (H2V_RLC_GROUPED) - the same pairs"""
+        self.params, self.device, self.grouped = params, device, grouped
+        self._calls = []      # (a verifier on the SRS, pair, included, the call again per proof -> accept list)
 
     def push(self, vk: VerifyingKey, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
              committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None) -> int:
@@ -381,7 +391,22 @@ class Aggregator:
             raise ValueError("verifier params do not match the verifying key's SRS (s_g2 differs)")
         v = verifier_for(vk, self.device)
         pair, included, _status, _info = v.aggregate_batch(proofs, instances, committed, seed=seed)
-        self._calls.append((v, pair, included, (proofs, instances, committed)))
+        self._calls.append((v, pair, included, lambda: v.verify_batch(proofs, instances, committed)))
+        return len(self._calls) - 1
+
+    def push_mixed(self, vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
+                   committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None) -> int:
+        """aggregates one call of proofs of SEVERAL keys, proof i under vks[i] (h2v_aggregate_mixed; with grouped=True the
+        H2V_RLC_GROUPED form: up to backend.MIXED_GROUPED_MAX_PLANS keys); returns the call's index"""
+        for i, vk in enumerate(vks):
+            if bytes(self.params.s_g2) != bytes.fromhex(vk.s_g2):
+                raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
+        if not proofs:
+            raise ValueError("no proofs")
+        (idx, verifiers, plan_of, pbytes, off, inst, ci), = _mixed_calls(vks, proofs, instances, committed, self.device)
+        pair, included, _status, _info = backend.aggregate_mixed([v.device_plan for v in verifiers], plan_of, pbytes, off, inst, ci,
+                                                                 ws=_mixed_workspace(verifiers, len(idx)), seed=seed, grouped=self.grouped)
+        self._calls.append((verifiers[0], pair, included, lambda: verify_mixed(vks, proofs, instances, committed, device=self.device)))
         return len(self._calls) - 1
 
     def finish(self, seed: Optional[bytes] = None):
@@ -393,10 +418,10 @@ class Aggregator:
         pairs = [c[1] for c in calls]
         ok, _st = calls[0][0].check_pairs(pairs, mode="rlc" if len(pairs) > 1 else "per-pair", seed=seed)
         accepts, reverified = [], []
-        for k, (v, _pair, included, (proofs, instances, committed)) in enumerate(calls):
+        for k, (_v, _pair, included, again) in enumerate(calls):
             if ok[k]:
                 accepts.append(list(included))
             else:
                 reverified.append(k)
-                accepts.append(v.verify_batch(proofs, instances, committed))
+                accepts.append(again())
         return accepts, reverified

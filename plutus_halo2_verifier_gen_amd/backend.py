@@ -79,17 +79,21 @@ OPT_COUNT = 16
 RLC_SEED_GIVEN = 1
 RLC_ONE_STREAM = 2
 RLC_FOLD_PAIRS = 4   # recursive plans: combine the pairs (el', er') the fold leaves (include/h2v.h)
+RLC_GROUPED = 16     # h2v_aggregate_mixed(_device) only: the MIXED_GROUPED form of the call (bit 8 stays unknown)
 SUBMIT_RLC = 1
 MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
 MIXED_FOLD_MSM = 2     # ... and ONE bucket MSM over the call's per-proof terms (only together with MIXED_RLC)
+MIXED_GROUPED = 4      # ... and phase 1 of every groupable plan in ONE launch per kernel (only together with both)
 MIXED_MAX_PLANS = 64   # H2V_MIXED_MAX_PLANS
+MIXED_GROUPED_MAX_PLANS = 1024   # H2V_MIXED_GROUPED_MAX_PLANS: plans listed in a MIXED_GROUPED call
+MIXED_GROUPED_MAX_OTHER = 62     # H2V_MIXED_GROUPED_MAX_OTHER: ... of which plans that cannot be grouped and have proofs
 BATCH_NOT_CHECKED = 2  # H2V_BATCH_NOT_CHECKED: batch_accepted of an aggregate call (Workspace.rlc_verdict)
 
 
-def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False):
-    if seed is None and not one_stream and not fold_pairs:
+def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False, grouped: bool = False):
+    if seed is None and not one_stream and not fold_pairs and not grouped:
         return None
-    flags = (RLC_ONE_STREAM if one_stream else 0) | (RLC_FOLD_PAIRS if fold_pairs else 0)
+    flags = (RLC_ONE_STREAM if one_stream else 0) | (RLC_FOLD_PAIRS if fold_pairs else 0) | (RLC_GROUPED if grouped else 0)
     if seed is None:
         return RlcOpts((C.c_uint8 * 32)(), flags)
     seed = bytes(seed)
@@ -562,22 +566,24 @@ class Workspace:
 
 
 # ---- mixed-key batches (include/h2v.h: h2v_verify_mixed)
-def _mixed_mode(mode: str, fold_msm: bool = False) -> int:
+def _mixed_mode(mode: str, fold_msm: bool = False, grouped: bool = False) -> int:
     if mode not in ("per-proof", "rlc"):
         raise ValueError("mode is 'per-proof' or 'rlc'")
     if fold_msm and mode != "rlc":
         raise ValueError("fold_msm needs mode='rlc' (H2V_MIXED_FOLD_MSM is valid only together with H2V_MIXED_RLC)")
-    return (MIXED_RLC if mode == "rlc" else 0) | (MIXED_FOLD_MSM if fold_msm else 0)
+    # (grouped without fold_msm goes to the library as it is: the library answers H2V_E_ARG)
+    return (MIXED_RLC if mode == "rlc" else 0) | (MIXED_FOLD_MSM if fold_msm else 0) | (MIXED_GROUPED if grouped else 0)
 
 
 def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
-                 mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False):
+                 mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False):
     """h2v_verify_mixed: n proofs of several plans on ONE SRS in one call; proof i belongs to plans[plan_of[i]], its public
     inputs (and committed instance, where its plan has one) follow those of the proofs before it.  Returns (accept bytes,
     status list, fell_back) in the caller's order.  mode="rlc": ONE pairing for the call (fell_back: the batch check failed
     and the per-pair kernels produced accept[]).  fold_msm (mode="rlc" only; MIXED_FOLD_MSM): ONE bucket MSM over the call's
     per-proof terms as well - no ladder MSM unless the check fails, in which case the call runs again without it (fell_back).
-    ws: typically Workspace.multi over the same plans; None: a temporary one."""
+    grouped (with fold_msm only; MIXED_GROUPED): phase 1 of every groupable plan in one launch per kernel, up to
+    MIXED_GROUPED_MAX_PLANS plans - the same results.  ws: typically Workspace.multi over the same plans; None: a temporary one."""
     n = len(proof_off) - 1
     if n < 0 or len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
@@ -594,7 +600,7 @@ def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[b
     acc = (C.c_uint8 * max(1, n))()
     st = (C.c_uint32 * max(1, n))()
     fb = C.c_int(0)
-    flags = _mixed_mode(mode, fold_msm)
+    flags = _mixed_mode(mode, fold_msm, grouped)
     opts = _rlc_opts(seed)
     check(lib().h2v_verify_mixed(arr, len(plans), C.byref(b), acc, st, ws.handle if ws else None, flags,
                                  C.byref(opts) if opts is not None else None, C.byref(fb)))
@@ -602,14 +608,14 @@ def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[b
 
 
 def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_accept, d_status=None, ws=None, stream=None,
-                        mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False) -> None:
+                        mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False) -> None:
     """h2v_verify_mixed_device: enqueues on `stream`; plan_of is a host list, every d_* a device pointer.  `stream` has
     waited for the call's lanes when this returns (a join point, deferred joins or not); ws.rlc_result() has the batch
     verdict of an mode="rlc" call once the stream is synchronised.  fold_msm: as verify_mixed; the call then returns only
     after the batch verdict is known (it synchronises `stream` once)."""
     if len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
-    flags = _mixed_mode(mode, fold_msm)
+    flags = _mixed_mode(mode, fold_msm, grouped)
     arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
     po = (C.c_uint32 * max(1, n))(*plan_of)
     b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
@@ -619,9 +625,10 @@ def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d
 
 
 def aggregate_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
-                    seed: Optional[bytes] = None):
+                    seed: Optional[bytes] = None, grouped: bool = False):
     """h2v_aggregate_mixed: the fold_msm form of verify_mixed without its verdict - (pair, included, status, info) for the call,
-    included / status in the caller's order; the coefficient of proof i follows its position in the call (info.chunk = 0)."""
+    included / status in the caller's order; the coefficient of proof i follows its position in the call (info.chunk = 0).
+    grouped (RLC_GROUPED): phase 1 as verify_mixed(grouped=True) runs it - the same pair."""
     n = len(proof_off) - 1
     if n < 0 or len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
@@ -639,14 +646,14 @@ def aggregate_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optiona
     inc = (C.c_uint8 * max(1, n))()
     st = (C.c_uint32 * max(1, n))()
     info = AggregateInfo()
-    opts = _rlc_opts(seed)
+    opts = _rlc_opts(seed, grouped=grouped)
     check(lib().h2v_aggregate_mixed(arr, len(plans), C.byref(b), pair, inc, st, ws.handle if ws else None,
                                     C.byref(opts) if opts is not None else None, C.byref(info)))
     return pair.raw, bytes(inc[:n]), list(st[:n]), info
 
 
 def aggregate_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_pair, d_included, d_status=None, ws=None,
-                           stream=None, seed: Optional[bytes] = None) -> AggregateInfo:
+                           stream=None, seed: Optional[bytes] = None, grouped: bool = False) -> AggregateInfo:
     """h2v_aggregate_mixed_device: enqueues on `stream` and returns - no verdict comes down, the stream is not synchronised"""
     if len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
@@ -654,7 +661,7 @@ def aggregate_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci
     po = (C.c_uint32 * max(1, n))(*plan_of)
     b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
     info = AggregateInfo()
-    opts = _rlc_opts(seed)
+    opts = _rlc_opts(seed, grouped=grouped)
     check(lib().h2v_aggregate_mixed_device(arr, len(plans), C.byref(b), d_pair, d_included, d_status, ws.handle if ws else None, stream,
                                            C.byref(opts) if opts is not None else None, C.byref(info)))
     return info

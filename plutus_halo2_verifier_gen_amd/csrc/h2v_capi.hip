@@ -18,6 +18,9 @@
 #include "h2v_mixed_dev.hpp"
 #include "h2v_mixed_fold.hpp"
 #include "h2v_mixed_fold_dev.hpp"
+#define H2V_GROUP_HD __host__ __device__ inline
+#include "h2v_mixed_group.hpp"
+#include "h2v_mixed_group_dev.hpp"
 #include "h2v_aggregate_dev.hpp"
 #include "h2v_msm_shape.hpp"
 #include "h2v_pairing_engine.hpp"
@@ -1423,9 +1426,11 @@ extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_
 //   MIXED_SUB_TERMS   H2V_MIXED_FOLD_MSM, a sub-batch of a plan that has the batch form: phase 1 alone, then k_mixed_terms writes the
 //                proofs' terms into the call's term pool (run_mixed_terms); no MSM, no pair; the record is a prepare call's
 //   MIXED_FOLD_TAIL   H2V_MIXED_FOLD_MSM: ONE bucket MSM over the call's term pool and ONE pairing (run_mixed_fold_tail)
+//   MIXED_GROUP  H2V_MIXED_GROUPED: MIXED_SUB_TERMS for a range of the grouped positions - every groupable plan's share of it in ONE
+//                launch per kernel (run_mixed_group); n / first: the range's size and first grouped position
 // seed: the batch coefficients' (RLC kinds).  fail_ctr: where a failed batch check is counted - a lane's chunk or a coalesced
 // group: its parent's word; NULL (a call of its own): its record's word, zeroed by the call.
-enum class UnitKind : uint8_t { VERIFY, PREPARE, CHECK, RLC, PAIR_RLC, FOLD_RLC, ROUTED, MIXED_SUB, MIXED_TAIL, MIXED_TAIL_RLC, MIXED_SUB_TERMS, MIXED_FOLD_TAIL };
+enum class UnitKind : uint8_t { VERIFY, PREPARE, CHECK, RLC, PAIR_RLC, FOLD_RLC, ROUTED, MIXED_SUB, MIXED_TAIL, MIXED_TAIL_RLC, MIXED_SUB_TERMS, MIXED_FOLD_TAIL, MIXED_GROUP };
 struct MixedFold;
 // the pool of a mixed call, caller's order: pairs (two-slot affine records), good_i, 2 x cap bytes of 1 (the `valid` of a two-slot
 // view) and the status words (pre-pairing bits; the tail folds H2V_ST_PAIRING in)
@@ -1663,6 +1668,7 @@ static int run_pairs_rlc(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
+static int run_mixed_group(const Unit &u, h2v_workspace *w, hipStream_t st);
 // ROUTING of RLC calls (round 4).  The batch-accept mode pays for every batch whose check fails: with 1 % rejecting proofs
 // nearly half of the groups of 64 fail, and the call costs 1.3 x the per-proof mode it falls back to.  A workspace therefore
 // keeps a running estimate of the rate of FAILING GROUPS among the groups its RLC calls have seen - cumulative device
@@ -1721,6 +1727,7 @@ static int run_unit(const Unit &u, h2v_workspace *w, hipStream_t st) {
     case UnitKind::MIXED_TAIL: case UnitKind::MIXED_TAIL_RLC: return run_mixed_tail(u, w, st);
     case UnitKind::MIXED_SUB_TERMS: return run_mixed_terms(u, w, st);
     case UnitKind::MIXED_FOLD_TAIL: return run_mixed_fold_tail(u, w, st);
+    case UnitKind::MIXED_GROUP: return run_mixed_group(u, w, st);
     case UnitKind::VERIFY: case UnitKind::PREPARE: case UnitKind::FOLD_RLC: case UnitKind::MIXED_SUB: break;
     }
     return run_pipeline(u, w, st);
@@ -1775,7 +1782,8 @@ static int run_on_lane(h2v_workspace *w, uint32_t l, const Unit &u, const LaneSe
     lw->opt[H2V_OPT_RLC_GROUP_STAGE] = w->opt[H2V_OPT_RLC_GROUP_STAGE];
     if (counted) lw->rlc_stats_ptr = w->rlc_stats;
     if (u.kind == UnitKind::ROUTED) lw->one_stream_mode = 1;
-    else if (u.kind == UnitKind::VERIFY || u.kind == UnitKind::PREPARE || u.kind == UnitKind::FOLD_RLC || u.kind == UnitKind::MIXED_SUB || u.kind == UnitKind::MIXED_SUB_TERMS)
+    else if (u.kind == UnitKind::VERIFY || u.kind == UnitKind::PREPARE || u.kind == UnitKind::FOLD_RLC || u.kind == UnitKind::MIXED_SUB || u.kind == UnitKind::MIXED_SUB_TERMS ||
+             u.kind == UnitKind::MIXED_GROUP)
         lw->one_stream_mode = s.stream_mode;
     int rc = run_unit(u, lw, w->lane_st[l]);
     if (rc == H2V_OK && counted) rc = rlc_stats_mirror(w, w->lane_st[l]);
@@ -3185,6 +3193,18 @@ struct MixedWs {
 };
 // one fold call: the pool, its layout, the device table of the foldable plans, the call's seed (ONE per call: chunks of a
 // sub-batch do not derive their own, coefficients follow the position in the call)
+// H2V_MIXED_GROUPED: which plans of a call are groupable and where their proofs lie among the grouped positions (decided on the
+// host before anything is enqueued: mixed_group_layout), and - per range of a running call - the device tables of its groups
+// (h2v_mixed_group.hpp), which travel in the call's pinned block
+struct MixedGroupPlan {
+    h2vmixed::GroupSpace sp;
+    std::vector<h2vmixed::GroupShape> shapes;
+};
+struct MixedGroupRange {
+    const H2vGroupRec *recs;
+    const uint32_t *comb[2], *dec, *terms;
+    uint32_t n_groups, n, blocks_comb[2], units, blocks_terms, lds[2];
+};
 struct MixedFold {
     MixedWs *m;
     const h2vmixed::FoldLayout *lay;
@@ -3193,6 +3213,9 @@ struct MixedFold {
     const H2vFoldPlan *d_plans;           // lay->n_foldable entries
     const uint32_t *d_perm;               // grouped index -> position in the call
     uint32_t seed[8];
+    const MixedGroupPlan *grp = nullptr;  // H2V_MIXED_GROUPED
+    std::vector<MixedGroupRange> ranges;  // its ranges, in order
+    const uint64_t *d_off = nullptr;      // the grouped proof offsets (n + 1)
 };
 static void mixed_release(h2v_workspace *w) {
     MixedWs *m = w->mixed;
@@ -3311,6 +3334,66 @@ static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st) {
     HIPCHK(hipGetLastError());
     return H2V_OK;
 }
+// H2V_MIXED_GROUPED, one range of the grouped positions (u.first .. + u.n): run_mixed_terms for every groupable plan's share of
+// the range at once - ONE decompression launch without window tables, the combiner beside it (one launch per transcript kind that
+// has proofs in the range), joined, then ONE k_mixed_terms_grouped.  Every block finds its plan in the range's group table; every
+// plan runs its narrow schedule with P = vm_lds_slots (the workspace's combiner options shape per-plan launches only).  Group g's
+// sub-batch lies at its first position x the call's union strides in the workspace's buffers.  The record is a prepare call's;
+// events [0]/[1] around the combiner launches, [2]/[3] around the decompression, [4]/[5] around k_mixed_terms_grouped (so that
+// h2v_workspace_timings reports it where a pipeline reports its MSM), [6] = [5].
+static int run_mixed_group(const Unit &u, h2v_workspace *w, hipStream_t st) {
+    const MixedFold &f = *u.fold;
+    const h2vmixed::GroupSpace &sp = f.grp->sp;
+    const size_t c = sp.chunk ? u.first / sp.chunk : 0u;
+    if (c >= f.ranges.size() || f.ranges[c].n != u.n || (sp.chunk && u.first % sp.chunk))
+        return fail(H2V_E_DEVICE, "internal: a grouped unit is not a range of the call");
+    const MixedGroupRange &g = f.ranges[c];
+    if (u.n > w->cap || sp.u_terms > w->sz_terms || sp.u_slots > w->sz_slots)
+        return fail(H2V_E_DEVICE, "internal: a grouped range does not fit the workspace");
+    LaunchOptsScope opts(w);
+    int rc;
+    CallRec &rec = rec_new(w, h2v_workspace::PREPARE);
+    hipEvent_t *ev = rec.ev;
+    const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode == 1 : w->in_flight_hint >= 3;
+    if (!one_stream && (rc = ws_streams(w, false, true))) return rc;
+    hipStream_t pm = st, ps = one_stream ? st : w->pside;
+    if (!one_stream) {
+        HIPCHK(hipEventRecord(w->ev_fork, st));
+        HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
+    }
+    MixedWs *m = f.m;
+    HIPCHK(hipEventRecord(ev[2], ps));
+    {
+        const uint32_t units = 2 * g.units, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
+        const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
+        HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, ps));
+        const GroupDecompressArgs da = {g.recs, g.dec, g.n_groups, g.units, m->proofs.p, f.d_off, m->inst.p, m->ci.p, w->pts, w->valid, w->valid_sub, w->dec_ctr};
+        hipLaunchKernelGGL(k_g1_decompress_queue_grouped, dim3(blocks), dim3(256), 0, ps, da);
+    }
+    HIPCHK(hipEventRecord(ev[3], ps));
+    HIPCHK(hipEventRecord(w->ev_join, ps));
+    HIPCHK(hipEventRecord(ev[0], pm));
+    for (int t = 0; t < 2; t++) {
+        if (!g.blocks_comb[t]) continue;
+        const auto k_grp = t == (int)H2V_TR_BLAKE2B_512 ? k_transcript_combiner_grouped_b512 : k_transcript_combiner_grouped;
+        if (g.lds[t] > H2V_VM_LDS_BYTES) return fail(H2V_E_DEVICE, "internal: a grouped plan's register file does not fit LDS");
+        HIPCHK(hipFuncSetAttribute((const void *)k_grp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds[t]));
+        const GroupCombinerArgs ca = {g.recs, g.comb[t], g.n_groups, m->proofs.p, f.d_off, m->inst.p, m->ci.p, w->scalars, (uint32_t *)w->status};
+        hipLaunchKernelGGL(k_grp, dim3(g.blocks_comb[t]), dim3(64), g.lds[t], pm, ca);
+    }
+    HIPCHK(hipEventRecord(ev[1], pm));
+    if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
+    HIPCHK(hipEventRecord(ev[4], pm));
+    RlcWs *r = m->fold;
+    GroupTermsArgs ta = {g.recs, g.terms, g.n_groups, w->scalars, (const uint32_t *)w->status, w->valid, w->valid_sub, w->pts, f.d_perm, {},
+                         r->r_scal, m->fold_rpts, r->l_scal, m->fold_lpts, r->vk_part, u.pool.good, u.pool.status};
+    for (int q = 0; q < 8; q++) ta.seed[q] = f.seed[q];
+    hipLaunchKernelGGL(k_mixed_terms_grouped, dim3(g.blocks_terms), dim3(64), 0, pm, ta);
+    HIPCHK(hipEventRecord(ev[5], pm));
+    HIPCHK(hipEventRecord(ev[6], pm));
+    HIPCHK(hipGetLastError());
+    return H2V_OK;
+}
 // H2V_MIXED_FOLD_MSM, the tail, behind every sub-batch of the call: the VK-base terms of the foldable plans (k_mixed_vk_sum), one
 // pair of terms per proof of the other plans out of the call's pool of pairs (k_mixed_pair_terms), then R over the term pool
 // (255-bit scalars, GLV) and L over the n call positions (128-bit) side by side in the six bucket-MSM launches, and ONE
@@ -3394,9 +3477,11 @@ static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
 // lay: H2V_MIXED_FOLD_MSM - the layout of the call's term pool (fold_layout over this workspace's chunk size) - or NULL
 static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
                      uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay = nullptr,
-                     uint32_t *agg_parts = nullptr /* h2v_aggregate_mixed (with lay): the tail exports its sums to part 0, accept = included[] */) {
+                     uint32_t *agg_parts = nullptr /* h2v_aggregate_mixed (with lay): the tail exports its sums to part 0, accept = included[] */,
+                     const MixedGroupPlan *grp = nullptr /* H2V_MIXED_GROUPED (with lay, whose block sums follow the grouped ranges) */) {
     const uint32_t n = pt.n;
     int rc;
+    if (grp && (!lay || grp->sp.chunk != lay->chunk)) return fail(H2V_E_DEVICE, "internal: grouped call without its fold layout");
     if (w->n_lanes && (rc = co_flush(w))) return rc;       // (calls start in submission order: the open groups of coalesced calls first)
     if ((rc = mixed_ensure(w, pt))) return rc;
     if (rlc && (rc = rlc_stats_ensure(w))) return rc;
@@ -3407,7 +3492,17 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     const size_t o_off = 0, o_isrc = o_off + up16(((size_t)n + 1) * 8), o_idst = o_isrc + up16((size_t)n * 8), o_perm = o_idst + up16((size_t)n * 8),
                  o_cap = o_perm + up16((size_t)n * 4), o_ilen = o_cap + up16((size_t)n * 4), o_csrc = o_ilen + up16((size_t)n * 4),
                  o_cdst = o_csrc + up16((size_t)n * 4), o_fold = o_cdst + up16((size_t)n * 4),
-                 need = o_fold + (lay ? up16((size_t)lay->n_foldable * sizeof(H2vFoldPlan)) : 0);
+                 o_grp = o_fold + (lay ? up16((size_t)lay->n_foldable * sizeof(H2vFoldPlan)) : 0);
+    // (grouped: per range its group records and its four prefix arrays)
+    std::vector<h2vmixed::GroupTables> gt(grp ? h2vmixed::group_ranges(grp->sp) : 0u);
+    size_t need = o_grp;
+    for (size_t c = 0; c < gt.size(); c++) {
+        uint32_t g0, g1;
+        h2vmixed::group_range(grp->sp, (uint32_t)c, g0, g1);
+        std::string err;
+        if (!h2vmixed::group_tables(grp->sp, grp->shapes.data(), pt, *lay, g0, g1, m->fold_cap_terms, m->fold_cap_parts, gt[c], &err)) return fail(H2V_E_DEVICE, err);
+        need += up16(gt[c].rec.size() * sizeof(H2vGroupRec)) + 4 * up16((gt[c].rec.size() + 1) * 4);
+    }
     const int si = (int)(m->next++ % MixedWs::SLOTS);
     MixedWs::Slot &sl = m->slot[si];
     if (sl.used) { HIPCHK(hipEventSynchronize(sl.done)); sl.used = false; }      // (the call that took this block last: its copy and its kernels are done)
@@ -3431,6 +3526,21 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
             if (lay->foldable[k])
                 *fp++ = H2vFoldPlan{plans[k]->d.vk_bases, plans[k]->d.terms, plans[k]->n_var, plans[k]->n_fix, lay->fix_base[k], lay->n_blocks[k], lay->vk_base[k], 0u, lay->part_base[k]};
     }
+    std::vector<MixedGroupRange> ranges(gt.size());
+    {
+        size_t o = o_grp;
+        auto put = [&](const void *src, size_t bytes) { memcpy(sl.h + o, src, bytes); const uint8_t *d = sl.d + o; o += up16(bytes); return d; };
+        for (size_t c = 0; c < gt.size(); c++) {
+            const h2vmixed::GroupTables &t = gt[c];
+            MixedGroupRange &r = ranges[c];
+            const uint32_t ng = (uint32_t)t.rec.size();
+            r.recs = (const H2vGroupRec *)put(t.rec.data(), (size_t)ng * sizeof(H2vGroupRec));
+            for (int q = 0; q < 2; q++) { r.comb[q] = (const uint32_t *)put(t.comb[q].data(), ((size_t)ng + 1) * 4); r.blocks_comb[q] = t.comb[q].back(); r.lds[q] = t.lds[q]; }
+            r.dec = (const uint32_t *)put(t.dec.data(), ((size_t)ng + 1) * 4); r.units = t.dec.back();
+            r.terms = (const uint32_t *)put(t.terms.data(), ((size_t)ng + 1) * 4); r.blocks_terms = t.terms.back();
+            r.n_groups = ng; r.n = t.n;
+        }
+    }
     if (m->last >= 0 && m->last != si && m->slot[m->last].used) HIPCHK(hipStreamWaitEvent(st, m->slot[m->last].done, 0));   // (the staging is the last call's until then)
     HIPCHK(hipMemcpyAsync(sl.d, sl.h, need, hipMemcpyHostToDevice, st));
     sl.used = true; m->last = si;
@@ -3449,10 +3559,23 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     if (hipGetLastError() != hipSuccess) return finish(fail(H2V_E_DEVICE, "launch of the gather kernels failed"));
     const h2v_plan *p0 = nullptr;          // any plan of the call: the tail reads nothing of it but the SRS's line tables
     uint32_t used_plans = 0;
-    for (uint32_t k = 0; k < pt.n_plans; k++) if (pt.count[k]) { if (!p0) p0 = plans[k]; used_plans++; }
+    // (own: the plan runs a sub-batch of its own - every plan with proofs, but for the groupable ones of a grouped call, which
+    //  share ONE unit and one record; used_plans: the records the call takes before its tail's)
+    auto own = [&](uint32_t k) { return pt.count[k] && !(grp && grp->sp.groupable[k]); };
+    const uint32_t G = grp ? grp->sp.total : 0u;
+    for (uint32_t k = 0; k < pt.n_plans; k++) if (pt.count[k]) { if (!p0) p0 = plans[k]; if (own(k)) used_plans++; }
+    if (G) used_plans++;
     const MixedPool pool = {m->pool, m->good, m->ones, m->status};
     MixedFold fc = {m, lay, &pt, plans, (const H2vFoldPlan *)(sl.d + o_fold), d_perm, {}};
     for (int q = 0; q < 8; q++) fc.seed[q] = seed ? seed[q] : 0;
+    fc.grp = grp; fc.ranges = std::move(ranges); fc.d_off = d_off;
+    Unit group{UnitKind::MIXED_GROUP, p0, G};
+    group.fold = &fc; group.pool = pool;
+    // More than RING records in one pass (the second pass of a grouped call of more than 64 plans with proofs): the sub-batches
+    // run in slices of at most SLICE plans, every slice joined before the next one starts, so that no record's slot is taken again
+    // while its kernels are in flight; the ONE tail stays the call's last record.
+    constexpr uint32_t SLICE = 62;
+    const bool sliced = used_plans > H2V_MIXED_MAX_PLANS;
     // plan k's sub-batch out of the grouped staging, and the tail over the whole pool
     auto sub_unit = [&](uint32_t k) {
         const H2vDevPlan &d = plans[k]->d;
@@ -3470,13 +3593,15 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     for (int q = 0; q < 8; q++) tail.seed[q] = seed ? seed[q] : 0;
     if (!w->n_lanes) {
         // an ordinary workspace: the sub-batches one after the other on `st`, then the tail
+        // (one stream: a slice is joined by construction)
+        if (G && (rc = run_unit(group, w, st))) return finish(rc);
         for (uint32_t k = 0; k < pt.n_plans; k++)
-            if (pt.count[k] && (rc = run_unit(sub_unit(k), w, st))) return finish(rc);
+            if (own(k) && (rc = run_unit(sub_unit(k), w, st))) return finish(rc);
         return finish(run_unit(tail, w, st));
     }
     // ---- laned: every plan's sub-batch in chunks through the lanes, nothing joined in between
-    uint32_t total_chunks = 0;
-    for (uint32_t k = 0; k < pt.n_plans; k++) total_chunks += n_chunks(pt.count[k], w->chunk);
+    uint32_t total_chunks = n_chunks(G, w->chunk);
+    for (uint32_t k = 0; k < pt.n_plans; k++) if (own(k)) total_chunks += n_chunks(pt.count[k], w->chunk);
     // (the sub-batches of all plans are in flight together: what they may assume is the call's chunks, not one plan's)
     const uint32_t sub_hint = call_hint(w, total_chunks > w->n_lanes, total_chunks);
     tail.fail_ctr = w->rec_fail ? w->rec_fail + (w->calls + used_plans) % h2v_workspace::RING : nullptr;   // the tail's record: the call's last
@@ -3484,8 +3609,21 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
     if (rlc && hipMemsetAsync(tail.fail_ctr, 0, 4, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "memset failed"));
     if (hipEventRecord(w->ev_fork, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
     bool used_lane[h2v_workspace::MAXL] = {};
+    if (G) {                 // the groupable plans: ONE unit over the grouped positions, one record
+        int stream_mode = 1;
+        const uint32_t L = laned_depth(w, G, false, &stream_mode);
+        rec_laned(w, h2v_workspace::PREPARE, L, G, w->chunk);
+        if ((rc = run_chunks(w, group, L, w->chunk, {sub_hint, stream_mode}, [&](uint32_t l, hipStream_t) { used_lane[l] = true; return (int)H2V_OK; })))
+            return finish(rc);
+    }
+    uint32_t in_slice = 0;
     for (uint32_t k = 0; k < pt.n_plans; k++) {
-        if (!pt.count[k]) continue;                                  // (a listed plan without a proof costs nothing)
+        if (!own(k)) continue;                                       // (a listed plan without a proof costs nothing)
+        if (sliced && in_slice++ == SLICE) {                         // the next slice starts behind the whole of this one
+            if ((rc = lanes_join(w, st))) return finish(rc);
+            if (hipEventRecord(w->ev_fork, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
+            in_slice = 1;
+        }
         int stream_mode = 1;
         const uint32_t L = laned_depth(w, pt.count[k], false, &stream_mode);
         rec_laned(w, h2v_workspace::PREPARE, L, pt.count[k], w->chunk);
@@ -3521,9 +3659,14 @@ static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt
 // argument checks shared by the two forms; on success *pt is the partition and *n_used the number of listed plans with proofs
 static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, const uint8_t *accept, uint32_t flags, h2vmixed::Partition *pt) {
     if (!plans || !b || !accept) return fail(H2V_E_ARG, "null argument");
-    if (n_plans > H2V_MIXED_MAX_PLANS) return fail(H2V_E_LIMIT, "at most " + std::to_string(H2V_MIXED_MAX_PLANS) + " plans in one mixed call (" + std::to_string(n_plans) + " listed)");
-    if (flags & ~(H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM)) return fail(H2V_E_ARG, "unknown flag");
+    const uint32_t max_plans = (flags & H2V_MIXED_GROUPED) ? H2V_MIXED_GROUPED_MAX_PLANS : H2V_MIXED_MAX_PLANS;
+    if (n_plans > max_plans)
+        return fail(H2V_E_LIMIT, "at most " + std::to_string(max_plans) + " plans in one mixed call" + ((flags & H2V_MIXED_GROUPED) ? " with H2V_MIXED_GROUPED (" : " (") +
+                                     std::to_string(n_plans) + " listed)");
+    if (flags & ~(H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | H2V_MIXED_GROUPED)) return fail(H2V_E_ARG, "unknown flag");
     if ((flags & H2V_MIXED_FOLD_MSM) && !(flags & H2V_MIXED_RLC)) return fail(H2V_E_ARG, "H2V_MIXED_FOLD_MSM is valid only together with H2V_MIXED_RLC");
+    if ((flags & H2V_MIXED_GROUPED) && (flags & (H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM)) != (H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM))
+        return fail(H2V_E_ARG, "H2V_MIXED_GROUPED is valid only together with H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM");
     if (b->n == 0) return H2V_OK;
     if (n_plans == 0) return fail(H2V_E_ARG, "no plan listed");
     if ((flags & H2V_MIXED_RLC) && b->n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 proofs");
@@ -3559,6 +3702,21 @@ static int mixed_fold_layout(const h2v_plan *const *plans, const h2vmixed::Parti
     if (!h2vmixed::fold_layout(shapes.data(), pt.count.data(), pt.n_plans, w->n_lanes ? w->chunk : 0u, *lay, &err)) return fail(H2V_E_LIMIT, err);
     return H2V_OK;
 }
+// H2V_MIXED_GROUPED, on the host before anything is enqueued: which plans are groupable (foldable, register file in LDS), the
+// grouped positions, and the fold layout's block sums re-cut along the ranges of those positions.  The records of a call: one for
+// the grouped part, one per other plan with proofs, the tail's - and the ring holds RING of them: more than
+// H2V_MIXED_GROUPED_MAX_OTHER other plans with proofs is H2V_E_LIMIT.
+static_assert(H2V_MIXED_GROUPED_MAX_OTHER + 2 <= h2v_workspace::RING, "a grouped call's records fit the ring");
+static int mixed_group_layout(const h2v_plan *const *plans, const h2vmixed::Partition &pt, h2vmixed::FoldLayout *lay, MixedGroupPlan *gp) {
+    gp->shapes.resize(pt.n_plans);
+    for (uint32_t k = 0; k < pt.n_plans; k++) gp->shapes[k] = {plans[k]->d, plans[k]->n_var, plans[k]->n_fix, vm_lds_slots(plans[k]->d), rlc_supported(plans[k])};
+    h2vmixed::group_space(gp->shapes.data(), pt.count.data(), pt.n_plans, lay->chunk, gp->sp);
+    if (gp->sp.n_other > H2V_MIXED_GROUPED_MAX_OTHER)
+        return fail(H2V_E_LIMIT, "at most " + std::to_string(H2V_MIXED_GROUPED_MAX_OTHER) + " plans that cannot be grouped (recursive, or with a global register file) may have proofs in one call, this one has " +
+                                     std::to_string(gp->sp.n_other));
+    h2vmixed::group_fold_blocks(gp->sp, gp->shapes.data(), pt.count.data(), *lay);
+    return H2V_OK;
+}
 // One mixed call on `st`.  lay (H2V_MIXED_FOLD_MSM): the fold form first - one bucket MSM and one pairing for the call - and then
 // the HOST decides: the record's verdict word comes down and `st` is synchronised (the one synchronisation of the form; phase-1
 // results no longer exist by then, the lanes have recycled them).  Passed: accept[] / status[] are final.  Failed: the
@@ -3566,9 +3724,9 @@ static int mixed_fold_layout(const h2v_plan *const *plans, const h2vmixed::Parti
 // rejects -, *fold_failed is set and the call's last record is that second pass's.
 static int run_mixed_call(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
                           uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay,
-                          bool *fold_failed) {
+                          bool *fold_failed, const MixedGroupPlan *grp = nullptr) {
     if (!lay) return run_mixed(plans, pt, host_off, in, accept, status_out, w, st, rlc, seed);
-    int rc = run_mixed(plans, pt, host_off, in, accept, status_out, w, st, true, seed, lay);
+    int rc = run_mixed(plans, pt, host_off, in, accept, status_out, w, st, true, seed, lay, nullptr, grp);
     if (rc) return rc;
     uint32_t failed = 0;
     if (verdict_down(w, &failed, st) || hipStreamSynchronize(st) != hipSuccess)
@@ -3593,8 +3751,11 @@ extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_
     h2vmixed::FoldLayout lay;
     const bool fold = (flags & H2V_MIXED_FOLD_MSM) != 0;
     if (fold && (rc = mixed_fold_layout(plans, pt, ws, &lay))) return rc;
+    MixedGroupPlan gp;
+    const bool grouped = (flags & H2V_MIXED_GROUPED) != 0;
+    if (grouped && (rc = mixed_group_layout(plans, pt, &lay, &gp))) return rc;
     const h2v_batch in = {b->n, b->proofs, b->proof_off, b->instances, b->committed};
-    return run_mixed_call(plans, pt, nullptr, in, accept, status, ws, (hipStream_t)stream, rlc, seed, fold ? &lay : nullptr, nullptr);
+    return run_mixed_call(plans, pt, nullptr, in, accept, status, ws, (hipStream_t)stream, rlc, seed, fold ? &lay : nullptr, nullptr, grouped ? &gp : nullptr);
 }
 // Host-buffer form: offsets | instances | committed | proofs go up in one pinned block on the workspace's own stream, the call
 // runs there behind it, and accept[] / status[] / the batch verdict come back before the function returns.
@@ -3627,6 +3788,9 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
     hostcall::ResultBlock R;
     rc = mixed_ws_check(plans, n_plans, n, ws);
     if (rc == H2V_OK && fold) rc = mixed_fold_layout(plans, pt, ws, &lay);
+    MixedGroupPlan gp;
+    const bool grouped = (flags & H2V_MIXED_GROUPED) != 0;
+    if (rc == H2V_OK && grouped) rc = mixed_group_layout(plans, pt, &lay, &gp);
     if (rc == H2V_OK && rlc) rc = rlc_seed(opts, seed);
     if (rc == H2V_OK) rc = mixed_ensure(ws, pt);
     if (rc == H2V_OK) rc = result_ensure(ws, hostcall::Call::MIXED, n, &R, ws->mixed);
@@ -3635,16 +3799,16 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
         rc = stage_batch(&hb, pt.inst_total, (size_t)pt.ci_total * 48, ws, ws->mixed->in, &in, ws->mixed);
     }
     if (rc == H2V_OK) {
-        std::vector<uint64_t> grouped(n + 1);
-        h2vmixed::group_offsets(pt, (const uint64_t *)ws->mixed->in.h_block.p, grouped.data());     // (the packed offsets: rebased)
+        std::vector<uint64_t> goff(n + 1);
+        h2vmixed::group_offsets(pt, (const uint64_t *)ws->mixed->in.h_block.p, goff.data());     // (the packed offsets: rebased)
         uint8_t *const d = ws->res.p, *d_accept = d + R.accept.off;
         uint32_t *d_status = (uint32_t *)(d + R.status.off);
         if (agg_pair) {
             AggSlot as{};
-            if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = run_mixed(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, true, seed, &lay, as.parts);
+            if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = run_mixed(plans, pt, goff.data(), in, d_accept, d_status, ws, ws->hs, true, seed, &lay, as.parts, grouped ? &gp : nullptr);
             if (rc == H2V_OK) rc = agg_export(ws, as, 1, d + R.pairs.off, ws->hs);
             if (rc == H2V_OK) rc = agg_info_fill(info, seed, 0, 1, lay.n_r);
-        } else rc = run_mixed_call(plans, pt, grouped.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed);
+        } else rc = run_mixed_call(plans, pt, goff.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed, grouped ? &gp : nullptr);
         rc = host_call_tail(ws, rc, {{agg_pair, R.pairs, "the pair"}, {accept, R.accept, "accept[]"}, {status, R.status, "the status words"}},
                             rlc && !agg_pair, fell_back, "mixed-call", fold_failed);
     }
@@ -3710,8 +3874,9 @@ static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint3
     return H2V_OK;
 }
 static void agg_pair_inf(uint8_t pair[96]) { memset(pair, 0, 96); pair[0] = 0xc0; pair[48] = 0xc0; }
-static int agg_flags(const h2v_rlc_opts *o) {
-    if (o && (o->flags & ~(H2V_RLC_SEED_GIVEN | H2V_RLC_ONE_STREAM | H2V_RLC_FOLD_PAIRS))) return fail(H2V_E_ARG, "unknown flag in h2v_rlc_opts.flags");
+// (mixed: h2v_aggregate_mixed(_device), the one call that knows H2V_RLC_GROUPED)
+static int agg_flags(const h2v_rlc_opts *o, bool mixed = false) {
+    if (o && (o->flags & ~(H2V_RLC_SEED_GIVEN | H2V_RLC_ONE_STREAM | H2V_RLC_FOLD_PAIRS | (mixed ? H2V_RLC_GROUPED : 0u)))) return fail(H2V_E_ARG, "unknown flag in h2v_rlc_opts.flags");
     return H2V_OK;
 }
 // the argument rules of the single-key forms that need no device
@@ -3793,9 +3958,10 @@ extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t
                                           uint32_t *status, h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
     if (!pair) return fail(H2V_E_ARG, "null argument: pair");
     if (b && b->n == 0 && !included) included = pair;      // (nothing to write; mixed_args wants a pointer)
-    if (int rca = agg_flags(opts)) return rca;
+    if (int rca = agg_flags(opts, true)) return rca;
+    const uint32_t mflags = H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | (opts && (opts->flags & H2V_RLC_GROUPED) ? H2V_MIXED_GROUPED : 0u);
     h2vmixed::Partition pt;
-    int rc = mixed_args(plans, n_plans, b, included, H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM, &pt);
+    int rc = mixed_args(plans, n_plans, b, included, mflags, &pt);
     if (rc) return rc;
     if ((uintptr_t)pair & 3) return fail(H2V_E_ARG, "pair must be 4-byte aligned");
     if (!ws) return fail(H2V_E_ARG, "the device form needs a workspace (h2v_workspace_create_multi over the listed plans)");
@@ -3814,28 +3980,32 @@ extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t
     }
     h2vmixed::FoldLayout lay;
     if ((rc = mixed_fold_layout(plans, pt, ws, &lay))) return rc;
+    MixedGroupPlan gp;
+    const bool grouped = (mflags & H2V_MIXED_GROUPED) != 0;
+    if (grouped && (rc = mixed_group_layout(plans, pt, &lay, &gp))) return rc;
     agg_info_fill(info, seed, 0, 1, lay.n_r);
     AggSlot as{};
     if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
     const h2v_batch in = {b->n, b->proofs, b->proof_off, b->instances, b->committed};
     // (run_mixed, not run_mixed_call: no verdict comes down, the stream is not synchronised and nothing runs a second time)
-    if ((rc = run_mixed(plans, pt, nullptr, in, included, status, ws, (hipStream_t)stream, true, seed, &lay, as.parts))) return rc;
+    if ((rc = run_mixed(plans, pt, nullptr, in, included, status, ws, (hipStream_t)stream, true, seed, &lay, as.parts, grouped ? &gp : nullptr))) return rc;
     return agg_export(ws, as, 1, pair, (hipStream_t)stream);
 }
 extern "C" int h2v_aggregate_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t pair[96], uint8_t *included,
                                    uint32_t *status, h2v_workspace *ws, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
     if (!pair) return fail(H2V_E_ARG, "null argument: pair");
-    if (int rca = agg_flags(opts)) return rca;
+    if (int rca = agg_flags(opts, true)) return rca;
+    const uint32_t mflags = H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | (opts && (opts->flags & H2V_RLC_GROUPED) ? H2V_MIXED_GROUPED : 0u);
     if (b && b->n == 0) {      // (inf, inf) without a device; the argument rules still hold
         h2vmixed::Partition pt;
-        if (int rc = mixed_args(plans, n_plans, b, pair, H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM, &pt)) return rc;
+        if (int rc = mixed_args(plans, n_plans, b, pair, mflags, &pt)) return rc;
         uint32_t seed[8] = {};
         if (int rc = rlc_seed(opts, seed)) return rc;
         agg_info_fill(info, seed, 0, 1, 0);
         agg_pair_inf(pair);
         return H2V_OK;
     }
-    return mixed_host(plans, n_plans, b, included, status, ws, H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM, opts, nullptr, pair, info);
+    return mixed_host(plans, n_plans, b, included, status, ws, mflags, opts, nullptr, pair, info);
 }
 
 // After the stream of an RLC call has been synchronised: did the batch check pass (1) or did the per-proof kernels run (0)?

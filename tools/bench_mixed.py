@@ -16,8 +16,17 @@ is CPU work).  Writes one JSON line per (shape, mode) and, with --out, the whole
                 synchronises the caller's stream once per call (the verdict comes back to the host).
 The three routes alternate (c), (a), (b), `--runs` each, in this one process; the fold form gains on a shape only when its
 slowest run beats the fastest run of (a) AND of (b), and loses when its fastest run is behind the slowest of either.
+--fold --grouped measures H2V_MIXED_GROUPED (phase 1 of every key in one launch per kernel), batch-accept mode, all-accepting batches:
+  (a) grouped:  the fold call with H2V_MIXED_GROUPED;
+  (b) fold:     the same call without it (the parent's route, same build) - not for shapes of more than 64 keys, which it cannot take;
+  (c) per key:  one h2v_verify_batch_rlc call per key and step (deferred joins, one caller stream).
+Shapes sixteen (16 x 64), sixtyfour (64 keys x 16), twofiftysix (256 keys x 4: (a) and (c) only), two (2 x 2048); every shape is
+warmed, the routes alternate (a), (b), (c), `--runs` each.  A gain or a loss of (a) over a route is claimed only when its slowest run
+is ahead of that route's fastest (behind: its fastest and that route's slowest).  Also records, per shape, the own durations of
+the grouped unit's three kernels in the last call (h2v_workspace_timings of the grouped part's record).
 usage: bench_mixed.py [--shapes two,sixteen] [--runs 5] [--steps 20] [--cache DIR] [--out profiles/mixed_keys.json]
-       bench_mixed.py --fold [...] [--out profiles/mixed_fold.json]"""
+       bench_mixed.py --fold [...] [--out profiles/mixed_fold.json]
+       bench_mixed.py --fold --grouped [--shapes sixteen,sixtyfour,twofiftysix,two] [...] [--out profiles/mixed_grouped.json]"""
 import argparse
 import json
 import os
@@ -34,6 +43,10 @@ SHAPES = {
     "two": [("lookup_table", None, 2048), ("atms_with_lookups", None, 2048)],
     "sixteen": [(name, 0x4d580000 + 16 * k + q, 64) for k, name in enumerate(("simple_mul", "lookup_table", "trashcan_mix", "atms_with_lookups"))
                 for q in range(4)],
+    "sixtyfour": [(name, 0x4d590000 + 64 * k + q, 16) for k, name in enumerate(("simple_mul", "lookup_table", "trashcan_mix", "atms_with_lookups"))
+                  for q in range(16)],
+    "twofiftysix": [(name, 0x4d5a0000 + 256 * k + q, 4) for k, name in enumerate(("simple_mul", "lookup_table", "trashcan_mix", "atms_with_lookups"))
+                    for q in range(64)],
 }
 
 
@@ -149,6 +162,96 @@ def run_shape(shape, runs, steps, cache, fold=False):
     return results
 
 
+def run_grouped(shape, runs, steps, cache):
+    """routes (a) grouped, (b) fold, (c) per key on one shape, batch-accept mode"""
+    import torch
+    from plutus_halo2_verifier_gen_amd import backend
+    keys = forged(shape, cache)
+    dev = torch.device("cuda", 0)
+    plans = [backend.DevicePlan(pl.to_bytes(), 0) for _vk, pl, _b in keys]
+    t = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) if b else None
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    per_key = []
+    for _vk, _pl, b in keys:
+        per_key.append((b.n, t(b.proofs), torch.tensor(b.proof_off, dtype=torch.int64, device=dev), t(b.instances), t(b.committed),
+                        torch.zeros(b.n, dtype=torch.uint8, device=dev), torch.zeros(b.n, dtype=torch.int32, device=dev)))
+    order = [(k, j) for k, (_vk, _pl, b) in enumerate(keys) for j in range(b.n)]
+    random.Random(5).shuffle(order)
+    proofs, inst, ci, off = [], [], [], [0]
+    for k, j in order:
+        vk, _pl, b = keys[k]
+        proofs.append(b.proof(j))
+        off.append(off[-1] + len(proofs[-1]))
+        inst.append(b.instances[32 * vk.n_public_inputs * j:32 * vk.n_public_inputs * (j + 1)])
+        if b.committed is not None:
+            ci.append(b.ci(j))
+    n = len(order)
+    plan_of = [k for k, _ in order]
+    m_in = (t(b"".join(proofs)), torch.tensor(off, dtype=torch.int64, device=dev), t(b"".join(inst)), t(b"".join(ci)))
+    m_acc = torch.zeros(n, dtype=torch.uint8, device=dev)
+    m_st = torch.zeros(n, dtype=torch.int32, device=dev)
+    cs = torch.cuda.Stream(device=dev).cuda_stream
+    seed = bytes(range(32))
+    with_fold = len(keys) <= backend.MIXED_MAX_PLANS
+    ws = {"grouped": backend.Workspace.multi(plans, n), "per_key": backend.Workspace.multi(plans, n)}
+    if with_fold:
+        ws["fold"] = backend.Workspace.multi(plans, n)
+    ws["per_key"].defer_joins(True)
+
+    def mixed_step(route):
+        backend.verify_mixed_device(plans, plan_of, n, *[ptr(x) for x in m_in], m_acc.data_ptr(), m_st.data_ptr(), ws=ws[route], stream=cs,
+                                    mode="rlc", seed=seed, fold_msm=True, grouped=route == "grouped")
+
+    def per_key_step():
+        for dp, (cnt, p, o, i, c, acc, st) in zip(plans, per_key):
+            dp.verify_batch_rlc_device(cnt, ptr(p), ptr(o), ptr(i), ptr(c), acc.data_ptr(), st.data_ptr(), ws=ws["per_key"], stream=cs, seed=seed)
+
+    steps_of = {"grouped": lambda: mixed_step("grouped"), "per_key": per_key_step}
+    if with_fold:
+        steps_of["fold"] = lambda: mixed_step("fold")
+
+    def run(route, k_steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(k_steps):
+            steps_of[route]()
+        ws[route].join(cs)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / k_steps
+
+    routes = [r for r in ("grouped", "fold", "per_key") if r in steps_of]
+    for route in routes:                                       # warm-up: first uses allocate; every route must accept everything
+        m_acc.zero_()
+        run(route, 3)
+        if route == "per_key":
+            assert all(x[5].cpu().tolist() == [1] * x[0] for x in per_key), "a per-key call rejects a forged proof"
+        else:
+            assert m_acc.cpu().tolist() == [1] * n, "the %s route rejects a forged proof" % route
+            assert ws[route].rlc_result(timings=False)[0], "the %s route's check failed on forged proofs: the runs would time the fall-back" % route
+    ms = {route: [] for route in routes}
+    for _ in range(runs):
+        for route in routes:
+            ms[route].append(run(route, steps))
+    med = lambda v: sorted(v)[len(v) // 2]
+    r = {"shape": shape, "keys": len(keys), "proofs": n, "mode": "rlc", "steps_per_run": steps}
+    for route in routes:
+        r[route + "_ms_per_step"] = [round(x, 4) for x in sorted(ms[route])]
+        r[route + "_median_ms"] = round(med(ms[route]), 4)
+    for other in routes[1:]:
+        r["grouped_gain_over_" + other] = max(ms["grouped"]) < min(ms[other])
+        r["grouped_loss_to_" + other] = min(ms["grouped"]) > max(ms[other])
+    # the grouped unit's own kernels in the last grouped call: its record is the one before the tail's (every key here is groupable)
+    run("grouped", 1)
+    tm = ws["grouped"].timings(1)
+    r["grouped_kernels_ms"] = {"transcript_combiner": round(tm.transcript_combiner_ms, 4), "g1_decompress": round(tm.g1_decompress_ms, 4),
+                               "mixed_terms": round(tm.g1_msm_ms, 4)}
+    r["msm_terms"] = ws["grouped"].rlc_result(timings=True)[1].msm_terms
+    print(json.dumps(r), flush=True)
+    for w in ws.values():
+        w.close()
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="two,sixteen")
@@ -158,7 +261,10 @@ def main():
     ap.add_argument("--forge-only", action="store_true", help="forge (and cache) the batches, then stop: no GPU needed")
     ap.add_argument("--out", default=None)
     ap.add_argument("--fold", action="store_true", help="batch-accept mode only, with route (c): the call with H2V_MIXED_FOLD_MSM")
+    ap.add_argument("--grouped", action="store_true", help="with --fold: H2V_MIXED_GROUPED against the fold form and the per-key calls")
     args = ap.parse_args()
+    if args.grouped and not args.fold:
+        ap.error("--grouped goes with --fold")
     if args.runs < 5 and not args.forge_only:
         ap.error("at least five runs of each route")
     if args.forge_only:
@@ -168,7 +274,7 @@ def main():
     import torch
     results = []
     for shape in args.shapes.split(","):
-        results += run_shape(shape, args.runs, args.steps, args.cache, args.fold)
+        results += run_grouped(shape, args.runs, args.steps, args.cache) if args.grouped else run_shape(shape, args.runs, args.steps, args.cache, args.fold)
     if args.out:
         with open(args.out, "w") as f:
             json.dump({"tool": "tools/bench_mixed.py", "device": torch.cuda.get_device_name(0), "runs": args.runs, "cases": results}, f, indent=1)
