@@ -25,6 +25,7 @@
 #include "h2v_msm_shape.hpp"
 #include "h2v_pairing_engine.hpp"
 #include "h2v_hostcall_layout.hpp"
+#include "h2v_mixed_tables.hpp"
 #include "h2v_plancc.hpp"
 
 static thread_local std::string g_err;
@@ -1473,6 +1474,10 @@ struct Unit {
         return c;
     }
 };
+// the eight words of a call's seed; src == NULL: zeros
+static void copy_seed(uint32_t dst[8], const uint32_t *src) {
+    for (int q = 0; q < 8; q++) dst[q] = src ? src[q] : 0;
+}
 static Unit unit_of_batch(UnitKind kind, const h2v_plan *p, const h2v_batch *b, uint8_t *accept, uint32_t *status) {
     Unit u{kind, p, (uint32_t)b->n};
     u.proofs = b->proofs; u.off = b->proof_off; u.inst = b->instances; u.ci = b->committed;
@@ -2004,7 +2009,7 @@ static int coalesce_call(const Unit &u, h2v_workspace *w, hipStream_t st) {
         Coalesce &c = *w->co[l];
         c.plan = p; c.plan_gen = p->gen; c.count = 0; c.parts.clear();
         c.rlc = rlc;
-        for (int k = 0; k < 8; k++) c.seed[k] = rlc ? u.seed[k] : 0;
+        copy_seed(c.seed, rlc ? u.seed : nullptr);
         HIPCHK(hipMemsetAsync(c.fail, 0, 16, w->lane_st[l]));   // verdict word and off[0] = 0: behind the previous group's flush on this stream
         w->co_open.push_back(l);
         found = (int)l;
@@ -2927,6 +2932,45 @@ static int agg_chunk(const Unit &u, RlcWs *r, h2v_workspace *w, CallRec &rec, hi
     HIPCHK(hipEventRecord(rec.ev[9], st));
     return H2V_OK;
 }
+// PHASE 1 of a batch-accept unit (run_rlc, run_mixed_terms, run_mixed_group): the decompression on the workspace's side stream,
+// forked from `st` and joined back into it, the combiner beside it on `st`; one_stream (each caller's own rule): both on `st`,
+// the decompression first.  dec_ev / comb_ev: the record's two events around each.  decompress(stream) / combine(stream) enqueue
+// the launch(es) and return a code.
+template <class Dec, class Comb>
+static int phase1(h2v_workspace *w, hipStream_t st, bool one_stream, const hipEvent_t *dec_ev, const hipEvent_t *comb_ev, Dec &&decompress, Comb &&combine) {
+    if (!one_stream)
+        if (int rc = ws_streams(w, false, true)) return rc;
+    hipStream_t ps = one_stream ? st : w->pside;
+    if (!one_stream) {
+        HIPCHK(hipEventRecord(w->ev_fork, st));
+        HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
+    }
+    HIPCHK(hipEventRecord(dec_ev[0], ps));
+    if (int rc = decompress(ps)) return rc;
+    HIPCHK(hipEventRecord(dec_ev[1], ps));
+    HIPCHK(hipEventRecord(w->ev_join, ps));
+    HIPCHK(hipEventRecord(comb_ev[0], st));
+    if (int rc = combine(st)) return rc;
+    HIPCHK(hipEventRecord(comb_ev[1], st));
+    if (!one_stream) HIPCHK(hipStreamWaitEvent(st, w->ev_join, 0));
+    return H2V_OK;
+}
+// THE SUMS of a batch check, R and L side by side in the same six bucket-MSM launches (pip_launch; the record's ev[5..8]), into
+// r->sums (R, then L at + 36).  A sum: n terms of scalars scal (halves = 2: 255 bits, GLV; 1: below 2^128), term t the point
+// pidx[t] (NULL: t) of pool0 (n_pool0 points) and, behind those, of pool1.  The record keeps R's shape for the timings.
+struct SumTerms { uint32_t n, halves; const uint32_t *scal, *pidx, *pool0; uint32_t n_pool0; const uint32_t *pool1; };
+static int launch_sums(RlcWs *r, const SumTerms &R, const SumTerms &L, CallRec &rec, hipStream_t st) {
+    PipArgs pa[2] = {};
+    const SumTerms *s[2] = {&R, &L};
+    for (int q = 0; q < 2; q++) {
+        pa[q].n = s[q]->n; pa[q].halves = s[q]->halves; pa[q].scal = s[q]->scal; pa[q].pidx = s[q]->pidx;
+        pa[q].pool0 = s[q]->pool0; pa[q].n_pool0 = s[q]->n_pool0; pa[q].pool1 = s[q]->pool1; pa[q].out = r->sums + 36 * q;
+    }
+    const PipWs *pws[2] = {&r->R, &r->L};
+    if (int rc = pip_launch(pws, pa, 2, st, rec.ev + 5)) return rc;   // ev[5..8]
+    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    return H2V_OK;
+}
 // One batch in RLC mode.  Phase 1 as in run_pipeline (the decompression launch builds no window tables), then the batch
 // check; the per-proof MSM + pairing kernels are queued behind it and return at once unless the batch check failed.
 // Events (the record's): [0]/[1] around the decompression, [2]/[3] around the
@@ -2946,39 +2990,23 @@ static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
     // one_stream (h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM, or H2V_OPT_STREAMS = 1): everything on
     // the caller's stream, decompression before the combiner - one stream per batch in flight instead of two
     const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode != 0 : (u.one_stream_opt || w->in_flight_hint >= 3);   // (H2V_OPT_STREAMS, the flag, or the caller's in-flight hint)
-    if (!one_stream && (rc = ws_streams(w, false, true))) return rc;
-    hipStream_t pm = st, ps = one_stream ? st : w->pside;
-    if (!one_stream) {
-        HIPCHK(hipEventRecord(w->ev_fork, st));
-        HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
-    }
-    // phase 1
-    HIPCHK(hipEventRecord(ev[0], ps));
-    if ((rc = launch_decompress(d, n, u.proofs, u.off, u.ci, u.inst, w, nullptr, ps))) return rc;
-    HIPCHK(hipEventRecord(ev[1], ps));
-    HIPCHK(hipEventRecord(w->ev_join, ps));
-    HIPCHK(hipEventRecord(ev[2], pm));
-    rc = launch_vm(d, n, w->stride, u.proofs, u.off, u.inst, u.ci, w->regs, w->scalars, w->status, nullptr, pm);
+    hipStream_t pm = st;
+    rc = phase1(w, st, one_stream, ev + 0, ev + 2,
+                [&](hipStream_t ps) { return launch_decompress(d, n, u.proofs, u.off, u.ci, u.inst, w, nullptr, ps); },
+                [&](hipStream_t s) { return launch_vm(d, n, w->stride, u.proofs, u.off, u.inst, u.ci, w->regs, w->scalars, w->status, nullptr, s); });
     if (rc) return rc;
-    HIPCHK(hipEventRecord(ev[3], pm));
-    if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
     HIPCHK(hipEventRecord(ev[10], pm));
     // the batch check
     RlcArgs ra = {n, p->n_var, p->n_fix, slots, d.pi_point, d.n_terms, d.terms, w->scalars, w->status, w->valid, w->valid_sub, {},
                   r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good};
-    for (int k = 0; k < 8; k++) ra.seed[k] = u.seed[k];
+    copy_seed(ra.seed, u.seed);
     const uint32_t blocks = (n + 63) / 64;
     hipLaunchKernelGGL(k_rlc_prepare, dim3(blocks), dim3(64), 0, pm, ra);
     hipLaunchKernelGGL(k_rlc_vk_sum, dim3((p->n_fix + 63) / 64), dim3(64), 0, pm, ra, blocks);
     HIPCHK(hipEventRecord(ev[4], pm));
     // both sums in the same launches: R = sum r_i er_i (255-bit scalars, GLV) and L = sum r_i pi_i (128-bit scalars)
-    PipArgs pa[2] = {};
-    pa[0].n = n * p->n_var + p->n_fix; pa[0].halves = 2; pa[0].scal = r->r_scal; pa[0].pidx = r->r_idx; pa[0].pool0 = w->pts; pa[0].n_pool0 = n * slots;
-    pa[0].pool1 = d.vk_bases; pa[0].out = r->sums;
-    pa[1].n = n; pa[1].halves = 1; pa[1].scal = r->l_scal; pa[1].pidx = r->l_idx; pa[1].pool0 = w->pts; pa[1].n_pool0 = n * slots; pa[1].pool1 = nullptr; pa[1].out = r->sums + 36;
-    const PipWs *pws[2] = {&r->R, &r->L};
-    if ((rc = pip_launch(pws, pa, 2, pm, ev + 5))) return rc;   // ev[5..8]
-    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    if ((rc = launch_sums(r, {n * p->n_var + p->n_fix, 2, r->r_scal, r->r_idx, w->pts, n * slots, d.vk_bases}, {n, 1, r->l_scal, r->l_idx, w->pts, n * slots, nullptr}, rec, pm)))
+        return rc;
     if (u.agg_parts) {      // an aggregate call stops here: no pairing, no group stage, no per-proof kernels
         if ((rc = agg_chunk(u, r, w, rec, pm))) return rc;
         if (u.status) HIPCHK(hipMemcpyAsync(u.status, w->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
@@ -3022,15 +3050,10 @@ static int pairs_rlc_core(const Unit &u, RlcWs *r, const uint32_t *pool, const u
     int rc;
     if (!good_given) HIPCHK(hipEventRecord(ev[10], st));
     RlcPairArgs ra = {n, status, valid, valid_sub, good_given ? r->good : nullptr, {}, r->r_scal, r->l_idx, r->r_idx, r->good};
-    for (int k = 0; k < 8; k++) ra.seed[k] = u.seed[k];
+    copy_seed(ra.seed, u.seed);
     hipLaunchKernelGGL(k_rlc_pairs_prepare, dim3((n + 63) / 64), dim3(64), 0, st, ra);
     HIPCHK(hipEventRecord(ev[4], st));
-    PipArgs pa[2] = {};
-    pa[0].n = n; pa[0].halves = 1; pa[0].scal = r->r_scal; pa[0].pidx = r->r_idx; pa[0].pool0 = pool; pa[0].n_pool0 = 2 * n; pa[0].pool1 = nullptr; pa[0].out = r->sums;
-    pa[1] = pa[0]; pa[1].pidx = r->l_idx; pa[1].out = r->sums + 36;
-    const PipWs *pws[2] = {&r->R, &r->L};
-    if ((rc = pip_launch(pws, pa, 2, st, ev + 5))) return rc;   // ev[5..8]
-    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    if ((rc = launch_sums(r, {n, 1, r->r_scal, r->r_idx, pool, 2 * n, nullptr}, {n, 1, r->r_scal, r->l_idx, pool, 2 * n, nullptr}, rec, st))) return rc;
     if (u.agg_parts) return agg_chunk(u, r, w, rec, st);      // (an aggregate call: the sums are exported, nothing is checked)
     if ((rc = launch_batch_pairing(u, r, grp_of_pairs(u.p, pool), nullptr, w, rec, st))) return rc;
     HIPCHK(hipGetLastError());
@@ -3200,10 +3223,25 @@ struct MixedGroupPlan {
     h2vmixed::GroupSpace sp;
     std::vector<h2vmixed::GroupShape> shapes;
 };
-struct MixedGroupRange {
+struct MixedGroupRange : mixedtab::RangeInfo {     // the range's counts (h2v_mixed_tables.hpp) and its tables in the device block
     const H2vGroupRec *recs;
     const uint32_t *comb[2], *dec, *terms;
-    uint32_t n_groups, n, blocks_comb[2], units, blocks_terms, lds[2];
+};
+// ONE MIXED CALL: what it verifies, how, and where its results go.  Filled once by its entry point - mixed_args (plans, flags,
+// partition), mixed_layouts, the seed, mixed_call_io (the I/O, and the one place where the combinations are checked) - and
+// read-only from then on.  The second pass after a failed fold check is the same descriptor with fold and grouped cleared.
+struct MixedCall {
+    const h2v_plan *const *plans = nullptr;
+    h2vmixed::Partition pt;
+    bool rlc = false, fold = false, grouped = false;     // H2V_MIXED_RLC, _FOLD_MSM, _GROUPED
+    uint32_t seed[8] = {};                               // of the batch coefficients (rlc)
+    h2vmixed::FoldLayout lay;    // fold: the layout of the call's term pool (fold_layout over the workspace's chunk size)
+    MixedGroupPlan grp;          // grouped: the groupable plans (lay's block sums then follow the grouped ranges)
+    h2v_batch in = {};                                   // the call's device-resident buffers
+    const uint64_t *host_off = nullptr;                  // the grouped proof offsets when the caller's proof_off is known on the host (the host form), else NULL
+    uint8_t *accept = nullptr;
+    uint32_t *status = nullptr;
+    uint32_t *agg_parts = nullptr;                       // h2v_aggregate_mixed: the tail exports its sums to part 0, accept = included[]
 };
 struct MixedFold {
     MixedWs *m;
@@ -3305,20 +3343,11 @@ static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st) {
     CallRec &rec = rec_new(w, h2v_workspace::PREPARE);
     hipEvent_t *ev = rec.ev;
     const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode == 1 : w->in_flight_hint >= 3;
-    if (!one_stream && (rc = ws_streams(w, false, true))) return rc;
-    hipStream_t pm = st, ps = one_stream ? st : w->pside;
-    if (!one_stream) {
-        HIPCHK(hipEventRecord(w->ev_fork, st));
-        HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
-    }
-    HIPCHK(hipEventRecord(ev[2], ps));
-    if ((rc = launch_decompress(d, n, u.proofs, u.off, u.ci, u.inst, w, nullptr, ps))) return rc;
-    HIPCHK(hipEventRecord(ev[3], ps));
-    HIPCHK(hipEventRecord(w->ev_join, ps));
-    HIPCHK(hipEventRecord(ev[0], pm));
-    if ((rc = launch_vm(d, n, w->stride, u.proofs, u.off, u.inst, u.ci, w->regs, w->scalars, w->status, nullptr, pm))) return rc;
-    HIPCHK(hipEventRecord(ev[1], pm));
-    if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
+    hipStream_t pm = st;
+    rc = phase1(w, st, one_stream, ev + 2, ev + 0,
+                [&](hipStream_t ps) { return launch_decompress(d, n, u.proofs, u.off, u.ci, u.inst, w, nullptr, ps); },
+                [&](hipStream_t s) { return launch_vm(d, n, w->stride, u.proofs, u.off, u.inst, u.ci, w->regs, w->scalars, w->status, nullptr, s); });
+    if (rc) return rc;
     HIPCHK(hipEventRecord(ev[4], pm));
     HIPCHK(hipEventRecord(ev[5], pm));
     RlcWs *r = f.m->fold;
@@ -3328,7 +3357,7 @@ static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st) {
         return fail(H2V_E_DEVICE, "internal: a chunk's terms lie outside the call's term pool");
     MixedTermsArgs a = {n, p->n_var, p->n_fix, slots, d.pi_point, d.n_terms, d.terms, w->scalars, w->status, w->valid, w->valid_sub, w->pts, u.pos, {},
                         r->r_scal + t0 * 8, f.m->fold_rpts + t0 * 24, r->l_scal, f.m->fold_lpts, r->vk_part + b0 * 8, u.pool.good, u.pool.status};
-    for (int q = 0; q < 8; q++) a.seed[q] = f.seed[q];
+    copy_seed(a.seed, f.seed);
     hipLaunchKernelGGL(k_mixed_terms, dim3((n + 63) / 64), dim3(64), 0, pm, a);
     HIPCHK(hipEventRecord(ev[6], pm));
     HIPCHK(hipGetLastError());
@@ -3355,39 +3384,33 @@ static int run_mixed_group(const Unit &u, h2v_workspace *w, hipStream_t st) {
     CallRec &rec = rec_new(w, h2v_workspace::PREPARE);
     hipEvent_t *ev = rec.ev;
     const bool one_stream = w->one_stream_mode >= 0 ? w->one_stream_mode == 1 : w->in_flight_hint >= 3;
-    if (!one_stream && (rc = ws_streams(w, false, true))) return rc;
-    hipStream_t pm = st, ps = one_stream ? st : w->pside;
-    if (!one_stream) {
-        HIPCHK(hipEventRecord(w->ev_fork, st));
-        HIPCHK(hipStreamWaitEvent(ps, w->ev_fork, 0));
-    }
+    hipStream_t pm = st;
     MixedWs *m = f.m;
-    HIPCHK(hipEventRecord(ev[2], ps));
-    {
+    auto decompress = [&](hipStream_t ps) -> int {
         const uint32_t units = 2 * g.units, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
         const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
         HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, ps));
         const GroupDecompressArgs da = {g.recs, g.dec, g.n_groups, g.units, m->proofs.p, f.d_off, m->inst.p, m->ci.p, w->pts, w->valid, w->valid_sub, w->dec_ctr};
         hipLaunchKernelGGL(k_g1_decompress_queue_grouped, dim3(blocks), dim3(256), 0, ps, da);
-    }
-    HIPCHK(hipEventRecord(ev[3], ps));
-    HIPCHK(hipEventRecord(w->ev_join, ps));
-    HIPCHK(hipEventRecord(ev[0], pm));
-    for (int t = 0; t < 2; t++) {
-        if (!g.blocks_comb[t]) continue;
-        const auto k_grp = t == (int)H2V_TR_BLAKE2B_512 ? k_transcript_combiner_grouped_b512 : k_transcript_combiner_grouped;
-        if (g.lds[t] > H2V_VM_LDS_BYTES) return fail(H2V_E_DEVICE, "internal: a grouped plan's register file does not fit LDS");
-        HIPCHK(hipFuncSetAttribute((const void *)k_grp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds[t]));
-        const GroupCombinerArgs ca = {g.recs, g.comb[t], g.n_groups, m->proofs.p, f.d_off, m->inst.p, m->ci.p, w->scalars, (uint32_t *)w->status};
-        hipLaunchKernelGGL(k_grp, dim3(g.blocks_comb[t]), dim3(64), g.lds[t], pm, ca);
-    }
-    HIPCHK(hipEventRecord(ev[1], pm));
-    if (!one_stream) HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
+        return H2V_OK;
+    };
+    auto combine = [&](hipStream_t s) -> int {      // one launch per transcript kind that has proofs in the range
+        for (int t = 0; t < 2; t++) {
+            if (!g.blocks_comb[t]) continue;
+            const auto k_grp = t == (int)H2V_TR_BLAKE2B_512 ? k_transcript_combiner_grouped_b512 : k_transcript_combiner_grouped;
+            if (g.lds[t] > H2V_VM_LDS_BYTES) return fail(H2V_E_DEVICE, "internal: a grouped plan's register file does not fit LDS");
+            HIPCHK(hipFuncSetAttribute((const void *)k_grp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds[t]));
+            const GroupCombinerArgs ca = {g.recs, g.comb[t], g.n_groups, m->proofs.p, f.d_off, m->inst.p, m->ci.p, w->scalars, (uint32_t *)w->status};
+            hipLaunchKernelGGL(k_grp, dim3(g.blocks_comb[t]), dim3(64), g.lds[t], s, ca);
+        }
+        return H2V_OK;
+    };
+    if ((rc = phase1(w, st, one_stream, ev + 2, ev + 0, decompress, combine))) return rc;
     HIPCHK(hipEventRecord(ev[4], pm));
     RlcWs *r = m->fold;
     GroupTermsArgs ta = {g.recs, g.terms, g.n_groups, w->scalars, (const uint32_t *)w->status, w->valid, w->valid_sub, w->pts, f.d_perm, {},
                          r->r_scal, m->fold_rpts, r->l_scal, m->fold_lpts, r->vk_part, u.pool.good, u.pool.status};
-    for (int q = 0; q < 8; q++) ta.seed[q] = f.seed[q];
+    copy_seed(ta.seed, f.seed);
     hipLaunchKernelGGL(k_mixed_terms_grouped, dim3(g.blocks_terms), dim3(64), 0, pm, ta);
     HIPCHK(hipEventRecord(ev[5], pm));
     HIPCHK(hipEventRecord(ev[6], pm));
@@ -3419,17 +3442,11 @@ static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st) 
     for (uint32_t k = 0; k < lay.n_plans; k++) {
         if (!f.pt->count[k] || lay.foldable[k]) continue;
         MixedPairTermsArgs pa = {f.pt->count[k], lay.pair_base[k], f.d_perm + f.pt->base[k], m->pool, m->good, {}, r->r_scal, m->fold_rpts, r->l_scal, m->fold_lpts};
-        for (int q = 0; q < 8; q++) pa.seed[q] = f.seed[q];
+        copy_seed(pa.seed, f.seed);
         hipLaunchKernelGGL(k_mixed_pair_terms, dim3((pa.n + 63) / 64), dim3(64), 0, st, pa);
     }
     HIPCHK(hipEventRecord(rec.ev[4], st));
-    PipArgs pa[2] = {};
-    pa[0].n = (uint32_t)lay.n_r; pa[0].halves = 2; pa[0].scal = r->r_scal; pa[0].pidx = nullptr; pa[0].pool0 = m->fold_rpts; pa[0].n_pool0 = (uint32_t)lay.n_r;
-    pa[0].pool1 = nullptr; pa[0].out = r->sums;
-    pa[1].n = n; pa[1].halves = 1; pa[1].scal = r->l_scal; pa[1].pidx = nullptr; pa[1].pool0 = m->fold_lpts; pa[1].n_pool0 = n; pa[1].pool1 = nullptr; pa[1].out = r->sums + 36;
-    const PipWs *pws[2] = {&r->R, &r->L};
-    if ((rc = pip_launch(pws, pa, 2, st, rec.ev + 5))) return rc;   // ev[5..8]
-    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    if ((rc = launch_sums(r, {(uint32_t)lay.n_r, 2, r->r_scal, nullptr, m->fold_rpts, (uint32_t)lay.n_r, nullptr}, {n, 1, r->l_scal, nullptr, m->fold_lpts, n, nullptr}, rec, st))) return rc;
     if (u.agg_parts) rc = agg_chunk(u, r, w, rec, st);
     else rc = launch_batch_pairing(u, r, GrpShape{}, nullptr, w, rec, st, false);
     if (rc) return rc;
@@ -3472,192 +3489,210 @@ static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
     if (u.status) HIPCHK(hipMemcpyAsync(u.status, mp.status, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
-// in: the call's device-resident buffers; host_off: the grouped proof offsets when the caller's proof_off is known on the host
-// (the host form), else NULL
-// lay: H2V_MIXED_FOLD_MSM - the layout of the call's term pool (fold_layout over this workspace's chunk size) - or NULL
-static int run_mixed(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
-                     uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay = nullptr,
-                     uint32_t *agg_parts = nullptr /* h2v_aggregate_mixed (with lay): the tail exports its sums to part 0, accept = included[] */,
-                     const MixedGroupPlan *grp = nullptr /* H2V_MIXED_GROUPED (with lay, whose block sums follow the grouped ranges) */) {
-    const uint32_t n = pt.n;
-    int rc;
-    if (grp && (!lay || grp->sp.chunk != lay->chunk)) return fail(H2V_E_DEVICE, "internal: grouped call without its fold layout");
-    if (w->n_lanes && (rc = co_flush(w))) return rc;       // (calls start in submission order: the open groups of coalesced calls first)
-    if ((rc = mixed_ensure(w, pt))) return rc;
-    if (rlc && (rc = rlc_stats_ensure(w))) return rc;
-    if (lay && (rc = mixed_fold_ensure(w, *lay))) return rc;
+// ---- run_mixed in parts: the tables, the units, the two schedules
+// The next of the four table blocks, once the call that took it last has finished on the device (its copy and its kernels are
+// done), grown to `need` bytes.
+static int mixed_slot(MixedWs *m, size_t need, int *si) {
+    *si = (int)(m->next++ % MixedWs::SLOTS);
+    MixedWs::Slot &sl = m->slot[*si];
+    if (sl.used) { HIPCHK(hipEventSynchronize(sl.done)); sl.used = false; }
+    if (need <= sl.cap) return H2V_OK;
+    if (sl.h) (void)hipHostFree(sl.h);
+    if (sl.d) (void)hipFree(sl.d);
+    sl.h = sl.d = nullptr; sl.cap = 0;
+    const size_t cap = need + need / 4;
+    if (hipHostMalloc((void **)&sl.h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&sl.d, cap) != hipSuccess)
+        return fail(H2V_E_DEVICE, "allocation of the mixed-call tables failed");
+    sl.cap = cap;
+    return H2V_OK;
+}
+// THE TABLES of a call: one pinned block (h2v_mixed_tables.hpp lays it out and packs it), one copy on `st` behind the last call's
+// block - the staging is that call's until then.  On success the block is IN USE: whoever called records sl->done behind the call.
+struct MixedTables {
+    MixedWs::Slot *sl = nullptr;
+    uint64_t *d_off = nullptr;                // the grouped proof offsets (n + 1)
+    H2vMixedTab tab = {};
+    const H2vFoldPlan *d_fold = nullptr;      // fold: lay.n_foldable entries
+    std::vector<MixedGroupRange> ranges;      // grouped: its ranges, in order
+};
+static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, MixedTables &out) {
     MixedWs *m = w->mixed;
-    // ---- the tables: one pinned block, one copy
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_off = 0, o_isrc = o_off + up16(((size_t)n + 1) * 8), o_idst = o_isrc + up16((size_t)n * 8), o_perm = o_idst + up16((size_t)n * 8),
-                 o_cap = o_perm + up16((size_t)n * 4), o_ilen = o_cap + up16((size_t)n * 4), o_csrc = o_ilen + up16((size_t)n * 4),
-                 o_cdst = o_csrc + up16((size_t)n * 4), o_fold = o_cdst + up16((size_t)n * 4),
-                 o_grp = o_fold + (lay ? up16((size_t)lay->n_foldable * sizeof(H2vFoldPlan)) : 0);
-    // (grouped: per range its group records and its four prefix arrays)
-    std::vector<h2vmixed::GroupTables> gt(grp ? h2vmixed::group_ranges(grp->sp) : 0u);
-    size_t need = o_grp;
-    for (size_t c = 0; c < gt.size(); c++) {
+    const h2vmixed::Partition &pt = c.pt;
+    std::vector<h2vmixed::GroupTables> gt(c.grouped ? h2vmixed::group_ranges(c.grp.sp) : 0u);
+    std::vector<uint32_t> n_groups(gt.size());
+    for (size_t q = 0; q < gt.size(); q++) {
         uint32_t g0, g1;
-        h2vmixed::group_range(grp->sp, (uint32_t)c, g0, g1);
+        h2vmixed::group_range(c.grp.sp, (uint32_t)q, g0, g1);
         std::string err;
-        if (!h2vmixed::group_tables(grp->sp, grp->shapes.data(), pt, *lay, g0, g1, m->fold_cap_terms, m->fold_cap_parts, gt[c], &err)) return fail(H2V_E_DEVICE, err);
-        need += up16(gt[c].rec.size() * sizeof(H2vGroupRec)) + 4 * up16((gt[c].rec.size() + 1) * 4);
+        if (!h2vmixed::group_tables(c.grp.sp, c.grp.shapes.data(), pt, c.lay, g0, g1, m->fold_cap_terms, m->fold_cap_parts, gt[q], &err)) return fail(H2V_E_DEVICE, err);
+        n_groups[q] = (uint32_t)gt[q].rec.size();
     }
-    const int si = (int)(m->next++ % MixedWs::SLOTS);
+    const mixedtab::TableBlock B = mixedtab::table_block(pt.n, c.fold ? (size_t)c.lay.n_foldable * sizeof(H2vFoldPlan) : 0, n_groups.data(), n_groups.size());
+    int si;
+    if (int rc = mixed_slot(m, B.extent, &si)) return rc;
     MixedWs::Slot &sl = m->slot[si];
-    if (sl.used) { HIPCHK(hipEventSynchronize(sl.done)); sl.used = false; }      // (the call that took this block last: its copy and its kernels are done)
-    if (need > sl.cap) {
-        if (sl.h) (void)hipHostFree(sl.h);
-        if (sl.d) (void)hipFree(sl.d);
-        sl.h = sl.d = nullptr; sl.cap = 0;
-        const size_t cap = need + need / 4;
-        if (hipHostMalloc((void **)&sl.h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&sl.d, cap) != hipSuccess)
-            return fail(H2V_E_DEVICE, "allocation of the mixed-call tables failed");
-        sl.cap = cap;
-    }
-    if (host_off) memcpy(sl.h + o_off, host_off, ((size_t)n + 1) * 8);
-    memcpy(sl.h + o_isrc, pt.inst_src.data(), (size_t)n * 8); memcpy(sl.h + o_idst, pt.inst_dst.data(), (size_t)n * 8);
-    memcpy(sl.h + o_perm, pt.perm.data(), (size_t)n * 4); memcpy(sl.h + o_cap, pt.len_cap.data(), (size_t)n * 4);
-    memcpy(sl.h + o_ilen, pt.inst_len.data(), (size_t)n * 4); memcpy(sl.h + o_csrc, pt.ci_src.data(), (size_t)n * 4);
-    memcpy(sl.h + o_cdst, pt.ci_dst.data(), (size_t)n * 4);
-    if (lay) {               // what k_mixed_vk_sum reads of the foldable plans, in list order
-        H2vFoldPlan *fp = (H2vFoldPlan *)(sl.h + o_fold);
+    std::vector<mixedtab::RangeInfo> info;
+    mixedtab::pack_tables(sl.h, B, pt, c.host_off, gt, info);
+    if (c.fold) {            // what k_mixed_vk_sum reads of the foldable plans, in list order (device pointers: written here)
+        H2vFoldPlan *fp = (H2vFoldPlan *)(sl.h + B.fold.off);
         for (uint32_t k = 0; k < pt.n_plans; k++)
-            if (lay->foldable[k])
-                *fp++ = H2vFoldPlan{plans[k]->d.vk_bases, plans[k]->d.terms, plans[k]->n_var, plans[k]->n_fix, lay->fix_base[k], lay->n_blocks[k], lay->vk_base[k], 0u, lay->part_base[k]};
-    }
-    std::vector<MixedGroupRange> ranges(gt.size());
-    {
-        size_t o = o_grp;
-        auto put = [&](const void *src, size_t bytes) { memcpy(sl.h + o, src, bytes); const uint8_t *d = sl.d + o; o += up16(bytes); return d; };
-        for (size_t c = 0; c < gt.size(); c++) {
-            const h2vmixed::GroupTables &t = gt[c];
-            MixedGroupRange &r = ranges[c];
-            const uint32_t ng = (uint32_t)t.rec.size();
-            r.recs = (const H2vGroupRec *)put(t.rec.data(), (size_t)ng * sizeof(H2vGroupRec));
-            for (int q = 0; q < 2; q++) { r.comb[q] = (const uint32_t *)put(t.comb[q].data(), ((size_t)ng + 1) * 4); r.blocks_comb[q] = t.comb[q].back(); r.lds[q] = t.lds[q]; }
-            r.dec = (const uint32_t *)put(t.dec.data(), ((size_t)ng + 1) * 4); r.units = t.dec.back();
-            r.terms = (const uint32_t *)put(t.terms.data(), ((size_t)ng + 1) * 4); r.blocks_terms = t.terms.back();
-            r.n_groups = ng; r.n = t.n;
-        }
-    }
-    if (m->last >= 0 && m->last != si && m->slot[m->last].used) HIPCHK(hipStreamWaitEvent(st, m->slot[m->last].done, 0));   // (the staging is the last call's until then)
-    HIPCHK(hipMemcpyAsync(sl.d, sl.h, need, hipMemcpyHostToDevice, st));
+            if (c.lay.foldable[k])
+                *fp++ = H2vFoldPlan{c.plans[k]->d.vk_bases, c.plans[k]->d.terms, c.plans[k]->n_var, c.plans[k]->n_fix, c.lay.fix_base[k], c.lay.n_blocks[k], c.lay.vk_base[k], 0u, c.lay.part_base[k]};    }
+    if (m->last >= 0 && m->last != si && m->slot[m->last].used) HIPCHK(hipStreamWaitEvent(st, m->slot[m->last].done, 0));
+    HIPCHK(hipMemcpyAsync(sl.d, sl.h, B.extent, hipMemcpyHostToDevice, st));
     sl.used = true; m->last = si;
-    // from here on the block is in use: every return records its end on `st` (after an error: drained first)
-    auto finish = [&](int code) -> int {
-        if (code) code = drain_after_error(w, code);
-        if (hipEventRecord(sl.done, st) != hipSuccess && !code) code = fail(H2V_E_DEVICE, "event record failed");
-        return code;
-    };
-    uint64_t *d_off = (uint64_t *)(sl.d + o_off);
-    const uint32_t *d_perm = (const uint32_t *)(sl.d + o_perm);
-    const H2vMixedTab tab = {n, (const uint64_t *)(sl.d + o_isrc), (const uint64_t *)(sl.d + o_idst), d_perm, (const uint32_t *)(sl.d + o_cap),
-                             (const uint32_t *)(sl.d + o_ilen), (const uint32_t *)(sl.d + o_csrc), (const uint32_t *)(sl.d + o_cdst)};
-    if (!host_off) hipLaunchKernelGGL(k_mixed_offsets, dim3(1), dim3(256), 0, st, in.proof_off, tab, d_off);
-    hipLaunchKernelGGL(k_mixed_gather, dim3((n + 3) / 4), dim3(256), 0, st, tab, in.proofs, in.proof_off, in.instances, in.committed, m->proofs.p, (const uint64_t *)d_off, m->inst.p, m->ci.p);
-    if (hipGetLastError() != hipSuccess) return finish(fail(H2V_E_DEVICE, "launch of the gather kernels failed"));
-    const h2v_plan *p0 = nullptr;          // any plan of the call: the tail reads nothing of it but the SRS's line tables
-    uint32_t used_plans = 0;
-    // (own: the plan runs a sub-batch of its own - every plan with proofs, but for the groupable ones of a grouped call, which
-    //  share ONE unit and one record; used_plans: the records the call takes before its tail's)
-    auto own = [&](uint32_t k) { return pt.count[k] && !(grp && grp->sp.groupable[k]); };
-    const uint32_t G = grp ? grp->sp.total : 0u;
-    for (uint32_t k = 0; k < pt.n_plans; k++) if (pt.count[k]) { if (!p0) p0 = plans[k]; if (own(k)) used_plans++; }
-    if (G) used_plans++;
+    auto dev = [&sl](const mixedtab::Region &g) { return sl.d + g.off; };
+    out.sl = &sl;
+    out.d_off = (uint64_t *)dev(B.offsets);
+    out.tab = {pt.n, (const uint64_t *)dev(B.inst_src), (const uint64_t *)dev(B.inst_dst), (const uint32_t *)dev(B.perm), (const uint32_t *)dev(B.len_cap),
+               (const uint32_t *)dev(B.inst_len), (const uint32_t *)dev(B.ci_src), (const uint32_t *)dev(B.ci_dst)};
+    out.d_fold = (const H2vFoldPlan *)dev(B.fold);
+    out.ranges.resize(gt.size());
+    for (size_t q = 0; q < gt.size(); q++) {
+        MixedGroupRange &r = out.ranges[q];
+        const mixedtab::RangeRegions &g = B.range[q];
+        static_cast<mixedtab::RangeInfo &>(r) = info[q];
+        r.recs = (const H2vGroupRec *)dev(g.recs); r.dec = (const uint32_t *)dev(g.dec); r.terms = (const uint32_t *)dev(g.terms);
+        for (int t = 0; t < 2; t++) r.comb[t] = (const uint32_t *)dev(g.comb[t]);
+    }
+    return H2V_OK;
+}
+// THE UNITS of a call.  phase1: the grouped unit if the call has grouped positions, then the sub-batch of every plan that runs one
+// of its own - every plan with proofs, but for the groupable ones of a grouped call, which share that ONE unit and one record -
+// in list order: the records the call takes before its tail's.  tail: over the whole pool.  The units point at `fc`.
+struct MixedUnits {
+    MixedFold fc;
+    std::vector<Unit> phase1;
+    Unit tail = {};
+    MixedUnits() = default;
+    MixedUnits(const MixedUnits &) = delete;
+};
+static void mixed_units(const MixedCall &c, MixedTables &t, MixedWs *m, MixedUnits &mu) {
+    const h2vmixed::Partition &pt = c.pt;
     const MixedPool pool = {m->pool, m->good, m->ones, m->status};
-    MixedFold fc = {m, lay, &pt, plans, (const H2vFoldPlan *)(sl.d + o_fold), d_perm, {}};
-    for (int q = 0; q < 8; q++) fc.seed[q] = seed ? seed[q] : 0;
-    fc.grp = grp; fc.ranges = std::move(ranges); fc.d_off = d_off;
-    Unit group{UnitKind::MIXED_GROUP, p0, G};
-    group.fold = &fc; group.pool = pool;
-    // More than RING records in one pass (the second pass of a grouped call of more than 64 plans with proofs): the sub-batches
-    // run in slices of at most SLICE plans, every slice joined before the next one starts, so that no record's slot is taken again
-    // while its kernels are in flight; the ONE tail stays the call's last record.
-    constexpr uint32_t SLICE = 62;
-    const bool sliced = used_plans > H2V_MIXED_MAX_PLANS;
-    // plan k's sub-batch out of the grouped staging, and the tail over the whole pool
-    auto sub_unit = [&](uint32_t k) {
-        const H2vDevPlan &d = plans[k]->d;
-        Unit u{lay && lay->foldable[k] ? UnitKind::MIXED_SUB_TERMS : UnitKind::MIXED_SUB, plans[k], pt.count[k]};
-        if (lay) { u.fold = &fc; u.fold_plan = k; }
-        u.proofs = m->proofs.p; u.off = d_off + pt.base[k];
+    MixedFold &fc = mu.fc;
+    fc.m = m; fc.lay = c.fold ? &c.lay : nullptr; fc.pt = &pt; fc.plans = c.plans; fc.d_plans = t.d_fold; fc.d_perm = t.tab.perm;
+    copy_seed(fc.seed, c.seed);
+    fc.grp = c.grouped ? &c.grp : nullptr; fc.ranges = std::move(t.ranges); fc.d_off = t.d_off;
+    const uint32_t G = c.grouped ? c.grp.sp.total : 0u;
+    if (G) {
+        Unit group{UnitKind::MIXED_GROUP, nullptr, G};
+        group.fold = &fc; group.pool = pool;
+        mu.phase1.push_back(group);
+    }
+    const h2v_plan *p0 = nullptr;          // any plan of the call: the tail reads nothing of it but the SRS's line tables
+    for (uint32_t k = 0; k < pt.n_plans; k++) {
+        if (!pt.count[k]) continue;                                  // (a listed plan without a proof costs nothing)
+        if (!p0) p0 = c.plans[k];
+        if (c.grouped && c.grp.sp.groupable[k]) continue;
+        // plan k's sub-batch out of the grouped staging
+        const H2vDevPlan &d = c.plans[k]->d;
+        Unit u{c.fold && c.lay.foldable[k] ? UnitKind::MIXED_SUB_TERMS : UnitKind::MIXED_SUB, c.plans[k], pt.count[k]};
+        if (c.fold) { u.fold = &fc; u.fold_plan = k; }
+        u.proofs = m->proofs.p; u.off = t.d_off + pt.base[k];
         u.inst = d.n_pi ? m->inst.p + pt.inst_base[k] : nullptr;
         u.ci = d.n_ci ? m->ci.p + (size_t)pt.ci_base[k] * 48 : nullptr;
-        u.pos = d_perm + pt.base[k]; u.pool = pool;
-        return u;
-    };
-    Unit tail{lay ? UnitKind::MIXED_FOLD_TAIL : rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, n};
-    tail.pool = pool; tail.accept = accept; tail.status = status_out; tail.fold = lay ? &fc : nullptr;
-    tail.agg_parts = lay ? agg_parts : nullptr;
-    for (int q = 0; q < 8; q++) tail.seed[q] = seed ? seed[q] : 0;
-    if (!w->n_lanes) {
-        // an ordinary workspace: the sub-batches one after the other on `st`, then the tail
-        // (one stream: a slice is joined by construction)
-        if (G && (rc = run_unit(group, w, st))) return finish(rc);
-        for (uint32_t k = 0; k < pt.n_plans; k++)
-            if (own(k) && (rc = run_unit(sub_unit(k), w, st))) return finish(rc);
-        return finish(run_unit(tail, w, st));
+        u.pos = t.tab.perm + pt.base[k]; u.pool = pool;
+        mu.phase1.push_back(u);
     }
-    // ---- laned: every plan's sub-batch in chunks through the lanes, nothing joined in between
-    uint32_t total_chunks = n_chunks(G, w->chunk);
-    for (uint32_t k = 0; k < pt.n_plans; k++) if (own(k)) total_chunks += n_chunks(pt.count[k], w->chunk);
+    if (G) mu.phase1.front().p = p0;
+    mu.tail = Unit{c.fold ? UnitKind::MIXED_FOLD_TAIL : c.rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, pt.n};
+    mu.tail.pool = pool; mu.tail.accept = c.accept; mu.tail.status = c.status;
+    if (c.fold) { mu.tail.fold = &fc; mu.tail.agg_parts = c.agg_parts; }
+    copy_seed(mu.tail.seed, c.seed);
+}
+// an ordinary workspace: the sub-batches one after the other on `st`, then the tail (one stream: everything is joined by
+// construction)
+static int mixed_run_ordinary(const MixedUnits &mu, h2v_workspace *w, hipStream_t st) {
+    for (const Unit &u : mu.phase1)
+        if (int rc = run_unit(u, w, st)) return rc;
+    return run_unit(mu.tail, w, st);
+}
+// a laned workspace: every phase-1 unit in chunks through the lanes, nothing joined in between; then the tail behind all of them.
+// More than RING records in one pass (the second pass of a grouped call of more than 64 plans with proofs): the sub-batches run
+// in slices of at most SLICE plans, every slice joined before the next one starts, so that no record's slot is taken again while
+// its kernels are in flight; the ONE tail stays the call's last record.  (The grouped unit is no member of a slice.)
+static int mixed_run_laned(const MixedCall &c, MixedUnits &mu, h2v_workspace *w, hipStream_t st) {
+    constexpr uint32_t SLICE = 62;
+    const uint32_t n = c.pt.n, used_plans = (uint32_t)mu.phase1.size();
+    const bool sliced = used_plans > H2V_MIXED_MAX_PLANS, rlc = c.rlc;
+    Unit &tail = mu.tail;
+    int rc;
+    uint32_t total_chunks = 0;
+    for (const Unit &u : mu.phase1) total_chunks += n_chunks(u.n, w->chunk);
     // (the sub-batches of all plans are in flight together: what they may assume is the call's chunks, not one plan's)
     const uint32_t sub_hint = call_hint(w, total_chunks > w->n_lanes, total_chunks);
     tail.fail_ctr = w->rec_fail ? w->rec_fail + (w->calls + used_plans) % h2v_workspace::RING : nullptr;   // the tail's record: the call's last
-    if (rlc && !tail.fail_ctr) return finish(fail(H2V_E_DEVICE, "internal: no verdict words"));
-    if (rlc && hipMemsetAsync(tail.fail_ctr, 0, 4, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "memset failed"));
-    if (hipEventRecord(w->ev_fork, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
+    if (rlc && !tail.fail_ctr) return fail(H2V_E_DEVICE, "internal: no verdict words");
+    if (rlc && hipMemsetAsync(tail.fail_ctr, 0, 4, st) != hipSuccess) return fail(H2V_E_DEVICE, "memset failed");
+    if (hipEventRecord(w->ev_fork, st) != hipSuccess) return fail(H2V_E_DEVICE, "event record failed");
     bool used_lane[h2v_workspace::MAXL] = {};
-    if (G) {                 // the groupable plans: ONE unit over the grouped positions, one record
-        int stream_mode = 1;
-        const uint32_t L = laned_depth(w, G, false, &stream_mode);
-        rec_laned(w, h2v_workspace::PREPARE, L, G, w->chunk);
-        if ((rc = run_chunks(w, group, L, w->chunk, {sub_hint, stream_mode}, [&](uint32_t l, hipStream_t) { used_lane[l] = true; return (int)H2V_OK; })))
-            return finish(rc);
-    }
     uint32_t in_slice = 0;
-    for (uint32_t k = 0; k < pt.n_plans; k++) {
-        if (!own(k)) continue;                                       // (a listed plan without a proof costs nothing)
-        if (sliced && in_slice++ == SLICE) {                         // the next slice starts behind the whole of this one
-            if ((rc = lanes_join(w, st))) return finish(rc);
-            if (hipEventRecord(w->ev_fork, st) != hipSuccess) return finish(fail(H2V_E_DEVICE, "event record failed"));
+    for (const Unit &u : mu.phase1) {
+        if (sliced && u.kind != UnitKind::MIXED_GROUP && in_slice++ == SLICE) {   // the next slice starts behind the whole of this one
+            if ((rc = lanes_join(w, st))) return rc;
+            if (hipEventRecord(w->ev_fork, st) != hipSuccess) return fail(H2V_E_DEVICE, "event record failed");
             in_slice = 1;
         }
         int stream_mode = 1;
-        const uint32_t L = laned_depth(w, pt.count[k], false, &stream_mode);
-        rec_laned(w, h2v_workspace::PREPARE, L, pt.count[k], w->chunk);
-        if ((rc = run_chunks(w, sub_unit(k), L, w->chunk, {sub_hint, stream_mode}, [&](uint32_t l, hipStream_t) { used_lane[l] = true; return (int)H2V_OK; })))
-            return finish(rc);
+        const uint32_t L = laned_depth(w, u.n, false, &stream_mode);
+        rec_laned(w, h2v_workspace::PREPARE, L, u.n, w->chunk);
+        if ((rc = run_chunks(w, u, L, w->chunk, {sub_hint, stream_mode}, [&](uint32_t l, hipStream_t) { used_lane[l] = true; return (int)H2V_OK; }))) return rc;
     }
-    if (lay) {
+    if (c.fold) {
         // ---- the fold form's tail: ONE piece on the call's stream, behind every lane; its record (one "chunk") is a lane's
-        if ((rc = lanes_join(w, st))) return finish(rc);
+        if ((rc = lanes_join(w, st))) return rc;
         CallRec &rec = rec_laned(w, h2v_workspace::RLC, w->n_lanes, n, n);
         rec.agg = tail.agg_parts != nullptr;
-        if (rec_word(w, rec) != tail.fail_ctr) return finish(fail(H2V_E_DEVICE, "internal: the tail's record is not the call's last"));
+        if (rec_word(w, rec) != tail.fail_ctr) return fail(H2V_E_DEVICE, "internal: the tail's record is not the call's last");
         const uint32_t l = (uint32_t)(w->next_lane++ % w->n_lanes);
-        if ((rc = ensure_lane(w, l))) return finish(rc);
-        return finish(run_unit(tail, w->lane[l], st));
+        if ((rc = ensure_lane(w, l))) return rc;
+        return run_unit(tail, w->lane[l], st);
     }
     // ---- the tail: chunks of the pool in the caller's order, each behind EVERY sub-batch (any of them may hold any position)
-    {
-        const uint32_t L = laned_depth(w, n, rlc, nullptr), nch = n_chunks(n, w->chunk);
-        rec_laned(w, rlc ? h2v_workspace::RLC : h2v_workspace::CHECK, L, n, w->chunk);
-        auto behind_subs = [&](uint32_t l, hipStream_t ls) -> int {
-            for (uint32_t q = 0; q < w->n_lanes; q++)
-                if (used_lane[q] && q != l && hipStreamWaitEvent(ls, w->lane_ev[q], 0) != hipSuccess) return fail(H2V_E_DEVICE, "stream wait failed");
-            used_lane[l] = true;
-            return H2V_OK;
-        };
-        // (a mixed call joins at its end: its tail has only its own chunks in flight unless joins are deferred)
-        if ((rc = run_chunks(w, tail, L, w->chunk, {call_hint(w, false, nch < L ? nch : L), 1}, behind_subs))) return finish(rc);
-    }
+    const uint32_t L = laned_depth(w, n, rlc, nullptr), nch = n_chunks(n, w->chunk);
+    rec_laned(w, rlc ? h2v_workspace::RLC : h2v_workspace::CHECK, L, n, w->chunk);
+    auto behind_subs = [&](uint32_t l, hipStream_t ls) -> int {
+        for (uint32_t q = 0; q < w->n_lanes; q++)
+            if (used_lane[q] && q != l && hipStreamWaitEvent(ls, w->lane_ev[q], 0) != hipSuccess) return fail(H2V_E_DEVICE, "stream wait failed");
+        used_lane[l] = true;
+        return H2V_OK;
+    };
+    // (a mixed call joins at its end: its tail has only its own chunks in flight unless joins are deferred)
+    if ((rc = run_chunks(w, tail, L, w->chunk, {call_hint(w, false, nch < L ? nch : L), 1}, behind_subs))) return rc;
     // a mixed call is a join point: its caller-stream wait happens here, deferred joins or not
-    return finish(lanes_join(w, st));
+    return lanes_join(w, st);
 }
-// argument checks shared by the two forms; on success *pt is the partition and *n_used the number of listed plans with proofs
-static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, const uint8_t *accept, uint32_t flags, h2vmixed::Partition *pt) {
+// One pass of a mixed call on `st`: the gather kernels behind the tables, then the schedule of the workspace's kind.
+static int mixed_enqueue(const MixedCall &c, MixedTables &t, h2v_workspace *w, hipStream_t st) {
+    MixedWs *m = w->mixed;
+    const h2v_batch &in = c.in;
+    if (!c.host_off) hipLaunchKernelGGL(k_mixed_offsets, dim3(1), dim3(256), 0, st, in.proof_off, t.tab, t.d_off);
+    hipLaunchKernelGGL(k_mixed_gather, dim3((c.pt.n + 3) / 4), dim3(256), 0, st, t.tab, in.proofs, in.proof_off, in.instances, in.committed, m->proofs.p, (const uint64_t *)t.d_off, m->inst.p, m->ci.p);
+    if (hipGetLastError() != hipSuccess) return fail(H2V_E_DEVICE, "launch of the gather kernels failed");
+    MixedUnits mu;
+    mixed_units(c, t, m, mu);
+    return w->n_lanes ? mixed_run_laned(c, mu, w, st) : mixed_run_ordinary(mu, w, st);
+}
+static int run_mixed(const MixedCall &c, h2v_workspace *w, hipStream_t st) {
+    int rc;
+    if (w->n_lanes && (rc = co_flush(w))) return rc;       // (calls start in submission order: the open groups of coalesced calls first)
+    if ((rc = mixed_ensure(w, c.pt))) return rc;
+    if (c.rlc && (rc = rlc_stats_ensure(w))) return rc;
+    if (c.fold && (rc = mixed_fold_ensure(w, c.lay))) return rc;
+    MixedTables t;
+    if ((rc = mixed_tables(c, w, st, t))) return rc;
+    // from here on the block is in use: THE return records its end on `st` (after an error: drained first)
+    rc = mixed_enqueue(c, t, w, st);
+    if (rc) rc = drain_after_error(w, rc);
+    if (hipEventRecord(t.sl->done, st) != hipSuccess && !rc) rc = fail(H2V_E_DEVICE, "event record failed");
+    return rc;
+}
+// argument checks shared by the forms; on success (and b->n != 0) c holds the plans, the flags and the partition
+static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, const uint8_t *accept, uint32_t flags, MixedCall *c) {
+    h2vmixed::Partition *pt = &c->pt;
+    c->plans = plans;
+    c->rlc = (flags & H2V_MIXED_RLC) != 0; c->fold = (flags & H2V_MIXED_FOLD_MSM) != 0; c->grouped = (flags & H2V_MIXED_GROUPED) != 0;
     if (!plans || !b || !accept) return fail(H2V_E_ARG, "null argument");
     const uint32_t max_plans = (flags & H2V_MIXED_GROUPED) ? H2V_MIXED_GROUPED_MAX_PLANS : H2V_MIXED_MAX_PLANS;
     if (n_plans > max_plans)
@@ -3686,11 +3721,14 @@ static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
     if (pt->ci_total && !b->committed) return fail(H2V_E_ARG, "a plan of the call has a committed instance but committed == NULL");
     return H2V_OK;
 }
+static int mixed_no_host_batch(const h2v_workspace *ws) {
+    if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
+    return H2V_OK;
+}
 static int mixed_ws_check(const h2v_plan *const *plans, uint32_t n_plans, uint64_t n, const h2v_workspace *ws) {
     for (uint32_t k = 0; k < n_plans; k++)
         if (int rc = ws_fits(ws, plans[k], n, false)) return fail(rc, "plans[" + std::to_string(k) + "]: " + g_err);
-    if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
-    return H2V_OK;
+    return mixed_no_host_batch(ws);
 }
 // H2V_MIXED_FOLD_MSM: the layout of the call's term pool on workspace w (h2v_mixed_fold.hpp) - which plans have the batch form
 // (rlc_supported), where their terms and block sums go, N_R - decided on the host before anything is enqueued: H2V_E_LIMIT above
@@ -3717,45 +3755,56 @@ static int mixed_group_layout(const h2v_plan *const *plans, const h2vmixed::Part
     h2vmixed::group_fold_blocks(gp->sp, gp->shapes.data(), pt.count.data(), *lay);
     return H2V_OK;
 }
-// One mixed call on `st`.  lay (H2V_MIXED_FOLD_MSM): the fold form first - one bucket MSM and one pairing for the call - and then
+// One mixed call on `st`.  c.fold (H2V_MIXED_FOLD_MSM): the fold form first - one bucket MSM and one pairing for the call - and then
 // the HOST decides: the record's verdict word comes down and `st` is synchronised (the one synchronisation of the form; phase-1
 // results no longer exist by then, the lanes have recycled them).  Passed: accept[] / status[] are final.  Failed: the
 // H2V_MIXED_RLC path runs on the same inputs with the same seed - its pair check, group stage and per-pair kernels localise the
 // rejects -, *fold_failed is set and the call's last record is that second pass's.
-static int run_mixed_call(const h2v_plan *const *plans, const h2vmixed::Partition &pt, const uint64_t *host_off, const h2v_batch &in, uint8_t *accept,
-                          uint32_t *status_out, h2v_workspace *w, hipStream_t st, bool rlc, const uint32_t seed[8], const h2vmixed::FoldLayout *lay,
-                          bool *fold_failed, const MixedGroupPlan *grp = nullptr) {
-    if (!lay) return run_mixed(plans, pt, host_off, in, accept, status_out, w, st, rlc, seed);
-    int rc = run_mixed(plans, pt, host_off, in, accept, status_out, w, st, true, seed, lay, nullptr, grp);
-    if (rc) return rc;
+static int run_mixed_call(const MixedCall &c, h2v_workspace *w, hipStream_t st, bool *fold_failed) {
+    int rc = run_mixed(c, w, st);
+    if (rc || !c.fold) return rc;
     uint32_t failed = 0;
     if (verdict_down(w, &failed, st) || hipStreamSynchronize(st) != hipSuccess)
         return drain_after_error(w, fail(H2V_E_DEVICE, "mixed-call kernels failed (fold form)"));
     if (!failed) return H2V_OK;
     if (fold_failed) *fold_failed = true;
-    return run_mixed(plans, pt, host_off, in, accept, status_out, w, st, true, seed);
+    MixedCall second = c;
+    second.fold = second.grouped = false;
+    return run_mixed(second, w, st);
+}
+// the layouts of a call on workspace ws, on the host before anything is enqueued: the fold form's, then the grouped form's
+static int mixed_layouts(MixedCall &c, const h2v_workspace *ws) {
+    if (c.fold)
+        if (int rc = mixed_fold_layout(c.plans, c.pt, ws, &c.lay)) return rc;
+    return c.grouped ? mixed_group_layout(c.plans, c.pt, &c.lay, &c.grp) : (int)H2V_OK;
+}
+// The last step of filling a MixedCall: its I/O.  THE place where the combinations of its parts are checked: the grouped form
+// needs the fold layout (cut at the same chunk size), an aggregate call needs it, and the fold form needs the coefficients.
+static int mixed_call_io(MixedCall &c, const h2v_batch &in, const uint64_t *host_off, uint8_t *accept, uint32_t *status, uint32_t *agg_parts) {
+    c.in = in; c.host_off = host_off; c.accept = accept; c.status = status; c.agg_parts = agg_parts;
+    if (c.grouped && (!c.fold || c.grp.sp.chunk != c.lay.chunk)) return fail(H2V_E_DEVICE, "internal: grouped call without its fold layout");
+    if (c.agg_parts && !c.fold) return fail(H2V_E_DEVICE, "internal: aggregate call without its fold layout");
+    if (c.fold && !c.rlc) return fail(H2V_E_DEVICE, "internal: fold form without its coefficients");
+    return H2V_OK;
+}
+// what H2V_MIXED_* flags an aggregate-mixed call is: the grouped fold form, H2V_RLC_GROUPED asking for the grouping
+static uint32_t agg_mixed_flags(const h2v_rlc_opts *opts) {
+    return H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | (opts && (opts->flags & H2V_RLC_GROUPED) ? H2V_MIXED_GROUPED : 0u);
 }
 extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
                                        h2v_workspace *ws, void *stream, uint32_t flags, const h2v_rlc_opts *opts) {
-    h2vmixed::Partition pt;
-    int rc = mixed_args(plans, n_plans, b, accept, flags, &pt);
+    MixedCall c;
+    int rc = mixed_args(plans, n_plans, b, accept, flags, &c);
     if (rc || b->n == 0) return rc;
     if (!ws) return fail(H2V_E_ARG, "the device form needs a workspace (h2v_workspace_create_multi over the listed plans)");
     ALIVE(ws);
     HIPCHK(hipSetDevice(plans[0]->device));
     if ((rc = mixed_ws_check(plans, n_plans, b->n, ws))) return rc;
     if ((rc = null_stream_check(ws, stream))) return rc;
-    const bool rlc = (flags & H2V_MIXED_RLC) != 0;
-    uint32_t seed[8] = {};
-    if (rlc && (rc = rlc_seed(opts, seed))) return rc;
-    h2vmixed::FoldLayout lay;
-    const bool fold = (flags & H2V_MIXED_FOLD_MSM) != 0;
-    if (fold && (rc = mixed_fold_layout(plans, pt, ws, &lay))) return rc;
-    MixedGroupPlan gp;
-    const bool grouped = (flags & H2V_MIXED_GROUPED) != 0;
-    if (grouped && (rc = mixed_group_layout(plans, pt, &lay, &gp))) return rc;
-    const h2v_batch in = {b->n, b->proofs, b->proof_off, b->instances, b->committed};
-    return run_mixed_call(plans, pt, nullptr, in, accept, status, ws, (hipStream_t)stream, rlc, seed, fold ? &lay : nullptr, nullptr, grouped ? &gp : nullptr);
+    if (c.rlc && (rc = rlc_seed(opts, c.seed))) return rc;      // (the device forms: the seed before the layouts)
+    if ((rc = mixed_layouts(c, ws))) return rc;
+    if ((rc = mixed_call_io(c, {b->n, b->proofs, b->proof_off, b->instances, b->committed}, nullptr, accept, status, nullptr))) return rc;
+    return run_mixed_call(c, ws, (hipStream_t)stream, nullptr);
 }
 // Host-buffer form: offsets | instances | committed | proofs go up in one pinned block on the workspace's own stream, the call
 // runs there behind it, and accept[] / status[] / the batch verdict come back before the function returns.
@@ -3768,8 +3817,9 @@ static int agg_ensure(h2v_workspace *ws, uint32_t n_parts, hipStream_t st, AggSl
 static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
                       h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back, uint8_t *agg_pair, h2v_aggregate_info *info) {
     if (fell_back) *fell_back = 0;
-    h2vmixed::Partition pt;
-    int rc = mixed_args(plans, n_plans, b, accept, flags, &pt);
+    MixedCall c;
+    const h2vmixed::Partition &pt = c.pt;
+    int rc = mixed_args(plans, n_plans, b, accept, flags, &c);
     if (rc || b->n == 0) return rc;
     ALIVE(ws);
     HIPCHK(hipSetDevice(plans[0]->device));
@@ -3779,19 +3829,12 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
         if ((rc = h2v_workspace_create_multi(plans, n_plans, n, 0, n < 4096 ? (uint32_t)n : 4096u, &tmp))) return rc;
         ws = tmp;
     }
-    const bool rlc = (flags & H2V_MIXED_RLC) != 0;
-    uint32_t seed[8] = {};
-    h2vmixed::FoldLayout lay;
-    const bool fold = (flags & H2V_MIXED_FOLD_MSM) != 0;
     bool fold_failed = false;
     h2v_batch in{};
     hostcall::ResultBlock R;
     rc = mixed_ws_check(plans, n_plans, n, ws);
-    if (rc == H2V_OK && fold) rc = mixed_fold_layout(plans, pt, ws, &lay);
-    MixedGroupPlan gp;
-    const bool grouped = (flags & H2V_MIXED_GROUPED) != 0;
-    if (rc == H2V_OK && grouped) rc = mixed_group_layout(plans, pt, &lay, &gp);
-    if (rc == H2V_OK && rlc) rc = rlc_seed(opts, seed);
+    if (rc == H2V_OK) rc = mixed_layouts(c, ws);                 // (the host form: the layouts before the seed)
+    if (rc == H2V_OK && c.rlc) rc = rlc_seed(opts, c.seed);
     if (rc == H2V_OK) rc = mixed_ensure(ws, pt);
     if (rc == H2V_OK) rc = result_ensure(ws, hostcall::Call::MIXED, n, &R, ws->mixed);
     if (rc == H2V_OK) {
@@ -3803,14 +3846,15 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
         h2vmixed::group_offsets(pt, (const uint64_t *)ws->mixed->in.h_block.p, goff.data());     // (the packed offsets: rebased)
         uint8_t *const d = ws->res.p, *d_accept = d + R.accept.off;
         uint32_t *d_status = (uint32_t *)(d + R.status.off);
-        if (agg_pair) {
+        if (agg_pair) {      // (run_mixed, not run_mixed_call: no verdict comes down and nothing runs a second time)
             AggSlot as{};
-            if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = run_mixed(plans, pt, goff.data(), in, d_accept, d_status, ws, ws->hs, true, seed, &lay, as.parts, grouped ? &gp : nullptr);
+            if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = mixed_call_io(c, in, goff.data(), d_accept, d_status, as.parts);
+            if (rc == H2V_OK) rc = run_mixed(c, ws, ws->hs);
             if (rc == H2V_OK) rc = agg_export(ws, as, 1, d + R.pairs.off, ws->hs);
-            if (rc == H2V_OK) rc = agg_info_fill(info, seed, 0, 1, lay.n_r);
-        } else rc = run_mixed_call(plans, pt, goff.data(), in, d_accept, d_status, ws, ws->hs, rlc, seed, fold ? &lay : nullptr, &fold_failed, grouped ? &gp : nullptr);
+            if (rc == H2V_OK) rc = agg_info_fill(info, c.seed, 0, 1, c.lay.n_r);
+        } else if ((rc = mixed_call_io(c, in, goff.data(), d_accept, d_status, nullptr)) == H2V_OK) rc = run_mixed_call(c, ws, ws->hs, &fold_failed);
         rc = host_call_tail(ws, rc, {{agg_pair, R.pairs, "the pair"}, {accept, R.accept, "accept[]"}, {status, R.status, "the status words"}},
-                            rlc && !agg_pair, fell_back, "mixed-call", fold_failed);
+                            c.rlc && !agg_pair, fell_back, "mixed-call", fold_failed);
     }
     if (tmp) h2v_workspace_free(tmp);
     return rc;
@@ -3959,46 +4003,40 @@ extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t
     if (!pair) return fail(H2V_E_ARG, "null argument: pair");
     if (b && b->n == 0 && !included) included = pair;      // (nothing to write; mixed_args wants a pointer)
     if (int rca = agg_flags(opts, true)) return rca;
-    const uint32_t mflags = H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | (opts && (opts->flags & H2V_RLC_GROUPED) ? H2V_MIXED_GROUPED : 0u);
-    h2vmixed::Partition pt;
-    int rc = mixed_args(plans, n_plans, b, included, mflags, &pt);
+    MixedCall c;
+    int rc = mixed_args(plans, n_plans, b, included, agg_mixed_flags(opts), &c);
     if (rc) return rc;
     if ((uintptr_t)pair & 3) return fail(H2V_E_ARG, "pair must be 4-byte aligned");
     if (!ws) return fail(H2V_E_ARG, "the device form needs a workspace (h2v_workspace_create_multi over the listed plans)");
     ALIVE(ws);
+    // ws->device, where the other forms say plans[0]->device: a call of NO proofs runs too (it exports the pair (inf, inf)), and it
+    // may list no plan at all.  With proofs the two are equal: mixed_ws_check -> ws_fits holds every plan to the workspace's device.
     HIPCHK(hipSetDevice(ws->device));
-    if (b->n && (rc = mixed_ws_check(plans, n_plans, b->n, ws))) return rc;
-    if (ws->pending) return fail(H2V_E_ARG, "the workspace has a host batch in flight: call h2v_verify_batch_wait first");
+    if ((rc = b->n ? mixed_ws_check(plans, n_plans, b->n, ws) : mixed_no_host_batch(ws))) return rc;   // (no proofs: no plan to fit)
     if ((rc = null_stream_check(ws, stream))) return rc;
-    uint32_t seed[8] = {};
-    if ((rc = rlc_seed(opts, seed))) return rc;
+    if ((rc = rlc_seed(opts, c.seed))) return rc;
+    AggSlot as{};
     if (b->n == 0) {
-        agg_info_fill(info, seed, 0, 1, 0);
-        AggSlot as{};
+        agg_info_fill(info, c.seed, 0, 1, 0);
         if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
         return agg_export(ws, as, 0, pair, (hipStream_t)stream);
     }
-    h2vmixed::FoldLayout lay;
-    if ((rc = mixed_fold_layout(plans, pt, ws, &lay))) return rc;
-    MixedGroupPlan gp;
-    const bool grouped = (mflags & H2V_MIXED_GROUPED) != 0;
-    if (grouped && (rc = mixed_group_layout(plans, pt, &lay, &gp))) return rc;
-    agg_info_fill(info, seed, 0, 1, lay.n_r);
-    AggSlot as{};
+    if ((rc = mixed_layouts(c, ws))) return rc;
+    agg_info_fill(info, c.seed, 0, 1, c.lay.n_r);
     if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
-    const h2v_batch in = {b->n, b->proofs, b->proof_off, b->instances, b->committed};
+    if ((rc = mixed_call_io(c, {b->n, b->proofs, b->proof_off, b->instances, b->committed}, nullptr, included, status, as.parts))) return rc;
     // (run_mixed, not run_mixed_call: no verdict comes down, the stream is not synchronised and nothing runs a second time)
-    if ((rc = run_mixed(plans, pt, nullptr, in, included, status, ws, (hipStream_t)stream, true, seed, &lay, as.parts, grouped ? &gp : nullptr))) return rc;
+    if ((rc = run_mixed(c, ws, (hipStream_t)stream))) return rc;
     return agg_export(ws, as, 1, pair, (hipStream_t)stream);
 }
 extern "C" int h2v_aggregate_mixed(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t pair[96], uint8_t *included,
                                    uint32_t *status, h2v_workspace *ws, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
     if (!pair) return fail(H2V_E_ARG, "null argument: pair");
     if (int rca = agg_flags(opts, true)) return rca;
-    const uint32_t mflags = H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | (opts && (opts->flags & H2V_RLC_GROUPED) ? H2V_MIXED_GROUPED : 0u);
+    const uint32_t mflags = agg_mixed_flags(opts);
     if (b && b->n == 0) {      // (inf, inf) without a device; the argument rules still hold
-        h2vmixed::Partition pt;
-        if (int rc = mixed_args(plans, n_plans, b, pair, mflags, &pt)) return rc;
+        MixedCall none;
+        if (int rc = mixed_args(plans, n_plans, b, pair, mflags, &none)) return rc;
         uint32_t seed[8] = {};
         if (int rc = rlc_seed(opts, seed)) return rc;
         agg_info_fill(info, seed, 0, 1, 0);
