@@ -127,6 +127,9 @@ int h2v_plan_transcript(const h2v_plan *plan, uint32_t *kind, uint8_t key_out[64
 /* 1 if the two plans carry the same SRS (the same s_g2: what h2v_verify_mixed demands of the plans of one call), 0 if not;
  * H2V_E_ARG for a null plan.  Host-only: needs no device. */
 int h2v_plan_same_srs(const h2v_plan *a, const h2v_plan *b);
+/* key_tag = blake2b-256(TAG("h2v-seed-key/1") || plan blob), computed at load: what a derived batch seed (H2V_RLC_SEED_TRANSCRIPT)
+ * binds the verifying key with.  Host-only. */
+int h2v_plan_key_tag(const h2v_plan *plan, uint8_t out[32]);
 
 /* A workspace is sized from `plan` (MSM terms, point slots, register file, recursion / fixed-base buffers).  It may be
  * reused with ANOTHER plan only if that plan needs no more of any of these; otherwise the verify calls return H2V_E_ARG
@@ -321,6 +324,26 @@ int h2v_verify_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_
                                * included[], same info; up to H2V_MIXED_GROUPED_MAX_PLANS plans.  H2V_E_ARG in any other aggregate call.
                                * (Bit 8 stays unassigned: the aggregate calls have always answered H2V_E_ARG to it, and callers
                                * and tests rely on that.) */
+/* DERIVED SEED (Fiat-Shamir).  With this flag nothing is drawn: the call's seed is a blake2b-256 digest of everything that
+ * determines the batch - the plan (key_tag = B(TAG("h2v-seed-key/1") || plan blob), h2v_plan_key_tag), the form, n, and per proof
+ * the lengths and bytes of its instance row, committed row and proof - computed on the device in front of the call, over the WHOLE
+ * call (a laned workspace tweaks it per chunk as it tweaks any seed).  B: unkeyed blake2b-256; TAG(s): s zero-padded to 16 bytes:
+ *   leaf_i = B(TAG("h2v-seed-leaf/1") || LE32(|inst_i|) || LE32(|ci_i|) || LE32(|proof_i|) || LE32(0) || inst_i || ci_i || proof_i)
+ *            (h2v_check_pairs_rlc: |inst| = |ci| = 0, proof_i = the 96 pair bytes)
+ *   node   = B(TAG("h2v-seed-node/1") || LE32(level) || LE32(m) || LE64(index in its level) || child_0 .. child_{m-1}), 64-ary,
+ *            level 1 over the leaves, levels added until one node is left (n = 1: one level-1 node)
+ *   seed   = B(TAG("h2v-seed-root/1") || LE32(form: 1 proofs, 2 pairs) || LE32(0) || LE64(n) || key_tag || top node)
+ * and the coefficients follow from the seed as from any other.  plutus_halo2_verifier_gen_amd/seed.py restates the rule with
+ * hashlib: whoever holds the same key, the same inputs and the same chunk size recomputes the same seed and the same pair.
+ * CLAIM: sound in the random-oracle model for blake2b - a prover making q hash evaluations gets a rejecting proof accepted with
+ * probability at most q / 2^128 (2^-128 flat with a secret seed); nothing has to be kept from the provers.  It is still not a
+ * succinct proof for someone without the inputs.
+ * Accepted by h2v_verify_batch_rlc(_device), h2v_verify_batch_submit with H2V_SUBMIT_RLC, h2v_check_pairs_rlc(_device) and
+ * h2v_aggregate_batch(_device) (recursive plans: on their fold-pairs route - the leaf binds the inputs, which determine the folded
+ * pairs).  H2V_E_ARG: together with H2V_RLC_SEED_GIVEN; in h2v_verify_mixed(_device) / h2v_aggregate_mixed(_device) - a mixed leaf
+ * needs the key tag of its own proof's plan: a later change.  A call with the flag is never coalesced; it is routed as ever, and a
+ * call that routing sends to the per-proof kernels derives nothing.  DESIGN.md section 17. */
+#define H2V_RLC_SEED_TRANSCRIPT 32u
 typedef struct h2v_rlc_opts_s {
     uint8_t seed[32];   /* used when flags & H2V_RLC_SEED_GIVEN (tests, reproducible measurements - never a service) */
     uint32_t flags;
@@ -340,6 +363,12 @@ int h2v_verify_batch_rlc_device(const h2v_plan *plan, const h2v_batch *batch, ui
  * H2V_BATCH_NOT_CHECKED and pairing_ms = 0.  H2V_E_ARG: no such record or a lane's ring has wrapped since (as there), a call that
  * was not an RLC call, or a coalesced call whose group has not run yet. */
 int h2v_workspace_rlc_result(h2v_workspace *ws, uint32_t calls_back, uint32_t *batch_accepted, h2v_rlc_timings *timings);
+/* after synchronising the stream of a call made with H2V_RLC_SEED_TRANSCRIPT: the 32 bytes of the seed it derived (the call's
+ * seed: a laned workspace's chunk tweaks are not in it).  calls_back as above.  H2V_E_ARG: no such record, or a call that derived
+ * nothing (no flag, or routed to the per-proof kernels).  h2v_workspace_seed_ms: the device time of that call's digest launches,
+ * first start to last end (HIP events on the call's stream); the same errors. */
+int h2v_workspace_seed_used(h2v_workspace *ws, uint32_t calls_back, uint8_t seed[32]);
+int h2v_workspace_seed_ms(h2v_workspace *ws, uint32_t calls_back, float *ms);
 
 /* ---- prepare and pair check (the two halves of verification: the reference's `prepare` -> DualMSM -> `check`) -----------
  * h2v_prepare_batch(_device) runs the verify pipeline up to the final pairing check  e(L, s_g2) == e(R, G2)  and returns the
@@ -527,11 +556,17 @@ int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, cons
  *   with pairing_ms = 0 and batch_accepted = H2V_BATCH_NOT_CHECKED.
  *   ERRORS as h2v_verify_batch_rlc(_device) / h2v_verify_mixed(_device): n > 2^22 is H2V_E_LIMIT; stream = NULL under deferred
  *   joins, a host batch in flight on ws, ws = NULL in a device form are H2V_E_ARG; ws = NULL in a host form: a temporary workspace.
- *   opts->flags: H2V_RLC_SEED_GIVEN and H2V_RLC_ONE_STREAM as ever, H2V_RLC_FOLD_PAIRS accepted and ignored, H2V_RLC_GROUPED in the
+ *   opts->flags: H2V_RLC_SEED_GIVEN and H2V_RLC_ONE_STREAM as ever, H2V_RLC_SEED_TRANSCRIPT in the single-key forms (not beside
+ *   H2V_RLC_SEED_GIVEN), H2V_RLC_FOLD_PAIRS accepted and ignored, H2V_RLC_GROUPED in the
  *   mixed forms (phase 1 grouped as with H2V_MIXED_GROUPED: the same pair bit for bit), any other bit H2V_E_ARG.
  *   The device forms take device pointers (pair 4-byte aligned; plan_of stays host memory); info is HOST memory in both forms.
- *   SOUNDNESS.  A pair vouches for its proofs only to someone who trusts that seed_used was unpredictable to the provers - the same
- *   trust domain as the caller of h2v_verify_batch_rlc.  It is NOT a proof for third parties.  Whoever combines the pairs of several
+ *   SOUNDNESS.  DRAWN OR GIVEN SEED: a pair vouches for its proofs only to someone who trusts that seed_used was unpredictable to
+ *   the provers - the same trust domain as the caller of h2v_verify_batch_rlc.  It is NOT a proof for third parties.  DERIVED SEED
+ *   (H2V_RLC_SEED_TRANSCRIPT, single-key form): nothing has to be kept from the provers - in the random-oracle model for blake2b a
+ *   prover making q hash evaluations gets a rejecting proof into an accepting pair with probability at most q / 2^128 - and anyone
+ *   who holds the same key, the same inputs and the same chunk size recomputes the same seed and the same pair (seed.py), so a
+ *   pair can be compared between nodes and re-derived by an auditor.  It is still not a succinct proof for someone without the
+ *   inputs.  Whoever combines the pairs of several
  *   calls must scale them again with fresh coefficients - which is what h2v_check_pairs_rlc does; adding pairs unscaled lets the
  *   errors of two calls cancel (tests/test_aggregate_gpu.py). */
 #define H2V_BATCH_NOT_CHECKED 2u  /* h2v_workspace_rlc_result: batch_accepted of an aggregate call */
@@ -540,8 +575,12 @@ typedef struct {
     uint32_t chunk;          /* 0 on an ordinary workspace and for the mixed form; else the chunk size that cut the call (coefficients follow it) */
     uint32_t n_chunks;       /* 1 on an ordinary workspace and for the mixed form (and for n = 0 on any workspace) */
     uint32_t msm_terms;      /* terms of the right-hand bucket MSM(s), summed over chunks */
-    uint32_t reserved;
+    uint32_t reserved;       /* the SEED SOURCE, under the name the word has always had (callers that zero `reserved` keep compiling; read it
+                              * as H2V_AGGREGATE_SEED_SOURCE(info)).  0: seed_used was drawn or given; 1: derived (H2V_RLC_SEED_TRANSCRIPT) -
+                              * the host form fills seed_used from its download, the device form writes zeros (the seed is not known
+                              * when the call returns: h2v_workspace_seed_used has it once the stream is synchronised) */
 } h2v_aggregate_info;        /* HOST memory, written before the call returns, in both forms; may be NULL */
+#define H2V_AGGREGATE_SEED_SOURCE(info) ((info)->reserved)   /* seed_source: 0 drawn or given, 1 derived */
 int h2v_aggregate_batch(const h2v_plan *plan, const h2v_batch *batch, uint8_t pair[96], uint8_t *included /* n */, uint32_t *status /* or NULL */,
                         h2v_workspace *ws /* or NULL */, const h2v_rlc_opts *opts /* or NULL */, h2v_aggregate_info *info /* or NULL */);
 int h2v_aggregate_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_t *pair, uint8_t *included, uint32_t *status,
@@ -605,6 +644,12 @@ int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uint8_t *msgs,
  * under a key (the key block is then the final block) is hashed on the device from the start. */
 int h2v_probe_blake2b_ex(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint32_t digest_len, const uint8_t *key,
                          uint32_t key_len, uint8_t *digests);
+/* The digest kernels of a derived seed (H2V_RLC_SEED_TRANSCRIPT) ALONE, as the calls queue them, on bytes that need not be proofs:
+ * form 1 - batch as for h2v_verify_batch, n_pi rows of 32 instance bytes and n_ci (0 / 1) rows of 48 committed bytes per proof;
+ * form 2 - batch->proofs holds n x 96 bytes, proof_off / instances / committed are ignored.  Host buffers; the proof bytes go up
+ * at the alignment proof_off[0] has (mod 16).  seed: the 32 bytes.  n = 0 or n > 2^22: H2V_E_ARG. */
+int h2v_probe_batch_seed(int device, uint32_t form, const uint8_t key_tag[32], const h2v_batch *batch /* host buffers */, uint32_t n_pi,
+                         uint32_t n_ci, uint8_t seed[32]);
 int h2v_probe_g1_decompress(int device, uint32_t n, const uint8_t *compressed, uint8_t *xy_be, uint8_t *valid);
 /* sum_t s_t * B_t per group: n groups of T terms; scalars n*T*32 B LE, bases n*T*48 B compressed; out n*96 B affine BE */
 int h2v_probe_g1_msm(int device, uint32_t n, uint32_t T, const uint8_t *scalars, const uint8_t *bases_compressed,

@@ -221,29 +221,35 @@ inline PairVerdicts check_pairs(const VerifyingKey &vk, const std::vector<uint8_
 // check_pairs with ONE pairing for the batch (h2v_check_pairs_rlc): the reference's "scale each DualMSM by a random coefficient,
 // add, check once" (examples/ivc.rs:85-96).  The same accept / status as check_pairs; fell_back (optional): the batch check
 // failed and the per-pair kernels produced them.  seed: 32 bytes that provers cannot predict, or nullptr = drawn from the OS.
+// derive_seed (H2V_RLC_SEED_TRANSCRIPT; not beside `seed`): the seed is a digest of the key and the pairs - nothing is drawn.
 inline PairVerdicts check_pairs_rlc(const VerifyingKey &vk, const std::vector<uint8_t> &pairs, h2v_workspace *ws = nullptr,
-                                    const uint8_t *seed = nullptr, bool *fell_back = nullptr) {
+                                    const uint8_t *seed = nullptr, bool *fell_back = nullptr, bool derive_seed = false) {
     if (pairs.size() % 96) throw Error(H2V_E_ARG, "pairs: a multiple of 96 bytes");
     const uint64_t n = pairs.size() / 96;
     PairVerdicts r{std::vector<uint8_t>(n), std::vector<uint32_t>(n)};
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
+    if (derive_seed) opts.flags |= H2V_RLC_SEED_TRANSCRIPT;
     int fb = 0;
-    check(h2v_check_pairs_rlc(vk.handle(), n, pairs.data(), r.accept.data(), r.status.data(), ws, seed ? &opts : nullptr, &fb));
+    check(h2v_check_pairs_rlc(vk.handle(), n, pairs.data(), r.accept.data(), r.status.data(), ws, (seed || derive_seed) ? &opts : nullptr, &fb));
     if (fell_back) *fell_back = fb != 0;
     return r;
 }
 // The same vector through the batch-accept fast path (one random linear combination of the batch's pairing equations:
 // one bucketed G1 MSM + one pairing; the per-proof kernels only if the batch check fails).  fell_back (optional) tells
 // which of the two produced the vector.  seed: 32 bytes that provers cannot predict, or nullptr = drawn from the OS.
+// derive_seed (H2V_RLC_SEED_TRANSCRIPT; not beside `seed`): the seed is a digest of the key and the batch (h2v.h has the rule):
+// nothing is drawn, nothing has to be kept from the provers, and the call is reproducible.
 inline std::vector<uint8_t> verify_batch_rlc(const VerifyingKey &vk, const h2v_batch &batch, h2v_workspace *ws = nullptr,
-                                             bool *fell_back = nullptr, const uint8_t *seed = nullptr, bool fold_pairs = false) {
+                                             bool *fell_back = nullptr, const uint8_t *seed = nullptr, bool fold_pairs = false,
+                                             bool derive_seed = false) {
     std::vector<uint8_t> accept(batch.n);
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
     if (fold_pairs) opts.flags |= H2V_RLC_FOLD_PAIRS;   // recursive keys: combine the pairs the fold leaves (ignored by other keys)
+    if (derive_seed) opts.flags |= H2V_RLC_SEED_TRANSCRIPT;
     int fb = 0;
-    check(h2v_verify_batch_rlc(vk.handle(), &batch, accept.data(), ws, (seed || fold_pairs) ? &opts : nullptr, &fb));
+    check(h2v_verify_batch_rlc(vk.handle(), &batch, accept.data(), ws, (seed || fold_pairs || derive_seed) ? &opts : nullptr, &fb));
     if (fell_back) *fell_back = fb != 0;
     return accept;
 }
@@ -291,11 +297,15 @@ struct Aggregate {
     std::vector<uint32_t> status;
     h2v_aggregate_info info;
 };
-inline Aggregate aggregate_batch(const VerifyingKey &vk, const h2v_batch &batch, h2v_workspace *ws = nullptr, const uint8_t *seed = nullptr) {
+// derive_seed (aggregate_batch; H2V_RLC_SEED_TRANSCRIPT): H2V_AGGREGATE_SEED_SOURCE(&info) = 1 and info.seed_used is a digest of
+// the key and the batch, so that anyone who holds the same inputs recomputes the same pair.
+inline Aggregate aggregate_batch(const VerifyingKey &vk, const h2v_batch &batch, h2v_workspace *ws = nullptr, const uint8_t *seed = nullptr,
+                                 bool derive_seed = false) {
     Aggregate r{{}, std::vector<uint8_t>(batch.n ? batch.n : 1), std::vector<uint32_t>(batch.n ? batch.n : 1), {}};
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
-    check(h2v_aggregate_batch(vk.handle(), &batch, r.pair, r.included.data(), r.status.data(), ws, seed ? &opts : nullptr, &r.info));
+    if (derive_seed) opts.flags |= H2V_RLC_SEED_TRANSCRIPT;
+    check(h2v_aggregate_batch(vk.handle(), &batch, r.pair, r.included.data(), r.status.data(), ws, (seed || derive_seed) ? &opts : nullptr, &r.info));
     r.included.resize(batch.n); r.status.resize(batch.n);
     return r;
 }
@@ -321,7 +331,8 @@ inline Aggregate aggregate_mixed(const std::vector<const VerifyingKey *> &vks, c
 // (aggregate_mixed; Aggregator(true): its grouped form) and is verified again, if its pair fails, with verify_mixed.
 class Aggregator {
   public:
-    explicit Aggregator(bool grouped = false) : grouped_(grouped) {}
+    /// derive_seed: every push derives its seed from its key and batch; single-key pushes only (push_mixed: Error(H2V_E_ARG))
+    explicit Aggregator(bool grouped = false, bool derive_seed = false) : grouped_(grouped), derive_seed_(derive_seed) {}
     Aggregator(const Aggregator &) = delete;
     Aggregator &operator=(const Aggregator &) = delete;
     /// one SRS per Aggregator - that of the first key pushed: a key on another SRS is Error(H2V_E_ARG), before anything runs
@@ -332,7 +343,7 @@ class Aggregator {
         if (same != 1) throw Error(H2V_E_ARG, "Aggregator: this key is on another SRS than the keys pushed before (s_g2 differs)");
         Call c;
         c.vk = &vk;
-        const Aggregate a = aggregate_batch(vk, b, nullptr, seed);
+        const Aggregate a = aggregate_batch(vk, b, nullptr, seed, derive_seed_);
         for (int k = 0; k < 96; k++) c.pair[k] = a.pair[k];
         c.included = a.included;
         c.off.assign(b.proof_off, b.proof_off + b.n + 1);
@@ -345,6 +356,7 @@ class Aggregator {
         return calls_.size() - 1;
     }
     size_t push_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &b, const uint8_t *seed = nullptr) {
+        if (derive_seed_) throw Error(H2V_E_ARG, "Aggregator: derive_seed takes single-key pushes only (the mixed calls have no derived seed)");
         if (vks.empty() || !vks[0]) throw Error(H2V_E_ARG, "Aggregator: no key");
         if (!srs_) srs_ = vks[0];
         for (const VerifyingKey *k : vks) {
@@ -406,7 +418,7 @@ class Aggregator {
     };
     std::vector<Call> calls_;
     const VerifyingKey *srs_ = nullptr;
-    bool grouped_ = false;
+    bool grouped_ = false, derive_seed_ = false;
 };
 
 // A reusable workspace, and the streaming form: submit() returns once the batch is copied and everything is enqueued,

@@ -98,19 +98,23 @@ class Verifier:
 
     def verify_batch(self, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
                      committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof",
-                     seed: Optional[bytes] = None, fold_pairs: bool = False) -> List[bool]:
+                     seed: Optional[bytes] = None, fold_pairs: bool = False, derive_seed: bool = False) -> List[bool]:
         """accept[i] for n independent proofs of this circuit (instances[i]: the public-input scalars of proof i;
         committed[i]: its committed instance as 48 compressed bytes, when the circuit has one).
         mode="rlc": the batch-accept fast path (one bucket MSM + one pairing for the batch, per-proof kernels only if
         the batch check fails; same accept vector up to a 2^-128 soundness error over `seed`, drawn from the OS when None).
-        fold_pairs (mode="rlc", recursive circuits): combine the pairs the fold leaves instead of one pairing per proof."""
+        fold_pairs (mode="rlc", recursive circuits): combine the pairs the fold leaves instead of one pairing per proof.
+        derive_seed (mode="rlc"; H2V_RLC_SEED_TRANSCRIPT): the seed is a digest of the key and the batch (seed.batch_seed) - nothing
+        is drawn, nothing has to be kept from the provers, and the call is reproducible; not together with `seed`."""
+        if derive_seed and mode != "rlc":
+            raise ValueError("derive_seed needs mode='rlc'")
         n = len(proofs)
         if n == 0:
             return []
         proofs_b, off, inst, ci = self._pack(proofs, instances, committed)
         if mode == "rlc":
             acc, _fell_back = self.device_plan.verify_batch_rlc(proofs_b, off, inst, ci, ws=self._workspace(n), seed=seed,
-                                                                   fold_pairs=fold_pairs)
+                                                                   fold_pairs=fold_pairs, derive_seed=derive_seed)
         elif mode == "per-proof":
             acc = self.device_plan.verify_batch(proofs_b, off, inst, ci, ws=self._workspace(n))
         else:
@@ -128,12 +132,15 @@ class Verifier:
         raw, st = self.device_plan.prepare_batch(*self._pack(proofs, instances, committed), ws=self._workspace(n))
         return [raw[96 * i:96 * i + 96] for i in range(n)], st
 
-    def check_pairs(self, pairs: Sequence[bytes], mode: str = "per-pair", seed: Optional[bytes] = None):
+    def check_pairs(self, pairs: Sequence[bytes], mode: str = "per-pair", seed: Optional[bytes] = None, derive_seed: bool = False):
         """The second half: (accept, status) for pairs compress(L) || compress(R) from anywhere (h2v_check_pairs).
         mode="rlc" (h2v_check_pairs_rlc): the same outputs from ONE pairing for the batch - "scale each DualMSM by a random
-        coefficient, add, check once" - with the per-pair kernels only behind a failed check."""
+        coefficient, add, check once" - with the per-pair kernels only behind a failed check.  derive_seed (mode="rlc"): the
+        coefficients follow from a digest of the key and the pairs (seed.pairs_seed), as for verify_batch."""
         if mode not in ("per-pair", "rlc"):
             raise ValueError("mode is 'per-pair' or 'rlc'")
+        if derive_seed and mode != "rlc":
+            raise ValueError("derive_seed needs mode='rlc'")
         n = len(pairs)
         if n == 0:
             return [], []
@@ -141,21 +148,23 @@ class Verifier:
             raise ValueError("a pair is 96 bytes: compress(L) || compress(R)")
         raw = b"".join(bytes(p) for p in pairs)
         if mode == "rlc":
-            acc, st, _fell_back = self.device_plan.check_pairs_rlc(raw, ws=self._workspace(n), seed=seed)
+            acc, st, _fell_back = self.device_plan.check_pairs_rlc(raw, ws=self._workspace(n), seed=seed, derive_seed=derive_seed)
         else:
             acc, st = self.device_plan.check_pairs(raw, ws=self._workspace(n))
         return [bool(a) for a in acc], st
 
     def aggregate_batch(self, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
-                        committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None):
+                        committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None, derive_seed: bool = False):
         """The batch's ONE pair instead of a verdict (h2v_aggregate_batch): (pair, included, status, info).  pair = compress(L) ||
         compress(R) with L = sum r_i L_i, R = sum r_i R_i over the included proofs - the reference's DualMSM of the batch, scaled
         and added, not yet checked; included[i] = "not rejected before the pairing" (not a verdict: an included proof is accepted
         iff the pair's equation holds); status as prepare_batch; info = backend.AggregateInfo.  check_pairs checks the pair -
-        with mode="rlc" many of them in one pairing (Aggregator does that).  seed: tests only, as for verify_batch."""
+        with mode="rlc" many of them in one pairing (Aggregator does that).  seed: tests only, as for verify_batch.  derive_seed:
+        the seed is a digest of the key and the batch (seed.batch_seed; info.seed_source = 1, info.seed_used has it), so that
+        anyone with the same inputs recomputes the same pair."""
         n = len(proofs)      # (n = 0 goes through the library too: (inf, inf), and the info carries the call's seed and n_chunks = 1)
         pair, inc, st, info = self.device_plan.aggregate_batch(*self._pack(proofs, instances, committed), ws=self._workspace(n) if n else None,
-                                                               seed=seed)
+                                                               seed=seed, derive_seed=derive_seed)
         return pair, [bool(a) for a in inc], st, info
 
     def _pack(self, proofs, instances, committed):
@@ -379,9 +388,11 @@ class Aggregator:
     kept.  The pairs of different calls are scaled again with fresh coefficients by the check, so the errors of two calls cannot
     cancel.  A pair is only worth what the seed of its call is: keep an Aggregator inside one trust domain."""
 
-    def __init__(self, params: ParamsVerifierKZG, device: int = 0, grouped: bool = False):
-        """grouped: push_mixed runs phase 1 of every key in one launch per kernel (H2V_RLC_GROUPED) - the same pairs"""
-        self.params, self.device, self.grouped = params, device, grouped
+    def __init__(self, params: ParamsVerifierKZG, device: int = 0, grouped: bool = False, derive_seed: bool = False):
+        """grouped: push_mixed runs phase 1 of every key in one launch per kernel (H2V_RLC_GROUPED) - the same pairs.
+        derive_seed: every push derives its seed from its key and batch (H2V_RLC_SEED_TRANSCRIPT): its pair can be recomputed by
+        anyone who holds the inputs.  Single-key pushes only: push_mixed raises ValueError (the mixed calls have no derived seed)."""
+        self.params, self.device, self.grouped, self.derive_seed = params, device, grouped, derive_seed
         self._calls = []      # (a verifier on the SRS, pair, included, the call again per proof -> accept list)
 
     def push(self, vk: VerifyingKey, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
@@ -390,7 +401,7 @@ class Aggregator:
         if bytes(self.params.s_g2) != bytes.fromhex(vk.s_g2):
             raise ValueError("verifier params do not match the verifying key's SRS (s_g2 differs)")
         v = verifier_for(vk, self.device)
-        pair, included, _status, _info = v.aggregate_batch(proofs, instances, committed, seed=seed)
+        pair, included, _status, _info = v.aggregate_batch(proofs, instances, committed, seed=seed, derive_seed=self.derive_seed)
         self._calls.append((v, pair, included, lambda: v.verify_batch(proofs, instances, committed)))
         return len(self._calls) - 1
 
@@ -398,6 +409,8 @@ class Aggregator:
                    committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None) -> int:
         """aggregates one call of proofs of SEVERAL keys, proof i under vks[i] (h2v_aggregate_mixed; with grouped=True the
         H2V_RLC_GROUPED form: up to backend.MIXED_GROUPED_MAX_PLANS keys); returns the call's index"""
+        if self.derive_seed:
+            raise ValueError("an Aggregator with derive_seed takes single-key pushes only: the mixed calls have no derived seed")
         for i, vk in enumerate(vks):
             if bytes(self.params.s_g2) != bytes.fromhex(vk.s_g2):
                 raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)

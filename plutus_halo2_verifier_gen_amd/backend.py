@@ -58,7 +58,12 @@ class RlcTimings(C.Structure):
 class AggregateInfo(C.Structure):
     """h2v_aggregate_info (include/h2v.h): what is needed to recompute the coefficients of an aggregate call"""
     _fields_ = [("seed_used", C.c_uint8 * 32), ("chunk", C.c_uint32), ("n_chunks", C.c_uint32), ("msm_terms", C.c_uint32),
-                ("reserved", C.c_uint32)]
+                ("reserved", C.c_uint32)]        # the seed source, under the header's name for the word
+
+    @property
+    def seed_source(self) -> int:
+        """0: seed_used was drawn or given; 1: derived (RLC_SEED_TRANSCRIPT) - H2V_AGGREGATE_SEED_SOURCE of the header"""
+        return self.reserved
 
 
 class PlanOpts(C.Structure):
@@ -80,6 +85,7 @@ RLC_SEED_GIVEN = 1
 RLC_ONE_STREAM = 2
 RLC_FOLD_PAIRS = 4   # recursive plans: combine the pairs (el', er') the fold leaves (include/h2v.h)
 RLC_GROUPED = 16     # h2v_aggregate_mixed(_device) only: the MIXED_GROUPED form of the call (bit 8 stays unknown)
+RLC_SEED_TRANSCRIPT = 32   # the seed is derived from the batch itself (seed.py has the rule); never beside RLC_SEED_GIVEN
 SUBMIT_RLC = 1
 MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
 MIXED_FOLD_MSM = 2     # ... and ONE bucket MSM over the call's per-proof terms (only together with MIXED_RLC)
@@ -90,10 +96,12 @@ MIXED_GROUPED_MAX_OTHER = 62     # H2V_MIXED_GROUPED_MAX_OTHER: ... of which pla
 BATCH_NOT_CHECKED = 2  # H2V_BATCH_NOT_CHECKED: batch_accepted of an aggregate call (Workspace.rlc_verdict)
 
 
-def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False, grouped: bool = False):
-    if seed is None and not one_stream and not fold_pairs and not grouped:
+def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False, grouped: bool = False, derive_seed: bool = False):
+    """derive_seed beside a seed goes to the library as it is: the library answers H2V_E_ARG"""
+    if seed is None and not one_stream and not fold_pairs and not grouped and not derive_seed:
         return None
-    flags = (RLC_ONE_STREAM if one_stream else 0) | (RLC_FOLD_PAIRS if fold_pairs else 0) | (RLC_GROUPED if grouped else 0)
+    flags = ((RLC_ONE_STREAM if one_stream else 0) | (RLC_FOLD_PAIRS if fold_pairs else 0) | (RLC_GROUPED if grouped else 0) |
+             (RLC_SEED_TRANSCRIPT if derive_seed else 0))
     if seed is None:
         return RlcOpts((C.c_uint8 * 32)(), flags)
     seed = bytes(seed)
@@ -117,6 +125,7 @@ EXPORTS = [
     "h2v_plan_transcript", "h2v_probe_blake2b_ex",
     "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums", "h2v_probe_decompress",
     "h2v_aggregate_batch", "h2v_aggregate_batch_device", "h2v_aggregate_mixed", "h2v_aggregate_mixed_device", "h2v_plan_same_srs",
+    "h2v_workspace_seed_used", "h2v_workspace_seed_ms", "h2v_probe_batch_seed", "h2v_plan_key_tag",
 ]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
@@ -207,6 +216,10 @@ def lib():
                                               C.c_void_p, C.c_uint32, C.POINTER(RlcOpts)]
         L.h2v_probe_mixed_fold_sums.argtypes = [C.c_void_p, C.c_void_p]
         L.h2v_plan_same_srs.argtypes = [C.c_void_p, C.c_void_p]
+        L.h2v_workspace_seed_used.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.h2v_workspace_seed_ms.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        L.h2v_probe_batch_seed.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.POINTER(Batch), C.c_uint32, C.c_uint32, C.c_void_p]
+        L.h2v_plan_key_tag.argtypes = [C.c_void_p, C.c_void_p]
         L.h2v_aggregate_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RlcOpts),
                                           C.POINTER(AggregateInfo)]
         L.h2v_aggregate_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -278,6 +291,9 @@ class DevicePlan:
         check(lib().h2v_plan_transcript(self._h, C.byref(kind), key, C.byref(klen)))
         # the transcript hash of the plan's key (TRANSCRIPT_*) and its blake2b key: what api.prepare holds a transcript's tag against
         self.transcript_kind, self.transcript_key = kind.value, key.raw[:klen.value]
+        tag = C.create_string_buffer(32)
+        check(lib().h2v_plan_key_tag(self._h, tag))
+        self.key_tag = tag.raw      # seed.key_tag(plan_bytes): what a derived batch seed binds the key with
 
     @property
     def handle(self):
@@ -326,28 +342,30 @@ class DevicePlan:
         return b, keep
 
     def submit(self, batch: "Batch", ws, rlc: bool = False, seed: Optional[bytes] = None, one_stream: bool = False,
-               fold_pairs: bool = False):
+               fold_pairs: bool = False, derive_seed: bool = False):
         """h2v_verify_batch_submit: copy + upload + verification + download enqueued on the workspace's stream."""
-        opts = _rlc_opts(seed, one_stream, fold_pairs)
+        opts = _rlc_opts(seed, one_stream, fold_pairs, derive_seed=derive_seed)
         check(lib().h2v_verify_batch_submit(self._h, C.byref(batch), ws.handle, SUBMIT_RLC if rlc else 0,
                                             C.byref(opts) if opts is not None else None))
 
     def verify_batch_rlc(self, proofs: bytes, proof_off, instances: bytes, committed: Optional[bytes], ws=None,
-                         seed: Optional[bytes] = None, fold_pairs: bool = False):
+                         seed: Optional[bytes] = None, fold_pairs: bool = False, derive_seed: bool = False):
         """Batch-accept fast path (h2v_verify_batch_rlc): returns (accept bytes, fell_back).  fold_pairs (RLC_FOLD_PAIRS):
-        the batch form of recursive plans, which starts after the fold; ignored by any other plan."""
+        the batch form of recursive plans, which starts after the fold; ignored by any other plan.  derive_seed
+        (RLC_SEED_TRANSCRIPT): the seed is a digest of the batch (seed.batch_seed); ws.seed_used() has it afterwards."""
         n, b, _keep = self._host_batch(proofs, proof_off, instances, committed)
         acc = (C.c_uint8 * max(1, n))()
         fb = C.c_int(0)
-        opts = _rlc_opts(seed, fold_pairs=fold_pairs)
+        opts = _rlc_opts(seed, fold_pairs=fold_pairs, derive_seed=derive_seed)
         check(lib().h2v_verify_batch_rlc(self._h, C.byref(b), acc, ws.handle if ws else None,
                                          C.byref(opts) if opts is not None else None, C.byref(fb)))
         return bytes(acc[:n]), bool(fb.value)
 
     def verify_batch_rlc_device(self, n, d_proofs, d_off, d_inst, d_ci, d_accept, d_status=None, ws=None, stream=None,
-                                seed: Optional[bytes] = None, one_stream: bool = False, fold_pairs: bool = False):
+                                seed: Optional[bytes] = None, one_stream: bool = False, fold_pairs: bool = False,
+                                derive_seed: bool = False):
         b = Batch(n, d_proofs, d_off, d_inst, d_ci)
-        opts = _rlc_opts(seed, one_stream, fold_pairs)
+        opts = _rlc_opts(seed, one_stream, fold_pairs, derive_seed=derive_seed)
         check(lib().h2v_verify_batch_rlc_device(self._h, C.byref(b), d_accept, d_status, ws.handle if ws else None, stream,
                                                 C.byref(opts) if opts is not None else None))
 
@@ -389,7 +407,7 @@ class DevicePlan:
         """h2v_check_pairs_device: enqueues on `stream`"""
         check(lib().h2v_check_pairs_device(self._h, n, d_pairs, d_accept, d_status, ws.handle if ws else None, stream))
 
-    def check_pairs_rlc(self, pairs: bytes, ws=None, seed: Optional[bytes] = None):
+    def check_pairs_rlc(self, pairs: bytes, ws=None, seed: Optional[bytes] = None, derive_seed: bool = False):
         """h2v_check_pairs_rlc: (accept bytes, status, fell_back) - check_pairs's outputs with ONE pairing for the batch
         when every decoded pair's equation holds; fell_back: the batch check failed and the per-pair kernels ran."""
         if len(pairs) % 96:
@@ -398,20 +416,21 @@ class DevicePlan:
         acc = (C.c_uint8 * max(1, n))()
         st = (C.c_uint32 * max(1, n))()
         fb = C.c_int(0)
-        opts = _rlc_opts(seed)
+        opts = _rlc_opts(seed, derive_seed=derive_seed)
         check(lib().h2v_check_pairs_rlc(self._h, n, bytes(pairs), acc, st, ws.handle if ws else None,
                                         C.byref(opts) if opts is not None else None, C.byref(fb)))
         return bytes(acc[:n]), list(st[:n]), bool(fb.value)
 
-    def check_pairs_rlc_device(self, n, d_pairs, d_accept, d_status=None, ws=None, stream=None, seed: Optional[bytes] = None):
+    def check_pairs_rlc_device(self, n, d_pairs, d_accept, d_status=None, ws=None, stream=None, seed: Optional[bytes] = None,
+                               derive_seed: bool = False):
         """h2v_check_pairs_rlc_device: enqueues on `stream`; ws.rlc_result() has the batch verdict afterwards"""
-        opts = _rlc_opts(seed)
+        opts = _rlc_opts(seed, derive_seed=derive_seed)
         check(lib().h2v_check_pairs_rlc_device(self._h, n, d_pairs, d_accept, d_status, ws.handle if ws else None, stream,
                                                C.byref(opts) if opts is not None else None))
 
     # ---- aggregate calls: the batch's ONE pair instead of a pairing on it (include/h2v.h: h2v_aggregate_batch)
     def aggregate_batch(self, proofs: bytes, proof_off, instances: bytes, committed: Optional[bytes], ws=None,
-                        seed: Optional[bytes] = None, one_stream: bool = False):
+                        seed: Optional[bytes] = None, one_stream: bool = False, derive_seed: bool = False):
         """h2v_aggregate_batch: (pair, included, status, info) - pair = 96 bytes compress(L) || compress(R) with L = sum r_i L_i,
         R = sum r_i R_i over the included proofs; included = n bytes, 1 = not rejected before the pairing (NOT a verdict);
         status = h2v_prepare_batch's; info = an AggregateInfo (the seed and the chunking the coefficients follow)."""
@@ -420,18 +439,18 @@ class DevicePlan:
         inc = (C.c_uint8 * max(1, n))()
         st = (C.c_uint32 * max(1, n))()
         info = AggregateInfo()
-        opts = _rlc_opts(seed, one_stream)
+        opts = _rlc_opts(seed, one_stream, derive_seed=derive_seed)
         check(lib().h2v_aggregate_batch(self._h, C.byref(b), pair, inc, st, ws.handle if ws else None,
                                         C.byref(opts) if opts is not None else None, C.byref(info)))
         return pair.raw, bytes(inc[:n]), list(st[:n]), info
 
     def aggregate_batch_device(self, n, d_proofs, d_off, d_inst, d_ci, d_pair, d_included, d_status=None, ws=None, stream=None,
-                               seed: Optional[bytes] = None, one_stream: bool = False) -> AggregateInfo:
+                               seed: Optional[bytes] = None, one_stream: bool = False, derive_seed: bool = False) -> AggregateInfo:
         """h2v_aggregate_batch_device: enqueues on `stream`; d_pair = 96 bytes of device memory (4-byte aligned), d_included = n.
         Returns the call's AggregateInfo (host memory, filled in before the call returns)."""
         b = Batch(n, d_proofs, d_off, d_inst, d_ci)
         info = AggregateInfo()
-        opts = _rlc_opts(seed, one_stream)
+        opts = _rlc_opts(seed, one_stream, derive_seed=derive_seed)
         check(lib().h2v_aggregate_batch_device(self._h, C.byref(b), d_pair, d_included, d_status, ws.handle if ws else None, stream,
                                                C.byref(opts) if opts is not None else None, C.byref(info)))
         return info
@@ -545,6 +564,19 @@ class Workspace:
         tm = RlcTimings() if timings else None
         check(lib().h2v_workspace_rlc_result(self._h, calls_back, C.byref(ok), C.byref(tm) if timings else None))
         return bool(ok.value), tm
+
+    def seed_used(self, calls_back: int = 0) -> bytes:
+        """h2v_workspace_seed_used: the 32-byte seed a past call with derive_seed derived; synchronise its stream first.  Raises
+        H2VError for a call that derived nothing."""
+        out = C.create_string_buffer(32)
+        check(lib().h2v_workspace_seed_used(self._h, calls_back, out))
+        return out.raw
+
+    def seed_ms(self, calls_back: int = 0) -> float:
+        """h2v_workspace_seed_ms: device time of that call's digest launches"""
+        ms = C.c_float(0)
+        check(lib().h2v_workspace_seed_ms(self._h, calls_back, C.byref(ms)))
+        return ms.value
 
     def rlc_verdict(self, calls_back: int = 0) -> int:
         """batch_accepted of h2v_workspace_rlc_result as the library reports it: 1 passed, 0 failed / routed, BATCH_NOT_CHECKED (2)
@@ -672,6 +704,26 @@ def probe_mixed_fold_sums(ws):
     out = C.create_string_buffer(192)
     check(lib().h2v_probe_mixed_fold_sums(ws.handle, out))
     return _unxy(out.raw[:96]), _unxy(out.raw[96:])
+
+
+def probe_batch_seed(form: int, key_tag: bytes, proofs: bytes, proof_off=None, instances: Optional[bytes] = None,
+                     committed: Optional[bytes] = None, n_pi: int = 0, n_ci: int = 0, device: int = 0) -> bytes:
+    """h2v_probe_batch_seed: the digest kernels of a derived seed alone, on bytes that need not be proofs.  form 1: proof i =
+    proofs[proof_off[i] : proof_off[i + 1]] with n_pi x 32 instance bytes and n_ci x 48 committed bytes; form 2: n = len(proofs) /
+    96 pairs.  Returns the 32-byte seed (seed.batch_seed states the same)."""
+    if form == 2:
+        n, off = len(proofs) // 96, None
+    else:
+        n = len(proof_off) - 1
+        off = (C.c_uint64 * (n + 1))(*proof_off)
+    pbuf = C.create_string_buffer(proofs, len(proofs)) if proofs else C.create_string_buffer(1)
+    ibuf = C.create_string_buffer(instances, len(instances)) if instances else None
+    cbuf = C.create_string_buffer(committed, len(committed)) if committed else None
+    b = Batch(n, C.cast(pbuf, C.c_void_p), C.cast(off, C.c_void_p) if off is not None else None,
+              C.cast(ibuf, C.c_void_p) if ibuf is not None else None, C.cast(cbuf, C.c_void_p) if cbuf is not None else None)
+    out = C.create_string_buffer(32)
+    check(lib().h2v_probe_batch_seed(device, form, bytes(key_tag), C.byref(b), n_pi, n_ci, out))
+    return out.raw
 
 
 # ---- primitive probes (GPU parity tests)

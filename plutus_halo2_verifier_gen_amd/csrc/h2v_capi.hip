@@ -25,6 +25,7 @@
 #include "h2v_msm_shape.hpp"
 #include "h2v_pairing_engine.hpp"
 #include "h2v_hostcall_layout.hpp"
+#include "h2v_seed.hpp"
 #include "h2v_mixed_tables.hpp"
 #include "h2v_plancc.hpp"
 
@@ -153,6 +154,7 @@ struct h2v_plan {
     uint8_t tr_key[H2V_TR_KEY_MAX] = {};
     uint64_t gen = 0;            // process-wide load counter: what caches key on (a freed plan's address may be reused)
     uint64_t sg2_digest[2] = {}; // of the s_g2 line-table section of the blob: plans of ONE SRS agree in it (h2v_verify_mixed)
+    uint8_t key_tag[32] = {};    // blake2b-256(TAG key || the plan blob): what a derived batch seed binds the key with (h2v_seed.hpp)
     std::vector<uint32_t> trace_slots;
 };
 
@@ -277,6 +279,7 @@ struct h2v_workspace {
         bool no_vm = false;        // an RLC call over pairs from anywhere: no transcript ran (transcript_combiner_ms = 0)
         bool routed = false;       // an RLC call sent straight to the per-proof kernels (rlc_route): per-proof times, no batch check
         bool agg = false;          // an aggregate call (h2v_aggregate_batch / _mixed): the sums were exported, no pairing ran ("not checked")
+        bool derived = false;      // its seed was derived from the batch (H2V_RLC_SEED_TRANSCRIPT): seed_ring holds it
         bool co = false, ran = false;   // coalesced (coalesce_call); its group has run - only then is the rest filled in (co_flush_lane)
         float share = 0.0f;        // coalesced: its proofs / the group's
         // ordinary workspace: the event set, created with the workspace.  Per proof (run_pipeline; run_check a subset):
@@ -294,6 +297,13 @@ struct h2v_workspace {
     CallRec rec[RING];
     uint64_t calls = 0;
     uint32_t *rec_fail = nullptr;   // RING device words: failed batch checks of record k at [k % RING] (RLC calls; rlc_stats_ensure)
+    // derived seeds (H2V_RLC_SEED_TRANSCRIPT; seed_enqueue): RING slots of 8 device dwords, the seed of record k at [k % RING] as
+    // rec_fail is indexed - it outlives the call's kernels; the digest buffer of the call being derived (h2v_seed.hpp: Tree), which
+    // the next derivation reuses behind ev_seed[..][1] of this one; per slot the two timed events around the digest launches
+    uint32_t *seed_ring = nullptr;
+    GrowBuf<false> seed_digests;
+    hipEvent_t ev_seed[RING][2] = {};
+    hipEvent_t ev_seed_last = nullptr;      // the end of the most recent derivation (one of ev_seed[..][1])
     struct RlcWs *rlc = nullptr;   // buffers of the RLC batch mode, created by its first call
     struct RlcWs *prlc = nullptr;  // the pair-RLC set (h2v_check_pairs_rlc, H2V_RLC_FOLD_PAIRS): created by the first such call
     hipEvent_t ev_pipe[12] = {};   // H2V_RLC_FOLD_PAIRS: the pipeline's own markers (the record's events carry the RLC layout)
@@ -642,6 +652,10 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
     }
     d.fix_tab = (const uint32_t *)p->fix_tab; d.n_var = p->n_var; d.n_fix = p->n_fix;
     digest_section(blob + w[H2V_HW_OFF_LINES28_SG2], 512u * H2V_MILLER_LINES, p->sg2_digest);
+    {
+        const h2vseed::TagWords kt = h2vseed::tag_words(h2vseed::TAG_KEY);
+        h2vhost::b2_256_host((const uint8_t *)kt.w, h2vseed::TAG_BYTES, blob, len, p->key_tag);
+    }
     p->n_squeezes = n_sq;
     p->stream_len = w[H2V_HW_STREAM_LEN];
     for (uint32_t k = 0; k < n_trace; k++) p->trace_slots.push_back(rd32(trp + 8 * k));
@@ -678,6 +692,11 @@ extern "C" int h2v_plan_transcript(const h2v_plan *p, uint32_t *kind, uint8_t ke
     if (kind) *kind = p->tr_kind;
     if (key_out) { memset(key_out, 0, H2V_TR_KEY_MAX); memcpy(key_out, p->tr_key, p->tr_key_len); }
     if (key_len) *key_len = p->tr_key_len;
+    return H2V_OK;
+}
+extern "C" int h2v_plan_key_tag(const h2v_plan *p, uint8_t out[32]) {
+    if (!p || !out) return fail(H2V_E_ARG, "null argument");
+    memcpy(out, p->key_tag, 32);
     return H2V_OK;
 }
 extern "C" int h2v_plan_same_srs(const h2v_plan *a, const h2v_plan *b) {
@@ -727,6 +746,10 @@ static void ws_release(h2v_workspace *w) {
     for (void *q : ptrs) if (q) (void)hipFree(q);
     w->res.release(); w->agg_parts.release();
     for (hipEvent_t &e : w->ev_agg) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    if (w->seed_ring) { (void)hipFree(w->seed_ring); w->seed_ring = nullptr; }
+    w->seed_digests.release();
+    for (auto &pair : w->ev_seed) for (hipEvent_t &e : pair) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    w->ev_seed_last = nullptr;
     if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
     if (w->copy_streams_owned) {
         if (w->hs) (void)hipStreamDestroy(w->hs);
@@ -1447,6 +1470,13 @@ struct Unit {
     const MixedFold *fold = nullptr;   // H2V_MIXED_FOLD_MSM: the call's term pool and its layout; fold_plan: the unit's plan in the call's
     uint32_t fold_plan = 0, first = 0; // list; first: the unit's first proof within its plan's sub-batch (slice)
     uint32_t seed[8] = {};
+    // H2V_RLC_SEED_TRANSCRIPT: derive (the entry points set it, on batch-check kinds only) asks run_call for a derived seed; it
+    // sets seed_dev - the call's slot of the workspace's seed ring, which the coefficient kernels then read in place of `seed` -
+    // and run_chunks the chunk's tweak of its word 7.  The form of the rule follows the kind (PAIR_RLC: pairs).  route: run_call's
+    // routing decision for an RLC call over proofs (a routed call derives nothing)
+    bool derive = false, route = false;
+    const uint32_t *seed_dev = nullptr;
+    uint32_t seed_xor7 = 0;
     uint32_t *fail_ctr = nullptr;
     bool one_stream_opt = false;       // RLC: h2v_rlc_opts.flags & H2V_RLC_ONE_STREAM (lanes and coalesced groups: always)
     bool trace = false;                // h2v_trace: the combiner's intermediate values to the workspace's trace buffer
@@ -1812,6 +1842,7 @@ template <class Before> static int run_chunks(h2v_workspace *w, const Unit &u, u
         const uint32_t lo = c * chunk;
         Unit cu = u.slice(lo, (u.n - lo) < chunk ? (u.n - lo) : chunk);
         cu.seed[7] ^= 0x9e3779b9u * (c + 1);      // (a chunk is its own batch check: its own coefficients)
+        cu.seed_xor7 ^= 0x9e3779b9u * (c + 1);    // (the same tweak for a derived seed, which is read on the device)
         cu.part = c;
         if (int rc = run_on_lane(w, l, cu, s)) return drain_after_error(w, rc);
         if (int rc = lane_done(w, l)) return rc;
@@ -1845,7 +1876,7 @@ static int run_laned(Unit u, h2v_workspace *w, hipStream_t st, Join join) {
         // the chunks report into this record's word.  RLC over proofs: routed - "a batch check failed" = the per-proof kernels
         // produce accept[]; over pairs (given or folded): never routed, and the failing-group estimate stays where it is
         if (int rcs = rlc_stats_ensure(w)) return rcs;
-        if (u.kind == UnitKind::RLC && !u.agg_parts && (rec.routed = rlc_route(w))) u.kind = UnitKind::ROUTED;   // (an aggregate call is never routed)
+        if (u.kind == UnitKind::RLC && !u.agg_parts && (rec.routed = u.route)) u.kind = UnitKind::ROUTED;   // (run_call's decision; an aggregate call is never routed)
         rec.agg = u.agg_parts != nullptr;
         HIPCHK(hipMemsetAsync(rec_word(w, rec), rec.routed ? 1 : 0, 4, st));
         u.fail_ctr = rec_word(w, rec);
@@ -2035,18 +2066,33 @@ static int coalesce_call(const Unit &u, h2v_workspace *w, hipStream_t st) {
 }
 // an RLC call on an ORDINARY workspace: the batch check, or - routed - the per-proof pipeline (its record's word: "failed")
 static int run_rlc_or_routed(Unit u, h2v_workspace *w, hipStream_t st) {
-    int rc = rlc_stats_ensure(w);
-    if (rc) return rc;
-    if (rlc_route(w)) u.kind = UnitKind::ROUTED;
+    int rc;
+    if (u.route) u.kind = UnitKind::ROUTED;      // (run_call's decision)
     if ((rc = run_unit(u, w, st))) return rc;
     if (u.kind == UnitKind::ROUTED) HIPCHK(hipMemsetAsync(rec_word(w, rec_last(w)), 1, 4, st));
     return rlc_stats_mirror(w, st);
 }
 // a call of its own (not gathered into a group) on either form of workspace
-static int run_call(const Unit &u, h2v_workspace *ws, hipStream_t st, Join join = Join::AS_DEFERRED) {
-    if (ws->n_lanes) return run_laned(u, ws, st, join);
-    if (u.kind == UnitKind::RLC) return run_rlc_or_routed(u, ws, st);
-    return run_unit(u, ws, st);
+// THE entry of every batch-accept call (and of the per-proof calls): the routing decision of an RLC call over proofs, then - a call
+// with H2V_RLC_SEED_TRANSCRIPT that is not routed - the digest launches of its derived seed (seed_enqueue: the one place that
+// queues them; on `st`, so behind the upload of a host form, and in front of everything the call forks from `st`), then the call.
+// The call's record is the next one of `ws` - nothing in between takes one (co_flush takes the lanes', coalesced calls took
+// theirs when they were made) -, and its slot of the seed ring is the record's.
+static int seed_enqueue(Unit &u, h2v_workspace *ws, hipStream_t st);
+static int run_call(Unit u, h2v_workspace *ws, hipStream_t st, Join join = Join::AS_DEFERRED) {
+    int rc;
+    if (ws->n_lanes && (rc = co_flush(ws))) return rc;      // (calls start in submission order; an open group may move the estimate)
+    if (u.kind == UnitKind::RLC && !u.agg_parts) {
+        if ((rc = rlc_stats_ensure(ws))) return rc;
+        u.route = rlc_route(ws);
+    }
+    const uint64_t call = ws->calls;
+    const bool derive = u.derive && u.batch_check() && !u.route;
+    if (derive && (rc = seed_enqueue(u, ws, st))) return rc;
+    rc = ws->n_lanes ? run_laned(u, ws, st, join) : (u.kind == UnitKind::RLC && !u.agg_parts) ? run_rlc_or_routed(u, ws, st) : run_unit(u, ws, st);
+    if (rc == H2V_OK && derive)
+        if (CallRec *r = rec_at(ws, call)) r->derived = true;
+    return rc;
 }
 // The argument rules of a batch with proofs in it
 static int batch_args(const h2v_plan *p, const h2v_batch *b) {
@@ -2397,6 +2443,8 @@ static int result_ensure(h2v_workspace *ws, hostcall::Call kind, uint64_t n, hos
 static bool rlc_supported(const h2v_plan *p);
 static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o);
 static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]);
+static int seed_flags(const h2v_rlc_opts *o, bool *derive);
+static int seed_flags_mixed(const h2v_rlc_opts *o);
 
 // Host-buffer batches on a LANED workspace: as many in flight as the mode has lanes, on ONE workspace.  Every batch gets a
 // staging slot of its own (pinned block + device block + accept buffers); uploads run in order on `hs`, the chunks on
@@ -2414,7 +2462,7 @@ static int submit_laned(Unit u, const h2v_batch *b, h2v_workspace *ws) {
     if (n) {
         if (int rcs = stage_unit(u, b, ws, sl)) return rcs;
         u.accept = sl.d_accept.p;
-        int rc = run_laned(u, ws, ws->hs, Join::NEVER);
+        int rc = run_call(u, ws, ws->hs, Join::NEVER);
         if (rc == H2V_OK) {
             // the download waits for the lanes this call's chunks ran on (their events as recorded just now)
             const CallRec &r = rec_last(ws);
@@ -2465,8 +2513,11 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
     const bool fold = (flags & H2V_SUBMIT_RLC) && !rlc && fold_pairs_wanted(p, opts);   // recursive plans: the batch check after the fold
     Unit u{fold ? UnitKind::FOLD_RLC : rlc ? UnitKind::RLC : UnitKind::VERIFY, p, (uint32_t)b->n};
     u.one_stream_opt = opts && (opts->flags & H2V_RLC_ONE_STREAM);
+    bool derive = false;
+    if ((flags & H2V_SUBMIT_RLC) && (rc = seed_flags(opts, &derive))) return rc;
+    u.derive = derive && u.batch_check();
     if (ws->n_lanes) {
-        if (u.batch_check() && (rc = rlc_seed(opts, u.seed))) return rc;
+        if (u.batch_check() && !u.derive && (rc = rlc_seed(opts, u.seed))) return rc;
         return submit_laned(u, b, ws);
     }
     h2v_workspace::HostSlot &sl = ws->hslot[0];
@@ -2474,7 +2525,7 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
     sl.n = b->n;
     sl.rlc = false;
     if (b->n) {
-        if (u.batch_check() && (rc = rlc_seed(opts, u.seed))) return rc;
+        if (u.batch_check() && !u.derive && (rc = rlc_seed(opts, u.seed))) return rc;
         if ((rc = stage_unit(u, b, ws, sl))) return rc;
         u.accept = ws->accept;
         rc = run_call(u, ws, ws->hs);
@@ -2587,7 +2638,10 @@ static int check_pairs_host(Unit u, const uint8_t *pairs, uint8_t *accept, uint3
     const bool rlc = u.kind == UnitKind::PAIR_RLC;
     TmpWs tmp;
     if (int rc = pairs_common(u.p, n, ws, nullptr, false, tmp)) return rc;
-    int rc = rlc ? rlc_seed(opts, u.seed) : H2V_OK;
+    bool derive = false;
+    int rc = rlc ? seed_flags(opts, &derive) : H2V_OK;
+    u.derive = derive;
+    if (rc == H2V_OK && rlc && !derive) rc = rlc_seed(opts, u.seed);
     hostcall::ResultBlock R;
     if (rc == H2V_OK) rc = result_ensure(ws, hostcall::Call::CHECK, n, &R);
     if (rc) return rc;
@@ -2998,7 +3052,7 @@ static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
     HIPCHK(hipEventRecord(ev[10], pm));
     // the batch check
     RlcArgs ra = {n, p->n_var, p->n_fix, slots, d.pi_point, d.n_terms, d.terms, w->scalars, w->status, w->valid, w->valid_sub, {},
-                  r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good};
+                  r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good, u.seed_dev, u.seed_xor7};
     copy_seed(ra.seed, u.seed);
     const uint32_t blocks = (n + 63) / 64;
     hipLaunchKernelGGL(k_rlc_prepare, dim3(blocks), dim3(64), 0, pm, ra);
@@ -3049,7 +3103,7 @@ static int pairs_rlc_core(const Unit &u, RlcWs *r, const uint32_t *pool, const u
     hipEvent_t *ev = rec.ev;
     int rc;
     if (!good_given) HIPCHK(hipEventRecord(ev[10], st));
-    RlcPairArgs ra = {n, status, valid, valid_sub, good_given ? r->good : nullptr, {}, r->r_scal, r->l_idx, r->r_idx, r->good};
+    RlcPairArgs ra = {n, status, valid, valid_sub, good_given ? r->good : nullptr, {}, r->r_scal, r->l_idx, r->r_idx, r->good, u.seed_dev, u.seed_xor7};
     copy_seed(ra.seed, u.seed);
     hipLaunchKernelGGL(k_rlc_pairs_prepare, dim3((n + 63) / 64), dim3(64), 0, st, ra);
     HIPCHK(hipEventRecord(ev[4], st));
@@ -3126,6 +3180,97 @@ static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]) {
     }
     return H2V_OK;
 }
+// ---- derived seeds (H2V_RLC_SEED_TRANSCRIPT): the seed is a digest of the whole call (h2v_seed.hpp has the rule), computed on the
+// device in front of the call and read there by the coefficient kernels; nothing of it is known on the host when the call returns.
+// what the flags of a batch-accept call say about its seed: *derive; the flag beside a given seed is a contradiction
+static int seed_flags(const h2v_rlc_opts *o, bool *derive) {
+    *derive = o && (o->flags & H2V_RLC_SEED_TRANSCRIPT);
+    if (*derive && (o->flags & H2V_RLC_SEED_GIVEN)) return fail(H2V_E_ARG, "H2V_RLC_SEED_TRANSCRIPT and H2V_RLC_SEED_GIVEN exclude each other");
+    return H2V_OK;
+}
+// the mixed forms have no derived seed yet: a mixed leaf needs the key tag of its own proof's plan
+static int seed_flags_mixed(const h2v_rlc_opts *o) {
+    if (o && (o->flags & H2V_RLC_SEED_TRANSCRIPT)) return fail(H2V_E_ARG, "H2V_RLC_SEED_TRANSCRIPT is not available in the mixed calls");
+    return H2V_OK;
+}
+// One derivation: the leaf launch, one node launch per level - the last forms the seed - on `st`.  Device pointers throughout;
+// digests: room for the tree's extent; form 2 (pairs): proofs holds n x 96 bytes and off, inst, ci are not read.
+struct SeedJob {
+    uint32_t form; uint64_t n; uint32_t inst_len, ci_len;
+    const uint8_t *proofs; const uint64_t *off; const uint8_t *inst, *ci;
+    const uint8_t *key_tag;      // host, 32 bytes
+    uint32_t *digests, *seed_out;
+};
+static int seed_launch(const SeedJob &j, hipStream_t st) {
+    h2vseed::Tree t;
+    if (!h2vseed::tree(j.n, &t) || t.levels == 0) return fail(H2V_E_ARG, "internal: no digest tree for this batch size");
+    const h2vseed::TagWords leaf = h2vseed::tag_words(h2vseed::TAG_LEAF), node = h2vseed::tag_words(h2vseed::TAG_NODE), root = h2vseed::tag_words(h2vseed::TAG_ROOT);
+    const bool pairs = j.form == h2vseed::FORM_PAIRS;
+    SeedLeafArgs la = {(uint32_t)j.n, pairs ? 0u : j.inst_len, pairs ? 0u : j.ci_len, pairs ? 1u : 0u, j.proofs, j.off, j.inst, j.ci, {}, j.digests};
+    memcpy(la.tag, leaf.w, 16);
+    hipLaunchKernelGGL(k_seed_leaves, dim3((uint32_t)((j.n + 63) / 64)), dim3(64), 0, st, la);
+    for (uint32_t l = 1; l <= t.levels; l++) {
+        SeedNodeArgs na = {l, (uint32_t)t.count[l - 1], (uint32_t)t.count[l], j.digests + t.off[l - 1] * 8, j.digests + t.off[l] * 8, {},
+                           j.form, (uint32_t)j.n, (uint32_t)(j.n >> 32), {}, {}, j.seed_out};
+        memcpy(na.tag, node.w, 16); memcpy(na.root_tag, root.w, 16); memcpy(na.key_tag, j.key_tag, 32);
+        hipLaunchKernelGGL(k_seed_nodes, dim3((uint32_t)((t.count[l] + 63) / 64)), dim3(64), 0, st, na);
+    }
+    HIPCHK(hipGetLastError());
+    return H2V_OK;
+}
+// THE place where a call's digest launches are queued (run_call): on `st`, into the slot of the seed ring that the call's record
+// - the next one of `ws` - indexes.  The digest buffer is one per workspace: a derivation waits for the one before it, on whatever
+// stream that ran (its consumers read the ring, not the buffer).  Sets u.seed_dev.
+static int seed_enqueue(Unit &u, h2v_workspace *ws, hipStream_t st) {
+    constexpr uint32_t RING = h2v_workspace::RING;
+    if (!ws->seed_ring) {
+        if (hipMalloc((void **)&ws->seed_ring, RING * 32) != hipSuccess) { ws->seed_ring = nullptr; return fail(H2V_E_DEVICE, "allocation of the seed ring failed"); }
+    }
+    h2vseed::Tree t;
+    if (!h2vseed::tree(u.n, &t)) return fail(H2V_E_LIMIT, "derived seeds are limited to 2^22 proofs");
+    if (int rc = ws->seed_digests.ensure((size_t)t.extent * 32, "the seed digests", [&]() -> int {
+            if (ws->ev_seed_last) HIPCHK(hipEventSynchronize(ws->ev_seed_last));
+            return H2V_OK;
+        })) return rc;
+    const uint32_t slot = (uint32_t)(ws->calls % RING);
+    for (hipEvent_t &e : ws->ev_seed[slot]) if (!e) HIPCHK(hipEventCreate(&e));
+    if (ws->ev_seed_last) HIPCHK(hipStreamWaitEvent(st, ws->ev_seed_last, 0));
+    HIPCHK(hipEventRecord(ws->ev_seed[slot][0], st));
+    const bool pairs = u.kind == UnitKind::PAIR_RLC;
+    const H2vDevPlan &d = u.p->d;
+    const SeedJob j = {pairs ? h2vseed::FORM_PAIRS : h2vseed::FORM_PROOFS, u.n, d.n_pi * 32u, d.n_ci * 48u, pairs ? u.pairs : u.proofs, u.off, u.inst, u.ci,
+                       u.p->key_tag, (uint32_t *)ws->seed_digests.p, ws->seed_ring + (size_t)slot * 8};
+    if (int rc = seed_launch(j, st)) return rc;
+    HIPCHK(hipEventRecord(ws->ev_seed[slot][1], st));
+    ws->ev_seed_last = ws->ev_seed[slot][1];
+    u.seed_dev = j.seed_out;
+    u.seed_xor7 = 0;
+    return H2V_OK;
+}
+// After the call's stream has been synchronised: the seed a call derived (calls_back as h2v_workspace_rlc_result counts them).
+extern "C" int h2v_workspace_seed_used(h2v_workspace *w, uint32_t calls_back, uint8_t seed[32]) {
+    if (!w || !seed) return fail(H2V_E_ARG, "null argument");
+    ALIVE(w);
+    const CallRec *r;
+    if (int rc = rec_lookup(w, calls_back, &r)) return rc;
+    if (!r->derived || !w->seed_ring) return fail(H2V_E_ARG, "that call derived no seed");
+    HIPCHK(hipSetDevice(w->device));
+    HIPCHK(hipMemcpy(seed, w->seed_ring + (r->call % h2v_workspace::RING) * 8, 32, hipMemcpyDeviceToHost));
+    return H2V_OK;
+}
+// ... and the device time of its digest launches, first start to last end (HIP events on the call's stream)
+extern "C" int h2v_workspace_seed_ms(h2v_workspace *w, uint32_t calls_back, float *ms) {
+    if (!w || !ms) return fail(H2V_E_ARG, "null argument");
+    ALIVE(w);
+    const CallRec *r;
+    if (int rc = rec_lookup(w, calls_back, &r)) return rc;
+    if (!r->derived) return fail(H2V_E_ARG, "that call derived no seed");
+    HIPCHK(hipSetDevice(w->device));
+    hipEvent_t *ev = w->ev_seed[r->call % h2v_workspace::RING];
+    HIPCHK(hipEventSynchronize(ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, ev[0], ev[1]));
+    return H2V_OK;
+}
 static int rlc_check_batch(const h2v_plan *p, const h2v_batch *b, const uint8_t *accept) {
     if (!p || !b || !accept) return fail(H2V_E_ARG, "null argument");
     if (b->n)
@@ -3148,8 +3293,11 @@ extern "C" int h2v_verify_batch_rlc_device(const h2v_plan *p, const h2v_batch *b
     // the opt-in one that starts after the fold
     Unit u = unit_of_batch(rlc_supported(p) ? UnitKind::RLC : fold_pairs_wanted(p, opts) ? UnitKind::FOLD_RLC : UnitKind::VERIFY, p, b, accept, status);
     u.one_stream_opt = opts && (opts->flags & H2V_RLC_ONE_STREAM);
-    if (u.batch_check() && (rc = rlc_seed(opts, u.seed))) return rc;
-    if (u.kind == UnitKind::RLC && co_wanted(ws, b->n)) return coalesce_call(u, ws, (hipStream_t)stream);
+    bool derive;
+    if ((rc = seed_flags(opts, &derive))) return rc;
+    u.derive = derive && u.batch_check();
+    if (u.batch_check() && !u.derive && (rc = rlc_seed(opts, u.seed))) return rc;
+    if (u.kind == UnitKind::RLC && !u.derive && co_wanted(ws, b->n)) return coalesce_call(u, ws, (hipStream_t)stream);   // (a derived seed is one call's)
     return run_call(u, ws, (hipStream_t)stream);
 }
 extern "C" int h2v_verify_batch_rlc(const h2v_plan *p, const h2v_batch *b, uint8_t *accept, h2v_workspace *ws, const h2v_rlc_opts *opts,
@@ -3173,7 +3321,9 @@ extern "C" int h2v_check_pairs_rlc_device(const h2v_plan *p, uint64_t n, const u
     TmpWs none;
     if (int rc = pairs_common(p, n, ws, stream, true, none)) return rc;
     Unit u = unit_of_pairs(UnitKind::PAIR_RLC, p, n, pairs, accept, status);
-    if (int rc = rlc_seed(opts, u.seed)) return rc;
+    if (int rc = seed_flags(opts, &u.derive)) return rc;
+    if (!u.derive)
+        if (int rc = rlc_seed(opts, u.seed)) return rc;
     return run_call(u, ws, (hipStream_t)stream);
 }
 extern "C" int h2v_check_pairs_rlc(const h2v_plan *p, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status, h2v_workspace *ws,
@@ -3793,6 +3943,7 @@ static uint32_t agg_mixed_flags(const h2v_rlc_opts *opts) {
 }
 extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
                                        h2v_workspace *ws, void *stream, uint32_t flags, const h2v_rlc_opts *opts) {
+    if (int rcs = seed_flags_mixed(opts)) return rcs;
     MixedCall c;
     int rc = mixed_args(plans, n_plans, b, accept, flags, &c);
     if (rc || b->n == 0) return rc;
@@ -3810,13 +3961,14 @@ extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_
 // runs there behind it, and accept[] / status[] / the batch verdict come back before the function returns.
 // agg_pair (h2v_aggregate_mixed): the fold form without its verdict - `accept` is the caller's included[], the call's pair comes
 // back in agg_pair and nothing is checked, downloaded in between or run a second time.
-static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint32_t chunk, uint32_t nch, uint64_t terms);
+static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint32_t chunk, uint32_t nch, uint64_t terms, bool derived = false);
 struct AggSlot { uint32_t *parts; uint32_t slot; };
 static int agg_export(h2v_workspace *ws, const AggSlot &a, uint32_t n_parts, uint8_t *d_pair, hipStream_t st);
 static int agg_ensure(h2v_workspace *ws, uint32_t n_parts, hipStream_t st, AggSlot *out);
 static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
                       h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back, uint8_t *agg_pair, h2v_aggregate_info *info) {
     if (fell_back) *fell_back = 0;
+    if (int rcs = seed_flags_mixed(opts)) return rcs;
     MixedCall c;
     const h2vmixed::Partition &pt = c.pt;
     int rc = mixed_args(plans, n_plans, b, accept, flags, &c);
@@ -3910,18 +4062,22 @@ static int agg_export(h2v_workspace *ws, const AggSlot &a, uint32_t n_parts, uin
     }
     return H2V_OK;
 }
-static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint32_t chunk, uint32_t nch, uint64_t terms) {
+static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint32_t chunk, uint32_t nch, uint64_t terms, bool derived) {
     if (!info) return H2V_OK;
     memset(info, 0, sizeof *info);
-    memcpy(info->seed_used, seed, 32);
+    if (!derived) memcpy(info->seed_used, seed, 32);      // (a derived seed is not known yet: zeros; h2v_workspace_seed_used has it)
+    info->reserved = derived ? 1u : 0u;                                                                        // (the seed source)
     info->chunk = chunk; info->n_chunks = nch; info->msm_terms = (uint32_t)terms;
     return H2V_OK;
 }
 static void agg_pair_inf(uint8_t pair[96]) { memset(pair, 0, 96); pair[0] = 0xc0; pair[48] = 0xc0; }
 // (mixed: h2v_aggregate_mixed(_device), the one call that knows H2V_RLC_GROUPED)
 static int agg_flags(const h2v_rlc_opts *o, bool mixed = false) {
-    if (o && (o->flags & ~(H2V_RLC_SEED_GIVEN | H2V_RLC_ONE_STREAM | H2V_RLC_FOLD_PAIRS | (mixed ? H2V_RLC_GROUPED : 0u)))) return fail(H2V_E_ARG, "unknown flag in h2v_rlc_opts.flags");
-    return H2V_OK;
+    if (mixed)
+        if (int rc = seed_flags_mixed(o)) return rc;
+    if (o && (o->flags & ~(H2V_RLC_SEED_GIVEN | H2V_RLC_ONE_STREAM | H2V_RLC_FOLD_PAIRS | (mixed ? H2V_RLC_GROUPED : H2V_RLC_SEED_TRANSCRIPT)))) return fail(H2V_E_ARG, "unknown flag in h2v_rlc_opts.flags");
+    bool derive;
+    return seed_flags(o, &derive);
 }
 // the argument rules of the single-key forms that need no device
 static int agg_batch_args(const h2v_plan *p, const h2v_batch *b, const uint8_t *pair, const uint8_t *included, const h2v_rlc_opts *opts) {
@@ -3943,14 +4099,15 @@ static int agg_run(const h2v_plan *p, const h2v_batch *in, uint8_t *d_pair, uint
     const uint32_t n = (uint32_t)in->n, nch = ws->n_lanes ? n_chunks(n, ws->chunk) : 1u;
     Unit u = unit_of_batch(rlc_supported(p) ? UnitKind::RLC : UnitKind::FOLD_RLC, p, in, d_included, d_status);
     u.one_stream_opt = opts && (opts->flags & H2V_RLC_ONE_STREAM);
-    int rc = rlc_seed(opts, u.seed);
+    int rc = seed_flags(opts, &u.derive);
+    if (rc == H2V_OK && !u.derive) rc = rlc_seed(opts, u.seed);
     if (rc) return rc;
-    agg_info_fill(info, u.seed, ws->n_lanes ? ws->chunk : 0u, nch, u.kind == UnitKind::RLC ? (uint64_t)n * p->n_var + (uint64_t)nch * p->n_fix : (uint64_t)n);
+    agg_info_fill(info, u.seed, ws->n_lanes ? ws->chunk : 0u, nch, u.kind == UnitKind::RLC ? (uint64_t)n * p->n_var + (uint64_t)nch * p->n_fix : (uint64_t)n, u.derive);
     if ((rc = rlc_stats_ensure(ws))) return rc;      // (the records' verdict words)
     AggSlot as{};
     if ((rc = agg_ensure(ws, nch, st, &as))) return rc;
     u.agg_parts = as.parts;
-    if ((rc = ws->n_lanes ? run_laned(u, ws, st, Join::NOW) : run_unit(u, ws, st))) return rc;
+    if ((rc = run_call(u, ws, st, Join::NOW))) return rc;
     return agg_export(ws, as, nch, d_pair, st);
 }
 extern "C" int h2v_aggregate_batch_device(const h2v_plan *p, const h2v_batch *b, uint8_t *pair, uint8_t *included, uint32_t *status, h2v_workspace *ws,
@@ -3996,7 +4153,9 @@ extern "C" int h2v_aggregate_batch(const h2v_plan *p, const h2v_batch *b, uint8_
     if (rc) return rc;
     uint8_t *const d = ws->res.p;
     rc = agg_run(p, &in, d + R.pairs.off, d + R.accept.off, (uint32_t *)(d + R.status.off), ws, ws->hs, opts, info);
-    return host_call_tail(ws, rc, {{pair, R.pairs, "the pair"}, {included, R.accept, "included[]"}, {status, R.status, "the status words"}}, false, nullptr, "aggregate");
+    rc = host_call_tail(ws, rc, {{pair, R.pairs, "the pair"}, {included, R.accept, "included[]"}, {status, R.status, "the status words"}}, false, nullptr, "aggregate");
+    if (rc == H2V_OK && info && H2V_AGGREGATE_SEED_SOURCE(info) == 1) rc = h2v_workspace_seed_used(ws, 0, info->seed_used);      // (the stream is synchronised: the derived seed is there)
+    return rc;
 }
 extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *pair, uint8_t *included,
                                           uint32_t *status, h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {

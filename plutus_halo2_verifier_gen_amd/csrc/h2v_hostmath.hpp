@@ -464,5 +464,21 @@ static inline uint32_t b2_keyed_midstate_host(uint64_t h[8], uint32_t digest_len
     b2_compress_host(h, block, 128, false);
     return 128;
 }
+// unkeyed blake2b-256 of prefix || msg (either may be empty): a plan's key tag at load (h2v_seed.hpp), once per plan
+static inline void b2_256_host(const uint8_t *prefix, size_t prefix_len, const uint8_t *msg, size_t len, uint8_t out[32]) {
+    uint64_t h[8];
+    (void)b2_keyed_midstate_host(h, 32, nullptr, 0);
+    const size_t total = prefix_len + len;
+    uint8_t block[128];
+    size_t at = 0;
+    do {
+        const size_t take = total - at < 128 ? total - at : 128;
+        memset(block, 0, sizeof block);
+        for (size_t k = 0; k < take; k++) block[k] = at + k < prefix_len ? prefix[at + k] : msg[at + k - prefix_len];
+        at += take;
+        b2_compress_host(h, block, at, at == total);
+    } while (at < total);
+    for (int i = 0; i < 32; i++) out[i] = (uint8_t)(h[i >> 3] >> (8 * (i & 7)));
+}
 
 }  // namespace h2vhost

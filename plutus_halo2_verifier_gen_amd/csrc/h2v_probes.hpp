@@ -114,6 +114,31 @@ extern "C" int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uin
     HIPCHK(hipDeviceSynchronize());
     return dout.download(digests, (size_t)n * 32) ? fail(H2V_E_DEVICE, "download failed") : (int)H2V_OK;
 }
+// the digest kernels of a derived seed alone, through seed_launch as run_call's seed_enqueue queues them.  The proof bytes go up
+// from byte 0 of the caller's buffer, so that proof_off[0] decides the alignment the leaf kernel meets.
+extern "C" int h2v_probe_batch_seed(int device, uint32_t form, const uint8_t key_tag[32], const h2v_batch *b, uint32_t n_pi, uint32_t n_ci, uint8_t seed[32]) {
+    int rc = pick_device(device);
+    if (rc) return rc;
+    if (!key_tag || !b || !seed || !b->proofs) return fail(H2V_E_ARG, "null argument");
+    if (form != h2vseed::FORM_PROOFS && form != h2vseed::FORM_PAIRS) return fail(H2V_E_ARG, "form: 1 (proofs) or 2 (pairs)");
+    const bool pairs = form == h2vseed::FORM_PAIRS;
+    h2vseed::Tree t;
+    if (b->n == 0 || !h2vseed::tree(b->n, &t)) return fail(H2V_E_ARG, "n out of range (1 .. 2^22)");
+    if (!pairs) {
+        if (!b->proof_off || (n_pi && !b->instances) || (n_ci && !b->committed) || n_ci > 1 || n_pi > (1u << 16)) return fail(H2V_E_ARG, "bad argument");
+        if (!hostcall::offsets_ascend(b->n, b->proof_off)) return fail(H2V_E_ARG, "proof offsets must ascend");
+    }
+    const size_t proof_bytes = pairs ? (size_t)b->n * 96 : (size_t)b->proof_off[b->n];
+    DevBuf dp, doff, di, dc, dd, ds;
+    if (dp.upload(b->proofs, proof_bytes) || dd.alloc((size_t)t.extent * 32) || ds.alloc(32)) return fail(H2V_E_DEVICE, "probe setup failed");
+    if (!pairs && (doff.upload(b->proof_off, ((size_t)b->n + 1) * 8) || (n_pi && di.upload(b->instances, (size_t)b->n * n_pi * 32)) ||
+                   (n_ci && dc.upload(b->committed, (size_t)b->n * n_ci * 48))))
+        return fail(H2V_E_DEVICE, "probe setup failed");
+    const SeedJob j = {form, b->n, n_pi * 32u, n_ci * 48u, dp.as<uint8_t>(), doff.as<uint64_t>(), di.as<uint8_t>(), dc.as<uint8_t>(), key_tag, dd.as<uint32_t>(), ds.as<uint32_t>()};
+    if ((rc = seed_launch(j, nullptr))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    return ds.download(seed, 32) ? fail(H2V_E_DEVICE, "download failed") : (int)H2V_OK;
+}
 extern "C" int h2v_probe_blake2b_ex(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint32_t digest_len, const uint8_t *key,
                                     uint32_t key_len, uint8_t *digests) {
     int rc = pick_device(device);

@@ -26,6 +26,8 @@ struct RlcArgs {
     uint32_t *l_scal, *l_idx;   // n terms of the left-hand MSM
     uint32_t *vk_part;          // ceil(n / 64) x n_fix x 8 (Montgomery): per-block sums of r_i s_{i,f}
     uint8_t *good;              // n
+    const uint32_t *seed_dev;   // NULL: `seed` above, bit for bit; else the call's derived seed in device memory (8 dwords) ...
+    uint32_t seed_xor7;         // ... whose word 7 is xored with this (a laned workspace's chunk tweak)
 };
 
 extern "C" __global__ void __launch_bounds__(64)
@@ -43,7 +45,7 @@ k_rlc_prepare(RlcArgs a) {
     Transcript tr;
     tr_init(tr);
 #pragma unroll 1
-    for (int k = 0; k < 32; k++) tr_put(tr, sbuf, lane, (a.seed[k >> 2] >> (8 * (k & 3))) & 0xffu);
+    for (int k = 0; k < 32; k++) tr_put(tr, sbuf, lane, (seed_word(a.seed, a.seed_dev, a.seed_xor7, k >> 2) >> (8 * (k & 3))) & 0xffu);
 #pragma unroll 1
     for (int k = 0; k < 4; k++) tr_put(tr, sbuf, lane, (ii >> (8 * k)) & 0xffu);
     uint64_t h[4];
@@ -194,6 +196,8 @@ struct RlcPairArgs {
     uint32_t seed[8];
     uint32_t *scal, *l_idx, *r_idx;          // n x 8, n, n
     uint8_t *good;                           // n
+    const uint32_t *seed_dev;                // as RlcArgs: NULL, or the derived seed in device memory
+    uint32_t seed_xor7;
 };
 extern "C" __global__ void __launch_bounds__(64)
 k_rlc_pairs_prepare(RlcPairArgs a) {
@@ -214,7 +218,7 @@ k_rlc_pairs_prepare(RlcPairArgs a) {
     Transcript tr;
     tr_init(tr);
 #pragma unroll 1
-    for (int k = 0; k < 32; k++) tr_put(tr, sbuf, lane, (a.seed[k >> 2] >> (8 * (k & 3))) & 0xffu);
+    for (int k = 0; k < 32; k++) tr_put(tr, sbuf, lane, (seed_word(a.seed, a.seed_dev, a.seed_xor7, k >> 2) >> (8 * (k & 3))) & 0xffu);
 #pragma unroll 1
     for (int k = 0; k < 4; k++) tr_put(tr, sbuf, lane, (ii >> (8 * k)) & 0xffu);
     uint64_t h[4];
