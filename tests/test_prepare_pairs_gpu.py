@@ -4,11 +4,11 @@ calling forms (host / device, laned, multi-plan, deferred joins with open coales
 edges and sizes, the Python API and points at infinity.  /root/reference is NOT needed."""
 import json
 import random
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
 from plutus_halo2_verifier_gen_amd import bls12_381 as bls
+from tests.degenerate_keys import oracle_pairs
 from tests.test_gpu_parity import be, circuits, _permute  # noqa: F401  (module fixtures)
 from tests.test_wide_keys_gpu import wide  # noqa: F401
 
@@ -19,15 +19,7 @@ PAIRING_ONLY = ["wrong_pi", "wrong_public_input"]
 ACC = ["acc_limb", "acc_scalar", "acc_fixed_scalar", "acc_sign", "acc_vk_hash"]
 
 
-def _oracle(ov, orc, batch, n_pi):
-    """per proof: (accept, the pair the oracle's pairing checks - or 96 zero bytes where it stops before the pairing)"""
-    def one(i):
-        ok, otr = ov.verify(batch.proof(i), batch.instance_ints(i, n_pi), batch.ci(i), trace=True)
-        if otr.status in (0, 1):
-            return int(ok), orc.g1_compress(otr.point("el")) + orc.g1_compress(otr.point("er"))
-        return int(ok), bytes(96)
-    with ThreadPoolExecutor(8) as ex:
-        return list(ex.map(one, range(batch.n)))
+_oracle = oracle_pairs   # (shared with the tests of degenerate keys: tests/degenerate_keys.py)
 
 
 def _dev(batch):
