@@ -28,6 +28,7 @@
 #include "h2v_seed.hpp"
 #include "h2v_mixed_tables.hpp"
 #include "h2v_plancc.hpp"
+#include "h2v_planblob.hpp"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) {
@@ -157,77 +158,6 @@ struct h2v_plan {
     uint8_t key_tag[32] = {};    // blake2b-256(TAG key || the plan blob): what a derived batch seed binds the key with (h2v_seed.hpp)
     std::vector<uint32_t> trace_slots;
 };
-
-// The six-lane pairing engine multiplies by lines with a UNIT coefficient (h2v_pairing_six.hpp): from the blob's line records
-// [-lambda, xi (-lambda), c, xi c] (28-bit Montgomery limbs) the constants A = -lambda / c, B = 1 / c of every line of both loops,
-// laid out [line][loop][A0, A1, B0, B1][16 dwords], followed by [1, K1, K2, K1 K2] (2 x 12 Montgomery words each) with K_u the
-// product of loop u's c along the Miller schedule (k <- k^2 per bit, k <- k c per line): K times the unit-line Miller value is
-// the plan's.  One Fp2 inversion per line, 136 per plan load.  false: some c is zero (no table; the engine is not offered).
-#define SIX_NORM_DW (H2V_MILLER_LINES * 2 * 4 * 16)
-static bool six_line_tables(const uint8_t *l28_sg2, const uint8_t *l28_g2, std::vector<uint32_t> &out) {
-    using namespace h2vhost;
-    U384 c376;                                   // a Montgomery product with 2^376 turns x 2^392 into the host form x 2^384
-    c376.w[5] = (uint64_t)1 << (376 - 320);
-    auto slot_fp = [&](const uint8_t *slot) {
-        U384 m;
-        for (int i = 0; i < 14; i++) {
-            uint32_t limb;
-            memcpy(&limb, slot + 4 * i, 4);
-            const int bit = 28 * i;
-            m.w[bit >> 6] |= (uint64_t)limb << (bit & 63);
-            if ((bit & 63) > 36 && (bit >> 6) + 1 < 6) m.w[(bit >> 6) + 1] |= (uint64_t)limb >> (64 - (bit & 63));
-        }
-        return FpE{FP().mul(m, c376)};
-    };
-    auto put_slot = [&](uint32_t *dst, const FpE &a) {
-        uint8_t b[48];
-        fp_mont392_bytes(a, b);
-        U384 m;
-        memcpy(m.w, b, 48);
-        for (int i = 0; i < 14; i++) {
-            const int bit = 28 * i;
-            uint64_t v = m.w[bit >> 6] >> (bit & 63);
-            if ((bit & 63) > 36 && (bit >> 6) + 1 < 6) v |= m.w[(bit >> 6) + 1] << (64 - (bit & 63));
-            dst[i] = (uint32_t)(v & 0xfffffffu);
-        }
-        dst[14] = dst[15] = 0;
-    };
-    auto put_words = [&](uint32_t *dst, const FpE &a) {
-        uint8_t b[48];
-        fp_mont392_bytes(a, b);
-        memcpy(dst, b, 48);
-    };
-    out.assign(SIX_NORM_DW + 4 * 24, 0);
-    const uint8_t *src[2] = {l28_sg2, l28_g2};
-    F2 K[2] = {f2_one(), f2_one()};
-    int ln = 0;
-    for (int bit = 62; bit >= 0; bit--) {
-        const int steps = ((0xd201000000010000ull >> bit) & 1) ? 2 : 1;
-        for (int u = 0; u < 2; u++) K[u] = f2_sqr(K[u]);
-        for (int s2 = 0; s2 < steps; s2++, ln++)
-            for (int u = 0; u < 2; u++) {
-                const uint8_t *rec = src[u] + (size_t)ln * 8 * 64;
-                const F2 nl = {slot_fp(rec), slot_fp(rec + 64)}, cc = {slot_fp(rec + 4 * 64), slot_fp(rec + 5 * 64)};
-                if (f2_is_zero(cc)) return false;
-                const F2 B = f2_inv(cc), A = f2_mul(nl, B);
-                uint32_t *dst = out.data() + ((size_t)ln * 2 + u) * 4 * 16;
-                put_slot(dst, A.a); put_slot(dst + 16, A.b); put_slot(dst + 32, B.a); put_slot(dst + 48, B.b);
-                K[u] = f2_mul(K[u], cc);
-            }
-    }
-    if (ln != H2V_MILLER_LINES) return false;
-    const F2 ks[4] = {f2_one(), K[0], K[1], f2_mul(K[0], K[1])};
-    for (int q = 0; q < 4; q++) { put_words(out.data() + SIX_NORM_DW + 24 * q, ks[q].a); put_words(out.data() + SIX_NORM_DW + 24 * q + 12, ks[q].b); }
-    return true;
-}
-
-// Two 64-bit FNV-1a sums (different offset bases) over a section of the plan blob: equal line tables of s_g2 = one SRS.  The
-// keys of a host are its own configuration, not an adversary's input: the digest guards against a mistake, not an attack.
-static void digest_section(const uint8_t *sec, size_t len, uint64_t out[2]) {
-    uint64_t a = 0xcbf29ce484222325ull, b = 0x84222325cbf29ce4ull;
-    for (size_t k = 0; k < len; k++) { a = (a ^ sec[k]) * 0x100000001b3ull; b = (b ^ (uint8_t)(sec[k] + 0x5a)) * 0x100000001b3ull; }
-    out[0] = a; out[1] = b;
-}
 
 struct h2v_workspace {
     int device = 0;
@@ -375,295 +305,7 @@ static CallRec *rec_at(h2v_workspace *w, uint64_t call) {
 static CallRec &rec_last(h2v_workspace *w) { return w->rec[(w->calls - 1) % h2v_workspace::RING]; }
 static uint32_t *rec_word(h2v_workspace *w, const CallRec &r) { return w->rec_fail + r.call % h2v_workspace::RING; }
 
-// LDS left for the combiner's register file in a block: 160 KB minus the 8 KB hash buffer and 1 KB of slack
-// (plan.py: VM_LDS_BYTES)
-#define H2V_VM_LDS_BYTES ((size_t)160 * 1024 - 8192 - 1024)
-static uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 // ---------------------------------------------------------------------------------------------- plan
-extern "C" int h2v_plan_load(const uint8_t *blob, size_t len, int device, h2v_plan **out) { return h2v_plan_load_ex(blob, len, device, nullptr, out); }
-extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, const h2v_plan_opts *opts, h2v_plan **out) {
-    if (!blob || !out) return fail(H2V_E_ARG, "null argument");
-    const uint32_t opt_fix_c = opts ? opts->fixed_base_window_bits : 0u;
-    if (opt_fix_c != 0 && opt_fix_c != 4 && opt_fix_c != 8 && opt_fix_c != 12) return fail(H2V_E_ARG, "fixed_base_window_bits: 0 (auto), 4, 8 or 12");
-    *out = nullptr;
-    const size_t hdr = 8 + 4 * H2V_PLAN_HDR_WORDS;
-    if (len < hdr || memcmp(blob, H2V_PLAN_MAGIC, 8) != 0) return fail(H2V_E_PLAN, "bad magic / truncated header");
-    uint32_t w[H2V_PLAN_HDR_WORDS];
-    for (int i = 0; i < H2V_PLAN_HDR_WORDS; i++) w[i] = rd32(blob + 8 + 4 * i);
-    if (w[H2V_HW_VERSION] != H2V_PLAN_VERSION && w[H2V_HW_VERSION] != H2V_PLAN_VERSION_FLAVOURED) return fail(H2V_E_PLAN, "unsupported plan version");
-    if (w[H2V_HW_TOTAL_LEN] != len) return fail(H2V_E_PLAN, "length mismatch");
-    // transcript hash of the key: version 4 knows the Cardano flavour only (its three words are spare and zero)
-    const uint32_t tr_kind = w[H2V_HW_TR_KIND], tr_key_off = w[H2V_HW_TR_KEY_OFF], tr_key_len = w[H2V_HW_TR_KEY_LEN];
-    if (w[H2V_HW_VERSION] == H2V_PLAN_VERSION && (tr_kind || tr_key_off || tr_key_len)) return fail(H2V_E_PLAN, "a version-4 plan names a transcript hash");
-    if (tr_kind >= H2V_TR_KIND_COUNT) return fail(H2V_E_PLAN, "unknown transcript hash kind " + std::to_string(tr_kind));
-    if (tr_key_len > H2V_TR_KEY_MAX) return fail(H2V_E_PLAN, "transcript hash key longer than 64 bytes");
-    if (tr_kind == H2V_TR_CARDANO_BLAKE2B_256 && (tr_key_len || tr_key_off)) return fail(H2V_E_PLAN, "the Cardano transcript hash is unkeyed");
-    if (tr_key_len ? (tr_key_off < 8 + 4 * H2V_PLAN_HDR_WORDS || (uint64_t)tr_key_off + tr_key_len > len) : tr_key_off != 0)
-        return fail(H2V_E_PLAN, "transcript hash key out of bounds");
-    struct Sec { int off_word; uint64_t bytes; };
-    const uint32_t n_instr = w[H2V_HW_N_INSTR], n_consts = w[H2V_HW_N_CONSTS], n_points = w[H2V_HW_N_POINTS],
-                   n_bases = w[H2V_HW_N_VK_BASES], n_terms = w[H2V_HW_N_TERMS], n_trace = w[H2V_HW_N_TRACE],
-                   n_regs = w[H2V_HW_N_REGS], proof_len = w[H2V_HW_PROOF_LEN], n_pi = w[H2V_HW_N_PI], n_ci = w[H2V_HW_N_CI];
-    const Sec secs[] = {{H2V_HW_OFF_INSTR, 8ull * n_instr}, {H2V_HW_OFF_CONSTS, 32ull * n_consts}, {H2V_HW_OFF_POINTS, 4ull * n_points},
-                        {H2V_HW_OFF_VK_BASES, 96ull * n_bases}, {H2V_HW_OFF_TERMS, 8ull * n_terms},
-                        {H2V_HW_OFF_LINES_SG2, 192ull * H2V_MILLER_LINES}, {H2V_HW_OFF_LINES_G2, 192ull * H2V_MILLER_LINES},
-                        {H2V_HW_OFF_TRACE, 8ull * n_trace},
-                        {H2V_HW_OFF_LINES28_SG2, 512ull * H2V_MILLER_LINES}, {H2V_HW_OFF_LINES28_G2, 512ull * H2V_MILLER_LINES}};
-    for (const Sec &s : secs) {
-        const uint64_t off = w[s.off_word];
-        if (off < hdr || (off & 15) || off + s.bytes > len) return fail(H2V_E_PLAN, "section out of bounds");
-    }
-    if (n_instr == 0 || n_instr > (1u << 20) || n_regs == 0 || n_regs > 65535 || n_points == 0 || n_points > 4096 ||
-        n_terms == 0 || n_ci > 1 || n_pi > (1u << 16) || proof_len > (1u << 24))
-        return fail(H2V_E_PLAN, "implausible counts");
-    const uint32_t ivc = w[H2V_HW_IVC], n_main = w[H2V_HW_N_MAIN_TERMS];
-    if (ivc > 1 || n_main == 0 || n_main > n_terms || (!ivc && n_main != n_terms) || (ivc && n_terms < n_main + 2))
-        return fail(H2V_E_PLAN, "inconsistent recursion header");
-    // the widest sum the launcher cuts into segments (H2V_MAX_MSM_TERMS; the partial-sum buffer is sized from it)
-    if (n_main > H2V_MAX_MSM_TERMS)
-        return fail(H2V_E_LIMIT, std::string(ivc ? "the proof's own MSM" : "the final MSM") + " has " + std::to_string(n_main) +
-                                     " terms; this backend sums at most " + std::to_string(H2V_MAX_MSM_TERMS) + " terms per MSM (H2V_MAX_MSM_TERMS)");
-    if (ivc && n_terms - n_main - 1 > H2V_MAX_MSM_TERMS)
-        return fail(H2V_E_LIMIT, "the recursion sum acc_right + fixed bases has " + std::to_string(n_terms - n_main - 1) +
-                                     " terms; this backend sums at most " + std::to_string(H2V_MAX_MSM_TERMS) + " terms per MSM (H2V_MAX_MSM_TERMS)");
-    if (ivc)
-        for (int k = 0; k < 8; k++)
-            if (w[H2V_HW_ACC_IDX0 + k] >= n_pi) return fail(H2V_E_PLAN, "accumulator public-input index out of range");
-    if (w[H2V_HW_PI_POINT] >= n_points) return fail(H2V_E_PLAN, "pi point index out of range");
-    // validate the program(s): every register / constant / offset the kernels will touch is in range, and the bundle
-    // discipline the multi-lane interpreter relies on holds (h2v_plan.h)
-    uint32_t n_sq = 0;
-    auto check_program = [&](const uint8_t *ip, uint32_t n_rec, uint32_t n_regs_v, uint32_t lanes, uint32_t *squeezes) -> int {
-        if (lanes == 0 || lanes > 32 || (lanes & (lanes - 1)) || n_rec % lanes) return fail(H2V_E_PLAN, "bad lane count of the program");
-        bool has_end = false;
-        uint32_t sq = 0;
-        for (uint32_t base_k = 0; base_k < n_rec && !has_end; base_k += lanes) {
-            uint32_t wr[32], n_wr = 0;
-            bool lane0_serial = false;
-            for (uint32_t l = 0; l < lanes; l++) {
-                const uint32_t k = base_k + l;
-                const uint8_t op = ip[8 * k];
-                const uint32_t dst = ip[8 * k + 2] | (ip[8 * k + 3] << 8), a = ip[8 * k + 4] | (ip[8 * k + 5] << 8), b = ip[8 * k + 6] | (ip[8 * k + 7] << 8);
-                const uint32_t off = a | (b << 16);
-                bool ok = true, writes = false, serial = false;
-                switch (op) {
-                case H2V_OP_END: has_end = true; serial = true; break;
-                case H2V_OP_NOP: break;
-                case H2V_OP_ABSORB_REG: ok = a < n_regs_v; serial = true; break;
-                case H2V_OP_ABSORB_CI: ok = n_ci == 1; serial = true; break;
-                case H2V_OP_LOAD_INSTANCE: ok = dst < n_regs_v && a < n_pi; writes = true; break;
-                case H2V_OP_READ_POINT: ok = (uint64_t)off + 48 <= proof_len; serial = true; break;
-                case H2V_OP_READ_SCALAR: ok = dst < n_regs_v && (uint64_t)off + 32 <= proof_len; writes = true; serial = true; break;
-                case H2V_OP_SQUEEZE: ok = dst < n_regs_v; sq++; writes = true; serial = true; break;
-                case H2V_OP_CONST: ok = dst < n_regs_v && a < n_consts; writes = true; break;
-                case H2V_OP_ADD: case H2V_OP_SUB: case H2V_OP_MUL: ok = dst < n_regs_v && a < n_regs_v && b < n_regs_v; writes = true; break;
-                case H2V_OP_NEG: case H2V_OP_INV: ok = dst < n_regs_v && a < n_regs_v; writes = true; break;
-                case H2V_OP_OUT_SCALAR: ok = dst < n_terms && a < n_regs_v; break;
-                case H2V_OP_ASSERT_ZERO: ok = a < n_regs_v; break;
-                default: ok = false;
-                }
-                if (!ok) return fail(H2V_E_PLAN, "instruction " + std::to_string(k) + " out of range");
-                if (serial && l != 0) return fail(H2V_E_PLAN, "transcript operation off lane 0 (record " + std::to_string(k) + ")");
-                if (l == 0) lane0_serial = serial;
-                else if (lane0_serial && op != H2V_OP_NOP) return fail(H2V_E_PLAN, "transcript operation shares its bundle (record " + std::to_string(k) + ")");
-                if (writes) wr[n_wr++] = (l << 16) | dst;
-            }
-            // independence inside the bundle: no register is written twice, none is read by a lane other than... any lane
-            for (uint32_t x = 0; x < n_wr; x++) {
-                const uint32_t reg = wr[x] & 0xffff;
-                for (uint32_t y = x + 1; y < n_wr; y++)
-                    if ((wr[y] & 0xffff) == reg) return fail(H2V_E_PLAN, "two lanes of a bundle write one register");
-                for (uint32_t l = 0; l < lanes; l++) {
-                    const uint32_t k = base_k + l;
-                    const uint8_t op = ip[8 * k];
-                    const uint32_t a = ip[8 * k + 4] | (ip[8 * k + 5] << 8), b = ip[8 * k + 6] | (ip[8 * k + 7] << 8);
-                    const bool reads_a = op == H2V_OP_ABSORB_REG || op == H2V_OP_ADD || op == H2V_OP_SUB || op == H2V_OP_MUL || op == H2V_OP_NEG ||
-                                         op == H2V_OP_INV || op == H2V_OP_OUT_SCALAR || op == H2V_OP_ASSERT_ZERO;
-                    const bool reads_b = op == H2V_OP_ADD || op == H2V_OP_SUB || op == H2V_OP_MUL;
-                    if (lanes > 1 && ((reads_a && a == reg) || (reads_b && b == reg)))
-                        return fail(H2V_E_PLAN, "a bundle reads a register it writes (record " + std::to_string(k) + ")");
-                }
-            }
-        }
-        if (!has_end) return fail(H2V_E_PLAN, "program has no END");
-        if (squeezes) *squeezes = sq;
-        return H2V_OK;
-    };
-    auto end_is_last = [&](const uint8_t *ip, uint32_t n_rec, uint32_t lanes) {   // the interpreter's trip count is n_rec / lanes - 1
-        for (uint32_t k = 0; k + lanes < n_rec; k++) if (ip[8 * k] == H2V_OP_END) return false;
-        return ip[8 * (n_rec - lanes)] == H2V_OP_END;
-    };
-    const uint32_t vm_lanes = w[H2V_HW_VM_LANES];
-    if (int rcp = check_program(blob + w[H2V_HW_OFF_INSTR], n_instr, n_regs, vm_lanes, &n_sq)) return rcp;
-    if (!end_is_last(blob + w[H2V_HW_OFF_INSTR], n_instr, vm_lanes)) return fail(H2V_E_PLAN, "END must be the last bundle of the program");
-    const uint32_t wide_lanes = w[H2V_HW_VM2_LANES], wide_n_regs = w[H2V_HW_VM2_N_REGS], wide_n_instr = w[H2V_HW_VM2_N_INSTR];
-    if (wide_lanes) {
-        const uint64_t off = w[H2V_HW_VM2_OFF_INSTR];
-        if (off < hdr || (off & 15) || off + 8ull * wide_n_instr > len || wide_n_instr == 0 || wide_n_instr > (1u << 20) ||
-            wide_n_regs == 0 || wide_n_regs > 65535)
-            return fail(H2V_E_PLAN, "wide program section out of bounds");
-        if (wide_lanes < 2 || (size_t)wide_n_regs * 32 * (64 / wide_lanes) > H2V_VM_LDS_BYTES)
-            return fail(H2V_E_PLAN, "wide program does not fit the LDS register file");
-        if (int rcp = check_program(blob + off, wide_n_instr, wide_n_regs, wide_lanes, nullptr)) return rcp;
-        if (!end_is_last(blob + off, wide_n_instr, wide_lanes)) return fail(H2V_E_PLAN, "END must be the last bundle of the program");
-    }
-    if (vm_lanes > 1 && (size_t)n_regs * 32 * (64 / vm_lanes) > H2V_VM_LDS_BYTES)
-        return fail(H2V_E_PLAN, "multi-lane program does not fit the LDS register file");
-    const uint8_t *pp = blob + w[H2V_HW_OFF_POINTS];
-    for (uint32_t k = 0; k < n_points; k++)
-        if ((uint64_t)rd32(pp + 4 * k) + 48 > proof_len) return fail(H2V_E_PLAN, "point offset out of range");
-    const uint8_t *tp = blob + w[H2V_HW_OFF_TERMS];
-    for (uint32_t k = 0; k < n_terms; k++) {
-        const uint32_t kind = rd32(tp + 8 * k), idx = rd32(tp + 8 * k + 4);
-        const bool ok = (kind == H2V_TERM_PROOF_POINT && idx < n_points) || (kind == H2V_TERM_VK_BASE && idx < n_bases) ||
-                        (kind == H2V_TERM_COMMITTED_INSTANCE && n_ci == 1) || (kind == H2V_TERM_ACC_POINT && ivc && idx < 2);
-        if (!ok) return fail(H2V_E_PLAN, "MSM term out of range");
-    }
-    const uint8_t *trp = blob + w[H2V_HW_OFF_TRACE];
-    for (uint32_t k = 0; k < n_trace; k++)
-        if (rd32(trp + 8 * k + 4) >= n_regs) return fail(H2V_E_PLAN, "trace register out of range");
-
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(H2V_E_DEVICE, "no HIP device: the HIP backend is required (no CPU fallback)");
-    if (device < 0 || device >= ndev) return fail(H2V_E_ARG, "device index out of range");
-    ALIVE_DEV(device);
-    HIPCHK(hipSetDevice(device));
-    h2v_plan *p = new h2v_plan();
-    p->device = device;
-    if (hipMalloc(&p->blob, len) != hipSuccess) { delete p; return fail(H2V_E_DEVICE, "hipMalloc(plan) failed"); }
-    // device copy of the blob with the committed-instance MSM terms rewritten to "per-proof slot n_points"
-    // (the decompression kernel stores the committed instance there), so the MSM kernel sees two term kinds only
-    std::vector<uint8_t> patched(blob, blob + len);
-    for (uint32_t k = 0; k < n_terms; k++) {
-        uint8_t *t = patched.data() + w[H2V_HW_OFF_TERMS] + 8 * k;
-        if (rd32(t) == H2V_TERM_COMMITTED_INSTANCE) {
-            const uint32_t kind = H2V_TERM_PROOF_POINT, idx = n_points;
-            memcpy(t, &kind, 4);
-            memcpy(t + 4, &idx, 4);
-        } else if (rd32(t) == H2V_TERM_ACC_POINT) {   // the decompression kernel rebuilds the accumulator points there
-            const uint32_t kind = H2V_TERM_PROOF_POINT, idx = n_points + n_ci + rd32(t + 4);
-            memcpy(t, &kind, 4);
-            memcpy(t + 4, &idx, 4);
-        }
-    }
-    if (ivc) {
-        const uint32_t ft[8] = {H2V_TERM_PROOF_POINT, 0, H2V_TERM_PROOF_POINT, 1, H2V_TERM_PROOF_POINT, 2, H2V_TERM_PROOF_POINT, 3};
-        if (hipMalloc(&p->fold_terms, sizeof ft) != hipSuccess || hipMemcpy(p->fold_terms, ft, sizeof ft, hipMemcpyHostToDevice) != hipSuccess) {
-            if (p->fold_terms) (void)hipFree(p->fold_terms);
-            (void)hipFree(p->blob); delete p;
-            return fail(H2V_E_DEVICE, "fold term upload failed");
-        }
-    }
-    if (hipMemcpy(p->blob, patched.data(), len, hipMemcpyHostToDevice) != hipSuccess) { if (p->fold_terms) (void)hipFree(p->fold_terms); (void)hipFree(p->blob); delete p; return fail(H2V_E_DEVICE, "plan upload failed"); }
-    const uint8_t *base = (const uint8_t *)p->blob;
-    H2vDevPlan &d = p->d;
-    d.proof_len = proof_len; d.n_pi = n_pi; d.n_ci = n_ci; d.n_regs = n_regs; d.n_instr = n_instr; d.n_consts = n_consts;
-    d.n_points = n_points; d.n_vk_bases = n_bases; d.n_terms = n_terms; d.n_trace = n_trace; d.pi_point = w[H2V_HW_PI_POINT];
-    d.instr = (const H2vInstr *)(base + w[H2V_HW_OFF_INSTR]);
-    d.vm_lanes = vm_lanes;
-    if (wide_lanes) {
-        d.wide_lanes = wide_lanes; d.wide_n_regs = wide_n_regs; d.wide_n_instr = wide_n_instr;
-        d.wide_instr = (const H2vInstr *)(base + w[H2V_HW_VM2_OFF_INSTR]);
-    }
-    d.consts = (const uint32_t *)(base + w[H2V_HW_OFF_CONSTS]);
-    d.points = (const uint32_t *)(base + w[H2V_HW_OFF_POINTS]);
-    d.vk_bases = (const uint32_t *)(base + w[H2V_HW_OFF_VK_BASES]);
-    d.terms = (const uint32_t *)(base + w[H2V_HW_OFF_TERMS]);
-    d.lines_sg2 = (const uint32_t *)(base + w[H2V_HW_OFF_LINES_SG2]);
-    d.lines_g2 = (const uint32_t *)(base + w[H2V_HW_OFF_LINES_G2]);
-    d.trace = (const uint32_t *)(base + w[H2V_HW_OFF_TRACE]);
-    d.lines28_sg2 = (const uint32_t *)(base + w[H2V_HW_OFF_LINES28_SG2]);
-    d.lines28_g2 = (const uint32_t *)(base + w[H2V_HW_OFF_LINES28_G2]);
-    d.ivc = ivc; d.n_main_terms = n_main;
-    // the state every proof's transcript starts from: parameter block, then the key block compressed here, once per plan
-    // (a transcript always hashes at least one byte before a digest is taken, so the key block is never the final one)
-    p->tr_kind = d.tr_kind = tr_kind;
-    p->tr_key_len = tr_key_len;
-    if (tr_key_len) memcpy(p->tr_key, blob + tr_key_off, tr_key_len);
-    if (tr_kind == H2V_TR_BLAKE2B_512) d.tr_t0 = h2vhost::b2_keyed_midstate_host(d.tr_h0, 64, p->tr_key, tr_key_len);
-    for (int k = 0; k < 8; k++) d.acc_idx[k] = w[H2V_HW_ACC_IDX0 + k];
-    d.fold_terms = (const uint32_t *)p->fold_terms;
-    // window tables of the VK bases for the MSM ladder: [1..8]B and [1..8]phi(B), affine, computed once per plan
-    if (hipMalloc(&p->vk_tab, (size_t)n_bases * 448 * 4 + 16) != hipSuccess || hipMemset(p->vk_tab, 0, (size_t)n_bases * 448 * 4 + 16) != hipSuccess) {
-        if (p->vk_tab) (void)hipFree(p->vk_tab);
-        if (p->fold_terms) (void)hipFree(p->fold_terms);
-        (void)hipFree(p->blob); delete p;
-        return fail(H2V_E_DEVICE, "hipMalloc(vk tables) failed");
-    }
-    if (n_bases) {
-        hipLaunchKernelGGL(k_vk_tables, dim3((n_bases + 63) / 64), dim3(64), 0, nullptr, d.vk_bases, n_bases, (uint32_t *)p->vk_tab);
-        if (hipDeviceSynchronize() != hipSuccess) {
-            (void)hipFree(p->vk_tab);
-            if (p->fold_terms) (void)hipFree(p->fold_terms);
-            (void)hipFree(p->blob); delete p;
-            return fail(H2V_E_DEVICE, "VK window-table kernel failed");
-        }
-    }
-    d.vk_tab = (const uint32_t *)p->vk_tab;
-    {   // the six-lane pairing engine's own line constants (host math, once per plan)
-        std::vector<uint32_t> six;
-        if (six_line_tables(blob + w[H2V_HW_OFF_LINES28_SG2], blob + w[H2V_HW_OFF_LINES28_G2], six)) {
-            if (hipMalloc(&p->six_tab, six.size() * 4) != hipSuccess || hipMemcpy(p->six_tab, six.data(), six.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-                if (p->six_tab) (void)hipFree(p->six_tab);
-                (void)hipFree(p->vk_tab);
-                if (p->fold_terms) (void)hipFree(p->fold_terms);
-                (void)hipFree(p->blob); delete p;
-                return fail(H2V_E_DEVICE, "six-lane line table upload failed");
-            }
-            d.six_norm28 = (const uint32_t *)p->six_tab;
-            d.six_k = d.six_norm28 + SIX_NORM_DW;
-        }
-    }
-    // fixed-base launches of the MSM (non-recursive plans whose VK-base terms are the tail of the term list, as plan.py
-    // orders them): every window multiple of every VK base
-    if (!ivc && n_bases) {
-        uint32_t nv = 0;
-        while (nv < n_terms && rd32(patched.data() + w[H2V_HW_OFF_TERMS] + 8 * nv) != H2V_TERM_VK_BASE) nv++;
-        bool tail_ok = nv < n_terms;
-        for (uint32_t k = nv; k < n_terms; k++) tail_ok = tail_ok && rd32(patched.data() + w[H2V_HW_OFF_TERMS] + 8 * k) == H2V_TERM_VK_BASE;
-        if (tail_ok) {
-            // window width of the tables: 12 bits (22 additions per VK term in every proof, 5 MB per base) unless that would
-            // take more than 2 GB; h2v_plan_opts.fixed_base_window_bits = 4 / 8 / 12 forces it (tests run all three)
-            uint32_t fc = (size_t)n_bases * 22 * 2048 * 112 <= ((size_t)2 << 30) ? 12u : 8u;
-            if (opt_fix_c) fc = opt_fix_c;
-            const uint32_t fW = fc == 4 ? 65u : fc == 8 ? 33u : 22u, fE = 1u << (fc - 1);
-            const size_t fix_bytes = (size_t)n_bases * fW * fE * 28 * 4;
-            void *wbase = nullptr;
-            bool okf = hipMalloc(&p->fix_tab, fix_bytes + 16) == hipSuccess && hipMemset(p->fix_tab, 0, fix_bytes + 16) == hipSuccess &&
-                       hipMalloc(&wbase, (size_t)n_bases * fW * 96 + 16) == hipSuccess;
-            if (okf) {
-                hipLaunchKernelGGL(k_vk_fixed_window_bases, dim3((n_bases * fW + 63) / 64), dim3(64), 0, nullptr, d.vk_bases, n_bases, fc, fW, (uint32_t *)wbase);
-                const uint64_t entries = (uint64_t)n_bases * fW * fE;
-                hipLaunchKernelGGL(k_vk_fixed_tables, dim3((uint32_t)((entries + 63) / 64)), dim3(64), 0, nullptr, (const uint32_t *)wbase, n_bases * fW, fc, (uint32_t *)p->fix_tab);
-                okf = hipDeviceSynchronize() == hipSuccess;
-            }
-            if (wbase) (void)hipFree(wbase);
-            d.fix_c = fc; d.fix_W = fW;
-            if (!okf) {
-                if (p->fix_tab) (void)hipFree(p->fix_tab);
-                if (p->six_tab) (void)hipFree(p->six_tab);
-                (void)hipFree(p->vk_tab);
-                (void)hipFree(p->blob); delete p;
-                return fail(H2V_E_DEVICE, "fixed-base table setup failed");
-            }
-            p->n_var = nv;
-            p->n_fix = n_terms - nv;
-        }
-    }
-    d.fix_tab = (const uint32_t *)p->fix_tab; d.n_var = p->n_var; d.n_fix = p->n_fix;
-    digest_section(blob + w[H2V_HW_OFF_LINES28_SG2], 512u * H2V_MILLER_LINES, p->sg2_digest);
-    {
-        const h2vseed::TagWords kt = h2vseed::tag_words(h2vseed::TAG_KEY);
-        h2vhost::b2_256_host((const uint8_t *)kt.w, h2vseed::TAG_BYTES, blob, len, p->key_tag);
-    }
-    p->n_squeezes = n_sq;
-    p->stream_len = w[H2V_HW_STREAM_LEN];
-    for (uint32_t k = 0; k < n_trace; k++) p->trace_slots.push_back(rd32(trp + 8 * k));
-    { static std::mutex mu; static uint64_t loads = 0; std::lock_guard<std::mutex> lock(mu); p->gen = ++loads; }
-    reg_add(g_plan_live, p);
-    *out = p;
-    return H2V_OK;
-}
 static void plan_release(h2v_plan *p) {   // the device memory; the host-side facts (h2v_plan_info) stay
     (void)hipSetDevice(p->device);
     if (p->blob) (void)hipFree(p->blob);
@@ -672,6 +314,113 @@ static void plan_release(h2v_plan *p) {   // the device memory; the host-side fa
     if (p->fix_tab) (void)hipFree(p->fix_tab);
     if (p->six_tab) (void)hipFree(p->six_tab);
     p->blob = p->fold_terms = p->vk_tab = p->fix_tab = p->six_tab = nullptr;
+}
+// All-window tables of the VK bases for the fixed-base launches of the MSM (planblob::fixed_tables has the shape): every window
+// multiple of every VK base.  The window bases are a temporary block of this function.
+static bool plan_fixed_tables(h2v_plan *p, const planblob::FixedTables &ft) {
+    const uint32_t n_bases = p->d.n_vk_bases;
+    void *wbase = nullptr;
+    bool ok = hipMalloc(&p->fix_tab, ft.bytes + 16) == hipSuccess && hipMemset(p->fix_tab, 0, ft.bytes + 16) == hipSuccess &&
+              hipMalloc(&wbase, (size_t)n_bases * ft.W * 96 + 16) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_vk_fixed_window_bases, dim3((n_bases * ft.W + 63) / 64), dim3(64), 0, nullptr, p->d.vk_bases, n_bases, ft.c, ft.W, (uint32_t *)wbase);
+        const uint64_t entries = (uint64_t)n_bases * ft.W * ft.entries;
+        hipLaunchKernelGGL(k_vk_fixed_tables, dim3((uint32_t)((entries + 63) / 64)), dim3(64), 0, nullptr, (const uint32_t *)wbase, n_bases * ft.W, ft.c, (uint32_t *)p->fix_tab);
+        ok = hipDeviceSynchronize() == hipSuccess;
+    }
+    if (wbase) (void)hipFree(wbase);
+    return ok;
+}
+// What a load learns on the host: the device view of the uploaded blob (the table pointers follow as the tables are built)
+// and the facts the plan's own entry points answer from (h2v_plan_transcript, _key_tag, _same_srs, _trace_slots).
+static void plan_fill(h2v_plan *p, const planblob::View &v, const uint8_t *blob, size_t len) {
+    auto at = [&](uint32_t off) { return (const uint32_t *)((const uint8_t *)p->blob + off); };
+    H2vDevPlan &d = p->d;
+    d.proof_len = v.proof_len; d.n_pi = v.n_pi; d.n_ci = v.n_ci; d.n_consts = v.n_consts;
+    d.n_points = v.n_points; d.n_vk_bases = v.n_bases; d.n_terms = v.n_terms; d.n_trace = v.n_trace; d.pi_point = v.pi_point;
+    d.instr = (const H2vInstr *)at(v.narrow.off);
+    d.n_instr = v.narrow.n_instr; d.n_regs = v.narrow.n_regs; d.vm_lanes = v.narrow.lanes;
+    if (v.wide.lanes) {
+        d.wide_lanes = v.wide.lanes; d.wide_n_regs = v.wide.n_regs; d.wide_n_instr = v.wide.n_instr;
+        d.wide_instr = (const H2vInstr *)at(v.wide.off);
+    }
+    d.consts = at(v.off_consts); d.points = at(v.off_points); d.vk_bases = at(v.off_bases); d.terms = at(v.off_terms); d.trace = at(v.off_trace);
+    d.lines_sg2 = at(v.off_lines_sg2); d.lines_g2 = at(v.off_lines_g2); d.lines28_sg2 = at(v.off_lines28_sg2); d.lines28_g2 = at(v.off_lines28_g2);
+    d.ivc = v.ivc; d.n_main_terms = v.n_main_terms;
+    memcpy(d.acc_idx, v.acc_idx, sizeof d.acc_idx);
+    d.fold_terms = (const uint32_t *)p->fold_terms;
+    p->tr_kind = d.tr_kind = v.tr_kind;
+    p->tr_key_len = v.tr_key_len;
+    if (v.tr_key_len) memcpy(p->tr_key, blob + v.tr_key_off, v.tr_key_len);
+    if (v.tr_kind == H2V_TR_BLAKE2B_512) d.tr_t0 = planblob::transcript_midstate(blob, v, d.tr_h0);
+    planblob::sg2_digest(blob, v, p->sg2_digest);
+    planblob::key_tag(blob, len, p->key_tag);
+    p->n_squeezes = v.n_squeezes; p->stream_len = v.stream_len; p->trace_slots = v.trace_slots;
+}
+extern "C" int h2v_plan_load(const uint8_t *blob, size_t len, int device, h2v_plan **out) { return h2v_plan_load_ex(blob, len, device, nullptr, out); }
+extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, const h2v_plan_opts *opts, h2v_plan **out) {
+    // 1. the arguments
+    if (!blob || !out) return fail(H2V_E_ARG, "null argument");
+    const uint32_t opt_fix_c = opts ? opts->fixed_base_window_bits : 0u;
+    if (opt_fix_c != 0 && opt_fix_c != 4 && opt_fix_c != 8 && opt_fix_c != 12) return fail(H2V_E_ARG, "fixed_base_window_bits: 0 (auto), 4, 8 or 12");
+    *out = nullptr;
+    // 2. the blob, validated completely on the host before any device work (h2v_planblob.hpp)
+    planblob::View v;
+    std::string why;
+    if (int rc = planblob::parse(blob, len, v, why)) return fail(rc, why);
+    // 3. the device
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(H2V_E_DEVICE, "no HIP device: the HIP backend is required (no CPU fallback)");
+    if (device < 0 || device >= ndev) return fail(H2V_E_ARG, "device index out of range");
+    ALIVE_DEV(device);
+    HIPCHK(hipSetDevice(device));
+    h2v_plan *p = new h2v_plan();
+    p->device = device;
+    // THE failure exit from here on: whatever has been allocated so far goes the way h2v_plan_free would send it
+    auto give_up = [&](const char *what) { plan_release(p); delete p; return fail(H2V_E_DEVICE, what); };
+    // 4. the blob on the device, its term table as the MSM kernel wants it (planblob::device_terms)
+    if (hipMalloc(&p->blob, len) != hipSuccess) return give_up("hipMalloc(plan) failed");
+    if (v.ivc) {
+        const uint32_t ft[8] = {H2V_TERM_PROOF_POINT, 0, H2V_TERM_PROOF_POINT, 1, H2V_TERM_PROOF_POINT, 2, H2V_TERM_PROOF_POINT, 3};
+        if (hipMalloc(&p->fold_terms, sizeof ft) != hipSuccess || hipMemcpy(p->fold_terms, ft, sizeof ft, hipMemcpyHostToDevice) != hipSuccess)
+            return give_up("fold term upload failed");
+    }
+    {
+        std::vector<uint8_t> patched(blob, blob + len);
+        const std::vector<uint8_t> terms = planblob::device_terms(blob, v);
+        memcpy(patched.data() + v.off_terms, terms.data(), terms.size());
+        if (hipMemcpy(p->blob, patched.data(), len, hipMemcpyHostToDevice) != hipSuccess) return give_up("plan upload failed");
+    }
+    // 5. the device view and the host-side facts, from the View
+    plan_fill(p, v, blob, len);
+    H2vDevPlan &d = p->d;
+    // 6. the tables.  Window tables of the VK bases for the MSM ladder: [1..8]B and [1..8]phi(B), affine, computed once per plan
+    const size_t vk_tab_bytes = (size_t)v.n_bases * 448 * 4 + 16;
+    if (hipMalloc(&p->vk_tab, vk_tab_bytes) != hipSuccess || hipMemset(p->vk_tab, 0, vk_tab_bytes) != hipSuccess) return give_up("hipMalloc(vk tables) failed");
+    if (v.n_bases) {
+        hipLaunchKernelGGL(k_vk_tables, dim3((v.n_bases + 63) / 64), dim3(64), 0, nullptr, d.vk_bases, v.n_bases, (uint32_t *)p->vk_tab);
+        if (hipDeviceSynchronize() != hipSuccess) return give_up("VK window-table kernel failed");
+    }
+    d.vk_tab = (const uint32_t *)p->vk_tab;
+    std::vector<uint32_t> six;   // the six-lane pairing engine's own line constants (host math, once per plan)
+    if (planblob::six_line_tables(blob, v, six)) {
+        if (hipMalloc(&p->six_tab, six.size() * 4) != hipSuccess || hipMemcpy(p->six_tab, six.data(), six.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+            return give_up("six-lane line table upload failed");
+        d.six_norm28 = (const uint32_t *)p->six_tab;
+        d.six_k = d.six_norm28 + planblob::SIX_NORM_DW;
+    }
+    if (v.n_fix) {   // the fixed-base launches of the MSM (tests force the window width: h2v_plan_opts)
+        const planblob::FixedTables ft = planblob::fixed_tables(v.n_bases, opt_fix_c);
+        if (!plan_fixed_tables(p, ft)) return give_up("fixed-base table setup failed");
+        d.fix_c = ft.c; d.fix_W = ft.W;
+        p->n_var = v.n_var; p->n_fix = v.n_fix;
+    }
+    d.fix_tab = (const uint32_t *)p->fix_tab; d.n_var = p->n_var; d.n_fix = p->n_fix;
+    // 7. the registry
+    { static std::mutex mu; static uint64_t loads = 0; std::lock_guard<std::mutex> lock(mu); p->gen = ++loads; }
+    reg_add(g_plan_live, p);
+    *out = p;
+    return H2V_OK;
 }
 extern "C" void h2v_plan_free(h2v_plan *p) {
     if (!p) return;
@@ -1206,7 +955,7 @@ extern "C" int h2v_probe_set_option(uint32_t option, int32_t value) {
 static uint32_t vm_lds_slots(const H2vDevPlan &d) {
     if (d.vm_lanes > 1) return 64 / d.vm_lanes;   // validated at load: fits
     uint32_t P = 64;
-    while (P >= 8 && (size_t)d.n_regs * 32 * P > H2V_VM_LDS_BYTES) P >>= 1;
+    while (P >= 8 && !vm_fits_lds(d.n_regs, 64 / P)) P >>= 1;
     return P >= 8 ? P : 0;
 }
 static int launch_vm(const H2vDevPlan &d0, uint32_t n, uint32_t stride, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst,

@@ -203,6 +203,29 @@ static inline void fp_mont392_bytes(const FpE &a, uint8_t *out) {
     static const FpE c256 = {FP().from_u64(256)};
     to_le_bytes(fp_mul(a, c256).v, out);     // Montgomery form with R = 2^384 is x 2^384; times 2^8
 }
+// THE operand slot of the pairing engines (bls12_381.py: fp_mont28_slot): x 2^392 mod p as 14 limbs of 28 bits, least
+// significant first; in memory a slot is 16 dwords, the last two zero.  Unpacking ORs the limbs in as they are (a limb of an
+// untrusted blob may have its top four bits set) and reduces: the result is a field element whatever the limbs were.
+static inline void fp_to_limbs28(const FpE &a, uint32_t limb[14]) {
+    static const FpE c256 = {FP().from_u64(256)};
+    const U384 m = fp_mul(a, c256).v;
+    for (int i = 0; i < 14; i++) {
+        const int bit = 28 * i, wd = bit >> 6, sh = bit & 63;
+        uint64_t v = m.w[wd] >> sh;
+        if (sh > 36 && wd + 1 < 6) v |= m.w[wd + 1] << (64 - sh);
+        limb[i] = (uint32_t)(v & 0xfffffffu);
+    }
+}
+static inline FpE fp_from_limbs28(const uint32_t limb[14]) {
+    static const U384 c376 = [] { U384 c; c.w[5] = (uint64_t)1 << (376 - 320); return c; }();   // x 2^392 times 2^376 / 2^384: x 2^384
+    U384 m;
+    for (int i = 0; i < 14; i++) {
+        const int bit = 28 * i, wd = bit >> 6, sh = bit & 63;
+        m.w[wd] |= (uint64_t)limb[i] << sh;
+        if (sh > 36 && wd + 1 < 6) m.w[wd + 1] |= (uint64_t)limb[i] >> (64 - sh);
+    }
+    return FpE{FP().mul(m, c376)};
+}
 
 // ---- Fp2 = Fp[u] / (u^2 + 1)
 struct F2 { FpE a, b; };

@@ -3,6 +3,7 @@
 // (/root/reference/src/plutus_gen/extraction/data/circuit_types/instantiation_data.rs:26-41) plus the
 // straight-line verifier program that `extract_circuit` + the emitters would have rendered as source text.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #define H2V_PLAN_MAGIC "H2VPLAN1"
@@ -48,6 +49,58 @@ enum {
     H2V_OP_NOP,
     H2V_OP_COUNT
 };
+// THE opcode table: what each of a record's three fields holds, and where the record may stand.  The loader's validation
+// (h2v_planblob.hpp: check_program) and the plan compiler's scheduler and register allocator (h2v_plancc.hpp) read these rows
+// and nothing else; plan.py keeps its own lists as the independent model, and tests/test_plan_blob.py compares the two.
+// A register in `dst` is WRITTEN by the record, a register in `a` / `b` is READ by it.
+enum {
+    H2V_ARG_NONE = 0,   // not looked at
+    H2V_ARG_REG,        // a register of the program
+    H2V_ARG_CONST,      // an index into the constant table
+    H2V_ARG_PI,         // an index into the proof's public inputs
+    H2V_ARG_TERM,       // an index into the MSM term table
+    H2V_ARG_OFF32,      // in `a`: a | b << 16 is the byte offset of a 32-byte scalar in the proof
+    H2V_ARG_OFF48       // in `a`: a | b << 16 is the byte offset of a 48-byte point in the proof
+};
+struct H2vOpInfo {
+    uint8_t dst, a, b;    // H2V_ARG_*
+    uint8_t serial;       // the bundle rule: stands on lane 0 with the rest of its bundle idle (the transcript operations AND END)
+    uint8_t transcript;   // the scheduler: a transcript operation - a bundle of its own, in program order (END is not one: the
+                          // scheduler drops it and closes the program itself)
+    uint8_t needs_ci;     // only in a plan with a committed instance
+};
+static constexpr H2vOpInfo H2V_OPS[H2V_OP_COUNT] = {
+    /* END           */ {H2V_ARG_NONE, H2V_ARG_NONE, H2V_ARG_NONE, 1, 0, 0},
+    /* ABSORB_REG    */ {H2V_ARG_NONE, H2V_ARG_REG, H2V_ARG_NONE, 1, 1, 0},
+    /* ABSORB_CI     */ {H2V_ARG_NONE, H2V_ARG_NONE, H2V_ARG_NONE, 1, 1, 1},
+    /* LOAD_INSTANCE */ {H2V_ARG_REG, H2V_ARG_PI, H2V_ARG_NONE, 0, 0, 0},
+    /* READ_POINT    */ {H2V_ARG_NONE, H2V_ARG_OFF48, H2V_ARG_NONE, 1, 1, 0},
+    /* READ_SCALAR   */ {H2V_ARG_REG, H2V_ARG_OFF32, H2V_ARG_NONE, 1, 1, 0},
+    /* SQUEEZE       */ {H2V_ARG_REG, H2V_ARG_NONE, H2V_ARG_NONE, 1, 1, 0},
+    /* CONST         */ {H2V_ARG_REG, H2V_ARG_CONST, H2V_ARG_NONE, 0, 0, 0},
+    /* ADD           */ {H2V_ARG_REG, H2V_ARG_REG, H2V_ARG_REG, 0, 0, 0},
+    /* SUB           */ {H2V_ARG_REG, H2V_ARG_REG, H2V_ARG_REG, 0, 0, 0},
+    /* MUL           */ {H2V_ARG_REG, H2V_ARG_REG, H2V_ARG_REG, 0, 0, 0},
+    /* NEG           */ {H2V_ARG_REG, H2V_ARG_REG, H2V_ARG_NONE, 0, 0, 0},
+    /* INV           */ {H2V_ARG_REG, H2V_ARG_REG, H2V_ARG_NONE, 0, 0, 0},
+    /* OUT_SCALAR    */ {H2V_ARG_TERM, H2V_ARG_REG, H2V_ARG_NONE, 0, 0, 0},
+    /* ASSERT_ZERO   */ {H2V_ARG_NONE, H2V_ARG_REG, H2V_ARG_NONE, 0, 0, 0},
+    /* NOP           */ {H2V_ARG_NONE, H2V_ARG_NONE, H2V_ARG_NONE, 0, 0, 0},
+};
+static_assert(H2V_OP_END == 0 && H2V_OP_SQUEEZE == 6 && H2V_OP_MUL == 10 && H2V_OP_OUT_SCALAR == 13 && H2V_OP_NOP == 15 && H2V_OP_COUNT == 16,
+              "the rows of H2V_OPS stand in the order of the opcodes");
+static constexpr bool h2v_op_known(int op) { return op >= 0 && op < H2V_OP_COUNT; }
+static constexpr bool h2v_op_reads_a(int op) { return h2v_op_known(op) && H2V_OPS[op].a == H2V_ARG_REG; }
+static constexpr bool h2v_op_reads_b(int op) { return h2v_op_known(op) && H2V_OPS[op].b == H2V_ARG_REG; }
+static constexpr bool h2v_op_writes(int op) { return h2v_op_known(op) && H2V_OPS[op].dst == H2V_ARG_REG; }
+static constexpr bool h2v_op_transcript(int op) { return h2v_op_known(op) && H2V_OPS[op].transcript; }
+
+// LDS left for the combiner's register file in a block: 160 KB minus the 8 KB hash buffer and 1 KB of slack (plan.py:
+// VM_LDS_BYTES), and THE rule by which a program of n_regs registers on `lanes` lanes per proof fits it: a block is one wave
+// of 64 / lanes proofs, each register 32 bytes (lanes >= 1).
+#define H2V_VM_LDS_BYTES ((size_t)160 * 1024 - 8192 - 1024)
+static constexpr bool vm_fits_lds(uint32_t n_regs, uint32_t lanes) { return (size_t)n_regs * 32 * (64 / lanes) <= H2V_VM_LDS_BYTES; }
+
 enum { H2V_TERM_PROOF_POINT = 0, H2V_TERM_VK_BASE = 1, H2V_TERM_COMMITTED_INSTANCE = 2, H2V_TERM_ACC_POINT = 3 };
 
 // per-proof status bits produced on the device: H2V_ST_* of include/h2v.h (0 = nothing wrong so far)

@@ -394,19 +394,15 @@ static const U256 &delta_const() {
 }
 
 // ------------------------------------------------------------------------------------------------ scheduling (plan.py: _schedule ...)
-static inline bool is_transcript_op(int op) {
-    return op == H2V_OP_ABSORB_REG || op == H2V_OP_ABSORB_CI || op == H2V_OP_READ_POINT || op == H2V_OP_READ_SCALAR || op == H2V_OP_SQUEEZE;
-}
+// which fields of a record are registers it reads or writes, and which records are transcript operations: h2v_plan.h, H2V_OPS
+static inline bool is_transcript_op(int op) { return h2v_op_transcript(op); }
 static inline int uses_of(const Ins &i, int (&u)[2]) {
-    const int op = i[0];
-    if (op == H2V_OP_ADD || op == H2V_OP_SUB || op == H2V_OP_MUL) { u[0] = i[2]; u[1] = i[3]; return 2; }
-    if (op == H2V_OP_NEG || op == H2V_OP_INV || op == H2V_OP_ABSORB_REG || op == H2V_OP_OUT_SCALAR || op == H2V_OP_ASSERT_ZERO) { u[0] = i[2]; return 1; }
-    return 0;
+    int n = 0;
+    if (h2v_op_reads_a(i[0])) u[n++] = i[2];
+    if (h2v_op_reads_b(i[0])) u[n++] = i[3];
+    return n;
 }
-static inline bool defines(int op) {
-    return op == H2V_OP_LOAD_INSTANCE || op == H2V_OP_READ_SCALAR || op == H2V_OP_SQUEEZE || op == H2V_OP_CONST || op == H2V_OP_ADD ||
-           op == H2V_OP_SUB || op == H2V_OP_MUL || op == H2V_OP_NEG || op == H2V_OP_INV;
-}
+static inline bool defines(int op) { return h2v_op_writes(op); }
 struct Rec { bool some = false; Ins ins{}; };
 typedef std::vector<std::vector<Rec>> Bundles;
 static Bundles schedule(const std::vector<Ins> &code, int lanes, bool pack_mul, const std::map<int, int> &not_before, int n_virt) {
@@ -495,9 +491,8 @@ static Allocated allocate(const Bundles &bundles, const std::vector<int> &keep_a
         for (const Rec &r : bundles[s]) {
             if (!r.some) { out.instrs.push_back(Ins{H2V_OP_NOP, 0, 0, 0}); continue; }
             const int op = r.ins[0], dst = r.ins[1], a = r.ins[2], c = r.ins[3];
-            int pa = a, pc = c, pd = dst;
-            if (op == H2V_OP_ADD || op == H2V_OP_SUB || op == H2V_OP_MUL) { pa = out.mapping[a]; pc = out.mapping[c]; }
-            else if (op == H2V_OP_NEG || op == H2V_OP_INV || op == H2V_OP_ABSORB_REG || op == H2V_OP_OUT_SCALAR || op == H2V_OP_ASSERT_ZERO) pa = out.mapping[a];
+            const int pa = h2v_op_reads_a(op) ? out.mapping[a] : a, pc = h2v_op_reads_b(op) ? out.mapping[c] : c;
+            int pd = dst;
             if (defines(op)) {
                 if (!free_list.empty()) { pd = free_list.back(); free_list.pop_back(); }
                 else pd = n_phys++;
@@ -513,7 +508,6 @@ static Allocated allocate(const Bundles &bundles, const std::vector<int> &keep_a
     return out;
 }
 struct Sched { double cost = 0; Allocated al; int lanes = 0; bool fits = false; };
-static const size_t VM_LDS_BYTES = (size_t)160 * 1024 - 8192 - 1024;
 static void schedule_and_allocate(const Builder &b, const std::vector<int> &keep_alive, Sched &narrow, bool &has_wide, Sched &wide) {
     static const int choices[] = {1, 2, 4, 8, 16};
     std::vector<Sched> cands;
@@ -525,7 +519,7 @@ static void schedule_and_allocate(const Builder &b, const std::vector<int> &keep
             const double cost = schedule_cost(bun);
             if (!have || cost < best.cost) { best.cost = cost; best.al = allocate(bun, keep_alive, b.n_virt); best.lanes = L; have = true; }
         }
-        best.fits = (size_t)best.al.n_regs * 32 * (64 / L) <= VM_LDS_BYTES;
+        best.fits = vm_fits_lds((uint32_t)best.al.n_regs, (uint32_t)L);
         cands.push_back(std::move(best));
     }
     std::vector<const Sched *> fitting;
@@ -567,17 +561,9 @@ static void put_f2(std::vector<uint8_t> &b, const F2 &v) {
     fp_mont392_bytes(v.b, t); b.insert(b.end(), t, t + 48);
 }
 static void put_slot28(std::vector<uint8_t> &b, const FpE &v) {   // bls12_381.py: fp_mont28_slot
-    uint8_t t[48];
-    fp_mont392_bytes(v, t);
-    U384 m;
-    for (int i = 0; i < 48; i++) m.w[i / 8] |= (uint64_t)t[i] << (8 * (i % 8));
-    for (int i = 0; i < 14; i++) {
-        const int bit = 28 * i;
-        uint64_t limb = m.w[bit / 64] >> (bit % 64);
-        if (bit % 64 > 36 && bit / 64 + 1 < 6) limb |= m.w[bit / 64 + 1] << (64 - bit % 64);
-        put32(b, (uint32_t)(limb & 0xfffffffu));
-    }
-    for (int i = 0; i < 8; i++) b.push_back(0);
+    uint32_t limb[16] = {};
+    fp_to_limbs28(v, limb);
+    for (uint32_t l : limb) put32(b, l);
 }
 struct Line { F2 lam, c; };
 static std::vector<Line> g2_line_table(const G2 &q) {   // bls12_381.py: g2_line_table

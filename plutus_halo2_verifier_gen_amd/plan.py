@@ -49,7 +49,7 @@ OP_NAMES = ["END", "ABSORB_REG", "ABSORB_CI", "LOAD_INSTANCE", "READ_POINT", "RE
 # the transcript is one hash chain: these run on lane 0 of a proof's lanes, alone in their bundle, in program order
 TRANSCRIPT_OPS = frozenset((OP_ABSORB_REG, OP_ABSORB_CI, OP_READ_POINT, OP_READ_SCALAR, OP_SQUEEZE))
 VM_LANE_CHOICES = (1, 2, 4, 8, 16)
-VM_LDS_BYTES = 160 * 1024 - 8192 - 1024   # register file budget of one block (h2v_capi.hip: vm_lds_fits)
+VM_LDS_BYTES = 160 * 1024 - 8192 - 1024   # register file budget of one block (h2v_plan.h: vm_fits_lds)
 
 # ---- MSM term kinds (ACC_POINT: the two accumulator points rebuilt from the public inputs, recursion only)
 TERM_PROOF_POINT, TERM_VK_BASE, TERM_COMMITTED_INSTANCE, TERM_ACC_POINT = 0, 1, 2, 3

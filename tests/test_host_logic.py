@@ -390,19 +390,13 @@ def test_plan_loader_rejects_mutated_blobs_without_a_gpu():
     crash the process."""
     import struct
     from plutus_halo2_verifier_gen_amd import backend
-    L = ctypes.CDLL(os.path.join(ROOT, "plutus_halo2_verifier_gen_amd", "libh2v_hip.so"))
-    L.h2v_plan_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    L.h2v_plan_load.restype = ctypes.c_int
-    L.h2v_plan_free.argtypes = [ctypes.c_void_p]
+    from tests.plan_loading import plan_loader
+    load_plan = plan_loader()
     have_gpu = backend.device_count() >= 1
     E_ARG, E_PLAN, E_DEVICE, E_LIMIT = -1, -2, -3, -4
 
     def load(blob):
-        h = ctypes.c_void_p()
-        rc = L.h2v_plan_load(bytes(blob), len(blob), 0, ctypes.byref(h))
-        if rc == 0:
-            L.h2v_plan_free(h)
-        return rc
+        return load_plan(blob)[0]
 
     rng = random.Random(11)
     for name in ("simple_mul", "ivc"):
@@ -498,16 +492,8 @@ def test_plan_loader_rejects_broken_bundles():
     """A bundle whose records depend on each other, or a transcript operation that is not alone on lane 0, must be refused
     by h2v_plan_load on the host (the interpreter's lanes run the records of a bundle in no particular order)."""
     import struct
-    L = ctypes.CDLL(os.path.join(ROOT, "plutus_halo2_verifier_gen_amd", "libh2v_hip.so"))
-    L.h2v_plan_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    L.h2v_plan_load.restype = ctypes.c_int
-    L.h2v_last_error.restype = ctypes.c_char_p
-
-    def load(blob):
-        h = ctypes.c_void_p()
-        rc = L.h2v_plan_load(bytes(blob), len(blob), 0, ctypes.byref(h))
-        assert rc != 0 or not h.value or L.h2v_plan_free(h) is not None or True
-        return rc, (L.h2v_last_error() or b"").decode()
+    from tests.plan_loading import plan_loader
+    load = plan_loader()
 
     vk, _ = V.BUILDERS["simple_mul"]()
     pl = PL.compile_plan(vk)

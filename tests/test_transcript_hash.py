@@ -13,6 +13,7 @@ import struct
 import pytest
 
 from plutus_halo2_verifier_gen_amd import backend, bls12_381 as bls, plan as PL, synth, vk as V
+from tests.plan_loading import plan_loader
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = bls.R
@@ -129,19 +130,9 @@ def test_cpp_compiler_matches_plan_py_on_flavoured_keys(name):
 
 
 def _loader():
-    backend.lib()                          # (built and loadable); a handle of its own, so that the binding's argtypes stay as they are
-    L = C.CDLL(os.path.join(ROOT, "plutus_halo2_verifier_gen_amd", "libh2v_hip.so"))
-    L.h2v_plan_free.argtypes = [C.c_void_p]
-    L.h2v_plan_load.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]
-    L.h2v_plan_load.restype = C.c_int
-
-    def load(blob):
-        h = C.c_void_p()
-        rc = L.h2v_plan_load(bytes(blob), len(blob), 0, C.byref(h))
-        if rc == 0:
-            L.h2v_plan_free(h)
-        return rc
-    return load
+    backend.lib()                          # (built and loadable)
+    load_plan = plan_loader()
+    return lambda blob: load_plan(blob)[0]
 
 
 def test_loader_takes_version_5_and_refuses_what_it_cannot_replay():

@@ -1,13 +1,13 @@
 """CPU side of the hand-assembled VM programs (tests/vm_asm.py): every program and batch the GPU tests of
 tests/test_vm_programs_gpu.py run is built here, passes plan.check_bundles and the loader's validation, the big-integer model
 plan.run_plan is pinned on hand-computed records, and the coverage the batches are meant to have is asserted, not assumed."""
-import ctypes
 import os
 
 import pytest
 
 from plutus_halo2_verifier_gen_amd import plan as PL
 from tests import vm_asm as A
+from tests.plan_loading import plan_loader
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R = A.R
@@ -18,9 +18,7 @@ def test_programs_pass_check_bundles_and_the_loader():
     """every program: plan.check_bundles (inside the assembler, again here for both schedules), and h2v_plan_load's own
     validation of the blob - which ends with H2V_E_DEVICE on a machine without a GPU (H2V_E_PLAN would be a refusal)"""
     from plutus_halo2_verifier_gen_amd import backend
-    lib = ctypes.CDLL(os.path.join(ROOT, "plutus_halo2_verifier_gen_amd", "libh2v_hip.so"))
-    lib.h2v_plan_load.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-    lib.h2v_plan_free.argtypes = [ctypes.c_void_p]
+    load = plan_loader()
     ok_rc = 0 if backend.device_count() >= 1 else E_DEVICE
     plans = A.all_programs()      # every program the GPU tests load: both files read the same tables of tests/vm_asm.py
     assert len(plans) == 2 + 4 + 3 + 3 * 62 + 2 * (6 + 4 + 1 + 2)
@@ -29,11 +27,7 @@ def test_programs_pass_check_bundles_and_the_loader():
         assert pl.instrs[-pl.vm_lanes][0] == PL.OP_END and all(r[0] != PL.OP_END for r in pl.instrs[:-pl.vm_lanes]), name
         if pl.wide:
             PL.check_bundles(pl.wide[2], pl.wide[0])
-        blob = pl.to_bytes()
-        h = ctypes.c_void_p()
-        rc = lib.h2v_plan_load(blob, len(blob), 0, ctypes.byref(h))
-        if rc == 0:
-            lib.h2v_plan_free(h)
+        rc, _msg = load(pl.to_bytes())
         assert rc == ok_rc, (name, rc)
     # the assembler refuses what the device relies on not happening
     with pytest.raises(AssertionError):

@@ -1,7 +1,6 @@
 """CPU tests (no GPU) of keys whose final MSM has more than 64 terms in one sum (vk.WIDE_BUILDERS): the plan loader accepts
 them up to H2V_MAX_MSM_TERMS terms per sum, both plan compilers agree on them, and the oracle accepts their forged proofs and
 rejects the corruptions with the status the narrow keys reject them with."""
-import ctypes
 import json
 import os
 import random
@@ -11,14 +10,14 @@ import pytest
 
 from plutus_halo2_verifier_gen_amd import backend, plan as PL, synth
 from plutus_halo2_verifier_gen_amd import vk as V
+from tests.plan_loading import plan_loader, with_terms as _with_terms
 from tests.test_host_logic import _set_sizes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 H2V_E_DEVICE, H2V_E_LIMIT = -3, -4
 MAX_TERMS = 4096
 # plan header words (csrc/h2v_plan.h)
-HW_N_TERMS, HW_OFF_TERMS, HW_TOTAL_LEN, HW_IVC, HW_N_MAIN_TERMS = 9, 18, 22, 25, 26
-TERM_VK_BASE = 1
+HW_IVC, HW_N_MAIN_TERMS = 25, 26
 
 
 def _wide(name):
@@ -27,12 +26,7 @@ def _wide(name):
 
 
 def _load_rc(blob: bytes):
-    L = backend.lib()
-    h = ctypes.c_void_p()
-    rc = L.h2v_plan_load(blob, len(blob), 0, ctypes.byref(h))
-    if rc == 0:
-        L.h2v_plan_free(h)
-    return rc, (L.h2v_last_error() or b"").decode()
+    return plan_loader()(blob)
 
 
 def _has_gpu():
@@ -41,19 +35,6 @@ def _has_gpu():
 
 def _oracle_vk(orc, vk):
     return orc.OracleVK(orc.vk_desc(json.loads(vk.to_json()), vk.omega, vk.omega_inv, vk.barycentric_weight))
-
-
-def _with_terms(blob: bytes, n_terms: int, n_main: int) -> bytes:
-    """The plan with its MSM term table replaced by one of n_terms VK-base terms (appended at the end of the blob)."""
-    w = list(struct.unpack_from("<%dI" % PL.PLAN_HDR_WORDS, blob, 8))
-    body = bytearray(blob)
-    while len(body) % 16:
-        body.append(0)
-    off = len(body)
-    body += struct.pack("<II", TERM_VK_BASE, 0) * n_terms
-    w[HW_OFF_TERMS], w[HW_N_TERMS], w[HW_N_MAIN_TERMS], w[HW_TOTAL_LEN] = off, n_terms, n_main, len(body)
-    struct.pack_into("<%dI" % PL.PLAN_HDR_WORDS, body, 8, *w)
-    return bytes(body)
 
 
 def test_wide_builders_are_wide_and_apart_from_builders():
