@@ -127,6 +127,8 @@ EXPORTS = [
     "h2v_aggregate_batch", "h2v_aggregate_batch_device", "h2v_aggregate_mixed", "h2v_aggregate_mixed_device", "h2v_plan_same_srs",
     "h2v_workspace_seed_used", "h2v_workspace_seed_ms", "h2v_probe_batch_seed", "h2v_plan_key_tag",
 ]
+# exported for the tests alone and not part of include/h2v.h (csrc/h2v_probes.hpp)
+PROBE_ONLY_EXPORTS = ["h2v_probe_device_memory"]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
 TRANSCRIPT_CARDANO_BLAKE2B_256, TRANSCRIPT_BLAKE2B_512 = 0, 1
@@ -220,6 +222,7 @@ def lib():
         L.h2v_workspace_seed_ms.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
         L.h2v_probe_batch_seed.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.POINTER(Batch), C.c_uint32, C.c_uint32, C.c_void_p]
         L.h2v_plan_key_tag.argtypes = [C.c_void_p, C.c_void_p]
+        L.h2v_probe_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
         L.h2v_aggregate_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RlcOpts),
                                           C.POINTER(AggregateInfo)]
         L.h2v_aggregate_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -704,6 +707,14 @@ def probe_mixed_fold_sums(ws):
     out = C.create_string_buffer(192)
     check(lib().h2v_probe_mixed_fold_sums(ws.handle, out))
     return _unxy(out.raw[:96]), _unxy(out.raw[96:])
+
+
+def probe_device_memory(device: int = 0):
+    """h2v_probe_device_memory: what the library's owners hold on `device` right now - (device blocks, device bytes, pinned
+    blocks, pinned bytes, events).  Counts; no GPU is touched."""
+    out = (C.c_uint64 * 5)()
+    check(lib().h2v_probe_device_memory(device, out))
+    return tuple(int(v) for v in out)
 
 
 def probe_batch_seed(form: int, key_tag: bytes, proofs: bytes, proof_off=None, instances: Optional[bytes] = None,

@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <initializer_list>
 #include <mutex>
 #include <string>
@@ -29,6 +30,10 @@
 #include "h2v_mixed_tables.hpp"
 #include "h2v_plancc.hpp"
 #include "h2v_planblob.hpp"
+#include "h2v_ws_layout.hpp"
+using wslayout::vm_lds_slots;
+using wslayout::msm_sum_width;
+static_assert(sizeof(PipArgs) == PIP_ARGS_BYTES, "h2v_pip_sizes.hpp: the argument record of a bucket MSM");
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) {
@@ -48,31 +53,89 @@ static int fail(int code, const std::string &msg) {
 
 extern "C" const char *h2v_last_error(void) { return g_err.c_str(); }
 
+// THE owner of device memory, pinned host memory and events.  Every block and every event of this file belongs to exactly one
+// Owner - a member of the struct whose typed pointer fields name them (h2v_plan, h2v_workspace, HostSlot, Coalesce, PipWs, RlcWs,
+// RlcWs::Grp, MixedWs, MixedWs::Slot) - which records WHERE the handle is kept, so that release() frees whatever was recorded and
+// leaves every field NULL: a buffer added to a struct cannot be forgotten in a list, and a second release does nothing.  Each block
+// is an allocation of its own (hipFree's implicit device wait and the alignment of every buffer depend on it).  No destructor:
+// the holder releases after ITS waits, on the right device (ws_release, plan_release).  A holder must not move while its owner
+// holds anything; assigning a fresh holder over a released one (`g = Grp()`) is the one copy there is, and both owners are empty.
+// g_mem_live: what is live per device, for h2v_probe_device_memory - device blocks, device bytes, pinned blocks, pinned bytes, events.
+static std::atomic<uint64_t> g_mem_live[16][5];
+struct Owner {
+    using Fill = wslayout::Fill;
+    static constexpr Fill NONE = wslayout::NONE, ZERO = wslayout::ZERO, ONES = wslayout::ONES;
+    struct Block { void **at; size_t bytes; bool pinned; };
+    std::vector<Block> blocks;
+    std::vector<hipEvent_t *> events;
+    int dev = -1;                      // where everything recorded lives: the device that was current at the first allocation
+    Owner() = default;
+    Owner(const Owner &) = delete;
+    Owner &operator=(const Owner &o) { if (!empty() || !o.empty()) abort(); return *this; }
+    bool empty() const { return blocks.empty() && events.empty(); }
+    void count(int what, uint64_t by) { if (dev >= 0 && dev < 16) g_mem_live[dev][what] += by; }
+    bool take(void **at, size_t bytes, bool pinned, Fill fill) {
+        *at = nullptr;
+        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = -1;
+        if ((pinned ? hipHostMalloc(at, bytes, hipHostMallocDefault) : hipMalloc(at, bytes)) != hipSuccess) { *at = nullptr; return false; }
+        if (!*at) return true;         // (a request of no bytes)
+        blocks.push_back({at, bytes, pinned});
+        count(pinned ? 2 : 0, 1); count(pinned ? 3 : 1, bytes);
+        if (fill != NONE && pinned) memset(*at, fill, bytes);
+        return fill == NONE || pinned || hipMemset(*at, fill, bytes) == hipSuccess;
+    }
+    template <class T> bool alloc(T *&field, size_t bytes, Fill fill = NONE) { return take((void **)&field, bytes, false, fill); }
+    template <class T> bool alloc_pinned(T *&field, size_t bytes, Fill fill = NONE) { return take((void **)&field, bytes, true, fill); }
+    // a row of a size table (h2v_ws_layout.hpp); a row of no bytes is a buffer the shape does not have
+    template <class T> bool alloc(T *&field, const wslayout::Row &r) { return r.bytes == 0 || alloc(field, r.bytes, r.fill); }
+    template <class T> bool alloc_pinned(T *&field, const wslayout::Row &r) { return r.bytes == 0 || alloc_pinned(field, r.bytes, r.fill); }
+    bool event(hipEvent_t &e, unsigned flags) {
+        if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = -1;
+        if (hipEventCreateWithFlags(&e, flags) != hipSuccess) { e = nullptr; return false; }
+        events.push_back(&e);
+        count(4, 1);
+        return true;
+    }
+    void free_block(const Block &b) {
+        if (*b.at) (void)(b.pinned ? hipHostFree(*b.at) : hipFree(*b.at));
+        *b.at = nullptr;
+        count(b.pinned ? 2 : 0, (uint64_t)0 - 1); count(b.pinned ? 3 : 1, (uint64_t)0 - b.bytes);
+    }
+    // one block back, the rest stays (a block that is re-allocated larger); a field this owner does not hold is left alone
+    template <class T> void drop(T *&field) {
+        for (size_t k = 0; k < blocks.size(); k++)
+            if (blocks[k].at == (void **)&field) { free_block(blocks[k]); blocks.erase(blocks.begin() + (long)k); return; }
+    }
+    void release() {
+        for (const Block &b : blocks) free_block(b);
+        for (hipEvent_t *e : events) { (void)hipEventDestroy(*e); *e = nullptr; count(4, (uint64_t)0 - 1); }
+        blocks.clear(); events.clear();
+    }
+};
 // A block of device (PINNED = false) or pinned host memory that grows on demand, and THE slack rule of every staging block of this
 // file: a request that does not fit frees the block and allocates a quarter more than was asked for, so that a caller whose
 // batches creep upwards does not re-allocate at every call.  What may still be using the old block differs from site to site:
-// the caller passes its wait as `quiet`, which runs before the free (its error is returned and the block stays).  No destructor:
-// the workspace releases its blocks itself (ws_release), on the right device.
+// the caller passes its wait as `quiet`, which runs before the free (its error is returned and the block stays).  The block
+// belongs to the holder's Owner `mem`, which frees it with the holder's other blocks.
 template <bool PINNED> struct GrowBuf {
     uint8_t *p = nullptr;
     size_t cap = 0;
-    template <class Quiet> int ensure(size_t need, const char *what, Quiet &&quiet) {
+    template <class Quiet> int ensure(Owner &mem, size_t need, const char *what, Quiet &&quiet) {
         if (need <= cap) return H2V_OK;
         if (int rc = quiet()) return rc;
-        release();
-        const size_t c = need + need / 4;
-        if ((PINNED ? hipHostMalloc((void **)&p, c, hipHostMallocDefault) : hipMalloc((void **)&p, c)) != hipSuccess) {
-            p = nullptr;
-            return fail(H2V_E_DEVICE, std::string("allocation of ") + what + " failed");
-        }
+        mem.drop(p);
+        cap = 0;
+        const size_t c = wslayout::grown(need);
+        if (!(PINNED ? mem.alloc_pinned(p, c) : mem.alloc(p, c))) return fail(H2V_E_DEVICE, std::string("allocation of ") + what + " failed");
         cap = c;
         return H2V_OK;
     }
-    void release() {
-        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
-        p = nullptr; cap = 0;
-    }
 };
+// an event created when first needed (one that exists stays)
+static int lazy_event(Owner &mem, hipEvent_t &e, unsigned flags) {
+    if (e || mem.event(e, flags)) return H2V_OK;
+    return fail(H2V_E_DEVICE, std::string("hipEventCreate: hip: ") + hipGetErrorString(hipPeekAtLastError()));
+}
 static int no_wait() { return H2V_OK; }      // (a GrowBuf whose old block nothing can still be using)
 
 // ---------------------------------------------------------------------------------------------- lifecycle
@@ -144,6 +207,7 @@ struct h2v_plan {
     int device = 0;
     bool dead = false;         // h2v_shutdown released the device memory: every call with this plan is H2V_E_DEVICE
     H2vDevPlan d{};            // device view
+    Owner mem;                 // of the five blocks below
     void *blob = nullptr;      // one device allocation holding every section
     void *fold_terms = nullptr;  // recursion: the 4-entry term table of the two fold MSMs
     void *vk_tab = nullptr;      // window tables of the VK bases (k_vk_tables at load)
@@ -166,19 +230,18 @@ struct h2v_workspace {
     bool hint_given = false;       // (laned: the caller said so itself; otherwise run_laned estimates it per call)
     uint64_t cap = 0;       // max batch
     uint32_t stride = 0;    // register-file stride (cap rounded up to 64)
-    // what the buffers were sized for (the creating plan's shape): a plan fits iff each of its values is <= these
-    uint32_t sz_terms = 0, sz_slots = 0, sz_regs = 0 /* 0: register file in LDS */, sz_trace = 0;
-    bool sz_ivc = false, sz_fix = false;
+    Owner mem;              // of every block and event named by a field of this struct itself (HostSlot, lanes and the lazy sets own theirs)
+    // what the buffers were sized for (the creating plan's shape, or the union of several): a plan fits iff wslayout::fits says so.
+    // A laned workspace: the shape its lanes are created with when first used
+    wslayout::Shape shape;
     uint32_t *regs = nullptr, *scalars = nullptr, *pts = nullptr, *er = nullptr, *status = nullptr, *trace = nullptr, *msm_tab = nullptr;
     // recursion (IVC): acc_left / acc_right_final sums, the fold's points + scalars, and the folded el / er
     uint32_t *accl = nullptr, *accr = nullptr, *fold_pts = nullptr, *fold_scal = nullptr, *el2 = nullptr, *er2 = nullptr;
     uint32_t *pt_tab = nullptr;  // MSM window tables of every per-proof point, written by the decompression kernel
     uint32_t *er_fix = nullptr;  // sum of the VK-base terms when the MSM is split into a ladder and a fixed-base launch
     // partial sums of a segmented MSM, [segment][proof][36 dwords] (plans with a sum of more than 64 terms only): room for
-    // sz_segs segments of cap proofs (msm_max_segments of the widest sum the workspace was created for)
+    // shape.segs segments of cap proofs (msm_max_segments of the widest sum the workspace was created for)
     uint32_t *msm_parts = nullptr;
-    uint32_t sz_segs = 0;
-    uint32_t lane_width = 0;     // laned: the widest MSM sum its lanes are created for (msm_sum_width; a multi-plan set: the widest plan's)
     uint32_t *dec_ctr = nullptr; // work-queue counter of the decompression launch
     uint8_t *valid = nullptr, *valid_sub = nullptr, *accept = nullptr;
     // pair check (run_check): the two-slot view of 96-byte records - offsets 96 i (cap + 1 entries) and the slot table {0, 48} -
@@ -251,10 +314,10 @@ struct h2v_workspace {
     bool defer_joins = false;
     uint32_t lanes_per_proof = 0;           // lanes the per-proof mode cycles through (the RLC mode uses all n_lanes)
     uint64_t next_lane = 0;                 // round-robin position (persists across calls: consecutive calls interleave)
-    H2vDevPlan lane_plan{};                 // the creating plan's shape: lanes are created when first used
     // host-buffer batches in flight on a laned workspace (h2v_verify_batch_submit / _wait): a ring of staging slots, each
     // with its own pinned block, device block and accept buffers; uploads on `hs`, downloads on `hs_down` (stage_batch)
     struct HostSlot {
+        Owner mem;
         GrowBuf<false> in_block, d_accept;      // (d_accept: laned only)
         GrowBuf<true> h_block, h_accept;
         hipEvent_t ev = nullptr;
@@ -308,27 +371,22 @@ static uint32_t *rec_word(h2v_workspace *w, const CallRec &r) { return w->rec_fa
 // ---------------------------------------------------------------------------------------------- plan
 static void plan_release(h2v_plan *p) {   // the device memory; the host-side facts (h2v_plan_info) stay
     (void)hipSetDevice(p->device);
-    if (p->blob) (void)hipFree(p->blob);
-    if (p->fold_terms) (void)hipFree(p->fold_terms);
-    if (p->vk_tab) (void)hipFree(p->vk_tab);
-    if (p->fix_tab) (void)hipFree(p->fix_tab);
-    if (p->six_tab) (void)hipFree(p->six_tab);
-    p->blob = p->fold_terms = p->vk_tab = p->fix_tab = p->six_tab = nullptr;
+    p->mem.release();
 }
 // All-window tables of the VK bases for the fixed-base launches of the MSM (planblob::fixed_tables has the shape): every window
 // multiple of every VK base.  The window bases are a temporary block of this function.
 static bool plan_fixed_tables(h2v_plan *p, const planblob::FixedTables &ft) {
     const uint32_t n_bases = p->d.n_vk_bases;
+    Owner tmp;
     void *wbase = nullptr;
-    bool ok = hipMalloc(&p->fix_tab, ft.bytes + 16) == hipSuccess && hipMemset(p->fix_tab, 0, ft.bytes + 16) == hipSuccess &&
-              hipMalloc(&wbase, (size_t)n_bases * ft.W * 96 + 16) == hipSuccess;
+    bool ok = p->mem.alloc(p->fix_tab, ft.bytes + 16, Owner::ZERO) && tmp.alloc(wbase, (size_t)n_bases * ft.W * 96 + 16);
     if (ok) {
         hipLaunchKernelGGL(k_vk_fixed_window_bases, dim3((n_bases * ft.W + 63) / 64), dim3(64), 0, nullptr, p->d.vk_bases, n_bases, ft.c, ft.W, (uint32_t *)wbase);
         const uint64_t entries = (uint64_t)n_bases * ft.W * ft.entries;
         hipLaunchKernelGGL(k_vk_fixed_tables, dim3((uint32_t)((entries + 63) / 64)), dim3(64), 0, nullptr, (const uint32_t *)wbase, n_bases * ft.W, ft.c, (uint32_t *)p->fix_tab);
         ok = hipDeviceSynchronize() == hipSuccess;
     }
-    if (wbase) (void)hipFree(wbase);
+    tmp.release();
     return ok;
 }
 // What a load learns on the host: the device view of the uploaded blob (the table pointers follow as the tables are built)
@@ -379,10 +437,10 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
     // THE failure exit from here on: whatever has been allocated so far goes the way h2v_plan_free would send it
     auto give_up = [&](const char *what) { plan_release(p); delete p; return fail(H2V_E_DEVICE, what); };
     // 4. the blob on the device, its term table as the MSM kernel wants it (planblob::device_terms)
-    if (hipMalloc(&p->blob, len) != hipSuccess) return give_up("hipMalloc(plan) failed");
+    if (!p->mem.alloc(p->blob, len)) return give_up("hipMalloc(plan) failed");
     if (v.ivc) {
         const uint32_t ft[8] = {H2V_TERM_PROOF_POINT, 0, H2V_TERM_PROOF_POINT, 1, H2V_TERM_PROOF_POINT, 2, H2V_TERM_PROOF_POINT, 3};
-        if (hipMalloc(&p->fold_terms, sizeof ft) != hipSuccess || hipMemcpy(p->fold_terms, ft, sizeof ft, hipMemcpyHostToDevice) != hipSuccess)
+        if (!p->mem.alloc(p->fold_terms, sizeof ft) || hipMemcpy(p->fold_terms, ft, sizeof ft, hipMemcpyHostToDevice) != hipSuccess)
             return give_up("fold term upload failed");
     }
     {
@@ -396,7 +454,7 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
     H2vDevPlan &d = p->d;
     // 6. the tables.  Window tables of the VK bases for the MSM ladder: [1..8]B and [1..8]phi(B), affine, computed once per plan
     const size_t vk_tab_bytes = (size_t)v.n_bases * 448 * 4 + 16;
-    if (hipMalloc(&p->vk_tab, vk_tab_bytes) != hipSuccess || hipMemset(p->vk_tab, 0, vk_tab_bytes) != hipSuccess) return give_up("hipMalloc(vk tables) failed");
+    if (!p->mem.alloc(p->vk_tab, vk_tab_bytes, Owner::ZERO)) return give_up("hipMalloc(vk tables) failed");
     if (v.n_bases) {
         hipLaunchKernelGGL(k_vk_tables, dim3((v.n_bases + 63) / 64), dim3(64), 0, nullptr, d.vk_bases, v.n_bases, (uint32_t *)p->vk_tab);
         if (hipDeviceSynchronize() != hipSuccess) return give_up("VK window-table kernel failed");
@@ -404,7 +462,7 @@ extern "C" int h2v_plan_load_ex(const uint8_t *blob, size_t len, int device, con
     d.vk_tab = (const uint32_t *)p->vk_tab;
     std::vector<uint32_t> six;   // the six-lane pairing engine's own line constants (host math, once per plan)
     if (planblob::six_line_tables(blob, v, six)) {
-        if (hipMalloc(&p->six_tab, six.size() * 4) != hipSuccess || hipMemcpy(p->six_tab, six.data(), six.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
+        if (!p->mem.alloc(p->six_tab, six.size() * 4) || hipMemcpy(p->six_tab, six.data(), six.size() * 4, hipMemcpyHostToDevice) != hipSuccess)
             return give_up("six-lane line table upload failed");
         d.six_norm28 = (const uint32_t *)p->six_tab;
         d.six_k = d.six_norm28 + planblob::SIX_NORM_DW;
@@ -467,52 +525,36 @@ static void mixed_release(h2v_workspace *w);
 static int co_flush(h2v_workspace *w);
 static int lane_streams(uint32_t l, hipStream_t *main_st, hipStream_t *side_st);
 static void slot_release(h2v_workspace::HostSlot &sl) {
-    sl.in_block.release(); sl.d_accept.release(); sl.h_block.release(); sl.h_accept.release();
-    if (sl.ev) (void)hipEventDestroy(sl.ev);
+    sl.mem.release();
     sl = h2v_workspace::HostSlot();
 }
 static void ws_release(h2v_workspace *w) {
     (void)hipSetDevice(w->device);
-    if (w->hs_down) (void)hipStreamSynchronize(w->hs_down);
-    for (auto &sl : w->hslot) slot_release(sl);
-    for (uint32_t l = 0; l < (uint32_t)h2v_workspace::MAXL; l++)
-        if (w->lane_st[l]) { (void)hipStreamSynchronize(w->lane_st[l]); }
+    // the waits, all of them before anything is freed: the copy streams, the lanes' streams, the pipeline's (pool streams are
+    // shared: make_stream; h2v_shutdown destroys them); mixed_release and every lane's own ws_release wait for what is theirs
+    for (hipStream_t q : {w->hs_down, w->hs, w->pmain, w->pside}) if (q) (void)hipStreamSynchronize(q);
+    for (hipStream_t q : w->lane_st) if (q) (void)hipStreamSynchronize(q);
+    // then one release per owner
     mixed_release(w);
-    co_release(w);                        // (an open group is dropped: whoever frees a workspace has joined it or no longer wants the verdicts)
-    for (uint32_t l = 0; l < (uint32_t)h2v_workspace::MAXL; l++) {
-        if (w->lane[l]) { ws_release(w->lane[l]); delete w->lane[l]; w->lane[l] = nullptr; }
-        if (w->lane_ev[l]) (void)hipEventDestroy(w->lane_ev[l]);
-    }
+    for (h2v_workspace *&lw : w->lane)
+        if (lw) { ws_release(lw); delete lw; lw = nullptr; }
     w->n_lanes = 0;
+    for (auto &sl : w->hslot) slot_release(sl);
+    co_release(w);                        // (an open group is dropped: whoever frees a workspace has joined it or no longer wants the verdicts)
     if (w->rlc) { rlc_release(w->rlc); w->rlc = nullptr; }
     for (struct RlcWs *r : w->rlc_parked) rlc_release(r);
     w->rlc_parked.clear();
     if (w->prlc) { rlc_release(w->prlc); w->prlc = nullptr; }
-    for (hipEvent_t &e : w->ev_pipe) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (w->h_rlc_stats) (void)hipHostFree(w->h_rlc_stats);
-    void *ptrs[] = {w->rlc_stats, w->rec_fail, w->regs, w->scalars, w->pts, w->er, w->status, w->trace, w->valid, w->valid_sub, w->er_fix, w->msm_parts, w->dec_ctr, w->accept, w->msm_tab,
-                    w->accl, w->accr, w->fold_pts, w->fold_scal, w->el2, w->er2, w->pt_tab, w->pair_off, w->pair_pts};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    w->res.release(); w->agg_parts.release();
-    for (hipEvent_t &e : w->ev_agg) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (w->seed_ring) { (void)hipFree(w->seed_ring); w->seed_ring = nullptr; }
-    w->seed_digests.release();
-    for (auto &pair : w->ev_seed) for (hipEvent_t &e : pair) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+    w->mem.release();
     w->ev_seed_last = nullptr;
-    if (w->hs) (void)hipStreamSynchronize(w->hs);   // (pool streams are shared: make_stream; h2v_shutdown destroys them)
     if (w->copy_streams_owned) {
         if (w->hs) (void)hipStreamDestroy(w->hs);
         if (w->hs_down) (void)hipStreamDestroy(w->hs_down);
         w->hs = w->hs_down = nullptr; w->copy_streams_owned = false;
     }
-    for (hipStream_t q : {w->pmain, w->pside}) if (q) (void)hipStreamSynchronize(q);
-    for (hipEvent_t e : {w->ev_fork, w->ev_join, w->ev_hold, w->ev_fix, w->ev_done}) if (e) (void)hipEventDestroy(e);
-    for (CallRec &r : w->rec) for (hipEvent_t e : r.ev) if (e) (void)hipEventDestroy(e);
 }
-static uint32_t vm_lds_slots(const H2vDevPlan &d);
-static uint32_t msm_sum_width(const H2vDevPlan &d);
-// width: the widest MSM sum the workspace must serve (0: the plan's own, msm_sum_width)
-static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bool with_trace, h2v_workspace **out, uint32_t width = 0) {
+// An ordinary workspace (or a lane) of max_batch proofs for plans that fit shape s: the rows of wslayout::pipeline, in their order
+static int ws_create_for(const wslayout::Shape &s, int device, uint64_t max_batch, h2v_workspace **out) {
     if (max_batch == 0 || max_batch > (1ull << 24)) return fail(H2V_E_ARG, "max_batch out of range");
     ALIVE_DEV(device);
     HIPCHK(hipSetDevice(device));
@@ -520,42 +562,24 @@ static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bo
     w->device = device;
     w->cap = max_batch;
     w->stride = (uint32_t)((max_batch + 63) / 64 * 64);
-    const uint64_t slots = H2V_SLOTS(d);
-    w->sz_terms = d.n_terms; w->sz_slots = (uint32_t)slots; w->sz_regs = vm_lds_slots(d) == 0 ? d.n_regs : 0;
-    w->sz_trace = with_trace ? d.n_trace : 0; w->sz_ivc = d.ivc != 0; w->sz_fix = d.fix_tab != nullptr;
-#define WSALLOC(field, bytes)                                                                  \
-    if (hipMalloc((void **)&w->field, (bytes)) != hipSuccess) { ws_release(w); delete w; return fail(H2V_E_DEVICE, "hipMalloc(" #field ") failed"); }
-    if (vm_lds_slots(d) == 0) { WSALLOC(regs, (size_t)d.n_regs * 8 * w->stride * 4) }  // else the register file lives in LDS
-    WSALLOC(scalars, (size_t)max_batch * d.n_terms * 32)
-    WSALLOC(pts, (size_t)max_batch * slots * 96)
-    WSALLOC(valid, (size_t)max_batch * slots)
-    WSALLOC(valid_sub, (size_t)max_batch * slots)
-    WSALLOC(dec_ctr, 4)
-    if (d.fix_tab) { WSALLOC(er_fix, (size_t)max_batch * 36 * 4) }
-    w->sz_segs = msm_max_segments(width ? width : msm_sum_width(d));
-    if (w->sz_segs) { WSALLOC(msm_parts, (size_t)max_batch * w->sz_segs * 144) }
-    WSALLOC(er, (size_t)max_batch * 144)
-    WSALLOC(pt_tab, (size_t)max_batch * slots * 448 * 4)             // per (proof, slot): [1..8]P and [1..8]phi(P), affine, 2 x 14 x 28-bit limbs
-    if (d.ivc) { WSALLOC(msm_tab, (size_t)max_batch * 4 * 2 * 8 * 112) }  // fold MSMs build their four tables on the spot
-    WSALLOC(status, (size_t)max_batch * 4)
-    WSALLOC(accept, (size_t)max_batch)
-    if (with_trace && d.n_trace) { WSALLOC(trace, (size_t)max_batch * d.n_trace * 32) }
-    if (d.ivc) {
-        WSALLOC(accl, (size_t)max_batch * 144)
-        WSALLOC(accr, (size_t)max_batch * 144)
-        WSALLOC(el2, (size_t)max_batch * 144)
-        WSALLOC(er2, (size_t)max_batch * 144)
-        WSALLOC(fold_pts, (size_t)max_batch * 4 * 96)
-        WSALLOC(fold_scal, (size_t)max_batch * 4 * 32)
-    }
-#undef WSALLOC
+    w->shape = s;
+    const auto T = wslayout::pipeline(s, max_batch);
+    const wslayout::Row *failed = nullptr;
+    auto row = [&](auto *&field, wslayout::Pipe k) { if (!failed && !w->mem.alloc(field, T.row[k])) failed = &T.row[k]; };
+    row(w->regs, wslayout::P_REGS); row(w->scalars, wslayout::P_SCALARS); row(w->pts, wslayout::P_PTS); row(w->valid, wslayout::P_VALID);
+    row(w->valid_sub, wslayout::P_VALID_SUB); row(w->dec_ctr, wslayout::P_DEC_CTR); row(w->er_fix, wslayout::P_ER_FIX);
+    row(w->msm_parts, wslayout::P_MSM_PARTS); row(w->er, wslayout::P_ER); row(w->pt_tab, wslayout::P_PT_TAB); row(w->msm_tab, wslayout::P_MSM_TAB);
+    row(w->status, wslayout::P_STATUS); row(w->accept, wslayout::P_ACCEPT); row(w->trace, wslayout::P_TRACE); row(w->accl, wslayout::P_ACCL);
+    row(w->accr, wslayout::P_ACCR); row(w->el2, wslayout::P_EL2); row(w->er2, wslayout::P_ER2); row(w->fold_pts, wslayout::P_FOLD_PTS);
+    row(w->fold_scal, wslayout::P_FOLD_SCAL);
+    if (failed) { const std::string what = failed->name; ws_release(w); delete w; return fail(H2V_E_DEVICE, "hipMalloc(" + what + ") failed"); }
     // Streams are created on first use (ws_streams): the runtime maps streams onto a few hardware queues round robin, and
     // streams that are never used would only make the ones in use collide (several batches in flight: bench.py --inflight).
     bool ok = true;
     for (hipEvent_t *e : {&w->ev_fork, &w->ev_join, &w->ev_hold, &w->ev_fix, &w->ev_done})
-        if (ok) ok = hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+        if (ok) ok = w->mem.event(*e, hipEventDisableTiming);
     for (CallRec &r : w->rec) for (hipEvent_t &e : r.ev)
-        if (ok) ok = hipEventCreate(&e) == hipSuccess;
+        if (ok) ok = w->mem.event(e, hipEventDefault);
     if (!ok) { ws_release(w); delete w; return fail(H2V_E_DEVICE, "stream/event creation failed"); }
     *out = w;
     return H2V_OK;
@@ -563,8 +587,8 @@ static int ws_create_for(const H2vDevPlan &d, int device, uint64_t max_batch, bo
 // Chunk size of the lanes: the batch that gives the kernels of the per-proof pipeline about one wave per SIMD - the merged
 // MSM runs one lane per (proof, term): 65536 / T proofs for 1024 waves (T = 16: 4096, the BASELINE batch; T = 60: 1092) -
 // as a power of two between 1024 and 4096.
-static uint32_t default_chunk(const H2vDevPlan &d) {
-    const double want = 65536.0 / (double)(d.n_main_terms ? d.n_main_terms : 1);
+static uint32_t default_chunk(const wslayout::Shape &s) {
+    const double want = 65536.0 / (double)(s.main_terms ? s.main_terms : 1);
     uint32_t c = 1024;
     while (c < 4096 && (double)c * 1.4142 < want) c <<= 1;
     return c;
@@ -576,7 +600,7 @@ static uint32_t default_chunk(const H2vDevPlan &d) {
 // atms x 2048 3.30 -> 2.78 (2.70), sha256 shape x 1024 1.96 -> 1.86 (1.87), secp256k1 x 512 1.01 -> 0.87, their shares x 128 / x 64
 // 0.32 / 0.17 -> 0.27 / 0.15; simple_mul x 4096 is at 4096 already (8192: the same).  A call that waits for its own chunks is
 // still cut down to default_chunk / 2 per lane (run_laned).
-static uint32_t lane_chunk(const H2vDevPlan &d) { (void)d; return 4096u; }
+static uint32_t lane_chunk() { return 4096u; }
 // Lanes: measured on MI355X, simple_mul, a stream of 4096-proof batches through one laned workspace (deferred joins; ms per
 // batch): per-proof mode, each lane's pipeline on the lane's stream with the decompression beside it on a side stream:
 // 4 lanes 4.60, 5: 4.35, 6: 4.31, 11: 4.72; everything on the lane's stream: 5: 4.64, 8: 4.26, 11: 4.43 (five caller-owned
@@ -592,9 +616,9 @@ static int ensure_lane(h2v_workspace *w, uint32_t l) {
     // NULL, and the next call tries again instead of enqueueing on a NULL stream)
     hipStream_t side_st = nullptr;
     if (int rcs = lane_streams(l, &w->lane_st[l], &side_st)) { w->lane_st[l] = nullptr; return rcs; }
-    if (!w->lane_ev[l] && hipEventCreateWithFlags(&w->lane_ev[l], hipEventDisableTiming) != hipSuccess) { w->lane_ev[l] = nullptr; return fail(H2V_E_DEVICE, "lane event creation failed"); }
+    if (!w->lane_ev[l] && !w->mem.event(w->lane_ev[l], hipEventDisableTiming)) return fail(H2V_E_DEVICE, "lane event creation failed");
     h2v_workspace *lw = nullptr;
-    int rc = ws_create_for(w->lane_plan, w->device, w->chunk, false, &lw, w->lane_width);
+    int rc = ws_create_for(w->shape, w->device, w->chunk, &lw);
     if (rc) return rc;
     lw->one_stream_mode = 2;            // (set per call: laned_depth)
     lw->pside = side_st;                // (the decompression's stream in the two-stream form: the other half of the lane's pair)
@@ -603,24 +627,22 @@ static int ensure_lane(h2v_workspace *w, uint32_t l) {
     w->lane[l] = lw;
     return H2V_OK;
 }
-static int create_lanes_for(const H2vDevPlan &d, int device, uint64_t max_batch, uint32_t n_lanes, uint32_t chunk, h2v_workspace **out, uint32_t width = 0) {
+static int create_lanes_for(const wslayout::Shape &s, int device, uint64_t max_batch, uint32_t n_lanes, uint32_t chunk, h2v_workspace **out) {
     if (max_batch == 0 || max_batch > (1ull << 24)) return fail(H2V_E_ARG, "max_batch out of range");
     if (n_lanes > (uint32_t)h2v_workspace::MAXL) return fail(H2V_E_ARG, "at most 16 lanes");
     // chunk = 0, the library's choice: the plan's own chunk even when max_batch - the largest single call - is smaller: the lanes
     // are what small calls are gathered into (coalesce_call).  An explicit chunk is the caller's, cut to max_batch.
-    if (chunk == 0) chunk = lane_chunk(d);
+    if (chunk == 0) chunk = lane_chunk();
     else if ((uint64_t)chunk > max_batch) chunk = (uint32_t)max_batch;
     HIPCHK(hipSetDevice(device));
     h2v_workspace *w = new h2v_workspace();
     w->device = device; w->cap = max_batch; w->chunk = chunk;
     w->stride = (uint32_t)((max_batch + 63) / 64 * 64);
-    w->lane_plan = d;
-    w->lane_width = width ? width : msm_sum_width(d);
-    w->sz_terms = d.n_terms; w->sz_slots = (uint32_t)H2V_SLOTS(d); w->sz_regs = vm_lds_slots(d) == 0 ? d.n_regs : 0; w->sz_trace = 0; w->sz_ivc = d.ivc != 0; w->sz_fix = d.fix_tab != nullptr;
+    w->shape = s;
     w->lanes_per_proof = n_lanes ? n_lanes : H2V_PER_PROOF_LANES;     // an explicit lane count holds for both modes
     w->n_lanes = n_lanes ? n_lanes : H2V_DEFAULT_LANES;
     w->in_flight_hint = w->n_lanes;
-    bool ok = hipEventCreateWithFlags(&w->ev_fork, hipEventDisableTiming) == hipSuccess && hipMalloc((void **)&w->accept, (size_t)max_batch) == hipSuccess;
+    bool ok = w->mem.event(w->ev_fork, hipEventDisableTiming) && w->mem.alloc(w->accept, wslayout::laned_accept(max_batch));
     // the first lane now (an allocation failure surfaces here, not in the middle of a verify call); the others on first use
     if (ok) ok = ensure_lane(w, 0) == H2V_OK;
     if (!ok) { const std::string e = g_err; ws_release(w); delete w; return fail(H2V_E_DEVICE, "lane creation failed: " + e); }
@@ -631,14 +653,14 @@ static int create_lanes_for(const H2vDevPlan &d, int device, uint64_t max_batch,
 extern "C" int h2v_workspace_create_lanes(const h2v_plan *p, uint64_t max_batch, uint32_t n_lanes, uint32_t chunk, h2v_workspace **out) {
     if (!p || !out) return fail(H2V_E_ARG, "null argument");
     ALIVE(p);
-    return create_lanes_for(p->d, p->device, max_batch, n_lanes, chunk, out);
+    return create_lanes_for(wslayout::shape_of(p->d, false), p->device, max_batch, n_lanes, chunk, out);
 }
 // One set of lanes for SEVERAL plans of one device (a node that verifies proofs of several circuits; BASELINE configs[2] names a
 // mixed batch): the lane workspaces are sized for the largest of every dimension - MSM terms, point slots, the combiner's
 // global register file where a plan needs one, the recursion and fixed-base buffers where a plan has them - so every listed plan
 // passes ws_fits, and the calls of all of them go round robin through the SAME lanes and streams.  (One laned workspace per plan
 // also works, but their lanes share the pool's sixteen streams pairwise: two plans x 2048 proofs, 6.70 ms per step on two
-// workspaces.)  The shape below is a synthetic H2vDevPlan that only ws_create_for / default_chunk / laned_depth ever read.
+// workspaces.)
 extern "C" int h2v_workspace_create_multi(const h2v_plan *const *plans, uint32_t n_plans, uint64_t max_batch, uint32_t n_lanes, uint32_t chunk, h2v_workspace **out) {
     if (!plans || !out || n_plans == 0) return fail(H2V_E_ARG, "null argument");
     for (uint32_t k = 0; k < n_plans; k++) {
@@ -646,34 +668,18 @@ extern "C" int h2v_workspace_create_multi(const h2v_plan *const *plans, uint32_t
         ALIVE(plans[k]);
         if (plans[k]->device != plans[0]->device) return fail(H2V_E_ARG, "the plans of one workspace must live on one device");
     }
-    H2vDevPlan u = plans[0]->d;
-    uint32_t slots = 0, regs_global = 0, chunk_min = 0, width = 0;
-    for (uint32_t k = 0; k < n_plans; k++) {
-        const H2vDevPlan &d = plans[k]->d;
-        width = msm_sum_width(d) > width ? msm_sum_width(d) : width;
-        u.n_terms = d.n_terms > u.n_terms ? d.n_terms : u.n_terms;
-        u.n_main_terms = d.n_main_terms > u.n_main_terms ? d.n_main_terms : u.n_main_terms;
-        slots = (uint32_t)H2V_SLOTS(d) > slots ? (uint32_t)H2V_SLOTS(d) : slots;
-        if (vm_lds_slots(d) == 0 && d.n_regs > regs_global) regs_global = d.n_regs;
-        if (d.ivc) u.ivc = d.ivc;
-        if (d.fix_tab) u.fix_tab = d.fix_tab;
-        const uint32_t c = lane_chunk(d);
-        chunk_min = chunk_min == 0 || c < chunk_min ? c : chunk_min;
-    }
-    u.n_ci = 0;
-    u.n_points = slots - 2u * (u.ivc ? 1u : 0u);                  // H2V_SLOTS(u) == the largest plan's
-    if (regs_global) { u.vm_lanes = 1; u.n_regs = regs_global; }   // vm_lds_slots(u) == 0: a global register file of that size
-    else if (vm_lds_slots(u) == 0) return fail(H2V_E_ARG, "internal: union shape");
-    (void)chunk_min;
-    return create_lanes_for(u, plans[0]->device, max_batch, n_lanes, chunk, out, width);      // (chunk = 0: the library's lane size, whatever max_batch is)
+    wslayout::Shape u = wslayout::shape_of(plans[0]->d, false);
+    for (uint32_t k = 1; k < n_plans; k++) u = wslayout::shape_union(u, wslayout::shape_of(plans[k]->d, false));
+    return create_lanes_for(u, plans[0]->device, max_batch, n_lanes, chunk, out);      // (chunk = 0: the library's lane size, whatever max_batch is)
 }
 extern "C" int h2v_workspace_create(const h2v_plan *p, uint64_t max_batch, h2v_workspace **out) {
     if (!p || !out) return fail(H2V_E_ARG, "null argument");
     // a workspace for batches of at least four chunks is laned: the call is pipelined inside the library (measured,
     // simple_mul: 8192 proofs in one launch per kernel 5.6 ms per 4096 against 5.9 in two chunks; 20480: 5.3 against 4.7)
     ALIVE(p);
-    if (max_batch >= 4ull * default_chunk(p->d)) return h2v_workspace_create_lanes(p, max_batch, 0, 0, out);
-    const int rc = ws_create_for(p->d, p->device, max_batch, false, out);
+    const wslayout::Shape s = wslayout::shape_of(p->d, false);
+    if (max_batch >= 4ull * default_chunk(s)) return h2v_workspace_create_lanes(p, max_batch, 0, 0, out);
+    const int rc = ws_create_for(s, p->device, max_batch, out);
     if (rc == H2V_OK) reg_add(g_ws_live, *out);
     return rc;
 }
@@ -799,20 +805,14 @@ extern "C" int h2v_workspace_hint_in_flight(h2v_workspace *ws, uint32_t n_in_fli
 // A workspace is sized from the plan it was created for; another plan may use it iff every buffer is large enough for
 // it (terms, point slots, a global register file if it needs one, recursion buffers, the fixed-base sum).
 static int ws_fits(const h2v_workspace *w, const h2v_plan *p, uint64_t n, bool want_trace) {
-    const H2vDevPlan &d = p->d;
     if (w->device != p->device) return fail(H2V_E_ARG, "workspace belongs to another device");
     if (w->cap < n) return fail(H2V_E_ARG, "workspace too small for this batch");
     if (w->n_lanes) {
         if (want_trace) return fail(H2V_E_ARG, "a laned workspace has no trace buffer");
         return ws_fits(w->lane[0], p, n < w->chunk ? n : w->chunk, false);
     }
-    if (d.n_terms > w->sz_terms || H2V_SLOTS(d) > w->sz_slots) return fail(H2V_E_ARG, "workspace was created for a smaller plan (MSM terms / point slots)");
-    if (vm_lds_slots(d) == 0 && d.n_regs > w->sz_regs) return fail(H2V_E_ARG, "workspace has no (or too small a) global register file for this plan");
-    if (d.ivc && !w->sz_ivc) return fail(H2V_E_ARG, "workspace was created for a non-recursive plan");
-    if (d.fix_tab && !w->sz_fix) return fail(H2V_E_ARG, "workspace lacks the fixed-base sum buffer of this plan");
-    if (msm_max_segments(msm_sum_width(d)) > w->sz_segs) return fail(H2V_E_ARG, "workspace was created for a plan with narrower MSM sums (no room for the partial sums of a segmented MSM)");
-    if (want_trace && d.n_trace > w->sz_trace) return fail(H2V_E_ARG, "workspace has no trace buffer for this plan");
-    return H2V_OK;
+    const wslayout::Fit f = wslayout::fits(w->shape, wslayout::shape_of(p->d, true), want_trace);
+    return f == wslayout::Fit::OK ? (int)H2V_OK : fail(H2V_E_ARG, wslayout::fit_message(f));
 }
 
 // Library-owned streams.  The runtime multiplexes ordinary streams onto GPU_MAX_HW_QUEUES (default 4) hardware queues per
@@ -952,12 +952,6 @@ extern "C" int h2v_probe_set_option(uint32_t option, int32_t value) {
 // bundles have L records), the Fr register file of the P proofs lives in LDS (160 KB per CU).  A single-lane plan whose
 // register file does not fit 64 proofs runs P = 32 / 16 / 8 proofs per block with the other lanes idle, or - below 8 -
 // with the register file in the workspace's global buffer.
-static uint32_t vm_lds_slots(const H2vDevPlan &d) {
-    if (d.vm_lanes > 1) return 64 / d.vm_lanes;   // validated at load: fits
-    uint32_t P = 64;
-    while (P >= 8 && !vm_fits_lds(d.n_regs, 64 / P)) P >>= 1;
-    return P >= 8 ? P : 0;
-}
 static int launch_vm(const H2vDevPlan &d0, uint32_t n, uint32_t stride, const uint8_t *proofs, const uint64_t *off, const uint8_t *inst,
                      const uint8_t *ci, uint32_t *regs, uint32_t *scalars, uint32_t *status, uint32_t *trace, hipStream_t st) {
     // The wide schedule (more lanes per proof: shorter chain, more waves) when the launch would leave most of the chip
@@ -1014,11 +1008,6 @@ struct SegBuf {
     uint32_t *parts = nullptr; uint32_t max_seg = 0;
     uint32_t room() const { return parts ? max_seg : 0u; }   // (what the shape model takes)
 };
-// the widest sum of a plan: the proof's own MSM; with recursion also acc_right + the fixed bases
-static uint32_t msm_sum_width(const H2vDevPlan &d) {
-    const uint32_t f = d.ivc && d.n_terms > d.n_main_terms + 1 ? d.n_terms - d.n_main_terms - 1 : 0;
-    return d.n_main_terms > f ? d.n_main_terms : f;
-}
 // The one-group range of a term table: terms [term_base, term_base + n_terms), their scalars from column col_base on of
 // scal_stride per proof, summed into `out`.  pt_tab: the per-proof window tables, or NULL (every lane builds its own).
 static H2vMsmArgs msm_args(const H2vDevPlan &d, uint32_t term_base, uint32_t n_terms, uint32_t scal_stride, uint32_t col_base, uint32_t slots,
@@ -1314,7 +1303,7 @@ static int run_pipeline(const Unit &u, h2v_workspace *w, hipStream_t st) {
     // combiner, the rest recorded by pairs_rlc_core - and the pipeline's own markers go to a set of the workspace that nobody reads
     hipEvent_t *ev = rec.ev;
     if (fold) {
-        for (hipEvent_t &e : w->ev_pipe) if (!e) HIPCHK(hipEventCreate(&e));
+        for (hipEvent_t &e : w->ev_pipe) if (int rce = lazy_event(w->mem, e, hipEventDefault)) return rce;
         ev = w->ev_pipe;
     }
     HIPCHK(hipEventRecord(w->ev_fork, st));
@@ -1344,7 +1333,7 @@ static int run_pipeline(const Unit &u, h2v_workspace *w, hipStream_t st) {
     HIPCHK(hipStreamWaitEvent(pm, w->ev_join, 0));
     HIPCHK(hipStreamWaitEvent(pm, w->ev_hold, 0));
     HIPCHK(hipEventRecord(ev[4], pm));
-    const SegBuf seg = {w->msm_parts, w->sz_segs};   // (NULL for workspaces of plans whose sums are all <= 64 terms)
+    const SegBuf seg = {w->msm_parts, w->shape.segs};   // (NULL for workspaces of plans whose sums are all <= 64 terms)
     const MsmModel mm = msm_model();
     const MsmShape single = msm_ladder_shape(mm, d.ivc ? d.n_terms : d.n_main_terms, n, 0.0, true, d.ivc ? 0u : seg.room());
     const MsmSplit split = w->er_fix && d.fix_tab && !d.ivc ? msm_split_shape(mm, MsmSplitTerms{d.n_var, d.n_fix, d.n_main_terms}, n, single, w->in_flight_hint, seg.room())
@@ -1411,11 +1400,11 @@ static int pair_view_ensure(h2v_workspace *w) {
     std::vector<uint64_t> off(w->cap + 1);
     for (uint64_t i = 0; i <= w->cap; i++) off[i] = 96 * i;
     const uint32_t slot_off[2] = {0, 48};
-    if (hipMalloc((void **)&w->pair_pts, 8) != hipSuccess || hipMalloc((void **)&w->pair_off, off.size() * 8) != hipSuccess ||
+    const auto T = wslayout::pair_view(w->cap);
+    if (!w->mem.alloc(w->pair_pts, T.row[wslayout::V_PTS]) || !w->mem.alloc(w->pair_off, T.row[wslayout::V_OFF]) ||
         hipMemcpy(w->pair_pts, slot_off, 8, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(w->pair_off, off.data(), off.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
-        for (void *q : {(void *)w->pair_off, (void *)w->pair_pts}) if (q) (void)hipFree(q);
-        w->pair_off = nullptr; w->pair_pts = nullptr;
+        w->mem.drop(w->pair_off); w->mem.drop(w->pair_pts);
         return fail(H2V_E_DEVICE, "allocation of the pair-check buffers failed");
     }
     return H2V_OK;
@@ -1466,9 +1455,9 @@ static int run_mixed_group(const Unit &u, h2v_workspace *w, hipStream_t st);
 // report into their parent's record)
 static int rlc_stats_ensure(h2v_workspace *w) {
     if (w->rlc_stats) return H2V_OK;
-    if (hipMalloc((void **)&w->rec_fail, h2v_workspace::RING * 4) != hipSuccess ||
-        hipMalloc((void **)&w->rlc_stats, 8) != hipSuccess || hipMemset(w->rlc_stats, 0, 8) != hipSuccess ||
-        hipHostMalloc((void **)&w->h_rlc_stats, 8, hipHostMallocDefault) != hipSuccess)
+    const auto T = wslayout::rlc_stats();
+    if (!w->mem.alloc(w->rec_fail, T.row[wslayout::S_REC_FAIL]) || !w->mem.alloc(w->rlc_stats, T.row[wslayout::S_RLC_STATS]) ||
+        !w->mem.alloc_pinned(w->h_rlc_stats, T.row[wslayout::S_H_RLC_STATS]))
         return fail(H2V_E_DEVICE, "allocation of the routing counters failed");
     w->h_rlc_stats[0] = w->h_rlc_stats[1] = 0;
     return H2V_OK;
@@ -1533,7 +1522,7 @@ static uint32_t laned_depth(const h2v_workspace *w, uint64_t n, bool rlc, int *s
     if (stream_mode) *stream_mode = 1;
     if (rlc) return w->n_lanes;
     const uint64_t m = n < w->chunk ? n : w->chunk;
-    const bool small = (double)m * w->lane_plan.n_terms / 64.0 <= msm_n_simd() / 2.0;
+    const bool small = (double)m * w->shape.terms / 64.0 <= msm_n_simd() / 2.0;
     if (stream_mode) {
         *stream_mode = w->one_stream_mode >= 0 ? w->one_stream_mode : small ? 1 : 2;
     }
@@ -1616,7 +1605,7 @@ static int run_laned(Unit u, h2v_workspace *w, hipStream_t st, Join join) {
     //  and whole chunks keep the full-chip launch shapes - a stream of 16 384-proof calls: 15.9 ms per call cut in 2048s, ~13 in 4096s)
     if (!u.batch_check() && !w->defer_joins && join != Join::NEVER && n > chunk && (uint64_t)n < (uint64_t)L * chunk) {
         const uint32_t c2 = (uint32_t)(((n + L - 1) / L + 511) / 512 * 512);
-        if (c2 >= default_chunk(u.p->d) / 2 && c2 < chunk) chunk = c2;       // (simple_mul: 2048; T = 60: 512)
+        if (c2 >= default_chunk(wslayout::shape_of(u.p->d, false)) / 2 && c2 < chunk) chunk = c2;       // (simple_mul: 2048; T = 60: 512)
     }
     const uint32_t nch = n_chunks(n, chunk);
     CallRec &rec = rec_laned(w, u.batch_check() ? h2v_workspace::RLC : u.kind == UnitKind::CHECK ? h2v_workspace::CHECK : u.kind == UnitKind::PREPARE ? h2v_workspace::PREPARE : h2v_workspace::VERIFY,
@@ -1650,6 +1639,7 @@ static int run_laned(Unit u, h2v_workspace *w, hipStream_t st, Join join) {
 // depend on it (a proof's verdict depends on its own bytes; tests/test_gpu_parity.py::test_small_calls_are_coalesced).
 // H2V_OPT_COALESCE = -1 on the workspace switches it off.
 struct Coalesce {
+    Owner mem;
     uint8_t *proofs = nullptr, *inst = nullptr, *ci = nullptr, *accept = nullptr;
     // one allocation: the group's verdict word (RLC: failed batch checks; 8 bytes) and behind it off[0 .. cap], so that the one
     // memset that opens a group zeroes both
@@ -1669,8 +1659,7 @@ struct Coalesce {
 static void co_release(h2v_workspace *w) {
     for (auto &c : w->co) {
         if (!c) continue;
-        void *ptrs[] = {c->proofs, c->inst, c->ci, c->accept, c->fail, c->status};
-        for (void *q : ptrs) if (q) (void)hipFree(q);
+        c->mem.release();
         delete c;
         c = nullptr;
     }
@@ -1681,16 +1670,15 @@ static int co_ensure(h2v_workspace *w, uint32_t l, const h2v_plan *p) {
     if (!w->co[l]) w->co[l] = new Coalesce();
     Coalesce &c = *w->co[l];
     const uint32_t cap = w->chunk;
-    const size_t need_p = (size_t)cap * p->d.proof_len + 64, need_i = (size_t)cap * (p->d.n_pi ? p->d.n_pi : 1) * 32;
+    const size_t need_p = wslayout::co_proof_bytes(cap, p->d.proof_len), need_i = wslayout::co_inst_bytes(cap, p->d.n_pi);
     if (c.cap == cap && c.cap_proof_bytes >= need_p && c.cap_inst >= need_i) return H2V_OK;
     HIPCHK(hipStreamSynchronize(w->lane_st[l]));              // (an earlier group may still be running out of the old buffers)
-    void *ptrs[] = {c.proofs, c.inst, c.ci, c.accept, c.fail, c.status};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    c.proofs = c.inst = c.ci = c.accept = nullptr; c.fail = nullptr; c.off = nullptr; c.status = nullptr; c.cap = 0;
+    c.mem.release();
+    c.off = nullptr; c.cap = 0;
     const size_t bp = need_p > c.cap_proof_bytes ? need_p : c.cap_proof_bytes, bi = need_i > c.cap_inst ? need_i : c.cap_inst;
-    bool ok = hipMalloc((void **)&c.proofs, bp) == hipSuccess && hipMalloc((void **)&c.inst, bi) == hipSuccess &&
-              hipMalloc((void **)&c.ci, (size_t)cap * 48) == hipSuccess && hipMalloc((void **)&c.accept, cap) == hipSuccess &&
-              hipMalloc((void **)&c.fail, ((size_t)cap + 2) * 8) == hipSuccess && hipMalloc((void **)&c.status, (size_t)cap * 4) == hipSuccess;
+    const auto T = wslayout::coalesce(cap, bp, bi);
+    const bool ok = c.mem.alloc(c.proofs, T.row[wslayout::C_PROOFS]) && c.mem.alloc(c.inst, T.row[wslayout::C_INST]) && c.mem.alloc(c.ci, T.row[wslayout::C_CI]) &&
+                    c.mem.alloc(c.accept, T.row[wslayout::C_ACCEPT]) && c.mem.alloc(c.fail, T.row[wslayout::C_FAIL]) && c.mem.alloc(c.status, T.row[wslayout::C_STATUS]);
     if (!ok) return fail(H2V_E_DEVICE, "hipMalloc(coalescing buffers) failed");
     c.off = (uint64_t *)c.fail + 1;
     c.cap = cap; c.cap_proof_bytes = bp; c.cap_inst = bi;
@@ -1857,7 +1845,7 @@ struct TmpWs {
     ~TmpWs() { if (ws) h2v_workspace_free(ws); }
     int make(const h2v_plan *p, uint64_t n, h2v_workspace *&ws_io) {
         if (ws_io) return H2V_OK;
-        if (int rc = ws_create_for(p->d, p->device, n, false, &ws)) return rc;
+        if (int rc = ws_create_for(wslayout::shape_of(p->d, false), p->device, n, &ws)) return rc;
         ws_io = ws;
         return H2V_OK;
     }
@@ -1915,11 +1903,11 @@ extern "C" int h2v_workspace_tune(const h2v_plan *p, const h2v_batch *b, h2v_wor
     const uint32_t depth = !laned ? 1u : co ? (ws->chunk / n) * laned_depth(ws, ws->chunk, false, nullptr) : laned_depth(ws, n, false, nullptr);   // (co: a group on every lane)
     const uint32_t m = laned && n > ws->chunk ? ws->chunk : co ? ws->chunk / n * n : n;         // proofs per launch
     const double S = msm_n_simd();
+    Owner tmp;                                // of the three below
     uint8_t *acc_tmp = nullptr;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipMalloc((void **)&acc_tmp, n) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) {
-        if (acc_tmp) (void)hipFree(acc_tmp);
-        if (e0) (void)hipEventDestroy(e0);
+    if (!tmp.alloc(acc_tmp, n) || !tmp.event(e0, hipEventDefault) || !tmp.event(e1, hipEventDefault)) {
+        tmp.release();
         return fail(H2V_E_DEVICE, "tuning: allocation failed");
     }
     const bool saved_defer = ws->defer_joins;
@@ -1995,8 +1983,7 @@ extern "C" int h2v_workspace_tune(const h2v_plan *p, const h2v_batch *b, h2v_wor
     ws->defer_joins = saved_defer;
     if (rc == H2V_OK) set2(best_pair, best_tpl); else set2(saved_pair, saved_tpl);
     (void)hipStreamSynchronize(st);
-    (void)hipFree(acc_tmp);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    tmp.release();
     if (rc == H2V_OK && rep) {
         memset(rep, 0, sizeof *rep);
         rep->n_measured = n_meas; rep->default_ms = def_ms; rep->best_ms = best_ms; rep->calls_in_flight = depth;
@@ -2129,8 +2116,8 @@ static int stage_batch(const h2v_batch *b, size_t inst_bytes, size_t ci_bytes, h
     if (int rc = host_stream(ws)) return rc;
     const hostcall::InputBlock L = hostcall::input_block(n, inst_bytes, ci_bytes, b->proof_off[n] - b->proof_off[0]);
     auto quiet = [&]() { return ws->n_lanes && !m ? (int)H2V_OK : host_quiet(ws, m); };
-    if (int rc = sl.in_block.ensure(L.need, "the staging block", quiet)) return rc;
-    if (int rc = sl.h_block.ensure(L.need, "the staging block", quiet)) return rc;
+    if (int rc = sl.in_block.ensure(sl.mem, L.need, "the staging block", quiet)) return rc;
+    if (int rc = sl.h_block.ensure(sl.mem, L.need, "the staging block", quiet)) return rc;
     hostcall::pack_input(sl.h_block.p, L, n, b->proof_off, b->proofs, b->instances, b->committed);
     HIPCHK(hipMemcpyAsync(sl.in_block.p, sl.h_block.p, L.need, hipMemcpyHostToDevice, ws->hs));
     *in = {n, sl.in_block.p + L.proofs, (const uint64_t *)(sl.in_block.p + L.offsets), sl.in_block.p + L.inst, sl.in_block.p + L.ci};
@@ -2147,9 +2134,9 @@ static int stage_batch(const h2v_plan *p, const h2v_batch *b, h2v_workspace *ws,
 // batch staged and u pointed at the device copy.
 static int stage_unit(Unit &u, const h2v_batch *b, h2v_workspace *ws, HostSlot &sl) {
     const size_t need = hostcall::accept_extent(b->n);
-    if (int rc = sl.h_accept.ensure(need, "the download block", no_wait)) return rc;
+    if (int rc = sl.h_accept.ensure(sl.mem, need, "the download block", no_wait)) return rc;
     if (ws->n_lanes)
-        if (int rc = sl.d_accept.ensure(need, "the download block", no_wait)) return rc;
+        if (int rc = sl.d_accept.ensure(sl.mem, need, "the download block", no_wait)) return rc;
     h2v_batch in;
     if (int rc = stage_batch(u.p, b, ws, sl, &in)) return rc;
     u.proofs = in.proofs; u.off = in.proof_off; u.inst = in.instances; u.ci = in.committed;
@@ -2187,7 +2174,7 @@ static int host_call_tail(h2v_workspace *ws, int rc, std::initializer_list<Down>
 static int result_ensure(h2v_workspace *ws, hostcall::Call kind, uint64_t n, hostcall::ResultBlock *R, MixedWs *m = nullptr) {
     if (int rc = host_stream(ws)) return rc;
     *R = hostcall::result_block(kind, n);
-    return ws->res.ensure(R->extent, "the result block", [&]() { return host_quiet(ws, m); });
+    return ws->res.ensure(ws->mem, R->extent, "the result block", [&]() { return host_quiet(ws, m); });
 }
 static bool rlc_supported(const h2v_plan *p);
 static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o);
@@ -2205,7 +2192,7 @@ static int submit_laned(Unit u, const h2v_batch *b, h2v_workspace *ws) {
         return fail(H2V_E_ARG, "as many batches in flight as this workspace has lanes: call h2v_verify_batch_wait first");
     if (!ws->hs_down) HIPCHK(make_stream(&ws->hs_down));
     h2v_workspace::HostSlot &sl = ws->hslot[ws->h_head % h2v_workspace::MAXH];
-    if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    if (int rce = lazy_event(sl.mem, sl.ev, hipEventDisableTiming)) return rce;
     const uint64_t n = b->n;
     sl.n = n; sl.rlc = u.batch_check();
     if (n) {
@@ -2270,7 +2257,7 @@ extern "C" int h2v_verify_batch_submit(const h2v_plan *p, const h2v_batch *b, h2
         return submit_laned(u, b, ws);
     }
     h2v_workspace::HostSlot &sl = ws->hslot[0];
-    if (!sl.ev) HIPCHK(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+    if (int rce = lazy_event(sl.mem, sl.ev, hipEventDisableTiming)) return rce;
     sl.n = b->n;
     sl.rlc = false;
     if (b->n) {
@@ -2410,24 +2397,21 @@ extern "C" int h2v_check_pairs(const h2v_plan *p, uint64_t n, const uint8_t *pai
 // ---------------------------------------------------------------------------------------------- bucket MSM (Pippenger)
 // Device buffers of one bucket MSM over at most cap_n terms (h2v_pippenger.hpp).
 struct PipWs {
+    Owner mem;
     uint32_t cap_n = 0, cap_halves = 0;
     uint32_t *pts28 = nullptr, *cnt = nullptr, *off = nullptr, *order = nullptr, *cls = nullptr, *list = nullptr, *partial = nullptr, *wsum = nullptr;
     int16_t *dig = nullptr;
 };
 static void pip_free(PipWs &w) {
-    void *ptrs[] = {w.pts28, w.cnt, w.off, w.order, w.cls, w.list, w.partial, w.wsum, w.dig};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
+    w.mem.release();
     w = PipWs();
 }
 static int pip_alloc(PipWs &w, uint32_t cap_n, uint32_t halves) {
-    const size_t nbmax = (size_t)PIP_MAX_W * (1u << (PIP_MAX_C - 1));
-    const size_t ent = (size_t)cap_n * halves * PIP_MAX_W;
+    const auto T = wslayout::bucket_msm(cap_n, halves);
     w.cap_n = cap_n; w.cap_halves = halves;
-    bool ok = hipMalloc((void **)&w.pts28, (size_t)(cap_n ? cap_n : 1) * PIP_PT_DW * 4) == hipSuccess &&
-              hipMalloc((void **)&w.dig, (ent ? ent : 1) * 2) == hipSuccess && hipMalloc((void **)&w.list, (ent ? ent : 1) * 4) == hipSuccess &&
-              hipMalloc((void **)&w.cnt, nbmax * 4) == hipSuccess && hipMalloc((void **)&w.off, (nbmax + 1) * 4) == hipSuccess &&
-              hipMalloc((void **)&w.order, nbmax * 4) == hipSuccess && hipMalloc((void **)&w.cls, PIP_CLS_DW * 4) == hipSuccess && hipMalloc((void **)&w.partial, nbmax * PIP_PART_DW * 4) == hipSuccess &&
-              hipMalloc((void **)&w.wsum, (size_t)PIP_MAX_W * PIP_PART_DW * 4) == hipSuccess;
+    const bool ok = w.mem.alloc(w.pts28, T.row[wslayout::B_PTS28]) && w.mem.alloc(w.dig, T.row[wslayout::B_DIG]) && w.mem.alloc(w.list, T.row[wslayout::B_LIST]) &&
+                    w.mem.alloc(w.cnt, T.row[wslayout::B_CNT]) && w.mem.alloc(w.off, T.row[wslayout::B_OFF]) && w.mem.alloc(w.order, T.row[wslayout::B_ORDER]) &&
+                    w.mem.alloc(w.cls, T.row[wslayout::B_CLS]) && w.mem.alloc(w.partial, T.row[wslayout::B_PARTIAL]) && w.mem.alloc(w.wsum, T.row[wslayout::B_WSUM]);
     if (!ok) { pip_free(w); return fail(H2V_E_DEVICE, "hipMalloc(bucket MSM workspace) failed"); }
     return H2V_OK;
 }
@@ -2491,6 +2475,7 @@ static int pip_launch(const PipWs *const *ws, PipArgs *a, uint32_t np, hipStream
 
 // ---------------------------------------------------------------------------------------------- RLC batch mode
 struct RlcWs {
+    Owner mem;                  // of the set's own blocks; the bucket-MSM sets R and L and the group stage own theirs
     uint64_t cap = 0;
     uint32_t n_var = 0, n_fix = 0;
     uint32_t *r_scal = nullptr, *r_idx = nullptr, *l_scal = nullptr, *l_idx = nullptr, *vk_part = nullptr;
@@ -2500,44 +2485,41 @@ struct RlcWs {
     uint32_t *sums = nullptr;   // er (36 dwords) then el (36): the two MSM results
     uint32_t *misc = nullptr;   // [0..23] a dummy affine point, [24] status of the batch check, [26] its valid byte, [27] its accept byte
     uint32_t *flags = nullptr;  // [0] the batch check passed, [1 + g] group g (proofs 64 g ..) is final: cap / 64 + 2 dwords
+    uint32_t *fold_rpts = nullptr, *fold_lpts = nullptr;   // the fold form of a mixed call: the COPIED points of the terms (24 dwords each)
     // fall-back stage 1 (group checks, created by the first call with at least GRP_MIN_N proofs): term lists, sums and
     // verdict buffers of the groups, the argument array of their 2 G bucket MSMs and ONE pool for those MSMs' buffers
     struct Grp {
+        Owner mem;
         uint32_t n = 0, G = 0, stride = 0, max_n = 0, acc_blocks = 0;
         uint64_t key_gen = 0;          // the plan (load counter) the cached arguments were built for
         const uint32_t *key_pts = nullptr;
         uint32_t cap_stride = 0;
-        std::vector<void *> staged;    // pinned host copies of argument arrays whose uploads may still be in flight
+        void *staged[8] = {};          // pinned host copies of argument arrays whose uploads may still be in flight
+        uint32_t n_staged = 0;
         uint32_t *g_scal = nullptr, *g_idx = nullptr, *er_g = nullptr, *el_g = nullptr, *pts_g = nullptr, *status_g = nullptr;
         uint8_t *valid_g = nullptr, *accept_g = nullptr, *pool = nullptr;
         PipArgs *args_d = nullptr;
-        size_t cnt_bytes = 0, pool_bytes = 0;
+        size_t cnt_bytes = 0;
         uint32_t cap_G = 0;
     } grp;
 };
-static void rlc_release(RlcWs *r) {
-    if (r->l_scal == r->r_scal) r->l_scal = nullptr;      // (the pair-RLC set: one scalar array for both sums)
-    void *ptrs[] = {r->pool, r->r_scal, r->r_idx, r->l_scal, r->l_idx, r->vk_part, r->good, r->sums, r->misc, r->flags, r->grp.g_scal, r->grp.g_idx, r->grp.er_g,
-                    r->grp.el_g, r->grp.pts_g, r->grp.status_g, r->grp.valid_g, r->grp.accept_g, r->grp.pool, r->grp.args_d};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
-    for (void *q : r->grp.staged) (void)hipHostFree(q);   // (the caller has drained the streams: ws_release)
+static void rlc_release(RlcWs *r) {      // (the caller has drained the streams: ws_release, or waited for the set's users)
+    r->mem.release(); r->grp.mem.release();
     pip_free(r->R); pip_free(r->L);
     delete r;
 }
-// n_fix == 0 (pairs): 128-bit scalars on both sides and no left-hand array of its own (l_scal = r_scal)
-static RlcWs *rlc_new(uint64_t cap, uint32_t n_var, uint32_t n_fix) {
+// THE allocator of an RlcWs, in the set's three shapes (h2v_ws_layout.hpp: rlc_plan, rlc_pairs, rlc_fold).  Pairs have 128-bit
+// scalars on both sides and no left-hand array of their own (l_scal = r_scal).
+static RlcWs *rlc_new(uint64_t cap, uint32_t n_var, uint32_t n_fix, const wslayout::RlcSet &S) {
     RlcWs *r = new RlcWs();
     r->cap = cap; r->n_var = n_var; r->n_fix = n_fix;
-    const bool pairs = n_fix == 0;
-    const size_t nr = (size_t)cap * n_var + n_fix, blocks = (cap + 63) / 64;
-    bool ok = hipMalloc((void **)&r->r_scal, nr * 32) == hipSuccess && hipMalloc((void **)&r->r_idx, nr * 4) == hipSuccess &&
-              (pairs || hipMalloc((void **)&r->l_scal, (size_t)cap * 32) == hipSuccess) && hipMalloc((void **)&r->l_idx, (size_t)cap * 4) == hipSuccess &&
-              hipMalloc((void **)&r->vk_part, blocks * (n_fix ? n_fix : 1) * 32) == hipSuccess && hipMalloc((void **)&r->good, cap) == hipSuccess &&
-              hipMalloc((void **)&r->sums, 72 * 4) == hipSuccess && hipMalloc((void **)&r->misc, 32 * 4) == hipSuccess &&
-              hipMemset(r->misc, 0, 32 * 4) == hipSuccess && hipMalloc((void **)&r->flags, (blocks + 2) * 4) == hipSuccess &&
-              hipMemset(r->flags, 0, (blocks + 2) * 4) == hipSuccess;
-    if (ok && pairs) r->l_scal = r->r_scal;
-    if (ok) ok = pip_alloc(r->R, (uint32_t)nr, pairs ? 1 : 2) == H2V_OK && pip_alloc(r->L, (uint32_t)cap, 1) == H2V_OK;
+    const auto &T = S.t;
+    bool ok = r->mem.alloc(r->r_scal, T.row[wslayout::R_R_SCAL]) && r->mem.alloc(r->r_idx, T.row[wslayout::R_R_IDX]) && r->mem.alloc(r->l_scal, T.row[wslayout::R_L_SCAL]) &&
+              r->mem.alloc(r->l_idx, T.row[wslayout::R_L_IDX]) && r->mem.alloc(r->vk_part, T.row[wslayout::R_VK_PART]) && r->mem.alloc(r->good, T.row[wslayout::R_GOOD]) &&
+              r->mem.alloc(r->sums, T.row[wslayout::R_SUMS]) && r->mem.alloc(r->misc, T.row[wslayout::R_MISC]) && r->mem.alloc(r->flags, T.row[wslayout::R_FLAGS]) &&
+              r->mem.alloc(r->fold_rpts, T.row[wslayout::R_FOLD_RPTS]) && r->mem.alloc(r->fold_lpts, T.row[wslayout::R_FOLD_LPTS]);
+    if (ok && !r->l_scal) r->l_scal = r->r_scal;
+    if (ok) ok = pip_alloc(r->R, S.r_cap_n, S.r_halves) == H2V_OK && pip_alloc(r->L, S.l_cap_n, 1) == H2V_OK;
     if (!ok) { rlc_release(r); return nullptr; }
     return r;
 }
@@ -2560,7 +2542,7 @@ static int rlc_ensure(h2v_workspace *w, const h2v_plan *p) {
         w->rlc_parked.push_back(w->rlc);
         w->rlc = nullptr;
     }
-    RlcWs *r = rlc_new(w->cap, p->n_var, p->n_fix);
+    RlcWs *r = rlc_new(w->cap, p->n_var, p->n_fix, wslayout::rlc_plan(w->cap, p->n_var, p->n_fix));
     if (!r) return fail(H2V_E_DEVICE, "RLC workspace allocation failed");
     w->rlc = r;
     return H2V_OK;
@@ -2569,8 +2551,8 @@ static int rlc_ensure(h2v_workspace *w, const h2v_plan *p) {
 // the first such call: the shape "one variable term per pair, no VK base" of the same buffers - one scalar array for both sums,
 // the index arrays 2 i / 2 i + 1, good, sums, flags, two bucket-MSM workspaces of 128-bit scalars.  with_pool: the folded pairs' own pool.
 static int pair_rlc_ensure(h2v_workspace *w, bool with_pool) {
-    if (!w->prlc && !(w->prlc = rlc_new(w->cap, 1, 0))) return fail(H2V_E_DEVICE, "pair-RLC workspace allocation failed");
-    if (with_pool && !w->prlc->pool && hipMalloc((void **)&w->prlc->pool, (size_t)w->cap * 48 * 4) != hipSuccess)
+    if (!w->prlc && !(w->prlc = rlc_new(w->cap, 1, 0, wslayout::rlc_pairs(w->cap)))) return fail(H2V_E_DEVICE, "pair-RLC workspace allocation failed");
+    if (with_pool && !w->prlc->pool && !w->prlc->mem.alloc(w->prlc->pool, wslayout::rlc_pair_pool(w->cap)))
         return fail(H2V_E_DEVICE, "pair-RLC workspace allocation failed");
     return H2V_OK;
 }
@@ -2585,7 +2567,7 @@ static bool rlc_supported(const h2v_plan *p) { return !p->d.ivc && p->n_var > 0 
 // what the fall-back waits for, not these sums.)
 #define GRP_MIN_N 256u
 #define GRP_MAX_G 512u
-#define GRP_C 7u
+using wslayout::GRP_C;      // (window bits of the group stage: its pool is laid out in h2v_ws_layout.hpp)
 static bool rlc_groups_on(uint32_t n) {
     return g_opts.v[H2V_OPT_RLC_GROUP_STAGE] >= 0 && n >= GRP_MIN_N && (n + 63) / 64 <= GRP_MAX_G;
 }
@@ -2606,30 +2588,23 @@ static int rlc_groups_ensure(RlcWs *r, const GrpShape &gs, uint32_t n, hipStream
     if (g.n == n && g.key_gen == gs.gen && g.key_pts == gs.pool && g.stride == stride) return H2V_OK;
     if (G > g.cap_G || stride > g.cap_stride) {
         HIPCHK(hipStreamSynchronize(st));     // (the buffers about to be freed may be in use by the previous call)
-        void *old[] = {g.g_scal, g.g_idx, g.er_g, g.el_g, g.pts_g, g.status_g, g.valid_g, g.accept_g, g.pool, g.args_d};
-        for (void *q : old) if (q) (void)hipFree(q);
-        for (void *q : g.staged) (void)hipHostFree(q);
+        g.mem.release();
         g = RlcWs::Grp();
-        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-        const size_t per_r = up((size_t)stride * PIP_PT_DW * 4) + up((size_t)stride * 2 * W * 2) + up((size_t)stride * 2 * W * 4),
-                     per_l = up((size_t)64 * PIP_PT_DW * 4) + up((size_t)64 * W * 2) + up((size_t)64 * W * 4),
-                     per_any = up((size_t)(nb + 1) * 4) + up((size_t)nb * 4) + up(PIP_CLS_DW * 4) + up((size_t)nb * PIP_PART_DW * 4) + up((size_t)W * PIP_PART_DW * 4);
-        g.cnt_bytes = (size_t)2 * G * up((size_t)nb * 4);
-        g.pool_bytes = g.cnt_bytes + (size_t)G * (per_r + per_l + 2 * per_any);
-        bool ok = hipMalloc((void **)&g.g_scal, (size_t)G * stride * 32) == hipSuccess && hipMalloc((void **)&g.g_idx, (size_t)G * stride * 4) == hipSuccess &&
-                  hipMalloc((void **)&g.er_g, (size_t)G * 144) == hipSuccess && hipMalloc((void **)&g.el_g, (size_t)G * 144) == hipSuccess &&
-                  hipMalloc((void **)&g.pts_g, (size_t)G * 96) == hipSuccess && hipMemset(g.pts_g, 0, (size_t)G * 96) == hipSuccess &&
-                  hipMalloc((void **)&g.status_g, (size_t)G * 4) == hipSuccess && hipMalloc((void **)&g.valid_g, G) == hipSuccess &&
-                  hipMemset(g.valid_g, 1, G) == hipSuccess && hipMalloc((void **)&g.accept_g, G) == hipSuccess &&
-                  hipMalloc((void **)&g.pool, g.pool_bytes) == hipSuccess && hipMalloc((void **)&g.args_d, (size_t)2 * G * sizeof(PipArgs)) == hipSuccess;
+        const auto T = wslayout::group_stage(G, stride);
+        const bool ok = g.mem.alloc(g.g_scal, T.row[wslayout::G_SCAL]) && g.mem.alloc(g.g_idx, T.row[wslayout::G_IDX]) && g.mem.alloc(g.er_g, T.row[wslayout::G_ER]) &&
+                        g.mem.alloc(g.el_g, T.row[wslayout::G_EL]) && g.mem.alloc(g.pts_g, T.row[wslayout::G_PTS]) && g.mem.alloc(g.status_g, T.row[wslayout::G_STATUS]) &&
+                        g.mem.alloc(g.valid_g, T.row[wslayout::G_VALID]) && g.mem.alloc(g.accept_g, T.row[wslayout::G_ACCEPT]) && g.mem.alloc(g.pool, T.row[wslayout::G_POOL]) &&
+                        g.mem.alloc(g.args_d, T.row[wslayout::G_ARGS]);
         if (!ok) return fail(H2V_E_DEVICE, "hipMalloc(RLC group stage) failed");
         g.cap_G = G; g.cap_stride = stride;
     }
-    // the argument array: problem 2 q = the right-hand sum of group q, 2 q + 1 its left-hand sum
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    // the argument array: problem 2 q = the right-hand sum of group q, 2 q + 1 its left-hand sum; their buffers lie in the pool
+    // where wslayout::group_pool says.  The pool was sized by the same function for cap_G groups of cap_stride terms in two halves,
+    // the counters of all cap_G groups come first, and a region only shrinks with the stride and the halves: groups q < G <= cap_G
+    // of this call's stride end inside it (tests/cpp/h2v_ws_layout.cpp binds every region of a pool of exactly the total)
+    const wslayout::GroupPool lay = wslayout::group_pool(g.cap_G, stride, gs.halves);
+    g.cnt_bytes = lay.cnt_bytes;
     std::vector<PipArgs> args(2 * (size_t)G);
-    uint8_t *cur = g.pool + g.cnt_bytes;
-    auto take = [&](size_t bytes) { uint8_t *q = cur; cur += up(bytes); return q; };
     uint32_t max_n = 0, acc_blocks = 1;
     for (uint32_t q = 0; q < G; q++) {
         const uint32_t ng = n - q * 64 < 64 ? n - q * 64 : 64;
@@ -2644,16 +2619,10 @@ static int rlc_groups_ensure(RlcWs *r, const GrpShape &gs, uint32_t n, hipStream
                 a.n = ng; a.halves = 1;
                 a.scal = r->l_scal + (size_t)q * 64 * 8; a.pidx = r->l_idx + (size_t)q * 64; a.pool1 = nullptr; a.out = g.el_g + (size_t)q * 36;
             }
-            const uint32_t cap_n = side == 0 ? stride : 64;
-            a.cnt = (uint32_t *)(g.pool + (size_t)(2 * q + side) * up((size_t)nb * 4));
-            a.pts28 = (uint32_t *)take((size_t)cap_n * PIP_PT_DW * 4);
-            a.dig = (int16_t *)take((size_t)cap_n * a.halves * W * 2);
-            a.list = (uint32_t *)take((size_t)cap_n * a.halves * W * 4);
-            a.off = (uint32_t *)take((size_t)(nb + 1) * 4);
-            a.order = (uint32_t *)take((size_t)nb * 4);
-            a.cls = (uint32_t *)take(PIP_CLS_DW * 4);
-            a.partial = (uint32_t *)take((size_t)nb * PIP_PART_DW * 4);
-            a.wsum = (uint32_t *)take((size_t)W * PIP_PART_DW * 4);
+            const wslayout::GroupPool::At at = lay.at(q, side);
+            a.cnt = (uint32_t *)(g.pool + at.cnt); a.pts28 = (uint32_t *)(g.pool + at.pts28); a.dig = (int16_t *)(g.pool + at.dig);
+            a.list = (uint32_t *)(g.pool + at.list); a.off = (uint32_t *)(g.pool + at.off); a.order = (uint32_t *)(g.pool + at.order);
+            a.cls = (uint32_t *)(g.pool + at.cls); a.partial = (uint32_t *)(g.pool + at.partial); a.wsum = (uint32_t *)(g.pool + at.wsum);
             args[2 * q + side] = a;
             max_n = a.n > max_n ? a.n : max_n;
             const uint64_t lanes = 2ull * a.n * a.halves * W / a.chain + nb + 256ull * PIP_N_CLASSES;
@@ -2661,15 +2630,14 @@ static int rlc_groups_ensure(RlcWs *r, const GrpShape &gs, uint32_t n, hipStream
             acc_blocks = blocks > acc_blocks ? blocks : acc_blocks;
         }
     }
-    if ((size_t)(cur - g.pool) > g.pool_bytes) return fail(H2V_E_DEVICE, "RLC group pool overrun");
-    if (g.staged.size() >= 8) {               // (a workspace whose batch size keeps alternating: drain, then reuse)
+    if (g.n_staged >= 8) {                    // (a workspace whose batch size keeps alternating: drain, then reuse)
         HIPCHK(hipStreamSynchronize(st));
-        for (void *q : g.staged) (void)hipHostFree(q);
-        g.staged.clear();
+        for (void *&q : g.staged) g.mem.drop(q);
+        g.n_staged = 0;
     }
-    void *pinned = nullptr;
-    if (hipHostMalloc(&pinned, args.size() * sizeof(PipArgs), hipHostMallocDefault) != hipSuccess) return fail(H2V_E_DEVICE, "staging allocation failed");
-    g.staged.push_back(pinned);
+    void *&pinned = g.staged[g.n_staged];
+    if (!g.mem.alloc_pinned(pinned, wslayout::group_args_bytes(G))) return fail(H2V_E_DEVICE, "staging allocation failed");
+    g.n_staged++;
     memcpy(pinned, args.data(), args.size() * sizeof(PipArgs));
     HIPCHK(hipMemcpyAsync(g.args_d, pinned, args.size() * sizeof(PipArgs), hipMemcpyHostToDevice, st));   // behind the earlier call's kernels
     g.n = n; g.G = G; g.stride = stride; g.max_n = max_n; g.acc_blocks = acc_blocks; g.key_gen = gs.gen; g.key_pts = gs.pool;
@@ -2829,7 +2797,7 @@ static int run_rlc(const Unit &u, h2v_workspace *w, hipStream_t st) {
     {
         H2vMsmArgs ma = msm_args(d, 0, d.n_main_terms, d.n_terms, 0, slots, w->er, w->pt_tab);
         ma.skip = skip;
-        if (!launch_msm_range(d, ma, n, w->scalars, w->pts, nullptr, pm, 1, SegBuf{w->msm_parts, w->sz_segs}))
+        if (!launch_msm_range(d, ma, n, w->scalars, w->pts, nullptr, pm, 1, SegBuf{w->msm_parts, w->shape.segs}))
             return fail(H2V_E_LIMIT, "internal: no MSM launch shape for this plan");
     }
     launch_pairing(d, n, w->pts, w->valid, w->valid_sub, w->er, nullptr, w->status, u.accept, nullptr, pm, w->in_flight_hint, skip);
@@ -2973,16 +2941,16 @@ static int seed_launch(const SeedJob &j, hipStream_t st) {
 static int seed_enqueue(Unit &u, h2v_workspace *ws, hipStream_t st) {
     constexpr uint32_t RING = h2v_workspace::RING;
     if (!ws->seed_ring) {
-        if (hipMalloc((void **)&ws->seed_ring, RING * 32) != hipSuccess) { ws->seed_ring = nullptr; return fail(H2V_E_DEVICE, "allocation of the seed ring failed"); }
+        if (!ws->mem.alloc(ws->seed_ring, wslayout::seed_ring_bytes())) return fail(H2V_E_DEVICE, "allocation of the seed ring failed");
     }
     h2vseed::Tree t;
     if (!h2vseed::tree(u.n, &t)) return fail(H2V_E_LIMIT, "derived seeds are limited to 2^22 proofs");
-    if (int rc = ws->seed_digests.ensure((size_t)t.extent * 32, "the seed digests", [&]() -> int {
+    if (int rc = ws->seed_digests.ensure(ws->mem, (size_t)t.extent * 32, "the seed digests", [&]() -> int {
             if (ws->ev_seed_last) HIPCHK(hipEventSynchronize(ws->ev_seed_last));
             return H2V_OK;
         })) return rc;
     const uint32_t slot = (uint32_t)(ws->calls % RING);
-    for (hipEvent_t &e : ws->ev_seed[slot]) if (!e) HIPCHK(hipEventCreate(&e));
+    for (hipEvent_t &e : ws->ev_seed[slot]) if (int rce = lazy_event(ws->mem, e, hipEventDefault)) return rce;
     if (ws->ev_seed_last) HIPCHK(hipStreamWaitEvent(st, ws->ev_seed_last, 0));
     HIPCHK(hipEventRecord(ws->ev_seed[slot][0], st));
     const bool pairs = u.kind == UnitKind::PAIR_RLC;
@@ -3095,7 +3063,8 @@ extern "C" int h2v_check_pairs_rlc(const h2v_plan *p, uint64_t n, const uint8_t 
 // and a block is reused only when the call that took it last has finished on the device.
 struct MixedWs {
     static constexpr int SLOTS = 4;
-    struct Slot { uint8_t *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; } slot[SLOTS];
+    struct Slot { Owner mem; uint8_t *h = nullptr, *d = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool used = false; } slot[SLOTS];
+    Owner mem;                            // of the base buffers and the grouped staging (the slots, `in` and `fold` own theirs)
     uint64_t next = 0;
     int last = -1;                        // the slot of the most recent call: the next one starts behind its end, whatever its stream
     GrowBuf<false> proofs, inst, ci;                                 // grouped staging, grown on demand behind mixed_quiesce
@@ -3107,7 +3076,7 @@ struct MixedWs {
     // H2V_MIXED_FOLD_MSM, allocated by the first fold call and grown behind mixed_quiesce: the call-level term pool - `fold` holds
     // the scalars of the R-terms (r_scal, fold_cap_terms records) and of the L-terms (l_scal, by call position), the per-block
     // sums of the VK-base scalars (vk_part, fold_cap_parts Fr records), good, the two bucket-MSM workspaces and the sums / misc /
-    // flags set of the one pairing; fold_rpts / fold_lpts are the COPIED points of the terms (24 dwords each)
+    // flags set of the one pairing; fold_rpts / fold_lpts are the COPIED points of the terms (24 dwords each; fold's own blocks)
     struct RlcWs *fold = nullptr;
     uint32_t *fold_rpts = nullptr, *fold_lpts = nullptr;
     size_t fold_cap_terms = 0, fold_cap_parts = 0;
@@ -3157,17 +3126,12 @@ struct MixedFold {
 static void mixed_release(h2v_workspace *w) {
     MixedWs *m = w->mixed;
     if (!m) return;
-    for (auto &s : m->slot) {
+    for (auto &s : m->slot)
         if (s.used && s.done) (void)hipEventSynchronize(s.done);
-        if (s.h) (void)hipHostFree(s.h);
-        if (s.d) (void)hipFree(s.d);
-        if (s.done) (void)hipEventDestroy(s.done);
-    }
+    for (auto &s : m->slot) s.mem.release();
     slot_release(m->in);
-    m->proofs.release(); m->inst.release(); m->ci.release();
     if (m->fold) rlc_release(m->fold);
-    void *ptrs[] = {m->pool, m->status, m->good, m->ones, m->fold_rpts, m->fold_lpts};
-    for (void *q : ptrs) if (q) (void)hipFree(q);
+    m->mem.release();
     delete m;
     w->mixed = nullptr;
 }
@@ -3181,18 +3145,17 @@ static int mixed_ensure(h2v_workspace *w, const h2vmixed::Partition &pt) {
     if (!w->mixed) {
         MixedWs *m = new MixedWs();
         w->mixed = m;
-        const size_t cap = (size_t)w->cap;
-        bool ok = hipMalloc((void **)&m->pool, cap * 48 * 4) == hipSuccess && hipMalloc((void **)&m->status, cap * 4) == hipSuccess &&
-                  hipMalloc((void **)&m->good, cap) == hipSuccess && hipMalloc((void **)&m->ones, cap * 2) == hipSuccess &&
-                  hipMemset(m->ones, 1, cap * 2) == hipSuccess;
-        for (auto &s : m->slot) ok = ok && hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
+        const auto T = wslayout::mixed_base(w->cap);
+        bool ok = m->mem.alloc(m->pool, T.row[wslayout::M_POOL]) && m->mem.alloc(m->status, T.row[wslayout::M_STATUS]) &&
+                  m->mem.alloc(m->good, T.row[wslayout::M_GOOD]) && m->mem.alloc(m->ones, T.row[wslayout::M_ONES]);
+        for (auto &s : m->slot) ok = ok && s.mem.event(s.done, hipEventDisableTiming);
         if (!ok) { mixed_release(w); return fail(H2V_E_DEVICE, "allocation of the mixed-call buffers failed"); }
     }
     MixedWs *m = w->mixed;
     auto quiet = [m]() { return mixed_quiesce(m); };
-    if (int rc = m->proofs.ensure((size_t)pt.proof_cap + 64, "the mixed-call staging", quiet)) return rc;
-    if (int rc = m->inst.ensure((size_t)pt.inst_total + 64, "the mixed-call staging", quiet)) return rc;
-    return m->ci.ensure((size_t)pt.ci_total * 48 + 64, "the mixed-call staging", quiet);
+    if (int rc = m->proofs.ensure(m->mem, (size_t)pt.proof_cap + 64, "the mixed-call staging", quiet)) return rc;
+    if (int rc = m->inst.ensure(m->mem, (size_t)pt.inst_total + 64, "the mixed-call staging", quiet)) return rc;
+    return m->ci.ensure(m->mem, (size_t)pt.ci_total * 48 + 64, "the mixed-call staging", quiet);
 }
 // The term pool of the fold form for a call of this layout (the first fold call allocates, a larger one grows it once every
 // earlier mixed call has finished on the device).
@@ -3202,27 +3165,13 @@ static int mixed_fold_ensure(h2v_workspace *w, const h2vmixed::FoldLayout &lay) 
     if (m->fold && need_t <= m->fold_cap_terms && need_p <= m->fold_cap_parts) return H2V_OK;
     if (int rc = mixed_quiesce(m)) return rc;
     if (m->fold) { rlc_release(m->fold); m->fold = nullptr; }
-    for (uint32_t **q : {&m->fold_rpts, &m->fold_lpts}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-    size_t cap_t = need_t + need_t / 4, cap_p = need_p + need_p / 4 + 1;
-    if (cap_t > H2V_MIXED_FOLD_MAX_TERMS) cap_t = (size_t)H2V_MIXED_FOLD_MAX_TERMS;
-    if (cap_t < m->fold_cap_terms) cap_t = m->fold_cap_terms;
-    if (cap_p < m->fold_cap_parts) cap_p = m->fold_cap_parts;
+    m->fold_rpts = m->fold_lpts = nullptr;
+    const wslayout::FoldCaps caps = wslayout::fold_caps(need_t, need_p, m->fold_cap_terms, m->fold_cap_parts);
+    const size_t cap_t = caps.terms, cap_p = caps.parts;
     m->fold_cap_terms = m->fold_cap_parts = 0; m->fold_ran = false;
-    RlcWs *r = new RlcWs();
-    const size_t cap = (size_t)w->cap, blocks = (cap + 63) / 64;
-    r->cap = cap;
-    bool ok = hipMalloc((void **)&r->r_scal, cap_t * 32) == hipSuccess && hipMalloc((void **)&r->l_scal, cap * 32) == hipSuccess &&
-              hipMalloc((void **)&r->vk_part, cap_p * 32) == hipSuccess && hipMalloc((void **)&r->good, cap) == hipSuccess &&
-              hipMalloc((void **)&r->sums, 72 * 4) == hipSuccess && hipMalloc((void **)&r->misc, 32 * 4) == hipSuccess &&
-              hipMemset(r->misc, 0, 32 * 4) == hipSuccess && hipMalloc((void **)&r->flags, (blocks + 2) * 4) == hipSuccess &&
-              hipMemset(r->flags, 0, (blocks + 2) * 4) == hipSuccess && hipMalloc((void **)&m->fold_rpts, cap_t * 96) == hipSuccess &&
-              hipMalloc((void **)&m->fold_lpts, cap * 96) == hipSuccess;
-    if (ok) ok = pip_alloc(r->R, (uint32_t)cap_t, 2) == H2V_OK && pip_alloc(r->L, (uint32_t)cap, 1) == H2V_OK;
-    if (!ok) {
-        rlc_release(r);
-        for (uint32_t **q : {&m->fold_rpts, &m->fold_lpts}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-        return fail(H2V_E_DEVICE, "allocation of the fold form's term pool failed");
-    }
+    RlcWs *r = rlc_new(w->cap, 0, 0, wslayout::rlc_fold(w->cap, cap_t, cap_p));
+    if (!r) return fail(H2V_E_DEVICE, "allocation of the fold form's term pool failed");
+    m->fold_rpts = r->fold_rpts; m->fold_lpts = r->fold_lpts;
     m->fold = r; m->fold_cap_terms = cap_t; m->fold_cap_parts = cap_p;
     return H2V_OK;
 }
@@ -3276,7 +3225,7 @@ static int run_mixed_group(const Unit &u, h2v_workspace *w, hipStream_t st) {
     if (c >= f.ranges.size() || f.ranges[c].n != u.n || (sp.chunk && u.first % sp.chunk))
         return fail(H2V_E_DEVICE, "internal: a grouped unit is not a range of the call");
     const MixedGroupRange &g = f.ranges[c];
-    if (u.n > w->cap || sp.u_terms > w->sz_terms || sp.u_slots > w->sz_slots)
+    if (u.n > w->cap || sp.u_terms > w->shape.terms || sp.u_slots > w->shape.slots)
         return fail(H2V_E_DEVICE, "internal: a grouped range does not fit the workspace");
     LaunchOptsScope opts(w);
     int rc;
@@ -3396,11 +3345,10 @@ static int mixed_slot(MixedWs *m, size_t need, int *si) {
     MixedWs::Slot &sl = m->slot[*si];
     if (sl.used) { HIPCHK(hipEventSynchronize(sl.done)); sl.used = false; }
     if (need <= sl.cap) return H2V_OK;
-    if (sl.h) (void)hipHostFree(sl.h);
-    if (sl.d) (void)hipFree(sl.d);
-    sl.h = sl.d = nullptr; sl.cap = 0;
-    const size_t cap = need + need / 4;
-    if (hipHostMalloc((void **)&sl.h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void **)&sl.d, cap) != hipSuccess)
+    sl.mem.drop(sl.h); sl.mem.drop(sl.d);
+    sl.cap = 0;
+    const size_t cap = wslayout::grown(need);
+    if (!sl.mem.alloc_pinned(sl.h, cap) || !sl.mem.alloc(sl.d, cap))
         return fail(H2V_E_DEVICE, "allocation of the mixed-call tables failed");
     sl.cap = cap;
     return H2V_OK;
@@ -3782,8 +3730,8 @@ extern "C" int h2v_verify_mixed(const h2v_plan *const *plans, uint32_t n_plans, 
 static int agg_ensure(h2v_workspace *ws, uint32_t n_parts, hipStream_t st, AggSlot *out) {
     constexpr uint32_t S = h2v_workspace::AGG_SLOTS, P = h2v_workspace::AGG_SLOT_PARTS;
     const uint32_t per = n_parts ? n_parts : 1u, need = per <= P ? S * P : per;
-    for (hipEvent_t &e : ws->ev_agg) if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (int rc = ws->agg_parts.ensure((size_t)need * AGG_PART_DW * 4, "the aggregate parts", [&]() -> int {
+    for (hipEvent_t &e : ws->ev_agg) if (int rce = lazy_event(ws->mem, e, hipEventDisableTiming)) return rce;
+    if (int rc = ws->agg_parts.ensure(ws->mem, (size_t)need * AGG_PART_DW * 4, "the aggregate parts", [&]() -> int {
             for (uint32_t q = 0; q < S; q++)
                 if (ws->agg_used[q]) { HIPCHK(hipEventSynchronize(ws->ev_agg[q])); ws->agg_used[q] = false; }
             return H2V_OK;

@@ -31,13 +31,7 @@
 #pragma once
 #include "h2v_curve28.hpp"
 #include "h2v_plan.h"
-
-#define PIP_PT_DW 42          // x, y, beta*x: 3 x 14 limbs per term
-#define PIP_PART_DW 44        // Jacobian partial sum: 42 limbs + infinity flag + pad (16-byte multiple)
-#define PIP_MAX_W 20
-#define PIP_MAX_C 10          // NB = 2^(c-1) <= 512 buckets per window: one block's LDS holds a window's bucket sums
-#define PIP_N_CLASSES 9       // lanes per bucket: 2^0 .. 2^8
-#define PIP_CLS_DW (3 * PIP_N_CLASSES + 1)   // per class: first rank, end rank, first lane; then the lane total
+#include "h2v_pip_sizes.hpp"   // PIP_PT_DW, PIP_PART_DW, PIP_MAX_W, PIP_MAX_C, PIP_N_CLASSES, PIP_CLS_DW
 
 struct PipArgs {
     uint32_t n;               // terms

@@ -6,7 +6,7 @@ extern "C" int h2v_trace(const h2v_plan *p, const uint8_t *proof, size_t proof_l
     ALIVE(p);
     HIPCHK(hipSetDevice(p->device));
     h2v_workspace *ws = nullptr;
-    int rc = ws_create_for(p->d, p->device, 1, true, &ws);
+    int rc = ws_create_for(wslayout::shape_of(p->d, true), p->device, 1, &ws);
     if (rc) return rc;
     uint64_t off[2] = {0, proof_len};
     h2v_batch b = {1, proof, off, instances, committed};
@@ -50,6 +50,15 @@ struct DevBuf {
     int download(void *dst, size_t n) const { return hipMemcpy(dst, p, n, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1; }
     template <class T> T *as() { return (T *)p; }
 };
+// What the library's owners (h2v_capi.hip: Owner) hold on `device` right now: out[0] device blocks, [1] device bytes, [2] pinned
+// host blocks, [3] pinned bytes, [4] events.  Everything a plan or a workspace allocates is counted, the temporary blocks of the
+// probes in this file and the pool streams are not.  Counts only: no device call, and valid after h2v_shutdown.  For tests
+// (tests/test_workspace_memory_gpu.py holds the counts against the size tables of h2v_ws_layout.hpp); not in include/h2v.h.
+extern "C" int h2v_probe_device_memory(int device, uint64_t out[5]) {
+    if (device < 0 || device >= 16 || !out) return fail(H2V_E_ARG, "bad argument");
+    for (int k = 0; k < 5; k++) out[k] = g_mem_live[device][k].load();
+    return H2V_OK;
+}
 static int pick_device(int device) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(H2V_E_DEVICE, "no HIP device: the HIP backend is required (no CPU fallback)");
@@ -357,7 +366,7 @@ extern "C" int h2v_probe_vm(const h2v_plan *p, const h2v_batch *b, int want_trac
     const uint32_t n = (uint32_t)b->n;
     const H2vDevPlan &d = p->d;
     h2v_workspace *ws = nullptr;
-    int rc = ws_create_for(d, p->device, n, want_trace != 0, &ws);
+    int rc = ws_create_for(wslayout::shape_of(d, want_trace != 0), p->device, n, &ws);
     if (rc) return rc;
     h2v_batch in;
     rc = stage_batch(p, b, ws, ws->hslot[0], &in);
@@ -392,7 +401,7 @@ extern "C" int h2v_probe_decompress(const h2v_plan *p, const h2v_batch *b, int w
     const H2vDevPlan &d = p->d;
     const size_t n_pts = (size_t)n * H2V_SLOTS(d);
     h2v_workspace *ws = nullptr;
-    int rc = ws_create_for(d, p->device, n, false, &ws);
+    int rc = ws_create_for(wslayout::shape_of(d, false), p->device, n, &ws);
     if (rc) return rc;
     DevBuf dout;
     h2v_batch in;
