@@ -654,6 +654,13 @@ int h2v_probe_g1_decompress(int device, uint32_t n, const uint8_t *compressed, u
 /* sum_t s_t * B_t per group: n groups of T terms; scalars n*T*32 B LE, bases n*T*48 B compressed; out n*96 B affine BE */
 int h2v_probe_g1_msm(int device, uint32_t n, uint32_t T, const uint8_t *scalars, const uint8_t *bases_compressed,
                      uint8_t *out_xy_be);
+/* The same sums through the multi-term ladder alone (k_g1_msm_multi: several GLV halves per lane on one accumulator, unchecked
+ * additions judged by one Z test at the end, the complete law for a lane that fails it), launched as the pipelines launch it
+ * but with halves_per_lane = 3 .. 8 given by the caller: half 2 t + h of a proof goes to lane (2 t + h) / halves_per_lane.
+ * Arguments as for h2v_probe_g1_msm.  H2V_E_ARG for halves_per_lane outside 3 .. 8 or more than 256 lanes per proof.  Crafted
+ * exceptional additions in every lane shape: tests/test_msm_multi_ladder_gpu.py */
+int h2v_probe_g1_msm_multi(int device, uint32_t n, uint32_t T, uint32_t halves_per_lane, const uint8_t *scalars,
+                           const uint8_t *bases_compressed, uint8_t *out_xy_be);
 /* the fixed-base launch of a split MSM on its own: sum over the plan's n_fix VK-base terms of s_t * B_t through the all-window
  * tables built at h2v_plan_load (k_g1_msm_fixed, bases_per_lane = 1 .. 4 as the launcher would pick); scalars n * n_fix * 32 B
  * LE in the order of the plan's VK-base terms, out n * 96 B affine BE; *n_fix_out (may be NULL) receives n_fix.  H2V_E_ARG for

@@ -116,7 +116,7 @@ EXPORTS = [
     "h2v_workspace_join", "h2v_workspace_lanes", "h2v_workspace_depth", "h2v_workspace_set_option", "h2v_workspace_get_option", "h2v_workspace_tune", "h2v_probe_set_option",
     "h2v_verify_batch", "h2v_verify_batch_submit", "h2v_verify_batch_wait", "h2v_verify_batch_device", "h2v_verify_batch_rlc", "h2v_verify_batch_rlc_device",
     "h2v_workspace_rlc_result", "h2v_probe_g1_msm_pippenger", "h2v_probe_g1_msm_pippenger_ex", "h2v_plan_trace_slots", "h2v_trace", "h2v_probe_vm", "h2v_probe_field",
-    "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_f28_dot2", "h2v_probe_pairing", "h2v_probe_pairing_ex",
+    "h2v_probe_blake2b", "h2v_probe_g1_decompress", "h2v_probe_g1_msm", "h2v_probe_g1_msm_multi", "h2v_probe_g1_msm_fixed", "h2v_probe_quad_madd", "h2v_probe_f28_dot2", "h2v_probe_pairing", "h2v_probe_pairing_ex",
     "h2v_probe_pairing_states",
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
@@ -198,6 +198,7 @@ def lib():
         L.h2v_probe_blake2b.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p]
         L.h2v_probe_g1_decompress.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p]
         L.h2v_probe_g1_msm.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
+        L.h2v_probe_g1_msm_multi.argtypes = [C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
         L.h2v_probe_g1_msm_fixed.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_char_p, C.c_void_p, C.POINTER(C.c_uint32)]
         L.h2v_probe_pairing.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p]
         L.h2v_probe_pairing_ex.argtypes = [C.c_void_p, C.c_uint32, C.c_char_p, C.c_char_p, C.c_void_p, C.c_int, C.c_void_p]
@@ -861,6 +862,18 @@ def probe_g1_msm(scalar_groups, base_groups, device: int = 0):
     bs = b"".join(b for g in base_groups for b in g)
     out = C.create_string_buffer(96 * n)
     check(lib().h2v_probe_g1_msm(device, n, T, sc, bs, out))
+    return [_unxy(out.raw[96 * i:96 * i + 96]) for i in range(n)]
+
+
+def probe_g1_msm_multi(scalar_groups, base_groups, halves_per_lane: int, device: int = 0):
+    """probe_g1_msm's sums through k_g1_msm_multi alone, `halves_per_lane` (3 .. 8) GLV halves per lane."""
+    n = len(scalar_groups)
+    T = len(scalar_groups[0])
+    assert all(len(g) == T for g in scalar_groups) and all(len(g) == T for g in base_groups) and len(base_groups) == n
+    sc = b"".join(int(s).to_bytes(32, "little") for g in scalar_groups for s in g)
+    bs = b"".join(b for g in base_groups for b in g)
+    out = C.create_string_buffer(96 * n)
+    check(lib().h2v_probe_g1_msm_multi(device, n, T, halves_per_lane, sc, bs, out))
     return [_unxy(out.raw[96 * i:96 * i + 96]) for i in range(n)]
 
 

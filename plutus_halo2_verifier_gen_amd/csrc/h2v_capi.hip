@@ -1076,12 +1076,10 @@ static uint32_t launch_msm_range(const H2vDevPlan &d, const H2vMsmArgs &ma, uint
     const bool fills = (double)n * ma.n_terms / 64.0 >= msm_n_simd() / (in_flight_hint >= 8 ? 8.0 : 4.0);
     const bool tpl_forced = m.terms_per_lane > 0;
     if (tpl > 1 && (fills || tpl_forced) && ma.pt_tab && !ma.skip && ma.grp_end[0] == ma.n_terms && ma.n_terms >= (uint32_t)tpl && ma.n_terms <= 256u * tpl) {
-        // lanes per proof as for `tpl` whole terms per lane, then the proof's 2 T GLV halves dealt out evenly over them: ten terms
-        // on four lanes are 5 + 5 + 5 + 5 halves, not 6 + 6 + 6 + 2 (a forced tpl keeps its 2 tpl halves per lane)
-        const uint32_t lpp0 = (ma.n_terms + tpl - 1) / tpl, bs = 256;
-        const uint32_t hpl = tpl_forced ? 2u * (uint32_t)tpl : (2 * ma.n_terms + lpp0 - 1) / lpp0;
-        const uint32_t lpp = (2 * ma.n_terms + hpl - 1) / hpl;
-        const uint32_t per_block = bs / lpp, blocks = (n + per_block - 1) / per_block;
+        // (h2v_msm_shape.hpp: the proof's 2 T GLV halves dealt out evenly over the lanes)
+        const MsmMultiShape ms = msm_multi_shape(ma.n_terms, tpl, tpl_forced);
+        const uint32_t bs = 256, hpl = ms.hpl;
+        const uint32_t per_block = bs / ms.lpp, blocks = (n + per_block - 1) / per_block;
         hipLaunchKernelGGL(k_g1_msm_multi, dim3(blocks), dim3(bs), MSM_LDS_BYTES(bs), st, d, ma, n, per_block, hpl, scalars, pts, tabws);
         return 16 + (hpl + 1) / 2;   // reported as msm_lanes_per_term: 18 / 19 / 20 = up to two / three / four terms' halves per lane
     }

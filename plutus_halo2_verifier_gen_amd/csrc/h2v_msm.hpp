@@ -13,6 +13,7 @@
 // One launch sums a RANGE of a term table (the proof's own MSM; with recursion also acc_left, acc_right + fixed bases,
 // and the two folds el + c*acc_left, er + c*acc_right over the fold's own point / scalar buffers):
 #pragma once
+#include "h2v_msm_shape.hpp"
 struct H2vMsmArgs {
     const uint32_t *terms;     // (kind, index) pairs; kind = VK base or per-proof slot of `pts`
     uint32_t term_base;        // first term of the range
@@ -430,7 +431,7 @@ extern "C" __global__ void __launch_bounds__(512, 2) k_g1_msm_fixed(MSM_ARGS, MS
 // One accumulator over DIFFERENT points has no lattice argument against exceptional additions (crafted proofs can make
 // P_2 = [m] P_1), so the ladder runs unchecked and is judged once at the end: an exceptional addition or doubling leaves
 // Z = 0, which every later Z inherits; such a lane (never an honest one) redoes its ladder with the complete group law.
-#define MSM_MAX_HALVES 8
+// (MSM_MAX_HALVES: h2v_msm_shape.hpp, where host code sees the bound)
 template <bool COMPLETE>
 H2V_DN void msm_multi_ladder(G1J28 &out, bool &out_inf, const int8_t (&dg)[MSM_MAX_HALVES][33], const uint32_t *const (&tab)[MSM_MAX_HALVES], const int H) {
     G1J28 lad;

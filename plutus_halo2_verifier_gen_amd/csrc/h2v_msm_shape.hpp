@@ -123,6 +123,19 @@ static inline int msm_terms_per_lane(const MsmModel &m, uint32_t in_flight_hint,
         if ((double)n * ((n_terms + t - 1) / t) / 64.0 >= m.n_simd / 4.0) return t;
     return 2;
 }
+// The lane shape of the multi-term launch (h2v_msm.hpp: k_g1_msm_multi): halves per lane and lanes per proof for T = n_terms
+// terms at `tpl` terms per lane (msm_terms_per_lane; forced: the option set it).  The launcher admits tpl <= T <= 256 tpl.
+// MSM_MAX_HALVES: the most halves a lane of that kernel carries (its digit and table arrays).
+#define MSM_MAX_HALVES 8
+struct MsmMultiShape { uint32_t hpl, lpp; };
+static inline MsmMultiShape msm_multi_shape(uint32_t n_terms, int tpl, bool tpl_forced) {
+    // lanes per proof as for `tpl` whole terms per lane, then the proof's 2 T GLV halves dealt out evenly over them: ten terms
+    // on four lanes are 5 + 5 + 5 + 5 halves, not 6 + 6 + 6 + 2 (a forced tpl keeps its 2 tpl halves per lane)
+    const uint32_t lpp0 = (n_terms + tpl - 1) / tpl;
+    const uint32_t hpl = tpl_forced ? 2u * (uint32_t)tpl : (2 * n_terms + lpp0 - 1) / lpp0;
+    const uint32_t lpp = (2 * n_terms + hpl - 1) / hpl;
+    return {hpl, lpp};
+}
 // Fixed-base split of the plan's own MSM (non-recursive plans, tables present): the per-proof terms [0, n_var) as ladders
 // and, beside them on another stream, the VK-base terms as one lane per term that walks the all-window table of its base
 // (65 mixed additions, no doubling: 0.88 ms alone).  Measured (2048 proofs): T = 50 with 30 VK bases 3.37 -> 2.52 ms,

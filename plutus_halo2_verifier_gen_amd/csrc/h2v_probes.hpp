@@ -231,6 +231,33 @@ extern "C" int h2v_probe_g1_msm(int device, uint32_t n, uint32_t T, const uint8_
     HIPCHK(hipDeviceSynchronize());
     return dout.download(out_xy_be, (size_t)n * 96) ? fail(H2V_E_DEVICE, "download failed") : (int)H2V_OK;
 }
+// The multi-term ladder (k_g1_msm_multi) with a lane shape of the caller's choosing: h2v_probe_g1_msm's setup, then the launch as
+// launch_msm_range makes it (256-thread blocks, 256 / lpp proofs per block) with `halves_per_lane` halves per lane - the odd
+// shapes included, which the launcher reaches only unforced and in large batches.
+extern "C" int h2v_probe_g1_msm_multi(int device, uint32_t n, uint32_t T, uint32_t halves_per_lane, const uint8_t *scalars, const uint8_t *bases_compressed,
+                                      uint8_t *out_xy_be) {
+    int rc = pick_device(device);
+    if (rc) return rc;
+    if (!scalars || !bases_compressed || !out_xy_be || n == 0 || T == 0) return fail(H2V_E_ARG, "bad argument");
+    if (halves_per_lane < 3 || halves_per_lane > MSM_MAX_HALVES) return fail(H2V_E_ARG, "halves per lane: 3 .. 8");
+    if (T > H2V_MAX_MSM_TERMS) return fail(H2V_E_LIMIT, "more terms than H2V_MAX_MSM_TERMS");
+    const uint32_t bs = 256, lpp = (2 * T + halves_per_lane - 1) / halves_per_lane;
+    if (lpp > bs) return fail(H2V_E_ARG, "more than 256 lanes per proof");
+    MiniPlan mp;
+    DevBuf din, doff, dsc, dpts, dvalid, der, dout, dtab;
+    if (mp.build(T, T, nullptr, nullptr) || upload_offsets(doff, n, 48 * T) || din.upload(bases_compressed, (size_t)n * T * 48) || dsc.upload(scalars, (size_t)n * T * 32) ||
+        dpts.alloc((size_t)n * T * 96) || dvalid.alloc((size_t)n * T) || der.alloc((size_t)n * 144) || dout.alloc((size_t)n * 96))
+        return fail(H2V_E_DEVICE, "probe setup failed");
+    if (dtab.alloc((size_t)n * T * 448 * 4)) return fail(H2V_E_DEVICE, "hipMalloc failed");
+    hipLaunchKernelGGL(k_g1_decompress, dim3((n * T + 63) / 64), dim3(128), 0, nullptr, mp.d, n, din.as<uint8_t>(), doff.as<uint64_t>(), (const uint8_t *)nullptr, (const uint8_t *)nullptr, dpts.as<uint32_t>(), dvalid.as<uint8_t>(), dtab.as<uint32_t>(), 0u, (uint8_t *)nullptr);
+    const H2vMsmArgs ma = msm_args(mp.d, 0, T, T, 0, H2V_SLOTS(mp.d), der.as<uint32_t>(), dtab.as<uint32_t>());
+    const uint32_t per_block = bs / lpp, blocks = (n + per_block - 1) / per_block;
+    hipLaunchKernelGGL(k_g1_msm_multi, dim3(blocks), dim3(bs), MSM_LDS_BYTES(bs), nullptr, mp.d, ma, n, per_block, halves_per_lane, dsc.as<uint32_t>(), dpts.as<uint32_t>(), (uint32_t *)nullptr);
+    hipLaunchKernelGGL(k_export_points, dim3((n + 63) / 64), dim3(64), 0, nullptr, n, 1, der.as<uint32_t>(), dout.as<uint8_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    return dout.download(out_xy_be, (size_t)n * 96) ? fail(H2V_E_DEVICE, "download failed") : (int)H2V_OK;
+}
 
 // the fixed-base launch of a split MSM over the plan's own VK-base terms, scalars given by the caller
 extern "C" int h2v_probe_g1_msm_fixed(const h2v_plan *p, uint32_t n, uint32_t k, const uint8_t *scalars, uint8_t *out_xy_be, uint32_t *n_fix_out) {

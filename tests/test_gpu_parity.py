@@ -1202,7 +1202,9 @@ def test_g1_msm_forced_shape(be, orc, lpt):
     """test_g1_msm (edge scalars, equal / opposite / infinity bases, T = 1 .. 64) again with the MSM shape forced through
     h2v_probe_set_option (in-process): the probe's small batches would otherwise always take two lanes per term.  tpl2 / tpl4:
     several terms per lane on one accumulator (k_g1_msm_multi*), where equal and opposite bases exercise the Z test and the
-    complete redo."""
+    complete redo - but only in windows 32 and 31, on the second term's slots, in lane 0 and with 4, 6 or 8 halves per lane
+    (tests/test_multi_ladder_model.py replays these inputs); every other position and the odd lane shapes:
+    tests/test_msm_multi_ladder_gpu.py."""
     opt, val = (be.OPT_MSM_TERMS_PER_LANE, int(lpt[3:])) if lpt.startswith("tpl") else (be.OPT_MSM_LANES_PER_TERM, int(lpt))
     be.probe_set_option(opt, val)
     try:
