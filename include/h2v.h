@@ -341,9 +341,29 @@ int h2v_verify_batch_device(const h2v_plan *plan, const h2v_batch *batch, uint8_
  * Accepted by h2v_verify_batch_rlc(_device), h2v_verify_batch_submit with H2V_SUBMIT_RLC, h2v_check_pairs_rlc(_device) and
  * h2v_aggregate_batch(_device) (recursive plans: on their fold-pairs route - the leaf binds the inputs, which determine the folded
  * pairs).  H2V_E_ARG: together with H2V_RLC_SEED_GIVEN; in h2v_verify_mixed(_device) / h2v_aggregate_mixed(_device) - a mixed leaf
- * needs the key tag of its own proof's plan: a later change.  A call with the flag is never coalesced; it is routed as ever, and a
+ * needs the key tag of its own proof's plan: the mixed calls take H2V_RLC_SEED_KEYED (below) instead.  A call with the flag is never coalesced; it is routed as ever, and a
  * call that routing sends to the per-proof kernels derives nothing.  DESIGN.md section 17. */
 #define H2V_RLC_SEED_TRANSCRIPT 32u
+/* DERIVED SEED OF A MIXED-KEY CALL: form 3, "keyed leaves" (frozen).  As above, but every leaf binds the key of its own proof and
+ * the root binds no key:
+ *   mleaf_i = B(TAG("h2v-seed-mleaf/1") || LE32(|inst_i|) || LE32(|ci_i|) || LE32(|proof_i|) || LE32(0)
+ *               || key_tag(plans[plan_of[i]]) || inst_i || ci_i || proof_i)
+ *   seed    = B(TAG("h2v-seed-root/1") || LE32(3) || LE32(0) || LE64(n) || 32 zero bytes || top node)
+ * B, TAG, node and the 64-ary tree as above.  The tag string is exactly 16 bytes, the leaf header 64.  Leaves enter in the CALLER's
+ * order - the position the coefficients are drawn from; inst_i: the proof's own 32 n_pi(plan) bytes; ci_i: its 48 committed bytes,
+ * or empty for a plan without a committed instance; proof_i: proofs[proof_off[i] .. proof_off[i + 1]) AS GIVEN, short or long (never
+ * the copy the grouping kernels cut to proof_len); a descending pair of offsets is an empty proof.  So the seed does not depend on
+ * the order in which the plans are listed, on listed plans without a proof, or on the call's other flags - the RLC, fold and
+ * grouped forms, verify and aggregate, share ONE seed on the same batch (the fold form's fall-back reuses the words of its first
+ * pass) - and it does depend on which key every position has.  A one-plan mixed call does NOT share its seed with the single-key
+ * form 1 call on the same bytes.  Behind the seed nothing changes: r_i = low 128 bits of B(seed' || LE32(pos)); the H2V_MIXED_RLC
+ * tail on a laned workspace tweaks word 7 per chunk by 0x9e3779b9 (c + 1); the fold tail is one piece.
+ * Accepted by h2v_verify_mixed(_device) with H2V_MIXED_RLC (with or without _FOLD_MSM and _GROUPED) and by
+ * h2v_aggregate_mixed(_device) (with or without H2V_RLC_GROUPED; H2V_AGGREGATE_SEED_SOURCE(info) = 1), recursive plans included
+ * (they join as one pair per proof).  H2V_E_ARG: beside H2V_RLC_SEED_GIVEN or H2V_RLC_SEED_TRANSCRIPT; in a mixed call without
+ * H2V_MIXED_RLC; in every single-key entry point.  n > 2^22: H2V_E_LIMIT; n = 0 derives nothing.  h2v_workspace_seed_used / _seed_ms
+ * (calls_back = 0) answer for the call's last record, fallen back or not.  seed.py: mixed_seed.  DESIGN.md section 17.1. */
+#define H2V_RLC_SEED_KEYED 64u
 typedef struct h2v_rlc_opts_s {
     uint8_t seed[32];   /* used when flags & H2V_RLC_SEED_GIVEN (tests, reproducible measurements - never a service) */
     uint32_t flags;
@@ -557,12 +577,12 @@ int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, cons
  *   ERRORS as h2v_verify_batch_rlc(_device) / h2v_verify_mixed(_device): n > 2^22 is H2V_E_LIMIT; stream = NULL under deferred
  *   joins, a host batch in flight on ws, ws = NULL in a device form are H2V_E_ARG; ws = NULL in a host form: a temporary workspace.
  *   opts->flags: H2V_RLC_SEED_GIVEN and H2V_RLC_ONE_STREAM as ever, H2V_RLC_SEED_TRANSCRIPT in the single-key forms (not beside
- *   H2V_RLC_SEED_GIVEN), H2V_RLC_FOLD_PAIRS accepted and ignored, H2V_RLC_GROUPED in the
- *   mixed forms (phase 1 grouped as with H2V_MIXED_GROUPED: the same pair bit for bit), any other bit H2V_E_ARG.
+ *   H2V_RLC_SEED_GIVEN), H2V_RLC_SEED_KEYED in the mixed forms (not beside either), H2V_RLC_FOLD_PAIRS accepted and ignored,
+ *   H2V_RLC_GROUPED in the mixed forms (phase 1 grouped as with H2V_MIXED_GROUPED: the same pair bit for bit), any other bit H2V_E_ARG.
  *   The device forms take device pointers (pair 4-byte aligned; plan_of stays host memory); info is HOST memory in both forms.
  *   SOUNDNESS.  DRAWN OR GIVEN SEED: a pair vouches for its proofs only to someone who trusts that seed_used was unpredictable to
  *   the provers - the same trust domain as the caller of h2v_verify_batch_rlc.  It is NOT a proof for third parties.  DERIVED SEED
- *   (H2V_RLC_SEED_TRANSCRIPT, single-key form): nothing has to be kept from the provers - in the random-oracle model for blake2b a
+ *   (H2V_RLC_SEED_TRANSCRIPT, single-key form; H2V_RLC_SEED_KEYED, mixed form): nothing has to be kept from the provers - in the random-oracle model for blake2b a
  *   prover making q hash evaluations gets a rejecting proof into an accepting pair with probability at most q / 2^128 - and anyone
  *   who holds the same key, the same inputs and the same chunk size recomputes the same seed and the same pair (seed.py), so a
  *   pair can be compared between nodes and re-derived by an auditor.  It is still not a succinct proof for someone without the
@@ -576,7 +596,7 @@ typedef struct {
     uint32_t n_chunks;       /* 1 on an ordinary workspace and for the mixed form (and for n = 0 on any workspace) */
     uint32_t msm_terms;      /* terms of the right-hand bucket MSM(s), summed over chunks */
     uint32_t reserved;       /* the SEED SOURCE, under the name the word has always had (callers that zero `reserved` keep compiling; read it
-                              * as H2V_AGGREGATE_SEED_SOURCE(info)).  0: seed_used was drawn or given; 1: derived (H2V_RLC_SEED_TRANSCRIPT) -
+                              * as H2V_AGGREGATE_SEED_SOURCE(info)).  0: seed_used was drawn or given; 1: derived (H2V_RLC_SEED_TRANSCRIPT / _KEYED) -
                               * the host form fills seed_used from its download, the device form writes zeros (the seed is not known
                               * when the call returns: h2v_workspace_seed_used has it once the stream is synchronised) */
 } h2v_aggregate_info;        /* HOST memory, written before the call returns, in both forms; may be NULL */
@@ -650,6 +670,12 @@ int h2v_probe_blake2b_ex(int device, uint32_t n, uint32_t len, const uint8_t *ms
  * at the alignment proof_off[0] has (mod 16).  seed: the 32 bytes.  n = 0 or n > 2^22: H2V_E_ARG. */
 int h2v_probe_batch_seed(int device, uint32_t form, const uint8_t key_tag[32], const h2v_batch *batch /* host buffers */, uint32_t n_pi,
                          uint32_t n_ci, uint8_t seed[32]);
+/* The digest kernels of a keyed seed (H2V_RLC_SEED_KEYED, form 3) ALONE, as the mixed calls queue them, on bytes that need not be
+ * proofs: n_plans listed plans given by key_tags (n_plans x 32 bytes), n_pi[k] rows of 32 instance bytes and n_ci[k] (0 / 1) rows of
+ * 48 committed bytes per proof of plan k; batch as for h2v_verify_mixed, host buffers (proof_off need not ascend: a descending pair
+ * is an empty proof).  seed: the 32 bytes.  n = 0 or n > 2^22, n_plans = 0 or a plan_of out of range: H2V_E_ARG. */
+int h2v_probe_mixed_seed(int device, uint32_t n_plans, const uint8_t *key_tags, const uint32_t *n_pi, const uint32_t *n_ci,
+                         const h2v_mixed_batch *batch /* host buffers */, uint8_t seed[32]);
 int h2v_probe_g1_decompress(int device, uint32_t n, const uint8_t *compressed, uint8_t *xy_be, uint8_t *valid);
 /* sum_t s_t * B_t per group: n groups of T terms; scalars n*T*32 B LE, bases n*T*48 B compressed; out n*96 B affine BE */
 int h2v_probe_g1_msm(int device, uint32_t n, uint32_t T, const uint8_t *scalars, const uint8_t *bases_compressed,

@@ -261,18 +261,21 @@ inline std::vector<uint8_t> verify_batch_rlc(const VerifyingKey &vk, const h2v_b
 // over the call's per-proof terms as well; a failed check runs the call again without it (fell_back).  grouped (only with
 // fold_msm; H2V_MIXED_GROUPED): phase 1 of every key in one launch per kernel, up to H2V_MIXED_GROUPED_MAX_PLANS keys - many keys
 // with few proofs each; the same vectors.  ws: one made for the same keys or a superset (Workspace(vks, max_batch)), or nullptr
-// for a temporary one.
+// for a temporary one.  keyed_seed (only with rlc, not beside `seed`; H2V_RLC_SEED_KEYED): nothing is drawn - the seed is a digest
+// of the call in which every leaf binds the key of its own proof (h2v.h has the rule), the same whatever fold_msm / grouped say.
 inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
                                  bool rlc = false, const uint8_t *seed = nullptr, bool *fell_back = nullptr, bool fold_msm = false,
-                                 bool grouped = false) {
+                                 bool grouped = false, bool keyed_seed = false) {
     std::vector<const h2v_plan *> plans;
     for (const VerifyingKey *k : vks) plans.push_back(k ? k->handle() : nullptr);
     PairVerdicts r{std::vector<uint8_t>(batch.n), std::vector<uint32_t>(batch.n)};
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
+    if (keyed_seed) opts.flags |= H2V_RLC_SEED_KEYED;
     int fb = 0;
     check(h2v_verify_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.accept.data(), r.status.data(), ws,
-                           (rlc ? H2V_MIXED_RLC : 0u) | (fold_msm ? H2V_MIXED_FOLD_MSM : 0u) | (grouped ? H2V_MIXED_GROUPED : 0u), seed ? &opts : nullptr, &fb));
+                           (rlc ? H2V_MIXED_RLC : 0u) | (fold_msm ? H2V_MIXED_FOLD_MSM : 0u) | (grouped ? H2V_MIXED_GROUPED : 0u),
+                           (seed || keyed_seed) ? &opts : nullptr, &fb));
     if (fell_back) *fell_back = fb != 0;
     return r;
 }
@@ -280,8 +283,8 @@ inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, c
 // one final check for a list of (vk, instances, proof) triples on one SRS.  Throws VerifyError (with the first rejected proof's
 // status) unless every proof is accepted.
 inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
-                         bool fold_msm = false, bool grouped = false) {
-    const PairVerdicts r = verify_mixed(vks, batch, ws, true, nullptr, nullptr, fold_msm, grouped);
+                         bool fold_msm = false, bool grouped = false, bool keyed_seed = false) {
+    const PairVerdicts r = verify_mixed(vks, batch, ws, true, nullptr, nullptr, fold_msm, grouped, keyed_seed);
     for (uint64_t i = 0; i < batch.n; i++)
         if (!r.accept[i]) throw VerifyError(r.status[i]);
 }
@@ -290,7 +293,8 @@ inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v
 // check_pairs(_rlc) is its `check`.  included[i] = 1: proof i was not rejected before the pairing (NOT a verdict: it is accepted
 // iff the pair's equation holds); status as prepare_batch; info: the seed and chunking the coefficients follow.  seed: 32 bytes
 // that provers cannot predict, or nullptr = drawn from the OS.  grouped (aggregate_mixed; H2V_RLC_GROUPED): phase 1 as
-// verify_mixed(.., grouped) runs it - the same pair.
+// verify_mixed(.., grouped) runs it - the same pair.  keyed_seed (aggregate_mixed; H2V_RLC_SEED_KEYED, not beside `seed`):
+// H2V_AGGREGATE_SEED_SOURCE(&info) = 1 and info.seed_used is the digest of the call with keyed leaves.
 struct Aggregate {
     uint8_t pair[96];
     std::vector<uint8_t> included;
@@ -310,15 +314,16 @@ inline Aggregate aggregate_batch(const VerifyingKey &vk, const h2v_batch &batch,
     return r;
 }
 inline Aggregate aggregate_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
-                                 const uint8_t *seed = nullptr, bool grouped = false) {
+                                 const uint8_t *seed = nullptr, bool grouped = false, bool keyed_seed = false) {
     std::vector<const h2v_plan *> plans;
     for (const VerifyingKey *k : vks) plans.push_back(k ? k->handle() : nullptr);
     Aggregate r{{}, std::vector<uint8_t>(batch.n ? batch.n : 1), std::vector<uint32_t>(batch.n ? batch.n : 1), {}};
     h2v_rlc_opts opts{};
     if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
     if (grouped) opts.flags |= H2V_RLC_GROUPED;
+    if (keyed_seed) opts.flags |= H2V_RLC_SEED_KEYED;
     check(h2v_aggregate_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.pair, r.included.data(), r.status.data(), ws,
-                              (seed || grouped) ? &opts : nullptr, &r.info));
+                              (seed || grouped || keyed_seed) ? &opts : nullptr, &r.info));
     r.included.resize(batch.n); r.status.resize(batch.n);
     return r;
 }
@@ -331,12 +336,22 @@ inline Aggregate aggregate_mixed(const std::vector<const VerifyingKey *> &vks, c
 // (aggregate_mixed; Aggregator(true): its grouped form) and is verified again, if its pair fails, with verify_mixed.
 class Aggregator {
   public:
-    /// derive_seed: every push derives its seed from its key and batch; single-key pushes only (push_mixed: Error(H2V_E_ARG))
-    explicit Aggregator(bool grouped = false, bool derive_seed = false) : grouped_(grouped), derive_seed_(derive_seed) {}
+    /// derive_seed: every push derives its seed from its key and batch; single-key pushes only (push_mixed: Error(H2V_E_ARG)).
+    /// keyed_seed: every push derives by the mixed calls' rule (H2V_RLC_SEED_KEYED) - push_mixed derives, and a single-key push goes
+    /// out as a one-plan mixed call, so that every pair of the aggregator follows one rule.  Both: Error(H2V_E_ARG).
+    explicit Aggregator(bool grouped = false, bool derive_seed = false, bool keyed_seed = false)
+        : grouped_(grouped), derive_seed_(derive_seed), keyed_seed_(keyed_seed) {
+        if (derive_seed && keyed_seed) throw Error(H2V_E_ARG, "Aggregator: derive_seed and keyed_seed exclude each other");
+    }
     Aggregator(const Aggregator &) = delete;
     Aggregator &operator=(const Aggregator &) = delete;
     /// one SRS per Aggregator - that of the first key pushed: a key on another SRS is Error(H2V_E_ARG), before anything runs
     size_t push(const VerifyingKey &vk, const h2v_batch &b, const uint8_t *seed = nullptr) {
+        if (keyed_seed_) {      // (a one-plan mixed call: the aggregator's one rule)
+            const std::vector<uint32_t> plan_of(b.n ? b.n : 1, 0u);
+            const h2v_mixed_batch mb = {b.n, plan_of.data(), b.proofs, b.proof_off, b.instances, b.committed};
+            return push_mixed({&vk}, mb, seed);
+        }
         if (!srs_) srs_ = &vk;
         const int same = h2v_plan_same_srs(srs_->handle(), vk.handle());
         if (same < 0) check(same);
@@ -367,7 +382,7 @@ class Aggregator {
         Call c;
         c.vk = vks[0];
         c.vks = vks;
-        const Aggregate a = aggregate_mixed(vks, b, nullptr, seed, grouped_);
+        const Aggregate a = aggregate_mixed(vks, b, nullptr, seed, grouped_, keyed_seed_);
         for (int k = 0; k < 96; k++) c.pair[k] = a.pair[k];
         c.included = a.included;
         c.plan_of.assign(b.plan_of, b.plan_of + b.n);
@@ -418,7 +433,7 @@ class Aggregator {
     };
     std::vector<Call> calls_;
     const VerifyingKey *srs_ = nullptr;
-    bool grouped_ = false, derive_seed_ = false;
+    bool grouped_ = false, derive_seed_ = false, keyed_seed_ = false;
 };
 
 // A reusable workspace, and the streaming form: submit() returns once the batch is copied and everything is enqueued,

@@ -299,7 +299,7 @@ def _mixed_workspace(verifiers, n: int) -> backend.Workspace:
 
 def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
                  committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof", seed: Optional[bytes] = None,
-                 device: int = 0, fold_msm: bool = False, grouped: bool = False) -> List[bool]:
+                 device: int = 0, fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False) -> List[bool]:
     """accept[i] for n proofs, proof i under the key vks[i] (instances[i]: its public-input scalars; committed[i]: its
     committed instance as 48 compressed bytes when its circuit has one, else None).  The proofs are grouped by SRS on the
     host - one h2v_verify_mixed call per distinct s_g2, each over all its keys - and the verdicts come back in the caller's
@@ -307,8 +307,11 @@ def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances
     over `seed` (from the OS when None).  fold_msm (mode="rlc" only): ONE bucket MSM over the call's per-proof terms as well
     (H2V_MIXED_FOLD_MSM); a failed check runs the call again without it.  grouped (with fold_msm only; H2V_MIXED_GROUPED): phase 1
     of every key in one launch per kernel and up to backend.MIXED_GROUPED_MAX_PLANS keys per call - for many keys with few proofs
-    each; the same verdicts."""
-    return _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm, grouped)[0]
+    each; the same verdicts.  keyed_seed (mode="rlc"; H2V_RLC_SEED_KEYED, not beside `seed`): nothing is drawn - every call's
+    seed is a digest of its proofs, instances and each proof's own key (seed.mixed_seed), the same whatever fold_msm / grouped say."""
+    if keyed_seed and mode != "rlc":
+        raise ValueError("keyed_seed needs mode='rlc'")
+    return _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm, grouped, keyed_seed)[0]
 
 
 def _mixed_calls(vks, proofs, instances, committed, device):
@@ -340,7 +343,7 @@ def _mixed_calls(vks, proofs, instances, committed, device):
         yield idx, verifiers, plan_of, b"".join(bytes(proofs[i]) for i in idx), off, b"".join(inst), b"".join(ci) or None
 
 
-def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm=False, grouped=False):
+def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm=False, grouped=False, keyed_seed=False):
     """(accept, status) of verify_mixed"""
     if mode not in ("per-proof", "rlc"):
         raise ValueError("mode is 'per-proof' or 'rlc'")
@@ -352,7 +355,8 @@ def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_ms
     status: List[int] = [0] * len(proofs)
     for idx, verifiers, plan_of, pbytes, off, inst, ci in _mixed_calls(vks, proofs, instances, committed, device):
         acc, st, _fb = backend.verify_mixed([v.device_plan for v in verifiers], plan_of, pbytes, off, inst, ci,
-                                             ws=_mixed_workspace(verifiers, len(idx)), mode=mode, seed=seed, fold_msm=fold_msm, grouped=grouped)
+                                             ws=_mixed_workspace(verifiers, len(idx)), mode=mode, seed=seed, fold_msm=fold_msm, grouped=grouped,
+                                             keyed_seed=keyed_seed)
         for i, a, s in zip(idx, acc, st):
             out[i], status[i] = bool(a), s
     return out, status
@@ -360,15 +364,16 @@ def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_ms
 
 def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instances: Sequence[Sequence[int]],
                  proofs: Sequence[bytes], committed: Optional[Sequence[Optional[bytes]]] = None, device: int = 0,
-                 fold_msm: bool = False, grouped: bool = False) -> None:
+                 fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False) -> None:
     """midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs) (src/circuits/schnorr_circuit.rs:223-231): one
     call and one final check for a list of (vk, instances, proof) triples on ONE SRS - the batch-accept mode of verify_mixed.
     Raises VerifyError unless every proof is accepted (Rust: Err(_)); a key on another SRS than `params` is a ValueError.
-    fold_msm: one bucket MSM for the list as well; grouped: phase 1 of every key in one launch per kernel (verify_mixed)."""
+    fold_msm: one bucket MSM for the list as well; grouped: phase 1 of every key in one launch per kernel; keyed_seed: the seed is
+    derived from the list itself (verify_mixed)."""
     for i, vk in enumerate(vks):
         if bytes(params.s_g2) != bytes.fromhex(vk.s_g2):
             raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
-    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm, grouped)
+    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm, grouped, keyed_seed)
     if not all(acc):
         raise VerifyError(next(s for a, s in zip(acc, status) if not a))
 
@@ -388,11 +393,19 @@ class Aggregator:
     kept.  The pairs of different calls are scaled again with fresh coefficients by the check, so the errors of two calls cannot
     cancel.  A pair is only worth what the seed of its call is: keep an Aggregator inside one trust domain."""
 
-    def __init__(self, params: ParamsVerifierKZG, device: int = 0, grouped: bool = False, derive_seed: bool = False):
+    def __init__(self, params: ParamsVerifierKZG, device: int = 0, grouped: bool = False, derive_seed: bool = False,
+                 keyed_seed: bool = False):
         """grouped: push_mixed runs phase 1 of every key in one launch per kernel (H2V_RLC_GROUPED) - the same pairs.
         derive_seed: every push derives its seed from its key and batch (H2V_RLC_SEED_TRANSCRIPT): its pair can be recomputed by
-        anyone who holds the inputs.  Single-key pushes only: push_mixed raises ValueError (the mixed calls have no derived seed)."""
-        self.params, self.device, self.grouped, self.derive_seed = params, device, grouped, derive_seed
+        anyone who holds the inputs.  Single-key pushes only: push_mixed raises ValueError (the mixed calls have no derived seed
+        of that form).
+        keyed_seed: every push derives its seed by the mixed calls' rule (H2V_RLC_SEED_KEYED; seed.mixed_seed - every leaf binds the
+        key of its own proof).  push_mixed derives, and a single-key push goes out as a ONE-PLAN MIXED CALL, so that every pair
+        of the aggregator follows one rule - its seed is NOT the one derive_seed would give the same batch.  Together with
+        derive_seed: ValueError (one rule per aggregator)."""
+        if derive_seed and keyed_seed:
+            raise ValueError("derive_seed and keyed_seed exclude each other: one seed rule per Aggregator")
+        self.params, self.device, self.grouped, self.derive_seed, self.keyed_seed = params, device, grouped, derive_seed, keyed_seed
         self._calls = []      # (a verifier on the SRS, pair, included, the call again per proof -> accept list)
 
     def push(self, vk: VerifyingKey, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
@@ -400,6 +413,10 @@ class Aggregator:
         """aggregates one call of proofs of `vk` and keeps its pair, included[] and a reference to the inputs; returns the call's index"""
         if bytes(self.params.s_g2) != bytes.fromhex(vk.s_g2):
             raise ValueError("verifier params do not match the verifying key's SRS (s_g2 differs)")
+        if self.keyed_seed:      # (a one-plan mixed call: the aggregator's one rule)
+            if seed is not None:
+                raise ValueError("keyed_seed derives the seed: none can be given")
+            return self.push_mixed([vk] * len(proofs), proofs, instances, committed)
         v = verifier_for(vk, self.device)
         pair, included, _status, _info = v.aggregate_batch(proofs, instances, committed, seed=seed, derive_seed=self.derive_seed)
         self._calls.append((v, pair, included, lambda: v.verify_batch(proofs, instances, committed)))
@@ -418,7 +435,8 @@ class Aggregator:
             raise ValueError("no proofs")
         (idx, verifiers, plan_of, pbytes, off, inst, ci), = _mixed_calls(vks, proofs, instances, committed, self.device)
         pair, included, _status, _info = backend.aggregate_mixed([v.device_plan for v in verifiers], plan_of, pbytes, off, inst, ci,
-                                                                 ws=_mixed_workspace(verifiers, len(idx)), seed=seed, grouped=self.grouped)
+                                                                 ws=_mixed_workspace(verifiers, len(idx)), seed=seed, grouped=self.grouped,
+                                                                 keyed_seed=self.keyed_seed)
         self._calls.append((verifiers[0], pair, included, lambda: verify_mixed(vks, proofs, instances, committed, device=self.device)))
         return len(self._calls) - 1
 

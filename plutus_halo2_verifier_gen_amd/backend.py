@@ -86,6 +86,7 @@ RLC_ONE_STREAM = 2
 RLC_FOLD_PAIRS = 4   # recursive plans: combine the pairs (el', er') the fold leaves (include/h2v.h)
 RLC_GROUPED = 16     # h2v_aggregate_mixed(_device) only: the MIXED_GROUPED form of the call (bit 8 stays unknown)
 RLC_SEED_TRANSCRIPT = 32   # the seed is derived from the batch itself (seed.py has the rule); never beside RLC_SEED_GIVEN
+RLC_SEED_KEYED = 64        # the mixed calls' derived seed: form 3, keyed leaves (seed.mixed_seed); never beside the two above
 SUBMIT_RLC = 1
 MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
 MIXED_FOLD_MSM = 2     # ... and ONE bucket MSM over the call's per-proof terms (only together with MIXED_RLC)
@@ -96,12 +97,13 @@ MIXED_GROUPED_MAX_OTHER = 62     # H2V_MIXED_GROUPED_MAX_OTHER: ... of which pla
 BATCH_NOT_CHECKED = 2  # H2V_BATCH_NOT_CHECKED: batch_accepted of an aggregate call (Workspace.rlc_verdict)
 
 
-def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False, grouped: bool = False, derive_seed: bool = False):
-    """derive_seed beside a seed goes to the library as it is: the library answers H2V_E_ARG"""
-    if seed is None and not one_stream and not fold_pairs and not grouped and not derive_seed:
+def _rlc_opts(seed, one_stream: bool = False, fold_pairs: bool = False, grouped: bool = False, derive_seed: bool = False,
+              keyed_seed: bool = False):
+    """derive_seed / keyed_seed beside a seed or beside each other go to the library as they are: the library answers H2V_E_ARG"""
+    if seed is None and not one_stream and not fold_pairs and not grouped and not derive_seed and not keyed_seed:
         return None
     flags = ((RLC_ONE_STREAM if one_stream else 0) | (RLC_FOLD_PAIRS if fold_pairs else 0) | (RLC_GROUPED if grouped else 0) |
-             (RLC_SEED_TRANSCRIPT if derive_seed else 0))
+             (RLC_SEED_TRANSCRIPT if derive_seed else 0) | (RLC_SEED_KEYED if keyed_seed else 0))
     if seed is None:
         return RlcOpts((C.c_uint8 * 32)(), flags)
     seed = bytes(seed)
@@ -126,6 +128,7 @@ EXPORTS = [
     "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums", "h2v_probe_decompress",
     "h2v_aggregate_batch", "h2v_aggregate_batch_device", "h2v_aggregate_mixed", "h2v_aggregate_mixed_device", "h2v_plan_same_srs",
     "h2v_workspace_seed_used", "h2v_workspace_seed_ms", "h2v_probe_batch_seed", "h2v_plan_key_tag",
+    "h2v_probe_mixed_seed",
 ]
 # exported for the tests alone and not part of include/h2v.h (csrc/h2v_probes.hpp)
 PROBE_ONLY_EXPORTS = ["h2v_probe_device_memory"]
@@ -222,6 +225,7 @@ def lib():
         L.h2v_workspace_seed_used.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.h2v_workspace_seed_ms.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
         L.h2v_probe_batch_seed.argtypes = [C.c_int, C.c_uint32, C.c_char_p, C.POINTER(Batch), C.c_uint32, C.c_uint32, C.c_void_p]
+        L.h2v_probe_mixed_seed.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_plan_key_tag.argtypes = [C.c_void_p, C.c_void_p]
         L.h2v_probe_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
         L.h2v_aggregate_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RlcOpts),
@@ -612,14 +616,16 @@ def _mixed_mode(mode: str, fold_msm: bool = False, grouped: bool = False) -> int
 
 
 def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
-                 mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False):
+                 mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False,
+                 keyed_seed: bool = False):
     """h2v_verify_mixed: n proofs of several plans on ONE SRS in one call; proof i belongs to plans[plan_of[i]], its public
     inputs (and committed instance, where its plan has one) follow those of the proofs before it.  Returns (accept bytes,
     status list, fell_back) in the caller's order.  mode="rlc": ONE pairing for the call (fell_back: the batch check failed
     and the per-pair kernels produced accept[]).  fold_msm (mode="rlc" only; MIXED_FOLD_MSM): ONE bucket MSM over the call's
     per-proof terms as well - no ladder MSM unless the check fails, in which case the call runs again without it (fell_back).
     grouped (with fold_msm only; MIXED_GROUPED): phase 1 of every groupable plan in one launch per kernel, up to
-    MIXED_GROUPED_MAX_PLANS plans - the same results.  ws: typically Workspace.multi over the same plans; None: a temporary one."""
+    MIXED_GROUPED_MAX_PLANS plans - the same results.  keyed_seed (mode="rlc"; RLC_SEED_KEYED): the seed is a digest of the call
+    (seed.mixed_seed: every leaf binds its own proof's key), the same in every form; ws.seed_used() has it afterwards.  ws: typically Workspace.multi over the same plans; None: a temporary one."""
     n = len(proof_off) - 1
     if n < 0 or len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
@@ -637,14 +643,15 @@ def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[b
     st = (C.c_uint32 * max(1, n))()
     fb = C.c_int(0)
     flags = _mixed_mode(mode, fold_msm, grouped)
-    opts = _rlc_opts(seed)
+    opts = _rlc_opts(seed, keyed_seed=keyed_seed)
     check(lib().h2v_verify_mixed(arr, len(plans), C.byref(b), acc, st, ws.handle if ws else None, flags,
                                  C.byref(opts) if opts is not None else None, C.byref(fb)))
     return bytes(acc[:n]), list(st[:n]), bool(fb.value)
 
 
 def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_accept, d_status=None, ws=None, stream=None,
-                        mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False) -> None:
+                        mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False,
+                        keyed_seed: bool = False) -> None:
     """h2v_verify_mixed_device: enqueues on `stream`; plan_of is a host list, every d_* a device pointer.  `stream` has
     waited for the call's lanes when this returns (a join point, deferred joins or not); ws.rlc_result() has the batch
     verdict of an mode="rlc" call once the stream is synchronised.  fold_msm: as verify_mixed; the call then returns only
@@ -655,16 +662,17 @@ def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d
     arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
     po = (C.c_uint32 * max(1, n))(*plan_of)
     b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
-    opts = _rlc_opts(seed)
+    opts = _rlc_opts(seed, keyed_seed=keyed_seed)
     check(lib().h2v_verify_mixed_device(arr, len(plans), C.byref(b), d_accept, d_status, ws.handle if ws else None, stream,
                                         flags, C.byref(opts) if opts is not None else None))
 
 
 def aggregate_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
-                    seed: Optional[bytes] = None, grouped: bool = False):
+                    seed: Optional[bytes] = None, grouped: bool = False, keyed_seed: bool = False):
     """h2v_aggregate_mixed: the fold_msm form of verify_mixed without its verdict - (pair, included, status, info) for the call,
     included / status in the caller's order; the coefficient of proof i follows its position in the call (info.chunk = 0).
-    grouped (RLC_GROUPED): phase 1 as verify_mixed(grouped=True) runs it - the same pair."""
+    grouped (RLC_GROUPED): phase 1 as verify_mixed(grouped=True) runs it - the same pair.  keyed_seed (RLC_SEED_KEYED): the seed
+    is seed.mixed_seed of the call - info.seed_source = 1, info.seed_used has it."""
     n = len(proof_off) - 1
     if n < 0 or len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
@@ -682,22 +690,23 @@ def aggregate_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optiona
     inc = (C.c_uint8 * max(1, n))()
     st = (C.c_uint32 * max(1, n))()
     info = AggregateInfo()
-    opts = _rlc_opts(seed, grouped=grouped)
+    opts = _rlc_opts(seed, grouped=grouped, keyed_seed=keyed_seed)
     check(lib().h2v_aggregate_mixed(arr, len(plans), C.byref(b), pair, inc, st, ws.handle if ws else None,
                                     C.byref(opts) if opts is not None else None, C.byref(info)))
     return pair.raw, bytes(inc[:n]), list(st[:n]), info
 
 
 def aggregate_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_pair, d_included, d_status=None, ws=None,
-                           stream=None, seed: Optional[bytes] = None, grouped: bool = False) -> AggregateInfo:
-    """h2v_aggregate_mixed_device: enqueues on `stream` and returns - no verdict comes down, the stream is not synchronised"""
+                           stream=None, seed: Optional[bytes] = None, grouped: bool = False, keyed_seed: bool = False) -> AggregateInfo:
+    """h2v_aggregate_mixed_device: enqueues on `stream` and returns - no verdict comes down, the stream is not synchronised
+    (keyed_seed: info.seed_used is zero, ws.seed_used() has the seed once the stream is synchronised)"""
     if len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
     arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
     po = (C.c_uint32 * max(1, n))(*plan_of)
     b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
     info = AggregateInfo()
-    opts = _rlc_opts(seed, grouped=grouped)
+    opts = _rlc_opts(seed, grouped=grouped, keyed_seed=keyed_seed)
     check(lib().h2v_aggregate_mixed_device(arr, len(plans), C.byref(b), d_pair, d_included, d_status, ws.handle if ws else None, stream,
                                            C.byref(opts) if opts is not None else None, C.byref(info)))
     return info
@@ -735,6 +744,29 @@ def probe_batch_seed(form: int, key_tag: bytes, proofs: bytes, proof_off=None, i
               C.cast(ibuf, C.c_void_p) if ibuf is not None else None, C.cast(cbuf, C.c_void_p) if cbuf is not None else None)
     out = C.create_string_buffer(32)
     check(lib().h2v_probe_batch_seed(device, form, bytes(key_tag), C.byref(b), n_pi, n_ci, out))
+    return out.raw
+
+
+def probe_mixed_seed(tags, shapes, plan_of, proofs: bytes, proof_off, instances: Optional[bytes] = None,
+                     committed: Optional[bytes] = None, device: int = 0) -> bytes:
+    """h2v_probe_mixed_seed: the digest kernels of a keyed seed (form 3) alone, on bytes that need not be proofs.  tags: 32 bytes
+    per listed plan; shapes[k] = (n_pi, n_ci); the rest as an h2v_mixed_batch (a descending pair of offsets is an empty proof).
+    Returns the 32-byte seed (seed.mixed_seed_flat states the same)."""
+    n, k = len(proof_off) - 1, len(tags)
+    if len(plan_of) != n or len(shapes) != k:
+        raise H2VError("plan_of: one entry per proof; shapes: one per tag")
+    tbuf = C.create_string_buffer(b"".join(bytes(t) for t in tags), 32 * max(1, k))
+    npi = (C.c_uint32 * max(1, k))(*[s[0] for s in shapes])
+    nci = (C.c_uint32 * max(1, k))(*[s[1] for s in shapes])
+    po = (C.c_uint32 * max(1, n))(*plan_of)
+    off = (C.c_uint64 * (n + 1))(*proof_off)
+    pbuf = C.create_string_buffer(proofs, len(proofs)) if proofs else C.create_string_buffer(1)
+    ibuf = C.create_string_buffer(instances, len(instances)) if instances else None
+    cbuf = C.create_string_buffer(committed, len(committed)) if committed else None
+    b = MixedBatch(n, C.cast(po, C.c_void_p), C.cast(pbuf, C.c_void_p), C.cast(off, C.c_void_p),
+                   C.cast(ibuf, C.c_void_p) if ibuf is not None else None, C.cast(cbuf, C.c_void_p) if cbuf is not None else None)
+    out = C.create_string_buffer(32)
+    check(lib().h2v_probe_mixed_seed(device, k, tbuf, npi, nci, C.byref(b), out))
     return out.raw
 
 

@@ -2178,7 +2178,7 @@ static bool rlc_supported(const h2v_plan *p);
 static bool fold_pairs_wanted(const h2v_plan *p, const h2v_rlc_opts *o);
 static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]);
 static int seed_flags(const h2v_rlc_opts *o, bool *derive);
-static int seed_flags_mixed(const h2v_rlc_opts *o);
+static int seed_flags_mixed(const h2v_rlc_opts *o, bool rlc, bool *keyed);
 
 // Host-buffer batches on a LANED workspace: as many in flight as the mode has lanes, on ONE workspace.  Every batch gets a
 // staging slot of its own (pinned block + device block + accept buffers); uploads run in order on `hs`, the chunks on
@@ -2895,97 +2895,7 @@ static int rlc_seed(const h2v_rlc_opts *o, uint32_t seed[8]) {
     }
     return H2V_OK;
 }
-// ---- derived seeds (H2V_RLC_SEED_TRANSCRIPT): the seed is a digest of the whole call (h2v_seed.hpp has the rule), computed on the
-// device in front of the call and read there by the coefficient kernels; nothing of it is known on the host when the call returns.
-// what the flags of a batch-accept call say about its seed: *derive; the flag beside a given seed is a contradiction
-static int seed_flags(const h2v_rlc_opts *o, bool *derive) {
-    *derive = o && (o->flags & H2V_RLC_SEED_TRANSCRIPT);
-    if (*derive && (o->flags & H2V_RLC_SEED_GIVEN)) return fail(H2V_E_ARG, "H2V_RLC_SEED_TRANSCRIPT and H2V_RLC_SEED_GIVEN exclude each other");
-    return H2V_OK;
-}
-// the mixed forms have no derived seed yet: a mixed leaf needs the key tag of its own proof's plan
-static int seed_flags_mixed(const h2v_rlc_opts *o) {
-    if (o && (o->flags & H2V_RLC_SEED_TRANSCRIPT)) return fail(H2V_E_ARG, "H2V_RLC_SEED_TRANSCRIPT is not available in the mixed calls");
-    return H2V_OK;
-}
-// One derivation: the leaf launch, one node launch per level - the last forms the seed - on `st`.  Device pointers throughout;
-// digests: room for the tree's extent; form 2 (pairs): proofs holds n x 96 bytes and off, inst, ci are not read.
-struct SeedJob {
-    uint32_t form; uint64_t n; uint32_t inst_len, ci_len;
-    const uint8_t *proofs; const uint64_t *off; const uint8_t *inst, *ci;
-    const uint8_t *key_tag;      // host, 32 bytes
-    uint32_t *digests, *seed_out;
-};
-static int seed_launch(const SeedJob &j, hipStream_t st) {
-    h2vseed::Tree t;
-    if (!h2vseed::tree(j.n, &t) || t.levels == 0) return fail(H2V_E_ARG, "internal: no digest tree for this batch size");
-    const h2vseed::TagWords leaf = h2vseed::tag_words(h2vseed::TAG_LEAF), node = h2vseed::tag_words(h2vseed::TAG_NODE), root = h2vseed::tag_words(h2vseed::TAG_ROOT);
-    const bool pairs = j.form == h2vseed::FORM_PAIRS;
-    SeedLeafArgs la = {(uint32_t)j.n, pairs ? 0u : j.inst_len, pairs ? 0u : j.ci_len, pairs ? 1u : 0u, j.proofs, j.off, j.inst, j.ci, {}, j.digests};
-    memcpy(la.tag, leaf.w, 16);
-    hipLaunchKernelGGL(k_seed_leaves, dim3((uint32_t)((j.n + 63) / 64)), dim3(64), 0, st, la);
-    for (uint32_t l = 1; l <= t.levels; l++) {
-        SeedNodeArgs na = {l, (uint32_t)t.count[l - 1], (uint32_t)t.count[l], j.digests + t.off[l - 1] * 8, j.digests + t.off[l] * 8, {},
-                           j.form, (uint32_t)j.n, (uint32_t)(j.n >> 32), {}, {}, j.seed_out};
-        memcpy(na.tag, node.w, 16); memcpy(na.root_tag, root.w, 16); memcpy(na.key_tag, j.key_tag, 32);
-        hipLaunchKernelGGL(k_seed_nodes, dim3((uint32_t)((t.count[l] + 63) / 64)), dim3(64), 0, st, na);
-    }
-    HIPCHK(hipGetLastError());
-    return H2V_OK;
-}
-// THE place where a call's digest launches are queued (run_call): on `st`, into the slot of the seed ring that the call's record
-// - the next one of `ws` - indexes.  The digest buffer is one per workspace: a derivation waits for the one before it, on whatever
-// stream that ran (its consumers read the ring, not the buffer).  Sets u.seed_dev.
-static int seed_enqueue(Unit &u, h2v_workspace *ws, hipStream_t st) {
-    constexpr uint32_t RING = h2v_workspace::RING;
-    if (!ws->seed_ring) {
-        if (!ws->mem.alloc(ws->seed_ring, wslayout::seed_ring_bytes())) return fail(H2V_E_DEVICE, "allocation of the seed ring failed");
-    }
-    h2vseed::Tree t;
-    if (!h2vseed::tree(u.n, &t)) return fail(H2V_E_LIMIT, "derived seeds are limited to 2^22 proofs");
-    if (int rc = ws->seed_digests.ensure(ws->mem, (size_t)t.extent * 32, "the seed digests", [&]() -> int {
-            if (ws->ev_seed_last) HIPCHK(hipEventSynchronize(ws->ev_seed_last));
-            return H2V_OK;
-        })) return rc;
-    const uint32_t slot = (uint32_t)(ws->calls % RING);
-    for (hipEvent_t &e : ws->ev_seed[slot]) if (int rce = lazy_event(ws->mem, e, hipEventDefault)) return rce;
-    if (ws->ev_seed_last) HIPCHK(hipStreamWaitEvent(st, ws->ev_seed_last, 0));
-    HIPCHK(hipEventRecord(ws->ev_seed[slot][0], st));
-    const bool pairs = u.kind == UnitKind::PAIR_RLC;
-    const H2vDevPlan &d = u.p->d;
-    const SeedJob j = {pairs ? h2vseed::FORM_PAIRS : h2vseed::FORM_PROOFS, u.n, d.n_pi * 32u, d.n_ci * 48u, pairs ? u.pairs : u.proofs, u.off, u.inst, u.ci,
-                       u.p->key_tag, (uint32_t *)ws->seed_digests.p, ws->seed_ring + (size_t)slot * 8};
-    if (int rc = seed_launch(j, st)) return rc;
-    HIPCHK(hipEventRecord(ws->ev_seed[slot][1], st));
-    ws->ev_seed_last = ws->ev_seed[slot][1];
-    u.seed_dev = j.seed_out;
-    u.seed_xor7 = 0;
-    return H2V_OK;
-}
-// After the call's stream has been synchronised: the seed a call derived (calls_back as h2v_workspace_rlc_result counts them).
-extern "C" int h2v_workspace_seed_used(h2v_workspace *w, uint32_t calls_back, uint8_t seed[32]) {
-    if (!w || !seed) return fail(H2V_E_ARG, "null argument");
-    ALIVE(w);
-    const CallRec *r;
-    if (int rc = rec_lookup(w, calls_back, &r)) return rc;
-    if (!r->derived || !w->seed_ring) return fail(H2V_E_ARG, "that call derived no seed");
-    HIPCHK(hipSetDevice(w->device));
-    HIPCHK(hipMemcpy(seed, w->seed_ring + (r->call % h2v_workspace::RING) * 8, 32, hipMemcpyDeviceToHost));
-    return H2V_OK;
-}
-// ... and the device time of its digest launches, first start to last end (HIP events on the call's stream)
-extern "C" int h2v_workspace_seed_ms(h2v_workspace *w, uint32_t calls_back, float *ms) {
-    if (!w || !ms) return fail(H2V_E_ARG, "null argument");
-    ALIVE(w);
-    const CallRec *r;
-    if (int rc = rec_lookup(w, calls_back, &r)) return rc;
-    if (!r->derived) return fail(H2V_E_ARG, "that call derived no seed");
-    HIPCHK(hipSetDevice(w->device));
-    hipEvent_t *ev = w->ev_seed[r->call % h2v_workspace::RING];
-    HIPCHK(hipEventSynchronize(ev[1]));
-    HIPCHK(hipEventElapsedTime(ms, ev[0], ev[1]));
-    return H2V_OK;
-}
+#include "h2v_seed_host.hpp"   // derived seeds: the flags, seed_launch, seed_enqueue(_at), h2v_workspace_seed_used / _seed_ms
 static int rlc_check_batch(const h2v_plan *p, const h2v_batch *b, const uint8_t *accept) {
     if (!p || !b || !accept) return fail(H2V_E_ARG, "null argument");
     if (b->n)
@@ -3101,6 +3011,12 @@ struct MixedCall {
     h2vmixed::Partition pt;
     bool rlc = false, fold = false, grouped = false;     // H2V_MIXED_RLC, _FOLD_MSM, _GROUPED
     uint32_t seed[8] = {};                               // of the batch coefficients (rlc)
+    // H2V_RLC_SEED_KEYED: the seed is derived from the call (form 3; mixed_seed) and `seed` stays zero.  plan_of: the caller's
+    // (host memory in both forms), for the plan index of every leaf.  seed_prev: the second pass after a failed fold check - the
+    // eight words the first pass derived, in the seed ring; nothing is hashed again
+    bool keyed = false;
+    const uint32_t *plan_of = nullptr;
+    const uint32_t *seed_prev = nullptr;
     h2vmixed::FoldLayout lay;    // fold: the layout of the call's term pool (fold_layout over the workspace's chunk size)
     MixedGroupPlan grp;          // grouped: the groupable plans (lay's block sums then follow the grouped ranges)
     h2v_batch in = {};                                   // the call's device-resident buffers
@@ -3117,6 +3033,7 @@ struct MixedFold {
     const H2vFoldPlan *d_plans;           // lay->n_foldable entries
     const uint32_t *d_perm;               // grouped index -> position in the call
     uint32_t seed[8];
+    const uint32_t *seed_dev = nullptr;   // H2V_RLC_SEED_KEYED: the call's slot of the seed ring, read in place of `seed`
     const MixedGroupPlan *grp = nullptr;  // H2V_MIXED_GROUPED
     std::vector<MixedGroupRange> ranges;  // its ranges, in order
     const uint64_t *d_off = nullptr;      // the grouped proof offsets (n + 1)
@@ -3204,6 +3121,7 @@ static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st) {
     MixedTermsArgs a = {n, p->n_var, p->n_fix, slots, d.pi_point, d.n_terms, d.terms, w->scalars, w->status, w->valid, w->valid_sub, w->pts, u.pos, {},
                         r->r_scal + t0 * 8, f.m->fold_rpts + t0 * 24, r->l_scal, f.m->fold_lpts, r->vk_part + b0 * 8, u.pool.good, u.pool.status};
     copy_seed(a.seed, f.seed);
+    a.seed_dev = f.seed_dev;
     hipLaunchKernelGGL(k_mixed_terms, dim3((n + 63) / 64), dim3(64), 0, pm, a);
     HIPCHK(hipEventRecord(ev[6], pm));
     HIPCHK(hipGetLastError());
@@ -3257,6 +3175,7 @@ static int run_mixed_group(const Unit &u, h2v_workspace *w, hipStream_t st) {
     GroupTermsArgs ta = {g.recs, g.terms, g.n_groups, w->scalars, (const uint32_t *)w->status, w->valid, w->valid_sub, w->pts, f.d_perm, {},
                          r->r_scal, m->fold_rpts, r->l_scal, m->fold_lpts, r->vk_part, u.pool.good, u.pool.status};
     copy_seed(ta.seed, f.seed);
+    ta.seed_dev = f.seed_dev;
     hipLaunchKernelGGL(k_mixed_terms_grouped, dim3(g.blocks_terms), dim3(64), 0, pm, ta);
     HIPCHK(hipEventRecord(ev[5], pm));
     HIPCHK(hipEventRecord(ev[6], pm));
@@ -3289,6 +3208,7 @@ static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st) 
         if (!f.pt->count[k] || lay.foldable[k]) continue;
         MixedPairTermsArgs pa = {f.pt->count[k], lay.pair_base[k], f.d_perm + f.pt->base[k], m->pool, m->good, {}, r->r_scal, m->fold_rpts, r->l_scal, m->fold_lpts};
         copy_seed(pa.seed, f.seed);
+        pa.seed_dev = f.seed_dev;
         hipLaunchKernelGGL(k_mixed_pair_terms, dim3((pa.n + 63) / 64), dim3(64), 0, st, pa);
     }
     HIPCHK(hipEventRecord(rec.ev[4], st));
@@ -3359,6 +3279,7 @@ struct MixedTables {
     H2vMixedTab tab = {};
     const H2vFoldPlan *d_fold = nullptr;      // fold: lay.n_foldable entries
     std::vector<MixedGroupRange> ranges;      // grouped: its ranges, in order
+    const uint32_t *d_plan_idx = nullptr, *d_key_tags = nullptr;      // keyed leaves: the plan of every grouped position; 8 dwords per listed plan
 };
 static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, MixedTables &out) {
     MixedWs *m = w->mixed;
@@ -3372,12 +3293,16 @@ static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, Mi
         if (!h2vmixed::group_tables(c.grp.sp, c.grp.shapes.data(), pt, c.lay, g0, g1, m->fold_cap_terms, m->fold_cap_parts, gt[q], &err)) return fail(H2V_E_DEVICE, err);
         n_groups[q] = (uint32_t)gt[q].rec.size();
     }
-    const mixedtab::TableBlock B = mixedtab::table_block(pt.n, c.fold ? (size_t)c.lay.n_foldable * sizeof(H2vFoldPlan) : 0, n_groups.data(), n_groups.size());
+    const bool leaves = c.keyed && !c.seed_prev;      // (the pass that derives: the second pass of a call copies eight words)
+    const mixedtab::TableBlock B = mixedtab::table_block(pt.n, c.fold ? (size_t)c.lay.n_foldable * sizeof(H2vFoldPlan) : 0, n_groups.data(), n_groups.size(),
+                                                         leaves ? pt.n_plans : 0u);
     int si;
     if (int rc = mixed_slot(m, B.extent, &si)) return rc;
     MixedWs::Slot &sl = m->slot[si];
     std::vector<mixedtab::RangeInfo> info;
-    mixedtab::pack_tables(sl.h, B, pt, c.host_off, gt, info);
+    std::vector<uint8_t> tags(leaves ? (size_t)pt.n_plans * 32 : 0u);
+    for (uint32_t k = 0; leaves && k < pt.n_plans; k++) memcpy(tags.data() + (size_t)k * 32, c.plans[k]->key_tag, 32);
+    mixedtab::pack_tables(sl.h, B, pt, c.host_off, gt, info, leaves ? c.plan_of : nullptr, leaves ? tags.data() : nullptr);
     if (c.fold) {            // what k_mixed_vk_sum reads of the foldable plans, in list order (device pointers: written here)
         H2vFoldPlan *fp = (H2vFoldPlan *)(sl.h + B.fold.off);
         for (uint32_t k = 0; k < pt.n_plans; k++)
@@ -3392,6 +3317,7 @@ static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, Mi
     out.tab = {pt.n, (const uint64_t *)dev(B.inst_src), (const uint64_t *)dev(B.inst_dst), (const uint32_t *)dev(B.perm), (const uint32_t *)dev(B.len_cap),
                (const uint32_t *)dev(B.inst_len), (const uint32_t *)dev(B.ci_src), (const uint32_t *)dev(B.ci_dst)};
     out.d_fold = (const H2vFoldPlan *)dev(B.fold);
+    out.d_plan_idx = (const uint32_t *)dev(B.plan_idx); out.d_key_tags = (const uint32_t *)dev(B.key_tags);
     out.ranges.resize(gt.size());
     for (size_t q = 0; q < gt.size(); q++) {
         MixedGroupRange &r = out.ranges[q];
@@ -3508,6 +3434,37 @@ static int mixed_run_laned(const MixedCall &c, MixedUnits &mu, h2v_workspace *w,
     // a mixed call is a join point: its caller-stream wait happens here, deferred joins or not
     return lanes_join(w, st);
 }
+// H2V_RLC_SEED_KEYED, THE place where a mixed call gets its seed: on the call's stream behind the table upload (and so behind the
+// host form's input upload) and in front of everything the pass forks to lanes or sub-batches.  The slot of the seed ring is the
+// one of the pass's LAST record - the tail's, `records` - 1 records ahead -, chosen before any record is taken: every consumer of the
+// pass reads that slot, h2v_workspace_seed_used / _seed_ms find it through the call's last record, and no other record of the
+// call is ever handed it, because records do not write the ring - only a derivation does, and a call has one.  The first pass
+// derives (seed_enqueue_at: the ring, the digest buffer and the events are seed_enqueue's); the second pass of a fold call that
+// failed its check (c.seed_prev) copies the eight words to its own tail's slot - the first pass has finished, the stream was
+// synchronised for its verdict - and takes over the two timed events of the derivation, so that the getters answer for the
+// call's last record whether it fell back or not.  The digest kernels read the CALLER's buffers (c.in): proofs as given.
+static int mixed_seed(const MixedCall &c, const MixedTables &t, h2v_workspace *w, hipStream_t st, size_t records, const uint32_t **seed_dev) {
+    constexpr uint32_t RING = h2v_workspace::RING;
+    const uint32_t slot = (uint32_t)((w->calls + records - 1) % RING);
+    if (!c.seed_prev) {
+        const SeedMixedLeafArgs ma = {c.pt.n, t.tab.perm, t.tab.inst_src, t.tab.inst_len, t.tab.ci_src, t.d_plan_idx, t.d_key_tags,
+                                      c.in.proofs, c.in.proof_off, c.in.instances, c.in.committed, {}, nullptr};
+        SeedJob j = {h2vseed::FORM_MIXED, c.pt.n, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        j.mixed = &ma;
+        return seed_enqueue_at(w, st, slot, j, seed_dev);
+    }
+    uint32_t *const dst = w->seed_ring + (size_t)slot * 8;
+    const size_t from = (size_t)(c.seed_prev - w->seed_ring) / 8;
+    if (dst != c.seed_prev) {
+        HIPCHK(hipMemcpyAsync(dst, c.seed_prev, 32, hipMemcpyDeviceToDevice, st));
+        // (the owner knows events by the FIELD that holds them: both slots hold one before the handles change places, so that the
+        //  release finds a live handle in every field it recorded)
+        for (hipEvent_t &e : w->ev_seed[slot]) if (int rce = lazy_event(w->mem, e, hipEventDefault)) return rce;
+        for (int q = 0; q < 2; q++) std::swap(w->ev_seed[slot][q], w->ev_seed[from][q]);
+    }
+    *seed_dev = dst;
+    return H2V_OK;
+}
 // One pass of a mixed call on `st`: the gather kernels behind the tables, then the schedule of the workspace's kind.
 static int mixed_enqueue(const MixedCall &c, MixedTables &t, h2v_workspace *w, hipStream_t st) {
     MixedWs *m = w->mixed;
@@ -3517,6 +3474,10 @@ static int mixed_enqueue(const MixedCall &c, MixedTables &t, h2v_workspace *w, h
     if (hipGetLastError() != hipSuccess) return fail(H2V_E_DEVICE, "launch of the gather kernels failed");
     MixedUnits mu;
     mixed_units(c, t, m, mu);
+    if (c.keyed) {      // (the records of the pass: one per phase-1 unit, then the tail's - on either kind of workspace)
+        if (int rc = mixed_seed(c, t, w, st, mu.phase1.size() + 1, &mu.fc.seed_dev)) return rc;
+        mu.tail.seed_dev = mu.fc.seed_dev; mu.tail.seed_xor7 = 0;
+    }
     return w->n_lanes ? mixed_run_laned(c, mu, w, st) : mixed_run_ordinary(mu, w, st);
 }
 static int run_mixed(const MixedCall &c, h2v_workspace *w, hipStream_t st) {
@@ -3529,6 +3490,7 @@ static int run_mixed(const MixedCall &c, h2v_workspace *w, hipStream_t st) {
     if ((rc = mixed_tables(c, w, st, t))) return rc;
     // from here on the block is in use: THE return records its end on `st` (after an error: drained first)
     rc = mixed_enqueue(c, t, w, st);
+    if (rc == H2V_OK && c.keyed) rec_last(w).derived = true;      // (the tail's record: the call's last, whose slot holds the seed)
     if (rc) rc = drain_after_error(w, rc);
     if (hipEventRecord(t.sl->done, st) != hipSuccess && !rc) rc = fail(H2V_E_DEVICE, "event record failed");
     return rc;
@@ -3536,7 +3498,7 @@ static int run_mixed(const MixedCall &c, h2v_workspace *w, hipStream_t st) {
 // argument checks shared by the forms; on success (and b->n != 0) c holds the plans, the flags and the partition
 static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, const uint8_t *accept, uint32_t flags, MixedCall *c) {
     h2vmixed::Partition *pt = &c->pt;
-    c->plans = plans;
+    c->plans = plans; c->plan_of = b ? b->plan_of : nullptr;
     c->rlc = (flags & H2V_MIXED_RLC) != 0; c->fold = (flags & H2V_MIXED_FOLD_MSM) != 0; c->grouped = (flags & H2V_MIXED_GROUPED) != 0;
     if (!plans || !b || !accept) return fail(H2V_E_ARG, "null argument");
     const uint32_t max_plans = (flags & H2V_MIXED_GROUPED) ? H2V_MIXED_GROUPED_MAX_PLANS : H2V_MIXED_MAX_PLANS;
@@ -3615,7 +3577,12 @@ static int run_mixed_call(const MixedCall &c, h2v_workspace *w, hipStream_t st, 
     if (fold_failed) *fold_failed = true;
     MixedCall second = c;
     second.fold = second.grouped = false;
-    return run_mixed(second, w, st);
+    const uint64_t first_tail = rec_last(w).call;
+    if (c.keyed) second.seed_prev = w->seed_ring + (size_t)(first_tail % h2v_workspace::RING) * 8;      // (derived once per call)
+    rc = run_mixed(second, w, st);
+    if (c.keyed && rc == H2V_OK)
+        if (CallRec *r = rec_at(w, first_tail)) r->derived = false;      // (the seed and its events are the second tail's now)
+    return rc;
 }
 // the layouts of a call on workspace ws, on the host before anything is enqueued: the fold form's, then the grouped form's
 static int mixed_layouts(MixedCall &c, const h2v_workspace *ws) {
@@ -3638,8 +3605,8 @@ static uint32_t agg_mixed_flags(const h2v_rlc_opts *opts) {
 }
 extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
                                        h2v_workspace *ws, void *stream, uint32_t flags, const h2v_rlc_opts *opts) {
-    if (int rcs = seed_flags_mixed(opts)) return rcs;
     MixedCall c;
+    if (int rcs = seed_flags_mixed(opts, (flags & H2V_MIXED_RLC) != 0, &c.keyed)) return rcs;
     int rc = mixed_args(plans, n_plans, b, accept, flags, &c);
     if (rc || b->n == 0) return rc;
     if (!ws) return fail(H2V_E_ARG, "the device form needs a workspace (h2v_workspace_create_multi over the listed plans)");
@@ -3647,7 +3614,7 @@ extern "C" int h2v_verify_mixed_device(const h2v_plan *const *plans, uint32_t n_
     HIPCHK(hipSetDevice(plans[0]->device));
     if ((rc = mixed_ws_check(plans, n_plans, b->n, ws))) return rc;
     if ((rc = null_stream_check(ws, stream))) return rc;
-    if (c.rlc && (rc = rlc_seed(opts, c.seed))) return rc;      // (the device forms: the seed before the layouts)
+    if (c.rlc && !c.keyed && (rc = rlc_seed(opts, c.seed))) return rc;      // (the device forms: the seed before the layouts)
     if ((rc = mixed_layouts(c, ws))) return rc;
     if ((rc = mixed_call_io(c, {b->n, b->proofs, b->proof_off, b->instances, b->committed}, nullptr, accept, status, nullptr))) return rc;
     return run_mixed_call(c, ws, (hipStream_t)stream, nullptr);
@@ -3663,8 +3630,8 @@ static int agg_ensure(h2v_workspace *ws, uint32_t n_parts, hipStream_t st, AggSl
 static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_mixed_batch *b, uint8_t *accept, uint32_t *status,
                       h2v_workspace *ws, uint32_t flags, const h2v_rlc_opts *opts, int *fell_back, uint8_t *agg_pair, h2v_aggregate_info *info) {
     if (fell_back) *fell_back = 0;
-    if (int rcs = seed_flags_mixed(opts)) return rcs;
     MixedCall c;
+    if (int rcs = seed_flags_mixed(opts, (flags & H2V_MIXED_RLC) != 0, &c.keyed)) return rcs;
     const h2vmixed::Partition &pt = c.pt;
     int rc = mixed_args(plans, n_plans, b, accept, flags, &c);
     if (rc || b->n == 0) return rc;
@@ -3681,7 +3648,7 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
     hostcall::ResultBlock R;
     rc = mixed_ws_check(plans, n_plans, n, ws);
     if (rc == H2V_OK) rc = mixed_layouts(c, ws);                 // (the host form: the layouts before the seed)
-    if (rc == H2V_OK && c.rlc) rc = rlc_seed(opts, c.seed);
+    if (rc == H2V_OK && c.rlc && !c.keyed) rc = rlc_seed(opts, c.seed);
     if (rc == H2V_OK) rc = mixed_ensure(ws, pt);
     if (rc == H2V_OK) rc = result_ensure(ws, hostcall::Call::MIXED, n, &R, ws->mixed);
     if (rc == H2V_OK) {
@@ -3698,10 +3665,11 @@ static int mixed_host(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
             if ((rc = agg_ensure(ws, 1, ws->hs, &as)) == H2V_OK) rc = mixed_call_io(c, in, goff.data(), d_accept, d_status, as.parts);
             if (rc == H2V_OK) rc = run_mixed(c, ws, ws->hs);
             if (rc == H2V_OK) rc = agg_export(ws, as, 1, d + R.pairs.off, ws->hs);
-            if (rc == H2V_OK) rc = agg_info_fill(info, c.seed, 0, 1, c.lay.n_r);
+            if (rc == H2V_OK) rc = agg_info_fill(info, c.seed, 0, 1, c.lay.n_r, c.keyed);
         } else if ((rc = mixed_call_io(c, in, goff.data(), d_accept, d_status, nullptr)) == H2V_OK) rc = run_mixed_call(c, ws, ws->hs, &fold_failed);
         rc = host_call_tail(ws, rc, {{agg_pair, R.pairs, "the pair"}, {accept, R.accept, "accept[]"}, {status, R.status, "the status words"}},
                             c.rlc && !agg_pair, fell_back, "mixed-call", fold_failed);
+        if (rc == H2V_OK && agg_pair && info && c.keyed) rc = h2v_workspace_seed_used(ws, 0, info->seed_used);      // (the stream is synchronised: the derived seed is there)
     }
     if (tmp) h2v_workspace_free(tmp);
     return rc;
@@ -3767,15 +3735,18 @@ static int agg_info_fill(h2v_aggregate_info *info, const uint32_t seed[8], uint3
 }
 static void agg_pair_inf(uint8_t pair[96]) { memset(pair, 0, 96); pair[0] = 0xc0; pair[48] = 0xc0; }
 // (mixed: h2v_aggregate_mixed(_device), the one call that knows H2V_RLC_GROUPED)
-static int agg_flags(const h2v_rlc_opts *o, bool mixed = false) {
-    if (mixed)
-        if (int rc = seed_flags_mixed(o)) return rc;
-    if (o && (o->flags & ~(H2V_RLC_SEED_GIVEN | H2V_RLC_ONE_STREAM | H2V_RLC_FOLD_PAIRS | (mixed ? H2V_RLC_GROUPED : H2V_RLC_SEED_TRANSCRIPT)))) return fail(H2V_E_ARG, "unknown flag in h2v_rlc_opts.flags");
+static int agg_flags(const h2v_rlc_opts *o, bool mixed = false, bool *keyed = nullptr) {
+    if (mixed) {
+        if (int rc = seed_flags_mixed(o, true, keyed)) return rc;
+    } else if (int rc = seed_keyed_refused(o)) return rc;
+    if (o && (o->flags & ~(H2V_RLC_SEED_GIVEN | H2V_RLC_ONE_STREAM | H2V_RLC_FOLD_PAIRS | (mixed ? H2V_RLC_GROUPED | H2V_RLC_SEED_KEYED : H2V_RLC_SEED_TRANSCRIPT))))
+        return fail(H2V_E_ARG, "unknown flag in h2v_rlc_opts.flags");
     bool derive;
-    return seed_flags(o, &derive);
+    return mixed ? (int)H2V_OK : seed_flags(o, &derive);
 }
 // the argument rules of the single-key forms that need no device
 static int agg_batch_args(const h2v_plan *p, const h2v_batch *b, const uint8_t *pair, const uint8_t *included, const h2v_rlc_opts *opts) {
+    if (int rck = seed_keyed_refused(opts)) return rck;      // (named before anything else: the mixed calls' flag in a single-key call)
     if (!p) return fail(H2V_E_ARG, "null argument: plan");
     if (!b) return fail(H2V_E_ARG, "null argument: batch");
     if (!pair) return fail(H2V_E_ARG, "null argument: pair");
@@ -3856,8 +3827,8 @@ extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t
                                           uint32_t *status, h2v_workspace *ws, void *stream, const h2v_rlc_opts *opts, h2v_aggregate_info *info) {
     if (!pair) return fail(H2V_E_ARG, "null argument: pair");
     if (b && b->n == 0 && !included) included = pair;      // (nothing to write; mixed_args wants a pointer)
-    if (int rca = agg_flags(opts, true)) return rca;
     MixedCall c;
+    if (int rca = agg_flags(opts, true, &c.keyed)) return rca;
     int rc = mixed_args(plans, n_plans, b, included, agg_mixed_flags(opts), &c);
     if (rc) return rc;
     if ((uintptr_t)pair & 3) return fail(H2V_E_ARG, "pair must be 4-byte aligned");
@@ -3868,15 +3839,15 @@ extern "C" int h2v_aggregate_mixed_device(const h2v_plan *const *plans, uint32_t
     HIPCHK(hipSetDevice(ws->device));
     if ((rc = b->n ? mixed_ws_check(plans, n_plans, b->n, ws) : mixed_no_host_batch(ws))) return rc;   // (no proofs: no plan to fit)
     if ((rc = null_stream_check(ws, stream))) return rc;
-    if ((rc = rlc_seed(opts, c.seed))) return rc;
+    if (!c.keyed && (rc = rlc_seed(opts, c.seed))) return rc;
     AggSlot as{};
-    if (b->n == 0) {
+    if (b->n == 0) {      // (keyed: nothing is derived from no proofs - seed_used stays zero)
         agg_info_fill(info, c.seed, 0, 1, 0);
         if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
         return agg_export(ws, as, 0, pair, (hipStream_t)stream);
     }
     if ((rc = mixed_layouts(c, ws))) return rc;
-    agg_info_fill(info, c.seed, 0, 1, c.lay.n_r);
+    agg_info_fill(info, c.seed, 0, 1, c.lay.n_r, c.keyed);
     if ((rc = agg_ensure(ws, 1, (hipStream_t)stream, &as))) return rc;
     if ((rc = mixed_call_io(c, {b->n, b->proofs, b->proof_off, b->instances, b->committed}, nullptr, included, status, as.parts))) return rc;
     // (run_mixed, not run_mixed_call: no verdict comes down, the stream is not synchronised and nothing runs a second time)
@@ -3892,7 +3863,8 @@ extern "C" int h2v_aggregate_mixed(const h2v_plan *const *plans, uint32_t n_plan
         MixedCall none;
         if (int rc = mixed_args(plans, n_plans, b, pair, mflags, &none)) return rc;
         uint32_t seed[8] = {};
-        if (int rc = rlc_seed(opts, seed)) return rc;
+        if (!(opts && (opts->flags & H2V_RLC_SEED_KEYED)))      // (keyed: nothing is derived from no proofs - seed_used stays zero)
+            if (int rc = rlc_seed(opts, seed)) return rc;
         agg_info_fill(info, seed, 0, 1, 0);
         agg_pair_inf(pair);
         return H2V_OK;

@@ -14,12 +14,13 @@
 #include <stdint.h>
 
 // the batch coefficient of call position `at` as four dwords; every lane of the block calls it (the hash works through sbuf)
-// (a: the kernel's argument struct - its seed stays in the argument segment, read at a run-time index by scalar loads)
+// (a: the kernel's argument struct - its seed stays in the argument segment, read at a run-time index by scalar loads; with
+// a.seed_dev - a call with keyed leaves, H2V_RLC_SEED_KEYED - the words come from device memory instead: seed_word, no chunk tweak)
 template <class A> H2V_DI void mixed_coeff(uint32_t (&r)[4], const A &a, uint32_t at, bool good, uint32_t *sbuf, int lane) {
     Transcript tr;
     tr_init(tr);
 #pragma unroll 1
-    for (int k = 0; k < 32; k++) tr_put(tr, sbuf, lane, (a.seed[k >> 2] >> (8 * (k & 3))) & 0xffu);
+    for (int k = 0; k < 32; k++) tr_put(tr, sbuf, lane, (seed_word(a.seed, a.seed_dev, 0u, k >> 2) >> (8 * (k & 3))) & 0xffu);
 #pragma unroll 1
     for (int k = 0; k < 4; k++) tr_put(tr, sbuf, lane, (at >> (8 * k)) & 0xffu);
     uint64_t h[4];
@@ -50,6 +51,7 @@ struct MixedTermsArgs {
     uint32_t *vk_part;          // the chunk's first block: ceil(n / 64) x n_fix x 8 (Montgomery)
     uint8_t *good;              // by position
     uint32_t *status_out;       // by position (H2V_ST_BAD_POINT folded in)
+    const uint32_t *seed_dev;   // NULL: `seed` above, bit for bit; else the call's derived seed in device memory (8 dwords)
 };
 
 extern "C" __global__ void __launch_bounds__(64)
@@ -108,6 +110,7 @@ struct MixedPairTermsArgs {
     const uint8_t *good;        // by position
     uint32_t seed[8];
     uint32_t *r_scal, *r_pts, *l_scal, *l_pts;
+    const uint32_t *seed_dev;   // as MixedTermsArgs
 };
 extern "C" __global__ void __launch_bounds__(64)
 k_mixed_pair_terms(MixedPairTermsArgs a) {

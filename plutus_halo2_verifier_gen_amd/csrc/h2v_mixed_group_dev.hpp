@@ -93,6 +93,7 @@ struct GroupTermsArgs {
     uint32_t *vk_part;           // the call's per-block sums from Fr record 0 on
     uint8_t *good;
     uint32_t *status_out;
+    const uint32_t *seed_dev;    // as MixedTermsArgs: NULL, or the call's derived seed in device memory
 };
 // what the terms body reads of a sub-batch (MixedTermsArgs without the seed)
 struct MixedTermsView {

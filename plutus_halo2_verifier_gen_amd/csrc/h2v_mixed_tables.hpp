@@ -5,6 +5,7 @@
 //
 //   offsets (n + 1 x 8) | inst_src | inst_dst (n x 8) | perm | len_cap | inst_len | ci_src | ci_dst (n x 4) | fold plans |
 //   per grouped range:  group records | comb[0] | comb[1] | dec | terms  (n_groups + 1 x 4 each)
+//   a call with keyed leaves (H2V_RLC_SEED_KEYED), behind everything else:  plan_idx (n x 4, by grouped position) | key_tags (n_plans x 32)
 // every region at a multiple of 16, an absent one (no fold layout, no grouped range) empty.  The fold-plan entries hold device
 // pointers: the caller writes them into the region named here, and gives its size in bytes - the device struct is not known here.
 #pragma once
@@ -25,10 +26,12 @@ struct RangeRegions { Region recs, comb[2], dec, terms; };
 struct TableBlock {
     Region offsets, inst_src, inst_dst, perm, len_cap, inst_len, ci_src, ci_dst, fold;
     std::vector<RangeRegions> range;
+    Region plan_idx, key_tags;              // keyed leaves only (else empty): behind every other region
     size_t extent;                          // bytes of the block
 };
-// n proofs, fold_bytes of fold-plan table (0: none), n_ranges grouped ranges of n_groups[c] groups each
-static inline TableBlock table_block(uint64_t n, size_t fold_bytes, const uint32_t *n_groups, size_t n_ranges) {
+// n proofs, fold_bytes of fold-plan table (0: none), n_ranges grouped ranges of n_groups[c] groups each; keyed_plans: the plans
+// listed in a call with keyed leaves (0: no such call - the two regions are empty and the block is what it was without them)
+static inline TableBlock table_block(uint64_t n, size_t fold_bytes, const uint32_t *n_groups, size_t n_ranges, size_t keyed_plans = 0) {
     TableBlock b{};
     size_t at = 0;
     auto put = [&at](Region &g, size_t bytes) { g = {at, bytes}; at += up16(bytes); };
@@ -44,6 +47,7 @@ static inline TableBlock table_block(uint64_t n, size_t fold_bytes, const uint32
         put(r.recs, ng * sizeof(H2vGroupRec));
         put(r.comb[0], (ng + 1) * 4); put(r.comb[1], (ng + 1) * 4); put(r.dec, (ng + 1) * 4); put(r.terms, (ng + 1) * 4);
     }
+    put(b.plan_idx, keyed_plans ? (size_t)n * 4 : 0); put(b.key_tags, keyed_plans * 32);
     b.extent = at;
     return b;
 }
@@ -53,9 +57,11 @@ struct RangeInfo { uint32_t n_groups, n, blocks_comb[2], units, blocks_terms, ld
 
 // Packs the partition, the grouped proof offsets when the host knows them (host_off: n + 1 entries, or NULL - the region is then
 // left for the device to fill) and every range's group tables into `block` (B.extent bytes; B = table_block(pt.n, .., the ranges'
-// rec.size())).  The fold region is the caller's.  info[c]: range c's counts.
+// rec.size())).  The fold region is the caller's.  info[c]: range c's counts.  Keyed leaves (B.key_tags is not empty): plan_of
+// (pt.n entries, the caller's order) gives the plan index of every grouped position, key_tags the 32 bytes of every listed plan.
 static inline void pack_tables(uint8_t *block, const TableBlock &B, const h2vmixed::Partition &pt, const uint64_t *host_off,
-                               const std::vector<h2vmixed::GroupTables> &gt, std::vector<RangeInfo> &info) {
+                               const std::vector<h2vmixed::GroupTables> &gt, std::vector<RangeInfo> &info,
+                               const uint32_t *plan_of = nullptr, const uint8_t *key_tags = nullptr) {
     auto put = [block](const Region &g, const void *src) { if (g.bytes) memcpy(block + g.off, src, g.bytes); };
     if (host_off) put(B.offsets, host_off);
     put(B.inst_src, pt.inst_src.data()); put(B.inst_dst, pt.inst_dst.data());
@@ -72,5 +78,8 @@ static inline void pack_tables(uint8_t *block, const TableBlock &B, const h2vmix
         put(r.terms, t.terms.data()); i.blocks_terms = t.terms.back();
         i.n_groups = (uint32_t)t.rec.size(); i.n = t.n;
     }
+    if (B.plan_idx.bytes && plan_of)
+        for (uint32_t g = 0; g < pt.n; g++) memcpy(block + B.plan_idx.off + (size_t)g * 4, &plan_of[pt.perm[g]], 4);
+    if (key_tags) put(B.key_tags, key_tags);
 }
 }   // namespace mixedtab

@@ -1,6 +1,6 @@
 // The body of k_mixed_terms and k_mixed_terms_grouped: block MT_BLK (64 proofs) of the sub-batch `a` - MixedTermsArgs itself, or the
 // view the grouped kernel makes of its block's group (h2v_mixed_group_dev.hpp); MT_SEED: the kernel's argument struct, which
-// holds the call's seed (mixed_coeff reads it there at a run-time index).  Included into both kernels' bodies, so that the per-plan
+// holds the call's seed (mixed_coeff reads it there at a run-time index, or through its seed_dev).  Included into both kernels' bodies, so that the per-plan
 // kernel is compiled from the very text it always had; the includer defines MT_BLK and MT_SEED and declares sbuf.
     const int lane = threadIdx.x;
     const uint32_t i = MT_BLK * 64 + lane;

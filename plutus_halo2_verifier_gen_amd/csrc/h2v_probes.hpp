@@ -148,6 +148,46 @@ extern "C" int h2v_probe_batch_seed(int device, uint32_t form, const uint8_t key
     HIPCHK(hipDeviceSynchronize());
     return ds.download(seed, 32) ? fail(H2V_E_DEVICE, "download failed") : (int)H2V_OK;
 }
+// the digest kernels of a keyed seed (form 3) alone, through seed_launch as mixed_seed queues them: the partition and the table
+// regions are the calls' own (h2v_mixed.hpp, h2v_mixed_tables.hpp), the plans are (key_tag, n_pi, n_ci) triples.  The proof bytes
+// go up from byte 0 of the caller's buffer to the largest offset, so that the offsets decide the alignment the leaf kernel meets.
+extern "C" int h2v_probe_mixed_seed(int device, uint32_t n_plans, const uint8_t *key_tags, const uint32_t *n_pi, const uint32_t *n_ci,
+                                    const h2v_mixed_batch *b, uint8_t seed[32]) {
+    int rc = pick_device(device);
+    if (rc) return rc;
+    if (!key_tags || !n_pi || !n_ci || !b || !seed || !b->proofs || !b->proof_off || !b->plan_of) return fail(H2V_E_ARG, "null argument");
+    h2vseed::Tree t;
+    if (b->n == 0 || !h2vseed::tree(b->n, &t)) return fail(H2V_E_ARG, "n out of range (1 .. 2^22)");
+    if (n_plans == 0 || n_plans > H2V_MIXED_GROUPED_MAX_PLANS) return fail(H2V_E_ARG, "n_plans out of range");
+    std::vector<h2vmixed::PlanShape> shapes(n_plans);
+    for (uint32_t k = 0; k < n_plans; k++) {
+        if (n_ci[k] > 1 || n_pi[k] > (1u << 16)) return fail(H2V_E_ARG, "bad argument");
+        shapes[k] = {0u, n_pi[k], n_ci[k]};
+    }
+    h2vmixed::Partition pt;
+    std::string err;
+    if (!h2vmixed::partition(shapes.data(), n_plans, b->plan_of, b->n, pt, &err)) return fail(H2V_E_ARG, err);
+    if ((pt.inst_total && !b->instances) || (pt.ci_total && !b->committed)) return fail(H2V_E_ARG, "bad argument");
+    const mixedtab::TableBlock B = mixedtab::table_block(pt.n, 0, nullptr, 0, n_plans);
+    std::vector<uint8_t> block(B.extent);
+    std::vector<mixedtab::RangeInfo> info;
+    mixedtab::pack_tables(block.data(), B, pt, nullptr, {}, info, b->plan_of, key_tags);
+    uint64_t proof_bytes = 0;
+    for (uint64_t i = 0; i <= b->n; i++) proof_bytes = b->proof_off[i] > proof_bytes ? b->proof_off[i] : proof_bytes;
+    DevBuf dt, dp, doff, di, dc, dd, ds;
+    if (dt.upload(block.data(), B.extent) || dp.upload(b->proofs, proof_bytes ? (size_t)proof_bytes : 1u) || doff.upload(b->proof_off, ((size_t)b->n + 1) * 8) ||
+        (pt.inst_total && di.upload(b->instances, (size_t)pt.inst_total)) || (pt.ci_total && dc.upload(b->committed, (size_t)pt.ci_total * 48)) ||
+        dd.alloc((size_t)t.extent * 32) || ds.alloc(32))
+        return fail(H2V_E_DEVICE, "probe setup failed");
+    auto tab = [&](const mixedtab::Region &g) { return dt.as<uint8_t>() + g.off; };
+    const SeedMixedLeafArgs ma = {pt.n, (const uint32_t *)tab(B.perm), (const uint64_t *)tab(B.inst_src), (const uint32_t *)tab(B.inst_len), (const uint32_t *)tab(B.ci_src),
+                                  (const uint32_t *)tab(B.plan_idx), (const uint32_t *)tab(B.key_tags), dp.as<uint8_t>(), doff.as<uint64_t>(), di.as<uint8_t>(), dc.as<uint8_t>(), {}, nullptr};
+    SeedJob j = {h2vseed::FORM_MIXED, b->n, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, dd.as<uint32_t>(), ds.as<uint32_t>()};
+    j.mixed = &ma;
+    if ((rc = seed_launch(j, nullptr))) return rc;
+    HIPCHK(hipDeviceSynchronize());
+    return ds.download(seed, 32) ? fail(H2V_E_DEVICE, "download failed") : (int)H2V_OK;
+}
 extern "C" int h2v_probe_blake2b_ex(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint32_t digest_len, const uint8_t *key,
                                     uint32_t key_len, uint8_t *digests) {
     int rc = pick_device(device);

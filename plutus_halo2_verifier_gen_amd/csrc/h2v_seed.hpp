@@ -4,6 +4,7 @@
 // h2v_seed_dev.hpp; the rule itself is stated in DESIGN.md section 17 and restated in plutus_halo2_verifier_gen_amd/seed.py.
 //
 //   leaf_i = B(TAG leaf || LE32(|inst|) || LE32(|ci|) || LE32(|proof|) || LE32(0) || inst || ci || proof)
+//   mleaf_i = B(TAG mleaf || the same four lengths || key_tag(plan of proof i) || inst || ci || proof)      form 3 (H2V_RLC_SEED_KEYED)
 //   node   = B(TAG node || LE32(level) || LE32(m) || LE64(index) || child_0 .. child_{m-1})      64-ary, level 1 over the leaves
 //   seed   = B(TAG root || LE32(form) || LE32(0) || LE64(n) || key_tag || top node)
 // B: unkeyed blake2b-256.  A tag is its ASCII string zero-padded to 16 bytes.
@@ -16,13 +17,15 @@ namespace h2vseed {
 constexpr uint32_t ARITY = 64;
 constexpr uint64_t MAX_N = 1ull << 22;       // the RLC forms' own limit
 constexpr uint32_t MAX_LEVELS = 4;           // 64^4 >= 2^22
-constexpr uint32_t FORM_PROOFS = 1, FORM_PAIRS = 2;
+constexpr uint32_t FORM_PROOFS = 1, FORM_PAIRS = 2, FORM_MIXED = 3;   // (3: keyed leaves, the mixed-key calls; its root hashes 32 zero bytes as key_tag)
 constexpr size_t TAG_BYTES = 16, DIGEST_BYTES = 32;
 constexpr char TAG_KEY[] = "h2v-seed-key/1";
 constexpr char TAG_LEAF[] = "h2v-seed-leaf/1";
+constexpr char TAG_MLEAF[] = "h2v-seed-mleaf/1";      // exactly 16 bytes: the keyed leaf's header is 64
 constexpr char TAG_NODE[] = "h2v-seed-node/1";
 constexpr char TAG_ROOT[] = "h2v-seed-root/1";
-static_assert(sizeof TAG_KEY <= TAG_BYTES + 1 && sizeof TAG_LEAF <= TAG_BYTES + 1 && sizeof TAG_NODE <= TAG_BYTES + 1 && sizeof TAG_ROOT <= TAG_BYTES + 1,
+static_assert(sizeof TAG_KEY <= TAG_BYTES + 1 && sizeof TAG_LEAF <= TAG_BYTES + 1 && sizeof TAG_NODE <= TAG_BYTES + 1 && sizeof TAG_ROOT <= TAG_BYTES + 1 &&
+                  sizeof TAG_MLEAF <= TAG_BYTES + 1,
               "a tag fits its 16 bytes");
 
 // a tag as the four little-endian dwords the kernels put in front of a message

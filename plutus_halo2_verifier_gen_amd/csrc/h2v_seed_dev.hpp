@@ -3,6 +3,8 @@
 //
 //   k_seed_leaves   one leaf per lane: blake2b-256 over the leaf's header and the proof's own bytes (instance row, committed
 //                   row, proof bytes), fed as whole 128-byte blocks
+//   k_seed_leaves_mixed   the same for the keyed leaves of a mixed-key call (H2V_RLC_SEED_KEYED, form 3): every leaf carries the
+//                   key tag of its own proof's plan; the per-proof facts come from the call's table block
 //   k_seed_nodes    one node per lane over up to 64 child digests; launched once per level, and the launch whose level holds ONE
 //                   node goes on to hash the root and stores the call's seed
 //
@@ -77,6 +79,73 @@ k_seed_leaves(SeedLeafArgs a) {
             else if (p < 32) w = p == 16 ? a.inst_len : p == 20 ? a.ci_len : p == 24 ? plen : 0u;
             else if (p < at_ci) w = seed_sec_dword(inst, (uint32_t)p - 32u, a.inst_len);
             else w = seed_sec_dword(ci, (uint32_t)p - at_ci, a.ci_len);
+            sbuf[d * 64 + lane] = w;
+        }
+        const bool last = b + 1 == n_blocks;
+        b2_compress_lds(h, sbuf + lane, last ? total : (b + 1) * 128, last);
+    }
+    uint32_t *out = a.digests + (size_t)i * 8;
+#pragma unroll
+    for (int q = 0; q < 4; q++) { out[2 * q] = (uint32_t)h[q]; out[2 * q + 1] = (uint32_t)(h[q] >> 32); }
+}
+
+// Form 3, keyed leaves (H2V_RLC_SEED_KEYED, the mixed-key calls): a leaf binds the key of its own proof,
+//   mleaf_i = B(TAG mleaf || LE32(|inst|) || LE32(|ci|) || LE32(|proof|) || LE32(0) || key_tag(plan of i) || inst || ci || proof)
+// - a 64-byte header, so every section still starts at a multiple of 4 in the hashed stream and the block fill is k_seed_leaves' -
+// and what differs per proof comes from the call's table block (h2v_mixed_tables.hpp): the instance offset and length, the
+// committed index (H2V_MIXED_NONE: none), the plan index, and the table of key tags by plan.
+//
+// ITERATION.  Lane l of block b takes GROUPED position g = 64 b + l and stores to digests[perm[g]]; the alternative - call positions
+// with inverse tables - was weighed and left.  Grouped: the six table reads per lane are coalesced and are the partition's own
+// arrays (only the plan index is new); the digest store is one whole aligned 32-byte sector per lane whatever its address, so
+// scattering it costs no extra traffic; the two proof_off reads are gathered, 16 bytes per lane once per leaf.  Above all the lanes
+// of a wave then hold proofs of ONE plan (but at a boundary), so their leaves have the same number of blocks and the wave runs no
+// longer than its own proofs need - in the caller's order a wave runs as long as the longest proof of any key among its 64.
+// The seed does not depend on the iteration order: leaf i lies at digests[i] either way.
+struct SeedMixedLeafArgs {
+    uint32_t n;
+    const uint32_t *perm;                         // grouped position -> position in the call
+    const uint64_t *inst_src;                     // byte offset of the proof's instance bytes in `inst`
+    const uint32_t *inst_len, *ci_src, *plan_idx; // bytes; index of the 48-byte committed row or H2V_MIXED_NONE; plan in the call's list
+    const uint32_t *key_tags;                     // 8 dwords per listed plan
+    const uint8_t *proofs;
+    const uint64_t *off;                          // the CALLER's proof_off, n + 1 entries, by position in the call
+    const uint8_t *inst, *ci;
+    uint32_t tag[4];
+    uint32_t *digests;                            // leaf i (position in the call) at dwords [8 i, 8 i + 8)
+};
+extern "C" __global__ void __launch_bounds__(64)
+k_seed_leaves_mixed(SeedMixedLeafArgs a) {
+    __shared__ uint32_t sbuf[32 * 64];
+    const int lane = threadIdx.x;
+    const uint32_t g = blockIdx.x * 64 + lane;
+    if (g >= a.n) return;
+    const uint32_t i = a.perm[g];
+    const uint64_t lo = a.off[i], hi = a.off[i + 1];
+    const uint32_t plen = hi > lo ? (hi - lo > 0xffffffffull ? 0xffffffffu : (uint32_t)(hi - lo)) : 0u;      // (descending: empty)
+    const uint32_t inst_len = a.inst_len[g], ci_at = a.ci_src[g], ci_len = ci_at == 0xffffffffu ? 0u : 48u;
+    const uint8_t *const proof = a.proofs + lo;
+    const uint8_t *const inst = inst_len ? a.inst + a.inst_src[g] : nullptr;
+    const uint8_t *const ci = ci_len ? a.ci + (size_t)ci_at * 48 : nullptr;
+    const uint32_t *const kt = a.key_tags + (size_t)a.plan_idx[g] * 8;
+    const uint32_t at_ci = 64u + inst_len, at_proof = at_ci + ci_len;
+    const uint64_t total = (uint64_t)at_proof + plen;
+    const uint64_t n_blocks = (total + 127) / 128;
+    uint64_t h[8];
+    seed_b2_init(h);
+#pragma unroll 1
+    for (uint64_t b = 0; b < n_blocks; b++) {
+#pragma unroll 1
+        for (uint32_t d = 0; d < 32; d++) {
+            const uint64_t p = b * 128 + 4ull * d;
+            uint32_t w = 0;
+            if (p >= at_proof) {
+                if (p < total) w = seed_sec_dword(proof, (uint32_t)(p - at_proof), plen);
+            } else if (p < 16) w = a.tag[p >> 2];
+            else if (p < 32) w = p == 16 ? inst_len : p == 20 ? ci_len : p == 24 ? plen : 0u;
+            else if (p < 64) w = kt[(p - 32) >> 2];
+            else if (p < at_ci) w = seed_sec_dword(inst, (uint32_t)p - 64u, inst_len);
+            else w = seed_sec_dword(ci, (uint32_t)p - at_ci, ci_len);
             sbuf[d * 64 + lane] = w;
         }
         const bool last = b + 1 == n_blocks;

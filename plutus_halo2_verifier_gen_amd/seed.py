@@ -11,12 +11,25 @@ B is unkeyed blake2b-256, TAG(s) the ASCII string s zero-padded to 16 bytes, int
 
 form 1: proofs (inst_i = the proof's instance bytes, ci_i = its committed bytes, proof_i = its bytes as given, short or long);
 form 2: pairs (h2v_check_pairs_rlc: |inst| = |ci| = 0, proof_i = the 96 pair bytes).  The coefficients follow from the seed as
-from any other: r_i = the low 128 bits of B(seed' || LE32(pos)), 1 if that is 0 (tests/agg_model.py::coeff)."""
+from any other: r_i = the low 128 bits of B(seed' || LE32(pos)), 1 if that is 0 (tests/agg_model.py::coeff).
+
+form 3, "keyed leaves" (H2V_RLC_SEED_KEYED, the mixed-key calls; frozen): every leaf binds the key of its own
+proof, and the root binds none -
+
+    mleaf_i = B(TAG("h2v-seed-mleaf/1") || LE32(|inst_i|) || LE32(|ci_i|) || LE32(|proof_i|) || LE32(0)
+                || key_tag(plans[plan_of[i]]) || inst_i || ci_i || proof_i)
+    seed    = B(TAG("h2v-seed-root/1") || LE32(3) || LE32(0) || LE64(n) || 32 zero bytes || top node)
+
+with the same node and tree.  The leaves enter in the caller's order (the position the coefficients are drawn from); inst_i is the
+proof's own 32 * n_pi(plan) bytes, ci_i its 48 committed bytes or empty, proof_i its bytes as given (a descending pair of offsets:
+empty).  The seed does not depend on the order in which the plans are listed, on listed plans without a proof or on the call's
+flags; it does depend on which key every position has; and a one-plan mixed call does NOT share its seed with the form 1 call on
+the same bytes."""
 import hashlib
 import struct
 
 ARITY = 64
-FORM_PROOFS, FORM_PAIRS = 1, 2
+FORM_PROOFS, FORM_PAIRS, FORM_MIXED = 1, 2, 3
 MAX_N = 1 << 22
 
 
@@ -93,3 +106,35 @@ def pairs_seed(tag: bytes, pairs: bytes) -> bytes:
     """form 2: n = len(pairs) / 96 pairs"""
     assert len(pairs) % 96 == 0
     return batch_seed(tag, FORM_PAIRS, None, None, [bytes(pairs[96 * i:96 * i + 96]) for i in range(len(pairs) // 96)])
+
+
+# ---- form 3: keyed leaves (the mixed-key calls)
+def mixed_leaf(tag: bytes, inst: bytes, ci: bytes, proof: bytes) -> bytes:
+    """tag: key_tag of the proof's own plan"""
+    assert len(tag) == 32
+    return B(TAG("h2v-seed-mleaf/1") + struct.pack("<IIII", len(inst), len(ci), len(proof), 0) + bytes(tag) + bytes(inst) + bytes(ci) + bytes(proof))
+
+
+def mixed_seed(tags, plan_of, instances, committed, proofs) -> bytes:
+    """tags: key_tag per listed plan; plan_of[i]: the plan of proof i; instances / committed / proofs: one bytes object per proof in
+    the caller's order (committed[i] = b"" or None for a plan without a committed instance)"""
+    n = len(proofs)
+    assert 1 <= n <= MAX_N and len(plan_of) == n and len(instances) == n and len(committed) == n
+    leaves = [mixed_leaf(tags[plan_of[i]], instances[i], committed[i] or b"", proofs[i]) for i in range(n)]
+    return B(TAG("h2v-seed-root/1") + struct.pack("<IIQ", FORM_MIXED, 0, n) + bytes(32) + root(leaves))
+
+
+def mixed_seed_flat(tags, shapes, plan_of, proofs: bytes, proof_off, instances: bytes = b"", committed: bytes = b"") -> bytes:
+    """form 3 from the flat buffers of an h2v_mixed_batch: shapes[k] = (n_pi, n_ci) of listed plan k; proof i =
+    proofs[proof_off[i] : proof_off[i + 1]] (descending: empty), its 32 * n_pi instance bytes and - n_ci = 1 - 48 committed bytes
+    follow those of the proofs before it"""
+    n = len(proof_off) - 1
+    inst, ci, prf, at_i, at_c = [], [], [], 0, 0
+    for i in range(n):
+        n_pi, n_ci = shapes[plan_of[i]]
+        inst.append(bytes((instances or b"")[at_i:at_i + 32 * n_pi]))
+        at_i += 32 * n_pi
+        ci.append(bytes((committed or b"")[at_c:at_c + 48]) if n_ci else b"")
+        at_c += 48 if n_ci else 0
+        prf.append(bytes(proofs[proof_off[i]:proof_off[i + 1]]) if proof_off[i + 1] > proof_off[i] else b"")
+    return mixed_seed(tags, plan_of, inst, ci, prf)
