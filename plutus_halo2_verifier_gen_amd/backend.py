@@ -131,7 +131,7 @@ EXPORTS = [
     "h2v_probe_mixed_seed",
 ]
 # exported for the tests alone and not part of include/h2v.h (csrc/h2v_probes.hpp)
-PROBE_ONLY_EXPORTS = ["h2v_probe_device_memory"]
+PROBE_ONLY_EXPORTS = ["h2v_probe_device_memory", "h2v_probe_six_call"]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
 TRANSCRIPT_CARDANO_BLAKE2B_256, TRANSCRIPT_BLAKE2B_512 = 0, 1
@@ -228,6 +228,7 @@ def lib():
         L.h2v_probe_mixed_seed.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.h2v_plan_key_tag.argtypes = [C.c_void_p, C.c_void_p]
         L.h2v_probe_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
+        L.h2v_probe_six_call.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 7
         L.h2v_aggregate_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RlcOpts),
                                           C.POINTER(AggregateInfo)]
         L.h2v_aggregate_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -950,6 +951,48 @@ def probe_f28_dot2(op: int, a, b=None, c=None, d=None, device: int = 0):
     if field:
         return [list(out[14 * i:14 * i + 14]) for i in range(n)]
     return [(tuple(list(out[44 * i + 14 * j:44 * i + 14 * j + 14]) for j in range(3)), int(out[44 * i + 42])) for i in range(n)]
+
+
+# h2v_probe_six_call ops (csrc/h2v_pairing_six.hpp: SIX_PROBE_*)
+SIX_MUL, SIX_SQR, SIX_LINE1, SIX_LINE2, SIX_PROD2, SIX_ROUND, SIX_CSQR, SIX_CONJ, SIX_FROB, SIX_INV, SIX_FOLD = range(11)
+PROBE_SIX_GUARD = 10          # H2V_PROBE_SIX_GUARD: groups' worth of preset records behind the last group
+
+
+class SixCall:
+    """What h2v_probe_six_call brought back.  parts: per group the 12 limb vectors (14 integers each) re, im of coefficients 0..5 as
+    six_result yields them - for SIX_PROD2 the 8 vectors of slots 22..29.  ok: per group the inverter's flag (SIX_INV; else None).
+    guard_clean: everything behind group n - 1, and every word of a record that the op does not write, is still the preset."""
+    __slots__ = ("parts", "ok", "guard_clean")
+
+
+def probe_six_call(op: int, a, b=None, pts=None, flags=None, lines=None, csqr_n: int = 0, device: int = 0) -> SixCall:
+    """One six-lane engine call per group on raw limb vectors.  a: per group 12 vectors of 14 limbs; b: the same (SIX_MUL; the lines:
+    vectors 0..7 are the T slots, the rest is ignored); pts: per group 4 vectors PX1, PY1, PX2, PY2; flags: per group bit 0 skip1,
+    bit 1 skip2; lines: 8 vectors [A0, A1, B0, B1] of loop 1, then loop 2, for the whole launch.  Arguments go to the library as they
+    are given: what an op needs and does not get is the library's H2V_E_ARG."""
+    n = len(a)
+
+    def pack(groups, per_group):
+        if groups is None:
+            return None
+        flat = [l for g in groups for v in g for l in v]
+        assert len(flat) == len(groups) * per_group * 14
+        return (C.c_uint32 * len(flat))(*flat)
+
+    cap = n + PROBE_SIX_GUARD
+    out = (C.c_uint32 * (cap * 168))()
+    ok = (C.c_uint32 * cap)()
+    check(lib().h2v_probe_six_call(device, op, n, csqr_n, pack(a, 12), pack(b, 12), pack(pts, 4),
+                                   (C.c_uint32 * n)(*flags) if flags is not None else None, pack([lines], 8) if lines is not None else None, out, ok))
+    r = SixCall()
+    n_vec = 8 if op == SIX_PROD2 else 12
+    r.parts = [[list(out[168 * i + 14 * j:168 * i + 14 * j + 14]) for j in range(n_vec)] for i in range(n)]
+    r.ok = [int(ok[i]) for i in range(n)] if op == SIX_INV else None
+    preset = 0xa5a5a5a5
+    r.guard_clean = (all(v == preset for v in out[168 * n:]) and all(v == preset for v in ok[n:]) and
+                     all(out[168 * i + q] == preset for i in range(n) for q in range(14 * n_vec, 168)) and
+                     (op == SIX_INV or all(v == preset for v in ok[:n])))
+    return r
 
 
 def probe_quad_madd(p_xy, q_xy, neg: bool, device: int = 0):

@@ -27,7 +27,9 @@
 // from the squaring to the round's last line and falls back with the next squaring; the loop's staging takes re <= 12p,
 // im <= 7p (gen_six_tables.py: miller_round_bounds), and the value is folded once after the loop.
 // Tables and the headroom argument: tools/gen_six_tables.py (value-level check against big-integer Fp12 arithmetic and a
-// limb-level model of this code with the column bounds asserted).  Program, line tables, semantics: h2v_pairing_coop.hpp.
+// limb-level model of this code with the column bounds asserted).  The device code is held to that model call by call: k_probe_six
+// (below; h2v_probe_six_call) runs ONE engine call per group on raw limb vectors, and tests/test_six_engine_calls_gpu.py compares every
+// result limb for limb with the model on operands at the stated bounds.  Program, line tables, semantics: h2v_pairing_coop.hpp.
 //
 // LDS: 38 operand slots of 56 bytes per proof (14 limbs, no padding: 8-byte reads), 23 KB per wave - six or seven waves per
 // CU, and at most 256 registers per lane, so that a SIMD holds a second wave beside this one: a lone wave issues a
@@ -526,29 +528,18 @@ H2V_DI void six_line_store(const uint2 v, int lane) {
     dst[1] = v.y;
 }
 
-// The engines return nothing and take no pointer into their caller's frame, so LLVM would mark their call sites `tail`; a
-// callee with a `tail`-marked call site is excluded from the interprocedural register allocation's no-callee-saved-registers
-// form (TargetFrameLowering::isSafeForNoCSROpt), and six_kara - which uses every register - would save and restore all 112
-// callee-saved VGPRs through private memory on every call (seen: 106 stores + 106 loads per call).  The callers therefore
-// opt out of tail-call marking.
-extern "C" __global__ void __launch_bounds__(64, 2) H2V_NO_TAIL_MARK
-k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, const uint8_t *__restrict__ valid, const uint8_t *__restrict__ valid_sub,
-              const uint32_t *__restrict__ er_jac, const uint32_t *__restrict__ el_jac /* folded el (recursion) or NULL */,
-              uint32_t *__restrict__ status, uint8_t *__restrict__ accept, uint32_t *__restrict__ dbg) {
-    const int lane = threadIdx.x;
+// What every kernel of this engine starts with (k_pairing_six, and k_probe_six, which runs single engine calls for the tests):
+// the lane's place - ten groups of six lanes, lanes 60..63 shadowing group 9 - (returns the group), and the operand tables and
+// the shared zero operand in LDS.  The callers' first barrier publishes both.
+H2V_DI int six_lane_setup(Six &c, const int lane) {
     const int grp6 = (lane * 43) >> 8;          // lane / 6 for lane < 64
-    Six c;
     c.act = lane < 6 * SIX_GROUPS;
     const int grp = c.act ? grp6 : SIX_GROUPS - 1;
     c.k = c.act ? lane - 6 * grp6 : lane - 6 * SIX_GROUPS;
     c.grp_off = SIX_GRP_OFF + grp * SIX_GROUP_DW;
-    const int leader = grp * 6;
-    const bool is_leader = c.act && c.k == 0;
-    const uint32_t i = blockIdx.x * SIX_GROUPS + grp;
-    const bool live = i < n;
-    const uint32_t ii = live ? i : n - 1;       // dead groups shadow the last proof, never write
-    const uint32_t slots = H2V_SLOTS(plan);
-
+    return grp;
+}
+H2V_DI void six_tables_to_lds(const int lane) {
     {   // operand tables -> LDS
         const uint32_t *src[5] = {reinterpret_cast<const uint32_t *>(&SIX_TAB_MUL[0][0]), reinterpret_cast<const uint32_t *>(&SIX_TAB_SQR[0][0]),
                                   reinterpret_cast<const uint32_t *>(&SIX_TAB_LINE1[0][0]), reinterpret_cast<const uint32_t *>(&SIX_TAB_LINE2[0][0]),
@@ -559,6 +550,34 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
             for (int q = lane; q < off[t + 1] - off[t]; q += 64) coop_lds[SIX_TAB_OFF + off[t] + q] = src[t][q];
     }
     if (lane < 14) coop_lds[(SIX_SLOT_ZERO - SIX_SHARED_BASE) * SIX_SLOT_DW + lane] = 0u;   // the shared zero operand
+}
+// The first pass of six_prod2 by lane: lane k < 4 takes part k & 1 of a = A xP of loop 1 + (k >> 1), lanes 4, 5 the parts of
+// b = B yP of loop 1 (the second pass, lanes 0 and 1, those of b of loop 2: six_prod2 itself).  Macros, not a function: six_prod2 is
+// compiled for the slot ranges its call sites hand it (an x operand in a shared slot, a y operand in the group's: six_slot_dw's
+// choice is then made at compile time), and that analysis runs before any function is inlined - it has to see constants here.
+#define SIX_PROD2_XS1(k) ((k) < 4 ? ((((k) >> 1) & 1) ? SIX_SLOT_LN2 : SIX_SLOT_LN1) + ((k) & 1) : SIX_SLOT_LN1 + 2 + ((k) & 1))
+#define SIX_PROD2_YS1(k) ((k) < 4 ? ((((k) >> 1) & 1) ? SIX_SLOT_PX2 : SIX_SLOT_PX1) : SIX_SLOT_PY1)
+
+// The engines return nothing and take no pointer into their caller's frame, so LLVM would mark their call sites `tail`; a
+// callee with a `tail`-marked call site is excluded from the interprocedural register allocation's no-callee-saved-registers
+// form (TargetFrameLowering::isSafeForNoCSROpt), and six_kara - which uses every register - would save and restore all 112
+// callee-saved VGPRs through private memory on every call (seen: 106 stores + 106 loads per call).  The callers therefore
+// opt out of tail-call marking.
+extern "C" __global__ void __launch_bounds__(64, 2) H2V_NO_TAIL_MARK
+k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, const uint8_t *__restrict__ valid, const uint8_t *__restrict__ valid_sub,
+              const uint32_t *__restrict__ er_jac, const uint32_t *__restrict__ el_jac /* folded el (recursion) or NULL */,
+              uint32_t *__restrict__ status, uint8_t *__restrict__ accept, uint32_t *__restrict__ dbg) {
+    const int lane = threadIdx.x;
+    Six c;
+    const int grp = six_lane_setup(c, lane);
+    const int leader = grp * 6;
+    const bool is_leader = c.act && c.k == 0;
+    const uint32_t i = blockIdx.x * SIX_GROUPS + grp;
+    const bool live = i < n;
+    const uint32_t ii = live ? i : n - 1;       // dead groups shadow the last proof, never write
+    const uint32_t slots = H2V_SLOTS(plan);
+
+    six_tables_to_lds(lane);
     // ---- leader: status, the two G1 arguments (el ; -er normalised to affine)
     uint32_t st = 0;
     uint32_t flags = 0;  // bit0: el is infinity, bit1: er is infinity
@@ -618,9 +637,7 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
             SixF2 f = vars[COOP_VAR_F];
             int ln = 0;
             uint2 cn = six_line_share(plan.six_norm28, 0, lane);
-            const int u = (c.k >> 1) & 1, part = c.k & 1;
-            const int xs1 = c.k < 4 ? (u ? SIX_SLOT_LN2 : SIX_SLOT_LN1) + part : SIX_SLOT_LN1 + 2 + part;
-            const int ys1 = c.k < 4 ? (u ? SIX_SLOT_PX2 : SIX_SLOT_PX1) : SIX_SLOT_PY1;
+            const int xs1 = SIX_PROD2_XS1(c.k), ys1 = SIX_PROD2_YS1(c.k);
 #pragma unroll 1
             for (int bit = 62; bit >= 0; bit--) {
                 f = six_sqr(c, f);
@@ -719,4 +736,126 @@ k_pairing_six(H2vDevPlan plan, uint32_t n, const uint32_t *__restrict__ pts, con
         status[i] = st;
         accept[i] = st == 0 ? 1 : 0;
     }
+}
+
+// ---- dev probe: ONE engine call per group, on raw limb vectors, through the functions the pairing calls (h2v_probe_six_call;
+// tests/test_six_engine_calls_gpu.py holds every result to the limb model of tools/gen_six_tables.py, limb for limb, with the
+// operands ON the bounds the headroom argument states).  Launch as k_pairing_six's: one wave per block, ten groups, lanes 60..63
+// shadowing group 9, SIX_LDS_BYTES of dynamic LDS; a dead group shadows the last live one and writes nothing.
+//   a, b      n x 12 vectors of 14 dwords: parts (re, im) of coefficients 0..5, as the lane stages them (carried, or for FOLD not)
+//             b: MUL's second operand; LINE1 / LINE2: vectors 0..7 are the T slots 22..29; else unread
+//   pts       n x 4 vectors: the point slots PX1, PY1, PX2, PY2 (PROD2, ROUND)
+//   flags     n words: bit 0 skip1, bit 1 skip2 (LINE1, LINE2, ROUND)
+//   lines16   the constants of one line of both loops as the plan-load table has them: 8 slots [A0, A1, B0, B1] x 2 of 16 dwords
+//             (14 limbs and 2 of padding), copied into the wave-shared slots by six_line_share / six_line_store (PROD2, ROUND)
+//   out       n x 6 x 28 dwords, lane k of group i at (6 i + k) 28: what six_result yields, re then im.  PROD2: the group's slots
+//             22..29 at 168 i + 14 j instead.        ok_out    n words, INV alone: the leader's `ok`
+#define SIX_PROBE_MUL 0
+#define SIX_PROBE_SQR 1
+#define SIX_PROBE_LINE1 2
+#define SIX_PROBE_LINE2 3
+#define SIX_PROBE_PROD2 4
+#define SIX_PROBE_ROUND 5
+#define SIX_PROBE_CSQR 6
+#define SIX_PROBE_CONJ 7
+#define SIX_PROBE_FROB 8
+#define SIX_PROBE_INV 9
+#define SIX_PROBE_FOLD 10
+#define SIX_PROBE_N_OPS 11
+#define SIX_PROBE_OUT_DW (6 * 2 * SIX_SLOT_DW)
+H2V_DI void six_probe_vec(F28 &r, const uint32_t *__restrict__ src, const size_t vec) {
+#pragma unroll
+    for (int q = 0; q < SIX_SLOT_DW; q++) r.l[q] = src[vec * SIX_SLOT_DW + q];
+}
+extern "C" __global__ void __launch_bounds__(64, 2) H2V_NO_TAIL_MARK
+k_probe_six(int op, uint32_t n, int csqr_n, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ pts,
+            const uint32_t *__restrict__ flags_in, const uint32_t *__restrict__ lines16, uint32_t *__restrict__ out, uint32_t *__restrict__ ok_out) {
+    const int lane = threadIdx.x;
+    Six c;
+    const int grp = six_lane_setup(c, lane);
+    const bool is_leader = c.act && c.k == 0;
+    const uint32_t i = blockIdx.x * SIX_GROUPS + grp;
+    const bool live = i < n;
+    const uint32_t ii = live ? i : n - 1;
+    six_tables_to_lds(lane);
+    const bool lines = op == SIX_PROBE_LINE1 || op == SIX_PROBE_LINE2, round = op == SIX_PROBE_PROD2 || op == SIX_PROBE_ROUND;
+    SixF2 x;
+    six_probe_vec(x.re, a, (size_t)ii * 12 + 2 * c.k);
+    six_probe_vec(x.im, a, (size_t)ii * 12 + 2 * c.k + 1);
+    if (lines && c.act && c.k < 4) {           // the T slots, two per lane
+        F28 t;
+        six_probe_vec(t, b, (size_t)ii * 12 + 2 * c.k);
+        six_store(six_slot(c, SIX_SLOT_T + 2 * c.k), t);
+        six_probe_vec(t, b, (size_t)ii * 12 + 2 * c.k + 1);
+        six_store(six_slot(c, SIX_SLOT_T + 2 * c.k + 1), t);
+    }
+    if (round && is_leader) {
+        static_assert(SIX_SLOT_PY1 == SIX_SLOT_PX1 + 1 && SIX_SLOT_PX2 == SIX_SLOT_PX1 + 2 && SIX_SLOT_PY2 == SIX_SLOT_PX1 + 3, "the point slots are one run");
+        for (int q = 0; q < 4; q++) {
+            F28 t;
+            six_probe_vec(t, pts, (size_t)ii * 4 + q);
+            six_store(six_slot(c, SIX_SLOT_PX1 + q), t);
+        }
+    }
+    const uint32_t flags = (lines || op == SIX_PROBE_ROUND) ? flags_in[ii] : 0u;
+    const bool skip1 = (flags & 1) != 0, skip2 = (flags & 2) != 0;
+    const int xs1 = SIX_PROD2_XS1(c.k), ys1 = SIX_PROD2_YS1(c.k);
+    __syncthreads();
+
+    SixF2 r = x;
+    bool ok = true;
+    switch (op) {
+    case SIX_PROBE_MUL: {
+        SixF2 y;
+        six_probe_vec(y.re, b, (size_t)ii * 12 + 2 * c.k);
+        six_probe_vec(y.im, b, (size_t)ii * 12 + 2 * c.k + 1);
+        r = six_mul(c, x, y);
+    } break;
+    case SIX_PROBE_SQR: r = six_sqr(c, x); break;
+    case SIX_PROBE_LINE1: r = six_line<1>(c, x, skip1); break;
+    case SIX_PROBE_LINE2: r = six_line<2>(c, x, skip2); break;
+    case SIX_PROBE_PROD2:
+    case SIX_PROBE_ROUND: {
+        if (op == SIX_PROBE_ROUND) r = six_sqr(c, x);
+        six_line_store(six_line_share(lines16, 0, lane), lane);
+        __syncthreads();
+        six_prod2(c, xs1, ys1);
+        if (op == SIX_PROBE_ROUND) {
+            r = six_line<1>(c, r, skip1);
+            r = six_line<2>(c, r, skip2);
+        } else {
+            __syncthreads();
+            six_load_pair(r.re.l, r.im.l, six_slot(c, SIX_SLOT_T + c.k), six_slot(c, SIX_SLOT_T + 6 + (c.k & 1)));
+        }
+    } break;
+    case SIX_PROBE_CSQR: r = six_csqr(c, x, csqr_n); break;
+    case SIX_PROBE_CONJ: r = six_conj(c, x); break;
+    case SIX_PROBE_FROB: r = six_frob(c, x); break;
+    case SIX_PROBE_INV: {
+        SixRegs fr;
+        fr.re = f28_pack(x.re);
+        fr.im = f28_pack(x.im);
+        r = six_unpack(six_inv_raw(c, fr, ok));
+    } break;
+    case SIX_PROBE_FOLD:
+        f28_fold(r.re);
+        f28_fold(r.im);
+        break;
+    default: break;
+    }
+    if (!live || !c.act) return;
+    if (op == SIX_PROBE_PROD2) {               // r: (T slot k, T slot 6 + (k & 1))
+#pragma unroll
+        for (int q = 0; q < SIX_SLOT_DW; q++) out[(size_t)i * SIX_PROBE_OUT_DW + c.k * SIX_SLOT_DW + q] = r.re.l[q];
+        if (c.k < 2)
+#pragma unroll
+            for (int q = 0; q < SIX_SLOT_DW; q++) out[(size_t)i * SIX_PROBE_OUT_DW + (6 + c.k) * SIX_SLOT_DW + q] = r.im.l[q];
+        return;
+    }
+#pragma unroll
+    for (int q = 0; q < SIX_SLOT_DW; q++) {
+        out[((size_t)i * 6 + c.k) * 2 * SIX_SLOT_DW + q] = r.re.l[q];
+        out[((size_t)i * 6 + c.k) * 2 * SIX_SLOT_DW + SIX_SLOT_DW + q] = r.im.l[q];
+    }
+    if (op == SIX_PROBE_INV && c.k == 0) ok_out[i] = ok ? 1u : 0u;
 }

@@ -111,6 +111,41 @@ extern "C" int h2v_probe_f28_dot2(int device, int op, uint32_t n, const uint32_t
     HIPCHK(hipDeviceSynchronize());
     return dout.download(out, out_b) ? fail(H2V_E_DEVICE, "download failed") : (int)H2V_OK;
 }
+// ONE call of the six-lane pairing engine per group (k_probe_six in h2v_pairing_six.hpp has the ops and the buffer layouts), on raw
+// 14-dword limb vectors, so that operands can sit ON the bounds the engine's headroom argument states.  a: n x 12 vectors, always;
+// b: n x 12 (MUL; LINE1 / LINE2: vectors 0..7 are the T slots); pts: n x 4 and lines: 8 vectors [A0, A1, B0, B1] of loop 1, then of
+// loop 2 (PROD2, ROUND); flags: n words (LINE1, LINE2, ROUND); csqr_n: the run length (CSQR, 1..64).  out: (n + GUARD) x 168 dwords and
+// ok_out (INV; else optional): n + GUARD words, GUARD = one block's ten groups - both preset to 0xA5 bytes and copied back whole, so
+// what a dead group of the last wave or a shadow lane wrote shows behind group n - 1.  For tests; not in include/h2v.h.
+#define H2V_PROBE_SIX_GUARD SIX_GROUPS
+extern "C" int h2v_probe_six_call(int device, int op, uint32_t n_groups, uint32_t csqr_n, const uint32_t *a, const uint32_t *b, const uint32_t *pts,
+                                  const uint32_t *flags, const uint32_t *lines, uint32_t *out, uint32_t *ok_out) {
+    int rc = pick_device(device);
+    if (rc) return rc;
+    if (op < 0 || op >= SIX_PROBE_N_OPS) return fail(H2V_E_ARG, "unknown op");
+    if (n_groups == 0 || n_groups > (1u << 16)) return fail(H2V_E_ARG, "n_groups out of range (1 .. 65536)");
+    if (op == SIX_PROBE_CSQR && (csqr_n == 0 || csqr_n > 64)) return fail(H2V_E_ARG, "CSQR: the run length is 1 .. 64");
+    const bool lines_op = op == SIX_PROBE_LINE1 || op == SIX_PROBE_LINE2, round_op = op == SIX_PROBE_PROD2 || op == SIX_PROBE_ROUND;
+    if (!a || !out || ((op == SIX_PROBE_MUL || lines_op) && !b) || (round_op && (!pts || !lines)) || ((lines_op || op == SIX_PROBE_ROUND) && !flags) ||
+        (op == SIX_PROBE_INV && !ok_out))
+        return fail(H2V_E_ARG, "a buffer this op reads or writes is missing");
+    const size_t n = n_groups, cap = n + H2V_PROBE_SIX_GUARD, vec = SIX_SLOT_DW * 4;
+    uint32_t lines16[8 * 16] = {};
+    if (lines)
+        for (int s = 0; s < 8; s++) memcpy(lines16 + 16 * s, lines + SIX_SLOT_DW * s, vec);
+    DevBuf da, db, dp, df, dl, dout, dok;
+    if (da.upload(a, n * 12 * vec) || (b ? db.upload(b, n * 12 * vec) : db.alloc(8)) || (pts ? dp.upload(pts, n * 4 * vec) : dp.alloc(8)) ||
+        (flags ? df.upload(flags, n * 4) : df.alloc(8)) || dl.upload(lines16, sizeof lines16) || dout.alloc(cap * SIX_PROBE_OUT_DW * 4) || dok.alloc(cap * 4))
+        return fail(H2V_E_DEVICE, "probe setup failed");
+    HIPCHK(hipMemset(dout.p, 0xa5, cap * SIX_PROBE_OUT_DW * 4));
+    HIPCHK(hipMemset(dok.p, 0xa5, cap * 4));
+    hipLaunchKernelGGL(k_probe_six, dim3((n_groups + SIX_GROUPS - 1) / SIX_GROUPS), dim3(64), SIX_LDS_BYTES, nullptr, op, n_groups, (int)csqr_n,
+                       da.as<uint32_t>(), db.as<uint32_t>(), dp.as<uint32_t>(), df.as<uint32_t>(), dl.as<uint32_t>(), dout.as<uint32_t>(), dok.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if (dout.download(out, cap * SIX_PROBE_OUT_DW * 4) || (ok_out && dok.download(ok_out, cap * 4))) return fail(H2V_E_DEVICE, "download failed");
+    return H2V_OK;
+}
 extern "C" int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint8_t *digests) {
     int rc = pick_device(device);
     if (rc) return rc;
