@@ -131,7 +131,7 @@ EXPORTS = [
     "h2v_probe_mixed_seed",
 ]
 # exported for the tests alone and not part of include/h2v.h (csrc/h2v_probes.hpp)
-PROBE_ONLY_EXPORTS = ["h2v_probe_device_memory", "h2v_probe_six_call"]
+PROBE_ONLY_EXPORTS = ["h2v_probe_device_memory", "h2v_probe_six_call", "h2v_probe_coop_call"]
 
 # transcript hash kinds of a plan (include/h2v.h: H2V_TRANSCRIPT_*; vk.TRANSCRIPT_KINDS)
 TRANSCRIPT_CARDANO_BLAKE2B_256, TRANSCRIPT_BLAKE2B_512 = 0, 1
@@ -229,6 +229,7 @@ def lib():
         L.h2v_plan_key_tag.argtypes = [C.c_void_p, C.c_void_p]
         L.h2v_probe_device_memory.argtypes = [C.c_int, C.POINTER(C.c_uint64)]
         L.h2v_probe_six_call.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 7
+        L.h2v_probe_coop_call.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32] + [C.c_void_p] * 7
         L.h2v_aggregate_batch.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RlcOpts),
                                           C.POINTER(AggregateInfo)]
         L.h2v_aggregate_batch_device.argtypes = [C.c_void_p, C.POINTER(Batch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -992,6 +993,55 @@ def probe_six_call(op: int, a, b=None, pts=None, flags=None, lines=None, csqr_n:
     r.guard_clean = (all(v == preset for v in out[168 * n:]) and all(v == preset for v in ok[n:]) and
                      all(out[168 * i + q] == preset for i in range(n) for q in range(14 * n_vec, 168)) and
                      (op == SIX_INV or all(v == preset for v in ok[:n])))
+    return r
+
+
+# h2v_probe_coop_call: engine shapes and ops (csrc/h2v_pairing_coop.hpp: COOP_PROBE_*)
+COOP_ENGINES = {"normal": 0, "wide": 1, "narrow": 2, "twelve": 3}
+COOP_MUL, COOP_SQR, COOP_CSQR, COOP_LINE1, COOP_LINE2, COOP_PROD, COOP_ROUND, COOP_CONJ, COOP_FROB, COOP_INV = range(10)
+PROBE_COOP_GUARD = 5          # H2V_PROBE_COOP_GUARD: groups' worth of preset records behind the last group
+
+
+class CoopCall:
+    """What h2v_probe_coop_call brought back.  parts: per group the 12 limb vectors (14 integers each) of the call's result, flat order
+    2k + part - for COOP_PROD the 8 vectors of the slots T1, T2.  spare: per group the four T slots the spare lanes wrote (the line
+    ops and COOP_ROUND of the shapes that have spare lanes; else None).  ok: per group the inverter's flag (1 for every other op).
+    lanes_agree: per group, every lane of each pair or quad returned the same limbs.  guard_clean: everything behind group n - 1,
+    and every word of a record that the op does not write, is still the preset."""
+    __slots__ = ("parts", "spare", "ok", "lanes_agree", "guard_clean")
+
+
+def probe_coop_call(engine: str, op: int, a, b=None, pts=None, flags=None, lines=None, csqr_n: int = 0, device: int = 0) -> CoopCall:
+    """One cooperative-engine call per group on raw limb vectors.  a: per group 12 vectors of 14 limbs; b: the same (COOP_MUL; the line
+    ops: vectors 0..3 are the loop's T slots, the rest is ignored); pts: per group 4 vectors PX1, PY1, PX2, PY2; flags: per group bit 0
+    skip1, bit 1 skip2; lines: 4 lines of 8 vectors - loop 1's lines 0 and 1, then loop 2's - for the whole launch.  Arguments go to
+    the library as they are given: what an op needs and does not get is the library's H2V_E_ARG."""
+    n = len(a)
+
+    def pack(groups, per_group):
+        if groups is None:
+            return None
+        flat = [l for g in groups for v in g for l in v]
+        assert len(flat) == len(groups) * per_group * 14
+        return (C.c_uint32 * len(flat))(*flat)
+
+    cap = n + PROBE_COOP_GUARD
+    out = (C.c_uint32 * (cap * 224))()
+    ok = (C.c_uint32 * (cap * 2))()
+    check(lib().h2v_probe_coop_call(device, COOP_ENGINES[engine], op, n, csqr_n, pack(a, 12), pack(b, 12), pack(pts, 4),
+                                    (C.c_uint32 * n)(*flags) if flags is not None else None,
+                                    pack([[v for line in lines for v in line]], 32) if lines is not None else None, out, ok))
+    r = CoopCall()
+    has_spare = op in (COOP_LINE1, COOP_LINE2, COOP_ROUND) and engine != "twelve"
+    n_vec = 8 if op == COOP_PROD else 16 if has_spare else 12
+    vec = lambda i, j: list(out[224 * i + 14 * j:224 * i + 14 * j + 14])
+    r.parts = [[vec(i, j) for j in range(min(n_vec, 12))] for i in range(n)]
+    r.spare = [[vec(i, j) for j in range(12, 16)] for i in range(n)] if has_spare else None
+    r.ok = [int(ok[2 * i]) for i in range(n)]
+    r.lanes_agree = [int(ok[2 * i + 1]) == 1 for i in range(n)]
+    preset = 0xa5a5a5a5
+    r.guard_clean = (all(v == preset for v in out[224 * n:]) and all(v == preset for v in ok[2 * n:]) and
+                     all(out[224 * i + q] == preset for i in range(n) for q in range(14 * n_vec, 224)))
     return r
 
 

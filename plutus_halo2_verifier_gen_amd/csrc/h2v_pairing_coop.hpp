@@ -121,6 +121,13 @@ H2V_DI void coop_load28_pair(uint32_t (&x)[14], uint32_t (&y)[14], const uint32_
 // Each of the two lanes sharing a coefficient reduces its half of the terms on its own: a half is below
 // (6 * 7 * 13 / 2520 + 1) p = 1.22 p for MUL and (3 * 2 * 168 / 2520 + 1) p = 1.4 p for the tripled cyclotomic
 // squaring (p / R < 1/2520), so the engine's result (the sum of the two halves) is below 3p.
+// This argument is restated limb by limb in tests/coop_engine_model.py (staging against the bias tables, the per-lane reduction, the
+// 64-bit columns with every slot at the limb maxima of its (v, lam)) and checked for every op and engine shape by
+// tests/test_coop_engine_model.py: the largest column any lane can reach is 0.643 x 2^64 (MUL and SQR with one lane per coefficient,
+// CSQR with two: 12 x 13 full products of weight 1, or 6 x 13 of weight 2 - no SQR row meets D in more than six terms - plus the
+// reduction), results stay below 2.51p (two lanes), 4.51p (four) and 1.37p / 2.001p (one).  The device code is held to that model
+// call by call: k_probe_coop* (below; h2v_probe_coop_call) runs ONE engine call per group through these functions, and
+// tests/test_coop_engine_calls_gpu.py compares every result limb for limb with the model on operands at the stated bounds.
 
 // out = sum_t X[tab[2t]] * Y[tab[2t+1]]  (mod p), one Montgomery reduction.  NT <= 12 (accumulator headroom).
 // TRIPLE: the column accumulators are multiplied by 3 before the reduction (6 terms * 3 still fits 64 bits).
@@ -202,8 +209,9 @@ H2V_DN F28Regs coop_accumulate(const Coop c, const int tab_row_byte) {
         }
     }
     // value: two halves < 2 * 1.4 p; four quarters < 4 * (3 * 168 / 2520 + 1) p = 4.8 p; one lane: (12 * 7 * 13 / 2520 + 1) p =
-    // 1.43 p (MUL), 1.56 p (SQR), 3.8 p (CSQR, above) (every operand bound of the staging code assumes v <= 6, CONJ and INV
-    // v <= 5); limbs back below 2^28
+    // 1.43 p (MUL), 1.56 p (SQR), 1.03 p (LINE), 1.2 p (CSQR: three terms, not tripled - coop_csqr forms 3 r -/+ 2 g, below 16.6 p,
+    // and folds it below 2p + p / 1024) (every operand bound of the staging code assumes v <= 6, CONJ and INV v <= 5); limbs back
+    // below 2^28
     if (NQ >= 2) f28_carry(r);   // (one lane per coefficient: the limbs left the extraction carried)
     return f28_pack(r);
 }
@@ -477,6 +485,49 @@ H2V_DI F28 coop_inv(const Coop &c, const F28 &f, bool &ok) {
     return f28_unpack(z.a, z.b, z.c, z.d);
 }
 
+// What every kernel of this engine starts with (the pairing kernels below, and k_probe_coop, which runs single engine calls for
+// the tests): the lane's place in its group and the group's slot area (returns the group), the operand tables and the two shared
+// constants of the cyclotomic squaring in LDS.  The callers' first barrier publishes the LDS parts.
+template <bool WIDE, bool NARROW, bool TWELVE>
+H2V_DI int coop_lane_setup(Coop &c, const int lane) {
+    const int grp12 = (lane * 43) >> 9;     // lane / 12 for lane < 64
+    const int grp = WIDE ? 0 : TWELVE ? (grp12 < COOP_GROUPS_TWELVE ? grp12 : COOP_GROUPS_TWELVE - 1) : NARROW ? lane >> 4 : lane >> 5;
+    c.g = TWELVE ? (grp12 < COOP_GROUPS_TWELVE ? lane - 12 * grp12 : 12 + (lane - 12 * COOP_GROUPS_TWELVE)) : lane & 15;
+    c.h = NARROW ? 0 : (lane >> 4) & 1;
+    c.both = NARROW;
+    c.twelve = TWELVE;
+    c.nq = WIDE ? 4 : NARROW ? 1 : 2;
+    c.q = WIDE ? c.h + 2 * (lane >> 5) : c.h;
+    c.grp_off = COOP_GRP_OFF + grp * COOP_GROUP_DW;
+    return grp;
+}
+H2V_DI void coop_tables_to_lds(const int lane) {
+    const uint32_t *t0 = reinterpret_cast<const uint32_t *>(&COOP_TAB_MUL[0][0]);
+    const uint32_t *t1 = reinterpret_cast<const uint32_t *>(&COOP_TAB_LINE1[0][0]);
+    const uint32_t *t2 = reinterpret_cast<const uint32_t *>(&COOP_TAB_LINE2[0][0]);
+    const uint32_t *t3 = reinterpret_cast<const uint32_t *>(&COOP_TAB_CSQR[0][0]);
+    constexpr int n0 = 16 * 2 * COOP_N_MUL_TERMS / 4, n1 = 16 * 2 * COOP_N_LINE_TERMS / 4, n3 = 16 * 2 * COOP_N_CSQR_TERMS / 4;
+    for (int q = lane; q < n0; q += 64) coop_lds[COOP_TAB_OFF + q] = t0[q];
+    for (int q = lane; q < n1; q += 64) { coop_lds[COOP_TAB_OFF + n0 + q] = t1[q]; coop_lds[COOP_TAB_OFF + n0 + n1 + q] = t2[q]; }
+    for (int q = lane; q < n3; q += 64) coop_lds[COOP_TAB_OFF + n0 + 2 * n1 + q] = t3[q];
+    const uint32_t *t4 = reinterpret_cast<const uint32_t *>(&COOP_TAB_SQR[0][0]);
+    constexpr int n4 = 16 * 2 * COOP_N_SQR_TERMS / 4;
+    for (int q = lane; q < n4; q += 64) coop_lds[COOP_TAB_OFF + n0 + 2 * n1 + n3 + q] = t4[q];
+}
+H2V_DI void coop_consts_to_lds(const int lane) {
+    if (lane < 14) {   // the two shared constants of the cyclotomic squaring
+        coop_lds[COOP_SHR_OFF + (COOP_SLOT_C23P - COOP_SHARED_BASE) * COOP_SLOT_DW + lane] = FP_C23P28[lane];
+        coop_lds[COOP_SHR_OFF + (COOP_SLOT_C23N - COOP_SHARED_BASE) * COOP_SLOT_DW + lane] = FP_C23N28[lane];
+    }
+}
+// The twelve-lane kernel's pass of a round's eight products (-lambda) xP: lane g < 8 takes constant g & 3 (nl0, nl1, nxl0, nxl1) of
+// loop 1 + (g >> 2); every lane runs the product, lanes 8..15 store nothing.
+H2V_DI void coop_twelve_prods(const Coop &c) {
+    const int lp = (c.g >> 2) & 1, which = c.g & 3;
+    const F28Regs z = coop_prod(c, (lp ? COOP_SLOT_LN2 : COOP_SLOT_LN1) + which, lp ? COOP_SLOT_PX2 : COOP_SLOT_PX1);
+    if (c.g < 8) coop_store28(coop_slot(c, (lp ? COOP_SLOT_T2 : COOP_SLOT_T1) + which), f28_unpack(z.a, z.b, z.c, z.d));
+}
+
 // dbg (optional): per proof 2 x 12 Fp (canonical, 12 dwords each): f after the Miller loop, f after the final
 // exponentiation; flat order (k, part).
 // The kernel interprets COOP_PROGRAM (coop_program.h: 34 steps since the Miller loop and the exponentiations by x are single
@@ -492,16 +543,8 @@ H2V_DI void pairing_coop_body(const H2vDevPlan &plan, uint32_t n, const uint32_t
     static_assert(!(WIDE && NARROW), "one proof per wave, or four");
     static_assert(!TWELVE || NARROW, "the twelve-lane kernel is the narrow engine, packed");
     const int lane = threadIdx.x;
-    const int grp12 = (lane * 43) >> 9;     // lane / 12 for lane < 64
-    const int grp = WIDE ? 0 : TWELVE ? (grp12 < COOP_GROUPS_TWELVE ? grp12 : COOP_GROUPS_TWELVE - 1) : NARROW ? lane >> 4 : lane >> 5;
     Coop c;
-    c.g = TWELVE ? (grp12 < COOP_GROUPS_TWELVE ? lane - 12 * grp12 : 12 + (lane - 12 * COOP_GROUPS_TWELVE)) : lane & 15;
-    c.h = NARROW ? 0 : (lane >> 4) & 1;
-    c.both = NARROW;
-    c.twelve = TWELVE;
-    c.nq = WIDE ? 4 : NARROW ? 1 : 2;
-    c.q = WIDE ? c.h + 2 * (lane >> 5) : c.h;
-    c.grp_off = COOP_GRP_OFF + grp * COOP_GROUP_DW;
+    const int grp = coop_lane_setup<WIDE, NARROW, TWELVE>(c, lane);
     const int leader = TWELVE ? grp * 12 : NARROW ? grp * 16 : grp * 32;  // lane (g = 0, h = 0) of the group
     const bool is_leader = lane == leader;
     const uint32_t i = WIDE ? bid : bid * (TWELVE ? COOP_GROUPS_TWELVE : NARROW ? COOP_GROUPS_NARROW : COOP_GROUPS_PER_WAVE) + grp;
@@ -509,20 +552,7 @@ H2V_DI void pairing_coop_body(const H2vDevPlan &plan, uint32_t n, const uint32_t
     const uint32_t ii = live ? i : n - 1;  // dead groups shadow the last proof, never write
     const uint32_t slots = H2V_SLOTS(plan);
 
-    // operand tables -> LDS
-    {
-        const uint32_t *t0 = reinterpret_cast<const uint32_t *>(&COOP_TAB_MUL[0][0]);
-        const uint32_t *t1 = reinterpret_cast<const uint32_t *>(&COOP_TAB_LINE1[0][0]);
-        const uint32_t *t2 = reinterpret_cast<const uint32_t *>(&COOP_TAB_LINE2[0][0]);
-        const uint32_t *t3 = reinterpret_cast<const uint32_t *>(&COOP_TAB_CSQR[0][0]);
-        constexpr int n0 = 16 * 2 * COOP_N_MUL_TERMS / 4, n1 = 16 * 2 * COOP_N_LINE_TERMS / 4, n3 = 16 * 2 * COOP_N_CSQR_TERMS / 4;
-        for (int q = lane; q < n0; q += 64) coop_lds[COOP_TAB_OFF + q] = t0[q];
-        for (int q = lane; q < n1; q += 64) { coop_lds[COOP_TAB_OFF + n0 + q] = t1[q]; coop_lds[COOP_TAB_OFF + n0 + n1 + q] = t2[q]; }
-        for (int q = lane; q < n3; q += 64) coop_lds[COOP_TAB_OFF + n0 + 2 * n1 + q] = t3[q];
-        const uint32_t *t4 = reinterpret_cast<const uint32_t *>(&COOP_TAB_SQR[0][0]);
-        constexpr int n4 = 16 * 2 * COOP_N_SQR_TERMS / 4;
-        for (int q = lane; q < n4; q += 64) coop_lds[COOP_TAB_OFF + n0 + 2 * n1 + n3 + q] = t4[q];
-    }
+    coop_tables_to_lds(lane);
     // ---- leader: status, the two G1 arguments (el ; -er normalised to affine)
     uint32_t st = 0;
     uint32_t flags = 0;  // bit0: el is infinity, bit1: er is infinity
@@ -562,10 +592,7 @@ H2V_DI void pairing_coop_body(const H2vDevPlan &plan, uint32_t n, const uint32_t
     const bool skip1 = (flags & 1) != 0, skip2 = (flags & 2) != 0;
     bool inv_ok = true;
 
-    if (lane < 14) {   // the two shared constants of the cyclotomic squaring
-        coop_lds[COOP_SHR_OFF + (COOP_SLOT_C23P - COOP_SHARED_BASE) * COOP_SLOT_DW + lane] = FP_C23P28[lane];
-        coop_lds[COOP_SHR_OFF + (COOP_SLOT_C23N - COOP_SHARED_BASE) * COOP_SLOT_DW + lane] = FP_C23N28[lane];
-    }
+    coop_consts_to_lds(lane);
     F28 vars[COOP_N_VARS];
     for (int pc = 0; pc < COOP_PROGRAM_LEN; pc++) {
         const uint32_t ins = COOP_PROGRAM[pc];
@@ -620,11 +647,7 @@ H2V_DI void pairing_coop_body(const H2vDevPlan &plan, uint32_t n, const uint32_t
                         coop_stage_line(c, COOP_SLOT_LN1, plan.lines28_sg2, ln, lane);
                         coop_stage_line(c, COOP_SLOT_LN2, plan.lines28_g2, ln, lane);
                         __syncthreads();
-                        {
-                            const int lp = (c.g >> 2) & 1, which = c.g & 3;
-                            const F28Regs z = coop_prod(c, (lp ? COOP_SLOT_LN2 : COOP_SLOT_LN1) + which, lp ? COOP_SLOT_PX2 : COOP_SLOT_PX1);
-                            if (c.g < 8) coop_store28(coop_slot(c, (lp ? COOP_SLOT_T2 : COOP_SLOT_T1) + which), f28_unpack(z.a, z.b, z.c, z.d));
-                        }
+                        coop_twelve_prods(c);
                         const F28 r1 = coop_line<1>(c, f);      // (its staging barrier covers the T slots)
                         if (!skip1 && c.g < 12) f = r1;
                         const F28 r2 = coop_line<2>(c, f);
@@ -788,3 +811,179 @@ k_pairing_rlc_groups(H2vDevPlan plan, const uint32_t *__restrict__ pts_g, const 
         if (i < n_batch) accept[i] = good[i];
     }
 }
+
+// ---- dev probe: ONE engine call per group, on raw limb vectors, through the functions the pairing calls (h2v_probe_coop_call;
+// tests/test_coop_engine_calls_gpu.py holds every result to the limb model of tests/coop_engine_model.py, limb for limb, with the
+// operands ON the bounds the headroom note above states).  Launch as the pairing kernel of the same shape: one wave per block,
+// COOP_LDS_BYTES(groups per wave) of dynamic LDS; a dead group shadows the last live one and writes nothing, and so do lanes
+// 60..63 of the twelve shape.
+//   a, b      n x 12 vectors of 14 dwords, flat order 2k + part: every lane of a coefficient's pair or quad loads the same vector,
+//             spare lanes zero.  b: MUL's second operand; LINE1 / LINE2: vectors 0..3 are the loop's own T slots; else unread
+//   pts       n x 4 vectors: the point slots PX1, PY1, PX2, PY2 (LINE1, LINE2, PROD, ROUND)
+//   flags     n words: bit 0 skip1, bit 1 skip2 (LINE1, LINE2, ROUND) - applied as the Miller loop applies them, to what the line
+//             step's caller keeps
+//   lines     four lines in the plan's format (8 slots x 16 dwords each), staged by coop_stage_line: [0], [1] loop 1's line 0 and 1,
+//             [2], [3] loop 2's (LINE1, LINE2, PROD: lines [0] and [2]; ROUND: [0], [1], [2])
+//   out       n x 16 vectors: 0..11 what the call returned in the lanes q = 0; 12..15 the four T slots the spare lanes wrote (LINE1:
+//             T2, LINE2: T1, ROUND: T1 of loop 1's line 1; not the twelve shape).  PROD: vectors 0..7 are T1 and T2, nothing else
+//   ok_out    n x 2 words: the leader's `ok` (INV; else 1), and whether every lane of each pair or quad returned the same limbs
+#define COOP_PROBE_MUL 0
+#define COOP_PROBE_SQR 1
+#define COOP_PROBE_CSQR 2
+#define COOP_PROBE_LINE1 3
+#define COOP_PROBE_LINE2 4
+#define COOP_PROBE_PROD 5
+#define COOP_PROBE_ROUND 6
+#define COOP_PROBE_CONJ 7
+#define COOP_PROBE_FROB 8
+#define COOP_PROBE_INV 9
+#define COOP_PROBE_N_OPS 10
+#define COOP_PROBE_OUT_DW (16 * 14)
+#define COOP_PROBE_LINE_DW (8 * 16)
+H2V_DI void coop_probe_vec(F28 &r, const uint32_t *__restrict__ src, const size_t vec) {
+#pragma unroll
+    for (int q = 0; q < 14; q++) r.l[q] = src[vec * 14 + q];
+}
+template <bool WIDE, bool NARROW, bool TWELVE>
+H2V_DI void probe_coop_body(int op, uint32_t n, int csqr_n, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ pts,
+                            const uint32_t *__restrict__ flags_in, const uint32_t *__restrict__ lines, uint32_t *__restrict__ out, uint32_t *__restrict__ ok_out) {
+    static_assert(COOP_SLOT_PY1 == COOP_SLOT_PX1 + 1 && COOP_SLOT_PX2 == COOP_SLOT_PX1 + 2 && COOP_SLOT_PY2 == COOP_SLOT_PX1 + 3, "the point slots are one run");
+    static_assert(COOP_SLOT_T2 == COOP_SLOT_T1 + 4, "the T slots are one run");
+    const int lane = threadIdx.x;
+    Coop c;
+    const int grp = coop_lane_setup<WIDE, NARROW, TWELVE>(c, lane);
+    const int leader = TWELVE ? grp * 12 : NARROW ? grp * 16 : grp * 32;
+    const int per_wave = WIDE ? 1 : TWELVE ? COOP_GROUPS_TWELVE : NARROW ? COOP_GROUPS_NARROW : COOP_GROUPS_PER_WAVE;
+    const uint32_t i = blockIdx.x * per_wave + grp;
+    const bool live = i < n;
+    const uint32_t ii = live ? i : n - 1;
+    const bool first = c.q == 0;               // the lane of a pair or quad that loads the group's slots and stores the result
+    coop_tables_to_lds(lane);
+    coop_consts_to_lds(lane);
+    const bool line_op = op == COOP_PROBE_LINE1 || op == COOP_PROBE_LINE2;
+    const bool uses_lines = line_op || op == COOP_PROBE_PROD || op == COOP_PROBE_ROUND;
+    F28 x;
+    f28_set_zero(x);
+    if (c.g < 12) coop_probe_vec(x, a, (size_t)ii * 12 + c.g);
+    // the group's slots the pairing's leader section fills: the loop's T slots (lanes 0..3), the points (4..7), ZERO (8)
+    if (first && c.g < 4 && line_op) {
+        F28 t;
+        coop_probe_vec(t, b, (size_t)ii * 12 + c.g);
+        coop_store28(coop_slot(c, (op == COOP_PROBE_LINE1 ? COOP_SLOT_T1 : COOP_SLOT_T2) + c.g), t);
+    }
+    if (first && c.g >= 4 && c.g < 8 && uses_lines) {
+        F28 t;
+        coop_probe_vec(t, pts, (size_t)ii * 4 + (c.g - 4));
+        coop_store28(coop_slot(c, COOP_SLOT_PX1 + (c.g - 4)), t);
+    }
+    if (first && c.g == 8) {
+        F28 z;
+        f28_set_zero(z);
+        coop_store28(coop_slot(c, COOP_SLOT_ZERO), z);
+    }
+    if (uses_lines) {
+        coop_stage_line(c, COOP_SLOT_LN1, lines, 0, lane);
+        coop_stage_line(c, COOP_SLOT_LN2, lines, 2, lane);
+    }
+    const uint32_t flags = (line_op || op == COOP_PROBE_ROUND) ? flags_in[ii] : 0u;
+    const bool skip1 = (flags & 1) != 0, skip2 = (flags & 2) != 0;
+    __syncthreads();
+
+    F28 r = x;
+    bool ok = true;
+    int t_from = -1;                           // first of the four T slots that go to vectors 12..15
+    switch (op) {
+    case COOP_PROBE_MUL: {
+        F28 y;
+        f28_set_zero(y);
+        if (c.g < 12) coop_probe_vec(y, b, (size_t)ii * 12 + c.g);
+        r = coop_mul(c, x, y);
+    } break;
+    case COOP_PROBE_SQR: r = coop_sqr(c, x); break;
+    case COOP_PROBE_CSQR:
+#pragma unroll 1
+        for (int rep = 0; rep < csqr_n; rep++) r = coop_csqr(c, r);
+        break;
+    case COOP_PROBE_LINE1: {
+        const F28 r1 = coop_line<1>(c, x);
+        if (!skip1 && c.g < 12) r = r1;
+        t_from = COOP_SLOT_T2;
+    } break;
+    case COOP_PROBE_LINE2: {
+        const F28 r2 = coop_line<2>(c, x);
+        if (!skip2 && c.g < 12) r = r2;
+        t_from = COOP_SLOT_T1;
+    } break;
+    case COOP_PROBE_PROD:
+        if (TWELVE) coop_twelve_prods(c);
+        break;
+    case COOP_PROBE_ROUND: {
+        // as COOP_OP_WARMUP and the first round (ln = 0) of COOP_OP_MILLER: pairing_coop_body's lines, mirrored
+        if (!TWELVE) (void)coop_line<2>(c, x);          // only its spare lanes matter: T1 of line 0
+        F28 f = coop_sqr(c, x);
+        if (TWELVE) coop_twelve_prods(c);              // (coop_line's staging barrier covers the T slots)
+        else __syncthreads();
+        const F28 r1 = coop_line<1>(c, f);
+        if (!skip1 && c.g < 12) f = r1;
+        if (!TWELVE) {
+            coop_stage_line(c, COOP_SLOT_LN1, lines, 1, lane);
+            __syncthreads();
+        }
+        const F28 r2 = coop_line<2>(c, f);
+        if (!skip2 && c.g < 12) f = r2;
+        r = f;
+        t_from = COOP_SLOT_T1;
+    } break;
+    case COOP_PROBE_CONJ: r = coop_conj(c, x); break;
+    case COOP_PROBE_FROB: r = coop_frob(c, x); break;
+    case COOP_PROBE_INV: r = coop_inv(c, x, ok); break;
+    default: break;
+    }
+    __syncthreads();                           // the spare lanes' T slots
+    // every lane of a pair or quad holds the call's result: compare with the partners before the first lane stores it
+    bool same = true;
+    if (!NARROW && c.g < 12) {
+#pragma unroll
+        for (int q = 0; q < 14; q++) {
+            same = same && (uint32_t)__shfl_xor((int)r.l[q], 16) == r.l[q];
+            if (WIDE) same = same && (uint32_t)__shfl_xor((int)r.l[q], 32) == r.l[q];
+        }
+    }
+    const unsigned long long bal = __ballot(same);
+    const bool agree = WIDE ? bal == ~0ull : TWELVE ? ((bal >> leader) & 0xfffull) == 0xfffull : NARROW ? ((bal >> leader) & 0xffffull) == 0xffffull : ((bal >> leader) & 0xffffffffull) == 0xffffffffull;
+    ok = __shfl((int)ok, leader) != 0;
+    if (!live || !first) return;
+    uint32_t *rec = out + (size_t)i * COOP_PROBE_OUT_DW;
+    if (op == COOP_PROBE_PROD) {
+        if (c.g < 8) {
+            uint32_t t[14];
+            coop_load28(t, coop_slot(c, COOP_SLOT_T1 + c.g));
+#pragma unroll
+            for (int q = 0; q < 14; q++) rec[c.g * 14 + q] = t[q];
+        }
+    } else if (c.g < 12) {
+#pragma unroll
+        for (int q = 0; q < 14; q++) rec[c.g * 14 + q] = r.l[q];
+        if (c.g < 4 && t_from >= 0 && !TWELVE) {
+            uint32_t t[14];
+            coop_load28(t, coop_slot(c, t_from + c.g));
+#pragma unroll
+            for (int q = 0; q < 14; q++) rec[(12 + c.g) * 14 + q] = t[q];
+        }
+    }
+    if (lane == leader) {
+        ok_out[2 * (size_t)i] = ok ? 1u : 0u;
+        ok_out[2 * (size_t)i + 1] = agree ? 1u : 0u;
+    }
+}
+#define COOP_PROBE_KERNEL(name, ...)                                                                                                                   \
+    extern "C" __global__ void __launch_bounds__(64, 2)                                                                                                \
+    name(int op, uint32_t n, int csqr_n, const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, const uint32_t *__restrict__ pts,           \
+         const uint32_t *__restrict__ flags_in, const uint32_t *__restrict__ lines, uint32_t *__restrict__ out, uint32_t *__restrict__ ok_out) {     \
+        probe_coop_body<__VA_ARGS__>(op, n, csqr_n, a, b, pts, flags_in, lines, out, ok_out);                                                           \
+    }
+COOP_PROBE_KERNEL(k_probe_coop, false, false, false)
+COOP_PROBE_KERNEL(k_probe_coop_wide, true, false, false)
+COOP_PROBE_KERNEL(k_probe_coop_narrow, false, true, false)
+COOP_PROBE_KERNEL(k_probe_coop_twelve, false, true, true)
+#undef COOP_PROBE_KERNEL

@@ -146,6 +146,47 @@ extern "C" int h2v_probe_six_call(int device, int op, uint32_t n_groups, uint32_
     if (dout.download(out, cap * SIX_PROBE_OUT_DW * 4) || (ok_out && dok.download(ok_out, cap * 4))) return fail(H2V_E_DEVICE, "download failed");
     return H2V_OK;
 }
+// ONE call of the cooperative pairing engine per group, in the shape of `engine`: 0 normal (two lanes per coefficient, two groups per
+// wave), 1 wide (four lanes, one group), 2 narrow (one lane, four groups), 3 twelve (one lane, five groups).  k_probe_coop in
+// h2v_pairing_coop.hpp has the ops and the buffer layouts.  a: n x 12 vectors, always; b: n x 12 (MUL; LINE1 / LINE2: vectors 0..3
+// are the loop's T slots); pts: n x 4, lines: 4 x 8 vectors (loop 1's lines 0 and 1, then loop 2's) and flags: n words (LINE1, LINE2,
+// PROD, ROUND; PROD - the twelve shape alone - takes no flags); csqr_n: the run length (CSQR, 1..64).  out: (n + GUARD) x 224 dwords
+// and ok_out: (n + GUARD) x 2 words (`ok`, and whether the lanes of every pair or quad agreed), GUARD = one block's worth of groups
+// at most - both preset to 0xA5 bytes and copied back whole, so what a dead group of the last wave or a spare lane wrote shows.
+// For tests; not in include/h2v.h.
+#define H2V_PROBE_COOP_GUARD COOP_GROUPS_TWELVE
+extern "C" int h2v_probe_coop_call(int device, int engine, int op, uint32_t n_groups, uint32_t csqr_n, const uint32_t *a, const uint32_t *b,
+                                   const uint32_t *pts, const uint32_t *flags, const uint32_t *lines, uint32_t *out, uint32_t *ok_out) {
+    int rc = pick_device(device);
+    if (rc) return rc;
+    if (engine < 0 || engine > 3) return fail(H2V_E_ARG, "unknown engine shape (0 normal, 1 wide, 2 narrow, 3 twelve)");
+    if (op < 0 || op >= COOP_PROBE_N_OPS) return fail(H2V_E_ARG, "unknown op");
+    if (n_groups == 0 || n_groups > (1u << 16)) return fail(H2V_E_ARG, "n_groups out of range (1 .. 65536)");
+    if (op == COOP_PROBE_CSQR && (csqr_n == 0 || csqr_n > 64)) return fail(H2V_E_ARG, "CSQR: the run length is 1 .. 64");
+    if (op == COOP_PROBE_PROD && engine != 3) return fail(H2V_E_ARG, "PROD: the twelve shape alone has a product pass");
+    const bool line_op = op == COOP_PROBE_LINE1 || op == COOP_PROBE_LINE2, uses_lines = line_op || op == COOP_PROBE_PROD || op == COOP_PROBE_ROUND;
+    if (!a || !out || !ok_out || ((op == COOP_PROBE_MUL || line_op) && !b) || (uses_lines && (!pts || !lines)) || ((line_op || op == COOP_PROBE_ROUND) && !flags))
+        return fail(H2V_E_ARG, "a buffer this op reads or writes is missing");
+    const size_t n = n_groups, cap = n + H2V_PROBE_COOP_GUARD, vec = 14 * 4;
+    uint32_t lines16[4 * COOP_PROBE_LINE_DW] = {};
+    if (lines)
+        for (int s = 0; s < 32; s++) memcpy(lines16 + 16 * s, lines + 14 * s, vec);
+    DevBuf da, db, dp, df, dl, dout, dok;
+    if (da.upload(a, n * 12 * vec) || (b ? db.upload(b, n * 12 * vec) : db.alloc(8)) || (pts ? dp.upload(pts, n * 4 * vec) : dp.alloc(8)) ||
+        (flags ? df.upload(flags, n * 4) : df.alloc(8)) || dl.upload(lines16, sizeof lines16) || dout.alloc(cap * COOP_PROBE_OUT_DW * 4) || dok.alloc(cap * 8))
+        return fail(H2V_E_DEVICE, "probe setup failed");
+    HIPCHK(hipMemset(dout.p, 0xa5, cap * COOP_PROBE_OUT_DW * 4));
+    HIPCHK(hipMemset(dok.p, 0xa5, cap * 8));
+    static const struct { void (*k)(int, uint32_t, int, const uint32_t *, const uint32_t *, const uint32_t *, const uint32_t *, const uint32_t *, uint32_t *, uint32_t *); uint32_t per_wave; } shapes[4] = {
+        {k_probe_coop, COOP_GROUPS_PER_WAVE}, {k_probe_coop_wide, 1}, {k_probe_coop_narrow, COOP_GROUPS_NARROW}, {k_probe_coop_twelve, COOP_GROUPS_TWELVE}};
+    const uint32_t per_wave = shapes[engine].per_wave;
+    hipLaunchKernelGGL(shapes[engine].k, dim3((n_groups + per_wave - 1) / per_wave), dim3(64), COOP_LDS_BYTES(per_wave), nullptr, op, n_groups, (int)csqr_n,
+                       da.as<uint32_t>(), db.as<uint32_t>(), dp.as<uint32_t>(), df.as<uint32_t>(), dl.as<uint32_t>(), dout.as<uint32_t>(), dok.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    if (dout.download(out, cap * COOP_PROBE_OUT_DW * 4) || dok.download(ok_out, cap * 8)) return fail(H2V_E_DEVICE, "download failed");
+    return H2V_OK;
+}
 extern "C" int h2v_probe_blake2b(int device, uint32_t n, uint32_t len, const uint8_t *msgs, uint8_t *digests) {
     int rc = pick_device(device);
     if (rc) return rc;

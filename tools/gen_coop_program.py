@@ -70,9 +70,10 @@ def build_program():
     return prog
 
 
-def check_bounds(prog):
+def check_bounds(prog, engine_v=3):
     """Static check of the value bounds the kernel's lazily reduced field relies on (h2v_pairing_coop.hpp): with
-    `v` = the multiple of p a variable may reach, engine results are 3, CONJ needs v <= 5 and gives 6, FROB gives 5,
+    `v` = the multiple of p a variable may reach, engine results are engine_v (3: two lanes per coefficient; the other engine
+    shapes' bounds: tests/test_coop_engine_model.py walks the program with each), CONJ needs v <= 5 and gives 6, FROB gives 5,
     and every staged operand needs v <= 6."""
     v = [None] * N_VARS
     for op, d, a, b in prog:
@@ -82,18 +83,19 @@ def check_bounds(prog):
             v[d] = 1
         elif op == OP_MUL:
             assert v[a] <= 6 and v[b] <= 6
-            v[d] = 3
+            v[d] = engine_v
         elif op == OP_CSQR:
             assert v[a] <= 6 and b >= 1
-            v[d] = 3
+            v[d] = engine_v
         elif op == OP_MSTEP:
             assert v[F] <= 6 and d in (1, 2)
-            v[F] = 3
+            v[F] = engine_v
         elif op == OP_MILLER:
             assert v[F] <= 6
-            v[F] = 3
+            v[F] = engine_v
         elif op == OP_EXPX:
             assert v[a] <= 6          # staged as an operand of the squarings and of the multiplications
+            assert engine_v <= 5      # its closing CONJ takes an engine result
             v[d] = 6                  # conj of an engine result
         elif op == OP_CONJ:
             assert v[a] <= 5, "CONJ of a value that is not an engine / FROB result"
@@ -103,7 +105,7 @@ def check_bounds(prog):
             v[d] = 5
         elif op == OP_INV:
             assert v[a] <= 5
-            v[d] = 3
+            v[d] = engine_v
         elif op == OP_MOV:
             v[d] = v[a]
         elif op == OP_WARMUP:
