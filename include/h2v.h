@@ -436,6 +436,38 @@ int h2v_check_pairs_rlc(const h2v_plan *plan, uint64_t n, const uint8_t *pairs /
                         h2v_workspace *ws /* or NULL */, const h2v_rlc_opts *opts /* or NULL */, int *fell_back /* or NULL */);
 int h2v_check_pairs_rlc_device(const h2v_plan *plan, uint64_t n, const uint8_t *pairs, uint8_t *accept, uint32_t *status,
                                h2v_workspace *ws /* not NULL */, void *stream, const h2v_rlc_opts *opts /* or NULL */);
+/* h2v_check_pairs_multi(_device): ONE batch check over pairs on SEVERAL SRS.  The pairs come grouped in ranges: the first
+ * counts[0] pairs are checked against the SRS (s_g2) of plans[0], the next counts[1] against plans[1], and so on.  accept[] and
+ * status[] are, position for position, what h2v_check_pairs(plans[k], ...) returns for range k alone - the same decoding,
+ * H2V_ST_BAD_POINT for an undecodable pair (coefficient 0), H2V_ST_PAIRING for a failed equation -; the batch check only decides
+ * which kernels produce them.  With r_i = low 128 bits of blake2b-256(seed' || LE32(i)), i the pair's position in the CALL (one
+ * check: no two pairs share a coefficient), never 0,
+ *     prod_k e( sum_{i in range k} r_i L_i , s_g2_k )  ==  e( sum_i r_i R_i , G2 )
+ * holds exactly when every decoded pair passes its own equation, except with probability <= 2^-128 over the seed: one decoding
+ * launch and one coefficient launch over the whole call, bucket MSMs of C + 1 problems (R over all pairs, L_k over range k), and
+ * ONE pairing kernel of C + 1 Miller loops under one final exponentiation.  Passed: accept[i] = "decoded", and nothing else
+ * runs.  Failed: the per-pair kernels of h2v_check_pairs run behind it on the device, range by range against that range's plan;
+ * nothing comes back to the host in between.  The 64-pair group stage of h2v_check_pairs_rlc is left out of this form: groups
+ * would straddle ranges.  The seed follows h2v_check_pairs_rlc's rules (OS randomness; H2V_RLC_SEED_GIVEN for tests).
+ *   counts[k] = 0 is allowed and costs no Miller loop; n = sum counts = 0 is H2V_OK; (inf, inf) pairs pass; a range whose L_k
+ *   sums to infinity skips its loop, R at infinity skips the G2 loop, an all-infinite call passes.  Ranges whose plans are on
+ *   one SRS (h2v_plan_same_srs) are legal and take a loop each; the verdicts do not depend on it.
+ *   H2V_E_ARG: n_plans = 0; a null plan; plans on different devices; H2V_RLC_SEED_TRANSCRIPT, H2V_RLC_SEED_KEYED,
+ *   H2V_RLC_FOLD_PAIRS or H2V_RLC_GROUPED (a derived seed would need a rule that binds each range's key); stream = NULL under
+ *   deferred joins; a host batch in flight on ws.  H2V_E_LIMIT: n_plans > H2V_MULTI_SRS_MAX; n > 2^22 - both decided on the host
+ *   before anything is enqueued.
+ *   WORKSPACE: any workspace h2v_check_pairs would take for the first plan with pairs and n pairs; ws = NULL in the host form: a
+ *   temporary one.  The call keeps a buffer set of its own on the workspace (created by the first such call).  On a laned
+ *   workspace it runs as ONE piece on the caller's stream behind a join of the lanes, like the fold tail of a mixed call: never
+ *   chunked, routed or coalesced.  fell_back, h2v_workspace_rlc_result (one record of kind RLC, msm_terms = n) and the verdict
+ *   word behave as in h2v_check_pairs_rlc.  n_plans = 1 gives the accept[] / status[] of h2v_check_pairs_rlc on the same bytes. */
+#define H2V_MULTI_SRS_MAX 16u
+int h2v_check_pairs_multi(const h2v_plan *const *plans, uint32_t n_plans, const uint64_t *counts /* n_plans */,
+                          const uint8_t *pairs /* (sum counts) * 96 */, uint8_t *accept, uint32_t *status /* or NULL */,
+                          h2v_workspace *ws /* or NULL */, const h2v_rlc_opts *opts /* or NULL */, int *fell_back /* or NULL */);
+int h2v_check_pairs_multi_device(const h2v_plan *const *plans, uint32_t n_plans, const uint64_t *counts, const uint8_t *pairs,
+                                 uint8_t *accept, uint32_t *status, h2v_workspace *ws /* not NULL */, void *stream,
+                                 const h2v_rlc_opts *opts /* or NULL */);
 
 /* ---- mixed-key batches: proofs of SEVERAL plans on one SRS in one call ---------------------------------------------------
  * The reference verifies a list of (vk, instances, proof) triples in one call and one final check

@@ -235,6 +235,29 @@ inline PairVerdicts check_pairs_rlc(const VerifyingKey &vk, const std::vector<ui
     if (fell_back) *fell_back = fb != 0;
     return r;
 }
+// ONE check over pairs on SEVERAL SRS (h2v_check_pairs_multi; at most H2V_MULTI_SRS_MAX ranges): the first counts[0] pairs are
+// checked against the SRS of *vks[0], the next counts[1] against *vks[1], and so on - C + 1 Miller loops under one final
+// exponentiation when every equation holds.  accept / status: position for position what check_pairs(*vks[k], ...) gives for
+// range k.  fell_back (optional): the check failed and the per-pair kernels produced them.  seed: as check_pairs_rlc.
+inline PairVerdicts check_pairs_multi(const std::vector<const VerifyingKey *> &vks, const std::vector<uint64_t> &counts, const std::vector<uint8_t> &pairs,
+                                      h2v_workspace *ws = nullptr, const uint8_t *seed = nullptr, bool *fell_back = nullptr) {
+    if (vks.size() != counts.size()) throw Error(H2V_E_ARG, "counts: one entry per key");
+    uint64_t n = 0;
+    for (uint64_t c : counts) n += c;
+    if (pairs.size() != n * 96) throw Error(H2V_E_ARG, "pairs: 96 bytes per pair, sum(counts) pairs");
+    std::vector<const h2v_plan *> plans;
+    for (const VerifyingKey *vk : vks) plans.push_back(vk ? vk->handle() : nullptr);
+    PairVerdicts r{std::vector<uint8_t>(n), std::vector<uint32_t>(n)};
+    const uint8_t none = 0;
+    uint8_t acc0 = 0;
+    h2v_rlc_opts opts{};
+    if (seed) { for (int k = 0; k < 32; k++) opts.seed[k] = seed[k]; opts.flags = H2V_RLC_SEED_GIVEN; }
+    int fb = 0;
+    check(h2v_check_pairs_multi(plans.data(), (uint32_t)plans.size(), counts.data(), n ? pairs.data() : &none, n ? r.accept.data() : &acc0, r.status.data(), ws,
+                                seed ? &opts : nullptr, &fb));
+    if (fell_back) *fell_back = fb != 0;
+    return r;
+}
 // The same vector through the batch-accept fast path (one random linear combination of the batch's pairing equations:
 // one bucketed G1 MSM + one pairing; the per-proof kernels only if the batch check fails).  fell_back (optional) tells
 // which of the two produced the vector.  seed: 32 bytes that provers cannot predict, or nullptr = drawn from the OS.

@@ -297,9 +297,32 @@ def _mixed_workspace(verifiers, n: int) -> backend.Workspace:
     return ws
 
 
+def check_pairs_multi(verifiers_and_pairs, seed: Optional[bytes] = None):
+    """ONE check over pairs on several SRS (h2v_check_pairs_multi): verifiers_and_pairs is a sequence of (Verifier, pairs) - the
+    pairs (96 bytes each: compress(L) || compress(R)) grouped by the verifier whose SRS they are checked against, in order; at
+    most backend.MULTI_SRS_MAX groups.  Returns (accept, status), flat, in the order the pairs were given: what each verifier's
+    own check_pairs gives for its group - from C + 1 Miller loops and one final exponentiation when every equation holds."""
+    groups = [(v, [bytes(p) for p in pairs]) for v, pairs in verifiers_and_pairs]
+    if any(len(p) != 96 for _v, pairs in groups for p in pairs):
+        raise ValueError("a pair is 96 bytes: compress(L) || compress(R)")
+    n = sum(len(pairs) for _v, pairs in groups)
+    if n == 0:
+        return [], []
+    first = next(v for v, pairs in groups if pairs)
+    acc, st, _fell_back = backend.check_pairs_multi([v.device_plan for v, _p in groups], [len(pairs) for _v, pairs in groups],
+                                                    b"".join(p for _v, pairs in groups for p in pairs), ws=first._workspace(n), seed=seed)
+    return [bool(a) for a in acc], st
+
+
+def _params_list(params) -> List[ParamsVerifierKZG]:
+    """`params` of Aggregator / batch_verify: one ParamsVerifierKZG, or a sequence of them (several SRS)"""
+    return [params] if isinstance(params, ParamsVerifierKZG) else list(params)
+
+
 def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
                  committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof", seed: Optional[bytes] = None,
-                 device: int = 0, fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False) -> List[bool]:
+                 device: int = 0, fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False,
+                 across_srs: bool = False) -> List[bool]:
     """accept[i] for n proofs, proof i under the key vks[i] (instances[i]: its public-input scalars; committed[i]: its
     committed instance as 48 compressed bytes when its circuit has one, else None).  The proofs are grouped by SRS on the
     host - one h2v_verify_mixed call per distinct s_g2, each over all its keys - and the verdicts come back in the caller's
@@ -308,9 +331,16 @@ def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances
     (H2V_MIXED_FOLD_MSM); a failed check runs the call again without it.  grouped (with fold_msm only; H2V_MIXED_GROUPED): phase 1
     of every key in one launch per kernel and up to backend.MIXED_GROUPED_MAX_PLANS keys per call - for many keys with few proofs
     each; the same verdicts.  keyed_seed (mode="rlc"; H2V_RLC_SEED_KEYED, not beside `seed`): nothing is drawn - every call's
-    seed is a digest of its proofs, instances and each proof's own key (seed.mixed_seed), the same whatever fold_msm / grouped say."""
+    seed is a digest of its proofs, instances and each proof's own key (seed.mixed_seed), the same whatever fold_msm / grouped say.
+    across_srs (mode="rlc" only): ONE pairing for the whole list instead of one per SRS - per distinct s_g2 one aggregate call
+    (h2v_aggregate_mixed: its pair and included[]), then one check_pairs_multi over the S pairs; an SRS whose pair fails is
+    verified by today's per-SRS call.  The same verdicts."""
     if keyed_seed and mode != "rlc":
         raise ValueError("keyed_seed needs mode='rlc'")
+    if across_srs and mode != "rlc":
+        raise ValueError("across_srs needs mode='rlc'")
+    if across_srs:
+        return _verify_across_srs(vks, proofs, instances, committed, seed, device, fold_msm, grouped, keyed_seed)[0]
     return _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm, grouped, keyed_seed)[0]
 
 
@@ -362,6 +392,32 @@ def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_ms
     return out, status
 
 
+def _verify_across_srs(vks, proofs, instances, committed, seed, device, fold_msm=False, grouped=False, keyed_seed=False):
+    """(accept, status) of verify_mixed(mode="rlc", across_srs=True)"""
+    if grouped and not fold_msm:
+        raise ValueError("grouped needs mode='rlc' and fold_msm")
+    out: List[bool] = [False] * len(proofs)
+    status: List[int] = [0] * len(proofs)
+    calls = []
+    for idx, verifiers, plan_of, pbytes, off, inst, ci in _mixed_calls(vks, proofs, instances, committed, device):
+        plans, ws = [v.device_plan for v in verifiers], _mixed_workspace(verifiers, len(idx))
+        pair, included, st, _info = backend.aggregate_mixed(plans, plan_of, pbytes, off, inst, ci, ws=ws, seed=seed, grouped=grouped,
+                                                            keyed_seed=keyed_seed)
+        calls.append((idx, verifiers, pair, included, st,
+                      lambda plans=plans, plan_of=plan_of, pbytes=pbytes, off=off, inst=inst, ci=ci, ws=ws: backend.verify_mixed(
+                          plans, plan_of, pbytes, off, inst, ci, ws=ws, mode="rlc", seed=seed, fold_msm=fold_msm, grouped=grouped,
+                          keyed_seed=keyed_seed)))
+    for lo in range(0, len(calls), backend.MULTI_SRS_MAX):       # (more SRS than one check takes: one check per slice)
+        part = calls[lo:lo + backend.MULTI_SRS_MAX]
+        ok, _st = check_pairs_multi([(c[1][0], [c[2]]) for c in part], seed=seed)
+        for passed, (idx, _verifiers, _pair, included, st, again) in zip(ok, part):
+            if not passed:
+                included, st, _fb = again()
+            for i, a, s in zip(idx, included, st):
+                out[i], status[i] = bool(a), s
+    return out, status
+
+
 def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instances: Sequence[Sequence[int]],
                  proofs: Sequence[bytes], committed: Optional[Sequence[Optional[bytes]]] = None, device: int = 0,
                  fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False) -> None:
@@ -369,11 +425,16 @@ def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instanc
     call and one final check for a list of (vk, instances, proof) triples on ONE SRS - the batch-accept mode of verify_mixed.
     Raises VerifyError unless every proof is accepted (Rust: Err(_)); a key on another SRS than `params` is a ValueError.
     fold_msm: one bucket MSM for the list as well; grouped: phase 1 of every key in one launch per kernel; keyed_seed: the seed is
-    derived from the list itself (verify_mixed)."""
+    derived from the list itself (verify_mixed).  `params` may also be a sequence of ParamsVerifierKZG: a list that spans several
+    SRS, still with one final check (verify_mixed(across_srs=True)); a key on none of them is a ValueError."""
+    known = [bytes(q.s_g2) for q in _params_list(params)]
     for i, vk in enumerate(vks):
-        if bytes(params.s_g2) != bytes.fromhex(vk.s_g2):
+        if bytes.fromhex(vk.s_g2) not in known:
             raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
-    acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm, grouped, keyed_seed)
+    if not isinstance(params, ParamsVerifierKZG):
+        acc, status = _verify_across_srs(vks, proofs, instances, committed, None, device, fold_msm, grouped, keyed_seed)
+    else:
+        acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm, grouped, keyed_seed)
     if not all(acc):
         raise VerifyError(next(s for a, s in zip(acc, status) if not a))
 
@@ -381,7 +442,8 @@ def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instanc
 class Aggregator:
     """Collects the pairs of several calls and checks them ONCE: the reference's `dual_msm.scale(r)` / `acc.add_msm(..)` per call
     and one `check` over everything collected (examples/ivc.rs:85-96, 195-208).  One Aggregator per SRS (`params`); a key on
-    another SRS is a ValueError.
+    another SRS is a ValueError.  `params` may also be a sequence of ParamsVerifierKZG: pushes on any of those SRS (one push is
+    one pair on ONE of them), and finish() still runs one check - a multi-pairing over all of them (check_pairs_multi).
 
         agg = Aggregator(params)
         agg.push(vk_a, proofs_a, instances_a)         # h2v_aggregate_batch: no pairing runs
@@ -406,20 +468,32 @@ class Aggregator:
         if derive_seed and keyed_seed:
             raise ValueError("derive_seed and keyed_seed exclude each other: one seed rule per Aggregator")
         self.params, self.device, self.grouped, self.derive_seed, self.keyed_seed = params, device, grouped, derive_seed, keyed_seed
-        self._calls = []      # (a verifier on the SRS, pair, included, the call again per proof -> accept list)
+        self._calls = []      # (a verifier on the SRS, pair, included, the call again per proof -> accept list, the SRS's index)
+
+    def _srs_of(self, vks, listed: bool = True) -> int:
+        """which of the aggregator's SRS every key of one push is on; ValueError for a key on none of them or keys on two"""
+        found, srs = None, [bytes(q.s_g2) for q in _params_list(self.params)]
+        for i, vk in enumerate(vks):
+            s_g2 = bytes.fromhex(vk.s_g2)
+            if s_g2 not in srs:
+                raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i if listed else
+                                 "verifier params do not match the verifying key's SRS (s_g2 differs)")
+            if found is not None and srs.index(s_g2) != found:
+                raise ValueError("one push is one pair on one SRS: vks[%d] is on another SRS than vks[0]" % i)
+            found = srs.index(s_g2)
+        return found or 0
 
     def push(self, vk: VerifyingKey, proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
              committed: Optional[Sequence[Optional[bytes]]] = None, seed: Optional[bytes] = None) -> int:
         """aggregates one call of proofs of `vk` and keeps its pair, included[] and a reference to the inputs; returns the call's index"""
-        if bytes(self.params.s_g2) != bytes.fromhex(vk.s_g2):
-            raise ValueError("verifier params do not match the verifying key's SRS (s_g2 differs)")
+        srs = self._srs_of([vk], listed=False)
         if self.keyed_seed:      # (a one-plan mixed call: the aggregator's one rule)
             if seed is not None:
                 raise ValueError("keyed_seed derives the seed: none can be given")
             return self.push_mixed([vk] * len(proofs), proofs, instances, committed)
         v = verifier_for(vk, self.device)
         pair, included, _status, _info = v.aggregate_batch(proofs, instances, committed, seed=seed, derive_seed=self.derive_seed)
-        self._calls.append((v, pair, included, lambda: v.verify_batch(proofs, instances, committed)))
+        self._calls.append((v, pair, included, lambda: v.verify_batch(proofs, instances, committed), srs))
         return len(self._calls) - 1
 
     def push_mixed(self, vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
@@ -428,16 +502,14 @@ class Aggregator:
         H2V_RLC_GROUPED form: up to backend.MIXED_GROUPED_MAX_PLANS keys); returns the call's index"""
         if self.derive_seed:
             raise ValueError("an Aggregator with derive_seed takes single-key pushes only: the mixed calls have no derived seed")
-        for i, vk in enumerate(vks):
-            if bytes(self.params.s_g2) != bytes.fromhex(vk.s_g2):
-                raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
+        srs = self._srs_of(list(vks))
         if not proofs:
             raise ValueError("no proofs")
         (idx, verifiers, plan_of, pbytes, off, inst, ci), = _mixed_calls(vks, proofs, instances, committed, self.device)
         pair, included, _status, _info = backend.aggregate_mixed([v.device_plan for v in verifiers], plan_of, pbytes, off, inst, ci,
                                                                  ws=_mixed_workspace(verifiers, len(idx)), seed=seed, grouped=self.grouped,
                                                                  keyed_seed=self.keyed_seed)
-        self._calls.append((verifiers[0], pair, included, lambda: verify_mixed(vks, proofs, instances, committed, device=self.device)))
+        self._calls.append((verifiers[0], pair, included, lambda: verify_mixed(vks, proofs, instances, committed, device=self.device), srs))
         return len(self._calls) - 1
 
     def finish(self, seed: Optional[bytes] = None):
@@ -447,9 +519,22 @@ class Aggregator:
         if not calls:
             return [], []
         pairs = [c[1] for c in calls]
-        ok, _st = calls[0][0].check_pairs(pairs, mode="rlc" if len(pairs) > 1 else "per-pair", seed=seed)
+        if len({c[4] for c in calls}) == 1:
+            ok, _st = calls[0][0].check_pairs(pairs, mode="rlc" if len(pairs) > 1 else "per-pair", seed=seed)
+        else:
+            # several SRS: the calls' pairs sorted by SRS, stably, and ONE multi-pairing; the verdicts back in push order
+            order = sorted(range(len(calls)), key=lambda k: calls[k][4])
+            groups = []
+            for k in order:
+                if not groups or groups[-1][0] != calls[k][4]:
+                    groups.append((calls[k][4], calls[k][0], []))
+                groups[-1][2].append(pairs[k])
+            flat, _st = check_pairs_multi([(v, ps) for _srs, v, ps in groups], seed=seed)
+            ok = [False] * len(calls)
+            for k, a in zip(order, flat):
+                ok[k] = a
         accepts, reverified = [], []
-        for k, (_v, _pair, included, again) in enumerate(calls):
+        for k, (_v, _pair, included, again, _srs) in enumerate(calls):
             if ok[k]:
                 accepts.append(list(included))
             else:

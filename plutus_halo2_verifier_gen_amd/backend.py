@@ -92,6 +92,7 @@ MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
 MIXED_FOLD_MSM = 2     # ... and ONE bucket MSM over the call's per-proof terms (only together with MIXED_RLC)
 MIXED_GROUPED = 4      # ... and phase 1 of every groupable plan in ONE launch per kernel (only together with both)
 MIXED_MAX_PLANS = 64   # H2V_MIXED_MAX_PLANS
+MULTI_SRS_MAX = 16     # H2V_MULTI_SRS_MAX: ranges (plans listed) in one h2v_check_pairs_multi call
 MIXED_GROUPED_MAX_PLANS = 1024   # H2V_MIXED_GROUPED_MAX_PLANS: plans listed in a MIXED_GROUPED call
 MIXED_GROUPED_MAX_OTHER = 62     # H2V_MIXED_GROUPED_MAX_OTHER: ... of which plans that cannot be grouped and have proofs
 BATCH_NOT_CHECKED = 2  # H2V_BATCH_NOT_CHECKED: batch_accepted of an aggregate call (Workspace.rlc_verdict)
@@ -123,7 +124,7 @@ EXPORTS = [
     "h2v_last_error", "h2v_build_id",
     "h2v_device_count", "h2v_shutdown",
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
-    "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device",
+    "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device", "h2v_check_pairs_multi", "h2v_check_pairs_multi_device",
     "h2v_plan_transcript", "h2v_probe_blake2b_ex",
     "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums", "h2v_probe_decompress",
     "h2v_aggregate_batch", "h2v_aggregate_batch_device", "h2v_aggregate_mixed", "h2v_aggregate_mixed_device", "h2v_plan_same_srs",
@@ -216,6 +217,10 @@ def lib():
                                           C.POINTER(C.c_int)]
         L.h2v_check_pairs_rlc_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                  C.POINTER(RlcOpts)]
+        L.h2v_check_pairs_multi.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(RlcOpts), C.POINTER(C.c_int)]
+        L.h2v_check_pairs_multi_device.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_void_p, C.POINTER(RlcOpts)]
         L.h2v_verify_mixed.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                        C.POINTER(RlcOpts), C.POINTER(C.c_int)]
         L.h2v_verify_mixed_device.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p,
@@ -712,6 +717,39 @@ def aggregate_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci
     check(lib().h2v_aggregate_mixed_device(arr, len(plans), C.byref(b), d_pair, d_included, d_status, ws.handle if ws else None, stream,
                                            C.byref(opts) if opts is not None else None, C.byref(info)))
     return info
+
+
+def check_pairs_multi(plans, counts, pairs: bytes, ws=None, seed: Optional[bytes] = None):
+    """h2v_check_pairs_multi: ONE batch check over pairs on several SRS.  The first counts[0] pairs (96 bytes each) are checked
+    against the SRS of plans[0], the next counts[1] against plans[1], ...; at most MULTI_SRS_MAX ranges.  Returns (accept bytes,
+    status list, fell_back) - position for position what plans[k].check_pairs gives for range k; fell_back: the one check
+    failed and the per-pair kernels produced accept[].  ws: any workspace check_pairs would take for n pairs; None: a temporary one."""
+    if len(plans) != len(counts):
+        raise H2VError("counts: one entry per plan")
+    n = sum(counts)
+    if len(pairs) != 96 * n:
+        raise H2VError("pairs: 96 bytes per pair, sum(counts) pairs")
+    arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
+    cnt = (C.c_uint64 * max(1, len(counts)))(*counts)
+    acc = (C.c_uint8 * max(1, n))()
+    st = (C.c_uint32 * max(1, n))()
+    fb = C.c_int(0)
+    opts = _rlc_opts(seed)
+    check(lib().h2v_check_pairs_multi(arr, len(plans), cnt, bytes(pairs), acc, st, ws.handle if ws else None,
+                                      C.byref(opts) if opts is not None else None, C.byref(fb)))
+    return bytes(acc[:n]), list(st[:n]), bool(fb.value)
+
+
+def check_pairs_multi_device(plans, counts, d_pairs, d_accept, d_status=None, ws=None, stream=None, seed: Optional[bytes] = None) -> None:
+    """h2v_check_pairs_multi_device: enqueues on `stream` (counts is a host list, every d_* a device pointer; ws is required);
+    ws.rlc_result() has the batch verdict once the stream is synchronised"""
+    if len(plans) != len(counts):
+        raise H2VError("counts: one entry per plan")
+    arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
+    cnt = (C.c_uint64 * max(1, len(counts)))(*counts)
+    opts = _rlc_opts(seed)
+    check(lib().h2v_check_pairs_multi_device(arr, len(plans), cnt, d_pairs, d_accept, d_status, ws.handle if ws else None, stream,
+                                             C.byref(opts) if opts is not None else None))
 
 
 def probe_mixed_fold_sums(ws):

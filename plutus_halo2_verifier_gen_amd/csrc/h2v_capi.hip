@@ -299,6 +299,7 @@ struct h2v_workspace {
     hipEvent_t ev_seed_last = nullptr;      // the end of the most recent derivation (one of ev_seed[..][1])
     struct RlcWs *rlc = nullptr;   // buffers of the RLC batch mode, created by its first call
     struct RlcWs *prlc = nullptr;  // the pair-RLC set (h2v_check_pairs_rlc, H2V_RLC_FOLD_PAIRS): created by the first such call
+    struct MultiWs *multi = nullptr;   // the set of h2v_check_pairs_multi (several SRS in one check): created by the first such call
     hipEvent_t ev_pipe[12] = {};   // H2V_RLC_FOLD_PAIRS: the pipeline's own markers (the record's events carry the RLC layout)
     std::vector<struct RlcWs *> rlc_parked;   // the same for OTHER plans this workspace has served in that mode (rlc_ensure swaps; never freed before the workspace)
     int32_t opt[H2V_OPT_COUNT] = {};   // h2v_workspace_set_option / h2v_workspace_tune: 0 = the launcher's choice
@@ -522,6 +523,7 @@ static void rlc_release(struct RlcWs *r);
 static hipError_t make_stream(hipStream_t *s);
 static void co_release(h2v_workspace *w);
 static void mixed_release(h2v_workspace *w);
+static void multi_release(h2v_workspace *w);
 static int co_flush(h2v_workspace *w);
 static int lane_streams(uint32_t l, hipStream_t *main_st, hipStream_t *side_st);
 static void slot_release(h2v_workspace::HostSlot &sl) {
@@ -545,6 +547,7 @@ static void ws_release(h2v_workspace *w) {
     for (struct RlcWs *r : w->rlc_parked) rlc_release(r);
     w->rlc_parked.clear();
     if (w->prlc) { rlc_release(w->prlc); w->prlc = nullptr; }
+    multi_release(w);
     w->mem.release();
     w->ev_seed_last = nullptr;
     if (w->copy_streams_owned) {
@@ -1260,14 +1263,21 @@ static int agg_chunk(const Unit &u, struct RlcWs *r, h2v_workspace *w, CallRec &
 // Decompression: ONE launch whose waves (at most one per SIMD) take 64-point units from a queue - all subgroup tests,
 // then all square roots (k_g1_decompress_queue).  v: the plan, or a view of it (pair_view); tab: where the MSM window tables
 // go (NULL: none are built); blocks_out (h2v_probe_decompress): the grid of the launch.
+// (DecBufs: where the points and their two verdict bytes go, and the launch's queue counter - a workspace's own, or the set of
+// h2v_check_pairs_multi)
+struct DecBufs { uint32_t *pts; uint8_t *valid, *valid_sub; uint32_t *dec_ctr; };
 static int launch_decompress(const H2vDevPlan &v, uint32_t n, const uint8_t *src, const uint64_t *off, const uint8_t *ci, const uint8_t *inst,
-                             h2v_workspace *w, uint32_t *tab, hipStream_t st, uint32_t *blocks_out = nullptr) {
+                             const DecBufs &b, uint32_t *tab, hipStream_t st, uint32_t *blocks_out = nullptr) {
     const uint32_t dec_grid = (n * H2V_SLOTS(v) + 63) / 64, units = 2 * dec_grid, max_blocks = (uint32_t)(msm_n_simd() / 4.0);
     const uint32_t blocks = (units + 3) / 4 < max_blocks ? (units + 3) / 4 : max_blocks;
     if (blocks_out) *blocks_out = blocks;
-    HIPCHK(hipMemsetAsync(w->dec_ctr, 0, 4, st));
-    hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, src, off, ci, inst, w->pts, w->valid, tab, w->valid_sub, w->dec_ctr, dec_grid);
+    HIPCHK(hipMemsetAsync(b.dec_ctr, 0, 4, st));
+    hipLaunchKernelGGL(k_g1_decompress_queue, dim3(blocks), dim3(256), 0, st, v, n, src, off, ci, inst, b.pts, b.valid, tab, b.valid_sub, b.dec_ctr, dec_grid);
     return H2V_OK;
+}
+static int launch_decompress(const H2vDevPlan &v, uint32_t n, const uint8_t *src, const uint64_t *off, const uint8_t *ci, const uint8_t *inst,
+                             h2v_workspace *w, uint32_t *tab, hipStream_t st, uint32_t *blocks_out = nullptr) {
+    return launch_decompress(v, n, src, off, ci, inst, DecBufs{w->pts, w->valid, w->valid_sub, w->dec_ctr}, tab, st, blocks_out);
 }
 static int run_pipeline(const Unit &u, h2v_workspace *w, hipStream_t st) {
     const H2vDevPlan &d = u.p->d;
@@ -2958,6 +2968,8 @@ extern "C" int h2v_check_pairs_rlc(const h2v_plan *p, uint64_t n, const uint8_t 
     if (n == 0) return H2V_OK;
     return check_pairs_host(Unit{UnitKind::PAIR_RLC, p, (uint32_t)n}, pairs, accept, status, ws, opts, fell_back);
 }
+
+#include "h2v_multi_srs.hpp"   // h2v_check_pairs_multi(_device): one batch check over pairs on several SRS
 // ---------------------------------------------------------------------------------------------- mixed-key batches
 // h2v_verify_mixed(_device): n proofs of SEVERAL plans on one SRS in one call.  Behind the per-proof MSM a proof of any key is a
 // pair (L, R) with e(L, s_g2) == e(R, G2), and the pairing sees nothing of the key but the SRS; so the call runs

@@ -812,6 +812,189 @@ k_pairing_rlc_groups(H2vDevPlan plan, const uint32_t *__restrict__ pts_g, const 
     }
 }
 
+// ---- the batch check ACROSS SEVERAL SRS (h2v_check_pairs_multi): one wave, the wide engine, decides
+//     FE( prod_k ML(L_k ; lines(s_g2_k)) * ML(-R ; lines(G2)) ) == 1
+// for up to COOP_MULTI_MAX left sums L_k, each against its own SRS's line table, and ONE right sum R: C + 1 Miller loops under one
+// final exponentiation.  The form is the simple one: COOP_PROGRAM is split at its MILLER op (found by one scan - no second
+// program header); the ops up to and including MILLER run once per range from F = 1, with L_k in the PX1 / PY1 slots and the
+// range's table serving loop 1 - loop 2 carries -R on the first pass and is an infinity (skip2) on the later ones -, every pass's
+// Miller value is multiplied into an accumulator (coop_mul), and the rest of the program - the final exponentiation - runs once on
+// the accumulator.  A pass restarts the staging invariants of coop_line<1 / 2> by itself: WARMUP stages line 0 of both tables and
+// makes T1 of line 0 from the PX1 the leader has just written.  A range whose L_k is infinity AND that carries no finite -R takes no
+// pass at all; no pass at all leaves the accumulator 1 (an all-infinite call passes).  The squarings are NOT shared between the
+// ranges (one coop_sqr per bit and C + 1 line steps behind it would be the better engine).
+// A body of its own, not one more instantiation of pairing_coop_body: that function sits at the register limit and its
+// co-compiled instantiations disturb each other.  A program without MILLER, or with an op this body does not know, fails closed.
+#define COOP_MULTI_MAX 16
+struct CoopMultiLines {
+    const uint32_t *sg2[COOP_MULTI_MAX];     // lines28_sg2 of range k's plan
+    uint32_t n;                              // ranges, 1 .. COOP_MULTI_MAX
+};
+H2V_DI void coop_load_jac(G1J &j, const uint32_t *__restrict__ src) {
+#pragma unroll
+    for (int k = 0; k < 12; k++) { j.x.v[k] = src[k]; j.y.v[k] = src[12 + k]; j.z.v[k] = src[24 + k]; }
+}
+// sums: R (36 dwords, Jacobian), then L_0 .. L_{n - 1}: the layout of RlcWs::sums, continued.  Returns the verdict in every lane.
+H2V_DI bool pairing_multi_body(const CoopMultiLines &tabs, const uint32_t *__restrict__ lines28_g2, const uint32_t *__restrict__ sums) {
+    const int lane = threadIdx.x;
+    Coop c;
+    (void)coop_lane_setup<true, false, false>(c, lane);
+    const bool is_leader = lane == 0;
+    coop_tables_to_lds(lane);
+    coop_consts_to_lds(lane);
+    int split = -1;                          // the op behind MILLER
+    for (int pc = 0; pc < COOP_PROGRAM_LEN; pc++)
+        if ((COOP_PROGRAM[pc] & 0xff) == COOP_OP_MILLER) { split = pc + 1; break; }
+    bool prog_ok = split > 0, inv_ok = true;
+    F28 vars[COOP_N_VARS];
+    F28 acc;
+    f28_set_zero(acc);
+    if (c.g == 0) f28_set_one(acc);
+    bool have_acc = false;
+#pragma unroll 1
+    for (uint32_t k = 0; k < tabs.n && prog_ok; k++) {
+        // ---- leader: L_k (and, first pass, -R) normalised to affine, as pairing_coop_body's leader does for one pair
+        uint32_t flags = 2;                  // bit0: L_k is infinity, bit1: loop 2 is skipped (later passes: always)
+        __syncthreads();                     // (the previous pass's last engine call has read the point slots)
+        if (is_leader) {
+            G1J lj;
+            G1A el;
+            coop_load_jac(lj, sums + 36 * (k + 1));
+            g1j_to_affine(el, lj);
+            if (g1a_is_inf(el)) flags |= 1;
+            coop_store28(coop_slot(c, COOP_SLOT_PX1), el.x);
+            coop_store28(coop_slot(c, COOP_SLOT_PY1), el.y);
+            if (k == 0) {
+                G1J rj;
+                G1A er;
+                coop_load_jac(rj, sums);
+                g1j_to_affine(er, rj);
+                if (!g1a_is_inf(er)) flags &= ~2u;
+                fp_neg(er.y, er.y);
+                coop_store28(coop_slot(c, COOP_SLOT_PX2), er.x);
+                coop_store28(coop_slot(c, COOP_SLOT_PY2), er.y);
+                Fp z;
+                fp_set_zero(z);
+                coop_store28(coop_slot(c, COOP_SLOT_ZERO), z);
+            }
+        }
+        flags = __shfl(flags, 0);
+        const bool skip1 = (flags & 1) != 0, skip2 = (flags & 2) != 0;
+        if (skip1 && skip2) continue;        // nothing to multiply in
+        const uint32_t *lines28_sg2 = tabs.sg2[k];
+#pragma unroll 1
+        for (int pc = 0; pc < split; pc++) {
+            const uint32_t ins = COOP_PROGRAM[pc];
+            const int op = ins & 0xff, d = (ins >> 8) & 0xff;
+            if (op == COOP_OP_SETONE) {
+                F28 o;
+                f28_set_zero(o);
+                if (c.g == 0) f28_set_one(o);
+                vars[d] = o;
+            } else if (op == COOP_OP_WARMUP) {
+                coop_stage_line(c, COOP_SLOT_LN1, lines28_sg2, 0, lane);
+                coop_stage_line(c, COOP_SLOT_LN2, lines28_g2, 0, lane);
+                __syncthreads();
+                (void)coop_line<2>(c, vars[COOP_VAR_F]);  // only its spare lanes matter: T1 of line 0
+            } else if (op == COOP_OP_MILLER) {
+                // as pairing_coop_body's MILLER (the wide engine's branch), line tables by argument
+                F28 f = vars[COOP_VAR_F];
+                int ln = 0;
+#pragma unroll 1
+                for (int bit = 62; bit >= 0; bit--) {
+                    f = coop_sqr(c, f);
+                    const int steps = ((BLS_X_ABS >> bit) & 1) ? 2 : 1;
+#pragma unroll 1
+                    for (int s2 = 0; s2 < steps; s2++, ln++) {
+                        if (ln > 0) coop_stage_line(c, COOP_SLOT_LN2, lines28_g2, ln, lane);
+                        __syncthreads();
+                        const F28 r1 = coop_line<1>(c, f);
+                        if (!skip1 && c.g < 12) f = r1;
+                        if (ln + 1 < H2V_MILLER_LINES) coop_stage_line(c, COOP_SLOT_LN1, lines28_sg2, ln + 1, lane);
+                        __syncthreads();
+                        const F28 r2 = coop_line<2>(c, f);
+                        if (!skip2 && c.g < 12) f = r2;
+                    }
+                }
+                vars[COOP_VAR_F] = f;
+            } else {
+                prog_ok = false;             // (the program's head is SETONE, WARMUP, MILLER)
+            }
+        }
+        if (have_acc) {
+            const F28 f = vars[COOP_VAR_F];
+            acc = coop_mul(c, acc, f);
+        } else {
+            acc = vars[COOP_VAR_F];
+        }
+        have_acc = true;
+    }
+    // ---- the rest of the program, once, on the product
+    vars[COOP_VAR_F] = acc;
+#pragma unroll 1
+    for (int pc = split > 0 ? split : COOP_PROGRAM_LEN; pc < COOP_PROGRAM_LEN; pc++) {
+        const uint32_t ins = COOP_PROGRAM[pc];
+        const int op = ins & 0xff, d = (ins >> 8) & 0xff, a = (ins >> 16) & 0xff, b = ins >> 24;
+        if (op == COOP_OP_END) break;
+        switch (op) {
+        case COOP_OP_MUL: {
+            const F28 x = vars[a], y = vars[b];
+            vars[d] = coop_mul(c, x, y);
+        } break;
+        case COOP_OP_CSQR: {
+            F28 x = vars[a];
+#pragma unroll 1
+            for (int rep = 0; rep < b; rep++) x = coop_csqr(c, x);
+            vars[d] = x;
+        } break;
+        case COOP_OP_EXPX: {
+            F28 x = vars[a];
+#pragma unroll 1
+            for (int bit = 62; bit >= 0; bit--) {
+                x = coop_csqr(c, x);
+                if ((BLS_X_ABS >> bit) & 1) {
+                    const F28 y = vars[a];
+                    x = coop_mul(c, x, y);
+                }
+            }
+            vars[d] = coop_conj(c, x);
+        } break;
+        case COOP_OP_CONJ: vars[d] = coop_conj(c, vars[a]); break;
+        case COOP_OP_FROB: vars[d] = coop_frob(c, vars[a]); break;
+        case COOP_OP_INV: {
+            bool ok = true;
+            vars[d] = coop_inv(c, vars[a], ok);
+            inv_ok = ok;
+        } break;
+        case COOP_OP_MOV: vars[d] = vars[a]; break;
+        case COOP_OP_DUMP: break;
+        default: prog_ok = false; break;     // (MSTEP, WARMUP, MILLER, SETONE: no part of a final exponentiation)
+        }
+    }
+    Fp res;
+    f28_to_fp(res, vars[COOP_VAR_F]);
+    bool mine = true;
+    if (c.g == 0) { Fp one; fp_set_one(one); mine = fp_eq(res, one); }
+    else if (c.g < 12) mine = fp_is_zero(res);
+    const bool is_one = __ballot(mine) == ~0ull;
+    inv_ok = __shfl((int)inv_ok, 0) != 0;
+    return prog_ok && is_one && inv_ok;
+}
+// Epilogue as k_pairing_rlc's (no group stage follows, no routing counters): flags[0] and flags[1 + g] = the batch verdict - the
+// per-pair kernels queued behind take them as skip flags, each range's launch indexing its own groups from 0, which is why every
+// word up to the whole call's group count carries the same verdict -, fail_ctr, and accept[i] = good_i when the check passed.
+extern "C" __global__ void __launch_bounds__(64, 2)
+k_pairing_rlc_multi(CoopMultiLines tabs, const uint32_t *__restrict__ lines28_g2, const uint32_t *__restrict__ sums, uint32_t n_batch,
+                    const uint8_t *__restrict__ good, uint8_t *__restrict__ accept, uint32_t *__restrict__ flags, uint32_t n_groups,
+                    uint32_t *__restrict__ fail_ctr) {
+    const bool ok = pairing_multi_body(tabs, lines28_g2, sums);
+    if (threadIdx.x == 0) flags[0] = ok ? 1u : 0u;
+    for (uint32_t g = threadIdx.x; g < n_groups; g += 64) flags[1 + g] = ok ? 1u : 0u;
+    if (threadIdx.x == 0 && !ok && fail_ctr) atomicAdd(fail_ctr, 1u);
+    if (ok)
+        for (uint32_t i = threadIdx.x; i < n_batch; i += 64) accept[i] = good[i];
+}
+
 // ---- dev probe: ONE engine call per group, on raw limb vectors, through the functions the pairing calls (h2v_probe_coop_call;
 // tests/test_coop_engine_calls_gpu.py holds every result to the limb model of tests/coop_engine_model.py, limb for limb, with the
 // operands ON the bounds the headroom note above states).  Launch as the pairing kernel of the same shape: one wave per block,

@@ -278,4 +278,32 @@ static inline Table<V_COUNT> pair_view(uint64_t cap) { return {{{"pair_pts", 8, 
 enum Stats { S_REC_FAIL, S_RLC_STATS, S_H_RLC_STATS, S_COUNT };
 static inline Table<S_COUNT> rlc_stats() { return {{{"rec_fail", RING * 4, NONE}, {"rlc_stats", 8, ZERO}, {"h_rlc_stats", 8, NONE}}}; }
 static inline size_t seed_ring_bytes() { return RING * 32; }
+
+// ---- the set of h2v_check_pairs_multi (one batch check across several SRS), created by the first such call on a workspace of
+// `cap` pairs - an ordinary or a laned one: the call runs as one piece, so the set has the decoding buffers of its own that a
+// lane's chunk could not hold.  With it go an RLC set of the pairs shape (rlc_pairs(cap): coefficients, index arrays, good, flags,
+// the bucket-MSM sets of R and of the first range's L), one bucket-MSM set per further range, sized by that range's count when a
+// call first needs it (multi_range_cap), MULTI_ARG_SLOTS untimed events and as many pinned copies of an argument array.
+constexpr uint32_t MULTI_MAX = 16, MULTI_ARG_SLOTS = 8;      // H2V_MULTI_SRS_MAX; calls whose argument arrays may be in flight
+enum Multi { X_PTS, X_VALID, X_VALID_SUB, X_DEC_CTR, X_STATUS, X_ER, X_PAIR_PTS, X_PAIR_OFF, X_SUMS, X_ARGS, X_COUNT };
+static inline size_t multi_args_bytes() { return (size_t)(MULTI_MAX + 1) * PIP_ARGS_BYTES; }     // one call's: R, then every range's L
+static inline Table<X_COUNT> multi_srs(uint64_t cap) {
+    const size_t n = (size_t)cap;
+    return {{{"pts", n * PAIR_BYTES, NONE},
+             {"valid", n * 2, NONE},
+             {"valid_sub", n * 2, NONE},
+             {"dec_ctr", 4, NONE},
+             {"status", n * 4, NONE},
+             {"er", n * JAC_BYTES, NONE},
+             {"pair_pts", 8, NONE},
+             {"pair_off", (n + 1) * 8, NONE},
+             {"sums", (size_t)(MULTI_MAX + 1) * JAC_BYTES, NONE},      // R, then L_0 ..: RlcWs::sums, continued
+             {"args_d", MULTI_ARG_SLOTS * multi_args_bytes(), NONE}}};
+}
+// the capacity a further range's bucket-MSM set is (re)allocated with for `count` pairs: the next power of two, at least 64
+static inline uint32_t multi_range_cap(uint64_t count) {
+    uint32_t c = 64;
+    while ((uint64_t)c < count) c <<= 1;
+    return c;
+}
 }   // namespace wslayout

@@ -9,8 +9,15 @@ pairs), rlc_one (one failing pair per batch), rlc_tenth (the pairs of a batch wi
 pairing-only kinds); recursive keys also verify / fold_valid and verify_one / fold_one.  Reported per kind: the best window and
 the spread (max - min) / max of the three; a gain counts only when it exceeds the larger spread of the two kinds compared.
 Writes one JSON line per case and, with --out, the whole set as one JSON file.
+--multi-srs S[,S..] (a mode of its own: nothing of the above runs): ONE h2v_check_pairs_multi_device call over pairs on S SRS
+against the S h2v_check_pairs_rlc_device calls, one per SRS, that it stands in for - same pairs, same ordinary workspace, one
+stream, one process.  Per S two shapes: S pairs in all, one per SRS (what an Aggregator holds), and 4096 pairs in all.  Both
+routes warmed, a given seed, five alternating runs of at least --seconds (0.5) each; every run's ms per window (one window = the
+whole list checked once) goes to --out (profiles/pairs_multi_srs.json).  A gain is stated only when the slowest run of the new
+call beats the fastest run of the baseline.
 usage: bench_pairs_rlc.py [--seconds 1.0] [--warmup 5] [--repeats 3] [--cases simple_mul:4096,sha256:1024,bls12381:1024,ivc:1024]
-                          [--out profiles/pairs_rlc.json]"""
+                          [--out profiles/pairs_rlc.json]
+       bench_pairs_rlc.py --multi-srs 2,4,8 [--seconds 0.5] [--out profiles/pairs_multi_srs.json]"""
 import argparse
 import json
 import os
@@ -139,14 +146,96 @@ def run_case(name, B, seconds, warmup, repeats):
     return out
 
 
+def run_multi_srs(S, total, seconds, runs=5):
+    """one shape: `total` valid pairs spread evenly over S SRS; returns the ms per window of every run of both routes"""
+    import torch
+    from plutus_halo2_verifier_gen_amd import backend, bls12_381 as bls, plan as PL, vk as V
+    per = total // S
+    assert per >= 1 and per * S == total
+    plans, raws = [], []
+    for q in range(S):
+        s = (0x5a17 + q) << 64 | (11 + q)
+        vk, _td = V.on_srs(*V.simple_mul_vk(seed=1 + q), s)
+        plans.append(backend.DevicePlan(PL.compile_plan(vk).to_bytes(), 0))
+        a, d = bls.g1_mul(bls.G1_GEN, 1000 + q), bls.g1_mul(bls.G1_GEN, 77)
+        sa, sd = bls.g1_mul(a, s), bls.g1_mul(d, s)
+        out = []
+        for _ in range(per):
+            out.append(bls.g1_compress(a) + bls.g1_compress(sa))
+            a, sa = bls.g1_add(a, d), bls.g1_add(sa, sd)
+        raws.append(b"".join(out))
+    dev = torch.device("cuda", 0)
+    pairs = torch.frombuffer(bytearray(b"".join(raws)), dtype=torch.uint8).to(dev)
+    acc = torch.zeros(total, dtype=torch.uint8, device=dev)
+    st = torch.zeros(total, dtype=torch.int32, device=dev)
+    caller = torch.cuda.Stream(device=dev)
+    cs = caller.cuda_stream
+    ws = backend.Workspace(plans[0], max(total, 64))
+    seed = bytes(range(32))
+    counts = [per] * S
+
+    def multi():
+        backend.check_pairs_multi_device(plans, counts, pairs.data_ptr(), acc.data_ptr(), st.data_ptr(), ws=ws, stream=cs, seed=seed)
+
+    def per_srs():
+        for q in range(S):
+            plans[q].check_pairs_rlc_device(per, pairs.data_ptr() + 96 * per * q, acc.data_ptr() + per * q, st.data_ptr() + 4 * per * q, ws=ws,
+                                            stream=cs, seed=seed)
+
+    def window(route, k):
+        t0 = time.perf_counter()
+        for _ in range(k):
+            route()
+        caller.synchronize()
+        return time.perf_counter() - t0
+
+    for route in (multi, per_srs):                      # correctness and warm-up (first uses allocate)
+        acc.zero_()
+        route()
+        caller.synchronize()
+        assert acc.cpu().tolist() == [1] * total and st.cpu().tolist() == [0] * total and ws.rlc_result(timings=False)[0]
+        window(route, 5)
+    ms = {"multi": [], "per_srs": []}
+    for _ in range(runs):                               # alternating
+        for name, route in (("multi", multi), ("per_srs", per_srs)):
+            per_window = window(route, 8) / 8           # (untimed calibration)
+            k = max(8, int(seconds / per_window) + 1)
+            ms[name].append(round(1e3 * window(route, k) / k, 4))
+    ws.close()
+    for p in plans:
+        p.close()
+    return {"srs": S, "pairs": total, "ms_per_window": ms, "gain": max(ms["multi"]) < min(ms["per_srs"]),
+            "loss": min(ms["multi"]) > max(ms["per_srs"]), "fastest_baseline_over_slowest_new": round(min(ms["per_srs"]) / max(ms["multi"]), 3)}
+
+
+def main_multi_srs(args):
+    import torch
+    results = []
+    for S in [int(v) for v in args.multi_srs.split(",")]:
+        for total in (S, 4096):
+            r = run_multi_srs(S, total, args.seconds if args.seconds_given else 0.5)
+            print(json.dumps(r), flush=True)
+            results.append(r)
+    out = args.out or os.path.join(ROOT, "profiles", "pairs_multi_srs.json")
+    with open(out, "w") as f:
+        json.dump({"tool": "tools/bench_pairs_rlc.py --multi-srs " + args.multi_srs, "device": torch.cuda.get_device_name(0),
+                   "window": "the whole list checked once: one h2v_check_pairs_multi_device call (multi) / S h2v_check_pairs_rlc_device calls (per_srs)",
+                   "runs": 5, "rule": "a gain only if the slowest run of multi beats the fastest run of per_srs", "shapes": results}, f, indent=1)
+        f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--multi-srs", default=None)
     ap.add_argument("--seconds", type=float, default=1.0)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--cases", default=DEFAULT_CASES)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.seconds_given = any(a.startswith("--seconds") for a in sys.argv[1:])
+    if args.multi_srs:
+        return main_multi_srs(args)
     import torch
     results = []
     for c in args.cases.split(","):
