@@ -549,10 +549,39 @@ int h2v_check_pairs_multi_device(const h2v_plan *const *plans, uint32_t n_plans,
  *   flag; 64 keys x 16 5.7-6.9 against 13.5-13.7 (48.6-49.0 for one h2v_verify_batch_rlc call per key); 256 keys x 4 5.7-7.5 (186-188
  *   per key; the call without the flag cannot take it) - it wins on all three by the project's rule.  NOT measured: 2 keys x 2048;
  *   expect no gain for few keys with thousands of proofs each, where the chunks of the grouped unit are what the per-plan
- *   sub-batches already were, and stay with the per-key h2v_verify_batch_rlc calls there.  The flag is opt-in.  DESIGN.md 15.2. */
+ *   sub-batches already were, and stay with the per-key h2v_verify_batch_rlc calls there.  The flag is opt-in.  DESIGN.md 15.2.
+ *   H2V_MIXED_ACROSS_SRS (only together with H2V_MIXED_RLC; otherwise H2V_E_ARG): the listed plans may be on SEVERAL SRS, and the
+ *   call still ends in ONE pairing: the multi-pairing of h2v_check_pairs_multi - one Miller loop per SRS and one for the right-hand
+ *   sum under one final exponentiation,  prod_k e(sum_{i in k} r_i L_i, s_g2_k) == e(sum_i r_i R_i, G2).  Every proof of the call
+ *   has a coefficient of its own, so the soundness argument of that call applies as it stands.  Without the flag every call
+ *   behaves exactly as before, the H2V_E_ARG that names two plans on different SRS included.
+ *   SRS CLASSES: the plans are classed by their s_g2; classes are numbered in the order in which a listed plan first carries
+ *   them.  A class without a proof takes no bucket problem and no Miller loop and does not count against the limit.
+ *   ARGUMENT RULES, decided on the host before anything is enqueued, in this order: the flag without H2V_MIXED_RLC is H2V_E_ARG;
+ *   the plan-count limits and n > 2^22 as without the flag; more than H2V_MULTI_SRS_MAX classes WITH proofs is H2V_E_LIMIT; then
+ *   N_R > 2^22 and the workspace and device rules as without the flag.  n = 0 is H2V_OK.
+ *   RESULTS: accept[] / status[] keep the contract above.  With ONE class among the proofs a call with the flag returns what the
+ *   same call without it returns.
+ *   WITH H2V_MIXED_FOLD_MSM (with or without H2V_MIXED_GROUPED): phase 1 and the term pool are exactly those of the call without
+ *   the flag - the SRS never enters phase 1 - and the coefficients follow the position in the CALL.  The tail sums R over the N_R
+ *   terms and, per class k with proofs, L_k over class k's proofs, all in the same six bucket-MSM launches, and ONE multi-pairing
+ *   follows; no group stage.  With one class R and L are the sums of the call without the flag.  FALL-BACK as above: after a
+ *   failed check the host runs the form below on the same inputs with the same seed (fell_back = 1, the last record is the second
+ *   pass's, ONE synchronisation per call).
+ *   WITHOUT H2V_MIXED_FOLD_MSM: the sub-batches run as under H2V_MIXED_RLC, and ONE tail follows, in one piece whatever the
+ *   workspace - on the caller's stream behind a join of the lanes, never chunked, routed or coalesced.  The coefficient of proof
+ *   i is drawn by its CLASS-MAJOR position P(i) = the proofs in lower classes + the rank of i within its class in the caller's
+ *   order (one class: P(i) = i):  r_i = low 128 bits of B(seed' || LE32(P(i))), 1 if 0, no chunk tweak.  Behind the multi-pairing's
+ *   skip flags the per-pair kernels of h2v_check_pairs run per class, through a plan of THAT class, so H2V_ST_PAIRING lands where
+ *   the per-key call puts it; nothing comes back to the host in between.  fell_back = 1: the check failed.
+ *   RECORDS: the tail takes the call's LAST record, of kind RLC; h2v_workspace_rlc_result(ws, 0, ..) gives the verdict and
+ *   msm_terms = N_R (with H2V_MIXED_FOLD_MSM) or n.  SEED: the rules above; H2V_RLC_SEED_KEYED binds each proof's own key, whose
+ *   tag covers the key's s_g2 tables, and both forms derive the same seed.
+ *   h2v_aggregate_mixed(_device) does not take the flag: one pair cannot span SRS.  Numbers: not measured.  DESIGN.md 15.3. */
 #define H2V_MIXED_RLC 1u          /* batch-accept: ONE pairing for the call; otherwise one pairing per proof, in ONE launch */
 #define H2V_MIXED_FOLD_MSM 2u     /* with H2V_MIXED_RLC: ONE bucket MSM over the call's per-proof terms as well; one host synchronisation */
 #define H2V_MIXED_GROUPED 4u      /* with both: phase 1 of every groupable plan in ONE launch per kernel; up to 1024 plans */
+#define H2V_MIXED_ACROSS_SRS 16u   /* with H2V_MIXED_RLC: the listed plans may be on several SRS; ONE multi-pairing for the call */
 #define H2V_MIXED_MAX_PLANS 64u   /* more plans in one call without H2V_MIXED_GROUPED: H2V_E_LIMIT */
 #define H2V_MIXED_GROUPED_MAX_PLANS 1024u /* more plans in one H2V_MIXED_GROUPED call: H2V_E_LIMIT */
 #define H2V_MIXED_GROUPED_MAX_OTHER 62u   /* ... of which plans that are not groupable and have proofs */
@@ -758,6 +787,9 @@ int h2v_probe_g1_msm_pippenger_ex(int device, uint32_t n_problems, const h2v_pip
 /* test-only: the two sums of the most recent H2V_MIXED_FOLD_MSM call on ws, L = sum r_i L_i then R = sum r_i R_i: affine, 96 B
  * big-endian x || y each, all-zero = infinity.  Synchronises the device.  H2V_E_ARG when no such call has run on ws. */
 int h2v_probe_mixed_fold_sums(h2v_workspace *ws, uint8_t out_xy_be[192]);
+/* test-only: the sums of the most recent H2V_MIXED_ACROSS_SRS | H2V_MIXED_FOLD_MSM call on ws: R, then L_k of every SRS class with
+ * proofs in class order, affine, 96 B each as above; *n_classes = the classes written.  cap: the classes out_xy_be has room for. */
+int h2v_probe_mixed_fold_sums_multi(h2v_workspace *ws, uint32_t cap, uint8_t *out_xy_be /* (1 + cap) * 96 */, uint32_t *n_classes);
 /* 2P + (neg ? -Q : Q) by the one-lane mixed addition and by the quad-cooperative one (the forced MSM shape H2V_MSM_LPT=8):
  * pq = x_P, y_P, x_Q, y_Q as 12 canonical LE dwords each; out = 5 x 42 dwords of lazily reduced limbs (X, Y, Z; 14 limbs of
  * 28 bits each, Montgomery form R = 2^392): the one-lane result, then lanes 0..3 of a quad.  Guards a compiler issue

@@ -286,9 +286,11 @@ inline std::vector<uint8_t> verify_batch_rlc(const VerifyingKey &vk, const h2v_b
 // with few proofs each; the same vectors.  ws: one made for the same keys or a superset (Workspace(vks, max_batch)), or nullptr
 // for a temporary one.  keyed_seed (only with rlc, not beside `seed`; H2V_RLC_SEED_KEYED): nothing is drawn - the seed is a digest
 // of the call in which every leaf binds the key of its own proof (h2v.h has the rule), the same whatever fold_msm / grouped say.
+// across_srs (only with rlc; H2V_MIXED_ACROSS_SRS): the listed keys may be on several SRS - at most H2V_MULTI_SRS_MAX of them with
+// proofs - and the call ends in ONE multi-pairing; the same vectors.
 inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
                                  bool rlc = false, const uint8_t *seed = nullptr, bool *fell_back = nullptr, bool fold_msm = false,
-                                 bool grouped = false, bool keyed_seed = false) {
+                                 bool grouped = false, bool keyed_seed = false, bool across_srs = false) {
     std::vector<const h2v_plan *> plans;
     for (const VerifyingKey *k : vks) plans.push_back(k ? k->handle() : nullptr);
     PairVerdicts r{std::vector<uint8_t>(batch.n), std::vector<uint32_t>(batch.n)};
@@ -297,17 +299,18 @@ inline PairVerdicts verify_mixed(const std::vector<const VerifyingKey *> &vks, c
     if (keyed_seed) opts.flags |= H2V_RLC_SEED_KEYED;
     int fb = 0;
     check(h2v_verify_mixed(plans.data(), (uint32_t)plans.size(), &batch, r.accept.data(), r.status.data(), ws,
-                           (rlc ? H2V_MIXED_RLC : 0u) | (fold_msm ? H2V_MIXED_FOLD_MSM : 0u) | (grouped ? H2V_MIXED_GROUPED : 0u),
+                           (rlc ? H2V_MIXED_RLC : 0u) | (fold_msm ? H2V_MIXED_FOLD_MSM : 0u) | (grouped ? H2V_MIXED_GROUPED : 0u) |
+                               (across_srs ? H2V_MIXED_ACROSS_SRS : 0u),
                            (seed || keyed_seed) ? &opts : nullptr, &fb));
     if (fell_back) *fell_back = fb != 0;
     return r;
 }
 // midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs) (src/circuits/schnorr_circuit.rs:223-231): one call and
 // one final check for a list of (vk, instances, proof) triples on one SRS.  Throws VerifyError (with the first rejected proof's
-// status) unless every proof is accepted.
+// status) unless every proof is accepted.  across_srs: the list may span several SRS (verify_mixed), still one final check.
 inline void batch_verify(const std::vector<const VerifyingKey *> &vks, const h2v_mixed_batch &batch, h2v_workspace *ws = nullptr,
-                         bool fold_msm = false, bool grouped = false, bool keyed_seed = false) {
-    const PairVerdicts r = verify_mixed(vks, batch, ws, true, nullptr, nullptr, fold_msm, grouped, keyed_seed);
+                         bool fold_msm = false, bool grouped = false, bool keyed_seed = false, bool across_srs = false) {
+    const PairVerdicts r = verify_mixed(vks, batch, ws, true, nullptr, nullptr, fold_msm, grouped, keyed_seed, across_srs);
     for (uint64_t i = 0; i < batch.n; i++)
         if (!r.accept[i]) throw VerifyError(r.status[i]);
 }

@@ -322,7 +322,7 @@ def _params_list(params) -> List[ParamsVerifierKZG]:
 def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances: Sequence[Sequence[int]],
                  committed: Optional[Sequence[Optional[bytes]]] = None, mode: str = "per-proof", seed: Optional[bytes] = None,
                  device: int = 0, fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False,
-                 across_srs: bool = False) -> List[bool]:
+                 across_srs: bool = False, one_call: bool = False) -> List[bool]:
     """accept[i] for n proofs, proof i under the key vks[i] (instances[i]: its public-input scalars; committed[i]: its
     committed instance as 48 compressed bytes when its circuit has one, else None).  The proofs are grouped by SRS on the
     host - one h2v_verify_mixed call per distinct s_g2, each over all its keys - and the verdicts come back in the caller's
@@ -334,25 +334,35 @@ def verify_mixed(vks: Sequence[VerifyingKey], proofs: Sequence[bytes], instances
     seed is a digest of its proofs, instances and each proof's own key (seed.mixed_seed), the same whatever fold_msm / grouped say.
     across_srs (mode="rlc" only): ONE pairing for the whole list instead of one per SRS - per distinct s_g2 one aggregate call
     (h2v_aggregate_mixed: its pair and included[]), then one check_pairs_multi over the S pairs; an SRS whose pair fails is
-    verified by today's per-SRS call.  The same verdicts."""
+    verified by today's per-SRS call.  The same verdicts.
+    one_call (with across_srs only): ONE library call per slice of at most backend.MULTI_SRS_MAX SRS instead - h2v_verify_mixed
+    with H2V_MIXED_ACROSS_SRS on one workspace over all the slice's keys: no pair leaves the device, nothing is decoded again and
+    a failing list is localised inside the call.  The same verdicts."""
     if keyed_seed and mode != "rlc":
         raise ValueError("keyed_seed needs mode='rlc'")
     if across_srs and mode != "rlc":
         raise ValueError("across_srs needs mode='rlc'")
+    if one_call and not across_srs:
+        raise ValueError("one_call needs across_srs (and mode='rlc')")
+    if one_call:
+        return _verify_one_call(vks, proofs, instances, committed, seed, device, fold_msm, grouped, keyed_seed)[0]
     if across_srs:
         return _verify_across_srs(vks, proofs, instances, committed, seed, device, fold_msm, grouped, keyed_seed)[0]
     return _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_msm, grouped, keyed_seed)[0]
 
 
-def _mixed_calls(vks, proofs, instances, committed, device):
-    """The proofs grouped by SRS: per distinct s_g2 (positions, verifiers, plan_of, proof bytes, offsets, instances, committed)"""
+def _mixed_calls(vks, proofs, instances, committed, device, srs_per_call: int = 1):
+    """The proofs grouped by SRS: per distinct s_g2 (positions, verifiers, plan_of, proof bytes, offsets, instances, committed).
+    srs_per_call > 1: per slice of that many SRS, in the order the list first carries them, the positions in the caller's order"""
     n = len(proofs)
     if len(vks) != n or len(instances) != n or (committed is not None and len(committed) != n):
         raise ValueError("one key, one instance list (and one committed instance or None) per proof")
     groups = {}                                   # s_g2 -> positions, in the caller's order
     for i, vk in enumerate(vks):
         groups.setdefault(vk.s_g2, []).append(i)
-    for idx in groups.values():
+    per_srs = list(groups.values())
+    for lo in range(0, len(per_srs), srs_per_call):
+        idx = per_srs[lo] if srs_per_call == 1 else sorted(i for g in per_srs[lo:lo + srs_per_call] for i in g)
         verifiers, slot, plan_of = [], {}, []
         for i in idx:
             v = verifier_for(vks[i], device)
@@ -392,6 +402,21 @@ def _verify_mixed(vks, proofs, instances, committed, mode, seed, device, fold_ms
     return out, status
 
 
+def _verify_one_call(vks, proofs, instances, committed, seed, device, fold_msm=False, grouped=False, keyed_seed=False):
+    """(accept, status) of verify_mixed(mode="rlc", across_srs=True, one_call=True)"""
+    if grouped and not fold_msm:
+        raise ValueError("grouped needs mode='rlc' and fold_msm")
+    out: List[bool] = [False] * len(proofs)
+    status: List[int] = [0] * len(proofs)
+    for idx, verifiers, plan_of, pbytes, off, inst, ci in _mixed_calls(vks, proofs, instances, committed, device, backend.MULTI_SRS_MAX):
+        acc, st, _fb = backend.verify_mixed([v.device_plan for v in verifiers], plan_of, pbytes, off, inst, ci,
+                                             ws=_mixed_workspace(verifiers, len(idx)), mode="rlc", seed=seed, fold_msm=fold_msm, grouped=grouped,
+                                             keyed_seed=keyed_seed, across_srs=True)
+        for i, a, s in zip(idx, acc, st):
+            out[i], status[i] = bool(a), s
+    return out, status
+
+
 def _verify_across_srs(vks, proofs, instances, committed, seed, device, fold_msm=False, grouped=False, keyed_seed=False):
     """(accept, status) of verify_mixed(mode="rlc", across_srs=True)"""
     if grouped and not fold_msm:
@@ -420,18 +445,23 @@ def _verify_across_srs(vks, proofs, instances, committed, seed, device, fold_msm
 
 def batch_verify(params: ParamsVerifierKZG, vks: Sequence[VerifyingKey], instances: Sequence[Sequence[int]],
                  proofs: Sequence[bytes], committed: Optional[Sequence[Optional[bytes]]] = None, device: int = 0,
-                 fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False) -> None:
+                 fold_msm: bool = False, grouped: bool = False, keyed_seed: bool = False, one_call: bool = False) -> None:
     """midnight_zk_stdlib::batch_verify(&params, &vks, &instances, &proofs) (src/circuits/schnorr_circuit.rs:223-231): one
     call and one final check for a list of (vk, instances, proof) triples on ONE SRS - the batch-accept mode of verify_mixed.
     Raises VerifyError unless every proof is accepted (Rust: Err(_)); a key on another SRS than `params` is a ValueError.
     fold_msm: one bucket MSM for the list as well; grouped: phase 1 of every key in one launch per kernel; keyed_seed: the seed is
     derived from the list itself (verify_mixed).  `params` may also be a sequence of ParamsVerifierKZG: a list that spans several
-    SRS, still with one final check (verify_mixed(across_srs=True)); a key on none of them is a ValueError."""
+    SRS, still with one final check (verify_mixed(across_srs=True)); a key on none of them is a ValueError.  one_call (with a
+    sequence of params only; otherwise ValueError): that list as ONE library call (verify_mixed(across_srs=True, one_call=True))."""
+    if one_call and isinstance(params, ParamsVerifierKZG):
+        raise ValueError("one_call needs across_srs: `params` as a sequence of ParamsVerifierKZG")
     known = [bytes(q.s_g2) for q in _params_list(params)]
     for i, vk in enumerate(vks):
         if bytes.fromhex(vk.s_g2) not in known:
             raise ValueError("verifier params do not match the SRS of vks[%d] (s_g2 differs)" % i)
-    if not isinstance(params, ParamsVerifierKZG):
+    if one_call:
+        acc, status = _verify_one_call(vks, proofs, instances, committed, None, device, fold_msm, grouped, keyed_seed)
+    elif not isinstance(params, ParamsVerifierKZG):
         acc, status = _verify_across_srs(vks, proofs, instances, committed, None, device, fold_msm, grouped, keyed_seed)
     else:
         acc, status = _verify_mixed(vks, proofs, instances, committed, "rlc", None, device, fold_msm, grouped, keyed_seed)

@@ -91,6 +91,7 @@ SUBMIT_RLC = 1
 MIXED_RLC = 1          # h2v_verify_mixed: ONE pairing for the call
 MIXED_FOLD_MSM = 2     # ... and ONE bucket MSM over the call's per-proof terms (only together with MIXED_RLC)
 MIXED_GROUPED = 4      # ... and phase 1 of every groupable plan in ONE launch per kernel (only together with both)
+MIXED_ACROSS_SRS = 16  # ... with MIXED_RLC: the listed plans may be on several SRS; ONE multi-pairing for the call (bit 8 stays unknown)
 MIXED_MAX_PLANS = 64   # H2V_MIXED_MAX_PLANS
 MULTI_SRS_MAX = 16     # H2V_MULTI_SRS_MAX: ranges (plans listed) in one h2v_check_pairs_multi call
 MIXED_GROUPED_MAX_PLANS = 1024   # H2V_MIXED_GROUPED_MAX_PLANS: plans listed in a MIXED_GROUPED call
@@ -126,7 +127,7 @@ EXPORTS = [
     "h2v_prepare_batch", "h2v_prepare_batch_device", "h2v_check_pairs", "h2v_check_pairs_device",
     "h2v_check_pairs_rlc", "h2v_check_pairs_rlc_device", "h2v_check_pairs_multi", "h2v_check_pairs_multi_device",
     "h2v_plan_transcript", "h2v_probe_blake2b_ex",
-    "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums", "h2v_probe_decompress",
+    "h2v_verify_mixed", "h2v_verify_mixed_device", "h2v_probe_mixed_fold_sums", "h2v_probe_mixed_fold_sums_multi", "h2v_probe_decompress",
     "h2v_aggregate_batch", "h2v_aggregate_batch_device", "h2v_aggregate_mixed", "h2v_aggregate_mixed_device", "h2v_plan_same_srs",
     "h2v_workspace_seed_used", "h2v_workspace_seed_ms", "h2v_probe_batch_seed", "h2v_plan_key_tag",
     "h2v_probe_mixed_seed",
@@ -226,6 +227,7 @@ def lib():
         L.h2v_verify_mixed_device.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(MixedBatch), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_uint32, C.POINTER(RlcOpts)]
         L.h2v_probe_mixed_fold_sums.argtypes = [C.c_void_p, C.c_void_p]
+        L.h2v_probe_mixed_fold_sums_multi.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32)]
         L.h2v_plan_same_srs.argtypes = [C.c_void_p, C.c_void_p]
         L.h2v_workspace_seed_used.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.h2v_workspace_seed_ms.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
@@ -613,26 +615,31 @@ class Workspace:
 
 
 # ---- mixed-key batches (include/h2v.h: h2v_verify_mixed)
-def _mixed_mode(mode: str, fold_msm: bool = False, grouped: bool = False) -> int:
+def _mixed_mode(mode: str, fold_msm: bool = False, grouped: bool = False, across_srs: bool = False) -> int:
     if mode not in ("per-proof", "rlc"):
         raise ValueError("mode is 'per-proof' or 'rlc'")
+    if across_srs and mode != "rlc":
+        raise ValueError("across_srs needs mode='rlc' (H2V_MIXED_ACROSS_SRS is valid only together with H2V_MIXED_RLC)")
     if fold_msm and mode != "rlc":
         raise ValueError("fold_msm needs mode='rlc' (H2V_MIXED_FOLD_MSM is valid only together with H2V_MIXED_RLC)")
     # (grouped without fold_msm goes to the library as it is: the library answers H2V_E_ARG)
-    return (MIXED_RLC if mode == "rlc" else 0) | (MIXED_FOLD_MSM if fold_msm else 0) | (MIXED_GROUPED if grouped else 0)
+    return ((MIXED_RLC if mode == "rlc" else 0) | (MIXED_FOLD_MSM if fold_msm else 0) | (MIXED_GROUPED if grouped else 0) |
+            (MIXED_ACROSS_SRS if across_srs else 0))
 
 
 def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[bytes], committed: Optional[bytes], ws=None,
                  mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False,
-                 keyed_seed: bool = False):
-    """h2v_verify_mixed: n proofs of several plans on ONE SRS in one call; proof i belongs to plans[plan_of[i]], its public
+                 keyed_seed: bool = False, across_srs: bool = False):
+    """h2v_verify_mixed: n proofs of several plans on ONE SRS (across_srs: on several) in one call; proof i belongs to plans[plan_of[i]], its public
     inputs (and committed instance, where its plan has one) follow those of the proofs before it.  Returns (accept bytes,
     status list, fell_back) in the caller's order.  mode="rlc": ONE pairing for the call (fell_back: the batch check failed
     and the per-pair kernels produced accept[]).  fold_msm (mode="rlc" only; MIXED_FOLD_MSM): ONE bucket MSM over the call's
     per-proof terms as well - no ladder MSM unless the check fails, in which case the call runs again without it (fell_back).
     grouped (with fold_msm only; MIXED_GROUPED): phase 1 of every groupable plan in one launch per kernel, up to
     MIXED_GROUPED_MAX_PLANS plans - the same results.  keyed_seed (mode="rlc"; RLC_SEED_KEYED): the seed is a digest of the call
-    (seed.mixed_seed: every leaf binds its own proof's key), the same in every form; ws.seed_used() has it afterwards.  ws: typically Workspace.multi over the same plans; None: a temporary one."""
+    (seed.mixed_seed: every leaf binds its own proof's key), the same in every form; ws.seed_used() has it afterwards.
+    across_srs (mode="rlc" only; MIXED_ACROSS_SRS): the plans may be on up to MULTI_SRS_MAX SRS with proofs, and the call ends in
+    ONE multi-pairing - with fold_msm over one left-hand bucket sum per SRS, without it over the proofs' pairs.  ws: typically Workspace.multi over the same plans; None: a temporary one."""
     n = len(proof_off) - 1
     if n < 0 or len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
@@ -649,7 +656,7 @@ def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[b
     acc = (C.c_uint8 * max(1, n))()
     st = (C.c_uint32 * max(1, n))()
     fb = C.c_int(0)
-    flags = _mixed_mode(mode, fold_msm, grouped)
+    flags = _mixed_mode(mode, fold_msm, grouped, across_srs)
     opts = _rlc_opts(seed, keyed_seed=keyed_seed)
     check(lib().h2v_verify_mixed(arr, len(plans), C.byref(b), acc, st, ws.handle if ws else None, flags,
                                  C.byref(opts) if opts is not None else None, C.byref(fb)))
@@ -658,14 +665,14 @@ def verify_mixed(plans, plan_of, proofs: bytes, proof_off, instances: Optional[b
 
 def verify_mixed_device(plans, plan_of, n: int, d_proofs, d_off, d_inst, d_ci, d_accept, d_status=None, ws=None, stream=None,
                         mode: str = "per-proof", seed: Optional[bytes] = None, fold_msm: bool = False, grouped: bool = False,
-                        keyed_seed: bool = False) -> None:
+                        keyed_seed: bool = False, across_srs: bool = False) -> None:
     """h2v_verify_mixed_device: enqueues on `stream`; plan_of is a host list, every d_* a device pointer.  `stream` has
     waited for the call's lanes when this returns (a join point, deferred joins or not); ws.rlc_result() has the batch
     verdict of an mode="rlc" call once the stream is synchronised.  fold_msm: as verify_mixed; the call then returns only
-    after the batch verdict is known (it synchronises `stream` once)."""
+    after the batch verdict is known (it synchronises `stream` once).  across_srs: as verify_mixed."""
     if len(plan_of) != n:
         raise H2VError("plan_of: one entry per proof")
-    flags = _mixed_mode(mode, fold_msm, grouped)
+    flags = _mixed_mode(mode, fold_msm, grouped, across_srs)
     arr = (C.c_void_p * max(1, len(plans)))(*[p.handle for p in plans])
     po = (C.c_uint32 * max(1, n))(*plan_of)
     b = MixedBatch(n, C.cast(po, C.c_void_p), d_proofs, d_off, d_inst, d_ci)
@@ -757,6 +764,15 @@ def probe_mixed_fold_sums(ws):
     out = C.create_string_buffer(192)
     check(lib().h2v_probe_mixed_fold_sums(ws.handle, out))
     return _unxy(out.raw[:96]), _unxy(out.raw[96:])
+
+
+def probe_mixed_fold_sums_multi(ws, cap: int = 16):
+    """h2v_probe_mixed_fold_sums_multi: (R, [L_k per SRS class with proofs, in class order]) of the most recent across_srs +
+    fold_msm call on ws, as affine (x, y) integer pairs, None = infinity"""
+    out = C.create_string_buffer((1 + cap) * 96)
+    nc = C.c_uint32(0)
+    check(lib().h2v_probe_mixed_fold_sums_multi(ws.handle, cap, out, C.byref(nc)))
+    return _unxy(out.raw[:96]), [_unxy(out.raw[96 * (1 + k):96 * (2 + k)]) for k in range(nc.value)]
 
 
 def probe_device_memory(device: int = 0):

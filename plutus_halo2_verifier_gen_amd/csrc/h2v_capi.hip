@@ -19,6 +19,8 @@
 #include "h2v_mixed_dev.hpp"
 #include "h2v_mixed_fold.hpp"
 #include "h2v_mixed_fold_dev.hpp"
+#include "h2v_mixed_srs.hpp"
+#include "h2v_mixed_srs_dev.hpp"
 #define H2V_GROUP_HD __host__ __device__ inline
 #include "h2v_mixed_group.hpp"
 #include "h2v_mixed_group_dev.hpp"
@@ -1189,11 +1191,13 @@ extern "C" int h2v_workspace_timings(h2v_workspace *w, uint32_t calls_back, h2v_
 //   MIXED_SUB_TERMS   H2V_MIXED_FOLD_MSM, a sub-batch of a plan that has the batch form: phase 1 alone, then k_mixed_terms writes the
 //                proofs' terms into the call's term pool (run_mixed_terms); no MSM, no pair; the record is a prepare call's
 //   MIXED_FOLD_TAIL   H2V_MIXED_FOLD_MSM: ONE bucket MSM over the call's term pool and ONE pairing (run_mixed_fold_tail)
+//   MIXED_ACROSS_TAIL   H2V_MIXED_ACROSS_SRS without the fold form: the batch check over the call's pool with one left-hand sum per
+//                SRS class and ONE multi-pairing, the per-pair kernels class by class behind it (run_across_tail)
 //   MIXED_GROUP  H2V_MIXED_GROUPED: MIXED_SUB_TERMS for a range of the grouped positions - every groupable plan's share of it in ONE
 //                launch per kernel (run_mixed_group); n / first: the range's size and first grouped position
 // seed: the batch coefficients' (RLC kinds).  fail_ctr: where a failed batch check is counted - a lane's chunk or a coalesced
 // group: its parent's word; NULL (a call of its own): its record's word, zeroed by the call.
-enum class UnitKind : uint8_t { VERIFY, PREPARE, CHECK, RLC, PAIR_RLC, FOLD_RLC, ROUTED, MIXED_SUB, MIXED_TAIL, MIXED_TAIL_RLC, MIXED_SUB_TERMS, MIXED_FOLD_TAIL, MIXED_GROUP };
+enum class UnitKind : uint8_t { VERIFY, PREPARE, CHECK, RLC, PAIR_RLC, FOLD_RLC, ROUTED, MIXED_SUB, MIXED_TAIL, MIXED_TAIL_RLC, MIXED_SUB_TERMS, MIXED_FOLD_TAIL, MIXED_GROUP, MIXED_ACROSS_TAIL };
 struct MixedFold;
 // the pool of a mixed call, caller's order: pairs (two-slot affine records), good_i, 2 x cap bytes of 1 (the `valid` of a two-slot
 // view) and the status words (pre-pairing bits; the tail folds H2V_ST_PAIRING in)
@@ -1450,6 +1454,7 @@ static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_mixed_terms(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
 static int run_mixed_group(const Unit &u, h2v_workspace *w, hipStream_t st);
+static int run_across_tail(const Unit &u, h2v_workspace *w, hipStream_t st);
 // ROUTING of RLC calls (round 4).  The batch-accept mode pays for every batch whose check fails: with 1 % rejecting proofs
 // nearly half of the groups of 64 fail, and the call costs 1.3 x the per-proof mode it falls back to.  A workspace therefore
 // keeps a running estimate of the rate of FAILING GROUPS among the groups its RLC calls have seen - cumulative device
@@ -1509,6 +1514,7 @@ static int run_unit(const Unit &u, h2v_workspace *w, hipStream_t st) {
     case UnitKind::MIXED_SUB_TERMS: return run_mixed_terms(u, w, st);
     case UnitKind::MIXED_FOLD_TAIL: return run_mixed_fold_tail(u, w, st);
     case UnitKind::MIXED_GROUP: return run_mixed_group(u, w, st);
+    case UnitKind::MIXED_ACROSS_TAIL: return run_across_tail(u, w, st);
     case UnitKind::VERIFY: case UnitKind::PREPARE: case UnitKind::FOLD_RLC: case UnitKind::MIXED_SUB: break;
     }
     return run_pipeline(u, w, st);
@@ -3001,6 +3007,7 @@ struct MixedWs {
     uint32_t *fold_rpts = nullptr, *fold_lpts = nullptr;
     size_t fold_cap_terms = 0, fold_cap_parts = 0;
     bool fold_ran = false;                // fold->sums holds the sums of a fold call (h2v_probe_mixed_fold_sums)
+    struct AcrossWs *across = nullptr;    // H2V_MIXED_ACROSS_SRS: the set of the one multi-pairing, created by the first such call
 };
 // one fold call: the pool, its layout, the device table of the foldable plans, the call's seed (ONE per call: chunks of a
 // sub-batch do not derive their own, coefficients follow the position in the call)
@@ -3022,6 +3029,8 @@ struct MixedCall {
     const h2v_plan *const *plans = nullptr;
     h2vmixed::Partition pt;
     bool rlc = false, fold = false, grouped = false;     // H2V_MIXED_RLC, _FOLD_MSM, _GROUPED
+    bool across = false;                                 // H2V_MIXED_ACROSS_SRS: the tail cuts its left-hand sum by SRS class ...
+    h2vsrs::Classes cls;                                 // ... these (mixed_args; h2v_mixed_srs.hpp)
     uint32_t seed[8] = {};                               // of the batch coefficients (rlc)
     // H2V_RLC_SEED_KEYED: the seed is derived from the call (form 3; mixed_seed) and `seed` stays zero.  plan_of: the caller's
     // (host memory in both forms), for the plan index of every leaf.  seed_prev: the second pass after a failed fold check - the
@@ -3049,7 +3058,12 @@ struct MixedFold {
     const MixedGroupPlan *grp = nullptr;  // H2V_MIXED_GROUPED
     std::vector<MixedGroupRange> ranges;  // its ranges, in order
     const uint64_t *d_off = nullptr;      // the grouped proof offsets (n + 1)
+    const h2vsrs::Classes *cls = nullptr; // H2V_MIXED_ACROSS_SRS: the call's SRS classes ...
+    const uint32_t *d_cpos = nullptr;     // ... and their position list on the device: class-major slot -> call position (n)
 };
+static void across_release(MixedWs *m);
+static int across_fold_sums(const Unit &u, h2v_workspace *w, CallRec &rec, hipStream_t st);
+static void across_fold_reset(MixedWs *m);
 static void mixed_release(h2v_workspace *w) {
     MixedWs *m = w->mixed;
     if (!m) return;
@@ -3058,6 +3072,7 @@ static void mixed_release(h2v_workspace *w) {
     for (auto &s : m->slot) s.mem.release();
     slot_release(m->in);
     if (m->fold) rlc_release(m->fold);
+    across_release(m);
     m->mem.release();
     delete m;
     w->mixed = nullptr;
@@ -3223,12 +3238,14 @@ static int run_mixed_fold_tail(const Unit &u, h2v_workspace *w, hipStream_t st) 
         pa.seed_dev = f.seed_dev;
         hipLaunchKernelGGL(k_mixed_pair_terms, dim3((pa.n + 63) / 64), dim3(64), 0, st, pa);
     }
+    if (f.cls) return across_fold_sums(u, w, rec, st);      // (H2V_MIXED_ACROSS_SRS: h2v_mixed_across.hpp)
     HIPCHK(hipEventRecord(rec.ev[4], st));
     if ((rc = launch_sums(r, {(uint32_t)lay.n_r, 2, r->r_scal, nullptr, m->fold_rpts, (uint32_t)lay.n_r, nullptr}, {n, 1, r->l_scal, nullptr, m->fold_lpts, n, nullptr}, rec, st))) return rc;
     if (u.agg_parts) rc = agg_chunk(u, r, w, rec, st);
     else rc = launch_batch_pairing(u, r, GrpShape{}, nullptr, w, rec, st, false);
     if (rc) return rc;
     m->fold_ran = true;
+    across_fold_reset(m);      // (the most recent fold call is on one SRS)
     HIPCHK(hipGetLastError());
     if (u.status) HIPCHK(hipMemcpyAsync(u.status, m->status, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
@@ -3267,6 +3284,7 @@ static int run_mixed_tail(const Unit &u, h2v_workspace *w, hipStream_t st) {
     if (u.status) HIPCHK(hipMemcpyAsync(u.status, mp.status, (size_t)m * 4, hipMemcpyDeviceToDevice, st));
     return H2V_OK;
 }
+#include "h2v_mixed_across.hpp"   // H2V_MIXED_ACROSS_SRS: the set of the one multi-pairing and the two tails that end in it
 // ---- run_mixed in parts: the tables, the units, the two schedules
 // The next of the four table blocks, once the call that took it last has finished on the device (its copy and its kernels are
 // done), grown to `need` bytes.
@@ -3292,6 +3310,7 @@ struct MixedTables {
     const H2vFoldPlan *d_fold = nullptr;      // fold: lay.n_foldable entries
     std::vector<MixedGroupRange> ranges;      // grouped: its ranges, in order
     const uint32_t *d_plan_idx = nullptr, *d_key_tags = nullptr;      // keyed leaves: the plan of every grouped position; 8 dwords per listed plan
+    const uint32_t *d_cpos = nullptr;         // across SRS: class-major slot -> call position (n)
 };
 static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, MixedTables &out) {
     MixedWs *m = w->mixed;
@@ -3307,7 +3326,7 @@ static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, Mi
     }
     const bool leaves = c.keyed && !c.seed_prev;      // (the pass that derives: the second pass of a call copies eight words)
     const mixedtab::TableBlock B = mixedtab::table_block(pt.n, c.fold ? (size_t)c.lay.n_foldable * sizeof(H2vFoldPlan) : 0, n_groups.data(), n_groups.size(),
-                                                         leaves ? pt.n_plans : 0u);
+                                                         leaves ? pt.n_plans : 0u, c.across);
     int si;
     if (int rc = mixed_slot(m, B.extent, &si)) return rc;
     MixedWs::Slot &sl = m->slot[si];
@@ -3315,6 +3334,7 @@ static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, Mi
     std::vector<uint8_t> tags(leaves ? (size_t)pt.n_plans * 32 : 0u);
     for (uint32_t k = 0; leaves && k < pt.n_plans; k++) memcpy(tags.data() + (size_t)k * 32, c.plans[k]->key_tag, 32);
     mixedtab::pack_tables(sl.h, B, pt, c.host_off, gt, info, leaves ? c.plan_of : nullptr, leaves ? tags.data() : nullptr);
+    if (c.across) memcpy(sl.h + B.class_pos.off, c.cls.pos.data(), B.class_pos.bytes);      // (h2v_mixed_srs.hpp: slot -> call position)
     if (c.fold) {            // what k_mixed_vk_sum reads of the foldable plans, in list order (device pointers: written here)
         H2vFoldPlan *fp = (H2vFoldPlan *)(sl.h + B.fold.off);
         for (uint32_t k = 0; k < pt.n_plans; k++)
@@ -3330,6 +3350,7 @@ static int mixed_tables(const MixedCall &c, h2v_workspace *w, hipStream_t st, Mi
                (const uint32_t *)dev(B.inst_len), (const uint32_t *)dev(B.ci_src), (const uint32_t *)dev(B.ci_dst)};
     out.d_fold = (const H2vFoldPlan *)dev(B.fold);
     out.d_plan_idx = (const uint32_t *)dev(B.plan_idx); out.d_key_tags = (const uint32_t *)dev(B.key_tags);
+    out.d_cpos = c.across ? (const uint32_t *)dev(B.class_pos) : nullptr;
     out.ranges.resize(gt.size());
     for (size_t q = 0; q < gt.size(); q++) {
         MixedGroupRange &r = out.ranges[q];
@@ -3357,6 +3378,7 @@ static void mixed_units(const MixedCall &c, MixedTables &t, MixedWs *m, MixedUni
     fc.m = m; fc.lay = c.fold ? &c.lay : nullptr; fc.pt = &pt; fc.plans = c.plans; fc.d_plans = t.d_fold; fc.d_perm = t.tab.perm;
     copy_seed(fc.seed, c.seed);
     fc.grp = c.grouped ? &c.grp : nullptr; fc.ranges = std::move(t.ranges); fc.d_off = t.d_off;
+    fc.cls = c.across ? &c.cls : nullptr; fc.d_cpos = t.d_cpos;
     const uint32_t G = c.grouped ? c.grp.sp.total : 0u;
     if (G) {
         Unit group{UnitKind::MIXED_GROUP, nullptr, G};
@@ -3379,9 +3401,10 @@ static void mixed_units(const MixedCall &c, MixedTables &t, MixedWs *m, MixedUni
         mu.phase1.push_back(u);
     }
     if (G) mu.phase1.front().p = p0;
-    mu.tail = Unit{c.fold ? UnitKind::MIXED_FOLD_TAIL : c.rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, pt.n};
+    mu.tail = Unit{c.fold ? UnitKind::MIXED_FOLD_TAIL : c.across ? UnitKind::MIXED_ACROSS_TAIL : c.rlc ? UnitKind::MIXED_TAIL_RLC : UnitKind::MIXED_TAIL, p0, pt.n};
     mu.tail.pool = pool; mu.tail.accept = c.accept; mu.tail.status = c.status;
     if (c.fold) { mu.tail.fold = &fc; mu.tail.agg_parts = c.agg_parts; }
+    if (c.across) mu.tail.fold = &fc;      // (the classes and their position list)
     copy_seed(mu.tail.seed, c.seed);
 }
 // an ordinary workspace: the sub-batches one after the other on `st`, then the tail (one stream: everything is joined by
@@ -3422,8 +3445,9 @@ static int mixed_run_laned(const MixedCall &c, MixedUnits &mu, h2v_workspace *w,
         rec_laned(w, h2v_workspace::PREPARE, L, u.n, w->chunk);
         if ((rc = run_chunks(w, u, L, w->chunk, {sub_hint, stream_mode}, [&](uint32_t l, hipStream_t) { used_lane[l] = true; return (int)H2V_OK; }))) return rc;
     }
-    if (c.fold) {
-        // ---- the fold form's tail: ONE piece on the call's stream, behind every lane; its record (one "chunk") is a lane's
+    if (c.fold || c.across) {
+        // ---- the fold form's tail, and the tail of a call across several SRS: ONE piece on the call's stream, behind every lane;
+        // its record (one "chunk") is a lane's
         if ((rc = lanes_join(w, st))) return rc;
         CallRec &rec = rec_laned(w, h2v_workspace::RLC, w->n_lanes, n, n);
         rec.agg = tail.agg_parts != nullptr;
@@ -3498,6 +3522,7 @@ static int run_mixed(const MixedCall &c, h2v_workspace *w, hipStream_t st) {
     if ((rc = mixed_ensure(w, c.pt))) return rc;
     if (c.rlc && (rc = rlc_stats_ensure(w))) return rc;
     if (c.fold && (rc = mixed_fold_ensure(w, c.lay))) return rc;
+    if (c.across && (rc = across_ensure(w, c.cls, !c.fold))) return rc;
     MixedTables t;
     if ((rc = mixed_tables(c, w, st, t))) return rc;
     // from here on the block is in use: THE return records its end on `st` (after an error: drained first)
@@ -3512,15 +3537,17 @@ static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
     h2vmixed::Partition *pt = &c->pt;
     c->plans = plans; c->plan_of = b ? b->plan_of : nullptr;
     c->rlc = (flags & H2V_MIXED_RLC) != 0; c->fold = (flags & H2V_MIXED_FOLD_MSM) != 0; c->grouped = (flags & H2V_MIXED_GROUPED) != 0;
+    c->across = (flags & H2V_MIXED_ACROSS_SRS) != 0;
     if (!plans || !b || !accept) return fail(H2V_E_ARG, "null argument");
     const uint32_t max_plans = (flags & H2V_MIXED_GROUPED) ? H2V_MIXED_GROUPED_MAX_PLANS : H2V_MIXED_MAX_PLANS;
     if (n_plans > max_plans)
         return fail(H2V_E_LIMIT, "at most " + std::to_string(max_plans) + " plans in one mixed call" + ((flags & H2V_MIXED_GROUPED) ? " with H2V_MIXED_GROUPED (" : " (") +
                                      std::to_string(n_plans) + " listed)");
-    if (flags & ~(H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | H2V_MIXED_GROUPED)) return fail(H2V_E_ARG, "unknown flag");
+    if (flags & ~(H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM | H2V_MIXED_GROUPED | H2V_MIXED_ACROSS_SRS)) return fail(H2V_E_ARG, "unknown flag");
     if ((flags & H2V_MIXED_FOLD_MSM) && !(flags & H2V_MIXED_RLC)) return fail(H2V_E_ARG, "H2V_MIXED_FOLD_MSM is valid only together with H2V_MIXED_RLC");
     if ((flags & H2V_MIXED_GROUPED) && (flags & (H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM)) != (H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM))
         return fail(H2V_E_ARG, "H2V_MIXED_GROUPED is valid only together with H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM");
+    if ((flags & H2V_MIXED_ACROSS_SRS) && !(flags & H2V_MIXED_RLC)) return fail(H2V_E_ARG, "H2V_MIXED_ACROSS_SRS is valid only together with H2V_MIXED_RLC");
     if (b->n == 0) return H2V_OK;
     if (n_plans == 0) return fail(H2V_E_ARG, "no plan listed");
     if ((flags & H2V_MIXED_RLC) && b->n > (1ull << 22)) return fail(H2V_E_LIMIT, "RLC batches are limited to 2^22 proofs");
@@ -3530,12 +3557,19 @@ static int mixed_args(const h2v_plan *const *plans, uint32_t n_plans, const h2v_
         if (!plans[k]) return fail(H2V_E_ARG, "null plan (plans[" + std::to_string(k) + "])");
         ALIVE(plans[k]);
         if (plans[k]->device != plans[0]->device) return fail(H2V_E_ARG, "plans[" + std::to_string(k) + "] lives on another device than plans[0]: one device per call");
-        if (memcmp(plans[k]->sg2_digest, plans[0]->sg2_digest, sizeof plans[0]->sg2_digest))
+        if (!c->across && memcmp(plans[k]->sg2_digest, plans[0]->sg2_digest, sizeof plans[0]->sg2_digest))
             return fail(H2V_E_ARG, "plans[0] and plans[" + std::to_string(k) + "] are on different SRS (their s_g2 differ): one SRS per mixed call");
         shapes[k] = {plans[k]->d.proof_len, plans[k]->d.n_pi, plans[k]->d.n_ci};
     }
     std::string err;
     if (!h2vmixed::partition(shapes.data(), n_plans, b->plan_of, b->n, *pt, &err)) return fail(H2V_E_ARG, err);
+    if (c->across) {         // the SRS classes of the call (h2v_mixed_srs.hpp): at most H2V_MULTI_SRS_MAX of them may have proofs
+        static_assert(sizeof(h2vsrs::Digest) == sizeof plans[0]->sg2_digest, "a class is one s_g2 digest");
+        std::vector<h2vsrs::Digest> dg(n_plans);
+        for (uint32_t k = 0; k < n_plans; k++) memcpy(&dg[k], plans[k]->sg2_digest, sizeof(h2vsrs::Digest));
+        bool limit = false;
+        if (!h2vsrs::classes(dg.data(), *pt, b->plan_of, H2V_MULTI_SRS_MAX, c->cls, &limit, &err)) return fail(limit ? H2V_E_LIMIT : H2V_E_ARG, err);
+    }
     if (pt->inst_total && !b->instances) return fail(H2V_E_ARG, "a plan of the call has public inputs but instances == NULL");
     if (pt->ci_total && !b->committed) return fail(H2V_E_ARG, "a plan of the call has a committed instance but committed == NULL");
     return H2V_OK;

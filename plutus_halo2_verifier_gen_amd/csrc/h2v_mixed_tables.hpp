@@ -6,6 +6,7 @@
 //   offsets (n + 1 x 8) | inst_src | inst_dst (n x 8) | perm | len_cap | inst_len | ci_src | ci_dst (n x 4) | fold plans |
 //   per grouped range:  group records | comb[0] | comb[1] | dec | terms  (n_groups + 1 x 4 each)
 //   a call with keyed leaves (H2V_RLC_SEED_KEYED), behind everything else:  plan_idx (n x 4, by grouped position) | key_tags (n_plans x 32)
+//   a call across several SRS (H2V_MIXED_ACROSS_SRS), behind those:  class_pos (n x 4: class-major slot -> call position)
 // every region at a multiple of 16, an absent one (no fold layout, no grouped range) empty.  The fold-plan entries hold device
 // pointers: the caller writes them into the region named here, and gives its size in bytes - the device struct is not known here.
 #pragma once
@@ -27,11 +28,13 @@ struct TableBlock {
     Region offsets, inst_src, inst_dst, perm, len_cap, inst_len, ci_src, ci_dst, fold;
     std::vector<RangeRegions> range;
     Region plan_idx, key_tags;              // keyed leaves only (else empty): behind every other region
+    Region class_pos;                       // a call across several SRS only (else empty): the last region
     size_t extent;                          // bytes of the block
 };
 // n proofs, fold_bytes of fold-plan table (0: none), n_ranges grouped ranges of n_groups[c] groups each; keyed_plans: the plans
-// listed in a call with keyed leaves (0: no such call - the two regions are empty and the block is what it was without them)
-static inline TableBlock table_block(uint64_t n, size_t fold_bytes, const uint32_t *n_groups, size_t n_ranges, size_t keyed_plans = 0) {
+// listed in a call with keyed leaves (0: no such call - the two regions are empty and the block is what it was without them);
+// across_srs: the call carries its class-major position list (h2v_mixed_srs.hpp: Classes::pos; the caller copies it in)
+static inline TableBlock table_block(uint64_t n, size_t fold_bytes, const uint32_t *n_groups, size_t n_ranges, size_t keyed_plans = 0, bool across_srs = false) {
     TableBlock b{};
     size_t at = 0;
     auto put = [&at](Region &g, size_t bytes) { g = {at, bytes}; at += up16(bytes); };
@@ -48,6 +51,7 @@ static inline TableBlock table_block(uint64_t n, size_t fold_bytes, const uint32
         put(r.comb[0], (ng + 1) * 4); put(r.comb[1], (ng + 1) * 4); put(r.dec, (ng + 1) * 4); put(r.terms, (ng + 1) * 4);
     }
     put(b.plan_idx, keyed_plans ? (size_t)n * 4 : 0); put(b.key_tags, keyed_plans * 32);
+    put(b.class_pos, across_srs ? (size_t)n * 4 : 0);
     b.extent = at;
     return b;
 }

@@ -14,6 +14,18 @@
 // ranges.  The call is one piece whatever the workspace: its buffers are a set of their own (MultiWs; a laned workspace owns no
 // kernel buffers and a lane's are a chunk's), and on a laned workspace it runs on the caller's stream behind a join of the lanes,
 // its record one "chunk" on a lane, as the fold tail of a mixed call.  Ranges without pairs take no problem and no Miller loop.
+// What "C + 1 bucket problems, then k_pairing_rlc_multi" needs of the set it runs on - h2v_check_pairs_multi's (MultiWs) or the one
+// of the mixed calls across several SRS (AcrossWs): the (1 + MULTI_MAX) sums, the argument ring (device arrays, pinned copies, the
+// events behind the calls that took a slot) and the bucket-MSM sets of the classes behind the first (Lx[0] stays empty).
+struct MultiCore {
+    uint32_t *sums;
+    PipArgs *args_d;
+    PipWs *Lx;
+    void **h_args;
+    hipEvent_t *ev;
+    bool *used;
+    uint64_t *next;
+};
 struct MultiWs {
     Owner mem;                  // of the set's own blocks and events; r and the ranges' bucket-MSM sets own theirs
     uint64_t cap = 0;
@@ -29,11 +41,71 @@ struct MultiWs {
     hipEvent_t ev[wslayout::MULTI_ARG_SLOTS] = {};
     bool used[wslayout::MULTI_ARG_SLOTS] = {};
     uint64_t next = 0;
+    MultiCore core() { return {sums, args_d, Lx, h_args, ev, used, &next}; }
 };
 static_assert(wslayout::MULTI_MAX == H2V_MULTI_SRS_MAX && wslayout::MULTI_MAX == COOP_MULTI_MAX, "one limit: header, size table, kernel");
-static int multi_quiesce(MultiWs *m) {
+static int multi_quiesce(const MultiCore &m) {
     for (uint32_t q = 0; q < wslayout::MULTI_ARG_SLOTS; q++)
-        if (m->used[q] && hipEventSynchronize(m->ev[q]) != hipSuccess) return fail(H2V_E_DEVICE, "waiting for an earlier multi-SRS check failed");
+        if (m.used[q] && hipEventSynchronize(m.ev[q]) != hipSuccess) return fail(H2V_E_DEVICE, "waiting for an earlier multi-SRS check failed");
+    return H2V_OK;
+}
+static int multi_quiesce(MultiWs *m) { return multi_quiesce(m->core()); }
+// THE SUMS AND THE CHECK of a call across several SRS, all on `st`: np = C + 1 bucket problems side by side in the six `_many`
+// launches - prob[0] is R, prob[1 + k] the left-hand sum of class k, whose line table is cls_plan[k]'s - into m.sums, and ONE
+// k_pairing_rlc_multi over them, whose epilogue writes the skip flags (r->flags), counts a failed check in fail_ctr and, passed,
+// copies good[0 .. n) to accept[].  Problem 0 runs on r->R, problem 1 on r->L, the further ones on m.Lx (sized by the caller).  The
+// call takes the next slot of the argument ring: *slot_out, whose event the CALLER records behind everything it enqueues.  Events
+// of the record: [5] .. [8] the bucket MSMs, [8]/[9] around the pairing; the record keeps R's shape.
+static int multi_sums_check(const MultiCore &m, RlcWs *r, const SumTerms *prob, uint32_t np, const h2v_plan *const *cls_plan, uint32_t n, const uint8_t *good,
+                            uint8_t *accept, uint32_t *fail_ctr, CallRec &rec, hipStream_t st, uint32_t *slot_out) {
+    hipEvent_t *ev = rec.ev;
+    const uint32_t C = np - 1;
+    if (C < 1 || C > wslayout::MULTI_MAX) return fail(H2V_E_DEVICE, "internal: a multi-SRS check of no class or of too many");
+    PipArgs pa[wslayout::MULTI_MAX + 1] = {};
+    uint32_t max_n = 0, max_W = 0, max_NB = 0, max_acc_blocks = 0;
+    for (uint32_t q = 0; q < np; q++) {
+        PipArgs &a = pa[q];
+        a.n = prob[q].n; a.halves = prob[q].halves;
+        a.scal = prob[q].scal; a.pidx = prob[q].pidx;
+        a.pool0 = prob[q].pool0; a.n_pool0 = prob[q].n_pool0; a.pool1 = prob[q].pool1; a.out = m.sums + 36 * q;
+        const PipWs &pw = q == 0 ? r->R : q == 1 ? r->L : m.Lx[q - 1];
+        if (a.n > pw.cap_n || a.halves > pw.cap_halves) return fail(H2V_E_DEVICE, "internal: bucket MSM workspace too small");
+        pip_bind(pw, a);
+        const uint64_t lanes = 2ull * a.n * a.halves * a.W / a.chain + (uint64_t)a.W * a.NB + 256ull * PIP_N_CLASSES;     // (as pip_launch)
+        const uint32_t blocks = (uint32_t)((lanes + 255) / 256);
+        max_n = a.n > max_n ? a.n : max_n; max_W = a.W > max_W ? a.W : max_W; max_NB = a.NB > max_NB ? a.NB : max_NB;
+        max_acc_blocks = blocks > max_acc_blocks ? blocks : max_acc_blocks;
+    }
+    const uint32_t slot = (uint32_t)((*m.next)++ % wslayout::MULTI_ARG_SLOTS);
+    if (m.used[slot]) HIPCHK(hipEventSynchronize(m.ev[slot]));
+    m.used[slot] = true;
+    *slot_out = slot;
+    PipArgs *args_d = m.args_d + (size_t)slot * (wslayout::MULTI_MAX + 1);
+    memcpy(m.h_args[slot], pa, np * sizeof(PipArgs));
+    HIPCHK(hipMemcpyAsync(args_d, m.h_args[slot], np * sizeof(PipArgs), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(ev[5], st));
+    for (uint32_t q = 0; q < np; q++) HIPCHK(hipMemsetAsync(pa[q].cnt, 0, (size_t)pa[q].W * pa[q].NB * 4, st));
+    const uint32_t *no_skip = nullptr;
+    hipLaunchKernelGGL(k_pip_digits_many, dim3((max_n + 255) / 256, np), dim3(256), 0, st, (const PipArgs *)args_d, no_skip);
+    hipLaunchKernelGGL(k_pip_scan_many, dim3(1, np), dim3(1024), 0, st, (const PipArgs *)args_d, no_skip);
+    hipLaunchKernelGGL(k_pip_scatter_many, dim3((max_n + 255) / 256, np), dim3(256), 0, st, (const PipArgs *)args_d, no_skip);
+    HIPCHK(hipEventRecord(ev[6], st));
+    hipLaunchKernelGGL(k_pip_accumulate_many, dim3(max_acc_blocks, np), dim3(256), 0, st, (const PipArgs *)args_d, no_skip);
+    HIPCHK(hipEventRecord(ev[7], st));
+    const size_t lds = (size_t)43 * max_NB * 4;
+    HIPCHK(hipFuncSetAttribute((const void *)k_pip_reduce_many, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_pip_reduce_many, dim3(max_W, np), dim3(max_NB), lds, st, (const PipArgs *)args_d, no_skip);
+    hipLaunchKernelGGL(k_pip_combine_many, dim3(1, np), dim3(64), 0, st, (const PipArgs *)args_d, no_skip);
+    HIPCHK(hipEventRecord(ev[8], st));
+    HIPCHK(hipGetLastError());
+    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = pa[0].n;
+    // ---- the check
+    CoopMultiLines tabs = {};
+    tabs.n = C;
+    for (uint32_t j = 0; j < C; j++) tabs.sg2[j] = cls_plan[j]->d.lines28_sg2;
+    hipLaunchKernelGGL(k_pairing_rlc_multi, dim3(1), dim3(64), COOP_LDS_BYTES(1), st, tabs, cls_plan[0]->d.lines28_g2, (const uint32_t *)m.sums, n, good, accept,
+                       r->flags, (n + 63) / 64, fail_ctr);
+    HIPCHK(hipEventRecord(ev[9], st));
     return H2V_OK;
 }
 static void multi_release(h2v_workspace *w) {
@@ -115,52 +187,17 @@ static int run_pairs_multi(const std::vector<MultiRange> &rg, const Unit &u, h2v
     copy_seed(ra.seed, u.seed);
     hipLaunchKernelGGL(k_rlc_pairs_prepare, dim3((n + 63) / 64), dim3(64), 0, st, ra);
     HIPCHK(hipEventRecord(ev[4], st));
-    // ---- the sums: problem 0 is R over all pairs, problem 1 + j is L of range j
-    PipArgs pa[wslayout::MULTI_MAX + 1] = {};
-    uint32_t max_n = 0, max_W = 0, max_NB = 0, max_acc_blocks = 0;
-    for (uint32_t q = 0; q < np; q++) {
-        PipArgs &a = pa[q];
-        const uint32_t lo = q ? rg[q - 1].lo : 0;
-        a.n = q ? rg[q - 1].n : n; a.halves = 1;
-        a.scal = r->r_scal + (size_t)lo * 8; a.pidx = (q ? r->l_idx : r->r_idx) + lo;
-        a.pool0 = m->pts; a.n_pool0 = 2 * n; a.pool1 = nullptr; a.out = m->sums + 36 * q;
-        const PipWs &pw = q == 0 ? r->R : q == 1 ? r->L : m->Lx[q - 1];
-        if (a.n > pw.cap_n) return fail(H2V_E_DEVICE, "internal: bucket MSM workspace too small");
-        pip_bind(pw, a);
-        const uint64_t lanes = 2ull * a.n * a.halves * a.W / a.chain + (uint64_t)a.W * a.NB + 256ull * PIP_N_CLASSES;     // (as pip_launch)
-        const uint32_t blocks = (uint32_t)((lanes + 255) / 256);
-        max_n = a.n > max_n ? a.n : max_n; max_W = a.W > max_W ? a.W : max_W; max_NB = a.NB > max_NB ? a.NB : max_NB;
-        max_acc_blocks = blocks > max_acc_blocks ? blocks : max_acc_blocks;
+    // ---- the sums and the check: problem 0 is R over all pairs, problem 1 + j is L of range j - views of the one scalar array
+    // and of l_idx (ranges are contiguous)
+    SumTerms prob[wslayout::MULTI_MAX + 1];
+    const h2v_plan *cls_plan[wslayout::MULTI_MAX];
+    prob[0] = {n, 1, r->r_scal, r->r_idx, m->pts, 2 * n, nullptr};
+    for (uint32_t j = 0; j < C; j++) {
+        prob[1 + j] = {rg[j].n, 1, r->r_scal + (size_t)rg[j].lo * 8, r->l_idx + rg[j].lo, m->pts, 2 * n, nullptr};
+        cls_plan[j] = rg[j].p;
     }
-    const uint32_t slot = (uint32_t)(m->next++ % wslayout::MULTI_ARG_SLOTS);
-    if (m->used[slot]) HIPCHK(hipEventSynchronize(m->ev[slot]));
-    m->used[slot] = true;
-    PipArgs *args_d = m->args_d + (size_t)slot * (wslayout::MULTI_MAX + 1);
-    memcpy(m->h_args[slot], pa, np * sizeof(PipArgs));
-    HIPCHK(hipMemcpyAsync(args_d, m->h_args[slot], np * sizeof(PipArgs), hipMemcpyHostToDevice, st));
-    HIPCHK(hipEventRecord(ev[5], st));
-    for (uint32_t q = 0; q < np; q++) HIPCHK(hipMemsetAsync(pa[q].cnt, 0, (size_t)pa[q].W * pa[q].NB * 4, st));
-    const uint32_t *no_skip = nullptr;
-    hipLaunchKernelGGL(k_pip_digits_many, dim3((max_n + 255) / 256, np), dim3(256), 0, st, (const PipArgs *)args_d, no_skip);
-    hipLaunchKernelGGL(k_pip_scan_many, dim3(1, np), dim3(1024), 0, st, (const PipArgs *)args_d, no_skip);
-    hipLaunchKernelGGL(k_pip_scatter_many, dim3((max_n + 255) / 256, np), dim3(256), 0, st, (const PipArgs *)args_d, no_skip);
-    HIPCHK(hipEventRecord(ev[6], st));
-    hipLaunchKernelGGL(k_pip_accumulate_many, dim3(max_acc_blocks, np), dim3(256), 0, st, (const PipArgs *)args_d, no_skip);
-    HIPCHK(hipEventRecord(ev[7], st));
-    const size_t lds = (size_t)43 * max_NB * 4;
-    HIPCHK(hipFuncSetAttribute((const void *)k_pip_reduce_many, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_pip_reduce_many, dim3(max_W, np), dim3(max_NB), lds, st, (const PipArgs *)args_d, no_skip);
-    hipLaunchKernelGGL(k_pip_combine_many, dim3(1, np), dim3(64), 0, st, (const PipArgs *)args_d, no_skip);
-    HIPCHK(hipEventRecord(ev[8], st));
-    HIPCHK(hipGetLastError());
-    rec.rlc_c = pa[0].c; rec.rlc_W = pa[0].W; rec.rlc_chain = pa[0].chain; rec.rlc_terms = n;
-    // ---- the check
-    CoopMultiLines tabs = {};
-    tabs.n = C;
-    for (uint32_t j = 0; j < C; j++) tabs.sg2[j] = rg[j].p->d.lines28_sg2;
-    hipLaunchKernelGGL(k_pairing_rlc_multi, dim3(1), dim3(64), COOP_LDS_BYTES(1), st, tabs, rg[0].p->d.lines28_g2, (const uint32_t *)m->sums, n, (const uint8_t *)r->good, u.accept,
-                       r->flags, (n + 63) / 64, fail_ctr);
-    HIPCHK(hipEventRecord(ev[9], st));
+    uint32_t slot = 0;
+    if ((rc = multi_sums_check(m->core(), r, prob, np, cls_plan, n, r->good, u.accept, fail_ctr, rec, st, &slot))) return rc;
     // ---- the fall-back, skipped on the device when the check passed: h2v_check_pairs's two kernels, range by range
     for (uint32_t j = 0; j < C; j++) {
         const uint32_t lo = rg[j].lo, nj = rg[j].n;

@@ -492,6 +492,27 @@ extern "C" int h2v_probe_mixed_fold_sums(h2v_workspace *ws, uint8_t out_xy_be[19
     HIPCHK(hipMemcpy(out_xy_be + 96, dout.p, 96, hipMemcpyDeviceToHost));
     return H2V_OK;
 }
+// The sums of the most recent H2V_MIXED_ACROSS_SRS | H2V_MIXED_FOLD_MSM call on ws: R, then L_k of every class with proofs, in
+// class order - (1 + *n_classes) affine records; cap: the classes the caller's buffer has room for.
+extern "C" int h2v_probe_mixed_fold_sums_multi(h2v_workspace *ws, uint32_t cap, uint8_t *out_xy_be, uint32_t *n_classes) {
+    if (!ws || !out_xy_be || !n_classes) return fail(H2V_E_ARG, "null argument");
+    ALIVE(ws);
+    const MixedWs *m = ws->mixed;
+    if (!m || !m->across || !m->fold_ran || !m->across->fold_classes)
+        return fail(H2V_E_ARG, "the most recent H2V_MIXED_FOLD_MSM call on this workspace (if any) did not carry H2V_MIXED_ACROSS_SRS");
+    const uint32_t C = m->across->fold_classes;
+    if (cap < C) return fail(H2V_E_ARG, "the call had " + std::to_string(C) + " SRS classes with proofs, the buffer has room for " + std::to_string(cap));
+    HIPCHK(hipSetDevice(ws->device));
+    DevBuf dout;
+    if (dout.alloc((size_t)(C + 1) * 96)) return fail(H2V_E_DEVICE, "hipMalloc failed");
+    HIPCHK(hipDeviceSynchronize());
+    hipLaunchKernelGGL(k_export_points, dim3(1), dim3(64), 0, nullptr, C + 1, 1, (const uint32_t *)m->across->sums, dout.as<uint8_t>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out_xy_be, dout.p, (size_t)(C + 1) * 96, hipMemcpyDeviceToHost));
+    *n_classes = C;
+    return H2V_OK;
+}
 // The transcript + combiner launch alone, on a batch: status words, term scalars and (want_trace) the plan's trace registers of
 // every proof.  Nothing behind launch_vm runs, so a plan whose OUT_SCALARs mean nothing to the MSM is safe here.  The outputs
 // are preset (scalars and trace zero, status all ones), so what the kernel left unwritten is visible as such.

@@ -306,4 +306,24 @@ static inline uint32_t multi_range_cap(uint64_t count) {
     while ((uint64_t)c < count) c <<= 1;
     return c;
 }
+
+// ---- the set of the mixed calls ACROSS several SRS (H2V_MIXED_ACROSS_SRS), created by the first such call on a workspace of `cap`
+// proofs and owned by its mixed-call staging: the (1 + MULTI_MAX) sums of the one multi-pairing, the argument ring of its bucket
+// MSMs (MULTI_ARG_SLOTS device arrays; with them as many pinned copies and untimed events), the class-major L-terms of the fold
+// form (scalars and point indices), and what the per-pair fall-back of the pairs form works on: the gathered pool, its status
+// words and verdicts, and R of every pair as a Jacobian point.  With it go one bucket-MSM set per further class, sized by that
+// class's count when a call first needs it (multi_range_cap), and - the pairs form only, at its first call - an RLC set of the
+// pairs shape (rlc_pairs(cap): coefficients, index arrays, good, flags, the bucket-MSM sets of R and of the first class's L).
+enum Across { A_SUMS, A_ARGS, A_CL_SCAL, A_CL_IDX, A_POOL_G, A_STATUS_G, A_ACCEPT_G, A_ER, A_COUNT };
+static inline Table<A_COUNT> across_srs(uint64_t cap) {
+    const size_t n = (size_t)cap;
+    return {{{"sums", (size_t)(MULTI_MAX + 1) * JAC_BYTES, NONE},      // R, then L_0 ..: the layout k_pairing_rlc_multi reads
+             {"args_d", MULTI_ARG_SLOTS * multi_args_bytes(), NONE},
+             {"cl_scal", n * FR_BYTES, NONE},
+             {"cl_idx", n * 4, NONE},
+             {"pool_g", n * PAIR_BYTES, NONE},
+             {"status_g", n * 4, NONE},
+             {"accept_g", n, NONE},
+             {"er", n * JAC_BYTES, NONE}}};
+}
 }   // namespace wslayout

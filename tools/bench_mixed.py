@@ -24,9 +24,17 @@ Shapes sixteen (16 x 64), sixtyfour (64 keys x 16), twofiftysix (256 keys x 4: (
 warmed, the routes alternate (a), (b), (c), `--runs` each.  A gain or a loss of (a) over a route is claimed only when its slowest run
 is ahead of that route's fastest (behind: its fastest and that route's slowest).  Also records, per shape, the own durations of
 the grouped unit's three kernels in the last call (h2v_workspace_timings of the grouped part's record).
+--across-srs S measures H2V_MIXED_ACROSS_SRS (one call and ONE multi-pairing for keys on S SRS), 1024 accepting proofs:
+  (a) across:   ONE h2v_verify_mixed_device call with H2V_MIXED_ACROSS_SRS | H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM over all keys;
+  (b) per SRS:  today's route - one H2V_MIXED_RLC | H2V_MIXED_FOLD_MSM device call per SRS and step, each on its own workspace, on
+                one caller stream.
+S = 4: 4 SRS x 4 keys x 64 proofs; S = 16: 16 SRS x 1 key x 64.  The routes alternate (a), (b), `--runs` (at least five) each; a
+run repeats its step until at least half a second has passed.  Every run goes to --out (default profiles/mixed_across_srs.json); a
+gain is claimed only when the slowest run of (a) beats the fastest run of (b).
 usage: bench_mixed.py [--shapes two,sixteen] [--runs 5] [--steps 20] [--cache DIR] [--out profiles/mixed_keys.json]
        bench_mixed.py --fold [...] [--out profiles/mixed_fold.json]
-       bench_mixed.py --fold --grouped [--shapes sixteen,sixtyfour,twofiftysix,two] [...] [--out profiles/mixed_grouped.json]"""
+       bench_mixed.py --fold --grouped [--shapes sixteen,sixtyfour,twofiftysix,two] [...] [--out profiles/mixed_grouped.json]
+       bench_mixed.py --across-srs 4 [--runs 5] [--cache DIR] [--out profiles/mixed_across_srs.json]"""
 import argparse
 import json
 import os
@@ -252,6 +260,108 @@ def run_grouped(shape, runs, steps, cache):
     return [r]
 
 
+ACROSS_SHAPES = {4: (4, 64), 16: (1, 64)}          # SRS -> (keys per SRS, proofs per key): 1024 proofs either way
+ACROSS_CIRCUITS = ("simple_mul", "lookup_table", "trashcan_mix", "atms_with_lookups")
+
+
+def forged_across(n_srs, cache):
+    """[(SRS index, vk, plan, batch)]: ACROSS_SHAPES[n_srs] keys on each of n_srs SRS"""
+    from plutus_halo2_verifier_gen_amd import plan as PL, synth, vk as V
+    path = os.path.join(cache, "bench_mixed_across_%d.pkl" % n_srs) if cache else None
+    if path and os.path.exists(path):
+        with open(path, "rb") as f:
+            return pickle.load(f)
+    per_srs, cnt = ACROSS_SHAPES[n_srs]
+    out = []
+    for s in range(n_srs):
+        secret = (0x4d5b0000 + s) << 64 | (1000003 + 2 * s)
+        for q in range(per_srs):
+            name = ACROSS_CIRCUITS[(s + q) % 4]
+            vk, td = V.on_srs(*V.BUILDERS[name](0x4d5c0000 + 16 * s + q), secret)
+            pl = PL.compile_plan(vk)
+            out.append((s, vk, pl, synth.forge_batch(vk, td, cnt, seed=300 + per_srs * s + q, plan=pl, workers=16)))
+    if path:
+        os.makedirs(cache, exist_ok=True)
+        with open(path, "wb") as f:
+            pickle.dump(out, f)
+    return out
+
+
+def run_across(n_srs, runs, cache):
+    """routes (a) across, (b) one fold call per SRS, batch-accept mode, all-accepting proofs"""
+    import torch
+    from plutus_halo2_verifier_gen_amd import backend
+    keys = forged_across(n_srs, cache)
+    dev = torch.device("cuda", 0)
+    plans = [backend.DevicePlan(pl.to_bytes(), 0) for _s, _vk, pl, _b in keys]
+    t = lambda b: torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev) if b else None
+    ptr = lambda x: x.data_ptr() if x is not None else None
+    order = [(k, j) for k, (_s, _vk, _pl, b) in enumerate(keys) for j in range(b.n)]
+    random.Random(5).shuffle(order)
+
+    def call_of(sub, listed):
+        """the device-resident mixed batch of the positions `sub` of the order over the listed keys"""
+        proofs, inst, ci, off = [], [], [], [0]
+        for k, j in sub:
+            _s, vk, _pl, b = keys[k]
+            proofs.append(b.proof(j))
+            off.append(off[-1] + len(proofs[-1]))
+            inst.append(b.instances[32 * vk.n_public_inputs * j:32 * vk.n_public_inputs * (j + 1)])
+            if b.committed is not None:
+                ci.append(b.ci(j))
+        n = len(sub)
+        return {"plans": [plans[k] for k in listed], "plan_of": [listed.index(k) for k, _ in sub], "n": n,
+                "in": (t(b"".join(proofs)), torch.tensor(off, dtype=torch.int64, device=dev), t(b"".join(inst)), t(b"".join(ci))),
+                "acc": torch.zeros(n, dtype=torch.uint8, device=dev), "st": torch.zeros(n, dtype=torch.int32, device=dev),
+                "ws": backend.Workspace.multi([plans[k] for k in listed], n)}
+
+    whole = call_of(order, list(range(len(keys))))
+    per_srs = [call_of([o for o in order if keys[o[0]][0] == s], [k for k in range(len(keys)) if keys[k][0] == s]) for s in range(n_srs)]
+    cs = torch.cuda.Stream(device=dev).cuda_stream
+    seed = bytes(range(32))
+
+    def step(c, across):
+        backend.verify_mixed_device(c["plans"], c["plan_of"], c["n"], *[ptr(x) for x in c["in"]], c["acc"].data_ptr(), c["st"].data_ptr(), ws=c["ws"],
+                                    stream=cs, mode="rlc", seed=seed, fold_msm=True, across_srs=across)
+
+    steps_of = {"across": lambda: step(whole, True), "per_srs": lambda: [step(c, False) for c in per_srs]}
+
+    def run(route, min_seconds):
+        torch.cuda.synchronize()
+        t0, k = time.perf_counter(), 0
+        while k < 1 or time.perf_counter() - t0 < min_seconds:
+            steps_of[route]()
+            k += 1
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / k, k
+
+    for route in ("across", "per_srs"):                        # warm-up: first uses allocate; every route must accept everything
+        run(route, 0.0)
+        run(route, 0.0)
+        for c in ([whole] if route == "across" else per_srs):
+            assert c["acc"].cpu().tolist() == [1] * c["n"], "the %s route rejects a forged proof" % route
+            assert c["ws"].rlc_result(timings=False)[0], "the %s route's check failed on forged proofs: the runs would time the fall-back" % route
+    ms = {"across": [], "per_srs": []}
+    steps = {"across": [], "per_srs": []}
+    for _ in range(runs):
+        for route in ("across", "per_srs"):
+            m, k = run(route, 0.5)
+            ms[route].append(m)
+            steps[route].append(k)
+    med = lambda v: sorted(v)[len(v) // 2]
+    r = {"srs": n_srs, "keys": len(keys), "proofs": whole["n"], "mode": "rlc", "msm_terms": whole["ws"].rlc_result(timings=True)[1].msm_terms}
+    for route in ("across", "per_srs"):
+        r[route + "_ms_per_step"] = [round(x, 4) for x in ms[route]]
+        r[route + "_steps_per_run"] = steps[route]
+        r[route + "_median_ms"] = round(med(ms[route]), 4)
+    r["across_gain_by_the_rule"] = max(ms["across"]) < min(ms["per_srs"])
+    r["across_loss_by_the_rule"] = min(ms["across"]) > max(ms["per_srs"])
+    print(json.dumps(r), flush=True)
+    for c in [whole] + per_srs:
+        c["ws"].close()
+    return [r]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="two,sixteen")
@@ -262,18 +372,31 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--fold", action="store_true", help="batch-accept mode only, with route (c): the call with H2V_MIXED_FOLD_MSM")
     ap.add_argument("--grouped", action="store_true", help="with --fold: H2V_MIXED_GROUPED against the fold form and the per-key calls")
+    ap.add_argument("--across-srs", type=int, default=0, choices=(0,) + tuple(sorted(ACROSS_SHAPES)),
+                    help="H2V_MIXED_ACROSS_SRS over this many SRS against one fold call per SRS (1024 proofs)")
     args = ap.parse_args()
+    if args.across_srs and (args.fold or args.grouped):
+        ap.error("--across-srs is a measurement of its own")
     if args.grouped and not args.fold:
         ap.error("--grouped goes with --fold")
     if args.runs < 5 and not args.forge_only:
         ap.error("at least five runs of each route")
     if args.forge_only:
+        if args.across_srs:
+            forged_across(args.across_srs, args.cache)
+            return
         for shape in args.shapes.split(","):
             forged(shape, args.cache)
         return
     import torch
     results = []
-    for shape in args.shapes.split(","):
+    if args.across_srs:
+        args.out = args.out or os.path.join(ROOT, "profiles", "mixed_across_srs.json")
+        if os.path.exists(args.out):          # (one file for both shapes: the other shape's runs are kept)
+            with open(args.out) as f:
+                results += [c for c in json.load(f)["cases"] if c.get("srs") != args.across_srs]
+        results += run_across(args.across_srs, args.runs, args.cache)
+    for shape in ([] if args.across_srs else args.shapes.split(",")):
         results += run_grouped(shape, args.runs, args.steps, args.cache) if args.grouped else run_shape(shape, args.runs, args.steps, args.cache, args.fold)
     if args.out:
         with open(args.out, "w") as f:
